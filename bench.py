@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Headline benchmark: 24 kHz samples/s through encode -> RVQ -> decode.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
 
 One process per GPU (the driver launches N > 1 through torch.distributed.run;
 RANK / LOCAL_RANK / WORLD_SIZE / MASTER_* come from the environment).  A "step"
@@ -11,13 +11,20 @@ is one forward of the "Soundstream default" codec (BASELINE.json configs[1]:
 no data-path collective (weak scaling: 32 clips per GPU).  Rank 0 prints ONE
 JSON line.
 
-Besides the contract fields the line carries
+A plain run sets up, warms up, times K steps and prints the contract fields
+(metric, value, unit, higher_is_better, dtype, ms_per_step, ...).  With
+--dump-outputs DIR, rank 0 also writes what the last timed step returned
+(y, commit, index) as DIR/<name>.npy; inputs, weights and codebooks are seeded,
+so two builds can be compared output for output.
+
+--full adds the secondary measurements and checks, all outside the timed region:
   roofline     -- the dominant kernel (by time) of the forward: achieved vs peak,
                   per-launch durations measured with HIP events on the launch stream;
   cpu_baseline -- the CPU oracle (torch fp32 conv stacks + the exact RVQ) timed on
                   this box's host cores on a bounded sample of the same workload;
   parity       -- GPU vs oracle on that sample (index equality on identical
-                  latents, waveform RMS), so every bench line is also a parity check.
+                  latents, waveform RMS);
+  other_arithmetic / other_codebooks / training_step* -- the other configurations.
 """
 from __future__ import annotations
 
@@ -343,12 +350,32 @@ def cpu_baseline_and_parity(model, x_cpu, y_gpu, idx_gpu, z_gpu, n_items):
     return base, parity, (sd, spec, z)
 
 
+DUMP_BUDGET_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, y, commit, index):
+    """Write what a caller of the timed forward receives from its last step: ``y`` (waveform) and ``commit`` as float32,
+    ``index`` (codebook indices) as float64.  Above DUMP_BUDGET_BYTES only the first clips of the batch are written."""
+    import numpy as np
+    per_clip = 4 * y[0].numel() + 8 * index[0].numel()
+    n = max(1, min(y.shape[0], (DUMP_BUDGET_BYTES - 4 * commit.numel()) // per_clip))
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {"y": y[:n].float(), "commit": commit.float(), "index": index[:n].double()}
+    for name, t in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), t.detach().cpu().numpy())
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--batch-per-gpu", type=int, default=BATCH_PER_GPU)
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps, write the last step's outputs (y, commit, index) as DIR/<name>.npy")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the secondary measurements and checks (roofline, CPU baseline + parity, other "
+                         "arithmetics and codebooks, training step); the --no-* / --cpu-items options select among them")
     ap.add_argument("--cpu-items", type=int, default=8, help="clips in the CPU-baseline sample (0 = skip)")
     ap.add_argument("--no-roofline", action="store_true")
     ap.add_argument("--no-graph", action="store_true", help="issue the launches eagerly instead of replaying a hipGraph")
@@ -362,6 +389,8 @@ def main():
     ap.add_argument("--no-train-step", action="store_true",
                     help="skip the config-5 training-step measurement (a child process, outside the timed region)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     from audio_generation_amd import dist as agx_dist
     from audio_generation_amd import ops
@@ -422,6 +451,8 @@ def main():
     elapsed = agx_dist.max_over_ranks(mine, device=red_dev)
     per_rank_ms = agx_dist.gather_floats(1e3 * mine / args.steps, device=red_dev)   # a straggler shows up here
     y, commit, index = out
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, y, commit, index)
     distinct0 = int(index[..., 0].unique().numel())
 
     ms_per_step = 1e3 * elapsed / args.steps
@@ -445,7 +476,7 @@ def main():
                                   "bf16 pieces, six bf16 MFMAs per product block, fp32 accumulation: same error vs fp64 as fp32)")},
     }
 
-    if rank == 0 and not args.no_roofline:
+    if rank == 0 and args.full and not args.no_roofline:
         # instrumented pass (outside the timed region): per-launch HIP-event durations
         timer = LaunchTimer()
         ops.set_observer(timer)
@@ -508,7 +539,7 @@ def main():
         if args.arith == "mixed":       # the measured configuration mixes the two matrix pipes: its own ceilings
             result["roofline_mixed"] = arithmetic_roofline(per, ms_per_step)
 
-    if rank == 0 and world == 1 and args.cpu_items > 0:
+    if rank == 0 and world == 1 and args.full and args.cpu_items > 0:
         with torch.no_grad():
             z_gpu = model._run_encoders(x)
         n_cpu = min(args.cpu_items, bsz)
@@ -531,7 +562,7 @@ def main():
                                                                                 z_gpu[:n_cpu], (z_cpu, idx_c, y_c)))
         model.quantizer.load_state_dict(keep)
 
-    if rank == 0 and world == 1 and not args.no_extra:
+    if rank == 0 and world == 1 and args.full and not args.no_extra:
         # secondary measurements, outside the timed region and NOT the headline value: the other arithmetics
         def measure(dec, enc):
             """Same protocol as the headline (hipGraph replay unless --no-graph), plus the eager figure."""
@@ -607,7 +638,7 @@ def main():
         result["other_codebooks"] = dict(recipe=other, **r)
         model.quantizer.load_state_dict(keep)
 
-    if rank == 0 and world == 1 and not args.no_train_step:
+    if rank == 0 and world == 1 and args.full and not args.no_train_step:
         # BASELINE configs[4] at its per-GPU batch (32 clips): one whole training step -- generator forward + native backward,
         # six discriminators x three passes, low-pass / pre-emphasis / 7-window mel terms, seven Adam steps -- measured by
         # tools/train_step_bench.py in a CHILD process after everything above (never inside the timed region); its JSON line
