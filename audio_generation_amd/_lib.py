@@ -61,6 +61,7 @@ SIGNATURES = {
     "agx_conv_bwd_weight": (c_int, [_PD, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                     c_void_p, c_size_t, c_void_p]),
     "agx_conv_kernel_name": (c_int, [_PD, c_char_p, c_size_t]),
+    "agx_conv_bwd_weight_kernel_name": (c_int, [_PD, c_char_p, c_size_t]),
     "agx_resblock_workspace_bytes": (c_size_t, [_PD]),
     "agx_resblock_kernel_name": (c_int, [_PD, c_char_p, c_size_t]),
     "agx_resblock_forward": (c_int, [_PD, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
@@ -116,6 +117,7 @@ SIGNATURES = {
                                           c_void_p]),
     "agx_conv_grouped_bwd_weight_workspace_bytes": (c_size_t, [_PD]),
     "agx_conv_grouped_bwd_weight": (c_int, [_PD, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "agx_conv_grouped_bwd_weight_kernel_name": (c_int, [_PD, c_char_p, c_size_t]),
     "agx_conv_pack_bwd_sigma": (c_int, [_PD, c_void_p, c_void_p, c_void_p, c_void_p]),
     "agx_avgpool1d_out_len": (c_int64, [c_int32, c_int32, c_int32, c_int32]),
     "agx_avgpool1d": (c_int, [c_void_p, c_void_p, c_int64, c_int32, c_int32, c_int32, c_int32, c_void_p]),
@@ -131,6 +133,7 @@ SIGNATURES = {
     "agx_conv2d_bwd_weight_workspace_bytes": (c_size_t, [_P2]),
     "agx_conv2d_bwd_weight": (c_int, [_P2, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                       c_void_p, c_void_p, c_size_t, c_void_p]),
+    "agx_conv2d_bwd_weight_kernel_name": (c_int, [_P2, c_char_p, c_size_t]),
     "agx_conv2d_colsplit_weights": (c_int, [_P2, c_void_p, c_void_p, c_void_p, c_void_p]),
     "agx_conv2d_colsum": (c_int, [_P2, c_void_p, c_void_p, c_void_p, c_void_p]),
     "agx_stft_frames": (c_int64, [c_int32, c_int32]),

@@ -597,6 +597,7 @@ struct Bw2dGeom {
     int prepad;          // 1: the kernel reads such planes (one "row" of pp_lpr positions per image)
     int pp_lpr, pp_hwi;  // positions per DYP plane (a multiple of 32) / floats per XP plane
     int pp_amin, pp_bmin;
+    int wk;              // direct kernels: waves of a workgroup that take different contraction slices (1 otherwise)
 };
 
 template <int MW, int NW, int WM, int WN, int PREC = 0>   // PREC 1: bf16x3 contraction (mfma_tile.hpp), both operands split in registers
@@ -1309,6 +1310,7 @@ static int bw2d_geometry(const agx_conv2d_desc *d, Bw2dGeom *g, int *cfg, int *b
     g->prec = d->impl == AGX_IMPL_MFMA_BF16X3 ? 1 : 0;
     g->xcd = tuning().dw_xcd;
     g->prepad = 0; g->pp_lpr = 0; g->pp_hwi = 0; g->pp_amin = 0; g->pp_bmin = 0;
+    g->wk = 1;
     *cfg = g->Cout >= 128 ? 0 : (g->Cout >= 64 ? 1 : 2);
     *bm = *cfg == 0 ? 128 : (*cfg == 1 ? 64 : 32);
     const int nt = ceil_div(g->Cin * KK, 128), mt = ceil_div(g->Cout, *bm);
@@ -1351,6 +1353,7 @@ static int bw2d_geometry(const agx_conv2d_desc *d, Bw2dGeom *g, int *cfg, int *b
         if (gz < 1) gz = 1;
         if (gz > 65535) gz = 65535;
         g->n_slices = int(gz);
+        g->wk = wk;
         *bm = dbm;
         *grid = dim3(dnt, dmt, g->n_slices);
         *lds = 0;
@@ -1385,9 +1388,30 @@ static int bw2d_geometry(const agx_conv2d_desc *d, Bw2dGeom *g, int *cfg, int *b
     return AGX_OK;
 }
 
+// The instantiation agx_conv2d_bwd_weight launches (as bw1_names / bw1_kernel below for the 1-D op)
+static const char *const bw2_names[] = {
+    "conv2d_bwd_weight_shared<2,2,2,2>", "conv2d_bwd_weight_shared<2,2,2,2,1>", "conv2d_bwd_weight_shared<2,1,1,4>",
+    "conv2d_bwd_weight_shared<2,1,1,4,1>", "conv2d_bwd_weight_shared<1,2,1,4>",
+    "conv2d_bwd_weight_direct<2,2,2,2>", "conv2d_bwd_weight_direct<2,2,1,2>", "conv2d_bwd_weight_direct<2,2,1,1>",
+    "conv2d_bwd_weight_direct<1,2,1,4>", "conv2d_bwd_weight_direct<1,3,1,1>", "conv2d_bwd_weight_direct<1,1,1,1>",
+    "conv2d_bwd_weight<2,2,2,2>", "conv2d_bwd_weight<1,2,2,2>", "conv2d_bwd_weight<1,1,1,4>",
+    "conv2d_bwd_weight<2,2,2,2,1>", "conv2d_bwd_weight<1,2,2,2,1>", "conv2d_bwd_weight<1,1,1,4,1>"};
+
+static int bw2_kernel(const Bw2dGeom &g, int cfg) {
+    if (cfg >= 10) {
+        const bool bf = g.prec == 1 && tuning().dw2_bf;   // bf16x3 descriptors: the shared kernel's bf16x3 contraction
+        if (cfg == 10 && tuning().dw2_shared) return bf ? 1 : 0;
+        if (cfg == 15) return bf ? 3 : 2;
+        if (cfg == 16) return 4;
+        return cfg == 10 ? 5 : cfg == 11 ? 6 : cfg == 12 ? 7 : cfg == 13 ? 8 : cfg == 17 ? 9 : 10;
+    }
+    return 11 + (g.prec ? 3 : 0) + cfg;                    // staged kernel, cfg 0..2
+}
+
 struct BwGeom {
     int cfg;  // 0: 128x128 tile, 1: 64x128, 2: 32x128;  direct kernel: 10..14 (see bw_geometry)
     int bm, span, n_chan, n_slices;
+    int wk;   // waves of a workgroup that take different contraction slices (direct kernel; 1 otherwise)
     bool direct;
     dim3 grid;
     size_t lds;
@@ -1417,6 +1441,7 @@ static BwGeom bw_geometry(const ConvPlan &p, bool bf16x3) {
         if (gz < 1) gz = 1;
         if (gz > 65535) gz = 65535;
         g.n_slices = gz;     // partial tiles in the workspace (the WK waves of a workgroup are added in LDS)
+        g.wk = wk;
         g.grid = dim3(nt, mt, gz);
         g.span = g.n_chan = 0;
         g.lds = 0;
@@ -1433,9 +1458,25 @@ static BwGeom bw_geometry(const ConvPlan &p, bool bf16x3) {
     if (ns < 1) ns = 1;
     if (ns > 65535) ns = 65535;
     g.n_slices = ns;
+    g.wk = 1;
     g.grid = dim3(nt, mt, ns);
     g.lds = (size_t(g.bm) * BW_TS + size_t(g.n_chan) * g.span) * sizeof(float);
     return g;
+}
+
+// The instantiation agx_conv_bwd_weight launches: its launcher switches on this index and
+// agx_conv_bwd_weight_kernel_name prints bw1_names[] of it, so the name is the selection.
+static const char *const bw1_names[] = {
+    "conv_bwd_weight_direct<2,2,2,2>", "conv_bwd_weight_direct<2,2,1,2>", "conv_bwd_weight_direct<2,2,1,1>",
+    "conv_bwd_weight_direct<1,2,1,4>", "conv_bwd_weight_direct<1,1,1,1>",
+    "conv_bwd_weight_direct<2,2,2,2,true>", "conv_bwd_weight_direct<2,2,1,2,true>", "conv_bwd_weight_direct<2,2,1,1,true>",
+    "conv_bwd_weight_direct<1,2,1,4,true>", "conv_bwd_weight_direct<1,1,1,1,true>",
+    "conv_bwd_weight<2,2,2,2>", "conv_bwd_weight<1,2,2,2>", "conv_bwd_weight<1,1,1,4>",
+    "conv_bwd_weight<2,2,2,2,1>", "conv_bwd_weight<1,2,2,2,1>", "conv_bwd_weight<1,1,1,4,1>"};
+
+static int bw1_kernel(const BwGeom &g, const ConvPlan &p, bool bf16x3) {
+    if (g.direct) return (p.s > 1 ? 5 : 0) + (g.cfg - 10);     // cfg 10..14; strided: x as a phase-split copy
+    return 10 + (bf16x3 ? 3 : 0) + g.cfg;                      // staged kernel, cfg 0..2
 }
 
 }  // namespace agx
@@ -1509,26 +1550,24 @@ int agx_conv_bwd_weight(const agx_conv_desc *d, const float *x, const float *dy,
         hipLaunchKernelGGL(kern, geo.grid, dim3(256), size_t(4) * blocks_per_wave * 4096, st, pd, sp, xd, dyd, part, bias_part);
         return AGX_OK;
     };
-    if (geo.direct && sp > 1)
-        rc = geo.cfg == 10 ? launch_direct(conv_bwd_weight_direct_kernel<2, 2, 2, 2, true>, 4)
-           : geo.cfg == 11 ? launch_direct(conv_bwd_weight_direct_kernel<2, 2, 1, 2, true>, 4)
-           : geo.cfg == 12 ? launch_direct(conv_bwd_weight_direct_kernel<2, 2, 1, 1, true>, 4)
-           : geo.cfg == 13 ? launch_direct(conv_bwd_weight_direct_kernel<1, 2, 1, 4, true>, 3)
-                           : launch_direct(conv_bwd_weight_direct_kernel<1, 1, 1, 1, true>, 2);
-    else if (geo.direct)
-        rc = geo.cfg == 10 ? launch_direct(conv_bwd_weight_direct_kernel<2, 2, 2, 2>, 4)
-           : geo.cfg == 11 ? launch_direct(conv_bwd_weight_direct_kernel<2, 2, 1, 2>, 4)
-           : geo.cfg == 12 ? launch_direct(conv_bwd_weight_direct_kernel<2, 2, 1, 1>, 4)
-           : geo.cfg == 13 ? launch_direct(conv_bwd_weight_direct_kernel<1, 2, 1, 4>, 3)
-                           : launch_direct(conv_bwd_weight_direct_kernel<1, 1, 1, 1>, 2);
-    else if (d->impl == AGX_IMPL_MFMA_BF16X3)
-        rc = geo.cfg == 0 ? launch(conv_bwd_weight_kernel<2, 2, 2, 2, 1>)
-           : geo.cfg == 1 ? launch(conv_bwd_weight_kernel<1, 2, 2, 2, 1>)
-                          : launch(conv_bwd_weight_kernel<1, 1, 1, 4, 1>);
-    else
-        rc = geo.cfg == 0 ? launch(conv_bwd_weight_kernel<2, 2, 2, 2>)
-           : geo.cfg == 1 ? launch(conv_bwd_weight_kernel<1, 2, 2, 2>)
-                          : launch(conv_bwd_weight_kernel<1, 1, 1, 4>);
+    switch (bw1_kernel(geo, p, d->impl == AGX_IMPL_MFMA_BF16X3)) {
+        case 0: rc = launch_direct(conv_bwd_weight_direct_kernel<2, 2, 2, 2>, 4); break;
+        case 1: rc = launch_direct(conv_bwd_weight_direct_kernel<2, 2, 1, 2>, 4); break;
+        case 2: rc = launch_direct(conv_bwd_weight_direct_kernel<2, 2, 1, 1>, 4); break;
+        case 3: rc = launch_direct(conv_bwd_weight_direct_kernel<1, 2, 1, 4>, 3); break;
+        case 4: rc = launch_direct(conv_bwd_weight_direct_kernel<1, 1, 1, 1>, 2); break;
+        case 5: rc = launch_direct(conv_bwd_weight_direct_kernel<2, 2, 2, 2, true>, 4); break;
+        case 6: rc = launch_direct(conv_bwd_weight_direct_kernel<2, 2, 1, 2, true>, 4); break;
+        case 7: rc = launch_direct(conv_bwd_weight_direct_kernel<2, 2, 1, 1, true>, 4); break;
+        case 8: rc = launch_direct(conv_bwd_weight_direct_kernel<1, 2, 1, 4, true>, 3); break;
+        case 9: rc = launch_direct(conv_bwd_weight_direct_kernel<1, 1, 1, 1, true>, 2); break;
+        case 10: rc = launch(conv_bwd_weight_kernel<2, 2, 2, 2>); break;
+        case 11: rc = launch(conv_bwd_weight_kernel<1, 2, 2, 2>); break;
+        case 12: rc = launch(conv_bwd_weight_kernel<1, 1, 1, 4>); break;
+        case 13: rc = launch(conv_bwd_weight_kernel<2, 2, 2, 2, 1>); break;
+        case 14: rc = launch(conv_bwd_weight_kernel<1, 2, 2, 2, 1>); break;
+        default: rc = launch(conv_bwd_weight_kernel<1, 1, 1, 4, 1>); break;
+    }
     if (rc != AGX_OK) return rc;
     launch_slice_reduce(part, geo.n_slices, nw, dwp, st);
     const bool transposed = d->kind == AGX_CONV_TRANSPOSED;
@@ -1596,6 +1635,13 @@ int agx_conv2d_bwd_weight(const agx_conv2d_desc *d, const float *x, const float 
                            dbias ? bias_part : nullptr);
         return AGX_OK;
     };
+    auto launch_shared = [&](auto kern, int blocks) -> int {   // two slots of (BM + BN) / 32 operand blocks of 4 KB
+        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kern),
+                                           hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+        if (e != hipSuccess) return fail(AGX_ERR_LAUNCH, "hipFuncSetAttribute: %s", hipGetErrorString(e));
+        hipLaunchKernelGGL(kern, grid, dim3(256), size_t(2) * blocks * 4096, st, g, x, dy, part, dbias ? bias_part : nullptr);
+        return AGX_OK;
+    };
     if (cfg >= 10) {
         if (g.prepad) {   // narrow map: zero-padded, phase-split, flattened copies of both operands
             float *xp = rowdot + M + 64;
@@ -1616,33 +1662,25 @@ int agx_conv2d_bwd_weight(const agx_conv2d_desc *d, const float *x, const float 
                                xs, xrows, g.Win, g.Wp, g.sw);
             x = xs;
         }
-        auto launch_shared = [&](auto kern, int blocks) -> int {   // two slots of (BM + BN) / 32 operand blocks of 4 KB
-            hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kern),
-                                               hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-            if (e != hipSuccess) return fail(AGX_ERR_LAUNCH, "hipFuncSetAttribute: %s", hipGetErrorString(e));
-            hipLaunchKernelGGL(kern, grid, dim3(256), size_t(2) * blocks * 4096, st, g, x, dy, part, dbias ? bias_part : nullptr);
-            return AGX_OK;
-        };
-        const bool bf = g.prec == 1 && tuning().dw2_bf;   // bf16x3 descriptors: the shared kernel's bf16x3 contraction
-        rc = (cfg == 10 && tuning().dw2_shared) ? (bf ? launch_shared(conv2d_bwd_weight_shared_kernel<2, 2, 2, 2, 1>, 8)
-                                                      : launch_shared(conv2d_bwd_weight_shared_kernel<2, 2, 2, 2>, 8))
-           : (cfg == 15) ? (bf ? launch_shared(conv2d_bwd_weight_shared_kernel<2, 1, 1, 4, 1>, 6)
-                               : launch_shared(conv2d_bwd_weight_shared_kernel<2, 1, 1, 4>, 6))
-           : (cfg == 16) ? launch_shared(conv2d_bwd_weight_shared_kernel<1, 2, 1, 4>, 9)
-           : cfg == 10 ? launch_direct(conv2d_bwd_weight_direct_kernel<2, 2, 2, 2>, 4)
-           : cfg == 11 ? launch_direct(conv2d_bwd_weight_direct_kernel<2, 2, 1, 2>, 4)
-           : cfg == 12 ? launch_direct(conv2d_bwd_weight_direct_kernel<2, 2, 1, 1>, 4)
-           : cfg == 13 ? launch_direct(conv2d_bwd_weight_direct_kernel<1, 2, 1, 4>, 3)
-           : cfg == 17 ? launch_direct(conv2d_bwd_weight_direct_kernel<1, 3, 1, 1>, 4)
-                       : launch_direct(conv2d_bwd_weight_direct_kernel<1, 1, 1, 1>, 2);
-    } else if (g.prec) {
-        rc = cfg == 0 ? launch(conv2d_bwd_weight_kernel<2, 2, 2, 2, 1>)
-           : cfg == 1 ? launch(conv2d_bwd_weight_kernel<1, 2, 2, 2, 1>)
-                      : launch(conv2d_bwd_weight_kernel<1, 1, 1, 4, 1>);
-    } else {
-        rc = cfg == 0 ? launch(conv2d_bwd_weight_kernel<2, 2, 2, 2>)
-           : cfg == 1 ? launch(conv2d_bwd_weight_kernel<1, 2, 2, 2>)
-                      : launch(conv2d_bwd_weight_kernel<1, 1, 1, 4>);
+    }
+    switch (bw2_kernel(g, cfg)) {
+        case 0: rc = launch_shared(conv2d_bwd_weight_shared_kernel<2, 2, 2, 2>, 8); break;
+        case 1: rc = launch_shared(conv2d_bwd_weight_shared_kernel<2, 2, 2, 2, 1>, 8); break;
+        case 2: rc = launch_shared(conv2d_bwd_weight_shared_kernel<2, 1, 1, 4>, 6); break;
+        case 3: rc = launch_shared(conv2d_bwd_weight_shared_kernel<2, 1, 1, 4, 1>, 6); break;
+        case 4: rc = launch_shared(conv2d_bwd_weight_shared_kernel<1, 2, 1, 4>, 9); break;
+        case 5: rc = launch_direct(conv2d_bwd_weight_direct_kernel<2, 2, 2, 2>, 4); break;
+        case 6: rc = launch_direct(conv2d_bwd_weight_direct_kernel<2, 2, 1, 2>, 4); break;
+        case 7: rc = launch_direct(conv2d_bwd_weight_direct_kernel<2, 2, 1, 1>, 4); break;
+        case 8: rc = launch_direct(conv2d_bwd_weight_direct_kernel<1, 2, 1, 4>, 3); break;
+        case 9: rc = launch_direct(conv2d_bwd_weight_direct_kernel<1, 3, 1, 1>, 4); break;
+        case 10: rc = launch_direct(conv2d_bwd_weight_direct_kernel<1, 1, 1, 1>, 2); break;
+        case 11: rc = launch(conv2d_bwd_weight_kernel<2, 2, 2, 2>); break;
+        case 12: rc = launch(conv2d_bwd_weight_kernel<1, 2, 2, 2>); break;
+        case 13: rc = launch(conv2d_bwd_weight_kernel<1, 1, 1, 4>); break;
+        case 14: rc = launch(conv2d_bwd_weight_kernel<2, 2, 2, 2, 1>); break;
+        case 15: rc = launch(conv2d_bwd_weight_kernel<1, 2, 2, 2, 1>); break;
+        default: rc = launch(conv2d_bwd_weight_kernel<1, 1, 1, 4, 1>); break;
     }
     if (rc != AGX_OK) return rc;
     launch_slice_reduce(part, g.n_slices, nw, dwp, st);
@@ -1651,6 +1689,42 @@ int agx_conv2d_bwd_weight(const agx_conv2d_desc *d, const float *x, const float 
     if (dbias)
         launch_slice_reduce(bias_part, g.n_slices, int64_t(M), dbias, st);
     return check_launch("agx_conv2d_bwd_weight");
+}
+
+// "<instantiation> cfg=<geometry> op=<operand copy> slices=<contraction slices> items=<work items>": what the op above runs,
+// from the same geometry and the same selection.  Items are 32-position chunks (direct / shared kernels) or staged tiles
+// (64 positions, cfg 0..2); slice k of a direct / shared kernel takes items [k per, (k + 1) per), per = ceil(items / slices).
+int agx_conv_bwd_weight_kernel_name(const agx_conv_desc *d, char *buf, size_t buf_len) {
+    using namespace agx;
+    ConvPlan p;
+    int rc = lower_conv(d, &p);
+    if (rc != AGX_OK) return rc;
+    if (!buf || buf_len == 0) return fail(AGX_ERR_NULL_POINTER, "agx_conv_bwd_weight_kernel_name: NULL buffer");
+    const bool bf = d->impl == AGX_IMPL_MFMA_BF16X3;
+    const BwGeom g = bw_geometry(p, bf);
+    const char *op = g.direct && p.s > 1 ? "phase_x" : (g.direct && p.q > 1 ? "phase_dy" : "none");
+    const long long items = (long long)p.B * ceil_div(p.Lt, g.direct ? 32 : BW_T);
+    snprintf(buf, buf_len, "%s cfg=%d op=%s slices=%d items=%lld", bw1_names[bw1_kernel(g, p, bf)], g.cfg, op,
+             g.n_slices * g.wk, items);
+    return AGX_OK;
+}
+
+int agx_conv2d_bwd_weight_kernel_name(const agx_conv2d_desc *d, char *buf, size_t buf_len) {
+    using namespace agx;
+    Bw2dGeom g;
+    int cfg, bm;
+    dim3 grid;
+    size_t lds;
+    int rc = bw2d_geometry(d, &g, &cfg, &bm, &grid, &lds);
+    if (rc != AGX_OK) return rc;
+    if (!buf || buf_len == 0) return fail(AGX_ERR_NULL_POINTER, "agx_conv2d_bwd_weight_kernel_name: NULL buffer");
+    const char *op = cfg >= 10 && g.prepad ? "prepad" : (cfg >= 10 && g.sw > 1 ? "deinterleave" : "none");
+    const long long items = cfg < 10 ? (long long)g.B * ceil_div(g.Hout, g.R) * ceil_div(g.Wout, g.WF)
+                          : g.prepad ? (long long)g.B * (g.pp_lpr / 32)
+                                     : (long long)g.B * g.Hout * (g.Wout / 32);
+    snprintf(buf, buf_len, "%s cfg=%d op=%s slices=%d items=%lld", bw2_names[bw2_kernel(g, cfg)], cfg, op, g.n_slices * g.wk,
+             items);
+    return AGX_OK;
 }
 
 #ifdef AGX_STAMPS

@@ -237,6 +237,13 @@ static int grouped_slices(const ConvPlan &p) {
     return int(ns);
 }
 
+// grouped_bwd_weight_tiled_kernel<opg> (true) or grouped_bwd_weight_kernel; *lds: the tiled kernel's LDS bytes
+static bool grouped_tiled(const ConvPlan &p, size_t *lds) {
+    const int cpg = p.Cin / p.G, opg = p.Cout / p.G;
+    *lds = (size_t(cpg) * ((GW_TT - 1) * p.s + p.J) + size_t(opg) * GW_TT) * sizeof(float);
+    return cpg * p.J + opg <= 256 && (opg == 16 || opg == 8 || opg == 4) && *lds <= 64 * 1024 && p.G <= 65535;
+}
+
 }  // namespace agx
 
 extern "C" {
@@ -290,10 +297,9 @@ int agx_conv_grouped_bwd_weight(const agx_conv_desc *d, const float *x, const fl
     const int ns = grouped_slices(p), row = (p.Cin / p.G) * p.J + 1;
     if (p.Cout > 65535) return fail(AGX_ERR_BAD_SHAPE, "grouped_bwd_weight: grid too large");
     float *part = static_cast<float *>(workspace);
-    const int cpg = p.Cin / p.G, opg = p.Cout / p.G;
-    const size_t lds = (size_t(cpg) * ((GW_TT - 1) * p.s + p.J) + size_t(opg) * GW_TT) * sizeof(float);
-    const bool tiled = cpg * p.J + opg <= 256 && (opg == 16 || opg == 8 || opg == 4) && lds <= 64 * 1024 && p.G <= 65535;
-    if (tiled) {
+    const int opg = p.Cout / p.G;
+    size_t lds;
+    if (grouped_tiled(p, &lds)) {
         dim3 grid(p.G, ns);
         if (opg == 16)
             hipLaunchKernelGGL(grouped_bwd_weight_tiled_kernel<16>, grid, dim3(256), lds, st, x, dz, part, p.B, p.Cin, p.Cout,
@@ -310,6 +316,25 @@ int agx_conv_grouped_bwd_weight(const agx_conv_desc *d, const float *x, const fl
     }
     hipLaunchKernelGGL(grouped_bwd_reduce_kernel, dim3(p.Cout), dim3(256), 0, st, part, ns, p.Cout, row, dw, dbias);
     return check_launch("agx_conv_grouped_bwd_weight");
+}
+
+// "<kernel> op=none slices=<n> items=<m>" as agx_conv_bwd_weight_kernel_name: items are 256-position tiles (tiled kernel,
+// slice k takes items k, k + slices, ...) or single positions (simple kernel, a contiguous range per slice)
+int agx_conv_grouped_bwd_weight_kernel_name(const agx_conv_desc *d, char *buf, size_t buf_len) {
+    using namespace agx;
+    ConvPlan p;
+    int rc = lower_conv(d, &p);
+    if (rc != AGX_OK) return rc;
+    if (d->kind != AGX_CONV_PADDED || p.d != 1) return fail(AGX_ERR_UNSUPPORTED, "grouped_bwd_weight: AGX_CONV_PADDED, dilation 1 only");
+    if (!buf || buf_len == 0) return fail(AGX_ERR_NULL_POINTER, "agx_conv_grouped_bwd_weight_kernel_name: NULL buffer");
+    size_t lds;
+    const bool tiled = grouped_tiled(p, &lds);
+    const long long items = (long long)p.B * (tiled ? ceil_div(p.Lout, GW_TT) : p.Lout);
+    if (tiled)
+        snprintf(buf, buf_len, "grouped_bwd_weight_tiled<%d> op=none slices=%d items=%lld", p.Cout / p.G, grouped_slices(p), items);
+    else
+        snprintf(buf, buf_len, "grouped_bwd_weight op=none slices=%d items=%lld", grouped_slices(p), items);
+    return AGX_OK;
 }
 
 }  // extern "C"

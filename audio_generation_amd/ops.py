@@ -254,6 +254,14 @@ def conv_bwd_weight(desc: ConvDesc, x: Tensor, dy: Tensor, v: Tensor, g: Optiona
     return dv, dg, db
 
 
+def conv_bwd_weight_kernel_name(desc: ConvDesc) -> str:
+    """What ``conv_bwd_weight`` runs: "<kernel> cfg=.. op=.. slices=.. items=.." (include/agx.h)."""
+    buf = ctypes.create_string_buffer(128)
+    _lib.check(_lib.load().agx_conv_bwd_weight_kernel_name(ctypes.byref(desc), buf, len(buf)),
+               "agx_conv_bwd_weight_kernel_name")
+    return buf.value.decode()
+
+
 def resblock_forward(desc: ConvDesc, x: Tensor, packed1: Tensor, bias1: Optional[Tensor],
                      packed2: Tensor, bias2: Optional[Tensor], post_act: bool = True) -> Tensor:
     lib = _lib.load()
@@ -632,6 +640,14 @@ def conv_grouped_bwd_weight(desc: ConvDesc, x: Tensor, dz: Tensor, want_bias: bo
     return dw, db
 
 
+def conv_grouped_bwd_weight_kernel_name(desc: ConvDesc) -> str:
+    """What ``conv_grouped_bwd_weight`` runs: "<kernel> op=none slices=.. items=.." (include/agx.h)."""
+    buf = ctypes.create_string_buffer(128)
+    _lib.check(_lib.load().agx_conv_grouped_bwd_weight_kernel_name(ctypes.byref(desc), buf, len(buf)),
+               "agx_conv_grouped_bwd_weight_kernel_name")
+    return buf.value.decode()
+
+
 def avgpool1d(x: Tensor, kernel: int, stride: int, padding: int) -> Tensor:
     lib = _lib.load()
     _need_gpu(x)
@@ -756,6 +772,14 @@ def conv2d_kernel_name(desc) -> str:
 def conv2d_bwd_data_kernel_name(desc) -> str:
     buf = ctypes.create_string_buffer(96)
     _lib.check(_lib.load().agx_conv2d_bwd_data_kernel_name(ctypes.byref(desc), buf, 96), "agx_conv2d_bwd_data_kernel_name")
+    return buf.value.decode()
+
+
+def conv2d_bwd_weight_kernel_name(desc) -> str:
+    """What ``conv2d_bwd_weight`` runs: "<kernel> cfg=.. op=.. slices=.. items=.." (include/agx.h)."""
+    buf = ctypes.create_string_buffer(128)
+    _lib.check(_lib.load().agx_conv2d_bwd_weight_kernel_name(ctypes.byref(desc), buf, len(buf)),
+               "agx_conv2d_bwd_weight_kernel_name")
     return buf.value.decode()
 
 

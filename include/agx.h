@@ -26,7 +26,7 @@
 extern "C" {
 #endif
 
-#define AGX_VERSION 120 /* 120: activation planes (agx_planes_bytes / agx_planes_split / agx_conv_forward_planes / agx_conv_planes_supported): pre-split bf16x3 input of the decoder's resampling convs; conv_p one-phase geometries (k = 1, "same" k = 11 / 3) with GELU / residual epilogues; 119: agx_rvq_verify_counts + knob rvq_verify (debug: the full defining search beside the fast path); agx_rvq_debug_stamps and the b3_dbg 7/8/9 bound knobs exist in the probe build only; 118: agx_feature_means(_backward) (the feature-matching pair in one pass); 117: agx_rvq_debug_stamps (diagnostic); 116: agx_multires_backward, agx_layernorm_ct one-pass kernel (same signature); agx_rvq_forward (legacy form) needs the workspace of agx_rvq_workspace_bytes since 114; 115: agx_rvq_ema_stats, agx_conv2d_bwd_data_kernel_name; 114: agx_attention_alibi_backward_ex (any T), agx_rvq_forward_ex; 113: tile images (resblock_p / conv_p), agx_attention_alibi_ex, agx_sizeof_*; 0.1.1: agx_conv_desc gained groups / padding (zero = old behaviour); 111: resample, conv2d column split */
+#define AGX_VERSION 121 /* 121: agx_conv_bwd_weight_kernel_name, agx_conv2d_bwd_weight_kernel_name, agx_conv_grouped_bwd_weight_kernel_name (kernel, operand copy, contraction slices and items of the weight-gradient ops); 120: activation planes (agx_planes_bytes / agx_planes_split / agx_conv_forward_planes / agx_conv_planes_supported): pre-split bf16x3 input of the decoder's resampling convs; conv_p one-phase geometries (k = 1, "same" k = 11 / 3) with GELU / residual epilogues; 119: agx_rvq_verify_counts + knob rvq_verify (debug: the full defining search beside the fast path); agx_rvq_debug_stamps and the b3_dbg 7/8/9 bound knobs exist in the probe build only; 118: agx_feature_means(_backward) (the feature-matching pair in one pass); 117: agx_rvq_debug_stamps (diagnostic); 116: agx_multires_backward, agx_layernorm_ct one-pass kernel (same signature); agx_rvq_forward (legacy form) needs the workspace of agx_rvq_workspace_bytes since 114; 115: agx_rvq_ema_stats, agx_conv2d_bwd_data_kernel_name; 114: agx_attention_alibi_backward_ex (any T), agx_rvq_forward_ex; 113: tile images (resblock_p / conv_p), agx_attention_alibi_ex, agx_sizeof_*; 0.1.1: agx_conv_desc gained groups / padding (zero = old behaviour); 111: resample, conv2d column split */
 
 #define AGX_OK 0
 #define AGX_ERR_BAD_SHAPE (-1)
@@ -176,6 +176,12 @@ size_t agx_conv_bwd_weight_workspace_bytes(const agx_conv_desc *d);
 int agx_conv_bwd_weight(const agx_conv_desc *d, const float *x, const float *dy, const float *v, const float *g,
                         float *dv, float *dg, float *dbias, void *workspace, size_t workspace_bytes,
                         void *stream);
+/* What agx_conv_bwd_weight runs for `d` (host only):
+ * "<kernel instantiation> cfg=<geometry> op=<none|phase_x|phase_dy> slices=<contraction slices> items=<work items>".
+ * op names the operand copy made first (phase-split x of a strided layer, phase-split dy of an upsampling /
+ * transposed one); items are 32-position chunks (direct kernels, cfg 10..14: slice k takes the contiguous range
+ * [k per, (k + 1) per), per = ceil(items / slices)) or 64-position tiles (staged kernel, cfg 0..2). */
+int agx_conv_bwd_weight_kernel_name(const agx_conv_desc *d, char *buf, size_t buf_len);
 
 /* Name of the kernel family/tile variant agx_conv_forward would launch for this
  * descriptor (e.g. "conv_mfma<2,2,2,2,16>"), for profilers and bench.py; matches
@@ -407,6 +413,9 @@ int agx_conv_grouped_bwd_data(const agx_conv_desc *d, const float *dz, const flo
 size_t agx_conv_grouped_bwd_weight_workspace_bytes(const agx_conv_desc *d);
 int agx_conv_grouped_bwd_weight(const agx_conv_desc *d, const float *x, const float *dz, float *dw, float *dbias,
                                 void *workspace, size_t workspace_bytes, void *stream);
+/* As agx_conv_bwd_weight_kernel_name for agx_conv_grouped_bwd_weight: items are 256-position tiles (tiled kernel) or
+ * single output positions (simple kernel). */
+int agx_conv_grouped_bwd_weight_kernel_name(const agx_conv_desc *d, char *buf, size_t buf_len);
 /* agx_conv_pack_bwd for a spectrally normalised dense layer (rows scaled by 1 / sigma[0]). */
 int agx_conv_pack_bwd_sigma(const agx_conv_desc *d, const float *w, const float *sigma, float *packed, void *stream);
 
@@ -456,6 +465,10 @@ size_t agx_conv2d_bwd_weight_workspace_bytes(const agx_conv2d_desc *d);
 int agx_conv2d_bwd_weight(const agx_conv2d_desc *d, const float *x, const float *dy, const float *w,
                           const float *sigma, const float *u, const float *v, float *dw, float *dbias,
                           void *workspace, size_t workspace_bytes, void *stream);
+/* As agx_conv_bwd_weight_kernel_name for agx_conv2d_bwd_weight: op is none, deinterleave (column-phase planes of x)
+ * or prepad (zero-padded, flattened copies of x and dy); items are 32-column chunks of an output row (direct /
+ * shared kernels, cfg 10..17; prepad: 32-position chunks of a flattened image) or staged tiles (cfg 0..2). */
+int agx_conv2d_bwd_weight_kernel_name(const agx_conv2d_desc *d, char *buf, size_t buf_len);
 
 /* The torch.stft call of STFTDiscriminator.forward (discriminator.py:181-187): rectangular window,
  * center=True (reflect padding), two-sided, optionally normalised by n_fft^-1/2, hop = n_fft / 4.

@@ -31,13 +31,13 @@ def _declared_symbols():
     return names
 
 
-def test_every_declared_symbol_is_exported_and_bound(lib):
+def test_every_declared_symbol_is_exported_and_bound_at_abi_121(lib):
     declared = _declared_symbols()
     assert declared, "no declarations found in include/*.h"
     assert declared == set(_lib.SIGNATURES), (declared ^ set(_lib.SIGNATURES))
     for name in declared:
         assert hasattr(lib, name), f"{name} declared in include/agx.h but not exported by libagx.so"
-    assert lib.agx_version() == 120
+    assert lib.agx_version() == 121
 
 
 def test_out_len_matches_reference_padding_rule(lib):
@@ -312,3 +312,47 @@ def test_bench_roofline_of_a_forward_that_mixes_the_two_matrix_pipes():
     floor = 1e3 * (200e9 / (2500e12 / 6) + 250e9 / 157.3e12)
     assert abs(r["blended_floor_ms"] - floor) < 1e-9 and abs(r["frac_of_blended_roofline"] - floor / 3.2) < 1e-12
     assert "frac_of_fp32_mfma_peak" not in r
+
+
+def test_weight_gradient_kernel_names_pin_the_production_slicing(lib):
+    """The weight-gradient name queries (host only) at config-5 shapes: kernel, operand copy, contraction slices and items.
+    These are the long-run regimes tests/test_gpu_weight_grad_training_size.py replays exactly; a dispatch change that
+    moves them (e.g. back to one item per slice) must show up here."""
+    from tests.wgrad_ref import parse_plan
+    c1, c2 = ops.conv_desc, ops.conv2d_desc
+    cases = [
+        (ops.conv_bwd_weight_kernel_name, c1(_lib.CONV_CAUSAL, 32, 32, 32, 72000, 7, 1, 1),
+         "conv_bwd_weight_direct<1,2,1,4> cfg=13 op=none slices=768 items=72000", 94),
+        (ops.conv_bwd_weight_kernel_name, c1(_lib.CONV_CAUSAL, 32, 512, 512, 225, 3, 1, 1),
+         "conv_bwd_weight_direct<2,2,2,2> cfg=10 op=none slices=16 items=256", 16),
+        (ops.conv_bwd_weight_kernel_name, c1(_lib.CONV_CAUSAL, 32, 32, 64, 72000, 5, 2, 1),
+         "conv_bwd_weight_direct<2,2,1,2,true> cfg=11 op=phase_x slices=768 items=36000", 47),
+        (ops.conv_bwd_weight_kernel_name, c1(_lib.CONV_TRANSPOSED, 32, 64, 32, 36000, 5, 2, 1),
+         "conv_bwd_weight_direct<2,2,1,2> cfg=11 op=phase_dy slices=768 items=36000", 47),
+        (ops.conv_bwd_weight_kernel_name, c1(_lib.CONV_UPSAMPLE, 32, 64, 32, 36000, 5, 2, 1),
+         "conv_bwd_weight_direct<2,2,1,2> cfg=11 op=phase_dy slices=768 items=36000", 47),
+        (ops.conv_grouped_bwd_weight_kernel_name, c1(_lib.CONV_PADDED, 32, 16, 64, 18000, 41, 4, 1, groups=4, padding=20),
+         "grouped_bwd_weight_tiled<16> op=none slices=1024 items=576", 1),
+        (ops.conv2d_bwd_weight_kernel_name, c2(32, 32, 32, 2251, 128, 3, 3, (1, 1), (1, 1)),
+         "conv2d_bwd_weight_direct<1,3,1,1> cfg=17 op=none slices=2048 items=288128", 141),
+        (ops.conv2d_bwd_weight_kernel_name, c2(32, 32, 64, 2251, 128, 3, 4, (1, 2), (1, 1)),
+         "conv2d_bwd_weight_shared<2,1,1,4> cfg=15 op=deinterleave slices=512 items=144064", 282),
+        (ops.conv2d_bwd_weight_kernel_name, c2(32, 128, 128, 1125, 32, 3, 3, (1, 1), (1, 1), impl=_lib.IMPL_MFMA_BF16X3),
+         "conv2d_bwd_weight_shared<2,2,2,2,1> cfg=10 op=none slices=171 items=36000", 211),
+        (ops.conv2d_bwd_weight_kernel_name, c2(32, 256, 256, 281, 8, 3, 3, (1, 1), (1, 1)),
+         "conv2d_bwd_weight_shared<2,2,2,2> cfg=10 op=prepad slices=43 items=2816", 66),
+        (ops.conv2d_bwd_weight_kernel_name, c2(32, 2, 32, 2251, 128, 7, 7, (1, 1), (3, 3)),
+         "conv2d_bwd_weight<1,1,1,4> cfg=2 op=none slices=1536 items=144064", 94),
+    ]
+    for query, desc, want, per in cases:
+        name = query(desc)
+        assert name == want, (name, want)
+        assert parse_plan(name)["per"] == per, name
+    # the queries read the knobs the launchers read
+    lib.agx_set_tuning(b"dw1_wgs", 1)
+    try:
+        assert ops.conv_bwd_weight_kernel_name(cases[0][1]).endswith("slices=1 items=72000")
+    finally:
+        lib.agx_set_tuning(b"dw1_wgs", 768)
+    with pytest.raises(_lib.AgxError):
+        ops.conv_grouped_bwd_weight_kernel_name(c1(_lib.CONV_CAUSAL, 1, 4, 4, 64, 3, 1, 1))
