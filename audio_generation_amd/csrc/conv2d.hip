@@ -6,24 +6,9 @@
 // c' = ci * kh + dh whose rows are rows t*sh + dh - ph of the input planes (zero rows outside the
 // image).  The MFMA kernel's LDS-DMA staging takes its row pointers from a RowMap (mfma_tile.hpp), so
 // the same tiles, pipeline and epilogue serve; blockIdx.x walks (b, t).
-#include "common.hpp"
+#include "conv_kernels.hpp"
 
 namespace agx {
-int launch_conv_direct(const ConvPlan &p, const float *x, const float *wp, const float *bias,
-                       const float *res, float *y, hipStream_t st);
-int launch_conv_mfma(const ConvPlan &p, const float *x, const float *wp, const float *bias,
-                     const float *res, float *y, hipStream_t st);
-bool conv_mfma_supported(const ConvPlan &p);
-const char *conv_mfma_variant(const ConvPlan &p);
-const char *conv_direct_variant(const ConvPlan &p);
-bool conv_p2d_supported(const ConvPlan &p);
-const char *conv_p2d_variant(const ConvPlan &p);
-int launch_conv_p2d(const ConvPlan &p, const float *x, const float *wp, const float *bias, const float *res, float *y,
-                    hipStream_t st);
-bool conv2d_b3_supported(const ConvPlan &p);
-const char *conv2d_b3_variant(const ConvPlan &p);
-int launch_conv2d_b3(const ConvPlan &p, const float *x, const float *wp, const float *bias, const float *res, float *y,
-                     hipStream_t st);
 void launch_b3_tile_from_bf(const float *img, float *timg, int64_t gj_count, int M, hipStream_t st);   // pack.hip
 
 int lower_conv2d(const agx_conv2d_desc *d, ConvPlan *p) {
@@ -371,6 +356,39 @@ static bool conv2d_fewout(const agx_conv2d_desc *d, const ConvPlan &p) {
     return (d->impl == AGX_IMPL_AUTO || d->impl == AGX_IMPL_MFMA_BF16X3) && p.pm_R == 0 && p.prec == 0 && p.M <= 4 && p.q == 1 && p.d == 1;
 }
 
+// Which kernel runs a Conv2d plan: agx_conv2d_forward / agx_conv2d_bwd_data switch on it, the name queries print
+// conv2d_kernel_name of it.  A negative result is a refusal (error code, message set).
+enum Conv2dKernel { C2D_FEWOUT, C2D_GATHER, C2D_B3, C2D_P2D, C2D_MFMA, C2D_DIRECT };
+static int conv2d_kernel(const agx_conv2d_desc *d, const ConvPlan &p) {
+    if (conv2d_fewout(d, p)) return C2D_FEWOUT;
+    if (p.prec == 1 && conv2d_b3_supported(p)) return C2D_B3;
+    if (tuning().conv_impl == 1 && conv_p2d_supported(p)) return C2D_P2D;
+    int impl = d->impl;
+    if (impl == AGX_IMPL_MFMA_BF16X3) impl = p.prec ? AGX_IMPL_MFMA : AGX_IMPL_AUTO;   // layers without a bf16x3 form run fp32
+    if (impl == AGX_IMPL_AUTO) impl = conv_mfma_supported(p) ? AGX_IMPL_MFMA : AGX_IMPL_DIRECT;
+    if (p.pm_R && impl != AGX_IMPL_MFMA)   // the patch-mode image has no direct kernel
+        return fail(AGX_ERR_UNSUPPORTED, "conv2d: no MFMA tile fits this layer (set impl = AGX_IMPL_DIRECT for pack and forward)");
+    if (impl == AGX_IMPL_MFMA) return C2D_MFMA;
+    if (impl == AGX_IMPL_DIRECT) return C2D_DIRECT;
+    return fail(AGX_ERR_BAD_SHAPE, "conv2d: unknown impl %d", impl);
+}
+
+static int conv2d_bwd_kernel(const agx_conv2d_desc *d, const ConvPlan &b) {
+    if (b.pm_R < 0) return C2D_GATHER;
+    if (b.prec == 1 && conv2d_b3_supported(b)) return C2D_B3;
+    if (tuning().conv_impl == 1 && conv_p2d_supported(b)) return C2D_P2D;
+    if (b.pm_R || (d->impl != AGX_IMPL_DIRECT && conv_mfma_supported(b))) return C2D_MFMA;
+    return C2D_DIRECT;
+}
+
+static int conv2d_kernel_name(int k, const ConvPlan &p, char *buf, size_t buf_len) {
+    if (k < 0) return k;
+    snprintf(buf, buf_len, "%s", k == C2D_FEWOUT ? "conv2d_fewout<4>" : k == C2D_GATHER ? "conv2d_bwd_data_gather"
+                                 : k == C2D_B3 ? conv2d_b3_variant(p) : k == C2D_P2D ? conv_p2d_variant(p)
+                                 : k == C2D_MFMA ? conv_mfma_variant(p) : conv_direct_variant(p));
+    return AGX_OK;
+}
+
 }  // namespace agx
 
 extern "C" {
@@ -420,18 +438,19 @@ int agx_conv2d_bwd_data(const agx_conv2d_desc *d, const float *dy, const float *
     b.mask = mask;
     b.slope = slope;
     hipStream_t st = static_cast<hipStream_t>(stream);
-    if (b.pm_R < 0) {
-        const int64_t total = int64_t(d->batch) * d->c_in * d->h_in * d->w_in;
-        hipLaunchKernelGGL(conv2d_bwd_data_gather_kernel, dim3((unsigned)ceil_div64(total, 256)), dim3(256), 0, st, dy,
-                           packed_bwd, add, mask, slope, dx, d->batch, d->c_in, d->c_out, d->h_in, d->w_in, b.Tin, b.Lin,
-                           d->kh, d->kw, d->stride_h, d->stride_w, d->pad_h, d->pad_w);
-        return check_launch("agx_conv2d_bwd_data");
+    switch (conv2d_bwd_kernel(d, b)) {
+        case C2D_GATHER: {
+            const int64_t total = int64_t(d->batch) * d->c_in * d->h_in * d->w_in;
+            hipLaunchKernelGGL(conv2d_bwd_data_gather_kernel, dim3((unsigned)ceil_div64(total, 256)), dim3(256), 0, st, dy,
+                               packed_bwd, add, mask, slope, dx, d->batch, d->c_in, d->c_out, d->h_in, d->w_in, b.Tin, b.Lin,
+                               d->kh, d->kw, d->stride_h, d->stride_w, d->pad_h, d->pad_w);
+            return check_launch("agx_conv2d_bwd_data");
+        }
+        case C2D_B3: return launch_conv2d_b3(b, dy, packed_bwd, nullptr, add, dx, st);
+        case C2D_P2D: return launch_conv_p2d(b, dy, packed_bwd, nullptr, add, dx, st);
+        case C2D_MFMA: return launch_conv_mfma(b, dy, packed_bwd, nullptr, add, dx, st);
+        default: return launch_conv_direct(b, dy, packed_bwd, nullptr, add, dx, st);   // C2D_DIRECT: this op refuses nothing
     }
-    if (b.prec == 1 && conv2d_b3_supported(b)) return launch_conv2d_b3(b, dy, packed_bwd, nullptr, add, dx, st);
-    if (tuning().conv_impl == 1 && conv_p2d_supported(b)) return launch_conv_p2d(b, dy, packed_bwd, nullptr, add, dx, st);
-    if (b.pm_R || (d->impl != AGX_IMPL_DIRECT && conv_mfma_supported(b)))
-        return launch_conv_mfma(b, dy, packed_bwd, nullptr, add, dx, st);
-    return launch_conv_direct(b, dy, packed_bwd, nullptr, add, dx, st);
 }
 
 int agx_conv2d_colsplit_weights(const agx_conv2d_desc *d, const float *w, const float *sigma, float *wp, void *stream) {
@@ -465,13 +484,6 @@ int agx_conv2d_out_shape(const agx_conv2d_desc *d, int32_t *h_out, int32_t *w_ou
     return AGX_OK;
 }
 
-static int conv2d_impl(const agx_conv2d_desc *d, const agx::ConvPlan &p) {
-    int impl = d->impl;
-    if (impl == AGX_IMPL_MFMA_BF16X3) impl = p.prec ? AGX_IMPL_MFMA : AGX_IMPL_AUTO;   // layers without a bf16x3 form run fp32
-    if (impl == AGX_IMPL_AUTO) impl = agx::conv_mfma_supported(p) ? AGX_IMPL_MFMA : AGX_IMPL_DIRECT;
-    return impl;
-}
-
 int agx_conv2d_forward(const agx_conv2d_desc *d, const float *x, const float *packed, const float *bias, float *y,
                        void *stream) {
     using namespace agx;
@@ -480,20 +492,20 @@ int agx_conv2d_forward(const agx_conv2d_desc *d, const float *x, const float *pa
     if (rc != AGX_OK) return rc;
     if (!x || !packed || !y) return fail(AGX_ERR_NULL_POINTER, "agx_conv2d_forward: NULL pointer");
     hipStream_t st = static_cast<hipStream_t>(stream);
-    if (conv2d_fewout(d, p)) {
-        const int64_t npos = int64_t(p.B) * p.Tout * p.Lout;
-        hipLaunchKernelGGL(conv2d_fewout_kernel<4>, dim3((unsigned)ceil_div64(npos, 4)), dim3(256), 0, st, p, x, packed, bias, y,
-                           npos);
-        return check_launch("agx_conv2d_forward");
+    const int k = conv2d_kernel(d, p);
+    switch (k) {
+        case C2D_FEWOUT: {
+            const int64_t npos = int64_t(p.B) * p.Tout * p.Lout;
+            hipLaunchKernelGGL(conv2d_fewout_kernel<4>, dim3((unsigned)ceil_div64(npos, 4)), dim3(256), 0, st, p, x, packed, bias, y,
+                               npos);
+            return check_launch("agx_conv2d_forward");
+        }
+        case C2D_B3: return launch_conv2d_b3(p, x, packed, bias, nullptr, y, st);
+        case C2D_P2D: return launch_conv_p2d(p, x, packed, bias, nullptr, y, st);
+        case C2D_MFMA: return launch_conv_mfma(p, x, packed, bias, nullptr, y, st);
+        case C2D_DIRECT: return launch_conv_direct(p, x, packed, bias, nullptr, y, st);
+        default: return k;
     }
-    if (p.prec == 1 && conv2d_b3_supported(p)) return launch_conv2d_b3(p, x, packed, bias, nullptr, y, st);
-    if (tuning().conv_impl == 1 && conv_p2d_supported(p)) return launch_conv_p2d(p, x, packed, bias, nullptr, y, st);
-    const int impl = conv2d_impl(d, p);
-    if (p.pm_R && impl != AGX_IMPL_MFMA)
-        return fail(AGX_ERR_UNSUPPORTED, "conv2d: no MFMA tile fits this layer (set impl = AGX_IMPL_DIRECT for pack and forward)");
-    if (impl == AGX_IMPL_MFMA) return launch_conv_mfma(p, x, packed, bias, nullptr, y, st);
-    if (impl == AGX_IMPL_DIRECT) return launch_conv_direct(p, x, packed, bias, nullptr, y, st);
-    return fail(AGX_ERR_BAD_SHAPE, "conv2d: unknown impl %d", impl);
 }
 
 int agx_conv2d_kernel_name(const agx_conv2d_desc *d, char *buf, size_t buf_len) {
@@ -502,11 +514,7 @@ int agx_conv2d_kernel_name(const agx_conv2d_desc *d, char *buf, size_t buf_len) 
     int rc = lower_conv2d(d, &p);
     if (rc != AGX_OK) return rc;
     if (!buf || buf_len == 0) return fail(AGX_ERR_NULL_POINTER, "agx_conv2d_kernel_name: NULL buffer");
-    snprintf(buf, buf_len, "%s", (p.prec == 1 && agx::conv2d_b3_supported(p)) ? agx::conv2d_b3_variant(p)
-                                 : (agx::tuning().conv_impl == 1 && agx::conv_p2d_supported(p)) ? agx::conv_p2d_variant(p)
-                                 : agx::conv2d_fewout(d, p) ? "conv2d_fewout<4>"
-                                 : (conv2d_impl(d, p) == AGX_IMPL_MFMA ? conv_mfma_variant(p) : conv_direct_variant(p)));
-    return AGX_OK;
+    return conv2d_kernel_name(conv2d_kernel(d, p), p, buf, buf_len);
 }
 
 int agx_conv2d_bwd_data_kernel_name(const agx_conv2d_desc *d, char *buf, size_t buf_len) {
@@ -515,12 +523,7 @@ int agx_conv2d_bwd_data_kernel_name(const agx_conv2d_desc *d, char *buf, size_t 
     int rc = lower_conv2d_bwd_data(d, &b);
     if (rc != AGX_OK) return rc;
     if (!buf || buf_len == 0) return fail(AGX_ERR_NULL_POINTER, "agx_conv2d_bwd_data_kernel_name: NULL buffer");
-    snprintf(buf, buf_len, "%s", b.pm_R < 0 ? "conv2d_bwd_data_gather"
-                                 : (b.prec == 1 && conv2d_b3_supported(b)) ? conv2d_b3_variant(b)
-                                 : (tuning().conv_impl == 1 && conv_p2d_supported(b)) ? conv_p2d_variant(b)
-                                 : (b.pm_R || (d->impl != AGX_IMPL_DIRECT && conv_mfma_supported(b))) ? conv_mfma_variant(b)
-                                                                                                       : conv_direct_variant(b));
-    return AGX_OK;
+    return conv2d_kernel_name(conv2d_bwd_kernel(d, b), b, buf, buf_len);
 }
 
 }  // extern "C"

@@ -1,37 +1,7 @@
 // C-ABI entry points of the convolution family: shape checks + kernel dispatch.
-#include "common.hpp"
+#include "conv_kernels.hpp"
 
 namespace agx {
-int launch_conv_direct(const ConvPlan &p, const float *x, const float *wp, const float *bias,
-                       const float *res, float *y, hipStream_t st);
-int launch_conv_mfma(const ConvPlan &p, const float *x, const float *wp, const float *bias,
-                     const float *res, float *y, hipStream_t st);
-bool conv_mfma_supported(const ConvPlan &p);
-const char *conv_mfma_variant(const ConvPlan &p);
-const char *conv_direct_variant(const ConvPlan &p);
-int launch_resblock_fused(const ConvPlan &p, const float *x, const float *w1, const float *b1,
-                          const float *w2, const float *b2, float *y, int post_act, hipStream_t st);
-bool resblock_fused_supported(const ConvPlan &p);
-const char *resblock_variant(const ConvPlan &p);
-int launch_resblock_p(const ConvPlan &p, const float *x, const float *w1, const float *b1, const float *w2,
-                      const float *b2, float *y, int post_act, hipStream_t st);
-bool resblock_p_supported(const ConvPlan &p);
-const char *resblock_p_variant(const ConvPlan &p);
-int launch_resblock_b3(const ConvPlan &p, const float *x, const float *w1, const float *b1, const float *w2,
-                       const float *b2, float *y, int post_act, hipStream_t st);
-bool resblock_b3_supported(const ConvPlan &p);
-const char *resblock_b3_variant(const ConvPlan &p);
-int launch_conv_b3(const ConvPlan &p, const float *x, const float *wp, const float *bias, float *y, hipStream_t st);
-bool conv_b3_supported(const ConvPlan &p);
-int launch_conv_b3_planes(const ConvPlan &p, const void *x_planes, const float *wp, const float *bias, float *y, void *y_planes,
-                          hipStream_t st);
-int launch_planes_split(const float *x, void *planes, int batch, int channels, int length, hipStream_t st);
-const char *conv_b3_variant(const ConvPlan &p);
-int launch_conv_p(const ConvPlan &p, const float *x, const float *wp, const float *bias, const float *res, float *y,
-                  hipStream_t st);
-bool conv_p_supported(const ConvPlan &p);
-const char *conv_p_variant(const ConvPlan &p);
-
 // dx *= gelu'(pre)  (exact erf GELU)
 __global__ __launch_bounds__(256) void gelu_grad_mul_kernel(float *__restrict__ dx, const float *__restrict__ pre, int64_t n) {
     const int64_t i = int64_t(blockIdx.x) * 256 + threadIdx.x;
@@ -40,15 +10,64 @@ __global__ __launch_bounds__(256) void gelu_grad_mul_kernel(float *__restrict__ 
     dx[i] *= 0.5f * (1.f + erff(x * 0.70710678118654752f)) + x * 0.3989422804014327f * expf(-0.5f * x * x);
 }
 
+// Which family runs a lowered 1-D plan (forward, backward-data, the two launches of the residual-block fallback): launcher and
+// name query both read it.  A negative result is a refusal (error code, message set); ring = false leaves the ring kernels out.
+enum ConvKernel { CONV_P, CONV_B3, CONV_MFMA, CONV_DIRECT };
+static int conv_kernel(const ConvPlan &p, int impl, bool ring = true) {
+    ring = ring && tuning().conv_impl == 1;
+    if ((impl == AGX_IMPL_AUTO || impl == AGX_IMPL_MFMA) && ring && conv_p_supported(p)) return CONV_P;
+    if (impl == AGX_IMPL_MFMA_BF16X3 && ring && conv_b3_supported(p)) return CONV_B3;
+    if (impl == AGX_IMPL_AUTO) return conv_mfma_supported(p) ? CONV_MFMA : CONV_DIRECT;
+    if (impl == AGX_IMPL_MFMA || impl == AGX_IMPL_MFMA_BF16X3) return CONV_MFMA;
+    if (impl == AGX_IMPL_DIRECT) return CONV_DIRECT;
+    return fail(AGX_ERR_BAD_SHAPE, "conv: unknown impl %d", impl);
+}
+
 static int run_conv(const ConvPlan &p, int impl, const float *x, const float *wp, const float *bias,
                     const float *res, float *y, hipStream_t st) {
-    if ((impl == AGX_IMPL_AUTO || impl == AGX_IMPL_MFMA) && tuning().conv_impl == 1 && conv_p_supported(p))
-        return launch_conv_p(p, x, wp, bias, res, y, st);
-    if (impl == AGX_IMPL_MFMA_BF16X3 && tuning().conv_impl == 1 && conv_b3_supported(p)) return launch_conv_b3(p, x, wp, bias, y, st);
-    if (impl == AGX_IMPL_AUTO) impl = conv_mfma_supported(p) ? AGX_IMPL_MFMA : AGX_IMPL_DIRECT;
-    if (impl == AGX_IMPL_MFMA || impl == AGX_IMPL_MFMA_BF16X3) return launch_conv_mfma(p, x, wp, bias, res, y, st);
-    if (impl == AGX_IMPL_DIRECT) return launch_conv_direct(p, x, wp, bias, res, y, st);
-    return fail(AGX_ERR_BAD_SHAPE, "conv: unknown impl %d", impl);
+    const int k = conv_kernel(p, impl);
+    switch (k) {
+        case CONV_P: return launch_conv_p(p, x, wp, bias, res, y, st);
+        case CONV_B3: return launch_conv_b3(p, x, wp, bias, y, st);
+        case CONV_MFMA: return launch_conv_mfma(p, x, wp, bias, res, y, st);
+        case CONV_DIRECT: return launch_conv_direct(p, x, wp, bias, res, y, st);
+        default: return k;
+    }
+}
+
+// "<prefix><variant>[:bf16x3]" of the family conv_kernel picks
+static int conv_name(const ConvPlan &p, int impl, bool ring, const char *prefix, char *buf, size_t buf_len) {
+    const int k = conv_kernel(p, impl, ring);
+    if (k < 0) return k;
+    const char *v = k == CONV_P ? conv_p_variant(p) : k == CONV_B3 ? conv_b3_variant(p) : k == CONV_MFMA ? conv_mfma_variant(p)
+                                                                                                          : conv_direct_variant(p);
+    snprintf(buf, buf_len, "%s%s%s", prefix, v, impl == AGX_IMPL_MFMA_BF16X3 ? ":bf16x3" : "");
+    return AGX_OK;
+}
+
+// The layer's bf16x3 ring kernel reads pre-split planes (the strided down-convs and the causal k = 3 layer take fp32 input only)
+static bool conv_takes_planes(const ConvPlan &p, int impl) {
+    return conv_kernel(p, impl) == CONV_B3 && p.s == 1 && !(p.q == 1 && p.J != 7);
+}
+
+// Plan of the residual block `d` describes (its first conv with the LeakyReLU epilogue), for the launcher and the name query
+static int lower_resblock(const agx_conv_desc *d, ConvPlan *p) {
+    if (!d) return fail(AGX_ERR_NULL_POINTER, "resblock: NULL descriptor");
+    if (d->kind != AGX_CONV_CAUSAL || d->stride != 1 || d->c_in != d->c_out)
+        return fail(AGX_ERR_BAD_SHAPE, "resblock: needs a stride-1 causal conv with c_in == c_out");
+    agx_conv_desc d1 = *d;
+    d1.epilogue = AGX_EPI_LEAKY_PRE;
+    return lower_conv(&d1, p);
+}
+
+// Form of the residual block: one kernel (fp32 ring / bf16x3 ring / staged MFMA tiles) or two conv launches
+enum ResblockKernel { RB_P, RB_B3, RB_FUSED, RB_TWO };
+static ResblockKernel resblock_kernel(const ConvPlan &p, int impl) {
+    const bool ring = tuning().rb_impl == 1;
+    if (impl != AGX_IMPL_DIRECT && ring && resblock_p_supported(p)) return RB_P;
+    if (ring && resblock_b3_supported(p)) return RB_B3;
+    if (impl != AGX_IMPL_DIRECT && resblock_fused_supported(p)) return RB_FUSED;
+    return RB_TWO;
 }
 }  // namespace agx
 
@@ -86,7 +105,7 @@ int agx_conv_forward_planes(const agx_conv_desc *d, const void *x_planes, const 
     int rc = lower_conv(d, &p);
     if (rc != AGX_OK) return rc;
     if (!x_planes || !packed || (!y && !y_planes)) return fail(AGX_ERR_NULL_POINTER, "agx_conv_forward_planes: NULL pointer");
-    if (d->impl != AGX_IMPL_MFMA_BF16X3 || tuning().conv_impl != 1 || !conv_b3_supported(p) || p.s != 1 || (p.q == 1 && p.J != 7))
+    if (!conv_takes_planes(p, d->impl))
         return fail(AGX_ERR_UNSUPPORTED, "agx_conv_forward_planes: the layer has no plane-fed bf16x3 ring form (ask agx_conv_planes_supported first)");
     return launch_conv_b3_planes(p, x_planes, packed, bias, y, y_planes, static_cast<hipStream_t>(stream));
 }
@@ -95,8 +114,7 @@ int agx_conv_planes_supported(const agx_conv_desc *d) {
     using namespace agx;
     ConvPlan p;
     if (lower_conv(d, &p) != AGX_OK) return 0;
-    if (d->impl != AGX_IMPL_MFMA_BF16X3 || tuning().conv_impl != 1 || !conv_b3_supported(p)) return 0;
-    if (p.s != 1 || (p.q == 1 && p.J != 7)) return 0;   // the strided down-convs and the causal k = 3 layer take fp32 input only
+    if (!conv_takes_planes(p, d->impl)) return 0;
     return (p.q == 1 && p.Cout % 8 == 0) ? 2 : 1;      // 2: the layer can also WRITE planes (one output phase)
 }
 
@@ -137,19 +155,7 @@ int agx_conv_kernel_name(const agx_conv_desc *d, char *buf, size_t buf_len) {
     int rc = lower_conv(d, &p);
     if (rc != AGX_OK) return rc;
     if (!buf || buf_len == 0) return fail(AGX_ERR_NULL_POINTER, "agx_conv_kernel_name: NULL buffer");
-    int impl = d->impl;
-    if (impl == AGX_IMPL_MFMA_BF16X3 && tuning().conv_impl == 1 && conv_b3_supported(p)) {
-        snprintf(buf, buf_len, "%s:bf16x3", conv_b3_variant(p));
-        return AGX_OK;
-    }
-    if ((impl == AGX_IMPL_AUTO || impl == AGX_IMPL_MFMA) && tuning().conv_impl == 1 && conv_p_supported(p)) {
-        snprintf(buf, buf_len, "%s", conv_p_variant(p));
-        return AGX_OK;
-    }
-    if (impl == AGX_IMPL_AUTO) impl = conv_mfma_supported(p) ? AGX_IMPL_MFMA : AGX_IMPL_DIRECT;
-    if (impl == AGX_IMPL_MFMA_BF16X3) snprintf(buf, buf_len, "%s:bf16x3", conv_mfma_variant(p));
-    else snprintf(buf, buf_len, "%s", impl == AGX_IMPL_MFMA ? conv_mfma_variant(p) : conv_direct_variant(p));
-    return AGX_OK;
+    return conv_name(p, d->impl, true, "", buf, buf_len);
 }
 
 size_t agx_resblock_workspace_bytes(const agx_conv_desc *d) {
@@ -159,23 +165,15 @@ size_t agx_resblock_workspace_bytes(const agx_conv_desc *d) {
 
 int agx_resblock_kernel_name(const agx_conv_desc *d, char *buf, size_t buf_len) {
     using namespace agx;
-    if (!d || !buf || buf_len == 0) return fail(AGX_ERR_NULL_POINTER, "agx_resblock_kernel_name: NULL pointer");
-    agx_conv_desc d1 = *d;
-    d1.epilogue = AGX_EPI_LEAKY_PRE;
     ConvPlan p;
-    int rc = lower_conv(&d1, &p);
+    int rc = lower_resblock(d, &p);
     if (rc != AGX_OK) return rc;
-    if (d->impl != AGX_IMPL_DIRECT && tuning().rb_impl == 1 && resblock_p_supported(p)) {
-        snprintf(buf, buf_len, "%s", resblock_p_variant(p));
-    } else if (tuning().rb_impl == 1 && resblock_b3_supported(p)) {
-        snprintf(buf, buf_len, "%s:bf16x3", resblock_b3_variant(p));
-    } else if (d->impl != AGX_IMPL_DIRECT && resblock_fused_supported(p)) {
-        snprintf(buf, buf_len, "%s%s", resblock_variant(p), p.prec ? ":bf16x3" : "");
-    } else {
-        int impl = d->impl;
-        if (impl == AGX_IMPL_AUTO) impl = conv_mfma_supported(p) ? AGX_IMPL_MFMA : AGX_IMPL_DIRECT;
-        snprintf(buf, buf_len, "2x:%s%s", impl == AGX_IMPL_DIRECT ? conv_direct_variant(p) : conv_mfma_variant(p),
-                 p.prec ? ":bf16x3" : "");
+    if (!buf || buf_len == 0) return fail(AGX_ERR_NULL_POINTER, "agx_resblock_kernel_name: NULL pointer");
+    switch (resblock_kernel(p, d->impl)) {
+        case RB_P: snprintf(buf, buf_len, "%s", resblock_p_variant(p)); return AGX_OK;
+        case RB_B3: snprintf(buf, buf_len, "%s:bf16x3", resblock_b3_variant(p)); return AGX_OK;
+        case RB_FUSED: snprintf(buf, buf_len, "%s%s", resblock_variant(p), p.prec ? ":bf16x3" : ""); return AGX_OK;
+        case RB_TWO: return conv_name(p, d->impl, false, "2x:", buf, buf_len);   // (the plan's tile family, as the name always was)
     }
     return AGX_OK;
 }
@@ -184,22 +182,17 @@ int agx_resblock_forward(const agx_conv_desc *d, const float *x, const float *pa
                          const float *bias1, const float *packed2, const float *bias2, float *y,
                          int32_t post_act, void *workspace, size_t workspace_bytes, void *stream) {
     using namespace agx;
-    if (!d) return fail(AGX_ERR_NULL_POINTER, "agx_resblock_forward: NULL descriptor");
-    if (d->kind != AGX_CONV_CAUSAL || d->stride != 1 || d->c_in != d->c_out)
-        return fail(AGX_ERR_BAD_SHAPE, "resblock: needs a stride-1 causal conv with c_in == c_out");
+    ConvPlan p1;
+    int rc = lower_resblock(d, &p1);
+    if (rc != AGX_OK) return rc;
     if (!x || !packed1 || !packed2 || !y) return fail(AGX_ERR_NULL_POINTER, "agx_resblock_forward: NULL pointer");
     hipStream_t st = static_cast<hipStream_t>(stream);
-    agx_conv_desc d1 = *d;
-    d1.epilogue = AGX_EPI_LEAKY_PRE;
-    ConvPlan p1;
-    int rc = lower_conv(&d1, &p1);
-    if (rc != AGX_OK) return rc;
-    if (d->impl != AGX_IMPL_DIRECT && tuning().rb_impl == 1 && resblock_p_supported(p1))
-        return launch_resblock_p(p1, x, packed1, bias1, packed2, bias2, y, post_act, st);
-    if (tuning().rb_impl == 1 && resblock_b3_supported(p1))
-        return launch_resblock_b3(p1, x, packed1, bias1, packed2, bias2, y, post_act, st);
-    if (d->impl != AGX_IMPL_DIRECT && resblock_fused_supported(p1))
-        return launch_resblock_fused(p1, x, packed1, bias1, packed2, bias2, y, post_act, st);
+    switch (resblock_kernel(p1, d->impl)) {
+        case RB_P: return launch_resblock_p(p1, x, packed1, bias1, packed2, bias2, y, post_act, st);
+        case RB_B3: return launch_resblock_b3(p1, x, packed1, bias1, packed2, bias2, y, post_act, st);
+        case RB_FUSED: return launch_resblock_fused(p1, x, packed1, bias1, packed2, bias2, y, post_act, st);
+        case RB_TWO: break;
+    }
     // two launches: h = leaky(conv1(x)+b1) -> workspace;  y = [leaky](x + conv2(h) + b2)
     if (!workspace || workspace_bytes < agx_resblock_workspace_bytes(d))
         return fail(AGX_ERR_WORKSPACE, "resblock: workspace too small (%zu < %zu)", workspace_bytes,

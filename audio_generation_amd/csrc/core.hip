@@ -30,6 +30,13 @@ Tuning &tuning() {
     return t;
 }
 
+static Knob *find_knob(const char *name) {
+#define AGX_KNOB_FIND(knob, value) if (!strcmp(name, #knob)) return &tuning().knob;
+    AGX_KNOBS(AGX_KNOB_FIND)
+#undef AGX_KNOB_FIND
+    return nullptr;
+}
+
 int lower_conv(const agx_conv_desc *d, ConvPlan *p) {
     if (!d) return fail(AGX_ERR_NULL_POINTER, "conv descriptor is NULL");
     if (d->batch <= 0 || d->c_in <= 0 || d->c_out <= 0 || d->l_in <= 0 || d->kernel <= 0 ||
@@ -240,62 +247,20 @@ const char *agx_last_error(void) { return agx::last_error(); }
 
 int agx_set_tuning(const char *name, int32_t value) {
     if (!name) return agx::fail(AGX_ERR_NULL_POINTER, "agx_set_tuning: NULL name");
-    if (!strcmp(name, "rb_cc")) agx::tuning().rb_cc = value;
-    else if (!strcmp(name, "rb_wgs")) agx::tuning().rb_wgs = value;
-    else if (!strcmp(name, "rb_sched")) agx::tuning().rb_sched = value;
-    else if (!strcmp(name, "rb_occ")) agx::tuning().rb_occ = value;
-    else if (!strcmp(name, "rb_impl")) agx::tuning().rb_impl = value;
-    else if (!strcmp(name, "b3_dbg")) {
+    agx::Knob *k = agx::find_knob(name);
+    if (!k) return agx::fail(AGX_ERR_BAD_SHAPE, "agx_set_tuning: unknown knob '%s'", name);
 #ifndef AGX_RVQ_PROBE
-        if (value >= 7 && value <= 9)   // they weaken / repurpose the RVQ candidate bound: never in the product library
-            return agx::fail(AGX_ERR_UNSUPPORTED, "agx_set_tuning: b3_dbg = %d exists in the probe build only (tools/rvq_stamps.py build)", value);
+    if (k == &agx::tuning().b3_dbg && value >= 7 && value <= 9)   // they weaken / repurpose the RVQ candidate bound: never in the product library
+        return agx::fail(AGX_ERR_UNSUPPORTED, "agx_set_tuning: b3_dbg = %d exists in the probe build only (tools/rvq_stamps.py build)", value);
 #endif
-        agx::tuning().b3_dbg = value;
-    } else if (!strcmp(name, "rvq_verify")) agx::tuning().rvq_verify = value;
-    else if (!strcmp(name, "conv_impl")) agx::tuning().conv_impl = value;
-    else if (!strcmp(name, "bf_sched")) agx::tuning().bf_sched = value;
-    else if (!strcmp(name, "patch_tie")) agx::tuning().patch_tie = value;
-    else if (!strcmp(name, "dw2_direct")) agx::tuning().dw2_direct = value;
-    else if (!strcmp(name, "dw2_shared")) agx::tuning().dw2_shared = value;
-    else if (!strcmp(name, "dw_wgs")) agx::tuning().dw_wgs = value;
-    else if (!strcmp(name, "dw_xcd")) agx::tuning().dw_xcd = value;
-    else if (!strcmp(name, "dw2_bf")) agx::tuning().dw2_bf = value;
-    else if (!strcmp(name, "dw2_prepad")) agx::tuning().dw2_prepad = value;
-    else if (!strcmp(name, "c2b3_sl")) agx::tuning().c2b3_sl = value;
-    else if (!strcmp(name, "dw_direct")) agx::tuning().dw_direct = value;
-    else if (!strcmp(name, "dw1_wgs")) agx::tuning().dw1_wgs = value;
-    else if (!strcmp(name, "conv_cc")) agx::tuning().conv_cc = value;
-    else if (!strcmp(name, "conv_shape")) agx::tuning().conv_shape = value;
-    else if (!strcmp(name, "conv_short")) agx::tuning().conv_short = value;
-    else return agx::fail(AGX_ERR_BAD_SHAPE, "agx_set_tuning: unknown knob '%s'", name);
+    *k = value;
     return AGX_OK;
 }
 
 int agx_get_tuning(const char *name) {
     if (!name) return agx::fail(AGX_ERR_NULL_POINTER, "agx_get_tuning: NULL name");
-    if (!strcmp(name, "rb_cc")) return agx::tuning().rb_cc;
-    if (!strcmp(name, "rb_wgs")) return agx::tuning().rb_wgs;
-    if (!strcmp(name, "rb_sched")) return agx::tuning().rb_sched;
-    if (!strcmp(name, "rb_occ")) return agx::tuning().rb_occ;
-    if (!strcmp(name, "rb_impl")) return agx::tuning().rb_impl;
-    if (!strcmp(name, "b3_dbg")) return agx::tuning().b3_dbg;
-    if (!strcmp(name, "rvq_verify")) return agx::tuning().rvq_verify;
-    if (!strcmp(name, "conv_impl")) return agx::tuning().conv_impl;
-    if (!strcmp(name, "bf_sched")) return agx::tuning().bf_sched;
-    if (!strcmp(name, "patch_tie")) return agx::tuning().patch_tie;
-    if (!strcmp(name, "dw2_direct")) return agx::tuning().dw2_direct;
-    if (!strcmp(name, "dw2_shared")) return agx::tuning().dw2_shared;
-    if (!strcmp(name, "dw_wgs")) return agx::tuning().dw_wgs;
-    if (!strcmp(name, "dw_xcd")) return agx::tuning().dw_xcd;
-    if (!strcmp(name, "dw2_bf")) return agx::tuning().dw2_bf;
-    if (!strcmp(name, "dw2_prepad")) return agx::tuning().dw2_prepad;
-    if (!strcmp(name, "c2b3_sl")) return agx::tuning().c2b3_sl;
-    if (!strcmp(name, "dw_direct")) return agx::tuning().dw_direct;
-    if (!strcmp(name, "dw1_wgs")) return agx::tuning().dw1_wgs;
-    if (!strcmp(name, "conv_cc")) return agx::tuning().conv_cc;
-    if (!strcmp(name, "conv_shape")) return agx::tuning().conv_shape;
-    if (!strcmp(name, "conv_short")) return agx::tuning().conv_short;
-    return agx::fail(AGX_ERR_BAD_SHAPE, "agx_get_tuning: unknown knob '%s'", name);
+    const agx::Knob *k = agx::find_knob(name);
+    return k ? int(*k) : agx::fail(AGX_ERR_BAD_SHAPE, "agx_get_tuning: unknown knob '%s'", name);
 }
 
 int64_t agx_conv_out_len(const agx_conv_desc *d) {

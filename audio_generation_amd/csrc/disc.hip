@@ -2,15 +2,9 @@
 // the STFT front end (as a polyphase conv on the MFMA kernels) and the loss reductions.
 // All are bandwidth- or latency-trivial next to the conv stacks; written for determinism
 // (fixed reduction orders, no atomics).
-#include "common.hpp"
+#include "conv_kernels.hpp"
 
 namespace agx {
-
-int launch_conv_mfma(const ConvPlan &p, const float *x, const float *wp, const float *bias,
-                     const float *res, float *y, hipStream_t st);
-int launch_conv_direct(const ConvPlan &p, const float *x, const float *wp, const float *bias,
-                       const float *res, float *y, hipStream_t st);
-bool conv_mfma_supported(const ConvPlan &p);
 
 __device__ __forceinline__ float block_sum_256(float v, float *sh4) {
     for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);

@@ -8,15 +8,10 @@
 // A window shorter than n_fft (the reference's short windows sit in n_fft = 512: training.py:51-78) is zero outside
 // [left, left + W): only the taps j0 .. j0 + Ke - 1 that meet it are kept (Ke = 4 instead of up to 64 for hop = W / 4);
 // the dropped products are exact zeros, so the sums do not change.
-#include "common.hpp"
+#include "conv_kernels.hpp"
 
 namespace agx {
 
-int launch_conv_mfma(const ConvPlan &p, const float *x, const float *wp, const float *bias, const float *res, float *y,
-                     hipStream_t st);
-int launch_conv_direct(const ConvPlan &p, const float *x, const float *wp, const float *bias, const float *res,
-                       float *y, hipStream_t st);
-bool conv_mfma_supported(const ConvPlan &p);
 // disc.hip: reflect-pad + polyphase transpose of `batch` rows (and its adjoint); ch_stride = channels allocated per item
 void launch_stft_prep(const float *x, float *xc, int batch, int L, int N, int H, int Ttau, int ch_stride, int tau_off,
                       hipStream_t st);

@@ -185,7 +185,9 @@ int agx_conv_bwd_weight_kernel_name(const agx_conv_desc *d, char *buf, size_t bu
 
 /* Name of the kernel family/tile variant agx_conv_forward would launch for this
  * descriptor (e.g. "conv_mfma<2,2,2,2,16>"), for profilers and bench.py; matches
- * the template arguments in the rocprofv3 kernel names.  Returns AGX_OK. */
+ * the template arguments in the rocprofv3 kernel names.  Launcher and name query read one selection, so a
+ * descriptor the launcher refuses (an impl value that does not exist) gets the launcher's error code and message
+ * here too -- as from the three name queries below. */
 int agx_conv_kernel_name(const agx_conv_desc *d, char *buf, size_t buf_len);
 
 /* Fused CausalResidualBlock1d + trailing activation (vae.py:113-117 wrapped by
