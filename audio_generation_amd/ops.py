@@ -951,3 +951,46 @@ def codes_unpack(stream: Tensor, n_codes: int, bits: int) -> Tensor:
     out = torch.empty(n_codes, dtype=torch.int64, device=stream.device)
     _lib.check(lib.agx_codes_unpack(_ptr(stream.contiguous()), n_codes, bits, _ptr(out), _stream()), "agx_codes_unpack")
     return out
+
+
+# ------------------------------------------------------------------ time folding (longform.py)
+def _fold_operand(x: Tensor, what: str) -> Tensor:
+    _need_gpu(x)
+    if x.dtype != torch.float32 or x.dim() != 3 or not x.is_contiguous():
+        raise AgxError(f"{what}: expected a contiguous float32 (B, C, L) tensor, got {x.dtype} {tuple(x.shape)}"
+                       f"{'' if x.is_contiguous() else ' (not contiguous)'}")
+    return x
+
+
+def time_fold(x: Tensor, windows: int, hop: int, width: int, src_off: int = 0) -> Tensor:
+    """(B, C, L) -> (B*windows, C, width): ``out[b*S + s, c, j] = x[b, c, src_off + s*hop + j]`` (overlapping windows)."""
+    lib = _lib.load()
+    x = _fold_operand(x, "time_fold")
+    b, c, length = x.shape
+    windows, hop, width, src_off = int(windows), int(hop), int(width), int(src_off)
+    if windows < 1 or width < 1 or hop < 0 or src_off < 0 or src_off + (windows - 1) * hop + width > length:
+        raise AgxError(f"time_fold: {windows} windows of {width} at hop {hop} from {src_off} leave the source (L = {length})")
+    out = torch.empty((b * windows, c, width), dtype=torch.float32, device=x.device)
+    _lib.check(lib.agx_time_fold(_ptr(x), _ptr(out), b, c, length, windows, hop, width, src_off, _stream()), "agx_time_fold")
+    return out
+
+
+def time_unfold(src: Tensor, out: Tensor, windows: int, keep: int, src_off: int = 0, dst_off: int = 0,
+                n_win: Optional[int] = None) -> Tensor:
+    """Crop-and-place into ``out`` (B, C, L'): ``out[b, c, dst_off + s*keep + j] = src[b*S + s, c, src_off + j]`` for
+    ``j < keep`` and ``s < n_win`` (default: all ``S = windows``).  Returns ``out``."""
+    lib = _lib.load()
+    src, out = _fold_operand(src, "time_unfold"), _fold_operand(out, "time_unfold")
+    windows, keep, src_off, dst_off = int(windows), int(keep), int(src_off), int(dst_off)
+    n_win = windows if n_win is None else int(n_win)
+    b, c, length = out.shape
+    if windows < 1 or src.shape[0] != b * windows or src.shape[1] != c or src.device != out.device:
+        raise AgxError(f"time_unfold: source {tuple(src.shape)} is not {windows} windows per clip of {tuple(out.shape)}")
+    width = src.shape[2]
+    if not (1 <= n_win <= windows) or keep < 1 or src_off < 0 or dst_off < 0 or src_off + keep > width \
+            or dst_off + n_win * keep > length:
+        raise AgxError(f"time_unfold: crop [{src_off}, {src_off + keep}) of width {width} x {n_win} windows placed at {dst_off} "
+                       f"does not fit (L = {length})")
+    _lib.check(lib.agx_time_unfold(_ptr(src), _ptr(out), b, c, windows, width, length, n_win, src_off, dst_off, keep, _stream()),
+               "agx_time_unfold")
+    return out

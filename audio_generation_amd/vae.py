@@ -518,6 +518,25 @@ class CausalVQAE(nn.Module):
         """Decoder half of ``forward`` on (B, D, T) quantised latents."""
         return self.rearrange_out(self._run_decoders(zq))
 
+    # -- time-folded long-clip inference (build-defined; longform.py) ----------------------------
+    def encode_long(self, x, segment_frames=None, codebook_n=None):
+        """``encode`` of long clips with the time axis folded into the batch: overlapping windows of ``segment_frames``
+        kept latent frames (plus the receptive-field halos) run as one batch through the encoder kernels, the RVQ
+        runs once on the stitched latents.  Same return contract as ``encode``; inference only.  A hop that leaves one
+        window IS the plain call, and so is ``None`` (folding bounds memory, it was measured not to be faster)."""
+        from . import longform
+        return longform.encode_long(self, x, segment_frames, codebook_n)
+
+    def decode_long(self, zq: Tensor, segment_frames=None) -> Tensor:
+        """``decode`` on (B, D, T) quantised latents, folded the same way with the decoder's halos."""
+        from . import longform
+        return longform.decode_long(self, zq, segment_frames)
+
+    def forward_long(self, x, segment_frames=None, codebook_n=None):
+        """``forward`` in eval mode through ``encode_long`` / ``decode_long`` -> (y, commit_loss, index)."""
+        from . import longform
+        return longform.forward_long(self, x, segment_frames, codebook_n)
+
     def sample(self, length=225, device="cuda", normal_var=5e3, n_iters=12):
         """vae.py:324-345: random codes -> dequantise -> decode."""
         self.to(device)

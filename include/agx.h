@@ -566,6 +566,17 @@ int64_t agx_codes_packed_bytes(int64_t n_codes, int32_t bits);
 int agx_codes_pack(const int64_t *codes, int64_t n_codes, int32_t bits, uint8_t *out, void *stream);
 int agx_codes_unpack(const uint8_t *in, int64_t n_codes, int32_t bits, int64_t *codes, void *stream);
 
+/* Time folding for long-clip inference (fp32, contiguous tensors; pure copies, stream-ordered, no synchronisation).
+ * fold:   (B, C, L) -> (B*S, C, W) overlapping windows,  dst[b*S + s, c, j] = src[b, c, src_off + s*hop + j],  j < W;
+ *         refused unless src_off + (S-1)*hop + W <= L.
+ * unfold: crop-and-place,  dst[b, c, dst_off + s*keep + j] = src[b*S + s, c, src_off + j],  j < keep, s < n_win <= S,
+ *         src (B*S, C, W), dst (B, C, dst_length); refused unless src_off + keep <= W and dst_off + n_win*keep <= dst_length.
+ *         n_win = 1 places window 0 alone (its longer contribution at the start of a clip), S = 1 a separately run tail. */
+int agx_time_fold(const float *src, float *dst, int32_t batch, int32_t channels, int64_t length, int32_t windows, int64_t hop,
+                  int64_t width, int64_t src_off, void *stream);
+int agx_time_unfold(const float *src, float *dst, int32_t batch, int32_t channels, int32_t windows, int64_t width, int64_t dst_length,
+                    int32_t n_win, int64_t src_off, int64_t dst_off, int64_t keep, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
