@@ -1292,10 +1292,234 @@ __global__ __launch_bounds__(256) void prepad_dy_kernel(const float *__restrict_
     dyp[e] = (t < Hout && cc < Wout) ? v : 0.f;
 }
 
-static int bw2d_geometry(const agx_conv2d_desc *d, Bw2dGeom *g, int *cfg, int *bm, dim3 *grid, size_t *lds) {
+// ---- host side: what the two ops share ----------------------------------------------------------------------------
+// One row per kernel instantiation an op can launch.  A row is made by wgrad_variant<> from the template arguments of its
+// kernel, so the printed name, the tile, the LDS size and the kernel that is launched cannot disagree; the geometry functions
+// pick a row, the launchers call row.launch and the name queries print row.name and row.cfg.
+enum { WG_STAGED, WG_DIRECT, WG_SHARED };   // operands staged through LDS / wave-private LDS-DMA buffers / a shared DMA ring
+template <class Args>
+struct WgradVariant {
+    const char *name;    // "<kernel><template arguments>"
+    int cfg;             // the tile's public number ("cfg=" of the name queries): 0..2 staged, 10..17 direct / shared
+    int kind, alt;       // WG_*; fifth template argument (PREC, or PHASES of the 1-D direct kernel)
+    int bm, bn, wk;      // tile rows x columns; waves of a workgroup that take different contraction slices
+    size_t lds;          // dynamic LDS of the direct / shared kernels (0 = staged: from the geometry)
+    int (*launch)(const Args &);
+};
+template <class Args, int MW, int NW, int WM, int WN, int ALT = 0>
+constexpr WgradVariant<Args> wgrad_variant(const char *name, int cfg, int kind, int (*launch)(const Args &)) {
+    return {name, cfg, kind, ALT, 32 * MW * WM, 32 * NW * WN, 4 / (WM * WN),
+            // 4 waves x (MW + NW) operand blocks of 4 KB / two slots of (BM + BN) / 32 blocks
+            kind == WG_DIRECT ? size_t(4) * (MW + NW) * 4096 : kind == WG_SHARED ? size_t(2) * (MW * WM + NW * WN) * 4096 : 0, launch};
+}
+// The row of (cfg, kind) with the fifth template argument `alt`, or its plain form where the kernel has no such instantiation.
+template <class Args, int N>
+const WgradVariant<Args> *wgrad_find(const WgradVariant<Args> (&rows)[N], int cfg, int kind, int alt) {
+    const WgradVariant<Args> *plain = nullptr;
+    for (const WgradVariant<Args> &r : rows) {
+        if (r.cfg != cfg || r.kind != kind) continue;
+        if (r.alt == alt) return &r;
+        if (r.alt == 0) plain = &r;
+    }
+    return plain;
+}
+// Compile-time checks of a table: a cfg number means one tile (the geometry sizes the grid from it before the family and the
+// arithmetic are known), and the names are spelled as the queries have always printed them (no blanks).
+template <class Args, int N>
+constexpr bool wgrad_table_ok(const WgradVariant<Args> (&rows)[N]) {
+    for (int i = 0; i < N; ++i) {
+        for (int j = 0; j < i; ++j)
+            if (rows[i].cfg == rows[j].cfg && (rows[i].bm != rows[j].bm || rows[i].bn != rows[j].bn || rows[i].wk != rows[j].wk)) return false;
+        for (const char *c = rows[i].name; *c; ++c)
+            if (*c == ' ') return false;
+    }
+    return true;
+}
+template <class Args, int N>
+constexpr bool wgrad_tile_is(const WgradVariant<Args> (&rows)[N], int cfg, int bm, int bn, int wk) {
+    for (int i = 0; i < N; ++i)
+        if (rows[i].cfg == cfg) return rows[i].bm == bm && rows[i].bn == bn && rows[i].wk == wk;
+    return false;
+}
+
+// Launch of one instantiation: its dynamic-LDS limit is raised once per device (`once` is per instantiation).
+template <auto Kern, class... A>
+int wgrad_launch(int lds_limit, const char *what, dim3 grid, size_t lds, hipStream_t st, A... args) {
+    static DeviceOnce once;
+    const int rc = prepare_kernel(reinterpret_cast<const void *>(Kern), once, lds_limit, nullptr, what);
+    if (rc != AGX_OK) return rc;
+    hipLaunchKernelGGL(Kern, grid, dim3(256), lds, st, args...);
+    return AGX_OK;
+}
+
+// Tile of the direct kernels for M rows x NK columns (the 2-D op adds a 96-column rung and the shared kernel's tiles):
+// the largest that M fills, narrow where NK is small -- the waves a narrow tile leaves over split the contraction (wk).
+inline int wgrad_direct_cfg(int M, int NK) {
+    if (M > 64) return 10;                    // 128 x 128
+    if (M > 32) return NK > 64 ? 11 : 12;     // 64 x 128 (wk 2) : 64 x 64 (wk 4)
+    return NK > 32 ? 13 : 14;                 // 32 x 256 : 32 x 32 (wk 4)
+}
+
+// Contraction slices (gridDim.z): `target` workgroups over `tiles` tiles, no more than the items give wk waves each, 1 .. 65535
+inline int wgrad_slices(int target, int tiles, int64_t items, int wk = 1) {
+    int64_t ns = ceil_div(target, tiles);
+    if (ns * wk > items) ns = ceil_div64(items, wk);
+    if (ns < 1) ns = 1;
+    if (ns > 65535) ns = 65535;
+    return int(ns);
+}
+
+// Operand copies the direct / shared kernels read instead of x or dy ("op=" of the name queries)
+enum { WG_COPY_NONE, WG_COPY_PHASE_X, WG_COPY_PHASE_DY, WG_COPY_PREPAD, WG_COPY_DEINTERLEAVE };
+inline const char *wgrad_copy_name(int copy) {
+    static const char *const names[] = {"none", "phase_x", "phase_dy", "prepad", "deinterleave"};
+    return names[copy];
+}
+
+// ---- host side of the 1-D op ---------------------------------------------------------------------------------------------------
+struct Bw1Args {   // what a launch passes on; p: the plan as the kernel sees it (phase-split operands: see the direct kernel's header)
+    ConvPlan p; int span, n_chan, n_slices, sp; const float *x, *dy; float *part, *bias_part; dim3 grid; size_t lds; hipStream_t st;
+};
+template <auto Kern>
+int bw1_staged(const Bw1Args &a) {
+    return wgrad_launch<Kern>(160 * 1024, "agx_conv_bwd_weight", a.grid, a.lds, a.st, a.p, a.span, a.n_chan, a.n_slices, a.x, a.dy,
+                              a.part, a.bias_part);
+}
+template <auto Kern>
+int bw1_direct(const Bw1Args &a) {
+    return wgrad_launch<Kern>(64 * 1024, "agx_conv_bwd_weight", a.grid, a.lds, a.st, a.p, a.sp, a.x, a.dy, a.part, a.bias_part);
+}
+
+// The instantiations agx_conv_bwd_weight can launch (template arguments without blanks: they are printed as written)
+#define BW1(CFG, KIND, THUNK, KERNEL, ...) \
+    wgrad_variant<Bw1Args, __VA_ARGS__>(#KERNEL "<" #__VA_ARGS__ ">", CFG, KIND, THUNK<KERNEL##_kernel<__VA_ARGS__>>)
+static constexpr WgradVariant<Bw1Args> bw1_variants[] = {
+    BW1(10, WG_DIRECT, bw1_direct, conv_bwd_weight_direct, 2,2,2,2), BW1(11, WG_DIRECT, bw1_direct, conv_bwd_weight_direct, 2,2,1,2),
+    BW1(12, WG_DIRECT, bw1_direct, conv_bwd_weight_direct, 2,2,1,1), BW1(13, WG_DIRECT, bw1_direct, conv_bwd_weight_direct, 1,2,1,4),
+    BW1(14, WG_DIRECT, bw1_direct, conv_bwd_weight_direct, 1,1,1,1),
+    BW1(10, WG_DIRECT, bw1_direct, conv_bwd_weight_direct, 2,2,2,2,true), BW1(11, WG_DIRECT, bw1_direct, conv_bwd_weight_direct, 2,2,1,2,true),
+    BW1(12, WG_DIRECT, bw1_direct, conv_bwd_weight_direct, 2,2,1,1,true), BW1(13, WG_DIRECT, bw1_direct, conv_bwd_weight_direct, 1,2,1,4,true),
+    BW1(14, WG_DIRECT, bw1_direct, conv_bwd_weight_direct, 1,1,1,1,true),
+    BW1(0, WG_STAGED, bw1_staged, conv_bwd_weight, 2,2,2,2), BW1(1, WG_STAGED, bw1_staged, conv_bwd_weight, 1,2,2,2),
+    BW1(2, WG_STAGED, bw1_staged, conv_bwd_weight, 1,1,1,4),
+    BW1(0, WG_STAGED, bw1_staged, conv_bwd_weight, 2,2,2,2,1), BW1(1, WG_STAGED, bw1_staged, conv_bwd_weight, 1,2,2,2,1),
+    BW1(2, WG_STAGED, bw1_staged, conv_bwd_weight, 1,1,1,4,1)};
+#undef BW1
+static_assert(wgrad_table_ok(bw1_variants), "one tile per cfg, names without blanks");
+// the tiles wgrad_direct_cfg and the staged row ladder below stand for
+static_assert(wgrad_tile_is(bw1_variants, 10, 128, 128, 1) && wgrad_tile_is(bw1_variants, 11, 64, 128, 2) &&
+              wgrad_tile_is(bw1_variants, 12, 64, 64, 4) && wgrad_tile_is(bw1_variants, 13, 32, 256, 1) &&
+              wgrad_tile_is(bw1_variants, 14, 32, 32, 4) && wgrad_tile_is(bw1_variants, 0, 128, 128, 1) &&
+              wgrad_tile_is(bw1_variants, 1, 64, 128, 1) && wgrad_tile_is(bw1_variants, 2, 32, 128, 1), "cfg <-> tile");
+
+struct BwGeom {
+    const WgradVariant<Bw1Args> *v;
+    int span, n_chan;
+    int n_slices;    // partial tiles in the workspace (the wk waves of a workgroup are added in LDS)
+    dim3 grid;
+    size_t lds;
+    int64_t items;   // 32-position chunks (direct kernel) or staged tiles of BW_T positions
+    int copy;        // WG_COPY_*: the operand the direct kernel reads through a phase-split copy
+};
+
+static BwGeom bw_geometry(const ConvPlan &p) {
+    BwGeom g;
+    // (also for AGX_IMPL_MFMA_BF16X3 descriptors: fp32 on this kernel is faster than bf16x3 on the staged one, and exact)
+    // dw_direct: 1 = the k = 1 layers, 2 = + every stride-1 layer, 3 (default) = + strided / transposed layers through a
+    // phase-split copy of x / dy
+    const int dd = tuning().dw_direct;
+    const bool direct = p.G == 1 && ((p.s == 1 && p.q == 1 && (dd >= 2 || (dd == 1 && p.J == 1))) ||
+                                     (dd >= 3 && (p.s == 1 || p.q == 1) && p.s <= 16 && p.q <= 16));
+    const int NK = p.Cin * p.J;
+    int target;
+    if (direct) {   // conv_bwd_weight_direct_kernel; strided: x as a phase-split copy
+        g.v = wgrad_find(bw1_variants, wgrad_direct_cfg(p.M, NK), WG_DIRECT, p.s > 1);
+        g.copy = p.s > 1 ? WG_COPY_PHASE_X : (p.q > 1 ? WG_COPY_PHASE_DY : WG_COPY_NONE);
+        g.items = int64_t(p.B) * ceil_div(p.Lt, 32);
+        g.span = g.n_chan = 0;
+        g.lds = g.v->lds;
+        target = tuning().dw1_wgs;
+    } else {
+        g.v = wgrad_find(bw1_variants, p.M >= 128 ? 0 : (p.M >= 64 ? 1 : 2), WG_STAGED, p.prec);
+        g.copy = WG_COPY_NONE;
+        g.items = int64_t(p.B) * ceil_div(p.Lt, BW_T);
+        g.span = (BW_T - 1) * p.s + (p.J - 1) * p.d + 1;
+        g.n_chan = 127 / p.J + 2;  // channels a 128-column tile of n = ci*J + j can touch
+        g.lds = (size_t(g.v->bm) * BW_TS + size_t(g.n_chan) * g.span) * sizeof(float);
+        target = 768;              // ~3 workgroups per CU in total
+    }
+    const int nt = ceil_div(NK, g.v->bn), mt = ceil_div(p.M, g.v->bm);
+    g.n_slices = wgrad_slices(target, nt * mt, g.items, g.v->wk);
+    g.grid = dim3(nt, mt, g.n_slices);
+    return g;
+}
+
+// The workspace, in floats from its start: slices of dWp (at 0), the reduced dWp, slices of the bias row sums, the reduced
+// row sums, then -- behind 64 floats of slack -- the phase-split copy of x or dy.  agx_conv_bwd_weight_workspace_bytes
+// returns `total`, the launcher takes its pointers from the same offsets.
+struct BwLayout {
+    size_t dwp, bias_part, rowsum, copy, total;
+};
+static BwLayout bw_layout(const ConvPlan &p, const BwGeom &g) {
+    BwLayout l;
+    const size_t nw = size_t(p.Cin) * p.J * p.M, ns = size_t(g.n_slices);
+    l.dwp = ns * nw;
+    l.bias_part = l.dwp + nw;
+    l.rowsum = l.bias_part + ns * p.M;
+    l.total = l.rowsum + p.M;
+    l.copy = l.total + 64;
+    if (g.copy == WG_COPY_PHASE_X) l.total += size_t(p.B) * p.Cin * p.s * ceil_div(p.Lin, p.s) + 128;
+    if (g.copy == WG_COPY_PHASE_DY) l.total += size_t(p.B) * p.M * p.Lt + 128;
+    return l;
+}
+
+// ---- host side of the 2-D op ---------------------------------------------------------------------------------------------------
+struct Bw2dArgs {   // what a launch passes on
+    Bw2dGeom g; const float *x, *dy; float *part, *bias_part; dim3 grid; size_t lds; hipStream_t st;
+};
+template <auto Kern, int LdsLimit>
+int bw2_launch(const Bw2dArgs &a) {
+    return wgrad_launch<Kern>(LdsLimit, "agx_conv2d_bwd_weight", a.grid, a.lds, a.st, a.g, a.x, a.dy, a.part, a.bias_part);
+}
+
+// The instantiations agx_conv2d_bwd_weight can launch (template arguments without blanks: they are printed as written)
+#define BW2(CFG, KIND, KERNEL, ...)                                                           \
+    wgrad_variant<Bw2dArgs, __VA_ARGS__>(#KERNEL "<" #__VA_ARGS__ ">", CFG, KIND,             \
+                                         bw2_launch<KERNEL##_kernel<__VA_ARGS__>, (KIND == WG_DIRECT ? 64 : 160) * 1024>)
+static constexpr WgradVariant<Bw2dArgs> bw2_variants[] = {
+    BW2(10, WG_SHARED, conv2d_bwd_weight_shared, 2,2,2,2), BW2(10, WG_SHARED, conv2d_bwd_weight_shared, 2,2,2,2,1),
+    BW2(15, WG_SHARED, conv2d_bwd_weight_shared, 2,1,1,4), BW2(15, WG_SHARED, conv2d_bwd_weight_shared, 2,1,1,4,1),
+    BW2(16, WG_SHARED, conv2d_bwd_weight_shared, 1,2,1,4),
+    BW2(10, WG_DIRECT, conv2d_bwd_weight_direct, 2,2,2,2), BW2(11, WG_DIRECT, conv2d_bwd_weight_direct, 2,2,1,2),
+    BW2(12, WG_DIRECT, conv2d_bwd_weight_direct, 2,2,1,1), BW2(13, WG_DIRECT, conv2d_bwd_weight_direct, 1,2,1,4),
+    BW2(17, WG_DIRECT, conv2d_bwd_weight_direct, 1,3,1,1), BW2(14, WG_DIRECT, conv2d_bwd_weight_direct, 1,1,1,1),
+    BW2(0, WG_STAGED, conv2d_bwd_weight, 2,2,2,2), BW2(0, WG_STAGED, conv2d_bwd_weight, 2,2,2,2,1),
+    BW2(1, WG_STAGED, conv2d_bwd_weight, 1,2,2,2), BW2(1, WG_STAGED, conv2d_bwd_weight, 1,2,2,2,1),
+    BW2(2, WG_STAGED, conv2d_bwd_weight, 1,1,1,4), BW2(2, WG_STAGED, conv2d_bwd_weight, 1,1,1,4,1)};
+#undef BW2
+static_assert(wgrad_table_ok(bw2_variants), "one tile per cfg, names without blanks");
+// the tiles wgrad_direct_cfg and the substitutions of bw2d_geometry stand for
+static_assert(wgrad_tile_is(bw2_variants, 10, 128, 128, 1) && wgrad_tile_is(bw2_variants, 11, 64, 128, 2) &&
+              wgrad_tile_is(bw2_variants, 12, 64, 64, 4) && wgrad_tile_is(bw2_variants, 13, 32, 256, 1) &&
+              wgrad_tile_is(bw2_variants, 14, 32, 32, 4) && wgrad_tile_is(bw2_variants, 15, 64, 128, 1) &&
+              wgrad_tile_is(bw2_variants, 16, 32, 256, 1) && wgrad_tile_is(bw2_variants, 17, 32, 96, 4) &&
+              wgrad_tile_is(bw2_variants, 0, 128, 128, 1) && wgrad_tile_is(bw2_variants, 1, 64, 128, 1) &&
+              wgrad_tile_is(bw2_variants, 2, 32, 128, 1), "cfg <-> tile");
+
+struct Bw2dPlan {
+    Bw2dGeom g;      // what the kernels read
+    const WgradVariant<Bw2dArgs> *v;
+    dim3 grid;
+    size_t lds;
+    int64_t items;   // 32-position chunks (direct / shared kernels) or staged tiles of R x WF positions
+    int copy;        // WG_COPY_*: operand copies the direct / shared kernel reads
+};
+
+static int bw2d_geometry(const agx_conv2d_desc *d, Bw2dPlan *o) {
     ConvPlan f;
     int rc = lower_conv2d(d, &f);
     if (rc != AGX_OK) return rc;
+    Bw2dGeom *g = &o->g;
     g->B = d->batch; g->Cin = d->c_in; g->Cout = d->c_out; g->Hin = d->h_in; g->Win = d->w_in;
     g->Hout = f.Tout; g->Wout = f.Lout; g->kh = d->kh; g->kw = d->kw; g->sh = d->stride_h; g->sw = d->stride_w;
     g->ph = d->pad_h; g->pw = d->pad_w;
@@ -1305,23 +1529,15 @@ static int bw2d_geometry(const agx_conv2d_desc *d, Bw2dGeom *g, int *cfg, int *b
     g->RH = (g->R - 1) * g->sh + g->kh;
     g->SW = (g->WF - 1) * g->sw + g->kw;
     g->span = g->RH * g->SW;
-    const int KK = g->kh * g->kw;
+    const int KK = g->kh * g->kw, NK = g->Cin * KK;
     g->n_chan = 127 / KK + 2;
     g->prec = d->impl == AGX_IMPL_MFMA_BF16X3 ? 1 : 0;
     g->xcd = tuning().dw_xcd;
     g->prepad = 0; g->pp_lpr = 0; g->pp_hwi = 0; g->pp_amin = 0; g->pp_bmin = 0;
-    g->wk = 1;
-    *cfg = g->Cout >= 128 ? 0 : (g->Cout >= 64 ? 1 : 2);
-    *bm = *cfg == 0 ? 128 : (*cfg == 1 ? 64 : 32);
-    const int nt = ceil_div(g->Cin * KK, 128), mt = ceil_div(g->Cout, *bm);
-    const int64_t items = int64_t(g->B) * ceil_div(g->Hout, g->R) * ceil_div(g->Wout, g->WF);
-    int64_t ns = ceil_div(tuning().dw_wgs, nt * mt);   // default 1536: +5..15 % over 768 on the 3x3 layers
-    if (ns > items) ns = items;
-    if (ns < 1) ns = 1;
-    if (ns > 65535) ns = 65535;
-    g->n_slices = int(ns);
-    *grid = dim3(nt, mt, g->n_slices);
-    *lds = (size_t(*bm) * BW_TS + size_t(g->n_chan) * g->span + BW_T) * sizeof(float);
+    // the staged kernel, unless one of the two forms below applies
+    int cfg = g->Cout >= 128 ? 0 : (g->Cout >= 64 ? 1 : 2), kind = WG_STAGED;
+    o->items = int64_t(g->B) * ceil_div(g->Hout, g->R) * ceil_div(g->Wout, g->WF);
+    o->copy = WG_COPY_NONE;
     // conv2d_bwd_weight_direct_kernel: stride-1 "same" layers whose rows are whole 32-column items
     // (also for AGX_IMPL_MFMA_BF16X3 descriptors: fp32 on this kernel is faster than bf16x3 on the staged one, and exact)
     // or column-strided ones whose output row is as wide as a column-phase plane of x
@@ -1330,34 +1546,23 @@ static int bw2d_geometry(const agx_conv2d_desc *d, Bw2dGeom *g, int *cfg, int *b
     const bool same = g->sh == 1 && g->sw == 1 && g->Hout == g->Hin && g->Wout == g->Win;
     const bool strided = tuning().dw2_direct >= 2 && g->sw > 1 && g->sw <= 4 && g->Win % g->sw == 0 && g->Wout == g->Wp &&
                          int64_t(g->sw) * g->B * g->Cin * g->Hin * g->Wp < (int64_t(1) << 31);   // 32-bit plane offsets
+    const int shared = tuning().dw2_shared;
     if (tuning().dw2_direct && (same || strided) &&
         g->Wout % 32 == 0 && -a_lo <= 4 && a_hi <= 4 && g->ph < 32 && g->kh - g->ph < 32 &&
-        (g->Cout > 32 || g->Cin * KK <= 32 || g->Cin * KK >= 192)) {   // (32 rows x 98 columns, the 7x7 first conv: the 256-wide tile loses to the staged kernel)
-        const int NK = g->Cin * KK;
-        int dbm, dbn, wk;
-        if (g->Cout > 64)      { *cfg = 10; dbm = 128; dbn = 128; wk = 1; }   // <2,2,2,2>
-        else if (g->Cout > 32) { if (NK > 64) { *cfg = 11; dbm = 64; dbn = 128; wk = 2; }    // <2,2,1,2>
-                                 else         { *cfg = 12; dbm = 64; dbn = 64; wk = 4; } }   // <2,2,1,1>
-        else                   { if (NK > 32) { *cfg = 13; dbm = 32; dbn = 256; wk = 1; }    // <1,2,1,4>
-                                 else         { *cfg = 14; dbm = 32; dbn = 32; wk = 4; } }   // <1,1,1,1>
+        (g->Cout > 32 || NK <= 32 || NK >= 192)) {   // (32 rows x 98 columns, the 7x7 first conv: the 256-wide tile loses to the staged kernel)
+        cfg = wgrad_direct_cfg(g->Cout, NK);
+        kind = WG_DIRECT;
         // 32 rows: 96-column tiles (the four waves split the contraction) when they waste fewer columns than 256-column
         // ones -- 32 -> 32 3x3: NK = 288 = 3 x 96, against 2 x 256
-        if (*cfg == 13 && ceil_div(NK, 96) * 96 < ceil_div(NK, 256) * 256) { *cfg = 17; dbm = 32; dbn = 96; wk = 4; }   // <1,3,1,1>
+        if (cfg == 13 && ceil_div(NK, 96) * 96 < ceil_div(NK, 256) * 256) cfg = 17;
         // (64 rows x 96 columns, <2,3,1,1>, for NK = 576 = 6 x 96: 73.8 TFLOP/s against 81 on 5 tiles of 128 -- not kept)
-        if (tuning().dw2_shared >= 2 && *cfg == 11) { *cfg = 15; dbm = 64; dbn = 128; wk = 1; }    // shared <2,1,1,4>
-        if (tuning().dw2_shared >= 2 && *cfg == 13) { *cfg = 16; dbm = 32; dbn = 256; wk = 1; }    // shared <1,2,1,4>
-        const int dnt = ceil_div(NK, dbn), dmt = ceil_div(g->Cout, dbm);
-        const int64_t ditems = int64_t(g->B) * g->Hout * (g->Wout / 32);
-        int64_t gz = ceil_div(tuning().dw_wgs, dnt * dmt);
-        if (gz * wk > ditems) gz = ceil_div64(ditems, wk);
-        if (gz < 1) gz = 1;
-        if (gz > 65535) gz = 65535;
-        g->n_slices = int(gz);
-        g->wk = wk;
-        *bm = dbm;
-        *grid = dim3(dnt, dmt, g->n_slices);
-        *lds = 0;
-    } else if (tuning().dw2_prepad && tuning().dw2_shared && g->Wout < 32 && g->Wout >= 4 && g->Cout >= 64 && g->sh <= 2 && g->sw <= 2 &&
+        // the shared kernel where it has the tile: 128 rows, and with dw2_shared >= 2 the 64- and 32-row tiles it replaces
+        if (shared >= 2 && cfg == 11) cfg = 15;
+        if (shared >= 2 && cfg == 13) cfg = 16;
+        if (cfg == 15 || cfg == 16 || (cfg == 10 && shared)) kind = WG_SHARED;
+        o->items = int64_t(g->B) * g->Hout * (g->Wout / 32);
+        if (g->sw > 1) o->copy = WG_COPY_DEINTERLEAVE;   // x through its sw column-phase planes
+    } else if (tuning().dw2_prepad && shared && g->Wout < 32 && g->Wout >= 4 && g->Cout >= 64 && g->sh <= 2 && g->sw <= 2 &&
                g->kh <= 8 && g->kw <= 8) {
         // narrow maps: the shared kernel on zero-padded, phase-split, flattened copies of x and dy (Bw2dGeom::prepad)
         const int amin = -ceil_div(g->ph, g->sh), amax = (g->kh - 1 - g->ph) >= 0 ? (g->kh - 1 - g->ph) / g->sh : -ceil_div(g->ph - g->kh + 1, g->sh);
@@ -1368,115 +1573,45 @@ static int bw2d_geometry(const agx_conv2d_desc *d, Bw2dGeom *g, int *cfg, int *b
         const bool fits = int64_t(g->sh) * g->sw * g->B * g->Cin * hwi < (int64_t(1) << 30) && int64_t(g->B) * g->Cout * lpr < (int64_t(1) << 30);
         if (fits && lpr * 10 <= int64_t(g->Hout) * g->Wout * 13) {      // padded positions <= 1.3 x the real ones: 8 columns and more
                                                                          // (measured: 16 columns 64 -> 79 TFLOP/s, 8 columns 69 -> 76, 4 columns 67 -> 61)
-            const int NK = g->Cin * KK;
-            int dbm, dbn;
-            if (g->Cout > 64) { *cfg = 10; dbm = 128; dbn = 128; }
-            else              { *cfg = 15; dbm = 64; dbn = 128; }
+            cfg = g->Cout > 64 ? 10 : 15;
+            kind = WG_SHARED;
             g->prepad = 1; g->Wp = Wpp; g->pp_lpr = int(lpr); g->pp_hwi = int(hwi); g->pp_amin = amin; g->pp_bmin = bmin;
-            const int dnt = ceil_div(NK, dbn), dmt = ceil_div(g->Cout, dbm);
-            const int64_t ditems = int64_t(g->B) * (lpr / 32);
-            int64_t gz = ceil_div(tuning().dw_wgs, dnt * dmt);
-            if (gz > ditems) gz = ditems;
-            if (gz < 1) gz = 1;
-            if (gz > 65535) gz = 65535;
-            g->n_slices = int(gz);
-            *bm = dbm;
-            *grid = dim3(dnt, dmt, g->n_slices);
-            *lds = 0;
+            o->items = int64_t(g->B) * (lpr / 32);
+            o->copy = WG_COPY_PREPAD;
         }
     }
+    // bf16x3 descriptors: the staged kernel's bf16x3 form, the shared kernel's with dw2_bf; the direct kernel is fp32 only
+    o->v = wgrad_find(bw2_variants, cfg, kind, kind == WG_STAGED ? g->prec : (g->prec == 1 && tuning().dw2_bf));
+    const int nt = ceil_div(NK, o->v->bn), mt = ceil_div(g->Cout, o->v->bm);
+    g->wk = o->v->wk;
+    g->n_slices = wgrad_slices(tuning().dw_wgs, nt * mt, o->items, g->wk);   // default 1536: +5..15 % over 768 on the 3x3 layers
+    o->grid = dim3(nt, mt, g->n_slices);
+    o->lds = kind == WG_STAGED ? (size_t(o->v->bm) * BW_TS + size_t(g->n_chan) * g->span + BW_T) * sizeof(float) : o->v->lds;
     return AGX_OK;
 }
 
-// The instantiation agx_conv2d_bwd_weight launches (as bw1_names / bw1_kernel below for the 1-D op)
-static const char *const bw2_names[] = {
-    "conv2d_bwd_weight_shared<2,2,2,2>", "conv2d_bwd_weight_shared<2,2,2,2,1>", "conv2d_bwd_weight_shared<2,1,1,4>",
-    "conv2d_bwd_weight_shared<2,1,1,4,1>", "conv2d_bwd_weight_shared<1,2,1,4>",
-    "conv2d_bwd_weight_direct<2,2,2,2>", "conv2d_bwd_weight_direct<2,2,1,2>", "conv2d_bwd_weight_direct<2,2,1,1>",
-    "conv2d_bwd_weight_direct<1,2,1,4>", "conv2d_bwd_weight_direct<1,3,1,1>", "conv2d_bwd_weight_direct<1,1,1,1>",
-    "conv2d_bwd_weight<2,2,2,2>", "conv2d_bwd_weight<1,2,2,2>", "conv2d_bwd_weight<1,1,1,4>",
-    "conv2d_bwd_weight<2,2,2,2,1>", "conv2d_bwd_weight<1,2,2,2,1>", "conv2d_bwd_weight<1,1,1,4,1>"};
-
-static int bw2_kernel(const Bw2dGeom &g, int cfg) {
-    if (cfg >= 10) {
-        const bool bf = g.prec == 1 && tuning().dw2_bf;   // bf16x3 descriptors: the shared kernel's bf16x3 contraction
-        if (cfg == 10 && tuning().dw2_shared) return bf ? 1 : 0;
-        if (cfg == 15) return bf ? 3 : 2;
-        if (cfg == 16) return 4;
-        return cfg == 10 ? 5 : cfg == 11 ? 6 : cfg == 12 ? 7 : cfg == 13 ? 8 : cfg == 17 ? 9 : 10;
-    }
-    return 11 + (g.prec ? 3 : 0) + cfg;                    // staged kernel, cfg 0..2
-}
-
-struct BwGeom {
-    int cfg;  // 0: 128x128 tile, 1: 64x128, 2: 32x128;  direct kernel: 10..14 (see bw_geometry)
-    int bm, span, n_chan, n_slices;
-    int wk;   // waves of a workgroup that take different contraction slices (direct kernel; 1 otherwise)
-    bool direct;
-    dim3 grid;
-    size_t lds;
+// The workspace, in floats from its start: slices of dWp (at 0), the reduced dWp, slices of the bias row sums, M floats
+// nothing uses any more (they stay: callers size their buffers by the byte count), the per-row <G, W>, then -- behind 64
+// floats of slack -- the operand copies.  agx_conv2d_bwd_weight_workspace_bytes returns `total`, the launcher takes its
+// pointers from the same offsets (the padded planes start at the next 16-byte boundary: their slack covers that).
+struct Bw2dLayout {
+    size_t dwp, bias_part, rowdot, copy, total;
+    size_t nx, ny;   // WG_COPY_PREPAD: floats of the padded copies of x and dy
 };
-
-static BwGeom bw_geometry(const ConvPlan &p, bool bf16x3) {
-    BwGeom g;
-    // (also for AGX_IMPL_MFMA_BF16X3 descriptors: fp32 on this kernel is faster than bf16x3 on the staged one, and exact)
-    // dw_direct: 1 = the k = 1 layers, 2 = + every stride-1 layer, 3 (default) = + strided / transposed layers through a
-    // phase-split copy of x / dy
-    const int dd = tuning().dw_direct;
-    g.direct = p.G == 1 && ((p.s == 1 && p.q == 1 && (dd >= 2 || (dd == 1 && p.J == 1))) ||
-                            (dd >= 3 && (p.s == 1 || p.q == 1) && p.s <= 16 && p.q <= 16));
-    (void)bf16x3;
-    if (g.direct) {   // conv_bwd_weight_direct_kernel: tile and the waves left for the contraction (WK)
-        const int NK = p.Cin * p.J;
-        int bn, wk;
-        if (p.M > 64)      { g.cfg = 10; g.bm = 128; bn = 128; wk = 1; }   // <2,2,2,2>
-        else if (p.M > 32) { if (NK > 64) { g.cfg = 11; g.bm = 64; bn = 128; wk = 2; }    // <2,2,1,2>
-                             else         { g.cfg = 12; g.bm = 64; bn = 64; wk = 4; } }   // <2,2,1,1>
-        else               { if (NK > 32) { g.cfg = 13; g.bm = 32; bn = 256; wk = 1; }    // <1,2,1,4>
-                             else         { g.cfg = 14; g.bm = 32; bn = 32; wk = 4; } }   // <1,1,1,1>
-        const int nt = ceil_div(NK, bn), mt = ceil_div(p.M, g.bm);
-        const int items = p.B * ceil_div(p.Lt, 32);
-        int gz = ceil_div(tuning().dw1_wgs, nt * mt);
-        if (gz * wk > items) gz = ceil_div(items, wk);
-        if (gz < 1) gz = 1;
-        if (gz > 65535) gz = 65535;
-        g.n_slices = gz;     // partial tiles in the workspace (the WK waves of a workgroup are added in LDS)
-        g.wk = wk;
-        g.grid = dim3(nt, mt, gz);
-        g.span = g.n_chan = 0;
-        g.lds = 0;
-        return g;
-    }
-    g.cfg = p.M >= 128 ? 0 : (p.M >= 64 ? 1 : 2);
-    g.bm = g.cfg == 0 ? 128 : (g.cfg == 1 ? 64 : 32);
-    g.span = (BW_T - 1) * p.s + (p.J - 1) * p.d + 1;
-    g.n_chan = 127 / p.J + 2;  // channels a 128-column tile of n = ci*J + j can touch
-    const int nt = ceil_div(p.Cin * p.J, 128), mt = ceil_div(p.M, g.bm);
-    const int items = p.B * ceil_div(p.Lt, BW_T);
-    int ns = ceil_div(768, nt * mt);  // ~3 workgroups per CU in total
-    if (ns > items) ns = items;
-    if (ns < 1) ns = 1;
-    if (ns > 65535) ns = 65535;
-    g.n_slices = ns;
-    g.wk = 1;
-    g.grid = dim3(nt, mt, ns);
-    g.lds = (size_t(g.bm) * BW_TS + size_t(g.n_chan) * g.span) * sizeof(float);
-    return g;
-}
-
-// The instantiation agx_conv_bwd_weight launches: its launcher switches on this index and
-// agx_conv_bwd_weight_kernel_name prints bw1_names[] of it, so the name is the selection.
-static const char *const bw1_names[] = {
-    "conv_bwd_weight_direct<2,2,2,2>", "conv_bwd_weight_direct<2,2,1,2>", "conv_bwd_weight_direct<2,2,1,1>",
-    "conv_bwd_weight_direct<1,2,1,4>", "conv_bwd_weight_direct<1,1,1,1>",
-    "conv_bwd_weight_direct<2,2,2,2,true>", "conv_bwd_weight_direct<2,2,1,2,true>", "conv_bwd_weight_direct<2,2,1,1,true>",
-    "conv_bwd_weight_direct<1,2,1,4,true>", "conv_bwd_weight_direct<1,1,1,1,true>",
-    "conv_bwd_weight<2,2,2,2>", "conv_bwd_weight<1,2,2,2>", "conv_bwd_weight<1,1,1,4>",
-    "conv_bwd_weight<2,2,2,2,1>", "conv_bwd_weight<1,2,2,2,1>", "conv_bwd_weight<1,1,1,4,1>"};
-
-static int bw1_kernel(const BwGeom &g, const ConvPlan &p, bool bf16x3) {
-    if (g.direct) return (p.s > 1 ? 5 : 0) + (g.cfg - 10);     // cfg 10..14; strided: x as a phase-split copy
-    return 10 + (bf16x3 ? 3 : 0) + g.cfg;                      // staged kernel, cfg 0..2
+static Bw2dLayout bw2d_layout(const Bw2dPlan &o) {
+    const Bw2dGeom &g = o.g;
+    Bw2dLayout l;
+    const size_t nw = size_t(g.Cin) * g.kh * g.kw * g.Cout, ns = size_t(g.n_slices), M = size_t(g.Cout);
+    l.dwp = ns * nw;
+    l.bias_part = l.dwp + nw;
+    l.rowdot = l.bias_part + ns * M + M;
+    l.total = l.rowdot + M;
+    l.copy = l.total + 64;
+    l.nx = size_t(g.sh) * g.sw * g.B * g.Cin * g.pp_hwi;
+    l.ny = size_t(g.B) * g.Cout * g.pp_lpr;
+    if (o.copy == WG_COPY_PREPAD) l.total += l.nx + l.ny + 256;
+    if (o.copy == WG_COPY_DEINTERLEAVE) l.total += size_t(g.sw) * g.B * g.Cin * g.Hin * g.Wp + 128;
+    return l;
 }
 
 }  // namespace agx
@@ -1487,12 +1622,7 @@ size_t agx_conv_bwd_weight_workspace_bytes(const agx_conv_desc *d) {
     using namespace agx;
     ConvPlan p;
     if (lower_conv(d, &p) != AGX_OK) return 0;
-    const BwGeom g = bw_geometry(p, d->impl == AGX_IMPL_MFMA_BF16X3);
-    // slices of dWp + the reduced dWp + slices of the bias row sums (+ the phase-split copy of x or dy)
-    size_t floats = (size_t(g.n_slices) + 1) * p.Cin * p.J * p.M + (size_t(g.n_slices) + 1) * p.M;
-    if (g.direct && p.s > 1) floats += size_t(p.B) * p.Cin * p.s * ceil_div(p.Lin, p.s) + 128;
-    if (g.direct && p.q > 1) floats += size_t(p.B) * p.M * p.Lt + 128;
-    return floats * sizeof(float);
+    return bw_layout(p, bw_geometry(p)).total * sizeof(float);
 }
 
 int agx_conv_bwd_weight(const agx_conv_desc *d, const float *x, const float *dy, const float *v, const float *g,
@@ -1503,71 +1633,35 @@ int agx_conv_bwd_weight(const agx_conv_desc *d, const float *x, const float *dy,
     int rc = lower_conv(d, &p);
     if (rc != AGX_OK) return rc;
     if (!x || !dy || !v || !dv || (g && !dg)) return fail(AGX_ERR_NULL_POINTER, "agx_conv_bwd_weight: NULL pointer");
-    if (!workspace || workspace_bytes < agx_conv_bwd_weight_workspace_bytes(d))
+    const BwGeom geo = bw_geometry(p);
+    const BwLayout lay = bw_layout(p, geo);
+    if (!workspace || workspace_bytes < lay.total * sizeof(float))
         return fail(AGX_ERR_WORKSPACE, "agx_conv_bwd_weight: workspace too small (%zu < %zu)", workspace_bytes,
-                    agx_conv_bwd_weight_workspace_bytes(d));
+                    lay.total * sizeof(float));
     hipStream_t st = static_cast<hipStream_t>(stream);
-    const BwGeom geo = bw_geometry(p, d->impl == AGX_IMPL_MFMA_BF16X3);
     if (geo.lds > 160 * 1024) return fail(AGX_ERR_UNSUPPORTED, "agx_conv_bwd_weight: tile needs %zu B of LDS", geo.lds);
     float *part = static_cast<float *>(workspace);
     const int64_t nw = int64_t(p.Cin) * p.J * p.M;
-    float *dwp = part + size_t(geo.n_slices) * nw;
-    float *bias_part = dbias ? dwp + nw : nullptr;
-    auto launch = [&](auto kern) -> int {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kern),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        if (e != hipSuccess) return fail(AGX_ERR_LAUNCH, "hipFuncSetAttribute: %s", hipGetErrorString(e));
-        hipLaunchKernelGGL(kern, geo.grid, dim3(256), geo.lds, st, p, geo.span, geo.n_chan, geo.n_slices, x, dy, part,
-                           bias_part);
-        return AGX_OK;
-    };
-    ConvPlan pd = p;            // the plan as the direct kernel sees it (phase-split operands: see the kernel's header)
-    const float *xd = x, *dyd = dy;
-    int sp = 1;
-    if (geo.direct && (p.s > 1 || p.q > 1)) {
-        float *extra = part + (size_t(geo.n_slices) + 1) * nw + (size_t(geo.n_slices) + 1) * p.M + 64;
-        if (p.s > 1) {
-            const int Lp = ceil_div(p.Lin, p.s);
-            const int64_t rows = int64_t(p.B) * p.Cin;
-            hipLaunchKernelGGL(phase_split_rows_kernel, dim3((unsigned)ceil_div64(rows * Lp, 256)), dim3(256), 0, st, x, extra,
-                               rows, p.Lin, p.Lvalid, Lp, p.s);
-            xd = extra;
-            sp = p.s;
-            pd.Lin = pd.Lvalid = Lp;
-        } else {
-            const int64_t rows = int64_t(p.B) * p.Cout;
-            hipLaunchKernelGGL(phase_split_rows_kernel, dim3((unsigned)ceil_div64(rows * p.Lt, 256)), dim3(256), 0, st, dy, extra,
-                               rows, p.Lout, p.Lout, p.Lt, p.q);
-            dyd = extra;
-            pd.Lout = p.Lt;
-            pd.Cout = p.M;
-        }
+    float *dwp = part + lay.dwp;
+    float *bias_part = dbias ? part + lay.bias_part : nullptr;
+    Bw1Args a{p, geo.span, geo.n_chan, geo.n_slices, 1, x, dy, part, bias_part, geo.grid, geo.lds, st};
+    if (geo.copy == WG_COPY_PHASE_X) {
+        const int Lp = ceil_div(p.Lin, p.s);
+        const int64_t rows = int64_t(p.B) * p.Cin;
+        hipLaunchKernelGGL(phase_split_rows_kernel, dim3((unsigned)ceil_div64(rows * Lp, 256)), dim3(256), 0, st, x, part + lay.copy,
+                           rows, p.Lin, p.Lvalid, Lp, p.s);
+        a.x = part + lay.copy;
+        a.sp = p.s;
+        a.p.Lin = a.p.Lvalid = Lp;
+    } else if (geo.copy == WG_COPY_PHASE_DY) {
+        const int64_t rows = int64_t(p.B) * p.Cout;
+        hipLaunchKernelGGL(phase_split_rows_kernel, dim3((unsigned)ceil_div64(rows * p.Lt, 256)), dim3(256), 0, st, dy, part + lay.copy,
+                           rows, p.Lout, p.Lout, p.Lt, p.q);
+        a.dy = part + lay.copy;
+        a.p.Lout = p.Lt;
+        a.p.Cout = p.M;
     }
-    auto launch_direct = [&](auto kern, int blocks_per_wave) -> int {   // 4 waves x (MW + NW) operand blocks of 4 KB
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kern),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, 64 * 1024);
-        if (e != hipSuccess) return fail(AGX_ERR_LAUNCH, "hipFuncSetAttribute: %s", hipGetErrorString(e));
-        hipLaunchKernelGGL(kern, geo.grid, dim3(256), size_t(4) * blocks_per_wave * 4096, st, pd, sp, xd, dyd, part, bias_part);
-        return AGX_OK;
-    };
-    switch (bw1_kernel(geo, p, d->impl == AGX_IMPL_MFMA_BF16X3)) {
-        case 0: rc = launch_direct(conv_bwd_weight_direct_kernel<2, 2, 2, 2>, 4); break;
-        case 1: rc = launch_direct(conv_bwd_weight_direct_kernel<2, 2, 1, 2>, 4); break;
-        case 2: rc = launch_direct(conv_bwd_weight_direct_kernel<2, 2, 1, 1>, 4); break;
-        case 3: rc = launch_direct(conv_bwd_weight_direct_kernel<1, 2, 1, 4>, 3); break;
-        case 4: rc = launch_direct(conv_bwd_weight_direct_kernel<1, 1, 1, 1>, 2); break;
-        case 5: rc = launch_direct(conv_bwd_weight_direct_kernel<2, 2, 2, 2, true>, 4); break;
-        case 6: rc = launch_direct(conv_bwd_weight_direct_kernel<2, 2, 1, 2, true>, 4); break;
-        case 7: rc = launch_direct(conv_bwd_weight_direct_kernel<2, 2, 1, 1, true>, 4); break;
-        case 8: rc = launch_direct(conv_bwd_weight_direct_kernel<1, 2, 1, 4, true>, 3); break;
-        case 9: rc = launch_direct(conv_bwd_weight_direct_kernel<1, 1, 1, 1, true>, 2); break;
-        case 10: rc = launch(conv_bwd_weight_kernel<2, 2, 2, 2>); break;
-        case 11: rc = launch(conv_bwd_weight_kernel<1, 2, 2, 2>); break;
-        case 12: rc = launch(conv_bwd_weight_kernel<1, 1, 1, 4>); break;
-        case 13: rc = launch(conv_bwd_weight_kernel<2, 2, 2, 2, 1>); break;
-        case 14: rc = launch(conv_bwd_weight_kernel<1, 2, 2, 2, 1>); break;
-        default: rc = launch(conv_bwd_weight_kernel<1, 1, 1, 4, 1>); break;
-    }
+    rc = geo.v->launch(a);
     if (rc != AGX_OK) return rc;
     launch_slice_reduce(part, geo.n_slices, nw, dwp, st);
     const bool transposed = d->kind == AGX_CONV_TRANSPOSED;
@@ -1575,120 +1669,12 @@ int agx_conv_bwd_weight(const agx_conv_desc *d, const float *x, const float *dy,
     hipLaunchKernelGGL(bwd_weight_unpack_kernel, dim3(dim0), dim3(256), 0, st, dwp, v, g, dv, dg, d->kind, p.Cin,
                        p.Cout, d->kernel, p.q, p.J, p.P, d->stride);
     if (dbias) {
-        float *rowsum = bias_part + size_t(geo.n_slices) * p.M;
+        float *rowsum = part + lay.rowsum;
         launch_slice_reduce(bias_part, geo.n_slices, int64_t(p.M), rowsum, st);
         hipLaunchKernelGGL(bwd_bias_fold_kernel, dim3(ceil_div(p.Cout, 256)), dim3(256), 0, st, rowsum, p.q, p.Cout,
                            dbias);
     }
     return check_launch("agx_conv_bwd_weight");
-}
-
-size_t agx_conv2d_bwd_weight_workspace_bytes(const agx_conv2d_desc *d) {
-    using namespace agx;
-    Bw2dGeom g;
-    int cfg, bm;
-    dim3 grid;
-    size_t lds;
-    if (bw2d_geometry(d, &g, &cfg, &bm, &grid, &lds) != AGX_OK) return 0;
-    const size_t nw = size_t(g.Cin) * g.kh * g.kw * g.Cout;
-    size_t floats = (size_t(g.n_slices) + 1) * nw + (size_t(g.n_slices) + 2) * g.Cout;
-    if (cfg >= 10 && g.prepad) floats += size_t(g.sh) * g.sw * g.B * g.Cin * g.pp_hwi + size_t(g.B) * g.Cout * g.pp_lpr + 256;   // padded copies
-    else if (cfg >= 10 && g.sw > 1) floats += size_t(g.sw) * g.B * g.Cin * g.Hin * g.Wp + 128;   // column-phase planes of x (+ slack)
-    return floats * sizeof(float);
-}
-
-int agx_conv2d_bwd_weight(const agx_conv2d_desc *d, const float *x, const float *dy, const float *w,
-                          const float *sigma, const float *u, const float *v, float *dw, float *dbias,
-                          void *workspace, size_t workspace_bytes, void *stream) {
-    using namespace agx;
-    Bw2dGeom g;
-    int cfg, bm;
-    dim3 grid;
-    size_t lds;
-    int rc = bw2d_geometry(d, &g, &cfg, &bm, &grid, &lds);
-    if (rc != AGX_OK) return rc;
-    if (!x || !dy || !dw || (sigma && (!w || !u || !v)))
-        return fail(AGX_ERR_NULL_POINTER, "agx_conv2d_bwd_weight: NULL pointer");
-    if (!workspace || workspace_bytes < agx_conv2d_bwd_weight_workspace_bytes(d))
-        return fail(AGX_ERR_WORKSPACE, "agx_conv2d_bwd_weight: workspace too small");
-    if (lds > 160 * 1024) return fail(AGX_ERR_UNSUPPORTED, "agx_conv2d_bwd_weight: tile needs %zu B of LDS", lds);
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    const int NK = g.Cin * g.kh * g.kw, M = g.Cout;
-    const int64_t nw = int64_t(NK) * M;
-    float *part = static_cast<float *>(workspace);
-    float *dwp = part + size_t(g.n_slices) * nw;
-    float *bias_part = dwp + nw;                       // [n_slices][M], then rowsum [M], then rowdot [M]
-    float *rowsum = bias_part + size_t(g.n_slices) * M;
-    float *rowdot = rowsum + M;
-    auto launch = [&](auto kern) -> int {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kern),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        if (e != hipSuccess) return fail(AGX_ERR_LAUNCH, "hipFuncSetAttribute: %s", hipGetErrorString(e));
-        hipLaunchKernelGGL(kern, grid, dim3(256), lds, st, g, x, dy, part, dbias ? bias_part : nullptr);
-        return AGX_OK;
-    };
-    auto launch_direct = [&](auto kern, int blocks_per_wave) -> int {   // 4 waves x (MW + NW) operand blocks of 4 KB
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kern),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, 64 * 1024);
-        if (e != hipSuccess) return fail(AGX_ERR_LAUNCH, "hipFuncSetAttribute: %s", hipGetErrorString(e));
-        hipLaunchKernelGGL(kern, grid, dim3(256), size_t(4) * blocks_per_wave * 4096, st, g, x, dy, part,
-                           dbias ? bias_part : nullptr);
-        return AGX_OK;
-    };
-    auto launch_shared = [&](auto kern, int blocks) -> int {   // two slots of (BM + BN) / 32 operand blocks of 4 KB
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kern),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        if (e != hipSuccess) return fail(AGX_ERR_LAUNCH, "hipFuncSetAttribute: %s", hipGetErrorString(e));
-        hipLaunchKernelGGL(kern, grid, dim3(256), size_t(2) * blocks * 4096, st, g, x, dy, part, dbias ? bias_part : nullptr);
-        return AGX_OK;
-    };
-    if (cfg >= 10) {
-        if (g.prepad) {   // narrow map: zero-padded, phase-split, flattened copies of both operands
-            float *xp = rowdot + M + 64;
-            xp += (4 - (reinterpret_cast<uintptr_t>(xp) / 4) % 4) % 4;          // 16-byte aligned planes
-            const int64_t nx = int64_t(g.sh) * g.sw * g.B * g.Cin * g.pp_hwi, ny = int64_t(g.B) * M * g.pp_lpr;
-            float *dyp = xp + nx;
-            const int amax_rows = g.Hout + ((g.kh - 1 - g.ph) >= 0 ? (g.kh - 1 - g.ph) / g.sh : 0) - g.pp_amin;
-            hipLaunchKernelGGL(prepad_x_kernel, dim3((unsigned)ceil_div64(nx, 256)), dim3(256), 0, st, x, xp, int64_t(g.B) * g.Cin, g.Hin,
-                               g.Win, amax_rows, g.Wp, g.pp_hwi, g.sh, g.sw, g.pp_amin, g.pp_bmin);
-            hipLaunchKernelGGL(prepad_dy_kernel, dim3((unsigned)ceil_div64(ny, 256)), dim3(256), 0, st, dy, dyp, int64_t(g.B) * M, g.Hout,
-                               g.Wout, g.Wp, g.pp_lpr);
-            x = xp;
-            dy = dyp;
-        } else if (g.sw > 1) {   // column-strided layer: x through its sw column-phase planes
-            float *xs = rowdot + M + 64;
-            const int64_t xrows = int64_t(g.B) * g.Cin * g.Hin;
-            hipLaunchKernelGGL(deinterleave_cols_kernel, dim3((unsigned)ceil_div64(xrows * g.Wp, 256)), dim3(256), 0, st, x,
-                               xs, xrows, g.Win, g.Wp, g.sw);
-            x = xs;
-        }
-    }
-    switch (bw2_kernel(g, cfg)) {
-        case 0: rc = launch_shared(conv2d_bwd_weight_shared_kernel<2, 2, 2, 2>, 8); break;
-        case 1: rc = launch_shared(conv2d_bwd_weight_shared_kernel<2, 2, 2, 2, 1>, 8); break;
-        case 2: rc = launch_shared(conv2d_bwd_weight_shared_kernel<2, 1, 1, 4>, 6); break;
-        case 3: rc = launch_shared(conv2d_bwd_weight_shared_kernel<2, 1, 1, 4, 1>, 6); break;
-        case 4: rc = launch_shared(conv2d_bwd_weight_shared_kernel<1, 2, 1, 4>, 9); break;
-        case 5: rc = launch_direct(conv2d_bwd_weight_direct_kernel<2, 2, 2, 2>, 4); break;
-        case 6: rc = launch_direct(conv2d_bwd_weight_direct_kernel<2, 2, 1, 2>, 4); break;
-        case 7: rc = launch_direct(conv2d_bwd_weight_direct_kernel<2, 2, 1, 1>, 4); break;
-        case 8: rc = launch_direct(conv2d_bwd_weight_direct_kernel<1, 2, 1, 4>, 3); break;
-        case 9: rc = launch_direct(conv2d_bwd_weight_direct_kernel<1, 3, 1, 1>, 4); break;
-        case 10: rc = launch_direct(conv2d_bwd_weight_direct_kernel<1, 1, 1, 1>, 2); break;
-        case 11: rc = launch(conv2d_bwd_weight_kernel<2, 2, 2, 2>); break;
-        case 12: rc = launch(conv2d_bwd_weight_kernel<1, 2, 2, 2>); break;
-        case 13: rc = launch(conv2d_bwd_weight_kernel<1, 1, 1, 4>); break;
-        case 14: rc = launch(conv2d_bwd_weight_kernel<2, 2, 2, 2, 1>); break;
-        case 15: rc = launch(conv2d_bwd_weight_kernel<1, 2, 2, 2, 1>); break;
-        default: rc = launch(conv2d_bwd_weight_kernel<1, 1, 1, 4, 1>); break;
-    }
-    if (rc != AGX_OK) return rc;
-    launch_slice_reduce(part, g.n_slices, nw, dwp, st);
-    hipLaunchKernelGGL(bwd2d_unpack_kernel, dim3(M), dim3(256), 0, st, dwp, sigma ? w : nullptr, dw, rowdot, NK, M);
-    if (sigma) hipLaunchKernelGGL(bwd2d_spectral_kernel, dim3(M), dim3(256), 0, st, dw, rowdot, sigma, u, v, NK, M);
-    if (dbias)
-        launch_slice_reduce(bias_part, g.n_slices, int64_t(M), dbias, st);
-    return check_launch("agx_conv2d_bwd_weight");
 }
 
 // "<instantiation> cfg=<geometry> op=<operand copy> slices=<contraction slices> items=<work items>": what the op above runs,
@@ -1700,30 +1686,76 @@ int agx_conv_bwd_weight_kernel_name(const agx_conv_desc *d, char *buf, size_t bu
     int rc = lower_conv(d, &p);
     if (rc != AGX_OK) return rc;
     if (!buf || buf_len == 0) return fail(AGX_ERR_NULL_POINTER, "agx_conv_bwd_weight_kernel_name: NULL buffer");
-    const bool bf = d->impl == AGX_IMPL_MFMA_BF16X3;
-    const BwGeom g = bw_geometry(p, bf);
-    const char *op = g.direct && p.s > 1 ? "phase_x" : (g.direct && p.q > 1 ? "phase_dy" : "none");
-    const long long items = (long long)p.B * ceil_div(p.Lt, g.direct ? 32 : BW_T);
-    snprintf(buf, buf_len, "%s cfg=%d op=%s slices=%d items=%lld", bw1_names[bw1_kernel(g, p, bf)], g.cfg, op,
-             g.n_slices * g.wk, items);
+    const BwGeom g = bw_geometry(p);
+    snprintf(buf, buf_len, "%s cfg=%d op=%s slices=%d items=%lld", g.v->name, g.v->cfg, wgrad_copy_name(g.copy),
+             g.n_slices * g.v->wk, (long long)g.items);
     return AGX_OK;
 }
 
+size_t agx_conv2d_bwd_weight_workspace_bytes(const agx_conv2d_desc *d) {
+    using namespace agx;
+    Bw2dPlan o;
+    if (bw2d_geometry(d, &o) != AGX_OK) return 0;
+    return bw2d_layout(o).total * sizeof(float);
+}
+
+int agx_conv2d_bwd_weight(const agx_conv2d_desc *d, const float *x, const float *dy, const float *w,
+                          const float *sigma, const float *u, const float *v, float *dw, float *dbias,
+                          void *workspace, size_t workspace_bytes, void *stream) {
+    using namespace agx;
+    Bw2dPlan o;
+    int rc = bw2d_geometry(d, &o);
+    if (rc != AGX_OK) return rc;
+    if (!x || !dy || !dw || (sigma && (!w || !u || !v)))
+        return fail(AGX_ERR_NULL_POINTER, "agx_conv2d_bwd_weight: NULL pointer");
+    const Bw2dGeom &g = o.g;
+    const Bw2dLayout lay = bw2d_layout(o);
+    if (!workspace || workspace_bytes < lay.total * sizeof(float))
+        return fail(AGX_ERR_WORKSPACE, "agx_conv2d_bwd_weight: workspace too small");
+    if (o.lds > 160 * 1024) return fail(AGX_ERR_UNSUPPORTED, "agx_conv2d_bwd_weight: tile needs %zu B of LDS", o.lds);
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    const int NK = g.Cin * g.kh * g.kw, M = g.Cout;
+    float *part = static_cast<float *>(workspace);
+    float *dwp = part + lay.dwp, *bias_part = part + lay.bias_part, *rowdot = part + lay.rowdot;
+    if (o.copy == WG_COPY_PREPAD) {   // narrow map: zero-padded, phase-split, flattened copies of both operands
+        float *xp = part + lay.copy;
+        xp += (4 - (reinterpret_cast<uintptr_t>(xp) / 4) % 4) % 4;          // 16-byte aligned planes
+        float *dyp = xp + lay.nx;
+        const int amax_rows = g.Hout + ((g.kh - 1 - g.ph) >= 0 ? (g.kh - 1 - g.ph) / g.sh : 0) - g.pp_amin;
+        hipLaunchKernelGGL(prepad_x_kernel, dim3((unsigned)ceil_div64(int64_t(lay.nx), 256)), dim3(256), 0, st, x, xp, int64_t(g.B) * g.Cin, g.Hin,
+                           g.Win, amax_rows, g.Wp, g.pp_hwi, g.sh, g.sw, g.pp_amin, g.pp_bmin);
+        hipLaunchKernelGGL(prepad_dy_kernel, dim3((unsigned)ceil_div64(int64_t(lay.ny), 256)), dim3(256), 0, st, dy, dyp, int64_t(g.B) * M, g.Hout,
+                           g.Wout, g.Wp, g.pp_lpr);
+        x = xp;
+        dy = dyp;
+    } else if (o.copy == WG_COPY_DEINTERLEAVE) {   // column-strided layer: x through its sw column-phase planes
+        float *xs = part + lay.copy;
+        const int64_t xrows = int64_t(g.B) * g.Cin * g.Hin;
+        hipLaunchKernelGGL(deinterleave_cols_kernel, dim3((unsigned)ceil_div64(xrows * g.Wp, 256)), dim3(256), 0, st, x,
+                           xs, xrows, g.Win, g.Wp, g.sw);
+        x = xs;
+    }
+    rc = o.v->launch(Bw2dArgs{g, x, dy, part, dbias ? bias_part : nullptr, o.grid, o.lds, st});
+    if (rc != AGX_OK) return rc;
+    const int64_t nw = int64_t(NK) * M;
+    launch_slice_reduce(part, g.n_slices, nw, dwp, st);
+    hipLaunchKernelGGL(bwd2d_unpack_kernel, dim3(M), dim3(256), 0, st, dwp, sigma ? w : nullptr, dw, rowdot, NK, M);
+    if (sigma) hipLaunchKernelGGL(bwd2d_spectral_kernel, dim3(M), dim3(256), 0, st, dw, rowdot, sigma, u, v, NK, M);
+    if (dbias)
+        launch_slice_reduce(bias_part, g.n_slices, int64_t(M), dbias, st);
+    return check_launch("agx_conv2d_bwd_weight");
+}
+
+// "<instantiation> cfg=<geometry> op=<operand copy> slices=<contraction slices> items=<work items>" as
+// agx_conv_bwd_weight_kernel_name: what the op above runs, from the same geometry.
 int agx_conv2d_bwd_weight_kernel_name(const agx_conv2d_desc *d, char *buf, size_t buf_len) {
     using namespace agx;
-    Bw2dGeom g;
-    int cfg, bm;
-    dim3 grid;
-    size_t lds;
-    int rc = bw2d_geometry(d, &g, &cfg, &bm, &grid, &lds);
+    Bw2dPlan o;
+    int rc = bw2d_geometry(d, &o);
     if (rc != AGX_OK) return rc;
     if (!buf || buf_len == 0) return fail(AGX_ERR_NULL_POINTER, "agx_conv2d_bwd_weight_kernel_name: NULL buffer");
-    const char *op = cfg >= 10 && g.prepad ? "prepad" : (cfg >= 10 && g.sw > 1 ? "deinterleave" : "none");
-    const long long items = cfg < 10 ? (long long)g.B * ceil_div(g.Hout, g.R) * ceil_div(g.Wout, g.WF)
-                          : g.prepad ? (long long)g.B * (g.pp_lpr / 32)
-                                     : (long long)g.B * g.Hout * (g.Wout / 32);
-    snprintf(buf, buf_len, "%s cfg=%d op=%s slices=%d items=%lld", bw2_names[bw2_kernel(g, cfg)], cfg, op, g.n_slices * g.wk,
-             items);
+    snprintf(buf, buf_len, "%s cfg=%d op=%s slices=%d items=%lld", o.v->name, o.v->cfg, wgrad_copy_name(o.copy),
+             o.g.n_slices * o.g.wk, (long long)o.items);
     return AGX_OK;
 }
 

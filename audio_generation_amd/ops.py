@@ -56,16 +56,19 @@ def _conv2d_macs(desc) -> int:
     return desc.batch * desc.c_in * desc.c_out * desc.kh * desc.kw * ho * wo
 
 
-def conv_kernel_name(desc: "ConvDesc") -> str:
-    buf = ctypes.create_string_buffer(96)
-    _lib.check(_lib.load().agx_conv_kernel_name(ctypes.byref(desc), buf, len(buf)), "agx_conv_kernel_name")
+def _kernel_name(symbol: str, desc, size: int = 96) -> str:
+    """The answer of one of the library's host-only name queries (``agx_*_kernel_name``)."""
+    buf = ctypes.create_string_buffer(size)
+    _lib.check(getattr(_lib.load(), symbol)(ctypes.byref(desc), buf, len(buf)), symbol)
     return buf.value.decode()
+
+
+def conv_kernel_name(desc: "ConvDesc") -> str:
+    return _kernel_name("agx_conv_kernel_name", desc)
 
 
 def resblock_kernel_name(desc: "ConvDesc") -> str:
-    buf = ctypes.create_string_buffer(96)
-    _lib.check(_lib.load().agx_resblock_kernel_name(ctypes.byref(desc), buf, len(buf)), "agx_resblock_kernel_name")
-    return buf.value.decode()
+    return _kernel_name("agx_resblock_kernel_name", desc)
 
 
 def _ptr(t: Optional[Tensor]):
@@ -256,10 +259,7 @@ def conv_bwd_weight(desc: ConvDesc, x: Tensor, dy: Tensor, v: Tensor, g: Optiona
 
 def conv_bwd_weight_kernel_name(desc: ConvDesc) -> str:
     """What ``conv_bwd_weight`` runs: "<kernel> cfg=.. op=.. slices=.. items=.." (include/agx.h)."""
-    buf = ctypes.create_string_buffer(128)
-    _lib.check(_lib.load().agx_conv_bwd_weight_kernel_name(ctypes.byref(desc), buf, len(buf)),
-               "agx_conv_bwd_weight_kernel_name")
-    return buf.value.decode()
+    return _kernel_name("agx_conv_bwd_weight_kernel_name", desc, 128)
 
 
 def resblock_forward(desc: ConvDesc, x: Tensor, packed1: Tensor, bias1: Optional[Tensor],
@@ -642,10 +642,7 @@ def conv_grouped_bwd_weight(desc: ConvDesc, x: Tensor, dz: Tensor, want_bias: bo
 
 def conv_grouped_bwd_weight_kernel_name(desc: ConvDesc) -> str:
     """What ``conv_grouped_bwd_weight`` runs: "<kernel> op=none slices=.. items=.." (include/agx.h)."""
-    buf = ctypes.create_string_buffer(128)
-    _lib.check(_lib.load().agx_conv_grouped_bwd_weight_kernel_name(ctypes.byref(desc), buf, len(buf)),
-               "agx_conv_grouped_bwd_weight_kernel_name")
-    return buf.value.decode()
+    return _kernel_name("agx_conv_grouped_bwd_weight_kernel_name", desc, 128)
 
 
 def avgpool1d(x: Tensor, kernel: int, stride: int, padding: int) -> Tensor:
@@ -764,23 +761,16 @@ def conv2d_bwd_data_fewchannels(desc, dy: Tensor, w: Tensor, sigma: Optional[Ten
 
 
 def conv2d_kernel_name(desc) -> str:
-    buf = ctypes.create_string_buffer(96)
-    _lib.check(_lib.load().agx_conv2d_kernel_name(ctypes.byref(desc), buf, 96), "agx_conv2d_kernel_name")
-    return buf.value.decode()
+    return _kernel_name("agx_conv2d_kernel_name", desc)
 
 
 def conv2d_bwd_data_kernel_name(desc) -> str:
-    buf = ctypes.create_string_buffer(96)
-    _lib.check(_lib.load().agx_conv2d_bwd_data_kernel_name(ctypes.byref(desc), buf, 96), "agx_conv2d_bwd_data_kernel_name")
-    return buf.value.decode()
+    return _kernel_name("agx_conv2d_bwd_data_kernel_name", desc)
 
 
 def conv2d_bwd_weight_kernel_name(desc) -> str:
     """What ``conv2d_bwd_weight`` runs: "<kernel> cfg=.. op=.. slices=.. items=.." (include/agx.h)."""
-    buf = ctypes.create_string_buffer(128)
-    _lib.check(_lib.load().agx_conv2d_bwd_weight_kernel_name(ctypes.byref(desc), buf, len(buf)),
-               "agx_conv2d_bwd_weight_kernel_name")
-    return buf.value.decode()
+    return _kernel_name("agx_conv2d_bwd_weight_kernel_name", desc, 128)
 
 
 _STFT_IMAGES = {}
