@@ -101,6 +101,14 @@ inline int prepare_kernel(const void *kern, DeviceOnce &once, int lds_limit_byte
 inline int ceil_div(int a, int b) { return (a + b - 1) / b; }
 inline int64_t ceil_div64(int64_t a, int64_t b) { return (a + b - 1) / b; }
 
+// Grid of a persistent ring kernel: wgs resident workgroups on each CU (two where two rings fit the 160 KiB of LDS), never more
+// workgroups than tiles; -1: more than 2^30 tiles (the launcher refuses the shape).
+inline int ring_wgs_per_cu(size_t lds_bytes) { return (160 * 1024) / lds_bytes >= 2 ? 2 : 1; }
+inline int ring_grid(int64_t ntiles, int n_cu, int wgs) {
+    if (ntiles > (1 << 30)) return -1;
+    return int(ntiles < int64_t(n_cu) * wgs ? ntiles : int64_t(n_cu) * wgs);
+}
+
 // Every layer kind of agx_conv_desc lowers to one "polyphase convolution":
 //   y[b, co, q*t + p] = epi( bias[co] + sum_{ci, j<J} Wp[ci*J + j][co*q + p] * x[b, ci, t*s + j*d - P] )
 // for t in [0, Lt), p in [0, q), output positions >= Lout dropped and input
@@ -165,17 +173,21 @@ __host__ __device__ inline int64_t tile_image_floats(int Cin, int J, int M) {
 __host__ __device__ inline size_t tile_image_index(int ci, int j, int m, int J, int M) {
     return ((size_t(ci / 4) * J + j) * M + m) * 4 + (ci % 4);
 }
-// Geometry class of a layer the persistent conv kernel is instantiated for (conv_p.hip), 0 = none.
-int conv_p_geometry(const ConvPlan &p);
-int conv_p2d_geometry(const ConvPlan &p);   // conv_p.hip: ring form of a patch-mode Conv2d plan (0 = none)
-// Layers that get a tile image: the stride-1 causal layers of the fused residual block (the dilated k = 7 conv and the
-// k = 1 conv, C in {32,64,128,256}) and the resampling / stride-1 layers of conv_p.hip.
+// Is the persistent conv kernel instantiated for a geometry that fits the layer (a row of the tables of conv_p.hip)?
+bool conv_p_geometry(const ConvPlan &p);
+bool conv_p2d_geometry(const ConvPlan &p);   // conv_p.hip: ring form of a patch-mode Conv2d plan
+// A stride-1 causal C x C layer of a fused residual block: the dilated k = 7 conv or the k = 1 conv.  The channel counts are the
+// rows of the block's table: resblock_p_has (resblock_p.hip, fp32), resblock_b3_has (resblock_b3.hip, bf16x3).
+bool resblock_p_has(int channels);
+bool resblock_b3_has(int channels);
+inline bool resblock_layer(const ConvPlan &p) {
+    return p.G == 1 && p.s == 1 && p.q == 1 && p.Cin == p.Cout && (p.J == 7 || p.J == 1);
+}
+// Layers that get a tile image: the layers of the fused residual block and the resampling / stride-1 layers of conv_p.hip.
 inline bool tile_image_eligible(const ConvPlan &p, int kind) {
     if (p.prec != 0 || p.G != 1) return false;
-    if (kind == AGX_CONV_CAUSAL && p.s == 1 && p.q == 1 && p.Cin == p.Cout &&
-        (p.Cin == 32 || p.Cin == 64 || p.Cin == 128 || p.Cin == 256) && (p.J == 7 || p.J == 1))
-        return true;
-    return conv_p_geometry(p) != 0;
+    if (kind == AGX_CONV_CAUSAL && resblock_layer(p) && resblock_p_has(p.Cin)) return true;
+    return conv_p_geometry(p);
 }
 
 // "B3 tile image" (resblock_b3.hip): the bf16x3 weights of a dense layer in the layout the bf16x3 ring kernels DMA and read:
@@ -184,14 +196,12 @@ inline bool tile_image_eligible(const ConvPlan &p, int kind) {
 // layers (the second conv of the fused block) are stored in GEMM2 order instead: slot e of lane half lh = channel
 // 16 g + 4 lh + e (e < 4), 16 g + 8 + 4 lh + (e - 4) (e >= 4) -- the hidden channels a lane holds in accumulator
 // registers 8 (g % 2) .. + 7.  Same size as the standard bf16x3 image; follows it and the dim0 scale scratch.
-int conv_b3_geometry(const ConvPlan &p);   // conv_b3.hip: bf16x3 ring form of a stride-1 polyphase layer (0 = none)
-int conv2d_b3_geometry(const ConvPlan &p); // conv_b3.hip: bf16x3 ring form of a patch-mode Conv2d plan (3 x 3, stride 1, "same"; 0 = none)
+bool conv_b3_geometry(const ConvPlan &p);   // conv_b3.hip: bf16x3 ring form of a polyphase layer (a row of its table)
+bool conv2d_b3_geometry(const ConvPlan &p); // conv_b3.hip: bf16x3 ring form of a patch-mode Conv2d plan
 inline bool b3_image_eligible(const ConvPlan &p, int kind) {
     if (p.prec != 1 || p.G != 1) return false;
-    if (kind == AGX_CONV_CAUSAL && p.s == 1 && p.q == 1 && p.Cin == p.Cout &&
-        (p.Cin == 32 || p.Cin == 64 || p.Cin == 128 || p.Cin == 256) && (p.J == 7 || p.J == 1))
-        return true;
-    return conv_b3_geometry(p) != 0;
+    if (kind == AGX_CONV_CAUSAL && resblock_layer(p) && resblock_b3_has(p.Cin)) return true;
+    return conv_b3_geometry(p);
 }
 
 // Lower a descriptor; returns AGX_OK or an error (message set).

@@ -59,9 +59,9 @@ int lower_conv2d(const agx_conv2d_desc *d, ConvPlan *p) {
     if (int64_t(p->B) * p->Tout > (int64_t(1) << 30)) return fail(AGX_ERR_BAD_SHAPE, "conv2d: batch * output rows too large");
     // layers the persistent ring kernel covers (conv_p.hip, D2 geometries) carry a tile image behind the scale scratch
     p->tile_off = -1;
-    if (patch && d->impl == AGX_IMPL_AUTO && conv_p2d_geometry(*p) != 0) p->tile_off = packed_weight_floats(p->ncv, p->J, p->M) + p->Cout;
+    if (patch && d->impl == AGX_IMPL_AUTO && conv_p2d_geometry(*p)) p->tile_off = packed_weight_floats(p->ncv, p->J, p->M) + p->Cout;
     // bf16x3 layers with the ring form (conv_b3.hip: 3 x 3, stride 1) carry a B3 tile image behind the scale scratch
-    if (p->prec == 1 && conv2d_b3_geometry(*p) != 0) p->tile_off = packed_weight_floats_bf(p->ncv, p->J, p->M) + p->Cout;
+    if (p->prec == 1 && conv2d_b3_geometry(*p)) p->tile_off = packed_weight_floats_bf(p->ncv, p->J, p->M) + p->Cout;
     return AGX_OK;
 }
 
@@ -147,8 +147,8 @@ int lower_conv2d_bwd_data(const agx_conv2d_desc *d, ConvPlan *b) {
     }
     b->pm_WF = 0;
     b->tile_off = -1;
-    if (patch && d->impl == AGX_IMPL_AUTO && conv_p2d_geometry(*b) != 0) b->tile_off = packed_weight_floats(b->ncv, b->J, b->M);
-    if (patch && b->prec == 1 && conv2d_b3_geometry(*b) != 0) b->tile_off = packed_weight_floats_bf(b->ncv, b->J, b->M);
+    if (patch && d->impl == AGX_IMPL_AUTO && conv_p2d_geometry(*b)) b->tile_off = packed_weight_floats(b->ncv, b->J, b->M);
+    if (patch && b->prec == 1 && conv2d_b3_geometry(*b)) b->tile_off = packed_weight_floats_bf(b->ncv, b->J, b->M);
     return AGX_OK;
 }
 

@@ -45,9 +45,9 @@ static int conv_name(const ConvPlan &p, int impl, bool ring, const char *prefix,
     return AGX_OK;
 }
 
-// The layer's bf16x3 ring kernel reads pre-split planes (the strided down-convs and the causal k = 3 layer take fp32 input only)
-static bool conv_takes_planes(const ConvPlan &p, int impl) {
-    return conv_kernel(p, impl) == CONV_B3 && p.s == 1 && !(p.q == 1 && p.J != 7);
+// The layer's bf16x3 ring kernel reads pre-split planes (1), and can write them as well (2): conv_b3_planes
+static int conv_takes_planes(const ConvPlan &p, int impl) {
+    return conv_kernel(p, impl) == CONV_B3 ? conv_b3_planes(p) : 0;
 }
 
 // Plan of the residual block `d` describes (its first conv with the LeakyReLU epilogue), for the launcher and the name query
@@ -114,8 +114,7 @@ int agx_conv_planes_supported(const agx_conv_desc *d) {
     using namespace agx;
     ConvPlan p;
     if (lower_conv(d, &p) != AGX_OK) return 0;
-    if (!conv_takes_planes(p, d->impl)) return 0;
-    return (p.q == 1 && p.Cout % 8 == 0) ? 2 : 1;      // 2: the layer can also WRITE planes (one output phase)
+    return conv_takes_planes(p, d->impl);      // 2: the layer can also WRITE planes (one output phase)
 }
 
 int agx_conv_bwd_data(const agx_conv_desc *d, const float *dy, const float *packed_bwd, const float *add,

@@ -759,54 +759,6 @@ __global__ __launch_bounds__(256, 2) void conv2d_b3_kernel(ConvPlan p, int cb_co
     C2S_WRITE();
 }
 
-enum { CB3_NONE = 0, CB3_UP2, CB3_UP4, CB3_UP5, CB3_UP8, CB3_K7, CB3_K3, CB3_DOWN2, CB3_DOWN4, CB3_DOWN5, CB3_DOWN8 };
-
-// shape-only test (also decides whether agx_conv_pack of a bf16x3 descriptor appends the B3 tile image: common.hpp)
-int conv_b3_geometry(const ConvPlan &p) {
-    if (p.prec != 1 || p.G != 1 || p.d != 1 || p.kh != 1 || p.Tout != 1 || p.pm_R != 0) return CB3_NONE;
-    if (p.Cin % 32 != 0) return CB3_NONE;                      // whole 16-channel chunks, an even number of them
-    if (p.s == 1) {
-        if (p.q == 2 && p.J == 3 && p.P == 1 && p.M == 64) return CB3_UP2;
-        if (p.q == 4 && p.J == 3 && p.P == 1 && p.M % 128 == 0) return CB3_UP4;
-        if (p.q == 5 && p.J == 3 && p.P == 1 && p.M % 128 == 0) return CB3_UP5;
-        if (p.q == 8 && p.J == 3 && p.P == 1 && p.M % 128 == 0) return CB3_UP8;
-        if (p.q == 1 && p.J == 7 && p.P == 6 && p.M % 128 == 0) return CB3_K7;
-        if (p.q == 1 && p.J == 3 && p.P == 2 && p.M % 128 == 0) return CB3_K3;      // causal k = 3 (the encoder's last conv, vae.py:266)
-        return CB3_NONE;
-    }
-    // round 4: the encoder's strided down-convs CausalConv1d(K = 2 s + 1, stride s) (vae.py:136-139), P = K - s
-    if (p.q != 1) return CB3_NONE;
-    if (p.s == 2 && p.J == 5 && p.P == 3 && p.M == 64) return CB3_DOWN2;
-    if (p.s == 4 && p.J == 9 && p.P == 5 && p.M % 128 == 0) return CB3_DOWN4;
-    if (p.s == 5 && p.J == 11 && p.P == 6 && p.M % 128 == 0) return CB3_DOWN5;
-    if (p.s == 8 && p.J == 17 && p.P == 9 && p.M % 128 == 0) return CB3_DOWN8;
-    return CB3_NONE;
-}
-
-bool conv_b3_supported(const ConvPlan &p) {
-    if (p.tile_off < 0 || conv_b3_geometry(p) == CB3_NONE) return false;
-    if ((p.epilogue & ~AGX_EPI_LEAKY_PRE) != 0 || p.oshift != 0 || p.mask != nullptr) return false;
-    if (p.Lvalid != p.Lin || p.Lin < 1 || p.Lout != p.q * p.Lt || (p.s == 1 && p.Lt != p.Lin)) return false;
-    if (int64_t(p.Cin) * p.Lin * 4 >= (int64_t(1) << 32)) return false;     // 32-bit byte offsets of the input loads
-    return true;
-}
-
-const char *conv_b3_variant(const ConvPlan &p) {
-    switch (conv_b3_geometry(p)) {
-        case CB3_UP2: return "conv_b3<up2,64x256>";
-        case CB3_UP4: return "conv_b3<up4,128x128>";
-        case CB3_UP5: return "conv_b3<up5,128x128>";
-        case CB3_UP8: return "conv_b3<up8,128x128>";
-        case CB3_K7: return "conv_b3<k7,128x128>";
-        case CB3_K3: return "conv_b3<k3,128x128>";
-        case CB3_DOWN2: return "conv_b3<down2,64x128>";
-        case CB3_DOWN4: return "conv_b3<down4,128x64>";
-        case CB3_DOWN5: return "conv_b3<down5,128x64>";
-        case CB3_DOWN8: return "conv_b3<down8,128x32>";
-        default: return "conv_b3<unsupported>";
-    }
-}
-
 template <int MW, int NW, int WM, int J_, int Q_, int P_, bool XP = false, bool YP = false, int S_ = 1>
 static int launch_cb3(const ConvPlan &p, const float *x, const float *wp, const float *bias, float *y, hipStream_t st) {
     using G = Cb3Geom<MW, NW, WM, J_, Q_, P_, XP, S_>;
@@ -817,31 +769,85 @@ static int launch_cb3(const ConvPlan &p, const float *x, const float *wp, const 
     static_assert(2 * G::LDS_BYTES <= 160 * 1024, "conv_b3: LDS budget of two workgroups per CU");
     const int tb = ceil_div(p.Lt, G::BN), mb = p.M / G::BM;
     const int64_t ntiles64 = int64_t(tb) * mb * p.B;
-    if (ntiles64 > (1 << 30)) return fail(AGX_ERR_BAD_SHAPE, "conv_b3: too many tiles");
-    const int ntiles = int(ntiles64);
-    const int grid = ntiles < 2 * n_cu ? ntiles : 2 * n_cu;
+    const int grid = ring_grid(ntiles64, n_cu, 2), ntiles = int(ntiles64);
+    if (grid < 0) return fail(AGX_ERR_BAD_SHAPE, "conv_b3: too many tiles");
     // B3 tile image: behind the bf16x3 standard image and the dim0 scale scratch
     const char *wt = reinterpret_cast<const char *>(wp + p.tile_off);
     hipLaunchKernelGGL(kern, dim3(grid), dim3(256), G::LDS_BYTES, st, p, tb, mb, ntiles, x, wt, bias, y);
     return check_launch("conv_b3");
 }
 
+// One row per geometry: everything the host knows about it.  A new geometry is one row.
+typedef int (*Cb3Launch)(const ConvPlan &, const float *, const float *, const float *, float *, hipStream_t);
+struct Cb3Row {
+    const char *name;   // pinned: tests/golden/kernel_names.json
+    int exact_m;        // the tile is the layer's whole M (0: any multiple of BM)
+    bool (*fits)(const ConvPlan &);
+    Cb3Launch launch, launch_xp, launch_xp_yp;   // fp32 input; plane input (XP); plane input and plane output (XP, YP); null: not instantiated
+};
+
+template <class G>
+static bool cb3_fits(const ConvPlan &p) {
+    return p.s == G::S && p.q == G::Q && p.J == G::J && p.P == G::P && p.M % G::BM == 0;
+}
+
+// PLANES: 0 fp32 input only (the strided down-convs: Cb3Geom, and the causal k = 3 layer), 1 also plane input, 2 also plane output
+template <int PLANES, int MW, int NW, int WM, int J, int Q, int P, int S = 1>
+static constexpr Cb3Row cb3_row(const char *name, int exact_m = 0) {
+    Cb3Row r = {name, exact_m, cb3_fits<Cb3Geom<MW, NW, WM, J, Q, P, false, S>>, launch_cb3<MW, NW, WM, J, Q, P, false, false, S>, nullptr, nullptr};
+    if constexpr (PLANES >= 1) r.launch_xp = launch_cb3<MW, NW, WM, J, Q, P, true, false, S>;
+    if constexpr (PLANES >= 2) r.launch_xp_yp = launch_cb3<MW, NW, WM, J, Q, P, true, true, S>;
+    return r;
+}
+
+//         planes MW NW WM  J  Q  P  S
+static const Cb3Row kCb3Rows[] = {
+    cb3_row<1, 2, 2, 1, 3, 2, 1>("conv_b3<up2,64x256>", 64),
+    cb3_row<1, 2, 2, 2, 3, 4, 1>("conv_b3<up4,128x128>"),
+    cb3_row<1, 2, 2, 2, 3, 5, 1>("conv_b3<up5,128x128>"),
+    cb3_row<1, 2, 2, 2, 3, 8, 1>("conv_b3<up8,128x128>"),
+    cb3_row<2, 2, 2, 2, 7, 1, 6>("conv_b3<k7,128x128>"),
+    cb3_row<0, 2, 2, 2, 3, 1, 2>("conv_b3<k3,128x128>"),      // causal k = 3 (the encoder's last conv, vae.py:266)
+    // round 4: the encoder's strided down-convs CausalConv1d(K = 2 s + 1, stride s) (vae.py:136-139), P = K - s
+    cb3_row<0, 2, 1, 1, 5, 1, 3, 2>("conv_b3<down2,64x128>", 64),
+    cb3_row<0, 2, 1, 2, 9, 1, 5, 4>("conv_b3<down4,128x64>"),
+    cb3_row<0, 2, 1, 2, 11, 1, 6, 5>("conv_b3<down5,128x64>"),
+    cb3_row<0, 1, 1, 4, 17, 1, 9, 8>("conv_b3<down8,128x32>")};
+
+// shape-only test (also decides whether agx_conv_pack of a bf16x3 descriptor appends the B3 tile image: common.hpp)
+static const Cb3Row *cb3_row_of(const ConvPlan &p) {
+    if (p.prec != 1 || p.G != 1 || p.d != 1 || p.kh != 1 || p.Tout != 1 || p.pm_R != 0) return nullptr;
+    if (p.Cin % 32 != 0) return nullptr;                       // whole 16-channel chunks, an even number of them
+    for (const Cb3Row &r : kCb3Rows)
+        if ((r.exact_m == 0 || p.M == r.exact_m) && r.fits(p)) return &r;
+    return nullptr;
+}
+bool conv_b3_geometry(const ConvPlan &p) { return cb3_row_of(p) != nullptr; }
+
+bool conv_b3_supported(const ConvPlan &p) {
+    if (p.tile_off < 0 || !conv_b3_geometry(p)) return false;
+    if ((p.epilogue & ~AGX_EPI_LEAKY_PRE) != 0 || p.oshift != 0 || p.mask != nullptr) return false;
+    if (p.Lvalid != p.Lin || p.Lin < 1 || p.Lout != p.q * p.Lt || (p.s == 1 && p.Lt != p.Lin)) return false;
+    if (int64_t(p.Cin) * p.Lin * 4 >= (int64_t(1) << 32)) return false;     // 32-bit byte offsets of the input loads
+    return true;
+}
+
+const char *conv_b3_variant(const ConvPlan &p) {
+    const Cb3Row *row = cb3_row_of(p);
+    return row ? row->name : "conv_b3<unsupported>";
+}
+
+// 0: the layer's kernel reads fp32 input only; 1: it can read activation planes; 2: it can also write them (one output phase,
+// whole 8-channel cells)
+int conv_b3_planes(const ConvPlan &p) {
+    const Cb3Row *row = conv_b3_supported(p) ? cb3_row_of(p) : nullptr;
+    if (!row || !row->launch_xp) return 0;
+    return (row->launch_xp_yp && p.Cout % 8 == 0) ? 2 : 1;
+}
+
 int launch_conv_b3(const ConvPlan &p, const float *x, const float *wp, const float *bias, float *y, hipStream_t st) {
     if (!conv_b3_supported(p)) return fail(AGX_ERR_UNSUPPORTED, "conv_b3: unsupported layer");
-    switch (conv_b3_geometry(p)) {
-        case CB3_UP2: return launch_cb3<2, 2, 1, 3, 2, 1>(p, x, wp, bias, y, st);
-        case CB3_UP4: return launch_cb3<2, 2, 2, 3, 4, 1>(p, x, wp, bias, y, st);
-        case CB3_UP5: return launch_cb3<2, 2, 2, 3, 5, 1>(p, x, wp, bias, y, st);
-        case CB3_UP8: return launch_cb3<2, 2, 2, 3, 8, 1>(p, x, wp, bias, y, st);
-        case CB3_K7: return launch_cb3<2, 2, 2, 7, 1, 6>(p, x, wp, bias, y, st);
-        case CB3_K3: return launch_cb3<2, 2, 2, 3, 1, 2>(p, x, wp, bias, y, st);
-        //                          MW NW WM  J  Q  P  XP     YP     S      tile (rows x output columns)
-        case CB3_DOWN2: return launch_cb3<2, 1, 1, 5, 1, 3, false, false, 2>(p, x, wp, bias, y, st);     //  64 x 128
-        case CB3_DOWN4: return launch_cb3<2, 1, 2, 9, 1, 5, false, false, 4>(p, x, wp, bias, y, st);     // 128 x 64
-        case CB3_DOWN5: return launch_cb3<2, 1, 2, 11, 1, 6, false, false, 5>(p, x, wp, bias, y, st);    // 128 x 64
-        case CB3_DOWN8: return launch_cb3<1, 1, 4, 17, 1, 9, false, false, 8>(p, x, wp, bias, y, st);    // 128 x 32
-        default: return fail(AGX_ERR_UNSUPPORTED, "conv_b3: unsupported layer");
-    }
+    return cb3_row_of(p)->launch(p, x, wp, bias, y, st);
 }
 
 // The same layers fed with activation planes (common.hpp) -- x_planes: bf16 [B][Cin / 8][3][Lin][8]; y_planes (k = 7 layer only, may
@@ -851,19 +857,11 @@ int launch_conv_b3_planes(const ConvPlan &p, const void *x_planes, const float *
     if (!conv_b3_supported(p)) return fail(AGX_ERR_UNSUPPORTED, "conv_b3: unsupported layer");
     if (int64_t(p.Cin / 8) * 3 * p.Lin * 16 >= (int64_t(1) << 40)) return fail(AGX_ERR_BAD_SHAPE, "conv_b3: clip too long");
     const float *xp = static_cast<const float *>(x_planes);
-    const int g = conv_b3_geometry(p);
-    if (p.s != 1 || g == CB3_K3) return fail(AGX_ERR_UNSUPPORTED, "conv_b3: plane input is for the decoder's stride-1 layers");
-    if (y_planes && (g != CB3_K7 || p.Cout % 8 != 0)) return fail(AGX_ERR_UNSUPPORTED, "conv_b3: plane output is for the one-phase layer");
-    switch (g) {
-        case CB3_UP2: return launch_cb3<2, 2, 1, 3, 2, 1, true>(p, xp, wp, bias, y, st);
-        case CB3_UP4: return launch_cb3<2, 2, 2, 3, 4, 1, true>(p, xp, wp, bias, y, st);
-        case CB3_UP5: return launch_cb3<2, 2, 2, 3, 5, 1, true>(p, xp, wp, bias, y, st);
-        case CB3_UP8: return launch_cb3<2, 2, 2, 3, 8, 1, true>(p, xp, wp, bias, y, st);
-        case CB3_K7:
-            return y_planes ? launch_cb3<2, 2, 2, 7, 1, 6, true, true>(p, xp, wp, bias, static_cast<float *>(y_planes), st)
-                            : launch_cb3<2, 2, 2, 7, 1, 6, true, false>(p, xp, wp, bias, y, st);
-        default: return fail(AGX_ERR_UNSUPPORTED, "conv_b3: unsupported layer");
-    }
+    const int planes = conv_b3_planes(p);
+    if (planes == 0) return fail(AGX_ERR_UNSUPPORTED, "conv_b3: plane input is for the decoder's stride-1 layers");
+    if (y_planes && planes != 2) return fail(AGX_ERR_UNSUPPORTED, "conv_b3: plane output is for the one-phase layer");
+    const Cb3Row *row = cb3_row_of(p);
+    return y_planes ? row->launch_xp_yp(p, xp, wp, bias, static_cast<float *>(y_planes), st) : row->launch_xp(p, xp, wp, bias, y, st);
 }
 
 // fp32 (B, C, L) -> activation planes: one thread = one cell (8 channels of one time step), loads coalesced along time
@@ -910,37 +908,6 @@ int64_t conv2d_b3_tile_floats(const ConvPlan &p) {
 }
 
 // ---- Conv2d (conv2d_b3_kernel) ---------------------------------------------------------------------------------------
-enum { C2B3_NONE = 0, C2B3_M128 = 1, C2B3_M64 = 2, C2B3_M32 = 3 };      // tile shape (low 4 bits of the geometry code)
-enum { C2B3_T33 = 0, C2B3_T22 = 1, C2B3_T32 = 2, C2B3_T22F = 3, C2B3_T32F = 4 };   // tap shape (next 4 bits); F: strided FORWARD, space-to-depth
-
-// shape-only test (also decides whether the conv2d pack functions append the B3 tile image: conv2d.hip)
-int conv2d_b3_geometry(const ConvPlan &p) {
-    if (p.prec != 1 || p.G != 1 || p.pm_R <= 0 || p.d != 1) return C2B3_NONE;
-    if (p.cin_real != p.Cin || p.ncv != p.Cin) return C2B3_NONE;
-    int taps;
-    if (p.s == 2 && p.q == 1 && p.qh == 1 && p.P == 1 && p.ph == 1 && p.oshift == 0 && p.oshift_h == 0 && p.Cin % 16 == 0 &&
-        ((p.sh == 2 && p.kh == 4 && p.J == 16) || (p.sh == 1 && p.kh == 3 && p.J == 12))) {
-        // FORWARD of the (4,4)/(2,2) and (3,4)/(1,2) layers, pad (1,1): space-to-depth = sh sw Cin virtual channels (16-channel
-        // chunks stay inside one phase), 2 x 2 resp. 3 x 2 taps, stride 1 (conv2d_b3_kernel's staging)
-        if (p.Lt != p.Lout || p.Tt != p.Tout) return C2B3_NONE;
-        taps = p.sh == 2 ? C2B3_T22F : C2B3_T32F;
-    } else if (p.s != 1 || p.sh != 1 || p.Cin % 32 != 0) {             // (stride-1 plans: whole 16-channel chunks, an even number)
-        return C2B3_NONE;
-    } else if (p.kh == 3 && p.J == 9 && p.q == 1 && p.qh == 1) {      // 3 x 3, stride 1, "same": forward and backward-data
-        if (p.P != 1 || p.ph != 1 || p.oshift != 0 || p.oshift_h != 0) return C2B3_NONE;
-        if (p.Lt != p.Lout || p.Tt != p.Tout || p.Lout != p.Lin || p.Tout != p.Tin) return C2B3_NONE;
-        taps = C2B3_T33;
-    } else if (p.kh == 2 && p.J == 4 && p.q == 2 && p.qh == 2 && p.P == 1 && p.ph == 1) {
-        taps = C2B3_T22;                                              // backward-data of a 4 x 4 stride-(2, 2) layer
-    } else if (p.kh == 3 && p.J == 6 && p.q == 2 && p.qh == 1 && p.P == 1 && p.ph == 1 && p.oshift_h == 0 && p.Tt == p.Tout) {
-        taps = C2B3_T32;                                              // backward-data of a 3 x 4 stride-(1, 2) layer
-    } else {
-        return C2B3_NONE;
-    }
-    const int tile = p.M % 128 == 0 ? C2B3_M128 : p.M == 64 ? C2B3_M64 : p.M == 32 ? C2B3_M32 : C2B3_NONE;
-    return tile == C2B3_NONE ? C2B3_NONE : (tile | (taps << 4));
-}
-
 // tile rows R = BN >> SL of WF = 2^SL columns over the base grid.  A tile costs its matrix time (the same for every split) plus
 // the staging of its input planes -- (R + kh - 1)(WF + kw - 1) positions x 2 halves of 8 channels in rounds of 256 threads, ~450
 // cycles a round against 32 cycles per MFMA: two rows of 128 columns stage 1040 tasks = 5 rounds, eight rows of 32 columns 680 =
@@ -1009,33 +976,6 @@ __global__ __launch_bounds__(256) void conv2d_b3_first_col_kernel(ConvPlan p, co
 // 2.07 -> 1.75 ms and 2.53 -> 2.24 ms, 129 and narrower lose)
 static inline bool c2b3_peels_first_col(const ConvPlan &p) { return p.q == 2 && p.oshift == 1 && p.P == 1 && p.Lt > 192; }
 
-bool conv2d_b3_supported(const ConvPlan &p) {
-    const int geom = conv2d_b3_geometry(p), tile = geom & 15;
-    if (p.tile_off < 0 || geom == C2B3_NONE) return false;
-    {   // very narrow / ragged feature maps: beyond 1.4 x padded area the fp32 ring kernel wins
-        ConvPlan pp = p;
-        if (c2b3_peels_first_col(p)) pp.Lt = p.Lt - 1;
-        const int BN = tile == C2B3_M128 ? 128 : 256, sl = c2b3_pick_sl(pp, BN, tile == C2B3_M128 ? 6 : 7, 1, 1, 0);
-        const int R = BN >> sl, WF = 1 << sl;
-        const int64_t area = int64_t(ceil_div(pp.Tt, R)) * R * ceil_div(pp.Lt, WF) * WF;
-        if (area * 10 > int64_t(pp.Tt) * pp.Lt * 14) return false;
-    }
-    if ((p.epilogue & ~(AGX_EPI_LEAKY_PRE | AGX_EPI_RESIDUAL | AGX_EPI_MASK)) != 0) return false;
-    if (p.x_cstride != int64_t(p.Tin) * p.Lin || p.y_cstride != int64_t(p.Tout) * p.Lout) return false;
-    if (p.x_cstride * 16 * 4 >= (int64_t(1) << 32) || p.y_cstride * p.Cout >= (int64_t(1) << 31)) return false;   // 32-bit offsets
-    return true;
-}
-
-const char *conv2d_b3_variant(const ConvPlan &p) {
-    static const char *names[5][3] = {{"conv2d_b3<3x3,128x128>", "conv2d_b3<3x3,64x256>", "conv2d_b3<3x3,32x256>"},
-                                      {"conv2d_b3<2x2 phases 2x2,128x128>", "conv2d_b3<2x2 phases 2x2,64x256>", "conv2d_b3<2x2 phases 2x2,32x256>"},
-                                      {"conv2d_b3<3x2 phases 1x2,128x128>", "conv2d_b3<3x2 phases 1x2,64x256>", "conv2d_b3<3x2 phases 1x2,32x256>"},
-                                      {"conv2d_b3<4x4 s2 as 2x2 s2d,128x128>", "conv2d_b3<4x4 s2 as 2x2 s2d,64x256>", "conv2d_b3<4x4 s2 as 2x2 s2d,32x256>"},
-                                      {"conv2d_b3<3x4 s(1,2) as 3x2 s2d,128x128>", "conv2d_b3<3x4 s(1,2) as 3x2 s2d,64x256>", "conv2d_b3<3x4 s(1,2) as 3x2 s2d,32x256>"}};
-    const int geom = conv2d_b3_geometry(p);
-    return geom == C2B3_NONE ? "conv2d_b3<unsupported>" : names[geom >> 4][(geom & 15) - 1];
-}
-
 template <int MW, int NW, int WM, int SL, int KH, int KW, int Q, int QH>
 static int launch_c2b3(const ConvPlan &p, const float *x, const float *wp, const float *bias, const float *add, const float *mask,
                        float *y, hipStream_t st) {
@@ -1047,61 +987,134 @@ static int launch_c2b3(const ConvPlan &p, const float *x, const float *wp, const
     static_assert(2 * G::LDS_BYTES <= 160 * 1024, "conv2d_b3: LDS budget of two workgroups per CU");
     const int cb = ceil_div(p.Lt, G::WF), rb = ceil_div(p.Tt, G::R), mb = p.M / G::BM;
     const int64_t ntiles64 = int64_t(cb) * rb * mb * p.B;
-    if (ntiles64 > (1 << 30)) return fail(AGX_ERR_BAD_SHAPE, "conv2d_b3: too many tiles");
-    const int ntiles = int(ntiles64);
-    const int grid = ntiles < 2 * n_cu ? ntiles : 2 * n_cu;
+    const int grid = ring_grid(ntiles64, n_cu, 2), ntiles = int(ntiles64);
+    if (grid < 0) return fail(AGX_ERR_BAD_SHAPE, "conv2d_b3: too many tiles");
     const char *wt = reinterpret_cast<const char *>(wp + p.tile_off);
     hipLaunchKernelGGL(kern, dim3(grid), dim3(256), G::LDS_BYTES, st, p, cb, rb, mb, ntiles, x, wt, bias,
                        (p.epilogue & AGX_EPI_RESIDUAL) ? add : nullptr, (p.epilogue & AGX_EPI_MASK) ? mask : nullptr, y);
     return check_launch("conv2d_b3");
 }
 
-template <int MW, int NW, int WM, int SLMAX, int KH, int KW, int Q, int QH>
-static int launch_c2b3_sl(const ConvPlan &p, const float *x, const float *wp, const float *bias, const float *add,
-                          const float *mask, float *y, hipStream_t st) {
-    const int sl = c2b3_pick_sl(p, 32 * NW * (4 / WM), SLMAX, KH, KW, MW * NW);
-    if (sl == 3) return launch_c2b3<MW, NW, WM, 3, KH, KW, Q, QH>(p, x, wp, bias, add, mask, y, st);
-    if (sl == 4) return launch_c2b3<MW, NW, WM, 4, KH, KW, Q, QH>(p, x, wp, bias, add, mask, y, st);
-    if (sl == 5) return launch_c2b3<MW, NW, WM, 5, KH, KW, Q, QH>(p, x, wp, bias, add, mask, y, st);
-    if (sl == 6 || SLMAX == 6) return launch_c2b3<MW, NW, WM, 6, KH, KW, Q, QH>(p, x, wp, bias, add, mask, y, st);
-    return launch_c2b3<MW, NW, WM, SLMAX, KH, KW, Q, QH>(p, x, wp, bias, add, mask, y, st);
+// tile shape: MW x NW fragments per wave on WM x 4 / WM waves, rows of at most 2^SLMAX columns
+template <int MW_, int NW_, int WM_, int SLMAX_>
+struct C2b3TileGeom {
+    static constexpr int MW = MW_, NW = NW_, WM = WM_, SLMAX = SLMAX_, BM = 32 * MW * WM, BN = 32 * NW * (4 / WM);
+};
+
+// res = the tensor added in the epilogue, p.mask the LeakyReLU-gradient mask (launch_conv2d_b3)
+template <class T, int KH, int KW, int Q, int QH>
+static int launch_c2b3_sl(const ConvPlan &p, const float *x, const float *wp, const float *bias, const float *res, float *y, hipStream_t st) {
+    constexpr int MW = T::MW, NW = T::NW, WM = T::WM, SLMAX = T::SLMAX;
+    const int sl = c2b3_pick_sl(p, T::BN, SLMAX, KH, KW, MW * NW);
+    if (sl == 3) return launch_c2b3<MW, NW, WM, 3, KH, KW, Q, QH>(p, x, wp, bias, res, p.mask, y, st);
+    if (sl == 4) return launch_c2b3<MW, NW, WM, 4, KH, KW, Q, QH>(p, x, wp, bias, res, p.mask, y, st);
+    if (sl == 5) return launch_c2b3<MW, NW, WM, 5, KH, KW, Q, QH>(p, x, wp, bias, res, p.mask, y, st);
+    if (sl == 6 || SLMAX == 6) return launch_c2b3<MW, NW, WM, 6, KH, KW, Q, QH>(p, x, wp, bias, res, p.mask, y, st);
+    return launch_c2b3<MW, NW, WM, SLMAX, KH, KW, Q, QH>(p, x, wp, bias, res, p.mask, y, st);
 }
 
-template <int KH, int KW, int Q, int QH>
-static int launch_c2b3_tile(int tile, const ConvPlan &p, const float *x, const float *wp, const float *bias, const float *res,
-                            float *y, hipStream_t st) {
-    switch (tile) {
-        case C2B3_M128: return launch_c2b3_sl<2, 2, 2, 6, KH, KW, Q, QH>(p, x, wp, bias, res, p.mask, y, st);   // (one row of 128 columns: the planes of two workgroups do not fit)
-        case C2B3_M64: return launch_c2b3_sl<2, 2, 1, 7, KH, KW, Q, QH>(p, x, wp, bias, res, p.mask, y, st);
-        case C2B3_M32: return launch_c2b3_sl<1, 2, 1, 7, KH, KW, Q, QH>(p, x, wp, bias, res, p.mask, y, st);
-        default: return fail(AGX_ERR_UNSUPPORTED, "conv2d_b3: unsupported layer");
+// tap shape of a layer; F: strided FORWARD, space-to-depth.  The (KH, KW, Q, QH) of each are the columns of C2b3Tile::launch.
+enum C2b3Taps { C2B3_T33, C2B3_T22, C2B3_T32, C2B3_T22F, C2B3_T32F, C2B3_NTAPS };
+
+// One row per tile shape: the host facts of the tile and its instantiations, one per tap shape
+struct C2b3Tile {
+    int exact_m;        // the tile is the layer's whole M (0: any multiple of bm)
+    int bm, bn, sl_max;
+    int (*launch[C2B3_NTAPS])(const ConvPlan &, const float *, const float *, const float *, const float *, float *, hipStream_t);
+    const char *name[C2B3_NTAPS];   // pinned: tests/golden/kernel_names.json
+};
+template <class T>
+static constexpr C2b3Tile c2b3_tile(int exact_m, const char *n33, const char *n22, const char *n32, const char *n22f, const char *n32f) {
+    return {exact_m, T::BM, T::BN, T::SLMAX,
+            {launch_c2b3_sl<T, 3, 3, 1, 1>, launch_c2b3_sl<T, 2, 2, 2, 2>, launch_c2b3_sl<T, 3, 2, 2, 1>, launch_c2b3_sl<T, 2, 2, 1, 1>,
+             launch_c2b3_sl<T, 3, 2, 1, 1>},
+            {n33, n22, n32, n22f, n32f}};
+}
+static const C2b3Tile kC2b3Tiles[] = {
+    // (one row of 128 columns: the planes of two workgroups do not fit)
+    c2b3_tile<C2b3TileGeom<2, 2, 2, 6>>(0, "conv2d_b3<3x3,128x128>", "conv2d_b3<2x2 phases 2x2,128x128>", "conv2d_b3<3x2 phases 1x2,128x128>",
+                                        "conv2d_b3<4x4 s2 as 2x2 s2d,128x128>", "conv2d_b3<3x4 s(1,2) as 3x2 s2d,128x128>"),
+    c2b3_tile<C2b3TileGeom<2, 2, 1, 7>>(64, "conv2d_b3<3x3,64x256>", "conv2d_b3<2x2 phases 2x2,64x256>", "conv2d_b3<3x2 phases 1x2,64x256>",
+                                        "conv2d_b3<4x4 s2 as 2x2 s2d,64x256>", "conv2d_b3<3x4 s(1,2) as 3x2 s2d,64x256>"),
+    c2b3_tile<C2b3TileGeom<1, 2, 1, 7>>(32, "conv2d_b3<3x3,32x256>", "conv2d_b3<2x2 phases 2x2,32x256>", "conv2d_b3<3x2 phases 1x2,32x256>",
+                                        "conv2d_b3<4x4 s2 as 2x2 s2d,32x256>", "conv2d_b3<3x4 s(1,2) as 3x2 s2d,32x256>")};
+
+// shape-only test (also decides whether the conv2d pack functions append the B3 tile image: conv2d.hip): the tile (null: no ring
+// form) and the tap shape
+struct C2b3Geo {
+    const C2b3Tile *tile;
+    C2b3Taps taps;
+};
+static C2b3Geo c2b3_geo(const ConvPlan &p) {
+    const C2b3Geo none = {nullptr, C2B3_T33};
+    if (p.prec != 1 || p.G != 1 || p.pm_R <= 0 || p.d != 1) return none;
+    if (p.cin_real != p.Cin || p.ncv != p.Cin) return none;
+    C2b3Taps taps;
+    if (p.s == 2 && p.q == 1 && p.qh == 1 && p.P == 1 && p.ph == 1 && p.oshift == 0 && p.oshift_h == 0 && p.Cin % 16 == 0 &&
+        ((p.sh == 2 && p.kh == 4 && p.J == 16) || (p.sh == 1 && p.kh == 3 && p.J == 12))) {
+        // FORWARD of the (4,4)/(2,2) and (3,4)/(1,2) layers, pad (1,1): space-to-depth = sh sw Cin virtual channels (16-channel
+        // chunks stay inside one phase), 2 x 2 resp. 3 x 2 taps, stride 1 (conv2d_b3_kernel's staging)
+        if (p.Lt != p.Lout || p.Tt != p.Tout) return none;
+        taps = p.sh == 2 ? C2B3_T22F : C2B3_T32F;
+    } else if (p.s != 1 || p.sh != 1 || p.Cin % 32 != 0) {             // (stride-1 plans: whole 16-channel chunks, an even number)
+        return none;
+    } else if (p.kh == 3 && p.J == 9 && p.q == 1 && p.qh == 1) {      // 3 x 3, stride 1, "same": forward and backward-data
+        if (p.P != 1 || p.ph != 1 || p.oshift != 0 || p.oshift_h != 0) return none;
+        if (p.Lt != p.Lout || p.Tt != p.Tout || p.Lout != p.Lin || p.Tout != p.Tin) return none;
+        taps = C2B3_T33;
+    } else if (p.kh == 2 && p.J == 4 && p.q == 2 && p.qh == 2 && p.P == 1 && p.ph == 1) {
+        taps = C2B3_T22;                                              // backward-data of a 4 x 4 stride-(2, 2) layer
+    } else if (p.kh == 3 && p.J == 6 && p.q == 2 && p.qh == 1 && p.P == 1 && p.ph == 1 && p.oshift_h == 0 && p.Tt == p.Tout) {
+        taps = C2B3_T32;                                              // backward-data of a 3 x 4 stride-(1, 2) layer
+    } else {
+        return none;
     }
+    for (const C2b3Tile &t : kC2b3Tiles)
+        if (t.exact_m ? p.M == t.exact_m : p.M % t.bm == 0) return {&t, taps};
+    return none;
+}
+bool conv2d_b3_geometry(const ConvPlan &p) { return c2b3_geo(p).tile != nullptr; }
+
+bool conv2d_b3_supported(const ConvPlan &p) {
+    const C2b3Tile *tile = c2b3_geo(p).tile;
+    if (p.tile_off < 0 || !tile) return false;
+    {   // very narrow / ragged feature maps: beyond 1.4 x padded area the fp32 ring kernel wins
+        ConvPlan pp = p;
+        if (c2b3_peels_first_col(p)) pp.Lt = p.Lt - 1;
+        const int sl = c2b3_pick_sl(pp, tile->bn, tile->sl_max, 1, 1, 0);
+        const int R = tile->bn >> sl, WF = 1 << sl;
+        const int64_t area = int64_t(ceil_div(pp.Tt, R)) * R * ceil_div(pp.Lt, WF) * WF;
+        if (area * 10 > int64_t(pp.Tt) * pp.Lt * 14) return false;
+    }
+    if ((p.epilogue & ~(AGX_EPI_LEAKY_PRE | AGX_EPI_RESIDUAL | AGX_EPI_MASK)) != 0) return false;
+    if (p.x_cstride != int64_t(p.Tin) * p.Lin || p.y_cstride != int64_t(p.Tout) * p.Lout) return false;
+    if (p.x_cstride * 16 * 4 >= (int64_t(1) << 32) || p.y_cstride * p.Cout >= (int64_t(1) << 31)) return false;   // 32-bit offsets
+    return true;
+}
+
+const char *conv2d_b3_variant(const ConvPlan &p) {
+    const C2b3Geo g = c2b3_geo(p);
+    return g.tile ? g.tile->name[g.taps] : "conv2d_b3<unsupported>";
 }
 
 // res = the tensor added in the epilogue (AGX_EPI_RESIDUAL: backward-data, the gradient arriving at this feature map); p.mask as conv_p2d
 int launch_conv2d_b3(const ConvPlan &p, const float *x, const float *wp, const float *bias, const float *res, float *y, hipStream_t st) {
     if (!conv2d_b3_supported(p)) return fail(AGX_ERR_UNSUPPORTED, "conv2d_b3: unsupported layer");
-    const int geom = conv2d_b3_geometry(p);
-    if ((geom >> 4) == C2B3_T22F || (geom >> 4) == C2B3_T32F) {     // the virtual (space-to-depth) plan the kernel loops over
-        ConvPlan v = p;
+    const C2b3Geo g = c2b3_geo(p);
+    ConvPlan v = p;
+    if (g.taps == C2B3_T22F || g.taps == C2B3_T32F) {     // the virtual (space-to-depth) plan the kernel loops over
         v.Cin = p.sh * p.s * p.Cin;
-        v.kh = (geom >> 4) == C2B3_T22F ? 2 : 3;
+        v.kh = g.taps == C2B3_T22F ? 2 : 3;
         v.J = v.kh * 2;
-        return (geom >> 4) == C2B3_T22F ? launch_c2b3_tile<2, 2, 1, 1>(geom & 15, v, x, wp, bias, res, y, st)
-                                        : launch_c2b3_tile<3, 2, 1, 1>(geom & 15, v, x, wp, bias, res, y, st);
-    }
-    if ((geom >> 4) == C2B3_T33) return launch_c2b3_tile<3, 3, 1, 1>(geom & 15, p, x, wp, bias, res, y, st);
-    ConvPlan pp = p;
-    if (c2b3_peels_first_col(p)) {      // column phases: base position 0 (output column 0) on its own kernel, whole blocks for the ring
+    } else if (c2b3_peels_first_col(p)) {      // column phases (backward-data of a strided layer): base position 0 (output column 0) on its own kernel, whole blocks for the ring
         if (int64_t(p.B) * p.Tt > (int64_t(1) << 30)) return fail(AGX_ERR_BAD_SHAPE, "conv2d_b3: grid too large");
         hipLaunchKernelGGL(conv2d_b3_first_col_kernel, dim3(p.B * p.Tt), dim3(256), size_t(p.kh) * p.Cin * sizeof(float), st, p, x,
                            reinterpret_cast<const __bf16 *>(wp), res, p.mask, y);
-        pp.Lt = p.Lt - 1;
-        pp.oshift = p.oshift - 2;
-        pp.P = p.P - 1;
+        v.Lt = p.Lt - 1;
+        v.oshift = p.oshift - 2;
+        v.P = p.P - 1;
     }
-    return (geom >> 4) == C2B3_T22 ? launch_c2b3_tile<2, 2, 2, 2>(geom & 15, pp, x, wp, bias, res, y, st)
-                                   : launch_c2b3_tile<3, 2, 2, 1>(geom & 15, pp, x, wp, bias, res, y, st);
+    return g.tile->launch[g.taps](v, x, wp, bias, res, y, st);
 }
 
 }  // namespace agx

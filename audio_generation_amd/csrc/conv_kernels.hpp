@@ -23,6 +23,7 @@ int launch_conv_p2d(const ConvPlan &p, const float *x, const float *wp, const fl
 bool conv_b3_supported(const ConvPlan &p);
 const char *conv_b3_variant(const ConvPlan &p);
 int launch_conv_b3(const ConvPlan &p, const float *x, const float *wp, const float *bias, float *y, hipStream_t st);
+int conv_b3_planes(const ConvPlan &p);   // 0: fp32 input only, 1: the kernel can read activation planes, 2: and write them
 int launch_conv_b3_planes(const ConvPlan &p, const void *x_planes, const float *wp, const float *bias, float *y, void *y_planes, hipStream_t st);
 int launch_planes_split(const float *x, void *planes, int batch, int channels, int length, hipStream_t st);
 bool conv2d_b3_supported(const ConvPlan &p);

@@ -562,11 +562,8 @@ static int launch_cp(const ConvPlan &p, const float *x, const float *wp, const f
     static_assert(G::LDS_BYTES <= 160 * 1024, "ring does not fit LDS");
     const int mblocks = p.M / G::BM, nblocks = ceil_div(p.Lt, G::BN);
     const int64_t ntiles64 = int64_t(mblocks) * nblocks * p.B;
-    if (ntiles64 > (1 << 30)) return fail(AGX_ERR_BAD_SHAPE, "conv_p: too many tiles");
-    const int ntiles = int(ntiles64);
-    const int wg_per_cu = int((160 * 1024) / G::LDS_BYTES) >= 2 ? 2 : 1;
-    int grid = n_cu * wg_per_cu;
-    if (grid > ntiles) grid = ntiles;
+    const int grid = ring_grid(ntiles64, n_cu, ring_wgs_per_cu(G::LDS_BYTES)), ntiles = int(ntiles64);
+    if (grid < 0) return fail(AGX_ERR_BAD_SHAPE, "conv_p: too many tiles");
     // grid = sb * (mblocks * nblocks) + sn * mblocks + sm
     const int per_clip = mblocks * nblocks;
     const int sb = grid / per_clip, rem = grid % per_clip;
@@ -647,11 +644,8 @@ static int launch_cp2d(const ConvPlan &p, const float *x, const float *wp, const
     const int wfs = cp2d_wf_shift(pp.Lt, G::BN);   // tile = (BN >> wfs) rows x (1 << wfs) columns
     const int mblocks = pp.M / G::BM, nblocks = ceil_div(pp.Lt, 1 << wfs);
     const int64_t ntiles64 = int64_t(mblocks) * nblocks * pp.B * ceil_div(pp.Tt, G::BN >> wfs);
-    if (ntiles64 > (1 << 30)) return fail(AGX_ERR_BAD_SHAPE, "conv_p: too many tiles");
-    const int ntiles = int(ntiles64);
-    const int wg_per_cu = int((160 * 1024) / G::LDS_BYTES) >= 2 ? 2 : 1;
-    int grid = n_cu * wg_per_cu;
-    if (grid > ntiles) grid = ntiles;
+    const int grid = ring_grid(ntiles64, n_cu, ring_wgs_per_cu(G::LDS_BYTES)), ntiles = int(ntiles64);
+    if (grid < 0) return fail(AGX_ERR_BAD_SHAPE, "conv_p: too many tiles");
     const int per_row = mblocks * nblocks;
     const int sb = grid / per_row, rem = grid % per_row;
     hipLaunchKernelGGL(kern, dim3(grid), dim3(256), G::LDS_BYTES, st, pp, mblocks, nblocks, ntiles, rem % mblocks,
@@ -693,128 +687,110 @@ typedef CpGeom<2, 2, 2, 2, 16, 2, 1, 2, 0, 2, true, 1> Cp2dB2;      // (kh x 4, 
 typedef CpGeom<2, 2, 1, 4, 8, 2, 1, 2, 0, 2, true, 1> Cp2dB2M64;    // ... M = 64:                  64 x 256
 typedef CpGeom<2, 2, 2, 2, 16, 2, 1, 2, 0, 2, true, 2> Cp2dB2H2;    // (4 x 4, stride (2, 2)):    128 x 128
 
-enum { CP2D_NONE = 0, CP2D_K3, CP2D_K3M64, CP2D_K3M32, CP2D_K4S2, CP2D_K4S2M64, CP2D_B2, CP2D_B2M64, CP2D_B2H2 };
+// One row per instantiated geometry: everything the host knows about it.  A new geometry is a typedef above and a row below.
+struct CpRow {
+    const char *name;   // pinned: tests/golden/kernel_names.json
+    int exact_m;        // the tile is the layer's whole M (0: any multiple of BM)
+    int bn;             // columns per tile
+    bool (*fits)(const ConvPlan &);
+    int (*launch)(const ConvPlan &, const float *, const float *, const float *, const float *, float *, hipStream_t);
+};
 
-// weights-only part of the test: the packed image of a layer must not depend on the size of the feature map it is
-// later applied to (discriminator.py packs with a nominal size)
+// 1-D: does the layer have the geometry's phases, taps, step and left offset, and whole tiles / chunks of it?
+template <class G>
+static bool cp_fits(const ConvPlan &p) {
+    return p.q == G::Q && p.J == G::J && p.s == G::S && p.P == G::PL && p.M % G::BM == 0 && p.Cin % G::CCH == 0 &&
+           (G::J % 2 == 0 || (p.Cin / G::CCH) % 2 == 0) && p.Cin / G::CCH >= 2 && p.Cout <= G::NBIAS;
+}
+
+// Conv2d: weights-only test -- the packed image of a layer must not depend on the size of the feature map it is later applied
+// to (discriminator.py packs with a nominal size).  G::J counts the column taps.  Q > 1: backward-data of a column-stride-Q layer
+// with pad 1; the ring runs base positions 1 .. Lt - 1 (launch_cp2d), so its left offset is one less than the plan's.
 template <class G>
 static bool cp2d_fits(const ConvPlan &p) {
     const int ncc = p.Cin / G::CCH;
     const int nch = ncc * p.kh;
+    constexpr int PEEL = G::Q > 1 ? 1 : 0;
+    if (p.J != p.kh * G::J || p.s != G::S || p.q != G::Q || p.qh != G::QH || p.P != G::PL + PEEL || p.oshift != PEEL) return false;
+    if ((PEEL && p.sh != 1) || (G::QH == 1 && p.oshift_h != 0)) return false;
     return p.M % G::BM == 0 && p.Cin % G::CCH == 0 && p.Cin == p.cin_real && ncc >= 1 && nch >= 2 &&
            (G::J % 2 == 0 || nch % 2 == 0) && p.Cout <= G::NBIAS;
 }
 
-// patch-mode plan of conv2d.hip (forward, or backward-data of a stride-1 layer) -> ring geometry; depends on the
-// layer (channels, kernel, strides, padding) only: decides whether the packed image carries a tile image
-int conv_p2d_geometry(const ConvPlan &p) {
-    if (p.pm_R == 0 || p.prec != 0 || p.G != 1 || p.d != 1 || p.kh <= 0 || p.J % p.kh != 0) return CP2D_NONE;
-    const int kw = p.J / p.kh;
-    if (p.q == 2 && kw == 2 && p.s == 1 && p.sh == 1 && p.P == 1 && p.oshift == 1) {   // backward-data, column stride 2, pad 1
-        if (p.qh == 1 && p.oshift_h == 0) {
-            if (p.M == 64 && cp2d_fits<Cp2dB2M64>(p)) return CP2D_B2M64;
-            if (cp2d_fits<Cp2dB2>(p)) return CP2D_B2;
-        }
-        if (p.qh == 2 && cp2d_fits<Cp2dB2H2>(p)) return CP2D_B2H2;
-        return CP2D_NONE;
-    }
-    if (p.q != 1 || p.qh != 1 || p.oshift != 0 || p.oshift_h != 0) return CP2D_NONE;
-    if (kw == 3 && p.s == 1 && p.P == 1) {
-        if (p.M == 32 && cp2d_fits<Cp2dK3M32>(p)) return CP2D_K3M32;
-        if (p.M == 64 && cp2d_fits<Cp2dK3M64>(p)) return CP2D_K3M64;
-        if (cp2d_fits<Cp2dK3>(p)) return CP2D_K3;
-    }
-    if (kw == 4 && p.s == 2 && p.P == 1) {
-        if (p.M == 64 && cp2d_fits<Cp2dK4S2M64>(p)) return CP2D_K4S2M64;
-        if (cp2d_fits<Cp2dK4S2>(p)) return CP2D_K4S2;
-    }
-    return CP2D_NONE;
+template <class G>
+static constexpr CpRow cp_row(const char *name, int exact_m = 0) {
+    if constexpr (G::D2) return {name, exact_m, G::BN, cp2d_fits<G>, launch_cp2d<G>};
+    else return {name, exact_m, G::BN, cp_fits<G>, launch_cp<G>};
 }
+
+static const CpRow kCp2dRows[] = {
+    cp_row<Cp2dB2M64>("conv_p2d<bwd s(1,2),64x256>", 64), cp_row<Cp2dB2>("conv_p2d<bwd s(1,2),128x128>"),
+    cp_row<Cp2dB2H2>("conv_p2d<bwd s(2,2),128x128>"),
+    cp_row<Cp2dK3M32>("conv_p2d<k3,32x512>", 32), cp_row<Cp2dK3M64>("conv_p2d<k3,64x256>", 64), cp_row<Cp2dK3>("conv_p2d<k3,128x128>"),
+    cp_row<Cp2dK4S2M64>("conv_p2d<k4s2,64x256>", 64), cp_row<Cp2dK4S2>("conv_p2d<k4s2,128x128>")};
+
+static const CpRow kCpRows[] = {
+    cp_row<CpDown2>("conv_p<down2,64x256>", 64), cp_row<CpDown3>("conv_p<down3,128x128>"), cp_row<CpDown4>("conv_p<down4,128x128>"),
+    cp_row<CpDown5>("conv_p<down5,128x128>"),    cp_row<CpDown8>("conv_p<down8,128x64>"),  cp_row<CpK3>("conv_p<k3,128x64>"),
+    cp_row<CpK7>("conv_p<k7,128x64>"),           cp_row<CpUp8>("conv_p<up8,128x64>"),      cp_row<CpUp5>("conv_p<up5,128x128>"),
+    cp_row<CpUp4>("conv_p<up4,128x128>"),        cp_row<CpUp3>("conv_p<up3,64x256>"),      cp_row<CpUp2>("conv_p<up2,64x256>", 64),
+    cp_row<CpK1>("conv_p<k1,128x128>"),          cp_row<CpSame11>("conv_p<same11,128x128>"), cp_row<CpSame3>("conv_p<same3,128x64>")};
+
+// the first row that fits, in table order (rows that differ by exact_m only: the exact ones first)
+template <size_t N>
+static const CpRow *cp_find(const CpRow (&rows)[N], const ConvPlan &p) {
+    for (const CpRow &r : rows)
+        if ((r.exact_m == 0 || p.M == r.exact_m) && r.fits(p)) return &r;
+    return nullptr;
+}
+
+// patch-mode plan of conv2d.hip (forward, or backward-data of a column-strided layer) -> ring geometry; depends on the
+// layer (channels, kernel, strides, padding) only: decides whether the packed image carries a tile image
+static const CpRow *cp2d_row(const ConvPlan &p) {
+    if (p.pm_R == 0 || p.prec != 0 || p.G != 1 || p.d != 1 || p.kh <= 0 || p.J % p.kh != 0) return nullptr;
+    return cp_find(kCp2dRows, p);
+}
+bool conv_p2d_geometry(const ConvPlan &p) { return cp2d_row(p) != nullptr; }
 
 // can THIS call run on the ring kernel?  (feature-map size: column blocks at least 70 % full -- narrow maps stay on the
 // patch tiles --, 32-bit DMA / epilogue offsets; epilogue: bias, LeakyReLU, gradient add, LeakyReLU-gradient mask)
 bool conv_p2d_supported(const ConvPlan &p) {
-    const int g = conv_p2d_geometry(p);
-    if (p.tile_off < 0 || g == CP2D_NONE) return false;
+    const CpRow *row = cp2d_row(p);
+    if (p.tile_off < 0 || !row) return false;
     if ((p.epilogue & ~(AGX_EPI_LEAKY_PRE | AGX_EPI_RESIDUAL | AGX_EPI_MASK)) != 0) return false;
     if (p.Lvalid != p.Lin || p.Lin < 4) return false;
     if (p.q == 1 && (p.Lt != p.Lout || p.Tt != p.Tout)) return false;
     if (int64_t(16) * p.x_cstride * 4 >= (int64_t(1) << 31)) return false;
     if (int64_t(p.Cout) * p.y_cstride * 4 >= (int64_t(1) << 32)) return false;
-    const int bn = g == CP2D_K3M32 ? 512 : ((g == CP2D_K3M64 || g == CP2D_K4S2M64 || g == CP2D_B2M64) ? 256 : 128);
     const int lt = p.q == 1 ? p.Lt : p.Lt - 1;   // column phases: the ring runs base positions 1 .. Lt - 1
     if (lt < 1) return false;
-    const int wf = 1 << cp2d_wf_shift(lt, bn);   // narrow maps: several rows per tile
+    const int wf = 1 << cp2d_wf_shift(lt, row->bn);   // narrow maps: several rows per tile
     return 10 * int64_t(lt) >= 7 * int64_t(ceil_div(lt, wf)) * wf;
 }
 
 const char *conv_p2d_variant(const ConvPlan &p) {
-    switch (conv_p2d_geometry(p)) {
-        case CP2D_K3: return "conv_p2d<k3,128x128>";
-        case CP2D_K3M64: return "conv_p2d<k3,64x256>";
-        case CP2D_K3M32: return "conv_p2d<k3,32x512>";
-        case CP2D_K4S2: return "conv_p2d<k4s2,128x128>";
-        case CP2D_K4S2M64: return "conv_p2d<k4s2,64x256>";
-        case CP2D_B2: return "conv_p2d<bwd s(1,2),128x128>";
-        case CP2D_B2M64: return "conv_p2d<bwd s(1,2),64x256>";
-        case CP2D_B2H2: return "conv_p2d<bwd s(2,2),128x128>";
-        default: return "conv_p2d<unsupported>";
-    }
+    const CpRow *row = cp2d_row(p);
+    return row ? row->name : "conv_p2d<unsupported>";
 }
 
 // res = the tensor added in the epilogue (AGX_EPI_RESIDUAL; backward-data: the gradient arriving at this feature map)
 int launch_conv_p2d(const ConvPlan &p, const float *x, const float *wp, const float *bias, const float *res, float *y,
                     hipStream_t st) {
     if (!conv_p2d_supported(p)) return fail(AGX_ERR_UNSUPPORTED, "conv_p2d: unsupported layer");
-    const float *add = (p.epilogue & AGX_EPI_RESIDUAL) ? res : nullptr;
-    switch (conv_p2d_geometry(p)) {
-        case CP2D_K3: return launch_cp2d<Cp2dK3>(p, x, wp, bias, add, y, st);
-        case CP2D_K3M64: return launch_cp2d<Cp2dK3M64>(p, x, wp, bias, add, y, st);
-        case CP2D_K3M32: return launch_cp2d<Cp2dK3M32>(p, x, wp, bias, add, y, st);
-        case CP2D_K4S2: return launch_cp2d<Cp2dK4S2>(p, x, wp, bias, add, y, st);
-        case CP2D_K4S2M64: return launch_cp2d<Cp2dK4S2M64>(p, x, wp, bias, add, y, st);
-        case CP2D_B2: return launch_cp2d<Cp2dB2>(p, x, wp, bias, add, y, st);
-        case CP2D_B2M64: return launch_cp2d<Cp2dB2M64>(p, x, wp, bias, add, y, st);
-        case CP2D_B2H2: return launch_cp2d<Cp2dB2H2>(p, x, wp, bias, add, y, st);
-        default: return fail(AGX_ERR_UNSUPPORTED, "conv_p2d: unsupported layer");
-    }
-}
-
-enum { CP_NONE = 0, CP_DOWN2, CP_DOWN4, CP_DOWN5, CP_DOWN8, CP_K3, CP_K7, CP_UP8, CP_UP5, CP_UP4, CP_UP2, CP_DOWN3, CP_UP3, CP_K1, CP_SAME11,
-       CP_SAME3 };
-
-template <class G>
-static bool cp_fits(const ConvPlan &p) {
-    return p.M % G::BM == 0 && p.Cin % G::CCH == 0 && (G::J % 2 == 0 || (p.Cin / G::CCH) % 2 == 0) && p.Cin / G::CCH >= 2 &&
-           p.Cout <= G::NBIAS;
+    return cp2d_row(p)->launch(p, x, wp, bias, (p.epilogue & AGX_EPI_RESIDUAL) ? res : nullptr, y, st);
 }
 
 // shape-only test (also decides whether agx_conv_pack appends a tile image: common.hpp)
-int conv_p_geometry(const ConvPlan &p) {
-    if (p.prec != 0 || p.G != 1 || p.d != 1 || p.kh != 1 || p.Tout != 1 || p.pm_R != 0) return CP_NONE;
-    const int J = p.J, S = p.s, Q = p.q, P = p.P;
-    if (Q == 1 && J == 5 && S == 2 && P == 3 && p.M == 64 && cp_fits<CpDown2>(p)) return CP_DOWN2;
-    if (Q == 1 && J == 7 && S == 3 && P == 4 && cp_fits<CpDown3>(p)) return CP_DOWN3;
-    if (Q == 1 && J == 9 && S == 4 && P == 5 && cp_fits<CpDown4>(p)) return CP_DOWN4;
-    if (Q == 1 && J == 11 && S == 5 && P == 6 && cp_fits<CpDown5>(p)) return CP_DOWN5;
-    if (Q == 1 && J == 17 && S == 8 && P == 9 && cp_fits<CpDown8>(p)) return CP_DOWN8;
-    if (Q == 1 && J == 3 && S == 1 && P == 2 && cp_fits<CpK3>(p)) return CP_K3;
-    if (Q == 1 && J == 7 && S == 1 && P == 6 && cp_fits<CpK7>(p)) return CP_K7;
-    if (Q == 8 && J == 3 && S == 1 && P == 1 && cp_fits<CpUp8>(p)) return CP_UP8;
-    if (Q == 5 && J == 3 && S == 1 && P == 1 && cp_fits<CpUp5>(p)) return CP_UP5;
-    if (Q == 4 && J == 3 && S == 1 && P == 1 && cp_fits<CpUp4>(p)) return CP_UP4;
-    if (Q == 3 && J == 3 && S == 1 && P == 1 && cp_fits<CpUp3>(p)) return CP_UP3;
-    if (Q == 2 && J == 3 && S == 1 && P == 1 && p.M == 64 && cp_fits<CpUp2>(p)) return CP_UP2;
-    if (Q == 1 && J == 1 && S == 1 && P == 0 && cp_fits<CpK1>(p)) return CP_K1;
-    if (Q == 1 && J == 11 && S == 1 && P == 5 && cp_fits<CpSame11>(p)) return CP_SAME11;
-    if (Q == 1 && J == 3 && S == 1 && P == 1 && cp_fits<CpSame3>(p)) return CP_SAME3;
-    return CP_NONE;
+static const CpRow *cp_row_of(const ConvPlan &p) {
+    if (p.prec != 0 || p.G != 1 || p.d != 1 || p.kh != 1 || p.Tout != 1 || p.pm_R != 0) return nullptr;
+    return cp_find(kCpRows, p);
 }
+bool conv_p_geometry(const ConvPlan &p) { return cp_row_of(p) != nullptr; }
 
 // can THIS call run on the ring kernel? (epilogue: bias + optional LeakyReLU; one-phase layers also GELU / residual / the
 // activation behind the residual)
 bool conv_p_supported(const ConvPlan &p) {
-    if (p.tile_off < 0 || conv_p_geometry(p) == CP_NONE) return false;
+    if (p.tile_off < 0 || !conv_p_geometry(p)) return false;
     const int epi_ok = p.q == 1 ? (AGX_EPI_LEAKY_PRE | AGX_EPI_RESIDUAL | AGX_EPI_LEAKY_POST | AGX_EPI_GELU_PRE) : AGX_EPI_LEAKY_PRE;
     if ((p.epilogue & ~epi_ok) != 0 || p.oshift != 0 || p.mask != nullptr) return false;
     if (p.Lvalid != p.Lin || p.Lin < 4 || p.Lout != p.q * p.Lt) return false;   // (ragged L: fix_ragged)
@@ -827,47 +803,14 @@ bool conv_p_supported(const ConvPlan &p) {
 }
 
 const char *conv_p_variant(const ConvPlan &p) {
-    switch (conv_p_geometry(p)) {
-        case CP_DOWN2: return "conv_p<down2,64x256>";
-        case CP_DOWN4: return "conv_p<down4,128x128>";
-        case CP_DOWN5: return "conv_p<down5,128x128>";
-        case CP_DOWN8: return "conv_p<down8,128x64>";
-        case CP_K3: return "conv_p<k3,128x64>";
-        case CP_K7: return "conv_p<k7,128x64>";
-        case CP_UP8: return "conv_p<up8,128x64>";
-        case CP_UP5: return "conv_p<up5,128x128>";
-        case CP_UP4: return "conv_p<up4,128x128>";
-        case CP_UP2: return "conv_p<up2,64x256>";
-        case CP_DOWN3: return "conv_p<down3,128x128>";
-        case CP_UP3: return "conv_p<up3,64x256>";
-        case CP_K1: return "conv_p<k1,128x128>";
-        case CP_SAME11: return "conv_p<same11,128x128>";
-        case CP_SAME3: return "conv_p<same3,128x64>";
-        default: return "conv_p<unsupported>";
-    }
+    const CpRow *row = cp_row_of(p);
+    return row ? row->name : "conv_p<unsupported>";
 }
 
 int launch_conv_p(const ConvPlan &p, const float *x, const float *wp, const float *bias, const float *res, float *y,
                   hipStream_t st) {
     if (!conv_p_supported(p)) return fail(AGX_ERR_UNSUPPORTED, "conv_p: unsupported layer");
-    switch (conv_p_geometry(p)) {
-        case CP_DOWN2: return launch_cp<CpDown2>(p, x, wp, bias, res, y, st);
-        case CP_DOWN4: return launch_cp<CpDown4>(p, x, wp, bias, res, y, st);
-        case CP_DOWN5: return launch_cp<CpDown5>(p, x, wp, bias, res, y, st);
-        case CP_DOWN8: return launch_cp<CpDown8>(p, x, wp, bias, res, y, st);
-        case CP_K3: return launch_cp<CpK3>(p, x, wp, bias, res, y, st);
-        case CP_K7: return launch_cp<CpK7>(p, x, wp, bias, res, y, st);
-        case CP_UP8: return launch_cp<CpUp8>(p, x, wp, bias, res, y, st);
-        case CP_UP5: return launch_cp<CpUp5>(p, x, wp, bias, res, y, st);
-        case CP_UP4: return launch_cp<CpUp4>(p, x, wp, bias, res, y, st);
-        case CP_UP2: return launch_cp<CpUp2>(p, x, wp, bias, res, y, st);
-        case CP_DOWN3: return launch_cp<CpDown3>(p, x, wp, bias, res, y, st);
-        case CP_UP3: return launch_cp<CpUp3>(p, x, wp, bias, res, y, st);
-        case CP_K1: return launch_cp<CpK1>(p, x, wp, bias, res, y, st);
-        case CP_SAME11: return launch_cp<CpSame11>(p, x, wp, bias, res, y, st);
-        case CP_SAME3: return launch_cp<CpSame3>(p, x, wp, bias, res, y, st);
-        default: return fail(AGX_ERR_UNSUPPORTED, "conv_p: unsupported layer");
-    }
+    return cp_row_of(p)->launch(p, x, wp, bias, res, y, st);
 }
 
 }  // namespace agx

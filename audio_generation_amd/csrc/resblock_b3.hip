@@ -488,10 +488,8 @@ static int launch_b3(const ConvPlan &p, const float *x, const float *w1, const f
     static_assert(G::LDS_BYTES * (NPB == 1 ? 2 : 1) <= 160 * 1024, "resblock_b3: LDS budget");
     const int tiles_per_clip = ceil_div(p.Lin, G::BN);
     const int64_t ntiles64 = int64_t(tiles_per_clip) * p.B;
-    if (ntiles64 > (1 << 30)) return fail(AGX_ERR_BAD_SHAPE, "resblock_b3: too many tiles");
-    const int ntiles = int(ntiles64);
-    const int want = n_cu * (NPB == 1 ? 2 : 1);            // persistent: two workgroups per CU where the LDS / registers allow
-    const int grid = ntiles < want ? ntiles : want;
+    const int grid = ring_grid(ntiles64, n_cu, NPB == 1 ? 2 : 1), ntiles = int(ntiles64);   // two workgroups per CU where the LDS / registers allow
+    if (grid < 0) return fail(AGX_ERR_BAD_SHAPE, "resblock_b3: too many tiles");
     // B3 tile images: behind the bf16x3 standard image and the dim0 scale scratch (common.hpp: b3 images)
     const char *wt1 = reinterpret_cast<const char *>(w1 + packed_weight_floats_bf(G::C, G::J, G::C) + G::C);
     const char *wt2 = reinterpret_cast<const char *>(w2 + packed_weight_floats_bf(G::C, 1, G::C) + G::C);
@@ -500,40 +498,53 @@ static int launch_b3(const ConvPlan &p, const float *x, const float *w1, const f
     return check_launch("resblock_b3");
 }
 
-// shapes the kernel is instantiated for: C in {32, 64, 128, 256}, k = 7, dilation in {1, 3, 9}, bf16x3 descriptors
+// One row per channel count the kernel is instantiated for (each with dilation 1, 3 and 9).
+// NPB = 1: one plane buffer, <= 256 registers: two workgroups per CU (one covers the other's vector work and barriers);
+// NPB = 2: double-buffered planes, one workgroup per CU with up to 512 registers (tiles too big for two)
+typedef int (*B3Launch)(const ConvPlan &, const float *, const float *, const float *, const float *, const float *, float *, int, hipStream_t);
+struct B3Fan {
+    B3Launch d[3];          // d = 1, 3, 9
+};
+struct B3Row {
+    int C;
+    const char *name;       // pinned: tests/golden/kernel_names.json
+    B3Fan launch, alt;      // alt: the diagnostic alternate of knob b3_dbg = 1 (null: none)
+};
+template <int MW, int NW, int NPB>
+static constexpr B3Fan b3_fan() {
+    return {{launch_b3<MW, NW, 1, NPB>, launch_b3<MW, NW, 3, NPB>, launch_b3<MW, NW, 9, NPB>}};
+}
+static const B3Row kB3Rows[] = {{B3Geom<1, 4, 1, 1>::C, "resblock_b3<1,4,x2>", b3_fan<1, 4, 1>(), {}},
+                                {B3Geom<2, 2, 1, 1>::C, "resblock_b3<2,2,x2>", b3_fan<2, 2, 1>(), b3_fan<2, 4, 2>()},
+                                {B3Geom<4, 1, 1, 1>::C, "resblock_b3<4,1,x2>", b3_fan<4, 1, 1>(), b3_fan<4, 2, 2>()},
+                                {B3Geom<8, 1, 1, 2>::C, "resblock_b3<8,1>", b3_fan<8, 1, 2>(), {}}};
+
+static const B3Row *b3_row_of(int channels) {
+    for (const B3Row &r : kB3Rows)
+        if (r.C == channels) return &r;
+    return nullptr;
+}
+bool resblock_b3_has(int channels) { return b3_row_of(channels) != nullptr; }
+
+// k = 7, dilation in {1, 3, 9}, bf16x3 descriptors
 bool resblock_b3_supported(const ConvPlan &p) {
-    if (p.prec != 1 || p.tile_off < 0 || p.Cin != p.Cout || p.s != 1 || p.q != 1 || p.J != 7 || p.G != 1) return false;
+    if (p.prec != 1 || p.tile_off < 0 || !resblock_layer(p) || p.J != 7 || !resblock_b3_has(p.Cin)) return false;
     if (p.Lvalid != p.Lin || p.Lt != p.Lin || p.Lin < 1) return false;
-    if (p.Cin != 32 && p.Cin != 64 && p.Cin != 128 && p.Cin != 256) return false;
     if (int64_t(p.Cin) * p.Lin * 4 >= (int64_t(1) << 32)) return false;
     return p.d == 1 || p.d == 3 || p.d == 9;
 }
 
 const char *resblock_b3_variant(const ConvPlan &p) {
-    switch (p.Cin) {
-        case 32: return "resblock_b3<1,4,x2>";
-        case 64: return "resblock_b3<2,2,x2>";
-        case 128: return "resblock_b3<4,1,x2>";
-        default: return "resblock_b3<8,1>";
-    }
+    const B3Row *row = b3_row_of(p.Cin);
+    return row ? row->name : "resblock_b3<unsupported>";
 }
 
 int launch_resblock_b3(const ConvPlan &p, const float *x, const float *w1, const float *b1, const float *w2, const float *b2,
                        float *y, int post_act, hipStream_t st) {
     if (!resblock_b3_supported(p)) return fail(AGX_ERR_UNSUPPORTED, "resblock_b3: unsupported shape");
-#define AGX_B3(MW, NW, NPB)                                                                  \
-    (p.d == 1 ? launch_b3<MW, NW, 1, NPB>(p, x, w1, b1, w2, b2, y, post_act, st)             \
-     : p.d == 3 ? launch_b3<MW, NW, 3, NPB>(p, x, w1, b1, w2, b2, y, post_act, st)           \
-                : launch_b3<MW, NW, 9, NPB>(p, x, w1, b1, w2, b2, y, post_act, st))
-    // <.., 1>: one plane buffer, <= 256 registers: two workgroups per CU (one covers the other's vector work and barriers);
-    // <.., 2>: double-buffered planes, one workgroup per CU with up to 512 registers (tiles too big for two)
-    switch (p.Cin) {
-        case 32: return AGX_B3(1, 4, 1);
-        case 64: return tuning().b3_dbg == 1 ? AGX_B3(2, 4, 2) : AGX_B3(2, 2, 1);
-        case 128: return tuning().b3_dbg == 1 ? AGX_B3(4, 2, 2) : AGX_B3(4, 1, 1);
-        default: return AGX_B3(8, 1, 2);
-    }
-#undef AGX_B3
+    const B3Row *row = b3_row_of(p.Cin);
+    const B3Fan &fan = (tuning().b3_dbg == 1 && row->alt.d[0]) ? row->alt : row->launch;
+    return fan.d[p.d == 1 ? 0 : p.d == 3 ? 1 : 2](p, x, w1, b1, w2, b2, y, post_act, st);
 }
 
 }  // namespace agx

@@ -470,13 +470,11 @@ static int launch_rbp(const ConvPlan &p, const float *x, const float *w1, const 
     if (int rc = prepare_kernel(reinterpret_cast<const void *>(kern), once, 160 * 1024, &n_cu, "resblock_p")) return rc;
     const int tiles_per_clip = ceil_div(p.Lin, G::BN);
     const int64_t ntiles64 = int64_t(tiles_per_clip) * p.B;
-    if (ntiles64 > (1 << 30)) return fail(AGX_ERR_BAD_SHAPE, "resblock_p: too many tiles");
-    const int ntiles = int(ntiles64);
-    int wg_per_cu = int((160 * 1024) / G::LDS_BYTES) >= 2 ? 2 : 1;
+    int wg_per_cu = ring_wgs_per_cu(G::LDS_BYTES);
     size_t lds_bytes = G::LDS_BYTES;
     if (tuning().rb_wgs == 1) wg_per_cu = 1, lds_bytes = 100 * 1024;   // diagnostic: one workgroup per CU
-    int grid = n_cu * wg_per_cu;
-    if (grid > ntiles) grid = ntiles;
+    const int grid = ring_grid(ntiles64, n_cu, wg_per_cu), ntiles = int(ntiles64);
+    if (grid < 0) return fail(AGX_ERR_BAD_SHAPE, "resblock_p: too many tiles");
     // the tile images follow the standard image and the dim0 scale scratch in the packed buffers (common.hpp)
     const float *wt1 = w1 + packed_weight_floats(G::C, G::J, G::C) + G::C;
     const float *wt2 = w2 + packed_weight_floats(G::C, 1, G::C) + G::C;
@@ -485,38 +483,45 @@ static int launch_rbp(const ConvPlan &p, const float *x, const float *w1, const 
     return check_launch("resblock_p");
 }
 
-// shapes the persistent kernel is instantiated for: C in {32, 64, 128, 256}, k = 7, dilation in {1, 3, 9}, L % 4 == 0
+// One row per channel count the persistent kernel is instantiated for (each with dilation 1, 3 and 9)
+typedef int (*RbpLaunch)(const ConvPlan &, const float *, const float *, const float *, const float *, const float *, float *, int, hipStream_t);
+struct RbpRow {
+    int C;
+    const char *name;       // pinned: tests/golden/kernel_names.json
+    RbpLaunch launch[3];    // d = 1, 3, 9
+};
+template <int MW, int NW, int CCH, int NS>
+static constexpr RbpRow rbp_row(const char *name) {
+    return {RbpGeom<MW, NW, CCH, 1, NS>::C, name, {launch_rbp<MW, NW, CCH, 1, NS>, launch_rbp<MW, NW, CCH, 3, NS>, launch_rbp<MW, NW, CCH, 9, NS>}};
+}
+static const RbpRow kRbpRows[] = {
+    rbp_row<1, 4, 8, 3>("resblock_p<1,4,8>"), rbp_row<2, 2, 8, 3>("resblock_p<2,2,8>"), rbp_row<4, 1, 4, 3>("resblock_p<4,1,4>"),
+    rbp_row<8, 1, 4, 2>("resblock_p<8,1,4>")};   // 28.7 KB of weights per 4-channel chunk: two slots keep two workgroups per CU
+
+static const RbpRow *rbp_row_of(int channels) {
+    for (const RbpRow &r : kRbpRows)
+        if (r.C == channels) return &r;
+    return nullptr;
+}
+bool resblock_p_has(int channels) { return rbp_row_of(channels) != nullptr; }
+
+// k = 7, dilation in {1, 3, 9}, L % 4 == 0
 bool resblock_p_supported(const ConvPlan &p) {
-    if (p.prec != 0 || p.Cin != p.Cout || p.s != 1 || p.q != 1 || p.J != 7 || p.G != 1) return false;
+    if (p.prec != 0 || !resblock_layer(p) || p.J != 7 || !resblock_p_has(p.Cin)) return false;
     if (p.Lvalid != p.Lin || p.Lt != p.Lin || p.Lin % 4 != 0 || p.Lin < 4) return false;
-    if (p.Cin != 32 && p.Cin != 64 && p.Cin != 128 && p.Cin != 256) return false;
     if (int64_t(p.Cin) * p.Lin * 4 >= (int64_t(1) << 32)) return false;   // 32-bit byte offsets inside a clip
     return p.d == 1 || p.d == 3 || p.d == 9;
 }
 
 const char *resblock_p_variant(const ConvPlan &p) {
-    switch (p.Cin) {
-        case 32: return "resblock_p<1,4,8>";
-        case 64: return "resblock_p<2,2,8>";
-        case 128: return "resblock_p<4,1,4>";
-        default: return "resblock_p<8,1,4>";
-    }
+    const RbpRow *row = rbp_row_of(p.Cin);
+    return row ? row->name : "resblock_p<unsupported>";
 }
 
 int launch_resblock_p(const ConvPlan &p, const float *x, const float *w1, const float *b1, const float *w2,
                       const float *b2, float *y, int post_act, hipStream_t st) {
     if (!resblock_p_supported(p)) return fail(AGX_ERR_UNSUPPORTED, "resblock_p: unsupported shape");
-#define AGX_RBP(MW, NW, CCH, NS)                                                                 \
-    (p.d == 1 ? launch_rbp<MW, NW, CCH, 1, NS>(p, x, w1, b1, w2, b2, y, post_act, st)            \
-     : p.d == 3 ? launch_rbp<MW, NW, CCH, 3, NS>(p, x, w1, b1, w2, b2, y, post_act, st)          \
-                : launch_rbp<MW, NW, CCH, 9, NS>(p, x, w1, b1, w2, b2, y, post_act, st))
-    switch (p.Cin) {
-        case 32: return AGX_RBP(1, 4, 8, 3);
-        case 64: return AGX_RBP(2, 2, 8, 3);
-        case 128: return AGX_RBP(4, 1, 4, 3);
-        default: return AGX_RBP(8, 1, 4, 2);   // 28.7 KB of weights per 4-channel chunk: two slots keep two workgroups per CU
-    }
-#undef AGX_RBP
+    return rbp_row_of(p.Cin)->launch[p.d == 1 ? 0 : p.d == 3 ? 1 : 2](p, x, w1, b1, w2, b2, y, post_act, st);
 }
 
 }  // namespace agx
