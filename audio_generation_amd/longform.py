@@ -5,7 +5,7 @@ windows, the windows run AS A BATCH on the kernels that are tuned for batches, a
 result stitched back -- the plain forward's result from a batch of bounded windows.  Stateless (nothing is carried
 between calls), inference only.  Measured: this bounds activation memory, it does not make a clip faster.
 
-* ``receptive_field(model)`` walks the module tree and accumulates, layer by layer, which input positions one output
+* ``receptive_field(model)`` walks the model's unit lists (``CausalVQAE._units``) and accumulates, layer by layer, which input positions one output
   frame reads (pad rules of ``vae.py`` / ``wavelets.py``; nothing is hard-coded per configuration);
 * ``plan(...)`` is the window table: no window hangs over either end of the clip, because zero-filling a halo is not
   what the kernels' own padding does (every LAYER pads its own input with zeros; a zero-filled waveform halo comes out
@@ -19,10 +19,8 @@ from dataclasses import dataclass
 from typing import List, Optional, Tuple
 
 import torch
-from torch import nn
-
 from . import ops
-from ._lib import CONV_CAUSAL, CONV_PADDED, CONV_TRANSPOSED, CONV_UPSAMPLE, needs_grad
+from ._lib import needs_grad
 
 Tensor = torch.Tensor
 
@@ -31,49 +29,10 @@ def _ceil_div(a: int, b: int) -> int:
     return -((-a) // b)
 
 
-# --------------------------------------------------------------------------- layer walk
-def _primitives(m: nn.Module) -> List[tuple]:
-    """The layers of ``m`` that move information along time, in execution order, as
-    ``("causal", k, stride, dilation)`` / ``("convt", k, stride)`` / ``("up", k, stride)`` /
-    ``("wavelet", k_in, scale, n_points, k_out)`` / ``("multires", k, depth)``."""
-    from .vae import (CausalDecoderBlock, CausalEncoderBlock, CausalResidualBlock1d, _ConvBase)
-    from .wavelets import CausalMultiresConv1d, WaveletLayer
-
-    if isinstance(m, CausalResidualBlock1d):
-        # x + conv_k1(act(conv_k7,dil(x))): only the dilated conv reaches back (the depthwise variant's extra conv is k = 1 too)
-        conv = m.conv1[1] if m.depthwise else m.conv1
-        return _primitives(conv) + _primitives(m.conv2)
-    if isinstance(m, _ConvBase):
-        c = m.conv
-        k, s, d = c.kernel_size[0], c.stride[0], c.dilation[0]
-        if m.kind == CONV_CAUSAL:
-            return [("causal", k, s, d)]
-        if m.kind == CONV_PADDED:
-            if k != 1 or s != 1:
-                raise NotImplementedError("receptive_field: grouped conv with kernel > 1")
-            return []
-        if m.kind == CONV_TRANSPOSED:
-            return [("convt", k, s)]
-        if m.kind == CONV_UPSAMPLE:
-            return [("up", k, s)]
-        raise NotImplementedError(f"receptive_field: conv kind {m.kind}")
-    if isinstance(m, WaveletLayer):
-        return [("wavelet", m.wavelet_kernel_size, m.scale_factor, m.n_points, m.out_conv_kernel_size)]
-    if isinstance(m, CausalMultiresConv1d):
-        return [("multires", m.kernel_size, m.depth)]
-    if isinstance(m, CausalEncoderBlock):
-        out = _primitives(m.layers)
-        return out + (_primitives(m.multires) if hasattr(m, "multires") else [])
-    if isinstance(m, CausalDecoderBlock):
-        out = _primitives(m.in_conv[0])
-        if hasattr(m, "multires"):
-            out += _primitives(m.multires)
-        return out + _primitives(m.layers)
-    if isinstance(m, (nn.Sequential, nn.ModuleList)):
-        return [p for child in m for p in _primitives(child)]
-    if isinstance(m, (nn.Identity, nn.LeakyReLU, nn.ReLU, nn.GELU, nn.Dropout)):
-        return []                                                   # pointwise
-    raise NotImplementedError(f"receptive_field: no rule for {type(m).__name__}")
+# --------------------------------------------------------------------------- layer rules
+def _primitives(model, which: str) -> List[tuple]:
+    """The layers of a stack that move information along time, in execution order (``Unit.primitives``)."""
+    return [p for u in model._units(which) for p in u.primitives()]
 
 
 def _same_pads(k: int) -> Tuple[int, int]:
@@ -172,7 +131,7 @@ def stack_reach(layers: List[tuple]):
 def receptive_field(model) -> ReceptiveField:
     """Derived from ``model.encoders`` / ``model.decoders`` as they are wired (see the module docstring)."""
     _require_foldable(model)
-    enc, dec = _primitives(model.encoders), _primitives(model.decoders)
+    enc, dec = _primitives(model, "encoders"), _primitives(model, "decoders")
     e_down, e_up, e_left, e_right, _ = stack_reach(enc)
     d_down, d_up, d_left, d_right, d_quirk = stack_reach(dec)
     sf = int(model.scale_factor)
@@ -251,9 +210,10 @@ def _require_inference(model, x: Tensor) -> None:
 
 
 def _rf(model) -> ReceptiveField:
-    key = tuple(_primitives(model.encoders)), tuple(_primitives(model.decoders)), int(model.scale_factor)
+    """``receptive_field(model)``, kept for as long as the unit lists it was derived from are the model's."""
+    key = model._units("encoders"), model._units("decoders")
     cached = model.__dict__.get("_longform_rf")
-    if cached is None or cached[0] != key:
+    if cached is None or cached[0][0] is not key[0] or cached[0][1] is not key[1]:
         cached = (key, receptive_field(model))
         model.__dict__["_longform_rf"] = cached
     return cached[1]

@@ -26,6 +26,8 @@ from torch import nn
 from . import ops
 from ._lib import (CONV_CAUSAL, CONV_PADDED, CONV_TRANSPOSED, CONV_UPSAMPLE, EPI_LEAKY_POST, EPI_LEAKY_PRE,
                    IMPL_AUTO, IMPL_MFMA_BF16X3, AgxError, needs_grad)
+from .native_backward import run_stack
+from .units import Unit, detached, leaky_slope, packed_image
 
 Tensor = torch.Tensor
 
@@ -38,18 +40,6 @@ def tuple_checker(item, length):
     elif isinstance(item, (tuple, list)):
         assert len(item) == length, f"Expected tuple of length {length}, got {len(item)}"
     return item
-
-
-def _leaky_slope(act: Optional[nn.Module]) -> Optional[float]:
-    """Negative slope if ``act`` is an activation the kernels fuse."""
-    if act is None or isinstance(act, nn.Identity):
-        return None
-    if isinstance(act, nn.LeakyReLU):
-        return float(act.negative_slope)
-    if isinstance(act, nn.ReLU):
-        return 0.0
-    raise NotImplementedError(
-        f"activation {type(act).__name__} has no HIP kernel (LeakyReLU / ReLU are fused into the convs)")
 
 
 class _ConvParams(nn.Module):
@@ -86,59 +76,63 @@ class _ConvParams(nn.Module):
         else:
             self.weight = nn.Parameter(w)
             self.register_parameter("bias", bias_p)
-        self._packed: Optional[Tensor] = None
-        self._packed_key = None
+
+    def weights(self):
+        """(direction, gain) of the weight-normed layer, (weight, None) of a plain one."""
+        return (self.weight_v, self.weight_g) if hasattr(self, "weight_v") else (self.weight, None)
 
     def packed_bwd(self, kind: int) -> Tensor:
         """Packed image of the layer's backward-data op (same invalidation rule as ``packed``)."""
-        if hasattr(self, "weight_v"):
-            v, g = self.weight_v, self.weight_g
-            key = (kind, v.data_ptr(), v._version, g.data_ptr(), g._version)
-        else:
-            v, g = self.weight, None
-            key = (kind, v.data_ptr(), v._version)
-        if getattr(self, "_packed_bwd", None) is None or self._packed_bwd_key != key:
-            desc = ops.conv_desc(kind, 1, self.in_channels, self.out_channels, 1 << 20,
-                                 self.kernel_size[0], self.stride[0], self.dilation[0])
-            self._packed_bwd = ops.conv_pack_bwd(desc, v.detach(), None if g is None else g.detach())
-            self._packed_bwd_key = key
-        return self._packed_bwd
+        return packed_image(self, "conv_pack_bwd", kind)
 
     def packed(self, kind: int, impl: int = IMPL_AUTO) -> Tensor:
-        """Packed (weight-norm folded) image, rebuilt when the parameters change
-        (optimizer step, ``load_state_dict``, ``.to(device)``).  The bf16x3 kernels have their own image."""
-        bf = impl == IMPL_MFMA_BF16X3
-        if hasattr(self, "weight_v"):
-            v, g = self.weight_v, self.weight_g
-            key = (kind, bf, v.data_ptr(), v._version, g.data_ptr(), g._version)
-        else:
-            v, g = self.weight, None
-            key = (kind, bf, v.data_ptr(), v._version)
-        if self._packed is None or self._packed_key != key:
-            desc = ops.conv_desc(kind, 1, self.in_channels, self.out_channels, 1 << 20,
-                                 self.kernel_size[0], self.stride[0], self.dilation[0],
-                                 impl=IMPL_MFMA_BF16X3 if bf else IMPL_AUTO, groups=self.groups)
-            self._packed = ops.conv_pack(desc, v.detach(), None if g is None else g.detach())
-            self._packed_key = key
-        return self._packed
+        """Packed (weight-norm folded) image, rebuilt when the parameters change.  The bf16x3 kernels have their own image."""
+        return packed_image(self, "conv_pack", kind, impl=IMPL_MFMA_BF16X3 if impl == IMPL_MFMA_BF16X3 else IMPL_AUTO,
+                            groups=self.groups)
 
 
 class _ConvBase(nn.Module):
     kind = CONV_CAUSAL
     impl = IMPL_AUTO  # tests override to pin a kernel family
+    _primitive = {CONV_CAUSAL: "causal", CONV_TRANSPOSED: "convt", CONV_UPSAMPLE: "up"}
+
+    def desc(self, shape, epilogue: int = 0, slope: float = 0.1, impl: Optional[int] = None):
+        """The layer's descriptor for an input of ``shape`` (B, C, L); ``impl`` overrides the layer's own (the nominal
+        bf16x3 query of ``set_conv_arithmetic``, the grouped k = 1 layer's backward, which is always ``IMPL_AUTO``)."""
+        c = self.conv
+        return ops.conv_desc(self.kind, shape[0], c.in_channels, c.out_channels, shape[2], c.kernel_size[0], c.stride[0],
+                             c.dilation[0], epilogue, slope, self.impl if impl is None else impl, groups=c.groups)
 
     def run(self, x: Tensor, epilogue: int = 0, slope: float = 0.1, res: Optional[Tensor] = None) -> Tensor:
         c = self.conv
         if x.dim() != 3 or x.shape[1] != c.in_channels:
             raise AgxError(f"{type(self).__name__}: expected (B,{c.in_channels},L), got {tuple(x.shape)}")
-        desc = ops.conv_desc(self.kind, x.shape[0], c.in_channels, c.out_channels, x.shape[2],
-                             c.kernel_size[0], c.stride[0], c.dilation[0], epilogue, slope, self.impl,
-                             groups=getattr(c, "groups", 1))
-        bias = None if c.bias is None else c.bias.detach()
-        return ops.conv_forward(desc, x, c.packed(self.kind, self.impl), bias, res)
+        return ops.conv_forward(self.desc(x.shape, epilogue, slope), x, c.packed(self.kind, self.impl), detached(c.bias), res)
+
+    def run_fused(self, x: Tensor, post_slope: Optional[float] = None) -> Tensor:
+        """``act(conv(x))`` with the activation folded into the kernel."""
+        return self.run(x, EPI_LEAKY_PRE if post_slope is not None else 0, post_slope or 0.0)
 
     def forward(self, x: Tensor) -> Tensor:
         return self.run(x)
+
+    def units(self, act: Optional[nn.Module] = None) -> List[Unit]:
+        return [Unit("conv", self, [self], leaky_slope(act), bare=act is None)]
+
+    def params(self) -> List[Tensor]:
+        """[weight_v, weight_g, bias] / [weight, bias]: the order of the gradients ``native_backward`` returns."""
+        return [p for p in (*self.conv.weights(), self.conv.bias) if p is not None]
+
+    def primitives(self) -> List[tuple]:
+        c = self.conv
+        k, s, d = c.kernel_size[0], c.stride[0], c.dilation[0]
+        if self.kind == CONV_PADDED:       # the grouped k = 1 conv moves nothing along time
+            if k != 1 or s != 1:
+                raise NotImplementedError("receptive_field: grouped conv with kernel > 1")
+            return []
+        if self.kind not in self._primitive:
+            raise NotImplementedError(f"receptive_field: conv kind {self.kind}")
+        return [(self._primitive[self.kind], k, s) + ((d,) if self.kind == CONV_CAUSAL else ())]
 
 
 class CausalConv1d(_ConvBase):
@@ -198,10 +192,8 @@ class CausalResidualBlock1d(nn.Module):
         if depthwise:   # vae.py:103-105: a per-channel k = 1 conv in front of the dilated conv (three launches, unfused)
             self.conv1 = nn.Sequential(CausalConv1d(in_channels, in_channels, 1, bias=bias, groups=in_channels),
                                        CausalConv1d(in_channels, out_channels, kernel_size, dilation=dilation, bias=bias))
-            object.__setattr__(self.conv1[0], "_parent_block", self)
         else:
             self.conv1 = CausalConv1d(in_channels, out_channels, kernel_size, dilation=dilation, bias=bias)
-            object.__setattr__(self.conv1, "_parent_block", self)   # plain attribute: no module cycle
         self.conv2 = CausalConv1d(out_channels, out_channels, 1, bias=bias)
         self.activation = nn.LeakyReLU(0.1) if activation is None else activation
         self.dropout = nn.Dropout(dropout)
@@ -209,29 +201,33 @@ class CausalResidualBlock1d(nn.Module):
     def run(self, x: Tensor, post_slope: Optional[float] = None) -> Tensor:
         """Whole block (+ the activation that follows it in the enclosing
         ``Sequential`` when ``post_slope`` is given) through ``agx_resblock_forward``."""
-        slope = _leaky_slope(self.activation)
+        slope = leaky_slope(self.activation)
         if self.depthwise:
             h = self.conv1[1].run(self.conv1[0].run(x), EPI_LEAKY_PRE if slope is not None else 0, slope or 0.0)
             if slope is None:
                 h = self.activation(h)
             epi = ops.EPI_RESIDUAL | (EPI_LEAKY_POST if post_slope is not None else 0)
             return self.conv2.run(h, epi, post_slope or 0.0, res=x)
-        c1, c2 = self.conv1.conv, self.conv2.conv
         if self.split_launches or slope is None or (post_slope is not None and post_slope != slope):
             # exotic activation mix: two convs with separate epilogues
             h = self.conv1.run(x, EPI_LEAKY_PRE if slope is not None else 0, slope or 0.0)
             epi = ops.EPI_RESIDUAL | (EPI_LEAKY_POST if post_slope is not None else 0)
             return self.conv2.run(h, epi, post_slope or 0.0, res=x)
-        desc = ops.conv_desc(CONV_CAUSAL, x.shape[0], c1.in_channels, c1.out_channels, x.shape[2],
-                             c1.kernel_size[0], 1, c1.dilation[0], 0, slope, self.conv1.impl)
-        b1 = None if c1.bias is None else c1.bias.detach()
-        b2 = None if c2.bias is None else c2.bias.detach()
-        impl = self.conv1.impl
-        return ops.resblock_forward(desc, x, c1.packed(CONV_CAUSAL, impl), b1, c2.packed(CONV_CAUSAL, impl), b2,
-                                    post_act=post_slope is not None)
+        c1, c2, impl = self.conv1.conv, self.conv2.conv, self.conv1.impl
+        return ops.resblock_forward(self.conv1.desc(x.shape, 0, slope), x, c1.packed(CONV_CAUSAL, impl), detached(c1.bias),
+                                    c2.packed(CONV_CAUSAL, impl), detached(c2.bias), post_act=post_slope is not None)
+
+    run_fused = run
 
     def forward(self, x: Tensor) -> Tensor:
         return self.run(x, None)
+
+    def units(self, act: Optional[nn.Module] = None) -> List[Unit]:
+        """One unit; a block whose own activation the kernels do not fuse (``nn.Identity``) runs, and has no backward."""
+        inner = leaky_slope(self.activation)
+        convs = [*self.conv1, self.conv2] if self.depthwise else [self.conv1, self.conv2]
+        return [Unit("resdw" if self.depthwise else "res", self, convs, leaky_slope(act), inner,
+                     None if inner is not None else f"a residual block around {type(self.activation).__name__}")]
 
 
 def _default_act():
@@ -256,12 +252,11 @@ class CausalEncoderBlock(nn.Module):
             from .wavelets import CausalMultiresConv1d
             self.multires = CausalMultiresConv1d(out_channels, multires[0], multires[1])
 
+    def units(self, act: Optional[nn.Module] = None) -> List[Unit]:
+        return [u for m, a in (*self.layers, *_multires_pair(self)) for u in m.units(a)]
+
     def forward(self, x: Tensor) -> Tensor:
-        for seq in self.layers:
-            x = _run_fused_pair(seq[0], seq[1], x)
-        if hasattr(self, "multires"):
-            x = self.multires._hip(x)
-        return x
+        return _run_units(self.units(), x)
 
 
 class CausalDecoderBlock(nn.Module):
@@ -292,38 +287,25 @@ class CausalDecoderBlock(nn.Module):
                                                 depthwise=depthwise), activation)
             for i in range(n_layers - 1)])
 
+    def units(self, act: Optional[nn.Module] = None) -> List[Unit]:
+        return [u for m, a in (self.in_conv, *_multires_pair(self), *self.layers) for u in m.units(a)]
+
     def forward(self, x: Tensor) -> Tensor:
-        x = _run_fused_pair(self.in_conv[0], self.in_conv[1], x)
-        if hasattr(self, "multires"):
-            x = self.multires._hip(x)
-        for seq in self.layers:
-            x = _run_fused_pair(seq[0], seq[1], x)
-        return x
+        return _run_units(self.units(), x)
 
 
-def _run_unit_forward(unit, x: Tensor) -> Tensor:
-    """Forward of one unit of native_backward.build_units (same fused kernels as inference)."""
-    if unit.kind in ("res", "resdw"):
-        res = unit.convs[0]._parent_block
-        return res.run(x, unit.slope)
-    if unit.kind == "wavelet":
-        return unit.convs[0].run_fused(x, unit.slope)
-    if unit.kind == "multires":
-        return unit.convs[0]._hip(x)
-    conv = unit.convs[0]
-    return conv.run(x, EPI_LEAKY_PRE if unit.slope is not None else 0, unit.slope or 0.0)
+def _multires_pair(block: nn.Module):
+    """The block's build-defined multires layer as a (layer, activation) pair like the block's ``Sequential``s, if it has one."""
+    return [(block.multires, None)] if hasattr(block, "multires") else []
 
 
-def _run_fused_pair(layer: nn.Module, act: nn.Module, x: Tensor) -> Tensor:
-    """``act(layer(x))`` with the activation folded into the layer's kernel."""
-    slope = _leaky_slope(act)
-    if isinstance(layer, CausalResidualBlock1d):
-        return layer.run(x, slope)
-    if isinstance(layer, _ConvBase):
-        return layer.run(x, EPI_LEAKY_PRE if slope is not None else 0, slope or 0.0)
-    if hasattr(layer, "run_fused"):  # WaveletLayer
-        return layer.run_fused(x, slope)
-    raise NotImplementedError(f"no HIP path for {type(layer).__name__}")
+def _run_units(units: Sequence[Unit], x: Tensor) -> Tensor:
+    """Inference walk.  A bare conv runs as its ``forward()``, a conv behind ``nn.Identity`` as ``run_fused(x, None)``: the same
+    launch, but the descriptor's slope field (unread without an epilogue) is 0.1 in the one and 0.0 in the other, and 0.0 in
+    the training forward of both -- kept as recorded in tests/golden/stack_launch_trace.json."""
+    for u in units:
+        x = u.layer(x) if u.bare else u.forward(x)
+    return x
 
 
 class CausalVQAE(nn.Module):
@@ -401,13 +383,12 @@ class CausalVQAE(nn.Module):
                 if isinstance(m, _ConvBase):
                     c = m.conv
                     q = c.stride[0] if m.kind in (CONV_TRANSPOSED, CONV_UPSAMPLE) else 1
-                    ok = mode == "bf16x3" and c.in_channels % 16 == 0 and q * c.out_channels >= 32 and getattr(c, "groups", 1) == 1
+                    ok = mode == "bf16x3" and c.in_channels % 16 == 0 and q * c.out_channels >= 32 and c.groups == 1
                     # resampling convs: bf16x3 where the layer has the ring form (conv_b3.hip: the decoder's up-convs and
                     # the k = 7 transposed conv) or where the first-round bf16x3 kernel beats the fp32 ring kernel (the
                     # stride-4 down-conv; tools/layer_times.py bf16x3); the others stay on the fp32 ring, which is at least as exact
                     if ok and id(m) not in in_block:
-                        nominal = ops.conv_desc(m.kind, 1, c.in_channels, c.out_channels, 4096, c.kernel_size[0], c.stride[0],
-                                                c.dilation[0], EPI_LEAKY_PRE, 0.1, IMPL_MFMA_BF16X3)
+                        nominal = m.desc((1, c.in_channels, 4096), EPI_LEAKY_PRE, 0.1, IMPL_MFMA_BF16X3)
                         ok = ops.conv_kernel_name(nominal).startswith("conv_b3") or (m.kind == CONV_CAUSAL and c.stride[0] == 4)
                     m.impl = IMPL_MFMA_BF16X3 if ok else IMPL_AUTO
         self.__dict__.pop("_unit_cache", None)
@@ -421,76 +402,61 @@ class CausalVQAE(nn.Module):
         return x.transpose(1, 2).contiguous() if self.input_format == "b l c" else x
 
     def _encoders_hip(self, x: Tensor) -> Tensor:
-        first = self.encoders[0]
-        if not isinstance(first[0], nn.Identity):
-            raise NotImplementedError("only norm=Identity (the reference default) has a HIP path")
-        x = first[1].run(x)
-        for enc in list(self.encoders)[1:]:
-            x = enc(x)
-        return x
+        return _run_units(self._units("encoders"), x)
 
     def _decoders_hip(self, x: Tensor) -> Tensor:
-        decs = list(self.decoders)
-        x, decs = self._decoder_head_on_planes(x, decs)
-        for dec in decs:
-            x = dec(x)
-        return x
+        x, units = self._decoder_head_on_planes(x, self._units("decoders"))
+        return _run_units(units, x)
 
     def _decoder_head_on_planes(self, x: Tensor, decs):
         """bf16x3 decoders, inference: the k = 7 transposed conv (vae.py:269) writes its output as ACTIVATION PLANES
         (include/agx.h: the three bf16 pieces of every element, split once in the producer's epilogue) and the first
         block's polyphase up-conv (vae.py:176-179; M = 8 x 256 rows = 16 row blocks that each re-split the same input
         tile otherwise) stages them by LDS-DMA.  Bit-identical to the fp32-activation path (same pieces, same products,
-        same order: tests/test_gpu_conv_b3.py, test_gpu_fullsize.py); any other configuration takes the plain path."""
-        if torch.is_grad_enabled() or len(decs) < 2 or x.dim() != 3:
+        same order: tests/test_gpu_conv_b3.py, test_gpu_fullsize.py); any other configuration takes the plain path.
+        ``decs``: the decoder units; returns the activation and the units still to run."""
+        if torch.is_grad_enabled() or len(decs) < 2 or x.dim() != 3 or decs[0].kind != "conv" or decs[1].kind != "conv":
             return x, decs
-        head, blk = decs[0], decs[1]
-        if not (isinstance(head, CausalConvT1d) and head.impl == IMPL_MFMA_BF16X3 and isinstance(blk, CausalDecoderBlock)
-                and not blk.wavelet and not hasattr(blk, "multires")):
+        head, up, slope = decs[0].layer, decs[1].layer, decs[1].slope
+        if not (head.kind == CONV_TRANSPOSED and up.kind == CONV_UPSAMPLE and head.impl == up.impl == IMPL_MFMA_BF16X3
+                and decs[0].slope is None and x.shape[1] % 8 == 0 and (len(decs) < 3 or decs[2].kind != "multires")):
             return x, decs
-        up, act = blk.in_conv[0], blk.in_conv[1]
-        slope = _leaky_slope(act)
-        if not (isinstance(up, CausalUpsampleConv1d) and up.impl == IMPL_MFMA_BF16X3 and x.shape[1] % 8 == 0):
+        d0 = head.desc(x.shape)
+        if head.conv.stride[0] != 1 or ops.conv_planes_supported(d0) != 2:
             return x, decs
-        hc, uc = head.conv, up.conv
-        d0 = ops.conv_desc(head.kind, x.shape[0], hc.in_channels, hc.out_channels, x.shape[2], hc.kernel_size[0], hc.stride[0],
-                           hc.dilation[0], 0, 0.1, head.impl)
-        if hc.stride[0] != 1 or ops.conv_planes_supported(d0) != 2:
-            return x, decs
-        d1 = ops.conv_desc(up.kind, x.shape[0], uc.in_channels, uc.out_channels, ops.conv_out_len(d0), uc.kernel_size[0], uc.stride[0],
-                           uc.dilation[0], EPI_LEAKY_PRE if slope is not None else 0, slope or 0.0, up.impl)
+        d1 = up.desc((x.shape[0], None, ops.conv_out_len(d0)), EPI_LEAKY_PRE if slope is not None else 0, slope or 0.0)
         if ops.conv_planes_supported(d1) < 1:
             return x, decs
         xp = ops.planes_split(x)                                             # the RVQ's output: 15 MB at config S
-        yp = ops.conv_forward_planes(d0, xp, hc.packed(head.kind, head.impl), None if hc.bias is None else hc.bias.detach(),
-                                     out_planes=True)
-        h = ops.conv_forward_planes(d1, yp, uc.packed(up.kind, up.impl), None if uc.bias is None else uc.bias.detach())
-        for seq in blk.layers:
-            h = _run_fused_pair(seq[0], seq[1], h)
-        return h, decs[2:]
+        yp = ops.conv_forward_planes(d0, xp, head.conv.packed(head.kind, head.impl), detached(head.conv.bias), out_planes=True)
+        return ops.conv_forward_planes(d1, yp, up.conv.packed(up.kind, up.impl), detached(up.conv.bias)), decs[2:]
 
     def _run_encoders(self, x: Tensor) -> Tensor:
         """Encoder stack; when a gradient is needed, forward + backward on the HIP kernels (native_backward.py)."""
-        if needs_grad(x, self.encoders):
-            from .native_backward import run_stack
-            return run_stack(self._units("encoders"), x)
-        return self._encoders_hip(x)
+        return run_stack(self._units("encoders"), x) if needs_grad(x, self.encoders) else self._encoders_hip(x)
 
     def _run_decoders(self, x: Tensor) -> Tensor:
-        if needs_grad(x, self.decoders):
-            from .native_backward import run_stack
-            return run_stack(self._units("decoders"), x)
-        return self._decoders_hip(x)
+        return run_stack(self._units("decoders"), x) if needs_grad(x, self.decoders) else self._decoders_hip(x)
 
-    def _units(self, which: str):
-        """Flattened unit list of a stack for the native backward; a stack with a layer the backward kernels do not
-        cover raises (there is no ATen fallback)."""
+    def _units(self, which: str) -> List[Unit]:
+        """Unit list of ``self.encoders`` / ``self.decoders``: the ONE description of a stack.  Inference, the native backward
+        and ``longform.receptive_field`` all read it.  Built by the first call that reaches the stack and cached; what is
+        frozen then is the order of the units, their kinds and their slopes -- ``set_conv_arithmetic`` drops the cache, and so
+        must whoever rewires a stack by hand.  A layer's ``impl``, parameters and biases, ``split_launches`` and
+        ``torch.is_grad_enabled()`` (the planes head) are read by every call.  A unit without backward kernels is listed
+        (inference runs it); ``run_stack`` raises for it when a gradient is asked for."""
         cache = self.__dict__.setdefault("_unit_cache", {})
         if which not in cache:
-            from .native_backward import build_units
-            if which == "encoders" and not isinstance(self.encoders[0][0], nn.Identity):
-                raise NotImplementedError("only norm=Identity (the reference default) has HIP kernels")
-            cache[which] = build_units(getattr(self, which))
+            units: List[Unit] = []
+            for m in getattr(self, which):
+                if isinstance(m, nn.Sequential):      # encoders[0]: Sequential(norm(), conv)
+                    if len(m) != 2 or not isinstance(m[0], nn.Identity):
+                        raise NotImplementedError("only norm=Identity (the reference default) has HIP kernels")
+                    m = m[1]
+                if not hasattr(m, "units"):
+                    raise NotImplementedError(f"no HIP path for {type(m).__name__}")
+                units += m.units()
+            cache[which] = units
         return cache[which]
 
     def encode(self, x, update_codebook=False, codebook_n=None, prioritize_early=False):
@@ -540,7 +506,6 @@ class CausalVQAE(nn.Module):
     def sample(self, length=225, device="cuda", normal_var=5e3, n_iters=12):
         """vae.py:324-345: random codes -> dequantise -> decode."""
         self.to(device)
-        was_training = self.training
         self.eval()
         with torch.no_grad():
             x = None
@@ -550,22 +515,24 @@ class CausalVQAE(nn.Module):
                 x = x_i if x is None else x + x_i
             y = self.rearrange_out(self._run_decoders(x.transpose(1, 2).contiguous()))
         self.train(True)  # the reference unconditionally returns to train mode (vae.py:344)
-        del was_training
         return y
 
     # -- codec wire format (bit budget of utils.py:137-147) ---------------------
+    @property
+    def _code_bits(self) -> int:
+        """Bits per code on the wire: every stage at the widest stage's width."""
+        return max(1, (max(int(k) for k in self.codebook_size) - 1).bit_length())
+
     def compress(self, x, codebook_n=None):
         """Waveform -> (uint8 bitstream, (B, T, Q)).  ceil(log2(K)) bits per code, dense."""
         with torch.no_grad():
             _, _, index = self.encode(x, codebook_n=codebook_n)
-        bits = max(1, (max(int(k) for k in self.codebook_size) - 1).bit_length())   # every stage at the widest stage's width
-        return ops.codes_pack(index, bits), tuple(index.shape)
+        return ops.codes_pack(index, self._code_bits), tuple(index.shape)
 
     def decompress(self, stream, shape):
         """Inverse of ``compress``: bitstream -> codes -> sum of codewords -> decoder."""
         b, t, q = shape
-        bits = max(1, (max(int(k) for k in self.codebook_size) - 1).bit_length())   # every stage at the widest stage's width
-        index = ops.codes_unpack(stream, b * t * q, bits).reshape(b, t, q)
+        index = ops.codes_unpack(stream, b * t * q, self._code_bits).reshape(b, t, q)
         with torch.no_grad():
             zq = None
             for i in range(q):

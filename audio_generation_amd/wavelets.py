@@ -15,13 +15,14 @@ constructor arguments, parameter / buffer names (``h0``, ``h1``, ``w``;
 from __future__ import annotations
 
 from math import sqrt
-from typing import Optional
+from typing import List, Optional
 
 import torch
 from torch import nn
 
 from . import ops
 from ._lib import CONV_CAUSAL, CONV_SAME, EPI_GELU_PRE, EPI_LEAKY_PRE, needs_grad
+from .units import Unit, leaky_slope, packed_image
 
 Tensor = torch.Tensor
 
@@ -51,6 +52,19 @@ class CausalMultiresConv1d(nn.Module):
             return _MultiresNative.apply(self, x, self.h0, self.h1, self.w)
         return self._hip(x)
 
+    # -- one unit of a conv stack (units.py) ------------------------------------------------------
+    def run_fused(self, x: Tensor, post_slope: Optional[float] = None) -> Tensor:
+        return self._hip(x)          # the GELU is the kernel's own; the blocks place nothing behind it
+
+    def units(self, act: Optional[nn.Module] = None) -> List[Unit]:
+        return [Unit("multires", self, [self], leaky_slope(act))]
+
+    def params(self):
+        return [self.h0, self.h1, self.w]
+
+    def primitives(self):
+        return [("multires", self.kernel_size, self.depth)]
+
 
 class _MultiresNative(torch.autograd.Function):
     """``agx_multires_forward`` / ``agx_multires_backward`` (the cascade is re-formed per tile in the backward kernel:
@@ -79,28 +93,20 @@ class _PlainConv(nn.Module):
         ref = nn.Conv1d(c_in, c_out, kernel)
         self.weight, self.bias = ref.weight, ref.bias
         self.in_channels, self.out_channels, self.kernel_size = c_in, c_out, (kernel,)
-        self._key, self._packed = None, None
-        self._bkey, self._packed_bwd = None, None
+        self.stride = self.dilation = (1,)
+
+    def weights(self):
+        return self.weight, None
 
     def desc(self, kind: int, x: Tensor, epilogue: int = 0, slope: float = 0.1):
         return ops.conv_desc(kind, x.shape[0], self.in_channels, self.out_channels, x.shape[2],
                              self.kernel_size[0], 1, 1, epilogue, slope)
 
     def packed_bwd(self, kind: int) -> Tensor:
-        key = (kind, self.weight.data_ptr(), self.weight._version)
-        if key != self._bkey:
-            d = ops.conv_desc(kind, 1, self.in_channels, self.out_channels, 1 << 20, self.kernel_size[0])
-            self._packed_bwd, self._bkey = ops.conv_pack_bwd(d, self.weight.detach()), key
-        return self._packed_bwd
+        return packed_image(self, "conv_pack_bwd", kind)
 
     def run(self, x: Tensor, kind: int, epilogue: int = 0, slope: float = 0.1) -> Tensor:
-        key = (kind, self.weight.data_ptr(), self.weight._version)
-        if key != self._key:
-            d = ops.conv_desc(kind, 1, self.in_channels, self.out_channels, 1 << 20, self.kernel_size[0])
-            self._packed, self._key = ops.conv_pack(d, self.weight.detach()), key
-        desc = ops.conv_desc(kind, x.shape[0], self.in_channels, self.out_channels, x.shape[2],
-                             self.kernel_size[0], 1, 1, epilogue, slope)
-        return ops.conv_forward(desc, x, self._packed, self.bias.detach())
+        return ops.conv_forward(self.desc(kind, x, epilogue, slope), x, packed_image(self, "conv_pack", kind), self.bias.detach())
 
 
 class MultiresScaleBlock(nn.Module):
@@ -191,9 +197,15 @@ class WaveletLayer(nn.Module):
     def forward(self, x: Tensor) -> Tensor:
         return self.run_fused(x, None)
 
-    # -- native backward (used by native_backward.py as one unit of a decoder stack) --------------
+    # -- one unit of a decoder stack (units.py), and its native backward --------------------------
+    def units(self, act: Optional[nn.Module] = None) -> List[Unit]:
+        return [Unit("wavelet", self, [self], leaky_slope(act))]
+
     def params(self):
         return [self.conv_in.weight, self.conv_in.bias, self.conv_out.weight, self.conv_out.bias, self.wavelet_scale]
+
+    def primitives(self):
+        return [("wavelet", self.wavelet_kernel_size, self.scale_factor, self.n_points, self.out_conv_kernel_size)]
 
     def backward_native(self, x: Tensor, dz: Tensor, mask: Optional[Tensor], mask_slope: float):
         """``dz`` = gradient w.r.t. conv_out's linear output.  Returns (dx, grads in ``params()`` order);
