@@ -16,14 +16,15 @@ Forward, all on HIP kernels through the C ABI:
 * loss           -> ``agx_reduce_mean`` / ``agx_reduce_mean_backward`` (every mean of the hinge and
   feature-matching terms, with hand-written gradients).
 
-Backward through the discriminator bodies runs on the HIP kernels as well (``_STFTDiscNative``,
-``_WaveBlockNative``); an activation other than LeakyReLU has no backward kernel and raises -- there is no
-ATen fallback.
+Each body describes itself once (``_chain()``: head op, links of conv + fused LeakyReLU slope + "is a feature", final
+sigmoid); ``_Chain.forward`` is the one forward walk and ``_ChainNative`` the one backward, on the HIP kernels as well.  An
+activation other than LeakyReLU has no kernel and raises -- there is no ATen fallback.
 """
 from __future__ import annotations
 
+import dataclasses
 import warnings
-from typing import List, Optional, Sequence, Tuple
+from typing import Callable, List, Optional, Tuple
 
 import torch
 from torch import nn
@@ -35,10 +36,23 @@ from .quantizer import tuple_checker
 Tensor = torch.Tensor
 
 
-def _slope(act: nn.Module) -> float:
+def _slope(act: nn.Module, backward_of: Optional[str] = None) -> float:
+    """Slope of the LeakyReLU fused on a conv's output; the one place that refuses another activation (``backward_of``: the
+    discriminator a gradient is asked of)."""
     if not isinstance(act, nn.LeakyReLU):
+        if backward_of is not None:
+            raise AgxError(f"{backward_of}: the backward kernels fuse the LeakyReLU gradient only; another activation "
+                           "can run forward (torch.no_grad) but has no backward -- there is no ATen fallback")
         raise NotImplementedError("only LeakyReLU is fused into the discriminator convs")
     return float(act.negative_slope)
+
+
+def _resized(desc, **fields):
+    """Copy of a descriptor with some fields replaced: the placeholder shapes the images are packed at."""
+    desc = type(desc).from_buffer_copy(desc)
+    for name, value in fields.items():
+        setattr(desc, name, value)
+    return desc
 
 
 class _SNConv(nn.Module):
@@ -127,43 +141,25 @@ class _SNConv(nn.Module):
         the power iteration moves sigma)."""
         w = self.raw_weight
         impl = self.impl if impl is None else impl
-        key = (w.data_ptr(), w._version, self.training, self._iter, impl,
-               getattr(self, "_wn_key", None) if self.norm != "spectral" else (self.weight_u._version, self.weight_v._version))
-        if self.training or key != self._key:
+
+        def key():
+            return (w.data_ptr(), w._version, self.training, self._iter, impl,
+                    getattr(self, "_wn_key", None) if self.norm != "spectral" else (self.weight_u._version, self.weight_v._version))
+
+        if self.training or key() != self._key:
             sigma = self._sigma()
             # what this forward normalised with (the native backward needs exactly these)
             self._tape = None if sigma is None else (sigma, self.weight_u.clone(), self.weight_v.clone())
             desc = make_desc()
             self._packed = pack_plain(desc, w.detach()) if sigma is None else pack_sigma(desc, w.detach(), sigma)
-            self._key = (w.data_ptr(), w._version, self.training, self._iter, impl,
-                         getattr(self, "_wn_key", None) if self.norm != "spectral" else (self.weight_u._version, self.weight_v._version))
+            self._key = key()      # after _sigma(): the stored key holds the moved _iter
         return self._packed
 
-    # -- 1-D --------------------------------------------------------------------------------------
-    def run1d(self, x: Tensor, slope: Optional[float]) -> Tensor:
-        b, _, length = x.shape
-
-        def desc(batch=b, l_in=length):
-            return ops.conv_desc(CONV_PADDED, batch, self.in_channels, self.out_channels, l_in, self.kernel_size[0],
-                                 self.stride[0], 1, EPI_LEAKY_PRE if slope is not None else 0, slope or 0.0,
-                                 groups=self.groups, padding=self.padding[0])
-
-        packed = self.packed(lambda: desc(1, 1 << 20), ops.conv_pack, ops.conv_pack_sigma)
-        return ops.conv_forward(desc(), x, packed, None if self.bias is None else self.bias.detach())
-
-    # -- 2-D --------------------------------------------------------------------------------------
-    def run2d(self, x: Tensor, slope: Optional[float]) -> Tensor:
-        b, _, h, w = x.shape
-        impl = self.impl_for(b, h, w)
-
-        def desc(batch=b, hh=h, ww=w):
-            return ops.conv2d_desc(batch, self.in_channels, self.out_channels, hh, ww, self.kernel_size[0],
-                                   self.kernel_size[1], self.stride, self.padding,
-                                   EPI_LEAKY_PRE if slope is not None else 0, slope or 0.0, impl)
-
-        packed = self.packed(lambda: desc(1, 64, 64), ops.conv2d_pack, ops.conv2d_pack, impl)
-        return ops.conv2d_forward(desc(), x, packed, None if self.bias is None else self.bias.detach())
-
+    # -- descriptors (forward ones; the backward ops read the same) ----------------------------------
+    def desc1d(self, x: Tensor, slope: Optional[float] = None):
+        return ops.conv_desc(CONV_PADDED, x.shape[0], self.in_channels, self.out_channels, x.shape[2],
+                             self.kernel_size[0], self.stride[0], 1, EPI_LEAKY_PRE if slope is not None else 0,
+                             slope or 0.0, groups=self.groups, padding=self.padding[0])
 
     def desc2d(self, x: Tensor, slope: Optional[float] = None, bwd: bool = False):
         b, _, h, w = x.shape
@@ -171,12 +167,32 @@ class _SNConv(nn.Module):
                                self.stride, self.padding, EPI_LEAKY_PRE if slope is not None else 0, slope or 0.0,
                                self.impl_for(b, h, w, bwd))
 
-    def bwd2d(self, x: Tensor, dy: Tensor, tape, need_dx: bool = True, add: Optional[Tensor] = None,
-              mask: Optional[Tensor] = None, slope: float = 0.2):
-        """(dx or None, [dbias, dweight]) of this layer for the forward that produced ``tape``."""
-        desc = self.desc2d(x, bwd=True)
+    # -- forward ------------------------------------------------------------------------------------
+    def run1d(self, x: Tensor, slope: Optional[float]) -> Tensor:
+        desc = self.desc1d(x, slope)
+        packed = self.packed(lambda: _resized(desc, batch=1, l_in=1 << 20), ops.conv_pack, ops.conv_pack_sigma)
+        return ops.conv_forward(desc, x, packed, None if self.bias is None else self.bias.detach())
+
+    def run2d(self, x: Tensor, slope: Optional[float]) -> Tensor:
+        desc = self.desc2d(x, slope)
+        packed = self.packed(lambda: _resized(desc, batch=1, h_in=64, w_in=64), ops.conv2d_pack, ops.conv2d_pack, desc.impl)
+        return ops.conv2d_forward(desc, x, packed, None if self.bias is None else self.bias.detach())
+
+    def run(self, x: Tensor, slope: Optional[float]) -> Tensor:
+        return self.run2d(x, slope) if self.nd == 2 else self.run1d(x, slope)
+
+    # -- backward -----------------------------------------------------------------------------------
+    def bwd(self, x: Tensor, dy: Tensor, tape, need_dx: bool = True, add: Optional[Tensor] = None,
+            mask: Optional[Tensor] = None, slope: Optional[float] = None):
+        """(dx or None, [dbias, dweight]) of this layer for the forward that produced ``tape``; the backward-data epilogue adds
+        ``add`` and applies the LeakyReLU gradient (``mask`` / ``slope``) of the activation that produced ``x``."""
         w = self.raw_weight.detach()
         sigma, u, v = tape if tape is not None else (None, None, None)
+        dx, dw, db = (self._bwd2d if self.nd == 2 else self._bwd1d)(x, dy, w, sigma, u, v, need_dx, add, mask, slope)
+        return dx, self._finish_grads([db, dw] if self.bias is not None else [dw])
+
+    def _bwd2d(self, x, dy, w, sigma, u, v, need_dx, add, mask, slope):
+        desc = self.desc2d(x, bwd=True)
         dw, db = ops.conv2d_bwd_weight(desc, x, dy, w, sigma, u, v, want_bias=self.bias is not None)
         dx = None
         if need_dx:
@@ -185,33 +201,24 @@ class _SNConv(nn.Module):
                    and self.kernel_size[0] - 1 - self.padding[0] >= 0)
             if few:    # the 2-channel first conv: kw * Cin rows on the MFMA tiles instead of Cin on the direct kernel
                 dx = ops.conv2d_bwd_data_fewchannels(desc, dy, w, sigma, add)
-            else:
-                dx = ops.conv2d_bwd_data(desc, dy, ops.conv2d_pack_bwd(desc, w, sigma), mask, slope, add)
-        return dx, self._finish_grads([db, dw] if self.bias is not None else [dw])
+            else:      # (no mask: the kernel ignores the slope; it has always been handed 0.2 here and 0.0 in 1-D)
+                dx = ops.conv2d_bwd_data(desc, dy, ops.conv2d_pack_bwd(desc, w, sigma), mask, 0.2 if slope is None else slope, add)
+        return dx, dw, db
 
-    def desc1d(self, x: Tensor, slope: Optional[float] = None):
-        return ops.conv_desc(CONV_PADDED, x.shape[0], self.in_channels, self.out_channels, x.shape[2],
-                             self.kernel_size[0], self.stride[0], 1, EPI_LEAKY_PRE if slope is not None else 0,
-                             slope or 0.0, groups=self.groups, padding=self.padding[0])
-
-    def bwd1d(self, x: Tensor, dz: Tensor, tape, need_dx: bool = True, add: Optional[Tensor] = None,
-              mask: Optional[Tensor] = None, slope: float = 0.2):
-        """(dx or None, [dbias, dweight]) of this 1-D layer for the forward that produced ``tape``."""
+    def _bwd1d(self, x, dz, w, sigma, u, v, need_dx, add, mask, slope):
         desc = self.desc1d(x)
-        w = self.raw_weight.detach()
-        sigma, u, v = tape if tape is not None else (None, None, None)
         if self.groups > 1:
             dw, db = ops.conv_grouped_bwd_weight(desc, x, dz, want_bias=self.bias is not None)
-            dx = ops.conv_grouped_bwd_data(desc, dz, w, sigma, add, mask, slope) if need_dx else None
+            dx = ops.conv_grouped_bwd_data(desc, dz, w, sigma, add, mask, slope or 0.0) if need_dx else None
         else:
             dw, _, db = ops.conv_bwd_weight(desc, x, dz, w, None, want_bias=self.bias is not None)
             dx = None
             if need_dx:
                 pk = ops.conv_pack_bwd(desc, w) if sigma is None else ops.conv_pack_bwd_sigma(desc, w, sigma)
-                dx = ops.conv_bwd_data(desc, dz, pk, add, mask, slope)
+                dx = ops.conv_bwd_data(desc, dz, pk, add, mask, slope or 0.0)
         if sigma is not None:
             ops.spectral_grad_(dw, w, sigma, u, v)
-        return dx, self._finish_grads([db, dw] if self.bias is not None else [dw])
+        return dx, dw, db
 
     def grad_params(self):
         weights = [self.weight_g, self.weight_v] if self.norm == "weight" else [self.raw_weight]
@@ -233,6 +240,43 @@ def set_arithmetic(module: nn.Module, mode: str = "fp32") -> nn.Module:
             m.ring_only = mode == "bf16x3_ring"      # decided per feature-map size by the library (impl_for)
             m._impl_of = {}
     return module
+
+
+@dataclasses.dataclass(frozen=True)
+class _Link:
+    conv: _SNConv
+    slope: Optional[float]      # of the LeakyReLU fused on the conv's output, or None
+    feature: bool               # the output is returned as a feature
+
+
+@dataclasses.dataclass(frozen=True)
+class _Chain:
+    """A discriminator body: head op -> links -> sigmoid or copy.  Inference, training and the backward all walk this."""
+    head: Callable[[Tensor], Tensor]                 # waveform -> the first conv's input
+    head_backward: Callable[[Tensor, int], Tensor]   # (its gradient, waveform length) -> the waveform's gradient
+    input_is_feature: bool                           # the first conv's input is features[0]
+    links: Tuple[_Link, ...]
+    sigmoid: bool
+
+    def forward(self, x: Tensor):
+        """(out, features, every conv's input, every conv's tape)."""
+        h = self.head(x)
+        feats, inputs, tapes = ([h] if self.input_is_feature else []), [], []
+        for link in self.links:
+            inputs.append(h)
+            h = link.conv.run(h, link.slope)
+            tapes.append(link.conv._tape)
+            if link.feature:
+                feats.append(h)
+        return (ops.sigmoid(h) if self.sigmoid else h.clone()), feats, inputs, tapes
+
+
+def _run(module: nn.Module, x: Tensor):
+    """out, features of ``module._chain()`` on the HIP kernels, with their hand-written backward when a gradient is needed."""
+    if not needs_grad(x, module):
+        return module._chain().forward(x)[:2]
+    flat = _ChainNative.apply(module._chain(backward_of=type(module).__name__), x, *module.parameters())
+    return flat[0], list(flat[1:])
 
 
 class WaveformDiscriminatorBlock(nn.Module):
@@ -259,30 +303,18 @@ class WaveformDiscriminatorBlock(nn.Module):
         self.layers = nn.ModuleList(layers)
         self.final_activation = nn.Sigmoid() if apply_sigmoid else nn.Identity()
 
-    def _hip(self, x: Tensor) -> List[Tensor]:
+    def _chain(self, backward_of: Optional[str] = None) -> _Chain:
+        """Pooled input (features[0]) -> convs, every output a feature: the last one too, which also feeds the sigmoid."""
         pool = self.layers[0]
-        x = ops.avgpool1d(x, pool.kernel_size[0] if isinstance(pool.kernel_size, tuple) else pool.kernel_size,
-                          pool.stride[0] if isinstance(pool.stride, tuple) else pool.stride,
-                          pool.padding[0] if isinstance(pool.padding, tuple) else pool.padding)
-        feats = [x]
-        for layer in list(self.layers)[1:]:
-            if isinstance(layer, nn.Sequential):
-                x = layer[0].run1d(x, _slope(layer[1]))
-            else:
-                x = layer.run1d(x, None)
-            feats.append(x)
-        out = ops.sigmoid(x) if isinstance(self.final_activation, nn.Sigmoid) else x.clone()
-        return [out] + feats
+        one = lambda t: t[0] if isinstance(t, tuple) else t  # noqa: E731
+        geom = (one(pool.kernel_size), one(pool.stride), one(pool.padding))
+        links = tuple(_Link(l[0], _slope(l[1], backward_of), True) if isinstance(l, nn.Sequential) else _Link(l, None, True)
+                      for l in list(self.layers)[1:])
+        return _Chain(lambda x: ops.avgpool1d(x, *geom), lambda d, length: ops.avgpool1d_backward(d, length, *geom),
+                      True, links, isinstance(self.final_activation, nn.Sigmoid))
 
     def forward(self, x: Tensor):
-        if needs_grad(x, self):
-            if not all(isinstance(l[1], nn.LeakyReLU) for l in self.layers if isinstance(l, nn.Sequential)):
-                raise AgxError("WaveformDiscriminatorBlock: the backward kernels fuse the LeakyReLU gradient only; another "
-                               "activation can run forward (torch.no_grad) but has no backward -- there is no ATen fallback")
-            flat = _WaveBlockNative.apply(self, x, *list(self.parameters()))
-            return flat[0], list(flat[1:])
-        flat = self._hip(x)
-        return flat[0], list(flat[1:])
+        return _run(self, x)
 
 
 class WaveFormDiscriminator(nn.Module):
@@ -321,9 +353,14 @@ class STFTDiscriminatorBlock(nn.Module):
             _SNConv(nn.Conv2d(in_channels, in_channels * channel_multiplier, stride=stride, kernel_size=kernel_size,
                               padding=padding), norm))
 
+    def _links(self, backward_of: Optional[str] = None) -> Tuple[_Link, _Link]:
+        """The activated 3 x 3 conv (not a feature) and the strided conv (a feature)."""
+        return _Link(self.layers[0], _slope(self.layers[1], backward_of), False), _Link(self.layers[2], None, True)
+
     def forward(self, x: Tensor) -> Tensor:
-        x = self.layers[0].run2d(x, _slope(self.layers[1]))
-        return self.layers[2].run2d(x, None)
+        for link in self._links():
+            x = link.conv.run(x, link.slope)
+        return x
 
 
 class STFTDiscriminator(nn.Module):
@@ -352,161 +389,62 @@ class STFTDiscriminator(nn.Module):
         self.final_conv = _SNConv(nn.Conv2d(ch, 1, kernel_size=(1, fk), padding=(0, (fk - 1) // 2)), norm)
         self.final_activation = nn.Sigmoid() if apply_sigmoid else nn.Identity()
 
-    def _hip(self, x: Tensor) -> List[Tensor]:
-        x = ops.stft(x.squeeze(1), self.n_fft, self.normalize_stft)          # (B, 2, T, F)
-        x = self.first_conv.run2d(x, None)
-        feats = [x]
-        for block in self.blocks:
-            x = block(x)
-            feats.append(x)
-        x = self.final_conv.run2d(x, None)
-        out = ops.sigmoid(x) if isinstance(self.final_activation, nn.Sigmoid) else x.clone()
-        return [out] + feats
+    def _chain(self, backward_of: Optional[str] = None) -> _Chain:
+        """Spectrogram (B, 2, T, F; not a feature) -> first_conv (a feature) -> the blocks' links -> final_conv (not a feature)."""
+        n_fft, normalized = self.n_fft, self.normalize_stft
+        links = (_Link(self.first_conv, None, True), *(link for block in self.blocks for link in block._links(backward_of)),
+                 _Link(self.final_conv, None, False))
+        return _Chain(lambda x: ops.stft(x.squeeze(1), n_fft, normalized),
+                      lambda d, length: ops.stft_backward(d, length, n_fft, normalized).unsqueeze(1),
+                      False, links, isinstance(self.final_activation, nn.Sigmoid))
 
     def forward(self, x: Tensor):
-        if needs_grad(x, self):
-            if not all(isinstance(b.layers[1], nn.LeakyReLU) for b in self.blocks):
-                raise AgxError("STFTDiscriminator: the backward kernels fuse the LeakyReLU gradient only; another activation "
-                               "can run forward (torch.no_grad) but has no backward -- there is no ATen fallback")
-            flat = _STFTDiscNative.apply(self, x, *list(self.parameters()))
-            return [flat[0]], list(flat[1:])
-        flat = self._hip(x)
-        return [flat[0]], list(flat[1:])
+        out, feats = _run(self, x)
+        return [out], feats
 
 
-class _WaveBlockNative(torch.autograd.Function):
-    """WaveformDiscriminatorBlock forward + hand-written backward on the HIP kernels (same scheme as
-    _STFTDiscNative: per layer one dW call and one bwd-data call with the feature gradient and the LeakyReLU
-    gradient of the layer below fused in)."""
+class _ChainNative(torch.autograd.Function):
+    """A discriminator body's forward + hand-written backward, everything on the HIP kernels: per conv one weight-gradient call
+    (spectral-norm chain rule included) and one backward-data call whose epilogue adds the gradient arriving at the conv's input
+    from the feature-matching loss and applies the LeakyReLU gradient of the activation that produced that input; the head's
+    adjoint closes the path to the waveform."""
 
     @staticmethod
-    def forward(ctx, blk, x: Tensor, *params: Tensor):
-        pool = blk.layers[0]
-        one = lambda t: t[0] if isinstance(t, tuple) else t  # noqa: E731
-        ctx.pool = (one(pool.kernel_size), one(pool.stride), one(pool.padding))
+    def forward(ctx, chain: _Chain, x: Tensor, *params: Tensor):
         with torch.no_grad():
-            h = ops.avgpool1d(x.detach(), *ctx.pool)
-            feats, convs, slopes, tapes = [h], [], [], []
-            for layer in list(blk.layers)[1:]:
-                conv, act = (layer[0], layer[1]) if isinstance(layer, nn.Sequential) else (layer, None)
-                sl = None if act is None else _slope(act)
-                h = conv.run1d(h, sl)
-                tapes.append(conv._tape)
-                convs.append(conv)
-                slopes.append(sl)
-                feats.append(h)
-            sig = isinstance(blk.final_activation, nn.Sigmoid)
-            out = ops.sigmoid(h) if sig else h.clone()
-        ctx.convs, ctx.slopes, ctx.tapes, ctx.sig, ctx.params, ctx.l_in = convs, slopes, tapes, sig, params, x.shape[-1]
-        ctx.save_for_backward(out, *feats)
+            out, feats, inputs, tapes = chain.forward(x.detach())
+        ctx.chain, ctx.tapes, ctx.params, ctx.length = chain, tapes, params, x.shape[-1]
+        ctx.save_for_backward(out, *inputs)
         return (out, *feats)
 
     @staticmethod
     def backward(ctx, g_out: Optional[Tensor], *g_feats: Optional[Tensor]):
-        saved = ctx.saved_tensors
-        out, feats = saved[0], saved[1:]
-        convs, slopes, tapes = ctx.convs, ctx.slopes, ctx.tapes
-        gf = [None if g is None else g.contiguous() for g in g_feats]
+        chain, links = ctx.chain, ctx.chain.links
+        out, *inputs = ctx.saved_tensors
+        gf = iter([None if g is None else g.contiguous() for g in g_feats])
+        # the feature gradient arriving at conv i's input (arriving[i]) and at the last conv's output (arriving[-1])
+        arriving = [next(gf) if chain.input_is_feature else None] + [next(gf) if link.feature else None for link in links]
         grads = {}
-        # gradient w.r.t. the last conv's output (a feature too): from the sigmoid output and from the feature loss
-        dz = None
+        dz = None                     # gradient w.r.t. the output of the conv being visited
         if g_out is not None:
-            dz = ops.sigmoid_backward(g_out.contiguous(), out) if ctx.sig else g_out.contiguous()
-        if gf[-1] is not None:
-            dz = gf[-1] if dz is None else dz + gf[-1]
-        for i in range(len(convs) - 1, -1, -1):
-            x_in = feats[i]                      # input of conv i (= feature i: pooled input or the layer below)
+            dz = ops.sigmoid_backward(g_out.contiguous(), out) if chain.sigmoid else g_out.contiguous()
+        if arriving[-1] is not None:
+            dz = arriving[-1] if dz is None else dz + arriving[-1]
+        for i in range(len(links) - 1, -1, -1):
+            x_in = inputs[i]
+            below = links[i - 1].slope if i > 0 else None      # of the activation that produced x_in
             if dz is None:
-                dz = gf[i]                       # nothing from above: the feature gradient, if any, starts the chain
-                if dz is not None and i > 0 and slopes[i - 1] is not None:
-                    dz = torch.where(x_in > 0, dz, dz * slopes[i - 1])
+                dz = arriving[i]                 # nothing from above: the feature gradient, if any, starts the chain
+                if dz is not None and below is not None:
+                    dz = torch.where(x_in > 0, dz, dz * below)
                 continue
-            below = slopes[i - 1] if i > 0 else None      # activation that produced x_in
-            need_dx = i > 0 or ctx.needs_input_grad[1]
-            dxl, gl = convs[i].bwd1d(x_in, dz, tapes[i], need_dx=need_dx, add=gf[i],
-                                     mask=x_in if below is not None else None, slope=below or 0.0)
-            for p_, g_ in zip(convs[i].grad_params(), gl):
-                grads[p_] = g_
-            dz = dxl
+            conv = links[i].conv
+            dz, gl = conv.bwd(x_in, dz, ctx.tapes[i], need_dx=i > 0 or ctx.needs_input_grad[1], add=arriving[i],
+                              mask=x_in if below is not None else None, slope=below)
+            grads.update(zip(conv.grad_params(), gl))
         dx = None
         if ctx.needs_input_grad[1] and dz is not None:
-            dx = ops.avgpool1d_backward(dz, ctx.l_in, *ctx.pool)
-        return (None, dx, *[grads.get(p_) for p_ in ctx.params])
-
-
-class _STFTDiscNative(torch.autograd.Function):
-    """STFTDiscriminator forward + hand-written backward, everything on the HIP kernels: per layer one
-    weight-gradient call (spectral-norm chain rule included) and one backward-data call whose epilogue adds
-    the gradient arriving at that feature map from the feature-matching loss and applies the LeakyReLU
-    gradient of the layer below; the STFT adjoint closes the path to the waveform."""
-
-    @staticmethod
-    def forward(ctx, disc, x: Tensor, *params: Tensor):
-        with torch.no_grad():
-            xd = x.detach()
-            spec = ops.stft(xd.squeeze(1), disc.n_fft, disc.normalize_stft)
-            convs, tapes, acts = [disc.first_conv], [], []
-            h = disc.first_conv.run2d(spec, None)
-            tapes.append(disc.first_conv._tape)
-            feats = [h]
-            for blk in disc.blocks:
-                c0, act, c2 = blk.layers[0], blk.layers[1], blk.layers[2]
-                a = c0.run2d(h, _slope(act))
-                tapes.append(c0._tape)
-                h = c2.run2d(a, None)
-                tapes.append(c2._tape)
-                convs += [c0, c2]
-                acts.append(a)
-                feats.append(h)
-            z = disc.final_conv.run2d(h, None)
-            tapes.append(disc.final_conv._tape)
-            convs.append(disc.final_conv)
-            sig = isinstance(disc.final_activation, nn.Sigmoid)
-            out = ops.sigmoid(z) if sig else z.clone()
-        ctx.disc, ctx.convs, ctx.tapes, ctx.sig, ctx.params = disc, convs, tapes, sig, params
-        ctx.length = x.shape[-1]
-        ctx.n_blocks = len(acts)
-        ctx.save_for_backward(spec, out, *feats, *acts)
-        return (out, *feats)
-
-    @staticmethod
-    def backward(ctx, g_out: Optional[Tensor], *g_feats: Optional[Tensor]):
-        disc, convs, tapes = ctx.disc, ctx.convs, ctx.tapes
-        saved = ctx.saved_tensors
-        nb = ctx.n_blocks
-        spec, out = saved[0], saved[1]
-        feats, acts = saved[2:3 + nb], saved[3 + nb:]
-        grads = {}
-
-        def put(conv, gl):
-            for p_, g_ in zip(conv.grad_params(), gl):
-                grads[p_] = g_
-
-        gf = [None if g is None else g.contiguous() for g in g_feats]
-        dh = None
-        if g_out is not None:
-            dz = ops.sigmoid_backward(g_out.contiguous(), out) if ctx.sig else g_out.contiguous()
-            dh, gl = convs[-1].bwd2d(feats[-1], dz, tapes[-1], add=gf[-1])
-            put(convs[-1], gl)
-        else:
-            dh = gf[-1]
-        for i in range(nb - 1, -1, -1):
-            c0, c2 = convs[1 + 2 * i], convs[2 + 2 * i]
-            slope = _slope(disc.blocks[i].layers[1])
-            if dh is None:                               # nothing arrives at this feature map or above
-                dh = gf[i]
-                continue
-            da, gl = c2.bwd2d(acts[i], dh, tapes[2 + 2 * i], mask=acts[i], slope=slope)
-            put(c2, gl)
-            dh, gl = c0.bwd2d(feats[i], da, tapes[1 + 2 * i], add=gf[i])
-            put(c0, gl)
-        dx = None
-        if dh is not None:
-            need_dx = ctx.needs_input_grad[1]
-            dspec, gl = convs[0].bwd2d(spec, dh, tapes[0], need_dx=need_dx)
-            put(convs[0], gl)
-            if need_dx:
-                dx = ops.stft_backward(dspec, ctx.length, disc.n_fft, disc.normalize_stft).unsqueeze(1)
+            dx = chain.head_backward(dz, ctx.length)
         return (None, dx, *[grads.get(p_) for p_ in ctx.params])
 
 

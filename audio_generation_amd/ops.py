@@ -110,19 +110,24 @@ def conv_out_len(desc: ConvDesc) -> int:
     return int(n)
 
 
+def _pack(size: str, pack: str, desc, w: Tensor, aux: Optional[Tensor], aux_f32c: bool = False) -> Tensor:
+    """The image the library's ``pack`` makes of ``w`` (and ``aux``: the weight-norm gain or sigma), ``size`` floats long."""
+    lib = _lib.load()
+    _need_gpu(w, aux)
+    n = getattr(lib, size)(ctypes.byref(desc))
+    if n < 0:
+        _lib.check(int(n), size)
+    w = _f32c(w)
+    if aux is not None and aux_f32c:
+        aux = _f32c(aux)
+    packed = torch.empty(int(n), dtype=torch.float32, device=w.device)
+    _lib.check(getattr(lib, pack)(ctypes.byref(desc), _ptr(w), _ptr(aux), _ptr(packed), _stream()), pack)
+    return packed
+
+
 def conv_pack(desc: ConvDesc, v: Tensor, g: Optional[Tensor] = None) -> Tensor:
     """Weight-norm fold + repack (``agx_conv_pack``).  Returns the packed image."""
-    lib = _lib.load()
-    _need_gpu(v, g)
-    n = lib.agx_conv_packed_floats(ctypes.byref(desc))
-    if n < 0:
-        _lib.check(int(n), "agx_conv_packed_floats")
-    v = _f32c(v)
-    g = None if g is None else _f32c(g)
-    packed = torch.empty(int(n), dtype=torch.float32, device=v.device)
-    _lib.check(lib.agx_conv_pack(ctypes.byref(desc), _ptr(v), _ptr(g), _ptr(packed), _stream()),
-               "agx_conv_pack")
-    return packed
+    return _pack("agx_conv_packed_floats", "agx_conv_pack", desc, v, g, aux_f32c=True)
 
 
 def conv_forward(desc: ConvDesc, x: Tensor, packed: Tensor, bias: Optional[Tensor],
@@ -206,17 +211,7 @@ def conv_forward_planes(desc: ConvDesc, x_planes: Tensor, packed: Tensor, bias: 
 
 def conv_pack_bwd(desc: ConvDesc, v: Tensor, g: Optional[Tensor] = None) -> Tensor:
     """Packed image of the layer's backward-data op (``agx_conv_pack_bwd``)."""
-    lib = _lib.load()
-    _need_gpu(v, g)
-    n = lib.agx_conv_bwd_packed_floats(ctypes.byref(desc))
-    if n < 0:
-        _lib.check(int(n), "agx_conv_bwd_packed_floats")
-    v = _f32c(v)
-    g = None if g is None else _f32c(g)
-    packed = torch.empty(int(n), dtype=torch.float32, device=v.device)
-    _lib.check(lib.agx_conv_pack_bwd(ctypes.byref(desc), _ptr(v), _ptr(g), _ptr(packed), _stream()),
-               "agx_conv_pack_bwd")
-    return packed
+    return _pack("agx_conv_bwd_packed_floats", "agx_conv_pack_bwd", desc, v, g, aux_f32c=True)
 
 
 def conv_bwd_data(desc: ConvDesc, dy: Tensor, packed_bwd: Tensor, add: Optional[Tensor] = None,
@@ -585,29 +580,11 @@ def spectral_sigma(w: Tensor, u: Tensor, v: Tensor, power_iterations: int, eps: 
 
 
 def conv_pack_sigma(desc: ConvDesc, w: Tensor, sigma: Tensor) -> Tensor:
-    lib = _lib.load()
-    _need_gpu(w, sigma)
-    n = lib.agx_conv_packed_floats(ctypes.byref(desc))
-    if n < 0:
-        _lib.check(int(n), "agx_conv_packed_floats")
-    w = _f32c(w)
-    packed = torch.empty(int(n), dtype=torch.float32, device=w.device)
-    _lib.check(lib.agx_conv_pack_sigma(ctypes.byref(desc), _ptr(w), _ptr(sigma), _ptr(packed), _stream()),
-               "agx_conv_pack_sigma")
-    return packed
+    return _pack("agx_conv_packed_floats", "agx_conv_pack_sigma", desc, w, sigma)
 
 
 def conv_pack_bwd_sigma(desc: ConvDesc, w: Tensor, sigma: Tensor) -> Tensor:
-    lib = _lib.load()
-    _need_gpu(w, sigma)
-    n = lib.agx_conv_bwd_packed_floats(ctypes.byref(desc))
-    if n < 0:
-        _lib.check(int(n), "agx_conv_bwd_packed_floats")
-    w = _f32c(w)
-    packed = torch.empty(int(n), dtype=torch.float32, device=w.device)
-    _lib.check(lib.agx_conv_pack_bwd_sigma(ctypes.byref(desc), _ptr(w), _ptr(sigma), _ptr(packed), _stream()),
-               "agx_conv_pack_bwd_sigma")
-    return packed
+    return _pack("agx_conv_bwd_packed_floats", "agx_conv_pack_bwd_sigma", desc, w, sigma)
 
 
 def conv_grouped_bwd_data(desc: ConvDesc, dz: Tensor, w: Tensor, sigma: Optional[Tensor] = None,
@@ -666,16 +643,7 @@ def conv2d_desc(batch, c_in, c_out, h_in, w_in, kh, kw, stride=(1, 1), padding=(
 
 
 def conv2d_pack(desc, w: Tensor, sigma: Optional[Tensor] = None) -> Tensor:
-    lib = _lib.load()
-    _need_gpu(w, sigma)
-    n = lib.agx_conv2d_packed_floats(ctypes.byref(desc))
-    if n < 0:
-        _lib.check(int(n), "agx_conv2d_packed_floats")
-    w = _f32c(w)
-    packed = torch.empty(int(n), dtype=torch.float32, device=w.device)
-    _lib.check(lib.agx_conv2d_pack(ctypes.byref(desc), _ptr(w), _ptr(sigma), _ptr(packed), _stream()),
-               "agx_conv2d_pack")
-    return packed
+    return _pack("agx_conv2d_packed_floats", "agx_conv2d_pack", desc, w, sigma)
 
 
 def conv2d_forward(desc, x: Tensor, packed: Tensor, bias: Optional[Tensor]) -> Tensor:
@@ -696,16 +664,7 @@ def conv2d_forward(desc, x: Tensor, packed: Tensor, bias: Optional[Tensor]) -> T
 
 
 def conv2d_pack_bwd(desc, w: Tensor, sigma: Optional[Tensor] = None) -> Tensor:
-    lib = _lib.load()
-    _need_gpu(w, sigma)
-    n = lib.agx_conv2d_bwd_packed_floats(ctypes.byref(desc))
-    if n < 0:
-        _lib.check(int(n), "agx_conv2d_bwd_packed_floats")
-    w = _f32c(w)
-    packed = torch.empty(int(n), dtype=torch.float32, device=w.device)
-    _lib.check(lib.agx_conv2d_pack_bwd(ctypes.byref(desc), _ptr(w), _ptr(sigma), _ptr(packed), _stream()),
-               "agx_conv2d_pack_bwd")
-    return packed
+    return _pack("agx_conv2d_bwd_packed_floats", "agx_conv2d_pack_bwd", desc, w, sigma)
 
 
 def conv2d_bwd_data(desc, dy: Tensor, packed_bwd: Tensor, mask: Optional[Tensor] = None, slope: float = 0.2,

@@ -259,6 +259,43 @@ def test_loss_matches_reference_and_oracle_gradients(g7, meta, tag):
     close(dl2, g7[f"loss_{tag}/discriminator_loss_2nd_call"], 2e-5)
 
 
+@pytest.mark.parametrize("tag", ["wave", "stft"])
+def test_one_mid_chain_feature_alone_matches_oracle_gradients(g7, meta, tag):
+    """Only features[3] is asked for (wave: the activated output of block 0's third conv; STFT: the output of blocks[2]):
+    the gradient reaches the input and the layers below the feature, and nothing else -- same state, input, oracle and
+    tolerances as test_loss_matches_reference_and_oracle_gradients."""
+    rec = g7["loss/reconstruction"]
+    sd0 = sub(g7, f"loss_{tag}/sd/")
+    if tag == "wave":
+        disc = ad.WaveFormDiscriminator(1, n_blocks=2)
+        disc.layers = torch.nn.ModuleList([_wave_block(meta, s) for s in (1, 2)])
+        groups = meta["wave"]["kwargs"]["groups"]
+        oracle = lambda sd: (lambda t: od.waveform_discriminator(t, sd, n_blocks=2, train=True, groups=groups))  # noqa: E731
+    else:
+        disc = ad.STFTDiscriminator(**meta["stft"]["kwargs"])
+        win = meta["stft"]["kwargs"]["win_length"]
+        oracle = lambda sd: (lambda t: od.stft_discriminator(t, sd, win, train=True))  # noqa: E731
+    disc.load_state_dict(sd0, strict=True)
+    disc = disc.to(DEV).train()
+    sd = {k: (v.clone().requires_grad_(True) if k.endswith("weight_orig") or k.endswith("bias") else v.clone())
+          for k, v in sd0.items()}
+    leaves = [k for k in sd if sd[k].requires_grad]
+    rec_c = rec.clone().requires_grad_(True)
+    want = torch.autograd.grad(oracle(sd)(rec_c)[1][3].sum(), [rec_c] + [sd[k] for k in leaves], allow_unused=True)
+    rec_d = rec.to(DEV).requires_grad_(True)
+    params = dict(disc.named_parameters())
+    got = torch.autograd.grad(disc(rec_d)[1][3].sum(), [rec_d] + [params[k] for k in leaves], allow_unused=True)
+    close(got[0], want[0], 2e-3)
+    checked = 0
+    for a, b in zip(got[1:], want[1:]):
+        if b is None:
+            assert a is None or float(a.abs().max()) == 0.0
+            continue
+        close(a, b, 3e-3)
+        checked += 1
+    assert checked == (2 * 3 if tag == "wave" else 2 * 7)      # weight and bias of the convs below the feature
+
+
 def test_full_size_stft_discriminator_against_oracle():
     """Default widths, win 1024, one 24 kHz second: every feature map against the CPU restatement."""
     torch.manual_seed(3)

@@ -55,7 +55,7 @@ def main():
             am = (torch.randn_like(hh), torch.randn_like(hh))      # the op as the training step runs it: LeakyReLU mask + gradient add
             tx = timeit(lambda: ops.conv2d_bwd_data(desc, dy, pk))
             txm = timeit(lambda: ops.conv2d_bwd_data(desc, dy, pk, am[0], 0.2, add=am[1]))
-            if c is d.first_conv:    # what _SNConv.bwd2d runs for the 2-channel layer
+            if c is d.first_conv:    # what _SNConv.bwd runs for the 2-channel layer
                 tx2 = timeit(lambda: ops.conv2d_bwd_data_fewchannels(desc, dy, w, tape[0]))
                 print(f"   first conv dx: direct {tx:.3f} ms, column-split {tx2:.3f} ms")
                 tx = tx2

@@ -8,7 +8,7 @@ AGX_GAN=1 adds the reference's six training discriminators (training.py:570-576)
 Trainer.mini_epoch does (training.py:363-385): discriminator_generator_loss per discriminator, the
 discriminator loss backward, the generator loss backward, one Adam step each -- BASELINE config 5 without the
 mel / pre-emphasis terms (torchaudio).  Discriminator forward AND backward run on the HIP kernels
-(discriminator.py: _STFTDiscNative / _WaveBlockNative); the all-reduce then covers generator + discriminator grads.
+(discriminator.py: _Chain / _ChainNative); the all-reduce then covers generator + discriminator grads.
 usage: [torchrun --nproc-per-node N] train_step_bench.py [batch_per_gpu] [steps]"""
 import json
 import os
