@@ -254,77 +254,84 @@ __global__ __launch_bounds__(256) void conv_fewrows_kernel(ConvPlan p, const flo
     }
 }
 
-static inline bool fewrows_ok(const ConvPlan &p) {
-    const int mm = p.M > 8 ? 16 : (p.M > 4 ? 8 : (p.M > 1 ? 4 : 1));
+// ------------------------------------------------------------------ host side
+// One table per kernel template, widest row first; a row's name and its launch thunk are made from the same template argument
+// (AGX_DIRECT_ROW).  direct_pick is the one place that chooses a row and sizes its launch, for the name query and the launcher.
+struct DirectPick;
+#define AGX_DIRECT_ARGS \
+    const DirectPick &k, const ConvPlan &p, const float *x, const float *wp, const float *bias, const float *res, float *y, hipStream_t st
+// n: the template argument (output rows per thread: narrow, fewrows / per block: direct); min_m: fewest GEMM rows (q * Cout) of a
+// dense layer that take the row; what: the kernel family, for messages
+struct DirectRow { int n, min_m; const char *what, *name; void (*launch)(AGX_DIRECT_ARGS); };
+enum DirectRefusal { DIRECT_OK, DIRECT_LDS, DIRECT_GROUPED_PHASES, DIRECT_GRID };
+// row is always set (the name query answers for layers the launcher refuses, too); ci_tile, span: conv_direct_kernel only
+struct DirectPick { const DirectRow *row; dim3 grid; size_t lds; int ci_tile, span; DirectRefusal refusal; };
+
+template <int N> static void run_conv_narrow(AGX_DIRECT_ARGS) { hipLaunchKernelGGL(conv_narrow_kernel<N>, k.grid, dim3(256), k.lds, st, p, x, wp, bias, res, y); }
+template <int N> static void run_conv_fewrows(AGX_DIRECT_ARGS) { hipLaunchKernelGGL(conv_fewrows_kernel<N>, k.grid, dim3(256), k.lds, st, p, x, wp, bias, res, y); }
+template <int N> static void run_conv_direct(AGX_DIRECT_ARGS) {
+    hipLaunchKernelGGL(conv_direct_kernel<N>, k.grid, dim3(256), k.lds, st, p, k.ci_tile, k.span, x, wp, bias, res, y);
+}
+#define AGX_DIRECT_ROW(FAMILY, N, MIN_M) {N, MIN_M, #FAMILY, #FAMILY "<" #N ">", run_##FAMILY<N>}
+static const DirectRow kNarrowRows[] = {AGX_DIRECT_ROW(conv_narrow, 16, 32), AGX_DIRECT_ROW(conv_narrow, 2, 2), AGX_DIRECT_ROW(conv_narrow, 1, 1)};
+static const DirectRow kFewRows[] = {AGX_DIRECT_ROW(conv_fewrows, 16, 9), AGX_DIRECT_ROW(conv_fewrows, 8, 5), AGX_DIRECT_ROW(conv_fewrows, 4, 2),
+                                     AGX_DIRECT_ROW(conv_fewrows, 1, 1)};
+static const DirectRow kDirectRows[] = {AGX_DIRECT_ROW(conv_direct, 32, 32), AGX_DIRECT_ROW(conv_direct, 16, 5), AGX_DIRECT_ROW(conv_direct, 4, 2),
+                                        AGX_DIRECT_ROW(conv_direct, 1, 1)};
+
+// the M -> rows ladder of a dense layer (every table ends in a row for M = 1)
+static const DirectRow &row_for_m(const DirectRow *rows, int m) {
+    while (m < rows->min_m) ++rows;
+    return *rows;
+}
+
+static inline bool fewrows_ok(const ConvPlan &p, const DirectRow &row) {
     return p.G == 1 && p.kh == 1 && p.Tout == 1 && p.M <= 16 && p.pm_R == 0 && p.prec == 0 && p.ncv == p.cin_real &&
-           p.J * mm <= 1024;   // one group of weights (J x 16 x rows) in <= 64 KB of LDS
+           p.J * row.n <= 1024;   // one group of weights (J x 16 x rows) in <= 64 KB of LDS
 }
 
-const char *conv_direct_variant(const ConvPlan &p) {
-    if (p.G > 1) {
-        const int rpg = p.Cout / p.G;
-        return rpg % 32 == 0 ? "conv_direct<32>" : (rpg % 16 == 0 ? "conv_direct<16>" : (rpg % 4 == 0 ? "conv_direct<4>" : "conv_direct<1>"));
-    }
-    if (narrow_ok(p)) return p.M == 32 ? "conv_narrow<16>" : (p.M == 2 ? "conv_narrow<2>" : "conv_narrow<1>");
-    if (fewrows_ok(p)) return p.M > 8 ? "conv_fewrows<16>" : (p.M > 4 ? "conv_fewrows<8>" : (p.M > 1 ? "conv_fewrows<4>" : "conv_fewrows<1>"));
-    return p.M >= 32 ? "conv_direct<32>" : (p.M > 4 ? "conv_direct<16>" : (p.M > 1 ? "conv_direct<4>" : "conv_direct<1>"));
-}
-
-int launch_conv_direct(const ConvPlan &p, const float *x, const float *wp, const float *bias,
-                       const float *res, float *y, hipStream_t st) {
+static DirectPick direct_pick(const ConvPlan &p) {
+    DirectPick k{};
+    const DirectRow &few = row_for_m(kFewRows, p.M);
     if (narrow_ok(p)) {
-        dim3 grid(ceil_div(p.Lt, 1024), p.B, p.M == 32 ? 2 : 1), block(256);
-        if (grid.y > 65535) return fail(AGX_ERR_BAD_SHAPE, "conv_narrow: grid too large");
-        if (p.M == 32)
-            hipLaunchKernelGGL(conv_narrow_kernel<16>, grid, block, 0, st, p, x, wp, bias, res, y);
-        else if (p.M == 2)
-            hipLaunchKernelGGL(conv_narrow_kernel<2>, grid, block, 0, st, p, x, wp, bias, res, y);
-        else
-            hipLaunchKernelGGL(conv_narrow_kernel<1>, grid, block, 0, st, p, x, wp, bias, res, y);
-        return check_launch("conv_narrow");
+        k.row = &row_for_m(kNarrowRows, p.M);
+        k.grid = dim3(ceil_div(p.Lt, 1024), p.B, p.M / k.row->n);   // M == 32: two 16-row halves
+    } else if (fewrows_ok(p, few)) {
+        k.row = &few;
+        k.grid = dim3(ceil_div(p.Lt, 256), p.B);
+        k.lds = size_t(p.J) * kWG * few.n * sizeof(float);
+    } else {
+        k.span = 255 * p.s + (p.J - 1) * p.d + 1;
+        const int cpg = p.ncv / p.G;
+        k.ci_tile = min(max((12 * 1024) / k.span, 1), cpg);   // <= 48 KB of LDS
+        k.lds = size_t(k.ci_tile) * k.span * sizeof(float);
+        k.row = &row_for_m(kDirectRows, p.M);
+        if (p.G > 1) {   // a block's rows must share their group: the widest row that divides Cout / G
+            k.row = kDirectRows;
+            while ((p.Cout / p.G) % k.row->n) ++k.row;
+        }
+        const int tiles_m = ceil_div(p.M, k.row->n);
+        k.grid = dim3(ceil_div(p.Lt, 256), tiles_m, p.B * p.Tout);
+        if (p.Tout > 1 || p.kh > 1) k.grid = dim3(p.B * p.Tout, tiles_m, ceil_div(p.Lt, 256));
+        if (k.lds > 150 * 1024) k.refusal = DIRECT_LDS;
+        else if (p.G > 1 && p.q != 1) k.refusal = DIRECT_GROUPED_PHASES;
     }
-    if (fewrows_ok(p)) {
-        dim3 grid(ceil_div(p.Lt, 256), p.B), block(256);
-        if (grid.y > 65535) return fail(AGX_ERR_BAD_SHAPE, "conv_fewrows: grid too large");
-        const int mm = p.M > 8 ? 16 : (p.M > 4 ? 8 : (p.M > 1 ? 4 : 1));
-        const size_t lds = size_t(p.J) * kWG * mm * sizeof(float);
-        if (mm == 16) hipLaunchKernelGGL(conv_fewrows_kernel<16>, grid, block, lds, st, p, x, wp, bias, res, y);
-        else if (mm == 8) hipLaunchKernelGGL(conv_fewrows_kernel<8>, grid, block, lds, st, p, x, wp, bias, res, y);
-        else if (mm == 4) hipLaunchKernelGGL(conv_fewrows_kernel<4>, grid, block, lds, st, p, x, wp, bias, res, y);
-        else hipLaunchKernelGGL(conv_fewrows_kernel<1>, grid, block, lds, st, p, x, wp, bias, res, y);
-        return check_launch("conv_fewrows");
+    if (!k.refusal && (k.grid.y > 65535 || k.grid.z > 65535)) k.refusal = DIRECT_GRID;
+    return k;
+}
+
+const char *conv_direct_variant(const ConvPlan &p) { return direct_pick(p).row->name; }
+
+int launch_conv_direct(const ConvPlan &p, const float *x, const float *wp, const float *bias, const float *res, float *y, hipStream_t st) {
+    const DirectPick k = direct_pick(p);
+    switch (k.refusal) {
+        case DIRECT_LDS: return fail(AGX_ERR_UNSUPPORTED, "conv_direct: tile needs %zu B of LDS", k.lds);
+        case DIRECT_GROUPED_PHASES: return fail(AGX_ERR_UNSUPPORTED, "conv_direct: grouped polyphase layers");
+        case DIRECT_GRID: return fail(AGX_ERR_BAD_SHAPE, "%s: grid too large", k.row->what);
+        case DIRECT_OK: break;
     }
-    const int span = 255 * p.s + (p.J - 1) * p.d + 1;
-    const int cpg = p.ncv / p.G;
-    int ci_tile = (12 * 1024) / span;  // <= 48 KB of LDS
-    if (ci_tile < 1) ci_tile = 1;
-    if (ci_tile > cpg) ci_tile = cpg;
-    const size_t lds = size_t(ci_tile) * span * sizeof(float);
-    if (lds > 150 * 1024) return fail(AGX_ERR_UNSUPPORTED, "conv_direct: tile needs %zu B of LDS", lds);
-    int co_t = p.M >= 32 ? 32 : (p.M > 4 ? 16 : (p.M > 1 ? 4 : 1));
-    if (p.G > 1) {
-        if (p.q != 1) return fail(AGX_ERR_UNSUPPORTED, "conv_direct: grouped polyphase layers");
-        const int rpg = p.Cout / p.G;  // a block's rows must share their group
-        co_t = rpg % 32 == 0 ? 32 : (rpg % 16 == 0 ? 16 : (rpg % 4 == 0 ? 4 : 1));
-    }
-    dim3 grid(ceil_div(p.Lt, 256), ceil_div(p.M, co_t), p.B * p.Tout), block(256);
-    if (p.Tout > 1 || p.kh > 1) grid = dim3(p.B * p.Tout, ceil_div(p.M, co_t), ceil_div(p.Lt, 256));
-    if (grid.y > 65535 || grid.z > 65535) return fail(AGX_ERR_BAD_SHAPE, "conv_direct: grid too large");
-    switch (co_t) {
-        case 32:
-            hipLaunchKernelGGL(conv_direct_kernel<32>, grid, block, lds, st, p, ci_tile, span, x, wp, bias, res, y);
-            break;
-        case 16:
-            hipLaunchKernelGGL(conv_direct_kernel<16>, grid, block, lds, st, p, ci_tile, span, x, wp, bias, res, y);
-            break;
-        case 4:
-            hipLaunchKernelGGL(conv_direct_kernel<4>, grid, block, lds, st, p, ci_tile, span, x, wp, bias, res, y);
-            break;
-        default:
-            hipLaunchKernelGGL(conv_direct_kernel<1>, grid, block, lds, st, p, ci_tile, span, x, wp, bias, res, y);
-            break;
-    }
-    return check_launch("conv_direct");
+    k.row->launch(k, p, x, wp, bias, res, y, st);
+    return check_launch(k.row->what);
 }
 
 }  // namespace agx

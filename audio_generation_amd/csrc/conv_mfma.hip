@@ -230,13 +230,16 @@ static int tile_span(const ConvPlan &p, int BN, int *R, int *WF) {
     return ((r - 1) * p.sh + p.kh) * ((wf - 1) * p.s + p.J / p.kh);
 }
 
+// double-buffered input tile of CC channels
+static size_t tile_lds(int cc, int span) { return size_t(2) * cc * span * sizeof(float); }
+
 template <int MW, int NW, int WM, int WN, int CC, int MODE = 0, int PREC = 0>
 static int launch_variant(const ConvPlan &p0, const float *x, const float *wp, const float *bias,
                           const float *res, float *y, hipStream_t st) {
     constexpr int BM = 32 * MW * WM, BN = 32 * NW * WN;
     ConvPlan p = p0;
     const int span = tile_span(p0, BN, &p.pm_R, &p.pm_WF);
-    const size_t lds = size_t(2) * CC * span * sizeof(float);  // double-buffered input tile
+    const size_t lds = tile_lds(CC, span);
     if (lds > 160 * 1024) return fail(AGX_ERR_UNSUPPORTED, "conv_mfma: tile needs %zu B of LDS", lds);
     auto kern = conv_mfma_kernel<MW, NW, WM, WN, CC, MODE, PREC>;
     static DeviceOnce once;
@@ -253,84 +256,85 @@ static int launch_variant(const ConvPlan &p0, const float *x, const float *wp, c
 // ---- tile variant table -----------------------------------------------------------
 // Preference order per M class; a variant is eligible when its input tile fits LDS.
 // <= 72 KB keeps two workgroups resident per CU, which is what hides the staging phase.
+typedef int (*ConvLaunch)(const ConvPlan &, const float *, const float *, const float *, const float *, float *, hipStream_t);
 struct Variant {
     int mw, nw, wm, wn, cc;
     const char *name;
-    int (*launch)(const ConvPlan &, const float *, const float *, const float *, const float *, float *,
-                  hipStream_t);
-    int (*launch2d)(const ConvPlan &, const float *, const float *, const float *, const float *, float *,
-                    hipStream_t);  // row-folded 2-D; nullptr: no 2-D instantiation of this tile
-    int (*launch_patch)(const ConvPlan &, const float *, const float *, const float *, const float *, float *,
-                        hipStream_t);  // patch 2-D
-    int (*launch_bf)(const ConvPlan &, const float *, const float *, const float *, const float *, float *,
-                     hipStream_t);     // 1-D bf16x3 (16-channel chunks only)
-    int (*launch_patch_bf)(const ConvPlan &, const float *, const float *, const float *, const float *, float *,
-                           hipStream_t);   // patch 2-D bf16x3
+    ConvLaunch launch[3][2];   // [MODE: 1-D, row-folded 2-D, patch 2-D][PREC: fp32, bf16x3]; nullptr: not instantiated
 };
+// What is built of a tile: the 1-D fp32 kernel; + the two 2-D modes; + bf16x3, 1-D and patch (16-channel chunks only)
+enum VariantForms { ONE_D, TWO_D, BF16X3 };
+template <int MW, int NW, int WM, int WN, int CC, VariantForms F>
+static constexpr Variant variant(const char *name) {
+    Variant v{MW, NW, WM, WN, CC, name, {{launch_variant<MW, NW, WM, WN, CC>}}};
+    if constexpr (F >= TWO_D) v.launch[1][0] = launch_variant<MW, NW, WM, WN, CC, 1>, v.launch[2][0] = launch_variant<MW, NW, WM, WN, CC, 2>;
+    if constexpr (F >= BF16X3) v.launch[0][1] = launch_variant<MW, NW, WM, WN, CC, 0, 1>, v.launch[2][1] = launch_variant<MW, NW, WM, WN, CC, 2, 1>;
+    return v;
+}
+#define AGX_VARIANT(MW, NW, WM, WN, CC, FORMS) variant<MW, NW, WM, WN, CC, FORMS>("conv_mfma<" #MW "," #NW "," #WM "," #WN "," #CC ">")
 
-#define AGX_VARIANT(MW, NW, WM, WN, CC) \
-    { MW, NW, WM, WN, CC, "conv_mfma<" #MW "," #NW "," #WM "," #WN "," #CC ">", launch_variant<MW, NW, WM, WN, CC>, nullptr, nullptr, nullptr, nullptr }
-#define AGX_VARIANT2(MW, NW, WM, WN, CC) \
-    { MW, NW, WM, WN, CC, "conv_mfma<" #MW "," #NW "," #WM "," #WN "," #CC ">", launch_variant<MW, NW, WM, WN, CC>, \
-      launch_variant<MW, NW, WM, WN, CC, 1>, launch_variant<MW, NW, WM, WN, CC, 2>, nullptr, nullptr }
-#define AGX_VARIANT3(MW, NW, WM, WN, CC) \
-    { MW, NW, WM, WN, CC, "conv_mfma<" #MW "," #NW "," #WM "," #WN "," #CC ">", launch_variant<MW, NW, WM, WN, CC>, \
-      launch_variant<MW, NW, WM, WN, CC, 1>, launch_variant<MW, NW, WM, WN, CC, 2>, launch_variant<MW, NW, WM, WN, CC, 0, 1>, \
-      launch_variant<MW, NW, WM, WN, CC, 2, 1> }
-
-static const Variant kWide[] = {AGX_VARIANT3(2, 2, 2, 2, 16), AGX_VARIANT2(2, 2, 2, 2, 8), AGX_VARIANT(2, 2, 2, 2, 32)};
+static const Variant kWide[] = {AGX_VARIANT(2, 2, 2, 2, 16, BF16X3), AGX_VARIANT(2, 2, 2, 2, 8, TWO_D), AGX_VARIANT(2, 2, 2, 2, 32, ONE_D)};
 // 128 x 64 tiles for short signals: twice the workgroups when the 128 x 128 grid would leave
 // a CU with a single resident workgroup (nothing to overlap staging / epilogue with).
-static const Variant kWideShort[] = {AGX_VARIANT3(1, 2, 4, 1, 16), AGX_VARIANT2(1, 2, 4, 1, 8), AGX_VARIANT(1, 2, 4, 1, 32)};
-static const Variant kWideAlt[] = {AGX_VARIANT(1, 4, 4, 1, 16), AGX_VARIANT(1, 4, 4, 1, 8), AGX_VARIANT(1, 4, 4, 1, 32)};
-static const Variant kMid[] = {AGX_VARIANT3(2, 2, 1, 4, 16), AGX_VARIANT2(2, 2, 1, 4, 8), AGX_VARIANT3(2, 1, 1, 4, 16),
-                               AGX_VARIANT2(2, 1, 1, 4, 8),  AGX_VARIANT(2, 2, 1, 4, 32)};
-static const Variant kNarrow[] = {AGX_VARIANT3(1, 4, 1, 4, 16), AGX_VARIANT2(1, 4, 1, 4, 8), AGX_VARIANT3(1, 1, 1, 4, 16),
-                                  AGX_VARIANT2(1, 1, 1, 4, 8),  AGX_VARIANT(1, 4, 1, 4, 32)};
+static const Variant kWideShort[] = {AGX_VARIANT(1, 2, 4, 1, 16, BF16X3), AGX_VARIANT(1, 2, 4, 1, 8, TWO_D), AGX_VARIANT(1, 2, 4, 1, 32, ONE_D)};
+static const Variant kWideAlt[] = {AGX_VARIANT(1, 4, 4, 1, 16, ONE_D), AGX_VARIANT(1, 4, 4, 1, 8, ONE_D), AGX_VARIANT(1, 4, 4, 1, 32, ONE_D)};
+static const Variant kMid[] = {AGX_VARIANT(2, 2, 1, 4, 16, BF16X3), AGX_VARIANT(2, 2, 1, 4, 8, TWO_D), AGX_VARIANT(2, 1, 1, 4, 16, BF16X3),
+                               AGX_VARIANT(2, 1, 1, 4, 8, TWO_D),   AGX_VARIANT(2, 2, 1, 4, 32, ONE_D)};
+static const Variant kNarrow[] = {AGX_VARIANT(1, 4, 1, 4, 16, BF16X3), AGX_VARIANT(1, 4, 1, 4, 8, TWO_D), AGX_VARIANT(1, 1, 1, 4, 16, BF16X3),
+                                  AGX_VARIANT(1, 1, 1, 4, 8, TWO_D),   AGX_VARIANT(1, 4, 1, 4, 32, ONE_D)};
+constexpr int kNarrow128 = 2;   // kNarrow from here on: the 128-column tiles
+
+struct VariantList { const Variant *v; int n; };
+template <int N>
+static constexpr VariantList list_of(const Variant (&list)[N], int from = 0) { return {list + from, N - from}; }
 
 static size_t variant_lds(const Variant &v, const ConvPlan &p) {
-    const int bn = 32 * v.nw * v.wn;
-    return size_t(2) * v.cc * size_t(tile_span(p, bn, nullptr, nullptr)) * sizeof(float);
+    return tile_lds(v.cc, tile_span(p, 32 * v.nw * v.wn, nullptr, nullptr));
 }
 
-static const Variant *pick(const Variant *list, int n, const ConvPlan &p, int want_cc) {
+static const Variant *pick(VariantList list, const ConvPlan &p, int want_cc) {
     if (want_cc) {
-        for (int i = 0; i < n; ++i)
-            if (list[i].cc == want_cc && (want_cc != 32 || p.Cin % 32 == 0) && variant_lds(list[i], p) <= 160 * 1024)
-                return &list[i];
+        for (int i = 0; i < list.n; ++i)
+            if (list.v[i].cc == want_cc && (want_cc != 32 || p.Cin % 32 == 0) && variant_lds(list.v[i], p) <= 160 * 1024)
+                return &list.v[i];
         return nullptr;
     }
     // (32-channel chunks measured no better than 16 on any config-S shape: kept as forced variants only)
-    for (int i = 0; i < n; ++i)
-        if (list[i].cc != 32 && variant_lds(list[i], p) <= 72 * 1024) return &list[i];
-    for (int i = 0; i < n; ++i)
-        if (list[i].cc != 32 && variant_lds(list[i], p) <= 160 * 1024) return &list[i];
+    for (size_t budget : {72 * 1024, 160 * 1024})
+        for (int i = 0; i < list.n; ++i)
+            if (list.v[i].cc != 32 && variant_lds(list.v[i], p) <= budget) return &list.v[i];
     return nullptr;
 }
 
 static const Variant *select_variant(const ConvPlan &p) {
     if (p.Cin % 16 != 0 || p.M < (p.pm_R ? 8 : 32) || p.G != 1) return nullptr;   // patch tiles tolerate few rows (clamped)
-    const Variant *list = p.M >= 128 ? kWide : (p.M >= 64 ? kMid : kNarrow);
-    const int n = p.M >= 128 ? 3 : 5;
-    if (p.M >= 128 && tuning().conv_shape == 1) list = kWideAlt;
-    const Variant *v = pick(list, n, p, p.prec ? 16 : tuning().conv_cc);
+    const bool wide = p.M >= 128, narrow = p.M < 64;
+    const VariantList list = wide ? (tuning().conv_shape == 1 ? list_of(kWideAlt) : list_of(kWide)) : (narrow ? list_of(kNarrow) : list_of(kMid));
+    const Variant *v = pick(list, p, p.prec ? 16 : tuning().conv_cc);
     // row-folded 2-D layers with few rows (the 2-channel 7x7 first conv of the STFT discriminators) on narrow maps: a tile
     // is ONE output row, so the 512-column tile of kNarrow's first entry is 25-50 % full on 128 / 256-column maps
     // (4.4 ms against 1.1 ms for the same work on 1024 columns): 128-column tiles there
-    if (v && list == kNarrow && !p.pm_R && (p.kh > 1 || p.Tout > 1) && p.Lt <= 256 && !p.prec && !tuning().conv_cc) {
-        const Variant *vn = pick(kNarrow + 2, 2, p, 0);
+    if (v && narrow && !p.pm_R && (p.kh > 1 || p.Tout > 1) && p.Lt <= 256 && !p.prec && !tuning().conv_cc) {
+        const Variant *vn = pick(list_of(kNarrow, kNarrow128), p, 0);
         if (vn) v = vn;
     }
-    if (v && p.M >= 128 && tuning().conv_short && !p.pm_R) {
+    if (v && wide && tuning().conv_short && !p.pm_R) {
         // Short signals: the same channel chunk (= the same summation order, so results do not depend on
         // the batch size or the signal length) on 128 x 64 tiles.
         const long wgs = long(ceil_div(p.Lt, 128)) * ceil_div(p.M, 128) * p.B * p.Tout;
         if (wgs < 2 * 256) {
-            const Variant *vs = pick(kWideShort, 3, p, v->cc);
+            const Variant *vs = pick(list_of(kWideShort), p, v->cc);
             if (vs) v = vs;
         }
     }
     return v;
+}
+
+// The instantiation of a tile that runs a plan: MODE 2 for patch plans, 1 for row-folded 2-D plans (several rows, a
+// kernel with rows, or virtual channels padded up to the weight group), 0 for 1-D; PREC = p.prec
+static ConvLaunch variant_launch(const Variant &v, const ConvPlan &p) {
+    const int mode = p.pm_R ? 2 : (p.kh > 1 || p.Tout > 1 || p.ncv != p.Cin) ? 1 : 0;
+    return v.launch[mode][p.prec ? 1 : 0];
 }
 
 bool conv_mfma_supported(const ConvPlan &p) { return select_variant(p) != nullptr; }
@@ -347,21 +351,11 @@ int launch_conv_mfma(const ConvPlan &p, const float *x, const float *wp, const f
         return fail(AGX_ERR_UNSUPPORTED,
                     "conv_mfma: needs Cin %% 16 == 0, q*Cout >= 32 and an input tile that fits LDS (Cin=%d M=%d s=%d J=%d d=%d)",
                     p.Cin, p.M, p.s, p.J, p.d);
-    if (p.prec) {
-        if (p.pm_R && v->launch_patch_bf) return v->launch_patch_bf(p, x, wp, bias, res, y, st);
-        if (!v->launch_bf || p.pm_R || p.kh > 1 || p.Tout > 1)
-            return fail(AGX_ERR_UNSUPPORTED, "conv_mfma: no bf16x3 instantiation for this layer (%s)", v->name);
-        return v->launch_bf(p, x, wp, bias, res, y, st);
-    }
-    if (p.pm_R) {
-        if (!v->launch_patch) return fail(AGX_ERR_UNSUPPORTED, "conv_mfma: no 2-D instantiation of %s", v->name);
-        return v->launch_patch(p, x, wp, bias, res, y, st);
-    }
-    if (p.kh > 1 || p.Tout > 1 || p.ncv != p.Cin) {
-        if (!v->launch2d) return fail(AGX_ERR_UNSUPPORTED, "conv_mfma: no 2-D instantiation of %s", v->name);
-        return v->launch2d(p, x, wp, bias, res, y, st);
-    }
-    return v->launch(p, x, wp, bias, res, y, st);
+    const ConvLaunch launch = variant_launch(*v, p);
+    if (!launch)
+        return p.prec ? fail(AGX_ERR_UNSUPPORTED, "conv_mfma: no bf16x3 instantiation for this layer (%s)", v->name)
+                      : fail(AGX_ERR_UNSUPPORTED, "conv_mfma: no 2-D instantiation of %s", v->name);
+    return launch(p, x, wp, bias, res, y, st);
 }
 
 }  // namespace agx

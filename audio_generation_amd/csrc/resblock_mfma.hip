@@ -189,93 +189,90 @@ __global__ __launch_bounds__(256, OCC) void resblock_mfma_kernel(ConvPlan p, int
     AGX_STAMP(5);
 }
 
-template <int MW, int NW, int CC, int SCHED = kSchedDefault, int OCC = (MW <= 4 ? 2 : 1), int PREC = 0>
-static int launch_rb(const ConvPlan &p, const float *x, const float *w1, const float *b1, const float *w2,
+// ---- host side ---------------------------------------------------------------------
+// What rb_pick resolves a plan to: the support test, the name query and the launcher all read it.
+struct RbRow;
+typedef int (*RbLaunch)(const ConvPlan &, int span, size_t lds, const float *, const float *, const float *, const float *,
+                        const float *, float *, int, hipStream_t);
+// row: nullptr = no fused kernel for the plan; span: LDS floats per staged channel; lds: the double-buffered input tile
+struct RbPick { const RbRow *row; RbLaunch launch; const char *name; int span; size_t lds; };
+
+template <int MW, int NW, int CC, int SCHED = kSchedDefault, int PREC = 0, int OCC = (MW <= 4 ? 2 : 1)>
+static int launch_rb(const ConvPlan &p, int span, size_t lds, const float *x, const float *w1, const float *b1, const float *w2,
                      const float *b2, float *y, int post_act, hipStream_t st) {
-    constexpr int BN = 32 * NW * 4;
-    const int span = (BN - 1) + (p.J - 1) * p.d + 1;
-    size_t lds = size_t(2) * CC * span * sizeof(float);  // double-buffered input tile
-    if (lds > 160 * 1024) return fail(AGX_ERR_UNSUPPORTED, "resblock: tile needs %zu B of LDS", lds);
     const int wgs = tuning().rb_wgs;  // diagnostic: cap workgroups per CU by requesting more LDS
     if (wgs >= 1 && wgs <= 3 && lds < size_t(160 * 1024) / wgs) lds = size_t(160 * 1024) / wgs;
     auto kern = resblock_mfma_kernel<MW, NW, CC, SCHED, OCC, PREC>;
     static DeviceOnce once;
     if (int rc = prepare_kernel(reinterpret_cast<const void *>(kern), once, 160 * 1024, nullptr, "resblock_mfma")) return rc;
-    dim3 grid(ceil_div(p.Lin, BN), p.B), block(256);
+    dim3 grid(ceil_div(p.Lin, 32 * NW * 4), p.B), block(256);
     if (grid.y > 65535) return fail(AGX_ERR_BAD_SHAPE, "resblock: batch too large for one launch");
     hipLaunchKernelGGL(kern, grid, block, lds, st, p, span, post_act, x, w1, b1, w2, b2, y);
     return check_launch("resblock_mfma");
 }
 
-static int rb_bn(int c) { return c == 32 ? 512 : (c == 64 ? 256 : 128); }
+// One row per channel count: the tile (a wave owns all 32 MW channels of its 32 NW columns, 4 waves side by side), the
+// measured schedules, and the instantiations that exist.  A name says MW, NW and the channel chunk only.
+struct RbRow {
+    int c, bn;             // channels, tile width: the kernel's C and BN
+    int sched, bf_sched;   // schedule the knobs rb_sched / bf_sched = -1 stand for (fp32, bf16x3)
+    const char *name, *name_cc32;
+    RbLaunch fp32[3], cc32, occ3, bf[3];   // by SCHED; 32-channel chunks; capped at 168 VGPRs (nullptr: not built); bf16x3 by SCHED
+};
+template <int MW, int NW, int SCHED, int BF_SCHED>
+static constexpr RbRow rb_row(const char *name, const char *name_cc32) {
+    RbRow r{32 * MW, 32 * NW * 4, SCHED, BF_SCHED, name, name_cc32,
+            {launch_rb<MW, NW, 16, 0>, launch_rb<MW, NW, 16, 1>, launch_rb<MW, NW, 16, 2>}, launch_rb<MW, NW, 32>, nullptr,
+            {launch_rb<MW, NW, 16, 0, 1>, launch_rb<MW, NW, 16, 1, 1>, launch_rb<MW, NW, 16, 2, 1>}};
+    if constexpr (MW <= 4) r.occ3 = launch_rb<MW, NW, 16, SCHED, 0, 3>;   // diagnostic: 3 waves/SIMD
+    return r;
+}
+#define AGX_RB_ROW(MW, NW, SCHED, BF_SCHED, NAME_CC32) \
+    rb_row<MW, NW, SCHED, BF_SCHED>("resblock_mfma<" #MW "," #NW ",16>", "resblock_mfma<" #MW "," #NW "," #NAME_CC32 ">")
+// schedules: measured best per shape, in-process A/B (tools/ab_bench.py rb_sched 0 1 2; AGX_BF16X3=1 ... bf_sched 0 1 2)
+static const RbRow kRbRows[] = {
+    AGX_RB_ROW(1, 4, 1, 0, 32),   // C = 32:  fp32 1 (-12 % vs 0), bf16x3 0
+    AGX_RB_ROW(2, 2, 2, 2, 32),   // C = 64:  fp32 2 (-6 %), bf16x3 2 (-5 %)
+    AGX_RB_ROW(4, 1, 1, 1, 32),   // C = 128: fp32 1 (-11 %), bf16x3 1 (-12 %)
+    AGX_RB_ROW(8, 1, 2, 1, 16),   // C = 256: fp32 2 (-2 %), bf16x3 1 (-6 %); its 32-channel build has always answered <8,1,16>
+};
 
-bool resblock_fused_supported(const ConvPlan &p) {
-    if (p.Cin != p.Cout || p.s != 1 || p.q != 1 || p.Lvalid != p.Lin || p.Lt != p.Lin) return false;
-    if (p.Cin != 32 && p.Cin != 64 && p.Cin != 128 && p.Cin != 256) return false;
-    const size_t span = size_t(rb_bn(p.Cin) - 1) + size_t(p.J - 1) * p.d + 1;
-    return 2 * 16 * span * sizeof(float) <= 160 * 1024;
+// Precedence of the knobs: bf16x3 descriptors first, then rb_cc = 32 (where the wider chunk fits), then rb_occ = 3, then the
+// fp32 schedule.
+static RbPick rb_pick(const ConvPlan &p) {
+    RbPick k{};
+    if (p.Cin != p.Cout || p.s != 1 || p.q != 1 || p.Lvalid != p.Lin || p.Lt != p.Lin) return k;
+    for (const RbRow &r : kRbRows) {
+        if (r.c != p.Cin) continue;
+        k.span = (r.bn - 1) + (p.J - 1) * p.d + 1;
+        const size_t chunk = size_t(2) * k.span * sizeof(float);   // bytes per staged channel
+        if (16 * chunk > 160 * 1024) return k;
+        const int sched = tuning().rb_sched, bs = tuning().bf_sched;
+        const bool cc32 = !p.prec && tuning().rb_cc == 32 && 32 * chunk <= 160 * 1024;
+        k.row = &r;
+        k.name = cc32 ? r.name_cc32 : r.name;
+        k.lds = (cc32 ? 32 : 16) * chunk;
+        if (p.prec) k.launch = r.bf[bs < 0 ? r.bf_sched : (bs == 1 || bs == 2 ? bs : 0)];   // both packed images are bf16x3 images
+        else if (cc32) k.launch = r.cc32;
+        else if (tuning().rb_occ == 3 && r.occ3) k.launch = r.occ3;
+        else k.launch = r.fp32[sched < 0 ? r.sched : (sched == 0 || sched == 2 ? sched : 1)];
+        return k;
+    }
+    return k;
 }
 
-static bool rb_use_cc32(const ConvPlan &p) {
-    const size_t span = size_t(rb_bn(p.Cin) - 1) + size_t(p.J - 1) * p.d + 1;
-    return tuning().rb_cc == 32 && 2 * 32 * span * sizeof(float) <= 160 * 1024;
-}
+bool resblock_fused_supported(const ConvPlan &p) { return rb_pick(p).row != nullptr; }
 
 const char *resblock_variant(const ConvPlan &p) {
-    const bool c32 = rb_use_cc32(p) && !p.prec;
-    switch (p.Cin) {
-        case 32: return c32 ? "resblock_mfma<1,4,32>" : "resblock_mfma<1,4,16>";
-        case 64: return c32 ? "resblock_mfma<2,2,32>" : "resblock_mfma<2,2,16>";
-        case 128: return c32 ? "resblock_mfma<4,1,32>" : "resblock_mfma<4,1,16>";
-        default: return "resblock_mfma<8,1,16>";
-    }
+    const RbPick k = rb_pick(p);
+    return k.row ? k.name : "resblock_mfma<unsupported>";
 }
 
 int launch_resblock_fused(const ConvPlan &p, const float *x, const float *w1, const float *b1,
                           const float *w2, const float *b2, float *y, int post_act, hipStream_t st) {
-    if (!resblock_fused_supported(p)) return fail(AGX_ERR_UNSUPPORTED, "resblock: no fused kernel for C=%d", p.Cin);
-    const bool c32 = rb_use_cc32(p);
-    // phase scheduling: measured best per shape (tools/ab_bench.py rb_sched 0 1 2, in-process A/B):
-    // C=32: 1 (-12 % vs 0), C=64: 2 (-6 %), C=128: 1 (-11 %), C=256: 2 (-2 %); knob -1 = this table
-    int sched = tuning().rb_sched;
-    if (sched < 0) sched = (p.Cin == 64 || p.Cin == 256) ? 2 : 1;
-#define AGX_RB(MW, NW)                                                                                   \
-    (c32 ? launch_rb<MW, NW, 32>(p, x, w1, b1, w2, b2, y, post_act, st)                                 \
-         : sched == 0 ? launch_rb<MW, NW, 16, 0>(p, x, w1, b1, w2, b2, y, post_act, st)                 \
-         : sched == 2 ? launch_rb<MW, NW, 16, 2>(p, x, w1, b1, w2, b2, y, post_act, st)                 \
-                      : launch_rb<MW, NW, 16, 1>(p, x, w1, b1, w2, b2, y, post_act, st))
-    if (p.prec) {   // bf16x3 (AGX_IMPL_MFMA_BF16X3): both packed images are bf16x3 images
-        // measured per shape (AGX_BF16X3=1 tools/ab_bench.py bf_sched 0 1 2): C=32: 0, C=64: 2 (-5 %), C=128: 1 (-12 %),
-        // C=256: 1 (-6 %); knob -1 = this table
-        int bs = tuning().bf_sched;
-        if (bs < 0) bs = p.Cin == 64 ? 2 : (p.Cin >= 128 ? 1 : 0);
-#define AGX_RBF(MW, NW, OCC)                                                                        \
-    (bs == 1 ? launch_rb<MW, NW, 16, 1, OCC, 1>(p, x, w1, b1, w2, b2, y, post_act, st)             \
-     : bs == 2 ? launch_rb<MW, NW, 16, 2, OCC, 1>(p, x, w1, b1, w2, b2, y, post_act, st)           \
-               : launch_rb<MW, NW, 16, 0, OCC, 1>(p, x, w1, b1, w2, b2, y, post_act, st))
-        switch (p.Cin) {
-            case 32: return AGX_RBF(1, 4, 2);
-            case 64: return AGX_RBF(2, 2, 2);
-            case 128: return AGX_RBF(4, 1, 2);
-            default: return AGX_RBF(8, 1, 1);
-        }
-#undef AGX_RBF
-    }
-    if (tuning().rb_occ == 3 && !c32) {  // diagnostic: cap VGPRs at 168 so that 3 waves/SIMD fit
-        switch (p.Cin) {
-            case 32: return launch_rb<1, 4, 16, 1, 3>(p, x, w1, b1, w2, b2, y, post_act, st);
-            case 64: return launch_rb<2, 2, 16, 2, 3>(p, x, w1, b1, w2, b2, y, post_act, st);
-            case 128: return launch_rb<4, 1, 16, 1, 3>(p, x, w1, b1, w2, b2, y, post_act, st);
-            default: break;
-        }
-    }
-    switch (p.Cin) {
-        case 32: return AGX_RB(1, 4);
-        case 64: return AGX_RB(2, 2);
-        case 128: return AGX_RB(4, 1);
-        default: return AGX_RB(8, 1);
-    }
-#undef AGX_RB
+    const RbPick k = rb_pick(p);
+    if (!k.row) return fail(AGX_ERR_UNSUPPORTED, "resblock: no fused kernel for C=%d", p.Cin);
+    return k.launch(p, k.span, k.lds, x, w1, b1, w2, b2, y, post_act, st);
 }
 
 }  // namespace agx
