@@ -19,9 +19,6 @@
 
 namespace agx {
 
-int launch_attention_flash(const float *qkv, const float *slopes, float *out, int B, int H, int Dh, int T, float scale_div,
-                           int precision, hipStream_t st);   // attention_flash.hip
-
 // ---------------------------------------------------------------------- LayerNorm
 // Block = 64 time steps x all channels; wave w takes channels w, w+4, ...
 __global__ __launch_bounds__(256) void layernorm_ct_kernel(const float *__restrict__ x,
@@ -234,14 +231,11 @@ __global__ __launch_bounds__(256) void attention_alibi_kernel(const float *__res
 }
 
 template <int NJ, int DVT>
-static int launch_attn(const float *qkv, const float *slopes, float *out, int B, int H, int Dh, int T,
-                       float scale_div, hipStream_t st) {
-    const size_t lds = size_t(32 * DVT) * (32 * NJ + 1) * sizeof(float);
+static int run_attention_alibi(AGX_ATTN_ARGS) {
     auto kern = attention_alibi_kernel<NJ, DVT>;
     static DeviceOnce once;
-    if (int rc = prepare_kernel(reinterpret_cast<const void *>(kern), once, 160 * 1024, nullptr, "attention")) return rc;
-    dim3 grid(ceil_div(T, 128), H, B), block(256);
-    hipLaunchKernelGGL(kern, grid, block, lds, st, qkv, slopes, out, H, Dh, T, scale_div);
+    if (int rc = prepare_kernel(reinterpret_cast<const void *>(kern), once, k.lds_limit, nullptr, "attention")) return rc;
+    hipLaunchKernelGGL(kern, k.grid, dim3(256), k.lds, st, qkv, slopes, out, H, Dh, T, scale_div);
     return check_launch("attention_alibi");
 }
 
@@ -453,6 +447,72 @@ __global__ __launch_bounds__(256) void attention_alibi_bwd_kernel(const float *_
     }
 }
 
+// ---------------------------------------------------------------------- host side: which attention kernel runs (common.hpp)
+#define AGX_ATTN_ROW(NJ, DVT) {256, "attention_alibi<" #NJ "," #DVT ">", run_attention_alibi<NJ, DVT>}
+static const AttnRow kAttnRows[9] = {AGX_ATTN_ROW(2, 1), AGX_ATTN_ROW(2, 2), AGX_ATTN_ROW(2, 4), AGX_ATTN_ROW(4, 1), AGX_ATTN_ROW(4, 2),
+                                     AGX_ATTN_ROW(4, 4), AGX_ATTN_ROW(8, 1), AGX_ATTN_ROW(8, 2), AGX_ATTN_ROW(8, 4)};   // [3 log2(NJ / 2) + log2(DVT)]
+#undef AGX_ATTN_ROW
+
+static AttnPick attn_pick(int B, int H, int Dh, int T, int precision, int flash) {
+    AttnPick k{};
+    k.bad_shape = B <= 0 || H <= 0 || Dh <= 0 || T <= 0;
+    if (k.bad_shape) k.code = fail(AGX_ERR_BAD_SHAPE, "attention_alibi: bad shape B=%d H=%d Dh=%d T=%d", B, H, Dh, T);
+    else if (precision != AGX_ATTN_FP32 && precision != AGX_ATTN_BF16) k.code = fail(AGX_ERR_BAD_SHAPE, "attention_alibi: unknown precision %d", precision);
+    else if (Dh > 128) k.code = fail(AGX_ERR_UNSUPPORTED, "attention_alibi: head_dim=%d > 128", Dh);
+    else if (H > 65535 || B > 65535) k.code = fail(AGX_ERR_BAD_SHAPE, "attention_alibi: grid too large");
+    if (k.code) return k;
+    const int dvt = Dh <= 32 ? 1 : (Dh <= 64 ? 2 : 4), di = dvt / 2;   // 32-row tiles of the head dim; di = log2(dvt)
+    k.tp = (T + 63) / 64 * 64;
+    k.lds_limit = 160 * 1024;
+    const size_t staged = size_t(2) * k.tp * 32 * dvt * 2;             // K and V of a (head, item) as bf16
+    if (precision == AGX_ATTN_FP32 && !flash && T <= 256) {            // single pass: all keys of a query in registers
+        const int ni = T <= 64 ? 0 : (T <= 128 ? 1 : 2), nj = 2 << ni;
+        k.row = &kAttnRows[3 * ni + di];
+        k.lds = size_t(32 * dvt) * (32 * nj + 1) * sizeof(float);
+    } else if (precision == AGX_ATTN_BF16 && staged <= 128 * 1024) {   // online softmax over key blocks (attention_flash.hip)
+        k.row = &attn_bf16_lds_rows()[di];
+        k.lds = staged;
+    } else {
+        k.row = &attn_flash_rows()[2 * di + precision];
+        k.lds = precision == AGX_ATTN_FP32 ? size_t(2) * 32 * dvt * 65 * sizeof(float) : 0;
+        k.lds_limit = k.lds > 48 * 1024 ? 96 * 1024 : 0;
+    }
+    k.grid = dim3(ceil_div(T, k.row->threads / 2), H, B);
+    return k;
+}
+
+template <int QB>
+static int run_attention_alibi_bwd(const AttnBwdPick &k, const float *qkv, const float *slopes, const float *dout, float *dqkv, int B,
+                                   int H, int Dh, int T, float scale_div, hipStream_t st) {
+    auto kern = attention_alibi_bwd_kernel<QB>;
+    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 156 * 1024);
+    if (e != hipSuccess) return fail(AGX_ERR_LAUNCH, "hipFuncSetAttribute: %s", hipGetErrorString(e));
+    hipLaunchKernelGGL(kern, dim3(H, B), dim3(256), k.lds, st, qkv, slopes, dout, dqkv, H, Dh, T, scale_div);
+    return check_launch("agx_attention_alibi_backward");
+}
+
+AttnBwdPick attn_bwd_pick(int B, int H, int Dh, int T, int split) {
+    AttnBwdPick k{};
+    const char *op = split ? "attention_alibi_backward_ex" : "attention_alibi_backward";
+    k.bad_shape = B <= 0 || H <= 0 || Dh <= 0 || T <= 0;
+    if (k.bad_shape) k.code = fail(AGX_ERR_BAD_SHAPE, "%s: bad shape", op);
+    else if (!split && (T > 256 || Dh > 64)) k.code = fail(AGX_ERR_UNSUPPORTED, "%s: T <= 256, head_dim <= 64", op);   // K, V in LDS, dK, dV in registers
+    else if (split && Dh > 128) k.code = fail(AGX_ERR_UNSUPPORTED, "%s: head_dim=%d > 128", op, Dh);
+    else if (H > 65535 || B > 65535) k.code = fail(AGX_ERR_BAD_SHAPE, "%s: grid too large", op);
+    if (k.code) return k;
+    if (split) {
+        k.name = "attn_bwd_stats+attn_bwd_dq+attn_bwd_dkv";   // attention_flash.hip
+        return k;
+    }
+    auto lds_of = [&](int qb) { return size_t(2 * Dh * T + 2 * Dh * qb + 2 * qb * T) * sizeof(float); };
+    k.qb = lds_of(16) <= 150 * 1024 ? 16 : 8;
+    k.name = k.qb == 16 ? "attention_alibi_bwd<16>" : "attention_alibi_bwd<8>";
+    k.lds = lds_of(k.qb);
+    // the kernel also holds 2 KB of static LDS (row reductions): ask for 156 KB of dynamic space at most
+    if (k.lds > 156 * 1024) k.code = fail(AGX_ERR_UNSUPPORTED, "%s: needs %zu B of LDS", op, k.lds);
+    return k;
+}
+
 }  // namespace agx
 
 extern "C" {
@@ -477,27 +537,21 @@ int agx_layernorm_ct_backward(const float *x, const float *weight, const float *
 int agx_attention_alibi_backward(const float *qkv, const float *slopes, const float *dout, float *dqkv, int32_t batch,
                                  int32_t heads, int32_t head_dim, int32_t t, float scale_div, void *stream) {
     using namespace agx;
-    if (batch <= 0 || heads <= 0 || head_dim <= 0 || t <= 0)
-        return fail(AGX_ERR_BAD_SHAPE, "attention_alibi_backward: bad shape");
-    if (!qkv || !slopes || !dout || !dqkv) return fail(AGX_ERR_NULL_POINTER, "attention_alibi_backward: NULL pointer");
-    if (t > 256 || head_dim > 64) return fail(AGX_ERR_UNSUPPORTED, "attention_alibi_backward: T <= 256, head_dim <= 64");
-    if (heads > 65535 || batch > 65535) return fail(AGX_ERR_BAD_SHAPE, "attention_alibi_backward: grid too large");
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    auto lds_of = [&](int qb) { return size_t(2 * head_dim * t + 2 * head_dim * qb + 2 * qb * t) * sizeof(float); };
-    const dim3 grid(heads, batch);
-    // the kernel also holds 2 KB of static LDS (row reductions): ask for 156 KB of dynamic space at most
-    constexpr size_t kDynMax = 156 * 1024;
-    auto run = [&](auto kern, int qb) -> int {
-        if (lds_of(qb) > kDynMax) return fail(AGX_ERR_UNSUPPORTED, "attention_alibi_backward: needs %zu B of LDS", lds_of(qb));
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kern),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, int(kDynMax));
-        if (e != hipSuccess) return fail(AGX_ERR_LAUNCH, "hipFuncSetAttribute: %s", hipGetErrorString(e));
-        hipLaunchKernelGGL(kern, grid, dim3(256), lds_of(qb), st, qkv, slopes, dout, dqkv, heads, head_dim, t, scale_div);
-        return check_launch("agx_attention_alibi_backward");
-    };
-    return lds_of(16) <= 150 * 1024 ? run(attention_alibi_bwd_kernel<16>, 16) : run(attention_alibi_bwd_kernel<8>, 8);
+    const AttnBwdPick k = attn_bwd_pick(batch, heads, head_dim, t, 0);
+    if (!k.bad_shape && (!qkv || !slopes || !dout || !dqkv)) return fail(AGX_ERR_NULL_POINTER, "attention_alibi_backward: NULL pointer");
+    if (k.code) return k.code;
+    return (k.qb == 16 ? run_attention_alibi_bwd<16> : run_attention_alibi_bwd<8>)(k, qkv, slopes, dout, dqkv, batch, heads, head_dim, t,
+                                                                                  scale_div, static_cast<hipStream_t>(stream));
 }
 
+int agx_attention_backward_kernel_name(int32_t heads, int32_t head_dim, int32_t t, int32_t split, char *buf, size_t buf_len) {
+    using namespace agx;
+    const AttnBwdPick k = attn_bwd_pick(1, heads, head_dim, t, split);
+    if (k.code) return k.code;
+    if (!buf || buf_len == 0) return fail(AGX_ERR_NULL_POINTER, "agx_attention_backward_kernel_name: NULL buffer");
+    snprintf(buf, buf_len, "%s", k.name);
+    return AGX_OK;
+}
 
 int agx_layernorm_ct(const float *x, const float *weight, const float *bias, float *y, int32_t batch,
                      int32_t channels, int32_t t, float eps, void *stream) {
@@ -529,33 +583,20 @@ int agx_attention_alibi(const float *qkv, const float *slopes, float *out, int32
 int agx_attention_alibi_ex(const float *qkv, const float *slopes, float *out, int32_t batch, int32_t heads,
                            int32_t head_dim, int32_t t, float scale_div, int32_t precision, int32_t flash, void *stream) {
     using namespace agx;
-    if (batch <= 0 || heads <= 0 || head_dim <= 0 || t <= 0)
-        return fail(AGX_ERR_BAD_SHAPE, "attention_alibi: bad shape B=%d H=%d Dh=%d T=%d", batch, heads, head_dim, t);
-    if (!qkv || !slopes || !out) return fail(AGX_ERR_NULL_POINTER, "attention_alibi: NULL pointer");
-    if (precision != AGX_ATTN_FP32 && precision != AGX_ATTN_BF16)
-        return fail(AGX_ERR_BAD_SHAPE, "attention_alibi: unknown precision %d", precision);
-    if (head_dim > 128) return fail(AGX_ERR_UNSUPPORTED, "attention_alibi: head_dim=%d > 128", head_dim);
-    if (heads > 65535 || batch > 65535) return fail(AGX_ERR_BAD_SHAPE, "attention_alibi: grid too large");
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    if (t > 256 || precision == AGX_ATTN_BF16 || flash)   // online softmax over key blocks (attention_flash.hip)
-        return launch_attention_flash(qkv, slopes, out, batch, heads, head_dim, t, scale_div, precision, st);
-    const int nj = t <= 64 ? 2 : (t <= 128 ? 4 : 8);
-    const int dvt = head_dim <= 32 ? 1 : (head_dim <= 64 ? 2 : 4);
-#define AGX_ATTN(NJ, DVT) return launch_attn<NJ, DVT>(qkv, slopes, out, batch, heads, head_dim, t, scale_div, st)
-    if (nj == 2) {
-        if (dvt == 1) AGX_ATTN(2, 1);
-        if (dvt == 2) AGX_ATTN(2, 2);
-        AGX_ATTN(2, 4);
-    }
-    if (nj == 4) {
-        if (dvt == 1) AGX_ATTN(4, 1);
-        if (dvt == 2) AGX_ATTN(4, 2);
-        AGX_ATTN(4, 4);
-    }
-    if (dvt == 1) AGX_ATTN(8, 1);
-    if (dvt == 2) AGX_ATTN(8, 2);
-    AGX_ATTN(8, 4);
-#undef AGX_ATTN
+    const AttnPick k = attn_pick(batch, heads, head_dim, t, precision, flash);
+    if (!k.bad_shape && (!qkv || !slopes || !out)) return fail(AGX_ERR_NULL_POINTER, "attention_alibi: NULL pointer");
+    if (k.code) return k.code;
+    return k.row->launch(k, qkv, slopes, out, heads, head_dim, t, scale_div, static_cast<hipStream_t>(stream));
+}
+
+int agx_attention_kernel_name(int32_t batch, int32_t heads, int32_t head_dim, int32_t t, int32_t precision, int32_t flash, char *buf,
+                              size_t buf_len) {
+    using namespace agx;
+    const AttnPick k = attn_pick(batch, heads, head_dim, t, precision, flash);
+    if (k.code) return k.code;
+    if (!buf || buf_len == 0) return fail(AGX_ERR_NULL_POINTER, "agx_attention_kernel_name: NULL buffer");
+    snprintf(buf, buf_len, "%s", k.row->name);
+    return AGX_OK;
 }
 
 }  // extern "C"

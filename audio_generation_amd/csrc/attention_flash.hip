@@ -378,46 +378,33 @@ __global__ __launch_bounds__(ABL_NT) void attention_bf16_lds_kernel(const float 
     }
 }
 
+// ------------------------------------------------------------------ host side (common.hpp; attn_pick of attention.hip chooses)
 template <int DVT>
-static int launch_bf16_lds(const float *qkv, const float *slopes, float *out, int B, int H, int Dh, int T, int Tp, float scale_div,
-                           hipStream_t st) {
-    const size_t lds = size_t(2) * Tp * 32 * DVT * 2;
+static int run_attention_bf16_lds(AGX_ATTN_ARGS) {
     auto kern = attention_bf16_lds_kernel<DVT>;
     static DeviceOnce once;
-    if (int rc = prepare_kernel(reinterpret_cast<const void *>(kern), once, 160 * 1024, nullptr, "attention_flash")) return rc;
-    hipLaunchKernelGGL(kern, dim3(ceil_div(T, ABL_NT / 2), H, B), dim3(ABL_NT), lds, st, qkv, slopes, out, H, Dh, T, Tp, scale_div);
+    if (int rc = prepare_kernel(reinterpret_cast<const void *>(kern), once, k.lds_limit, nullptr, "attention_flash")) return rc;
+    hipLaunchKernelGGL(kern, k.grid, dim3(ABL_NT), k.lds, st, qkv, slopes, out, H, Dh, T, k.tp, scale_div);
     return check_launch("attention_bf16_lds");
 }
 
 template <int DVT, int PREC>
-static int launch_flash(const float *qkv, const float *slopes, float *out, int B, int H, int Dh, int T, float scale_div,
-                        hipStream_t st) {
-    const size_t lds = PREC == 0 ? size_t(2) * 32 * DVT * 65 * sizeof(float) : 0;
+static int run_attention_flash(AGX_ATTN_ARGS) {
     auto kern = attention_flash_kernel<DVT, PREC>;
     static DeviceOnce once;
-    if (int rc = prepare_kernel(reinterpret_cast<const void *>(kern), once, lds > 48 * 1024 ? 96 * 1024 : 0, nullptr, "attention_flash")) return rc;
-    dim3 grid(ceil_div(T, 128), H, B), block(256);
-    hipLaunchKernelGGL(kern, grid, block, lds, st, qkv, slopes, out, H, Dh, T, scale_div);
+    if (int rc = prepare_kernel(reinterpret_cast<const void *>(kern), once, k.lds_limit, nullptr, "attention_flash")) return rc;
+    hipLaunchKernelGGL(kern, k.grid, dim3(256), k.lds, st, qkv, slopes, out, H, Dh, T, scale_div);
     return check_launch("attention_flash");
 }
 
-int launch_attention_flash(const float *qkv, const float *slopes, float *out, int B, int H, int Dh, int T, float scale_div,
-                           int precision, hipStream_t st) {
-    const int dvt = Dh <= 32 ? 1 : (Dh <= 64 ? 2 : 4);
-    const int Tp = (T + 63) / 64 * 64;
-    if (precision && size_t(2) * Tp * 32 * dvt * 2 <= 128 * 1024) {   // K and V of a (head, item) fit the LDS as bf16
-        if (dvt == 1) return launch_bf16_lds<1>(qkv, slopes, out, B, H, Dh, T, Tp, scale_div, st);
-        if (dvt == 2) return launch_bf16_lds<2>(qkv, slopes, out, B, H, Dh, T, Tp, scale_div, st);
-        return launch_bf16_lds<4>(qkv, slopes, out, B, H, Dh, T, Tp, scale_div, st);
-    }
-#define AGX_FL(DVT)                                                                                          \
-    return precision ? launch_flash<DVT, 1>(qkv, slopes, out, B, H, Dh, T, scale_div, st)                    \
-                     : launch_flash<DVT, 0>(qkv, slopes, out, B, H, Dh, T, scale_div, st)
-    if (dvt == 1) AGX_FL(1);
-    if (dvt == 2) AGX_FL(2);
-    AGX_FL(4);
-#undef AGX_FL
-}
+#define AGX_ATTN_ROW(DVT, PREC) {256, "attention_flash<" #DVT "," #PREC ">", run_attention_flash<DVT, PREC>}
+static const AttnRow kAttnFlashRows[6] = {AGX_ATTN_ROW(1, 0), AGX_ATTN_ROW(1, 1), AGX_ATTN_ROW(2, 0), AGX_ATTN_ROW(2, 1), AGX_ATTN_ROW(4, 0), AGX_ATTN_ROW(4, 1)};
+#undef AGX_ATTN_ROW
+#define AGX_ATTN_ROW(DVT) {ABL_NT, "attention_bf16_lds<" #DVT ">", run_attention_bf16_lds<DVT>}
+static const AttnRow kAttnBf16LdsRows[3] = {AGX_ATTN_ROW(1), AGX_ATTN_ROW(2), AGX_ATTN_ROW(4)};
+#undef AGX_ATTN_ROW
+const AttnRow *attn_flash_rows() { return kAttnFlashRows; }
+const AttnRow *attn_bf16_lds_rows() { return kAttnBf16LdsRows; }
 
 }  // namespace agx
 
@@ -687,12 +674,10 @@ int agx_attention_alibi_backward_ex(const float *qkv, const float *slopes, const
                                     float *workspace, size_t workspace_bytes, int32_t batch, int32_t heads, int32_t head_dim,
                                     int32_t t, float scale_div, void *stream) {
     using namespace agx;
-    if (batch <= 0 || heads <= 0 || head_dim <= 0 || t <= 0)
-        return fail(AGX_ERR_BAD_SHAPE, "attention_alibi_backward_ex: bad shape");
-    if (!qkv || !slopes || !out || !dout || !dqkv || !workspace)
+    const AttnBwdPick k = attn_bwd_pick(batch, heads, head_dim, t, 1);
+    if (!k.bad_shape && (!qkv || !slopes || !out || !dout || !dqkv || !workspace))
         return fail(AGX_ERR_NULL_POINTER, "attention_alibi_backward_ex: NULL pointer");
-    if (head_dim > 128) return fail(AGX_ERR_UNSUPPORTED, "attention_alibi_backward_ex: head_dim=%d > 128", head_dim);
-    if (heads > 65535 || batch > 65535) return fail(AGX_ERR_BAD_SHAPE, "attention_alibi_backward_ex: grid too large");
+    if (k.code) return k.code;
     if (workspace_bytes < agx_attention_backward_workspace_bytes(batch, heads, t))
         return fail(AGX_ERR_WORKSPACE, "attention_alibi_backward_ex: workspace too small");
     return launch_attention_flash_backward(qkv, slopes, out, dout, dqkv, workspace, batch, heads, head_dim, t, scale_div,

@@ -101,6 +101,22 @@ inline int prepare_kernel(const void *kern, DeviceOnce &once, int lds_limit_byte
 inline int ceil_div(int a, int b) { return (a + b - 1) / b; }
 inline int64_t ceil_div64(int64_t a, int64_t b) { return (a + b - 1) / b; }
 
+// Attention (attention.hip, attention_flash.hip).  One table per forward kernel template; a row's printed name and its launch
+// thunk are made from the same template arguments.  attn_pick (attention.hip) is the one place that chooses a row and sizes its
+// launch, for agx_attention_alibi_ex and agx_attention_kernel_name; attn_bwd_pick is the same for the backward entry points.
+// A pick that refuses has called fail(): code is what the caller returns (bad_shape: ahead of its NULL-pointer check).
+struct AttnPick;
+#define AGX_ATTN_ARGS const AttnPick &k, const float *qkv, const float *slopes, float *out, int H, int Dh, int T, float scale_div, hipStream_t st
+struct AttnRow { int threads; const char *name; int (*launch)(AGX_ATTN_ARGS); };   // a workgroup takes threads / 2 queries
+// lds_limit: what prepare_kernel raises the kernel's dynamic-LDS limit to (0: left alone); tp: T rounded up to 64
+struct AttnPick { const AttnRow *row; dim3 grid; size_t lds; int lds_limit, tp, code; bool bad_shape; };
+const AttnRow *attn_flash_rows();      // attention_flash.hip: attention_flash_kernel<DVT,PREC> at [2 log2(DVT) + PREC]
+const AttnRow *attn_bf16_lds_rows();   //                      attention_bf16_lds_kernel<DVT> at [log2(DVT)]
+// split = 0: the single launch of agx_attention_alibi_backward (qb = its QB, lds = its dynamic LDS); split = 1: the three kernels
+// of agx_attention_alibi_backward_ex
+struct AttnBwdPick { const char *name; int qb; size_t lds; int code; bool bad_shape; };
+AttnBwdPick attn_bwd_pick(int batch, int heads, int head_dim, int t, int split);
+
 // Grid of a persistent ring kernel: wgs resident workgroups on each CU (two where two rings fit the 160 KiB of LDS), never more
 // workgroups than tiles; -1: more than 2^30 tiles (the launcher refuses the shape).
 inline int ring_wgs_per_cu(size_t lds_bytes) { return (160 * 1024) / lds_bytes >= 2 ? 2 : 1; }

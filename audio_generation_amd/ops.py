@@ -56,10 +56,11 @@ def _conv2d_macs(desc) -> int:
     return desc.batch * desc.c_in * desc.c_out * desc.kh * desc.kw * ho * wo
 
 
-def _kernel_name(symbol: str, desc, size: int = 96) -> str:
-    """The answer of one of the library's host-only name queries (``agx_*_kernel_name``)."""
+def _kernel_name(symbol: str, *what, size: int = 96) -> str:
+    """The answer of one of the library's host-only name queries (``agx_*_kernel_name``) for a descriptor or a shape."""
     buf = ctypes.create_string_buffer(size)
-    _lib.check(getattr(_lib.load(), symbol)(ctypes.byref(desc), buf, len(buf)), symbol)
+    args = [ctypes.byref(w) if isinstance(w, ctypes.Structure) else int(w) for w in what]
+    _lib.check(getattr(_lib.load(), symbol)(*args, buf, len(buf)), symbol)
     return buf.value.decode()
 
 
@@ -254,7 +255,7 @@ def conv_bwd_weight(desc: ConvDesc, x: Tensor, dy: Tensor, v: Tensor, g: Optiona
 
 def conv_bwd_weight_kernel_name(desc: ConvDesc) -> str:
     """What ``conv_bwd_weight`` runs: "<kernel> cfg=.. op=.. slices=.. items=.." (include/agx.h)."""
-    return _kernel_name("agx_conv_bwd_weight_kernel_name", desc, 128)
+    return _kernel_name("agx_conv_bwd_weight_kernel_name", desc, size=128)
 
 
 def resblock_forward(desc: ConvDesc, x: Tensor, packed1: Tensor, bias1: Optional[Tensor],
@@ -415,10 +416,12 @@ def attention_alibi(qkv: Tensor, slopes: Tensor, heads: int, head_dim: int, scal
     if c3 != 3 * heads * head_dim:
         raise AgxError(f"attention_alibi: qkv has {c3} channels, expected {3 * heads * head_dim}")
     out = torch.empty((b, heads * head_dim, t), dtype=torch.float32, device=qkv.device)
-    name = "attention_alibi" + (":bf16" if precision == ATTN_BF16 else "") + (":flash" if (flash or t > 256 or precision) else "")
-    # algorithmic work: QK^T and PV, 2 * B * H * T * T * Dh MACs; bytes: qkv read once + out written once
-    tok = (_observer.begin("other", (name, 4 * (qkv.numel() + out.numel()), 2 * b * heads * t * t * head_dim))
-           if _observer is not None else None)
+    tok = None
+    if _observer is not None:    # the label tools/config_bench.py keys on: [:bf16][:flash], flash = any online-softmax kernel
+        single_pass = attention_kernel_name(b, heads, head_dim, t, precision, flash).startswith("attention_alibi<")
+        name = "attention_alibi" + (":bf16" if precision == ATTN_BF16 else "") + ("" if single_pass else ":flash")
+        # algorithmic work: QK^T and PV, 2 * B * H * T * T * Dh MACs; bytes: qkv read once + out written once
+        tok = _observer.begin("other", (name, 4 * (qkv.numel() + out.numel()), 2 * b * heads * t * t * head_dim))
     _lib.check(lib.agx_attention_alibi_ex(_ptr(qkv), _ptr(_f32c(slopes)), _ptr(out), b, heads, head_dim, t,
                                           float(scale_div), int(precision), int(bool(flash)), _stream()),
                "agx_attention_alibi_ex")
@@ -445,16 +448,29 @@ def layernorm_ct_backward(x: Tensor, weight: Optional[Tensor], dy: Tensor, eps: 
     return dx, dw, db
 
 
+def attention_kernel_name(batch: int, heads: int, head_dim: int, t: int, precision: int = ATTN_FP32, flash: bool = False) -> str:
+    """The kernel ``attention_alibi`` runs for this shape (host-only); ``AgxError`` with the launcher's message if it refuses."""
+    return _kernel_name("agx_attention_kernel_name", batch, heads, head_dim, t, precision, bool(flash))
+
+
+def attention_backward_kernel_name(heads: int, head_dim: int, t: int, split: bool = False) -> str:
+    """The single-launch kernel of ``agx_attention_alibi_backward`` (or ``AgxError``: the shape is beyond it), with ``split``
+    the three kernels of ``agx_attention_alibi_backward_ex`` (host-only)."""
+    return _kernel_name("agx_attention_backward_kernel_name", heads, head_dim, t, bool(split))
+
+
 def attention_alibi_backward(qkv: Tensor, slopes: Tensor, dout: Tensor, heads: int, head_dim: int,
                              scale_div: float, out: Optional[Tensor] = None) -> Tensor:
-    """dqkv of ``attention_alibi``.  T <= 256 and head_dim <= 64: the single-launch kernel; otherwise the flash-style
-    split (``agx_attention_alibi_backward_ex``), which needs ``out`` = the forward's output."""
+    """dqkv of ``attention_alibi``: the single-launch kernel where the library has one for the shape
+    (``attention_backward_kernel_name``), otherwise the flash-style split (``agx_attention_alibi_backward_ex``), which needs
+    ``out`` = the forward's output."""
     lib = _lib.load()
     _need_gpu(qkv, slopes, dout, out)
     qkv, dout = _f32c(qkv), _f32c(dout)
     b, _, t = qkv.shape
     dqkv = torch.empty_like(qkv)
-    if t <= 256 and head_dim <= 64:
+    buf = ctypes.create_string_buffer(96)
+    if lib.agx_attention_backward_kernel_name(heads, head_dim, t, 0, buf, len(buf)) == 0:
         _lib.check(lib.agx_attention_alibi_backward(_ptr(qkv), _ptr(_f32c(slopes)), _ptr(dout), _ptr(dqkv), b, heads,
                                                     head_dim, t, float(scale_div), _stream()),
                    "agx_attention_alibi_backward")
@@ -619,7 +635,7 @@ def conv_grouped_bwd_weight(desc: ConvDesc, x: Tensor, dz: Tensor, want_bias: bo
 
 def conv_grouped_bwd_weight_kernel_name(desc: ConvDesc) -> str:
     """What ``conv_grouped_bwd_weight`` runs: "<kernel> op=none slices=.. items=.." (include/agx.h)."""
-    return _kernel_name("agx_conv_grouped_bwd_weight_kernel_name", desc, 128)
+    return _kernel_name("agx_conv_grouped_bwd_weight_kernel_name", desc, size=128)
 
 
 def avgpool1d(x: Tensor, kernel: int, stride: int, padding: int) -> Tensor:
@@ -729,7 +745,7 @@ def conv2d_bwd_data_kernel_name(desc) -> str:
 
 def conv2d_bwd_weight_kernel_name(desc) -> str:
     """What ``conv2d_bwd_weight`` runs: "<kernel> cfg=.. op=.. slices=.. items=.." (include/agx.h)."""
-    return _kernel_name("agx_conv2d_bwd_weight_kernel_name", desc, 128)
+    return _kernel_name("agx_conv2d_bwd_weight_kernel_name", desc, size=128)
 
 
 _STFT_IMAGES = {}

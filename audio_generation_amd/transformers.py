@@ -56,39 +56,61 @@ class Alibi(nn.Module):
 
 
 class _PackedLinear:
-    """Cache of the packed image of one or more ``nn.Linear`` weights stacked
-    along the output dim (k=1 conv weights)."""
+    """One or more ``nn.Linear`` stacked along the output dim and run as one k=1 convolution over the channel dim of a
+    (B, C, T) tensor; caches the packed image of the stacked weights."""
 
-    def __init__(self):
-        self.key = None
-        self.packed = None
-        self.bias = None
-        self.w3d = None
+    def __init__(self, *linears):
+        self.linears = linears
+        self.c_out = sum(l.out_features for l in linears)
+        self.key = self.packed = self.bias = self.w3d = None
 
-    def get(self, linears):
+    def get(self):
         key = tuple((l.weight.data_ptr(), l.weight._version,
-                     None if l.bias is None else (l.bias.data_ptr(), l.bias._version)) for l in linears)
+                     None if l.bias is None else (l.bias.data_ptr(), l.bias._version)) for l in self.linears)
         if key != self.key:
-            w = torch.cat([l.weight.detach() for l in linears], dim=0)
+            w = torch.cat([l.weight.detach() for l in self.linears], dim=0)
             c_out, c_in = w.shape
             desc = ops.conv_desc(CONV_CAUSAL, 1, c_in, c_out, 1 << 20, 1)
             self.w3d = w.reshape(c_out, c_in, 1).contiguous()      # the native backward reads it
             self.packed = ops.conv_pack(desc, self.w3d)
-            if any(l.bias is not None for l in linears):
+            if any(l.bias is not None for l in self.linears):
                 self.bias = torch.cat([l.bias.detach() if l.bias is not None
-                                       else torch.zeros(l.out_features, device=w.device) for l in linears])
+                                       else torch.zeros(l.out_features, device=w.device) for l in self.linears])
             else:
                 self.bias = None
             self.key = key
         return self.packed, self.bias
 
+    def forward(self, x: Tensor, epilogue: int = 0, res: Optional[Tensor] = None) -> Tensor:
+        packed, bias = self.get()
+        b, c_in, t = x.shape
+        desc = ops.conv_desc(CONV_CAUSAL, b, c_in, self.c_out, t, 1, 1, 1, epilogue)
+        return ops.conv_forward(desc, x, packed, bias, res)
 
-def _linear_ct(x: Tensor, packed: Tensor, bias: Optional[Tensor], c_out: int, epilogue: int = 0,
-               res: Optional[Tensor] = None) -> Tensor:
-    """``Linear`` over the channel dim of a (B, C, T) tensor = k=1 conv."""
-    b, c_in, t = x.shape
-    desc = ops.conv_desc(CONV_CAUSAL, b, c_in, c_out, t, 1, 1, 1, epilogue)
-    return ops.conv_forward(desc, x, packed, bias, res)
+    def backward(self, x_in: Tensor, dy: Tensor, pre: Optional[Tensor] = None):
+        """Backward of ``forward`` with epilogue 0, on the image that forward packed: (dx, the gradients of the linears'
+        parameters in ``parameters()`` order); with ``pre`` the GELU gradient of the layer BELOW (at its pre-activation)
+        is fused into the bwd-data epilogue."""
+        b, c_in, t = x_in.shape
+        desc = ops.conv_desc(CONV_CAUSAL, b, c_in, self.c_out, t, 1)
+        dw, _, db = ops.conv_bwd_weight(desc, x_in, dy, self.w3d, None, want_bias=self.bias is not None)
+        pk = ops.conv_pack_bwd(desc, self.w3d)
+        dx = ops.conv_bwd_data(desc, dy, pk) if pre is None else ops.conv_bwd_data_gelu(desc, dy, pk, pre)
+        dw, grads, row = dw.reshape(self.c_out, c_in), [], 0
+        for l in self.linears:
+            rows = slice(row, row + l.out_features)
+            grads += [dw[rows]] if l.bias is None else [dw[rows], db[rows]]
+            row = rows.stop
+        return dx, grads
+
+
+def _ln(ln: nn.LayerNorm, x: Tensor) -> Tensor:
+    return ops.layernorm_ct(x, ln.weight.detach(), ln.bias.detach(), ln.eps)
+
+
+def _ln_bwd(ln: nn.LayerNorm, x: Tensor, dy: Tensor, add: Tensor):
+    """(dx + add, dweight, dbias): ``add`` is the gradient that reached the residual branch around the sub-block."""
+    return ops.layernorm_ct_backward(x, ln.weight.detach(), dy, ln.eps, add=add)
 
 
 class Attention(nn.Module):
@@ -116,25 +138,39 @@ class Attention(nn.Module):
         self.cross_attention = False
         self.context = context_x
         self.alibi_obj = Alibi(context_x, None, n_heads=n_heads)
-        self._qkv, self._o = _PackedLinear(), _PackedLinear()
+        self._qkv, self._o = _PackedLinear(self.W_q, self.W_k, self.W_v), _PackedLinear(self.W_o)
         # arithmetic of the QK^T / PV contractions: "fp32" (exact, the reference's) or "bf16" (bf16 MFMA, fp32 accumulate
-        # and softmax -- BASELINE config 3); inference only: with autograd on, the block's forward runs the fp32 kernel
-        # (Transformer.run_bct), which is what the backward kernels differentiate
+        # and softmax -- BASELINE config 3); inference only (run_bct: ``keep``)
         self.attention_dtype = "fp32"
 
-    def run_bct(self, x: Tensor, residual: Optional[Tensor] = None) -> Tensor:
-        """(B, dim, T) -> W_o(attn(LN(x))) [+ residual], channel-major."""
+    def _attn(self) -> dict:
+        return dict(slopes=self.alibi_obj.head_scalars, heads=self.n_heads, head_dim=self.dim_head, scale_div=self.dim_head ** 0.5)
+
+    def run_bct(self, x: Tensor, residual: Optional[Tensor] = None, keep: Optional[dict] = None) -> Tensor:
+        """(B, dim, T) -> W_o(attn(LN(x))) [+ residual], channel-major.  ``keep`` marks the training forward: the dict
+        receives what ``backward_bct`` reads, and the attention arithmetic is fp32 whatever ``attention_dtype`` says
+        (the backward kernels recompute P from fp32 scores, and cover head_dim <= 128)."""
         if x.shape[-1] > self.context:
             raise AgxError(f"sequence length {x.shape[-1]} exceeds the ALiBi context {self.context} "
                            "(the reference fails here too, transformers.py:88-93)")
-        xn = ops.layernorm_ct(x, self.norm.weight.detach(), self.norm.bias.detach(), self.norm.eps)
-        wqkv, bqkv = self._qkv.get([self.W_q, self.W_k, self.W_v])
-        qkv = _linear_ct(xn, wqkv, bqkv, 3 * self.inner_dim)
-        o = ops.attention_alibi(qkv, self.alibi_obj.head_scalars, self.n_heads, self.dim_head,
-                                self.dim_head ** 0.5,
-                                ops.ATTN_BF16 if self.attention_dtype == "bf16" else ops.ATTN_FP32)
-        wo, bo = self._o.get([self.W_o])
-        return _linear_ct(o, wo, bo, self.dim, EPI_RESIDUAL if residual is not None else 0, residual)
+        if keep is not None and self.dim_head > 128:
+            raise AgxError("Transformer: the attention backward kernels cover head_dim <= 128 "
+                           "(agx_attention_alibi_backward_ex); larger heads run forward only -- there is no ATen fallback")
+        xn = _ln(self.norm, x)
+        qkv = self._qkv.forward(xn)
+        bf16 = self.attention_dtype == "bf16" and keep is None
+        o = ops.attention_alibi(qkv, precision=ops.ATTN_BF16 if bf16 else ops.ATTN_FP32, **self._attn())
+        if keep is not None:
+            keep.update(h=x, xn1=xn, qkv=qkv, o=o)
+        return self._o.forward(o, EPI_RESIDUAL if residual is not None else 0, residual)
+
+    def backward_bct(self, kept: dict, g: Tensor):
+        """``g`` = the gradient of ``run_bct(h, residual=h, keep=kept)`` -> (dh, gradients in ``parameters()`` order)."""
+        do, g_o = self._o.backward(kept["o"], g)
+        dqkv = ops.attention_alibi_backward(kept["qkv"], dout=do, out=kept["o"], **self._attn())
+        dxn, g_qkv = self._qkv.backward(kept["xn1"], dqkv)
+        dh, dweight, dbias = _ln_bwd(self.norm, kept["h"], dxn, add=g)
+        return dh, [dweight, dbias] + g_qkv + g_o
 
     def forward(self, x: Tensor, y=None) -> Tensor:
         """Reference layout: (B, T, dim) -> (B, T, dim)."""
@@ -154,103 +190,53 @@ class FeedForward(nn.Module):
             raise NotImplementedError("dropout > 0 is training-only and not on the forward path")
         self.net = nn.Sequential(nn.LayerNorm(dim), nn.Linear(dim, hidden_dim), activation(), nn.Dropout(dropout),
                                  nn.Linear(hidden_dim, dim), nn.Dropout(dropout))
-        self._l1, self._l2 = _PackedLinear(), _PackedLinear()
+        self._l1, self._l2 = _PackedLinear(self.net[1]), _PackedLinear(self.net[4])
 
-    def run_bct(self, x: Tensor, residual: Optional[Tensor] = None) -> Tensor:
-        ln, l1, l2 = self.net[0], self.net[1], self.net[4]
-        xn = ops.layernorm_ct(x, ln.weight.detach(), ln.bias.detach(), ln.eps)
-        w1, b1 = self._l1.get([l1])
-        h = _linear_ct(xn, w1, b1, l1.out_features, EPI_GELU_PRE)
-        w2, b2 = self._l2.get([l2])
-        return _linear_ct(h, w2, b2, l2.out_features, EPI_RESIDUAL if residual is not None else 0, residual)
+    def run_bct(self, x: Tensor, residual: Optional[Tensor] = None, keep: Optional[dict] = None) -> Tensor:
+        xn = _ln(self.net[0], x)
+        hid = self._l1.forward(xn, EPI_GELU_PRE)
+        if keep is not None:
+            keep.update(x1=x, xn2=xn, hid=hid)
+        return self._l2.forward(hid, EPI_RESIDUAL if residual is not None else 0, residual)
+
+    def backward_bct(self, kept: dict, g: Tensor):
+        """As ``Attention.backward_bct``; the GELU gradient sits in the FFN-out bwd-data epilogue, at the pre-activation,
+        which is recomputed with one conv launch: the forward's FFN-in projection with epilogue 0."""
+        pre = self._l1.forward(kept["xn2"])
+        dpre, g2 = self._l2.backward(kept["hid"], g, pre=pre)
+        dxn, g1 = self._l1.backward(kept["xn2"], dpre)
+        dx1, dweight, dbias = _ln_bwd(self.net[0], kept["x1"], dxn, add=g)
+        return dx1, [dweight, dbias] + g1 + g2
 
     def forward(self, x: Tensor) -> Tensor:
         return self.run_bct(x.transpose(1, 2).contiguous()).transpose(1, 2).contiguous()
 
 
-def _lin_bwd(pl: "_PackedLinear", x_in: Tensor, dy: Tensor, c_out: int, pre: Optional[Tensor] = None,
-             need_dx: bool = True):
-    """Backward of ``_linear_ct`` (k=1 conv): (dx or None, dW (c_out, c_in), dbias or None); with ``pre`` the
-    GELU gradient of the layer BELOW (at its pre-activation) is fused into the bwd-data epilogue."""
-    b, c_in, t = x_in.shape
-    desc = ops.conv_desc(CONV_CAUSAL, b, c_in, c_out, t, 1)
-    dw, _, db = ops.conv_bwd_weight(desc, x_in, dy, pl.w3d, None, want_bias=pl.bias is not None)
-    dx = None
-    if need_dx:
-        pk = ops.conv_pack_bwd(desc, pl.w3d)
-        dx = ops.conv_bwd_data(desc, dy, pk) if pre is None else ops.conv_bwd_data_gelu(desc, dy, pk, pre)
-    return dx, dw.reshape(c_out, c_in), db
-
-
 class _TransformerNative(torch.autograd.Function):
     """Transformer forward + hand-written backward on the HIP kernels: k=1 conv backward for every Linear,
     ``agx_attention_alibi_backward``, ``agx_layernorm_ct_backward`` (residual adds fused as ``add``), the GELU
-    gradient in a bwd-data epilogue (the pre-activation is recomputed with one conv launch)."""
+    gradient in a bwd-data epilogue.  Every layer, the first included, computes its input gradient."""
 
     @staticmethod
     def forward(ctx, tf, x: Tensor, *params: Tensor):
-        saved = []
+        keep = []
         with torch.no_grad():
-            h = x.detach()
-            for attention, ff in tf.layers:
-                ln1 = attention.norm
-                xn1 = ops.layernorm_ct(h, ln1.weight.detach(), ln1.bias.detach(), ln1.eps)
-                wqkv, bqkv = attention._qkv.get([attention.W_q, attention.W_k, attention.W_v])
-                qkv = _linear_ct(xn1, wqkv, bqkv, 3 * attention.inner_dim)
-                o = ops.attention_alibi(qkv, attention.alibi_obj.head_scalars, attention.n_heads, attention.dim_head,
-                                        attention.dim_head ** 0.5)
-                wo, bo = attention._o.get([attention.W_o])
-                x1 = _linear_ct(o, wo, bo, attention.dim, EPI_RESIDUAL, h)
-                ln2, l1, l2 = ff.net[0], ff.net[1], ff.net[4]
-                xn2 = ops.layernorm_ct(x1, ln2.weight.detach(), ln2.bias.detach(), ln2.eps)
-                w1, b1 = ff._l1.get([l1])
-                hid = _linear_ct(xn2, w1, b1, l1.out_features, EPI_GELU_PRE)
-                w2, b2 = ff._l2.get([l2])
-                x2 = _linear_ct(hid, w2, b2, l2.out_features, EPI_RESIDUAL, x1)
-                saved += [h, xn1, qkv, o, x1, xn2, hid]
-                h = x2
-        ctx.tf, ctx.params = tf, params
-        ctx.save_for_backward(*saved)
-        return h
+            y = tf._hip_bct(x.detach(), keep)
+        ctx.tf, ctx.names = tf, [(li, name) for li, kept in enumerate(keep) for name in kept]
+        ctx.save_for_backward(*[t for kept in keep for t in kept.values()])
+        return y
 
     @staticmethod
     def backward(ctx, g: Tensor):
-        tf, saved = ctx.tf, ctx.saved_tensors
-        g = g.contiguous()
-        grads = {}
-        for li in range(len(tf.layers) - 1, -1, -1):
-            attention, ff = tf.layers[li]
-            h, xn1, qkv, o, x1, xn2, hid = saved[7 * li:7 * li + 7]
-            ln2, l1, l2 = ff.net[0], ff.net[1], ff.net[4]
-            # x2 = x1 + W2 gelu(W1 LN2(x1) + b1) + b2
-            w1, b1 = ff._l1.get([l1])
-            pre = _linear_ct(xn2, w1, b1, l1.out_features)                 # pre-activation, recomputed
-            dpre, dw2, db2 = _lin_bwd(ff._l2, hid, g, l2.out_features, pre=pre)
-            dxn2, dw1, db1 = _lin_bwd(ff._l1, xn2, dpre, l1.out_features)
-            dx1, dg2, dbt2 = ops.layernorm_ct_backward(x1, ln2.weight.detach(), dxn2, ln2.eps, add=g)
-            grads[l2.weight], grads[l1.weight], grads[ln2.weight], grads[ln2.bias] = dw2, dw1, dg2, dbt2
-            if l2.bias is not None:
-                grads[l2.bias] = db2
-            if l1.bias is not None:
-                grads[l1.bias] = db1
-            # x1 = h + W_o attn(W_qkv LN1(h))
-            ln1, inner = attention.norm, attention.inner_dim
-            do, dwo, dbo = _lin_bwd(attention._o, o, dx1, attention.dim)
-            dqkv = ops.attention_alibi_backward(qkv, attention.alibi_obj.head_scalars, do, attention.n_heads,
-                                                attention.dim_head, attention.dim_head ** 0.5, out=o)
-            need_dx = li > 0 or ctx.needs_input_grad[1]
-            dxn1, dwqkv, dbqkv = _lin_bwd(attention._qkv, xn1, dqkv, 3 * inner)
-            dx, dg1, dbt1 = ops.layernorm_ct_backward(h, ln1.weight.detach(), dxn1, ln1.eps, add=dx1)
-            grads[attention.W_o.weight], grads[ln1.weight], grads[ln1.bias] = dwo, dg1, dbt1
-            for k, lin in enumerate((attention.W_q, attention.W_k, attention.W_v)):
-                grads[lin.weight] = dwqkv[k * inner:(k + 1) * inner]
-                if lin.bias is not None:
-                    grads[lin.bias] = dbqkv[k * inner:(k + 1) * inner]
-            if attention.W_o.bias is not None:
-                grads[attention.W_o.bias] = dbo
-            g = dx
-            del need_dx
-        return (None, g if ctx.needs_input_grad[1] else None, *[grads.get(p_) for p_ in ctx.params])
+        keep = [{} for _ in ctx.tf.layers]
+        for (li, name), t in zip(ctx.names, ctx.saved_tensors):
+            keep[li][name] = t
+        g, grads = g.contiguous(), []
+        for (attention, ff), kept in zip(reversed(ctx.tf.layers), reversed(keep)):
+            g, g_ff = ff.backward_bct(kept, g)              # x2 = x1 + W2 gelu(W1 LN2(x1) + b1) + b2
+            g, g_attention = attention.backward_bct(kept, g)   # x1 = h + W_o attn(W_qkv LN1(h))
+            grads = g_attention + g_ff + grads              # the order of Transformer.parameters()
+        return (None, g if ctx.needs_input_grad[1] else None, *grads)
 
 
 class Transformer(nn.Module):
@@ -268,25 +254,22 @@ class Transformer(nn.Module):
                            FeedForward(dim, dim, dropout=dropout)])
             for _ in range(depth)])
 
-    def _hip_bct(self, x: Tensor) -> Tensor:
+    def _hip_bct(self, x: Tensor, keep: Optional[list] = None) -> Tensor:
+        """The one forward walk, LN1 -> QKV -> attention -> W_o (+res) -> LN2 -> FFN-in (GELU) -> FFN-out (+res) per layer:
+        7 launches, both residual adds fused into the W_o / FFN-out conv epilogues.  ``keep``: the training forward
+        (``Attention.run_bct``) -- the list receives one dict of named intermediates per layer."""
         for attention, ff in self.layers:
-            x = attention.run_bct(x, residual=x)
-            x = ff.run_bct(x, residual=x)
+            kept = None if keep is None else {}
+            x = attention.run_bct(x, x, kept)
+            x = ff.run_bct(x, x, kept)
+            if keep is not None:
+                keep.append(kept)
         return x
 
     def run_bct(self, x: Tensor) -> Tensor:
-        """Channel-major (B, dim, T) in and out: 7 launches per layer, both residual adds fused into
-        the W_o / FFN-out conv epilogues.  With autograd on, the backward runs on the HIP kernels too
-        (_TransformerNative: head_dim <= 128; the training forward always uses the fp32 attention arithmetic, whatever
-        ``attention_dtype`` says -- the backward kernels recompute P from fp32 scores)."""
-        for attention, _ in self.layers:
-            if x.shape[-1] > attention.context:
-                raise AgxError(f"sequence length {x.shape[-1]} exceeds the ALiBi context {attention.context} "
-                               "(the reference fails here too, transformers.py:88-93)")
+        """Channel-major (B, dim, T) in and out.  With autograd on, the backward runs on the HIP kernels too
+        (_TransformerNative)."""
         if needs_grad(x, self):
-            if any(a.dim_head > 128 for a, _ in self.layers):
-                raise AgxError("Transformer: the attention backward kernels cover head_dim <= 128 "
-                               "(agx_attention_alibi_backward_ex); larger heads run forward only -- there is no ATen fallback")
             return _TransformerNative.apply(self, x, *list(self.parameters()))
         return self._hip_bct(x)
 

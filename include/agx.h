@@ -26,7 +26,7 @@
 extern "C" {
 #endif
 
-#define AGX_VERSION 121 /* 121: agx_conv_bwd_weight_kernel_name, agx_conv2d_bwd_weight_kernel_name, agx_conv_grouped_bwd_weight_kernel_name (kernel, operand copy, contraction slices and items of the weight-gradient ops); 120: activation planes (agx_planes_bytes / agx_planes_split / agx_conv_forward_planes / agx_conv_planes_supported): pre-split bf16x3 input of the decoder's resampling convs; conv_p one-phase geometries (k = 1, "same" k = 11 / 3) with GELU / residual epilogues; 119: agx_rvq_verify_counts + knob rvq_verify (debug: the full defining search beside the fast path); agx_rvq_debug_stamps and the b3_dbg 7/8/9 bound knobs exist in the probe build only; 118: agx_feature_means(_backward) (the feature-matching pair in one pass); 117: agx_rvq_debug_stamps (diagnostic); 116: agx_multires_backward, agx_layernorm_ct one-pass kernel (same signature); agx_rvq_forward (legacy form) needs the workspace of agx_rvq_workspace_bytes since 114; 115: agx_rvq_ema_stats, agx_conv2d_bwd_data_kernel_name; 114: agx_attention_alibi_backward_ex (any T), agx_rvq_forward_ex; 113: tile images (resblock_p / conv_p), agx_attention_alibi_ex, agx_sizeof_*; 0.1.1: agx_conv_desc gained groups / padding (zero = old behaviour); 111: resample, conv2d column split */
+#define AGX_VERSION 122 /* 122: agx_attention_kernel_name, agx_attention_backward_kernel_name (which attention kernel the forward / backward entry points run); 121: agx_conv_bwd_weight_kernel_name, agx_conv2d_bwd_weight_kernel_name, agx_conv_grouped_bwd_weight_kernel_name (kernel, operand copy, contraction slices and items of the weight-gradient ops); 120: activation planes (agx_planes_bytes / agx_planes_split / agx_conv_forward_planes / agx_conv_planes_supported): pre-split bf16x3 input of the decoder's resampling convs; conv_p one-phase geometries (k = 1, "same" k = 11 / 3) with GELU / residual epilogues; 119: agx_rvq_verify_counts + knob rvq_verify (debug: the full defining search beside the fast path); agx_rvq_debug_stamps and the b3_dbg 7/8/9 bound knobs exist in the probe build only; 118: agx_feature_means(_backward) (the feature-matching pair in one pass); 117: agx_rvq_debug_stamps (diagnostic); 116: agx_multires_backward, agx_layernorm_ct one-pass kernel (same signature); agx_rvq_forward (legacy form) needs the workspace of agx_rvq_workspace_bytes since 114; 115: agx_rvq_ema_stats, agx_conv2d_bwd_data_kernel_name; 114: agx_attention_alibi_backward_ex (any T), agx_rvq_forward_ex; 113: tile images (resblock_p / conv_p), agx_attention_alibi_ex, agx_sizeof_*; 0.1.1: agx_conv_desc gained groups / padding (zero = old behaviour); 111: resample, conv2d column split */
 
 #define AGX_OK 0
 #define AGX_ERR_BAD_SHAPE (-1)
@@ -330,6 +330,12 @@ int agx_attention_alibi(const float *qkv, const float *slopes, float *out, int32
 #define AGX_ATTN_BF16 1
 int agx_attention_alibi_ex(const float *qkv, const float *slopes, float *out, int32_t batch, int32_t heads,
                            int32_t head_dim, int32_t t, float scale_div, int32_t precision, int32_t flash, void *stream);
+/* Host-only: the kernel instantiation agx_attention_alibi_ex runs for these arguments, from the selection the launcher uses --
+ * "attention_alibi<NJ,DVT>" (single pass: fp32, not flash, t <= 256), "attention_bf16_lds<DVT>" (bf16 with K and V of a
+ * (head, item) staged in LDS) or "attention_flash<DVT,PREC>" -- or the launcher's refusal (code and message) for a shape it
+ * refuses.  The name is truncated to buf_len - 1 characters. */
+int agx_attention_kernel_name(int32_t batch, int32_t heads, int32_t head_dim, int32_t t, int32_t precision, int32_t flash,
+                              char *buf, size_t buf_len);
 
 /* ------------------------------------------------------------------------- *
  * Wavelet / multiresolution layers (networks/wavelets.py)                     *
@@ -387,6 +393,10 @@ size_t agx_attention_backward_workspace_bytes(int32_t batch, int32_t heads, int3
 int agx_attention_alibi_backward_ex(const float *qkv, const float *slopes, const float *out, const float *dout, float *dqkv,
                                     float *workspace, size_t workspace_bytes, int32_t batch, int32_t heads, int32_t head_dim,
                                     int32_t t, float scale_div, void *stream);
+/* Host-only: split = 0: the kernel agx_attention_alibi_backward runs, "attention_alibi_bwd<16>" or "<8>" (queries per LDS block),
+ * or its refusal of the shape (t > 256, head_dim > 64); split != 0: the three kernels of agx_attention_alibi_backward_ex, or its
+ * refusal (head_dim > 128).  A caller that has the forward output takes the single launch iff split = 0 answers AGX_OK. */
+int agx_attention_backward_kernel_name(int32_t heads, int32_t head_dim, int32_t t, int32_t split, char *buf, size_t buf_len);
 /* agx_conv_bwd_data followed by the exact-GELU gradient: dx = (W^T dy [+ add]) * gelu'(pre)  (two launches). */
 int agx_conv_bwd_data_gelu(const agx_conv_desc *d, const float *dy, const float *packed_bwd, const float *add,
                            const float *pre, float *dx, void *stream);

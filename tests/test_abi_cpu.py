@@ -31,13 +31,13 @@ def _declared_symbols():
     return names
 
 
-def test_every_declared_symbol_is_exported_and_bound_at_abi_121(lib):
+def test_every_declared_symbol_is_exported_and_bound_at_abi_122(lib):
     declared = _declared_symbols()
     assert declared, "no declarations found in include/*.h"
     assert declared == set(_lib.SIGNATURES), (declared ^ set(_lib.SIGNATURES))
     for name in declared:
         assert hasattr(lib, name), f"{name} declared in include/agx.h but not exported by libagx.so"
-    assert lib.agx_version() == 121
+    assert lib.agx_version() == 122
 
 
 def test_out_len_matches_reference_padding_rule(lib):
