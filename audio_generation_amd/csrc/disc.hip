@@ -1,5 +1,5 @@
-// Small kernels of the discriminators (networks/discriminator.py): spectral-norm sigma, AvgPool1d,
-// the STFT front end (as a polyphase conv on the MFMA kernels) and the loss reductions.
+// Small kernels of the discriminators (networks/discriminator.py): spectral-norm sigma, AvgPool1d, sigmoid
+// and the loss reductions.  (The STFT front end is one row of the framed DFT's geometry: spectral.hip.)
 // All are bandwidth- or latency-trivial next to the conv stacks; written for determinism
 // (fixed reduction orders, no atomics).
 #include "conv_kernels.hpp"
@@ -76,97 +76,6 @@ __global__ __launch_bounds__(256) void avgpool1d_kernel(const float *__restrict_
     y[size_t(blockIdx.y) * l_out + o] = acc / float(kernel);  // count_include_pad=True
 }
 
-// ------------------------------------------------------------------ STFT front end
-// Polyphase view of the framed DFT: with hop H = N / 4 and n = j H + p,
-//   Y[c, f, t] = sum_{p < H} sum_{j < 4} D_c[f, j H + p] xp[(t + j) H + p]
-// = an unpadded K = 4 conv over H channels xc[p][tau] = xp[tau H + p] (xp = reflect-padded input).
-// (tau_off: the first hop-column kept -- the framed DFT of a window shorter than n_fft skips the taps where the window is zero)
-__global__ __launch_bounds__(256) void stft_prep_kernel(const float *__restrict__ x, float *__restrict__ xc,
-                                                        int L, int N, int H, int Ttau, int chs, int tau_off) {
-    // one block per (tau-tile of 64, batch); thread -> (p fastest over reads, tau fastest over writes)
-    __shared__ float tile[64][65];
-    const int b = blockIdx.z, tau0 = blockIdx.x * 64, p0 = blockIdx.y * 64;
-    const int Lp = L + N;
-    for (int e = threadIdx.x; e < 64 * 64; e += 256) {
-        const int tt = e >> 6, pp = e & 63;  // consecutive threads: consecutive p = consecutive samples
-        const int tau = tau0 + tt, p = p0 + pp;
-        float v = 0.f;
-        if (tau < Ttau && p < H) {
-            const int i = (tau + tau_off) * H + p;
-            if (i < Lp) {
-                int src = i - N / 2;
-                if (src < 0) src = -src;
-                if (src >= L) src = 2 * (L - 1) - src;
-                v = x[size_t(b) * L + src];
-            }
-        }
-        tile[tt][pp] = v;
-    }
-    __syncthreads();
-    for (int e = threadIdx.x; e < 64 * 64; e += 256) {
-        const int pp = e >> 6, tt = e & 63;
-        const int tau = tau0 + tt, p = p0 + pp;
-        if (tau < Ttau && p < H) xc[(size_t(b) * chs + p) * Ttau + tau] = tile[tt][pp];
-    }
-}
-
-// conv output (B, 2N, T) -> (B, 2, T, N)
-__global__ __launch_bounds__(256) void stft_transpose_kernel(const float *__restrict__ src, float *__restrict__ dst,
-                                                             int N, int T) {
-    __shared__ float tile[64][65];
-    const int bc = blockIdx.z;  // b * 2 + c
-    const int f0 = blockIdx.y * 64, t0 = blockIdx.x * 64;
-    for (int e = threadIdx.x; e < 64 * 64; e += 256) {
-        const int ff = e >> 6, tt = e & 63;
-        const int f = f0 + ff, t = t0 + tt;
-        tile[ff][tt] = (f < N && t < T) ? src[(size_t(bc) * N + f) * T + t] : 0.f;
-    }
-    __syncthreads();
-    for (int e = threadIdx.x; e < 64 * 64; e += 256) {
-        const int tt = e >> 6, ff = e & 63;
-        const int f = f0 + ff, t = t0 + tt;
-        if (f < N && t < T) dst[(size_t(bc) * T + t) * N + f] = tile[ff][tt];
-    }
-}
-
-// (B, 2, T, N) -> (B, 2N, T): the transpose back, for the adjoint
-__global__ __launch_bounds__(256) void stft_untranspose_kernel(const float *__restrict__ src, float *__restrict__ dst,
-                                                               int N, int T) {
-    __shared__ float tile[64][65];
-    const int bc = blockIdx.z;
-    const int f0 = blockIdx.y * 64, t0 = blockIdx.x * 64;
-    for (int e = threadIdx.x; e < 64 * 64; e += 256) {
-        const int tt = e >> 6, ff = e & 63;
-        const int f = f0 + ff, t = t0 + tt;
-        tile[tt][ff] = (f < N && t < T) ? src[(size_t(bc) * T + t) * N + f] : 0.f;
-    }
-    __syncthreads();
-    for (int e = threadIdx.x; e < 64 * 64; e += 256) {
-        const int ff = e >> 6, tt = e & 63;
-        const int f = f0 + ff, t = t0 + tt;
-        if (f < N && t < T) dst[(size_t(bc) * N + f) * T + t] = tile[tt][ff];
-    }
-}
-
-// adjoint of stft_prep_kernel: dx[n] = sum over the padded positions i that read x[n]
-// (i = n + N/2 always; the reflected copies i = N/2 - n for 1 <= n <= N/2 and
-//  i = N/2 + 2(L-1) - n for L-1-N/2 <= n <= L-2), with dxc[p][tau] = dxp[tau H + p]
-__global__ __launch_bounds__(256) void stft_unprep_kernel(const float *__restrict__ dxc, float *__restrict__ dx, int L,
-                                                          int N, int H, int Ttau, int chs, int tau_off) {
-    const int n = blockIdx.x * 256 + threadIdx.x;
-    if (n >= L) return;
-    const int b = blockIdx.y, Lp = L + N, half = N / 2;
-    auto at = [&](int i) -> float {
-        if (i < 0 || i >= Lp) return 0.f;
-        const int th = i / H, p = i - th * H, tau = th - tau_off;
-        return (tau >= 0 && tau < Ttau) ? dxc[(size_t(b) * chs + p) * Ttau + tau] : 0.f;
-    };
-    float acc = at(n + half);
-    if (n >= 1 && n <= half) acc += at(half - n);
-    if (n <= L - 2 && n >= L - 1 - half) acc += at(half + 2 * (L - 1) - n);
-    dx[size_t(b) * L + n] = acc;
-}
-
 __global__ __launch_bounds__(256) void avgpool1d_bwd_kernel(const float *__restrict__ dy, const float *__restrict__ add,
                                                             float *__restrict__ dx, int l_in, int l_out, int kernel,
                                                             int stride, int padding) {
@@ -213,41 +122,6 @@ __global__ __launch_bounds__(256) void sn_grad_kernel(float *__restrict__ g, con
     const float sg = sigma[0], coef = tot_s / (sg * sg) * u[blockIdx.x], inv = 1.f / sg;
     const size_t base = size_t(blockIdx.x) * cols;
     for (int c = threadIdx.x; c < cols; c += 256) g[base + c] = g[base + c] * inv - coef * v[c];
-}
-
-// packed image of the DFT "weights": row m = c * N + f, channel p, tap j  ->  D_c[f, j H + p] * scale
-__global__ __launch_bounds__(256) void stft_pack_kernel(float *__restrict__ packed, int N, int H, float scale) {
-    const int M = 2 * N;
-    const int64_t total = packed_weight_floats(H, 4, M);
-    const int64_t e = int64_t(blockIdx.x) * 256 + threadIdx.x;
-    if (e >= total) return;
-    const int c16 = int(e % kWG);
-    const int m = int((e / kWG) % M);
-    const int gj = int(e / (int64_t(kWG) * M));
-    const int j = gj % 4, p = (gj / 4) * kWG + c16;
-    const int c = m / N, f = m - c * N, n = j * H + p;
-    const long long k = (long long)f * n % N;  // exact argument reduction
-    double sn, cs;
-    sincospi(2.0 * double(k) / double(N), &sn, &cs);
-    packed[e] = float((c == 0 ? cs : -sn) * double(scale));
-}
-
-// image of the adjoint conv (backward-data plan of the DFT conv: channels = the 2N spectrum rows, rows = the
-// H phase channels, tap jb <-> forward tap 3 - jb)
-__global__ __launch_bounds__(256) void stft_pack_bwd_kernel(float *__restrict__ packed, int N, int H, float scale) {
-    const int Mb = H;
-    const int64_t total = packed_weight_floats(2 * N, 4, Mb);
-    const int64_t e = int64_t(blockIdx.x) * 256 + threadIdx.x;
-    if (e >= total) return;
-    const int c16 = int(e % kWG);
-    const int p = int((e / kWG) % Mb);
-    const int gj = int(e / (int64_t(kWG) * Mb));
-    const int jb = gj % 4, m = (gj / 4) * kWG + c16;
-    const int c = m / N, f = m - c * N, n = (3 - jb) * H + p;
-    const long long k = (long long)f * n % N;
-    double sn, cs;
-    sincospi(2.0 * double(k) / double(N), &sn, &cs);
-    packed[e] = float((c == 0 ? cs : -sn) * double(scale));
 }
 
 // ------------------------------------------------------------------ loss reductions
@@ -388,18 +262,6 @@ __global__ __launch_bounds__(256) void sigmoid_kernel(const float *__restrict__ 
     if (i < n) y[i] = 1.f / (1.f + expf(-x[i]));
 }
 
-void launch_stft_prep(const float *x, float *xc, int batch, int L, int N, int H, int Ttau, int ch_stride, int tau_off,
-                      hipStream_t st) {
-    hipLaunchKernelGGL(stft_prep_kernel, dim3(ceil_div(Ttau, 64), ceil_div(H, 64), batch), dim3(256), 0, st, x, xc, L, N,
-                       H, Ttau, ch_stride, tau_off);
-}
-
-void launch_stft_unprep(const float *dxc, float *dx, int batch, int L, int N, int H, int Ttau, int ch_stride, int tau_off,
-                        hipStream_t st) {
-    hipLaunchKernelGGL(stft_unprep_kernel, dim3(ceil_div(L, 256), batch), dim3(256), 0, st, dxc, dx, L, N, H, Ttau,
-                       ch_stride, tau_off);
-}
-
 }  // namespace agx
 
 extern "C" {
@@ -439,63 +301,6 @@ int agx_avgpool1d(const float *x, float *y, int64_t rows, int32_t l_in, int32_t 
     hipLaunchKernelGGL(avgpool1d_kernel, dim3(ceil_div(int(l_out), 256), unsigned(rows)), dim3(256), 0,
                        static_cast<hipStream_t>(stream), x, y, l_in, int(l_out), kernel, stride, padding);
     return check_launch("agx_avgpool1d");
-}
-
-static int stft_check(int32_t length, int32_t n_fft) {
-    if (n_fft < 64 || (n_fft & (n_fft - 1))) return agx::fail(AGX_ERR_UNSUPPORTED, "stft: n_fft must be a power of two >= 64");
-    if (length <= n_fft / 2) return agx::fail(AGX_ERR_BAD_SHAPE, "stft: reflect padding needs length > n_fft / 2");
-    return AGX_OK;
-}
-
-int64_t agx_stft_frames(int32_t length, int32_t n_fft) {
-    int rc = stft_check(length, n_fft);
-    return rc != AGX_OK ? rc : 1 + length / (n_fft / 4);
-}
-
-int64_t agx_stft_packed_floats(int32_t n_fft) {
-    if (n_fft < 64 || (n_fft & (n_fft - 1))) return agx::fail(AGX_ERR_UNSUPPORTED, "stft: n_fft must be a power of two >= 64");
-    return agx::packed_weight_floats(n_fft / 4, 4, 2 * n_fft);
-}
-
-int agx_stft_pack(int32_t n_fft, int32_t normalized, float *packed, void *stream) {
-    using namespace agx;
-    const int64_t n = agx_stft_packed_floats(n_fft);
-    if (n < 0) return int(n);
-    if (!packed) return fail(AGX_ERR_NULL_POINTER, "stft_pack: NULL pointer");
-    const float scale = normalized ? float(1.0 / sqrt(double(n_fft))) : 1.f;
-    hipLaunchKernelGGL(stft_pack_kernel, dim3((unsigned)ceil_div64(n, 256)), dim3(256), 0,
-                       static_cast<hipStream_t>(stream), packed, n_fft, n_fft / 4, scale);
-    return check_launch("agx_stft_pack");
-}
-
-int64_t agx_stft_workspace_bytes(int32_t batch, int32_t length, int32_t n_fft) {
-    const int64_t T = agx_stft_frames(length, n_fft);
-    if (T < 0) return T;
-    if (batch <= 0) return agx::fail(AGX_ERR_BAD_SHAPE, "stft: batch <= 0");
-    return (int64_t(batch) * (n_fft / 4) * (T + 3) + int64_t(batch) * 2 * n_fft * T) * int64_t(sizeof(float));
-}
-
-int agx_stft_forward(const float *x, const float *packed, float *y, void *workspace, int32_t batch, int32_t length,
-                     int32_t n_fft, void *stream) {
-    using namespace agx;
-    const int64_t T64 = agx_stft_frames(length, n_fft);
-    if (T64 < 0) return int(T64);
-    if (batch <= 0 || batch > 32767) return fail(AGX_ERR_BAD_SHAPE, "stft: batch out of range");
-    if (!x || !packed || !y || !workspace) return fail(AGX_ERR_NULL_POINTER, "stft_forward: NULL pointer");
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    const int N = n_fft, H = N / 4, T = int(T64), Ttau = T + 3;
-    float *xc = static_cast<float *>(workspace);
-    float *cv = xc + size_t(batch) * H * Ttau;
-    launch_stft_prep(x, xc, batch, length, N, H, Ttau, H, 0, st);
-    agx_conv_desc d{AGX_CONV_PADDED, batch, H, 2 * N, Ttau, 4, 1, 1, 0, 0.f, AGX_IMPL_MFMA, 1, 0};
-    ConvPlan p;
-    int rc = lower_conv(&d, &p);
-    if (rc != AGX_OK) return rc;
-    rc = launch_conv_mfma(p, xc, packed, nullptr, nullptr, cv, st);
-    if (rc != AGX_OK) return rc;
-    hipLaunchKernelGGL(stft_transpose_kernel, dim3(ceil_div(T, 64), ceil_div(N, 64), batch * 2), dim3(256), 0, st, cv,
-                       y, N, T);
-    return check_launch("agx_stft_forward");
 }
 
 static inline int aligned16(const void *a, const void *b, const void *c, const void *d) {
@@ -556,47 +361,6 @@ int agx_sigmoid(const float *x, float *y, int64_t n, void *stream) {
     hipLaunchKernelGGL(sigmoid_kernel, dim3((unsigned)ceil_div64(n, 256)), dim3(256), 0,
                        static_cast<hipStream_t>(stream), x, y, n);
     return check_launch("agx_sigmoid");
-}
-
-// The adjoint runs the DFT conv's backward-data plan (core.hip:lower_conv_bwd_data: stride 1 -> the flipped
-// kernel with the channel roles swapped) on the same MFMA kernel.
-static agx_conv_desc stft_conv_desc(int batch, int n_fft, int Ttau) {
-    return agx_conv_desc{AGX_CONV_PADDED, batch, n_fft / 4, 2 * n_fft, Ttau, 4, 1, 1, 0, 0.f, AGX_IMPL_MFMA, 1, 0};
-}
-
-int agx_stft_pack_bwd(int32_t n_fft, int32_t normalized, float *packed_bwd, void *stream) {
-    using namespace agx;
-    const int64_t n = agx_stft_packed_floats(n_fft);
-    if (n < 0) return int(n);
-    if (!packed_bwd) return fail(AGX_ERR_NULL_POINTER, "stft_pack_bwd: NULL pointer");
-    const float scale = normalized ? float(1.0 / sqrt(double(n_fft))) : 1.f;
-    hipLaunchKernelGGL(stft_pack_bwd_kernel, dim3((unsigned)ceil_div64(n, 256)), dim3(256), 0,
-                       static_cast<hipStream_t>(stream), packed_bwd, n_fft, n_fft / 4, scale);
-    return check_launch("agx_stft_pack_bwd");
-}
-
-int agx_stft_backward(const float *dy, const float *packed_bwd, float *dx, void *workspace, int32_t batch,
-                      int32_t length, int32_t n_fft, void *stream) {
-    using namespace agx;
-    const int64_t T64 = agx_stft_frames(length, n_fft);
-    if (T64 < 0) return int(T64);
-    if (batch <= 0 || batch > 32767) return fail(AGX_ERR_BAD_SHAPE, "stft: batch out of range");
-    if (!dy || !packed_bwd || !dx || !workspace) return fail(AGX_ERR_NULL_POINTER, "stft_backward: NULL pointer");
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    const int N = n_fft, H = N / 4, T = int(T64), Ttau = T + 3;
-    float *dxc = static_cast<float *>(workspace);
-    float *cv = dxc + size_t(batch) * H * Ttau;
-    hipLaunchKernelGGL(stft_untranspose_kernel, dim3(ceil_div(T, 64), ceil_div(N, 64), batch * 2), dim3(256), 0, st, dy,
-                       cv, N, T);
-    const agx_conv_desc d = stft_conv_desc(batch, n_fft, Ttau);
-    ConvPlan p;
-    int rc = lower_conv_bwd_data(&d, &p);
-    if (rc != AGX_OK) return rc;
-    rc = conv_mfma_supported(p) ? launch_conv_mfma(p, cv, packed_bwd, nullptr, nullptr, dxc, st)
-                                : launch_conv_direct(p, cv, packed_bwd, nullptr, nullptr, dxc, st);  // n_fft = 64: 16 rows
-    if (rc != AGX_OK) return rc;
-    launch_stft_unprep(dxc, dx, batch, length, N, H, Ttau, H, 0, st);
-    return check_launch("agx_stft_backward");
 }
 
 int agx_avgpool1d_backward(const float *dy, const float *add, float *dx, int64_t rows, int32_t l_in, int32_t kernel,

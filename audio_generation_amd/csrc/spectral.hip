@@ -1,27 +1,29 @@
 // Training-loop signal ops (torchaudio in the reference, training.py:151-156, 316-318, 333-334):
-// pre-emphasis, low-pass biquad, and the mel spectrogram of the multi-resolution spectral loss.
+// pre-emphasis, low-pass biquad, and the mel spectrogram of the multi-resolution spectral loss -- and the framed DFT
+// under that spectrogram AND under the discriminators' STFT front end (networks/discriminator.py).
 //
 // Framed DFT ("fdft"): a windowed, optionally one-sided STFT with hop H and n_fft = K H as a K-tap,
-// stride-1 conv over H phase channels (disc.hip: the same formulation as the discriminator STFT) on the
-// MFMA conv kernel; the weight image holds window[n] * twiddle(f, n) * norm.  Output stays channel-major
-// (B, 2F, T): real rows then imaginary rows -- what the mel / power kernel below consumes.
+// stride-1 conv over H phase channels on the MFMA conv kernel; the weight image holds
+// window[n] * twiddle(f, n) * norm.  Output stays channel-major (B, 2F, T): real rows then imaginary rows -- what the
+// mel / power kernel below consumes.
 // A window shorter than n_fft (the reference's short windows sit in n_fft = 512: training.py:51-78) is zero outside
 // [left, left + W): only the taps j0 .. j0 + Ke - 1 that meet it are kept (Ke = 4 instead of up to 64 for hop = W / 4);
 // the dropped products are exact zeros, so the sums do not change.
+// All of its host side is here, once: fdft_geom (the geometry), fdft_conv_desc (the conv), fdft_launch_pack (the weight
+// images), fdft_run_forward / fdft_run_backward (the drivers).  agx_fdft_* serve any row of fdft_geom; agx_stft_* serve
+// the one row stft_geom names (rectangular window = n_fft, hop n_fft / 4, two-sided) and add only the transpose
+// (B, 2N, T) <-> (B, 2, T, N) that the Conv2d stack behind them wants.
 #include "conv_kernels.hpp"
 
 namespace agx {
-
-// disc.hip: reflect-pad + polyphase transpose of `batch` rows (and its adjoint); ch_stride = channels allocated per item
-void launch_stft_prep(const float *x, float *xc, int batch, int L, int N, int H, int Ttau, int ch_stride, int tau_off,
-                      hipStream_t st);
-void launch_stft_unprep(const float *dxc, float *dx, int batch, int L, int N, int H, int Ttau, int ch_stride, int tau_off,
-                        hipStream_t st);
 
 struct FdftGeom {
     int N, W, H, K, Hc, F, Fp, M;   // n_fft, win_length, hop, taps, channels (H rounded up to 16), bins, bins rounded up to 8, rows = 2 Fp
     int j0, Ke;                     // first tap that meets the window, taps kept
 };
+
+static int fdft_channels(int hop) { return ceil_div(hop, kWG) * kWG; }
+static int fdft_rows(int n_fft, int onesided) { return ceil_div(onesided ? n_fft / 2 + 1 : n_fft, 8) * 8; }
 
 static int fdft_geom(int n_fft, int win_length, int hop, int onesided, FdftGeom *g) {
     if (n_fft < 16 || hop <= 0 || n_fft % hop || win_length <= 0 || win_length > n_fft)
@@ -30,9 +32,9 @@ static int fdft_geom(int n_fft, int win_length, int hop, int onesided, FdftGeom 
     const int left = (n_fft - win_length) / 2;
     g->j0 = left / hop;
     g->Ke = ceil_div(left + win_length, hop) - g->j0;
-    g->Hc = ceil_div(hop, kWG) * kWG;
+    g->Hc = fdft_channels(hop);
     g->F = onesided ? n_fft / 2 + 1 : n_fft;
-    g->Fp = ceil_div(g->F, 8) * 8;   // 2 Fp rows: a multiple of 16, so the backward plan's channels fill MFMA chunks
+    g->Fp = fdft_rows(n_fft, onesided);   // 2 Fp rows: a multiple of 16, so the backward plan's channels fill MFMA chunks
     g->M = 2 * g->Fp;
     return AGX_OK;
 }
@@ -69,6 +71,109 @@ __global__ __launch_bounds__(256) void fdft_pack_kernel(float *__restrict__ pack
         out = float((c == 0 ? cs : -sn) * fdft_window(n, g.N, g.W, window_kind) * double(scale));
     }
     packed[e] = out;
+}
+
+// Polyphase view of the framed DFT (written out for the discriminator STFT): with hop H = N / 4 and n = j H + p,
+//   Y[c, f, t] = sum_{p < H} sum_{j < 4} D_c[f, j H + p] xp[(t + j) H + p]
+// = an unpadded K = 4 conv over H channels xc[p][tau] = xp[tau H + p] (xp = reflect-padded input).
+// (tau_off: the first hop-column kept -- the framed DFT of a window shorter than n_fft skips the taps where the window is zero)
+__global__ __launch_bounds__(256) void stft_prep_kernel(const float *__restrict__ x, float *__restrict__ xc,
+                                                        int L, int N, int H, int Ttau, int chs, int tau_off) {
+    // one block per (tau-tile of 64, batch); thread -> (p fastest over reads, tau fastest over writes)
+    __shared__ float tile[64][65];
+    const int b = blockIdx.z, tau0 = blockIdx.x * 64, p0 = blockIdx.y * 64;
+    const int Lp = L + N;
+    for (int e = threadIdx.x; e < 64 * 64; e += 256) {
+        const int tt = e >> 6, pp = e & 63;  // consecutive threads: consecutive p = consecutive samples
+        const int tau = tau0 + tt, p = p0 + pp;
+        float v = 0.f;
+        if (tau < Ttau && p < H) {
+            const int i = (tau + tau_off) * H + p;
+            if (i < Lp) {
+                int src = i - N / 2;
+                if (src < 0) src = -src;
+                if (src >= L) src = 2 * (L - 1) - src;
+                v = x[size_t(b) * L + src];
+            }
+        }
+        tile[tt][pp] = v;
+    }
+    __syncthreads();
+    for (int e = threadIdx.x; e < 64 * 64; e += 256) {
+        const int pp = e >> 6, tt = e & 63;
+        const int tau = tau0 + tt, p = p0 + pp;
+        if (tau < Ttau && p < H) xc[(size_t(b) * chs + p) * Ttau + tau] = tile[tt][pp];
+    }
+}
+
+// conv output (B, 2N, T) -> (B, 2, T, N)
+__global__ __launch_bounds__(256) void stft_transpose_kernel(const float *__restrict__ src, float *__restrict__ dst,
+                                                             int N, int T) {
+    __shared__ float tile[64][65];
+    const int bc = blockIdx.z;  // b * 2 + c
+    const int f0 = blockIdx.y * 64, t0 = blockIdx.x * 64;
+    for (int e = threadIdx.x; e < 64 * 64; e += 256) {
+        const int ff = e >> 6, tt = e & 63;
+        const int f = f0 + ff, t = t0 + tt;
+        tile[ff][tt] = (f < N && t < T) ? src[(size_t(bc) * N + f) * T + t] : 0.f;
+    }
+    __syncthreads();
+    for (int e = threadIdx.x; e < 64 * 64; e += 256) {
+        const int tt = e >> 6, ff = e & 63;
+        const int f = f0 + ff, t = t0 + tt;
+        if (f < N && t < T) dst[(size_t(bc) * T + t) * N + f] = tile[ff][tt];
+    }
+}
+
+// (B, 2, T, N) -> (B, 2N, T): the transpose back, for the adjoint
+__global__ __launch_bounds__(256) void stft_untranspose_kernel(const float *__restrict__ src, float *__restrict__ dst,
+                                                               int N, int T) {
+    __shared__ float tile[64][65];
+    const int bc = blockIdx.z;
+    const int f0 = blockIdx.y * 64, t0 = blockIdx.x * 64;
+    for (int e = threadIdx.x; e < 64 * 64; e += 256) {
+        const int tt = e >> 6, ff = e & 63;
+        const int f = f0 + ff, t = t0 + tt;
+        tile[tt][ff] = (f < N && t < T) ? src[(size_t(bc) * T + t) * N + f] : 0.f;
+    }
+    __syncthreads();
+    for (int e = threadIdx.x; e < 64 * 64; e += 256) {
+        const int ff = e >> 6, tt = e & 63;
+        const int f = f0 + ff, t = t0 + tt;
+        if (f < N && t < T) dst[(size_t(bc) * N + f) * T + t] = tile[tt][ff];
+    }
+}
+
+// adjoint of stft_prep_kernel: dx[n] = sum over the padded positions i that read x[n]
+// (i = n + N/2 always; the reflected copies i = N/2 - n for 1 <= n <= N/2 and
+//  i = N/2 + 2(L-1) - n for L-1-N/2 <= n <= L-2), with dxc[p][tau] = dxp[tau H + p]
+__global__ __launch_bounds__(256) void stft_unprep_kernel(const float *__restrict__ dxc, float *__restrict__ dx, int L,
+                                                          int N, int H, int Ttau, int chs, int tau_off) {
+    const int n = blockIdx.x * 256 + threadIdx.x;
+    if (n >= L) return;
+    const int b = blockIdx.y, Lp = L + N, half = N / 2;
+    auto at = [&](int i) -> float {
+        if (i < 0 || i >= Lp) return 0.f;
+        const int th = i / H, p = i - th * H, tau = th - tau_off;
+        return (tau >= 0 && tau < Ttau) ? dxc[(size_t(b) * chs + p) * Ttau + tau] : 0.f;
+    };
+    float acc = at(n + half);
+    if (n >= 1 && n <= half) acc += at(half - n);
+    if (n <= L - 2 && n >= L - 1 - half) acc += at(half + 2 * (L - 1) - n);
+    dx[size_t(b) * L + n] = acc;
+}
+
+// reflect-pad + polyphase transpose of `batch` rows (and its adjoint); ch_stride = channels allocated per item
+static void launch_stft_prep(const float *x, float *xc, int batch, int L, int N, int H, int Ttau, int ch_stride,
+                             int tau_off, hipStream_t st) {
+    hipLaunchKernelGGL(stft_prep_kernel, dim3(ceil_div(Ttau, 64), ceil_div(H, 64), batch), dim3(256), 0, st, x, xc, L, N,
+                       H, Ttau, ch_stride, tau_off);
+}
+
+static void launch_stft_unprep(const float *dxc, float *dx, int batch, int L, int N, int H, int Ttau, int ch_stride,
+                               int tau_off, hipStream_t st) {
+    hipLaunchKernelGGL(stft_unprep_kernel, dim3(ceil_div(L, 256), batch), dim3(256), 0, st, dxc, dx, L, N, H, Ttau,
+                       ch_stride, tau_off);
 }
 
 // mel[b, m, t] = sum_f fb[f, m] (re[b,f,t]^2 + im[b,f,t]^2)      (MelScale(Spectrogram(power=2)))
@@ -170,8 +275,83 @@ __global__ __launch_bounds__(64) void biquad_kernel(const float *__restrict__ x,
     }
 }
 
+// ------------------------------------------------------------------ framed DFT: host side
+// The discriminator STFT (rectangular window = n_fft, hop n_fft / 4, two-sided) is one row of fdft_geom:
+// j0 = 0, Ke = K = 4, Hc = H, Fp = F = N, M = 2 N.
+static int stft_geom(int n_fft, FdftGeom *g) {
+    if (n_fft < 64 || (n_fft & (n_fft - 1))) return fail(AGX_ERR_UNSUPPORTED, "stft: n_fft must be a power of two >= 64");
+    return fdft_geom(n_fft, n_fft, n_fft / 4, 0, g);
+}
+
+static int stft_check(int length, int n_fft, FdftGeom *g) {
+    int rc = stft_geom(n_fft, g);
+    if (rc != AGX_OK) return rc;
+    if (length <= n_fft / 2) return fail(AGX_ERR_BAD_SHAPE, "stft: reflect padding needs length > n_fft / 2");
+    return AGX_OK;
+}
+
+static int64_t fdft_frames(int length, int hop) { return 1 + length / hop; }
+
+static int64_t fdft_packed_floats(const FdftGeom &g, int backward) {
+    return backward ? packed_weight_floats(g.M, g.Ke, g.Hc) : packed_weight_floats(g.Hc, g.Ke, g.M);
+}
+
+// the phase-channel buffer xc (batch, Hc, T + taps - 1), sized for a window that fills n_fft (Ke <= K)
+static int64_t fdft_xc_floats(int Hc, int K, int batch, int64_t T) { return int64_t(batch) * Hc * (T + K - 1); }
+
+static float fdft_scale(int norm_kind, int n_fft, int win_length, int window_kind) {
+    double scale = 1.0;
+    if (norm_kind == 1) scale = 1.0 / sqrt(double(n_fft));
+    if (norm_kind == 2) {   // 1 / sqrt(sum window^2)
+        double e = 0.0;
+        for (int k = 0; k < win_length; ++k) {
+            const double w = window_kind == 0 ? 1.0 : 0.5 - 0.5 * cos(2.0 * M_PI * double(k) / double(win_length));
+            e += w * w;
+        }
+        scale = 1.0 / sqrt(e);
+    }
+    return float(scale);
+}
+
+static void fdft_launch_pack(const FdftGeom &g, int window_kind, float scale, int backward, float *packed, hipStream_t st) {
+    hipLaunchKernelGGL(fdft_pack_kernel, dim3((unsigned)ceil_div64(fdft_packed_floats(g, backward), 256)), dim3(256), 0, st,
+                       packed, g, window_kind, scale, backward);
+}
+
+// The adjoint runs this conv's backward-data plan (core.hip:lower_conv_bwd_data: stride 1 -> the flipped kernel with the
+// channel roles swapped) on the same kernels.
 static agx_conv_desc fdft_conv_desc(const FdftGeom &g, int batch, int Ttau) {
     return agx_conv_desc{AGX_CONV_PADDED, batch, g.Hc, g.M, Ttau, g.Ke, 1, 1, 0, 0.f, AGX_IMPL_AUTO, 1, 0};
+}
+
+static int fdft_launch_conv(const ConvPlan &p, const float *x, const float *packed, float *y, hipStream_t st) {
+    return conv_mfma_supported(p) ? launch_conv_mfma(p, x, packed, nullptr, nullptr, y, st)
+                                  : launch_conv_direct(p, x, packed, nullptr, nullptr, y, st);   // few rows (hop 8 / 16 backward)
+}
+
+// x (batch, length) -> y (batch, M, T) through xc (batch, Hc, T + Ke - 1)
+static int fdft_run_forward(const FdftGeom &g, const float *x, const float *packed, float *y, float *xc, int batch,
+                            int length, hipStream_t st) {
+    const int Ttau = int(fdft_frames(length, g.H)) + g.Ke - 1;
+    if (g.Hc != g.H) hipMemsetAsync(xc, 0, size_t(batch) * g.Hc * Ttau * sizeof(float), st);   // padding channels
+    launch_stft_prep(x, xc, batch, length, g.N, g.H, Ttau, g.Hc, g.j0, st);
+    const agx_conv_desc d = fdft_conv_desc(g, batch, Ttau);
+    ConvPlan p;
+    int rc = lower_conv(&d, &p);
+    return rc != AGX_OK ? rc : fdft_launch_conv(p, xc, packed, y, st);
+}
+
+// dy (batch, M, T) -> dx (batch, length) through dxc (batch, Hc, T + Ke - 1)
+static int fdft_run_backward(const FdftGeom &g, const float *dy, const float *packed_bwd, float *dx, float *dxc, int batch,
+                             int length, hipStream_t st) {
+    const int Ttau = int(fdft_frames(length, g.H)) + g.Ke - 1;
+    const agx_conv_desc d = fdft_conv_desc(g, batch, Ttau);
+    ConvPlan p;
+    int rc = lower_conv_bwd_data(&d, &p);
+    if (rc == AGX_OK) rc = fdft_launch_conv(p, dy, packed_bwd, dxc, st);
+    if (rc != AGX_OK) return rc;
+    launch_stft_unprep(dxc, dx, batch, length, g.N, g.H, Ttau, g.Hc, g.j0, st);
+    return AGX_OK;
 }
 
 }  // namespace agx
@@ -204,14 +384,13 @@ extern "C" {
 
 int64_t agx_fdft_frames(int32_t length, int32_t n_fft, int32_t hop) {
     if (hop <= 0 || length <= n_fft / 2) return agx::fail(AGX_ERR_BAD_SHAPE, "fdft: reflect padding needs length > n_fft / 2");
-    return 1 + length / hop;
+    return agx::fdft_frames(length, hop);
 }
 
 int64_t agx_fdft_packed_floats(int32_t n_fft, int32_t win_length, int32_t hop, int32_t onesided, int32_t backward) {
     agx::FdftGeom g;
     int rc = agx::fdft_geom(n_fft, win_length, hop, onesided, &g);
-    if (rc != AGX_OK) return rc;
-    return backward ? agx::packed_weight_floats(g.M, g.Ke, g.Hc) : agx::packed_weight_floats(g.Hc, g.Ke, g.M);
+    return rc != AGX_OK ? rc : agx::fdft_packed_floats(g, backward);
 }
 
 int agx_fdft_pack(int32_t n_fft, int32_t win_length, int32_t hop, int32_t onesided, int32_t window_kind,
@@ -221,27 +400,16 @@ int agx_fdft_pack(int32_t n_fft, int32_t win_length, int32_t hop, int32_t onesid
     int rc = fdft_geom(n_fft, win_length, hop, onesided, &g);
     if (rc != AGX_OK) return rc;
     if (!packed) return fail(AGX_ERR_NULL_POINTER, "fdft_pack: NULL pointer");
-    double scale = 1.0;
-    if (norm_kind == 1) scale = 1.0 / sqrt(double(n_fft));
-    if (norm_kind == 2) {   // 1 / sqrt(sum window^2)
-        double e = 0.0;
-        for (int k = 0; k < win_length; ++k) {
-            const double w = window_kind == 0 ? 1.0 : 0.5 - 0.5 * cos(2.0 * M_PI * double(k) / double(win_length));
-            e += w * w;
-        }
-        scale = 1.0 / sqrt(e);
-    }
-    const int64_t n = agx_fdft_packed_floats(n_fft, win_length, hop, onesided, backward);
-    hipLaunchKernelGGL(fdft_pack_kernel, dim3((unsigned)ceil_div64(n, 256)), dim3(256), 0,
-                       static_cast<hipStream_t>(stream), packed, g, window_kind, float(scale), backward);
+    fdft_launch_pack(g, window_kind, fdft_scale(norm_kind, n_fft, win_length, window_kind), backward, packed,
+                     static_cast<hipStream_t>(stream));
     return check_launch("agx_fdft_pack");
 }
 
 int64_t agx_fdft_workspace_bytes(int32_t batch, int32_t length, int32_t n_fft, int32_t hop) {
     const int64_t T = agx_fdft_frames(length, n_fft, hop);
     if (T < 0) return T;
-    const int K = n_fft / hop, Hc = agx::ceil_div(hop, agx::kWG) * agx::kWG;
-    return int64_t(batch) * Hc * (T + K - 1) * int64_t(sizeof(float));
+    // (no win_length here: the buffer of the full window serves every shorter one; a query, so it answers before fdft_geom refuses)
+    return agx::fdft_xc_floats(agx::fdft_channels(hop), n_fft / hop, batch, T) * int64_t(sizeof(float));
 }
 
 int agx_fdft_forward(const float *x, const float *packed, float *y, void *workspace, int32_t batch, int32_t length,
@@ -254,19 +422,8 @@ int agx_fdft_forward(const float *x, const float *packed, float *y, void *worksp
     if (T64 < 0) return int(T64);
     if (!x || !packed || !y || !workspace) return fail(AGX_ERR_NULL_POINTER, "fdft_forward: NULL pointer");
     if (batch <= 0 || batch > 32767) return fail(AGX_ERR_BAD_SHAPE, "fdft: batch out of range");
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    const int T = int(T64), Ttau = T + g.Ke - 1;
-    float *xc = static_cast<float *>(workspace);
-    if (g.Hc != g.H) hipMemsetAsync(xc, 0, size_t(batch) * g.Hc * Ttau * sizeof(float), st);   // padding channels
-    launch_stft_prep(x, xc, batch, length, g.N, g.H, Ttau, g.Hc, g.j0, st);
-    const agx_conv_desc d = fdft_conv_desc(g, batch, Ttau);
-    ConvPlan p;
-    rc = lower_conv(&d, &p);
-    if (rc != AGX_OK) return rc;
-    rc = conv_mfma_supported(p) ? launch_conv_mfma(p, xc, packed, nullptr, nullptr, y, st)
-                                : launch_conv_direct(p, xc, packed, nullptr, nullptr, y, st);
-    if (rc != AGX_OK) return rc;
-    return check_launch("agx_fdft_forward");
+    rc = fdft_run_forward(g, x, packed, y, static_cast<float *>(workspace), batch, length, static_cast<hipStream_t>(stream));
+    return rc != AGX_OK ? rc : check_launch("agx_fdft_forward");
 }
 
 int agx_fdft_backward(const float *dy, const float *packed_bwd, float *dx, void *workspace, int32_t batch,
@@ -279,23 +436,87 @@ int agx_fdft_backward(const float *dy, const float *packed_bwd, float *dx, void 
     if (T64 < 0) return int(T64);
     if (!dy || !packed_bwd || !dx || !workspace) return fail(AGX_ERR_NULL_POINTER, "fdft_backward: NULL pointer");
     if (batch <= 0 || batch > 32767) return fail(AGX_ERR_BAD_SHAPE, "fdft: batch out of range");
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    const int T = int(T64), Ttau = T + g.Ke - 1;
-    float *dxc = static_cast<float *>(workspace);
-    const agx_conv_desc d = fdft_conv_desc(g, batch, Ttau);
-    ConvPlan p;
-    rc = lower_conv_bwd_data(&d, &p);
-    if (rc != AGX_OK) return rc;
-    rc = conv_mfma_supported(p) ? launch_conv_mfma(p, dy, packed_bwd, nullptr, nullptr, dxc, st)
-                                : launch_conv_direct(p, dy, packed_bwd, nullptr, nullptr, dxc, st);
-    if (rc != AGX_OK) return rc;
-    launch_stft_unprep(dxc, dx, batch, length, g.N, g.H, Ttau, g.Hc, g.j0, st);
-    return check_launch("agx_fdft_backward");
+    rc = fdft_run_backward(g, dy, packed_bwd, dx, static_cast<float *>(workspace), batch, length, static_cast<hipStream_t>(stream));
+    return rc != AGX_OK ? rc : check_launch("agx_fdft_backward");
 }
 
 int64_t agx_fdft_rows(int32_t n_fft, int32_t onesided) {   // rows per half of the channel-major spectrum (bins rounded up to 8)
-    const int f = onesided ? n_fft / 2 + 1 : n_fft;
-    return agx::ceil_div(f, 8) * 8;
+    return agx::fdft_rows(n_fft, onesided);
+}
+
+// ---- the discriminator STFT: the stft_geom row, (B, 2N, T) <-> (B, 2, T, N) on the way out / in
+int64_t agx_stft_frames(int32_t length, int32_t n_fft) {
+    agx::FdftGeom g;
+    int rc = agx::stft_check(length, n_fft, &g);
+    return rc != AGX_OK ? rc : agx::fdft_frames(length, g.H);
+}
+
+int64_t agx_stft_packed_floats(int32_t n_fft) {
+    agx::FdftGeom g;
+    int rc = agx::stft_geom(n_fft, &g);
+    return rc != AGX_OK ? rc : agx::fdft_packed_floats(g, 0);   // (== the backward image's: H is a multiple of 16)
+}
+
+static int stft_pack(int32_t n_fft, int32_t normalized, int backward, float *packed, void *stream, const char *name) {
+    using namespace agx;
+    FdftGeom g;
+    int rc = stft_geom(n_fft, &g);
+    if (rc != AGX_OK) return rc;
+    if (!packed) return fail(AGX_ERR_NULL_POINTER, "%s: NULL pointer", name + 4);   // (the name without "agx_")
+    fdft_launch_pack(g, 0, fdft_scale(normalized ? 1 : 0, n_fft, n_fft, 0), backward, packed, static_cast<hipStream_t>(stream));
+    return check_launch(name);
+}
+
+int agx_stft_pack(int32_t n_fft, int32_t normalized, float *packed, void *stream) {
+    return stft_pack(n_fft, normalized, 0, packed, stream, "agx_stft_pack");
+}
+
+int agx_stft_pack_bwd(int32_t n_fft, int32_t normalized, float *packed_bwd, void *stream) {
+    return stft_pack(n_fft, normalized, 1, packed_bwd, stream, "agx_stft_pack_bwd");
+}
+
+int64_t agx_stft_workspace_bytes(int32_t batch, int32_t length, int32_t n_fft) {   // xc, then the conv side of the transpose
+    agx::FdftGeom g;
+    int rc = agx::stft_check(length, n_fft, &g);
+    if (rc != AGX_OK) return rc;
+    if (batch <= 0) return agx::fail(AGX_ERR_BAD_SHAPE, "stft: batch <= 0");
+    const int64_t T = agx::fdft_frames(length, g.H);
+    return (agx::fdft_xc_floats(g.Hc, g.K, batch, T) + int64_t(batch) * g.M * T) * int64_t(sizeof(float));
+}
+
+int agx_stft_forward(const float *x, const float *packed, float *y, void *workspace, int32_t batch, int32_t length,
+                     int32_t n_fft, void *stream) {
+    using namespace agx;
+    FdftGeom g;
+    int rc = stft_check(length, n_fft, &g);
+    if (rc != AGX_OK) return rc;
+    if (batch <= 0 || batch > 32767) return fail(AGX_ERR_BAD_SHAPE, "stft: batch out of range");
+    if (!x || !packed || !y || !workspace) return fail(AGX_ERR_NULL_POINTER, "stft_forward: NULL pointer");
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    const int T = int(fdft_frames(length, g.H));
+    float *xc = static_cast<float *>(workspace), *cv = xc + fdft_xc_floats(g.Hc, g.K, batch, T);
+    rc = fdft_run_forward(g, x, packed, cv, xc, batch, length, st);
+    if (rc != AGX_OK) return rc;
+    hipLaunchKernelGGL(stft_transpose_kernel, dim3(ceil_div(T, 64), ceil_div(g.N, 64), batch * 2), dim3(256), 0, st, cv, y,
+                       g.N, T);
+    return check_launch("agx_stft_forward");
+}
+
+int agx_stft_backward(const float *dy, const float *packed_bwd, float *dx, void *workspace, int32_t batch,
+                      int32_t length, int32_t n_fft, void *stream) {
+    using namespace agx;
+    FdftGeom g;
+    int rc = stft_check(length, n_fft, &g);
+    if (rc != AGX_OK) return rc;
+    if (batch <= 0 || batch > 32767) return fail(AGX_ERR_BAD_SHAPE, "stft: batch out of range");
+    if (!dy || !packed_bwd || !dx || !workspace) return fail(AGX_ERR_NULL_POINTER, "stft_backward: NULL pointer");
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    const int T = int(fdft_frames(length, g.H));
+    float *dxc = static_cast<float *>(workspace), *cv = dxc + fdft_xc_floats(g.Hc, g.K, batch, T);
+    hipLaunchKernelGGL(stft_untranspose_kernel, dim3(ceil_div(T, 64), ceil_div(g.N, 64), batch * 2), dim3(256), 0, st, dy, cv,
+                       g.N, T);
+    rc = fdft_run_backward(g, cv, packed_bwd, dx, dxc, batch, length, st);
+    return rc != AGX_OK ? rc : check_launch("agx_stft_backward");
 }
 
 int agx_melpower(const float *cv, const float *fb, float *mel, int32_t batch, int32_t bins, int32_t frames,

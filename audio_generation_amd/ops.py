@@ -751,6 +751,19 @@ def conv2d_bwd_weight_kernel_name(desc) -> str:
 _STFT_IMAGES = {}
 
 
+def _stft_image_and_workspace(backward: bool, b: int, length: int, n_fft: int, normalized: bool, device):
+    """The cached weight image of one direction (packed on first use) and a fresh workspace."""
+    lib = _lib.load()
+    key = (bool(backward), n_fft, bool(normalized), device)
+    if key not in _STFT_IMAGES:
+        pack, name = (lib.agx_stft_pack_bwd, "agx_stft_pack_bwd") if backward else (lib.agx_stft_pack, "agx_stft_pack")
+        img = torch.empty(int(lib.agx_stft_packed_floats(n_fft)), dtype=torch.float32, device=device)
+        _lib.check(pack(n_fft, int(normalized), _ptr(img), _stream()), name)
+        _STFT_IMAGES[key] = img
+    ws = torch.empty(int(lib.agx_stft_workspace_bytes(b, length, n_fft)) // 4, dtype=torch.float32, device=device)
+    return _STFT_IMAGES[key], ws
+
+
 def stft(x: Tensor, n_fft: int, normalized: bool = True) -> Tensor:
     """(B, L) -> (B, 2, T, n_fft): two-sided rectangular-window STFT, hop n_fft / 4, reflect-centred."""
     lib = _lib.load()
@@ -760,16 +773,10 @@ def stft(x: Tensor, n_fft: int, normalized: bool = True) -> Tensor:
     t = lib.agx_stft_frames(length, n_fft)
     if t < 0:
         _lib.check(int(t), "agx_stft_frames")
-    key = (n_fft, bool(normalized), x.device)
-    if key not in _STFT_IMAGES:
-        img = torch.empty(int(lib.agx_stft_packed_floats(n_fft)), dtype=torch.float32, device=x.device)
-        _lib.check(lib.agx_stft_pack(n_fft, int(normalized), _ptr(img), _stream()), "agx_stft_pack")
-        _STFT_IMAGES[key] = img
-    ws = torch.empty(int(lib.agx_stft_workspace_bytes(b, length, n_fft)) // 4, dtype=torch.float32, device=x.device)
+    img, ws = _stft_image_and_workspace(False, b, length, n_fft, normalized, x.device)
     y = torch.empty(b, 2, int(t), n_fft, dtype=torch.float32, device=x.device)
     tok = _observer.begin("other", ("stft", 4 * (x.numel() + y.numel()), b * 2 * n_fft * n_fft * int(t))) if _observer is not None else None
-    _lib.check(lib.agx_stft_forward(_ptr(x), _ptr(_STFT_IMAGES[key]), _ptr(y), _ptr(ws), b, length, n_fft, _stream()),
-               "agx_stft_forward")
+    _lib.check(lib.agx_stft_forward(_ptr(x), _ptr(img), _ptr(y), _ptr(ws), b, length, n_fft, _stream()), "agx_stft_forward")
     if tok is not None:
         _observer.end(tok)
     return y
@@ -781,16 +788,10 @@ def stft_backward(dy: Tensor, length: int, n_fft: int, normalized: bool = True) 
     _need_gpu(dy)
     dy = _f32c(dy)
     b = dy.shape[0]
-    key = ("bwd", n_fft, bool(normalized), dy.device)
-    if key not in _STFT_IMAGES:
-        img = torch.empty(int(lib.agx_stft_packed_floats(n_fft)), dtype=torch.float32, device=dy.device)
-        _lib.check(lib.agx_stft_pack_bwd(n_fft, int(normalized), _ptr(img), _stream()), "agx_stft_pack_bwd")
-        _STFT_IMAGES[key] = img
-    ws = torch.empty(int(lib.agx_stft_workspace_bytes(b, length, n_fft)) // 4, dtype=torch.float32, device=dy.device)
+    img, ws = _stft_image_and_workspace(True, b, length, n_fft, normalized, dy.device)
     dx = torch.empty(b, length, dtype=torch.float32, device=dy.device)
     count_macs("stft_backward", b * 2 * n_fft * n_fft * dy.shape[2])
-    _lib.check(lib.agx_stft_backward(_ptr(dy), _ptr(_STFT_IMAGES[key]), _ptr(dx), _ptr(ws), b, length, n_fft, _stream()),
-               "agx_stft_backward")
+    _lib.check(lib.agx_stft_backward(_ptr(dy), _ptr(img), _ptr(dx), _ptr(ws), b, length, n_fft, _stream()), "agx_stft_backward")
     return dx
 
 
