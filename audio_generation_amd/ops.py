@@ -80,6 +80,9 @@ def _stream():
     return ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
 
 
+_DTYPES = (torch.float32, torch.int64, torch.float64, torch.uint8, torch.bfloat16)   # bfloat16: activation planes
+
+
 def _need_gpu(*tensors: Optional[Tensor]) -> None:
     for t in tensors:
         if t is None:
@@ -87,7 +90,7 @@ def _need_gpu(*tensors: Optional[Tensor]) -> None:
         if not t.is_cuda:
             raise AgxError("audio_generation_amd runs on the MI355X only: got a tensor on "
                            f"'{t.device}'.  There is no CPU / eager fallback.")
-        if t.dtype not in (torch.float32, torch.int64, torch.float64, torch.uint8, torch.bfloat16):   # bfloat16: activation planes
+        if t.dtype not in _DTYPES:
             raise AgxError(f"unsupported dtype {t.dtype}")
 
 
@@ -95,6 +98,14 @@ def _f32c(t: Tensor) -> Tensor:
     if t.dtype != torch.float32:
         raise AgxError(f"expected float32, got {t.dtype}")
     return t if t.is_contiguous() else t.contiguous()
+
+
+def _workspace(nbytes: int, device, query: str) -> Tensor:
+    """Exactly the bytes a ``*_workspace_bytes`` query of the library answered (a negative answer is its error code)."""
+    nbytes = int(nbytes)
+    if nbytes < 0:
+        _lib.check(nbytes, query)
+    return torch.empty(nbytes, dtype=torch.uint8, device=device)
 
 
 # --------------------------------------------------------------------------- conv
@@ -246,7 +257,7 @@ def conv_bwd_weight(desc: ConvDesc, x: Tensor, dy: Tensor, v: Tensor, g: Optiona
     dg = None if g is None else torch.empty_like(g)
     db = torch.empty(desc.c_out, dtype=torch.float32, device=x.device) if want_bias else None
     ws_bytes = int(lib.agx_conv_bwd_weight_workspace_bytes(ctypes.byref(desc)))
-    ws = torch.empty(max(ws_bytes, 4) // 4, dtype=torch.float32, device=x.device)
+    ws = _workspace(ws_bytes, x.device, "agx_conv_bwd_weight_workspace_bytes")
     count_macs("conv_bwd_weight", _conv_macs(desc), desc)
     _lib.check(lib.agx_conv_bwd_weight(ctypes.byref(desc), _ptr(x), _ptr(dy), _ptr(v), _ptr(g), _ptr(dv), _ptr(dg),
                                        _ptr(db), _ptr(ws), ws_bytes, _stream()), "agx_conv_bwd_weight")
@@ -268,7 +279,7 @@ def resblock_forward(desc: ConvDesc, x: Tensor, packed1: Tensor, bias1: Optional
                        f"{(desc.batch, desc.c_in, desc.l_in)}")
     y = torch.empty_like(x)
     ws_bytes = int(lib.agx_resblock_workspace_bytes(ctypes.byref(desc)))
-    ws = torch.empty(max(ws_bytes, 4) // 4, dtype=torch.float32, device=x.device)
+    ws = _workspace(ws_bytes, x.device, "agx_resblock_workspace_bytes")
     tok = _observer.begin("resblock", desc) if _observer is not None else None
     _lib.check(lib.agx_resblock_forward(ctypes.byref(desc), _ptr(x), _ptr(packed1), _ptr(bias1),
                                         _ptr(packed2), _ptr(bias2), _ptr(y), int(bool(post_act)),
@@ -333,12 +344,12 @@ def rvq_forward(x: Tensor, codebooks: Tensor, packed: Tensor, q_used: int,
     # one f64 buffer: [q_used per-stage sums | per-workgroup partials (the library's workspace)]; the commit loss is a
     # separate f32 scalar -- all three written by the launch, nothing to zero, no reduction on the torch side
     ws_bytes = int(lib.agx_rvq_workspace_bytes(b, t, d, k, q_used))
-    buf = torch.empty(max(q_used, 1) + ws_bytes // 8, dtype=torch.float64, device=x.device)
+    buf = torch.empty(q_used + ws_bytes // 8, dtype=torch.float64, device=x.device)
     commit = torch.empty((), dtype=torch.float32, device=x.device)
     tok = _observer.begin("rvq", (b, t, d, k, q_used)) if _observer is not None else None
     _lib.check(lib.agx_rvq_forward_ex(_ptr(x), sb, st, sd, _ptr(codebooks), _ptr(packed), b, t, d, k, q_used,
                                       _ptr(xq), qb, qt, qd, _ptr(index), _ptr(buf), _ptr(commit),
-                                      ctypes.c_void_p(buf.data_ptr() + 8 * max(q_used, 1)), ws_bytes, _stream()),
+                                      ctypes.c_void_p(buf.data_ptr() + 8 * q_used), ws_bytes, _stream()),
                "agx_rvq_forward_ex")
     if tok is not None:
         _observer.end(tok)
@@ -359,8 +370,8 @@ def rvq_ema_stats(frames: Tensor, codebooks: Tensor, index: Tensor) -> Tensor:
     q_used = index.shape[1]
     k = codebooks.shape[1]
     stats = torch.empty(q_used, k, d + 1, dtype=torch.float32, device=frames.device)
-    nbytes = lib.agx_rvq_ema_workspace_bytes(n, d, q_used)
-    ws = torch.empty(nbytes // 4, dtype=torch.float32, device=frames.device)
+    nbytes = int(lib.agx_rvq_ema_workspace_bytes(n, d, q_used))
+    ws = _workspace(nbytes, frames.device, "agx_rvq_ema_workspace_bytes")
     _lib.check(lib.agx_rvq_ema_stats(_ptr(frames), _ptr(codebooks), _ptr(index), _ptr(stats), n, d, k, q_used, _ptr(ws), nbytes,
                                      _stream()), "agx_rvq_ema_stats")
     return stats
@@ -477,8 +488,8 @@ def attention_alibi_backward(qkv: Tensor, slopes: Tensor, dout: Tensor, heads: i
         return dqkv
     if out is None:
         raise AgxError("attention_alibi_backward: T > 256 or head_dim > 64 needs the forward output (out=)")
-    nbytes = lib.agx_attention_backward_workspace_bytes(b, heads, t)
-    ws = torch.empty(nbytes // 4, dtype=torch.float32, device=qkv.device)
+    nbytes = int(lib.agx_attention_backward_workspace_bytes(b, heads, t))
+    ws = _workspace(nbytes, qkv.device, "agx_attention_backward_workspace_bytes")
     _lib.check(lib.agx_attention_alibi_backward_ex(_ptr(qkv), _ptr(_f32c(slopes)), _ptr(_f32c(out)), _ptr(dout), _ptr(dqkv),
                                                    _ptr(ws), nbytes, b, heads, head_dim, t, float(scale_div), _stream()),
                "agx_attention_alibi_backward_ex")
@@ -524,7 +535,7 @@ def multires_backward(x: Tensor, dout: Tensor, h0: Tensor, h1: Tensor, w: Tensor
         raise AgxError("multires_backward: shapes do not match (B,C,L) / (C,1,K) / (C,depth+2)")
     dx, dh0, dh1, dw = torch.empty_like(x), torch.empty_like(h0), torch.empty_like(h1), torch.empty_like(w)
     nbytes = int(lib.agx_multires_backward_workspace_bytes(b, c, length, k, depth))
-    ws = torch.empty(max(nbytes, 4) // 4, dtype=torch.float32, device=x.device)
+    ws = _workspace(nbytes, x.device, "agx_multires_backward_workspace_bytes")
     _lib.check(lib.agx_multires_backward(_ptr(x), _ptr(dout), _ptr(_f32c(h0)), _ptr(_f32c(h1)), _ptr(_f32c(w)), _ptr(dx),
                                          _ptr(dh0), _ptr(dh1), _ptr(dw), _ptr(ws), nbytes, b, c, length, k, depth,
                                          _stream()), "agx_multires_backward")
@@ -626,7 +637,7 @@ def conv_grouped_bwd_weight(desc: ConvDesc, x: Tensor, dz: Tensor, want_bias: bo
     dw = torch.empty(desc.c_out, desc.c_in // g, desc.kernel, dtype=torch.float32, device=x.device)
     db = torch.empty(desc.c_out, dtype=torch.float32, device=x.device) if want_bias else None
     nbytes = int(lib.agx_conv_grouped_bwd_weight_workspace_bytes(ctypes.byref(desc)))
-    ws = torch.empty(nbytes // 4 + 1, dtype=torch.float32, device=x.device)
+    ws = _workspace(nbytes, x.device, "agx_conv_grouped_bwd_weight_workspace_bytes")
     count_macs("conv_bwd_weight", _conv_macs(desc), desc)
     _lib.check(lib.agx_conv_grouped_bwd_weight(ctypes.byref(desc), _ptr(x), _ptr(dz), _ptr(dw), _ptr(db), _ptr(ws),
                                                nbytes, _stream()), "agx_conv_grouped_bwd_weight")
@@ -708,7 +719,7 @@ def conv2d_bwd_weight(desc, x: Tensor, dy: Tensor, w: Optional[Tensor] = None, s
     dw = torch.empty(desc.c_out, desc.c_in, desc.kh, desc.kw, dtype=torch.float32, device=x.device)
     db = torch.empty(desc.c_out, dtype=torch.float32, device=x.device) if want_bias else None
     nbytes = int(lib.agx_conv2d_bwd_weight_workspace_bytes(ctypes.byref(desc)))
-    ws = torch.empty(nbytes // 4 + 1, dtype=torch.float32, device=x.device)
+    ws = _workspace(nbytes, x.device, "agx_conv2d_bwd_weight_workspace_bytes")
     w = None if w is None else _f32c(w)
     count_macs("conv2d_bwd_weight", _conv2d_macs(desc), desc)
     _lib.check(lib.agx_conv2d_bwd_weight(ctypes.byref(desc), _ptr(x), _ptr(dy), _ptr(w), _ptr(sigma), _ptr(u), _ptr(v),
@@ -749,6 +760,7 @@ def conv2d_bwd_weight_kernel_name(desc) -> str:
 
 
 _STFT_IMAGES = {}
+_DEVICE_CACHES = (_STFT_IMAGES,)     # every module-level cache that keeps device buffers across calls
 
 
 def _stft_image_and_workspace(backward: bool, b: int, length: int, n_fft: int, normalized: bool, device):
@@ -760,7 +772,7 @@ def _stft_image_and_workspace(backward: bool, b: int, length: int, n_fft: int, n
         img = torch.empty(int(lib.agx_stft_packed_floats(n_fft)), dtype=torch.float32, device=device)
         _lib.check(pack(n_fft, int(normalized), _ptr(img), _stream()), name)
         _STFT_IMAGES[key] = img
-    ws = torch.empty(int(lib.agx_stft_workspace_bytes(b, length, n_fft)) // 4, dtype=torch.float32, device=device)
+    ws = _workspace(lib.agx_stft_workspace_bytes(b, length, n_fft), device, "agx_stft_workspace_bytes")
     return _STFT_IMAGES[key], ws
 
 

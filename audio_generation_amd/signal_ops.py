@@ -198,9 +198,7 @@ class MelSpectrogram(nn.Module):
 
     def _ws(self, b: int, length: int, device) -> Tensor:
         n = _lib.load().agx_fdft_workspace_bytes(b, length, self.n_fft, self.hop_length)
-        if n < 0:
-            _lib.check(int(n), "agx_fdft_workspace_bytes")
-        return torch.empty(int(n) // 4 + 1, dtype=torch.float32, device=device)
+        return ops._workspace(n, device, "agx_fdft_workspace_bytes")
 
     def _forward_raw(self, x: Tensor):
         lib = _lib.load()
