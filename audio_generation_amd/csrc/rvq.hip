@@ -957,15 +957,17 @@ __global__ __launch_bounds__(256) void rvq_residuals_kernel(const float *__restr
     }
 }
 
+// The row sum both per-code kernels share: the calling workgroup (256 threads) adds the rows Rq[f][:] of the frames f with
+// index[f][q] == k, in list order as described above, and leaves the four wave sums in part[wave][0 .. dim).  Returns the
+// number of such frames (uniform); the caller may read `part` right away.  A code that owns more than EMA_LIST - 256
+// frames drains its list every time the next block of 256 might not fit.
 template <bool VEC>
-__global__ __launch_bounds__(256) void rvq_ema_stats_kernel(const float *__restrict__ R, const int64_t *__restrict__ index,
-                                                            float *__restrict__ stats, int n, int dim, int K, int Q) {
+__device__ __forceinline__ int rvq_code_row_sum(const float *__restrict__ Rq, const int64_t *__restrict__ index, int n,
+                                                int dim, int Q, int q, int k, float (*part)[1024]) {
     constexpr int NA = VEC ? 4 : 16;          // accumulators per lane: dim <= 1024
     __shared__ int list[EMA_LIST];
     __shared__ int wave_cnt[4];
-    __shared__ float part[4][1024];
-    const int k = blockIdx.x, q = blockIdx.y, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const float *Rq = R + int64_t(q) * n * dim;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     f32x4 av[VEC ? NA : 1];
     float as[VEC ? 1 : NA];
 #pragma unroll
@@ -1028,9 +1030,121 @@ __global__ __launch_bounds__(256) void rvq_ema_stats_kernel(const float *__restr
         }
     }
     __syncthreads();
+    return total;
+}
+
+template <bool VEC>
+__global__ __launch_bounds__(256) void rvq_ema_stats_kernel(const float *__restrict__ R, const int64_t *__restrict__ index,
+                                                            float *__restrict__ stats, int n, int dim, int K, int Q) {
+    __shared__ float part[4][1024];
+    const int k = blockIdx.x, q = blockIdx.y, tid = threadIdx.x;
+    const int total = rvq_code_row_sum<VEC>(R + int64_t(q) * n * dim, index, n, dim, Q, q, k, part);
     float *o = stats + (size_t(q) * K + k) * (dim + 1);
     if (tid == 0) o[0] = float(total);
     for (int d = tid; d < dim; d += 256) o[1 + d] = ((part[0][d] + part[1][d]) + part[2][d]) + part[3][d];
+}
+
+// Backward of the training call (agx_rvq_backward).  Everything is elementwise in d, so a workgroup owns a tile of
+// BW_TF frames x BW_TD dims:
+//   rvq_bwd_dx_kernel        x and g_xq tiles -> LDS with the lanes along whichever axis the tensor is contiguous in
+//                            ((B, D, T) tensors: frames; (B, T, D): dims), then lanes along d (codeword rows and the S_q rows
+//                            are D-contiguous): the residual chain r_1 .. r_Q in registers, walked back into the suffix sums
+//                            S_q (-> workspace [q][n][D], when the codebook gradient is wanted) and dx = g + a S_0 -> LDS ->
+//                            global, again along dx's own contiguous axis.
+//   rvq_bwd_codebook_kernel  the ordered row sum of the EMA statistics over S_q, times -a; stages >= Q are zero-filled.
+constexpr int BW_TF = 64, BW_TD = 64, BW_RS = BW_TD + 1;
+
+struct RvqBwdArgs {
+    const float *x;
+    int64_t x_sb, x_st, x_sd;
+    const float *g;            // NULL: zero
+    int64_t g_sb, g_st, g_sd;
+    float *dx;
+    int64_t d_sb, d_st, d_sd;
+    const float *cb;
+    const int64_t *index;
+    const float *g_commit;     // device scalar, NULL: zero
+    float *S;                  // NULL: not wanted
+    int n, t, dim, K, Q;
+    float scale;               // 2 / (N D)
+};
+
+template <int QMAX>   // Q <= QMAX residuals per element live in registers
+__global__ __launch_bounds__(256) void rvq_bwd_dx_kernel(RvqBwdArgs a) {
+    __shared__ float xs[BW_TF * BW_RS], gs[BW_TF * BW_RS];
+    __shared__ int64_t off[3][BW_TF];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int n0 = blockIdx.x * BW_TF, d0 = blockIdx.y * BW_TD;
+    const int nf = min(BW_TF, a.n - n0), nd = min(BW_TD, a.dim - d0);
+    if (tid < nf) {
+        const int n = n0 + tid, b = n / a.t, t = n - b * a.t;
+        off[0][tid] = b * a.x_sb + t * a.x_st;
+        off[1][tid] = b * a.g_sb + t * a.g_st;
+        off[2][tid] = b * a.d_sb + t * a.d_st;
+    }
+    __syncthreads();
+    auto stage = [&](const float *__restrict__ p, int64_t sd, const int64_t *o, float *tile) {
+        if (sd == 1) {
+            if (lane < nd)
+                for (int f = wave; f < nf; f += 4) tile[f * BW_RS + lane] = p[o[f] + (d0 + lane)];
+        } else if (lane < nf) {
+            for (int d = wave; d < nd; d += 4) tile[lane * BW_RS + d] = p[o[lane] + (d0 + d) * sd];
+        }
+    };
+    stage(a.x, a.x_sd, off[0], xs);
+    if (a.g) stage(a.g, a.g_sd, off[1], gs);
+    __syncthreads();
+    const float av = (a.g_commit && a.Q > 0) ? *a.g_commit * a.scale : 0.f;
+    if (lane < nd) {
+        const int d = d0 + lane;
+        for (int f = wave; f < nf; f += 4) {
+            const int64_t n = n0 + f;
+            const int64_t *ix = a.index + n * a.Q;
+            float r = xs[f * BW_RS + lane], rq[QMAX];
+#pragma unroll
+            for (int q = 0; q < QMAX; ++q) {
+                if (q < a.Q) {
+                    const int64_t c = ix[q];
+                    if (c >= 0 && c < a.K) r -= a.cb[(int64_t(q) * a.K + c) * a.dim + d];
+                }
+                rq[q] = r;
+            }
+            float s = 0.f;
+#pragma unroll
+            for (int q = QMAX - 1; q >= 0; --q) {
+                if (q < a.Q) {
+                    s += rq[q];        // S_{Q-1} = 0 + r_Q
+                    if (a.S) a.S[(int64_t(q) * a.n + n) * a.dim + d] = s;
+                }
+            }
+            xs[f * BW_RS + lane] = (a.g ? gs[f * BW_RS + lane] : 0.f) + av * s;
+        }
+    }
+    __syncthreads();
+    if (a.d_sd == 1) {
+        if (lane < nd)
+            for (int f = wave; f < nf; f += 4) a.dx[off[2][f] + (d0 + lane)] = xs[f * BW_RS + lane];
+    } else if (lane < nf) {
+        for (int d = wave; d < nd; d += 4) a.dx[off[2][lane] + (d0 + d) * a.d_sd] = xs[lane * BW_RS + d];
+    }
+}
+
+template <bool VEC>
+__global__ __launch_bounds__(256) void rvq_bwd_codebook_kernel(const float *__restrict__ S, const int64_t *__restrict__ index,
+                                                               const float *__restrict__ g_commit, float scale,
+                                                               float *__restrict__ dcb, int n, int dim, int K, int Q) {
+    __shared__ float part[4][1024];
+    const int k = blockIdx.x, q = blockIdx.y, tid = threadIdx.x;
+    float *o = dcb + (size_t(q) * K + k) * dim;
+    if (q >= Q) {   // a stage this call did not run (uniform)
+        for (int d = tid; d < dim; d += 256) o[d] = 0.f;
+        return;
+    }
+    const int total = rvq_code_row_sum<VEC>(S + int64_t(q) * n * dim, index, n, dim, Q, q, k, part);
+    // a code no frame chose gets +0 whatever g_commit holds: the padding rows of a short stage stay zero under Adam
+    const float na = (g_commit && total > 0) ? -(*g_commit * scale) : 0.f;
+    for (int d = tid; d < dim; d += 256)
+        o[d] = total > 0 ? na * (((part[0][d] + part[1][d]) + part[2][d]) + part[3][d]) : 0.f;
 }
 
 }  // namespace agx
@@ -1195,6 +1309,49 @@ int agx_rvq_ema_stats(const float *frames, const float *codebooks, const int64_t
         hipLaunchKernelGGL(rvq_ema_stats_kernel<false>, dim3(k, q_used), dim3(256), 0, st, R, index, stats, int(n_frames), dim,
                            k, q_used);
     return check_launch("rvq_ema_stats");
+}
+
+size_t agx_rvq_backward_workspace_bytes(int64_t n_frames, int32_t dim, int32_t q_used) {
+    if (n_frames <= 0 || dim <= 0 || q_used <= 0) return 0;
+    return size_t(n_frames) * dim * q_used * sizeof(float);
+}
+
+int agx_rvq_backward(const float *x, int64_t x_sb, int64_t x_st, int64_t x_sd, const float *codebooks, const int64_t *index,
+                     const float *g_xq, int64_t g_sb, int64_t g_st, int64_t g_sd, const float *g_commit,
+                     int32_t batch, int32_t t, int32_t dim, int32_t k, int32_t n_q, int32_t q_used,
+                     float *dx, int64_t d_sb, int64_t d_st, int64_t d_sd, float *dcodebooks,
+                     void *workspace, size_t workspace_bytes, void *stream) {
+    using namespace agx;
+    const int64_t n = int64_t(batch) * t;
+    if (batch <= 0 || t <= 0 || dim <= 0 || k <= 0 || n_q <= 0 || q_used < 0 || q_used > n_q || n > INT32_MAX)
+        return fail(AGX_ERR_BAD_SHAPE, "rvq_backward: bad shape B=%d T=%d D=%d K=%d n_q=%d q_used=%d", batch, t, dim, k, n_q, q_used);
+    if (dim > 1024) return fail(AGX_ERR_UNSUPPORTED, "rvq_backward: D=%d > 1024", dim);
+    if (n_q > 64) return fail(AGX_ERR_UNSUPPORTED, "rvq_backward: at most 64 stages (n_q=%d)", n_q);
+    const bool want_dc = dcodebooks != nullptr && q_used > 0;   // the S_q are kept only for the codebook kernel
+    if (!x || !dx || (q_used > 0 && (!codebooks || !index)) || (want_dc && !workspace))
+        return fail(AGX_ERR_NULL_POINTER, "rvq_backward: NULL pointer");
+    if (want_dc && workspace_bytes < agx_rvq_backward_workspace_bytes(n, dim, q_used))
+        return fail(AGX_ERR_WORKSPACE, "rvq_backward: workspace too small (%zu < %zu)", workspace_bytes,
+                    agx_rvq_backward_workspace_bytes(n, dim, q_used));
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    float *S = want_dc ? static_cast<float *>(workspace) : nullptr;
+    const float scale = float(2.0 / (double(n) * dim));
+    RvqBwdArgs a{x, x_sb, x_st, x_sd, g_xq, g_sb, g_st, g_sd, dx, d_sb, d_st, d_sd, codebooks, index, g_commit, S,
+                 int(n), t, dim, k, q_used, scale};
+    const dim3 grid((unsigned)ceil_div64(n, BW_TF), (unsigned)ceil_div(dim, BW_TD));
+    if (q_used <= 16)
+        hipLaunchKernelGGL(rvq_bwd_dx_kernel<16>, grid, dim3(256), 0, st, a);
+    else
+        hipLaunchKernelGGL(rvq_bwd_dx_kernel<64>, grid, dim3(256), 0, st, a);
+    if (dcodebooks) {
+        if (dim % 4 == 0)
+            hipLaunchKernelGGL(rvq_bwd_codebook_kernel<true>, dim3(k, n_q), dim3(256), 0, st, S, index, g_commit, scale,
+                               dcodebooks, int(n), dim, k, q_used);
+        else
+            hipLaunchKernelGGL(rvq_bwd_codebook_kernel<false>, dim3(k, n_q), dim3(256), 0, st, S, index, g_commit, scale,
+                               dcodebooks, int(n), dim, k, q_used);
+    }
+    return check_launch("rvq_backward");
 }
 
 }  // extern "C"

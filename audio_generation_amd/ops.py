@@ -377,6 +377,47 @@ def rvq_ema_stats(frames: Tensor, codebooks: Tensor, index: Tensor) -> Tensor:
     return stats
 
 
+def rvq_backward(x: Tensor, codebooks: Tensor, index: Tensor, g_xq: Optional[Tensor], g_commit: Optional[Tensor],
+                 layout: str = "b l c", want_codebook_grad: bool = False) -> Tuple[Tensor, Optional[Tensor]]:
+    """Backward of the quantiser's training call (``agx_rvq_backward``): x and g_xq (any strides, ``None`` = zero) in
+    ``layout`` as for ``rvq_forward``, index (B, T, q_used) as the forward returned it, g_commit a 0-d device tensor (``None`` =
+    zero; never read on the host) -> (dx contiguous in x's shape, d codebooks (Q, K, D) or ``None``)."""
+    lib = _lib.load()
+    _need_gpu(x, codebooks, index, g_xq, g_commit)
+    for t_ in (x, g_xq, g_commit):
+        if t_ is not None and t_.dtype != torch.float32:
+            raise AgxError(f"rvq_backward: expected float32, got {t_.dtype}")
+    if index.dtype != torch.int64 or not index.is_contiguous():
+        raise AgxError("rvq_backward: index must be the contiguous int64 tensor rvq_forward returned")
+    codebooks = _f32c(codebooks)
+    q_total, k, d = codebooks.shape
+    if layout == "b l c":
+        perm = (0, 1, 2)
+    elif layout == "b c l":
+        perm = (0, 2, 1)
+    else:
+        raise AgxError(f"rvq_backward: unknown layout {layout!r}")
+    b, t, dim = (x.shape[p] for p in perm)
+    q_used = index.shape[-1]
+    if dim != d or tuple(index.shape) != (b, t, q_used) or not 0 <= q_used <= q_total:
+        raise AgxError(f"rvq_backward: x {tuple(x.shape)} ({layout}), index {tuple(index.shape)}, codebooks {tuple(codebooks.shape)}")
+    if g_xq is not None and g_xq.shape != x.shape:
+        raise AgxError(f"rvq_backward: g_xq {tuple(g_xq.shape)} for x {tuple(x.shape)}")
+    if g_commit is not None and g_commit.numel() != 1:
+        raise AgxError("rvq_backward: g_commit must hold one element")
+    dx = torch.empty(x.shape, dtype=torch.float32, device=x.device)
+    dcb = torch.empty(codebooks.shape, dtype=torch.float32, device=x.device) if want_codebook_grad else None
+    nbytes = int(lib.agx_rvq_backward_workspace_bytes(b * t, d, q_used)) if want_codebook_grad else 0
+    ws = _workspace(nbytes, x.device, "agx_rvq_backward_workspace_bytes") if nbytes else None
+
+    def strides(t_):
+        return [0, 0, 0] if t_ is None else [t_.stride(p) for p in perm]
+    _lib.check(lib.agx_rvq_backward(_ptr(x), *strides(x), _ptr(codebooks), _ptr(index), _ptr(g_xq), *strides(g_xq),
+                                    _ptr(g_commit), b, t, d, k, q_total, q_used, _ptr(dx), *strides(dx), _ptr(dcb),
+                                    _ptr(ws), nbytes, _stream()), "agx_rvq_backward")
+    return dx, dcb
+
+
 def rvq_dequantize(codebook: Tensor, idx: Tensor, out: Optional[Tensor] = None,
                    accumulate: bool = False) -> Tensor:
     """``codebook[idx]``: idx (...,) int64 -> (..., D)."""

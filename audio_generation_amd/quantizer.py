@@ -20,6 +20,15 @@ external module (EMA / SOM neighbourhoods) are unknown and training-only, so
 ``update_codebook=True`` applies a plain EMA k-means update (build-defined,
 torch bookkeeping, not on the measured path).
 
+**Training** (build-defined).  With grad enabled and an input or codebooks that require it, the call is one
+autograd ``Function``: its forward is the same single search launch as in eval -- ``x_q`` and ``commit`` are bit for bit the eval
+results -- and its backward is ``agx_rvq_backward``.  With ``r_0 = x``, ``r_{q+1} = fl32(r_q - c_q[idx])``, the commit loss
+``L = sum_q mean(r_{q+1}^2)``, ``S_q = sum_{q' >= q} r_{q'+1}`` and ``a = 2 g_L / (N D)``: ``dx = g_xq + a S_0`` (straight-through
+plus commitment term) and, for ``quantizer_class="base"`` only, ``dC[q][k] = -a sum_{n: idx[n][q] = k} S_q[n]`` (the loss is
+differentiable in the selected codewords; exactly zero for codes nobody chose, stages that did not run and padding rows).
+``"ema"`` codebooks are a buffer and get no gradient.  No ATen arithmetic runs between the encoder's output and the decoder's
+input, forward or backward.
+
 **Not performed** (their definition lives in the absent ``som_quantizer``; parity unpinned): the SOM
 neighbourhood update (``use_som`` / ``som_kernel_type``, ``vae.py:249-250``), early-stage prioritisation
 (``prioritize_early``, ``training.py:325-328``) and stale-code replacement (``vq_cutoff_freq`` only feeds
@@ -84,6 +93,26 @@ def _warn_once(key: str, message: str) -> None:
         warnings.warn(message, UserWarning, stacklevel=3)
 
 
+class _QuantizeNative(torch.autograd.Function):
+    """The training call: the search launch forward, ``agx_rvq_backward`` backward (module docstring, "Training")."""
+
+    @staticmethod
+    def forward(ctx, x: Tensor, codebooks: Tensor, packed: Tensor, q_used: int, layout: str):
+        xq, index, _, commit = ops.rvq_forward(x.detach(), codebooks.detach(), packed, q_used, layout)
+        ctx.layout = layout
+        ctx.save_for_backward(x, codebooks, index)     # the codebooks' version counter guards against an update in between
+        ctx.mark_non_differentiable(index)
+        ctx.set_materialize_grads(False)               # an unused output arrives as None, not as a frame-sized zero tensor
+        return xq, index, commit
+
+    @staticmethod
+    def backward(ctx, g_xq, _g_index, g_commit):
+        x, codebooks, index = ctx.saved_tensors
+        dx, dcb = ops.rvq_backward(x, codebooks, index, g_xq, g_commit, ctx.layout,
+                                   want_codebook_grad=ctx.needs_input_grad[1])
+        return (dx if ctx.needs_input_grad[0] else None), dcb, None, None, None
+
+
 class ResidualQuantizer(nn.Module):
     def __init__(self, num_quantizers=8, dim=512, quantizer_class="ema", codebook_sizes=1024,
                  vq_cutoff_freq=1, use_som=True, som_kernel_type="hard", ema_decay=0.99):
@@ -141,21 +170,14 @@ class ResidualQuantizer(nn.Module):
                        f"(som_kernel_type={self.som_kernel_type!r}) and stale-code replacement are NOT performed -- their "
                        "definition lives in the external `som_quantizer` module, which is absent from the reference tree "
                        "(parity unpinned); update_codebook=True applies the build-defined plain EMA k-means update only.")
-        xq, index, sq_err, commit_eval = ops.rvq_forward(x.detach(), self.codebooks.detach(), self._packed_codebooks(),
-                                                         q_used, layout)
-        if torch.is_grad_enabled() and x.requires_grad:
-            # training semantics (build-defined, the external module's are unknown): straight-through
-            # estimator for x_q, and a commitment loss that is differentiable in the encoder output --
-            # sum over stages of mean((x - sum_{p<=q} c_p)^2) with the selected codewords detached.
-            partial, commit = None, x.new_zeros(())
-            for q in range(q_used):
-                c = ops.rvq_dequantize(self.codebooks.detach()[q], index[..., q])          # (B,T,D)
-                c = c if layout == "b l c" else c.transpose(1, 2)
-                partial = c if partial is None else partial + c
-                commit = commit + ((x - partial) ** 2).mean()
-            xq = x + (xq - x).detach()
+        cb = self.codebooks
+        if torch.is_grad_enabled() and (x.requires_grad or cb.requires_grad):
+            packed = self._packed_codebooks()
+            if update_codebook and self.training and self.quantizer_class != "base":
+                cb = cb.clone()     # the EMA update below overwrites the buffer before the backward reads the codewords
+            xq, index, commit = _QuantizeNative.apply(x, cb, packed, q_used, layout)
         else:
-            commit = commit_eval                          # sum(sq_err) / numel, written by the search launch itself
+            xq, index, _, commit = ops.rvq_forward(x.detach(), cb.detach(), self._packed_codebooks(), q_used, layout)
         if update_codebook and self.training:
             frames = x if layout == "b l c" else x.transpose(1, 2)
             self._ema_update(frames.reshape(-1, self.dim), index.reshape(-1, q_used))

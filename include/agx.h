@@ -261,6 +261,28 @@ size_t agx_rvq_ema_workspace_bytes(int64_t n_frames, int32_t dim, int32_t q_used
 int agx_rvq_ema_stats(const float *frames, const float *codebooks, const int64_t *index, float *stats, int64_t n_frames,
                       int32_t dim, int32_t k, int32_t q_used, void *workspace, size_t workspace_bytes, void *stream);
 
+/* Backward of the quantiser's training call (build-defined like the rest of its training semantics).  With
+ * N = B*T frames, idx = the indices agx_rvq_forward returned, r_0 = x, r_{q+1} = fl32(r_q - c_q[idx[.][q]]) (the search's
+ * residual chain), L = sum_{q < q_used} mean(r_{q+1}^2) (the commit loss of agx_rvq_forward_ex), the suffix sums
+ * S_{Q-1} = r_Q, S_q = fl32(S_{q+1} + r_{q+1}) and a = 2 * g_commit / (N * D):
+ *   dx[n]          = g_xq[n] + a * S_0[n]                            (straight-through term + commitment term)
+ *   dcodebooks[q][k] = -a * sum over {n : idx[n][q] == k} of S_q[n]  (rows in frame order, fixed tree: deterministic, no
+ *                    atomics); exactly 0 for codes no frame chose and for stages >= q_used.
+ *   x, g_xq, dx : element (b,t,d) at b*stride_b + t*stride_t + d*stride_d, each with its own strides; g_xq NULL = zero;
+ *   g_commit    : ONE float on the device (no host read: the call can be captured), NULL = zero;
+ *   index       : (N, q_used) int64 contiguous; an index outside [0, K) contributes nothing;
+ *   codebooks, dcodebooks : (n_q, K, D) contiguous, q_used <= n_q <= 64; dcodebooks NULL = not wanted (an EMA codebook);
+ *   workspace   : the S_q, [q][n][D] floats -- exactly 4 * q_used * N * D bytes, no rounding (agx_rvq_backward_workspace_bytes;
+ *                 0 for a non-positive argument).  Read and written only when dcodebooks is given; may be NULL otherwise.
+ * q_used == 0: dx = g_xq (or zero), dcodebooks = 0.  D <= 1024 (AGX_ERR_UNSUPPORTED beyond).  Everything is validated
+ * before the device is touched. */
+size_t agx_rvq_backward_workspace_bytes(int64_t n_frames, int32_t dim, int32_t q_used);
+int agx_rvq_backward(const float *x, int64_t x_sb, int64_t x_st, int64_t x_sd, const float *codebooks, const int64_t *index,
+                     const float *g_xq, int64_t g_sb, int64_t g_st, int64_t g_sd, const float *g_commit,
+                     int32_t batch, int32_t t, int32_t dim, int32_t k, int32_t n_q, int32_t q_used,
+                     float *dx, int64_t d_sb, int64_t d_st, int64_t d_sd, float *dcodebooks,
+                     void *workspace, size_t workspace_bytes, void *stream);
+
 /* ------------------------------------------------------------------------- *
  * Activation planes (bf16x3 arithmetic, round 4)                              *
  * ------------------------------------------------------------------------- *
