@@ -537,6 +537,60 @@ def attention_alibi_backward(qkv: Tensor, slopes: Tensor, dout: Tensor, heads: i
     return dqkv
 
 
+def _cross_shapes(op: str, q: Tensor, kv: Tensor, heads: int, head_dim: int):
+    (b, cq, tq), (bk, ckv, tk) = q.shape, kv.shape
+    if cq != heads * head_dim:
+        raise AgxError(f"{op}: q has {cq} channels, expected {heads * head_dim}")
+    if ckv != 2 * heads * head_dim:
+        raise AgxError(f"{op}: kv has {ckv} channels, expected {2 * heads * head_dim}")
+    if bk != b:
+        raise AgxError(f"{op}: q has batch {b}, kv has batch {bk}")
+    return b, tq, tk
+
+
+def attention_cross_kernel_name(batch: int, heads: int, head_dim: int, tq: int, tk: int, backward: bool = False) -> str:
+    """The kernel ``attention_alibi_cross`` runs for this shape, with ``backward`` the three kernels of
+    ``attention_alibi_cross_backward`` (host-only); ``AgxError`` with the launcher's message if it refuses."""
+    return _kernel_name("agx_attention_cross_kernel_name", batch, heads, head_dim, tq, tk, bool(backward))
+
+
+def attention_alibi_cross(q: Tensor, kv: Tensor, slopes: Tensor, heads: int, head_dim: int, scale_div: float) -> Tensor:
+    """softmax(Q K^T / scale_div + ALiBi) V with queries ``q`` (B, H*Dh, Tq) and keys / values ``kv`` (B, 2*H*Dh, Tk: K rows,
+    then V rows) -> (B, H*Dh, Tq); the bias is ``-slope_h |i - j|`` on the absolute positions.  fp32, any Tq, Tk >= 1."""
+    lib = _lib.load()
+    _need_gpu(q, kv, slopes)
+    q, kv = _f32c(q), _f32c(kv)
+    b, tq, tk = _cross_shapes("attention_alibi_cross", q, kv, heads, head_dim)
+    out = torch.empty((b, heads * head_dim, tq), dtype=torch.float32, device=q.device)
+    tok = None
+    if _observer is not None:    # work: QK^T and PV, 2 * B * H * Tq * Tk * Dh MACs; bytes: q, kv read once + out written once
+        tok = _observer.begin("other", ("attention_alibi_cross:flash", 4 * (q.numel() + kv.numel() + out.numel()),
+                                        2 * b * heads * tq * tk * head_dim))
+    _lib.check(lib.agx_attention_alibi_cross(_ptr(q), _ptr(kv), _ptr(_f32c(slopes)), _ptr(out), b, heads, head_dim, tq, tk,
+                                             float(scale_div), _stream()), "agx_attention_alibi_cross")
+    if tok is not None:
+        _observer.end(tok)
+    return out
+
+
+def attention_alibi_cross_backward(q: Tensor, kv: Tensor, slopes: Tensor, out: Tensor, dout: Tensor, heads: int, head_dim: int,
+                                   scale_div: float) -> Tuple[Tensor, Tensor]:
+    """(dq, dkv) of ``attention_alibi_cross`` from its inputs, its output ``out`` and ``dout`` (both (B, H*Dh, Tq))."""
+    lib = _lib.load()
+    _need_gpu(q, kv, slopes, out, dout)
+    q, kv, out, dout = _f32c(q), _f32c(kv), _f32c(out), _f32c(dout)
+    b, tq, tk = _cross_shapes("attention_alibi_cross_backward", q, kv, heads, head_dim)
+    if out.shape != q.shape or dout.shape != q.shape:
+        raise AgxError(f"attention_alibi_cross_backward: out {tuple(out.shape)} / dout {tuple(dout.shape)} are not q's {tuple(q.shape)}")
+    dq, dkv = torch.empty_like(q), torch.empty_like(kv)
+    nbytes = int(lib.agx_attention_cross_backward_workspace_bytes(b, heads, tq))
+    ws = _workspace(nbytes, q.device, "agx_attention_cross_backward_workspace_bytes")
+    _lib.check(lib.agx_attention_alibi_cross_backward(_ptr(q), _ptr(kv), _ptr(_f32c(slopes)), _ptr(out), _ptr(dout), _ptr(dq),
+                                                      _ptr(dkv), _ptr(ws), nbytes, b, heads, head_dim, tq, tk, float(scale_div),
+                                                      _stream()), "agx_attention_alibi_cross_backward")
+    return dq, dkv
+
+
 def conv_bwd_data_gelu(desc: ConvDesc, dy: Tensor, packed_bwd: Tensor, pre: Tensor, add: Optional[Tensor] = None) -> Tensor:
     """``conv_bwd_data`` followed (in the epilogue) by the exact-GELU gradient at the pre-activation ``pre``."""
     lib = _lib.load()

@@ -3,15 +3,20 @@ by libagx, plus the bottleneck adapter the reference never shipped.
 
 Mirrors ``networks/transformers.py:7-279`` (class names, constructor arguments,
 ``state_dict()`` keys ``layers.{i}.0.norm.*``, ``layers.{i}.0.W_{q,k,v,o}.weight``,
-``layers.{i}.1.net.{0,1,4}.*``).  Only the branch the reference can actually
-execute is implemented -- self-attention with ALiBi (the learned
-pos-emb and cross-attention branches raise in the reference); ``depth > 1`` is
-build-defined as "every layer uses ALiBi".
+``layers.{i}.1.net.{0,1,4}.*``).  The branches the reference can actually
+execute are implemented: ALiBi self-attention, and ALiBi cross-attention
+(``context_y=``: queries from ``LN(x)``, keys and values from the un-normalised
+second sequence ``y``, transformers.py:159-170 -- it runs in the reference, with
+``Alibi.M`` stored transposed, see ``Alibi``).  The learned pos-emb branch raises
+in the reference and here.  ``depth > 1`` is build-defined as "every
+layer uses ALiBi"; with ``context_y`` layer 0 is the cross-attention layer
+(transformers.py:272-273) and the later ones are self-attention over ``context_x``.
 
 Execution is channel-major: the block works on ``(B, C, T)`` tensors (what the
 encoder emits), every ``Linear`` is a k=1 convolution on the fp32 MFMA conv
 kernel with the activation / residual fused into its epilogue, LayerNorm and
-softmax(QK^T + ALiBi)V are the two dedicated kernels of ``csrc/attention.hip``.
+softmax(QK^T + ALiBi)V are the two dedicated kernels of ``csrc/attention.hip``
+(cross-attention: ``csrc/attention_cross.hip``, fp32 only).
 The ``nn.LayerNorm`` / ``nn.Linear`` children only hold parameters.
 """
 from __future__ import annotations
@@ -30,19 +35,22 @@ Tensor = torch.Tensor
 class Alibi(nn.Module):
     """transformers.py:7-93.  ``M`` is a registered (non-persistent) buffer here,
     so it follows ``.to(device)`` -- the reference leaves it on the CPU.
-    The attention kernel never reads ``M``: it evaluates ``-slope_h * |i - j|`` itself."""
+    The attention kernels never read ``M``: they evaluate ``-slope_h * |i - j|`` themselves.
+
+    With ``context_y`` the reference's ``_create_M`` (:45-77) builds ``M`` as ``(H, context_y, context_x)`` in both of its
+    branches -- the transpose of the ``(context_x, context_y)`` it is cropped as (:92) -- with every entry
+    ``-slope_h * |row - col|``.  The formula is symmetric, so the transposition changes the lengths a call accepts
+    (``Attention.run_bct``) and no value; ``M`` is built here with the reference's shape."""
 
     def __init__(self, context_x, context_y=None, n_heads=8):
         super().__init__()
-        if context_y is not None and context_y != context_x:
-            raise NotImplementedError("cross-attention ALiBi (context_y != context_x) has no HIP kernel")
         self.context_x = context_x
         self.context_y = context_x if context_y is None else context_y
         self.n_heads = n_heads
         n_sequence = torch.arange(start=n_heads, end=0, step=-1)
         self.register_buffer("head_scalars", 2 ** (-8 / n_sequence), persistent=False)  # :38-39
-        idx = torch.arange(context_x, dtype=torch.float32)
-        m = -(idx[:, None] - idx[None, :]).abs()
+        rows, cols = torch.arange(self.context_y, dtype=torch.float32), torch.arange(context_x, dtype=torch.float32)
+        m = -(rows[:, None] - cols[None, :]).abs()
         self.register_buffer("M", m[None, :] * self.head_scalars[:, None, None], persistent=False)
         self.requires_grad_(False)
 
@@ -87,15 +95,17 @@ class _PackedLinear:
         desc = ops.conv_desc(CONV_CAUSAL, b, c_in, self.c_out, t, 1, 1, 1, epilogue)
         return ops.conv_forward(desc, x, packed, bias, res)
 
-    def backward(self, x_in: Tensor, dy: Tensor, pre: Optional[Tensor] = None):
+    def backward(self, x_in: Tensor, dy: Tensor, pre: Optional[Tensor] = None, want_dx: bool = True):
         """Backward of ``forward`` with epilogue 0, on the image that forward packed: (dx, the gradients of the linears'
         parameters in ``parameters()`` order); with ``pre`` the GELU gradient of the layer BELOW (at its pre-activation)
-        is fused into the bwd-data epilogue."""
+        is fused into the bwd-data epilogue.  ``want_dx=False`` skips the backward-data conv (dx is None)."""
         b, c_in, t = x_in.shape
         desc = ops.conv_desc(CONV_CAUSAL, b, c_in, self.c_out, t, 1)
         dw, _, db = ops.conv_bwd_weight(desc, x_in, dy, self.w3d, None, want_bias=self.bias is not None)
-        pk = ops.conv_pack_bwd(desc, self.w3d)
-        dx = ops.conv_bwd_data(desc, dy, pk) if pre is None else ops.conv_bwd_data_gelu(desc, dy, pk, pre)
+        dx = None
+        if want_dx:
+            pk = ops.conv_pack_bwd(desc, self.w3d)
+            dx = ops.conv_bwd_data(desc, dy, pk) if pre is None else ops.conv_bwd_data_gelu(desc, dy, pk, pre)
         dw, grads, row = dw.reshape(self.c_out, c_in), [], 0
         for l in self.linears:
             rows = slice(row, row + l.out_features)
@@ -114,15 +124,14 @@ def _ln_bwd(ln: nn.LayerNorm, x: Tensor, dy: Tensor, add: Tensor):
 
 
 class Attention(nn.Module):
-    """transformers.py:95-191 (pre-LN multi-head self-attention with ALiBi)."""
+    """transformers.py:95-191 (pre-LN multi-head attention with ALiBi).  ``context_y`` makes it a cross-attention layer:
+    ``W_q`` reads ``LN(x)``, ``W_k`` / ``W_v`` (stacked into one projection) read the second sequence ``y`` as given."""
 
     def __init__(self, dim, dim_head=64, n_heads=8, dropout=0., bias=False, context_x=32, context_y=None,
                  has_pos_emb=True, alibi=True):
         super().__init__()
         if not alibi:
             raise NotImplementedError("only the ALiBi branch is defined in the reference (SURVEY 5.1)")
-        if context_y is not None:
-            raise NotImplementedError("cross-attention has no HIP kernel")
         if dropout != 0.:
             raise NotImplementedError("dropout > 0 is training-only and not on the forward path")
         self.dim, self.dim_head, self.n_heads = dim, dim_head, n_heads
@@ -135,10 +144,14 @@ class Attention(nn.Module):
         self.dropout = nn.Dropout(dropout)
         self.alibi = alibi
         self.has_pos_emb = has_pos_emb
-        self.cross_attention = False
+        self.cross_attention = context_y is not None     # :146
         self.context = context_x
-        self.alibi_obj = Alibi(context_x, None, n_heads=n_heads)
-        self._qkv, self._o = _PackedLinear(self.W_q, self.W_k, self.W_v), _PackedLinear(self.W_o)
+        self.alibi_obj = Alibi(context_x, context_y, n_heads=n_heads)
+        self._o = _PackedLinear(self.W_o)
+        if self.cross_attention:     # two projections: W_q on LN(x), W_k / W_v stacked on y
+            self._q, self._kv = _PackedLinear(self.W_q), _PackedLinear(self.W_k, self.W_v)
+        else:
+            self._qkv = _PackedLinear(self.W_q, self.W_k, self.W_v)
         # arithmetic of the QK^T / PV contractions: "fp32" (exact, the reference's) or "bf16" (bf16 MFMA, fp32 accumulate
         # and softmax -- BASELINE config 3); inference only (run_bct: ``keep``)
         self.attention_dtype = "fp32"
@@ -146,10 +159,44 @@ class Attention(nn.Module):
     def _attn(self) -> dict:
         return dict(slopes=self.alibi_obj.head_scalars, heads=self.n_heads, head_dim=self.dim_head, scale_div=self.dim_head ** 0.5)
 
-    def run_bct(self, x: Tensor, residual: Optional[Tensor] = None, keep: Optional[dict] = None) -> Tensor:
-        """(B, dim, T) -> W_o(attn(LN(x))) [+ residual], channel-major.  ``keep`` marks the training forward: the dict
+    def _run_cross_bct(self, x: Tensor, residual: Optional[Tensor], keep: Optional[dict], y: Optional[Tensor]) -> Tensor:
+        """The cross-attention layer: LN1 -> Q projection, KV projection of ``y`` (no LayerNorm, transformers.py:170) ->
+        attention -> W_o (+res).  Lengths: what the reference runs -- its transposed ``M[:, :Tx, :Ty]`` (:92) must broadcast,
+        ``Tx <= context_y and Ty <= context_x`` -- and the intended reading ``Tx <= context_x and Ty <= context_y``; the
+        bias is the same formula in both."""
+        if y is None:
+            raise AgxError("Cross attention requires two inputs: this layer was built with context_y and got no y "
+                           "(the reference asserts here, transformers.py:166)")
+        if y.dim() != 3 or y.shape[0] != x.shape[0] or y.shape[1] != self.dim:
+            raise AgxError(f"cross-attention: y is {tuple(y.shape)}, expected ({x.shape[0]}, {self.dim}, Ty)")
+        cx, cy = self.alibi_obj.context_x, self.alibi_obj.context_y
+        tx, ty = x.shape[-1], y.shape[-1]
+        if not ((tx <= cx and ty <= cy) or (tx <= cy and ty <= cx)):
+            raise AgxError(f"sequence lengths ({tx}, {ty}) exceed the ALiBi contexts ({cx}, {cy}) in both orders "
+                           "(the reference fails here too, transformers.py:88-93)")
+        if self.attention_dtype != "fp32":
+            raise AgxError(f"cross-attention runs in fp32: attention_dtype = {self.attention_dtype!r} has no kernel")
+        if keep is not None and self.dim_head > 128:
+            raise AgxError("Transformer: the attention backward kernels cover head_dim <= 128 "
+                           "(agx_attention_alibi_cross_backward); larger heads have no kernel -- there is no ATen fallback")
+        xn = _ln(self.norm, x)
+        q = self._q.forward(xn)
+        kv = self._kv.forward(y)
+        o = ops.attention_alibi_cross(q, kv, **self._attn())
+        if keep is not None:
+            keep.update(h=x, xn1=xn, q=q, y=y, kv=kv, o=o)
+        return self._o.forward(o, EPI_RESIDUAL if residual is not None else 0, residual)
+
+    def run_bct(self, x: Tensor, residual: Optional[Tensor] = None, keep: Optional[dict] = None,
+                y: Optional[Tensor] = None) -> Tensor:
+        """(B, dim, T) -> W_o(attn(LN(x))) [+ residual], channel-major; a cross-attention layer also takes ``y``
+        (B, dim, Ty).  ``keep`` marks the training forward: the dict
         receives what ``backward_bct`` reads, and the attention arithmetic is fp32 whatever ``attention_dtype`` says
         (the backward kernels recompute P from fp32 scores, and cover head_dim <= 128)."""
+        if self.cross_attention:
+            return self._run_cross_bct(x, residual, keep, y)
+        if y is not None:
+            raise AgxError("a self-attention layer (built without context_y) takes no second sequence y")
         if x.shape[-1] > self.context:
             raise AgxError(f"sequence length {x.shape[-1]} exceeds the ALiBi context {self.context} "
                            "(the reference fails here too, transformers.py:88-93)")
@@ -164,19 +211,26 @@ class Attention(nn.Module):
             keep.update(h=x, xn1=xn, qkv=qkv, o=o)
         return self._o.forward(o, EPI_RESIDUAL if residual is not None else 0, residual)
 
-    def backward_bct(self, kept: dict, g: Tensor):
-        """``g`` = the gradient of ``run_bct(h, residual=h, keep=kept)`` -> (dh, gradients in ``parameters()`` order)."""
+    def backward_bct(self, kept: dict, g: Tensor, want_dy: bool = False):
+        """``g`` = the gradient of ``run_bct(h, residual=h, keep=kept)`` -> (dh, gradients in ``parameters()`` order, dy).
+        ``dy`` is the gradient of a cross-attention layer's second sequence -- the backward-data of the stacked W_k / W_v
+        projection, run only when ``want_dy`` -- and None otherwise."""
         do, g_o = self._o.backward(kept["o"], g)
+        if self.cross_attention:
+            dq, dkv = ops.attention_alibi_cross_backward(kept["q"], kept["kv"], dout=do, out=kept["o"], **self._attn())
+            dxn, g_q = self._q.backward(kept["xn1"], dq)
+            dy, g_kv = self._kv.backward(kept["y"], dkv, want_dx=want_dy)
+            dh, dweight, dbias = _ln_bwd(self.norm, kept["h"], dxn, add=g)
+            return dh, [dweight, dbias] + g_q + g_kv + g_o, dy
         dqkv = ops.attention_alibi_backward(kept["qkv"], dout=do, out=kept["o"], **self._attn())
         dxn, g_qkv = self._qkv.backward(kept["xn1"], dqkv)
         dh, dweight, dbias = _ln_bwd(self.norm, kept["h"], dxn, add=g)
-        return dh, [dweight, dbias] + g_qkv + g_o
+        return dh, [dweight, dbias] + g_qkv + g_o, None
 
     def forward(self, x: Tensor, y=None) -> Tensor:
-        """Reference layout: (B, T, dim) -> (B, T, dim)."""
-        if y is not None:
-            raise NotImplementedError("cross-attention has no HIP kernel")
-        return self.run_bct(x.transpose(1, 2).contiguous()).transpose(1, 2).contiguous()
+        """Reference layout: (B, T, dim) [, (B, Ty, dim)] -> (B, T, dim)."""
+        y = None if y is None else y.transpose(1, 2).contiguous()
+        return self.run_bct(x.transpose(1, 2).contiguous(), y=y).transpose(1, 2).contiguous()
 
 
 class FeedForward(nn.Module):
@@ -214,29 +268,33 @@ class FeedForward(nn.Module):
 
 class _TransformerNative(torch.autograd.Function):
     """Transformer forward + hand-written backward on the HIP kernels: k=1 conv backward for every Linear,
-    ``agx_attention_alibi_backward``, ``agx_layernorm_ct_backward`` (residual adds fused as ``add``), the GELU
-    gradient in a bwd-data epilogue.  Every layer, the first included, computes its input gradient."""
+    ``agx_attention_alibi_backward`` / ``agx_attention_alibi_cross_backward``, ``agx_layernorm_ct_backward`` (residual
+    adds fused as ``add``), the GELU gradient in a bwd-data epilogue.  Every layer, the first included, computes its
+    input gradient; ``y`` (None without cross-attention) is a differentiable input too: its gradient is the backward-data
+    of the cross layer's stacked W_k / W_v projection."""
 
     @staticmethod
-    def forward(ctx, tf, x: Tensor, *params: Tensor):
+    def forward(ctx, tf, x: Tensor, y: Optional[Tensor], *params: Tensor):
         keep = []
         with torch.no_grad():
-            y = tf._hip_bct(x.detach(), keep)
+            out = tf._hip_bct(x.detach(), keep, None if y is None else y.detach())
         ctx.tf, ctx.names = tf, [(li, name) for li, kept in enumerate(keep) for name in kept]
         ctx.save_for_backward(*[t for kept in keep for t in kept.values()])
-        return y
+        return out
 
     @staticmethod
     def backward(ctx, g: Tensor):
         keep = [{} for _ in ctx.tf.layers]
         for (li, name), t in zip(ctx.names, ctx.saved_tensors):
             keep[li][name] = t
-        g, grads = g.contiguous(), []
+        g, grads, gy = g.contiguous(), [], None
         for (attention, ff), kept in zip(reversed(ctx.tf.layers), reversed(keep)):
             g, g_ff = ff.backward_bct(kept, g)              # x2 = x1 + W2 gelu(W1 LN2(x1) + b1) + b2
-            g, g_attention = attention.backward_bct(kept, g)   # x1 = h + W_o attn(W_qkv LN1(h))
+            # x1 = h + W_o attn(W_qkv LN1(h))  (cross: W_q LN1(h), W_kv y -- dy only when y asks for a gradient)
+            g, g_attention, dy = attention.backward_bct(kept, g, want_dy=ctx.needs_input_grad[2])
             grads = g_attention + g_ff + grads              # the order of Transformer.parameters()
-        return (None, g if ctx.needs_input_grad[1] else None, *grads)
+            gy = dy if attention.cross_attention else gy
+        return (None, g if ctx.needs_input_grad[1] else None, gy, *grads)
 
 
 class Transformer(nn.Module):
@@ -245,38 +303,40 @@ class Transformer(nn.Module):
     def __init__(self, dim, depth=1, heads=8, head_dim=64, dropout=0., context_x=32, context_y=None,
                  has_pos_emb=True, alibi=True):
         super().__init__()
-        if context_y is not None:
-            raise NotImplementedError("cross-attention has no HIP kernel")
-        self.cross_attention = False
+        self.cross_attention = context_y is not None     # :253-256
         self.layers = nn.ModuleList([
             nn.ModuleList([Attention(dim, n_heads=heads, dim_head=head_dim, dropout=dropout, context_x=context_x,
+                                     context_y=context_y if i == 0 else None,     # :272-273: the first layer only
                                      has_pos_emb=has_pos_emb, alibi=alibi),
                            FeedForward(dim, dim, dropout=dropout)])
-            for _ in range(depth)])
+            for i in range(depth)])
 
-    def _hip_bct(self, x: Tensor, keep: Optional[list] = None) -> Tensor:
+    def _hip_bct(self, x: Tensor, keep: Optional[list] = None, y: Optional[Tensor] = None) -> Tensor:
         """The one forward walk, LN1 -> QKV -> attention -> W_o (+res) -> LN2 -> FFN-in (GELU) -> FFN-out (+res) per layer:
-        7 launches, both residual adds fused into the W_o / FFN-out conv epilogues.  ``keep``: the training forward
+        7 launches, both residual adds fused into the W_o / FFN-out conv epilogues (a cross-attention layer: 8, a Q and a
+        KV projection in place of the QKV one).  ``keep``: the training forward
         (``Attention.run_bct``) -- the list receives one dict of named intermediates per layer."""
+        if (y is not None) != self.cross_attention:
+            raise AgxError("Cross attention requires two inputs: this Transformer was built with context_y and got no y"
+                           if y is None else "this Transformer was built without context_y and takes no second sequence y")
         for attention, ff in self.layers:
             kept = None if keep is None else {}
-            x = attention.run_bct(x, x, kept)
+            x = attention.run_bct(x, x, kept, y if attention.cross_attention else None)
             x = ff.run_bct(x, x, kept)
             if keep is not None:
                 keep.append(kept)
         return x
 
-    def run_bct(self, x: Tensor) -> Tensor:
-        """Channel-major (B, dim, T) in and out.  With autograd on, the backward runs on the HIP kernels too
-        (_TransformerNative)."""
-        if needs_grad(x, self):
-            return _TransformerNative.apply(self, x, *list(self.parameters()))
-        return self._hip_bct(x)
+    def run_bct(self, x: Tensor, y: Optional[Tensor] = None) -> Tensor:
+        """Channel-major (B, dim, T) in and out; ``y`` (B, dim, Ty) is the cross-attention layer's second sequence.  With
+        autograd on, the backward runs on the HIP kernels too (_TransformerNative)."""
+        if needs_grad(x, self) or (y is not None and torch.is_grad_enabled() and y.requires_grad):
+            return _TransformerNative.apply(self, x, y, *list(self.parameters()))
+        return self._hip_bct(x, None, y)
 
     def forward(self, x: Tensor, y=None) -> Tensor:
-        if y is not None:
-            raise NotImplementedError("cross-attention has no HIP kernel")
-        return self.run_bct(x.transpose(1, 2).contiguous()).transpose(1, 2).contiguous()
+        y = None if y is None else y.transpose(1, 2).contiguous()
+        return self.run_bct(x.transpose(1, 2).contiguous(), y).transpose(1, 2).contiguous()
 
 
 class TransformerBottleneck(nn.Module):
@@ -294,6 +354,9 @@ class TransformerBottleneck(nn.Module):
         self.use_som = False                    # utils.py:239
 
     def quantize_bcl(self, x: Tensor, codebook_n=None, update_codebook=False, prioritize_early=False):
+        if self.transformer.cross_attention:
+            raise AgxError("TransformerBottleneck: the transformer has a cross-attention layer (context_y) and the quantiser call "
+                           "contract of CausalVQAE.forward carries no second sequence y -- call Transformer.forward(x, y) directly")
         y = self.transformer.run_bct(x)
         return y, None, torch.zeros((), dtype=torch.float32, device=x.device)
 

@@ -26,7 +26,7 @@
 extern "C" {
 #endif
 
-#define AGX_VERSION 122 /* 122: agx_attention_kernel_name, agx_attention_backward_kernel_name (which attention kernel the forward / backward entry points run); 121: agx_conv_bwd_weight_kernel_name, agx_conv2d_bwd_weight_kernel_name, agx_conv_grouped_bwd_weight_kernel_name (kernel, operand copy, contraction slices and items of the weight-gradient ops); 120: activation planes (agx_planes_bytes / agx_planes_split / agx_conv_forward_planes / agx_conv_planes_supported): pre-split bf16x3 input of the decoder's resampling convs; conv_p one-phase geometries (k = 1, "same" k = 11 / 3) with GELU / residual epilogues; 119: agx_rvq_verify_counts + knob rvq_verify (debug: the full defining search beside the fast path); agx_rvq_debug_stamps and the b3_dbg 7/8/9 bound knobs exist in the probe build only; 118: agx_feature_means(_backward) (the feature-matching pair in one pass); 117: agx_rvq_debug_stamps (diagnostic); 116: agx_multires_backward, agx_layernorm_ct one-pass kernel (same signature); agx_rvq_forward (legacy form) needs the workspace of agx_rvq_workspace_bytes since 114; 115: agx_rvq_ema_stats, agx_conv2d_bwd_data_kernel_name; 114: agx_attention_alibi_backward_ex (any T), agx_rvq_forward_ex; 113: tile images (resblock_p / conv_p), agx_attention_alibi_ex, agx_sizeof_*; 0.1.1: agx_conv_desc gained groups / padding (zero = old behaviour); 111: resample, conv2d column split */
+#define AGX_VERSION 122 /* still 122 with the cross-attention entry points (agx_attention_alibi_cross, agx_attention_alibi_cross_backward, agx_attention_cross_backward_workspace_bytes, agx_attention_cross_kernel_name): the ABI only grew -- no existing symbol, struct or meaning changed, so a binding made for 122 keeps working and the number stays; 122: agx_attention_kernel_name, agx_attention_backward_kernel_name (which attention kernel the forward / backward entry points run); 121: agx_conv_bwd_weight_kernel_name, agx_conv2d_bwd_weight_kernel_name, agx_conv_grouped_bwd_weight_kernel_name (kernel, operand copy, contraction slices and items of the weight-gradient ops); 120: activation planes (agx_planes_bytes / agx_planes_split / agx_conv_forward_planes / agx_conv_planes_supported): pre-split bf16x3 input of the decoder's resampling convs; conv_p one-phase geometries (k = 1, "same" k = 11 / 3) with GELU / residual epilogues; 119: agx_rvq_verify_counts + knob rvq_verify (debug: the full defining search beside the fast path); agx_rvq_debug_stamps and the b3_dbg 7/8/9 bound knobs exist in the probe build only; 118: agx_feature_means(_backward) (the feature-matching pair in one pass); 117: agx_rvq_debug_stamps (diagnostic); 116: agx_multires_backward, agx_layernorm_ct one-pass kernel (same signature); agx_rvq_forward (legacy form) needs the workspace of agx_rvq_workspace_bytes since 114; 115: agx_rvq_ema_stats, agx_conv2d_bwd_data_kernel_name; 114: agx_attention_alibi_backward_ex (any T), agx_rvq_forward_ex; 113: tile images (resblock_p / conv_p), agx_attention_alibi_ex, agx_sizeof_*; 0.1.1: agx_conv_desc gained groups / padding (zero = old behaviour); 111: resample, conv2d column split */
 
 #define AGX_OK 0
 #define AGX_ERR_BAD_SHAPE (-1)
@@ -358,6 +358,30 @@ int agx_attention_alibi_ex(const float *qkv, const float *slopes, float *out, in
  * refuses.  The name is truncated to buf_len - 1 characters. */
 int agx_attention_kernel_name(int32_t batch, int32_t heads, int32_t head_dim, int32_t t, int32_t precision, int32_t flash,
                               char *buf, size_t buf_len);
+
+/* Cross-attention (transformers.py:165-188 with `cross_attention`): queries of one sequence, keys and values of another,
+ *     out[b,h,:,i] = sum_j softmax_j( q_i . k_j / scale_div - slopes[h] * |i - j| ) v_j,   j in [0, tk)
+ * with i and j the absolute positions in their own sequences (Alibi._create_M :45-77; the reference stores the bias
+ * transposed, (H, context_y, context_x), which changes no value: the formula is symmetric).  q is (B, H*Dh, tq); kv is
+ * (B, 2*H*Dh, tk), k rows [0, H*Dh), v rows [H*Dh, 2*H*Dh), head-major inside each; out is (B, H*Dh, tq).  fp32-input
+ * MFMA for both contractions, online softmax over 64-key blocks (csrc/attention_cross.hip), any tq >= 1 and tk >= 1,
+ * Dh <= 128 (AGX_ERR_UNSUPPORTED beyond).  batch, heads, tq or tk <= 0: returns AGX_OK and launches nothing. */
+int agx_attention_alibi_cross(const float *q, const float *kv, const float *slopes, float *out, int32_t batch, int32_t heads,
+                              int32_t head_dim, int32_t tq, int32_t tk, float scale_div, void *stream);
+/* Backward of agx_attention_alibi_cross: dq (B, H*Dh, tq) and dkv (B, 2*H*Dh, tk) from q, kv, the forward's `out` and dout
+ * (B, H*Dh, tq).  Three deterministic kernels (row statistics over tq, dQ per 16-query block, dK / dV per 64-key block; P is
+ * recomputed from the row statistics, no atomics): two calls on the same inputs agree bit for bit.  workspace: lse + delta
+ * = 2 * batch * heads * tq floats = agx_attention_cross_backward_workspace_bytes() bytes (AGX_ERR_WORKSPACE when shorter);
+ * every float of it is written.  Empty shapes as above. */
+size_t agx_attention_cross_backward_workspace_bytes(int32_t batch, int32_t heads, int32_t tq);
+int agx_attention_alibi_cross_backward(const float *q, const float *kv, const float *slopes, const float *out, const float *dout,
+                                       float *dq, float *dkv, float *workspace, size_t workspace_bytes, int32_t batch,
+                                       int32_t heads, int32_t head_dim, int32_t tq, int32_t tk, float scale_div, void *stream);
+/* Host-only: the kernel agx_attention_alibi_cross runs for this shape, "attention_cross<DVT>" (DVT = 1 / 2 / 4 32-row tiles of
+ * the head dim), with backward != 0 the three kernels of agx_attention_alibi_cross_backward, "none" for an empty shape, or
+ * the launcher's refusal (code and message).  The name is truncated to buf_len - 1 characters. */
+int agx_attention_cross_kernel_name(int32_t batch, int32_t heads, int32_t head_dim, int32_t tq, int32_t tk, int32_t backward,
+                                    char *buf, size_t buf_len);
 
 /* ------------------------------------------------------------------------- *
  * Wavelet / multiresolution layers (networks/wavelets.py)                     *
