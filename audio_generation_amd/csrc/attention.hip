@@ -25,12 +25,14 @@ __global__ __launch_bounds__(256) void layernorm_ct_kernel(const float *__restri
                                                            const float *__restrict__ weight,
                                                            const float *__restrict__ bias,
                                                            float *__restrict__ y, int C, int T, float eps) {
-    __shared__ float part[4][64];
+    __shared__ float part[4][64], parts[4][64];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int t = blockIdx.x * 64 + lane;
     const int tc = min(t, T - 1);
     const float *xb = x + size_t(blockIdx.y) * C * T + tc;
     float *yb = y + size_t(blockIdx.y) * C * T + tc;
+    // `mean` is a plain fp32 sum: with a large common offset it is some ulp of the offset away from the column's mean.  The
+    // second pass sums the residuals x - mean too; their mean `corr` is that error (the corrected two-pass algorithm).
 
     float s = 0.f;
     for (int c = wave; c < C; c += 4) s += xb[size_t(c) * T];
@@ -38,19 +40,22 @@ __global__ __launch_bounds__(256) void layernorm_ct_kernel(const float *__restri
     __syncthreads();
     const float mean = ((part[0][lane] + part[1][lane]) + (part[2][lane] + part[3][lane])) / float(C);
     __syncthreads();
-    float v = 0.f;
+    float v = 0.f, r = 0.f;
     for (int c = wave; c < C; c += 4) {
         const float d = xb[size_t(c) * T] - mean;
+        r += d;
         v = fmaf(d, d, v);
     }
     part[wave][lane] = v;
+    parts[wave][lane] = r;
     __syncthreads();
-    const float var = ((part[0][lane] + part[1][lane]) + (part[2][lane] + part[3][lane])) / float(C);
-    const float rstd = 1.f / sqrtf(var + eps);
+    const float corr = ((parts[0][lane] + parts[1][lane]) + (parts[2][lane] + parts[3][lane])) / float(C);
+    const float var = ((part[0][lane] + part[1][lane]) + (part[2][lane] + part[3][lane])) / float(C) - corr * corr;
+    const float rstd = 1.f / sqrtf(fmaxf(var, 0.f) + eps);
     if (t >= T) return;
     for (int c = wave; c < C; c += 4) {
         const float w = weight ? weight[c] : 1.f, b = bias ? bias[c] : 0.f;
-        yb[size_t(c) * T] = (xb[size_t(c) * T] - mean) * rstd * w + b;
+        yb[size_t(c) * T] = ((xb[size_t(c) * T] - mean) - corr) * rstd * w + b;
     }
 }
 
@@ -63,7 +68,7 @@ __global__ __launch_bounds__(TS * NG) void layernorm_ct_regs_kernel(const float 
                                                                     const float *__restrict__ weight,
                                                                     const float *__restrict__ bias,
                                                                     float *__restrict__ y, int C, int T, float eps) {
-    __shared__ float part[NG][TS + 1];
+    __shared__ float part[NG][TS + 1], parts[NG][TS + 1];
     const int tl = threadIdx.x % TS, g = threadIdx.x / TS;
     const int t = blockIdx.x * TS + tl;
     const int tc = min(t, T - 1);
@@ -84,18 +89,26 @@ __global__ __launch_bounds__(TS * NG) void layernorm_ct_regs_kernel(const float 
     for (int j = 0; j < NG; ++j) tot += part[j][tl];
     const float mean = tot / float(C);
     __syncthreads();
-    float q = 0.f;
+    // `mean` is a plain fp32 sum: with a large common offset it is some ulp of the offset away from the column's mean.  The
+    // residuals v - mean are summed with their squares; their mean `corr` is that error (the corrected two-pass algorithm).
+    float q = 0.f, r = 0.f;
 #pragma unroll
     for (int k = 0; k < CPT; ++k) {
         const float d = (g + NG * k < C) ? v[k] - mean : 0.f;
+        r += d;
         q = fmaf(d, d, q);
     }
     part[g][tl] = q;
+    parts[g][tl] = r;
     __syncthreads();
-    float var = 0.f;
+    float var = 0.f, corr = 0.f;
 #pragma unroll
-    for (int j = 0; j < NG; ++j) var += part[j][tl];
-    const float rstd = 1.f / sqrtf(var / float(C) + eps);
+    for (int j = 0; j < NG; ++j) {
+        var += part[j][tl];
+        corr += parts[j][tl];
+    }
+    corr /= float(C);
+    const float rstd = 1.f / sqrtf(fmaxf(var / float(C) - corr * corr, 0.f) + eps);
     if (t >= T) return;
     float *yb = y + size_t(blockIdx.y) * C * T + t;
 #pragma unroll
@@ -103,7 +116,7 @@ __global__ __launch_bounds__(TS * NG) void layernorm_ct_regs_kernel(const float 
         const int c = g + NG * k;
         if (c < C) {
             const float w = weight ? weight[c] : 1.f, b = bias ? bias[c] : 0.f;
-            yb[size_t(c) * T] = (v[k] - mean) * rstd * w + b;
+            yb[size_t(c) * T] = ((v[k] - mean) - corr) * rstd * w + b;
         }
     }
 }
@@ -263,16 +276,18 @@ __global__ __launch_bounds__(256) void layernorm_ct_bwd_kernel(const float *__re
     float s = 0.f;
     for (int c = wave; c < C; c += 4) s += x[base + size_t(c) * T];
     const float mean = colsum(s) / float(C);
-    float v = 0.f;
+    float v = 0.f, r = 0.f;       // residuals and their squares: `corr` is the error of the plain fp32 `mean`, as in the forward
     for (int c = wave; c < C; c += 4) {
         const float d = x[base + size_t(c) * T] - mean;
+        r += d;
         v = fmaf(d, d, v);
     }
-    const float rstd = 1.f / sqrtf(colsum(v) / float(C) + eps);
+    const float corr = colsum(r) / float(C);
+    const float rstd = 1.f / sqrtf(fmaxf(colsum(v) / float(C) - corr * corr, 0.f) + eps);
     const int blk = blockIdx.y * gridDim.x + blockIdx.x, nblk = gridDim.x * gridDim.y;
     float s1 = 0.f, s2 = 0.f;
     for (int c = wave; c < C; c += 4) {
-        const float xh = (x[base + size_t(c) * T] - mean) * rstd;
+        const float xh = ((x[base + size_t(c) * T] - mean) - corr) * rstd;
         const float g = live ? dy[base + size_t(c) * T] : 0.f;
         const float dxh = g * (weight ? weight[c] : 1.f);
         s1 += dxh;
@@ -292,7 +307,7 @@ __global__ __launch_bounds__(256) void layernorm_ct_bwd_kernel(const float *__re
     if (!live) return;
     for (int c = wave; c < C; c += 4) {
         const size_t e = base + size_t(c) * T;
-        const float xh = (x[e] - mean) * rstd;
+        const float xh = ((x[e] - mean) - corr) * rstd;
         const float dxh = dy[e] * (weight ? weight[c] : 1.f);
         dx[e] = rstd * (dxh - m1 - xh * m2) + (add ? add[e] : 0.f);
     }

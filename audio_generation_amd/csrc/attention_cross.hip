@@ -154,7 +154,22 @@ __global__ __launch_bounds__(256) void attention_cross_kernel(const float *__res
 constexpr int AC_QB = 16;    // queries per block
 constexpr int AC_KB = 64;    // keys per block
 
-// one workgroup per (query block, head, item): lse and delta of its 16 queries
+// The logit of (query i, key j), rounded the same way in all three kernels: the product feeds an explicit fmaf, so no
+// contraction can differ between them.  lse is built from these values, and P = exp(logit - lse) is exactly 1 on a row that one
+// key holds alone; a logit near 100 rounded differently in two kernels would put 1e-5 of relative error into P instead.
+// The bias is taken relative to the query's nearest key, max(0, i - (Tk - 1)) positions away: a constant of the row, which the
+// softmax does not see, subtracted exactly.  A query far beyond the last key (Tq > Tk) with a steep slope would otherwise
+// have all its logits near -slope (i - Tk), and lse = m + log l, rounded to an ulp of that magnitude, would lose log l.
+// The workspace's lse is that of these relative logits.  (The self-attention twin has no such rows: i <= T - 1.)
+static __device__ __forceinline__ float attn_cross_bwd_logit(float s, float inv, int i, int j, int Tk, float slope) {
+    return fmaf(-float(abs(i - j) - max(0, i - (Tk - 1))), slope, s * inv);
+}
+
+// one workgroup per (query block, head, item): lse and delta of its 16 queries.  delta_i = sum_j P_ij dP_ij is summed online
+// next to l, from dP values formed exactly as the dq and dkv kernels form them (the same fmaf chain over d), not taken as
+// sum_d dO[d,i] O[d,i] from the forward's output: where one key holds all of a row's weight, dP_ij == delta_i must cancel
+// to zero in dS = P (dP - delta), and two differently rounded dot products leave a residue that K / scale multiplies into dQ.
+// (`out` stays in the signature for the callers; it is not read.)
 __global__ __launch_bounds__(256) void attn_cross_bwd_stats_kernel(const float *__restrict__ q, const float *__restrict__ kv,
                                                                    const float *__restrict__ slopes, const float *__restrict__ out,
                                                                    const float *__restrict__ dout, float *__restrict__ lse,
@@ -162,32 +177,41 @@ __global__ __launch_bounds__(256) void attn_cross_bwd_stats_kernel(const float *
                                                                    float scale_div) {
     extern __shared__ __attribute__((aligned(16))) float sm[];
     float *Qs = sm;                 // [Dh][QB]
-    float *Ks = Qs + Dh * AC_QB;    // [Dh][KB]
-    float *Ss = Ks + Dh * AC_KB;    // [QB][KB]
-    __shared__ float red[AC_QB][16];
+    float *Os = Qs + Dh * AC_QB;    // [Dh][QB]  dO
+    float *Ks = Os + Dh * AC_QB;    // [Dh][KB]
+    float *Vs = Ks + Dh * AC_KB;    // [Dh][KB]
+    float *Ss = Vs + Dh * AC_KB;    // [QB][KB]
+    float *Ds = Ss + AC_QB * AC_KB;  // [QB][KB]  dP
+    __shared__ float red[AC_QB][16], redd[AC_QB][16];
     const int tid = threadIdx.x, h = blockIdx.y, b = blockIdx.z, i0 = blockIdx.x * AC_QB;
     const int HD = H * Dh;
-    const float *qg = q + (size_t(b) * HD + h * Dh) * Tq, *kg = kv + (size_t(b) * 2 * HD + h * Dh) * Tk;
-    const float *og = out + (size_t(b) * HD + h * Dh) * Tq, *dg = dout + (size_t(b) * HD + h * Dh) * Tq;
+    const float *qg = q + (size_t(b) * HD + h * Dh) * Tq, *kg = kv + (size_t(b) * 2 * HD + h * Dh) * Tk, *vg = kg + size_t(HD) * Tk;
+    const float *dg = dout + (size_t(b) * HD + h * Dh) * Tq;
     const float slope = slopes[h], inv = 1.f / scale_div;
     for (int e = tid; e < Dh * AC_QB; e += 256) {
-        const int d = e / AC_QB, qi = e - d * AC_QB;
-        Qs[e] = qg[size_t(d) * Tq + min(i0 + qi, Tq - 1)];
+        const int d = e / AC_QB, qi = e - d * AC_QB, i = min(i0 + qi, Tq - 1);
+        Qs[e] = qg[size_t(d) * Tq + i];
+        Os[e] = dg[size_t(d) * Tq + i];
     }
     const int rq = tid / 16, rl = tid % 16;   // 16 threads per query row
-    float m = -3.0e38f, l = 0.f;
+    float m = -3.0e38f, l = 0.f, dl = 0.f;
     for (int j0 = 0; j0 < Tk; j0 += AC_KB) {
         __syncthreads();
         for (int e = tid; e < Dh * AC_KB; e += 256) {
-            const int d = e / AC_KB, j = e - d * AC_KB;
-            Ks[e] = kg[size_t(d) * Tk + min(j0 + j, Tk - 1)];
+            const int d = e / AC_KB, j = e - d * AC_KB, jc = min(j0 + j, Tk - 1);
+            Ks[e] = kg[size_t(d) * Tk + jc];
+            Vs[e] = vg[size_t(d) * Tk + jc];
         }
         __syncthreads();
         for (int e = tid; e < AC_QB * AC_KB; e += 256) {
             const int qi = e / AC_KB, j = e - qi * AC_KB;
-            float s = 0.f;
-            for (int d = 0; d < Dh; ++d) s = fmaf(Qs[d * AC_QB + qi], Ks[d * AC_KB + j], s);
-            Ss[e] = (j0 + j < Tk) ? s * inv - fabsf(float(i0 + qi - (j0 + j))) * slope : -3.0e38f;
+            float s = 0.f, dp = 0.f;
+            for (int d = 0; d < Dh; ++d) {
+                s = fmaf(Qs[d * AC_QB + qi], Ks[d * AC_KB + j], s);
+                dp = fmaf(Os[d * AC_QB + qi], Vs[d * AC_KB + j], dp);
+            }
+            Ds[e] = dp;
+            Ss[e] = (j0 + j < Tk) ? attn_cross_bwd_logit(s, inv, i0 + qi, j0 + j, Tk, slope) : -3.0e38f;
         }
         __syncthreads();
         float bm = -3.0e38f;
@@ -197,29 +221,30 @@ __global__ __launch_bounds__(256) void attn_cross_bwd_stats_kernel(const float *
         bm = red[rq][0];
         for (int k = 1; k < 16; ++k) bm = fmaxf(bm, red[rq][k]);
         const float mn = fmaxf(m, bm);
-        float bs = 0.f;
-        for (int j = rl; j < AC_KB; j += 16) bs += expf(Ss[rq * AC_KB + j] - mn);
+        float bs = 0.f, bd = 0.f;
+        for (int j = rl; j < AC_KB; j += 16) {
+            const float p = expf(Ss[rq * AC_KB + j] - mn);   // 0 for a padded key
+            bs += p;
+            bd = fmaf(p, Ds[rq * AC_KB + j], bd);
+        }
         __syncthreads();
         red[rq][rl] = bs;
+        redd[rq][rl] = bd;
         __syncthreads();
-        bs = 0.f;
-        for (int k = 0; k < 16; ++k) bs += red[rq][k];
-        l = l * expf(m - mn) + bs;
+        bs = bd = 0.f;
+        for (int k = 0; k < 16; ++k) {
+            bs += red[rq][k];
+            bd += redd[rq][k];
+        }
+        const float alpha = expf(m - mn);
+        l = l * alpha + bs;
+        dl = dl * alpha + bd;
         m = mn;
     }
-    // delta_i = sum_d dO[d,i] O[d,i]
-    float dl = 0.f;
-    const int iq = min(i0 + rq, Tq - 1);
-    for (int d = rl; d < Dh; d += 16) dl = fmaf(dg[size_t(d) * Tq + iq], og[size_t(d) * Tq + iq], dl);
-    __syncthreads();
-    red[rq][rl] = dl;
-    __syncthreads();
     if (rl == 0 && i0 + rq < Tq) {
-        float s = 0.f;
-        for (int k = 0; k < 16; ++k) s += red[rq][k];
         const size_t o = (size_t(b) * H + h) * Tq + i0 + rq;
         lse[o] = m + logf(l);
-        delta[o] = s;
+        delta[o] = dl / l;
     }
 }
 
@@ -269,7 +294,7 @@ __global__ __launch_bounds__(256) void attn_cross_bwd_dq_kernel(const float *__r
             }
             float ds = 0.f;
             if (i < Tq && j0 + j < Tk) {
-                const float pn = expf(s * inv - fabsf(float(i - (j0 + j))) * slope - lse[so + i]);
+                const float pn = expf(attn_cross_bwd_logit(s, inv, i, j0 + j, Tk, slope) - lse[so + i]);
                 ds = pn * (dp - delta[so + i]) * inv;
             }
             Ss[e] = ds;
@@ -343,7 +368,7 @@ __global__ __launch_bounds__(256) void attn_cross_bwd_dkv_kernel(const float *__
             }
             float pn = 0.f, ds = 0.f;
             if (i < Tq && j0 + j < Tk) {
-                pn = expf(s * inv - fabsf(float(i - (j0 + j))) * slope - lse[so + i]);
+                pn = expf(attn_cross_bwd_logit(s, inv, i, j0 + j, Tk, slope) - lse[so + i]);
                 ds = pn * (dp - delta[so + i]) * inv;
             }
             Ps[e] = pn;
@@ -421,7 +446,7 @@ static int launch_attention_cross_backward(const float *q, const float *kv, cons
                                            float scale_div, hipStream_t st) {
     float *lse = workspace, *delta = workspace + size_t(B) * H * Tq;
     const dim3 gq(ceil_div(Tq, AC_QB), H, B), gk(ceil_div(Tk, AC_KB), H, B);
-    const size_t l_stats = size_t(Dh * AC_QB + Dh * AC_KB + AC_QB * AC_KB) * sizeof(float);
+    const size_t l_stats = size_t(2 * Dh * AC_QB + 2 * Dh * AC_KB + 2 * AC_QB * AC_KB) * sizeof(float);
     const size_t l_dq = size_t(2 * Dh * AC_QB + 2 * Dh * AC_KB + AC_QB * AC_KB) * sizeof(float);
     const size_t l_dkv = size_t(2 * Dh * AC_KB + 2 * Dh * AC_QB + 2 * AC_QB * AC_KB) * sizeof(float);
     static DeviceOnce once[3];

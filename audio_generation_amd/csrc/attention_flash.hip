@@ -412,7 +412,7 @@ const AttnRow *attn_bf16_lds_rows() { return kAttnBf16LdsRows; }
 // Backward for any T (and head_dim <= 128): attention.hip's backward holds K and V of one (head, item) in LDS and the
 // dK / dV accumulators in registers -- T <= 256, head_dim <= 64.  Beyond that the work is split the flash way, in
 // three deterministic VALU kernels (no atomics; a bottleneck of 1125 frames is 10 GFLOP per batch of 32):
-//   stats   lse_i = log sum_j exp(s_ij)  (online over key blocks),  delta_i = sum_d dO[d,i] O[d,i]  (= sum_j P_ij dP_ij)
+//   stats   lse_i = log sum_j exp(s_ij)  and  delta_i = sum_j P_ij dP_ij  (both online over key blocks)
 //   dq      per 16-query block, loop over key blocks:  P = exp(s - lse), dP = dO^T V, dS = P (dP - delta),  dQ += dS K^T / scale
 //   dkv     per 64-key block, loop over query blocks:  dK += dS^T Q / scale,  dV += P^T dO   (accumulators in registers)
 // s_ij = q_i . k_j / scale - slope |i - j|  (transformers.py:177-183).
@@ -423,39 +423,59 @@ namespace agx {
 constexpr int AB_QB = 16;    // queries per block
 constexpr int AB_KB = 64;    // keys per block
 
-// one workgroup per (query block, head, item): lse and delta of its 16 queries
+// The logit of (query i, key j), rounded the same way in all three kernels: the product feeds an explicit fmaf, so no
+// contraction can differ between them.  lse is built from these values, and P = exp(logit - lse) is exactly 1 on a row that one
+// key holds alone; a logit near 100 rounded differently in two kernels would put 1e-5 of relative error into P instead.
+static __device__ __forceinline__ float attn_bwd_logit(float s, float inv, int dist, float slope) {
+    return fmaf(-fabsf(float(dist)), slope, s * inv);
+}
+
+// one workgroup per (query block, head, item): lse and delta of its 16 queries.  delta_i = sum_j P_ij dP_ij is summed online
+// next to l, from dP values formed exactly as the dq and dkv kernels form them (the same fmaf chain over d), not taken as
+// sum_d dO[d,i] O[d,i] from the forward's output: where one key holds all of a row's weight, dP_ij == delta_i must cancel
+// to zero in dS = P (dP - delta), and two differently rounded dot products leave a residue that K / scale multiplies into dQ.
+// (`out` stays in the signature for the callers; it is not read.)
 __global__ __launch_bounds__(256) void attn_bwd_stats_kernel(const float *__restrict__ qkv, const float *__restrict__ slopes,
                                                              const float *__restrict__ out, const float *__restrict__ dout,
                                                              float *__restrict__ lse, float *__restrict__ delta, int H, int Dh,
                                                              int T, float scale_div) {
     extern __shared__ __attribute__((aligned(16))) float sm[];
     float *Qs = sm;                 // [Dh][QB]
-    float *Ks = Qs + Dh * AB_QB;    // [Dh][KB]
-    float *Ss = Ks + Dh * AB_KB;    // [QB][KB]
-    __shared__ float red[AB_QB][16];
+    float *Os = Qs + Dh * AB_QB;    // [Dh][QB]  dO
+    float *Ks = Os + Dh * AB_QB;    // [Dh][KB]
+    float *Vs = Ks + Dh * AB_KB;    // [Dh][KB]
+    float *Ss = Vs + Dh * AB_KB;    // [QB][KB]
+    float *Ds = Ss + AB_QB * AB_KB;  // [QB][KB]  dP
+    __shared__ float red[AB_QB][16], redd[AB_QB][16];
     const int tid = threadIdx.x, h = blockIdx.y, b = blockIdx.z, i0 = blockIdx.x * AB_QB;
     const int HD = H * Dh;
-    const float *qg = qkv + (size_t(b) * 3 * HD + h * Dh) * T, *kg = qg + size_t(HD) * T;
-    const float *og = out + (size_t(b) * HD + h * Dh) * T, *dg = dout + (size_t(b) * HD + h * Dh) * T;
+    const float *qg = qkv + (size_t(b) * 3 * HD + h * Dh) * T, *kg = qg + size_t(HD) * T, *vg = kg + size_t(HD) * T;
+    const float *dg = dout + (size_t(b) * HD + h * Dh) * T;
     const float slope = slopes[h], inv = 1.f / scale_div;
     for (int e = tid; e < Dh * AB_QB; e += 256) {
-        const int d = e / AB_QB, q = e - d * AB_QB;
-        Qs[e] = qg[size_t(d) * T + min(i0 + q, T - 1)];
+        const int d = e / AB_QB, q = e - d * AB_QB, i = min(i0 + q, T - 1);
+        Qs[e] = qg[size_t(d) * T + i];
+        Os[e] = dg[size_t(d) * T + i];
     }
     const int rq = tid / 16, rl = tid % 16;   // 16 threads per query row
-    float m = -3.0e38f, l = 0.f;
+    float m = -3.0e38f, l = 0.f, dl = 0.f;
     for (int j0 = 0; j0 < T; j0 += AB_KB) {
         __syncthreads();
         for (int e = tid; e < Dh * AB_KB; e += 256) {
-            const int d = e / AB_KB, j = e - d * AB_KB;
-            Ks[e] = kg[size_t(d) * T + min(j0 + j, T - 1)];
+            const int d = e / AB_KB, j = e - d * AB_KB, jc = min(j0 + j, T - 1);
+            Ks[e] = kg[size_t(d) * T + jc];
+            Vs[e] = vg[size_t(d) * T + jc];
         }
         __syncthreads();
         for (int e = tid; e < AB_QB * AB_KB; e += 256) {
             const int q = e / AB_KB, j = e - q * AB_KB;
-            float s = 0.f;
-            for (int d = 0; d < Dh; ++d) s = fmaf(Qs[d * AB_QB + q], Ks[d * AB_KB + j], s);
-            Ss[e] = (j0 + j < T) ? s * inv - fabsf(float(i0 + q - (j0 + j))) * slope : -3.0e38f;
+            float s = 0.f, dp = 0.f;
+            for (int d = 0; d < Dh; ++d) {
+                s = fmaf(Qs[d * AB_QB + q], Ks[d * AB_KB + j], s);
+                dp = fmaf(Os[d * AB_QB + q], Vs[d * AB_KB + j], dp);
+            }
+            Ds[e] = dp;
+            Ss[e] = (j0 + j < T) ? attn_bwd_logit(s, inv, i0 + q - (j0 + j), slope) : -3.0e38f;
         }
         __syncthreads();
         float bm = -3.0e38f;
@@ -465,29 +485,30 @@ __global__ __launch_bounds__(256) void attn_bwd_stats_kernel(const float *__rest
         bm = red[rq][0];
         for (int k = 1; k < 16; ++k) bm = fmaxf(bm, red[rq][k]);
         const float mn = fmaxf(m, bm);
-        float bs = 0.f;
-        for (int j = rl; j < AB_KB; j += 16) bs += expf(Ss[rq * AB_KB + j] - mn);
+        float bs = 0.f, bd = 0.f;
+        for (int j = rl; j < AB_KB; j += 16) {
+            const float p = expf(Ss[rq * AB_KB + j] - mn);   // 0 for a padded key
+            bs += p;
+            bd = fmaf(p, Ds[rq * AB_KB + j], bd);
+        }
         __syncthreads();
         red[rq][rl] = bs;
+        redd[rq][rl] = bd;
         __syncthreads();
-        bs = 0.f;
-        for (int k = 0; k < 16; ++k) bs += red[rq][k];
-        l = l * expf(m - mn) + bs;
+        bs = bd = 0.f;
+        for (int k = 0; k < 16; ++k) {
+            bs += red[rq][k];
+            bd += redd[rq][k];
+        }
+        const float alpha = expf(m - mn);
+        l = l * alpha + bs;
+        dl = dl * alpha + bd;
         m = mn;
     }
-    // delta_i = sum_d dO[d,i] O[d,i]
-    float dl = 0.f;
-    const int iq = min(i0 + rq, T - 1);
-    for (int d = rl; d < Dh; d += 16) dl = fmaf(dg[size_t(d) * T + iq], og[size_t(d) * T + iq], dl);
-    __syncthreads();
-    red[rq][rl] = dl;
-    __syncthreads();
     if (rl == 0 && i0 + rq < T) {
-        float s = 0.f;
-        for (int k = 0; k < 16; ++k) s += red[rq][k];
         const size_t o = (size_t(b) * H + h) * T + i0 + rq;
         lse[o] = m + logf(l);
-        delta[o] = s;
+        delta[o] = dl / l;
     }
 }
 
@@ -535,7 +556,7 @@ __global__ __launch_bounds__(256) void attn_bwd_dq_kernel(const float *__restric
             }
             float ds = 0.f;
             if (i < T && j0 + j < T) {
-                const float pn = expf(s * inv - fabsf(float(i - (j0 + j))) * slope - lse[so + i]);
+                const float pn = expf(attn_bwd_logit(s, inv, i - (j0 + j), slope) - lse[so + i]);
                 ds = pn * (dp - delta[so + i]) * inv;
             }
             Ss[e] = ds;
@@ -607,7 +628,7 @@ __global__ __launch_bounds__(256) void attn_bwd_dkv_kernel(const float *__restri
             }
             float pn = 0.f, ds = 0.f;
             if (i < T && j0 + j < T) {
-                pn = expf(s * inv - fabsf(float(i - (j0 + j))) * slope - lse[so + i]);
+                pn = expf(attn_bwd_logit(s, inv, i - (j0 + j), slope) - lse[so + i]);
                 ds = pn * (dp - delta[so + i]) * inv;
             }
             Ps[e] = pn;
@@ -647,7 +668,7 @@ int launch_attention_flash_backward(const float *qkv, const float *slopes, const
                                     float *workspace, int B, int H, int Dh, int T, float scale_div, hipStream_t st) {
     float *lse = workspace, *delta = workspace + size_t(B) * H * T;
     const dim3 gq(ceil_div(T, AB_QB), H, B), gk(ceil_div(T, AB_KB), H, B);
-    const size_t l_stats = size_t(Dh * AB_QB + Dh * AB_KB + AB_QB * AB_KB) * sizeof(float);
+    const size_t l_stats = size_t(2 * Dh * AB_QB + 2 * Dh * AB_KB + 2 * AB_QB * AB_KB) * sizeof(float);
     const size_t l_dq = size_t(2 * Dh * AB_QB + 2 * Dh * AB_KB + AB_QB * AB_KB) * sizeof(float);
     const size_t l_dkv = size_t(2 * Dh * AB_KB + 2 * Dh * AB_QB + 2 * AB_QB * AB_KB) * sizeof(float);
     static DeviceOnce once[3];
