@@ -9,7 +9,7 @@ from __future__ import annotations
 import ctypes
 import os
 from ctypes import (POINTER, Structure, c_char_p, c_double, c_float, c_int, c_int32, c_int64,
-                    c_size_t, c_void_p)
+                    c_size_t, c_uint32, c_uint64, c_void_p)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "lib", "libagx.so")
@@ -113,6 +113,15 @@ SIGNATURES = {
                                                    c_void_p, c_size_t, c_int32, c_int32, c_int32, c_int32, c_int32,
                                                    c_float, c_void_p]),
     "agx_attention_cross_kernel_name": (c_int, [c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, c_char_p, c_size_t]),
+    "agx_attention_alibi_dropout": (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_int32, c_int32, c_int32,
+                                            c_int32, c_int32, c_float, c_double, c_uint64, c_uint32, c_void_p]),
+    "agx_attention_dropout_backward_workspace_bytes": (c_size_t, [c_int32, c_int32, c_int32]),
+    "agx_attention_alibi_dropout_backward": (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_void_p,
+                                                     c_void_p, c_int64, c_int64, c_void_p, c_size_t, c_int32, c_int32, c_int32,
+                                                     c_int32, c_int32, c_float, c_double, c_uint64, c_uint32, c_void_p]),
+    "agx_attention_dropout_kernel_name": (c_int, [c_int32, c_int32, c_int32, c_int32, c_int32, c_double, c_int32, c_char_p,
+                                                  c_size_t]),
+    "agx_dropout_add": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_double, c_uint64, c_uint32, c_void_p]),
     "agx_conv_bwd_data_gelu": (c_int, [_PD, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "agx_multires_forward": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32,
                                      c_int32, c_int32, c_void_p]),

@@ -591,6 +591,118 @@ def attention_alibi_cross_backward(q: Tensor, kv: Tensor, slopes: Tensor, out: T
     return dq, dkv
 
 
+# ------------------------------------------------------------------ dropout (include/agx.h "Dropout masks")
+def draw_dropout_seed() -> int:
+    """A 64-bit mask seed from torch's default CPU generator, so that ``torch.manual_seed`` reproduces a run."""
+    hi, lo = torch.randint(0, 1 << 32, (2,), dtype=torch.int64).tolist()
+    return (hi << 32) | lo
+
+
+def _drop_args(p: float, seed: int, stream_id: int):
+    return ctypes.c_double(float(p)), ctypes.c_uint64(int(seed) & 0xFFFFFFFFFFFFFFFF), ctypes.c_uint32(int(stream_id) & 0xFFFFFFFF)
+
+
+def _off(t: Tensor, floats: int):
+    return ctypes.c_void_p(t.data_ptr() + 4 * floats)
+
+
+def attention_dropout_kernel_name(batch: int, heads: int, head_dim: int, tq: int, tk: int, p: float, backward: bool = False) -> str:
+    """The kernel ``attention_alibi_dropout`` runs for this shape, with ``backward`` the three kernels of its backward
+    (host-only); ``AgxError`` with the launcher's message if it refuses (head_dim > 128, p outside [0, 1))."""
+    buf = ctypes.create_string_buffer(96)
+    _lib.check(_lib.load().agx_attention_dropout_kernel_name(batch, heads, head_dim, tq, tk, float(p), int(bool(backward)), buf,
+                                                             len(buf)), "agx_attention_dropout_kernel_name")
+    return buf.value.decode()
+
+
+def _drop_shapes(op: str, q: Tensor, kv: Optional[Tensor], heads: int, head_dim: int):
+    """(b, tq, tk, hd) -- ``kv`` None: ``q`` is a (B, 3*H*Dh, T) qkv tensor, read in place through pointers and strides."""
+    hd = heads * head_dim
+    if kv is not None:
+        return (*_cross_shapes(op, q, kv, heads, head_dim), hd)
+    b, c3, t = q.shape
+    if c3 != 3 * hd:
+        raise AgxError(f"{op}: qkv has {c3} channels, expected {3 * hd}")
+    return b, t, t, hd
+
+
+def attention_alibi_dropout(q: Tensor, kv: Optional[Tensor], slopes: Tensor, heads: int, head_dim: int, scale_div: float,
+                            p: float, seed: int, stream_id: int) -> Tensor:
+    """(mask * 1/(1-p) o softmax(Q K^T / scale_div + ALiBi)) V -> (B, H*Dh, Tq), the mask that of include/agx.h for
+    (``seed``, ``stream_id``).  ``q`` (B, H*Dh, Tq) and ``kv`` (B, 2*H*Dh, Tk), or ``kv=None`` and ``q`` a self-attention
+    (B, 3*H*Dh, T) qkv tensor (no copy).  fp32, head_dim <= 128, 0 <= p < 1."""
+    lib = _lib.load()
+    _need_gpu(q, kv, slopes)
+    q = _f32c(q)
+    kv = None if kv is None else _f32c(kv)
+    b, tq, tk, hd = _drop_shapes("attention_alibi_dropout", q, kv, heads, head_dim)
+    out = torch.empty((b, hd, tq), dtype=torch.float32, device=q.device)
+    qp, kp, sq, skv = (_ptr(q), _ptr(kv), hd * tq, 2 * hd * tk) if kv is not None else (_ptr(q), _off(q, hd * tq), 3 * hd * tq, 3 * hd * tq)
+    tok = None
+    if _observer is not None:
+        tok = _observer.begin("other", ("attention_alibi_dropout:flash", 4 * (q.numel() + (0 if kv is None else kv.numel()) + out.numel()),
+                                        2 * b * heads * tq * tk * head_dim))
+    _lib.check(lib.agx_attention_alibi_dropout(qp, kp, sq, skv, _ptr(_f32c(slopes)), _ptr(out), b, heads, head_dim, tq, tk,
+                                               float(scale_div), *_drop_args(p, seed, stream_id), _stream()),
+               "agx_attention_alibi_dropout")
+    if tok is not None:
+        _observer.end(tok)
+    return out
+
+
+def attention_alibi_dropout_backward(q: Tensor, kv: Optional[Tensor], slopes: Tensor, out: Tensor, dout: Tensor, heads: int,
+                                     head_dim: int, scale_div: float, p: float, seed: int, stream_id: int):
+    """Backward of ``attention_alibi_dropout`` with the same (p, seed, stream_id): (dq, dkv), or with ``kv=None`` the one
+    (B, 3*H*Dh, T) dqkv tensor, written in place through pointers and strides."""
+    lib = _lib.load()
+    _need_gpu(q, kv, slopes, out, dout)
+    q, out, dout = _f32c(q), _f32c(out), _f32c(dout)
+    kv = None if kv is None else _f32c(kv)
+    b, tq, tk, hd = _drop_shapes("attention_alibi_dropout_backward", q, kv, heads, head_dim)
+    if tuple(out.shape) != (b, hd, tq) or dout.shape != out.shape:
+        raise AgxError(f"attention_alibi_dropout_backward: out {tuple(out.shape)} / dout {tuple(dout.shape)} are not {(b, hd, tq)}")
+    dq = torch.empty_like(q)
+    if kv is not None:
+        dkv = torch.empty_like(kv)
+        ptrs = (_ptr(q), _ptr(kv), hd * tq, 2 * hd * tk)
+        dptrs = (_ptr(dq), _ptr(dkv), hd * tq, 2 * hd * tk)
+    else:
+        dkv = None
+        ptrs = (_ptr(q), _off(q, hd * tq), 3 * hd * tq, 3 * hd * tq)
+        dptrs = (_ptr(dq), _off(dq, hd * tq), 3 * hd * tq, 3 * hd * tq)
+    nbytes = int(lib.agx_attention_dropout_backward_workspace_bytes(b, heads, tq))
+    ws = _workspace(nbytes, q.device, "agx_attention_dropout_backward_workspace_bytes")
+    _lib.check(lib.agx_attention_alibi_dropout_backward(*ptrs, _ptr(_f32c(slopes)), _ptr(out), _ptr(dout), *dptrs, _ptr(ws), nbytes,
+                                                        b, heads, head_dim, tq, tk, float(scale_div),
+                                                        *_drop_args(p, seed, stream_id), _stream()),
+               "agx_attention_alibi_dropout_backward")
+    return dq if kv is None else (dq, dkv)
+
+
+def dropout_add(x: Tensor, res: Optional[Tensor], p: float, seed: int, stream_id: int, out: Optional[Tensor] = None) -> Tensor:
+    """``res + mask * x / (1 - p)`` (``res`` None: no residual) over a contiguous tensor, the mask that of include/agx.h for
+    (``seed``, ``stream_id``) on the linear index.  ``out`` may be ``x`` (in place).  With ``res=None`` and the forward's
+    arguments it is its own backward."""
+    lib = _lib.load()
+    _need_gpu(x, res, out)
+    if x.dtype != torch.float32 or not x.is_contiguous():
+        raise AgxError("dropout_add: x must be a contiguous float32 tensor (the mask is indexed by the linear position)")
+    if res is not None:
+        res = _f32c(res)
+        if res.shape != x.shape:
+            raise AgxError(f"dropout_add: residual is {tuple(res.shape)}, x is {tuple(x.shape)}")
+    if out is None:
+        out = torch.empty_like(x)
+    elif out.shape != x.shape or out.dtype != torch.float32 or not out.is_contiguous():
+        raise AgxError("dropout_add: out must be a contiguous float32 tensor of x's shape")
+    tok = _observer.begin("other", ("dropout_add", 4 * x.numel() * (2 if res is None else 3))) if _observer is not None else None
+    _lib.check(lib.agx_dropout_add(_ptr(x), _ptr(res), _ptr(out), x.numel(), *_drop_args(p, seed, stream_id), _stream()),
+               "agx_dropout_add")
+    if tok is not None:
+        _observer.end(tok)
+    return out
+
+
 def conv_bwd_data_gelu(desc: ConvDesc, dy: Tensor, packed_bwd: Tensor, pre: Tensor, add: Optional[Tensor] = None) -> Tensor:
     """``conv_bwd_data`` followed (in the epilogue) by the exact-GELU gradient at the pre-activation ``pre``."""
     lib = _lib.load()

@@ -16,7 +16,9 @@ Execution is channel-major: the block works on ``(B, C, T)`` tensors (what the
 encoder emits), every ``Linear`` is a k=1 convolution on the fp32 MFMA conv
 kernel with the activation / residual fused into its epilogue, LayerNorm and
 softmax(QK^T + ALiBi)V are the two dedicated kernels of ``csrc/attention.hip``
-(cross-attention: ``csrc/attention_cross.hip``, fp32 only).
+(cross-attention: ``csrc/attention_cross.hip``, fp32 only).  ``dropout > 0`` acts in
+training mode only, on counter-based masks generated inside the kernels of
+``csrc/attention_dropout.hip`` (``Transformer._hip_bct``); in eval mode it is the identity.
 The ``nn.LayerNorm`` / ``nn.Linear`` children only hold parameters.
 """
 from __future__ import annotations
@@ -123,6 +125,29 @@ def _ln_bwd(ln: nn.LayerNorm, x: Tensor, dy: Tensor, add: Tensor):
     return ops.layernorm_ct_backward(x, ln.weight.detach(), dy, ln.eps, add=add)
 
 
+def _active_p(drop: nn.Dropout) -> float:
+    """The probability a dropout site applies in this call: 0 in eval mode (the site is the identity and no dropout kernel
+    runs).  p = 1 drops everything and has no finite scale 1 / (1 - p): refused at the first training-mode call."""
+    if not drop.training or drop.p == 0:
+        return 0.0
+    if not 0.0 < drop.p < 1.0:
+        raise AgxError(f"dropout = {drop.p} in training mode: the kernels take 0 <= p < 1 (agx_dropout_add)")
+    return float(drop.p)
+
+
+def _site(drop: Optional[tuple], module: nn.Module) -> tuple:
+    """(seed, layer) of a dropout site: what the enclosing ``Transformer`` drew for this forward, or -- a sub-block called on
+    its own -- a fresh seed for layer 0, kept on the module as ``last_dropout_seed``."""
+    if drop is None:
+        drop = (ops.draw_dropout_seed(), 0)
+        module.last_dropout_seed = drop[0]
+    return drop
+
+
+# stream ids of the four dropout sites of layer ``l``: 4 l + site
+SITE_PROB, SITE_ATTN_OUT, SITE_FFN_HIDDEN, SITE_FFN_OUT = 0, 1, 2, 3
+
+
 class Attention(nn.Module):
     """transformers.py:95-191 (pre-LN multi-head attention with ALiBi).  ``context_y`` makes it a cross-attention layer:
     ``W_q`` reads ``LN(x)``, ``W_k`` / ``W_v`` (stacked into one projection) read the second sequence ``y`` as given."""
@@ -132,8 +157,6 @@ class Attention(nn.Module):
         super().__init__()
         if not alibi:
             raise NotImplementedError("only the ALiBi branch is defined in the reference (SURVEY 5.1)")
-        if dropout != 0.:
-            raise NotImplementedError("dropout > 0 is training-only and not on the forward path")
         self.dim, self.dim_head, self.n_heads = dim, dim_head, n_heads
         self.inner_dim = dim_head * n_heads
         self.norm = nn.LayerNorm(dim)
@@ -155,11 +178,13 @@ class Attention(nn.Module):
         # arithmetic of the QK^T / PV contractions: "fp32" (exact, the reference's) or "bf16" (bf16 MFMA, fp32 accumulate
         # and softmax -- BASELINE config 3); inference only (run_bct: ``keep``)
         self.attention_dtype = "fp32"
+        self.last_dropout_seed = None     # the mask seed of the last training-mode forward with dropout > 0
 
     def _attn(self) -> dict:
         return dict(slopes=self.alibi_obj.head_scalars, heads=self.n_heads, head_dim=self.dim_head, scale_div=self.dim_head ** 0.5)
 
-    def _run_cross_bct(self, x: Tensor, residual: Optional[Tensor], keep: Optional[dict], y: Optional[Tensor]) -> Tensor:
+    def _run_cross_bct(self, x: Tensor, residual: Optional[Tensor], keep: Optional[dict], y: Optional[Tensor],
+                       drop: Optional[tuple] = None) -> Tensor:
         """The cross-attention layer: LN1 -> Q projection, KV projection of ``y`` (no LayerNorm, transformers.py:170) ->
         attention -> W_o (+res).  Lengths: what the reference runs -- its transposed ``M[:, :Tx, :Ty]`` (:92) must broadcast,
         ``Tx <= context_y and Ty <= context_x`` -- and the intended reading ``Tx <= context_x and Ty <= context_y``; the
@@ -179,22 +204,41 @@ class Attention(nn.Module):
         if keep is not None and self.dim_head > 128:
             raise AgxError("Transformer: the attention backward kernels cover head_dim <= 128 "
                            "(agx_attention_alibi_cross_backward); larger heads have no kernel -- there is no ATen fallback")
+        p = _active_p(self.dropout)
         xn = _ln(self.norm, x)
         q = self._q.forward(xn)
         kv = self._kv.forward(y)
-        o = ops.attention_alibi_cross(q, kv, **self._attn())
+        if p > 0:
+            seed, layer = _site(drop, self)
+            o = ops.attention_alibi_dropout(q, kv, p=p, seed=seed, stream_id=4 * layer + SITE_PROB, **self._attn())
+        else:
+            o = ops.attention_alibi_cross(q, kv, **self._attn())
         if keep is not None:
             keep.update(h=x, xn1=xn, q=q, y=y, kv=kv, o=o)
+        if p > 0:
+            return self._drop_out(o, residual, keep, p, seed, layer)
         return self._o.forward(o, EPI_RESIDUAL if residual is not None else 0, residual)
 
+    def _drop_out(self, o: Tensor, residual: Optional[Tensor], keep: Optional[dict], p: float, seed: int, layer: int) -> Tensor:
+        """The tail of a training-mode walk with dropout: W_o without the fused residual, then dropout (+ residual) in place."""
+        if keep is not None:
+            keep["drop"] = dict(seed=seed, layer=layer, attn=p)
+        ao = self._o.forward(o)
+        return ops.dropout_add(ao, residual, p, seed, 4 * layer + SITE_ATTN_OUT, out=ao)
+
     def run_bct(self, x: Tensor, residual: Optional[Tensor] = None, keep: Optional[dict] = None,
-                y: Optional[Tensor] = None) -> Tensor:
+                y: Optional[Tensor] = None, drop: Optional[tuple] = None) -> Tensor:
         """(B, dim, T) -> W_o(attn(LN(x))) [+ residual], channel-major; a cross-attention layer also takes ``y``
         (B, dim, Ty).  ``keep`` marks the training forward: the dict
         receives what ``backward_bct`` reads, and the attention arithmetic is fp32 whatever ``attention_dtype`` says
-        (the backward kernels recompute P from fp32 scores, and cover head_dim <= 128)."""
+        (the backward kernels recompute P from fp32 scores, and cover head_dim <= 128).
+
+        In training mode (``self.training``; grad mode plays no part, as in torch) with ``dropout > 0`` the probabilities and
+        the W_o output are dropped (transformers.py:185, :191): ``attention_alibi_dropout``, then W_o without the fused
+        residual and ``dropout_add(., residual)``.  ``drop`` = (seed, layer) from the enclosing ``Transformer``.  fp32,
+        head_dim <= 128.  In eval mode, or with ``dropout == 0``, the walk is the one it always was."""
         if self.cross_attention:
-            return self._run_cross_bct(x, residual, keep, y)
+            return self._run_cross_bct(x, residual, keep, y, drop)
         if y is not None:
             raise AgxError("a self-attention layer (built without context_y) takes no second sequence y")
         if x.shape[-1] > self.context:
@@ -203,6 +247,17 @@ class Attention(nn.Module):
         if keep is not None and self.dim_head > 128:
             raise AgxError("Transformer: the attention backward kernels cover head_dim <= 128 "
                            "(agx_attention_alibi_backward_ex); larger heads run forward only -- there is no ATen fallback")
+        p = _active_p(self.dropout)
+        if p > 0:
+            if self.attention_dtype != "fp32":
+                raise AgxError(f"attention with dropout runs in fp32: attention_dtype = {self.attention_dtype!r} has no kernel")
+            seed, layer = _site(drop, self)
+            xn = _ln(self.norm, x)
+            qkv = self._qkv.forward(xn)
+            o = ops.attention_alibi_dropout(qkv, None, p=p, seed=seed, stream_id=4 * layer + SITE_PROB, **self._attn())
+            if keep is not None:
+                keep.update(h=x, xn1=xn, qkv=qkv, o=o)
+            return self._drop_out(o, residual, keep, p, seed, layer)
         xn = _ln(self.norm, x)
         qkv = self._qkv.forward(xn)
         bf16 = self.attention_dtype == "bf16" and keep is None
@@ -215,14 +270,26 @@ class Attention(nn.Module):
         """``g`` = the gradient of ``run_bct(h, residual=h, keep=kept)`` -> (dh, gradients in ``parameters()`` order, dy).
         ``dy`` is the gradient of a cross-attention layer's second sequence -- the backward-data of the stacked W_k / W_v
         projection, run only when ``want_dy`` -- and None otherwise."""
-        do, g_o = self._o.backward(kept["o"], g)
+        d = kept.get("drop")
+        d = d if d is not None and d.get("attn") else None      # the forward's (seed, layer, p): its masks are regenerated
+        if d is not None:    # the W_o site: the residual branch takes g unmasked (``add=g`` below)
+            mask = dict(p=d["attn"], seed=d["seed"], stream_id=4 * d["layer"] + SITE_PROB)
+            do, g_o = self._o.backward(kept["o"], ops.dropout_add(g, None, d["attn"], d["seed"], 4 * d["layer"] + SITE_ATTN_OUT))
+        else:
+            do, g_o = self._o.backward(kept["o"], g)
         if self.cross_attention:
-            dq, dkv = ops.attention_alibi_cross_backward(kept["q"], kept["kv"], dout=do, out=kept["o"], **self._attn())
+            if d is not None:
+                dq, dkv = ops.attention_alibi_dropout_backward(kept["q"], kept["kv"], dout=do, out=kept["o"], **mask, **self._attn())
+            else:
+                dq, dkv = ops.attention_alibi_cross_backward(kept["q"], kept["kv"], dout=do, out=kept["o"], **self._attn())
             dxn, g_q = self._q.backward(kept["xn1"], dq)
             dy, g_kv = self._kv.backward(kept["y"], dkv, want_dx=want_dy)
             dh, dweight, dbias = _ln_bwd(self.norm, kept["h"], dxn, add=g)
             return dh, [dweight, dbias] + g_q + g_kv + g_o, dy
-        dqkv = ops.attention_alibi_backward(kept["qkv"], dout=do, out=kept["o"], **self._attn())
+        if d is not None:
+            dqkv = ops.attention_alibi_dropout_backward(kept["qkv"], None, dout=do, out=kept["o"], **mask, **self._attn())
+        else:
+            dqkv = ops.attention_alibi_backward(kept["qkv"], dout=do, out=kept["o"], **self._attn())
         dxn, g_qkv = self._qkv.backward(kept["xn1"], dqkv)
         dh, dweight, dbias = _ln_bwd(self.norm, kept["h"], dxn, add=g)
         return dh, [dweight, dbias] + g_qkv + g_o, None
@@ -240,24 +307,43 @@ class FeedForward(nn.Module):
         super().__init__()
         if activation is not nn.GELU:
             raise NotImplementedError("only GELU is fused into the FFN kernel epilogue")
-        if dropout != 0.:
-            raise NotImplementedError("dropout > 0 is training-only and not on the forward path")
         self.net = nn.Sequential(nn.LayerNorm(dim), nn.Linear(dim, hidden_dim), activation(), nn.Dropout(dropout),
                                  nn.Linear(hidden_dim, dim), nn.Dropout(dropout))
         self._l1, self._l2 = _PackedLinear(self.net[1]), _PackedLinear(self.net[4])
+        self.last_dropout_seed = None
 
-    def run_bct(self, x: Tensor, residual: Optional[Tensor] = None, keep: Optional[dict] = None) -> Tensor:
+    def run_bct(self, x: Tensor, residual: Optional[Tensor] = None, keep: Optional[dict] = None,
+                drop: Optional[tuple] = None) -> Tensor:
+        """In training mode with ``dropout > 0`` the hidden tensor is dropped in place behind the fused GELU (``net[3]``) and
+        the FFN-out result before the residual add (``net[5]``: the conv runs without its fused residual, then
+        ``dropout_add(., residual)``); otherwise the two launches it always was."""
+        p_hid, p_out = _active_p(self.net[3]), _active_p(self.net[5])
         xn = _ln(self.net[0], x)
         hid = self._l1.forward(xn, EPI_GELU_PRE)
+        if p_hid > 0 or p_out > 0:
+            seed, layer = _site(drop, self)
+            if keep is not None:
+                keep.setdefault("drop", dict(seed=seed, layer=layer)).update(hid=p_hid, out=p_out)
+        if p_hid > 0:
+            ops.dropout_add(hid, None, p_hid, seed, 4 * layer + SITE_FFN_HIDDEN, out=hid)
         if keep is not None:
-            keep.update(x1=x, xn2=xn, hid=hid)
+            keep.update(x1=x, xn2=xn, hid=hid)     # with dropout: the masked hidden tensor, FFN-out's input
+        if p_out > 0:
+            out = self._l2.forward(hid)
+            return ops.dropout_add(out, residual, p_out, seed, 4 * layer + SITE_FFN_OUT, out=out)
         return self._l2.forward(hid, EPI_RESIDUAL if residual is not None else 0, residual)
 
     def backward_bct(self, kept: dict, g: Tensor):
         """As ``Attention.backward_bct``; the GELU gradient sits in the FFN-out bwd-data epilogue, at the pre-activation,
         which is recomputed with one conv launch: the forward's FFN-in projection with epilogue 0."""
+        d = kept.get("drop") or {}
+        g_out = g        # the FFN-out site: the residual branch takes g unmasked (``add=g`` below)
+        if d.get("out"):
+            g_out = ops.dropout_add(g, None, d["out"], d["seed"], 4 * d["layer"] + SITE_FFN_OUT)
         pre = self._l1.forward(kept["xn2"])
-        dpre, g2 = self._l2.backward(kept["hid"], g, pre=pre)
+        dpre, g2 = self._l2.backward(kept["hid"], g_out, pre=pre)
+        if d.get("hid"):     # d hid~ -> d pre: mask * scale and the GELU gradient commute
+            ops.dropout_add(dpre, None, d["hid"], d["seed"], 4 * d["layer"] + SITE_FFN_HIDDEN, out=dpre)
         dxn, g1 = self._l1.backward(kept["xn2"], dpre)
         dx1, dweight, dbias = _ln_bwd(self.net[0], kept["x1"], dxn, add=g)
         return dx1, [dweight, dbias] + g1 + g2
@@ -269,22 +355,24 @@ class FeedForward(nn.Module):
 class _TransformerNative(torch.autograd.Function):
     """Transformer forward + hand-written backward on the HIP kernels: k=1 conv backward for every Linear,
     ``agx_attention_alibi_backward`` / ``agx_attention_alibi_cross_backward``, ``agx_layernorm_ct_backward`` (residual
-    adds fused as ``add``), the GELU gradient in a bwd-data epilogue.  Every layer, the first included, computes its
-    input gradient; ``y`` (None without cross-attention) is a differentiable input too: its gradient is the backward-data
-    of the cross layer's stacked W_k / W_v projection."""
+    adds fused as ``add``), the GELU gradient in a bwd-data epilogue; the dropout masks of a training-mode forward are
+    regenerated from the seed saved in the context (``agx_attention_alibi_dropout_backward``, ``agx_dropout_add``).
+    Every layer, the first included, computes its input gradient; ``y`` (None without cross-attention) is a differentiable
+    input too: its gradient is the backward-data of the cross layer's stacked W_k / W_v projection."""
 
     @staticmethod
     def forward(ctx, tf, x: Tensor, y: Optional[Tensor], *params: Tensor):
         keep = []
         with torch.no_grad():
             out = tf._hip_bct(x.detach(), keep, None if y is None else y.detach())
+        ctx.drop = [kept.pop("drop", None) for kept in keep]     # per layer: the seed, layer and probabilities of its masks
         ctx.tf, ctx.names = tf, [(li, name) for li, kept in enumerate(keep) for name in kept]
         ctx.save_for_backward(*[t for kept in keep for t in kept.values()])
         return out
 
     @staticmethod
     def backward(ctx, g: Tensor):
-        keep = [{} for _ in ctx.tf.layers]
+        keep = [{"drop": d} for d in ctx.drop]
         for (li, name), t in zip(ctx.names, ctx.saved_tensors):
             keep[li][name] = t
         g, grads, gy = g.contiguous(), [], None
@@ -310,19 +398,35 @@ class Transformer(nn.Module):
                                      has_pos_emb=has_pos_emb, alibi=alibi),
                            FeedForward(dim, dim, dropout=dropout)])
             for i in range(depth)])
+        self.last_dropout_seed = None     # the mask seed of the last training-mode forward with dropout > 0
+
+    def _dropout_active(self) -> bool:
+        return any(m.training and m.p > 0 for a, f in self.layers for m in (a.dropout, f.net[3], f.net[5]))
 
     def _hip_bct(self, x: Tensor, keep: Optional[list] = None, y: Optional[Tensor] = None) -> Tensor:
         """The one forward walk, LN1 -> QKV -> attention -> W_o (+res) -> LN2 -> FFN-in (GELU) -> FFN-out (+res) per layer:
         7 launches, both residual adds fused into the W_o / FFN-out conv epilogues (a cross-attention layer: 8, a Q and a
         KV projection in place of the QKV one).  ``keep``: the training forward
-        (``Attention.run_bct``) -- the list receives one dict of named intermediates per layer."""
+        (``Attention.run_bct``) -- the list receives one dict of named intermediates per layer.
+
+        Training mode with ``dropout > 0``: LN1 -> QKV -> attention with dropout on the probabilities -> W_o -> dropout + res ->
+        LN2 -> FFN-in (GELU) -> dropout in place -> FFN-out -> dropout + res: 10 launches (a cross-attention layer: 11).  The
+        four masks of layer ``l`` have the stream ids ``4 l + {0: probabilities, 1: attention output, 2: FFN hidden, 3: FFN
+        output}`` under one 64-bit seed per call, drawn on the CPU from torch's default generator (``torch.manual_seed``
+        reproduces a run) and kept as ``last_dropout_seed``.  The seed travels to the kernels by value: a captured graph
+        (``torch.cuda.graph``) replays the one mask it was captured with -- capture-safe seeds are not provided.  In eval mode
+        or with ``dropout == 0`` nothing changes: the same 7 (8) launches, no seed is drawn."""
         if (y is not None) != self.cross_attention:
             raise AgxError("Cross attention requires two inputs: this Transformer was built with context_y and got no y"
                            if y is None else "this Transformer was built without context_y and takes no second sequence y")
-        for attention, ff in self.layers:
+        seed = None
+        if self._dropout_active():
+            seed = self.last_dropout_seed = ops.draw_dropout_seed()
+        for li, (attention, ff) in enumerate(self.layers):
             kept = None if keep is None else {}
-            x = attention.run_bct(x, x, kept, y if attention.cross_attention else None)
-            x = ff.run_bct(x, x, kept)
+            drop = None if seed is None else (seed, li)
+            x = attention.run_bct(x, x, kept, y if attention.cross_attention else None, drop)
+            x = ff.run_bct(x, x, kept, drop)
             if keep is not None:
                 keep.append(kept)
         return x

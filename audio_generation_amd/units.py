@@ -30,6 +30,14 @@ def leaky_slope(act: Optional[nn.Module]) -> Optional[float]:
         f"activation {type(act).__name__} has no HIP kernel (LeakyReLU / ReLU are fused into the convs)")
 
 
+def refuse_training_dropout(layer: nn.Module, drop: nn.Dropout) -> None:
+    """The conv stacks have no dropout kernel: a layer built with ``dropout > 0`` runs in eval mode (dropout is the identity
+    there, the path is the one of ``dropout = 0``) and refuses a training-mode call."""
+    if drop.p > 0 and drop.training:
+        raise ops.AgxError(f"{type(layer).__name__}: dropout = {drop.p} in training mode has no kernel (it runs in eval mode, "
+                           "where dropout is the identity) -- there is no ATen fallback")
+
+
 def detached(t: Optional[Tensor]) -> Optional[Tensor]:
     """A parameter as the kernels take it (an absent bias stays ``None``)."""
     return None if t is None else t.detach()

@@ -27,7 +27,7 @@ from . import ops
 from ._lib import (CONV_CAUSAL, CONV_PADDED, CONV_TRANSPOSED, CONV_UPSAMPLE, EPI_LEAKY_POST, EPI_LEAKY_PRE,
                    IMPL_AUTO, IMPL_MFMA_BF16X3, AgxError, needs_grad)
 from .native_backward import run_stack
-from .units import Unit, detached, leaky_slope, packed_image
+from .units import Unit, detached, leaky_slope, packed_image, refuse_training_dropout
 
 Tensor = torch.Tensor
 
@@ -184,8 +184,6 @@ class CausalResidualBlock1d(nn.Module):
     def __init__(self, in_channels, out_channels, kernel_size=7, dilation=1, bias=True,
                  activation=None, dropout=0.0, depthwise=False):
         super().__init__()
-        if dropout != 0.0:
-            raise NotImplementedError("dropout > 0 is training-only and not on the forward path")
         if in_channels != out_channels:
             raise AgxError("residual block needs in_channels == out_channels (as the reference's add does)")
         self.depthwise = depthwise
@@ -201,6 +199,7 @@ class CausalResidualBlock1d(nn.Module):
     def run(self, x: Tensor, post_slope: Optional[float] = None) -> Tensor:
         """Whole block (+ the activation that follows it in the enclosing
         ``Sequential`` when ``post_slope`` is given) through ``agx_resblock_forward``."""
+        refuse_training_dropout(self, self.dropout)
         slope = leaky_slope(self.activation)
         if self.depthwise:
             h = self.conv1[1].run(self.conv1[0].run(x), EPI_LEAKY_PRE if slope is not None else 0, slope or 0.0)
@@ -224,6 +223,7 @@ class CausalResidualBlock1d(nn.Module):
 
     def units(self, act: Optional[nn.Module] = None) -> List[Unit]:
         """One unit; a block whose own activation the kernels do not fuse (``nn.Identity``) runs, and has no backward."""
+        refuse_training_dropout(self, self.dropout)
         inner = leaky_slope(self.activation)
         convs = [*self.conv1, self.conv2] if self.depthwise else [self.conv1, self.conv2]
         return [Unit("resdw" if self.depthwise else "res", self, convs, leaky_slope(act), inner,

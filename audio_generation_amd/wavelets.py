@@ -22,7 +22,7 @@ from torch import nn
 
 from . import ops
 from ._lib import CONV_CAUSAL, CONV_SAME, EPI_GELU_PRE, EPI_LEAKY_PRE, needs_grad
-from .units import Unit, leaky_slope, packed_image
+from .units import Unit, leaky_slope, packed_image, refuse_training_dropout
 
 Tensor = torch.Tensor
 
@@ -34,8 +34,6 @@ class CausalMultiresConv1d(nn.Module):
         super().__init__()
         if activation is not None and not isinstance(activation, nn.GELU):
             raise NotImplementedError("only GELU is fused into the multires kernel")
-        if dropout != 0.0:
-            raise NotImplementedError("dropout > 0 is training-only and not on the forward path")
         self.channels, self.kernel_size, self.depth, self.dropout = channels, kernel_size, depth, dropout
         self.activation = nn.GELU() if activation is None else activation
         scalar = sqrt(2.0) / (kernel_size * 2)
@@ -45,6 +43,7 @@ class CausalMultiresConv1d(nn.Module):
         self.dropout_layer = nn.Dropout(dropout)
 
     def _hip(self, x: Tensor) -> Tensor:
+        refuse_training_dropout(self, self.dropout_layer)
         return ops.multires_forward(x, self.h0.detach(), self.h1.detach(), self.w.detach(), self.depth)
 
     def forward(self, x: Tensor) -> Tensor:
@@ -57,6 +56,7 @@ class CausalMultiresConv1d(nn.Module):
         return self._hip(x)          # the GELU is the kernel's own; the blocks place nothing behind it
 
     def units(self, act: Optional[nn.Module] = None) -> List[Unit]:
+        refuse_training_dropout(self, self.dropout_layer)
         return [Unit("multires", self, [self], leaky_slope(act))]
 
     def params(self):

@@ -26,7 +26,7 @@
 extern "C" {
 #endif
 
-#define AGX_VERSION 122 /* still 122 with the cross-attention entry points (agx_attention_alibi_cross, agx_attention_alibi_cross_backward, agx_attention_cross_backward_workspace_bytes, agx_attention_cross_kernel_name): the ABI only grew -- no existing symbol, struct or meaning changed, so a binding made for 122 keeps working and the number stays; 122: agx_attention_kernel_name, agx_attention_backward_kernel_name (which attention kernel the forward / backward entry points run); 121: agx_conv_bwd_weight_kernel_name, agx_conv2d_bwd_weight_kernel_name, agx_conv_grouped_bwd_weight_kernel_name (kernel, operand copy, contraction slices and items of the weight-gradient ops); 120: activation planes (agx_planes_bytes / agx_planes_split / agx_conv_forward_planes / agx_conv_planes_supported): pre-split bf16x3 input of the decoder's resampling convs; conv_p one-phase geometries (k = 1, "same" k = 11 / 3) with GELU / residual epilogues; 119: agx_rvq_verify_counts + knob rvq_verify (debug: the full defining search beside the fast path); agx_rvq_debug_stamps and the b3_dbg 7/8/9 bound knobs exist in the probe build only; 118: agx_feature_means(_backward) (the feature-matching pair in one pass); 117: agx_rvq_debug_stamps (diagnostic); 116: agx_multires_backward, agx_layernorm_ct one-pass kernel (same signature); agx_rvq_forward (legacy form) needs the workspace of agx_rvq_workspace_bytes since 114; 115: agx_rvq_ema_stats, agx_conv2d_bwd_data_kernel_name; 114: agx_attention_alibi_backward_ex (any T), agx_rvq_forward_ex; 113: tile images (resblock_p / conv_p), agx_attention_alibi_ex, agx_sizeof_*; 0.1.1: agx_conv_desc gained groups / padding (zero = old behaviour); 111: resample, conv2d column split */
+#define AGX_VERSION 122 /* still 122 with the dropout entry points (agx_attention_alibi_dropout, agx_attention_alibi_dropout_backward, agx_attention_dropout_backward_workspace_bytes, agx_attention_dropout_kernel_name, agx_dropout_add) and with the cross-attention entry points (agx_attention_alibi_cross, agx_attention_alibi_cross_backward, agx_attention_cross_backward_workspace_bytes, agx_attention_cross_kernel_name): the ABI only grew -- no existing symbol, struct or meaning changed, so a binding made for 122 keeps working and the number stays; 122: agx_attention_kernel_name, agx_attention_backward_kernel_name (which attention kernel the forward / backward entry points run); 121: agx_conv_bwd_weight_kernel_name, agx_conv2d_bwd_weight_kernel_name, agx_conv_grouped_bwd_weight_kernel_name (kernel, operand copy, contraction slices and items of the weight-gradient ops); 120: activation planes (agx_planes_bytes / agx_planes_split / agx_conv_forward_planes / agx_conv_planes_supported): pre-split bf16x3 input of the decoder's resampling convs; conv_p one-phase geometries (k = 1, "same" k = 11 / 3) with GELU / residual epilogues; 119: agx_rvq_verify_counts + knob rvq_verify (debug: the full defining search beside the fast path); agx_rvq_debug_stamps and the b3_dbg 7/8/9 bound knobs exist in the probe build only; 118: agx_feature_means(_backward) (the feature-matching pair in one pass); 117: agx_rvq_debug_stamps (diagnostic); 116: agx_multires_backward, agx_layernorm_ct one-pass kernel (same signature); agx_rvq_forward (legacy form) needs the workspace of agx_rvq_workspace_bytes since 114; 115: agx_rvq_ema_stats, agx_conv2d_bwd_data_kernel_name; 114: agx_attention_alibi_backward_ex (any T), agx_rvq_forward_ex; 113: tile images (resblock_p / conv_p), agx_attention_alibi_ex, agx_sizeof_*; 0.1.1: agx_conv_desc gained groups / padding (zero = old behaviour); 111: resample, conv2d column split */
 
 #define AGX_OK 0
 #define AGX_ERR_BAD_SHAPE (-1)
@@ -382,6 +382,55 @@ int agx_attention_alibi_cross_backward(const float *q, const float *kv, const fl
  * the launcher's refusal (code and message).  The name is truncated to buf_len - 1 characters. */
 int agx_attention_cross_kernel_name(int32_t batch, int32_t heads, int32_t head_dim, int32_t tq, int32_t tk, int32_t backward,
                                     char *buf, size_t buf_len);
+
+/* Dropout masks (transformers.py:185, :191, :217, :219 in training mode).  No mask tensor is ever stored: a mask is a pure
+ * function of its arguments, regenerated by every kernel that needs it (the backward kernels regenerate the forward's).
+ *   Generator.  Philox4x32-10, standard constants: multipliers M0 = 0xD2511F53, M1 = 0xCD9E8D57, key increments 0x9E3779B9 /
+ *     0xBB67AE85; one round maps the counter (c0, c1, c2, c3) under the key (k0, k1) to
+ *     (hi(M1 c2) ^ c1 ^ k0, lo(M1 c2), hi(M0 c0) ^ c3 ^ k1, lo(M0 c0)), then both key words take their increment; ten rounds;
+ *     the output is the four 32-bit words of the final counter.
+ *   Key.  k0 = the low, k1 = the high 32 bits of `seed`.
+ *   Keep rule.  An element is kept iff its word >= thresh, thresh = min(2^32 - 1, floor(p * 2^32 + 1/2)); kept values are
+ *     multiplied by scale = (float)(1 / (1 - p)), both computed on the host in double.  0 <= p < 1 (AGX_ERR_BAD_SHAPE
+ *     otherwise); p = 0 keeps every element at scale 1.
+ *   Attention element (b, h, i, j), i the query and j the key position (absolute, in their own sequences): counter
+ *     (j >> 2, i, b * heads + h, stream_id), word j & 3 -- the same for all four attention kernels, whatever their tiling.
+ *   Elementwise element e (the linear index in the contiguous tensor): counter (low32(e >> 2), high32(e >> 2), 0,
+ *     stream_id), word e & 3.
+ * `stream_id` names the call site, so that sites sharing a seed draw independent masks.  There is no parity with any other
+ * library's random stream: the guarantee is exact results given the mask, and a mask that is what this paragraph says.
+ *
+ * Attention with dropout on the probabilities (csrc/attention_dropout.hip):
+ *     out[b,h,:,i] = sum_j keep(b,h,i,j) * scale * P_ij * v_j,   P = softmax_j( q_i . k_j / scale_div - slopes[h] * |i - j| )
+ * (the softmax is that of the unmasked logits).  Layouts as agx_attention_alibi_cross, with explicit batch strides in floats
+ * for q and kv: item b of q starts at q + b * q_batch_stride (>= H*Dh*tq), of kv at kv + b * kv_batch_stride (>= 2*H*Dh*tk;
+ * AGX_ERR_BAD_SHAPE when shorter).  Self-attention on a (B, 3*H*Dh, T) qkv tensor is q = qkv, kv = qkv + H*Dh*T, both strides
+ * 3*H*Dh*T, tq = tk = T.  out is contiguous (B, H*Dh, tq).  fp32, any tq, tk >= 1, Dh <= 128 (AGX_ERR_UNSUPPORTED beyond);
+ * batch, heads, tq or tk <= 0: returns AGX_OK and launches nothing. */
+int agx_attention_alibi_dropout(const float *q, const float *kv, int64_t q_batch_stride, int64_t kv_batch_stride, const float *slopes,
+                                float *out, int32_t batch, int32_t heads, int32_t head_dim, int32_t tq, int32_t tk, float scale_div,
+                                double p, uint64_t seed, uint32_t stream_id, void *stream);
+/* Its backward, with the forward's p, seed and stream_id: dq and dkv from q, kv and dout (contiguous (B, H*Dh, tq); `out` is
+ * not read).  dq and dkv take their own batch strides, so self-attention writes dq = dqkv, dkv = dqkv + H*Dh*T with both
+ * strides 3*H*Dh*T.  Three deterministic kernels as agx_attention_alibi_cross_backward (no atomics: two calls agree bit for
+ * bit); workspace = 2 * batch * heads * tq floats = agx_attention_dropout_backward_workspace_bytes() bytes, every float of
+ * it written (AGX_ERR_WORKSPACE when shorter).  Empty shapes as above. */
+size_t agx_attention_dropout_backward_workspace_bytes(int32_t batch, int32_t heads, int32_t tq);
+int agx_attention_alibi_dropout_backward(const float *q, const float *kv, int64_t q_batch_stride, int64_t kv_batch_stride,
+                                         const float *slopes, const float *out, const float *dout, float *dq, float *dkv,
+                                         int64_t dq_batch_stride, int64_t dkv_batch_stride, float *workspace, size_t workspace_bytes,
+                                         int32_t batch, int32_t heads, int32_t head_dim, int32_t tq, int32_t tk, float scale_div,
+                                         double p, uint64_t seed, uint32_t stream_id, void *stream);
+/* Host-only: "attention_drop<DVT>" (DVT = 1 / 2 / 4 32-row tiles of the head dim), with backward != 0 the three backward
+ * kernels, "none" for an empty shape, or the launcher's refusal (code and message; p outside [0, 1) included). */
+int agx_attention_dropout_kernel_name(int32_t batch, int32_t heads, int32_t head_dim, int32_t tq, int32_t tk, double p,
+                                      int32_t backward, char *buf, size_t buf_len);
+/* Elementwise dropout with an optional residual over n contiguous floats:
+ *     out[e] = (res ? res[e] : 0) + (keep(e) ? x[e] * scale : 0)
+ * with the product rounded to fp32 before the add.  out may alias x; res may be NULL.  With res = NULL and the forward's
+ * (p, seed, stream_id) the call is its own backward.  n <= 0: returns AGX_OK and launches nothing. */
+int agx_dropout_add(const float *x, const float *res, float *out, int64_t n, double p, uint64_t seed, uint32_t stream_id,
+                    void *stream);
 
 /* ------------------------------------------------------------------------- *
  * Wavelet / multiresolution layers (networks/wavelets.py)                     *
