@@ -679,6 +679,90 @@ def attention_alibi_dropout_backward(q: Tensor, kv: Optional[Tensor], slopes: Te
     return dq if kv is None else (dq, dkv)
 
 
+# ------------------------------------------------------------------ causal attention (include/agx.h "Causal self-attention")
+def attention_causal_kernel_name(batch: int, heads: int, head_dim: int, tq: int, tk: int, backward: bool = False) -> str:
+    """The kernel ``attention_alibi_causal`` runs for this shape, with ``backward`` the three kernels of
+    ``attention_alibi_causal_backward`` (host-only); ``AgxError`` with the launcher's message if it refuses."""
+    return _kernel_name("agx_attention_causal_kernel_name", batch, heads, head_dim, tq, tk, bool(backward))
+
+
+def _causal_macs(b: int, heads: int, head_dim: int, tq: int, tk: int, q_pos0: int) -> int:
+    """The MACs the causal forward executes: per workgroup of 128 queries, both contractions over the 64-key blocks up to the
+    last one any of its queries sees (the blocks above the diagonal are skipped)."""
+    blocks = sum(min(tk - 1, q0 + 127 + q_pos0) // 64 + 1 for q0 in range(0, tq, 128))
+    return 2 * b * heads * head_dim * 128 * 64 * blocks
+
+
+def attention_alibi_causal(q: Tensor, kv: Optional[Tensor], slopes: Tensor, heads: int, head_dim: int, scale_div: float,
+                           q_pos0: int = 0, tk: Optional[int] = None) -> Tensor:
+    """Causal attention with the one-sided ALiBi bias: query ``i`` sits at position ``i + q_pos0`` and sees the keys
+    ``j <= i + q_pos0`` at the bias ``-slope_h (i + q_pos0 - j)`` -> (B, H*Dh, Tq).  ``kv=None``: ``q`` is a (B, 3*H*Dh, T) qkv
+    tensor read in place (full causal self-attention with ``q_pos0 = 0``).  Otherwise ``q`` holds the queries in its first
+    H*Dh rows (a (B, H*Dh, Tq) tensor, or a (B, 3*H*Dh, Tq) qkv tensor whose Q rows are read in place) and ``kv`` is a
+    (B, 2*H*Dh, cap) key/value buffer with ``tk <= cap`` valid columns (default ``cap``); columns >= ``tk`` are never read.
+    fp32, head_dim <= 128."""
+    lib = _lib.load()
+    _need_gpu(q, kv, slopes)
+    q = _f32c(q)
+    hd = heads * head_dim
+    b, cq, tq = q.shape
+    if kv is None:
+        if cq != 3 * hd:
+            raise AgxError(f"attention_alibi_causal: qkv has {cq} channels, expected {3 * hd}")
+        if tk not in (None, tq):
+            raise AgxError(f"attention_alibi_causal: tk = {tk} with kv=None (the keys are the {tq} columns of qkv)")
+        tk, cap = tq, tq
+        qp, kp, sq, skv = _ptr(q), _off(q, hd * tq), 3 * hd * tq, 3 * hd * tq
+        nbytes = 4 * q.numel()
+    else:
+        kv = _f32c(kv)
+        bk, ckv, cap = kv.shape
+        if cq not in (hd, 3 * hd):
+            raise AgxError(f"attention_alibi_causal: q has {cq} channels, expected {hd} (or a {3 * hd}-channel qkv tensor)")
+        if ckv != 2 * hd:
+            raise AgxError(f"attention_alibi_causal: kv has {ckv} channels, expected {2 * hd}")
+        if bk != b:
+            raise AgxError(f"attention_alibi_causal: q has batch {b}, kv has batch {bk}")
+        tk = cap if tk is None else int(tk)
+        if not 0 <= tk <= cap:
+            raise AgxError(f"attention_alibi_causal: tk = {tk} is outside the kv buffer's {cap} columns")
+        qp, kp, sq, skv = _ptr(q), _ptr(kv), cq * tq, 2 * hd * cap
+        nbytes = 4 * (b * hd * tq + 2 * b * hd * tk)
+    out = torch.empty((b, hd, tq), dtype=torch.float32, device=q.device)
+    tok = None
+    if _observer is not None and min(b, heads, tq, tk) > 0 and q_pos0 >= 0:
+        tok = _observer.begin("other", ("attention_alibi_causal:flash", nbytes + 4 * out.numel(),
+                                        _causal_macs(b, heads, head_dim, tq, tk, int(q_pos0))))
+    _lib.check(lib.agx_attention_alibi_causal(qp, kp, sq, skv, cap, _ptr(_f32c(slopes)), _ptr(out), b, heads, head_dim, tq, tk,
+                                              int(q_pos0), float(scale_div), _stream()), "agx_attention_alibi_causal")
+    if tok is not None:
+        _observer.end(tok)
+    return out
+
+
+def attention_alibi_causal_backward(qkv: Tensor, slopes: Tensor, out: Tensor, dout: Tensor, heads: int, head_dim: int,
+                                    scale_div: float) -> Tensor:
+    """dqkv of the full causal self-attention ``attention_alibi_causal(qkv, None, ...)`` from qkv (B, 3*H*Dh, T), the forward's
+    ``out`` and ``dout`` (both (B, H*Dh, T)); qkv is read and dqkv written in place through pointers and strides."""
+    lib = _lib.load()
+    _need_gpu(qkv, slopes, out, dout)
+    qkv, out, dout = _f32c(qkv), _f32c(out), _f32c(dout)
+    hd = heads * head_dim
+    b, c3, t = qkv.shape
+    if c3 != 3 * hd:
+        raise AgxError(f"attention_alibi_causal_backward: qkv has {c3} channels, expected {3 * hd}")
+    if tuple(out.shape) != (b, hd, t) or dout.shape != out.shape:
+        raise AgxError(f"attention_alibi_causal_backward: out {tuple(out.shape)} / dout {tuple(dout.shape)} are not {(b, hd, t)}")
+    dqkv = torch.empty_like(qkv)
+    nbytes = int(lib.agx_attention_causal_backward_workspace_bytes(b, heads, t))
+    ws = _workspace(nbytes, qkv.device, "agx_attention_causal_backward_workspace_bytes")
+    _lib.check(lib.agx_attention_alibi_causal_backward(_ptr(qkv), _off(qkv, hd * t), 3 * hd * t, 3 * hd * t, _ptr(_f32c(slopes)),
+                                                       _ptr(out), _ptr(dout), _ptr(dqkv), _off(dqkv, hd * t), 3 * hd * t, 3 * hd * t,
+                                                       _ptr(ws), nbytes, b, heads, head_dim, t, float(scale_div), _stream()),
+               "agx_attention_alibi_causal_backward")
+    return dqkv
+
+
 def dropout_add(x: Tensor, res: Optional[Tensor], p: float, seed: int, stream_id: int, out: Optional[Tensor] = None) -> Tensor:
     """``res + mask * x / (1 - p)`` (``res`` None: no residual) over a contiguous tensor, the mask that of include/agx.h for
     (``seed``, ``stream_id``) on the linear index.  ``out`` may be ``x`` (in place).  With ``res=None`` and the forward's

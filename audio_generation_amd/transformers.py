@@ -19,6 +19,9 @@ softmax(QK^T + ALiBi)V are the two dedicated kernels of ``csrc/attention.hip``
 (cross-attention: ``csrc/attention_cross.hip``, fp32 only).  ``dropout > 0`` acts in
 training mode only, on counter-based masks generated inside the kernels of
 ``csrc/attention_dropout.hip`` (``Transformer._hip_bct``); in eval mode it is the identity.
+``causal=True`` (build-defined, default off) makes every self-attention layer one-sided -- keys ``j <= i``, bias
+``-slope_h (i - j)`` -- on the kernels of ``csrc/attention_causal.hip``, and lets a ``Transformer`` run incrementally on a
+key/value cache (``Transformer.new_cache``).
 The ``nn.LayerNorm`` / ``nn.Linear`` children only hold parameters.
 """
 from __future__ import annotations
@@ -153,10 +156,13 @@ class Attention(nn.Module):
     ``W_q`` reads ``LN(x)``, ``W_k`` / ``W_v`` (stacked into one projection) read the second sequence ``y`` as given."""
 
     def __init__(self, dim, dim_head=64, n_heads=8, dropout=0., bias=False, context_x=32, context_y=None,
-                 has_pos_emb=True, alibi=True):
+                 has_pos_emb=True, alibi=True, causal=False):
         super().__init__()
         if not alibi:
             raise NotImplementedError("only the ALiBi branch is defined in the reference (SURVEY 5.1)")
+        if causal and context_y is not None:
+            raise ValueError("causal=True with context_y: causal cross-attention is not defined (cross-attention stays symmetric)")
+        self.causal = bool(causal)     # build-defined: keys j <= i, bias -slope_h (i - j); parameters and state_dict unchanged
         self.dim, self.dim_head, self.n_heads = dim, dim_head, n_heads
         self.inner_dim = dim_head * n_heads
         self.norm = nn.LayerNorm(dim)
@@ -226,8 +232,35 @@ class Attention(nn.Module):
         ao = self._o.forward(o)
         return ops.dropout_add(ao, residual, p, seed, 4 * layer + SITE_ATTN_OUT, out=ao)
 
+    def _run_causal_bct(self, x: Tensor, residual: Optional[Tensor], keep: Optional[dict], kv_cache: Optional[tuple]) -> Tensor:
+        """The causal layer: the walk of the self-attention layer with ``attention_alibi_causal`` in place of
+        ``attention_alibi``.  Every refusal comes before the first op.  ``kv_cache`` = (buffer (B, 2*H*Dh, capacity), length):
+        the K / V rows of the new frames are copied into columns [length, length + n) of the buffer (a strided device copy) and
+        the queries, read in place from qkv, attend to the buffer's first length + n columns from position ``length``."""
+        if self.attention_dtype != "fp32":
+            raise AgxError(f"causal attention runs in fp32: attention_dtype = {self.attention_dtype!r} has no kernel")
+        if _active_p(self.dropout) > 0:
+            raise AgxError("causal attention with dropout > 0 in training mode has no kernel (eval mode runs)")
+        if keep is not None and kv_cache is not None:
+            raise AgxError("there is no backward through a cached call")
+        if kv_cache is not None and kv_cache[1] + x.shape[-1] > min(kv_cache[0].shape[-1], self.context):
+            raise AgxError(f"cached call: {kv_cache[1]} cached + {x.shape[-1]} new frames exceed the buffer's "
+                           f"{kv_cache[0].shape[-1]} columns or the ALiBi context {self.context}")
+        xn = _ln(self.norm, x)
+        qkv = self._qkv.forward(xn)
+        if kv_cache is None:
+            o = ops.attention_alibi_causal(qkv, None, **self._attn())
+        else:
+            buf, length = kv_cache
+            n = x.shape[-1]
+            buf[:, :, length:length + n].copy_(qkv[:, self.inner_dim:, :])
+            o = ops.attention_alibi_causal(qkv, buf, q_pos0=length, tk=length + n, **self._attn())
+        if keep is not None:
+            keep.update(h=x, xn1=xn, qkv=qkv, o=o)
+        return self._o.forward(o, EPI_RESIDUAL if residual is not None else 0, residual)
+
     def run_bct(self, x: Tensor, residual: Optional[Tensor] = None, keep: Optional[dict] = None,
-                y: Optional[Tensor] = None, drop: Optional[tuple] = None) -> Tensor:
+                y: Optional[Tensor] = None, drop: Optional[tuple] = None, kv_cache: Optional[tuple] = None) -> Tensor:
         """(B, dim, T) -> W_o(attn(LN(x))) [+ residual], channel-major; a cross-attention layer also takes ``y``
         (B, dim, Ty).  ``keep`` marks the training forward: the dict
         receives what ``backward_bct`` reads, and the attention arithmetic is fp32 whatever ``attention_dtype`` says
@@ -236,7 +269,11 @@ class Attention(nn.Module):
         In training mode (``self.training``; grad mode plays no part, as in torch) with ``dropout > 0`` the probabilities and
         the W_o output are dropped (transformers.py:185, :191): ``attention_alibi_dropout``, then W_o without the fused
         residual and ``dropout_add(., residual)``.  ``drop`` = (seed, layer) from the enclosing ``Transformer``.  fp32,
-        head_dim <= 128.  In eval mode, or with ``dropout == 0``, the walk is the one it always was."""
+        head_dim <= 128.  In eval mode, or with ``dropout == 0``, the walk is the one it always was.
+
+        A ``causal`` layer runs ``_run_causal_bct`` (fp32, no dropout in training mode); ``kv_cache`` is its cached call."""
+        if kv_cache is not None and not self.causal:
+            raise AgxError("a key/value cache needs a causal self-attention layer (causal=True, no context_y)")
         if self.cross_attention:
             return self._run_cross_bct(x, residual, keep, y, drop)
         if y is not None:
@@ -247,6 +284,8 @@ class Attention(nn.Module):
         if keep is not None and self.dim_head > 128:
             raise AgxError("Transformer: the attention backward kernels cover head_dim <= 128 "
                            "(agx_attention_alibi_backward_ex); larger heads run forward only -- there is no ATen fallback")
+        if self.causal:
+            return self._run_causal_bct(x, residual, keep, kv_cache)
         p = _active_p(self.dropout)
         if p > 0:
             if self.attention_dtype != "fp32":
@@ -288,6 +327,8 @@ class Attention(nn.Module):
             return dh, [dweight, dbias] + g_q + g_kv + g_o, dy
         if d is not None:
             dqkv = ops.attention_alibi_dropout_backward(kept["qkv"], None, dout=do, out=kept["o"], **mask, **self._attn())
+        elif self.causal:
+            dqkv = ops.attention_alibi_causal_backward(kept["qkv"], out=kept["o"], dout=do, **self._attn())
         else:
             dqkv = ops.attention_alibi_backward(kept["qkv"], dout=do, out=kept["o"], **self._attn())
         dxn, g_qkv = self._qkv.backward(kept["xn1"], dqkv)
@@ -385,17 +426,34 @@ class _TransformerNative(torch.autograd.Function):
         return (None, g if ctx.needs_input_grad[1] else None, gy, *grads)
 
 
+class TransformerCache:
+    """The key/value cache of a causal ``Transformer`` (``Transformer.new_cache``): per layer one fp32
+    (B, 2*H*Dh, capacity) buffer, K rows first, then V rows -- the kv layout of ``agx_attention_alibi_causal`` with
+    ``kv_row_stride = capacity`` -- and one ``length``, the frames every layer holds.  The buffers come from ``torch.empty``
+    and are never cleared: the kernel reads nothing at or beyond column ``length`` of a row."""
+
+    def __init__(self, kv: list, batch: int, capacity: int):
+        self.kv, self.batch, self.capacity, self.length = kv, batch, capacity, 0
+
+    def reset(self) -> None:
+        self.length = 0
+
+
 class Transformer(nn.Module):
-    """transformers.py:225-279: ``x += attn(x); x += ff(x)`` per layer."""
+    """transformers.py:225-279: ``x += attn(x); x += ff(x)`` per layer.  ``causal=True`` (build-defined): every layer is
+    causal self-attention, and ``new_cache`` / ``run_bct(x, cache=)`` run the block incrementally."""
 
     def __init__(self, dim, depth=1, heads=8, head_dim=64, dropout=0., context_x=32, context_y=None,
-                 has_pos_emb=True, alibi=True):
+                 has_pos_emb=True, alibi=True, causal=False):
         super().__init__()
+        if causal and context_y is not None:
+            raise ValueError("causal=True with context_y: causal cross-attention is not defined (cross-attention stays symmetric)")
+        self.causal, self.context_x = bool(causal), context_x
         self.cross_attention = context_y is not None     # :253-256
         self.layers = nn.ModuleList([
             nn.ModuleList([Attention(dim, n_heads=heads, dim_head=head_dim, dropout=dropout, context_x=context_x,
                                      context_y=context_y if i == 0 else None,     # :272-273: the first layer only
-                                     has_pos_emb=has_pos_emb, alibi=alibi),
+                                     has_pos_emb=has_pos_emb, alibi=alibi, causal=causal),
                            FeedForward(dim, dim, dropout=dropout)])
             for i in range(depth)])
         self.last_dropout_seed = None     # the mask seed of the last training-mode forward with dropout > 0
@@ -403,7 +461,37 @@ class Transformer(nn.Module):
     def _dropout_active(self) -> bool:
         return any(m.training and m.p > 0 for a, f in self.layers for m in (a.dropout, f.net[3], f.net[5]))
 
-    def _hip_bct(self, x: Tensor, keep: Optional[list] = None, y: Optional[Tensor] = None) -> Tensor:
+    def new_cache(self, batch: int, capacity: Optional[int] = None) -> TransformerCache:
+        """An empty key/value cache for ``batch`` sequences of up to ``capacity`` frames (default ``context_x``), on the
+        parameters' device.  No memset: see ``TransformerCache``."""
+        if not self.causal or self.cross_attention:
+            raise AgxError("new_cache: a key/value cache needs a causal self-attention Transformer (causal=True, no context_y)")
+        capacity = self.context_x if capacity is None else int(capacity)
+        if batch < 1 or capacity < 1:
+            raise AgxError(f"new_cache: batch = {batch}, capacity = {capacity}")
+        device = next(self.parameters()).device
+        kv = [torch.empty((batch, 2 * a.inner_dim, capacity), dtype=torch.float32, device=device) for a, _ in self.layers]
+        return TransformerCache(kv, batch, capacity)
+
+    def _check_cache(self, x: Tensor, cache: TransformerCache) -> None:
+        """The refusals of a cached call, before any op."""
+        if not self.causal or self.cross_attention:
+            raise AgxError("a key/value cache needs a causal self-attention Transformer (causal=True, no context_y)")
+        if needs_grad(x, self):
+            raise AgxError("there is no backward through a cached call: run it under torch.no_grad()")
+        if self._dropout_active():
+            raise AgxError("a cached call with an active dropout site (training mode, dropout > 0) has no kernel")
+        if len(cache.kv) != len(self.layers):
+            raise AgxError(f"the cache holds {len(cache.kv)} layers, this Transformer has {len(self.layers)}")
+        if x.dim() != 3 or x.shape[0] != cache.batch:
+            raise AgxError(f"cached call: x is {tuple(x.shape)}, the cache was made for batch {cache.batch}")
+        limit = min(cache.capacity, self.context_x)
+        if cache.length + x.shape[-1] > limit:
+            raise AgxError(f"cached call: {cache.length} cached + {x.shape[-1]} new frames exceed min(capacity {cache.capacity}, "
+                           f"context_x {self.context_x}) = {limit}")
+
+    def _hip_bct(self, x: Tensor, keep: Optional[list] = None, y: Optional[Tensor] = None,
+                 cache: Optional[TransformerCache] = None) -> Tensor:
         """The one forward walk, LN1 -> QKV -> attention -> W_o (+res) -> LN2 -> FFN-in (GELU) -> FFN-out (+res) per layer:
         7 launches, both residual adds fused into the W_o / FFN-out conv epilogues (a cross-attention layer: 8, a Q and a
         KV projection in place of the QKV one).  ``keep``: the training forward
@@ -415,32 +503,50 @@ class Transformer(nn.Module):
         output}`` under one 64-bit seed per call, drawn on the CPU from torch's default generator (``torch.manual_seed``
         reproduces a run) and kept as ``last_dropout_seed``.  The seed travels to the kernels by value: a captured graph
         (``torch.cuda.graph``) replays the one mask it was captured with -- capture-safe seeds are not provided.  In eval mode
-        or with ``dropout == 0`` nothing changes: the same 7 (8) launches, no seed is drawn."""
+        or with ``dropout == 0`` nothing changes: the same 7 (8) launches, no seed is drawn.
+
+        ``causal``: the same 7 launches with ``attention_alibi_causal`` in place of ``attention_alibi``; fp32, and refused in
+        training mode with ``dropout > 0``.  With ``cache`` the ``n`` frames of ``x`` continue the cached sequence: per layer
+        LN1 -> QKV of the n frames -> their K / V rows copied behind the cached ones -> attention from position
+        ``cache.length`` over ``cache.length + n`` keys -> W_o (+res) -> FFN; ``cache.length`` advances after the last layer."""
         if (y is not None) != self.cross_attention:
             raise AgxError("Cross attention requires two inputs: this Transformer was built with context_y and got no y"
                            if y is None else "this Transformer was built without context_y and takes no second sequence y")
+        if self.causal and self._dropout_active():
+            raise AgxError("a causal Transformer with dropout > 0 in training mode has no kernel (eval mode runs)")
         seed = None
         if self._dropout_active():
             seed = self.last_dropout_seed = ops.draw_dropout_seed()
         for li, (attention, ff) in enumerate(self.layers):
             kept = None if keep is None else {}
             drop = None if seed is None else (seed, li)
-            x = attention.run_bct(x, x, kept, y if attention.cross_attention else None, drop)
+            if cache is not None:
+                x = attention.run_bct(x, x, kept, None, drop, kv_cache=(cache.kv[li], cache.length))
+            else:
+                x = attention.run_bct(x, x, kept, y if attention.cross_attention else None, drop)
             x = ff.run_bct(x, x, kept, drop)
             if keep is not None:
                 keep.append(kept)
+        if cache is not None:
+            cache.length += x.shape[-1]
         return x
 
-    def run_bct(self, x: Tensor, y: Optional[Tensor] = None) -> Tensor:
+    def run_bct(self, x: Tensor, y: Optional[Tensor] = None, cache: Optional[TransformerCache] = None) -> Tensor:
         """Channel-major (B, dim, T) in and out; ``y`` (B, dim, Ty) is the cross-attention layer's second sequence.  With
-        autograd on, the backward runs on the HIP kernels too (_TransformerNative)."""
+        autograd on, the backward runs on the HIP kernels too (_TransformerNative).  ``cache`` (``new_cache``): ``x`` holds
+        the next ``n`` frames of a causal Transformer's sequence; inference only."""
+        if cache is not None:
+            self._check_cache(x, cache)
+            if y is not None:
+                raise AgxError("this Transformer was built without context_y and takes no second sequence y")
+            return self._hip_bct(x, None, None, cache)
         if needs_grad(x, self) or (y is not None and torch.is_grad_enabled() and y.requires_grad):
             return _TransformerNative.apply(self, x, y, *list(self.parameters()))
         return self._hip_bct(x, None, y)
 
-    def forward(self, x: Tensor, y=None) -> Tensor:
+    def forward(self, x: Tensor, y=None, cache: Optional[TransformerCache] = None) -> Tensor:
         y = None if y is None else y.transpose(1, 2).contiguous()
-        return self.run_bct(x.transpose(1, 2).contiguous(), y).transpose(1, 2).contiguous()
+        return self.run_bct(x.transpose(1, 2).contiguous(), y, cache).transpose(1, 2).contiguous()
 
 
 class TransformerBottleneck(nn.Module):

@@ -432,6 +432,36 @@ int agx_attention_dropout_kernel_name(int32_t batch, int32_t heads, int32_t head
 int agx_dropout_add(const float *x, const float *res, float *out, int64_t n, double p, uint64_t seed, uint32_t stream_id,
                     void *stream);
 
+/* Causal self-attention with the one-sided ALiBi bias (csrc/attention_causal.hip; build-defined, the reference has no causal
+ * branch): the query at absolute position i + q_pos0 sees the keys j <= i + q_pos0 only,
+ *     out[b,h,:,i] = sum_j softmax_j( q_i . k_j / scale_div - slopes[h] * (i + q_pos0 - j) ) v_j,   j in [0, min(i + q_pos0, tk - 1)]
+ * q (B, H*Dh, tq) and kv (B, 2*H*Dh, .: K rows, then V rows) with batch strides in floats as agx_attention_alibi_dropout, and
+ * kv rows of pitch kv_row_stride >= tk floats: the pitch of a preallocated key/value cache whose valid length is tk.  Nothing
+ * at or beyond column tk of a kv row is read, so the tail of a cache may hold anything (NaN included).  Full causal
+ * self-attention on a (B, 3*H*Dh, T) qkv tensor is q = qkv, kv = qkv + H*Dh*T, batch strides 3*H*Dh*T, kv_row_stride = T,
+ * tq = tk = T, q_pos0 = 0; a step of tq new frames on a cache is q_pos0 = tk - tq.  out is contiguous (B, H*Dh, tq).  Key
+ * blocks no query of a workgroup can see are skipped.  fp32, Dh <= 128 (AGX_ERR_UNSUPPORTED beyond); q_pos0 < 0,
+ * kv_row_stride < tk or a batch stride too small for the shape: AGX_ERR_BAD_SHAPE; batch, heads, tq or tk <= 0: returns
+ * AGX_OK and launches nothing.  Every refusal happens before anything is launched. */
+int agx_attention_alibi_causal(const float *q, const float *kv, int64_t q_batch_stride, int64_t kv_batch_stride,
+                               int64_t kv_row_stride, const float *slopes, float *out, int32_t batch, int32_t heads,
+                               int32_t head_dim, int32_t tq, int32_t tk, int32_t q_pos0, float scale_div, void *stream);
+/* Backward of the full causal self-attention (q_pos0 = 0, tq = tk = t, rows of pitch t): dq and dkv from q, kv and dout
+ * (contiguous (B, H*Dh, t); `out` is not read), each through its own pointer and batch stride, so dqkv is written in place.
+ * Three deterministic kernels as agx_attention_alibi_cross_backward (no atomics: two calls agree bit for bit), skipping the
+ * key / query blocks the mask empties; a masked (i, j) pair contributes exactly 0.  workspace = 2 * batch * heads * t floats =
+ * agx_attention_causal_backward_workspace_bytes() bytes, every float of it written (AGX_ERR_WORKSPACE when shorter). */
+size_t agx_attention_causal_backward_workspace_bytes(int32_t batch, int32_t heads, int32_t t);
+int agx_attention_alibi_causal_backward(const float *q, const float *kv, int64_t q_batch_stride, int64_t kv_batch_stride,
+                                        const float *slopes, const float *out, const float *dout, float *dq, float *dkv,
+                                        int64_t dq_batch_stride, int64_t dkv_batch_stride, float *workspace,
+                                        size_t workspace_bytes, int32_t batch, int32_t heads, int32_t head_dim, int32_t t,
+                                        float scale_div, void *stream);
+/* Host-only: "attention_causal<DVT>" (DVT = 1 / 2 / 4 32-row tiles of the head dim), with backward != 0 the three backward
+ * kernels, "none" for an empty shape, or the launcher's refusal (code and message). */
+int agx_attention_causal_kernel_name(int32_t batch, int32_t heads, int32_t head_dim, int32_t tq, int32_t tk, int32_t backward,
+                                     char *buf, size_t buf_len);
+
 /* ------------------------------------------------------------------------- *
  * Wavelet / multiresolution layers (networks/wavelets.py)                     *
  * ------------------------------------------------------------------------- */
