@@ -128,6 +128,13 @@ SIGNATURES = {
                                                     c_void_p, c_int64, c_int64, c_void_p, c_size_t, c_int32, c_int32, c_int32,
                                                     c_int32, c_float, c_void_p]),
     "agx_attention_causal_kernel_name": (c_int, [c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, c_char_p, c_size_t]),
+    "agx_attention_alibi_window": (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_int64, c_void_p, c_void_p, c_int32, c_int32,
+                                           c_int32, c_int32, c_int64, c_int32, c_int32, c_float, c_void_p]),
+    "agx_attention_window_backward_workspace_bytes": (c_size_t, [c_int32, c_int32, c_int32]),
+    "agx_attention_alibi_window_backward": (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_void_p,
+                                                    c_void_p, c_int64, c_int64, c_void_p, c_size_t, c_int32, c_int32, c_int32,
+                                                    c_int32, c_int32, c_float, c_void_p]),
+    "agx_attention_window_kernel_name": (c_int, [c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, c_char_p, c_size_t]),
     "agx_dropout_add": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_double, c_uint64, c_uint32, c_void_p]),
     "agx_conv_bwd_data_gelu": (c_int, [_PD, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "agx_multires_forward": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32,

@@ -763,6 +763,99 @@ def attention_alibi_causal_backward(qkv: Tensor, slopes: Tensor, out: Tensor, do
     return dqkv
 
 
+# ------------------------------------------------------------------ sliding-window attention (include/agx.h "Sliding-window")
+def attention_window_kernel_name(batch: int, heads: int, head_dim: int, tq: int, window: int, backward: bool = False) -> str:
+    """The kernel ``attention_alibi_window`` runs for this shape, with ``backward`` the three kernels of
+    ``attention_alibi_window_backward`` (host-only); ``AgxError`` with the launcher's message if it refuses."""
+    return _kernel_name("agx_attention_window_kernel_name", batch, heads, head_dim, tq, window, bool(backward))
+
+
+def _window_macs(b: int, heads: int, head_dim: int, tq: int, q_pos0: int, window: int) -> int:
+    """The MACs the windowed forward executes: per workgroup of 128 queries, both contractions over the 64-key blocks from the
+    one that holds the first key any of its queries sees to the one that holds the last."""
+    blocks = sum((min(q0 + 127, tq - 1) + q_pos0) // 64 - max(0, q0 + q_pos0 - window + 1) // 64 + 1 for q0 in range(0, tq, 128))
+    return 2 * b * heads * head_dim * 128 * 64 * blocks
+
+
+def attention_alibi_window(q: Tensor, kv: Optional[Tensor], slopes: Tensor, heads: int, head_dim: int, scale_div: float,
+                           window: int, q_pos0: int = 0, ring: int = 0) -> Tensor:
+    """Sliding-window causal attention with the one-sided ALiBi bias: query ``i`` sits at position ``p = i + q_pos0`` and sees
+    the keys ``max(0, p - window + 1) <= j <= p`` at the bias ``-slope_h (p - j)`` -> (B, H*Dh, Tq).  ``kv=None``: ``q`` is a
+    (B, 3*H*Dh, T) qkv tensor read in place (full self-attention: ``q_pos0 = 0``, ``ring = 0``).  Otherwise ``q`` holds the
+    queries in its first H*Dh rows (a (B, H*Dh, Tq) tensor, or a (B, 3*H*Dh, Tq) qkv tensor whose Q rows are read in place) and
+    ``kv`` is a (B, 2*H*Dh, cap) key/value buffer: key ``j`` in column ``j`` (``ring = 0``, ``cap >= q_pos0 + Tq``) or in
+    column ``j mod ring`` (``Tq + min(window - 1, q_pos0) <= ring <= cap``); a column outside the window may hold anything.  ``q_pos0`` is
+    a 64-bit position.  fp32, head_dim <= 128."""
+    lib = _lib.load()
+    _need_gpu(q, kv, slopes)
+    q = _f32c(q)
+    hd = heads * head_dim
+    b, cq, tq = q.shape
+    if kv is None:
+        if cq != 3 * hd:
+            raise AgxError(f"attention_alibi_window: qkv has {cq} channels, expected {3 * hd}")
+        if q_pos0 != 0 or ring != 0:
+            raise AgxError(f"attention_alibi_window: q_pos0 = {q_pos0}, ring = {ring} with kv=None (the keys are the {tq} columns of qkv)")
+        cap = tq
+        qp, kp, sq, skv = _ptr(q), _off(q, hd * tq), 3 * hd * tq, 3 * hd * tq
+        nbytes = 4 * q.numel()
+    else:
+        kv = _f32c(kv)
+        bk, ckv, cap = kv.shape
+        if cq not in (hd, 3 * hd):
+            raise AgxError(f"attention_alibi_window: q has {cq} channels, expected {hd} (or a {3 * hd}-channel qkv tensor)")
+        if ckv != 2 * hd:
+            raise AgxError(f"attention_alibi_window: kv has {ckv} channels, expected {2 * hd}")
+        if bk != b:
+            raise AgxError(f"attention_alibi_window: q has batch {b}, kv has batch {bk}")
+        qp, kp, sq, skv = _ptr(q), _ptr(kv), cq * tq, 2 * hd * cap
+        nbytes = 4 * (b * hd * tq + 2 * b * hd * min(cap, tq + max(int(window), 1) - 1))
+    out = torch.empty((b, hd, tq), dtype=torch.float32, device=q.device)
+    tok = None
+    if _observer is not None and min(b, heads, tq) > 0 and q_pos0 >= 0 and window >= 1:
+        tok = _observer.begin("other", ("attention_alibi_window:flash", nbytes + 4 * out.numel(),
+                                        _window_macs(b, heads, head_dim, tq, int(q_pos0), int(window))))
+    _lib.check(lib.agx_attention_alibi_window(qp, kp, sq, skv, cap, _ptr(_f32c(slopes)), _ptr(out), b, heads, head_dim, tq,
+                                              int(q_pos0), min(int(window), 0x7fffffff), int(ring), float(scale_div), _stream()),
+               "agx_attention_alibi_window")
+    if tok is not None:
+        _observer.end(tok)
+    return out
+
+
+def attention_alibi_window_backward(qkv: Tensor, slopes: Tensor, out: Tensor, dout: Tensor, heads: int, head_dim: int,
+                                    scale_div: float, window: int) -> Tensor:
+    """dqkv of the full windowed self-attention ``attention_alibi_window(qkv, None, ..., window)`` from qkv (B, 3*H*Dh, T), the
+    forward's ``out`` and ``dout`` (both (B, H*Dh, T)); qkv is read and dqkv written in place through pointers and strides."""
+    lib = _lib.load()
+    _need_gpu(qkv, slopes, out, dout)
+    qkv, out, dout = _f32c(qkv), _f32c(out), _f32c(dout)
+    hd = heads * head_dim
+    b, c3, t = qkv.shape
+    if c3 != 3 * hd:
+        raise AgxError(f"attention_alibi_window_backward: qkv has {c3} channels, expected {3 * hd}")
+    if tuple(out.shape) != (b, hd, t) or dout.shape != out.shape:
+        raise AgxError(f"attention_alibi_window_backward: out {tuple(out.shape)} / dout {tuple(dout.shape)} are not {(b, hd, t)}")
+    dqkv = torch.empty_like(qkv)
+    nbytes = int(lib.agx_attention_window_backward_workspace_bytes(b, heads, t))
+    ws = _workspace(nbytes, qkv.device, "agx_attention_window_backward_workspace_bytes")
+    _lib.check(lib.agx_attention_alibi_window_backward(_ptr(qkv), _off(qkv, hd * t), 3 * hd * t, 3 * hd * t, _ptr(_f32c(slopes)),
+                                                       _ptr(out), _ptr(dout), _ptr(dqkv), _off(dqkv, hd * t), 3 * hd * t, 3 * hd * t,
+                                                       _ptr(ws), nbytes, b, heads, head_dim, t, min(int(window), 0x7fffffff), float(scale_div),
+                                                       _stream()),
+               "agx_attention_alibi_window_backward")
+    return dqkv
+
+
+def ring_write(buf: Tensor, src: Tensor, col0: int) -> None:
+    """``buf[:, :, col0:col0 + n] = src`` for src (B, C, n): one strided device copy (``Tensor.copy_``) of a chunk's K / V rows
+    into a ring cache.  The caller splits a chunk that wraps the ring into two."""
+    n = src.shape[-1]
+    if not 0 <= col0 <= buf.shape[-1] - n or buf.shape[:2] != src.shape[:2]:
+        raise AgxError(f"ring_write: columns [{col0}, {col0 + n}) of {tuple(src.shape)} do not fit {tuple(buf.shape)}")
+    buf[:, :, col0:col0 + n].copy_(src)
+
+
 def dropout_add(x: Tensor, res: Optional[Tensor], p: float, seed: int, stream_id: int, out: Optional[Tensor] = None) -> Tensor:
     """``res + mask * x / (1 - p)`` (``res`` None: no residual) over a contiguous tensor, the mask that of include/agx.h for
     (``seed``, ``stream_id``) on the linear index.  ``out`` may be ``x`` (in place).  With ``res=None`` and the forward's

@@ -21,7 +21,8 @@ training mode only, on counter-based masks generated inside the kernels of
 ``csrc/attention_dropout.hip`` (``Transformer._hip_bct``); in eval mode it is the identity.
 ``causal=True`` (build-defined, default off) makes every self-attention layer one-sided -- keys ``j <= i``, bias
 ``-slope_h (i - j)`` -- on the kernels of ``csrc/attention_causal.hip``, and lets a ``Transformer`` run incrementally on a
-key/value cache (``Transformer.new_cache``).
+key/value cache (``Transformer.new_cache``).  ``window=W`` (with ``causal=True``) narrows every query to its last ``W`` keys
+on the kernels of ``csrc/attention_window.hip``; the cache is then a ring of fixed size and the stream has no end.
 The ``nn.LayerNorm`` / ``nn.Linear`` children only hold parameters.
 """
 from __future__ import annotations
@@ -151,18 +152,33 @@ def _site(drop: Optional[tuple], module: nn.Module) -> tuple:
 SITE_PROB, SITE_ATTN_OUT, SITE_FFN_HIDDEN, SITE_FFN_OUT = 0, 1, 2, 3
 
 
+def _checked_window(window, causal, context_x) -> Optional[int]:
+    """The ``window=`` constructor argument of ``Attention`` / ``Transformer``: None, or 1 <= window <= context_x on a causal layer."""
+    if window is None:
+        return None
+    if not causal:
+        raise ValueError("window= needs causal=True: the sliding window is a narrowed causal mask")
+    if int(window) != window or window < 1:
+        raise ValueError(f"window = {window}: a query sees at least itself (window >= 1)")
+    if window > context_x:
+        raise ValueError(f"window = {window} exceeds context_x = {context_x}: no call is longer than context_x frames, "
+                         "so a larger window is causal=True without window")
+    return int(window)
+
+
 class Attention(nn.Module):
     """transformers.py:95-191 (pre-LN multi-head attention with ALiBi).  ``context_y`` makes it a cross-attention layer:
     ``W_q`` reads ``LN(x)``, ``W_k`` / ``W_v`` (stacked into one projection) read the second sequence ``y`` as given."""
 
     def __init__(self, dim, dim_head=64, n_heads=8, dropout=0., bias=False, context_x=32, context_y=None,
-                 has_pos_emb=True, alibi=True, causal=False):
+                 has_pos_emb=True, alibi=True, causal=False, window=None):
         super().__init__()
         if not alibi:
             raise NotImplementedError("only the ALiBi branch is defined in the reference (SURVEY 5.1)")
         if causal and context_y is not None:
             raise ValueError("causal=True with context_y: causal cross-attention is not defined (cross-attention stays symmetric)")
         self.causal = bool(causal)     # build-defined: keys j <= i, bias -slope_h (i - j); parameters and state_dict unchanged
+        self.window = _checked_window(window, causal, context_x)     # build-defined: the last ``window`` keys only
         self.dim, self.dim_head, self.n_heads = dim, dim_head, n_heads
         self.inner_dim = dim_head * n_heads
         self.norm = nn.LayerNorm(dim)
@@ -236,19 +252,40 @@ class Attention(nn.Module):
         """The causal layer: the walk of the self-attention layer with ``attention_alibi_causal`` in place of
         ``attention_alibi``.  Every refusal comes before the first op.  ``kv_cache`` = (buffer (B, 2*H*Dh, capacity), length):
         the K / V rows of the new frames are copied into columns [length, length + n) of the buffer (a strided device copy) and
-        the queries, read in place from qkv, attend to the buffer's first length + n columns from position ``length``."""
+        the queries, read in place from qkv, attend to the buffer's first length + n columns from position ``length``.
+
+        With ``window`` the two causal ops are ``attention_alibi_window`` / ``attention_alibi_window_backward`` and the buffer
+        is a ring: frame ``length + t`` goes to column ``(length + t) mod capacity`` (one strided copy, two when the chunk
+        wraps), ``n + min(window - 1, length) <= capacity`` and ``length`` has no limit."""
         if self.attention_dtype != "fp32":
             raise AgxError(f"causal attention runs in fp32: attention_dtype = {self.attention_dtype!r} has no kernel")
         if _active_p(self.dropout) > 0:
             raise AgxError("causal attention with dropout > 0 in training mode has no kernel (eval mode runs)")
         if keep is not None and kv_cache is not None:
             raise AgxError("there is no backward through a cached call")
-        if kv_cache is not None and kv_cache[1] + x.shape[-1] > min(kv_cache[0].shape[-1], self.context):
+        if kv_cache is not None and self.window is not None:
+            behind = min(self.window - 1, kv_cache[1])      # the cached frames the first new query still sees
+            if x.shape[-1] + behind > kv_cache[0].shape[-1]:
+                raise AgxError(f"cached call: {x.shape[-1]} new frames + the {behind} cached frames their window reaches exceed "
+                               f"the ring's {kv_cache[0].shape[-1]} columns")
+        elif kv_cache is not None and kv_cache[1] + x.shape[-1] > min(kv_cache[0].shape[-1], self.context):
             raise AgxError(f"cached call: {kv_cache[1]} cached + {x.shape[-1]} new frames exceed the buffer's "
                            f"{kv_cache[0].shape[-1]} columns or the ALiBi context {self.context}")
         xn = _ln(self.norm, x)
         qkv = self._qkv.forward(xn)
-        if kv_cache is None:
+        if self.window is not None:
+            if kv_cache is None:
+                o = ops.attention_alibi_window(qkv, None, window=self.window, **self._attn())
+            else:
+                buf, length = kv_cache
+                n, cap = x.shape[-1], buf.shape[-1]
+                col0 = length % cap
+                head = min(n, cap - col0)          # the frames that fit before the ring wraps
+                ops.ring_write(buf, qkv[:, self.inner_dim:, :head], col0)
+                if head < n:
+                    ops.ring_write(buf, qkv[:, self.inner_dim:, head:], 0)
+                o = ops.attention_alibi_window(qkv, buf, window=self.window, q_pos0=length, ring=cap, **self._attn())
+        elif kv_cache is None:
             o = ops.attention_alibi_causal(qkv, None, **self._attn())
         else:
             buf, length = kv_cache
@@ -327,6 +364,8 @@ class Attention(nn.Module):
             return dh, [dweight, dbias] + g_q + g_kv + g_o, dy
         if d is not None:
             dqkv = ops.attention_alibi_dropout_backward(kept["qkv"], None, dout=do, out=kept["o"], **mask, **self._attn())
+        elif self.window is not None:
+            dqkv = ops.attention_alibi_window_backward(kept["qkv"], out=kept["o"], dout=do, window=self.window, **self._attn())
         elif self.causal:
             dqkv = ops.attention_alibi_causal_backward(kept["qkv"], out=kept["o"], dout=do, **self._attn())
         else:
@@ -430,10 +469,13 @@ class TransformerCache:
     """The key/value cache of a causal ``Transformer`` (``Transformer.new_cache``): per layer one fp32
     (B, 2*H*Dh, capacity) buffer, K rows first, then V rows -- the kv layout of ``agx_attention_alibi_causal`` with
     ``kv_row_stride = capacity`` -- and one ``length``, the frames every layer holds.  The buffers come from ``torch.empty``
-    and are never cleared: the kernel reads nothing at or beyond column ``length`` of a row."""
+    and are never cleared: the kernel reads nothing at or beyond column ``length`` of a row.
 
-    def __init__(self, kv: list, batch: int, capacity: int):
-        self.kv, self.batch, self.capacity, self.length = kv, batch, capacity, 0
+    On a windowed Transformer (``window`` is its window) every buffer is a ring: frame ``p`` lives in column ``p mod capacity``,
+    ``length`` keeps counting (a Python int: no 32-bit limit) and the kernel reads no column outside a workgroup's window."""
+
+    def __init__(self, kv: list, batch: int, capacity: int, window: Optional[int] = None):
+        self.kv, self.batch, self.capacity, self.length, self.window = kv, batch, capacity, 0, window
 
     def reset(self) -> None:
         self.length = 0
@@ -441,19 +483,21 @@ class TransformerCache:
 
 class Transformer(nn.Module):
     """transformers.py:225-279: ``x += attn(x); x += ff(x)`` per layer.  ``causal=True`` (build-defined): every layer is
-    causal self-attention, and ``new_cache`` / ``run_bct(x, cache=)`` run the block incrementally."""
+    causal self-attention, and ``new_cache`` / ``run_bct(x, cache=)`` run the block incrementally.  ``window=W`` (with
+    ``causal=True``, 1 <= W <= context_x): every query sees its last W keys, the cache is a ring and a stream has no end."""
 
     def __init__(self, dim, depth=1, heads=8, head_dim=64, dropout=0., context_x=32, context_y=None,
-                 has_pos_emb=True, alibi=True, causal=False):
+                 has_pos_emb=True, alibi=True, causal=False, window=None):
         super().__init__()
         if causal and context_y is not None:
             raise ValueError("causal=True with context_y: causal cross-attention is not defined (cross-attention stays symmetric)")
         self.causal, self.context_x = bool(causal), context_x
+        self.window = _checked_window(window, causal, context_x)
         self.cross_attention = context_y is not None     # :253-256
         self.layers = nn.ModuleList([
             nn.ModuleList([Attention(dim, n_heads=heads, dim_head=head_dim, dropout=dropout, context_x=context_x,
                                      context_y=context_y if i == 0 else None,     # :272-273: the first layer only
-                                     has_pos_emb=has_pos_emb, alibi=alibi, causal=causal),
+                                     has_pos_emb=has_pos_emb, alibi=alibi, causal=causal, window=window),
                            FeedForward(dim, dim, dropout=dropout)])
             for i in range(depth)])
         self.last_dropout_seed = None     # the mask seed of the last training-mode forward with dropout > 0
@@ -463,15 +507,19 @@ class Transformer(nn.Module):
 
     def new_cache(self, batch: int, capacity: Optional[int] = None) -> TransformerCache:
         """An empty key/value cache for ``batch`` sequences of up to ``capacity`` frames (default ``context_x``), on the
-        parameters' device.  No memset: see ``TransformerCache``."""
+        parameters' device.  No memset: see ``TransformerCache``.  On a windowed Transformer the cache is a ring of
+        ``capacity >= window`` columns: a call of ``n`` frames needs ``n + min(window - 1, cache.length) <= capacity`` -- the
+        new frames must not overwrite a cached frame their first query still sees -- and the stream has no end."""
         if not self.causal or self.cross_attention:
             raise AgxError("new_cache: a key/value cache needs a causal self-attention Transformer (causal=True, no context_y)")
         capacity = self.context_x if capacity is None else int(capacity)
         if batch < 1 or capacity < 1:
             raise AgxError(f"new_cache: batch = {batch}, capacity = {capacity}")
+        if self.window is not None and capacity < self.window:
+            raise AgxError(f"new_cache: a ring of capacity = {capacity} cannot hold a window of {self.window} frames")
         device = next(self.parameters()).device
         kv = [torch.empty((batch, 2 * a.inner_dim, capacity), dtype=torch.float32, device=device) for a, _ in self.layers]
-        return TransformerCache(kv, batch, capacity)
+        return TransformerCache(kv, batch, capacity, self.window)
 
     def _check_cache(self, x: Tensor, cache: TransformerCache) -> None:
         """The refusals of a cached call, before any op."""
@@ -485,6 +533,14 @@ class Transformer(nn.Module):
             raise AgxError(f"the cache holds {len(cache.kv)} layers, this Transformer has {len(self.layers)}")
         if x.dim() != 3 or x.shape[0] != cache.batch:
             raise AgxError(f"cached call: x is {tuple(x.shape)}, the cache was made for batch {cache.batch}")
+        if self.window is not None:       # a ring: the new frames must not overwrite what their first query still sees
+            if cache.window != self.window:
+                raise AgxError(f"the cache was made for window {cache.window}, this Transformer has window {self.window}")
+            behind = min(self.window - 1, cache.length)
+            if x.shape[-1] + behind > cache.capacity:
+                raise AgxError(f"cached call: {x.shape[-1]} new frames + the {behind} cached frames their window reaches exceed "
+                               f"the ring's capacity {cache.capacity}")
+            return
         limit = min(cache.capacity, self.context_x)
         if cache.length + x.shape[-1] > limit:
             raise AgxError(f"cached call: {cache.length} cached + {x.shape[-1]} new frames exceed min(capacity {cache.capacity}, "
@@ -508,7 +564,10 @@ class Transformer(nn.Module):
         ``causal``: the same 7 launches with ``attention_alibi_causal`` in place of ``attention_alibi``; fp32, and refused in
         training mode with ``dropout > 0``.  With ``cache`` the ``n`` frames of ``x`` continue the cached sequence: per layer
         LN1 -> QKV of the n frames -> their K / V rows copied behind the cached ones -> attention from position
-        ``cache.length`` over ``cache.length + n`` keys -> W_o (+res) -> FFN; ``cache.length`` advances after the last layer."""
+        ``cache.length`` over ``cache.length + n`` keys -> W_o (+res) -> FFN; ``cache.length`` advances after the last layer.
+
+        ``window``: the causal walk with ``attention_alibi_window`` / ``attention_alibi_window_backward`` in place of the causal
+        ops and the same refusals; with ``cache`` the K / V rows go into a ring (``Attention._run_causal_bct``)."""
         if (y is not None) != self.cross_attention:
             raise AgxError("Cross attention requires two inputs: this Transformer was built with context_y and got no y"
                            if y is None else "this Transformer was built without context_y and takes no second sequence y")
@@ -563,15 +622,16 @@ class TransformerBottleneck(nn.Module):
         self.num_quantizers = num_quantizers   # training.py:183 reads it
         self.use_som = False                    # utils.py:239
 
-    def quantize_bcl(self, x: Tensor, codebook_n=None, update_codebook=False, prioritize_early=False):
+    def quantize_bcl(self, x: Tensor, codebook_n=None, update_codebook=False, prioritize_early=False, cache=None):
+        """``cache`` (``Transformer.new_cache``; default None: the uncached call) is passed on to the transformer."""
         if self.transformer.cross_attention:
             raise AgxError("TransformerBottleneck: the transformer has a cross-attention layer (context_y) and the quantiser call "
                            "contract of CausalVQAE.forward carries no second sequence y -- call Transformer.forward(x, y) directly")
-        y = self.transformer.run_bct(x)
+        y = self.transformer.run_bct(x, cache=cache)
         return y, None, torch.zeros((), dtype=torch.float32, device=x.device)
 
-    def forward(self, x: Tensor, codebook_n=None, update_codebook=False, prioritize_early=False):
-        y, idx, loss = self.quantize_bcl(x.transpose(1, 2).contiguous())
+    def forward(self, x: Tensor, codebook_n=None, update_codebook=False, prioritize_early=False, cache=None):
+        y, idx, loss = self.quantize_bcl(x.transpose(1, 2).contiguous(), cache=cache)
         return y.transpose(1, 2).contiguous(), idx, loss
 
     def get_stale_clusters(self):

@@ -462,6 +462,42 @@ int agx_attention_alibi_causal_backward(const float *q, const float *kv, int64_t
 int agx_attention_causal_kernel_name(int32_t batch, int32_t heads, int32_t head_dim, int32_t tq, int32_t tk, int32_t backward,
                                      char *buf, size_t buf_len);
 
+/* Sliding-window causal self-attention (csrc/attention_window.hip; build-defined, the causal form above narrowed to the last
+ * `window` keys): the query at absolute position p = i + q_pos0 sees the keys j in [max(0, p - window + 1), p] only,
+ *     out[b,h,:,i] = sum_j softmax_j( q_i . k_j / scale_div - slopes[h] * (p - j) ) v_j
+ * window >= p + 1 for every query is agx_attention_alibi_causal; window = 1 returns v_p.  q, kv, the strides and out as there.
+ * The keys are the positions 0 .. q_pos0 + tq - 1 and key j sits in column j of a kv row (kv_ring = 0, the linear form:
+ * kv_row_stride >= q_pos0 + tq) or in column j mod kv_ring (kv_ring > 0, a ring cache: tq + min(window - 1, q_pos0) <= kv_ring <=
+ * kv_row_stride, so that the oldest key the first query sees, max(0, q_pos0 - window + 1), has not been overwritten by the
+ * newest; from q_pos0 >= window - 1 on that is tq + window - 1 <= kv_ring).  q_pos0 is 64-bit and
+ * a stream has no end: on a ring the launcher lowers every position by a multiple of lcm(64, kv_ring), which keeps the
+ * 64-key block alignment, the ring column and every p - j, and the kernel indexes in int32 (a lowered q_pos0 + tq beyond
+ * int32 -- only a ring of ~2^25 columns and more can get there -- is AGX_ERR_BAD_SHAPE).  Key blocks are aligned to absolute
+ * positions (block = j / 64), so a query's result does not depend on the chunk that delivered it, bit for bit.  Only the key
+ * blocks some query of a workgroup sees are walked.  A ring column outside a workgroup's window is never read as V and never
+ * reaches a score: it may hold anything (an older frame, NaN, unwritten memory).  fp32, Dh <= 128 (AGX_ERR_UNSUPPORTED
+ * beyond); window < 1, q_pos0 < 0, kv_ring < 0, kv_ring too small for tq + min(window - 1, q_pos0) or larger than kv_row_stride, a linear
+ * kv_row_stride < q_pos0 + tq, or a batch stride too small for the shape: AGX_ERR_BAD_SHAPE; batch, heads or tq <= 0: returns
+ * AGX_OK and launches nothing.  Every refusal happens before anything is launched and before any pointer is used. */
+int agx_attention_alibi_window(const float *q, const float *kv, int64_t q_batch_stride, int64_t kv_batch_stride,
+                               int64_t kv_row_stride, const float *slopes, float *out, int32_t batch, int32_t heads,
+                               int32_t head_dim, int32_t tq, int64_t q_pos0, int32_t window, int32_t kv_ring, float scale_div,
+                               void *stream);
+/* Backward of the full windowed self-attention (q_pos0 = 0, tq = t keys, linear kv, rows of pitch t), as
+ * agx_attention_alibi_causal_backward: three deterministic kernels, no atomics, dqkv written in place, `out` not read; the
+ * key / query blocks outside the band i - window < j <= i are skipped and a masked (i, j) pair contributes exactly 0.
+ * workspace = 2 * batch * heads * t floats, every float of it written (AGX_ERR_WORKSPACE when shorter). */
+size_t agx_attention_window_backward_workspace_bytes(int32_t batch, int32_t heads, int32_t t);
+int agx_attention_alibi_window_backward(const float *q, const float *kv, int64_t q_batch_stride, int64_t kv_batch_stride,
+                                        const float *slopes, const float *out, const float *dout, float *dq, float *dkv,
+                                        int64_t dq_batch_stride, int64_t dkv_batch_stride, float *workspace,
+                                        size_t workspace_bytes, int32_t batch, int32_t heads, int32_t head_dim, int32_t t,
+                                        int32_t window, float scale_div, void *stream);
+/* Host-only: "attention_window<DVT>" (DVT = 1 / 2 / 4 32-row tiles of the head dim), with backward != 0 the three backward
+ * kernels, "none" for an empty shape, or the launcher's refusal (code and message; window < 1 included). */
+int agx_attention_window_kernel_name(int32_t batch, int32_t heads, int32_t head_dim, int32_t tq, int32_t window,
+                                     int32_t backward, char *buf, size_t buf_len);
+
 /* ------------------------------------------------------------------------- *
  * Wavelet / multiresolution layers (networks/wavelets.py)                     *
  * ------------------------------------------------------------------------- */
