@@ -679,6 +679,104 @@ def attention_alibi_dropout_backward(q: Tensor, kv: Optional[Tensor], slopes: Te
     return dq if kv is None else (dq, dkv)
 
 
+# ------------------------------------------------------------------ ragged batches (include/agx.h "Ragged batches")
+def attention_ragged_kernel_name(batch: int, heads: int, head_dim: int, tq: int, tk: int, backward: bool = False) -> str:
+    """The kernel ``attention_alibi_ragged`` runs for this shape, with ``backward`` the three kernels of
+    ``attention_alibi_ragged_backward`` (host-only); ``AgxError`` with the launcher's message if it refuses."""
+    return _kernel_name("agx_attention_ragged_kernel_name", batch, heads, head_dim, tq, tk, bool(backward))
+
+
+def _len_arg(op: str, lengths: Optional[Tensor], batch: int, what: str) -> Optional[Tensor]:
+    """A per-row length array as the kernels read it: None (every row full), or ``batch`` contiguous int32 entries on the
+    device.  The values stay on the device -- the kernels clamp them -- so nothing here synchronises."""
+    if lengths is None:
+        return None
+    if not lengths.is_cuda or lengths.dtype != torch.int32 or lengths.dim() != 1 or not lengths.is_contiguous():
+        raise AgxError(f"{op}: {what} must be a contiguous int32 device tensor, got {lengths.dtype} {tuple(lengths.shape)} on "
+                       f"'{lengths.device}'")
+    if lengths.numel() != batch:
+        raise AgxError(f"{op}: {what} has {lengths.numel()} entries, the batch is {batch}")
+    return lengths
+
+
+def attention_alibi_ragged(q: Tensor, kv: Optional[Tensor], slopes: Tensor, heads: int, head_dim: int, scale_div: float,
+                           q_len: Optional[Tensor] = None, k_len: Optional[Tensor] = None) -> Tensor:
+    """softmax(Q K^T / scale_div + ALiBi) V over the first ``k_len[b]`` keys of every batch row, for its first ``q_len[b]``
+    queries; exactly 0 behind them (include/agx.h "Ragged batches") -> (B, H*Dh, Tq).  ``q`` (B, H*Dh, Tq) and ``kv``
+    (B, 2*H*Dh, Tk), or ``kv=None`` and ``q`` a self-attention (B, 3*H*Dh, T) qkv tensor (no copy).  The lengths are
+    contiguous int32 device tensors of B entries (None: every row is full), read by the kernel: no sync.  What lies at or
+    beyond a row's length may hold anything, NaN included.  fp32, head_dim <= 128."""
+    lib = _lib.load()
+    op = "attention_alibi_ragged"
+    _need_gpu(q, kv, slopes)
+    q = _f32c(q)
+    kv = None if kv is None else _f32c(kv)
+    b, tq, tk, hd = _drop_shapes(op, q, kv, heads, head_dim)
+    q_len, k_len = _len_arg(op, q_len, b, "q_len"), _len_arg(op, k_len, b, "k_len")
+    out = torch.empty((b, hd, tq), dtype=torch.float32, device=q.device)
+    qp, kp, sq, skv = (_ptr(q), _ptr(kv), hd * tq, 2 * hd * tk) if kv is not None else (_ptr(q), _off(q, hd * tq), 3 * hd * tq, 3 * hd * tq)
+    tok = None
+    if _observer is not None:    # the full shape: the lengths live on the device
+        tok = _observer.begin("other", ("attention_alibi_ragged:flash", 4 * (q.numel() + (0 if kv is None else kv.numel()) + out.numel()),
+                                        2 * b * heads * tq * tk * head_dim))
+    _lib.check(lib.agx_attention_alibi_ragged(qp, kp, sq, skv, _ptr(_f32c(slopes)), _ptr(q_len), _ptr(k_len), _ptr(out), b, heads,
+                                              head_dim, tq, tk, float(scale_div), _stream()), "agx_attention_alibi_ragged")
+    if tok is not None:
+        _observer.end(tok)
+    return out
+
+
+def attention_alibi_ragged_backward(q: Tensor, kv: Optional[Tensor], slopes: Tensor, out: Tensor, dout: Tensor, heads: int,
+                                    head_dim: int, scale_div: float, q_len: Optional[Tensor] = None,
+                                    k_len: Optional[Tensor] = None):
+    """Backward of ``attention_alibi_ragged`` with the same lengths: (dq, dkv), or with ``kv=None`` the one (B, 3*H*Dh, T)
+    dqkv tensor, written in place through pointers and strides.  Exactly 0 at and beyond a row's lengths; ``dout`` there may
+    hold anything.  Deterministic."""
+    lib = _lib.load()
+    op = "attention_alibi_ragged_backward"
+    _need_gpu(q, kv, slopes, out, dout)
+    q, out, dout = _f32c(q), _f32c(out), _f32c(dout)
+    kv = None if kv is None else _f32c(kv)
+    b, tq, tk, hd = _drop_shapes(op, q, kv, heads, head_dim)
+    if tuple(out.shape) != (b, hd, tq) or dout.shape != out.shape:
+        raise AgxError(f"{op}: out {tuple(out.shape)} / dout {tuple(dout.shape)} are not {(b, hd, tq)}")
+    q_len, k_len = _len_arg(op, q_len, b, "q_len"), _len_arg(op, k_len, b, "k_len")
+    dq = torch.empty_like(q)
+    if kv is not None:
+        dkv = torch.empty_like(kv)
+        ptrs = (_ptr(q), _ptr(kv), hd * tq, 2 * hd * tk)
+        dptrs = (_ptr(dq), _ptr(dkv), hd * tq, 2 * hd * tk)
+    else:
+        dkv = None
+        ptrs = (_ptr(q), _off(q, hd * tq), 3 * hd * tq, 3 * hd * tq)
+        dptrs = (_ptr(dq), _off(dq, hd * tq), 3 * hd * tq, 3 * hd * tq)
+    nbytes = int(lib.agx_attention_ragged_backward_workspace_bytes(b, heads, tq))
+    ws = _workspace(nbytes, q.device, "agx_attention_ragged_backward_workspace_bytes")
+    count_macs("attention_bwd", 5 * b * heads * tq * tk * head_dim)
+    _lib.check(lib.agx_attention_alibi_ragged_backward(*ptrs, _ptr(_f32c(slopes)), _ptr(q_len), _ptr(k_len), _ptr(out), _ptr(dout),
+                                                       *dptrs, _ptr(ws), nbytes, b, heads, head_dim, tq, tk, float(scale_div),
+                                                       _stream()), "agx_attention_alibi_ragged_backward")
+    return dq if kv is None else (dq, dkv)
+
+
+def mask_tail(x: Tensor, lengths: Optional[Tensor], out: Optional[Tensor] = None) -> Tensor:
+    """``out[b, c, i] = x[b, c, i] if i < lengths[b] else 0`` over fp32 (B, C, T): a select, so a NaN tail becomes 0.
+    ``out`` may be ``x`` (in place); default: a new tensor.  It is its own backward."""
+    lib = _lib.load()
+    _need_gpu(x, out)
+    if x.dim() != 3:
+        raise AgxError(f"mask_tail: x is {tuple(x.shape)}, expected (B, C, T)")
+    x = _f32c(x)
+    b, c, t = x.shape
+    lengths = _len_arg("mask_tail", lengths, b, "lengths")
+    if out is None:
+        out = torch.empty_like(x)
+    elif out.shape != x.shape or out.dtype != torch.float32 or not out.is_contiguous():
+        raise AgxError(f"mask_tail: out must be a contiguous float32 tensor of x's shape {tuple(x.shape)}")
+    _lib.check(lib.agx_mask_tail(_ptr(x), _ptr(lengths), _ptr(out), b, c, t, _stream()), "agx_mask_tail")
+    return out
+
+
 # ------------------------------------------------------------------ causal attention (include/agx.h "Causal self-attention")
 def attention_causal_kernel_name(batch: int, heads: int, head_dim: int, tq: int, tk: int, backward: bool = False) -> str:
     """The kernel ``attention_alibi_causal`` runs for this shape, with ``backward`` the three kernels of

@@ -23,6 +23,11 @@ training mode only, on counter-based masks generated inside the kernels of
 ``-slope_h (i - j)`` -- on the kernels of ``csrc/attention_causal.hip``, and lets a ``Transformer`` run incrementally on a
 key/value cache (``Transformer.new_cache``).  ``window=W`` (with ``causal=True``) narrows every query to its last ``W`` keys
 on the kernels of ``csrc/attention_window.hip``; the cache is then a ring of fixed size and the stream has no end.
+``lengths=`` / ``y_lengths=`` (build-defined, keyword-only, default None) give every batch row of ``x`` / ``y`` its own valid
+length for a right-padded ragged batch: the symmetric layers run on the kernels of ``csrc/attention_ragged.hip``, which read
+the lengths from device memory, the block's output is exactly 0 at padded positions, and its valid positions and every
+gradient are independent of what the padding held, NaN included (``Transformer._hip_bct``).  fp32, no dropout, not on a
+causal layer -- whose valid frames never see right padding anyway.
 The ``nn.LayerNorm`` / ``nn.Linear`` children only hold parameters.
 """
 from __future__ import annotations
@@ -166,6 +171,26 @@ def _checked_window(window, causal, context_x) -> Optional[int]:
     return int(window)
 
 
+def _checked_lengths(what: str, lengths, batch: int, t: int, device) -> Optional[Tensor]:
+    """A ``lengths=`` / ``y_lengths=`` argument as the kernels read it: ``batch`` int32 entries on ``device``, or None.
+    A Python sequence or a CPU integer tensor is validated here (0 <= length <= t) and copied to the device.  A device
+    integer tensor is used as it is, without a sync: the kernels clamp what it holds when they run, so under graph capture
+    a replay reads the lengths of the replay."""
+    if lengths is None:
+        return None
+    on_device = isinstance(lengths, Tensor) and lengths.is_cuda
+    host = lengths if on_device else torch.as_tensor(lengths)
+    if host.dtype.is_floating_point or host.dtype.is_complex or host.dtype == torch.bool:
+        raise AgxError(f"{what} must hold integers, got {host.dtype}")
+    if host.dim() != 1 or host.numel() != batch:
+        raise AgxError(f"{what} has shape {tuple(host.shape)}: one length per batch row is ({batch},)")
+    if on_device:
+        return host.to(torch.int32).contiguous()
+    if batch and (int(host.min()) < 0 or int(host.max()) > t):
+        raise AgxError(f"{what} = {host.tolist()}: every length must lie in [0, {t}], the padded length")
+    return host.to(torch.int32).to(device)
+
+
 class Attention(nn.Module):
     """transformers.py:95-191 (pre-LN multi-head attention with ALiBi).  ``context_y`` makes it a cross-attention layer:
     ``W_q`` reads ``LN(x)``, ``W_k`` / ``W_v`` (stacked into one projection) read the second sequence ``y`` as given."""
@@ -205,8 +230,20 @@ class Attention(nn.Module):
     def _attn(self) -> dict:
         return dict(slopes=self.alibi_obj.head_scalars, heads=self.n_heads, head_dim=self.dim_head, scale_div=self.dim_head ** 0.5)
 
+    def _check_ragged(self) -> None:
+        """The refusals of a call with ``lengths`` / ``y_lengths``, before any op."""
+        if self.causal:
+            raise AgxError("lengths= on a causal" + (" (windowed)" if self.window is not None else "") + " layer: a causal layer's "
+                           "valid frames never see right padding, so the call without lengths is already correct")
+        if _active_p(self.dropout) > 0:
+            raise AgxError("lengths= with an active dropout site (training mode, dropout > 0): dropout on ragged batches has "
+                           "no kernel (eval mode runs)")
+        if self.attention_dtype != "fp32":
+            raise AgxError(f"lengths=: ragged attention runs in fp32, attention_dtype = {self.attention_dtype!r} has no kernel")
+
     def _run_cross_bct(self, x: Tensor, residual: Optional[Tensor], keep: Optional[dict], y: Optional[Tensor],
-                       drop: Optional[tuple] = None) -> Tensor:
+                       drop: Optional[tuple] = None, lengths: Optional[Tensor] = None,
+                       y_lengths: Optional[Tensor] = None) -> Tensor:
         """The cross-attention layer: LN1 -> Q projection, KV projection of ``y`` (no LayerNorm, transformers.py:170) ->
         attention -> W_o (+res).  Lengths: what the reference runs -- its transposed ``M[:, :Tx, :Ty]`` (:92) must broadcast,
         ``Tx <= context_y and Ty <= context_x`` -- and the intended reading ``Tx <= context_x and Ty <= context_y``; the
@@ -233,6 +270,8 @@ class Attention(nn.Module):
         if p > 0:
             seed, layer = _site(drop, self)
             o = ops.attention_alibi_dropout(q, kv, p=p, seed=seed, stream_id=4 * layer + SITE_PROB, **self._attn())
+        elif lengths is not None or y_lengths is not None:
+            o = ops.attention_alibi_ragged(q, kv, q_len=lengths, k_len=y_lengths, **self._attn())
         else:
             o = ops.attention_alibi_cross(q, kv, **self._attn())
         if keep is not None:
@@ -297,7 +336,8 @@ class Attention(nn.Module):
         return self._o.forward(o, EPI_RESIDUAL if residual is not None else 0, residual)
 
     def run_bct(self, x: Tensor, residual: Optional[Tensor] = None, keep: Optional[dict] = None,
-                y: Optional[Tensor] = None, drop: Optional[tuple] = None, kv_cache: Optional[tuple] = None) -> Tensor:
+                y: Optional[Tensor] = None, drop: Optional[tuple] = None, kv_cache: Optional[tuple] = None, *,
+                lengths=None, y_lengths=None) -> Tensor:
         """(B, dim, T) -> W_o(attn(LN(x))) [+ residual], channel-major; a cross-attention layer also takes ``y``
         (B, dim, Ty).  ``keep`` marks the training forward: the dict
         receives what ``backward_bct`` reads, and the attention arithmetic is fp32 whatever ``attention_dtype`` says
@@ -308,11 +348,26 @@ class Attention(nn.Module):
         residual and ``dropout_add(., residual)``.  ``drop`` = (seed, layer) from the enclosing ``Transformer``.  fp32,
         head_dim <= 128.  In eval mode, or with ``dropout == 0``, the walk is the one it always was.
 
-        A ``causal`` layer runs ``_run_causal_bct`` (fp32, no dropout in training mode); ``kv_cache`` is its cached call."""
+        A ``causal`` layer runs ``_run_causal_bct`` (fp32, no dropout in training mode); ``kv_cache`` is its cached call.
+
+        ``lengths`` (``y_lengths``: a cross-attention layer's second sequence) are the valid lengths of the batch rows
+        (``_checked_lengths``): the layer's launches are unchanged but for ``attention_alibi_ragged`` where its attention op
+        was, with ``q_len = k_len = lengths`` (cross: ``k_len = y_lengths``).  Only the attention mixes positions, so the
+        valid positions of the result do not depend on the padding; the padded ones hold whatever the pointwise ops make of
+        it -- zeroing them (``ops.mask_tail``) is the caller's part: ``forward`` and ``Transformer`` do it."""
+        if lengths is not None or y_lengths is not None:
+            if kv_cache is not None:
+                raise AgxError("lengths= with a key/value cache: a cached call is causal and takes no lengths")
+            self._check_ragged()
+            if y_lengths is not None and not self.cross_attention:
+                raise AgxError("y_lengths= on a self-attention layer (built without context_y): there is no second sequence")
+            lengths = _checked_lengths("lengths", lengths, x.shape[0], x.shape[-1], x.device)
+            if y_lengths is not None and y is not None and y.dim() == 3:
+                y_lengths = _checked_lengths("y_lengths", y_lengths, y.shape[0], y.shape[-1], y.device)
         if kv_cache is not None and not self.causal:
             raise AgxError("a key/value cache needs a causal self-attention layer (causal=True, no context_y)")
         if self.cross_attention:
-            return self._run_cross_bct(x, residual, keep, y, drop)
+            return self._run_cross_bct(x, residual, keep, y, drop, lengths, y_lengths)
         if y is not None:
             raise AgxError("a self-attention layer (built without context_y) takes no second sequence y")
         if x.shape[-1] > self.context:
@@ -337,15 +392,20 @@ class Attention(nn.Module):
         xn = _ln(self.norm, x)
         qkv = self._qkv.forward(xn)
         bf16 = self.attention_dtype == "bf16" and keep is None
-        o = ops.attention_alibi(qkv, precision=ops.ATTN_BF16 if bf16 else ops.ATTN_FP32, **self._attn())
+        if lengths is not None:
+            o = ops.attention_alibi_ragged(qkv, None, q_len=lengths, k_len=lengths, **self._attn())
+        else:
+            o = ops.attention_alibi(qkv, precision=ops.ATTN_BF16 if bf16 else ops.ATTN_FP32, **self._attn())
         if keep is not None:
             keep.update(h=x, xn1=xn, qkv=qkv, o=o)
         return self._o.forward(o, EPI_RESIDUAL if residual is not None else 0, residual)
 
-    def backward_bct(self, kept: dict, g: Tensor, want_dy: bool = False):
+    def backward_bct(self, kept: dict, g: Tensor, want_dy: bool = False, lengths: Optional[Tensor] = None,
+                     y_lengths: Optional[Tensor] = None):
         """``g`` = the gradient of ``run_bct(h, residual=h, keep=kept)`` -> (dh, gradients in ``parameters()`` order, dy).
         ``dy`` is the gradient of a cross-attention layer's second sequence -- the backward-data of the stacked W_k / W_v
-        projection, run only when ``want_dy`` -- and None otherwise."""
+        projection, run only when ``want_dy`` -- and None otherwise.  ``lengths`` / ``y_lengths``: the device tensors the
+        forward ran with (``attention_alibi_ragged_backward`` in the attention backward's place)."""
         d = kept.get("drop")
         d = d if d is not None and d.get("attn") else None      # the forward's (seed, layer, p): its masks are regenerated
         if d is not None:    # the W_o site: the residual branch takes g unmasked (``add=g`` below)
@@ -356,6 +416,9 @@ class Attention(nn.Module):
         if self.cross_attention:
             if d is not None:
                 dq, dkv = ops.attention_alibi_dropout_backward(kept["q"], kept["kv"], dout=do, out=kept["o"], **mask, **self._attn())
+            elif lengths is not None or y_lengths is not None:
+                dq, dkv = ops.attention_alibi_ragged_backward(kept["q"], kept["kv"], dout=do, out=kept["o"], q_len=lengths,
+                                                              k_len=y_lengths, **self._attn())
             else:
                 dq, dkv = ops.attention_alibi_cross_backward(kept["q"], kept["kv"], dout=do, out=kept["o"], **self._attn())
             dxn, g_q = self._q.backward(kept["xn1"], dq)
@@ -368,16 +431,35 @@ class Attention(nn.Module):
             dqkv = ops.attention_alibi_window_backward(kept["qkv"], out=kept["o"], dout=do, window=self.window, **self._attn())
         elif self.causal:
             dqkv = ops.attention_alibi_causal_backward(kept["qkv"], out=kept["o"], dout=do, **self._attn())
+        elif lengths is not None:
+            dqkv = ops.attention_alibi_ragged_backward(kept["qkv"], None, dout=do, out=kept["o"], q_len=lengths, k_len=lengths,
+                                                       **self._attn())
         else:
             dqkv = ops.attention_alibi_backward(kept["qkv"], dout=do, out=kept["o"], **self._attn())
         dxn, g_qkv = self._qkv.backward(kept["xn1"], dqkv)
         dh, dweight, dbias = _ln_bwd(self.norm, kept["h"], dxn, add=g)
         return dh, [dweight, dbias] + g_qkv + g_o, None
 
-    def forward(self, x: Tensor, y=None) -> Tensor:
-        """Reference layout: (B, T, dim) [, (B, Ty, dim)] -> (B, T, dim)."""
+    def forward(self, x: Tensor, y=None, *, lengths=None, y_lengths=None) -> Tensor:
+        """Reference layout: (B, T, dim) [, (B, Ty, dim)] -> (B, T, dim).  With ``lengths`` / ``y_lengths`` (``run_bct``) the
+        padded tails of the inputs are zeroed first and the padded tail of the result after: exactly 0 there."""
         y = None if y is None else y.transpose(1, 2).contiguous()
-        return self.run_bct(x.transpose(1, 2).contiguous(), y=y).transpose(1, 2).contiguous()
+        x = x.transpose(1, 2).contiguous()
+        if lengths is None and y_lengths is None:
+            return self.run_bct(x, y=y).transpose(1, 2).contiguous()
+        self._check_ragged()
+        if y_lengths is not None and (not self.cross_attention or y is None):
+            raise AgxError("y_lengths= on a self-attention layer (built without context_y): there is no second sequence")
+        lengths = _checked_lengths("lengths", lengths, x.shape[0], x.shape[-1], x.device)
+        if y_lengths is not None:
+            y_lengths = _checked_lengths("y_lengths", y_lengths, y.shape[0], y.shape[-1], y.device)
+            y = ops.mask_tail(y, y_lengths)               # out of place: the caller's tensor is not modified
+        if lengths is not None:
+            x = ops.mask_tail(x, lengths)
+        out = self.run_bct(x, y=y, lengths=lengths, y_lengths=y_lengths)
+        if lengths is not None:
+            ops.mask_tail(out, lengths, out=out)
+        return out.transpose(1, 2).contiguous()
 
 
 class FeedForward(nn.Module):
@@ -438,13 +520,20 @@ class _TransformerNative(torch.autograd.Function):
     adds fused as ``add``), the GELU gradient in a bwd-data epilogue; the dropout masks of a training-mode forward are
     regenerated from the seed saved in the context (``agx_attention_alibi_dropout_backward``, ``agx_dropout_add``).
     Every layer, the first included, computes its input gradient; ``y`` (None without cross-attention) is a differentiable
-    input too: its gradient is the backward-data of the cross layer's stacked W_k / W_v projection."""
+    input too: its gradient is the backward-data of the cross layer's stacked W_k / W_v projection.
+
+    ``lens`` = (lengths, y_lengths), the checked device tensors of a ragged call (``Transformer.run_bct``), or None: they
+    travel in the context as non-differentiable values.  The backward masks the incoming gradient's tail first
+    (``mask_tail``, out of place), then walks as usual with ``attention_alibi_ragged_backward``: every tensor the forward
+    kept is finite at padded positions and every gradient there exactly 0, so the padding contributes exactly 0 to every
+    parameter gradient and ``dx`` / ``dy`` come out exactly 0 there."""
 
     @staticmethod
-    def forward(ctx, tf, x: Tensor, y: Optional[Tensor], *params: Tensor):
+    def forward(ctx, tf, lens, x: Tensor, y: Optional[Tensor], *params: Tensor):
         keep = []
+        ctx.lens = lens
         with torch.no_grad():
-            out = tf._hip_bct(x.detach(), keep, None if y is None else y.detach())
+            out = tf._hip_bct(x.detach(), keep, None if y is None else y.detach(), lens=lens)
         ctx.drop = [kept.pop("drop", None) for kept in keep]     # per layer: the seed, layer and probabilities of its masks
         ctx.tf, ctx.names = tf, [(li, name) for li, kept in enumerate(keep) for name in kept]
         ctx.save_for_backward(*[t for kept in keep for t in kept.values()])
@@ -456,13 +545,20 @@ class _TransformerNative(torch.autograd.Function):
         for (li, name), t in zip(ctx.names, ctx.saved_tensors):
             keep[li][name] = t
         g, grads, gy = g.contiguous(), [], None
+        lengths, y_lengths = ctx.lens if ctx.lens is not None else (None, None)
+        if lengths is not None:
+            g = ops.mask_tail(g, lengths)                   # the backward of the block's last op
         for (attention, ff), kept in zip(reversed(ctx.tf.layers), reversed(keep)):
             g, g_ff = ff.backward_bct(kept, g)              # x2 = x1 + W2 gelu(W1 LN2(x1) + b1) + b2
             # x1 = h + W_o attn(W_qkv LN1(h))  (cross: W_q LN1(h), W_kv y -- dy only when y asks for a gradient)
-            g, g_attention, dy = attention.backward_bct(kept, g, want_dy=ctx.needs_input_grad[2])
+            if ctx.lens is None:
+                g, g_attention, dy = attention.backward_bct(kept, g, want_dy=ctx.needs_input_grad[3])
+            else:
+                g, g_attention, dy = attention.backward_bct(kept, g, want_dy=ctx.needs_input_grad[3], lengths=lengths,
+                                                            y_lengths=y_lengths if attention.cross_attention else None)
             grads = g_attention + g_ff + grads              # the order of Transformer.parameters()
             gy = dy if attention.cross_attention else gy
-        return (None, g if ctx.needs_input_grad[1] else None, gy, *grads)
+        return (None, None, g if ctx.needs_input_grad[2] else None, gy, *grads)
 
 
 class TransformerCache:
@@ -546,8 +642,29 @@ class Transformer(nn.Module):
             raise AgxError(f"cached call: {cache.length} cached + {x.shape[-1]} new frames exceed min(capacity {cache.capacity}, "
                            f"context_x {self.context_x}) = {limit}")
 
+    def _check_lengths(self, x: Tensor, y: Optional[Tensor], cache, lengths, y_lengths) -> tuple:
+        """The refusals of a ragged call, before any op, and its (lengths, y_lengths) as checked device tensors."""
+        if cache is not None:
+            raise AgxError("lengths= with cache=: a cached call is causal, and a causal layer's valid frames never see right "
+                           "padding -- run it without lengths")
+        for attention, _ in self.layers:
+            attention._check_ragged()
+        if self._dropout_active():
+            raise AgxError("lengths= with an active dropout site (training mode, dropout > 0): dropout on ragged batches has "
+                           "no kernel (eval mode runs)")
+        if y_lengths is not None and not self.cross_attention:
+            raise AgxError("y_lengths= on a Transformer without a cross-attention layer (built without context_y)")
+        if x.dim() != 3:
+            raise AgxError(f"lengths=: x is {tuple(x.shape)}, expected (B, dim, T)")
+        lengths = _checked_lengths("lengths", lengths, x.shape[0], x.shape[-1], x.device)
+        if y_lengths is not None:
+            if y is None or y.dim() != 3:
+                raise AgxError("y_lengths= without a second sequence y of shape (B, dim, Ty)")
+            y_lengths = _checked_lengths("y_lengths", y_lengths, y.shape[0], y.shape[-1], y.device)
+        return lengths, y_lengths
+
     def _hip_bct(self, x: Tensor, keep: Optional[list] = None, y: Optional[Tensor] = None,
-                 cache: Optional[TransformerCache] = None) -> Tensor:
+                 cache: Optional[TransformerCache] = None, lens: Optional[tuple] = None) -> Tensor:
         """The one forward walk, LN1 -> QKV -> attention -> W_o (+res) -> LN2 -> FFN-in (GELU) -> FFN-out (+res) per layer:
         7 launches, both residual adds fused into the W_o / FFN-out conv epilogues (a cross-attention layer: 8, a Q and a
         KV projection in place of the QKV one).  ``keep``: the training forward
@@ -567,7 +684,16 @@ class Transformer(nn.Module):
         ``cache.length`` over ``cache.length + n`` keys -> W_o (+res) -> FFN; ``cache.length`` advances after the last layer.
 
         ``window``: the causal walk with ``attention_alibi_window`` / ``attention_alibi_window_backward`` in place of the causal
-        ops and the same refusals; with ``cache`` the K / V rows go into a ring (``Attention._run_causal_bct``)."""
+        ops and the same refusals; with ``cache`` the K / V rows go into a ring (``Attention._run_causal_bct``).
+
+        ``lens`` = (lengths, y_lengths) (``_check_lengths``; either may be None = every row is full), a right-padded ragged
+        batch: ``x0 = mask_tail(x, lengths)`` and ``y0 = mask_tail(y, y_lengths)`` out of place (the caller's tensors are not
+        modified), then per layer the unchanged launches with ``attention_alibi_ragged`` where the attention op was
+        (self-attention: ``q_len = k_len = lengths``; the cross layer: ``q_len = lengths``, ``k_len = y_lengths``), then
+        ``mask_tail`` in place on the block's output: two more launches per call (three with ``y_lengths``).  Every other op
+        is pointwise in time, so the output at valid positions does not depend on what the padding held (NaN included: the
+        masked inputs are finite) and is exactly 0 at padded ones.  ``lens=None``: no new op is called."""
+        lengths, y_lengths = lens if lens is not None else (None, None)
         if (y is not None) != self.cross_attention:
             raise AgxError("Cross attention requires two inputs: this Transformer was built with context_y and got no y"
                            if y is None else "this Transformer was built without context_y and takes no second sequence y")
@@ -576,11 +702,18 @@ class Transformer(nn.Module):
         seed = None
         if self._dropout_active():
             seed = self.last_dropout_seed = ops.draw_dropout_seed()
+        if lengths is not None:
+            x = ops.mask_tail(x, lengths)
+        if y_lengths is not None:
+            y = ops.mask_tail(y, y_lengths)
         for li, (attention, ff) in enumerate(self.layers):
             kept = None if keep is None else {}
             drop = None if seed is None else (seed, li)
             if cache is not None:
                 x = attention.run_bct(x, x, kept, None, drop, kv_cache=(cache.kv[li], cache.length))
+            elif lens is not None:
+                x = attention.run_bct(x, x, kept, y if attention.cross_attention else None, drop, lengths=lengths,
+                                      y_lengths=y_lengths if attention.cross_attention else None)
             else:
                 x = attention.run_bct(x, x, kept, y if attention.cross_attention else None, drop)
             x = ff.run_bct(x, x, kept, drop)
@@ -588,24 +721,40 @@ class Transformer(nn.Module):
                 keep.append(kept)
         if cache is not None:
             cache.length += x.shape[-1]
+        if lengths is not None:
+            x = ops.mask_tail(x, lengths, out=x)
         return x
 
-    def run_bct(self, x: Tensor, y: Optional[Tensor] = None, cache: Optional[TransformerCache] = None) -> Tensor:
+    def run_bct(self, x: Tensor, y: Optional[Tensor] = None, cache: Optional[TransformerCache] = None, *,
+                lengths=None, y_lengths=None) -> Tensor:
         """Channel-major (B, dim, T) in and out; ``y`` (B, dim, Ty) is the cross-attention layer's second sequence.  With
         autograd on, the backward runs on the HIP kernels too (_TransformerNative).  ``cache`` (``new_cache``): ``x`` holds
-        the next ``n`` frames of a causal Transformer's sequence; inference only."""
+        the next ``n`` frames of a causal Transformer's sequence; inference only.
+
+        ``lengths`` / ``y_lengths`` (keyword-only): the valid length of every batch row of ``x`` / ``y``, padding on the right
+        (``_hip_bct``: the walk and its contract).  A Python sequence or a CPU integer tensor of B entries is validated on the
+        host (0 <= length <= T) and copied to the device; a device integer tensor is used without a sync and clamped by the
+        kernels -- the form to pass under graph capture.  ``y_lengths`` alone leaves every row of ``x`` full.  Refused, before
+        any op: a causal or windowed Transformer, ``cache=``, an active dropout site, ``attention_dtype = "bf16"``,
+        ``y_lengths`` without a cross-attention layer, a size other than B."""
+        if lengths is not None or y_lengths is not None:
+            lens = self._check_lengths(x, y, cache, lengths, y_lengths)
+            if needs_grad(x, self) or (y is not None and torch.is_grad_enabled() and y.requires_grad):
+                return _TransformerNative.apply(self, lens, x, y, *list(self.parameters()))
+            return self._hip_bct(x, None, y, lens=lens)
         if cache is not None:
             self._check_cache(x, cache)
             if y is not None:
                 raise AgxError("this Transformer was built without context_y and takes no second sequence y")
             return self._hip_bct(x, None, None, cache)
         if needs_grad(x, self) or (y is not None and torch.is_grad_enabled() and y.requires_grad):
-            return _TransformerNative.apply(self, x, y, *list(self.parameters()))
+            return _TransformerNative.apply(self, None, x, y, *list(self.parameters()))
         return self._hip_bct(x, None, y)
 
-    def forward(self, x: Tensor, y=None, cache: Optional[TransformerCache] = None) -> Tensor:
+    def forward(self, x: Tensor, y=None, cache: Optional[TransformerCache] = None, *, lengths=None, y_lengths=None) -> Tensor:
         y = None if y is None else y.transpose(1, 2).contiguous()
-        return self.run_bct(x.transpose(1, 2).contiguous(), y, cache).transpose(1, 2).contiguous()
+        return self.run_bct(x.transpose(1, 2).contiguous(), y, cache, lengths=lengths,
+                            y_lengths=y_lengths).transpose(1, 2).contiguous()
 
 
 class TransformerBottleneck(nn.Module):
@@ -622,16 +771,18 @@ class TransformerBottleneck(nn.Module):
         self.num_quantizers = num_quantizers   # training.py:183 reads it
         self.use_som = False                    # utils.py:239
 
-    def quantize_bcl(self, x: Tensor, codebook_n=None, update_codebook=False, prioritize_early=False, cache=None):
-        """``cache`` (``Transformer.new_cache``; default None: the uncached call) is passed on to the transformer."""
+    def quantize_bcl(self, x: Tensor, codebook_n=None, update_codebook=False, prioritize_early=False, cache=None, *,
+                     lengths=None):
+        """``cache`` (``Transformer.new_cache``; default None: the uncached call) and ``lengths`` (the valid frames of every
+        row of a right-padded batch, ``Transformer.run_bct``) are passed on to the transformer."""
         if self.transformer.cross_attention:
             raise AgxError("TransformerBottleneck: the transformer has a cross-attention layer (context_y) and the quantiser call "
                            "contract of CausalVQAE.forward carries no second sequence y -- call Transformer.forward(x, y) directly")
-        y = self.transformer.run_bct(x, cache=cache)
+        y = self.transformer.run_bct(x, cache=cache, lengths=lengths)
         return y, None, torch.zeros((), dtype=torch.float32, device=x.device)
 
-    def forward(self, x: Tensor, codebook_n=None, update_codebook=False, prioritize_early=False, cache=None):
-        y, idx, loss = self.quantize_bcl(x.transpose(1, 2).contiguous(), cache=cache)
+    def forward(self, x: Tensor, codebook_n=None, update_codebook=False, prioritize_early=False, cache=None, *, lengths=None):
+        y, idx, loss = self.quantize_bcl(x.transpose(1, 2).contiguous(), cache=cache, lengths=lengths)
         return y.transpose(1, 2).contiguous(), idx, loss
 
     def get_stale_clusters(self):

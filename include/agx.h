@@ -498,6 +498,48 @@ int agx_attention_alibi_window_backward(const float *q, const float *kv, int64_t
 int agx_attention_window_kernel_name(int32_t batch, int32_t heads, int32_t head_dim, int32_t tq, int32_t window,
                                      int32_t backward, char *buf, size_t buf_len);
 
+/* Ragged batches (csrc/attention_ragged.hip; build-defined): symmetric ALiBi attention, self or cross, with a valid length
+ * per batch row for the queries and for the keys.  q_len and k_len are device arrays of `batch` int32 entries, read by the
+ * kernels (no host copy, no sync; a captured graph replays with the lengths the arrays hold at replay time); either may be
+ * NULL, which means every row is full.  With ql = clamp(q_len[b], 0, tq) and kl = clamp(k_len[b], 0, tk), positions absolute
+ * and padding on the right:
+ *     out[b,h,:,i] = sum_{j < kl} softmax_{j < kl}( q_i . k_j / scale_div - slopes[h] * |i - j| ) v_j     for i < ql
+ *     out[b,h,:,i] = 0                                               for ql <= i < tq, and for every i when kl == 0
+ * q (rows of pitch tq) and kv (K rows, then V rows, of pitch tk) have their own base pointers and batch strides as in
+ * agx_attention_alibi_dropout: self-attention on a (B, 3*H*Dh, T) qkv tensor is q = qkv, kv = qkv + H*Dh*T, both strides
+ * 3*H*Dh*T.  out is contiguous (B, H*Dh, tq) and every element of it is written.  Nothing at or beyond a row's length
+ * reaches a result: q at i >= ql and K / V at j >= kl are never multiplied (loads are clamped below the length, V is staged
+ * as 0) and may hold anything, NaN included -- the contract of the key/value cache's tail.  Only ceil(kl / 64) key blocks
+ * are walked, and a workgroup without a valid query stores its zeros and returns.  A row computes bit for bit what the same
+ * call computes for that row cropped to (ql, kl) and run alone.  fp32, Dh <= 128 (AGX_ERR_UNSUPPORTED beyond); a batch
+ * stride too small for the shape: AGX_ERR_BAD_SHAPE; batch, heads, tq or tk <= 0: returns AGX_OK and launches nothing.
+ * Every refusal happens before anything is launched and before any pointer is used. */
+int agx_attention_alibi_ragged(const float *q, const float *kv, int64_t q_batch_stride, int64_t kv_batch_stride,
+                               const float *slopes, const int32_t *q_len, const int32_t *k_len, float *out, int32_t batch,
+                               int32_t heads, int32_t head_dim, int32_t tq, int32_t tk, float scale_div, void *stream);
+/* Backward: dq and dkv from q, kv and dout (contiguous (B, H*Dh, tq); `out` is not read), each through its own pointer and
+ * batch stride, so a dqkv tensor is written in place.  Three deterministic kernels as agx_attention_alibi_cross_backward
+ * (attn_ragged_bwd_stats / _dq / _dkv; P recomputed from the row statistics, no atomics: two calls agree bit for bit).  A
+ * masked (i, j) pair contributes exactly 0; dq is exactly 0 at i >= ql, dkv exactly 0 at j >= kl, both 0 for a row with
+ * ql == 0 or kl == 0; every element of dq and dkv is written.  Query blocks beyond ql and key blocks beyond kl are not
+ * walked.  dout at i >= ql is never read into a result and may hold anything.  workspace = 2 * batch * heads * tq floats
+ * (lse, delta) = agx_attention_ragged_backward_workspace_bytes() bytes, every float of it written, masked rows and queries
+ * included (AGX_ERR_WORKSPACE when shorter). */
+size_t agx_attention_ragged_backward_workspace_bytes(int32_t batch, int32_t heads, int32_t tq);
+int agx_attention_alibi_ragged_backward(const float *q, const float *kv, int64_t q_batch_stride, int64_t kv_batch_stride,
+                                        const float *slopes, const int32_t *q_len, const int32_t *k_len, const float *out,
+                                        const float *dout, float *dq, float *dkv, int64_t dq_batch_stride,
+                                        int64_t dkv_batch_stride, float *workspace, size_t workspace_bytes, int32_t batch,
+                                        int32_t heads, int32_t head_dim, int32_t tq, int32_t tk, float scale_div, void *stream);
+/* Host-only: "attention_ragged<DVT>" (DVT = 1 / 2 / 4 32-row tiles of the head dim), with backward != 0 the three backward
+ * kernels joined with '+', "none" for an empty shape, or the launcher's refusal (code and message). */
+int agx_attention_ragged_kernel_name(int32_t batch, int32_t heads, int32_t head_dim, int32_t tq, int32_t tk, int32_t backward,
+                                     char *buf, size_t buf_len);
+/* out[b,c,i] = i < clamp(len[b], 0, t) ? x[b,c,i] : 0 over contiguous fp32 (batch, channels, t) tensors: a select, not a
+ * multiply, so a NaN tail becomes 0.  out may alias x.  It is its own backward.  len: `batch` int32 entries on the device
+ * (NULL: a copy).  batch, channels or t <= 0: returns AGX_OK and launches nothing. */
+int agx_mask_tail(const float *x, const int32_t *len, float *out, int32_t batch, int32_t channels, int32_t t, void *stream);
+
 /* ------------------------------------------------------------------------- *
  * Wavelet / multiresolution layers (networks/wavelets.py)                     *
  * ------------------------------------------------------------------------- */
