@@ -135,6 +135,12 @@ SIGNATURES = {
                                                     c_void_p, c_int64, c_int64, c_void_p, c_size_t, c_int32, c_int32, c_int32,
                                                     c_int32, c_int32, c_float, c_void_p]),
     "agx_attention_window_kernel_name": (c_int, [c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, c_char_p, c_size_t]),
+    "agx_attention_alibi_stream": (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_int32,
+                                           c_int32, c_int32, c_int32, c_int32, c_int32, c_float, c_void_p]),
+    "agx_ring_write_pos": (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_int64, c_void_p, c_int32, c_int32, c_int32, c_int32,
+                                   c_void_p]),
+    "agx_stream_advance": (c_int, [c_void_p, c_int32, c_int64, c_void_p]),
+    "agx_attention_stream_kernel_name": (c_int, [c_int32, c_int32, c_int32, c_int32, c_int32, c_char_p, c_size_t]),
     "agx_attention_alibi_ragged": (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_int32,
                                            c_int32, c_int32, c_int32, c_int32, c_float, c_void_p]),
     "agx_attention_ragged_backward_workspace_bytes": (c_size_t, [c_int32, c_int32, c_int32]),

@@ -954,6 +954,96 @@ def ring_write(buf: Tensor, src: Tensor, col0: int) -> None:
     buf[:, :, col0:col0 + n].copy_(src)
 
 
+# ------------------------------------------------------------------ device-held stream positions (include/agx.h "Device-held")
+def attention_stream_kernel_name(batch: int, heads: int, head_dim: int, tq: int, window: int) -> str:
+    """The kernel ``attention_alibi_stream`` runs for this shape (host-only); ``AgxError`` with the launcher's message if it
+    refuses."""
+    return _kernel_name("agx_attention_stream_kernel_name", batch, heads, head_dim, tq, window)
+
+
+def _checked_pos(op: str, pos, b: int, device) -> Tensor:
+    """``pos`` as the kernels read it: a contiguous int64 device tensor of B entries, on the operands' device."""
+    if not isinstance(pos, Tensor) or pos.dtype != torch.int64 or pos.dim() != 1 or pos.numel() != b or not pos.is_contiguous():
+        what = f"{tuple(pos.shape)} {pos.dtype}" if isinstance(pos, Tensor) else type(pos).__name__
+        raise AgxError(f"{op}: pos must be a contiguous int64 device tensor of {b} entries (one position per batch row), got {what}")
+    _need_gpu(pos)
+    if pos.device != device:
+        raise AgxError(f"{op}: pos is on '{pos.device}', the operands are on '{device}'")
+    return pos
+
+
+def attention_alibi_stream(q: Tensor, kv: Tensor, pos: Tensor, slopes: Tensor, heads: int, head_dim: int, scale_div: float,
+                           window: int, ring: int) -> Tensor:
+    """``attention_alibi_window`` on a ring with the positions in device memory: row ``b``'s query ``i`` sits at
+    ``p = i + pos[b]`` and sees the keys ``max(0, p - window + 1) <= j <= p``, key ``j`` in column ``j mod ring`` of ``kv``
+    (B, 2*H*Dh, cap) -> (B, H*Dh, Tq).  ``q`` holds the queries in its first H*Dh rows ((B, H*Dh, Tq), or a (B, 3*H*Dh, Tq) qkv
+    tensor read in place).  ``pos``: a contiguous int64 device tensor of B entries, read by the kernel and never written -- no
+    sync, and a captured graph replays with the positions of the replay.  ``Tq + window - 1 <= ring <= cap``: the worst case
+    over every position, since the host reads none.  Row ``b`` is bit for bit ``attention_alibi_window(..., q_pos0=pos[b])``.
+    fp32, head_dim <= 128.
+
+    The bench observer cannot know the positions without a sync: it is told the blocks of the steady state (every row at
+    ``pos >= window - 1``), counted at ``pos = window - 1``; a row younger than that walks fewer blocks, and another alignment
+    of the window to the 64-key blocks can touch one block more or fewer."""
+    lib = _lib.load()
+    _need_gpu(q, kv, slopes)
+    q, kv = _f32c(q), _f32c(kv)
+    hd = heads * head_dim
+    b, cq, tq = q.shape
+    bk, ckv, cap = kv.shape
+    if cq not in (hd, 3 * hd):
+        raise AgxError(f"attention_alibi_stream: q has {cq} channels, expected {hd} (or a {3 * hd}-channel qkv tensor)")
+    if ckv != 2 * hd:
+        raise AgxError(f"attention_alibi_stream: kv has {ckv} channels, expected {2 * hd}")
+    if bk != b:
+        raise AgxError(f"attention_alibi_stream: q has batch {b}, kv has batch {bk}")
+    pos = _checked_pos("attention_alibi_stream", pos, b, q.device)
+    window = min(int(window), 0x7fffffff)
+    out = torch.empty((b, hd, tq), dtype=torch.float32, device=q.device)
+    tok = None
+    if _observer is not None and min(b, heads, tq) > 0 and window >= 1:
+        nbytes = 4 * (b * hd * tq + 2 * b * hd * min(cap, tq + window - 1))
+        tok = _observer.begin("other", ("attention_alibi_stream:flash", nbytes + 4 * out.numel(),
+                                        _window_macs(b, heads, head_dim, tq, window - 1, window)))
+    _lib.check(lib.agx_attention_alibi_stream(_ptr(q), _ptr(kv), cq * tq, 2 * hd * cap, cap, _ptr(pos), _ptr(_f32c(slopes)), _ptr(out),
+                                              b, heads, head_dim, tq, window, int(ring), float(scale_div), _stream()),
+               "agx_attention_alibi_stream")
+    if tok is not None:
+        _observer.end(tok)
+    return out
+
+
+def ring_write_pos(buf: Tensor, src: Tensor, pos: Tensor, ring: int) -> None:
+    """``buf[b, :, (pos[b] + t) mod ring] = src[b, :, t]`` for src (B, C, n) and buf (B, C, cap), ``n <= ring <= cap``: a chunk's
+    K / V rows into a ring cache at every row's own position, one launch, wrap included.  ``src`` is read in place: rows of
+    pitch ``n`` at any batch stride (the K / V rows ``qkv[:, H*Dh:]`` of a qkv tensor).  ``pos`` as in
+    ``attention_alibi_stream``; it is not written.  Allocates nothing."""
+    lib = _lib.load()
+    _need_gpu(buf, src)
+    if buf.dtype != torch.float32 or src.dtype != torch.float32 or buf.dim() != 3 or src.dim() != 3 or not buf.is_contiguous():
+        raise AgxError("ring_write_pos: buf must be a contiguous float32 (B, C, cap) tensor and src a float32 (B, C, n) tensor")
+    b, c, n = src.shape
+    if tuple(buf.shape[:2]) != (b, c) or src.device != buf.device:
+        raise AgxError(f"ring_write_pos: src {tuple(src.shape)} does not match buf {tuple(buf.shape)}")
+    if b == 0 or c == 0 or n == 0:
+        return
+    if (n > 1 and src.stride(2) != 1) or (c > 1 and src.stride(1) != n) or (b > 1 and src.stride(0) < c * n):
+        raise AgxError(f"ring_write_pos: src {tuple(src.shape)} with strides {tuple(src.stride())} is not rows of pitch {n}")
+    pos = _checked_pos("ring_write_pos", pos, b, buf.device)
+    cap = buf.shape[-1]
+    _lib.check(lib.agx_ring_write_pos(_ptr(buf), _ptr(src), c * cap, cap, src.stride(0) if b > 1 else c * n, _ptr(pos), b, c, n,
+                                      int(ring), _stream()), "agx_ring_write_pos")
+
+
+def stream_advance(pos: Tensor, n: int) -> None:
+    """``pos[b] += n`` on the device (exact int64 arithmetic): the advance of every row's stream by the ``n`` frames of a call."""
+    lib = _lib.load()
+    if not isinstance(pos, Tensor):
+        raise AgxError(f"stream_advance: pos must be a contiguous int64 device tensor, got {type(pos).__name__}")
+    pos = _checked_pos("stream_advance", pos, pos.numel(), pos.device)
+    _lib.check(lib.agx_stream_advance(_ptr(pos), pos.numel(), int(n), _stream()), "agx_stream_advance")
+
+
 def dropout_add(x: Tensor, res: Optional[Tensor], p: float, seed: int, stream_id: int, out: Optional[Tensor] = None) -> Tensor:
     """``res + mask * x / (1 - p)`` (``res`` None: no residual) over a contiguous tensor, the mask that of include/agx.h for
     (``seed``, ``stream_id``) on the linear index.  ``out`` may be ``x`` (in place).  With ``res=None`` and the forward's

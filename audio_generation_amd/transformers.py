@@ -23,6 +23,8 @@ training mode only, on counter-based masks generated inside the kernels of
 ``-slope_h (i - j)`` -- on the kernels of ``csrc/attention_causal.hip``, and lets a ``Transformer`` run incrementally on a
 key/value cache (``Transformer.new_cache``).  ``window=W`` (with ``causal=True``) narrows every query to its last ``W`` keys
 on the kernels of ``csrc/attention_window.hip``; the cache is then a ring of fixed size and the stream has no end.
+``Transformer.new_stream_cache`` keeps the position of every batch row in device memory (``csrc/attention_stream.hip``): a
+cached step can be captured and replayed, and a row restarts without the others.
 ``lengths=`` / ``y_lengths=`` (build-defined, keyword-only, default None) give every batch row of ``x`` / ``y`` its own valid
 length for a right-padded ragged batch: the symmetric layers run on the kernels of ``csrc/attention_ragged.hip``, which read
 the lengths from device memory, the block's output is exactly 0 at padded positions, and its valid positions and every
@@ -295,15 +297,24 @@ class Attention(nn.Module):
 
         With ``window`` the two causal ops are ``attention_alibi_window`` / ``attention_alibi_window_backward`` and the buffer
         is a ring: frame ``length + t`` goes to column ``(length + t) mod capacity`` (one strided copy, two when the chunk
-        wraps), ``n + min(window - 1, length) <= capacity`` and ``length`` has no limit."""
+        wraps), ``n + min(window - 1, length) <= capacity`` and ``length`` has no limit.
+
+        ``kv_cache`` = (ring, pos) with ``pos`` an int64 (B,) device tensor (``TransformerStreamCache``): the same walk with
+        ``ops.ring_write_pos`` / ``ops.attention_alibi_stream`` in place of ``ops.ring_write`` / ``ops.attention_alibi_window`` --
+        both read every row's position from ``pos`` -- and the worst-case bound ``n + window - 1 <= capacity``."""
         if self.attention_dtype != "fp32":
             raise AgxError(f"causal attention runs in fp32: attention_dtype = {self.attention_dtype!r} has no kernel")
         if _active_p(self.dropout) > 0:
             raise AgxError("causal attention with dropout > 0 in training mode has no kernel (eval mode runs)")
         if keep is not None and kv_cache is not None:
             raise AgxError("there is no backward through a cached call")
+        on_device = kv_cache is not None and isinstance(kv_cache[1], Tensor)     # a stream cache: positions in device memory
+        if on_device and self.window is None:
+            raise AgxError("device-held positions need a windowed layer (window=): the linear cache's limit needs the host to "
+                           "know the position")
         if kv_cache is not None and self.window is not None:
-            behind = min(self.window - 1, kv_cache[1])      # the cached frames the first new query still sees
+            # the cached frames the first new query still sees; the worst case where the host does not know the position
+            behind = self.window - 1 if on_device else min(self.window - 1, kv_cache[1])
             if x.shape[-1] + behind > kv_cache[0].shape[-1]:
                 raise AgxError(f"cached call: {x.shape[-1]} new frames + the {behind} cached frames their window reaches exceed "
                                f"the ring's {kv_cache[0].shape[-1]} columns")
@@ -315,6 +326,10 @@ class Attention(nn.Module):
         if self.window is not None:
             if kv_cache is None:
                 o = ops.attention_alibi_window(qkv, None, window=self.window, **self._attn())
+            elif on_device:      # pos (B,) is read by both kernels: one write launch, wrap included
+                buf, pos = kv_cache
+                ops.ring_write_pos(buf, qkv[:, self.inner_dim:, :], pos, buf.shape[-1])
+                o = ops.attention_alibi_stream(qkv, buf, pos, window=self.window, ring=buf.shape[-1], **self._attn())
             else:
                 buf, length = kv_cache
                 n, cap = x.shape[-1], buf.shape[-1]
@@ -577,6 +592,38 @@ class TransformerCache:
         self.length = 0
 
 
+class TransformerStreamCache:
+    """The ring key/value cache of a windowed causal ``Transformer`` with the positions in device memory, one per batch row
+    (``Transformer.new_stream_cache``): per layer one fp32 (B, 2*H*Dh, capacity) ring from ``torch.empty``, never cleared, and
+    ``pos``, an int64 (B,) device tensor of the frames every row has consumed.  The kernels read ``pos`` (``ops.ring_write_pos``,
+    ``ops.attention_alibi_stream``) and a kernel advances it (``ops.stream_advance``): a cached step makes no host decision that
+    depends on the position, so it can be captured once and replayed for ever, and every row has an age of its own --
+    ``reset(rows=[r])`` hands row ``r`` to a new stream while the others go on.
+
+    The host does not know the positions, so a call of ``n`` frames is bounded by the worst case over all of them,
+    ``n <= max_chunk = min(capacity - window + 1, context_x)``: stricter than ``TransformerCache`` at the start of a stream, where
+    ``n + min(window - 1, length) <= capacity`` lets the first call fill the whole ring."""
+
+    def __init__(self, kv: list, pos: Tensor, capacity: int, window: int, max_chunk: int):
+        self.kv, self.pos, self.batch, self.capacity, self.window, self.max_chunk = kv, pos, pos.numel(), capacity, window, max_chunk
+
+    def reset(self, rows=None) -> None:
+        """Zero the positions of ``rows`` (default: every row) with a device fill: those rows start a new stream at their next
+        call; what their ring columns hold is never read again.  Call it between steps, outside any captured graph."""
+        if rows is None:
+            self.pos.zero_()
+            return
+        rows = [int(r) for r in rows]
+        if any(not 0 <= r < self.batch for r in rows):
+            raise AgxError(f"reset: rows {rows} are not rows of a cache of batch {self.batch}")
+        for r in rows:
+            self.pos[r:r + 1].zero_()
+
+    def positions(self) -> list:
+        """The positions as a list of ints.  Synchronises: for tests and debugging, never called in the walk."""
+        return self.pos.tolist()
+
+
 class Transformer(nn.Module):
     """transformers.py:225-279: ``x += attn(x); x += ff(x)`` per layer.  ``causal=True`` (build-defined): every layer is
     causal self-attention, and ``new_cache`` / ``run_bct(x, cache=)`` run the block incrementally.  ``window=W`` (with
@@ -616,6 +663,45 @@ class Transformer(nn.Module):
         device = next(self.parameters()).device
         kv = [torch.empty((batch, 2 * a.inner_dim, capacity), dtype=torch.float32, device=device) for a, _ in self.layers]
         return TransformerCache(kv, batch, capacity, self.window)
+
+    def new_stream_cache(self, batch: int, capacity: Optional[int] = None) -> "TransformerStreamCache":
+        """An empty ring cache for ``batch`` live streams with the positions in device memory (``TransformerStreamCache``), on the
+        parameters' device: ``capacity`` columns per row (default ``context_x``, at least ``window``), every position 0.  Needs a
+        windowed causal self-attention Transformer.  A call takes ``1 <= n <= cache.max_chunk`` frames."""
+        if not self.causal or self.cross_attention or self.window is None:
+            raise AgxError("new_stream_cache: device-held positions need a windowed causal self-attention Transformer "
+                           "(causal=True, window=W, no context_y)")
+        capacity = self.context_x if capacity is None else int(capacity)
+        if batch < 1 or capacity < 1:
+            raise AgxError(f"new_stream_cache: batch = {batch}, capacity = {capacity}")
+        if capacity < self.window:
+            raise AgxError(f"new_stream_cache: a ring of capacity = {capacity} cannot hold a window of {self.window} frames")
+        device = next(self.parameters()).device
+        kv = [torch.empty((batch, 2 * a.inner_dim, capacity), dtype=torch.float32, device=device) for a, _ in self.layers]
+        pos = torch.zeros(batch, dtype=torch.int64, device=device)
+        return TransformerStreamCache(kv, pos, capacity, self.window, min(capacity - self.window + 1, self.context_x))
+
+    def _check_stream_cache(self, x: Tensor, cache: "TransformerStreamCache") -> None:
+        """The refusals of a call on a stream cache, before any op; none of them reads a position."""
+        if not self.causal or self.cross_attention or self.window is None:
+            raise AgxError("a stream cache needs a windowed causal self-attention Transformer (causal=True, window=W, no context_y)")
+        if needs_grad(x, self):
+            raise AgxError("there is no backward through a cached call: run it under torch.no_grad()")
+        if self._dropout_active():
+            raise AgxError("a cached call with an active dropout site (training mode, dropout > 0) has no kernel")
+        for attention, _ in self.layers:
+            if attention.attention_dtype != "fp32":
+                raise AgxError(f"causal attention runs in fp32: attention_dtype = {attention.attention_dtype!r} has no kernel")
+        if len(cache.kv) != len(self.layers):
+            raise AgxError(f"the cache holds {len(cache.kv)} layers, this Transformer has {len(self.layers)}")
+        if x.dim() != 3 or x.shape[0] != cache.batch:
+            raise AgxError(f"cached call: x is {tuple(x.shape)}, the cache was made for batch {cache.batch}")
+        if cache.window != self.window:
+            raise AgxError(f"the cache was made for window {cache.window}, this Transformer has window {self.window}")
+        n = x.shape[-1]
+        if n < 1 or n > cache.max_chunk:
+            raise AgxError(f"stream cache: a call takes 1 <= n <= max_chunk = {cache.max_chunk} frames (min(capacity {cache.capacity} "
+                           f"- window {self.window} + 1, context_x {self.context_x}): the worst case over every position), got {n}")
 
     def _check_cache(self, x: Tensor, cache: TransformerCache) -> None:
         """The refusals of a cached call, before any op."""
@@ -664,7 +750,7 @@ class Transformer(nn.Module):
         return lengths, y_lengths
 
     def _hip_bct(self, x: Tensor, keep: Optional[list] = None, y: Optional[Tensor] = None,
-                 cache: Optional[TransformerCache] = None, lens: Optional[tuple] = None) -> Tensor:
+                 cache=None, lens: Optional[tuple] = None) -> Tensor:
         """The one forward walk, LN1 -> QKV -> attention -> W_o (+res) -> LN2 -> FFN-in (GELU) -> FFN-out (+res) per layer:
         7 launches, both residual adds fused into the W_o / FFN-out conv epilogues (a cross-attention layer: 8, a Q and a
         KV projection in place of the QKV one).  ``keep``: the training forward
@@ -686,6 +772,11 @@ class Transformer(nn.Module):
         ``window``: the causal walk with ``attention_alibi_window`` / ``attention_alibi_window_backward`` in place of the causal
         ops and the same refusals; with ``cache`` the K / V rows go into a ring (``Attention._run_causal_bct``).
 
+        A ``TransformerStreamCache`` walks the same steps and differs at three places: the ring write is ``ops.ring_write_pos``,
+        the attention op is ``ops.attention_alibi_stream`` (both read every row's position from ``cache.pos``) and the advance is
+        ``ops.stream_advance`` -- 8 launches per layer and one advance per call, no host read of a position, no allocation but
+        the ops' outputs, one stream: the step can be captured (``torch.cuda.graph``) as a linear chain.
+
         ``lens`` = (lengths, y_lengths) (``_check_lengths``; either may be None = every row is full), a right-padded ragged
         batch: ``x0 = mask_tail(x, lengths)`` and ``y0 = mask_tail(y, y_lengths)`` out of place (the caller's tensors are not
         modified), then per layer the unchanged launches with ``attention_alibi_ragged`` where the attention op was
@@ -694,6 +785,7 @@ class Transformer(nn.Module):
         is pointwise in time, so the output at valid positions does not depend on what the padding held (NaN included: the
         masked inputs are finite) and is exactly 0 at padded ones.  ``lens=None``: no new op is called."""
         lengths, y_lengths = lens if lens is not None else (None, None)
+        on_device = isinstance(cache, TransformerStreamCache)
         if (y is not None) != self.cross_attention:
             raise AgxError("Cross attention requires two inputs: this Transformer was built with context_y and got no y"
                            if y is None else "this Transformer was built without context_y and takes no second sequence y")
@@ -710,7 +802,7 @@ class Transformer(nn.Module):
             kept = None if keep is None else {}
             drop = None if seed is None else (seed, li)
             if cache is not None:
-                x = attention.run_bct(x, x, kept, None, drop, kv_cache=(cache.kv[li], cache.length))
+                x = attention.run_bct(x, x, kept, None, drop, kv_cache=(cache.kv[li], cache.pos if on_device else cache.length))
             elif lens is not None:
                 x = attention.run_bct(x, x, kept, y if attention.cross_attention else None, drop, lengths=lengths,
                                       y_lengths=y_lengths if attention.cross_attention else None)
@@ -719,17 +811,19 @@ class Transformer(nn.Module):
             x = ff.run_bct(x, x, kept, drop)
             if keep is not None:
                 keep.append(kept)
-        if cache is not None:
+        if on_device:
+            ops.stream_advance(cache.pos, x.shape[-1])      # once per call: every layer read the same positions
+        elif cache is not None:
             cache.length += x.shape[-1]
         if lengths is not None:
             x = ops.mask_tail(x, lengths, out=x)
         return x
 
-    def run_bct(self, x: Tensor, y: Optional[Tensor] = None, cache: Optional[TransformerCache] = None, *,
-                lengths=None, y_lengths=None) -> Tensor:
+    def run_bct(self, x: Tensor, y: Optional[Tensor] = None, cache=None, *, lengths=None, y_lengths=None) -> Tensor:
         """Channel-major (B, dim, T) in and out; ``y`` (B, dim, Ty) is the cross-attention layer's second sequence.  With
         autograd on, the backward runs on the HIP kernels too (_TransformerNative).  ``cache`` (``new_cache``): ``x`` holds
-        the next ``n`` frames of a causal Transformer's sequence; inference only.
+        the next ``n`` frames of a causal Transformer's sequence; inference only.  A ``TransformerStreamCache``
+        (``new_stream_cache``) keeps one position per batch row in device memory: ``1 <= n <= cache.max_chunk``.
 
         ``lengths`` / ``y_lengths`` (keyword-only): the valid length of every batch row of ``x`` / ``y``, padding on the right
         (``_hip_bct``: the walk and its contract).  A Python sequence or a CPU integer tensor of B entries is validated on the
@@ -743,7 +837,10 @@ class Transformer(nn.Module):
                 return _TransformerNative.apply(self, lens, x, y, *list(self.parameters()))
             return self._hip_bct(x, None, y, lens=lens)
         if cache is not None:
-            self._check_cache(x, cache)
+            if isinstance(cache, TransformerStreamCache):
+                self._check_stream_cache(x, cache)
+            else:
+                self._check_cache(x, cache)
             if y is not None:
                 raise AgxError("this Transformer was built without context_y and takes no second sequence y")
             return self._hip_bct(x, None, None, cache)
@@ -751,7 +848,7 @@ class Transformer(nn.Module):
             return _TransformerNative.apply(self, None, x, y, *list(self.parameters()))
         return self._hip_bct(x, None, y)
 
-    def forward(self, x: Tensor, y=None, cache: Optional[TransformerCache] = None, *, lengths=None, y_lengths=None) -> Tensor:
+    def forward(self, x: Tensor, y=None, cache=None, *, lengths=None, y_lengths=None) -> Tensor:
         y = None if y is None else y.transpose(1, 2).contiguous()
         return self.run_bct(x.transpose(1, 2).contiguous(), y, cache, lengths=lengths,
                             y_lengths=y_lengths).transpose(1, 2).contiguous()

@@ -498,6 +498,38 @@ int agx_attention_alibi_window_backward(const float *q, const float *kv, int64_t
 int agx_attention_window_kernel_name(int32_t batch, int32_t heads, int32_t head_dim, int32_t tq, int32_t window,
                                      int32_t backward, char *buf, size_t buf_len);
 
+/* Device-held stream positions (csrc/attention_stream.hip; build-defined): agx_attention_alibi_window on a ring cache with the
+ * position of every batch row in device memory.  pos is a device array of `batch` int64 entries read by the kernels (no host
+ * copy, no sync; a captured graph replays with the positions the array holds at replay time, and rows have ages of their
+ * own): row b's query i sits at p = i + max(pos[b], 0) and sees the keys j in [max(0, p - window + 1), p], key j in column
+ * j mod kv_ring of a kv row.  q, kv, the strides, slopes and out as agx_attention_alibi_window; the ring is mandatory
+ * (kv_ring >= 1).  The host does not know the positions, so the bound is the worst case over all of them,
+ * tq + window - 1 <= kv_ring <= kv_row_stride (stricter than the host-position form while pos < window - 1), and the lowering
+ * by a multiple of lcm(64, kv_ring) is done by every workgroup; lcm(64, kv_ring) + window + tq + 128 beyond int32 is
+ * AGX_ERR_BAD_SHAPE.  Memory safety does not depend on what pos holds: columns are formed modulo the ring and the bound above
+ * holds for every position.  Row b computes bit for bit what agx_attention_alibi_window computes for it with q_pos0 = pos[b]
+ * on the same ring.  A ring column outside a workgroup's window may hold anything.  pos is never written.  fp32, Dh <= 128
+ * (AGX_ERR_UNSUPPORTED beyond); window < 1, kv_ring < tq + window - 1 or > kv_row_stride, a batch stride too small:
+ * AGX_ERR_BAD_SHAPE; batch, heads or tq <= 0: returns AGX_OK and launches nothing.  Every refusal happens before anything is
+ * launched and before any pointer is used. */
+int agx_attention_alibi_stream(const float *q, const float *kv, int64_t q_batch_stride, int64_t kv_batch_stride,
+                               int64_t kv_row_stride, const int64_t *pos, const float *slopes, float *out, int32_t batch,
+                               int32_t heads, int32_t head_dim, int32_t tq, int32_t window, int32_t kv_ring, float scale_div,
+                               void *stream);
+/* buf[b, c, (max(pos[b], 0) + t) mod ring] = src[b, c, t] for c < rows, t < n: a chunk's K / V rows into a ring cache at every
+ * row's own position, in one launch, wrap included.  src is read in place: rows of pitch n from src + b * src_batch_stride (the
+ * K / V rows of a qkv tensor); buf has rows of pitch buf_row_stride >= ring.  Exactly n columns of every row are written and
+ * nothing else; pos is not written.  1 <= n <= ring (no column is written twice), else AGX_ERR_BAD_SHAPE; batch, rows or
+ * n <= 0: AGX_OK, nothing launched.  Refusals precede every use of a pointer. */
+int agx_ring_write_pos(float *buf, const float *src, int64_t buf_batch_stride, int64_t buf_row_stride, int64_t src_batch_stride,
+                       const int64_t *pos, int32_t batch, int32_t rows, int32_t n, int32_t ring, void *stream);
+/* pos[b] += n for b < batch (exact int64 arithmetic, n >= 0): the advance of a stream, on the device.  Writes pos only. */
+int agx_stream_advance(int64_t *pos, int32_t batch, int64_t n, void *stream);
+/* Host-only: "attention_stream<DVT>" (DVT = 1 / 2 / 4 32-row tiles of the head dim), "none" for an empty shape, or the
+ * launcher's refusal (code and message; window < 1 included). */
+int agx_attention_stream_kernel_name(int32_t batch, int32_t heads, int32_t head_dim, int32_t tq, int32_t window, char *buf,
+                                     size_t buf_len);
+
 /* Ragged batches (csrc/attention_ragged.hip; build-defined): symmetric ALiBi attention, self or cross, with a valid length
  * per batch row for the queries and for the keys.  q_len and k_len are device arrays of `batch` int32 entries, read by the
  * kernels (no host copy, no sync; a captured graph replays with the lengths the arrays hold at replay time); either may be
