@@ -149,6 +149,16 @@ SIGNATURES = {
                                                     c_int32, c_int32, c_int32, c_int32, c_float, c_void_p]),
     "agx_attention_ragged_kernel_name": (c_int, [c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, c_char_p, c_size_t]),
     "agx_mask_tail": (c_int, [c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_void_p]),
+    "agx_attention_alibi_packed": (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_int32,
+                                           c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, c_float, c_void_p]),
+    "agx_attention_packed_backward_workspace_bytes": (c_size_t, [c_int32, c_int32]),
+    "agx_attention_alibi_packed_backward": (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_void_p,
+                                                    c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_void_p, c_size_t, c_int32,
+                                                    c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, c_float, c_void_p]),
+    "agx_attention_packed_kernel_name": (c_int, [c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, c_char_p,
+                                                 c_size_t]),
+    "agx_pack_rows": (c_int, [c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_void_p]),
+    "agx_unpack_rows": (c_int, [c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_void_p]),
     "agx_dropout_add": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_double, c_uint64, c_uint32, c_void_p]),
     "agx_conv_bwd_data_gelu": (c_int, [_PD, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "agx_multires_forward": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32,

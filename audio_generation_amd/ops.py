@@ -777,6 +777,143 @@ def mask_tail(x: Tensor, lengths: Optional[Tensor], out: Optional[Tensor] = None
     return out
 
 
+# ------------------------------------------------------------------ packed batches (include/agx.h "Packed variable-length batches")
+def attention_packed_kernel_name(n_seq: int, heads: int, head_dim: int, nq: int, nk: int, max_q: int, max_k: int,
+                                 backward: bool = False) -> str:
+    """The kernel ``attention_alibi_packed`` runs for this shape, with ``backward`` the three kernels of
+    ``attention_alibi_packed_backward`` (host-only); ``AgxError`` with the launcher's message if it refuses."""
+    return _kernel_name("agx_attention_packed_kernel_name", n_seq, heads, head_dim, nq, nk, max_q, max_k, bool(backward))
+
+
+def _cu_arg(op: str, cu: Optional[Tensor], what: str, n_seq: Optional[int] = None) -> Tensor:
+    """A ``cu_seqlens`` array as the kernels read it: contiguous int32 device tensor of ``n_seq + 1`` entries (``n_seq`` None:
+    any count of at least one sequence).  The values stay on the device -- the kernels clamp them -- so nothing here
+    synchronises."""
+    if not isinstance(cu, Tensor):
+        raise AgxError(f"{op}: {what} must be a contiguous int32 device tensor, got {type(cu).__name__}")
+    if not cu.is_cuda or cu.dtype != torch.int32 or cu.dim() != 1 or not cu.is_contiguous():
+        raise AgxError(f"{op}: {what} must be a contiguous int32 device tensor, got {cu.dtype} {tuple(cu.shape)} on '{cu.device}'")
+    if cu.numel() < 2 or (n_seq is not None and cu.numel() != n_seq + 1):
+        raise AgxError(f"{op}: {what} has {cu.numel()} entries, expected " +
+                       ("n_seq + 1 >= 2" if n_seq is None else f"n_seq + 1 = {n_seq + 1}"))
+    return cu
+
+
+def _packed_args(op: str, q: Tensor, kv: Optional[Tensor], heads: int, head_dim: int, cu_q, cu_k, max_q, max_k):
+    """(nq, nk, hd, cu_q, cu_k, n_seq, max_q, max_k) of a packed call; ``kv`` None: ``q`` is a (1, 3*H*Dh, N) qkv tensor and
+    ``cu_k`` / ``max_k`` default to the queries'."""
+    if q.dim() != 3 or q.shape[0] != 1 or (kv is not None and (kv.dim() != 3 or kv.shape[0] != 1)):
+        raise AgxError(f"{op}: a packed batch is one row, q (1, C, N)" + ("" if kv is None else " and kv (1, 2*H*Dh, Nk)") +
+                       f": got {tuple(q.shape)}" + ("" if kv is None else f" / {tuple(kv.shape)}"))
+    _, nq, nk, hd = _drop_shapes(op, q, kv, heads, head_dim)
+    if kv is None:
+        cu_k, max_k = (cu_q if cu_k is None else cu_k), (max_q if max_k is None else max_k)
+    elif cu_k is None or max_k is None:
+        raise AgxError(f"{op}: separate keys need cu_k and max_k")
+    cu_q = _cu_arg(op, cu_q, "cu_q")
+    n_seq = cu_q.numel() - 1
+    cu_k = _cu_arg(op, cu_k, "cu_k", n_seq)
+    if int(max_q) != max_q or int(max_k) != max_k or max_q < 0 or max_k < 0:
+        raise AgxError(f"{op}: max_q = {max_q}, max_k = {max_k}: the bounds of the sequence lengths are integers >= 0")
+    return nq, nk, hd, cu_q, cu_k, n_seq, int(max_q), int(max_k)
+
+
+def attention_alibi_packed(q: Tensor, kv: Optional[Tensor], slopes: Tensor, heads: int, head_dim: int, scale_div: float,
+                           cu_q: Tensor, max_q: int, cu_k: Optional[Tensor] = None, max_k: Optional[int] = None) -> Tensor:
+    """softmax(Q K^T / scale_div + ALiBi) V of every sequence of a packed batch on its own (include/agx.h "Packed
+    variable-length batches") -> (1, H*Dh, Nq).  Sequence ``s`` owns the query columns ``[cu_q[s], cu_q[s+1])`` and the key
+    columns ``[cu_k[s], cu_k[s+1])``; positions are relative to its start.  ``q`` (1, H*Dh, Nq) and ``kv`` (1, 2*H*Dh, Nk), or
+    ``kv=None`` and ``q`` a self-attention (1, 3*H*Dh, N) qkv tensor (no copy; ``cu_k`` / ``max_k`` default to the queries').
+    The cu arrays are contiguous int32 device tensors of n_seq + 1 entries, read by the kernel: no sync.  ``max_q`` /
+    ``max_k``: host-known upper bounds of the sequence lengths (they size the grid).  Exactly 0 in the columns no sequence
+    owns; what the neighbours and the slack of the inputs hold never reaches a result.  fp32, head_dim <= 128."""
+    lib = _lib.load()
+    op = "attention_alibi_packed"
+    _need_gpu(q, kv, slopes)
+    q = _f32c(q)
+    kv = None if kv is None else _f32c(kv)
+    nq, nk, hd, cu_q, cu_k, n_seq, max_q, max_k = _packed_args(op, q, kv, heads, head_dim, cu_q, cu_k, max_q, max_k)
+    out = torch.empty((1, hd, nq), dtype=torch.float32, device=q.device)
+    qp, kp = (_ptr(q), _ptr(kv)) if kv is not None else (_ptr(q), _off(q, hd * nq))
+    tok = None
+    if _observer is not None:    # an upper bound of the work, n_seq * max_q * max_k pairs: the lengths live on the device
+        tok = _observer.begin("other", ("attention_alibi_packed:flash", 4 * (q.numel() + (0 if kv is None else kv.numel()) + out.numel()),
+                                        2 * heads * min(nq, n_seq * max_q) * min(nk, max_k) * head_dim))
+    _lib.check(lib.agx_attention_alibi_packed(qp, kp, nq, nk, _ptr(_f32c(slopes)), _ptr(cu_q), _ptr(cu_k), _ptr(out), n_seq, heads,
+                                              head_dim, nq, nk, max_q, max_k, float(scale_div), _stream()),
+               "agx_attention_alibi_packed")
+    if tok is not None:
+        _observer.end(tok)
+    return out
+
+
+def attention_alibi_packed_backward(q: Tensor, kv: Optional[Tensor], slopes: Tensor, out: Tensor, dout: Tensor, heads: int,
+                                    head_dim: int, scale_div: float, cu_q: Tensor, max_q: int, cu_k: Optional[Tensor] = None,
+                                    max_k: Optional[int] = None):
+    """Backward of ``attention_alibi_packed`` with the same partition: (dq, dkv), or with ``kv=None`` the one (1, 3*H*Dh, N)
+    dqkv tensor, written in place through pointers and strides.  Exactly 0 in the columns no sequence owns; ``dout`` there
+    may hold anything.  Deterministic."""
+    lib = _lib.load()
+    op = "attention_alibi_packed_backward"
+    _need_gpu(q, kv, slopes, out, dout)
+    q, out, dout = _f32c(q), _f32c(out), _f32c(dout)
+    kv = None if kv is None else _f32c(kv)
+    nq, nk, hd, cu_q, cu_k, n_seq, max_q, max_k = _packed_args(op, q, kv, heads, head_dim, cu_q, cu_k, max_q, max_k)
+    if tuple(out.shape) != (1, hd, nq) or dout.shape != out.shape:
+        raise AgxError(f"{op}: out {tuple(out.shape)} / dout {tuple(dout.shape)} are not {(1, hd, nq)}")
+    dq = torch.empty_like(q)
+    if kv is not None:
+        dkv = torch.empty_like(kv)
+        ptrs, dptrs = (_ptr(q), _ptr(kv), nq, nk), (_ptr(dq), _ptr(dkv), nq, nk)
+    else:
+        dkv = None
+        ptrs, dptrs = (_ptr(q), _off(q, hd * nq), nq, nk), (_ptr(dq), _off(dq, hd * nq), nq, nk)
+    nbytes = int(lib.agx_attention_packed_backward_workspace_bytes(heads, nq))
+    ws = _workspace(nbytes, q.device, "agx_attention_packed_backward_workspace_bytes")
+    count_macs("attention_bwd", 5 * heads * min(nq, n_seq * max_q) * min(nk, max_k) * head_dim)
+    _lib.check(lib.agx_attention_alibi_packed_backward(*ptrs, _ptr(_f32c(slopes)), _ptr(cu_q), _ptr(cu_k), _ptr(out), _ptr(dout),
+                                                       *dptrs, _ptr(ws), nbytes, n_seq, heads, head_dim, nq, nk, max_q, max_k,
+                                                       float(scale_div), _stream()), "agx_attention_alibi_packed_backward")
+    return dq if kv is None else (dq, dkv)
+
+
+def pack_rows(x: Tensor, cu: Tensor, total: int) -> Tensor:
+    """A right-padded fp32 (B, C, T) batch -> its packed form (1, C, total): ``out[0, c, cu[b] + i] = x[b, c, i]`` for
+    ``i < cu[b+1] - cu[b]``, exactly 0 in the columns no row owns; the padding of ``x`` is never read.  ``cu``: B + 1 int32
+    entries on the device.  The adjoint of ``unpack_rows``."""
+    lib = _lib.load()
+    _need_gpu(x)
+    if x.dim() != 3:
+        raise AgxError(f"pack_rows: x is {tuple(x.shape)}, expected (B, C, T)")
+    x = _f32c(x)
+    b, c, t = x.shape
+    if int(total) != total or total < 0:
+        raise AgxError(f"pack_rows: total = {total}: the packed length is an integer >= 0")
+    cu = _cu_arg("pack_rows", cu, "cu", b)
+    out = torch.empty((1, c, int(total)), dtype=torch.float32, device=x.device)
+    _lib.check(lib.agx_pack_rows(_ptr(x), _ptr(cu), _ptr(out), b, c, t, int(total), _stream()), "agx_pack_rows")
+    return out
+
+
+def unpack_rows(xp: Tensor, cu: Tensor, t: int) -> Tensor:
+    """A packed fp32 (1, C, N) batch -> the right-padded (B, C, t) form: ``out[b, c, i] = xp[0, c, cu[b] + i]`` for
+    ``i < cu[b+1] - cu[b]``, exactly 0 at padded positions (a select: the slack of ``xp`` is never read).  ``cu``: B + 1
+    int32 entries on the device.  The adjoint of ``pack_rows``."""
+    lib = _lib.load()
+    _need_gpu(xp)
+    if xp.dim() != 3 or xp.shape[0] != 1:
+        raise AgxError(f"unpack_rows: xp is {tuple(xp.shape)}, expected (1, C, N)")
+    xp = _f32c(xp)
+    _, c, n = xp.shape
+    if int(t) != t or t < 0:
+        raise AgxError(f"unpack_rows: t = {t}: the padded length is an integer >= 0")
+    cu = _cu_arg("unpack_rows", cu, "cu")
+    b = cu.numel() - 1
+    out = torch.empty((b, c, int(t)), dtype=torch.float32, device=xp.device)
+    _lib.check(lib.agx_unpack_rows(_ptr(xp), _ptr(cu), _ptr(out), b, c, int(t), n, _stream()), "agx_unpack_rows")
+    return out
+
+
 # ------------------------------------------------------------------ causal attention (include/agx.h "Causal self-attention")
 def attention_causal_kernel_name(batch: int, heads: int, head_dim: int, tq: int, tk: int, backward: bool = False) -> str:
     """The kernel ``attention_alibi_causal`` runs for this shape, with ``backward`` the three kernels of

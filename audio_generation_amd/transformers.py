@@ -30,6 +30,10 @@ length for a right-padded ragged batch: the symmetric layers run on the kernels 
 the lengths from device memory, the block's output is exactly 0 at padded positions, and its valid positions and every
 gradient are independent of what the padding held, NaN included (``Transformer._hip_bct``).  fp32, no dropout, not on a
 causal layer -- whose valid frames never see right padding anyway.
+``Transformer.run_packed`` (build-defined) takes the same batch without its padding: the sequences concatenated along the time
+axis, ``(1, dim, N)`` with ``N`` the sum of the lengths, and ``cu_seqlens``, the n_seq + 1 starts and ends.  Every op but the
+attention is pointwise in time and runs on the packed tensor as it is; the attention runs on the kernels of
+``csrc/attention_packed.hip``, which read ``cu_seqlens`` from device memory.  ``pack_padded`` / ``unpack_padded`` convert.
 The ``nn.LayerNorm`` / ``nn.Linear`` children only hold parameters.
 """
 from __future__ import annotations
@@ -193,6 +197,85 @@ def _checked_lengths(what: str, lengths, batch: int, t: int, device) -> Optional
     return host.to(torch.int32).to(device)
 
 
+class _Packed:
+    """The checked partition of a packed call (``Transformer._check_packed``): ``cu`` / ``y_cu`` are int32 device tensors of
+    n_seq + 1 entries, ``max_len`` / ``y_max_len`` host-known bounds of the sequence lengths, and ``slack`` / ``y_slack`` say
+    whether columns behind the last sequence may exist (a device array, or a host array that ends before N): only then does
+    the walk mask them (``Transformer._hip_bct``)."""
+
+    def __init__(self, cu, max_len, slack, y_cu=None, y_max_len=None, y_slack=False):
+        self.cu, self.max_len, self.slack, self.y_cu, self.y_max_len, self.y_slack = cu, max_len, slack, y_cu, y_max_len, y_slack
+
+    def attn_args(self, cross: bool) -> dict:
+        if cross:
+            return dict(cu_seqlens=self.cu, max_len=self.max_len, y_cu_seqlens=self.y_cu, y_max_len=self.y_max_len)
+        return dict(cu_seqlens=self.cu, max_len=self.max_len)
+
+
+def _checked_cu(what: str, cu, n: int, max_len, device) -> tuple:
+    """A ``cu_seqlens`` argument over ``n`` packed columns -> (int32 device tensor, max_len, slack).  A Python sequence or a CPU
+    integer tensor is validated here -- starts at 0, non-decreasing, ends at or before ``n`` -- its longest sequence is
+    ``max_len`` (a given ``max_len`` must not be smaller) and ``slack`` says whether it ends before ``n``.  A device integer
+    tensor is used as it is, without a sync: ``max_len`` must then be given, the kernels clamp what the array holds when they
+    run, and ``slack`` is True because nobody here knows."""
+    on_device = isinstance(cu, Tensor) and cu.is_cuda
+    host = cu if on_device else torch.as_tensor(cu)
+    if host.dtype.is_floating_point or host.dtype.is_complex or host.dtype == torch.bool:
+        raise AgxError(f"{what} must hold integers, got {host.dtype}")
+    if host.dim() != 1 or host.numel() < 2:
+        raise AgxError(f"{what} has shape {tuple(host.shape)}: n_seq + 1 >= 2 entries, the start of every sequence and the end of the last")
+    if max_len is not None and (int(max_len) != max_len or max_len < 0):
+        raise AgxError(f"max_len = {max_len} for {what}: the bound of the sequence lengths is an integer >= 0")
+    if on_device:
+        if max_len is None:
+            raise AgxError(f"a device {what} needs max_len: the host does not read the array, and the bound sizes the grid")
+        return host.to(torch.int32).contiguous(), int(max_len), True
+    vals = [int(v) for v in host.tolist()]
+    if vals[0] != 0 or any(b < a for a, b in zip(vals, vals[1:])) or vals[-1] > n:
+        raise AgxError(f"{what} = {vals}: it must start at 0, never decrease and end at or before N = {n}")
+    longest = max(b - a for a, b in zip(vals, vals[1:]))
+    if max_len is not None and max_len < longest:
+        raise AgxError(f"max_len = {max_len} for {what}, whose longest sequence has {longest} frames")
+    return host.to(torch.int32).to(device), (longest if max_len is None else int(max_len)), vals[-1] < n
+
+
+def pack_padded(x: Tensor, lengths, total: Optional[int] = None) -> tuple:
+    """A right-padded channel-major batch ``x`` (B, dim, T) with the valid ``lengths`` of its rows -> ``(xp, cu_seqlens,
+    max_len)``, the arguments of ``Transformer.run_packed``: ``xp`` (1, dim, N), ``cu_seqlens`` an int32 device tensor (a device
+    ``cumsum`` of the lengths).  Host ``lengths`` (a Python sequence or a CPU integer tensor) are validated, ``N`` is their sum
+    and ``max_len`` their maximum.  Device ``lengths`` are not read: the caller passes ``total``, the capacity ``N`` of the
+    packed tensor (at least their sum -- what lies behind it is slack, exactly 0), and ``max_len`` is T."""
+    if x.dim() != 3:
+        raise AgxError(f"pack_padded: x is {tuple(x.shape)}, expected (B, dim, T)")
+    b, _, t = x.shape
+    dev = _checked_lengths("lengths", lengths, b, t, x.device)
+    if dev is None:
+        raise AgxError("pack_padded: lengths is required")
+    if isinstance(lengths, Tensor) and lengths.is_cuda:
+        if total is None:
+            raise AgxError("pack_padded: device lengths need total=, the capacity of the packed tensor (the host does not read them)")
+        n, max_len = int(total), t
+    else:
+        host = [int(v) for v in torch.as_tensor(lengths).tolist()]
+        n, max_len = sum(host), max(host, default=0)
+        if total is not None:
+            if total < n:
+                raise AgxError(f"pack_padded: total = {total} is less than the sum of the lengths, {n}")
+            n = int(total)
+    cu = torch.zeros(b + 1, dtype=torch.int32, device=x.device)
+    cu[1:] = torch.cumsum(dev, 0)
+    return ops.pack_rows(x, cu, n), cu, max_len
+
+
+def unpack_padded(xp: Tensor, cu_seqlens, t: int) -> Tensor:
+    """The inverse of ``pack_padded``: a packed (1, dim, N) tensor -> the right-padded (B, dim, ``t``) batch, exactly 0 at padded
+    positions.  ``cu_seqlens`` as ``Transformer.run_packed`` takes it."""
+    if xp.dim() != 3 or xp.shape[0] != 1:
+        raise AgxError(f"unpack_padded: xp is {tuple(xp.shape)}, expected (1, dim, N)")
+    cu, _, _ = _checked_cu("cu_seqlens", cu_seqlens, xp.shape[-1], t, xp.device)
+    return ops.unpack_rows(xp, cu, t)
+
+
 class Attention(nn.Module):
     """transformers.py:95-191 (pre-LN multi-head attention with ALiBi).  ``context_y`` makes it a cross-attention layer:
     ``W_q`` reads ``LN(x)``, ``W_k`` / ``W_v`` (stacked into one projection) read the second sequence ``y`` as given."""
@@ -242,6 +325,64 @@ class Attention(nn.Module):
                            "no kernel (eval mode runs)")
         if self.attention_dtype != "fp32":
             raise AgxError(f"lengths=: ragged attention runs in fp32, attention_dtype = {self.attention_dtype!r} has no kernel")
+
+    def _check_packed(self) -> None:
+        """The refusals of a packed call that depend on the layer alone, before any op."""
+        if self.causal:
+            raise AgxError("a packed batch on a causal" + (" (windowed)" if self.window is not None else "") + " layer: packed "
+                           "attention is symmetric, causal and windowed packed calls have no kernel")
+        if _active_p(self.dropout) > 0:
+            raise AgxError("a packed batch with an active dropout site (training mode, dropout > 0): dropout on packed batches "
+                           "has no kernel (eval mode runs)")
+        if self.attention_dtype != "fp32":
+            raise AgxError(f"a packed batch runs in fp32: attention_dtype = {self.attention_dtype!r} has no packed kernel")
+
+    def _run_packed_bct(self, x: Tensor, residual: Optional[Tensor], keep: Optional[dict], y: Optional[Tensor], kv_cache,
+                        cu_seqlens, max_len, y_cu_seqlens, y_max_len) -> Tensor:
+        """The layer on a packed batch (``run_bct``): every refusal, then the plain walk with ``attention_alibi_packed`` where
+        the attention op was."""
+        if kv_cache is not None:
+            raise AgxError("a packed batch with a key/value cache: a cached call is causal and packed attention is symmetric")
+        self._check_packed()
+        if x.dim() != 3 or x.shape[0] != 1 or x.shape[1] != self.dim:
+            raise AgxError(f"a packed batch is one row: x is {tuple(x.shape)}, expected (1, {self.dim}, N)")
+        if cu_seqlens is None or max_len is None:
+            raise AgxError("a packed call needs cu_seqlens and max_len (a device array is not read by the host: max_len sizes the grid)")
+        if self.cross_attention != (y_cu_seqlens is not None):
+            raise AgxError("y_cu_seqlens= on a self-attention layer (built without context_y): there is no second sequence"
+                           if y_cu_seqlens is not None else
+                           "a cross-attention layer (built with context_y) needs y_cu_seqlens, the partition of its second sequence")
+        if keep is not None and self.dim_head > 128:
+            raise AgxError("Transformer: the attention backward kernels cover head_dim <= 128 "
+                           "(agx_attention_alibi_packed_backward); larger heads have no kernel -- there is no ATen fallback")
+        if self.cross_attention:
+            if y is None or y.dim() != 3 or y.shape[0] != 1 or y.shape[1] != self.dim:
+                raise AgxError(f"packed cross-attention: y is {None if y is None else tuple(y.shape)}, expected (1, {self.dim}, Ny)")
+            if y_max_len is None:
+                raise AgxError("a packed call needs y_max_len with y_cu_seqlens")
+            if y_cu_seqlens.numel() != cu_seqlens.numel():
+                raise AgxError(f"x has {cu_seqlens.numel() - 1} sequences and y has {y_cu_seqlens.numel() - 1}: sequence s of x "
+                               "attends to sequence s of y")
+            cx, cy = self.alibi_obj.context_x, self.alibi_obj.context_y
+            if not ((max_len <= cx and y_max_len <= cy) or (max_len <= cy and y_max_len <= cx)):
+                raise AgxError(f"sequence lengths up to ({max_len}, {y_max_len}) exceed the ALiBi contexts ({cx}, {cy}) in both orders")
+            xn = _ln(self.norm, x)
+            q = self._q.forward(xn)
+            kv = self._kv.forward(y)
+            o = ops.attention_alibi_packed(q, kv, cu_q=cu_seqlens, max_q=max_len, cu_k=y_cu_seqlens, max_k=y_max_len, **self._attn())
+            if keep is not None:
+                keep.update(h=x, xn1=xn, q=q, y=y, kv=kv, o=o)
+            return self._o.forward(o, EPI_RESIDUAL if residual is not None else 0, residual)
+        if y is not None:
+            raise AgxError("a self-attention layer (built without context_y) takes no second sequence y")
+        if max_len > self.context:
+            raise AgxError(f"sequence lengths up to max_len = {max_len} exceed the ALiBi context {self.context}")
+        xn = _ln(self.norm, x)
+        qkv = self._qkv.forward(xn)
+        o = ops.attention_alibi_packed(qkv, None, cu_q=cu_seqlens, max_q=max_len, **self._attn())
+        if keep is not None:
+            keep.update(h=x, xn1=xn, qkv=qkv, o=o)
+        return self._o.forward(o, EPI_RESIDUAL if residual is not None else 0, residual)
 
     def _run_cross_bct(self, x: Tensor, residual: Optional[Tensor], keep: Optional[dict], y: Optional[Tensor],
                        drop: Optional[tuple] = None, lengths: Optional[Tensor] = None,
@@ -352,7 +493,7 @@ class Attention(nn.Module):
 
     def run_bct(self, x: Tensor, residual: Optional[Tensor] = None, keep: Optional[dict] = None,
                 y: Optional[Tensor] = None, drop: Optional[tuple] = None, kv_cache: Optional[tuple] = None, *,
-                lengths=None, y_lengths=None) -> Tensor:
+                lengths=None, y_lengths=None, cu_seqlens=None, max_len=None, y_cu_seqlens=None, y_max_len=None) -> Tensor:
         """(B, dim, T) -> W_o(attn(LN(x))) [+ residual], channel-major; a cross-attention layer also takes ``y``
         (B, dim, Ty).  ``keep`` marks the training forward: the dict
         receives what ``backward_bct`` reads, and the attention arithmetic is fp32 whatever ``attention_dtype`` says
@@ -369,7 +510,18 @@ class Attention(nn.Module):
         (``_checked_lengths``): the layer's launches are unchanged but for ``attention_alibi_ragged`` where its attention op
         was, with ``q_len = k_len = lengths`` (cross: ``k_len = y_lengths``).  Only the attention mixes positions, so the
         valid positions of the result do not depend on the padding; the padded ones hold whatever the pointwise ops make of
-        it -- zeroing them (``ops.mask_tail``) is the caller's part: ``forward`` and ``Transformer`` do it."""
+        it -- zeroing them (``ops.mask_tail``) is the caller's part: ``forward`` and ``Transformer`` do it.
+
+        ``cu_seqlens`` / ``max_len`` (``y_cu_seqlens`` / ``y_max_len``: a cross-attention layer's second sequence) make ``x``
+        (1, dim, N) a packed batch: int32 device tensors of n_seq + 1 entries and host-known bounds of the sequence lengths, as
+        ``ops.attention_alibi_packed`` takes them.  The layer's launches are unchanged but for that op where its attention op
+        was.  Not with ``lengths``; fp32, symmetric layers, no active dropout site.  The columns no sequence owns hold what the
+        pointwise ops make of them -- ``Transformer.run_packed`` masks them where they can exist.  With all four absent no
+        packed op is called."""
+        if cu_seqlens is not None or max_len is not None or y_cu_seqlens is not None or y_max_len is not None:
+            if lengths is not None or y_lengths is not None:
+                raise AgxError("lengths= with cu_seqlens=: a batch is right-padded or packed, not both")
+            return self._run_packed_bct(x, residual, keep, y, kv_cache, cu_seqlens, max_len, y_cu_seqlens, y_max_len)
         if lengths is not None or y_lengths is not None:
             if kv_cache is not None:
                 raise AgxError("lengths= with a key/value cache: a cached call is causal and takes no lengths")
@@ -416,11 +568,12 @@ class Attention(nn.Module):
         return self._o.forward(o, EPI_RESIDUAL if residual is not None else 0, residual)
 
     def backward_bct(self, kept: dict, g: Tensor, want_dy: bool = False, lengths: Optional[Tensor] = None,
-                     y_lengths: Optional[Tensor] = None):
+                     y_lengths: Optional[Tensor] = None, packed: Optional["_Packed"] = None):
         """``g`` = the gradient of ``run_bct(h, residual=h, keep=kept)`` -> (dh, gradients in ``parameters()`` order, dy).
         ``dy`` is the gradient of a cross-attention layer's second sequence -- the backward-data of the stacked W_k / W_v
         projection, run only when ``want_dy`` -- and None otherwise.  ``lengths`` / ``y_lengths``: the device tensors the
-        forward ran with (``attention_alibi_ragged_backward`` in the attention backward's place)."""
+        forward ran with (``attention_alibi_ragged_backward`` in the attention backward's place).  ``packed``: the partition
+        of a packed forward (``attention_alibi_packed_backward`` in that place)."""
         d = kept.get("drop")
         d = d if d is not None and d.get("attn") else None      # the forward's (seed, layer, p): its masks are regenerated
         if d is not None:    # the W_o site: the residual branch takes g unmasked (``add=g`` below)
@@ -431,6 +584,10 @@ class Attention(nn.Module):
         if self.cross_attention:
             if d is not None:
                 dq, dkv = ops.attention_alibi_dropout_backward(kept["q"], kept["kv"], dout=do, out=kept["o"], **mask, **self._attn())
+            elif packed is not None:
+                dq, dkv = ops.attention_alibi_packed_backward(kept["q"], kept["kv"], dout=do, out=kept["o"], cu_q=packed.cu,
+                                                              max_q=packed.max_len, cu_k=packed.y_cu, max_k=packed.y_max_len,
+                                                              **self._attn())
             elif lengths is not None or y_lengths is not None:
                 dq, dkv = ops.attention_alibi_ragged_backward(kept["q"], kept["kv"], dout=do, out=kept["o"], q_len=lengths,
                                                               k_len=y_lengths, **self._attn())
@@ -446,6 +603,9 @@ class Attention(nn.Module):
             dqkv = ops.attention_alibi_window_backward(kept["qkv"], out=kept["o"], dout=do, window=self.window, **self._attn())
         elif self.causal:
             dqkv = ops.attention_alibi_causal_backward(kept["qkv"], out=kept["o"], dout=do, **self._attn())
+        elif packed is not None:
+            dqkv = ops.attention_alibi_packed_backward(kept["qkv"], None, dout=do, out=kept["o"], cu_q=packed.cu,
+                                                       max_q=packed.max_len, **self._attn())
         elif lengths is not None:
             dqkv = ops.attention_alibi_ragged_backward(kept["qkv"], None, dout=do, out=kept["o"], q_len=lengths, k_len=lengths,
                                                        **self._attn())
@@ -541,14 +701,20 @@ class _TransformerNative(torch.autograd.Function):
     travel in the context as non-differentiable values.  The backward masks the incoming gradient's tail first
     (``mask_tail``, out of place), then walks as usual with ``attention_alibi_ragged_backward``: every tensor the forward
     kept is finite at padded positions and every gradient there exactly 0, so the padding contributes exactly 0 to every
-    parameter gradient and ``dx`` / ``dy`` come out exactly 0 there."""
+    parameter gradient and ``dx`` / ``dy`` come out exactly 0 there.
+
+    ``lens`` may instead be the ``_Packed`` partition of ``Transformer.run_packed``, carried the same way: the backward zeroes
+    the slack columns of the incoming gradient once (one ``mask_tail`` of the one packed row at ``cu_seqlens[-1]``, and only
+    where slack can exist), then walks as usual with ``attention_alibi_packed_backward``; the same argument keeps the slack
+    out of every parameter gradient."""
 
     @staticmethod
     def forward(ctx, tf, lens, x: Tensor, y: Optional[Tensor], *params: Tensor):
         keep = []
-        ctx.lens = lens
+        ctx.packed = lens if isinstance(lens, _Packed) else None
+        ctx.lens = lens = None if ctx.packed is not None else lens
         with torch.no_grad():
-            out = tf._hip_bct(x.detach(), keep, None if y is None else y.detach(), lens=lens)
+            out = tf._hip_bct(x.detach(), keep, None if y is None else y.detach(), lens=lens, packed=ctx.packed)
         ctx.drop = [kept.pop("drop", None) for kept in keep]     # per layer: the seed, layer and probabilities of its masks
         ctx.tf, ctx.names = tf, [(li, name) for li, kept in enumerate(keep) for name in kept]
         ctx.save_for_backward(*[t for kept in keep for t in kept.values()])
@@ -563,10 +729,14 @@ class _TransformerNative(torch.autograd.Function):
         lengths, y_lengths = ctx.lens if ctx.lens is not None else (None, None)
         if lengths is not None:
             g = ops.mask_tail(g, lengths)                   # the backward of the block's last op
+        if ctx.packed is not None and ctx.packed.slack:
+            g = ops.mask_tail(g, ctx.packed.cu[-1:])        # likewise: the one packed row ends at cu_seqlens[-1]
         for (attention, ff), kept in zip(reversed(ctx.tf.layers), reversed(keep)):
             g, g_ff = ff.backward_bct(kept, g)              # x2 = x1 + W2 gelu(W1 LN2(x1) + b1) + b2
             # x1 = h + W_o attn(W_qkv LN1(h))  (cross: W_q LN1(h), W_kv y -- dy only when y asks for a gradient)
-            if ctx.lens is None:
+            if ctx.packed is not None:
+                g, g_attention, dy = attention.backward_bct(kept, g, want_dy=ctx.needs_input_grad[3], packed=ctx.packed)
+            elif ctx.lens is None:
                 g, g_attention, dy = attention.backward_bct(kept, g, want_dy=ctx.needs_input_grad[3])
             else:
                 g, g_attention, dy = attention.backward_bct(kept, g, want_dy=ctx.needs_input_grad[3], lengths=lengths,
@@ -750,7 +920,7 @@ class Transformer(nn.Module):
         return lengths, y_lengths
 
     def _hip_bct(self, x: Tensor, keep: Optional[list] = None, y: Optional[Tensor] = None,
-                 cache=None, lens: Optional[tuple] = None) -> Tensor:
+                 cache=None, lens: Optional[tuple] = None, packed: Optional[_Packed] = None) -> Tensor:
         """The one forward walk, LN1 -> QKV -> attention -> W_o (+res) -> LN2 -> FFN-in (GELU) -> FFN-out (+res) per layer:
         7 launches, both residual adds fused into the W_o / FFN-out conv epilogues (a cross-attention layer: 8, a Q and a
         KV projection in place of the QKV one).  ``keep``: the training forward
@@ -783,7 +953,16 @@ class Transformer(nn.Module):
         (self-attention: ``q_len = k_len = lengths``; the cross layer: ``q_len = lengths``, ``k_len = y_lengths``), then
         ``mask_tail`` in place on the block's output: two more launches per call (three with ``y_lengths``).  Every other op
         is pointwise in time, so the output at valid positions does not depend on what the padding held (NaN included: the
-        masked inputs are finite) and is exactly 0 at padded ones.  ``lens=None``: no new op is called."""
+        masked inputs are finite) and is exactly 0 at padded ones.  ``lens=None``: no new op is called.
+
+        ``packed`` (``_check_packed``): ``x`` (1, dim, N) and ``y`` (1, dim, Ny) hold the sequences back to back.  The walk is
+        the plain one, 7 launches per layer (8 for the cross layer), with ``attention_alibi_packed`` where the attention op
+        was (``cu_q = cu_k = packed.cu``; the cross layer: ``cu_k = packed.y_cu``): nothing else mixes columns, and a
+        partition the host validated to end at N leaves no column without an owner, so there is nothing to mask.  Where
+        slack columns can exist -- a device ``cu_seqlens``, which the host does not read, or a host one that ends before N --
+        they are masked exactly as the padded tails above: ``mask_tail`` of the one packed row at ``cu[-1]``, out of place on
+        ``x`` (and on ``y`` likewise), in place on the output, so the output is exactly 0 there, the kept tensors are finite
+        and NaN in the slack changes nothing.  ``packed=None``: no packed op is called."""
         lengths, y_lengths = lens if lens is not None else (None, None)
         on_device = isinstance(cache, TransformerStreamCache)
         if (y is not None) != self.cross_attention:
@@ -798,11 +977,18 @@ class Transformer(nn.Module):
             x = ops.mask_tail(x, lengths)
         if y_lengths is not None:
             y = ops.mask_tail(y, y_lengths)
+        if packed is not None and packed.slack:
+            x = ops.mask_tail(x, packed.cu[-1:])
+        if packed is not None and packed.y_slack:
+            y = ops.mask_tail(y, packed.y_cu[-1:])
         for li, (attention, ff) in enumerate(self.layers):
             kept = None if keep is None else {}
             drop = None if seed is None else (seed, li)
             if cache is not None:
                 x = attention.run_bct(x, x, kept, None, drop, kv_cache=(cache.kv[li], cache.pos if on_device else cache.length))
+            elif packed is not None:
+                x = attention.run_bct(x, x, kept, y if attention.cross_attention else None, drop,
+                                      **packed.attn_args(attention.cross_attention))
             elif lens is not None:
                 x = attention.run_bct(x, x, kept, y if attention.cross_attention else None, drop, lengths=lengths,
                                       y_lengths=y_lengths if attention.cross_attention else None)
@@ -817,7 +1003,76 @@ class Transformer(nn.Module):
             cache.length += x.shape[-1]
         if lengths is not None:
             x = ops.mask_tail(x, lengths, out=x)
+        if packed is not None and packed.slack:
+            x = ops.mask_tail(x, packed.cu[-1:], out=x)
         return x
+
+    def _check_packed(self, x: Tensor, cu_seqlens, max_len, y: Optional[Tensor], y_cu_seqlens, y_max_len) -> _Packed:
+        """The refusals of a packed call, before any op, and its partition as checked device tensors."""
+        if self.causal:
+            raise AgxError("run_packed on a causal" + (" (windowed)" if self.window is not None else "") + " Transformer: packed "
+                           "attention is symmetric, causal and windowed packed calls have no kernel")
+        if self._dropout_active():
+            raise AgxError("run_packed with an active dropout site (training mode, dropout > 0): dropout on packed batches has "
+                           "no kernel (eval mode runs)")
+        for attention, _ in self.layers:
+            attention._check_packed()
+        if y_cu_seqlens is not None and not self.cross_attention:
+            raise AgxError("y_cu_seqlens= on a Transformer without a cross-attention layer (built without context_y)")
+        if self.cross_attention and (y is None or y_cu_seqlens is None):
+            raise AgxError("run_packed on a Transformer with a cross-attention layer (built with context_y) needs y and "
+                           "y_cu_seqlens, the packed second sequence and its partition")
+        if y is not None and not self.cross_attention:
+            raise AgxError("this Transformer was built without context_y and takes no second sequence y")
+        dim = self.layers[0][0].dim
+        if x.dim() != 3 or x.shape[0] != 1 or x.shape[1] != dim:
+            raise AgxError(f"run_packed: x is {tuple(x.shape)}, expected (1, {dim}, N): a packed batch is one row")
+        cu, max_len, slack = _checked_cu("cu_seqlens", cu_seqlens, x.shape[-1], max_len, x.device)
+        if not self.cross_attention:
+            if max_len > self.context_x:
+                raise AgxError(f"run_packed: sequences of up to max_len = {max_len} frames exceed context_x = {self.context_x}")
+            return _Packed(cu, max_len, slack)
+        if y.dim() != 3 or y.shape[0] != 1 or y.shape[1] != dim:
+            raise AgxError(f"run_packed: y is {tuple(y.shape)}, expected (1, {dim}, Ny): a packed batch is one row")
+        y_cu, y_max_len, y_slack = _checked_cu("y_cu_seqlens", y_cu_seqlens, y.shape[-1], y_max_len, y.device)
+        if y_cu.numel() != cu.numel():
+            raise AgxError(f"run_packed: x has {cu.numel() - 1} sequences and y has {y_cu.numel() - 1}: sequence s of x attends to "
+                           "sequence s of y")
+        cx, cy = self.context_x, self.layers[0][0].alibi_obj.context_y
+        if not ((max_len <= cx and y_max_len <= cy) or (max_len <= cy and y_max_len <= cx)) or (len(self.layers) > 1 and max_len > cx):
+            raise AgxError(f"run_packed: sequences of up to ({max_len}, {y_max_len}) frames exceed the ALiBi contexts ({cx}, {cy}) "
+                           "in both orders, or context_x in the self-attention layers")
+        return _Packed(cu, max_len, slack, y_cu, y_max_len, y_slack)
+
+    def run_packed(self, x: Tensor, cu_seqlens, max_len: Optional[int] = None, y: Optional[Tensor] = None, y_cu_seqlens=None,
+                   y_max_len: Optional[int] = None, cache=None) -> Tensor:
+        """A ragged batch without its padding: ``x`` (1, dim, N) holds the sequences back to back, channel-major, and sequence
+        ``s`` owns the columns ``[cu_seqlens[s], cu_seqlens[s+1])``; (1, dim, N) comes back, exactly 0 in the columns behind
+        ``cu_seqlens[-1]``.  ``y`` (1, dim, Ny) with ``y_cu_seqlens`` is the cross-attention layer's second sequence, packed
+        the same way, un-normalised as ever; sequence ``s`` of ``x`` attends to sequence ``s`` of ``y``.  Every sequence
+        comes out as ``run_bct`` computes it alone (``_hip_bct``: the walk).  With autograd on, the backward runs on the HIP
+        kernels too.
+
+        A Python sequence or a CPU integer tensor is validated on the host -- it starts at 0, never decreases, ends at or
+        before N, no sequence exceeds ``context_x`` (with ``y``: the two-order rule of the cross layer) -- and ``max_len`` is
+        derived from it.  A device integer tensor is used without a sync and clamped by the kernels -- the form to pass
+        under graph capture -- and ``max_len`` (``y_max_len``), a bound of the sequence lengths, is then required.  Refused,
+        before any op: a causal or windowed Transformer, ``cache=``, an active dropout site, ``attention_dtype = "bf16"``,
+        ``y_cu_seqlens`` without a cross-attention layer or such a layer without it, a device ``cu_seqlens`` without
+        ``max_len``, ``x`` not (1, dim, N), a count of sequences that differs between ``x`` and ``y``."""
+        if cache is not None:
+            raise AgxError("run_packed with cache=: a cached call is causal and packed attention is symmetric")
+        packed = self._check_packed(x, cu_seqlens, max_len, y, y_cu_seqlens, y_max_len)
+        if needs_grad(x, self) or (y is not None and torch.is_grad_enabled() and y.requires_grad):
+            return _TransformerNative.apply(self, packed, x, y, *list(self.parameters()))
+        return self._hip_bct(x, None, y, packed=packed)
+
+    def forward_packed(self, x: Tensor, cu_seqlens, max_len: Optional[int] = None, y: Optional[Tensor] = None, y_cu_seqlens=None,
+                       y_max_len: Optional[int] = None) -> Tensor:
+        """``run_packed`` in the reference layout: (1, N, dim) [, (1, Ny, dim)] -> (1, N, dim)."""
+        y = None if y is None else y.transpose(1, 2).contiguous()
+        return self.run_packed(x.transpose(1, 2).contiguous(), cu_seqlens, max_len, y, y_cu_seqlens,
+                               y_max_len).transpose(1, 2).contiguous()
 
     def run_bct(self, x: Tensor, y: Optional[Tensor] = None, cache=None, *, lengths=None, y_lengths=None) -> Tensor:
         """Channel-major (B, dim, T) in and out; ``y`` (B, dim, Ty) is the cross-attention layer's second sequence.  With

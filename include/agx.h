@@ -572,6 +572,64 @@ int agx_attention_ragged_kernel_name(int32_t batch, int32_t heads, int32_t head_
  * (NULL: a copy).  batch, channels or t <= 0: returns AGX_OK and launches nothing. */
 int agx_mask_tail(const float *x, const int32_t *len, float *out, int32_t batch, int32_t channels, int32_t t, void *stream);
 
+/* Packed variable-length batches (csrc/attention_packed.hip; build-defined): symmetric ALiBi attention, self or cross, over
+ * n_seq sequences concatenated along the time axis.  cu_q and cu_k are device arrays of n_seq + 1 int32 entries, read by the
+ * kernels (no host copy, no sync; a captured graph replays with whatever the arrays hold at replay time).  Sequence s owns the
+ * query columns [cu_q[s], cu_q[s+1]) and the key columns [cu_k[s], cu_k[s+1]); positions are relative to the sequence's own
+ * start, and with ql / kl the two lengths
+ *     out[h,:,cu_q[s] + i] = sum_{j < kl} softmax_{j < kl}( q_i . k_j / scale_div - slopes[h] * |i - j| ) v_j     for i < ql
+ * which is agx_attention_alibi_cross applied to that sequence alone; a sequence with kl == 0 gets 0, a sequence with ql == 0
+ * gets nothing.  q has heads * head_dim rows of pitch q_row_stride >= nq; kv has the K rows, then the V rows,
+ * 2 * heads * head_dim of them, of pitch kv_row_stride >= nk: self-attention on one (1, 3*H*Dh, N) qkv tensor is q = qkv,
+ * kv = qkv + H*Dh*N, both strides N, cu_k = cu_q, nq = nk = N.  out is contiguous (H*Dh, nq).  The query columns that no
+ * sequence owns -- before cu_q[0], which is 0 in a valid array, and from cu_q[n_seq] on, the slack when nq is a capacity --
+ * are written exactly 0, so every element of out is written.  max_q / max_k are host-known upper bounds of the sequence
+ * lengths; they size the grid, (ceil(max_q / 128), heads, n_seq + 1), and a workgroup beyond its sequence's length returns
+ * at once.  Memory safety does not depend on what the device arrays hold: every start and end is clamped into [0, nq] /
+ * [0, nk], an end to at least its start, a length to at most max_q / max_k.  For arrays that violate the contract
+ * (decreasing, or a sequence longer than its bound) the values are unspecified and columns may stay unwritten, but no
+ * access leaves the tensors.  Nothing outside a sequence reaches its result: loads are clamped below the sequence's end and
+ * V is staged as 0 beyond it, so the neighbours and the slack of q and kv may hold anything, NaN included.  Key and query
+ * blocks are aligned to the sequence's start: sequence s computes bit for bit what agx_attention_alibi_ragged computes for
+ * that sequence cropped and run alone with NULL lengths.  fp32, Dh <= 128 (AGX_ERR_UNSUPPORTED beyond); a row stride too
+ * small, max_q < 0 or max_k < 0: AGX_ERR_BAD_SHAPE; n_seq, heads, nq or nk <= 0: returns AGX_OK and launches nothing.
+ * Every refusal happens before anything is launched and before any pointer is used. */
+int agx_attention_alibi_packed(const float *q, const float *kv, int64_t q_row_stride, int64_t kv_row_stride, const float *slopes,
+                               const int32_t *cu_q, const int32_t *cu_k, float *out, int32_t n_seq, int32_t heads,
+                               int32_t head_dim, int32_t nq, int32_t nk, int32_t max_q, int32_t max_k, float scale_div,
+                               void *stream);
+/* Backward: dq and dkv from q, kv and dout (contiguous (H*Dh, nq); `out` is not read), each through its own pointer and row
+ * stride (>= nq / >= nk), so a dqkv tensor is written in place.  Three deterministic kernels as
+ * agx_attention_alibi_ragged_backward (attn_packed_bwd_stats / _dq / _dkv; no atomics: two calls agree bit for bit), sequence
+ * s bit for bit that backward on its crop.  dq / dkv are exactly 0 for a sequence without keys / without queries and in the
+ * columns no sequence owns; every element of both is written.  dout outside a sequence never reaches that sequence's
+ * gradients and may hold anything.  workspace = 2 * heads * nq floats (lse, delta) =
+ * agx_attention_packed_backward_workspace_bytes() bytes, every float of it written (AGX_ERR_WORKSPACE when shorter).  The
+ * clamps, the unspecified cases and the refusals are those of the forward. */
+size_t agx_attention_packed_backward_workspace_bytes(int32_t heads, int32_t nq);
+int agx_attention_alibi_packed_backward(const float *q, const float *kv, int64_t q_row_stride, int64_t kv_row_stride,
+                                        const float *slopes, const int32_t *cu_q, const int32_t *cu_k, const float *out,
+                                        const float *dout, float *dq, float *dkv, int64_t dq_row_stride, int64_t dkv_row_stride,
+                                        float *workspace, size_t workspace_bytes, int32_t n_seq, int32_t heads,
+                                        int32_t head_dim, int32_t nq, int32_t nk, int32_t max_q, int32_t max_k, float scale_div,
+                                        void *stream);
+/* Host-only: "attention_packed<DVT>" (DVT = 1 / 2 / 4 32-row tiles of the head dim), with backward != 0 the three backward
+ * kernels joined with '+', "none" for an empty shape, or the launcher's refusal (code and message). */
+int agx_attention_packed_kernel_name(int32_t n_seq, int32_t heads, int32_t head_dim, int32_t nq, int32_t nk, int32_t max_q,
+                                     int32_t max_k, int32_t backward, char *buf, size_t buf_len);
+/* The two layouts of a ragged batch, each kernel the other's adjoint; cu: batch + 1 int32 entries on the device, read by the
+ * kernel and clamped as above (start and end into [0, n], the end to at least the start, the length to at most t).
+ * agx_pack_rows: x contiguous (batch, channels, t) -> out contiguous (channels, n) with out[c, cu[b] + i] = x[b, c, i] for
+ * i < cu[b+1] - cu[b], and exactly 0 in the columns no row owns; the padding of x is never read.  agx_unpack_rows: xp
+ * contiguous (channels, n) -> out contiguous (batch, channels, t) with out[b, c, i] = xp[c, cu[b] + i] for i < cu[b+1] - cu[b]
+ * and exactly 0 at the padded positions; the slack of xp is never read.  Both are selects on the index: a NaN never becomes
+ * anything else and never moves.  Every output element is written.  An empty output (batch, channels or t <= 0; pack: n <= 0;
+ * unpack: n < 0): AGX_OK, nothing launched -- agx_unpack_rows with n == 0 writes its zeros and does not read xp. */
+int agx_pack_rows(const float *x, const int32_t *cu, float *out, int32_t batch, int32_t channels, int32_t t, int32_t n,
+                  void *stream);
+int agx_unpack_rows(const float *xp, const int32_t *cu, float *out, int32_t batch, int32_t channels, int32_t t, int32_t n,
+                    void *stream);
+
 /* ------------------------------------------------------------------------- *
  * Wavelet / multiresolution layers (networks/wavelets.py)                     *
  * ------------------------------------------------------------------------- */
