@@ -416,8 +416,9 @@ const AttnRow *attn_bf16_lds_rows() { return kAttnBf16LdsRows; }
 //   dq      per 16-query block, loop over key blocks:  P = exp(s - lse), dP = dO^T V, dS = P (dP - delta),  dQ += dS K^T / scale
 //   dkv     per 64-key block, loop over query blocks:  dK += dS^T Q / scale,  dV += P^T dO   (accumulators in registers)
 // s_ij = q_i . k_j / scale - slope |i - j|  (transformers.py:177-183).
-// TWIN CODE: attention_cross.hip holds a copy of these three kernels with the query side indexed by Tq and the key side by Tk
-// (attn_cross_bwd_stats / _dq / _dkv).  A fix to one belongs in the other too.
+// The masked families (cross, causal, window, ragged, packed) run the same three kernels as the bodies of attention_masked.hpp,
+// with the query side indexed by Tq and the key side by Tk; these stay the self-attention code they were, so a fix to the
+// arithmetic here belongs in attn_bwd_stats_body / _dq_body / _dkv_body too.
 namespace agx {
 
 constexpr int AB_QB = 16;    // queries per block

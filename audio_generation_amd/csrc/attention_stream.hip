@@ -12,11 +12,9 @@
 // then V rows, rows of pitch kv_row_stride >= ring;  out (B, H*Dh, Tq).  q and kv have their own base pointers and batch
 // strides, so the Q rows of a (B, 3*H*Dh, Tq) qkv tensor are read in place.
 //
-// TWIN CODE: attention_stream_kernel<DVT> is a copy of attention_window_kernel<DVT> of attention_window.hip (itself a copy of
-// attention_causal_kernel<DVT> of attention_causal.hip): same tiling, same arithmetic, same block bounds, same two hazards and
-// cures.  The ONLY difference is where q_pos0 comes from -- there an argument the launcher lowered into int32, here pos[b]
-// read and lowered by every workgroup (below) -- and that the ring is mandatory (ring >= 1).  Kept apart so that the window and
-// causal kernels stay the code they were.  A fix to one belongs in the others too.
+// attention_stream_kernel<DVT> is the shared forward body of attention_masked.hpp under WindowMask<false>: the window kernel with
+// a mandatory ring (ring >= 1).  The ONLY other difference is where q_pos0 comes from -- there an argument the launcher lowered
+// into int32, here pos[b] read and lowered by every workgroup (below).
 //
 // The position.  b = blockIdx.z, so pos[b] is one workgroup-uniform load: pmax, jlo, the block bounds and the V prefetch stay
 // workgroup-uniform and every thread meets every __syncthreads.  A negative entry is read as 0.  The kernel indexes in int32, and
@@ -32,11 +30,8 @@
 // pmax - jlo <= (Tq - 1 + pos) - (q0 + pos - W + 1); jlo = 0: pmax <= Tq - 1 + W - 1 - q0), so the single conditional subtract
 // of col_of stays valid, every K / V load lands in a column [0, ring) of its own row, and out is indexed by blockIdx and
 // threadIdx alone.  This is stricter than the host-position form at the start of a stream (there: Tq + min(W - 1, pos) <= ring).
-//
-// Block bounds and the two hazards -- leading all-masked blocks (ms = mn == -inf ? 0 : mn), stale or unwritten ring columns (V
-// staged as zeros outside [jlo, pmax], K gathers clamped into [jlo, pmax], the masked score replaced by a select) -- are those of
-// attention_window.hip, word for word; see its header.  A row at position 0 reads no column it has not written in this call.
-#include "mfma_tile.hpp"
+// A row at position 0 reads no column it has not written in this call.
+#include "attention_masked.hpp"
 
 namespace agx {
 
@@ -46,142 +41,14 @@ __global__ __launch_bounds__(256) void attention_stream_kernel(const float *__re
                                                                const int64_t *__restrict__ pos, int64_t period,
                                                                const float *__restrict__ slopes, float *__restrict__ out, int H,
                                                                int Dh, int Tq, int W, int ring, float scale_div) {
-    constexpr int KB = 64;         // keys per block (two 32-key accumulator tiles)
-    constexpr int DH = 32 * DVT;   // head_dim rounded up to the tile
-    constexpr int VP = KB + 1;     // LDS pitch of the V block
-    extern __shared__ __attribute__((aligned(16))) float vs[];   // [2][DH][VP]
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int li = lane & 31, lh = lane >> 5;
     const int h = blockIdx.y, b = blockIdx.z;
-    const int HD = H * Dh;
     // ---- the row's position: workgroup-uniform, lowered into int32 (see the header) ----
     int64_t p64 = pos[b];
     p64 = p64 < 0 ? 0 : p64;
     if (p64 > W - 1) p64 -= (p64 - (W - 1)) / period * period;
-    const int q_pos0 = int(p64);
-    const float *qb = q + size_t(b) * sq + size_t(h) * Dh * Tq;
-    const float *kb = kv + size_t(b) * skv + size_t(h) * Dh * krs;
-    const float *vb = kb + size_t(HD) * krs;
-    const int q0 = blockIdx.x * 128;
-    const int i = q0 + wave * 32 + li;   // this lane's query
-    const int ic = min(i, Tq - 1);
-    const int ip = ic + q_pos0;          // its absolute position: the last key it sees
-    const float slope = slopes[h], inv_scale = 1.f / scale_div;
-    // workgroup-uniform: the positions of the 128 queries, the keys any of them sees, the blocks that hold those keys
-    const int pmax = min(q0 + 127, Tq - 1) + q_pos0;
-    const int jlo = max(0, q0 + q_pos0 - W + 1);
-    const int blk_lo = jlo / KB, blk_hi = pmax / KB;
-    const int c0 = jlo % ring;                    // the column of key jlo; pmax - jlo < ring (host check), so one wrap at most
-    auto col_of = [&](int j) {                    // the column of key j in [jlo, pmax]
-        const int c = c0 + (j - jlo);
-        return c >= ring ? c - ring : c;
-    };
-
-    // ---- the query fragment stays in registers for the whole key loop ----
-    float qf[DH / 2];
-#pragma unroll
-    for (int s = 0; s < DH / 2; ++s) {
-        const int d = 2 * s + lh;
-        qf[s] = d < Dh ? qb[size_t(d) * Tq + ic] : 0.f;
-    }
-
-    f32x16 o[DVT];
-#pragma unroll
-    for (int dt = 0; dt < DVT; ++dt)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) o[dt][r] = 0.f;
-    float m = -INFINITY, l = 0.f;
-
-    auto stage_v = [&](int blk, float *dst) {   // V[dv < Dh][64 keys of block blk] -> LDS, zeros outside [jlo, pmax] (stale columns are never read)
-        for (int e = tid; e < DH * KB; e += 256) {
-            const int dv = e / KB, jj = e - dv * KB, j = blk * KB + jj;
-            dst[dv * VP + jj] = (dv < Dh && j >= jlo && j <= pmax) ? vb[size_t(dv) * krs + col_of(j)] : 0.f;
-        }
-    };
-    stage_v(blk_lo, vs + (blk_lo & 1) * DH * VP);
-    __syncthreads();
-
-    for (int blk = blk_lo; blk <= blk_hi; ++blk) {
-        const int j0 = blk * KB;
-        float *vcur = vs + (blk & 1) * DH * VP;
-        if (blk + 1 <= blk_hi) stage_v(blk + 1, vs + ((blk + 1) & 1) * DH * VP);   // next block streams in meanwhile
-
-        // ---- S^T = K^T Q for this block: rows = keys, columns = queries ----
-        f32x16 acc[2];
-#pragma unroll
-        for (int t2 = 0; t2 < 2; ++t2)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[t2][r] = 0.f;
-        int kcol[2];
-#pragma unroll
-        for (int t2 = 0; t2 < 2; ++t2) kcol[t2] = col_of(max(jlo, min(j0 + t2 * 32 + li, pmax)));
-#pragma unroll 4
-        for (int s = 0; s < DH / 2; ++s) {
-            const int d = min(2 * s + lh, Dh - 1);
-            float kf[2];
-#pragma unroll
-            for (int t2 = 0; t2 < 2; ++t2) kf[t2] = kb[size_t(d) * krs + kcol[t2]];
-#pragma unroll
-            for (int t2 = 0; t2 < 2; ++t2) acc[t2] = __builtin_amdgcn_mfma_f32_32x32x2f32(kf[t2], qf[s], acc[t2], 0, 0, 0);
-        }
-
-        // ---- scale, one-sided ALiBi, window mask, online softmax (in-lane over the 32 registers + one shuffle) ----
-        float bm = -INFINITY;
-#pragma unroll
-        for (int t2 = 0; t2 < 2; ++t2)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const int j = j0 + t2 * 32 + acc_row(r, lh);
-                float s = acc[t2][r] * inv_scale - float(ip - j) * slope;
-                s = (j <= ip && j > ip - W) ? s : -INFINITY;   // a select: whatever the masked score was, it is gone
-                acc[t2][r] = s;
-                bm = fmaxf(bm, s);
-            }
-        bm = fmaxf(bm, __shfl_xor(bm, 32));
-        const float mn = fmaxf(m, bm);                    // -inf until the row has seen its first key
-        const float ms = mn == -INFINITY ? 0.f : mn;      // never (-inf) - (-inf): a leading all-masked block is the identity
-        const float alpha = expf(m - ms);                 // m = -inf: exp(-inf) = 0 (l = 0, o = 0 stay); a later all-masked block: exp(0) = 1
-        float bl = 0.f;
-#pragma unroll
-        for (int t2 = 0; t2 < 2; ++t2)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const float pe = expf(acc[t2][r] - ms);   // masked: exp(-inf) = 0 exactly
-                acc[t2][r] = pe;
-                bl += pe;
-            }
-        bl += __shfl_xor(bl, 32);
-        l = l * alpha + bl;
-        m = mn;
-#pragma unroll
-        for (int dt = 0; dt < DVT; ++dt)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) o[dt][r] *= alpha;
-
-        // ---- O^T += V P^T : B operand = the probability registers ----
-#pragma unroll
-        for (int t2 = 0; t2 < 2; ++t2)
-#pragma unroll
-            for (int s = 0; s < 16; ++s) {
-                const int jj = t2 * 32 + acc_row(s, lh);
-#pragma unroll
-                for (int dt = 0; dt < DVT; ++dt)
-                    o[dt] = __builtin_amdgcn_mfma_f32_32x32x2f32(vcur[(dt * 32 + li) * VP + jj], acc[t2][s], o[dt], 0, 0, 0);
-            }
-        __syncthreads();   // the next block's V has been written by everyone; this block's is free
-    }
-
-    const float inv = 1.f / l;
-    float *ob = out + (size_t(b) * HD + size_t(h) * Dh) * Tq;
-    if (i < Tq) {
-#pragma unroll
-        for (int dt = 0; dt < DVT; ++dt)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const int dv = dt * 32 + acc_row(r, lh);
-                if (dv < Dh) ob[size_t(dv) * Tq + i] = o[dt][r] * inv;
-            }
-    }
+    auto v = window_view<false>(q, kv, sq, skv, krs, nullptr, h, b, H, Dh, Tq, int(p64), W, ring);
+    v.place(blockIdx.x * 128, Tq);   // the keys this workgroup's 128 queries see
+    attn_fwd_body<DVT>(v, out + (size_t(b) * (H * Dh) + size_t(h) * Dh) * Tq, slopes, h, Dh, scale_div);
 }
 
 // A chunk's K / V rows into the ring: buf[b, c, (pos[b] + t) mod ring] = src[b, c, t] for c < C, t < n.  src is read in place
@@ -210,58 +77,8 @@ __global__ __launch_bounds__(256) void stream_advance_kernel(int64_t *__restrict
     if (b < B) pos[b] += n;
 }
 
-// ------------------------------------------------------------------ host side: one pick feeds launch and name query
-struct AttnStreamPick;
-#define AGX_ATTN_STREAM_ARGS                                                                                                        \
-    const AttnStreamPick &k, const float *q, const float *kv, int64_t sq, int64_t skv, int krs, const int64_t *pos, int64_t period, \
-        const float *slopes, float *out, int H, int Dh, int Tq, int W, int ring, float scale_div, hipStream_t st
-struct AttnStreamRow { const char *name; int (*launch)(AGX_ATTN_STREAM_ARGS); };
-// empty: batch, heads or tq <= 0 -- the entry points return AGX_OK and launch nothing; code: a refusal (fail() was called)
-struct AttnStreamPick { const AttnStreamRow *row; dim3 grid; size_t lds; int lds_limit, code; bool empty; };
-
-template <int DVT>
-static int run_attention_stream(AGX_ATTN_STREAM_ARGS) {
-    auto kern = attention_stream_kernel<DVT>;
-    static DeviceOnce once;
-    if (int rc = prepare_kernel(reinterpret_cast<const void *>(kern), once, k.lds_limit, nullptr, "attention_stream")) return rc;
-    hipLaunchKernelGGL(kern, k.grid, dim3(256), k.lds, st, q, kv, sq, skv, krs, pos, period, slopes, out, H, Dh, Tq, W, ring, scale_div);
-    return check_launch("attention_stream");
-}
-
-#define AGX_ATTN_ROW(DVT) {"attention_stream<" #DVT ">", run_attention_stream<DVT>}
-static const AttnStreamRow kAttnStreamRows[3] = {AGX_ATTN_ROW(1), AGX_ATTN_ROW(2), AGX_ATTN_ROW(4)};   // [log2(DVT)]
-#undef AGX_ATTN_ROW
-
-// the pick of attn_window_pick (attention_window.hip): same tiles, same LDS, same grid
-static AttnStreamPick attn_stream_pick(const char *op, int B, int H, int Dh, int Tq, int W) {
-    AttnStreamPick k{};
-    k.empty = B <= 0 || H <= 0 || Tq <= 0;
-    if (Dh <= 0) k.code = fail(AGX_ERR_BAD_SHAPE, "%s: bad shape head_dim=%d", op, Dh);
-    else if (Dh > 128) k.code = fail(AGX_ERR_UNSUPPORTED, "%s: head_dim=%d > 128", op, Dh);
-    else if (H > 65535 || B > 65535) k.code = fail(AGX_ERR_BAD_SHAPE, "%s: grid too large", op);
-    else if (W < 1) k.code = fail(AGX_ERR_BAD_SHAPE, "%s: window=%d < 1", op, W);
-    if (k.code || k.empty) return k;
-    const int dvt = Dh <= 32 ? 1 : (Dh <= 64 ? 2 : 4), di = dvt / 2;   // 32-row tiles of the head dim; di = log2(dvt)
-    k.row = &kAttnStreamRows[di];
-    k.lds = size_t(2) * 32 * dvt * 65 * sizeof(float);                 // the double-buffered V block
-    k.lds_limit = k.lds > 48 * 1024 ? 96 * 1024 : 0;
-    k.grid = dim3(ceil_div(Tq, 128), H, B);
-    return k;
-}
-
-// a batch stride must hold one item: the kernels index [b * stride + row * pitch + t]
-static int check_stream_strides(const char *op, int64_t have, int64_t need, const char *what) {
-    return have >= need ? AGX_OK : fail(AGX_ERR_BAD_SHAPE, "%s: %s batch stride %lld < %lld", op, what, (long long)have, (long long)need);
-}
-
-static int64_t stream_gcd64(int64_t a, int64_t b) {
-    while (b) {
-        const int64_t r = a % b;
-        a = b;
-        b = r;
-    }
-    return a;
-}
+// ------------------------------------------------------------------ host side
+static MaskedRow<decltype(&attention_stream_kernel<1>)> kAttnStreamRows[3] = AGX_MASKED_ROWS(stream);
 
 }  // namespace agx
 
@@ -272,7 +89,7 @@ int agx_attention_alibi_stream(const float *q, const float *kv, int64_t q_batch_
                                int32_t tq, int32_t window, int32_t kv_ring, float scale_div, void *stream) {
     using namespace agx;
     const char *op = "attention_alibi_stream";
-    const AttnStreamPick k = attn_stream_pick(op, batch, heads, head_dim, tq, window);
+    const MaskedPick k = masked_window_pick(op, batch, heads, head_dim, tq, window);
     if (k.code) return k.code;
     if (k.empty) return AGX_OK;
     if (kv_ring < 1) return fail(AGX_ERR_BAD_SHAPE, "%s: kv_ring=%d < 1 (the ring is mandatory)", op, kv_ring);
@@ -283,15 +100,15 @@ int agx_attention_alibi_stream(const float *q, const float *kv, int64_t q_batch_
     if (kv_ring > kv_row_stride) return fail(AGX_ERR_BAD_SHAPE, "%s: kv_ring=%d > kv row stride %lld", op, kv_ring, (long long)kv_row_stride);
     if (kv_row_stride > 0x7fffffffLL) return fail(AGX_ERR_BAD_SHAPE, "%s: kv row stride %lld is beyond int32", op, (long long)kv_row_stride);
     // The kernel lowers a position to below window - 1 + period and indexes in int32.
-    const int64_t period = 64 / stream_gcd64(64, kv_ring) * int64_t(kv_ring);
+    const int64_t period = 64 / gcd64(64, kv_ring) * int64_t(kv_ring);
     if (period + window + tq + 128 > 0x7fffffffLL)
         return fail(AGX_ERR_BAD_SHAPE, "%s: lcm(64, kv_ring=%d) + window + tq is beyond int32", op, kv_ring);
     if (!q || !kv || !pos || !slopes || !out) return fail(AGX_ERR_NULL_POINTER, "%s: NULL pointer", op);
     const int64_t hd = int64_t(heads) * head_dim;
-    if (int rc = check_stream_strides(op, q_batch_stride, hd * tq, "q")) return rc;
-    if (int rc = check_stream_strides(op, kv_batch_stride, 2 * hd * kv_row_stride, "kv")) return rc;
-    return k.row->launch(k, q, kv, q_batch_stride, kv_batch_stride, int(kv_row_stride), pos, period, slopes, out, heads, head_dim, tq,
-                         window, kv_ring, scale_div, static_cast<hipStream_t>(stream));
+    if (int rc = check_strides(op, q_batch_stride, hd * tq, "q")) return rc;
+    if (int rc = check_strides(op, kv_batch_stride, 2 * hd * kv_row_stride, "kv")) return rc;
+    return masked_launch(kAttnStreamRows[k.di], k, "attention_stream", static_cast<hipStream_t>(stream), q, kv, q_batch_stride,
+                         kv_batch_stride, int(kv_row_stride), pos, period, slopes, out, heads, head_dim, tq, window, kv_ring, scale_div);
 }
 
 int agx_ring_write_pos(float *buf, const float *src, int64_t buf_batch_stride, int64_t buf_row_stride, int64_t src_batch_stride,
@@ -306,8 +123,8 @@ int agx_ring_write_pos(float *buf, const float *src, int64_t buf_batch_stride, i
     if (buf_row_stride > 0x7fffffffLL) return fail(AGX_ERR_BAD_SHAPE, "%s: buf row stride %lld is beyond int32", op, (long long)buf_row_stride);
     if (int64_t(rows) * n + 256 > 0x7fffffffLL) return fail(AGX_ERR_BAD_SHAPE, "%s: rows * n = %lld is beyond int32", op, (long long)rows * n);
     if (!buf || !src || !pos) return fail(AGX_ERR_NULL_POINTER, "%s: NULL pointer", op);
-    if (int rc = check_stream_strides(op, buf_batch_stride, int64_t(rows) * buf_row_stride, "buf")) return rc;
-    if (int rc = check_stream_strides(op, src_batch_stride, int64_t(rows) * n, "src")) return rc;
+    if (int rc = check_strides(op, buf_batch_stride, int64_t(rows) * buf_row_stride, "buf")) return rc;
+    if (int rc = check_strides(op, src_batch_stride, int64_t(rows) * n, "src")) return rc;
     hipLaunchKernelGGL(ring_write_pos_kernel, dim3(ceil_div(rows * n, 256), batch), dim3(256), 0, static_cast<hipStream_t>(stream), buf,
                        src, buf_batch_stride, int(buf_row_stride), src_batch_stride, pos, rows, n, ring);
     return check_launch("ring_write_pos");
@@ -325,11 +142,8 @@ int agx_stream_advance(int64_t *pos, int32_t batch, int64_t n, void *stream) {
 int agx_attention_stream_kernel_name(int32_t batch, int32_t heads, int32_t head_dim, int32_t tq, int32_t window, char *buf,
                                      size_t buf_len) {
     using namespace agx;
-    const AttnStreamPick k = attn_stream_pick("attention_alibi_stream", batch, heads, head_dim, tq, window);
-    if (k.code) return k.code;
-    if (!buf || buf_len == 0) return fail(AGX_ERR_NULL_POINTER, "agx_attention_stream_kernel_name: NULL buffer");
-    snprintf(buf, buf_len, "%s", k.empty ? "none" : k.row->name);
-    return AGX_OK;
+    const MaskedPick k = masked_window_pick("attention_alibi_stream", batch, heads, head_dim, tq, window);
+    return masked_name(k, "agx_attention_stream_kernel_name", kAttnStreamRows[k.di].name, buf, buf_len);
 }
 
 }  // extern "C"
