@@ -18,6 +18,7 @@ LIB_PATH = os.path.join(_HERE, "lib", "libagx.so")
 CONV_CAUSAL, CONV_TRANSPOSED, CONV_UPSAMPLE, CONV_SAME, CONV_PADDED = 0, 1, 2, 3, 4
 IMPL_AUTO, IMPL_DIRECT, IMPL_MFMA, IMPL_MFMA_BF16X3 = 0, 1, 2, 3
 EPI_LEAKY_PRE, EPI_RESIDUAL, EPI_LEAKY_POST, EPI_GELU_PRE, EPI_MASK = 1, 2, 4, 8, 16
+FILM_CT, FILM_TC = 0, 1
 
 
 class ConvDesc(Structure):
@@ -237,6 +238,14 @@ SIGNATURES = {
     "agx_time_fold": (c_int, [c_void_p, c_void_p, c_int32, c_int32, c_int64, c_int32, c_int64, c_int64, c_int64, c_void_p]),
     "agx_time_unfold": (c_int, [c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int64, c_int64, c_int32, c_int64, c_int64,
                                 c_int64, c_void_p]),
+    "agx_film_params": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_void_p]),
+    "agx_film_apply": (c_int, [c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_int32, c_void_p]),
+    "agx_film_backward": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32,
+                                  c_int32, c_void_p]),
+    "agx_film_params_backward": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_int32,
+                                         c_int32, c_void_p]),
+    "agx_sigmoid_gate": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_void_p]),
+    "agx_sigmoid_gate_backward": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p]),
 }
 
 _lib = None

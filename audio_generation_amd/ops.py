@@ -1681,3 +1681,123 @@ def time_unfold(src: Tensor, out: Tensor, windows: int, keep: int, src_off: int 
     _lib.check(lib.agx_time_unfold(_ptr(src), _ptr(out), b, c, windows, width, length, n_win, src_off, dst_off, keep, _stream()),
                "agx_time_unfold")
     return out
+
+
+# ------------------------------------------------------------------ conditioning (conditioning.py)
+FILM_CT, FILM_TC = _lib.FILM_CT, _lib.FILM_TC
+
+
+def _film_shape(op: str, x: Tensor, gb: Tensor, has_beta: bool, layout: int):
+    """(B, C, T) of a FiLM operand in ``layout``; ``gb`` must be the (B, C) or (B, 2 C) tensor that goes with it."""
+    if layout not in (FILM_CT, FILM_TC):
+        raise AgxError(f"{op}: layout = {layout!r} is neither FILM_CT nor FILM_TC")
+    if x.dim() != 3:
+        raise AgxError(f"{op}: x is {tuple(x.shape)}, expected three dimensions")
+    b, c, t = x.shape if layout == FILM_CT else (x.shape[0], x.shape[2], x.shape[1])
+    if tuple(gb.shape) != (b, (2 if has_beta else 1) * c):
+        raise AgxError(f"{op}: gb is {tuple(gb.shape)}, expected {(b, (2 if has_beta else 1) * c)}")
+    return b, c, t
+
+
+def _same_out(op: str, x: Tensor, out: Optional[Tensor]) -> Tensor:
+    """``out`` of an elementwise op over contiguous ``x``: a new tensor, or the caller's (``x`` itself: in place)."""
+    if out is None:
+        return torch.empty_like(x)
+    if out.shape != x.shape or out.dtype != torch.float32 or not out.is_contiguous():
+        raise AgxError(f"{op}: out must be a contiguous float32 tensor of x's shape")
+    return out
+
+
+def film_params(cond: Tensor, w: Tensor, bias: Optional[Tensor]) -> Tensor:
+    """``gb[b, r] = bias[r] + sum_d cond[b, d] w[r, d]``: cond (B, D), w (R, D), bias (R) or None -> (B, R)."""
+    lib = _lib.load()
+    _need_gpu(cond, w, bias)
+    cond, w = _f32c(cond), _f32c(w)
+    if cond.dim() != 2 or w.dim() != 2 or cond.shape[1] != w.shape[1] or (bias is not None and tuple(bias.shape) != (w.shape[0],)):
+        raise AgxError(f"film_params: cond {tuple(cond.shape)}, w {tuple(w.shape)}, bias "
+                       f"{None if bias is None else tuple(bias.shape)}: expected (B, D), (R, D), (R,)")
+    (b, d), r = cond.shape, w.shape[0]
+    gb = torch.empty((b, r), dtype=torch.float32, device=cond.device)
+    tok = _observer.begin("other", ("film_params", 4 * (cond.numel() + b * w.numel() + gb.numel()))) if _observer is not None else None
+    _lib.check(lib.agx_film_params(_ptr(cond), _ptr(w), _ptr(None if bias is None else _f32c(bias)), _ptr(gb), b, d, r,
+                                   _stream()), "agx_film_params")
+    if tok is not None:
+        _observer.end(tok)
+    return gb
+
+
+def film_apply(x: Tensor, gb: Tensor, has_beta: bool, layout: int = FILM_CT, out: Optional[Tensor] = None) -> Tensor:
+    """``x * gamma + beta`` per (batch row, channel): x (B, C, T) for FILM_CT or (B, T, C) for FILM_TC, gb (B, 2 C) -- gamma
+    then beta -- or (B, C) without beta.  ``out`` may be ``x`` (in place)."""
+    lib = _lib.load()
+    _need_gpu(x, gb, out)
+    b, c, t = _film_shape("film_apply", x, gb, has_beta, layout)
+    if x.dtype != torch.float32 or not x.is_contiguous():
+        raise AgxError("film_apply: x must be a contiguous float32 tensor")
+    out = _same_out("film_apply", x, out)
+    tok = _observer.begin("other", ("film_apply", 8 * x.numel())) if _observer is not None else None
+    _lib.check(lib.agx_film_apply(_ptr(x), _ptr(_f32c(gb)), _ptr(out), b, c, t, int(bool(has_beta)), int(layout), _stream()),
+               "agx_film_apply")
+    if tok is not None:
+        _observer.end(tok)
+    return out
+
+
+def film_backward(x: Tensor, gb: Tensor, dout: Tensor, has_beta: bool, layout: int = FILM_CT):
+    """(dx, dgb) of ``film_apply``: ``dx = dout * gamma``; ``dgb`` has gb's shape, ``sum_t dout * x`` then (with beta)
+    ``sum_t dout``.  One pass, no atomics; bitwise the same in both layouts."""
+    lib = _lib.load()
+    _need_gpu(x, gb, dout)
+    b, c, t = _film_shape("film_backward", x, gb, has_beta, layout)
+    if dout.shape != x.shape:
+        raise AgxError(f"film_backward: dout is {tuple(dout.shape)}, x is {tuple(x.shape)}")
+    x, dout = _f32c(x), _f32c(dout)
+    dx = torch.empty_like(x)
+    dgb = torch.empty((b, gb.shape[1]), dtype=torch.float32, device=x.device)
+    _lib.check(lib.agx_film_backward(_ptr(x), _ptr(_f32c(gb)), _ptr(dout), _ptr(dx), _ptr(dgb), b, c, t, int(bool(has_beta)),
+                                     int(layout), _stream()), "agx_film_backward")
+    return dx, dgb
+
+
+def film_params_backward(cond: Tensor, w: Tensor, dgb: Tensor, want_dcond: bool = True):
+    """(dw (R, D), dbias (R), dcond (B, D) or None) of ``film_params``."""
+    lib = _lib.load()
+    _need_gpu(cond, w, dgb)
+    cond, w, dgb = _f32c(cond), _f32c(w), _f32c(dgb)
+    (b, d), r = cond.shape, w.shape[0]
+    if tuple(w.shape) != (r, d) or tuple(dgb.shape) != (b, r):
+        raise AgxError(f"film_params_backward: cond {tuple(cond.shape)}, w {tuple(w.shape)}, dgb {tuple(dgb.shape)}: expected "
+                       "(B, D), (R, D), (B, R)")
+    dw = torch.empty_like(w)
+    dbias = torch.empty(r, dtype=torch.float32, device=w.device)
+    dcond = torch.empty_like(cond) if want_dcond else None
+    _lib.check(lib.agx_film_params_backward(_ptr(cond), _ptr(w), _ptr(dgb), _ptr(dw), _ptr(dbias), _ptr(dcond), b, d, r,
+                                            _stream()), "agx_film_params_backward")
+    return dw, dbias, dcond
+
+
+def sigmoid_gate(x: Tensor, z: Tensor, out: Optional[Tensor] = None) -> Tensor:
+    """``x * sigmoid(z)`` elementwise; ``out`` may be ``x`` (in place)."""
+    lib = _lib.load()
+    _need_gpu(x, z, out)
+    if x.dtype != torch.float32 or not x.is_contiguous() or z.shape != x.shape:
+        raise AgxError(f"sigmoid_gate: x must be a contiguous float32 tensor and z of its shape (x {tuple(x.shape)}, z {tuple(z.shape)})")
+    out = _same_out("sigmoid_gate", x, out)
+    tok = _observer.begin("other", ("sigmoid_gate", 12 * x.numel())) if _observer is not None else None
+    _lib.check(lib.agx_sigmoid_gate(_ptr(x), _ptr(_f32c(z)), _ptr(out), x.numel(), _stream()), "agx_sigmoid_gate")
+    if tok is not None:
+        _observer.end(tok)
+    return out
+
+
+def sigmoid_gate_backward(x: Tensor, z: Tensor, dout: Tensor):
+    """(dx, dz) of ``sigmoid_gate``: ``dout * s`` and ``dout * x * s * (1 - s)`` with ``s = sigmoid(z)``, one launch."""
+    lib = _lib.load()
+    _need_gpu(x, z, dout)
+    if z.shape != x.shape or dout.shape != x.shape:
+        raise AgxError(f"sigmoid_gate_backward: x {tuple(x.shape)}, z {tuple(z.shape)}, dout {tuple(dout.shape)} differ in shape")
+    x, z, dout = _f32c(x), _f32c(z), _f32c(dout)
+    dx, dz = torch.empty_like(x), torch.empty_like(x)
+    _lib.check(lib.agx_sigmoid_gate_backward(_ptr(x), _ptr(z), _ptr(dout), _ptr(dx), _ptr(dz), x.numel(), _stream()),
+               "agx_sigmoid_gate_backward")
+    return dx, dz

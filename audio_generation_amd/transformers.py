@@ -106,23 +106,27 @@ class _PackedLinear:
             self.key = key
         return self.packed, self.bias
 
-    def forward(self, x: Tensor, epilogue: int = 0, res: Optional[Tensor] = None) -> Tensor:
+    def forward(self, x: Tensor, epilogue: int = 0, res: Optional[Tensor] = None, slope: float = 0.1) -> Tensor:
+        """``slope``: the LeakyReLU slope of an ``EPI_LEAKY_PRE`` epilogue (0.0: ReLU); the descriptor's default otherwise."""
         packed, bias = self.get()
         b, c_in, t = x.shape
-        desc = ops.conv_desc(CONV_CAUSAL, b, c_in, self.c_out, t, 1, 1, 1, epilogue)
+        desc = ops.conv_desc(CONV_CAUSAL, b, c_in, self.c_out, t, 1, 1, 1, epilogue, slope)
         return ops.conv_forward(desc, x, packed, bias, res)
 
-    def backward(self, x_in: Tensor, dy: Tensor, pre: Optional[Tensor] = None, want_dx: bool = True):
+    def backward(self, x_in: Tensor, dy: Tensor, pre: Optional[Tensor] = None, want_dx: bool = True,
+                 add: Optional[Tensor] = None, mask: Optional[Tensor] = None, slope: float = 0.1):
         """Backward of ``forward`` with epilogue 0, on the image that forward packed: (dx, the gradients of the linears'
         parameters in ``parameters()`` order); with ``pre`` the GELU gradient of the layer BELOW (at its pre-activation)
-        is fused into the bwd-data epilogue.  ``want_dx=False`` skips the backward-data conv (dx is None)."""
+        is fused into the bwd-data epilogue.  ``want_dx=False`` skips the backward-data conv (dx is None).  Without ``pre``:
+        ``add`` is accumulated into dx first and ``mask`` -- the layer input, the LeakyReLU(``slope``) output of the layer
+        below -- multiplies it by that activation's gradient (``ops.conv_bwd_data``)."""
         b, c_in, t = x_in.shape
         desc = ops.conv_desc(CONV_CAUSAL, b, c_in, self.c_out, t, 1)
         dw, _, db = ops.conv_bwd_weight(desc, x_in, dy, self.w3d, None, want_bias=self.bias is not None)
         dx = None
         if want_dx:
             pk = ops.conv_pack_bwd(desc, self.w3d)
-            dx = ops.conv_bwd_data(desc, dy, pk) if pre is None else ops.conv_bwd_data_gelu(desc, dy, pk, pre)
+            dx = ops.conv_bwd_data(desc, dy, pk, add, mask, slope) if pre is None else ops.conv_bwd_data_gelu(desc, dy, pk, pre)
         dw, grads, row = dw.reshape(self.c_out, c_in), [], 0
         for l in self.linears:
             rows = slice(row, row + l.out_features)

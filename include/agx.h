@@ -880,6 +880,50 @@ int agx_time_fold(const float *src, float *dst, int32_t batch, int32_t channels,
 int agx_time_unfold(const float *src, float *dst, int32_t batch, int32_t channels, int32_t windows, int64_t width, int64_t dst_length,
                     int32_t n_win, int64_t src_off, int64_t dst_off, int64_t keep, void *stream);
 
+/* ------------------------------------------------------------------------- *
+ * Conditioning on a vector (networks/conditioning.py): FiLM and the gate of SqueezeExcite.  fp32, contiguous tensors,
+ * stream-ordered, no synchronisation, no atomics: every result is bitwise reproducible.  Every entry point validates
+ * on the host before it touches the device: a non-positive extent returns AGX_OK and launches nothing, a NULL required
+ * pointer is AGX_ERR_NULL_POINTER, a layout other than the two below AGX_ERR_BAD_SHAPE.  Every grid is one-dimensional
+ * (x only); a shape that needs more than 2^31 - 1 workgroups is AGX_ERR_BAD_SHAPE.
+ * ------------------------------------------------------------------------- */
+#define AGX_FILM_CT 0 /* x is (B, C, T): channel-major, what the conv stacks and Transformer.run_bct work in */
+#define AGX_FILM_TC 1 /* x is (B, T, C): the reference layout, conditioning.py:50 */
+
+/* The two projections of FiLM (conditioning.py:44-46) as one launch:  gb[b, r] = bias[r] + sum_d cond[b, d] w[r, d].
+ * cond (B, D), w (R, D) -- gamma.weight stacked over beta.weight, R = C or 2 C --, bias (R) or NULL (zeros), gb (B, R).
+ * One wavefront per (b, r): lane l sums d = l, l + 64, ... in increasing order, the 64 partial sums are added in a
+ * fixed tree and the bias last.  Any D >= 1. */
+int agx_film_params(const float *cond, const float *w, const float *bias, float *gb, int32_t B, int32_t D, int32_t R,
+                    void *stream);
+/* out = x * gamma + beta (one fma; without beta one multiply) with gamma = gb[b, c] and beta = gb[b, C + c]: gb is
+ * (B, 2 C) with has_beta != 0 and (B, C) without.  out may be x.  Loads and stores are 16 bytes wide from the first
+ * 16-byte boundary of a row (CT: the T floats of one (b, c); TC: the T * C floats of one b) to its last whole
+ * quadruple and scalar at the ragged ends; all scalar where x and out are not equally aligned.  The arithmetic of an
+ * element is the same in both layouts. */
+int agx_film_apply(const float *x, const float *gb, float *out, int32_t B, int32_t C, int32_t T, int32_t has_beta,
+                   int32_t layout, void *stream);
+/* Backward of agx_film_apply in one pass that reads x and dout once:
+ *   dx = dout * gamma,   dgb[b, c] = sum_t dout * x,   with has_beta: dgb[b, C + c] = sum_t dout.
+ * dgb has the shape of gb and every element of it is written.  The sum over t of one (b, c) has one order in both
+ * layouts: walker j of 256 takes t = j, j + 256, ... in increasing order (fma for dout * x), the walkers of each group
+ * of 64 are added in a halving tree and the four groups as (g0 + g1) + (g2 + g3).  CT: one workgroup per (b, c) row,
+ * a thread per walker.  TC: one workgroup per (b, 64 channels), a lane per channel and 64 walkers per thread, every
+ * load a coalesced channel-fastest row.  A launch with few rows (CT) or few channel tiles (TC) under-fills the chip. */
+int agx_film_backward(const float *x, const float *gb, const float *dout, float *dx, float *dgb, int32_t B, int32_t C,
+                      int32_t T, int32_t has_beta, int32_t layout, void *stream);
+/* Backward of agx_film_params, one launch, every sum serial in increasing index:
+ *   dw[r, d] = sum_b dgb[b, r] cond[b, d],   dbias[r] = sum_b dgb[b, r],   dcond[b, d] = sum_r dgb[b, r] w[r, d].
+ * dcond may be NULL (w is then not read and may be NULL too). */
+int agx_film_params_backward(const float *cond, const float *w, const float *dgb, float *dw, float *dbias, float *dcond,
+                             int32_t B, int32_t D, int32_t R, void *stream);
+/* The gate of SqueezeExcite (conditioning.py:23-24): out = x * s with s = 1 / (1 + expf(-z)), elementwise over n
+ * floats; out may be x.  z <= -89 gives exactly 0, z >= 17 exactly x; no NaN for finite operands. */
+int agx_sigmoid_gate(const float *x, const float *z, float *out, int64_t n, void *stream);
+/* Its backward, one launch that writes both:  dx = dout * s,  dz = (dout * x) * (s * (1 - s)). */
+int agx_sigmoid_gate_backward(const float *x, const float *z, const float *dout, float *dx, float *dz, int64_t n,
+                              void *stream);
+
 #ifdef __cplusplus
 }
 #endif
