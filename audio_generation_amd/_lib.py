@@ -19,6 +19,7 @@ CONV_CAUSAL, CONV_TRANSPOSED, CONV_UPSAMPLE, CONV_SAME, CONV_PADDED = 0, 1, 2, 3
 IMPL_AUTO, IMPL_DIRECT, IMPL_MFMA, IMPL_MFMA_BF16X3 = 0, 1, 2, 3
 EPI_LEAKY_PRE, EPI_RESIDUAL, EPI_LEAKY_POST, EPI_GELU_PRE, EPI_MASK = 1, 2, 4, 8, 16
 FILM_CT, FILM_TC = 0, 1
+SNAKE_PLAIN, SNAKE_RELU = 0, 1
 
 
 class ConvDesc(Structure):
@@ -246,6 +247,10 @@ SIGNATURES = {
                                          c_int32, c_void_p]),
     "agx_sigmoid_gate": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_void_p]),
     "agx_sigmoid_gate_backward": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p]),
+    "agx_snake_forward": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int32, c_int64, c_int32, c_float, c_void_p]),
+    "agx_snake_backward_workspace_bytes": (c_size_t, [c_int64, c_int32, c_int64]),
+    "agx_snake_backward": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_int64, c_int32,
+                                   c_int64, c_int32, c_float, c_void_p]),
 }
 
 _lib = None

@@ -1801,3 +1801,62 @@ def sigmoid_gate_backward(x: Tensor, z: Tensor, dout: Tensor):
     _lib.check(lib.agx_sigmoid_gate_backward(_ptr(x), _ptr(z), _ptr(dout), _ptr(dx), _ptr(dz), x.numel(), _stream()),
                "agx_sigmoid_gate_backward")
     return dx, dz
+
+
+# ------------------------------------------------------------------ snake activations (utils.py:44-105)
+SNAKE_PLAIN, SNAKE_RELU = _lib.SNAKE_PLAIN, _lib.SNAKE_RELU
+
+
+def _snake_shape(op: str, x: Tensor, alpha: Tensor, variant: int):
+    """(rows, channels, n) of a snake operand: x is (B, C, ...), rows = B * C, and ``alpha`` holds C floats or one."""
+    if variant not in (SNAKE_PLAIN, SNAKE_RELU):
+        raise AgxError(f"{op}: variant = {variant!r} is neither SNAKE_PLAIN nor SNAKE_RELU")
+    if x.dim() < 2:
+        raise AgxError(f"{op}: x is {tuple(x.shape)}, expected (B, C, ...)")
+    if x.dtype != torch.float32 or not x.is_contiguous():
+        raise AgxError(f"{op}: x must be a contiguous float32 tensor (x {tuple(x.shape)}, {x.dtype})")
+    channels = alpha.numel()
+    if channels not in (1, x.shape[1]):
+        raise AgxError(f"{op}: x is {tuple(x.shape)} and has {x.shape[1]} channels, alpha {tuple(alpha.shape)} holds {channels}")
+    rows = x.shape[0] * x.shape[1]
+    return rows, channels, (x.numel() // rows if rows else 0)
+
+
+def snake_forward(x: Tensor, alpha: Tensor, variant: int, eps: float = 1e-6, out: Optional[Tensor] = None) -> Tensor:
+    """``(max(x, 0) if variant else x) + sin(alpha x)^2 / (alpha + eps)`` per channel: x (B, C, ...), alpha of C elements or
+    of one (every channel).  ``out`` may be ``x`` (in place).  One launch."""
+    lib = _lib.load()
+    _need_gpu(x, alpha, out)
+    rows, channels, n = _snake_shape("snake_forward", x, alpha, variant)
+    out = _same_out("snake_forward", x, out)
+    tok = _observer.begin("other", ("snake_forward", 8 * x.numel())) if _observer is not None else None
+    _lib.check(lib.agx_snake_forward(_ptr(x), _ptr(_f32c(alpha)), _ptr(out), rows, channels, n, int(variant), float(eps), _stream()),
+               "agx_snake_forward")
+    if tok is not None:
+        _observer.end(tok)
+    return out
+
+
+def snake_backward(x: Tensor, alpha: Tensor, dout: Tensor, variant: int, eps: float = 1e-6, want_dx: bool = True,
+                   want_dalpha: bool = True):
+    """(dx or None, dalpha or None) of ``snake_forward``; ``dalpha`` has C (or one) elements.  Without ``dalpha`` one
+    element-wise launch; with it one pass that writes ``dx`` and per-segment partial sums, and a second launch that adds them
+    per channel in a fixed order."""
+    lib = _lib.load()
+    _need_gpu(x, alpha, dout)
+    rows, channels, n = _snake_shape("snake_backward", x, alpha, variant)
+    if dout.shape != x.shape:
+        raise AgxError(f"snake_backward: dout is {tuple(dout.shape)}, x is {tuple(x.shape)}")
+    alpha, dout = _f32c(alpha), _f32c(dout)
+    dx = torch.empty_like(x) if want_dx else None
+    dalpha = ws = None
+    nbytes = 0
+    if want_dalpha:
+        if x.numel() == 0:          # nothing is launched: the empty sum
+            return dx, torch.zeros(channels, dtype=torch.float32, device=x.device)
+        dalpha = torch.empty(channels, dtype=torch.float32, device=x.device)
+        nbytes = int(lib.agx_snake_backward_workspace_bytes(rows, channels, n))
+        ws = _workspace(nbytes, x.device, "agx_snake_backward_workspace_bytes")
+    _lib.check(lib.agx_snake_backward(_ptr(x), _ptr(alpha), _ptr(dout), _ptr(dx), _ptr(dalpha), _ptr(ws), nbytes, rows, channels, n,
+                                      int(variant), float(eps), _stream()), "agx_snake_backward")
+    return dx, dalpha

@@ -924,6 +924,48 @@ int agx_sigmoid_gate(const float *x, const float *z, float *out, int64_t n, void
 int agx_sigmoid_gate_backward(const float *x, const float *z, const float *dout, float *dx, float *dz, int64_t n,
                               void *stream);
 
+/* ------------------------------------------------------------------------- *
+ * Snake activations (networks/utils.py:44-105): Snek and SnekReLU.  fp32, contiguous tensors, stream-ordered, no
+ * synchronisation, no atomics: every result is bitwise reproducible.  x is rows = B * C contiguous rows of n floats
+ * (n = T for (B, C, T), n = H * W for (B, C, H, W)); the channel of a row is row % channels, alpha holds `channels`
+ * floats, and channels == 1 is one alpha for every row.  With a = alpha[c], inv = 1 / (a + eps) (fp32, once per row),
+ * theta = a * x and (s, c) = sincosf(theta), one range reduction per element:
+ *   out       = (variant ? max(x, 0) : x) + inv * s^2
+ *   dx        = dout * ((variant ? (x >= 0) : 1) + a * inv * 2 s c)
+ *   dalpha[c] = sum over the rows of channel c and their n positions of  dout * inv * (x * 2 s c - inv * s^2)
+ * SnekReLU's gradient at x == 0 (either sign of zero) is 1, the convention of torch.clamp.  A channel with a == 0 gives
+ * out == x (Snek), dx == dout * (the mask) and dalpha == 0 exactly.
+ * rows <= 0 or n <= 0 returns AGX_OK and launches nothing; channels <= 0, rows % channels != 0, a variant other than
+ * the two below or a shape beyond the one-dimensional grid (2^31 - 1 workgroups) is AGX_ERR_BAD_SHAPE before anything
+ * is launched; a NULL required pointer is AGX_ERR_NULL_POINTER.
+ * A non-finite x makes that element of out / dx non-finite and the dalpha of its channel NaN; it reaches no other
+ * element and no other channel, and costs no more time than a large finite x.
+ * ------------------------------------------------------------------------- */
+#define AGX_SNAKE_PLAIN 0 /* Snek:     x + sin^2(alpha x) / (alpha + eps) */
+#define AGX_SNAKE_RELU 1  /* SnekReLU: max(x, 0) + sin^2(alpha x) / (alpha + eps) */
+
+/* One launch.  out may be x.  Loads and stores are 16 bytes wide from the first 16-byte boundary of a row to its last
+ * whole quadruple and scalar at the ragged ends; all scalar where x and out are not equally aligned. */
+int agx_snake_forward(const float *x, const float *alpha, float *out, int64_t rows, int32_t channels, int64_t n,
+                      int32_t variant, float eps, void *stream);
+/* Bytes of the workspace agx_snake_backward needs when it is asked for dalpha: one float per (row, segment of 2048
+ * floats of the row).  0 for an empty or invalid shape. */
+size_t agx_snake_backward_workspace_bytes(int64_t rows, int32_t channels, int64_t n);
+/* dx and dalpha in one pass over x and dout; either may be NULL (both: nothing is launched).  dx may be dout.
+ * dalpha == NULL (frozen alphas) is one launch of the element-wise walk of the forward: no workspace, no reduction;
+ * its dx is bitwise the dx of the full call.
+ * dalpha != NULL is two launches.  Stage 1: one workgroup per (row, segment of 2048 floats) writes dx and one partial
+ * sum into the workspace, every float of which is written (AGX_ERR_WORKSPACE when it is NULL or shorter than the
+ * query's answer): walker j of 256 takes the segment's elements j, j + 256, ... in increasing order (one fma per
+ * element), the walkers of each group of 64 are added in a halving tree and the four groups as (g0 + g1) + (g2 + g3).
+ * Stage 2: one wavefront per channel numbers the channel's partials p = b * segments + segment over its rows
+ * b * channels + c; lane l adds p = l, l + 64, ... in increasing order, then the halving tree.  The segment length is
+ * a constant and the walk goes by index, never by address: the order of the sum is a function of (rows, channels, n)
+ * alone -- not of the device, the launch or the alignment of an operand. */
+int agx_snake_backward(const float *x, const float *alpha, const float *dout, float *dx, float *dalpha, void *workspace,
+                       size_t workspace_bytes, int64_t rows, int32_t channels, int64_t n, int32_t variant, float eps,
+                       void *stream);
+
 #ifdef __cplusplus
 }
 #endif
