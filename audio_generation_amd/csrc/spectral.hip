@@ -242,6 +242,10 @@ __global__ __launch_bounds__(256) void preemphasis_kernel(const float *__restric
 // it, the two homogeneous responses (unit y[-1], unit y[-2]); a 64-step carry over the lanes turns those into each
 // chunk's true entry state; pass 2 reruns the chunk from that state and writes the clamped output.  Sequential
 // depth 2 L / 64 instead of L (32 x 72 000 samples: 12.8 ms as one thread per row).
+// Pass 1 and the carry run in float64, the entry state is rounded to float32 for pass 2: an entry state is the sum of up
+// to 63 chunk responses pushed through as many 2 x 2 matrices, and with poles near the unit circle (a filter whose impulse
+// response is long against the chunk) float32 there cost 10 .. 300 x the error of the plain float32 recurrence
+// (tests/test_gpu_signal_edges.py has the table; 32 x 72 000 samples take 0.357 ms, 0.366 ms with float32 there).
 __global__ __launch_bounds__(64) void biquad_kernel(const float *__restrict__ x, float *__restrict__ y, int L, float b0,
                                                     float b1, float b2, float a1, float a2) {
     const int lane = threadIdx.x;
@@ -249,24 +253,28 @@ __global__ __launch_bounds__(64) void biquad_kernel(const float *__restrict__ x,
     float *yr = y + size_t(blockIdx.x) * L;
     const int Lc = (L + 63) / 64, n0 = min(L, lane * Lc), n1 = min(L, n0 + Lc);
     const float xm1 = n0 >= 1 ? xr[n0 - 1] : 0.f, xm2 = n0 >= 2 ? xr[n0 - 2] : 0.f;
-    float x1 = xm1, x2 = xm2, y1 = 0.f, y2 = 0.f, p1 = 1.f, p2 = 0.f, q1 = 0.f, q2 = 1.f;
-    for (int n = n0; n < n1; ++n) {
-        const float xn = xr[n];
-        const float yn = b0 * xn + b1 * x1 + b2 * x2 - a1 * y1 - a2 * y2;
-        const float pn = -a1 * p1 - a2 * p2, qn = -a1 * q1 - a2 * q2;
-        x2 = x1; x1 = xn; y2 = y1; y1 = yn;
-        p2 = p1; p1 = pn; q2 = q1; q1 = qn;
+    float in1 = 0.f, in2 = 0.f;
+    {
+        const double db0 = b0, db1 = b1, db2 = b2, da1 = a1, da2 = a2;
+        double x1 = xm1, x2 = xm2, y1 = 0.0, y2 = 0.0, p1 = 1.0, p2 = 0.0, q1 = 0.0, q2 = 1.0;
+        for (int n = n0; n < n1; ++n) {
+            const double xn = xr[n];
+            const double yn = db0 * xn + db1 * x1 + db2 * x2 - da1 * y1 - da2 * y2;
+            const double pn = -da1 * p1 - da2 * p2, qn = -da1 * q1 - da2 * q2;
+            x2 = x1; x1 = xn; y2 = y1; y1 = yn;
+            p2 = p1; p1 = pn; q2 = q1; q1 = qn;
+        }
+        // entry state of every chunk: s(c+1) = zero-state end of chunk c + M s(c)
+        double s1 = 0.0, s2 = 0.0;
+        for (int c = 0; c < 64; ++c) {
+            if (lane == c) { in1 = float(s1); in2 = float(s2); }
+            const double z1 = __shfl(y1, c), z2 = __shfl(y2, c);
+            const double m11 = __shfl(p1, c), m12 = __shfl(q1, c), m21 = __shfl(p2, c), m22 = __shfl(q2, c);
+            const double t1 = z1 + m11 * s1 + m12 * s2, t2 = z2 + m21 * s1 + m22 * s2;
+            s1 = t1; s2 = t2;
+        }
     }
-    // entry state of every chunk: s(c+1) = zero-state end of chunk c + M s(c)
-    float s1 = 0.f, s2 = 0.f, in1 = 0.f, in2 = 0.f;
-    for (int c = 0; c < 64; ++c) {
-        if (lane == c) { in1 = s1; in2 = s2; }
-        const float z1 = __shfl(y1, c), z2 = __shfl(y2, c);
-        const float m11 = __shfl(p1, c), m12 = __shfl(q1, c), m21 = __shfl(p2, c), m22 = __shfl(q2, c);
-        const float t1 = z1 + m11 * s1 + m12 * s2, t2 = z2 + m21 * s1 + m22 * s2;
-        s1 = t1; s2 = t2;
-    }
-    x1 = xm1; x2 = xm2; y1 = in1; y2 = in2;
+    float x1 = xm1, x2 = xm2, y1 = in1, y2 = in2;
     for (int n = n0; n < n1; ++n) {
         const float xn = xr[n];
         const float yn = b0 * xn + b1 * x1 + b2 * x2 - a1 * y1 - a2 * y2;

@@ -31,6 +31,9 @@ def preemphasis(x: Tensor, coeff: float = 0.97) -> Tensor:
 
 
 def lowpass_biquad(x: Tensor, sample_rate: int, cutoff_freq: float, q: float = 0.707) -> Tensor:
+    """Direct form I in the input's precision (float32 unless given float64) -- the definition, not an error-free reference:
+    with poles near the unit circle the float32 recurrence itself is 1e-5 .. 1e-3 off.  The float64 reference on the same
+    float32-rounded coefficients is ``tests/signal_ref.py: biquad_f64`` (``biquad_f32_sequential`` there is this recurrence)."""
     w0 = 2 * math.pi * cutoff_freq / sample_rate
     alpha = math.sin(w0) / 2 / q
     b0, b1, b2 = (1 - math.cos(w0)) / 2, 1 - math.cos(w0), (1 - math.cos(w0)) / 2
