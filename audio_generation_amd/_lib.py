@@ -20,6 +20,7 @@ IMPL_AUTO, IMPL_DIRECT, IMPL_MFMA, IMPL_MFMA_BF16X3 = 0, 1, 2, 3
 EPI_LEAKY_PRE, EPI_RESIDUAL, EPI_LEAKY_POST, EPI_GELU_PRE, EPI_MASK = 1, 2, 4, 8, 16
 FILM_CT, FILM_TC = 0, 1
 SNAKE_PLAIN, SNAKE_RELU = 0, 1
+CONFORMER_MAX_K = 64
 
 
 class ConvDesc(Structure):
@@ -251,6 +252,21 @@ SIGNATURES = {
     "agx_snake_backward_workspace_bytes": (c_size_t, [c_int64, c_int32, c_int64]),
     "agx_snake_backward": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_int64, c_int32,
                                    c_int64, c_int32, c_float, c_void_p]),
+    "agx_glu_dwconv_forward": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_float, c_void_p,
+                                       c_int32, c_int32, c_int32, c_int32, c_void_p]),
+    "agx_bn_stats_workspace_bytes": (c_size_t, [c_int32, c_int32, c_int32]),
+    "agx_bn_stats": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_float, c_void_p, c_size_t, c_int32,
+                             c_int32, c_int32, c_void_p]),
+    "agx_bn_silu_forward": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_float, c_int32, c_void_p, c_int32,
+                                    c_int32, c_int32, c_void_p]),
+    "agx_bn_silu_backward_workspace_bytes": (c_size_t, [c_int32, c_int32, c_int32]),
+    "agx_bn_silu_backward": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_float, c_int32, c_void_p,
+                                     c_void_p, c_void_p, c_void_p, c_size_t, c_int32, c_int32, c_int32, c_void_p]),
+    "agx_glu_dwconv_backward_workspace_bytes": (c_size_t, [c_int32, c_int32, c_int32, c_int32]),
+    "agx_glu_dwconv_backward": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_int32,
+                                        c_int32, c_int32, c_int32, c_void_p]),
+    "agx_silu": (c_int, [c_void_p, c_void_p, c_int64, c_void_p]),
+    "agx_silu_backward": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_void_p]),
 }
 
 _lib = None

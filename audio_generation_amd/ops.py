@@ -1860,3 +1860,161 @@ def snake_backward(x: Tensor, alpha: Tensor, dout: Tensor, variant: int, eps: fl
     _lib.check(lib.agx_snake_backward(_ptr(x), _ptr(alpha), _ptr(dout), _ptr(dx), _ptr(dalpha), _ptr(ws), nbytes, rows, channels, n,
                                       int(variant), float(eps), _stream()), "agx_snake_backward")
     return dx, dalpha
+
+
+# ------------------------------------------------------------------ Conformer convolution module (transformers.py:281-335)
+CONFORMER_MAX_K = _lib.CONFORMER_MAX_K
+
+
+def _glu_shape(op: str, u: Tensor, w: Tensor):
+    """(B, C, T, K) of the fused GLU + depthwise conv: u (B, 2 C, T), w (C, 1, K) or (C, K)."""
+    if u.dim() != 3 or u.shape[1] % 2 or u.dtype != torch.float32 or not u.is_contiguous():
+        raise AgxError(f"{op}: u must be a contiguous float32 (B, 2 C, T) tensor, got {tuple(u.shape)} {u.dtype}")
+    b, c2, t = u.shape
+    c = c2 // 2
+    if w.dim() not in (2, 3) or w.shape[0] != c or w.numel() != c * w.shape[-1]:
+        raise AgxError(f"{op}: w is {tuple(w.shape)}, expected ({c}, 1, K): one filter per channel")
+    k = w.shape[-1]
+    if not 1 <= k <= CONFORMER_MAX_K:
+        raise AgxError(f"{op}: kernel_size = {k} is outside [1, {CONFORMER_MAX_K}]")
+    return b, c, t, k
+
+
+def _bn_vectors(op: str, c: int, *vectors: Tensor):
+    for v in vectors:
+        if v.numel() != c:
+            raise AgxError(f"{op}: a per-channel vector holds {v.numel()} floats, the tensor has {c} channels")
+    return tuple(_f32c(v) for v in vectors)
+
+
+def _bct(op: str, *tensors: Tensor):
+    x = tensors[0]
+    if x.dim() != 3:
+        raise AgxError(f"{op}: expected (B, C, T), got {tuple(x.shape)}")
+    for t in tensors:
+        if t.shape != x.shape or t.dtype != torch.float32 or not t.is_contiguous():
+            raise AgxError(f"{op}: operands must be contiguous float32 tensors of one shape {tuple(x.shape)}, got {tuple(t.shape)} {t.dtype}")
+    return x.shape
+
+
+def glu_dwconv(u: Tensor, w: Tensor, bias: Tensor, bn: Optional[tuple] = None, eps: float = 1e-5) -> Tensor:
+    """``z = bias + depthwise_same_conv(u[:, :C] * sigmoid(u[:, C:]), w)``: u (B, 2 C, T) -> (B, C, T), one launch, the GLU
+    output never written.  ``bn`` = (gamma, beta, running_mean, running_var): the eval-mode module -- the normalisation on the
+    given statistics and SiLU applied in the same launch, ``y`` returned and ``z`` not written."""
+    lib = _lib.load()
+    _need_gpu(u, w, bias, *(bn or ()))
+    b, c, t, k = _glu_shape("glu_dwconv", u, w)
+    w, (bias,) = _f32c(w), _bn_vectors("glu_dwconv", c, bias)
+    bn = (None,) * 4 if bn is None else _bn_vectors("glu_dwconv", c, *bn)
+    out = torch.empty((b, c, t), dtype=torch.float32, device=u.device)
+    tok = _observer.begin("other", ("glu_dwconv", 12 * out.numel())) if _observer is not None else None
+    _lib.check(lib.agx_glu_dwconv_forward(_ptr(u), _ptr(w), _ptr(bias), *(_ptr(v) for v in bn), float(eps), _ptr(out), b, c, t, k,
+                                          _stream()), "agx_glu_dwconv_forward")
+    if tok is not None:
+        _observer.end(tok)
+    return out
+
+
+def glu_dwconv_backward(dz: Tensor, u: Tensor, w: Tensor, want_du: bool = True, want_params: bool = True):
+    """(du (B, 2 C, T) or None, dw of w's shape or None, dbias (C) or None) of ``glu_dwconv`` without ``bn``."""
+    lib = _lib.load()
+    _need_gpu(dz, u, w)
+    b, c, t, k = _glu_shape("glu_dwconv_backward", u, w)
+    if tuple(dz.shape) != (b, c, t):
+        raise AgxError(f"glu_dwconv_backward: dz is {tuple(dz.shape)}, expected {(b, c, t)}")
+    dz, w = _f32c(dz), _f32c(w)
+    du = torch.empty_like(u) if want_du else None
+    dw = dbias = ws = None
+    nbytes = 0
+    if want_params:
+        dw, dbias = torch.empty_like(w), torch.empty(c, dtype=torch.float32, device=u.device)
+        nbytes = int(lib.agx_glu_dwconv_backward_workspace_bytes(b, c, t, k))
+        ws = _workspace(nbytes, u.device, "agx_glu_dwconv_backward_workspace_bytes")
+    _lib.check(lib.agx_glu_dwconv_backward(_ptr(dz), _ptr(u), _ptr(w), _ptr(du), _ptr(dw), _ptr(dbias), _ptr(ws), nbytes, b, c, t, k,
+                                           _stream()), "agx_glu_dwconv_backward")
+    return du, dw, dbias
+
+
+def bn_stats(z: Tensor, running_mean: Optional[Tensor] = None, running_var: Optional[Tensor] = None,
+             num_batches_tracked: Optional[Tensor] = None, momentum: float = 0.1):
+    """(mean, var): the per-channel mean and biased variance of z (B, C, T) over (B, T), by a merge of per-segment (n, mean,
+    M2).  The running statistics (unbiased variance) and the int64 counter are updated in place by the finishing launch."""
+    lib = _lib.load()
+    _need_gpu(z, running_mean, running_var, num_batches_tracked)
+    b, c, t = _bct("bn_stats", z)
+    if b * t < 2:
+        raise ValueError(f"Expected more than 1 value per channel when training, got input size {tuple(z.shape)}")
+    for v in (running_mean, running_var):
+        if v is not None and (v.dtype != torch.float32 or not v.is_contiguous() or v.numel() != c):
+            raise AgxError(f"bn_stats: a running statistic must be a contiguous float32 tensor of {c} elements")
+    if num_batches_tracked is not None and (num_batches_tracked.dtype != torch.int64 or num_batches_tracked.numel() != 1):
+        raise AgxError("bn_stats: num_batches_tracked must be one int64")
+    mean, var = torch.empty(c, dtype=torch.float32, device=z.device), torch.empty(c, dtype=torch.float32, device=z.device)
+    nbytes = int(lib.agx_bn_stats_workspace_bytes(b, c, t))
+    ws = _workspace(nbytes, z.device, "agx_bn_stats_workspace_bytes")
+    _lib.check(lib.agx_bn_stats(_ptr(z), _ptr(mean), _ptr(var), _ptr(running_mean), _ptr(running_var), _ptr(num_batches_tracked),
+                                float(momentum), _ptr(ws), nbytes, b, c, t, _stream()), "agx_bn_stats")
+    return mean, var
+
+
+def bn_silu(z: Tensor, gamma: Tensor, beta: Tensor, mean: Tensor, var: Tensor, eps: float = 1e-5, training: bool = True,
+            out: Optional[Tensor] = None) -> Tensor:
+    """``silu(a)`` with ``a = (z - mean) rstd gamma + beta`` per channel (``training=False``: ``z scale + shift``, the folded
+    form of the fused eval launch, bit for bit).  ``out`` may be ``z``."""
+    lib = _lib.load()
+    _need_gpu(z, gamma, beta, mean, var, out)
+    b, c, t = _bct("bn_silu", z)
+    gamma, beta, mean, var = _bn_vectors("bn_silu", c, gamma, beta, mean, var)
+    out = _same_out("bn_silu", z, out)
+    tok = _observer.begin("other", ("bn_silu", 8 * z.numel())) if _observer is not None else None
+    _lib.check(lib.agx_bn_silu_forward(_ptr(z), _ptr(gamma), _ptr(beta), _ptr(mean), _ptr(var), float(eps), int(bool(training)),
+                                       _ptr(out), b, c, t, _stream()), "agx_bn_silu_forward")
+    if tok is not None:
+        _observer.end(tok)
+    return out
+
+
+def bn_silu_backward(dy: Tensor, z: Tensor, gamma: Tensor, beta: Tensor, mean: Tensor, var: Tensor, eps: float = 1e-5,
+                     training: bool = True, want_dz: bool = True, want_params: bool = True, out: Optional[Tensor] = None):
+    """(dz or None, dgamma or None, dbeta or None) of ``bn_silu`` -- in training mode through the batch statistics as well.
+    ``out`` (for dz) may be ``dy``."""
+    lib = _lib.load()
+    _need_gpu(dy, z, gamma, beta, mean, var, out)
+    b, c, t = _bct("bn_silu_backward", z, dy)
+    gamma, beta, mean, var = _bn_vectors("bn_silu_backward", c, gamma, beta, mean, var)
+    dz = _same_out("bn_silu_backward", z, out) if want_dz else None
+    dgamma = torch.empty(c, dtype=torch.float32, device=z.device) if want_params else None
+    dbeta = torch.empty(c, dtype=torch.float32, device=z.device) if want_params else None
+    if not want_dz and not want_params:
+        return None, None, None
+    nbytes = int(lib.agx_bn_silu_backward_workspace_bytes(b, c, t))
+    ws = _workspace(nbytes, z.device, "agx_bn_silu_backward_workspace_bytes")
+    _lib.check(lib.agx_bn_silu_backward(_ptr(dy), _ptr(z), _ptr(gamma), _ptr(beta), _ptr(mean), _ptr(var), float(eps),
+                                        int(bool(training)), _ptr(dz), _ptr(dgamma), _ptr(dbeta), _ptr(ws), nbytes, b, c, t,
+                                        _stream()), "agx_bn_silu_backward")
+    return dz, dgamma, dbeta
+
+
+def silu(x: Tensor, out: Optional[Tensor] = None) -> Tensor:
+    """``x * sigmoid(x)`` elementwise; ``out`` may be ``x`` (in place)."""
+    lib = _lib.load()
+    _need_gpu(x, out)
+    if x.dtype != torch.float32 or not x.is_contiguous():
+        raise AgxError("silu: x must be a contiguous float32 tensor")
+    out = _same_out("silu", x, out)
+    tok = _observer.begin("other", ("silu", 8 * x.numel())) if _observer is not None else None
+    _lib.check(lib.agx_silu(_ptr(x), _ptr(out), x.numel(), _stream()), "agx_silu")
+    if tok is not None:
+        _observer.end(tok)
+    return out
+
+
+def silu_backward(x: Tensor, dout: Tensor, out: Optional[Tensor] = None) -> Tensor:
+    """``dout * silu'(x)`` elementwise; ``out`` may be ``dout`` (in place)."""
+    lib = _lib.load()
+    _need_gpu(x, dout, out)
+    if x.dtype != torch.float32 or not x.is_contiguous() or dout.shape != x.shape or dout.dtype != torch.float32 or not dout.is_contiguous():
+        raise AgxError(f"silu_backward: x and dout must be contiguous float32 tensors of one shape (x {tuple(x.shape)}, dout {tuple(dout.shape)})")
+    out = _same_out("silu_backward", x, out)
+    _lib.check(lib.agx_silu_backward(_ptr(x), _ptr(dout), _ptr(out), x.numel(), _stream()), "agx_silu_backward")
+    return out

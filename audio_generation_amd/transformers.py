@@ -34,6 +34,9 @@ causal layer -- whose valid frames never see right padding anyway.
 axis, ``(1, dim, N)`` with ``N`` the sum of the lengths, and ``cu_seqlens``, the n_seq + 1 starts and ends.  Every op but the
 attention is pointwise in time and runs on the packed tensor as it is; the attention runs on the kernels of
 ``csrc/attention_packed.hip``, which read ``cu_seqlens`` from device memory.  ``pack_padded`` / ``unpack_padded`` convert.
+``ConformerConvBlock`` / ``ConformerBlock`` (transformers.py:281-368; build-defined where the reference cannot be constructed, see the
+classes) run their GLU, depthwise "same" convolution, BatchNorm1d and SiLU on the kernels of ``csrc/conformer.hip``, training and eval
+mode, forward and backward; ``FeedForward(activation=nn.SiLU)`` is their feed-forward half.
 The ``nn.LayerNorm`` / ``nn.Linear`` children only hold parameters.
 """
 from __future__ import annotations
@@ -82,10 +85,12 @@ class Alibi(nn.Module):
 
 class _PackedLinear:
     """One or more ``nn.Linear`` stacked along the output dim and run as one k=1 convolution over the channel dim of a
-    (B, C, T) tensor; caches the packed image of the stacked weights."""
+    (B, C, T) tensor; caches the packed image of the stacked weights.  ``scale`` (a power of two: exact in fp32) is folded into
+    the image and the bias -- ``scale (W h + b) == (scale W) h + scale b`` bit for bit, short of underflow -- and into the
+    parameter gradients ``backward`` returns: the 0.5 of ``ConformerBlock``'s half-step feed-forwards costs no launch."""
 
-    def __init__(self, *linears):
-        self.linears = linears
+    def __init__(self, *linears, scale: float = 1.0):
+        self.linears, self.scale = linears, float(scale)
         self.c_out = sum(l.out_features for l in linears)
         self.key = self.packed = self.bias = self.w3d = None
 
@@ -94,6 +99,8 @@ class _PackedLinear:
                      None if l.bias is None else (l.bias.data_ptr(), l.bias._version)) for l in self.linears)
         if key != self.key:
             w = torch.cat([l.weight.detach() for l in self.linears], dim=0)
+            if self.scale != 1.0:
+                w = w * self.scale
             c_out, c_in = w.shape
             desc = ops.conv_desc(CONV_CAUSAL, 1, c_in, c_out, 1 << 20, 1)
             self.w3d = w.reshape(c_out, c_in, 1).contiguous()      # the native backward reads it
@@ -103,6 +110,8 @@ class _PackedLinear:
                                        else torch.zeros(l.out_features, device=w.device) for l in self.linears])
             else:
                 self.bias = None
+            if self.bias is not None and self.scale != 1.0:
+                self.bias = self.bias * self.scale
             self.key = key
         return self.packed, self.bias
 
@@ -128,6 +137,8 @@ class _PackedLinear:
             pk = ops.conv_pack_bwd(desc, self.w3d)
             dx = ops.conv_bwd_data(desc, dy, pk, add, mask, slope) if pre is None else ops.conv_bwd_data_gelu(desc, dy, pk, pre)
         dw, grads, row = dw.reshape(self.c_out, c_in), [], 0
+        if self.scale != 1.0:      # dy reached the scaled layer: the gradients of the unscaled parameters
+            dw, db = dw * self.scale, None if db is None else db * self.scale
         for l in self.linears:
             rows = slice(row, row + l.out_features)
             grads += [dw[rows]] if l.bias is None else [dw[rows], db[rows]]
@@ -642,25 +653,41 @@ class Attention(nn.Module):
 
 
 class FeedForward(nn.Module):
-    """transformers.py:193-223: LN -> Linear -> exact GELU -> Linear."""
+    """transformers.py:193-223: LN -> Linear -> activation -> Linear.  ``nn.GELU`` (exact) is fused into the FFN-in conv's epilogue;
+    ``nn.SiLU`` -- what ``ConformerBlock`` passes -- runs FFN-in with epilogue 0 and the stand-alone ``agx_silu`` behind it."""
 
     def __init__(self, dim, hidden_dim, dropout=0., activation=nn.GELU):
         super().__init__()
-        if activation is not nn.GELU:
-            raise NotImplementedError("only GELU is fused into the FFN kernel epilogue")
+        if activation is not nn.GELU and activation is not nn.SiLU:
+            raise NotImplementedError("only GELU (fused into the FFN kernel epilogue) and SiLU (one element-wise kernel) have kernels")
+        self.silu = activation is nn.SiLU
         self.net = nn.Sequential(nn.LayerNorm(dim), nn.Linear(dim, hidden_dim), activation(), nn.Dropout(dropout),
                                  nn.Linear(hidden_dim, dim), nn.Dropout(dropout))
         self._l1, self._l2 = _PackedLinear(self.net[1]), _PackedLinear(self.net[4])
+        self._l2_scaled = {}      # scale -> FFN-out with the scale folded into its image (``run_bct``: ``scale``)
         self.last_dropout_seed = None
 
+    def _out(self, scale: float) -> _PackedLinear:
+        if scale == 1.0:
+            return self._l2
+        if scale not in self._l2_scaled:
+            self._l2_scaled[scale] = _PackedLinear(self.net[4], scale=scale)
+        return self._l2_scaled[scale]
+
     def run_bct(self, x: Tensor, residual: Optional[Tensor] = None, keep: Optional[dict] = None,
-                drop: Optional[tuple] = None) -> Tensor:
-        """In training mode with ``dropout > 0`` the hidden tensor is dropped in place behind the fused GELU (``net[3]``) and
+                drop: Optional[tuple] = None, scale: float = 1.0) -> Tensor:
+        """In training mode with ``dropout > 0`` the hidden tensor is dropped in place behind the activation (``net[3]``) and
         the FFN-out result before the residual add (``net[5]``: the conv runs without its fused residual, then
-        ``dropout_add(., residual)``); otherwise the two launches it always was."""
+        ``dropout_add(., residual)``); otherwise the two launches it always was (SiLU: three).  ``scale`` (a power of two)
+        multiplies the result before the residual add, folded into FFN-out's packed image: no launch."""
         p_hid, p_out = _active_p(self.net[3]), _active_p(self.net[5])
+        l2 = self._out(scale)
         xn = _ln(self.net[0], x)
-        hid = self._l1.forward(xn, EPI_GELU_PRE)
+        if self.silu:
+            pre = self._l1.forward(xn)
+            hid = ops.silu(pre, out=None if keep is not None else pre)      # the backward reads the pre-activation
+        else:
+            hid = self._l1.forward(xn, EPI_GELU_PRE)
         if p_hid > 0 or p_out > 0:
             seed, layer = _site(drop, self)
             if keep is not None:
@@ -669,22 +696,30 @@ class FeedForward(nn.Module):
             ops.dropout_add(hid, None, p_hid, seed, 4 * layer + SITE_FFN_HIDDEN, out=hid)
         if keep is not None:
             keep.update(x1=x, xn2=xn, hid=hid)     # with dropout: the masked hidden tensor, FFN-out's input
+            if self.silu:
+                keep.update(pre=pre)
         if p_out > 0:
-            out = self._l2.forward(hid)
+            out = l2.forward(hid)
             return ops.dropout_add(out, residual, p_out, seed, 4 * layer + SITE_FFN_OUT, out=out)
-        return self._l2.forward(hid, EPI_RESIDUAL if residual is not None else 0, residual)
+        return l2.forward(hid, EPI_RESIDUAL if residual is not None else 0, residual)
 
-    def backward_bct(self, kept: dict, g: Tensor):
+    def backward_bct(self, kept: dict, g: Tensor, scale: float = 1.0):
         """As ``Attention.backward_bct``; the GELU gradient sits in the FFN-out bwd-data epilogue, at the pre-activation,
-        which is recomputed with one conv launch: the forward's FFN-in projection with epilogue 0."""
+        which is recomputed with one conv launch: the forward's FFN-in projection with epilogue 0.  SiLU: the plain k = 1
+        backward of FFN-out, then ``agx_silu_backward`` in place at the saved pre-activation."""
         d = kept.get("drop") or {}
         g_out = g        # the FFN-out site: the residual branch takes g unmasked (``add=g`` below)
         if d.get("out"):
             g_out = ops.dropout_add(g, None, d["out"], d["seed"], 4 * d["layer"] + SITE_FFN_OUT)
-        pre = self._l1.forward(kept["xn2"])
-        dpre, g2 = self._l2.backward(kept["hid"], g_out, pre=pre)
-        if d.get("hid"):     # d hid~ -> d pre: mask * scale and the GELU gradient commute
+        if self.silu:
+            dpre, g2 = self._out(scale).backward(kept["hid"], g_out)
+        else:
+            pre = self._l1.forward(kept["xn2"])
+            dpre, g2 = self._out(scale).backward(kept["hid"], g_out, pre=pre)
+        if d.get("hid"):     # d hid~ -> d pre: mask * scale and the activation's gradient commute
             ops.dropout_add(dpre, None, d["hid"], d["seed"], 4 * d["layer"] + SITE_FFN_HIDDEN, out=dpre)
+        if self.silu:
+            ops.silu_backward(kept["pre"], dpre, out=dpre)
         dxn, g1 = self._l1.backward(kept["xn2"], dpre)
         dx1, dweight, dbias = _ln_bwd(self.net[0], kept["x1"], dxn, add=g)
         return dx1, [dweight, dbias] + g1 + g2
@@ -1146,3 +1181,224 @@ class TransformerBottleneck(nn.Module):
 
     def update_cutoff(self, new_cutoff=None, ratio=None):
         return None
+
+
+class _Conv1x1:
+    """A k = 1 ``nn.Conv1d`` seen as the ``nn.Linear`` ``_PackedLinear`` stacks: ``weight`` (out, in) is a view of the conv's
+    (out, in, 1), so its data pointer and version are the parameter's."""
+
+    def __init__(self, conv: nn.Conv1d):
+        self.conv, self.out_features = conv, conv.out_channels
+
+    @property
+    def weight(self):
+        return self.conv.weight[:, :, 0]
+
+    @property
+    def bias(self):
+        return self.conv.bias
+
+
+# Stream ids of the dropout sites of a ConformerBlock: its four sub-blocks are "layers" 0..3 of the one seed a call draws, so
+# first_ff takes the streams 2, 3, the attention 4, 5, the conv block 8 and second_ff 14, 15 -- seven distinct pairs.
+CONFORMER_FF1, CONFORMER_ATTENTION, CONFORMER_CONV, CONFORMER_FF2 = 0, 1, 2, 3
+SITE_CONV_OUT = 0
+
+
+class ConformerConvBlock(nn.Module):
+    """transformers.py:281-335, the convolution module of a Conformer block: LayerNorm -> pointwise conv C -> 2 C -> GLU ->
+    depthwise conv, ``padding="same"`` -> BatchNorm1d -> SiLU -> pointwise conv -> dropout, with the reference's ``net`` layout
+    and ``state_dict()`` keys.  Build-defined, because the reference's class cannot be constructed or run:
+    ``out_channels = in_channels`` (the reference reads an attribute it never sets: the conv is depthwise), and the LayerNorm
+    acts over channels, before the rearrangement to (b, d, n), as in the Conformer paper (the reference applies it after, to
+    the time axis).  ``forward`` takes (B, T, C); ``run_bct`` the channel-major (B, C, T) it computes in.
+
+    Eval mode is four launches: LN, pointwise-in, the fused GLU + depthwise conv + BatchNorm (running statistics) + SiLU kernel
+    of ``csrc/conformer.hip``, pointwise-out (+ residual).  Training mode: LN, pointwise-in, GLU + depthwise conv, batch
+    statistics (two launches; the running statistics and ``num_batches_tracked`` are updated by the second), normalise + SiLU,
+    pointwise-out, and with ``dropout > 0`` ``dropout_add``.  The ``nn`` children only hold parameters and buffers."""
+
+    def __init__(self, in_channels, kernel_size=17, dropout=0.1, activation=nn.SiLU):
+        super().__init__()
+        if activation is not nn.SiLU:
+            raise NotImplementedError("only SiLU is fused behind the BatchNorm (csrc/conformer.hip)")
+        if int(kernel_size) != kernel_size or not 1 <= kernel_size <= ops.CONFORMER_MAX_K:
+            raise ValueError(f"kernel_size = {kernel_size}: the depthwise kernel takes 1 <= kernel_size <= {ops.CONFORMER_MAX_K}")
+        self.in_channels = self.out_channels = in_channels
+        self.kernel_size = int(kernel_size)
+        self.net = nn.Sequential(
+            nn.LayerNorm(in_channels),
+            nn.Conv1d(in_channels, 2 * in_channels, kernel_size=1),
+            nn.GLU(dim=-2),
+            nn.Conv1d(in_channels, in_channels, kernel_size=self.kernel_size, padding="same", groups=in_channels),
+            nn.BatchNorm1d(in_channels),
+            activation(),
+            nn.Conv1d(in_channels, in_channels, kernel_size=1),
+            nn.Dropout(dropout) if dropout > 0 else nn.Identity())
+        self._in, self._out = _PackedLinear(_Conv1x1(self.net[1])), _PackedLinear(_Conv1x1(self.net[6]))
+        self.last_dropout_seed = None
+
+    def _p_out(self) -> float:
+        return _active_p(self.net[7]) if isinstance(self.net[7], nn.Dropout) else 0.0
+
+    def run_bct(self, x: Tensor, residual: Optional[Tensor] = None, keep: Optional[dict] = None,
+                drop: Optional[tuple] = None) -> Tensor:
+        """(B, C, T) -> net(x) [+ residual: x itself].  ``keep`` marks a forward whose backward will run (``backward_bct``): z is then
+        written in eval mode too.  With autograd on and no ``keep`` the call goes through ``_ConformerNative``."""
+        if residual is not None and residual is not x:
+            raise AgxError("ConformerConvBlock: the residual is the block's own input (x + net(x)), or None")
+        if keep is None and needs_grad(x, self):
+            return _ConformerNative.apply(self, residual is not None, drop, x, *list(self.parameters()))
+        dw, bn = self.net[3], self.net[4]
+        if x.dim() != 3 or x.shape[1] != self.in_channels:
+            raise AgxError(f"ConformerConvBlock: x is {tuple(x.shape)}, expected (B, {self.in_channels}, T)")
+        if bn.training and x.shape[0] * x.shape[2] < 2:
+            raise ValueError(f"Expected more than 1 value per channel when training, got input size {tuple(x.shape)}")
+        p = self._p_out()
+        gamma, beta = bn.weight.detach(), bn.bias.detach()
+        xn = _ln(self.net[0], x)
+        u = self._in.forward(xn)
+        if not bn.training and keep is None:
+            y = ops.glu_dwconv(u, dw.weight.detach(), dw.bias.detach(), bn=(gamma, beta, bn.running_mean, bn.running_var), eps=bn.eps)
+        else:
+            z = ops.glu_dwconv(u, dw.weight.detach(), dw.bias.detach())
+            if bn.training:
+                mean, var = ops.bn_stats(z, bn.running_mean, bn.running_var, bn.num_batches_tracked, bn.momentum)
+            else:       # frozen statistics: a private copy, the backward must see what the forward saw
+                mean, var = bn.running_mean.clone(), bn.running_var.clone()
+            y = ops.bn_silu(z, gamma, beta, mean, var, bn.eps, training=bn.training)
+            if keep is not None:
+                keep.update(cx=x, cxn=xn, u=u, z=z, mean=mean, var=var, y=y)
+                keep["conv"] = dict(training=bn.training)
+        if p > 0:
+            seed, layer = _site(drop, self)
+            if keep is not None:
+                keep["conv"].update(p=p, seed=seed, layer=layer)
+            out = self._out.forward(y)
+            return ops.dropout_add(out, residual, p, seed, 4 * layer + SITE_CONV_OUT, out=out)
+        return self._out.forward(y, EPI_RESIDUAL if residual is not None else 0, residual)
+
+    def backward_bct(self, kept: dict, g: Tensor, residual: bool = True):
+        """``g`` = the gradient of ``run_bct(x, residual=x, keep=kept)`` -> (dx, gradients in ``parameters()`` order); without
+        ``residual`` the gradient does not reach x around the block."""
+        c = kept["conv"]
+        dw, bn = self.net[3], self.net[4]
+        g_out = g
+        if c.get("p"):
+            g_out = ops.dropout_add(g, None, c["p"], c["seed"], 4 * c["layer"] + SITE_CONV_OUT)
+        dy, g_o = self._out.backward(kept["y"], g_out)
+        dz, dgamma, dbeta = ops.bn_silu_backward(dy, kept["z"], bn.weight.detach(), bn.bias.detach(), kept["mean"], kept["var"],
+                                                 bn.eps, training=c["training"], out=dy)
+        du, d_dw, d_db = ops.glu_dwconv_backward(dz, kept["u"], dw.weight.detach())
+        dxn, g_i = self._in.backward(kept["cxn"], du)
+        dx, dweight, dbias = _ln_bwd(self.net[0], kept["cx"], dxn, add=g if residual else None)
+        return dx, [dweight, dbias, g_i[0].unsqueeze(-1), g_i[1], d_dw, d_db, dgamma, dbeta, g_o[0].unsqueeze(-1), g_o[1]]
+
+    def forward(self, x: Tensor) -> Tensor:
+        return self.run_bct(x.transpose(1, 2).contiguous()).transpose(1, 2).contiguous()
+
+
+class ConformerBlock(nn.Module):
+    """transformers.py:337-368: ``x += 0.5 ff1(x); x += attention(x); x += conv_block(x); LN(x + 0.5 ff2(x))``.  Build-defined
+    where the reference cannot be constructed: the stray ``activation`` keyword it passes to ``Attention`` is
+    dropped, and ``kernel_size`` / ``context_x`` -- which the reference hard-codes through the defaults of its children -- are
+    keyword-only arguments.  Both 0.5 factors are folded into the packed image of the FFN-out projections (``_PackedLinear``):
+    no launch, no pass over the tensor.
+
+    An eval-mode call is 4 + 4 + 4 + 4 + 1 = 17 launches: per feed-forward LN, FFN-in, SiLU, FFN-out (+res) -- the SiLU one more
+    than a GELU feed-forward --, the attention's LN, QKV, attention, W_o (+res), the conv block's four and the final LN.  A
+    training-mode call with ``dropout > 0`` draws one 64-bit seed (``last_dropout_seed``; ``torch.manual_seed`` reproduces it);
+    its seven sites take distinct stream ids (``CONFORMER_*``)."""
+
+    def __init__(self, dim, hidden_dim_ratio=4, heads=8, dropout=0.1, ff_activation=nn.SiLU, conv_activation=nn.SiLU, *,
+                 kernel_size=17, context_x=32):
+        super().__init__()
+        self.first_ff = FeedForward(dim, dim * hidden_dim_ratio, activation=ff_activation, dropout=dropout)
+        self.attention = Attention(dim, n_heads=heads, dim_head=dim // heads, dropout=dropout, context_x=context_x)
+        self.conv_block = ConformerConvBlock(dim, kernel_size=kernel_size, dropout=dropout, activation=conv_activation)
+        self.second_ff = FeedForward(dim, dim * hidden_dim_ratio, activation=ff_activation, dropout=dropout)
+        self.layer_norm = nn.LayerNorm(dim)
+        self.dim, self.context_x = dim, context_x
+        self.last_dropout_seed = None
+
+    def _dropout_active(self) -> bool:
+        sites = [self.attention.dropout, self.conv_block.net[7]] + [f.net[i] for f in (self.first_ff, self.second_ff) for i in (3, 5)]
+        return any(isinstance(m, nn.Dropout) and m.training and m.p > 0 for m in sites)
+
+    def _hip_bct(self, x: Tensor, keep: Optional[dict] = None) -> Tensor:
+        """The one forward walk.  ``keep``: the training forward -- the dict receives one dict of named intermediates per
+        sub-block."""
+        if x.dim() != 3 or x.shape[1] != self.dim:
+            raise AgxError(f"ConformerBlock: x is {tuple(x.shape)}, expected (B, {self.dim}, T)")
+        if x.shape[-1] > self.context_x:
+            raise AgxError(f"sequence length {x.shape[-1]} exceeds the ALiBi context {self.context_x}")
+        seed = None
+        if self._dropout_active():
+            seed = self.last_dropout_seed = ops.draw_dropout_seed()
+        kept = {name: (None if keep is None else {}) for name in ("ff1", "attention", "conv", "ff2")}
+        site = (lambda layer: None) if seed is None else (lambda layer: (seed, layer))
+        x = self.first_ff.run_bct(x, x, kept["ff1"], site(CONFORMER_FF1), scale=0.5)
+        x = self.attention.run_bct(x, x, kept["attention"], None, site(CONFORMER_ATTENTION))
+        x = self.conv_block.run_bct(x, x, kept["conv"], site(CONFORMER_CONV))
+        x = self.second_ff.run_bct(x, x, kept["ff2"], site(CONFORMER_FF2), scale=0.5)
+        if keep is not None:
+            kept["ln"] = dict(x4=x)
+            keep.update(kept)
+        return _ln(self.layer_norm, x)
+
+    def backward_bct(self, keep: dict, g: Tensor):
+        """``g`` = the gradient of ``_hip_bct(x, keep)`` -> (dx, gradients in ``parameters()`` order)."""
+        g, dweight, dbias = _ln_bwd(self.layer_norm, keep["ln"]["x4"], g, add=None)
+        g, g_ff2 = self.second_ff.backward_bct(keep["ff2"], g, scale=0.5)
+        g, g_conv = self.conv_block.backward_bct(keep["conv"], g)
+        g, g_attention, _ = self.attention.backward_bct(keep["attention"], g)
+        g, g_ff1 = self.first_ff.backward_bct(keep["ff1"], g, scale=0.5)
+        return g, g_ff1 + g_attention + g_conv + g_ff2 + [dweight, dbias]
+
+    def run_bct(self, x: Tensor) -> Tensor:
+        """Channel-major (B, dim, T) in and out, T <= context_x.  With autograd on, the backward runs on the HIP kernels too
+        (``_ConformerNative``)."""
+        if needs_grad(x, self):
+            return _ConformerNative.apply(self, False, None, x, *list(self.parameters()))
+        return self._hip_bct(x)
+
+    def forward(self, x: Tensor) -> Tensor:
+        return self.run_bct(x.transpose(1, 2).contiguous()).transpose(1, 2).contiguous()
+
+
+class _ConformerNative(torch.autograd.Function):
+    """``ConformerBlock`` or ``ConformerConvBlock`` forward + hand-written backward on the HIP kernels, in the style of
+    ``_TransformerNative``: the k = 1 conv backward for every Linear and pointwise conv, the attention and LayerNorm backward
+    kernels, ``agx_silu_backward``, and the three backward ops of ``csrc/conformer.hip``; the dropout masks of a training-mode
+    forward are regenerated from the seed saved in the context.  No ATen arithmetic touches an activation.  ``residual`` and
+    ``drop`` are the conv block's own arguments (a block passes False and None)."""
+
+    @staticmethod
+    def forward(ctx, module, residual: bool, drop, x: Tensor, *params: Tensor):
+        keep = {}
+        x = x.detach()
+        with torch.no_grad():
+            if isinstance(module, ConformerBlock):
+                out = module._hip_bct(x, keep)
+            else:
+                keep["conv"] = {}
+                out = module.run_bct(x, x if residual else None, keep["conv"], drop)
+        # tensors go through save_for_backward, everything else (seeds, probabilities, modes) stays in the context
+        ctx.meta = {name: {k: v for k, v in kept.items() if not isinstance(v, Tensor)} for name, kept in keep.items()}
+        ctx.names = [(name, k) for name, kept in keep.items() for k, v in kept.items() if isinstance(v, Tensor)]
+        ctx.save_for_backward(*[keep[name][k] for name, k in ctx.names])
+        ctx.module, ctx.residual = module, residual
+        return out
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g: Tensor):
+        keep = {name: dict(meta) for name, meta in ctx.meta.items()}
+        for (name, k), t in zip(ctx.names, ctx.saved_tensors):
+            keep[name][k] = t
+        g = g.contiguous()
+        if isinstance(ctx.module, ConformerBlock):
+            dx, grads = ctx.module.backward_bct(keep, g)
+        else:
+            dx, grads = ctx.module.backward_bct(keep["conv"], g, residual=ctx.residual)
+        return (None, None, None, dx if ctx.needs_input_grad[3] else None, *grads)

@@ -966,6 +966,79 @@ int agx_snake_backward(const float *x, const float *alpha, const float *dout, fl
                        size_t workspace_bytes, int64_t rows, int32_t channels, int64_t n, int32_t variant, float eps,
                        void *stream);
 
+/* ------------------------------------------------------------------------- *
+ * The convolution module of a Conformer block (networks/transformers.py:281-335) and the SiLU of its feed-forward
+ * halves.  fp32, channel-major contiguous (B, C, T), stream-ordered, no synchronisation, no atomics: every result is
+ * bitwise reproducible, and every sum has one order that is a function of (B, C, T, K) alone -- elements are walked by
+ * index, never by address, so the alignment of an operand changes no bit.  With left = (K - 1) / 2 (torch's "same":
+ * K - 1 - left zeros on the right) and sigmoid(v) = 1 / (1 + expf(-v)) as agx_sigmoid_gate has it (v <= -89: exactly
+ * 0, v >= 17: exactly 1):
+ *   g[b, c, t] = u[b, c, t] * sigmoid(u[b, C + c, t])                   u is (B, 2 C, T); g is never written
+ *   z[b, c, t] = bias[c] + sum_k w[c, k] g[b, c, t + k - left]          zeros outside [0, T); one fma per tap, k rising
+ *   rstd = 1 / sqrtf(var[c] + eps)    scale = gamma[c] rstd    shift = beta[c] - mean[c] scale    zhat = (z - mean[c]) rstd
+ *   a = training ? zhat * gamma[c] + beta[c] : z * scale + shift        y = a * sigmoid(a)
+ * A channel whose taps are all zero gives z == bias[c] exactly for finite u.
+ * B, C, T <= 0, K outside [1, AGX_CONFORMER_MAX_K] or a shape beyond the one-dimensional grid (2^31 - 1 workgroups) is
+ * AGX_ERR_BAD_SHAPE before anything is launched; a NULL required pointer is AGX_ERR_NULL_POINTER; a workspace that is
+ * NULL or shorter than its query's answer is AGX_ERR_WORKSPACE.  Every float of a workspace that is read has been written
+ * by the same call.  A non-finite value of u, z or dy in channel c stays in channel c -- its outputs, its statistics
+ * and its parameter gradients -- and where no statistic is taken (the forward with gamma) within the K positions around
+ * it.
+ * ------------------------------------------------------------------------- */
+#define AGX_CONFORMER_MAX_K 64
+/* One launch, one workgroup per (b, c, tile of 1024 positions).  gamma == beta == mean == var == NULL: out = z.  All
+ * four given (eval mode, the running statistics): out = y with training = 0 above, and z is not written. */
+int agx_glu_dwconv_forward(const float *u, const float *w, const float *bias, const float *gamma, const float *beta,
+                           const float *mean, const float *var, float eps, float *out, int32_t B, int32_t C, int32_t T,
+                           int32_t K, void *stream);
+/* Bytes of the workspace of agx_bn_stats: two floats per (b, c, segment of 2048 positions).  0 for an invalid shape. */
+size_t agx_bn_stats_workspace_bytes(int32_t B, int32_t C, int32_t T);
+/* mean[c] and the biased variance var[c] of z over (B, T), two launches.  Stage 1: one workgroup per (b, c, segment)
+ * writes the segment's mean and M2 = sum (z - mean)^2 about it (two passes over registers, one read).  Stage 2: one
+ * wavefront per channel merges the (n, mean, M2) of the segments p = b * segments + segment by Chan's rule -- lane l
+ * takes p = l, l + 64, ... in increasing order, then a halving tree with the lower lane on the left -- so no variance is
+ * ever formed as E[z^2] - E[z]^2.  The same stage updates, where the pointers are not NULL,
+ *   running_mean += momentum (mean - running_mean),  running_var += momentum (M2 / (B T - 1) - running_var)
+ * and adds 1 to *num_batches_tracked.  B * T < 2 is AGX_ERR_BAD_SHAPE. */
+int agx_bn_stats(const float *z, float *mean, float *var, float *running_mean, float *running_var,
+                 int64_t *num_batches_tracked, float momentum, void *workspace, size_t workspace_bytes, int32_t B, int32_t C,
+                 int32_t T, void *stream);
+/* y from z, one launch on the row walk of agx_snake_forward (16-byte accesses between the row's 16-byte boundaries,
+ * scalar at its ragged ends and everywhere when z and y are not equally aligned).  y may be z.  With training == 0 the
+ * result is bitwise what agx_glu_dwconv_forward writes for the same z. */
+int agx_bn_silu_forward(const float *z, const float *gamma, const float *beta, const float *mean, const float *var,
+                        float eps, int32_t training, float *y, int32_t B, int32_t C, int32_t T, void *stream);
+/* Bytes of the workspace of agx_bn_silu_backward: two floats per (b, c, segment of 2048 positions) and 2 C. */
+size_t agx_bn_silu_backward_workspace_bytes(int32_t B, int32_t C, int32_t T);
+/* With da = dy * s (1 + a (1 - s)), s = sigmoid(a):
+ *   dbeta[c] = sum da,   dgamma[c] = sum da zhat                                    (over b and t)
+ *   training == 0:  dz = da scale                       (frozen statistics; two launches)
+ *   training != 0:  dz = scale (da - dbeta[c] / (B T) - zhat dgamma[c] / (B T))      (three launches)
+ * Stage 1: one workgroup per (b, c, segment of 2048) sums da and da zhat -- walker j of 256 takes the elements j,
+ * j + 256, ... in increasing order, the walkers of a group of 64 are added in a halving tree, the groups as
+ * (g0 + g1) + (g2 + g3) -- and writes dz where the statistics are frozen.  Stage 2: one wavefront per channel, lane l
+ * adds the partials p = l, l + 64, ... (p = b * segments + segment), then the halving tree.  Stage 3 (training): dz on the
+ * row walk of agx_bn_silu_forward.  dz, or dgamma and dbeta, may be NULL (all three: nothing is launched); dz may be dy. */
+int agx_bn_silu_backward(const float *dy, const float *z, const float *gamma, const float *beta, const float *mean,
+                         const float *var, float eps, int32_t training, float *dz, float *dgamma, float *dbeta,
+                         void *workspace, size_t workspace_bytes, int32_t B, int32_t C, int32_t T, void *stream);
+/* Bytes of the workspace of agx_glu_dwconv_backward when it is asked for dw and dbias: K + 1 floats per (b, c, tile of
+ * 1024 positions). */
+size_t agx_glu_dwconv_backward_workspace_bytes(int32_t B, int32_t C, int32_t T, int32_t K);
+/* Backward of z(u, w, bias); g and the sigmoid are recomputed from u.
+ *   dg[b, c, t] = sum_k w[c, k] dz[b, c, t + left - k]       (one fma per tap, k rising, from 0)
+ *   du[b, c, t] = dg s,   du[b, C + c, t] = (dg u[b, c, t]) (s (1 - s)),   s = sigmoid(u[b, C + c, t])
+ *   dw[c, k] = sum_{b, t} dz[b, c, t] g[b, c, t + k - left],   dbias[c] = sum_{b, t} dz[b, c, t]
+ * du (B, 2 C, T): both halves are written.  du may be NULL; dw and dbias come together or not at all (all NULL: nothing
+ * is launched).  Without dw one launch and no workspace; with it two: the tile's share of every sum (walkers, halving
+ * tree and groups as above), then one wavefront per channel over the shares p = b * tiles + tile. */
+int agx_glu_dwconv_backward(const float *dz, const float *u, const float *w, float *du, float *dw, float *dbias,
+                            void *workspace, size_t workspace_bytes, int32_t B, int32_t C, int32_t T, int32_t K, void *stream);
+/* out = x * sigmoid(x) over n floats, one launch; out may be x. */
+int agx_silu(const float *x, float *out, int64_t n, void *stream);
+/* dx = dout * s (1 + x (1 - s)), s = sigmoid(x), one launch; dx may be dout or x. */
+int agx_silu_backward(const float *x, const float *dout, float *dx, int64_t n, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
