@@ -21,6 +21,7 @@ EPI_LEAKY_PRE, EPI_RESIDUAL, EPI_LEAKY_POST, EPI_GELU_PRE, EPI_MASK = 1, 2, 4, 8
 FILM_CT, FILM_TC = 0, 1
 SNAKE_PLAIN, SNAKE_RELU = 0, 1
 CONFORMER_MAX_K = 64
+CONFORMER_MAX_STEP = 64     # AGX_CONFORMER_MAX_STEP: the frames one agx_glu_dwconv_step takes
 
 
 class ConvDesc(Structure):
@@ -265,6 +266,14 @@ SIGNATURES = {
     "agx_glu_dwconv_backward_workspace_bytes": (c_size_t, [c_int32, c_int32, c_int32, c_int32]),
     "agx_glu_dwconv_backward": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_int32,
                                         c_int32, c_int32, c_int32, c_void_p]),
+    "agx_glu_dwconv_causal_forward": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_float, c_void_p,
+                                              c_void_p, c_int32, c_int32, c_int32, c_int32, c_void_p]),
+    "agx_glu_dwconv_causal_backward_workspace_bytes": (c_size_t, [c_int32, c_int32, c_int32, c_int32]),
+    "agx_glu_dwconv_causal_backward": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_int32,
+                                               c_int32, c_int32, c_int32, c_void_p]),
+    "agx_glu_dwconv_step": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_float, c_void_p, c_void_p,
+                                    c_int32, c_int32, c_int32, c_int32, c_void_p]),
+    "agx_glu_hist_update": (c_int, [c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_void_p]),
     "agx_silu": (c_int, [c_void_p, c_void_p, c_int64, c_void_p]),
     "agx_silu_backward": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_void_p]),
 }

@@ -9,6 +9,10 @@
 //
 // g is never written to memory: the forward and the backward stage it in LDS from u, with its K - 1 halo.  An element is indexed,
 // never addressed: the arithmetic and the order of every sum do not depend on how an operand is aligned.
+//
+// The causal form (agx.h: left = K - 1) is the same kernels with the other halo width, and it streams: hist (B, C, K - 1) holds the
+// post-GLU values of the K - 1 frames before a call -- the one place g is written -- and the step kernel (7) and the history
+// update (8) rewrite it in place.  Chunked calls are bit for bit the single call: an output's fma chain sees the same K operands.
 #include "common.hpp"
 
 namespace {
@@ -71,30 +75,35 @@ __device__ inline Norm norm_of(const float *__restrict__ gamma, const float *__r
 __device__ inline float zhat_of(float z, const Norm &n) { return (z - n.mean) * n.rstd; }
 __device__ inline float act_of(float z, const Norm &n) { return n.training ? fmaf(zhat_of(z, n), n.gamma, n.beta) : fmaf(z, n.scale, n.shift); }
 
-// g of the positions [first, first + span) of row (b, c) into LDS, zeros outside [0, T).
-__device__ inline void stage_glu(const float *__restrict__ ua, const float *__restrict__ ug, float *sg, int first, int span, int T) {
+// g of the positions [first, first + span) of row (b, c) into LDS, zeros outside [0, T).  HIST: before 0 the row's history
+// instead, hr[t] with hr the end of its K - 1 floats -- the g of the frame t < 0 of an earlier call.
+template <bool HIST>
+__device__ inline void stage_glu(const float *__restrict__ ua, const float *__restrict__ ug, const float *__restrict__ hr, float *sg,
+                                 int first, int span, int T) {
     for (int i = threadIdx.x; i < span; i += 256) {
         const int t = first + i;
-        sg[i] = (t >= 0 && t < T) ? ua[t] * sigmoidf(ug[t]) : 0.f;
+        if (HIST && t < 0) sg[i] = hr[t];
+        else sg[i] = (t >= 0 && t < T) ? ua[t] * sigmoidf(ug[t]) : 0.f;
     }
 }
 
 // Kernel 1.  One workgroup per (row, tile of kTile positions): g of the tile and its K - 1 halo goes to LDS, thread j takes the
 // positions j, j + 256, ... of the tile.  EVAL: the normalisation on the running statistics and the SiLU are applied and only y is
-// written.
-template <bool EVAL>
+// written.  CAUSAL: left = K - 1 instead of (K - 1) / 2, and the halo before 0 comes from hist (B, C, K - 1) where it is given.
+template <bool EVAL, bool CAUSAL>
 __global__ __launch_bounds__(256) void glu_dwconv_kernel(const float *__restrict__ u, const float *__restrict__ w,
                                                          const float *__restrict__ bias, const float *__restrict__ gamma,
                                                          const float *__restrict__ beta, const float *__restrict__ mean,
-                                                         const float *__restrict__ var, float eps, float *__restrict__ out, int C,
-                                                         int T, int K, int tiles) {
+                                                         const float *__restrict__ var, float eps, const float *__restrict__ hist,
+                                                         float *__restrict__ out, int C, int T, int K, int tiles) {
     __shared__ float sg[kTile + kMaxK - 1];
     const int64_t row = int64_t(blockIdx.x) / tiles;
     const int t0 = int(int64_t(blockIdx.x) - row * tiles) * kTile;
     const int b = int(row / C), c = int(row - int64_t(b) * C);
-    const int n = T - t0 < kTile ? T - t0 : kTile, left = (K - 1) / 2;
+    const int n = T - t0 < kTile ? T - t0 : kTile, left = CAUSAL ? K - 1 : (K - 1) / 2;
     const float *ua = u + (int64_t(b) * 2 * C + c) * T, *ug = ua + int64_t(C) * T;
-    stage_glu(ua, ug, sg, t0 - left, n + K - 1, T);
+    if (CAUSAL && hist) stage_glu<true>(ua, ug, hist + (row + 1) * (K - 1), sg, t0 - left, n + K - 1, T);
+    else stage_glu<false>(ua, ug, nullptr, sg, t0 - left, n + K - 1, T);
     __syncthreads();
     const float *wc = w + int64_t(c) * K;
     const float bc = bias[c];
@@ -287,7 +296,7 @@ __global__ __launch_bounds__(64) void bn_silu_bwd_finish_kernel(const float *__r
 //   dg[t] = sum_k w[c, k] dz[t + left - k]   (fma chain in increasing k from 0)      du_a = dg s      du_gate = (dg a) (s (1 - s))
 // PARAMS: the tile's share of dw[c, k] = sum_t dz[t] g[t + k - left] for every k, and of dbias[c] = sum_t dz[t] (slot K): walker
 // sums in increasing t (fma), the halving tree per group of 64, the groups as (g0 + g1) + (g2 + g3).
-template <bool PARAMS>
+template <bool PARAMS, bool CAUSAL>
 __global__ __launch_bounds__(256) void glu_dwconv_bwd_kernel(const float *__restrict__ dz, const float *__restrict__ u,
                                                              const float *__restrict__ w, float *__restrict__ du,
                                                              float *__restrict__ partial, int C, int T, int K, int tiles) {
@@ -296,9 +305,9 @@ __global__ __launch_bounds__(256) void glu_dwconv_bwd_kernel(const float *__rest
     const int64_t row = int64_t(blockIdx.x) / tiles;
     const int t0 = int(int64_t(blockIdx.x) - row * tiles) * kTile;
     const int b = int(row / C), c = int(row - int64_t(b) * C);
-    const int n = T - t0 < kTile ? T - t0 : kTile, left = (K - 1) / 2, right = K - 1 - left;
+    const int n = T - t0 < kTile ? T - t0 : kTile, left = CAUSAL ? K - 1 : (K - 1) / 2, right = K - 1 - left;
     const float *ua = u + (int64_t(b) * 2 * C + c) * T, *ug = ua + int64_t(C) * T, *dzr = dz + row * T;
-    if (PARAMS) stage_glu(ua, ug, sg, t0 - left, n + K - 1, T);
+    if (PARAMS) stage_glu<false>(ua, ug, nullptr, sg, t0 - left, n + K - 1, T);
     for (int i = threadIdx.x; i < n + K - 1; i += 256) {
         const int t = t0 - right + i;
         sd[i] = (t >= 0 && t < T) ? dzr[t] : 0.f;
@@ -374,6 +383,87 @@ __global__ __launch_bounds__(256) void silu_kernel(const float *x, const float *
     for (int64_t e = 4 * n4 + i; e < n; e += stride) out[e] = one(x[e], BWD ? d[e] : 0.f);
 }
 
+// i / d for 0 <= i < 2^15 and a quotient below 2^9, inv = 1.f / float(d), 1 <= d <= 64: the product is within 2^9 2^-22 of
+// (i + 0.5) / d, which is at least 0.5 / 64 from an integer.  An integer division costs a latency-bound step a tenth of its time.
+__device__ inline int quot(int i, float inv) { return int((float(i) + 0.5f) * inv); }
+
+// Kernel 7, the streaming step: n <= kMaxStep new frames of every row, packed by output.  A workgroup owns R whole rows
+// row0 .. row0 + R - 1 (R n <= 256) and keeps per row, in LDS, the image [hist (K - 1) | g of the chunk (n)] at an odd stride and
+// the row's K taps at an odd stride: the three fills walk hist, u and w in address order, and with odd strides the 32 lanes of an
+// LDS access group fall on 32 banks at n == 1, where neighbouring lanes are neighbouring rows.  After the one barrier thread e
+// takes the output (row0 + e / n, e % n) -- the fma chain of kernel 1 on the same values, then the eval normalisation and SiLU --
+// and the image's last K - 1 floats go back to hist.  rows = B C < 2^31: row arithmetic is 32-bit.  Every read of hist is before the barrier, every write behind it, and no
+// other workgroup touches these rows.
+__global__ __launch_bounds__(256) void glu_dwconv_step_kernel(const float *__restrict__ u, const float *__restrict__ w,
+                                                              const float *__restrict__ bias, const float *__restrict__ gamma,
+                                                              const float *__restrict__ beta, const float *__restrict__ mean,
+                                                              const float *__restrict__ var, float eps, float *hist,
+                                                              float *__restrict__ out, int C, int n, int K, int R, int rows, float inv_n,
+                                                              float inv_h, float inv_k) {
+    extern __shared__ float step_lds[];
+    const int H = K - 1, stride = (H + n) | 1, wstride = K | 1;
+    float *img = step_lds, *sw = step_lds + R * stride;
+    const int row0 = int(blockIdx.x) * R;
+    const int nr = rows - row0 < R ? rows - row0 : R;
+    // this thread's output (R n <= 256: one each) and its channel's constants: their loads are in flight with the fills
+    const int e = threadIdx.x;
+    const bool mine = e < nr * n;
+    int r = 0, t = 0, c = 0;
+    float bc = 0.f;
+    Norm nm{};
+    if (mine) {
+        r = quot(e, inv_n);
+        t = e - r * n;
+        const unsigned row = unsigned(row0 + r), b = row / unsigned(C);
+        c = int(row - b * unsigned(C));
+        bc = bias[c];
+        nm = norm_of(gamma, beta, mean, var, eps, c, 0);
+        const float *ua = u + (int64_t(b) * 2 * C + c) * n;
+        img[r * stride + H + t] = ua[t] * sigmoidf(ua[int64_t(C) * n + t]);
+    }
+    // the walks of the history start at the third wavefront and the one of the taps at the second: where a workgroup holds few rows
+    // (a small batch) the outputs, the taps and the history are the work of different wavefronts, side by side
+    for (int i = (threadIdx.x + 128) & 255; i < nr * H; i += 256) {
+        const int ri = quot(i, inv_h);
+        img[ri * stride + (i - ri * H)] = hist[int64_t(row0) * H + i];
+    }
+    for (int i = (threadIdx.x + 192) & 255; i < nr * K; i += 256) {
+        const int ri = quot(i, inv_k);
+        sw[ri * wstride + (i - ri * K)] = w[int64_t(unsigned(row0 + ri) % unsigned(C)) * K + (i - ri * K)];
+    }
+    __syncthreads();
+    for (int i = (threadIdx.x + 128) & 255; i < nr * H; i += 256) {
+        const int ri = quot(i, inv_h);
+        hist[int64_t(row0) * H + i] = img[ri * stride + n + (i - ri * H)];
+    }
+    if (mine) {
+        const float *wc = sw + r * wstride, *sg = img + r * stride + t;
+        float z = bc;
+        for (int k = 0; k < K; ++k) z = fmaf(wc[k], sg[k], z);
+        out[int64_t(row0) * n + e] = siluf(act_of(z, nm));
+    }
+}
+
+// Kernel 8.  hist <- the last K - 1 values of [hist | g of a chunk of T frames], K >= 2.  A workgroup owns R whole rows,
+// R (K - 1) <= 256: thread e holds element (row0 + e / (K - 1), j = e % (K - 1)) of the new history in a register -- g[j + T - (K - 1)]
+// from u, or where that frame lies before the chunk the old hist[j + T] -- then the barrier, then the write.
+__global__ __launch_bounds__(256) void glu_hist_update_kernel(const float *__restrict__ u, float *hist, int C, int T, int K, int R,
+                                                              int rows, float inv_h) {
+    const int H = K - 1, e = threadIdx.x;
+    const int row0 = int(blockIdx.x) * R;
+    const int nr = rows - row0 < R ? rows - row0 : R;
+    const bool mine = e < nr * H;
+    float v = 0.f;
+    if (mine) {
+        const int r = quot(e, inv_h), t = e - r * H + T - H;
+        const unsigned row = unsigned(row0 + r), b = row / unsigned(C);
+        const float *ua = u + (int64_t(b) * 2 * C + (row - b * unsigned(C))) * T;
+        v = t >= 0 ? ua[t] * sigmoidf(ua[int64_t(C) * T + t]) : hist[int64_t(row0) * H + e + T];
+    }
+    __syncthreads();
+    if (mine) hist[int64_t(row0) * H + e] = v;
+}
+
 inline bool all_aligned16(std::initializer_list<const void *> ps) {
     for (const void *p : ps)
         if (reinterpret_cast<uintptr_t>(p) & 15) return false;
@@ -411,24 +501,39 @@ inline bool shape_ok(int32_t B, int32_t C, int32_t T, int32_t K, Shape &s) {
 
 }  // namespace
 
+namespace {
+
+// The "same" and the causal forward: the one tile kernel with its left halo width and, causal only, the history.
+int glu_dwconv_forward(const char *op, const float *u, const float *w, const float *bias, const float *gamma, const float *beta,
+                       const float *mean, const float *var, float eps, const float *hist, float *out, int32_t B, int32_t C, int32_t T,
+                       int32_t K, bool causal, void *stream) {
+    Shape s;
+    if (const int rc = shape_of(op, B, C, T, K, s); rc != AGX_OK) return rc;
+    if (!u || !w || !bias || !out) return fail(AGX_ERR_NULL_POINTER, "%s: NULL pointer", op);
+    const bool eval = gamma || beta || mean || var;
+    if (eval && !(gamma && beta && mean && var))
+        return fail(AGX_ERR_NULL_POINTER, "%s: gamma, beta, mean and var come together or not at all", op);
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    const dim3 grid(unsigned(s.rows * s.tiles));
+    auto kernel = eval ? (causal ? glu_dwconv_kernel<true, true> : glu_dwconv_kernel<true, false>)
+                       : (causal ? glu_dwconv_kernel<false, true> : glu_dwconv_kernel<false, false>);
+    hipLaunchKernelGGL(kernel, grid, dim3(256), 0, st, u, w, bias, gamma, beta, mean, var, eps, hist, out, C, T, K, int(s.tiles));
+    return check_launch(op);
+}
+
+}  // namespace
+
 int agx_glu_dwconv_forward(const float *u, const float *w, const float *bias, const float *gamma, const float *beta,
                            const float *mean, const float *var, float eps, float *out, int32_t B, int32_t C, int32_t T, int32_t K,
                            void *stream) {
-    Shape s;
-    if (const int rc = shape_of("glu_dwconv_forward", B, C, T, K, s); rc != AGX_OK) return rc;
-    if (!u || !w || !bias || !out) return fail(AGX_ERR_NULL_POINTER, "glu_dwconv_forward: NULL pointer");
-    const bool eval = gamma || beta || mean || var;
-    if (eval && !(gamma && beta && mean && var))
-        return fail(AGX_ERR_NULL_POINTER, "glu_dwconv_forward: gamma, beta, mean and var come together or not at all");
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    const dim3 grid(unsigned(s.rows * s.tiles));
-    if (eval)
-        hipLaunchKernelGGL(glu_dwconv_kernel<true>, grid, dim3(256), 0, st, u, w, bias, gamma, beta, mean, var, eps, out, C, T, K,
-                           int(s.tiles));
-    else
-        hipLaunchKernelGGL(glu_dwconv_kernel<false>, grid, dim3(256), 0, st, u, w, bias, gamma, beta, mean, var, eps, out, C, T, K,
-                           int(s.tiles));
-    return check_launch("agx_glu_dwconv_forward");
+    return glu_dwconv_forward("agx_glu_dwconv_forward", u, w, bias, gamma, beta, mean, var, eps, nullptr, out, B, C, T, K, false, stream);
+}
+
+int agx_glu_dwconv_causal_forward(const float *u, const float *w, const float *bias, const float *gamma, const float *beta,
+                                  const float *mean, const float *var, float eps, const float *hist, float *out, int32_t B, int32_t C,
+                                  int32_t T, int32_t K, void *stream) {
+    return glu_dwconv_forward("agx_glu_dwconv_causal_forward", u, w, bias, gamma, beta, mean, var, eps, hist, out, B, C, T, K, true,
+                              stream);
 }
 
 size_t agx_bn_stats_workspace_bytes(int32_t B, int32_t C, int32_t T) {
@@ -508,30 +613,90 @@ size_t agx_glu_dwconv_backward_workspace_bytes(int32_t B, int32_t C, int32_t T, 
     return size_t(s.rows * s.tiles * (K + 1)) * sizeof(float);
 }
 
-int agx_glu_dwconv_backward(const float *dz, const float *u, const float *w, float *du, float *dw, float *dbias, void *workspace,
-                            size_t workspace_bytes, int32_t B, int32_t C, int32_t T, int32_t K, void *stream) {
+namespace {
+
+int glu_dwconv_backward(const char *op, const float *dz, const float *u, const float *w, float *du, float *dw, float *dbias,
+                        void *workspace, size_t workspace_bytes, int32_t B, int32_t C, int32_t T, int32_t K, bool causal, void *stream) {
     Shape s;
-    if (const int rc = shape_of("glu_dwconv_backward", B, C, T, K, s); rc != AGX_OK) return rc;
+    if (const int rc = shape_of(op, B, C, T, K, s); rc != AGX_OK) return rc;
     if (!du && !dw && !dbias) return AGX_OK;
-    if ((dw == nullptr) != (dbias == nullptr))
-        return fail(AGX_ERR_NULL_POINTER, "glu_dwconv_backward: dw and dbias come together or not at all");
-    if (!dz || !u || !w) return fail(AGX_ERR_NULL_POINTER, "glu_dwconv_backward: NULL pointer");
+    if ((dw == nullptr) != (dbias == nullptr)) return fail(AGX_ERR_NULL_POINTER, "%s: dw and dbias come together or not at all", op);
+    if (!dz || !u || !w) return fail(AGX_ERR_NULL_POINTER, "%s: NULL pointer", op);
     hipStream_t st = static_cast<hipStream_t>(stream);
     const dim3 grid(unsigned(s.rows * s.tiles));
     if (!dw) {
-        hipLaunchKernelGGL(glu_dwconv_bwd_kernel<false>, grid, dim3(256), 0, st, dz, u, w, du, static_cast<float *>(nullptr), C, T, K,
-                           int(s.tiles));
-        return check_launch("agx_glu_dwconv_backward");
+        auto kernel = causal ? glu_dwconv_bwd_kernel<false, true> : glu_dwconv_bwd_kernel<false, false>;
+        hipLaunchKernelGGL(kernel, grid, dim3(256), 0, st, dz, u, w, du, static_cast<float *>(nullptr), C, T, K, int(s.tiles));
+        return check_launch(op);
     }
     const size_t need = agx_glu_dwconv_backward_workspace_bytes(B, C, T, K);
-    if (!workspace || workspace_bytes < need)
-        return fail(AGX_ERR_WORKSPACE, "glu_dwconv_backward: workspace of %zu bytes, %zu needed", workspace_bytes, need);
+    if (!workspace || workspace_bytes < need) return fail(AGX_ERR_WORKSPACE, "%s: workspace of %zu bytes, %zu needed", op, workspace_bytes, need);
     float *partial = static_cast<float *>(workspace);
-    hipLaunchKernelGGL(glu_dwconv_bwd_kernel<true>, grid, dim3(256), 0, st, dz, u, w, du, partial, C, T, K, int(s.tiles));
-    if (const int rc = check_launch("agx_glu_dwconv_backward"); rc != AGX_OK) return rc;
+    auto kernel = causal ? glu_dwconv_bwd_kernel<true, true> : glu_dwconv_bwd_kernel<true, false>;
+    hipLaunchKernelGGL(kernel, grid, dim3(256), 0, st, dz, u, w, du, partial, C, T, K, int(s.tiles));
+    if (const int rc = check_launch(op); rc != AGX_OK) return rc;
     hipLaunchKernelGGL(glu_dwconv_bwd_finish_kernel, dim3(unsigned(C)), dim3(64), 0, st, static_cast<const float *>(partial), dw, dbias,
                        C, K, int(s.tiles), int64_t(B) * s.tiles);
-    return check_launch("agx_glu_dwconv_backward");
+    return check_launch(op);
+}
+
+// Rows a workgroup of the step kernel owns: as many as fill its 256 threads with outputs, within kStepFloats of LDS -- and no
+// more than leave kStepGrid workgroups: a step is bound by the latency of one workgroup's fills, not by bytes, so a small batch
+// is spread over the compute units before it is packed.  A function of the shape alone.
+constexpr int kMaxStep = AGX_CONFORMER_MAX_STEP;
+constexpr int kStepFloats = 12288;
+constexpr int kStepGrid = 1024;
+inline int step_rows(int64_t rows, int n, int K) {
+    const int per_row = ((K - 1 + n) | 1) + (K | 1);
+    int64_t r = 256 / n;                                     // >= 4
+    if (r > kStepFloats / per_row) r = kStepFloats / per_row;       // >= 64: per_row <= 127 + 65
+    if (r > ceil_div64(rows, kStepGrid)) r = ceil_div64(rows, kStepGrid);
+    return int(r);
+}
+
+}  // namespace
+
+int agx_glu_dwconv_backward(const float *dz, const float *u, const float *w, float *du, float *dw, float *dbias, void *workspace,
+                            size_t workspace_bytes, int32_t B, int32_t C, int32_t T, int32_t K, void *stream) {
+    return glu_dwconv_backward("agx_glu_dwconv_backward", dz, u, w, du, dw, dbias, workspace, workspace_bytes, B, C, T, K, false, stream);
+}
+
+size_t agx_glu_dwconv_causal_backward_workspace_bytes(int32_t B, int32_t C, int32_t T, int32_t K) {
+    return agx_glu_dwconv_backward_workspace_bytes(B, C, T, K);
+}
+
+int agx_glu_dwconv_causal_backward(const float *dz, const float *u, const float *w, float *du, float *dw, float *dbias, void *workspace,
+                                   size_t workspace_bytes, int32_t B, int32_t C, int32_t T, int32_t K, void *stream) {
+    return glu_dwconv_backward("agx_glu_dwconv_causal_backward", dz, u, w, du, dw, dbias, workspace, workspace_bytes, B, C, T, K, true,
+                               stream);
+}
+
+int agx_glu_dwconv_step(const float *u, const float *w, const float *bias, const float *gamma, const float *beta, const float *mean,
+                        const float *var, float eps, float *hist, float *out, int32_t B, int32_t C, int32_t n, int32_t K, void *stream) {
+    if (B <= 0 || C <= 0) return fail(AGX_ERR_BAD_SHAPE, "glu_dwconv_step: (B, C) = (%d, %d)", B, C);
+    if (n < 1 || n > kMaxStep) return fail(AGX_ERR_BAD_SHAPE, "glu_dwconv_step: n = %d is outside [1, %d]", n, kMaxStep);
+    if (K < 1 || K > kMaxK) return fail(AGX_ERR_BAD_SHAPE, "glu_dwconv_step: K = %d is outside [1, %d]", K, kMaxK);
+    const int64_t rows = int64_t(B) * C;
+    if (rows > kMaxGrid) return fail(AGX_ERR_BAD_SHAPE, "glu_dwconv_step: (%d, %d, %d) exceeds the grid", B, C, n);
+    const int R = step_rows(rows, n, K);
+    if (!u || !w || !bias || !gamma || !beta || !mean || !var || !out || (K > 1 && !hist))
+        return fail(AGX_ERR_NULL_POINTER, "glu_dwconv_step: NULL pointer (the step is the eval form: every statistic, and hist for K > 1)");
+    const size_t lds = size_t(R) * (((K - 1 + n) | 1) + (K | 1)) * sizeof(float);
+    hipLaunchKernelGGL(glu_dwconv_step_kernel, dim3(unsigned(ceil_div64(rows, R))), dim3(256), lds, static_cast<hipStream_t>(stream), u,
+                       w, bias, gamma, beta, mean, var, eps, hist, out, C, n, K, R, int(rows), 1.f / float(n), K > 1 ? 1.f / float(K - 1) : 0.f,
+                       1.f / float(K));
+    return check_launch("agx_glu_dwconv_step");
+}
+
+int agx_glu_hist_update(const float *u, float *hist, int32_t B, int32_t C, int32_t T, int32_t K, void *stream) {
+    Shape s;
+    if (const int rc = shape_of("glu_hist_update", B, C, T, K, s); rc != AGX_OK) return rc;
+    if (K == 1) return AGX_OK;
+    if (!u || !hist) return fail(AGX_ERR_NULL_POINTER, "glu_hist_update: NULL pointer");
+    const int R = 256 / (K - 1);                              // >= 4
+    hipLaunchKernelGGL(glu_hist_update_kernel, dim3(unsigned(ceil_div64(s.rows, R))), dim3(256), 0, static_cast<hipStream_t>(stream), u,
+                       hist, C, T, K, R, int(s.rows), 1.f / float(K - 1));
+    return check_launch("agx_glu_hist_update");
 }
 
 int agx_silu(const float *x, float *out, int64_t n, void *stream) {

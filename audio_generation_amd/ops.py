@@ -1935,6 +1935,97 @@ def glu_dwconv_backward(dz: Tensor, u: Tensor, w: Tensor, want_du: bool = True, 
     return du, dw, dbias
 
 
+CONFORMER_MAX_STEP = _lib.CONFORMER_MAX_STEP
+
+
+def _glu_hist(op: str, hist: Optional[Tensor], b: int, c: int, k: int) -> None:
+    """A conv state is a contiguous float32 (B, C, K - 1) tensor: it is written in place, so it is never copied."""
+    if hist is not None and (tuple(hist.shape) != (b, c, k - 1) or hist.dtype != torch.float32 or not hist.is_contiguous()):
+        raise AgxError(f"{op}: hist must be a contiguous float32 {(b, c, k - 1)} tensor (B, C, K - 1), got {tuple(hist.shape)} {hist.dtype}")
+
+
+def glu_dwconv_causal(u: Tensor, w: Tensor, bias: Tensor, bn: Optional[tuple] = None, eps: float = 1e-5,
+                      hist: Optional[Tensor] = None) -> Tensor:
+    """``glu_dwconv`` with the causal conv: an output sees its own frame and the K - 1 before it.  ``hist`` (B, C, K - 1), oldest
+    frame first: the post-GLU values of the K - 1 frames before ``u`` (None: zeros, the start of a sequence); read, not written."""
+    lib = _lib.load()
+    _need_gpu(u, w, bias, hist, *(bn or ()))
+    b, c, t, k = _glu_shape("glu_dwconv_causal", u, w)
+    w, (bias,) = _f32c(w), _bn_vectors("glu_dwconv_causal", c, bias)
+    bn = (None,) * 4 if bn is None else _bn_vectors("glu_dwconv_causal", c, *bn)
+    _glu_hist("glu_dwconv_causal", hist, b, c, k)
+    out = torch.empty((b, c, t), dtype=torch.float32, device=u.device)
+    tok = _observer.begin("other", ("glu_dwconv_causal", 12 * out.numel())) if _observer is not None else None
+    _lib.check(lib.agx_glu_dwconv_causal_forward(_ptr(u), _ptr(w), _ptr(bias), *(_ptr(v) for v in bn), float(eps), _ptr(hist), _ptr(out),
+                                                 b, c, t, k, _stream()), "agx_glu_dwconv_causal_forward")
+    if tok is not None:
+        _observer.end(tok)
+    return out
+
+
+def glu_dwconv_causal_backward(dz: Tensor, u: Tensor, w: Tensor, want_du: bool = True, want_params: bool = True):
+    """(du (B, 2 C, T) or None, dw of w's shape or None, dbias (C) or None) of ``glu_dwconv_causal`` without ``bn`` and without
+    ``hist``: there is no backward through a cached call."""
+    lib = _lib.load()
+    _need_gpu(dz, u, w)
+    b, c, t, k = _glu_shape("glu_dwconv_causal_backward", u, w)
+    if tuple(dz.shape) != (b, c, t):
+        raise AgxError(f"glu_dwconv_causal_backward: dz is {tuple(dz.shape)}, expected {(b, c, t)}")
+    dz, w = _f32c(dz), _f32c(w)
+    du = torch.empty_like(u) if want_du else None
+    dw = dbias = ws = None
+    nbytes = 0
+    if want_params:
+        dw, dbias = torch.empty_like(w), torch.empty(c, dtype=torch.float32, device=u.device)
+        nbytes = int(lib.agx_glu_dwconv_causal_backward_workspace_bytes(b, c, t, k))
+        ws = _workspace(nbytes, u.device, "agx_glu_dwconv_causal_backward_workspace_bytes")
+    _lib.check(lib.agx_glu_dwconv_causal_backward(_ptr(dz), _ptr(u), _ptr(w), _ptr(du), _ptr(dw), _ptr(dbias), _ptr(ws), nbytes, b, c, t,
+                                                  k, _stream()), "agx_glu_dwconv_causal_backward")
+    return du, dw, dbias
+
+
+def glu_dwconv_step(u: Tensor, w: Tensor, bias: Tensor, bn: tuple, hist: Optional[Tensor], eps: float = 1e-5) -> Tensor:
+    """The streaming step, one launch: ``y`` (B, C, n) of the ``n <= CONFORMER_MAX_STEP`` new frames ``u`` (B, 2 C, n) -- the eval
+    form, ``bn`` = (gamma, beta, running_mean, running_var) -- and ``hist`` (B, C, K - 1) rewritten in place with the last K - 1
+    post-GLU values of [hist | chunk].  ``hist`` may be None only for K == 1."""
+    lib = _lib.load()
+    _need_gpu(u, w, bias, hist, *(bn or ()))
+    b, c, n, k = _glu_shape("glu_dwconv_step", u, w)
+    if not 1 <= n <= CONFORMER_MAX_STEP:
+        raise AgxError(f"glu_dwconv_step: n = {n} frames is outside [1, {CONFORMER_MAX_STEP}] (longer chunks: glu_dwconv_causal(hist=) "
+                       "+ glu_hist_update)")
+    if bn is None or len(bn) != 4 or any(v is None for v in bn):
+        raise AgxError("glu_dwconv_step: the step is the eval form: bn = (gamma, beta, running_mean, running_var)")
+    if hist is None and k > 1:
+        raise AgxError(f"glu_dwconv_step: kernel_size = {k} needs hist (B, C, K - 1)")
+    w, (bias,) = _f32c(w), _bn_vectors("glu_dwconv_step", c, bias)
+    bn = _bn_vectors("glu_dwconv_step", c, *bn)
+    _glu_hist("glu_dwconv_step", hist, b, c, k)
+    out = torch.empty((b, c, n), dtype=torch.float32, device=u.device)
+    tok = _observer.begin("other", ("glu_dwconv_step", 12 * out.numel())) if _observer is not None else None
+    _lib.check(lib.agx_glu_dwconv_step(_ptr(u), _ptr(w), _ptr(bias), *(_ptr(v) for v in bn), float(eps), _ptr(hist), _ptr(out), b, c, n, k,
+                                       _stream()), "agx_glu_dwconv_step")
+    if tok is not None:
+        _observer.end(tok)
+    return out
+
+
+def glu_hist_update(u: Tensor, hist: Tensor) -> Tensor:
+    """``hist`` (B, C, K - 1) <- the last K - 1 post-GLU values of [hist | u (B, 2 C, T)], in place, one launch, any T: what
+    ``glu_dwconv_step`` does to its state, for cached calls longer than a step.  K == 1: nothing to do.  Returns ``hist``."""
+    lib = _lib.load()
+    _need_gpu(u, hist)
+    if u.dim() != 3 or u.shape[1] % 2 or u.dtype != torch.float32 or not u.is_contiguous():
+        raise AgxError(f"glu_hist_update: u must be a contiguous float32 (B, 2 C, T) tensor, got {tuple(u.shape)} {u.dtype}")
+    b, c, t = u.shape[0], u.shape[1] // 2, u.shape[2]
+    if hist.dim() != 3 or not 1 <= hist.shape[-1] + 1 <= CONFORMER_MAX_K:
+        raise AgxError(f"glu_hist_update: hist is {tuple(hist.shape)}, expected (B, C, K - 1) with 1 <= K <= {CONFORMER_MAX_K}")
+    k = hist.shape[-1] + 1
+    _glu_hist("glu_hist_update", hist, b, c, k)
+    _lib.check(lib.agx_glu_hist_update(_ptr(u), _ptr(hist), b, c, t, k, _stream()), "agx_glu_hist_update")
+    return hist
+
+
 def bn_stats(z: Tensor, running_mean: Optional[Tensor] = None, running_var: Optional[Tensor] = None,
              num_batches_tracked: Optional[Tensor] = None, momentum: float = 0.1):
     """(mean, var): the per-channel mean and biased variance of z (B, C, T) over (B, T), by a merge of per-segment (n, mean,

@@ -1216,20 +1216,30 @@ class ConformerConvBlock(nn.Module):
     Eval mode is four launches: LN, pointwise-in, the fused GLU + depthwise conv + BatchNorm (running statistics) + SiLU kernel
     of ``csrc/conformer.hip``, pointwise-out (+ residual).  Training mode: LN, pointwise-in, GLU + depthwise conv, batch
     statistics (two launches; the running statistics and ``num_batches_tracked`` are updated by the second), normalise + SiLU,
-    pointwise-out, and with ``dropout > 0`` ``dropout_add``.  The ``nn`` children only hold parameters and buffers."""
+    pointwise-out, and with ``dropout > 0`` ``dropout_add``.  The ``nn`` children only hold parameters and buffers.
 
-    def __init__(self, in_channels, kernel_size=17, dropout=0.1, activation=nn.SiLU):
+    ``causal=True`` (build-defined, keyword-only): ``net[3]`` is the same depthwise ``nn.Conv1d`` without padding, the input is
+    padded by K - 1 frames on the left -- an output sees its own frame and the K - 1 before it -- and every launch count above
+    holds with the causal ops of ``csrc/conformer.hip`` in place of the "same" ones.  The ``state_dict()`` keys and shapes are
+    those of the non-causal block.  A causal block in eval mode also runs incrementally: ``new_conv_state(batch)`` is the
+    (B, C, K - 1) history of post-GLU values, and ``run_bct(x, conv_state=state)`` takes the next ``n`` frames -- up to
+    ``ops.CONFORMER_MAX_STEP`` in the one launch of ``ops.glu_dwconv_step`` where the fused conv launch was, a longer chunk in
+    ``ops.glu_dwconv_causal(hist=)`` + ``ops.glu_hist_update`` -- and rewrites the state in place.  Chunked calls are bit for bit
+    the single call."""
+
+    def __init__(self, in_channels, kernel_size=17, dropout=0.1, activation=nn.SiLU, *, causal=False):
         super().__init__()
         if activation is not nn.SiLU:
             raise NotImplementedError("only SiLU is fused behind the BatchNorm (csrc/conformer.hip)")
         if int(kernel_size) != kernel_size or not 1 <= kernel_size <= ops.CONFORMER_MAX_K:
             raise ValueError(f"kernel_size = {kernel_size}: the depthwise kernel takes 1 <= kernel_size <= {ops.CONFORMER_MAX_K}")
         self.in_channels = self.out_channels = in_channels
-        self.kernel_size = int(kernel_size)
+        self.kernel_size, self.causal = int(kernel_size), bool(causal)
         self.net = nn.Sequential(
             nn.LayerNorm(in_channels),
             nn.Conv1d(in_channels, 2 * in_channels, kernel_size=1),
             nn.GLU(dim=-2),
+            nn.Conv1d(in_channels, in_channels, kernel_size=self.kernel_size, groups=in_channels) if self.causal else
             nn.Conv1d(in_channels, in_channels, kernel_size=self.kernel_size, padding="same", groups=in_channels),
             nn.BatchNorm1d(in_channels),
             activation(),
@@ -1241,12 +1251,42 @@ class ConformerConvBlock(nn.Module):
     def _p_out(self) -> float:
         return _active_p(self.net[7]) if isinstance(self.net[7], nn.Dropout) else 0.0
 
+    def new_conv_state(self, batch: int) -> Tensor:
+        """The conv state of ``batch`` streams at their start: zeros (B, C, K - 1) on the parameters' device -- the post-GLU values
+        of the K - 1 frames before the next call, oldest first.  ``state[rows].zero_()`` hands rows to new streams."""
+        if not self.causal:
+            raise AgxError("new_conv_state: a conv state needs a causal block (causal=True): the \"same\" conv looks ahead")
+        if batch < 1:
+            raise AgxError(f"new_conv_state: batch = {batch}")
+        return torch.zeros((batch, self.in_channels, self.kernel_size - 1), dtype=torch.float32, device=self.net[3].weight.device)
+
+    def _check_conv_state(self, x: Tensor, keep: Optional[dict], conv_state: Tensor) -> None:
+        """The refusals of a call on a conv state, before any op."""
+        if not self.causal:
+            raise AgxError("a conv state needs a causal block (causal=True): the \"same\" conv looks ahead")
+        if self.net[4].training:
+            raise AgxError("a conv state with BatchNorm in training mode: batch statistics of a chunk are not those of the sequence "
+                           "(a cached call runs in eval mode)")
+        if keep is not None or needs_grad(x, self):
+            raise AgxError("there is no backward through a cached call: run it under torch.no_grad()")
+        if x.dim() != 3 or x.shape[1] != self.in_channels:
+            raise AgxError(f"ConformerConvBlock: x is {tuple(x.shape)}, expected (B, {self.in_channels}, T)")
+        want = (x.shape[0], self.in_channels, self.kernel_size - 1)
+        if not isinstance(conv_state, Tensor) or tuple(conv_state.shape) != want or conv_state.dtype != torch.float32 \
+                or not conv_state.is_contiguous():
+            got = tuple(conv_state.shape) if isinstance(conv_state, Tensor) else type(conv_state).__name__
+            raise AgxError(f"conv state: expected a contiguous float32 {want} tensor (B, C, K - 1) for x {tuple(x.shape)}, got {got}")
+
     def run_bct(self, x: Tensor, residual: Optional[Tensor] = None, keep: Optional[dict] = None,
-                drop: Optional[tuple] = None) -> Tensor:
+                drop: Optional[tuple] = None, conv_state: Optional[Tensor] = None) -> Tensor:
         """(B, C, T) -> net(x) [+ residual: x itself].  ``keep`` marks a forward whose backward will run (``backward_bct``): z is then
-        written in eval mode too.  With autograd on and no ``keep`` the call goes through ``_ConformerNative``."""
+        written in eval mode too.  With autograd on and no ``keep`` the call goes through ``_ConformerNative``.  ``conv_state``
+        (``new_conv_state``; a causal block in eval mode, no gradient): ``x`` holds the next T frames of the streams the state
+        belongs to, and the state is rewritten in place."""
         if residual is not None and residual is not x:
             raise AgxError("ConformerConvBlock: the residual is the block's own input (x + net(x)), or None")
+        if conv_state is not None:
+            self._check_conv_state(x, keep, conv_state)
         if keep is None and needs_grad(x, self):
             return _ConformerNative.apply(self, residual is not None, drop, x, *list(self.parameters()))
         dw, bn = self.net[3], self.net[4]
@@ -1256,12 +1296,20 @@ class ConformerConvBlock(nn.Module):
             raise ValueError(f"Expected more than 1 value per channel when training, got input size {tuple(x.shape)}")
         p = self._p_out()
         gamma, beta = bn.weight.detach(), bn.bias.detach()
+        conv = ops.glu_dwconv_causal if self.causal else ops.glu_dwconv
         xn = _ln(self.net[0], x)
         u = self._in.forward(xn)
-        if not bn.training and keep is None:
-            y = ops.glu_dwconv(u, dw.weight.detach(), dw.bias.detach(), bn=(gamma, beta, bn.running_mean, bn.running_var), eps=bn.eps)
+        if conv_state is not None:
+            bn_eval = (gamma, beta, bn.running_mean, bn.running_var)
+            if x.shape[-1] <= ops.CONFORMER_MAX_STEP:
+                y = ops.glu_dwconv_step(u, dw.weight.detach(), dw.bias.detach(), bn_eval, conv_state, eps=bn.eps)
+            else:
+                y = ops.glu_dwconv_causal(u, dw.weight.detach(), dw.bias.detach(), bn=bn_eval, eps=bn.eps, hist=conv_state)
+                ops.glu_hist_update(u, conv_state)
+        elif not bn.training and keep is None:
+            y = conv(u, dw.weight.detach(), dw.bias.detach(), bn=(gamma, beta, bn.running_mean, bn.running_var), eps=bn.eps)
         else:
-            z = ops.glu_dwconv(u, dw.weight.detach(), dw.bias.detach())
+            z = conv(u, dw.weight.detach(), dw.bias.detach())
             if bn.training:
                 mean, var = ops.bn_stats(z, bn.running_mean, bn.running_var, bn.num_batches_tracked, bn.momentum)
             else:       # frozen statistics: a private copy, the backward must see what the forward saw
@@ -1289,7 +1337,7 @@ class ConformerConvBlock(nn.Module):
         dy, g_o = self._out.backward(kept["y"], g_out)
         dz, dgamma, dbeta = ops.bn_silu_backward(dy, kept["z"], bn.weight.detach(), bn.bias.detach(), kept["mean"], kept["var"],
                                                  bn.eps, training=c["training"], out=dy)
-        du, d_dw, d_db = ops.glu_dwconv_backward(dz, kept["u"], dw.weight.detach())
+        du, d_dw, d_db = (ops.glu_dwconv_causal_backward if self.causal else ops.glu_dwconv_backward)(dz, kept["u"], dw.weight.detach())
         dxn, g_i = self._in.backward(kept["cxn"], du)
         dx, dweight, dbias = _ln_bwd(self.net[0], kept["cx"], dxn, add=g if residual else None)
         return dx, [dweight, dbias, g_i[0].unsqueeze(-1), g_i[1], d_dw, d_db, dgamma, dbeta, g_o[0].unsqueeze(-1), g_o[1]]
@@ -1308,30 +1356,125 @@ class ConformerBlock(nn.Module):
     An eval-mode call is 4 + 4 + 4 + 4 + 1 = 17 launches: per feed-forward LN, FFN-in, SiLU, FFN-out (+res) -- the SiLU one more
     than a GELU feed-forward --, the attention's LN, QKV, attention, W_o (+res), the conv block's four and the final LN.  A
     training-mode call with ``dropout > 0`` draws one 64-bit seed (``last_dropout_seed``; ``torch.manual_seed`` reproduces it);
-    its seven sites take distinct stream ids (``CONFORMER_*``)."""
+    its seven sites take distinct stream ids (``CONFORMER_*``).
+
+    ``causal=True`` (build-defined, keyword-only; ``window=W`` with it): the attention is the causal (windowed) layer of
+    ``Attention`` and the conv block the causal one, so no output sees a later frame; parameters and ``state_dict()`` are
+    unchanged.  Causal attention has no dropout kernel: a causal block whose attention dropout is active (training mode,
+    ``dropout > 0``) is refused.  ``new_cache`` / ``new_stream_cache`` and ``run_bct(x, cache=)`` run the block incrementally, as
+    ``Transformer`` does: the attention on its key/value buffer or ring, the conv block on its (B, C, K - 1) state.  A cached
+    step is the 17 launches above plus the attention's write into its cache and, on a stream cache, ``ops.stream_advance``:
+    the conv state needs no position, so a step on a stream cache makes no host decision and can be captured once and
+    replayed (``GraphedForward``)."""
 
     def __init__(self, dim, hidden_dim_ratio=4, heads=8, dropout=0.1, ff_activation=nn.SiLU, conv_activation=nn.SiLU, *,
-                 kernel_size=17, context_x=32):
+                 kernel_size=17, context_x=32, causal=False, window=None):
         super().__init__()
         self.first_ff = FeedForward(dim, dim * hidden_dim_ratio, activation=ff_activation, dropout=dropout)
-        self.attention = Attention(dim, n_heads=heads, dim_head=dim // heads, dropout=dropout, context_x=context_x)
-        self.conv_block = ConformerConvBlock(dim, kernel_size=kernel_size, dropout=dropout, activation=conv_activation)
+        self.attention = Attention(dim, n_heads=heads, dim_head=dim // heads, dropout=dropout, context_x=context_x, causal=causal,
+                                   window=window)
+        self.conv_block = ConformerConvBlock(dim, kernel_size=kernel_size, dropout=dropout, activation=conv_activation, causal=causal)
         self.second_ff = FeedForward(dim, dim * hidden_dim_ratio, activation=ff_activation, dropout=dropout)
         self.layer_norm = nn.LayerNorm(dim)
         self.dim, self.context_x = dim, context_x
+        self.causal, self.window = bool(causal), self.attention.window
         self.last_dropout_seed = None
+
+    def _new_kv(self, what: str, batch: int, capacity: Optional[int]) -> tuple:
+        capacity = self.context_x if capacity is None else int(capacity)
+        if batch < 1 or capacity < 1:
+            raise AgxError(f"{what}: batch = {batch}, capacity = {capacity}")
+        if self.window is not None and capacity < self.window:
+            raise AgxError(f"{what}: a ring of capacity = {capacity} cannot hold a window of {self.window} frames")
+        device = next(self.parameters()).device
+        return torch.empty((batch, 2 * self.attention.inner_dim, capacity), dtype=torch.float32, device=device), capacity
+
+    def new_cache(self, batch: int, capacity: Optional[int] = None) -> "ConformerCache":
+        """An empty cache for ``batch`` sequences (``ConformerCache``): the attention's key/value buffer of ``capacity`` columns
+        (default ``context_x``; a ring of at least ``window`` columns on a windowed block) as ``Transformer.new_cache`` makes it,
+        and the conv state at the start of a stream.  Needs a causal block."""
+        if not self.causal:
+            raise AgxError("new_cache: a cache needs a causal ConformerBlock (causal=True)")
+        kv, capacity = self._new_kv("new_cache", batch, capacity)
+        return ConformerCache(kv, batch, capacity, self.window, self.conv_block.new_conv_state(batch))
+
+    def new_stream_cache(self, batch: int, capacity: Optional[int] = None) -> "ConformerStreamCache":
+        """An empty cache for ``batch`` live streams with the positions in device memory (``ConformerStreamCache``): the ring of
+        ``Transformer.new_stream_cache``, every position 0, and the conv state at the start of a stream.  Needs a windowed causal
+        block.  A call takes ``1 <= n <= cache.max_chunk`` frames."""
+        if not self.causal or self.window is None:
+            raise AgxError("new_stream_cache: device-held positions need a windowed causal ConformerBlock (causal=True, window=W)")
+        kv, capacity = self._new_kv("new_stream_cache", batch, capacity)
+        pos = torch.zeros(batch, dtype=torch.int64, device=kv.device)
+        return ConformerStreamCache(kv, pos, capacity, self.window, min(capacity - self.window + 1, self.context_x),
+                                    self.conv_block.new_conv_state(batch))
+
+    def _check_cache(self, x: Tensor, cache) -> None:
+        """The refusals of a cached call, before any op; on a stream cache none of them reads a position."""
+        on_device = isinstance(cache, ConformerStreamCache)
+        if not isinstance(cache, (ConformerCache, ConformerStreamCache)):
+            raise AgxError(f"cache= takes a ConformerCache or a ConformerStreamCache (new_cache / new_stream_cache), got {type(cache).__name__}")
+        if not self.causal or (on_device and self.window is None):
+            raise AgxError("a stream cache needs a windowed causal ConformerBlock (causal=True, window=W)" if on_device else
+                           "a cache needs a causal ConformerBlock (causal=True)")
+        if needs_grad(x, self):
+            raise AgxError("there is no backward through a cached call: run it under torch.no_grad()")
+        if self._dropout_active():
+            raise AgxError("a cached call with an active dropout site (training mode, dropout > 0) has no kernel")
+        if self.conv_block.net[4].training:
+            raise AgxError("a cached call with BatchNorm in training mode: batch statistics of a chunk are not those of the sequence "
+                           "(a cached call runs in eval mode)")
+        if self.attention.attention_dtype != "fp32":
+            raise AgxError(f"causal attention runs in fp32: attention_dtype = {self.attention.attention_dtype!r} has no kernel")
+        if x.dim() != 3 or x.shape[0] != cache.batch or x.shape[1] != self.dim:
+            raise AgxError(f"cached call: x is {tuple(x.shape)}, the cache was made for batch {cache.batch} of a block of dim {self.dim}")
+        if tuple(cache.kv.shape) != (cache.batch, 2 * self.attention.inner_dim, cache.capacity):
+            raise AgxError(f"the cache's key/value buffer is {tuple(cache.kv.shape)}, this block needs "
+                           f"{(cache.batch, 2 * self.attention.inner_dim, cache.capacity)}")
+        if cache.window != self.window:
+            raise AgxError(f"the cache was made for window {cache.window}, this block has window {self.window}")
+        want = (cache.batch, self.dim, self.conv_block.kernel_size - 1)
+        if tuple(cache.conv_state.shape) != want:
+            raise AgxError(f"the cache's conv state is {tuple(cache.conv_state.shape)}, this block needs {want} (B, C, K - 1)")
+        n = x.shape[-1]
+        if on_device:
+            if n < 1 or n > cache.max_chunk:
+                raise AgxError(f"stream cache: a call takes 1 <= n <= max_chunk = {cache.max_chunk} frames (min(capacity {cache.capacity} "
+                               f"- window {self.window} + 1, context_x {self.context_x}): the worst case over every position), got {n}")
+        elif self.window is not None:       # a ring: the new frames must not overwrite what their first query still sees
+            behind = min(self.window - 1, cache.length)
+            if n < 1 or n + behind > cache.capacity:
+                raise AgxError(f"cached call: {n} new frames + the {behind} cached frames their window reaches exceed the ring's "
+                               f"capacity {cache.capacity}")
+        elif n < 1 or cache.length + n > min(cache.capacity, self.context_x):
+            raise AgxError(f"cached call: {cache.length} cached + {n} new frames exceed min(capacity {cache.capacity}, context_x "
+                           f"{self.context_x}) = {min(cache.capacity, self.context_x)}")
 
     def _dropout_active(self) -> bool:
         sites = [self.attention.dropout, self.conv_block.net[7]] + [f.net[i] for f in (self.first_ff, self.second_ff) for i in (3, 5)]
         return any(isinstance(m, nn.Dropout) and m.training and m.p > 0 for m in sites)
 
-    def _hip_bct(self, x: Tensor, keep: Optional[dict] = None) -> Tensor:
+    def _hip_bct(self, x: Tensor, keep: Optional[dict] = None, cache=None) -> Tensor:
         """The one forward walk.  ``keep``: the training forward -- the dict receives one dict of named intermediates per
-        sub-block."""
+        sub-block.  ``cache`` (checked by ``_check_cache``): the attention runs on the cache's key/value buffer, the conv block on
+        its state, and the cache advances by the call's frames."""
         if x.dim() != 3 or x.shape[1] != self.dim:
             raise AgxError(f"ConformerBlock: x is {tuple(x.shape)}, expected (B, {self.dim}, T)")
         if x.shape[-1] > self.context_x:
             raise AgxError(f"sequence length {x.shape[-1]} exceeds the ALiBi context {self.context_x}")
+        if self.causal and _active_p(self.attention.dropout) > 0:
+            raise AgxError("a causal ConformerBlock with attention dropout > 0 in training mode has no kernel (eval mode runs)")
+        if cache is not None:
+            on_device = isinstance(cache, ConformerStreamCache)
+            x = self.first_ff.run_bct(x, x, None, None, scale=0.5)
+            x = self.attention.run_bct(x, x, None, None, None, kv_cache=(cache.kv, cache.pos if on_device else cache.length))
+            x = self.conv_block.run_bct(x, x, None, None, conv_state=cache.conv_state)
+            x = self.second_ff.run_bct(x, x, None, None, scale=0.5)
+            if on_device:
+                ops.stream_advance(cache.pos, x.shape[-1])
+            else:
+                cache.length += x.shape[-1]
+            return _ln(self.layer_norm, x)
         seed = None
         if self._dropout_active():
             seed = self.last_dropout_seed = ops.draw_dropout_seed()
@@ -1355,15 +1498,61 @@ class ConformerBlock(nn.Module):
         g, g_ff1 = self.first_ff.backward_bct(keep["ff1"], g, scale=0.5)
         return g, g_ff1 + g_attention + g_conv + g_ff2 + [dweight, dbias]
 
-    def run_bct(self, x: Tensor) -> Tensor:
+    def run_bct(self, x: Tensor, cache=None) -> Tensor:
         """Channel-major (B, dim, T) in and out, T <= context_x.  With autograd on, the backward runs on the HIP kernels too
-        (``_ConformerNative``)."""
+        (``_ConformerNative``).  ``cache`` (``new_cache`` / ``new_stream_cache``): ``x`` holds the next ``n`` frames of a causal
+        block's sequences; inference only, eval mode."""
+        if cache is not None:
+            self._check_cache(x, cache)
+            return self._hip_bct(x, None, cache)
         if needs_grad(x, self):
             return _ConformerNative.apply(self, False, None, x, *list(self.parameters()))
         return self._hip_bct(x)
 
-    def forward(self, x: Tensor) -> Tensor:
-        return self.run_bct(x.transpose(1, 2).contiguous()).transpose(1, 2).contiguous()
+    def forward(self, x: Tensor, cache=None) -> Tensor:
+        return self.run_bct(x.transpose(1, 2).contiguous(), cache).transpose(1, 2).contiguous()
+
+
+class ConformerCache:
+    """The cache of a causal ``ConformerBlock`` (``ConformerBlock.new_cache``): ``kv``, the attention's fp32
+    (B, 2*H*Dh, capacity) key/value buffer with one ``length`` as ``TransformerCache`` has them -- a ring on a windowed block --,
+    and ``conv_state``, the conv block's (B, C, K - 1) post-GLU history (zeros: the start of a stream)."""
+
+    def __init__(self, kv: Tensor, batch: int, capacity: int, window: Optional[int], conv_state: Tensor):
+        self.kv, self.batch, self.capacity, self.length, self.window, self.conv_state = kv, batch, capacity, 0, window, conv_state
+
+    def reset(self) -> None:
+        self.length = 0
+        self.conv_state.zero_()
+
+
+class ConformerStreamCache:
+    """The cache of a windowed causal ``ConformerBlock`` with the positions in device memory (``ConformerBlock.new_stream_cache``):
+    the ring ``kv`` and the int64 (B,) ``pos`` of ``TransformerStreamCache``, ``max_chunk`` as there, and ``conv_state``
+    (B, C, K - 1).  The conv state holds values, not positions: the step kernel shifts it by the call's frames whatever the
+    row's age, so a cached step makes no host decision and every row is a stream of its own."""
+
+    def __init__(self, kv: Tensor, pos: Tensor, capacity: int, window: int, max_chunk: int, conv_state: Tensor):
+        self.kv, self.pos, self.batch, self.capacity, self.window, self.max_chunk = kv, pos, pos.numel(), capacity, window, max_chunk
+        self.conv_state = conv_state
+
+    def reset(self, rows=None) -> None:
+        """Zero the positions and the conv-state rows of ``rows`` (default: every row) with device fills: those rows start a new
+        stream at their next call.  Call it between steps, outside any captured graph."""
+        if rows is None:
+            self.pos.zero_()
+            self.conv_state.zero_()
+            return
+        rows = [int(r) for r in rows]
+        if any(not 0 <= r < self.batch for r in rows):
+            raise AgxError(f"reset: rows {rows} are not rows of a cache of batch {self.batch}")
+        for r in rows:
+            self.pos[r:r + 1].zero_()
+            self.conv_state[r:r + 1].zero_()
+
+    def positions(self) -> list:
+        """The positions as a list of ints.  Synchronises: for tests and debugging, never called in the walk."""
+        return self.pos.tolist()
 
 
 class _ConformerNative(torch.autograd.Function):

@@ -1034,6 +1034,50 @@ size_t agx_glu_dwconv_backward_workspace_bytes(int32_t B, int32_t C, int32_t T, 
  * tree and groups as above), then one wavefront per channel over the shares p = b * tiles + tile. */
 int agx_glu_dwconv_backward(const float *dz, const float *u, const float *w, float *du, float *dw, float *dbias,
                             void *workspace, size_t workspace_bytes, int32_t B, int32_t C, int32_t T, int32_t K, void *stream);
+/* ------------------------------------------------------------------------- *
+ * The causal form of the module above and its streaming cache.  Everything stated there holds -- formats, determinism,
+ * error codes before any launch -- with left = K - 1: an output sees its own frame and the K - 1 before it, nothing
+ * later.
+ *   z[b, c, t]  = bias[c] + sum_k w[c, k] G[b, c, t + k - (K - 1)]      one fma per tap, k rising, from bias (as above)
+ *   G[t] = g[t] for 0 <= t < T;   G[t] = hist[b, c, (K - 1) + t] for -(K - 1) <= t < 0   (0.f where hist == NULL)
+ *   dg[b, c, t] = sum_k w[c, k] dz[b, c, t + (K - 1) - k]               zeros at and beyond T
+ *   dw[c, k]    = sum_{b, t} dz[b, c, t] g[b, c, t + k - (K - 1)],   dbias[c] = sum_{b, t} dz[b, c, t]
+ * hist is (B, C, K - 1) fp32, oldest frame first: the post-GLU values g of the K - 1 frames before the call (half the
+ * size of their u, and no sigmoid is taken twice); all zeros is the start of a stream.  A history is an exact operand.
+ * A non-finite value stays in its channel, and leaves the stream K - 1 frames after it entered.  Chunked calls are bit
+ * for bit the single call: feeding T frames through hist in chunks of any lengths -- agx_glu_dwconv_step, or
+ * agx_glu_dwconv_causal_forward(hist) followed by agx_glu_hist_update -- writes the y that one
+ * agx_glu_dwconv_causal_forward over the T frames writes, and leaves in hist the last K - 1 values of g.
+ * ------------------------------------------------------------------------- */
+#define AGX_CONFORMER_MAX_STEP 64
+/* agx_glu_dwconv_forward with left = K - 1: the same tile kernel, the same gamma .. var convention (all NULL: out = z,
+ * all given: out = y on the running statistics).  hist may be NULL; it is read, never written. */
+int agx_glu_dwconv_causal_forward(const float *u, const float *w, const float *bias, const float *gamma, const float *beta,
+                                  const float *mean, const float *var, float eps, const float *hist, float *out, int32_t B,
+                                  int32_t C, int32_t T, int32_t K, void *stream);
+/* The workspace of agx_glu_dwconv_causal_backward: that of agx_glu_dwconv_backward. */
+size_t agx_glu_dwconv_causal_backward_workspace_bytes(int32_t B, int32_t C, int32_t T, int32_t K);
+/* agx_glu_dwconv_backward with left = K - 1: its stages, reduction orders and NULL conventions.  No history: there is
+ * no backward through a cached call. */
+int agx_glu_dwconv_causal_backward(const float *dz, const float *u, const float *w, float *du, float *dw, float *dbias,
+                                   void *workspace, size_t workspace_bytes, int32_t B, int32_t C, int32_t T, int32_t K,
+                                   void *stream);
+/* The streaming step, one launch: y (B, C, n) of the n new frames u (B, 2 C, n) from hist and u -- the eval form, every
+ * one of gamma .. var required -- and hist rewritten in place with the last K - 1 values of [hist | g(u)]; with
+ * n < K - 1 the newest K - 1 - n old values move to the front.  1 <= n <= AGX_CONFORMER_MAX_STEP, else
+ * AGX_ERR_BAD_SHAPE; hist may be NULL only for K == 1.  Work is packed by output: a workgroup owns R whole (b, c) rows,
+ * R = min(256 / n, what 48 KiB of LDS hold, ceil(B C / 1024)) -- its 256 threads filled with outputs once the batch
+ * is large enough to leave 1024 workgroups --, stages their histories, their g and their taps in LDS, and reads every
+ * history value before the barrier that precedes its writes; no other workgroup touches those rows.  The fma chain of
+ * an output is that of agx_glu_dwconv_causal_forward; R changes no bit. */
+int agx_glu_dwconv_step(const float *u, const float *w, const float *bias, const float *gamma, const float *beta,
+                        const float *mean, const float *var, float eps, float *hist, float *out, int32_t B, int32_t C,
+                        int32_t n, int32_t K, void *stream);
+/* hist <- the last K - 1 values of [hist | g(u)] for a chunk u (B, 2 C, T) of any T, one launch: what the step does to
+ * hist, for cached calls longer than AGX_CONFORMER_MAX_STEP (agx_glu_dwconv_causal_forward(hist), then this).  A
+ * workgroup owns whole rows: it reads, then a barrier, then it writes.  K == 1: nothing is launched. */
+int agx_glu_hist_update(const float *u, float *hist, int32_t B, int32_t C, int32_t T, int32_t K, void *stream);
+
 /* out = x * sigmoid(x) over n floats, one launch; out may be x. */
 int agx_silu(const float *x, float *out, int64_t n, void *stream);
 /* dx = dout * s (1 + x (1 - s)), s = sigmoid(x), one launch; dx may be dout or x. */
