@@ -22,6 +22,7 @@ FILM_CT, FILM_TC = 0, 1
 SNAKE_PLAIN, SNAKE_RELU = 0, 1
 CONFORMER_MAX_K = 64
 CONFORMER_MAX_STEP = 64     # AGX_CONFORMER_MAX_STEP: the frames one agx_glu_dwconv_step takes
+STREAM_LIVE = (1 << 63) - 1  # AGX_STREAM_LIVE: end[b] of a row whose stream has not ended
 
 
 class ConvDesc(Structure):
@@ -276,6 +277,13 @@ SIGNATURES = {
     "agx_glu_hist_update": (c_int, [c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_void_p]),
     "agx_silu": (c_int, [c_void_p, c_void_p, c_int64, c_void_p]),
     "agx_silu_backward": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_void_p]),
+    "agx_conv_stream_step": (c_int, [c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, c_float, c_void_p, c_void_p,
+                                     c_void_p, c_int32, c_void_p, c_int32, c_void_p, c_int32, c_void_p, c_void_p, c_int32, c_int32,
+                                     c_int32, c_int64, c_void_p]),
+    "agx_conv_stream_kernel_name": (c_int, [c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, c_char_p,
+                                            c_size_t]),
+    "agx_ring_write_rate": (c_int, [c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_int32, c_void_p]),
+    "agx_stream_mark_end": (c_int, [c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_void_p]),
 }
 
 _lib = None

@@ -2109,3 +2109,116 @@ def silu_backward(x: Tensor, dout: Tensor, out: Optional[Tensor] = None) -> Tens
     out = _same_out("silu_backward", x, out)
     _lib.check(lib.agx_silu_backward(_ptr(x), _ptr(dout), _ptr(out), x.numel(), _stream()), "agx_silu_backward")
     return out
+
+
+# ------------------------------------------------------------------ streaming conv stacks (include/agx.h "Streaming conv stacks")
+STREAM_LIVE = _lib.STREAM_LIVE
+
+
+def conv_stream_pack(desc: ConvDesc, v: Tensor, g: Optional[Tensor] = None) -> Tensor:
+    """The image ``conv_stream_step`` reads: the standard fp32 image of ``conv_pack`` whatever arithmetic the layer's plain call
+    uses (a name of its own, so that ``units.packed_image`` keeps it beside the plain call's image)."""
+    if desc.impl != IMPL_AUTO or desc.groups != 1:
+        raise AgxError("conv_stream_pack: the streaming step reads the dense fp32 image (impl = IMPL_AUTO, groups = 1)")
+    return conv_pack(desc, v, g)
+
+
+def conv_stream_kernel_name(kind: int, c_in: int, c_out: int, kernel: int, stride: int, dilation: int, n: int, rate_in: int) -> str:
+    """The kernel ``conv_stream_step`` runs for this layer and step (host-only); ``AgxError`` with the launcher's refusal."""
+    return _kernel_name("agx_conv_stream_kernel_name", kind, c_in, c_out, kernel, stride, dilation, n, rate_in)
+
+
+def _stream_rates(kind: int, stride: int, rate_in: int, delay_in: int) -> Tuple[int, int]:
+    """(rate_out, delay_out) of a layer (include/agx.h); the library refuses what does not divide."""
+    if kind == CONV_UPSAMPLE:
+        return rate_in * stride, delay_in * stride + stride
+    if kind == CONV_CAUSAL:
+        return rate_in // stride, delay_in // stride
+    return rate_in, delay_in
+
+
+def conv_stream_step(kind: int, c_in: int, c_out: int, kernel: int, stride: int, dilation: int, packed: Tensor, bias: Optional[Tensor],
+                     src: Tensor, dst: Tensor, pos: Tensor, n: int, rate_in: int, delay_in: int, src_ring: bool = True,
+                     dst_ring: bool = True, res: Optional[Tensor] = None, end: Optional[Tensor] = None, epilogue: int = 0,
+                     slope: float = 0.1) -> Tensor:
+    """One chunk of ``n`` frames through one conv layer of a stream (``agx_conv_stream_step``).  ``src``: the layer's input ring
+    (B, c_in, cap), or with ``src_ring=False`` a plain (B, c_in, n * rate_in) tensor of the step's own columns (kernel 1 only);
+    ``dst``: the consumer's ring (B, c_out, cap') or, ``dst_ring=False``, a plain (B, c_out, n * rate_out) tensor; ``res``: the
+    ring the residual is read from, at the output's columns; ``pos`` / ``end``: int64 (B,) device tensors, read by the kernel
+    and never written (``end=None``: no validity mask).  Writes the step's n * rate_out columns of ``dst`` and returns it.
+    Every refusal -- this wrapper's or the library's -- precedes the launch."""
+    lib = _lib.load()
+    _need_gpu(packed, bias, src, dst, res)
+    n, rate_in, delay_in = int(n), int(rate_in), int(delay_in)
+    if n < 1:
+        raise AgxError(f"conv_stream_step: a step takes n >= 1 frames, got {n}")
+    for name, t in (("src", src), ("dst", dst), ("res", res)):
+        if t is not None and (t.dtype != torch.float32 or t.dim() != 3 or not t.is_contiguous()):
+            raise AgxError(f"conv_stream_step: {name} must be a contiguous float32 (B, C, columns) tensor")
+    b = src.shape[0]
+    rate_out, _ = _stream_rates(kind, stride, rate_in, delay_in)
+    if src.shape[1] != c_in or (not src_ring and src.shape[2] != n * rate_in):
+        raise AgxError(f"conv_stream_step: src is {tuple(src.shape)} for c_in={c_in}"
+                       + ("" if src_ring else f" and {n * rate_in} plain columns"))
+    if tuple(dst.shape[:2]) != (b, c_out) or (not dst_ring and dst.shape[2] != n * rate_out):
+        raise AgxError(f"conv_stream_step: dst is {tuple(dst.shape)} for batch {b}, c_out={c_out}"
+                       + ("" if dst_ring else f" and {n * rate_out} plain columns"))
+    if bool(epilogue & EPI_RESIDUAL) != (res is not None):
+        raise AgxError("conv_stream_step: EPI_RESIDUAL and the residual ring go together")
+    if res is not None and tuple(res.shape[:2]) != (b, c_out):
+        raise AgxError(f"conv_stream_step: the residual ring is {tuple(res.shape)} for batch {b}, c_out={c_out}")
+    if any(t is not None and t.device != src.device for t in (packed, bias, dst, res)):
+        raise AgxError("conv_stream_step: operands on different devices")
+    pos = _checked_pos("conv_stream_step", pos, b, src.device)
+    if end is not None:
+        end = _checked_pos("conv_stream_step", end, b, src.device)
+    packed = _f32c(packed)
+    need = _lib.load().agx_conv_packed_floats(ctypes.byref(conv_desc(kind, 1, c_in, c_out, 1 << 20, kernel, stride, dilation)))
+    if need < 0:
+        _lib.check(int(need), "agx_conv_packed_floats")
+    if packed.numel() != need:
+        raise AgxError(f"conv_stream_step: the packed image has {packed.numel()} floats, the layer's has {need}")
+    if bias is not None:
+        bias = _f32c(bias)
+        if bias.numel() != c_out:
+            raise AgxError(f"conv_stream_step: bias has {bias.numel()} entries for c_out={c_out}")
+    tok = None
+    if _observer is not None:
+        tok = _observer.begin("other", ("conv_stream_step", 4 * (packed.numel() + b * c_out * n * rate_out), 0))
+    _lib.check(lib.agx_conv_stream_step(kind, c_in, c_out, kernel, stride, dilation, int(epilogue), float(slope), _ptr(packed),
+                                        _ptr(bias), _ptr(src), src.shape[2] if src_ring else 0, _ptr(res),
+                                        res.shape[2] if res is not None else 0, _ptr(dst), dst.shape[2] if dst_ring else 0,
+                                        _ptr(pos), _ptr(end), b, n, rate_in, delay_in, _stream()), "agx_conv_stream_step")
+    if tok is not None:
+        _observer.end(tok)
+    return dst
+
+
+def ring_write_rate(buf: Tensor, src: Tensor, pos: Tensor, rate: int) -> None:
+    """``buf[b, :, (pos[b] * rate + t) mod cap] = src[b, :, t]`` for src (B, C, n * rate) and the ring buf (B, C, cap): a stack's
+    input chunk into its first ring, every row at its own position, one launch.  ``pos`` is not written."""
+    lib = _lib.load()
+    _need_gpu(buf, src)
+    if any(t.dtype != torch.float32 or t.dim() != 3 or not t.is_contiguous() for t in (buf, src)):
+        raise AgxError("ring_write_rate: buf (B, C, cap) and src (B, C, columns) must be contiguous float32 tensors")
+    b, c, cols = src.shape
+    if tuple(buf.shape[:2]) != (b, c) or src.device != buf.device:
+        raise AgxError(f"ring_write_rate: src {tuple(src.shape)} does not match buf {tuple(buf.shape)}")
+    if int(rate) < 1 or cols % int(rate):
+        raise AgxError(f"ring_write_rate: {cols} columns are not whole frames of {rate}")
+    pos = _checked_pos("ring_write_rate", pos, b, buf.device)
+    _lib.check(lib.agx_ring_write_rate(_ptr(buf), _ptr(src), _ptr(pos), b, c, cols, buf.shape[2], int(rate), _stream()),
+               "agx_ring_write_rate")
+
+
+def stream_mark_end(pos: Tensor, end: Tensor, rows: Optional[Tensor] = None) -> None:
+    """``end[r] = pos[r]`` on the device for the row numbers in ``rows`` (an int64 device tensor; default every row)."""
+    lib = _lib.load()
+    if not isinstance(pos, Tensor) or not isinstance(end, Tensor):
+        raise AgxError("stream_mark_end: pos and end must be contiguous int64 device tensors")
+    pos = _checked_pos("stream_mark_end", pos, pos.numel(), pos.device)
+    end = _checked_pos("stream_mark_end", end, pos.numel(), pos.device)
+    if rows is not None:
+        rows = _checked_pos("stream_mark_end", rows, rows.numel() if isinstance(rows, Tensor) else 0, pos.device)
+    _lib.check(lib.agx_stream_mark_end(_ptr(pos), _ptr(end), _ptr(rows), 0 if rows is None else rows.numel(), pos.numel(), _stream()),
+               "agx_stream_mark_end")

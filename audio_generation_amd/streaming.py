@@ -1,0 +1,301 @@
+"""Streaming codec: chunked encode / decode on per-layer conv state rings.
+
+The conv stacks are causal up to a bounded look-ahead, so a live stream does not have to re-run the receptive field on every hop:
+every unit of a stack keeps a ring of its own INPUT, a step of ``n`` latent frames pushes the new columns through the stack with
+``ops.conv_stream_step`` (one tap-gather launch per conv, the producer writing straight into the consumer's ring), and the positions
+live in device memory, so a step makes no host decision and replays from a captured graph.
+
+* ``plan(model, max_chunk)`` walks ``model._units("encoders" | "decoders")`` -- the list inference, training and ``longform`` read --
+  and gives every unit its rate ``r`` (columns per latent frame), left reach ``H``, cumulative delay ``D`` and ring capacity;
+  nothing is hard-coded per configuration.
+* ``CodecStream`` holds the rings, ``enc_pos`` / ``dec_pos`` / ``end`` (int64 (B,), device), ``max_chunk`` and ``decoder_delay``.
+
+What a stream computes.  A unit's step produces exactly ``n r_out`` columns, the stream indices ``[pos r_out - D_out,
+(pos + n) r_out - D_out)``; a column ``j`` is stored as exact 0 unless ``0 <= j < end[b] r_out`` -- the layer's own zero padding in
+the plain call, before the start and after the end.  The encoder has no delay (a strided conv looks ``s - 1`` samples ahead, inside
+the frame's own samples) and needs no mask.  The decoder's upsampling convs are not causal (``vae.py:66-89``), so its output lags
+the input by ``decoder_delay`` samples: ``decode_stream`` returns the raw block of that index rule, zeros where the index is
+negative, and ``decode_flush`` pushes the ``ceil(decoder_delay / scale_factor)`` zero frames that bring the tail out.  With the
+delay removed, the stream equals the plain call on the whole clip.  Ragged last frames are the caller's: pad the last hop to a
+whole frame; the plain call pads every layer instead, so that frame differs.
+"""
+from __future__ import annotations
+
+from dataclasses import dataclass
+from typing import List, Optional
+
+import torch
+
+from . import ops
+from ._lib import (CONV_CAUSAL, CONV_TRANSPOSED, CONV_UPSAMPLE, EPI_LEAKY_POST, EPI_LEAKY_PRE, EPI_RESIDUAL, STREAM_LIVE, AgxError,
+                   needs_grad)
+from .units import Unit, detached, packed_image
+
+Tensor = torch.Tensor
+
+
+def _ceil_div(a: int, b: int) -> int:
+    return -((-a) // b)
+
+
+@dataclass(frozen=True)
+class UnitPlan:
+    """One unit of a stack as a stream runs it.  ``kind``: "causal" | "convt" | "up" | "res"; ``k, s, d`` of its conv (of the
+    dilated conv of a residual unit); ``rate_in`` / ``delay_in`` and ``rate_out`` / ``delay_out`` in columns; ``reach``: input
+    columns it reads before the chunk's first new one; ``cap = reach + max_chunk * rate_in``: its ring, so that a step's writes
+    never alias the history the step reads."""
+    kind: str
+    c_in: int
+    c_out: int
+    k: int
+    s: int
+    d: int
+    rate_in: int
+    delay_in: int
+    rate_out: int
+    delay_out: int
+    reach: int
+    cap: int
+
+
+@dataclass(frozen=True)
+class StreamPlan:
+    scale_factor: int
+    max_chunk: int
+    encoders: tuple
+    decoders: tuple
+
+    @property
+    def decoder_delay(self) -> int:
+        """Samples by which the decoder's output lags its input."""
+        return self.decoders[-1].delay_out
+
+    @property
+    def flush_frames(self) -> int:
+        return _ceil_div(self.decoder_delay, self.scale_factor)
+
+    @property
+    def enc_left(self) -> int:
+        """Input samples before a frame's first that the encoder reads: ``longform.receptive_field(model).enc_left``."""
+        return sum(u.reach * (self.scale_factor // u.rate_in) for u in self.encoders)
+
+
+_REFUSED_UNITS = {
+    "wavelet": "a wavelet decoder block folds its time axis and has no streaming step",
+    "multires": "a multiresolution layer has no streaming step",
+    "resdw": "a depthwise residual block (depthwise=True) has no streaming step",
+}
+
+
+def _unit_plan(u: Unit, rate: int, delay: int, max_chunk: int) -> UnitPlan:
+    if u.kind in _REFUSED_UNITS:
+        raise NotImplementedError(f"streaming: {_REFUSED_UNITS[u.kind]}; use the plain or the *_long calls")
+    if u.kind not in ("conv", "res"):
+        raise NotImplementedError(f"streaming: no step for a unit of kind {u.kind!r}")
+    c = u.convs[0].conv
+    k, s, d = c.kernel_size[0], c.stride[0], c.dilation[0]
+    layer_kind = u.convs[0].kind
+    if u.kind == "res":
+        c2 = u.convs[1].conv
+        if u.inner_slope is None:
+            raise NotImplementedError("streaming: a residual block around an activation the kernels do not fuse")
+        if layer_kind != CONV_CAUSAL or s != 1 or c2.kernel_size[0] != 1 or c2.stride[0] != 1:
+            raise NotImplementedError("streaming: a residual block is a stride-1 causal conv and a k = 1 conv")
+        kind, reach, rate_out, delay_out = "res", d * (k - 1), rate, delay
+    elif layer_kind == CONV_CAUSAL:
+        reach = d * (k - 1) - s + 1
+        if rate % s or delay % s:
+            raise NotImplementedError(f"streaming: a stride-{s} conv at {rate} columns per frame and delay {delay} leaves no whole columns")
+        if reach < 0:
+            raise NotImplementedError(f"streaming: a causal conv with stride {s} > dilation (k - 1) + 1")
+        kind, rate_out, delay_out = "causal", rate // s, delay // s
+    elif layer_kind == CONV_TRANSPOSED:
+        if s != 1:
+            raise NotImplementedError(f"streaming: a transposed conv with stride {s} > 1 has no streaming step (the decoder blocks "
+                                      "upsample with CausalUpsampleConv1d)")
+        kind, reach, rate_out, delay_out = "convt", k - 1, rate, delay
+    elif layer_kind == CONV_UPSAMPLE:
+        if k != 2 * s + 1:
+            raise NotImplementedError(f"streaming: an upsampling conv with kernel {k} != 2 * stride + 1")
+        kind, reach, rate_out, delay_out = "up", 2, rate * s, delay * s + s
+    else:
+        raise NotImplementedError(f"streaming: conv kind {layer_kind} has no streaming step")
+    return UnitPlan(kind, c.in_channels, u.convs[-1].conv.out_channels, k, s, d, rate, delay, rate_out, delay_out, reach,
+                    reach + max_chunk * rate)
+
+
+def plan(model, max_chunk: int) -> StreamPlan:
+    """Derived from the model's unit lists as they are wired; raises ``NotImplementedError`` for what a stream does not cover."""
+    from .quantizer import ResidualQuantizer
+    max_chunk = int(max_chunk)
+    if max_chunk < 1:
+        raise AgxError(f"streaming: max_chunk = {max_chunk} < 1")
+    if not isinstance(model.quantizer, ResidualQuantizer):
+        raise NotImplementedError(f"streaming: the bottleneck {type(model.quantizer).__name__} is not a ResidualQuantizer (the "
+                                  "quantiser is stateless per frame; an attention bottleneck needs its own cache wired in)")
+    sf = int(model.scale_factor)
+    stacks = []
+    for which, rate in (("encoders", sf), ("decoders", 1)):
+        delay, out = 0, []
+        for u in model._units(which):
+            p = _unit_plan(u, rate, delay, max_chunk)
+            out.append(p)
+            rate, delay = p.rate_out, p.delay_out
+        if rate != (1 if which == "encoders" else sf):
+            raise NotImplementedError(f"streaming: the {which} leave {rate} columns per frame, scale_factor is {sf}")
+        stacks.append(tuple(out))
+    if stacks[0][-1].delay_out != 0:
+        raise NotImplementedError("streaming: an encoder with a delay")
+    return StreamPlan(sf, max_chunk, stacks[0], stacks[1])
+
+
+class CodecStream:
+    """The state of ``batch`` live streams through one ``CausalVQAE`` (``model.new_stream``): per unit one fp32 ring
+    (B, c_in, cap) of its input, zero-filled; ``enc_pos`` / ``dec_pos``: the frames every row's encoder / decoder has received;
+    ``end``: the frame at which a row's stream ended, ``ops.STREAM_LIVE`` while it is live.  All int64 (B,) on the device, read by
+    the kernels and advanced by a kernel.  ``decoder_delay``: samples by which ``decode_stream``'s output lags."""
+
+    def __init__(self, model, batch: int, max_chunk: int, device=None):
+        batch = int(batch)
+        if batch < 1:
+            raise AgxError(f"new_stream: batch = {batch} < 1")
+        self.plan = plan(model, max_chunk)
+        self.model_id = id(model)
+        self.batch, self.max_chunk = batch, self.plan.max_chunk
+        self.scale_factor, self.decoder_delay = self.plan.scale_factor, self.plan.decoder_delay
+        self.device = torch.device(device) if device is not None else next(model.parameters()).device
+        self.enc_rings = [torch.zeros((batch, u.c_in, u.cap), dtype=torch.float32, device=self.device) for u in self.plan.encoders]
+        self.dec_rings = [torch.zeros((batch, u.c_in, u.cap), dtype=torch.float32, device=self.device) for u in self.plan.decoders]
+        self.enc_pos = torch.zeros(batch, dtype=torch.int64, device=self.device)
+        self.dec_pos = torch.zeros(batch, dtype=torch.int64, device=self.device)
+        self.end = torch.full((batch,), STREAM_LIVE, dtype=torch.int64, device=self.device)
+
+    def _rows(self, rows, what: str) -> Optional[List[int]]:
+        if rows is None:
+            return None
+        rows = [int(r) for r in rows]
+        if any(not 0 <= r < self.batch for r in rows):
+            raise AgxError(f"{what}: rows {rows} are not rows of a stream of batch {self.batch}")
+        return rows
+
+    def finish(self, rows=None) -> None:
+        """The streams of ``rows`` (default: every row) end at the frames their decoders have received: ``end[r] = dec_pos[r]``,
+        on the device.  What the decoder produces past that frame is the plain call's zero padding; ``decode_flush`` brings the
+        delayed tail out."""
+        rows = self._rows(rows, "finish")
+        ops.stream_mark_end(self.dec_pos, self.end,
+                            None if rows is None else torch.tensor(rows, dtype=torch.int64).to(self.device))
+
+    def reset(self, rows=None) -> None:
+        """``rows`` (default: every row) start a new stream at their next call: positions to 0, ``end`` to live and those rows of
+        every ring to zero, all device fills.  Call it between steps, outside any captured graph."""
+        rows = self._rows(rows, "reset")
+        for sel in ([slice(None)] if rows is None else [slice(r, r + 1) for r in rows]):
+            self.enc_pos[sel].zero_()
+            self.dec_pos[sel].zero_()
+            self.end[sel].fill_(STREAM_LIVE)
+            for ring in (*self.enc_rings, *self.dec_rings):
+                ring[sel].zero_()
+
+    def positions(self) -> dict:
+        """The positions as lists of ints.  Synchronises: for tests and debugging, never called in a step."""
+        return {"enc_pos": self.enc_pos.tolist(), "dec_pos": self.dec_pos.tolist(), "end": self.end.tolist()}
+
+
+# --------------------------------------------------------------------------- the step
+def _image(layer) -> Tensor:
+    return packed_image(layer.conv, "conv_stream_pack", layer.kind)
+
+
+def _run_stack(units: List[Unit], plans, rings: List[Tensor], x: Tensor, pos: Tensor, end: Optional[Tensor], n: int) -> Tensor:
+    """``n`` frames through a stack: the chunk into the first ring, one or two step launches per unit, the last unit into a plain
+    tensor, then the advance of ``pos``."""
+    b = x.shape[0]
+    ops.ring_write_rate(rings[0], x, pos, plans[0].rate_in)
+    out = None
+    for i, (u, p) in enumerate(zip(units, plans)):
+        last = i + 1 == len(units)
+        dst = torch.empty((b, p.c_out, n * p.rate_out), dtype=torch.float32, device=x.device) if last else rings[i + 1]
+        out = run_unit(u, p, rings[i], dst, not last, pos, end, n)
+    ops.stream_advance(pos, n)
+    return out
+
+
+def run_unit(u: Unit, p: UnitPlan, ring: Tensor, dst: Tensor, dst_ring: bool, pos: Tensor, end: Optional[Tensor], n: int) -> Tensor:
+    """One unit's step: ``ring`` -> ``dst``.  A conv is one launch; a residual unit is two, its hidden activation (which only the
+    k = 1 conv at the same column reads, so it needs no mask and no history) in a plain scratch tensor."""
+    post = u.slope
+    if p.kind == "res":
+        c1, c2 = u.convs[0], u.convs[1]
+        hid = torch.empty((ring.shape[0], c1.conv.out_channels, n * p.rate_in), dtype=torch.float32, device=ring.device)
+        ops.conv_stream_step(CONV_CAUSAL, p.c_in, c1.conv.out_channels, p.k, 1, p.d, _image(c1), detached(c1.conv.bias), ring, hid, pos,
+                             n, p.rate_in, p.delay_in, dst_ring=False, epilogue=EPI_LEAKY_PRE, slope=u.inner_slope)
+        return ops.conv_stream_step(CONV_CAUSAL, c1.conv.out_channels, p.c_out, 1, 1, 1, _image(c2), detached(c2.conv.bias), hid, dst, pos,
+                                    n, p.rate_in, p.delay_in, src_ring=False, dst_ring=dst_ring, res=ring, end=end,
+                                    epilogue=EPI_RESIDUAL | (EPI_LEAKY_POST if post is not None else 0), slope=post or 0.0)
+    layer = u.convs[0]
+    return ops.conv_stream_step(layer.kind, p.c_in, p.c_out, p.k, p.s, p.d, _image(layer), detached(layer.conv.bias), ring, dst, pos, n,
+                                p.rate_in, p.delay_in, dst_ring=dst_ring, end=end, epilogue=EPI_LEAKY_PRE if post is not None else 0,
+                                slope=post or 0.0)
+
+
+def _check(model, stream: CodecStream, x: Tensor, what: str, per_frame: int, channels: int) -> int:
+    """Every refusal of a step, before the first launch; returns the chunk's frames."""
+    if not isinstance(stream, CodecStream) or stream.model_id != id(model):
+        raise AgxError(f"{what}: the stream belongs to another model (model.new_stream makes one for this model)")
+    if model.training:
+        raise NotImplementedError(f"{what}: a stream is inference only: call model.eval() (there is no backward through a stream)")
+    if needs_grad(x, model):
+        raise NotImplementedError(f"{what}: a stream is inference only: call it under torch.no_grad()")
+    if x.dim() != 3 or x.shape[1] != channels:
+        raise AgxError(f"{what}: expected (B, {channels}, columns) after rearrange_in, got {tuple(x.shape)}")
+    if x.shape[0] != stream.batch:
+        raise AgxError(f"{what}: the chunk has batch {x.shape[0]}, the stream has {stream.batch}")
+    if x.device != stream.device:
+        raise AgxError(f"{what}: the chunk is on '{x.device}', the stream on '{stream.device}'")
+    n, rest = divmod(x.shape[2], per_frame)
+    if rest or n < 1:
+        raise AgxError(f"{what}: a chunk is n >= 1 whole frames of {per_frame} columns, got {x.shape[2]} (pad the last hop)")
+    if n > stream.max_chunk:
+        raise AgxError(f"{what}: a chunk of {n} frames exceeds the stream's max_chunk = {stream.max_chunk}")
+    if x.dtype != torch.float32:
+        raise AgxError(f"{what}: expected float32, got {x.dtype}")
+    return n
+
+
+def encode_latents_stream(model, x: Tensor, stream: CodecStream) -> Tensor:
+    """Encoder stack on a chunk in the model's input format -> (B, D, n) latents of the chunk's ``n`` frames."""
+    xin = model.rearrange_in(x)
+    n = _check(model, stream, xin, "encode_stream", stream.scale_factor, model.in_channels)
+    return _run_stack(model._units("encoders"), stream.plan.encoders, stream.enc_rings, xin.contiguous(), stream.enc_pos, None, n)
+
+
+def encode_stream(model, x: Tensor, stream: CodecStream, codebook_n: Optional[int] = None):
+    z = encode_latents_stream(model, x, stream)
+    zq, index, commit = model.quantizer.quantize_bcl(z, codebook_n, update_codebook=False, prioritize_early=False)
+    return zq, commit, index
+
+
+def decode_stream(model, zq: Tensor, stream: CodecStream) -> Tensor:
+    n = _check(model, stream, zq, "decode_stream", 1, stream.plan.decoders[0].c_in)
+    y = _run_stack(model._units("decoders"), stream.plan.decoders, stream.dec_rings, zq.contiguous(), stream.dec_pos, stream.end, n)
+    return model.rearrange_out(y)
+
+
+def forward_stream(model, x: Tensor, stream: CodecStream, codebook_n: Optional[int] = None):
+    zq, commit, index = encode_stream(model, x, stream, codebook_n)
+    return decode_stream(model, zq, stream), commit, index
+
+
+def decode_flush(model, stream: CodecStream) -> Tensor:
+    """The ``ceil(decoder_delay / scale_factor)`` zero-frame steps that bring the delayed tail out, in chunks of at most
+    ``max_chunk`` frames -> (B, C, frames * scale_factor) in the model's output format."""
+    left, parts = stream.plan.flush_frames, []
+    c = stream.plan.decoders[0].c_in
+    while left > 0:
+        n = min(left, stream.max_chunk)
+        parts.append(decode_stream(model, torch.zeros((stream.batch, c, n), dtype=torch.float32, device=stream.device), stream))
+        left -= n
+    if not parts:
+        return model.rearrange_out(torch.zeros((stream.batch, model.in_channels, 0), dtype=torch.float32, device=stream.device))
+    return parts[0] if len(parts) == 1 else torch.cat(parts, dim=1 if model.input_format == "b l c" else 2)

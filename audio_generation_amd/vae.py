@@ -503,6 +503,34 @@ class CausalVQAE(nn.Module):
         from . import longform
         return longform.forward_long(self, x, segment_frames, codebook_n)
 
+    # -- streaming on per-layer conv state rings (build-defined; streaming.py) -------------------
+    def new_stream(self, batch: int, max_chunk: int = 4, device=None):
+        """A ``CodecStream`` for ``batch`` live streams that advance by 1 .. ``max_chunk`` latent frames per call."""
+        from . import streaming
+        return streaming.CodecStream(self, batch, max_chunk, device)
+
+    def encode_stream(self, x_chunk, stream, codebook_n=None):
+        """``encode`` of the next ``n`` whole frames of every row -> (zq (B, D, n), commit_loss, index (B, n, Q)); the conv state
+        is carried in ``stream``, the quantiser is stateless per frame.  Inference only."""
+        from . import streaming
+        return streaming.encode_stream(self, x_chunk, stream, codebook_n)
+
+    def decode_stream(self, zq_chunk: Tensor, stream) -> Tensor:
+        """Decoder on the next ``n`` frames of (B, D, n) quantised latents -> ``n * scale_factor`` samples per row in the model's
+        output format: the block that lags the input by ``stream.decoder_delay`` samples, zeros before the stream's start."""
+        from . import streaming
+        return streaming.decode_stream(self, zq_chunk, stream)
+
+    def forward_stream(self, x_chunk, stream, codebook_n=None):
+        """``encode_stream`` then ``decode_stream`` -> (y, commit_loss, index)."""
+        from . import streaming
+        return streaming.forward_stream(self, x_chunk, stream, codebook_n)
+
+    def decode_flush(self, stream) -> Tensor:
+        """After ``stream.finish()``: the zero-frame steps that bring the decoder's delayed tail out."""
+        from . import streaming
+        return streaming.decode_flush(self, stream)
+
     def sample(self, length=225, device="cuda", normal_var=5e3, n_iters=12):
         """vae.py:324-345: random codes -> dequantise -> decode."""
         self.to(device)

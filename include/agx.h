@@ -1083,6 +1083,43 @@ int agx_silu(const float *x, float *out, int64_t n, void *stream);
 /* dx = dout * s (1 + x (1 - s)), s = sigmoid(x), one launch; dx may be dout or x. */
 int agx_silu_backward(const float *x, const float *dout, float *dx, int64_t n, void *stream);
 
+/* ---- Streaming conv stacks (csrc/conv_stream.hip) -----------------------------------------------------------
+ * A stream advances in whole latent frames; pos[b] (int64, device) counts the frames row b has received.  A layer has a rate
+ * (columns per frame) and a delay (how many columns its output lags the stream) on either side:
+ *     AGX_CONV_CAUSAL (k, s, d):        rate_out = rate_in / s, delay_out = delay_in / s (s must divide both);
+ *     AGX_CONV_TRANSPOSED (k, s = 1):   rate_out = rate_in,     delay_out = delay_in;
+ *     AGX_CONV_UPSAMPLE (k = 2 s + 1):  rate_out = rate_in s,   delay_out = delay_in s + s.
+ * A step of n frames reads the input columns [pos rate_in - delay_in - reach, (pos + n) rate_in - delay_in) -- reach =
+ * d (k - 1) - s + 1, k - 1 and 2 -- and produces exactly the n rate_out output columns [pos rate_out - delay_out,
+ * (pos + n) rate_out - delay_out), each the polyphase sum of agx_conv_forward on the standard image of agx_conv_pack
+ * (impl AGX_IMPL_AUTO) with epilogue = bias, AGX_EPI_LEAKY_PRE, AGX_EPI_RESIDUAL, AGX_EPI_LEAKY_POST in that order.
+ *   src   ring (B, c_in, src_cap): column i of the stream sits at (i mod src_cap), floor mod -- indices are negative at the start
+ *         of a delayed layer; src_cap >= reach + n rate_in.  src_cap == 0: a plain (B, c_in, n rate_in) tensor holding the
+ *         step's own columns (kernel 1, stride 1 only: the hidden activation of a residual unit).
+ *   res   AGX_EPI_RESIDUAL: ring (B, c_out, res_cap >= n rate_out) indexed by the OUTPUT column (stride-1 layers).
+ *   dst   ring (B, c_out, dst_cap >= n rate_out) written at (index mod dst_cap), or dst_cap == 0: plain (B, c_out, n rate_out).
+ *   end   NULL: no mask.  Else int64 (B,): output column j is stored as exact 0 unless 0 <= j < end[b] rate_out;
+ *         AGX_STREAM_LIVE = no end yet.  This is the layer's own zero padding in the plain call, on both sides.
+ * pos and end are read, never written; only the n rate_out destination columns of every row are written.  fp32; every
+ * output is one fixed fmaf chain whatever n, batch or the ring phase (the split of the reduction over the waves of a workgroup is
+ * a function of (c_in, taps) alone).  batch or n <= 0: AGX_OK, nothing launched.  Refusals precede every use of a pointer. */
+#define AGX_STREAM_LIVE INT64_MAX
+int agx_conv_stream_step(int32_t kind, int32_t c_in, int32_t c_out, int32_t kernel, int32_t stride, int32_t dilation, int32_t epilogue,
+                         float slope, const float *packed, const float *bias, const float *src, int32_t src_cap, const float *res,
+                         int32_t res_cap, float *dst, int32_t dst_cap, const int64_t *pos, const int64_t *end, int32_t batch, int32_t n,
+                         int32_t rate_in, int64_t delay_in, void *stream);
+/* Host-only: "conv_stream<KS,NT>" (KS waves split the reduction, a lane carries NT base positions), "none" for an empty step,
+ * or the launcher's refusal of the layer. */
+int agx_conv_stream_kernel_name(int32_t kind, int32_t c_in, int32_t c_out, int32_t kernel, int32_t stride, int32_t dilation, int32_t n,
+                                int32_t rate_in, char *buf, size_t buf_len);
+/* buf[b, c, (pos[b] rate + t) mod cap] = src[b, c, t] for src (B, rows, n_cols) contiguous, buf (B, rows, cap), n_cols <= cap:
+ * a stack's input chunk (n frames of `rate` columns) into its first ring.  Writes those columns only; pos is not written. */
+int agx_ring_write_rate(float *buf, const float *src, const int64_t *pos, int32_t batch, int32_t rows, int32_t n_cols, int32_t cap,
+                        int32_t rate, void *stream);
+/* end[r] = pos[r] for the n_rows row numbers in `rows` (int64, device; entries outside [0, batch) are skipped), or for every
+ * row when rows is NULL: the stream of those rows ends at the frames they have received.  Writes end only. */
+int agx_stream_mark_end(const int64_t *pos, int64_t *end, const int64_t *rows, int32_t n_rows, int32_t batch, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

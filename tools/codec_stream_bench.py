@@ -1,0 +1,151 @@
+"""One streamed hop of the codec beside what the plain forward offers for the same new frames.
+
+The protocol of tools/causal_conformer_bench.py: one process; every case is captured once as a graph (the Python wrappers and their
+allocations are in the capture, not in the replay), warmed up, and replayed once per round between two HIP events, the cases
+alternated; median [min .. max] of the per-round microseconds over ROUNDS rounds.  Comparators are listed twice (``again``): the
+difference of the two rows is the spread every row has to be read against.
+
+  (a) one ``forward_stream`` step of config S at B in {1, 8}, n in {1, 4} new frames: ring write, 60 step launches, the RVQ, two
+      position advances
+  (b) ``model.forward`` on a window of 16 + 20 + n + 2 frames -- the encoder's and the decoder's left halos, the new frames and the
+      decoder's right halo: what a live user of the plain calls re-runs per hop for the same n frames.  ``--plain-only`` measures
+      (b) alone, so that this file runs unchanged in a checkout of the commit before the streaming step (where (a) does not exist)
+  (c) per unit of config S (every distinct layer shape), B = 1: the unit's step launches beside the unit's plain call on a window
+      of H + n r_in columns
+
+Beside every (a) row: the hop's real time, n * 320 / 24 000 s.
+
+    python tools/codec_stream_bench.py [--plain-only] > profiles/codec_stream.txt
+"""
+import argparse
+import os
+import statistics
+import sys
+
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+from audio_generation_amd.vae import CausalVQAE  # noqa: E402
+
+ROUNDS = 9
+STEPS_PER_GRAPH = 10
+ENC_HALO, DEC_HALO_LEFT, DEC_HALO_RIGHT = 16, 20, 2
+SAMPLE_RATE = 24000
+
+
+def measure(cases, launches):
+    """[(name, fn)] -> {name: [microseconds per call, one per round]}."""
+    graphs = []
+    side = torch.cuda.Stream()
+    for _, fn in cases:
+        side.wait_stream(torch.cuda.current_stream())
+        with torch.cuda.stream(side), torch.no_grad():
+            fn()
+            fn()
+        torch.cuda.current_stream().wait_stream(side)
+        torch.cuda.synchronize()
+        g = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(g), torch.no_grad():
+            for _ in range(launches):
+                fn()
+        g.replay()
+        graphs.append(g)
+    torch.cuda.synchronize()
+    times = {name: [] for name, _ in cases}
+    for _ in range(ROUNDS):
+        for (name, _), g in zip(cases, graphs):
+            start, stop = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            start.record()
+            g.replay()
+            stop.record()
+            stop.synchronize()
+            times[name].append(1e3 * start.elapsed_time(stop) / launches)
+    del graphs
+    return times
+
+
+def show(times):
+    for name, ts in times.items():
+        print(f"  {name:<64}{statistics.median(ts):10.2f} us [{min(ts):10.2f} .. {max(ts):10.2f}]", flush=True)
+
+
+def config_s(dev):
+    torch.manual_seed(0)
+    model = CausalVQAE(in_channels=1, n_blocks=4, strides=(2, 4, 5, 8), num_quantizers=8, codebook_size=1024, codebook_dim=512,
+                       input_format="n c l", wavelet_decoders=False).eval().to(dev)
+    gen = torch.Generator().manual_seed(1234)
+    x = (0.1 * torch.randn(2, 1, 72000, generator=gen)).clamp(-1, 1).to(dev)
+    with torch.no_grad():
+        model.quantizer.init_from_latents(model._run_encoders(model.rearrange_in(x)))
+    return model
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--plain-only", action="store_true", help="measure (b) alone (a checkout without the streaming step)")
+    args = ap.parse_args()
+    assert torch.cuda.is_available(), "needs the MI355X"
+    dev = "cuda"
+    model = config_s(dev)
+    sf = model.scale_factor
+    gen = torch.Generator().manual_seed(0)
+    print(f"device: {torch.cuda.get_device_name(0)}; config S; per-call time over {ROUNDS} replays of a graph of {STEPS_PER_GRAPH} "
+          f"back-to-back calls (median [min .. max]){'; --plain-only' if args.plain_only else ''}")
+    verdicts = []
+    for b in (1, 8):
+        for n in (1, 4):
+            frames = ENC_HALO + DEC_HALO_LEFT + n + DEC_HALO_RIGHT
+            window = (0.1 * torch.randn(b, 1, frames * sf, generator=gen)).to(dev)
+            plain = lambda: model(window)                                           # noqa: E731
+            cases = [(f"(b) model.forward on {frames} frames", plain)]
+            if not args.plain_only:
+                chunk = window[:, :, :n * sf].contiguous()
+                stream = model.new_stream(b, max_chunk=4)
+                cases.append(("(a) forward_stream step", lambda: model.forward_stream(chunk, stream)))
+            cases.append((f"(b) model.forward on {frames} frames (again)", plain))
+            times = measure(cases, STEPS_PER_GRAPH)
+            print(f"\nB = {b}, n = {n} new frames: the hop lasts {1e6 * n * sf / SAMPLE_RATE:.0f} us of audio")
+            show(times)
+            if not args.plain_only:
+                names = list(times)
+                a, b1, b2 = times[names[1]], times[names[0]], times[names[2]]
+                ok = max(a) < min(b1 + b2)
+                verdicts.append(ok)
+                print(f"  (b) / (a) = {min(statistics.median(b1), statistics.median(b2)) / statistics.median(a):.2f}; (a)'s slowest round "
+                      f"below (b)'s fastest: {'yes' if ok else 'NO'}")
+    if args.plain_only:
+        return
+    print(f"\nacceptance (a) below (b) by more than the spread: {sum(verdicts)} of {len(verdicts)} cases")
+
+    from audio_generation_amd import streaming
+    print("\n(c) per unit, B = 1: the unit's step launches | the unit's plain call on H + n r_in columns")
+    losers = []
+    for n in (1, 4):
+        plan = streaming.plan(model, n)
+        seen = set()
+        for which, plans in (("encoders", plan.encoders), ("decoders", plan.decoders)):
+            for u, p in zip(model._units(which), plans):
+                key = (p.kind, p.c_in, p.c_out, p.k, p.s, p.d, p.rate_in)
+                if key in seen:
+                    continue
+                seen.add(key)
+                ring = torch.randn(1, p.c_in, p.cap, generator=gen).to(dev)
+                dst = torch.empty(1, p.c_out, n * p.rate_out, device=dev)
+                pos = torch.full((1,), 1000, dtype=torch.int64, device=dev)
+                window = torch.randn(1, p.c_in, p.reach + n * p.rate_in, generator=gen).to(dev)
+                plain = (lambda u=u, window=window: u.layer(window) if u.bare else u.forward(window))
+                step = (lambda u=u, p=p, ring=ring, dst=dst, pos=pos: streaming.run_unit(u, p, ring, dst, False, pos, None, n))
+                label = f"{p.kind}({p.c_in}->{p.c_out}, k{p.k} s{p.s} d{p.d}) r_in {p.rate_in} n {n}"
+                times = measure([(f"plain {label}", plain), (f"step  {label}", step), (f"plain {label} (again)", plain)], 20)
+                show(times)
+                names = list(times)
+                if statistics.median(times[names[1]]) > max(times[names[0]] + times[names[2]]):
+                    losers.append(label)
+    print(f"\nunits where the step's median is above every round of the plain call: {len(losers)}")
+    for label in losers:
+        print(f"  {label}")
+
+
+if __name__ == "__main__":
+    main()
