@@ -15,7 +15,7 @@
 //           Operands are rounded to bf16 in registers.  No LDS at all: the k-slot <-> key assignment of the PV product
 //           is chosen so that the probability registers are the B operand as they stand (k-slot (lh, e) <-> key
 //           4 lh + (e & 3) + 8 (e >> 2) of a 16-key half block) and the matching V fragment is two 16-byte global loads.
-#include "mfma_tile.hpp"
+#include "attention_masked.hpp"
 
 namespace agx {
 
@@ -416,273 +416,50 @@ const AttnRow *attn_bf16_lds_rows() { return kAttnBf16LdsRows; }
 //   dq      per 16-query block, loop over key blocks:  P = exp(s - lse), dP = dO^T V, dS = P (dP - delta),  dQ += dS K^T / scale
 //   dkv     per 64-key block, loop over query blocks:  dK += dS^T Q / scale,  dV += P^T dO   (accumulators in registers)
 // s_ij = q_i . k_j / scale - slope |i - j|  (transformers.py:177-183).
-// The masked families (cross, causal, window, ragged, packed) run the same three kernels as the bodies of attention_masked.hpp,
-// with the query side indexed by Tq and the key side by Tk; these stay the self-attention code they were, so a fix to the
-// arithmetic here belongs in attn_bwd_stats_body / _dq_body / _dkv_body too.
+// The three are the shared bodies of attention_masked.hpp under the symmetric mask with ql = kl = T, the cross family's
+// arithmetic on the packed layout: Q, K and V rows of a 3 H Dh-row item at h Dh, + H Dh, + 2 H Dh, every pitch T, and dQ, dK,
+// dV at the same rows of dqkv.  (With ql = kl the logit's relative term is 0 for every valid query: s_ij as above.)
 namespace agx {
 
-constexpr int AB_QB = 16;    // queries per block
-constexpr int AB_KB = 64;    // keys per block
-
-// The logit of (query i, key j), rounded the same way in all three kernels: the product feeds an explicit fmaf, so no
-// contraction can differ between them.  lse is built from these values, and P = exp(logit - lse) is exactly 1 on a row that one
-// key holds alone; a logit near 100 rounded differently in two kernels would put 1e-5 of relative error into P instead.
-static __device__ __forceinline__ float attn_bwd_logit(float s, float inv, int dist, float slope) {
-    return fmaf(-fabsf(float(dist)), slope, s * inv);
+static __device__ __forceinline__ AttnView<SymMask<false>> self_view(const float *qkv, const float *dout, int h, int b, int H, int Dh,
+                                                                     int T) {
+    const int HD = H * Dh;
+    AttnView<SymMask<false>> v{};
+    v.ql = v.q_end = v.kl = v.k_end = T;
+    v.qg = qkv + (size_t(b) * 3 * HD + h * Dh) * T;
+    v.kg = v.qg + size_t(HD) * T;
+    v.vg = v.kg + size_t(HD) * T;
+    v.dg = dout + (size_t(b) * HD + h * Dh) * T;
+    v.pq = v.pk = v.pd = T;
+    v.so = (size_t(b) * H + h) * T;
+    return v;
 }
 
-// one workgroup per (query block, head, item): lse and delta of its 16 queries.  delta_i = sum_j P_ij dP_ij is summed online
-// next to l, from dP values formed exactly as the dq and dkv kernels form them (the same fmaf chain over d), not taken as
-// sum_d dO[d,i] O[d,i] from the forward's output: where one key holds all of a row's weight, dP_ij == delta_i must cancel
-// to zero in dS = P (dP - delta), and two differently rounded dot products leave a residue that K / scale multiplies into dQ.
 // (`out` stays in the signature for the callers; it is not read.)
 __global__ __launch_bounds__(256) void attn_bwd_stats_kernel(const float *__restrict__ qkv, const float *__restrict__ slopes,
                                                              const float *__restrict__ out, const float *__restrict__ dout,
                                                              float *__restrict__ lse, float *__restrict__ delta, int H, int Dh,
                                                              int T, float scale_div) {
-    extern __shared__ __attribute__((aligned(16))) float sm[];
-    float *Qs = sm;                 // [Dh][QB]
-    float *Os = Qs + Dh * AB_QB;    // [Dh][QB]  dO
-    float *Ks = Os + Dh * AB_QB;    // [Dh][KB]
-    float *Vs = Ks + Dh * AB_KB;    // [Dh][KB]
-    float *Ss = Vs + Dh * AB_KB;    // [QB][KB]
-    float *Ds = Ss + AB_QB * AB_KB;  // [QB][KB]  dP
-    __shared__ float red[AB_QB][16], redd[AB_QB][16];
-    const int tid = threadIdx.x, h = blockIdx.y, b = blockIdx.z, i0 = blockIdx.x * AB_QB;
-    const int HD = H * Dh;
-    const float *qg = qkv + (size_t(b) * 3 * HD + h * Dh) * T, *kg = qg + size_t(HD) * T, *vg = kg + size_t(HD) * T;
-    const float *dg = dout + (size_t(b) * HD + h * Dh) * T;
-    const float slope = slopes[h], inv = 1.f / scale_div;
-    for (int e = tid; e < Dh * AB_QB; e += 256) {
-        const int d = e / AB_QB, q = e - d * AB_QB, i = min(i0 + q, T - 1);
-        Qs[e] = qg[size_t(d) * T + i];
-        Os[e] = dg[size_t(d) * T + i];
-    }
-    const int rq = tid / 16, rl = tid % 16;   // 16 threads per query row
-    float m = -3.0e38f, l = 0.f, dl = 0.f;
-    for (int j0 = 0; j0 < T; j0 += AB_KB) {
-        __syncthreads();
-        for (int e = tid; e < Dh * AB_KB; e += 256) {
-            const int d = e / AB_KB, j = e - d * AB_KB, jc = min(j0 + j, T - 1);
-            Ks[e] = kg[size_t(d) * T + jc];
-            Vs[e] = vg[size_t(d) * T + jc];
-        }
-        __syncthreads();
-        for (int e = tid; e < AB_QB * AB_KB; e += 256) {
-            const int q = e / AB_KB, j = e - q * AB_KB;
-            float s = 0.f, dp = 0.f;
-            for (int d = 0; d < Dh; ++d) {
-                s = fmaf(Qs[d * AB_QB + q], Ks[d * AB_KB + j], s);
-                dp = fmaf(Os[d * AB_QB + q], Vs[d * AB_KB + j], dp);
-            }
-            Ds[e] = dp;
-            Ss[e] = (j0 + j < T) ? attn_bwd_logit(s, inv, i0 + q - (j0 + j), slope) : -3.0e38f;
-        }
-        __syncthreads();
-        float bm = -3.0e38f;
-        for (int j = rl; j < AB_KB; j += 16) bm = fmaxf(bm, Ss[rq * AB_KB + j]);
-        red[rq][rl] = bm;
-        __syncthreads();
-        bm = red[rq][0];
-        for (int k = 1; k < 16; ++k) bm = fmaxf(bm, red[rq][k]);
-        const float mn = fmaxf(m, bm);
-        float bs = 0.f, bd = 0.f;
-        for (int j = rl; j < AB_KB; j += 16) {
-            const float p = expf(Ss[rq * AB_KB + j] - mn);   // 0 for a padded key
-            bs += p;
-            bd = fmaf(p, Ds[rq * AB_KB + j], bd);
-        }
-        __syncthreads();
-        red[rq][rl] = bs;
-        redd[rq][rl] = bd;
-        __syncthreads();
-        bs = bd = 0.f;
-        for (int k = 0; k < 16; ++k) {
-            bs += red[rq][k];
-            bd += redd[rq][k];
-        }
-        const float alpha = expf(m - mn);
-        l = l * alpha + bs;
-        dl = dl * alpha + bd;
-        m = mn;
-    }
-    if (rl == 0 && i0 + rq < T) {
-        const size_t o = (size_t(b) * H + h) * T + i0 + rq;
-        lse[o] = m + logf(l);
-        delta[o] = dl / l;
-    }
+    const int h = blockIdx.y, b = blockIdx.z;
+    attn_bwd_stats_body(self_view(qkv, dout, h, b, H, Dh, T), slopes, h, lse, delta, Dh, scale_div);
 }
 
-// one workgroup per (query block, head, item): dQ of its 16 queries, keys in blocks of 64
 __global__ __launch_bounds__(256) void attn_bwd_dq_kernel(const float *__restrict__ qkv, const float *__restrict__ slopes,
                                                           const float *__restrict__ dout, const float *__restrict__ lse,
                                                           const float *__restrict__ delta, float *__restrict__ dqkv, int H,
                                                           int Dh, int T, float scale_div) {
-    extern __shared__ __attribute__((aligned(16))) float sm[];
-    float *Qs = sm;                  // [Dh][QB]
-    float *Os = Qs + Dh * AB_QB;     // [Dh][QB]  dO
-    float *Ks = Os + Dh * AB_QB;     // [Dh][KB]
-    float *Vs = Ks + Dh * AB_KB;     // [Dh][KB]
-    float *Ss = Vs + Dh * AB_KB;     // [QB][KB]  dS / scale
-    const int tid = threadIdx.x, h = blockIdx.y, b = blockIdx.z, i0 = blockIdx.x * AB_QB;
-    const int HD = H * Dh;
-    const float *qg = qkv + (size_t(b) * 3 * HD + h * Dh) * T, *kg = qg + size_t(HD) * T, *vg = kg + size_t(HD) * T;
-    const float *dg = dout + (size_t(b) * HD + h * Dh) * T;
-    float *dqg = dqkv + (size_t(b) * 3 * HD + h * Dh) * T;
-    const float slope = slopes[h], inv = 1.f / scale_div;
-    const size_t so = (size_t(b) * H + h) * T;
-    for (int e = tid; e < Dh * AB_QB; e += 256) {
-        const int d = e / AB_QB, q = e - d * AB_QB, i = min(i0 + q, T - 1);
-        Qs[e] = qg[size_t(d) * T + i];
-        Os[e] = dg[size_t(d) * T + i];
-    }
-    constexpr int MAXA = 8;          // dQ elements per thread: Dh * 16 <= 128 * 16 = 8 * 256
-    float dq[MAXA];
-#pragma unroll
-    for (int u = 0; u < MAXA; ++u) dq[u] = 0.f;
-    for (int j0 = 0; j0 < T; j0 += AB_KB) {
-        __syncthreads();
-        for (int e = tid; e < Dh * AB_KB; e += 256) {
-            const int d = e / AB_KB, j = e - d * AB_KB, jc = min(j0 + j, T - 1);
-            Ks[e] = kg[size_t(d) * T + jc];
-            Vs[e] = vg[size_t(d) * T + jc];
-        }
-        __syncthreads();
-        for (int e = tid; e < AB_QB * AB_KB; e += 256) {
-            const int q = e / AB_KB, j = e - q * AB_KB, i = i0 + q;
-            float s = 0.f, dp = 0.f;
-            for (int d = 0; d < Dh; ++d) {
-                s = fmaf(Qs[d * AB_QB + q], Ks[d * AB_KB + j], s);
-                dp = fmaf(Os[d * AB_QB + q], Vs[d * AB_KB + j], dp);
-            }
-            float ds = 0.f;
-            if (i < T && j0 + j < T) {
-                const float pn = expf(attn_bwd_logit(s, inv, i - (j0 + j), slope) - lse[so + i]);
-                ds = pn * (dp - delta[so + i]) * inv;
-            }
-            Ss[e] = ds;
-        }
-        __syncthreads();
-#pragma unroll
-        for (int u = 0; u < MAXA; ++u) {
-            const int e = tid + u * 256;
-            if (e < Dh * AB_QB) {
-                const int d = e / AB_QB, q = e - d * AB_QB;
-                float a = dq[u];
-                for (int j = 0; j < AB_KB; ++j) a = fmaf(Ss[q * AB_KB + j], Ks[d * AB_KB + j], a);
-                dq[u] = a;
-            }
-        }
-    }
-#pragma unroll
-    for (int u = 0; u < MAXA; ++u) {
-        const int e = tid + u * 256;
-        if (e < Dh * AB_QB) {
-            const int d = e / AB_QB, q = e - d * AB_QB;
-            if (i0 + q < T) dqg[size_t(d) * T + i0 + q] = dq[u];
-        }
-    }
+    const int h = blockIdx.y, b = blockIdx.z;
+    attn_bwd_dq_body(self_view(qkv, dout, h, b, H, Dh, T), slopes, h, lse, delta, dqkv + (size_t(b) * 3 * (H * Dh) + h * Dh) * T, T,
+                     Dh, scale_div);
 }
 
-// one workgroup per (key block, head, item): dK and dV of its 64 keys, queries in blocks of 16
 __global__ __launch_bounds__(256) void attn_bwd_dkv_kernel(const float *__restrict__ qkv, const float *__restrict__ slopes,
                                                            const float *__restrict__ dout, const float *__restrict__ lse,
                                                            const float *__restrict__ delta, float *__restrict__ dqkv, int H,
                                                            int Dh, int T, float scale_div) {
-    extern __shared__ __attribute__((aligned(16))) float sm[];
-    float *Ks = sm;                  // [Dh][KB]
-    float *Vs = Ks + Dh * AB_KB;     // [Dh][KB]
-    float *Qs = Vs + Dh * AB_KB;     // [Dh][QB]
-    float *Os = Qs + Dh * AB_QB;     // [Dh][QB]
-    float *Ps = Os + Dh * AB_QB;     // [QB][KB]
-    float *Ss = Ps + AB_QB * AB_KB;  // [QB][KB]
-    const int tid = threadIdx.x, h = blockIdx.y, b = blockIdx.z, j0 = blockIdx.x * AB_KB;
-    const int HD = H * Dh;
-    const float *qg = qkv + (size_t(b) * 3 * HD + h * Dh) * T, *kg = qg + size_t(HD) * T, *vg = kg + size_t(HD) * T;
-    const float *dg = dout + (size_t(b) * HD + h * Dh) * T;
-    float *dkg = dqkv + (size_t(b) * 3 * HD + size_t(HD) + h * Dh) * T, *dvg = dkg + size_t(HD) * T;
-    const float slope = slopes[h], inv = 1.f / scale_div;
-    const size_t so = (size_t(b) * H + h) * T;
-    for (int e = tid; e < Dh * AB_KB; e += 256) {
-        const int d = e / AB_KB, j = e - d * AB_KB, jc = min(j0 + j, T - 1);
-        Ks[e] = kg[size_t(d) * T + jc];
-        Vs[e] = vg[size_t(d) * T + jc];
-    }
-    constexpr int MAXE = 32;         // dK / dV elements per thread: Dh * 64 <= 128 * 64 = 32 * 256
-    float dk[MAXE], dv[MAXE];
-#pragma unroll
-    for (int u = 0; u < MAXE; ++u) dk[u] = dv[u] = 0.f;
-    for (int i0 = 0; i0 < T; i0 += AB_QB) {
-        __syncthreads();
-        for (int e = tid; e < Dh * AB_QB; e += 256) {
-            const int d = e / AB_QB, q = e - d * AB_QB, i = min(i0 + q, T - 1);
-            Qs[e] = qg[size_t(d) * T + i];
-            Os[e] = (i0 + q < T) ? dg[size_t(d) * T + i] : 0.f;
-        }
-        __syncthreads();
-        for (int e = tid; e < AB_QB * AB_KB; e += 256) {
-            const int q = e / AB_KB, j = e - q * AB_KB, i = i0 + q;
-            float s = 0.f, dp = 0.f;
-            for (int d = 0; d < Dh; ++d) {
-                s = fmaf(Qs[d * AB_QB + q], Ks[d * AB_KB + j], s);
-                dp = fmaf(Os[d * AB_QB + q], Vs[d * AB_KB + j], dp);
-            }
-            float pn = 0.f, ds = 0.f;
-            if (i < T && j0 + j < T) {
-                pn = expf(attn_bwd_logit(s, inv, i - (j0 + j), slope) - lse[so + i]);
-                ds = pn * (dp - delta[so + i]) * inv;
-            }
-            Ps[e] = pn;
-            Ss[e] = ds;
-        }
-        __syncthreads();
-#pragma unroll
-        for (int u = 0; u < MAXE; ++u) {
-            const int e = tid + u * 256;
-            if (e < Dh * AB_KB) {
-                const int d = e / AB_KB, j = e - d * AB_KB;
-                float ak = dk[u], av = dv[u];
-#pragma unroll
-                for (int q = 0; q < AB_QB; ++q) {
-                    ak = fmaf(Ss[q * AB_KB + j], Qs[d * AB_QB + q], ak);
-                    av = fmaf(Ps[q * AB_KB + j], Os[d * AB_QB + q], av);
-                }
-                dk[u] = ak;
-                dv[u] = av;
-            }
-        }
-    }
-#pragma unroll
-    for (int u = 0; u < MAXE; ++u) {
-        const int e = tid + u * 256;
-        if (e < Dh * AB_KB) {
-            const int d = e / AB_KB, j = e - d * AB_KB;
-            if (j0 + j < T) {
-                dkg[size_t(d) * T + j0 + j] = dk[u];
-                dvg[size_t(d) * T + j0 + j] = dv[u];
-            }
-        }
-    }
-}
-
-int launch_attention_flash_backward(const float *qkv, const float *slopes, const float *out, const float *dout, float *dqkv,
-                                    float *workspace, int B, int H, int Dh, int T, float scale_div, hipStream_t st) {
-    float *lse = workspace, *delta = workspace + size_t(B) * H * T;
-    const dim3 gq(ceil_div(T, AB_QB), H, B), gk(ceil_div(T, AB_KB), H, B);
-    const size_t l_stats = size_t(2 * Dh * AB_QB + 2 * Dh * AB_KB + 2 * AB_QB * AB_KB) * sizeof(float);
-    const size_t l_dq = size_t(2 * Dh * AB_QB + 2 * Dh * AB_KB + AB_QB * AB_KB) * sizeof(float);
-    const size_t l_dkv = size_t(2 * Dh * AB_KB + 2 * Dh * AB_QB + 2 * AB_QB * AB_KB) * sizeof(float);
-    static DeviceOnce once[3];
-    {
-        const void *ks[3] = {reinterpret_cast<const void *>(attn_bwd_stats_kernel), reinterpret_cast<const void *>(attn_bwd_dq_kernel),
-                             reinterpret_cast<const void *>(attn_bwd_dkv_kernel)};
-        for (int i = 0; i < 3; ++i)
-            if (int rc = prepare_kernel(ks[i], once[i], 96 * 1024, nullptr, "attention_flash_backward")) return rc;   // head_dim 128: 90 KB
-    }
-    hipLaunchKernelGGL(attn_bwd_stats_kernel, gq, dim3(256), l_stats, st, qkv, slopes, out, dout, lse, delta, H, Dh, T, scale_div);
-    hipLaunchKernelGGL(attn_bwd_dq_kernel, gq, dim3(256), l_dq, st, qkv, slopes, dout, lse, delta, dqkv, H, Dh, T, scale_div);
-    hipLaunchKernelGGL(attn_bwd_dkv_kernel, gk, dim3(256), l_dkv, st, qkv, slopes, dout, lse, delta, dqkv, H, Dh, T, scale_div);
-    return check_launch("attention_flash_backward");
+    const int h = blockIdx.y, b = blockIdx.z, HD = H * Dh;
+    float *dkg = dqkv + (size_t(b) * 3 * HD + size_t(HD) + h * Dh) * T;
+    attn_bwd_dkv_body(self_view(qkv, dout, h, b, H, Dh, T), slopes, h, lse, delta, dkg, dkg + size_t(HD) * T, T, Dh, scale_div);
 }
 
 }  // namespace agx
@@ -704,8 +481,15 @@ int agx_attention_alibi_backward_ex(const float *qkv, const float *slopes, const
     if (k.code) return k.code;
     if (workspace_bytes < agx_attention_backward_workspace_bytes(batch, heads, t))
         return fail(AGX_ERR_WORKSPACE, "attention_alibi_backward_ex: workspace too small");
-    return launch_attention_flash_backward(qkv, slopes, out, dout, dqkv, workspace, batch, heads, head_dim, t, scale_div,
-                                           static_cast<hipStream_t>(stream));
+    float *lse = workspace, *delta = workspace + size_t(batch) * heads * t;
+    const auto dims = std::make_tuple(heads, head_dim, t, scale_div);
+    static DeviceOnce once[3];
+    return masked_launch_backward("attention_flash_backward", once, attn_bwd_stats_kernel, attn_bwd_dq_kernel, attn_bwd_dkv_kernel,
+                                  dim3(ceil_div(t, kAttnQB), heads, batch), dim3(ceil_div(t, kAttnKB), heads, batch), head_dim,
+                                  static_cast<hipStream_t>(stream),
+                                  std::tuple_cat(std::make_tuple(qkv, slopes, out, dout, lse, delta), dims),
+                                  std::tuple_cat(std::make_tuple(qkv, slopes, dout, lse, delta, dqkv), dims),
+                                  std::tuple_cat(std::make_tuple(qkv, slopes, dout, lse, delta, dqkv), dims));
 }
 
 }  // extern "C"

@@ -1,6 +1,9 @@
 // Masked ALiBi attention: the one forward body and the one backward trio behind the cross, causal, window, stream, ragged and
-// packed families (attention_{cross,causal,window,stream,ragged,packed}.hip), and the host scaffolding they share.
-// (One kernel is not an instance: the ragged forward, which measured slower as one; attention_ragged.hip says why.)
+// packed families (attention_{cross,causal,window,stream,ragged,packed}.hip), the dropout family (attention_dropout.hip: the cross
+// view behind batch strides, with a dropout policy) and the self-attention split backward (attention_flash.hip: the cross view on
+// the packed qkv layout), and the host scaffolding they share.
+// (One kernel is not an instance: the ragged forward, which measured slower as one; attention_ragged.hip says why.  The
+// self-attention forwards of attention_flash.hip / attention.hip, with their bf16 variants, are their own code.)
 //
 // Each family's file holds its __global__ kernels -- a few lines that build a View and call a body -- and its C entry points.
 // A View says what the families really differ in and nothing else:
@@ -197,13 +200,23 @@ static __device__ __forceinline__ float attn_score(float a, float inv, float b, 
     }
 }
 
+// Dropout on the probabilities is a policy of the bodies.  kDrop = false: no factor exists, and every line that would use one is
+// compiled out, so a family without dropout pays nothing for it.  A policy with kDrop = true (PhiloxDrop, attention_dropout.hip) answers
+//   live()              whether any pair is dropped at all (p > 0), a runtime test around the forward's hook;
+//   quartet(jq, i, f)   the factors (1 / (1 - p) or 0) of keys 4 jq .. 4 jq + 3 of query i, when live();
+//   factors(jq, i, f)   the same, or the scale for all four when not live() -- what the backward multiplies by either way.
+// The softmax statistics (m, l, lse) never see a factor: P is the softmax, P~ = f o P meets V and dO only.
+struct NoDrop {
+    static constexpr bool kDrop = false;
+};
+
 // --------------------------------------------------------------------------------------------------------- the forward
 // 128 queries per workgroup (one per lane of each wave's two halves), keys in blocks of 64: the query fragment in registers,
 // S^T = K^T Q and O^T += V P^T on the fp32-input MFMA, V double-buffered through LDS at pitch 65, the row statistics in-lane.
 // og: the out rows of this (item, head), pitch pd.  Dynamic LDS: 2 * 32 * DVT * 65 floats.
-template <int DVT, class View>
+template <int DVT, class View, class Drop = NoDrop>
 __device__ __forceinline__ void attn_fwd_body(const View &v, float *og, const float *slopes, int h, int Dh,
-                                              float scale_div) {
+                                              float scale_div, const Drop &drop = Drop{}) {
     constexpr int KB = kAttnKB;    // keys per block (two 32-key accumulator tiles)
     constexpr int DH = 32 * DVT;   // head_dim rounded up to the tile
     constexpr int VP = KB + 1;     // LDS pitch of the V block
@@ -212,6 +225,7 @@ __device__ __forceinline__ void attn_fwd_body(const View &v, float *og, const fl
     const auto pq = v.pq;   // the pitches as locals (see AttnView)
     const auto pk = v.pk;
     const auto pd = v.pd;
+    const Drop dr = drop;   // ... and the policy's fields
     const int li = lane & 31, lh = lane >> 5;
     const int q0 = blockIdx.x * 128;                   // this workgroup's first query
     if constexpr (View::kEarlyExit) {
@@ -302,7 +316,7 @@ __device__ __forceinline__ void attn_fwd_body(const View &v, float *og, const fl
             for (int r = 0; r < 16; ++r) {
                 const float pe = expf(acc[t2][r] - ms);   // masked: exp(-inf) = 0 exactly
                 acc[t2][r] = pe;
-                bl += pe;
+                bl += pe;                                 // m and l come from the UNMASKED exponentials: P is the softmax
             }
         bl += __shfl_xor(bl, 32);
         l = l * alpha + bl;
@@ -312,7 +326,22 @@ __device__ __forceinline__ void attn_fwd_body(const View &v, float *og, const fl
 #pragma unroll
             for (int r = 0; r < 16; ++r) o[dt][r] *= alpha;
 
-        // ---- O^T += V P^T : B operand = the probability registers ----
+        // ---- dropout: registers 4 g .. 4 g + 3 of a lane are the aligned key quartet j0 + 32 t2 + 8 g + 4 lh (acc_row) ----
+        if constexpr (Drop::kDrop) {
+            if (dr.live()) {
+#pragma unroll
+                for (int t2 = 0; t2 < 2; ++t2)
+#pragma unroll
+                    for (int g = 0; g < 4; ++g) {
+                        float f[4];
+                        dr.quartet(uint32_t(j0 + t2 * 32 + 8 * g + 4 * lh) >> 2, uint32_t(i), f);   // i: the unclamped query
+#pragma unroll
+                        for (int u = 0; u < 4; ++u) acc[t2][4 * g + u] *= f[u];
+                    }
+            }
+        }
+
+        // ---- O^T += V P~^T : B operand = the (masked) probability registers ----
 #pragma unroll
         for (int t2 = 0; t2 < 2; ++t2)
 #pragma unroll
@@ -344,14 +373,44 @@ __device__ __forceinline__ void attn_fwd_body(const View &v, float *og, const fl
 // between them.  lse is built from these values, and P = exp(logit - lse) is exactly 1 on a row that one key holds alone; a
 // logit near 100 rounded differently in two kernels would put 1e-5 of relative error into P instead.
 
+// The pair pass of all three, over the 16 x 64 tile: thread tid owns query qi = tid / 16 and the aligned keys jb .. jb + 3,
+// jb = 4 (tid % 16) -- Q / dO read once per four pairs, 16-byte reads of Ks / Vs, lse_i / delta_i loaded once, and one Philox call
+// where there is dropout.  s[u] = q_i . k_j and dp[u] = dO_i . v_j, each the fmaf chain over d; under dropout dp takes the pair's
+// factor f[u], one multiply on top (dP = f o (dO V^T)), and f is written; without, neither exists.  jq: the quartet
+// (j0 + jb) / 4; i: the unclamped query.  (An ownership of four scattered elements, tid + 256 k, gives every pair the same value
+// in the same LDS slot with 10 registers fewer, an occupancy step of the stats and dq kernels, and 1.6 times the time:
+// DESIGN.md 4.5.)
+template <class Drop>
+static __device__ __forceinline__ void attn_bwd_pair_dots(const float *Qs, const float *Os, const float *Ks, const float *Vs, int Dh,
+                                                          int qi, int jb, const Drop &dr, uint32_t jq, uint32_t i, float (&s)[4],
+                                                          float (&dp)[4], float (&f)[4]) {
+#pragma unroll
+    for (int u = 0; u < 4; ++u) s[u] = dp[u] = 0.f;
+    for (int d = 0; d < Dh; ++d) {
+        const float qv = Qs[d * kAttnQB + qi], ov = Os[d * kAttnQB + qi];
+        const f32x4 k4 = *reinterpret_cast<const f32x4 *>(Ks + d * kAttnKB + jb);
+        const f32x4 v4 = *reinterpret_cast<const f32x4 *>(Vs + d * kAttnKB + jb);
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+            s[u] = fmaf(qv, k4[u], s[u]);
+            dp[u] = fmaf(ov, v4[u], dp[u]);
+        }
+    }
+    if constexpr (Drop::kDrop) {
+        dr.factors(jq, i, f);
+#pragma unroll
+        for (int u = 0; u < 4; ++u) dp[u] *= f[u];
+    }
+}
+
 // One workgroup per (query block, head, item): lse and delta of its 16 queries; 0 for a query >= ql it owns.  delta_i =
 // sum_j P_ij dP_ij is summed online next to l, from dP values formed exactly as the dq and dkv kernels form them (the same fmaf
 // chain over d), not taken as sum_d dO[d,i] O[d,i] from the forward's output: where one key holds all of a row's weight,
 // dP_ij == delta_i must cancel to zero in dS = P (dP - delta), and two differently rounded dot products leave a residue that
 // K / scale multiplies into dQ.  Dynamic LDS: 2 Dh 16 + 2 Dh 64 + 2 * 16 * 64 floats.
-template <class View>
+template <class View, class Drop = NoDrop>
 __device__ __forceinline__ void attn_bwd_stats_body(const View &v, const float *slopes, int h, float *lse,
-                                                    float *delta, int Dh, float scale_div) {
+                                                    float *delta, int Dh, float scale_div, const Drop &drop = Drop{}) {
     constexpr int QB = kAttnQB, KB = kAttnKB;
     extern __shared__ __attribute__((aligned(16))) float sm[];
     float *Qs = sm;                 // [Dh][QB]
@@ -365,6 +424,7 @@ __device__ __forceinline__ void attn_bwd_stats_body(const View &v, const float *
     const auto pq = v.pq;   // the pitches as locals (see AttnView)
     const auto pk = v.pk;
     const auto pd = v.pd;
+    const Drop dr = drop;   // ... and the policy's fields
     if constexpr (View::kEarlyExit) {
         if (i0 >= v.ql || v.kl == 0) {      // workgroup-uniform, before the first barrier
             if (tid < QB && i0 + tid < v.q_end) lse[v.so + i0 + tid] = delta[v.so + i0 + tid] = 0.f;
@@ -377,7 +437,7 @@ __device__ __forceinline__ void attn_bwd_stats_body(const View &v, const float *
         Qs[e] = v.qg[size_t(d) * pq + i];
         Os[e] = v.dg[size_t(d) * pd + i];
     }
-    const int rq = tid / 16, rl = tid % 16;   // 16 threads per query row
+    const int rq = tid / 16, rl = tid % 16;   // 16 threads per query row; the pair pass: query rq, keys 4 rl .. 4 rl + 3
     float m = kAttnMasked, l = 0.f, dl = 0.f;
     const int jbeg = v.key_begin(i0), jend = v.key_end(i0);   // workgroup-uniform
     for (int j0 = jbeg; j0 < jend; j0 += KB) {
@@ -388,15 +448,16 @@ __device__ __forceinline__ void attn_bwd_stats_body(const View &v, const float *
             Vs[e] = v.vg[size_t(d) * pk + jc];
         }
         __syncthreads();
-        for (int e = tid; e < QB * KB; e += 256) {
-            const int qi = e / KB, j = e - qi * KB, i = v.stats_row(i0 + qi);
-            float s = 0.f, dp = 0.f;
-            for (int d = 0; d < Dh; ++d) {
-                s = fmaf(Qs[d * QB + qi], Ks[d * KB + j], s);
-                dp = fmaf(Os[d * QB + qi], Vs[d * KB + j], dp);
+        {
+            const int jb = 4 * rl, i = v.stats_row(i0 + rq);
+            float s[4], dp[4], f[4];
+            attn_bwd_pair_dots(Qs, Os, Ks, Vs, Dh, rq, jb, dr, uint32_t(j0 + jb) >> 2, uint32_t(i0 + rq), s, dp, f);
+#pragma unroll
+            for (int u = 0; u < 4; ++u) {
+                const int e = rq * KB + jb + u, j = j0 + jb + u;
+                Ds[e] = dp[u];
+                Ss[e] = v.visible(i, j) ? v.logit(s[u], inv, i, j, slope) : kAttnMasked;
             }
-            Ds[e] = dp;
-            Ss[e] = v.visible(i, j0 + j) ? v.logit(s, inv, i, j0 + j, slope) : kAttnMasked;
         }
         __syncthreads();
         float bm = kAttnMasked;
@@ -437,10 +498,10 @@ __device__ __forceinline__ void attn_bwd_stats_body(const View &v, const float *
 
 // One workgroup per (query block, head, item): dQ of its 16 queries, keys in blocks of 64 over [key_begin, key_end).
 // dqg: the dQ rows of this (item, head), pitch pdq.  Dynamic LDS: 2 Dh 16 + 2 Dh 64 + 16 * 64 floats.
-template <class View, class Pitch>
+template <class View, class Pitch, class Drop = NoDrop>
 __device__ __forceinline__ void attn_bwd_dq_body(const View &v, const float *slopes, int h, const float *lse,
                                                  const float *delta, float *dqg, Pitch pdq, int Dh,
-                                                 float scale_div) {
+                                                 float scale_div, const Drop &drop = Drop{}) {
     constexpr int QB = kAttnQB, KB = kAttnKB;
     extern __shared__ __attribute__((aligned(16))) float sm[];
     float *Qs = sm;                  // [Dh][QB]
@@ -452,6 +513,7 @@ __device__ __forceinline__ void attn_bwd_dq_body(const View &v, const float *slo
     const auto pq = v.pq;   // the pitches as locals (see AttnView)
     const auto pk = v.pk;
     const auto pd = v.pd;
+    const Drop dr = drop;   // ... and the policy's fields
     if constexpr (View::kEarlyExit) {
         if (i0 >= v.ql || v.kl == 0) {       // workgroup-uniform, before the first barrier: this block's dQ is 0
             if (i0 < v.q_end)
@@ -468,6 +530,12 @@ __device__ __forceinline__ void attn_bwd_dq_body(const View &v, const float *slo
         Qs[e] = v.qg[size_t(d) * pq + i];
         Os[e] = v.dg[size_t(d) * pd + i];
     }
+    const int rq = tid / 16, jb = 4 * (tid % 16), iq = i0 + rq;   // the pair pass: query iq, keys j0 + jb .. + 3
+    float lse_i = 0.f, delta_i = 0.f;
+    if (iq < v.ql) {
+        lse_i = lse[v.so + iq];
+        delta_i = delta[v.so + iq];
+    }
     constexpr int MAXA = 8;          // dQ elements per thread: Dh * 16 <= 128 * 16 = 8 * 256
     float dq[MAXA];
 #pragma unroll
@@ -481,19 +549,19 @@ __device__ __forceinline__ void attn_bwd_dq_body(const View &v, const float *slo
             Vs[e] = v.vg[size_t(d) * pk + jc];
         }
         __syncthreads();
-        for (int e = tid; e < QB * KB; e += 256) {
-            const int qi = e / KB, j = e - qi * KB, i = i0 + qi;
-            float s = 0.f, dp = 0.f;
-            for (int d = 0; d < Dh; ++d) {
-                s = fmaf(Qs[d * QB + qi], Ks[d * KB + j], s);
-                dp = fmaf(Os[d * QB + qi], Vs[d * KB + j], dp);
+        {
+            float s[4], dp[4], f[4];
+            attn_bwd_pair_dots(Qs, Os, Ks, Vs, Dh, rq, jb, dr, uint32_t(j0 + jb) >> 2, uint32_t(iq), s, dp, f);
+#pragma unroll
+            for (int u = 0; u < 4; ++u) {
+                const int j = j0 + jb + u;
+                float ds = 0.f;
+                if (iq < v.ql && v.visible(iq, j)) {     // a visible pair; every other one contributes exactly 0
+                    const float pn = expf(v.logit(s[u], inv, iq, j, slope) - lse_i);
+                    ds = pn * (dp[u] - delta_i) * inv;
+                }
+                Ss[rq * KB + jb + u] = ds;
             }
-            float ds = 0.f;
-            if (i < v.ql && v.visible(i, j0 + j)) {     // a visible pair; every other one contributes exactly 0
-                const float pn = expf(v.logit(s, inv, i, j0 + j, slope) - lse[v.so + i]);
-                ds = pn * (dp - delta[v.so + i]) * inv;
-            }
-            Ss[e] = ds;
         }
         __syncthreads();
 #pragma unroll
@@ -519,22 +587,23 @@ __device__ __forceinline__ void attn_bwd_dq_body(const View &v, const float *slo
 
 // One workgroup per (key block, head, item): dK and dV of its 64 keys, queries in blocks of 16 over [query_begin, query_end).
 // dkg / dvg: the dK and dV rows of this (item, head), pitch pdk.  Dynamic LDS: 2 Dh 64 + 2 Dh 16 + 2 * 16 * 64 floats.
-template <class View, class Pitch>
+template <class View, class Pitch, class Drop = NoDrop>
 __device__ __forceinline__ void attn_bwd_dkv_body(const View &v, const float *slopes, int h, const float *lse,
                                                   const float *delta, float *dkg, float *dvg,
-                                                  Pitch pdk, int Dh, float scale_div) {
+                                                  Pitch pdk, int Dh, float scale_div, const Drop &drop = Drop{}) {
     constexpr int QB = kAttnQB, KB = kAttnKB;
     extern __shared__ __attribute__((aligned(16))) float sm[];
     float *Ks = sm;                  // [Dh][KB]
     float *Vs = Ks + Dh * KB;        // [Dh][KB]
     float *Qs = Vs + Dh * KB;        // [Dh][QB]
     float *Os = Qs + Dh * QB;        // [Dh][QB]
-    float *Ps = Os + Dh * QB;        // [QB][KB]
-    float *Ss = Ps + QB * KB;        // [QB][KB]
+    float *Ps = Os + Dh * QB;        // [QB][KB]  P, under dropout P~ = f o P
+    float *Ss = Ps + QB * KB;        // [QB][KB]  dS / scale
     const int tid = threadIdx.x, j0 = blockIdx.x * KB;
     const auto pq = v.pq;   // the pitches as locals (see AttnView)
     const auto pk = v.pk;
     const auto pd = v.pd;
+    const Drop dr = drop;   // ... and the policy's fields
     if constexpr (View::kEarlyExit) {
         if (j0 >= v.kl || v.ql == 0) {       // workgroup-uniform, before the first barrier: this block's dK / dV are 0
             if (j0 < v.k_end)
@@ -551,6 +620,7 @@ __device__ __forceinline__ void attn_bwd_dkv_body(const View &v, const float *sl
         Ks[e] = v.kg[size_t(d) * pk + jc];
         Vs[e] = v.vg[size_t(d) * pk + jc];
     }
+    const int rq = tid / 16, jb = 4 * (tid % 16);   // the pair pass: query i0 + rq, keys j0 + jb .. + 3
     constexpr int MAXE = 32;         // dK / dV elements per thread: Dh * 64 <= 128 * 64 = 32 * 256
     float dk[MAXE], dv[MAXE];
 #pragma unroll
@@ -564,20 +634,28 @@ __device__ __forceinline__ void attn_bwd_dkv_body(const View &v, const float *sl
             Os[e] = (i0 + qi < v.ql) ? v.dg[size_t(d) * pd + i] : 0.f;   // a masked query's dO is never multiplied
         }
         __syncthreads();
-        for (int e = tid; e < QB * KB; e += 256) {
-            const int qi = e / KB, j = e - qi * KB, i = i0 + qi;
-            float s = 0.f, dp = 0.f;
-            for (int d = 0; d < Dh; ++d) {
-                s = fmaf(Qs[d * QB + qi], Ks[d * KB + j], s);
-                dp = fmaf(Os[d * QB + qi], Vs[d * KB + j], dp);
+        {
+            const int iq = i0 + rq;
+            float s[4], dp[4], f[4];
+            attn_bwd_pair_dots(Qs, Os, Ks, Vs, Dh, rq, jb, dr, uint32_t(j0 + jb) >> 2, uint32_t(iq), s, dp, f);
+            float lse_i = 0.f, delta_i = 0.f;
+            if (iq < v.ql) {
+                lse_i = lse[v.so + iq];
+                delta_i = delta[v.so + iq];
             }
-            float pn = 0.f, ds = 0.f;
-            if (i < v.ql && v.visible(i, j0 + j)) {
-                pn = expf(v.logit(s, inv, i, j0 + j, slope) - lse[v.so + i]);
-                ds = pn * (dp - delta[v.so + i]) * inv;
+#pragma unroll
+            for (int u = 0; u < 4; ++u) {
+                const int j = j0 + jb + u;
+                float pm = 0.f, ds = 0.f;
+                if (iq < v.ql && v.visible(iq, j)) {
+                    const float pn = expf(v.logit(s[u], inv, iq, j, slope) - lse_i);
+                    ds = pn * (dp[u] - delta_i) * inv;
+                    pm = pn;
+                    if constexpr (Drop::kDrop) pm = pn * f[u];
+                }
+                Ps[rq * KB + jb + u] = pm;
+                Ss[rq * KB + jb + u] = ds;
             }
-            Ps[e] = pn;
-            Ss[e] = ds;
         }
         __syncthreads();
 #pragma unroll

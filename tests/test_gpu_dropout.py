@@ -11,7 +11,7 @@ import numpy as np
 import pytest
 import torch
 
-from audio_generation_amd import ops
+from audio_generation_amd import AgxError, ops
 from oracle import attention as oattn
 from tests import philox
 from tests.dropout_ref import attention_factor, drop_core
@@ -142,6 +142,42 @@ def test_backward_against_float64_autograd(case, p):
         s_max, s_rms = float(want.abs().max()), float(want.pow(2).mean().sqrt())
         print(f"dropout backward {case} p={p} {name}: max err {e_max:.3e} (max {s_max:.3e}), rms err {e_rms:.3e} (rms {s_rms:.3e})")
         assert e_max < 5e-5 * max(1.0, s_max) and e_rms < 1e-5 * max(1.0, s_rms), name
+
+
+# ------------------------------------------------------------------------------------------------- 3b. one source
+# The dropout backward, the cross backward and the self-attention three-kernel backward are instances of the same three bodies
+# (csrc/attention_masked.hpp): where they compute the same thing, they compute the same bits.
+@pytest.mark.parametrize("case", [(1, 2, 64, 130, 70), (2, 2, 128, 17, 129), (2, 1, 8, 1, 1)], ids=_case_id)
+def test_p_zero_backward_is_the_cross_backward_bit_for_bit(case):
+    """A partial last key block, more than one query block, Tq > Tk (the relative logit is live), DVT 1 / 2 / 4.  At p = 0 every
+    factor is exactly 1.0f and every other operation is an explicit fmaf chain."""
+    b, heads, dh, tq, tk = case
+    q, kv, dout, slopes = (t.to(DEV) for t in _inputs(case))
+    out = ops.attention_alibi_cross(q, kv, slopes, heads, dh, dh ** 0.5)
+    want_dq, want_dkv = ops.attention_alibi_cross_backward(q, kv, slopes, out, dout, heads, dh, dh ** 0.5)
+    dq, dkv = ops.attention_alibi_dropout_backward(q, kv, slopes, out, dout, heads, dh, dh ** 0.5, 0.0, SEED, STREAM)
+    assert torch.equal(dq, want_dq), f"dq differs by {max_abs(dq, want_dq):.3e}"
+    assert torch.equal(dkv, want_dkv), f"dkv differs by {max_abs(dkv, want_dkv):.3e}"
+
+
+@pytest.mark.parametrize("dh,t", [(24, 257), (128, 130)], ids=["dh24xT257", "dh128xT130"])
+def test_self_attention_split_backward_is_the_cross_backward_bit_for_bit(dh, t):
+    """qkv split into q and kv, the result split the same way; T > 256 or head_dim > 64 selects the three-kernel path."""
+    b, heads = 1, 2
+    hd = heads * dh
+    gen = torch.Generator().manual_seed(1000 * t + dh)
+    qkv = (0.7 * torch.randn(b, 3 * hd, t, generator=gen)).to(DEV)
+    dout = torch.randn(b, hd, t, generator=gen).to(DEV)
+    slopes = oattn.alibi_slopes(heads).to(DEV)
+    assert ops.attention_backward_kernel_name(heads, dh, t, split=True) == "attn_bwd_stats+attn_bwd_dq+attn_bwd_dkv"
+    with pytest.raises(AgxError):
+        ops.attention_backward_kernel_name(heads, dh, t)          # no single-launch kernel for this shape
+    q, kv = qkv[:, :hd].contiguous(), qkv[:, hd:].contiguous()
+    out = ops.attention_alibi_cross(q, kv, slopes, heads, dh, dh ** 0.5)
+    want_dq, want_dkv = ops.attention_alibi_cross_backward(q, kv, slopes, out, dout, heads, dh, dh ** 0.5)
+    dqkv = ops.attention_alibi_backward(qkv, slopes, dout, heads, dh, dh ** 0.5, out=out)
+    assert torch.equal(dqkv[:, :hd], want_dq), f"dq differs by {max_abs(dqkv[:, :hd], want_dq):.3e}"
+    assert torch.equal(dqkv[:, hd:], want_dkv), f"dkv differs by {max_abs(dqkv[:, hd:], want_dkv):.3e}"
 
 
 # ------------------------------------------------------------------------------------------------- 4. elementwise
