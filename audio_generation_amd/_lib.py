@@ -284,6 +284,20 @@ SIGNATURES = {
                                             c_size_t]),
     "agx_ring_write_rate": (c_int, [c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_int32, c_void_p]),
     "agx_stream_mark_end": (c_int, [c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_void_p]),
+    # per-row frame counts: the uncounted signatures with the counts pointer behind pos / end (hist / out, x)
+    "agx_conv_stream_step_counted": (c_int, [c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, c_float, c_void_p, c_void_p,
+                                             c_void_p, c_int32, c_void_p, c_int32, c_void_p, c_int32, c_void_p, c_void_p, c_void_p,
+                                             c_int32, c_int32, c_int32, c_int64, c_void_p]),
+    "agx_ring_write_rate_counted": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_int32,
+                                            c_void_p]),
+    "agx_ring_write_pos_counted": (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_int64, c_void_p, c_void_p, c_int32, c_int32, c_int32,
+                                           c_int32, c_void_p]),
+    "agx_attention_alibi_stream_counted": (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_void_p,
+                                                   c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, c_float, c_void_p]),
+    "agx_stream_advance_counted": (c_int, [c_void_p, c_void_p, c_int32, c_int64, c_void_p]),
+    "agx_glu_dwconv_step_counted": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_float, c_void_p,
+                                            c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_void_p]),
+    "agx_mask_tail_counted": (c_int, [c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_void_p]),
 }
 
 _lib = None

@@ -22,6 +22,11 @@ namespace agx {
 
 // the valid length of batch row b: clamp(len[b], 0, t); NULL: the full row
 static __device__ __forceinline__ int ragged_len(const int32_t *len, int b, int t) { return len ? min(max(int(len[b]), 0), t) : t; }
+// the int64 frame counts of a counted streaming step, clamped the same way
+static __device__ __forceinline__ int ragged_len(const int64_t *len, int b, int t) {
+    const int64_t v = len[b];
+    return int(v < 0 ? 0 : v > t ? t : v);
+}
 
 using RaggedView = AttnView<SymMask<true>>;
 
@@ -222,8 +227,9 @@ __global__ __launch_bounds__(256) void attn_ragged_bwd_dkv_kernel(const float *_
 // out[b,c,i] = i < clamp(len[b], 0, T) ? x[b,c,i] : 0 over a contiguous (B, C, T) tensor: a select, so a NaN tail gives 0.
 // A thread owns four consecutive elements of the flat tensor (one 16-byte access when both pointers allow it), reads all of
 // them before it writes any: out may alias x.  x and out are deliberately not __restrict__.
-__global__ __launch_bounds__(256) void mask_tail_kernel(const float *x, const int32_t *__restrict__ len, float *out, int64_t n, int C,
-                                                        int T, int vec) {
+template <typename L>   // int32_t: the lengths of a ragged batch; int64_t: the counts of a counted streaming step
+__global__ __launch_bounds__(256) void mask_tail_kernel(const float *x, const L *__restrict__ len, float *out, int64_t n, int C, int T,
+                                                        int vec) {
     const int64_t e0 = (int64_t(blockIdx.x) * 256 + threadIdx.x) * 4;
     if (e0 >= n) return;
     int64_t row = e0 / T;            // b * C + c
@@ -261,6 +267,20 @@ static const char *const kAttnRaggedBwdName = "attn_ragged_bwd_stats+attn_ragged
 
 static MaskedPick attn_ragged_pick(const char *op, int B, int H, int Dh, int Tq, int Tk) {
     return masked_pick(op, B <= 0 || H <= 0 || Tq <= 0 || Tk <= 0, masked_head_dim(op, Dh), Dh, ceil_div(Tq, 128), H, B);
+}
+
+template <typename L>
+static int mask_tail(const char *op, const float *x, const L *len, float *out, int32_t batch, int32_t channels, int32_t t, void *stream) {
+    if (batch <= 0 || channels <= 0 || t <= 0) return AGX_OK;
+    const int64_t n = int64_t(batch) * channels * t;
+    const int64_t blocks = ceil_div64(ceil_div64(n, 4), 256);
+    if (blocks > 0x7fffffff || int64_t(batch) * channels > 0x7fffffff)
+        return fail(AGX_ERR_BAD_SHAPE, "%s: (%d, %d, %d) is beyond the grid", op, batch, channels, t);
+    if (!x || !out) return fail(AGX_ERR_NULL_POINTER, "%s: NULL pointer", op);   // len: NULL = every row is full
+    const int vec = ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(out)) & 15) == 0;
+    hipLaunchKernelGGL(mask_tail_kernel<L>, dim3(unsigned(blocks)), dim3(256), 0, static_cast<hipStream_t>(stream), x, len, out, n, channels,
+                       t, vec);
+    return check_launch(op);
 }
 
 }  // namespace agx
@@ -326,17 +346,12 @@ int agx_attention_ragged_kernel_name(int32_t batch, int32_t heads, int32_t head_
 }
 
 int agx_mask_tail(const float *x, const int32_t *len, float *out, int32_t batch, int32_t channels, int32_t t, void *stream) {
-    using namespace agx;
-    if (batch <= 0 || channels <= 0 || t <= 0) return AGX_OK;
-    const int64_t n = int64_t(batch) * channels * t;
-    const int64_t blocks = ceil_div64(ceil_div64(n, 4), 256);
-    if (blocks > 0x7fffffff || int64_t(batch) * channels > 0x7fffffff)
-        return fail(AGX_ERR_BAD_SHAPE, "mask_tail: (%d, %d, %d) is beyond the grid", batch, channels, t);
-    if (!x || !out) return fail(AGX_ERR_NULL_POINTER, "mask_tail: NULL pointer");   // len: NULL = every row is full
-    const int vec = ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(out)) & 15) == 0;
-    hipLaunchKernelGGL(mask_tail_kernel, dim3(unsigned(blocks)), dim3(256), 0, static_cast<hipStream_t>(stream), x, len, out, n, channels, t,
-                       vec);
-    return check_launch("mask_tail");
+    return agx::mask_tail("mask_tail", x, len, out, batch, channels, t, stream);
+}
+
+int agx_mask_tail_counted(const float *x, const int64_t *counts, float *out, int32_t batch, int32_t channels, int32_t t, void *stream) {
+    if (!counts && batch > 0 && channels > 0 && t > 0) return agx::fail(AGX_ERR_NULL_POINTER, "mask_tail_counted: NULL counts");
+    return agx::mask_tail("mask_tail_counted", x, counts, out, batch, channels, t, stream);
 }
 
 }  // extern "C"

@@ -394,12 +394,23 @@ __device__ inline int quot(int i, float inv) { return int((float(i) + 0.5f) * in
 // takes the output (row0 + e / n, e % n) -- the fma chain of kernel 1 on the same values, then the eval normalisation and SiLU --
 // and the image's last K - 1 floats go back to hist.  rows = B C < 2^31: row arithmetic is 32-bit.  Every read of hist is before the barrier, every write behind it, and no
 // other workgroup touches these rows.
+//
+// CNT, the counted form: batch entry b takes its first cnt = clamp(counts[b], 0, n) frames.  A workgroup holds rows of several
+// batch entries, so the count is per thread and nobody returns early.  Outputs at t >= cnt are exact 0 (a select); the new history
+// is the image's K - 1 floats from cnt on, the last K - 1 values of [hist | first cnt chunk values], and is not written at all
+// where cnt == 0.  An output t < cnt and the new history read image columns below H + cnt only: what u holds past the count (NaN
+// included) reaches neither.  The uncounted instance compiles the count out.
+template <bool CNT>
 __global__ __launch_bounds__(256) void glu_dwconv_step_kernel(const float *__restrict__ u, const float *__restrict__ w,
                                                               const float *__restrict__ bias, const float *__restrict__ gamma,
                                                               const float *__restrict__ beta, const float *__restrict__ mean,
                                                               const float *__restrict__ var, float eps, float *hist,
-                                                              float *__restrict__ out, int C, int n, int K, int R, int rows, float inv_n,
-                                                              float inv_h, float inv_k) {
+                                                              float *__restrict__ out, const int64_t *__restrict__ counts, int C, int n,
+                                                              int K, int R, int rows, float inv_n, float inv_h, float inv_k) {
+    auto count_of = [&](unsigned row) {      // the frames the row's batch entry takes
+        const int64_t cb = counts[row / unsigned(C)];
+        return int(cb < 0 ? 0 : cb > n ? n : cb);
+    };
     extern __shared__ float step_lds[];
     const int H = K - 1, stride = (H + n) | 1, wstride = K | 1;
     float *img = step_lds, *sw = step_lds + R * stride;
@@ -408,7 +419,7 @@ __global__ __launch_bounds__(256) void glu_dwconv_step_kernel(const float *__res
     // this thread's output (R n <= 256: one each) and its channel's constants: their loads are in flight with the fills
     const int e = threadIdx.x;
     const bool mine = e < nr * n;
-    int r = 0, t = 0, c = 0;
+    int r = 0, t = 0, c = 0, cnt = n;
     float bc = 0.f;
     Norm nm{};
     if (mine) {
@@ -416,6 +427,7 @@ __global__ __launch_bounds__(256) void glu_dwconv_step_kernel(const float *__res
         t = e - r * n;
         const unsigned row = unsigned(row0 + r), b = row / unsigned(C);
         c = int(row - b * unsigned(C));
+        if (CNT) cnt = count_of(row);
         bc = bias[c];
         nm = norm_of(gamma, beta, mean, var, eps, c, 0);
         const float *ua = u + (int64_t(b) * 2 * C + c) * n;
@@ -434,13 +446,16 @@ __global__ __launch_bounds__(256) void glu_dwconv_step_kernel(const float *__res
     __syncthreads();
     for (int i = (threadIdx.x + 128) & 255; i < nr * H; i += 256) {
         const int ri = quot(i, inv_h);
-        hist[int64_t(row0) * H + i] = img[ri * stride + n + (i - ri * H)];
+        const int ci = CNT ? count_of(unsigned(row0 + ri)) : n;
+        if (CNT && ci == 0) continue;
+        hist[int64_t(row0) * H + i] = img[ri * stride + ci + (i - ri * H)];
     }
     if (mine) {
         const float *wc = sw + r * wstride, *sg = img + r * stride + t;
         float z = bc;
         for (int k = 0; k < K; ++k) z = fmaf(wc[k], sg[k], z);
-        out[int64_t(row0) * n + e] = siluf(act_of(z, nm));
+        const float y = siluf(act_of(z, nm));
+        out[int64_t(row0) * n + e] = CNT && t >= cnt ? 0.f : y;
     }
 }
 
@@ -671,21 +686,39 @@ int agx_glu_dwconv_causal_backward(const float *dz, const float *u, const float 
                                stream);
 }
 
-int agx_glu_dwconv_step(const float *u, const float *w, const float *bias, const float *gamma, const float *beta, const float *mean,
-                        const float *var, float eps, float *hist, float *out, int32_t B, int32_t C, int32_t n, int32_t K, void *stream) {
-    if (B <= 0 || C <= 0) return fail(AGX_ERR_BAD_SHAPE, "glu_dwconv_step: (B, C) = (%d, %d)", B, C);
-    if (n < 1 || n > kMaxStep) return fail(AGX_ERR_BAD_SHAPE, "glu_dwconv_step: n = %d is outside [1, %d]", n, kMaxStep);
-    if (K < 1 || K > kMaxK) return fail(AGX_ERR_BAD_SHAPE, "glu_dwconv_step: K = %d is outside [1, %d]", K, kMaxK);
+static int glu_dwconv_step(const char *op, const float *u, const float *w, const float *bias, const float *gamma, const float *beta,
+                           const float *mean, const float *var, float eps, float *hist, float *out, const int64_t *counts, int32_t B,
+                           int32_t C, int32_t n, int32_t K, void *stream) {
+    if (B <= 0 || C <= 0) return fail(AGX_ERR_BAD_SHAPE, "%s: (B, C) = (%d, %d)", op, B, C);
+    if (n < 1 || n > kMaxStep) return fail(AGX_ERR_BAD_SHAPE, "%s: n = %d is outside [1, %d]", op, n, kMaxStep);
+    if (K < 1 || K > kMaxK) return fail(AGX_ERR_BAD_SHAPE, "%s: K = %d is outside [1, %d]", op, K, kMaxK);
     const int64_t rows = int64_t(B) * C;
-    if (rows > kMaxGrid) return fail(AGX_ERR_BAD_SHAPE, "glu_dwconv_step: (%d, %d, %d) exceeds the grid", B, C, n);
+    if (rows > kMaxGrid) return fail(AGX_ERR_BAD_SHAPE, "%s: (%d, %d, %d) exceeds the grid", op, B, C, n);
     const int R = step_rows(rows, n, K);
     if (!u || !w || !bias || !gamma || !beta || !mean || !var || !out || (K > 1 && !hist))
-        return fail(AGX_ERR_NULL_POINTER, "glu_dwconv_step: NULL pointer (the step is the eval form: every statistic, and hist for K > 1)");
+        return fail(AGX_ERR_NULL_POINTER, "%s: NULL pointer (the step is the eval form: every statistic, and hist for K > 1)", op);
     const size_t lds = size_t(R) * (((K - 1 + n) | 1) + (K | 1)) * sizeof(float);
-    hipLaunchKernelGGL(glu_dwconv_step_kernel, dim3(unsigned(ceil_div64(rows, R))), dim3(256), lds, static_cast<hipStream_t>(stream), u,
-                       w, bias, gamma, beta, mean, var, eps, hist, out, C, n, K, R, int(rows), 1.f / float(n), K > 1 ? 1.f / float(K - 1) : 0.f,
-                       1.f / float(K));
-    return check_launch("agx_glu_dwconv_step");
+    const dim3 grid(unsigned(ceil_div64(rows, R)));
+    const float inv_n = 1.f / float(n), inv_h = K > 1 ? 1.f / float(K - 1) : 0.f, inv_k = 1.f / float(K);
+    if (counts)
+        hipLaunchKernelGGL(glu_dwconv_step_kernel<true>, grid, dim3(256), lds, static_cast<hipStream_t>(stream), u, w, bias, gamma, beta,
+                           mean, var, eps, hist, out, counts, C, n, K, R, int(rows), inv_n, inv_h, inv_k);
+    else
+        hipLaunchKernelGGL(glu_dwconv_step_kernel<false>, grid, dim3(256), lds, static_cast<hipStream_t>(stream), u, w, bias, gamma, beta,
+                           mean, var, eps, hist, out, counts, C, n, K, R, int(rows), inv_n, inv_h, inv_k);
+    return check_launch(op);
+}
+
+int agx_glu_dwconv_step(const float *u, const float *w, const float *bias, const float *gamma, const float *beta, const float *mean,
+                        const float *var, float eps, float *hist, float *out, int32_t B, int32_t C, int32_t n, int32_t K, void *stream) {
+    return glu_dwconv_step("glu_dwconv_step", u, w, bias, gamma, beta, mean, var, eps, hist, out, nullptr, B, C, n, K, stream);
+}
+
+int agx_glu_dwconv_step_counted(const float *u, const float *w, const float *bias, const float *gamma, const float *beta,
+                                const float *mean, const float *var, float eps, float *hist, float *out, const int64_t *counts, int32_t B,
+                                int32_t C, int32_t n, int32_t K, void *stream) {
+    if (!counts) return fail(AGX_ERR_NULL_POINTER, "glu_dwconv_step_counted: NULL counts");
+    return glu_dwconv_step("glu_dwconv_step_counted", u, w, bias, gamma, beta, mean, var, eps, hist, out, counts, B, C, n, K, stream);
 }
 
 int agx_glu_hist_update(const float *u, float *hist, int32_t B, int32_t C, int32_t T, int32_t K, void *stream) {

@@ -18,6 +18,8 @@ struct StreamArgs {
     const float *W, *bias, *src, *res;
     float *dst;
     const int64_t *pos, *end;
+    const int64_t *counts;   // counted form: row b takes its first clamp(counts[b], 0, n) frames
+    int n;                   // frames of the step
     int Cin, Cout, M, q, J, s, d, P;
     int nt;            // base positions of the step (n * rt)
     int rt;            // base positions per frame
@@ -35,7 +37,10 @@ __device__ __forceinline__ int floor_mod(int64_t a, int cap) {
     return int(r < 0 ? r + cap : r);
 }
 
-template <int KS, int NT>
+// CNT, the counted form (include/agx.h "Per-row frame counts"): row b takes lim = clamp(counts[b], 0, n) rt of the step's base
+// positions.  The count only decides which outputs are stored -- a plain destination gets exact 0 past lim, a ring destination is
+// left alone -- never what a chain is: KS, NT and the grid are those of the uncounted step.  The uncounted instances compile it out.
+template <int KS, int NT, bool CNT>
 __global__ __launch_bounds__(64 * KS) void conv_stream_kernel(const StreamArgs a) {
     __shared__ float red[KS > 1 ? KS * NT * 64 : 1];
     const int lane = threadIdx.x & 63;
@@ -45,6 +50,19 @@ __global__ __launch_bounds__(64 * KS) void conv_stream_kernel(const StreamArgs a
     const int tb = blockIdx.y * NT;
     const int64_t t0 = a.pos[b] * a.rt - a.Dt;           // workgroup-uniform
     const int mr = m < a.M ? m : a.M - 1;               // lanes past the last row repeat it and store nothing
+    int lim = a.nt;                                      // workgroup-uniform: the base positions row b takes
+    if (CNT) {
+        const int64_t c = a.counts[b];
+        lim = int(c < 0 ? 0 : c > a.n ? a.n : c) * a.rt;
+        if (tb >= lim) {      // nothing of this tile is taken: the whole workgroup leaves here, before the KS > 1 barrier
+            if (!a.dst_cap && ks == 0 && m < a.M) {
+                const int co = m / a.q, ph = m - co * a.q;
+                for (int i = 0; i < NT && tb + i < a.nt; ++i)
+                    a.dst[(size_t(b) * a.Cout + co) * (size_t(a.nt) * a.q) + (tb + i) * a.q + ph] = 0.f;
+            }
+            return;
+        }
+    }
 
     // The NV = 16 NT activation values of one (g, j) -- 16 channels x NT columns -- are loaded once per wave, value v = c NT + i by
     // lane (v mod 64) into register (v / 64), and broadcast to the fmaf chain by v_readlane: 6 memory instructions per (g, j)
@@ -131,6 +149,10 @@ __global__ __launch_bounds__(64 * KS) void conv_stream_kernel(const StreamArgs a
 #pragma unroll
     for (int i = 0; i < NT; ++i) {
         if (tb + i >= a.nt) break;
+        if (CNT && tb + i >= lim) {                      // past the row's count: zero to a plain tensor, a ring is not written
+            if (!a.dst_cap) a.dst[(size_t(b) * a.Cout + co) * n_out + (tb + i) * a.q + ph] = 0.f;
+            continue;
+        }
         const int64_t jo = (t0 + tb + i) * a.q + ph;     // the output's stream index
         float v = acc[i] + bias;
         if (a.epilogue & AGX_EPI_LEAKY_PRE) v = v > 0.f ? v : v * a.slope;
@@ -144,13 +166,20 @@ __global__ __launch_bounds__(64 * KS) void conv_stream_kernel(const StreamArgs a
     }
 }
 
-// buf[b, c, (pos[b] * rate + t) mod cap] = src[b, c, t], t < n_cols: a stack's input chunk into its first ring
+// buf[b, c, (pos[b] * rate + t) mod cap] = src[b, c, t], t < n_cols: a stack's input chunk into its first ring.  CNT: only the
+// columns of the row's first clamp(counts[b], 0, n_cols / rate) frames; the others are neither read nor written.
+template <bool CNT>
 __global__ __launch_bounds__(256) void ring_write_rate_kernel(float *__restrict__ buf, const float *__restrict__ src,
-                                                              const int64_t *__restrict__ pos, int C, int n_cols, int cap, int rate) {
+                                                              const int64_t *__restrict__ pos, const int64_t *__restrict__ counts, int C,
+                                                              int n_cols, int cap, int rate) {
     const int b = blockIdx.y;
     const int e = blockIdx.x * 256 + threadIdx.x;
     if (e >= C * n_cols) return;
     const int c = e / n_cols, t = e - c * n_cols;
+    if (CNT) {
+        const int64_t cb = counts[b], n = n_cols / rate;
+        if (t >= int(cb < 0 ? 0 : cb > n ? n : cb) * rate) return;
+    }
     buf[(size_t(b) * C + c) * cap + floor_mod(pos[b] * rate + t, cap)] = src[size_t(b) * C * n_cols + e];
 }
 
@@ -243,25 +272,31 @@ static StreamPick stream_pick(const char *op, int kind, int c_in, int c_out, int
     return k;
 }
 
-template <int KS>
+template <int KS, bool CNT>
 static void stream_launch_nt(const StreamPick &k, dim3 grid, hipStream_t st) {
     switch (k.nt_tile) {
-        case 1: hipLaunchKernelGGL((conv_stream_kernel<KS, 1>), grid, dim3(64 * KS), 0, st, k.a); break;
-        case 4: hipLaunchKernelGGL((conv_stream_kernel<KS, 4>), grid, dim3(64 * KS), 0, st, k.a); break;
-        default: hipLaunchKernelGGL((conv_stream_kernel<KS, 8>), grid, dim3(64 * KS), 0, st, k.a); break;
+        case 1: hipLaunchKernelGGL((conv_stream_kernel<KS, 1, CNT>), grid, dim3(64 * KS), 0, st, k.a); break;
+        case 4: hipLaunchKernelGGL((conv_stream_kernel<KS, 4, CNT>), grid, dim3(64 * KS), 0, st, k.a); break;
+        default: hipLaunchKernelGGL((conv_stream_kernel<KS, 8, CNT>), grid, dim3(64 * KS), 0, st, k.a); break;
     }
 }
 
-}  // namespace agx
+template <bool CNT>
+static void stream_launch(const StreamPick &k, dim3 grid, hipStream_t st) {
+    switch (k.ks) {
+        case 1: stream_launch_nt<1, CNT>(k, grid, st); break;
+        case 2: stream_launch_nt<2, CNT>(k, grid, st); break;
+        case 4: stream_launch_nt<4, CNT>(k, grid, st); break;
+        case 8: stream_launch_nt<8, CNT>(k, grid, st); break;
+        default: stream_launch_nt<16, CNT>(k, grid, st); break;
+    }
+}
 
-extern "C" {
-
-int agx_conv_stream_step(int32_t kind, int32_t c_in, int32_t c_out, int32_t kernel, int32_t stride, int32_t dilation, int32_t epilogue,
-                         float slope, const float *packed, const float *bias, const float *src, int32_t src_cap, const float *res,
-                         int32_t res_cap, float *dst, int32_t dst_cap, const int64_t *pos, const int64_t *end, int32_t batch, int32_t n,
-                         int32_t rate_in, int64_t delay_in, void *stream) {
-    using namespace agx;
-    const char *op = "conv_stream_step";
+// The one launcher of both entry points: counts == nullptr is the uncounted step, the instances without the count.
+static int stream_step(const char *op, int32_t kind, int32_t c_in, int32_t c_out, int32_t kernel, int32_t stride, int32_t dilation,
+                       int32_t epilogue, float slope, const float *packed, const float *bias, const float *src, int32_t src_cap,
+                       const float *res, int32_t res_cap, float *dst, int32_t dst_cap, const int64_t *pos, const int64_t *end,
+                       const int64_t *counts, int32_t batch, int32_t n, int32_t rate_in, int64_t delay_in, void *stream) {
     StreamPick k = stream_pick(op, kind, c_in, c_out, kernel, stride, dilation, batch, n, rate_in, delay_in);
     if (k.code) return k.code;
     if (k.empty) return AGX_OK;
@@ -286,17 +321,54 @@ int agx_conv_stream_step(int32_t kind, int32_t c_in, int32_t c_out, int32_t kern
     if (!packed || !src || !dst || !pos) return fail(AGX_ERR_NULL_POINTER, "%s: NULL pointer", op);
     if (dst == src || dst == res) return fail(AGX_ERR_BAD_SHAPE, "%s: the destination is one of the sources", op);
     a.W = packed, a.bias = bias, a.src = src, a.res = (epilogue & AGX_EPI_RESIDUAL) ? res : nullptr, a.dst = dst, a.pos = pos, a.end = end;
+    a.counts = counts, a.n = n;
     a.src_cap = src_cap, a.res_cap = res_cap, a.dst_cap = dst_cap, a.epilogue = epilogue, a.slope = slope;
     const dim3 grid(ceil_div(a.M, 64), ceil_div(a.nt, k.nt_tile), batch);
     hipStream_t st = static_cast<hipStream_t>(stream);
-    switch (k.ks) {
-        case 1: stream_launch_nt<1>(k, grid, st); break;
-        case 2: stream_launch_nt<2>(k, grid, st); break;
-        case 4: stream_launch_nt<4>(k, grid, st); break;
-        case 8: stream_launch_nt<8>(k, grid, st); break;
-        default: stream_launch_nt<16>(k, grid, st); break;
-    }
+    if (counts)
+        stream_launch<true>(k, grid, st);
+    else
+        stream_launch<false>(k, grid, st);
     return check_launch(op);
+}
+
+static int ring_write_rate(const char *op, float *buf, const float *src, const int64_t *pos, const int64_t *counts, int32_t batch,
+                           int32_t rows, int32_t n_cols, int32_t cap, int32_t rate, void *stream) {
+    if (batch <= 0 || rows <= 0 || n_cols <= 0) return AGX_OK;
+    if (batch > 65535) return fail(AGX_ERR_BAD_SHAPE, "%s: grid too large", op);
+    if (rate < 1) return fail(AGX_ERR_BAD_SHAPE, "%s: rate=%d < 1", op, rate);
+    if (n_cols > cap) return fail(AGX_ERR_BAD_SHAPE, "%s: n_cols=%d > cap=%d (a column would be written twice)", op, n_cols, cap);
+    if (int64_t(rows) * n_cols + 256 > 0x7fffffffLL) return fail(AGX_ERR_BAD_SHAPE, "%s: rows * n_cols is beyond int32", op);
+    if (!buf || !src || !pos) return fail(AGX_ERR_NULL_POINTER, "%s: NULL pointer", op);
+    const dim3 grid(ceil_div(rows * n_cols, 256), batch);
+    if (counts)
+        hipLaunchKernelGGL(ring_write_rate_kernel<true>, grid, dim3(256), 0, static_cast<hipStream_t>(stream), buf, src, pos, counts, rows,
+                           n_cols, cap, rate);
+    else
+        hipLaunchKernelGGL(ring_write_rate_kernel<false>, grid, dim3(256), 0, static_cast<hipStream_t>(stream), buf, src, pos, counts, rows,
+                           n_cols, cap, rate);
+    return check_launch(op);
+}
+
+}  // namespace agx
+
+extern "C" {
+
+int agx_conv_stream_step(int32_t kind, int32_t c_in, int32_t c_out, int32_t kernel, int32_t stride, int32_t dilation, int32_t epilogue,
+                         float slope, const float *packed, const float *bias, const float *src, int32_t src_cap, const float *res,
+                         int32_t res_cap, float *dst, int32_t dst_cap, const int64_t *pos, const int64_t *end, int32_t batch, int32_t n,
+                         int32_t rate_in, int64_t delay_in, void *stream) {
+    return agx::stream_step("conv_stream_step", kind, c_in, c_out, kernel, stride, dilation, epilogue, slope, packed, bias, src, src_cap, res,
+                            res_cap, dst, dst_cap, pos, end, nullptr, batch, n, rate_in, delay_in, stream);
+}
+
+int agx_conv_stream_step_counted(int32_t kind, int32_t c_in, int32_t c_out, int32_t kernel, int32_t stride, int32_t dilation,
+                                 int32_t epilogue, float slope, const float *packed, const float *bias, const float *src, int32_t src_cap,
+                                 const float *res, int32_t res_cap, float *dst, int32_t dst_cap, const int64_t *pos, const int64_t *end,
+                                 const int64_t *counts, int32_t batch, int32_t n, int32_t rate_in, int64_t delay_in, void *stream) {
+    if (!counts && batch > 0 && n > 0) return agx::fail(AGX_ERR_NULL_POINTER, "conv_stream_step_counted: NULL counts");
+    return agx::stream_step("conv_stream_step_counted", kind, c_in, c_out, kernel, stride, dilation, epilogue, slope, packed, bias, src,
+                            src_cap, res, res_cap, dst, dst_cap, pos, end, counts, batch, n, rate_in, delay_in, stream);
 }
 
 int agx_conv_stream_kernel_name(int32_t kind, int32_t c_in, int32_t c_out, int32_t kernel, int32_t stride, int32_t dilation, int32_t n,
@@ -314,17 +386,13 @@ int agx_conv_stream_kernel_name(int32_t kind, int32_t c_in, int32_t c_out, int32
 
 int agx_ring_write_rate(float *buf, const float *src, const int64_t *pos, int32_t batch, int32_t rows, int32_t n_cols, int32_t cap,
                         int32_t rate, void *stream) {
-    using namespace agx;
-    const char *op = "ring_write_rate";
-    if (batch <= 0 || rows <= 0 || n_cols <= 0) return AGX_OK;
-    if (batch > 65535) return fail(AGX_ERR_BAD_SHAPE, "%s: grid too large", op);
-    if (rate < 1) return fail(AGX_ERR_BAD_SHAPE, "%s: rate=%d < 1", op, rate);
-    if (n_cols > cap) return fail(AGX_ERR_BAD_SHAPE, "%s: n_cols=%d > cap=%d (a column would be written twice)", op, n_cols, cap);
-    if (int64_t(rows) * n_cols + 256 > 0x7fffffffLL) return fail(AGX_ERR_BAD_SHAPE, "%s: rows * n_cols is beyond int32", op);
-    if (!buf || !src || !pos) return fail(AGX_ERR_NULL_POINTER, "%s: NULL pointer", op);
-    hipLaunchKernelGGL(ring_write_rate_kernel, dim3(ceil_div(rows * n_cols, 256), batch), dim3(256), 0, static_cast<hipStream_t>(stream),
-                       buf, src, pos, rows, n_cols, cap, rate);
-    return check_launch(op);
+    return agx::ring_write_rate("ring_write_rate", buf, src, pos, nullptr, batch, rows, n_cols, cap, rate, stream);
+}
+
+int agx_ring_write_rate_counted(float *buf, const float *src, const int64_t *pos, const int64_t *counts, int32_t batch, int32_t rows,
+                                int32_t n_cols, int32_t cap, int32_t rate, void *stream) {
+    if (!counts && batch > 0 && rows > 0 && n_cols > 0) return agx::fail(AGX_ERR_NULL_POINTER, "ring_write_rate_counted: NULL counts");
+    return agx::ring_write_rate("ring_write_rate_counted", buf, src, pos, counts, batch, rows, n_cols, cap, rate, stream);
 }
 
 int agx_stream_mark_end(const int64_t *pos, int64_t *end, const int64_t *rows, int32_t n_rows, int32_t batch, void *stream) {

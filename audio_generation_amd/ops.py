@@ -759,20 +759,29 @@ def attention_alibi_ragged_backward(q: Tensor, kv: Optional[Tensor], slopes: Ten
     return dq if kv is None else (dq, dkv)
 
 
-def mask_tail(x: Tensor, lengths: Optional[Tensor], out: Optional[Tensor] = None) -> Tensor:
+def mask_tail(x: Tensor, lengths: Optional[Tensor], out: Optional[Tensor] = None, *, counts: Optional[Tensor] = None) -> Tensor:
     """``out[b, c, i] = x[b, c, i] if i < lengths[b] else 0`` over fp32 (B, C, T): a select, so a NaN tail becomes 0.
-    ``out`` may be ``x`` (in place); default: a new tensor.  It is its own backward."""
+    ``out`` may be ``x`` (in place); default: a new tensor.  It is its own backward.  ``counts`` (keyword-only, in place of
+    ``lengths``): the int64 (B,) frame counts of a counted streaming step, clamped to [0, T] by the kernel
+    (``agx_mask_tail_counted``)."""
     lib = _lib.load()
     _need_gpu(x, out)
     if x.dim() != 3:
         raise AgxError(f"mask_tail: x is {tuple(x.shape)}, expected (B, C, T)")
     x = _f32c(x)
     b, c, t = x.shape
+    if counts is not None:
+        if lengths is not None:
+            raise AgxError("mask_tail: lengths= or counts=, not both")
+        counts = _checked_counts("mask_tail", counts, b, x.device)
     lengths = _len_arg("mask_tail", lengths, b, "lengths")
     if out is None:
         out = torch.empty_like(x)
     elif out.shape != x.shape or out.dtype != torch.float32 or not out.is_contiguous():
         raise AgxError(f"mask_tail: out must be a contiguous float32 tensor of x's shape {tuple(x.shape)}")
+    if counts is not None:
+        _lib.check(lib.agx_mask_tail_counted(_ptr(x), _ptr(counts), _ptr(out), b, c, t, _stream()), "agx_mask_tail_counted")
+        return out
     _lib.check(lib.agx_mask_tail(_ptr(x), _ptr(lengths), _ptr(out), b, c, t, _stream()), "agx_mask_tail")
     return out
 
@@ -1109,8 +1118,22 @@ def _checked_pos(op: str, pos, b: int, device) -> Tensor:
     return pos
 
 
+def _checked_counts(op: str, counts, b: int, device) -> Tensor:
+    """``counts`` as the counted kernels read it (include/agx.h "Per-row frame counts"): a contiguous int64 device tensor of B
+    entries on the operands' device.  The values stay on the device -- the kernels clamp them to [0, n] -- so nothing here
+    synchronises or checks one."""
+    if not isinstance(counts, Tensor) or counts.dtype != torch.int64 or counts.dim() != 1 or counts.numel() != b \
+            or not counts.is_contiguous():
+        what = f"{tuple(counts.shape)} {counts.dtype}" if isinstance(counts, Tensor) else type(counts).__name__
+        raise AgxError(f"{op}: counts must be a contiguous int64 device tensor of {b} entries (one frame count per batch row), got {what}")
+    _need_gpu(counts)
+    if counts.device != device:
+        raise AgxError(f"{op}: counts is on '{counts.device}', the operands are on '{device}'")
+    return counts
+
+
 def attention_alibi_stream(q: Tensor, kv: Tensor, pos: Tensor, slopes: Tensor, heads: int, head_dim: int, scale_div: float,
-                           window: int, ring: int) -> Tensor:
+                           window: int, ring: int, counts: Optional[Tensor] = None) -> Tensor:
     """``attention_alibi_window`` on a ring with the positions in device memory: row ``b``'s query ``i`` sits at
     ``p = i + pos[b]`` and sees the keys ``max(0, p - window + 1) <= j <= p``, key ``j`` in column ``j mod ring`` of ``kv``
     (B, 2*H*Dh, cap) -> (B, H*Dh, Tq).  ``q`` holds the queries in its first H*Dh rows ((B, H*Dh, Tq), or a (B, 3*H*Dh, Tq) qkv
@@ -1118,6 +1141,11 @@ def attention_alibi_stream(q: Tensor, kv: Tensor, pos: Tensor, slopes: Tensor, h
     sync, and a captured graph replays with the positions of the replay.  ``Tq + window - 1 <= ring <= cap``: the worst case
     over every position, since the host reads none.  Row ``b`` is bit for bit ``attention_alibi_window(..., q_pos0=pos[b])``.
     fp32, head_dim <= 128.
+
+    ``counts`` (int64 (B,), device; ``agx_attention_alibi_stream_counted``): row ``b``'s chunk holds ``c_b = clamp(counts[b], 0,
+    Tq)`` frames, whose K / V rows ``ring_write_pos(counts=)`` wrote.  The keys end at ``pos[b] + c_b - 1``: the ring columns
+    behind them are never multiplied as stored.  The queries below the count are bit for bit the uncounted call on ``c_b``
+    frames; the others are written and mean nothing (NaN where no key is live): mask them (``mask_tail(counts=)``).
 
     The bench observer cannot know the positions without a sync: it is told the blocks of the steady state (every row at
     ``pos >= window - 1``), counted at ``pos = window - 1``; a row younger than that walks fewer blocks, and another alignment
@@ -1135,6 +1163,8 @@ def attention_alibi_stream(q: Tensor, kv: Tensor, pos: Tensor, slopes: Tensor, h
     if bk != b:
         raise AgxError(f"attention_alibi_stream: q has batch {b}, kv has batch {bk}")
     pos = _checked_pos("attention_alibi_stream", pos, b, q.device)
+    if counts is not None:
+        counts = _checked_counts("attention_alibi_stream", counts, b, q.device)
     window = min(int(window), 0x7fffffff)
     out = torch.empty((b, hd, tq), dtype=torch.float32, device=q.device)
     tok = None
@@ -1142,19 +1172,25 @@ def attention_alibi_stream(q: Tensor, kv: Tensor, pos: Tensor, slopes: Tensor, h
         nbytes = 4 * (b * hd * tq + 2 * b * hd * min(cap, tq + window - 1))
         tok = _observer.begin("other", ("attention_alibi_stream:flash", nbytes + 4 * out.numel(),
                                         _window_macs(b, heads, head_dim, tq, window - 1, window)))
-    _lib.check(lib.agx_attention_alibi_stream(_ptr(q), _ptr(kv), cq * tq, 2 * hd * cap, cap, _ptr(pos), _ptr(_f32c(slopes)), _ptr(out),
-                                              b, heads, head_dim, tq, window, int(ring), float(scale_div), _stream()),
-               "agx_attention_alibi_stream")
+    if counts is not None:
+        _lib.check(lib.agx_attention_alibi_stream_counted(_ptr(q), _ptr(kv), cq * tq, 2 * hd * cap, cap, _ptr(pos), _ptr(counts),
+                                                          _ptr(_f32c(slopes)), _ptr(out), b, heads, head_dim, tq, window, int(ring),
+                                                          float(scale_div), _stream()), "agx_attention_alibi_stream_counted")
+    else:
+        _lib.check(lib.agx_attention_alibi_stream(_ptr(q), _ptr(kv), cq * tq, 2 * hd * cap, cap, _ptr(pos), _ptr(_f32c(slopes)),
+                                                  _ptr(out), b, heads, head_dim, tq, window, int(ring), float(scale_div), _stream()),
+                   "agx_attention_alibi_stream")
     if tok is not None:
         _observer.end(tok)
     return out
 
 
-def ring_write_pos(buf: Tensor, src: Tensor, pos: Tensor, ring: int) -> None:
+def ring_write_pos(buf: Tensor, src: Tensor, pos: Tensor, ring: int, counts: Optional[Tensor] = None) -> None:
     """``buf[b, :, (pos[b] + t) mod ring] = src[b, :, t]`` for src (B, C, n) and buf (B, C, cap), ``n <= ring <= cap``: a chunk's
     K / V rows into a ring cache at every row's own position, one launch, wrap included.  ``src`` is read in place: rows of
     pitch ``n`` at any batch stride (the K / V rows ``qkv[:, H*Dh:]`` of a qkv tensor).  ``pos`` as in
-    ``attention_alibi_stream``; it is not written.  Allocates nothing."""
+    ``attention_alibi_stream``; it is not written.  Allocates nothing.  ``counts`` (int64 (B,), device): only the first
+    ``clamp(counts[b], 0, n)`` columns of row ``b`` are written; the ring columns behind them are left as they are."""
     lib = _lib.load()
     _need_gpu(buf, src)
     if buf.dtype != torch.float32 or src.dtype != torch.float32 or buf.dim() != 3 or src.dim() != 3 or not buf.is_contiguous():
@@ -1168,16 +1204,26 @@ def ring_write_pos(buf: Tensor, src: Tensor, pos: Tensor, ring: int) -> None:
         raise AgxError(f"ring_write_pos: src {tuple(src.shape)} with strides {tuple(src.stride())} is not rows of pitch {n}")
     pos = _checked_pos("ring_write_pos", pos, b, buf.device)
     cap = buf.shape[-1]
+    if counts is not None:
+        counts = _checked_counts("ring_write_pos", counts, b, buf.device)
+        _lib.check(lib.agx_ring_write_pos_counted(_ptr(buf), _ptr(src), c * cap, cap, src.stride(0) if b > 1 else c * n, _ptr(pos),
+                                                  _ptr(counts), b, c, n, int(ring), _stream()), "agx_ring_write_pos_counted")
+        return
     _lib.check(lib.agx_ring_write_pos(_ptr(buf), _ptr(src), c * cap, cap, src.stride(0) if b > 1 else c * n, _ptr(pos), b, c, n,
                                       int(ring), _stream()), "agx_ring_write_pos")
 
 
-def stream_advance(pos: Tensor, n: int) -> None:
-    """``pos[b] += n`` on the device (exact int64 arithmetic): the advance of every row's stream by the ``n`` frames of a call."""
+def stream_advance(pos: Tensor, n: int, counts: Optional[Tensor] = None) -> None:
+    """``pos[b] += n`` on the device (exact int64 arithmetic): the advance of every row's stream by the ``n`` frames of a call.
+    ``counts`` (int64 (B,), device): ``pos[b] += clamp(counts[b], 0, n)``, the frames every row took of a counted call."""
     lib = _lib.load()
     if not isinstance(pos, Tensor):
         raise AgxError(f"stream_advance: pos must be a contiguous int64 device tensor, got {type(pos).__name__}")
     pos = _checked_pos("stream_advance", pos, pos.numel(), pos.device)
+    if counts is not None:
+        counts = _checked_counts("stream_advance", counts, pos.numel(), pos.device)
+        _lib.check(lib.agx_stream_advance_counted(_ptr(pos), _ptr(counts), pos.numel(), int(n), _stream()), "agx_stream_advance_counted")
+        return
     _lib.check(lib.agx_stream_advance(_ptr(pos), pos.numel(), int(n), _stream()), "agx_stream_advance")
 
 
@@ -1984,10 +2030,13 @@ def glu_dwconv_causal_backward(dz: Tensor, u: Tensor, w: Tensor, want_du: bool =
     return du, dw, dbias
 
 
-def glu_dwconv_step(u: Tensor, w: Tensor, bias: Tensor, bn: tuple, hist: Optional[Tensor], eps: float = 1e-5) -> Tensor:
+def glu_dwconv_step(u: Tensor, w: Tensor, bias: Tensor, bn: tuple, hist: Optional[Tensor], eps: float = 1e-5,
+                    counts: Optional[Tensor] = None) -> Tensor:
     """The streaming step, one launch: ``y`` (B, C, n) of the ``n <= CONFORMER_MAX_STEP`` new frames ``u`` (B, 2 C, n) -- the eval
     form, ``bn`` = (gamma, beta, running_mean, running_var) -- and ``hist`` (B, C, K - 1) rewritten in place with the last K - 1
-    post-GLU values of [hist | chunk].  ``hist`` may be None only for K == 1."""
+    post-GLU values of [hist | chunk].  ``hist`` may be None only for K == 1.  ``counts`` (int64 (B,), device): row ``b`` takes
+    its first ``c_b = clamp(counts[b], 0, n)`` frames -- ``y`` is exact 0 behind them and the history is that of
+    [hist | first c_b frames], untouched where ``c_b == 0``."""
     lib = _lib.load()
     _need_gpu(u, w, bias, hist, *(bn or ()))
     b, c, n, k = _glu_shape("glu_dwconv_step", u, w)
@@ -2001,10 +2050,16 @@ def glu_dwconv_step(u: Tensor, w: Tensor, bias: Tensor, bn: tuple, hist: Optiona
     w, (bias,) = _f32c(w), _bn_vectors("glu_dwconv_step", c, bias)
     bn = _bn_vectors("glu_dwconv_step", c, *bn)
     _glu_hist("glu_dwconv_step", hist, b, c, k)
+    if counts is not None:
+        counts = _checked_counts("glu_dwconv_step", counts, b, u.device)
     out = torch.empty((b, c, n), dtype=torch.float32, device=u.device)
     tok = _observer.begin("other", ("glu_dwconv_step", 12 * out.numel())) if _observer is not None else None
-    _lib.check(lib.agx_glu_dwconv_step(_ptr(u), _ptr(w), _ptr(bias), *(_ptr(v) for v in bn), float(eps), _ptr(hist), _ptr(out), b, c, n, k,
-                                       _stream()), "agx_glu_dwconv_step")
+    if counts is not None:
+        _lib.check(lib.agx_glu_dwconv_step_counted(_ptr(u), _ptr(w), _ptr(bias), *(_ptr(v) for v in bn), float(eps), _ptr(hist), _ptr(out),
+                                                   _ptr(counts), b, c, n, k, _stream()), "agx_glu_dwconv_step_counted")
+    else:
+        _lib.check(lib.agx_glu_dwconv_step(_ptr(u), _ptr(w), _ptr(bias), *(_ptr(v) for v in bn), float(eps), _ptr(hist), _ptr(out), b, c,
+                                           n, k, _stream()), "agx_glu_dwconv_step")
     if tok is not None:
         _observer.end(tok)
     return out
@@ -2140,13 +2195,17 @@ def _stream_rates(kind: int, stride: int, rate_in: int, delay_in: int) -> Tuple[
 def conv_stream_step(kind: int, c_in: int, c_out: int, kernel: int, stride: int, dilation: int, packed: Tensor, bias: Optional[Tensor],
                      src: Tensor, dst: Tensor, pos: Tensor, n: int, rate_in: int, delay_in: int, src_ring: bool = True,
                      dst_ring: bool = True, res: Optional[Tensor] = None, end: Optional[Tensor] = None, epilogue: int = 0,
-                     slope: float = 0.1) -> Tensor:
+                     slope: float = 0.1, counts: Optional[Tensor] = None) -> Tensor:
     """One chunk of ``n`` frames through one conv layer of a stream (``agx_conv_stream_step``).  ``src``: the layer's input ring
     (B, c_in, cap), or with ``src_ring=False`` a plain (B, c_in, n * rate_in) tensor of the step's own columns (kernel 1 only);
     ``dst``: the consumer's ring (B, c_out, cap') or, ``dst_ring=False``, a plain (B, c_out, n * rate_out) tensor; ``res``: the
     ring the residual is read from, at the output's columns; ``pos`` / ``end``: int64 (B,) device tensors, read by the kernel
     and never written (``end=None``: no validity mask).  Writes the step's n * rate_out columns of ``dst`` and returns it.
-    Every refusal -- this wrapper's or the library's -- precedes the launch."""
+    Every refusal -- this wrapper's or the library's -- precedes the launch.
+
+    ``counts`` (int64 (B,), device; ``agx_conv_stream_step_counted``): row ``b`` takes the first ``c_b = clamp(counts[b], 0, n)``
+    frames.  Its first ``c_b * rate_out`` output columns are bit for bit those of the uncounted step on these frames; behind them
+    a plain ``dst`` holds exact 0 and a ring ``dst`` is not written.  The kernel reads ``counts``; the host never does."""
     lib = _lib.load()
     _need_gpu(packed, bias, src, dst, res)
     n, rate_in, delay_in = int(n), int(rate_in), int(delay_in)
@@ -2172,6 +2231,8 @@ def conv_stream_step(kind: int, c_in: int, c_out: int, kernel: int, stride: int,
     pos = _checked_pos("conv_stream_step", pos, b, src.device)
     if end is not None:
         end = _checked_pos("conv_stream_step", end, b, src.device)
+    if counts is not None:
+        counts = _checked_counts("conv_stream_step", counts, b, src.device)
     packed = _f32c(packed)
     need = _lib.load().agx_conv_packed_floats(ctypes.byref(conv_desc(kind, 1, c_in, c_out, 1 << 20, kernel, stride, dilation)))
     if need < 0:
@@ -2185,18 +2246,23 @@ def conv_stream_step(kind: int, c_in: int, c_out: int, kernel: int, stride: int,
     tok = None
     if _observer is not None:
         tok = _observer.begin("other", ("conv_stream_step", 4 * (packed.numel() + b * c_out * n * rate_out), 0))
-    _lib.check(lib.agx_conv_stream_step(kind, c_in, c_out, kernel, stride, dilation, int(epilogue), float(slope), _ptr(packed),
-                                        _ptr(bias), _ptr(src), src.shape[2] if src_ring else 0, _ptr(res),
-                                        res.shape[2] if res is not None else 0, _ptr(dst), dst.shape[2] if dst_ring else 0,
-                                        _ptr(pos), _ptr(end), b, n, rate_in, delay_in, _stream()), "agx_conv_stream_step")
+    head = (kind, c_in, c_out, kernel, stride, dilation, int(epilogue), float(slope), _ptr(packed), _ptr(bias), _ptr(src),
+            src.shape[2] if src_ring else 0, _ptr(res), res.shape[2] if res is not None else 0, _ptr(dst),
+            dst.shape[2] if dst_ring else 0, _ptr(pos), _ptr(end))
+    if counts is not None:
+        _lib.check(lib.agx_conv_stream_step_counted(*head, _ptr(counts), b, n, rate_in, delay_in, _stream()),
+                   "agx_conv_stream_step_counted")
+    else:
+        _lib.check(lib.agx_conv_stream_step(*head, b, n, rate_in, delay_in, _stream()), "agx_conv_stream_step")
     if tok is not None:
         _observer.end(tok)
     return dst
 
 
-def ring_write_rate(buf: Tensor, src: Tensor, pos: Tensor, rate: int) -> None:
+def ring_write_rate(buf: Tensor, src: Tensor, pos: Tensor, rate: int, counts: Optional[Tensor] = None) -> None:
     """``buf[b, :, (pos[b] * rate + t) mod cap] = src[b, :, t]`` for src (B, C, n * rate) and the ring buf (B, C, cap): a stack's
-    input chunk into its first ring, every row at its own position, one launch.  ``pos`` is not written."""
+    input chunk into its first ring, every row at its own position, one launch.  ``pos`` is not written.  ``counts`` (int64
+    (B,), device): only the ``clamp(counts[b], 0, n) * rate`` first columns of row ``b``; the others are neither read nor written."""
     lib = _lib.load()
     _need_gpu(buf, src)
     if any(t.dtype != torch.float32 or t.dim() != 3 or not t.is_contiguous() for t in (buf, src)):
@@ -2207,6 +2273,11 @@ def ring_write_rate(buf: Tensor, src: Tensor, pos: Tensor, rate: int) -> None:
     if int(rate) < 1 or cols % int(rate):
         raise AgxError(f"ring_write_rate: {cols} columns are not whole frames of {rate}")
     pos = _checked_pos("ring_write_rate", pos, b, buf.device)
+    if counts is not None:
+        counts = _checked_counts("ring_write_rate", counts, b, buf.device)
+        _lib.check(lib.agx_ring_write_rate_counted(_ptr(buf), _ptr(src), _ptr(pos), _ptr(counts), b, c, cols, buf.shape[2], int(rate),
+                                                   _stream()), "agx_ring_write_rate_counted")
+        return
     _lib.check(lib.agx_ring_write_rate(_ptr(buf), _ptr(src), _ptr(pos), b, c, cols, buf.shape[2], int(rate), _stream()),
                "agx_ring_write_rate")
 

@@ -18,6 +18,14 @@ the input by ``decoder_delay`` samples: ``decode_stream`` returns the raw block 
 negative, and ``decode_flush`` pushes the ``ceil(decoder_delay / scale_factor)`` zero frames that bring the tail out.  With the
 delay removed, the stream equals the plain call on the whole clip.  Ragged last frames are the caller's: pad the last hop to a
 whole frame; the plain call pads every layer instead, so that frame differs.
+
+Per-row frame counts.  Every step takes ``counts=``, a contiguous int64 (B,) device tensor: row ``b`` takes the first
+``c_b = clamp(counts[b], 0, n)`` frames of the chunk and advances by ``c_b``; with ``c_b = 0`` nothing of the row changes.  The
+kernels read it -- the host never does, so a captured step replays with whatever the tensor holds.  The first ``c_b`` frames of
+a row's latents, ``zq`` and waveform are bit for bit those of an uncounted stream fed the same frames; every floating-point output
+behind them is exact 0 (NaN in the chunk there reaches no result and no ring).  ``index`` behind the count is the code of the
+zero latent and means nothing -- slice by ``counts`` -- and ``commit`` is computed over the whole chunk, zero latents included:
+it is not meaningful on a counted call.  ``counts=None`` is the uncounted call, launch for launch.
 """
 from __future__ import annotations
 
@@ -207,39 +215,57 @@ def _image(layer) -> Tensor:
     return packed_image(layer.conv, "conv_stream_pack", layer.kind)
 
 
-def _run_stack(units: List[Unit], plans, rings: List[Tensor], x: Tensor, pos: Tensor, end: Optional[Tensor], n: int) -> Tensor:
+def _run_stack(units: List[Unit], plans, rings: List[Tensor], x: Tensor, pos: Tensor, end: Optional[Tensor], n: int,
+               counts: Optional[Tensor] = None) -> Tensor:
     """``n`` frames through a stack: the chunk into the first ring, one or two step launches per unit, the last unit into a plain
-    tensor, then the advance of ``pos``."""
+    tensor, then the advance of ``pos``.  ``counts``: the same launches in their counted forms (None: the uncounted ones)."""
     b = x.shape[0]
-    ops.ring_write_rate(rings[0], x, pos, plans[0].rate_in)
+    ops.ring_write_rate(rings[0], x, pos, plans[0].rate_in, counts=counts)
     out = None
     for i, (u, p) in enumerate(zip(units, plans)):
         last = i + 1 == len(units)
         dst = torch.empty((b, p.c_out, n * p.rate_out), dtype=torch.float32, device=x.device) if last else rings[i + 1]
-        out = run_unit(u, p, rings[i], dst, not last, pos, end, n)
-    ops.stream_advance(pos, n)
+        out = run_unit(u, p, rings[i], dst, not last, pos, end, n, counts)
+    ops.stream_advance(pos, n, counts=counts)
     return out
 
 
-def run_unit(u: Unit, p: UnitPlan, ring: Tensor, dst: Tensor, dst_ring: bool, pos: Tensor, end: Optional[Tensor], n: int) -> Tensor:
+def run_unit(u: Unit, p: UnitPlan, ring: Tensor, dst: Tensor, dst_ring: bool, pos: Tensor, end: Optional[Tensor], n: int,
+             counts: Optional[Tensor] = None) -> Tensor:
     """One unit's step: ``ring`` -> ``dst``.  A conv is one launch; a residual unit is two, its hidden activation (which only the
-    k = 1 conv at the same column reads, so it needs no mask and no history) in a plain scratch tensor."""
+    k = 1 conv at the same column reads, so it needs no mask and no history) in a plain scratch tensor.  ``counts``: the counted
+    launches (the hidden activation is exact 0 behind a row's count)."""
     post = u.slope
     if p.kind == "res":
         c1, c2 = u.convs[0], u.convs[1]
         hid = torch.empty((ring.shape[0], c1.conv.out_channels, n * p.rate_in), dtype=torch.float32, device=ring.device)
         ops.conv_stream_step(CONV_CAUSAL, p.c_in, c1.conv.out_channels, p.k, 1, p.d, _image(c1), detached(c1.conv.bias), ring, hid, pos,
-                             n, p.rate_in, p.delay_in, dst_ring=False, epilogue=EPI_LEAKY_PRE, slope=u.inner_slope)
+                             n, p.rate_in, p.delay_in, dst_ring=False, epilogue=EPI_LEAKY_PRE, slope=u.inner_slope, counts=counts)
         return ops.conv_stream_step(CONV_CAUSAL, c1.conv.out_channels, p.c_out, 1, 1, 1, _image(c2), detached(c2.conv.bias), hid, dst, pos,
                                     n, p.rate_in, p.delay_in, src_ring=False, dst_ring=dst_ring, res=ring, end=end,
-                                    epilogue=EPI_RESIDUAL | (EPI_LEAKY_POST if post is not None else 0), slope=post or 0.0)
+                                    epilogue=EPI_RESIDUAL | (EPI_LEAKY_POST if post is not None else 0), slope=post or 0.0,
+                                    counts=counts)
     layer = u.convs[0]
     return ops.conv_stream_step(layer.kind, p.c_in, p.c_out, p.k, p.s, p.d, _image(layer), detached(layer.conv.bias), ring, dst, pos, n,
                                 p.rate_in, p.delay_in, dst_ring=dst_ring, end=end, epilogue=EPI_LEAKY_PRE if post is not None else 0,
-                                slope=post or 0.0)
+                                slope=post or 0.0, counts=counts)
 
 
-def _check(model, stream: CodecStream, x: Tensor, what: str, per_frame: int, channels: int) -> int:
+def _check_counts(what: str, counts, batch: int, device) -> None:
+    """The refusals of ``counts=``, before the first launch.  No value is read: the kernels clamp every entry to [0, n]."""
+    if counts is None:
+        return
+    if not isinstance(counts, Tensor) or counts.dtype != torch.int64 or counts.dim() != 1 or counts.numel() != batch:
+        got = f"{tuple(counts.shape)} {counts.dtype}" if isinstance(counts, Tensor) else type(counts).__name__
+        raise AgxError(f"{what}: counts must be a contiguous int64 device tensor of {batch} entries (one frame count per batch row), "
+                       f"got {got}")
+    if not counts.is_contiguous():
+        raise AgxError(f"{what}: counts is not contiguous (stride {tuple(counts.stride())}): the kernels read {batch} adjacent int64")
+    if counts.device != device:
+        raise AgxError(f"{what}: counts is on '{counts.device}', the stream on '{device}'")
+
+
+def _check(model, stream: CodecStream, x: Tensor, what: str, per_frame: int, channels: int, counts=None) -> int:
     """Every refusal of a step, before the first launch; returns the chunk's frames."""
     if not isinstance(stream, CodecStream) or stream.model_id != id(model):
         raise AgxError(f"{what}: the stream belongs to another model (model.new_stream makes one for this model)")
@@ -260,41 +286,63 @@ def _check(model, stream: CodecStream, x: Tensor, what: str, per_frame: int, cha
         raise AgxError(f"{what}: a chunk of {n} frames exceeds the stream's max_chunk = {stream.max_chunk}")
     if x.dtype != torch.float32:
         raise AgxError(f"{what}: expected float32, got {x.dtype}")
+    _check_counts(what, counts, stream.batch, stream.device)
     return n
 
 
-def encode_latents_stream(model, x: Tensor, stream: CodecStream) -> Tensor:
-    """Encoder stack on a chunk in the model's input format -> (B, D, n) latents of the chunk's ``n`` frames."""
+def encode_latents_stream(model, x: Tensor, stream: CodecStream, counts: Optional[Tensor] = None) -> Tensor:
+    """Encoder stack on a chunk in the model's input format -> (B, D, n) latents of the chunk's ``n`` frames.  ``counts`` (module
+    docstring): row ``b`` takes its first ``c_b`` frames, and its latents behind them are exact 0."""
     xin = model.rearrange_in(x)
-    n = _check(model, stream, xin, "encode_stream", stream.scale_factor, model.in_channels)
-    return _run_stack(model._units("encoders"), stream.plan.encoders, stream.enc_rings, xin.contiguous(), stream.enc_pos, None, n)
+    n = _check(model, stream, xin, "encode_stream", stream.scale_factor, model.in_channels, counts)
+    return _run_stack(model._units("encoders"), stream.plan.encoders, stream.enc_rings, xin.contiguous(), stream.enc_pos, None, n, counts)
 
 
-def encode_stream(model, x: Tensor, stream: CodecStream, codebook_n: Optional[int] = None):
-    z = encode_latents_stream(model, x, stream)
+def encode_stream(model, x: Tensor, stream: CodecStream, codebook_n: Optional[int] = None, counts: Optional[Tensor] = None):
+    """-> (zq, commit, index) of the chunk.  With ``counts``, ``zq`` is masked to exact 0 behind a row's count; ``index`` there is
+    the code of the zero latent and ``commit`` covers the whole chunk (module docstring)."""
+    z = encode_latents_stream(model, x, stream, counts)
     zq, index, commit = model.quantizer.quantize_bcl(z, codebook_n, update_codebook=False, prioritize_early=False)
+    if counts is not None:
+        zq = ops.mask_tail(zq, None, counts=counts)
     return zq, commit, index
 
 
-def decode_stream(model, zq: Tensor, stream: CodecStream) -> Tensor:
-    n = _check(model, stream, zq, "decode_stream", 1, stream.plan.decoders[0].c_in)
-    y = _run_stack(model._units("decoders"), stream.plan.decoders, stream.dec_rings, zq.contiguous(), stream.dec_pos, stream.end, n)
+def decode_stream(model, zq: Tensor, stream: CodecStream, counts: Optional[Tensor] = None) -> Tensor:
+    n = _check(model, stream, zq, "decode_stream", 1, stream.plan.decoders[0].c_in, counts)
+    y = _run_stack(model._units("decoders"), stream.plan.decoders, stream.dec_rings, zq.contiguous(), stream.dec_pos, stream.end, n,
+                   counts)
     return model.rearrange_out(y)
 
 
-def forward_stream(model, x: Tensor, stream: CodecStream, codebook_n: Optional[int] = None):
-    zq, commit, index = encode_stream(model, x, stream, codebook_n)
-    return decode_stream(model, zq, stream), commit, index
+def forward_stream(model, x: Tensor, stream: CodecStream, codebook_n: Optional[int] = None, counts: Optional[Tensor] = None):
+    zq, commit, index = encode_stream(model, x, stream, codebook_n, counts)
+    return decode_stream(model, zq, stream, counts), commit, index
 
 
-def decode_flush(model, stream: CodecStream) -> Tensor:
+def flush_counts(stream: CodecStream, rows, n: int) -> Tensor:
+    """The counts of one flush step of ``n`` frames that only ``rows`` receive: ``n`` for them, 0 for every other row, as an int64
+    (B,) tensor on the stream's device.  Built on the host: between steps, outside any captured graph."""
+    rows = stream._rows(rows, "decode_flush")
+    counts = [0] * stream.batch
+    for r in rows:
+        counts[r] = int(n)
+    return torch.tensor(counts, dtype=torch.int64).to(stream.device)
+
+
+def decode_flush(model, stream: CodecStream, rows=None) -> Tensor:
     """The ``ceil(decoder_delay / scale_factor)`` zero-frame steps that bring the delayed tail out, in chunks of at most
-    ``max_chunk`` frames -> (B, C, frames * scale_factor) in the model's output format."""
+    ``max_chunk`` frames -> (B, C, frames * scale_factor) in the model's output format.  ``rows``: only those rows receive the
+    flush frames (counted steps, ``flush_counts``) -- one stream's tail comes out while the others stay put, their part of the
+    result exact 0.  Call it between steps, outside any captured graph."""
     left, parts = stream.plan.flush_frames, []
     c = stream.plan.decoders[0].c_in
+    if rows is not None:
+        stream._rows(rows, "decode_flush")      # the refusal precedes the first launch
     while left > 0:
         n = min(left, stream.max_chunk)
-        parts.append(decode_stream(model, torch.zeros((stream.batch, c, n), dtype=torch.float32, device=stream.device), stream))
+        counts = None if rows is None else flush_counts(stream, rows, n)
+        parts.append(decode_stream(model, torch.zeros((stream.batch, c, n), dtype=torch.float32, device=stream.device), stream, counts))
         left -= n
     if not parts:
         return model.rearrange_out(torch.zeros((stream.batch, model.in_channels, 0), dtype=torch.float32, device=stream.device))

@@ -457,7 +457,12 @@ class Attention(nn.Module):
 
         ``kv_cache`` = (ring, pos) with ``pos`` an int64 (B,) device tensor (``TransformerStreamCache``): the same walk with
         ``ops.ring_write_pos`` / ``ops.attention_alibi_stream`` in place of ``ops.ring_write`` / ``ops.attention_alibi_window`` --
-        both read every row's position from ``pos`` -- and the worst-case bound ``n + window - 1 <= capacity``."""
+        both read every row's position from ``pos`` -- and the worst-case bound ``n + window - 1 <= capacity``.
+
+        ``kv_cache`` = (ring, pos, counts): the counted step.  Row ``b``'s K / V rows beyond its first
+        ``counts[b]`` frames are not written, and the attention's keys end at the count -- a masked key still meets its V
+        as ``0 * v``, so an unwritten ring column must not be live.  What the queries behind the count hold is the caller's to
+        mask (``Transformer`` / ``ConformerBlock`` do)."""
         if self.attention_dtype != "fp32":
             raise AgxError(f"causal attention runs in fp32: attention_dtype = {self.attention_dtype!r} has no kernel")
         if _active_p(self.dropout) > 0:
@@ -483,9 +488,10 @@ class Attention(nn.Module):
             if kv_cache is None:
                 o = ops.attention_alibi_window(qkv, None, window=self.window, **self._attn())
             elif on_device:      # pos (B,) is read by both kernels: one write launch, wrap included
-                buf, pos = kv_cache
-                ops.ring_write_pos(buf, qkv[:, self.inner_dim:, :], pos, buf.shape[-1])
-                o = ops.attention_alibi_stream(qkv, buf, pos, window=self.window, ring=buf.shape[-1], **self._attn())
+                buf, pos = kv_cache[:2]
+                counts = kv_cache[2] if len(kv_cache) > 2 else None
+                ops.ring_write_pos(buf, qkv[:, self.inner_dim:, :], pos, buf.shape[-1], counts=counts)
+                o = ops.attention_alibi_stream(qkv, buf, pos, window=self.window, ring=buf.shape[-1], counts=counts, **self._attn())
             else:
                 buf, length = kv_cache
                 n, cap = x.shape[-1], buf.shape[-1]
@@ -801,6 +807,28 @@ class TransformerCache:
         self.length = 0
 
 
+def _checked_counts(what: str, counts, cache, stream_type, host_type, x: Tensor) -> Tensor:
+    """The refusals of ``counts=`` on a cached call, before any op.  No value is read: the kernels clamp every entry to [0, n]."""
+    if cache is None:
+        raise AgxError(f"{what}: counts= without cache=: a per-row frame count belongs to a cached step on a stream cache "
+                       "(new_stream_cache)")
+    if isinstance(cache, host_type):
+        raise AgxError(f"{what}: counts= with a {host_type.__name__}: its length is one host integer for the whole batch; per-row "
+                       f"counts need the device-held positions of a {stream_type.__name__} (new_stream_cache)")
+    if not isinstance(cache, stream_type):
+        raise AgxError(f"{what}: counts= needs a {stream_type.__name__} (new_stream_cache), got {type(cache).__name__}")
+    b = cache.batch
+    if not isinstance(counts, Tensor) or counts.dtype != torch.int64 or counts.dim() != 1 or counts.numel() != b:
+        got = f"{tuple(counts.shape)} {counts.dtype}" if isinstance(counts, Tensor) else type(counts).__name__
+        raise AgxError(f"{what}: counts must be a contiguous int64 device tensor of {b} entries (one frame count per batch row), "
+                       f"got {got}")
+    if not counts.is_contiguous():
+        raise AgxError(f"{what}: counts is not contiguous (stride {tuple(counts.stride())}): the kernels read {b} adjacent int64")
+    if counts.device != cache.pos.device:
+        raise AgxError(f"{what}: counts is on '{counts.device}', the cache on '{cache.pos.device}'")
+    return counts
+
+
 class TransformerStreamCache:
     """The ring key/value cache of a windowed causal ``Transformer`` with the positions in device memory, one per batch row
     (``Transformer.new_stream_cache``): per layer one fp32 (B, 2*H*Dh, capacity) ring from ``torch.empty``, never cleared, and
@@ -959,7 +987,7 @@ class Transformer(nn.Module):
         return lengths, y_lengths
 
     def _hip_bct(self, x: Tensor, keep: Optional[list] = None, y: Optional[Tensor] = None,
-                 cache=None, lens: Optional[tuple] = None, packed: Optional[_Packed] = None) -> Tensor:
+                 cache=None, lens: Optional[tuple] = None, packed: Optional[_Packed] = None, counts: Optional[Tensor] = None) -> Tensor:
         """The one forward walk, LN1 -> QKV -> attention -> W_o (+res) -> LN2 -> FFN-in (GELU) -> FFN-out (+res) per layer:
         7 launches, both residual adds fused into the W_o / FFN-out conv epilogues (a cross-attention layer: 8, a Q and a
         KV projection in place of the QKV one).  ``keep``: the training forward
@@ -1001,7 +1029,13 @@ class Transformer(nn.Module):
         slack columns can exist -- a device ``cu_seqlens``, which the host does not read, or a host one that ends before N --
         they are masked exactly as the padded tails above: ``mask_tail`` of the one packed row at ``cu[-1]``, out of place on
         ``x`` (and on ``y`` likewise), in place on the output, so the output is exactly 0 there, the kept tensors are finite
-        and NaN in the slack changes nothing.  ``packed=None``: no packed op is called."""
+        and NaN in the slack changes nothing.  ``packed=None``: no packed op is called.
+
+        ``counts`` (``_checked_counts``; a stream cache only): row ``b`` takes the first ``clamp(counts[b], 0, n)`` frames of
+        ``x``.  ``x0 = mask_tail(x, counts=)`` out of place, then per layer the stream-cache launches with the
+        counted ring write, the counted advance, and ``mask_tail`` in place on the output: two more launches per call, and the
+        contract of the padded tails above -- valid frames bit for bit those of an uncounted call on them, exact 0 behind the
+        count, NaN there harmless.  ``counts=None``: no counted op is called."""
         lengths, y_lengths = lens if lens is not None else (None, None)
         on_device = isinstance(cache, TransformerStreamCache)
         if (y is not None) != self.cross_attention:
@@ -1016,6 +1050,8 @@ class Transformer(nn.Module):
             x = ops.mask_tail(x, lengths)
         if y_lengths is not None:
             y = ops.mask_tail(y, y_lengths)
+        if counts is not None:
+            x = ops.mask_tail(x, None, counts=counts)
         if packed is not None and packed.slack:
             x = ops.mask_tail(x, packed.cu[-1:])
         if packed is not None and packed.y_slack:
@@ -1023,7 +1059,9 @@ class Transformer(nn.Module):
         for li, (attention, ff) in enumerate(self.layers):
             kept = None if keep is None else {}
             drop = None if seed is None else (seed, li)
-            if cache is not None:
+            if counts is not None:
+                x = attention.run_bct(x, x, kept, None, drop, kv_cache=(cache.kv[li], cache.pos, counts))
+            elif cache is not None:
                 x = attention.run_bct(x, x, kept, None, drop, kv_cache=(cache.kv[li], cache.pos if on_device else cache.length))
             elif packed is not None:
                 x = attention.run_bct(x, x, kept, y if attention.cross_attention else None, drop,
@@ -1037,11 +1075,13 @@ class Transformer(nn.Module):
             if keep is not None:
                 keep.append(kept)
         if on_device:
-            ops.stream_advance(cache.pos, x.shape[-1])      # once per call: every layer read the same positions
+            ops.stream_advance(cache.pos, x.shape[-1], counts=counts)      # once per call: every layer read the same positions
         elif cache is not None:
             cache.length += x.shape[-1]
         if lengths is not None:
             x = ops.mask_tail(x, lengths, out=x)
+        if counts is not None:
+            x = ops.mask_tail(x, None, out=x, counts=counts)
         if packed is not None and packed.slack:
             x = ops.mask_tail(x, packed.cu[-1:], out=x)
         return x
@@ -1113,7 +1153,7 @@ class Transformer(nn.Module):
         return self.run_packed(x.transpose(1, 2).contiguous(), cu_seqlens, max_len, y, y_cu_seqlens,
                                y_max_len).transpose(1, 2).contiguous()
 
-    def run_bct(self, x: Tensor, y: Optional[Tensor] = None, cache=None, *, lengths=None, y_lengths=None) -> Tensor:
+    def run_bct(self, x: Tensor, y: Optional[Tensor] = None, cache=None, *, lengths=None, y_lengths=None, counts=None) -> Tensor:
         """Channel-major (B, dim, T) in and out; ``y`` (B, dim, Ty) is the cross-attention layer's second sequence.  With
         autograd on, the backward runs on the HIP kernels too (_TransformerNative).  ``cache`` (``new_cache``): ``x`` holds
         the next ``n`` frames of a causal Transformer's sequence; inference only.  A ``TransformerStreamCache``
@@ -1124,7 +1164,16 @@ class Transformer(nn.Module):
         host (0 <= length <= T) and copied to the device; a device integer tensor is used without a sync and clamped by the
         kernels -- the form to pass under graph capture.  ``y_lengths`` alone leaves every row of ``x`` full.  Refused, before
         any op: a causal or windowed Transformer, ``cache=``, an active dropout site, ``attention_dtype = "bf16"``,
-        ``y_lengths`` without a cross-attention layer, a size other than B."""
+        ``y_lengths`` without a cross-attention layer, a size other than B.
+
+        ``counts`` (keyword-only; a ``TransformerStreamCache`` only): a contiguous int64 (B,) device tensor; row ``b`` takes the
+        first ``clamp(counts[b], 0, n)`` frames and advances by as many (``_hip_bct``).  The kernels read it, the host never
+        does.  Refused, before any op: no cache, a ``TransformerCache`` (its ``length`` is a host integer), ``lengths=``, a
+        wrong dtype, shape or device, a non-contiguous tensor."""
+        if counts is not None:
+            if lengths is not None or y_lengths is not None:
+                raise AgxError("counts= with lengths=: a counted call is a cached causal step and takes no lengths")
+            _checked_counts("Transformer", counts, cache, TransformerStreamCache, TransformerCache, x)
         if lengths is not None or y_lengths is not None:
             lens = self._check_lengths(x, y, cache, lengths, y_lengths)
             if needs_grad(x, self) or (y is not None and torch.is_grad_enabled() and y.requires_grad):
@@ -1137,15 +1186,15 @@ class Transformer(nn.Module):
                 self._check_cache(x, cache)
             if y is not None:
                 raise AgxError("this Transformer was built without context_y and takes no second sequence y")
-            return self._hip_bct(x, None, None, cache)
+            return self._hip_bct(x, None, None, cache, counts=counts)
         if needs_grad(x, self) or (y is not None and torch.is_grad_enabled() and y.requires_grad):
             return _TransformerNative.apply(self, None, x, y, *list(self.parameters()))
         return self._hip_bct(x, None, y)
 
-    def forward(self, x: Tensor, y=None, cache=None, *, lengths=None, y_lengths=None) -> Tensor:
+    def forward(self, x: Tensor, y=None, cache=None, *, lengths=None, y_lengths=None, counts=None) -> Tensor:
         y = None if y is None else y.transpose(1, 2).contiguous()
-        return self.run_bct(x.transpose(1, 2).contiguous(), y, cache, lengths=lengths,
-                            y_lengths=y_lengths).transpose(1, 2).contiguous()
+        return self.run_bct(x.transpose(1, 2).contiguous(), y, cache, lengths=lengths, y_lengths=y_lengths,
+                            counts=counts).transpose(1, 2).contiguous()
 
 
 class TransformerBottleneck(nn.Module):
@@ -1277,14 +1326,41 @@ class ConformerConvBlock(nn.Module):
             got = tuple(conv_state.shape) if isinstance(conv_state, Tensor) else type(conv_state).__name__
             raise AgxError(f"conv state: expected a contiguous float32 {want} tensor (B, C, K - 1) for x {tuple(x.shape)}, got {got}")
 
+    def _check_counts(self, x: Tensor, conv_state: Optional[Tensor], counts) -> None:
+        """The refusals of ``counts=``, before any op.  No value is read: the kernel clamps every entry to [0, n]."""
+        if conv_state is None:
+            raise AgxError("ConformerConvBlock: counts= without a conv state: a per-row frame count belongs to a cached step")
+        b = conv_state.shape[0] if isinstance(conv_state, Tensor) else 0
+        if not isinstance(counts, Tensor) or counts.dtype != torch.int64 or counts.dim() != 1 or counts.numel() != b:
+            got = f"{tuple(counts.shape)} {counts.dtype}" if isinstance(counts, Tensor) else type(counts).__name__
+            raise AgxError(f"ConformerConvBlock: counts must be a contiguous int64 device tensor of {b} entries (one frame count per "
+                           f"batch row), got {got}")
+        if not counts.is_contiguous():
+            raise AgxError(f"ConformerConvBlock: counts is not contiguous (stride {tuple(counts.stride())}): the kernel reads {b} "
+                           "adjacent int64")
+        if counts.device != conv_state.device:
+            raise AgxError(f"ConformerConvBlock: counts is on '{counts.device}', the conv state on '{conv_state.device}'")
+        if x.dim() == 3 and x.shape[-1] > ops.CONFORMER_MAX_STEP:
+            raise AgxError(f"ConformerConvBlock: a counted call takes at most CONFORMER_MAX_STEP = {ops.CONFORMER_MAX_STEP} frames (the "
+                           f"one launch of glu_dwconv_step), got {x.shape[-1]}")
+
     def run_bct(self, x: Tensor, residual: Optional[Tensor] = None, keep: Optional[dict] = None,
-                drop: Optional[tuple] = None, conv_state: Optional[Tensor] = None) -> Tensor:
+                drop: Optional[tuple] = None, conv_state: Optional[Tensor] = None, counts: Optional[Tensor] = None,
+                mask_counts: bool = True) -> Tensor:
         """(B, C, T) -> net(x) [+ residual: x itself].  ``keep`` marks a forward whose backward will run (``backward_bct``): z is then
         written in eval mode too.  With autograd on and no ``keep`` the call goes through ``_ConformerNative``.  ``conv_state``
         (``new_conv_state``; a causal block in eval mode, no gradient): ``x`` holds the next T frames of the streams the state
-        belongs to, and the state is rewritten in place."""
+        belongs to, and the state is rewritten in place.
+
+        ``counts`` (with ``conv_state``; int64 (B,), device; T <= ``ops.CONFORMER_MAX_STEP``): row ``b`` takes its first
+        ``clamp(counts[b], 0, T)`` frames -- ``ops.glu_dwconv_step(counts=)`` where the step was, so the state is that of those
+        frames alone -- and the result is exact 0 behind them (``ops.mask_tail`` in place, one more launch; the enclosing
+        ``ConformerBlock`` passes ``mask_counts=False`` and masks its own output instead).  Every other op of the block is
+        pointwise in time, so NaN in ``x`` behind a row's count reaches neither a valid frame nor the state."""
         if residual is not None and residual is not x:
             raise AgxError("ConformerConvBlock: the residual is the block's own input (x + net(x)), or None")
+        if counts is not None:
+            self._check_counts(x, conv_state, counts)
         if conv_state is not None:
             self._check_conv_state(x, keep, conv_state)
         if keep is None and needs_grad(x, self):
@@ -1301,7 +1377,9 @@ class ConformerConvBlock(nn.Module):
         u = self._in.forward(xn)
         if conv_state is not None:
             bn_eval = (gamma, beta, bn.running_mean, bn.running_var)
-            if x.shape[-1] <= ops.CONFORMER_MAX_STEP:
+            if counts is not None:
+                y = ops.glu_dwconv_step(u, dw.weight.detach(), dw.bias.detach(), bn_eval, conv_state, eps=bn.eps, counts=counts)
+            elif x.shape[-1] <= ops.CONFORMER_MAX_STEP:
                 y = ops.glu_dwconv_step(u, dw.weight.detach(), dw.bias.detach(), bn_eval, conv_state, eps=bn.eps)
             else:
                 y = ops.glu_dwconv_causal(u, dw.weight.detach(), dw.bias.detach(), bn=bn_eval, eps=bn.eps, hist=conv_state)
@@ -1324,7 +1402,10 @@ class ConformerConvBlock(nn.Module):
                 keep["conv"].update(p=p, seed=seed, layer=layer)
             out = self._out.forward(y)
             return ops.dropout_add(out, residual, p, seed, 4 * layer + SITE_CONV_OUT, out=out)
-        return self._out.forward(y, EPI_RESIDUAL if residual is not None else 0, residual)
+        out = self._out.forward(y, EPI_RESIDUAL if residual is not None else 0, residual)
+        if counts is not None and mask_counts:
+            ops.mask_tail(out, None, out=out, counts=counts)
+        return out
 
     def backward_bct(self, kept: dict, g: Tensor, residual: bool = True):
         """``g`` = the gradient of ``run_bct(x, residual=x, keep=kept)`` -> (dx, gradients in ``parameters()`` order); without
@@ -1342,8 +1423,19 @@ class ConformerConvBlock(nn.Module):
         dx, dweight, dbias = _ln_bwd(self.net[0], kept["cx"], dxn, add=g if residual else None)
         return dx, [dweight, dbias, g_i[0].unsqueeze(-1), g_i[1], d_dw, d_db, dgamma, dbeta, g_o[0].unsqueeze(-1), g_o[1]]
 
-    def forward(self, x: Tensor) -> Tensor:
-        return self.run_bct(x.transpose(1, 2).contiguous()).transpose(1, 2).contiguous()
+    def forward(self, x: Tensor, cache=None, counts=None) -> Tensor:
+        """Reference layout (B, T, C).  ``cache`` (a ``ConformerStreamCache``, or a ``ConformerCache`` without ``counts``): the
+        block runs on the cache's conv state; it has no position of its own and advances none.  ``counts``: ``run_bct``."""
+        if cache is None:
+            if counts is not None:
+                raise AgxError("ConformerConvBlock: counts= without cache=: a per-row frame count belongs to a cached step on a stream "
+                               "cache (new_stream_cache)")
+            return self.run_bct(x.transpose(1, 2).contiguous()).transpose(1, 2).contiguous()
+        if not isinstance(cache, (ConformerCache, ConformerStreamCache)):
+            raise AgxError(f"cache= takes a ConformerCache or a ConformerStreamCache (new_cache / new_stream_cache), got {type(cache).__name__}")
+        if counts is not None:
+            _checked_counts("ConformerConvBlock", counts, cache, ConformerStreamCache, ConformerCache, x)
+        return self.run_bct(x.transpose(1, 2).contiguous(), conv_state=cache.conv_state, counts=counts).transpose(1, 2).contiguous()
 
 
 class ConformerBlock(nn.Module):
@@ -1454,10 +1546,14 @@ class ConformerBlock(nn.Module):
         sites = [self.attention.dropout, self.conv_block.net[7]] + [f.net[i] for f in (self.first_ff, self.second_ff) for i in (3, 5)]
         return any(isinstance(m, nn.Dropout) and m.training and m.p > 0 for m in sites)
 
-    def _hip_bct(self, x: Tensor, keep: Optional[dict] = None, cache=None) -> Tensor:
+    def _hip_bct(self, x: Tensor, keep: Optional[dict] = None, cache=None, counts: Optional[Tensor] = None) -> Tensor:
         """The one forward walk.  ``keep``: the training forward -- the dict receives one dict of named intermediates per
         sub-block.  ``cache`` (checked by ``_check_cache``): the attention runs on the cache's key/value buffer, the conv block on
-        its state, and the cache advances by the call's frames."""
+        its state, and the cache advances by the call's frames.
+
+        ``counts`` (a stream cache only): ``mask_tail(x, counts=)`` out of place on the way in, the counted ring
+        write and the counted conv step where the uncounted ones were, the counted advance, and ``mask_tail`` in place on the
+        output -- two more launches than the uncounted step.  ``counts=None``: no counted op is called."""
         if x.dim() != 3 or x.shape[1] != self.dim:
             raise AgxError(f"ConformerBlock: x is {tuple(x.shape)}, expected (B, {self.dim}, T)")
         if x.shape[-1] > self.context_x:
@@ -1466,6 +1562,15 @@ class ConformerBlock(nn.Module):
             raise AgxError("a causal ConformerBlock with attention dropout > 0 in training mode has no kernel (eval mode runs)")
         if cache is not None:
             on_device = isinstance(cache, ConformerStreamCache)
+            if counts is not None:
+                x = ops.mask_tail(x, None, counts=counts)
+                x = self.first_ff.run_bct(x, x, None, None, scale=0.5)
+                x = self.attention.run_bct(x, x, None, None, None, kv_cache=(cache.kv, cache.pos, counts))
+                x = self.conv_block.run_bct(x, x, None, None, conv_state=cache.conv_state, counts=counts, mask_counts=False)
+                x = self.second_ff.run_bct(x, x, None, None, scale=0.5)
+                ops.stream_advance(cache.pos, x.shape[-1], counts=counts)
+                x = _ln(self.layer_norm, x)
+                return ops.mask_tail(x, None, out=x, counts=counts)
             x = self.first_ff.run_bct(x, x, None, None, scale=0.5)
             x = self.attention.run_bct(x, x, None, None, None, kv_cache=(cache.kv, cache.pos if on_device else cache.length))
             x = self.conv_block.run_bct(x, x, None, None, conv_state=cache.conv_state)
@@ -1498,19 +1603,24 @@ class ConformerBlock(nn.Module):
         g, g_ff1 = self.first_ff.backward_bct(keep["ff1"], g, scale=0.5)
         return g, g_ff1 + g_attention + g_conv + g_ff2 + [dweight, dbias]
 
-    def run_bct(self, x: Tensor, cache=None) -> Tensor:
+    def run_bct(self, x: Tensor, cache=None, counts=None) -> Tensor:
         """Channel-major (B, dim, T) in and out, T <= context_x.  With autograd on, the backward runs on the HIP kernels too
         (``_ConformerNative``).  ``cache`` (``new_cache`` / ``new_stream_cache``): ``x`` holds the next ``n`` frames of a causal
-        block's sequences; inference only, eval mode."""
+        block's sequences; inference only, eval mode.  ``counts`` (a ``ConformerStreamCache`` only): a contiguous int64 (B,)
+        device tensor; row ``b`` takes the first ``clamp(counts[b], 0, n)`` frames and advances by as many (``_hip_bct``).
+        Refused, before any op: no cache, a ``ConformerCache`` (its ``length`` is a host integer), a wrong dtype, shape or
+        device, a non-contiguous tensor."""
+        if counts is not None:
+            _checked_counts("ConformerBlock", counts, cache, ConformerStreamCache, ConformerCache, x)
         if cache is not None:
             self._check_cache(x, cache)
-            return self._hip_bct(x, None, cache)
+            return self._hip_bct(x, None, cache, counts)
         if needs_grad(x, self):
             return _ConformerNative.apply(self, False, None, x, *list(self.parameters()))
         return self._hip_bct(x)
 
-    def forward(self, x: Tensor, cache=None) -> Tensor:
-        return self.run_bct(x.transpose(1, 2).contiguous(), cache).transpose(1, 2).contiguous()
+    def forward(self, x: Tensor, cache=None, counts=None) -> Tensor:
+        return self.run_bct(x.transpose(1, 2).contiguous(), cache, counts).transpose(1, 2).contiguous()
 
 
 class ConformerCache:

@@ -509,27 +509,30 @@ class CausalVQAE(nn.Module):
         from . import streaming
         return streaming.CodecStream(self, batch, max_chunk, device)
 
-    def encode_stream(self, x_chunk, stream, codebook_n=None):
+    def encode_stream(self, x_chunk, stream, codebook_n=None, counts=None):
         """``encode`` of the next ``n`` whole frames of every row -> (zq (B, D, n), commit_loss, index (B, n, Q)); the conv state
-        is carried in ``stream``, the quantiser is stateless per frame.  Inference only."""
+        is carried in ``stream``, the quantiser is stateless per frame.  Inference only.  ``counts`` (int64 (B,), device): row
+        ``b`` takes the first ``clamp(counts[b], 0, n)`` frames of the chunk (``streaming``: per-row frame counts)."""
         from . import streaming
-        return streaming.encode_stream(self, x_chunk, stream, codebook_n)
+        return streaming.encode_stream(self, x_chunk, stream, codebook_n, counts)
 
-    def decode_stream(self, zq_chunk: Tensor, stream) -> Tensor:
+    def decode_stream(self, zq_chunk: Tensor, stream, counts=None) -> Tensor:
         """Decoder on the next ``n`` frames of (B, D, n) quantised latents -> ``n * scale_factor`` samples per row in the model's
-        output format: the block that lags the input by ``stream.decoder_delay`` samples, zeros before the stream's start."""
+        output format: the block that lags the input by ``stream.decoder_delay`` samples, zeros before the stream's start.
+        ``counts``: as in ``encode_stream``; the samples behind a row's count are exact 0."""
         from . import streaming
-        return streaming.decode_stream(self, zq_chunk, stream)
+        return streaming.decode_stream(self, zq_chunk, stream, counts)
 
-    def forward_stream(self, x_chunk, stream, codebook_n=None):
+    def forward_stream(self, x_chunk, stream, codebook_n=None, counts=None):
         """``encode_stream`` then ``decode_stream`` -> (y, commit_loss, index)."""
         from . import streaming
-        return streaming.forward_stream(self, x_chunk, stream, codebook_n)
+        return streaming.forward_stream(self, x_chunk, stream, codebook_n, counts)
 
-    def decode_flush(self, stream) -> Tensor:
-        """After ``stream.finish()``: the zero-frame steps that bring the decoder's delayed tail out."""
+    def decode_flush(self, stream, rows=None) -> Tensor:
+        """After ``stream.finish()``: the zero-frame steps that bring the decoder's delayed tail out.  ``rows``: only those rows
+        receive the flush frames; the others stay where they are."""
         from . import streaming
-        return streaming.decode_flush(self, stream)
+        return streaming.decode_flush(self, stream, rows)
 
     def sample(self, length=225, device="cuda", normal_var=5e3, n_iters=12):
         """vae.py:324-345: random codes -> dequantise -> decode."""

@@ -1120,6 +1120,47 @@ int agx_ring_write_rate(float *buf, const float *src, const int64_t *pos, int32_
  * row when rows is NULL: the stream of those rows ends at the frames they have received.  Writes end only. */
 int agx_stream_mark_end(const int64_t *pos, int64_t *end, const int64_t *rows, int32_t n_rows, int32_t batch, void *stream);
 
+/* ---- Per-row frame counts -------------------------------------------------------------------------------------
+ * The counted form of every streaming step.  counts is int64 (B,) in device memory, read by the kernels and never by the host:
+ * row b takes the first c_b = clamp(counts[b], 0, n) frames of the chunk, n still the chunk's width.  A captured step replays
+ * with whatever counts holds at the replay.  Memory safety does not depend on the values: every workgroup clamps them (the
+ * stance of "a negative position is read as 0").
+ *   - the valid part of row b's result -- its first c_b rate_out columns -- is bit for bit what the uncounted entry point
+ *     computes for those frames: the count decides which outputs are stored, never how one is computed;
+ *   - a plain (non-ring) fp32 output is exact 0 past the count (a select: NaN in the chunk past the count reaches nothing);
+ *   - a ring column, a history value and a position past the count are not written: with c_b == 0 nothing of row b changes.
+ * Arguments, refusals and kernel choice are those of the uncounted entry point, plus AGX_ERR_NULL_POINTER for counts == NULL.
+ * The uncounted entry points run instances with the count compiled out. */
+/* agx_conv_stream_step on the first c_b rt base positions of row b (KS, NT and the grid as for n). */
+int agx_conv_stream_step_counted(int32_t kind, int32_t c_in, int32_t c_out, int32_t kernel, int32_t stride, int32_t dilation,
+                                 int32_t epilogue, float slope, const float *packed, const float *bias, const float *src, int32_t src_cap,
+                                 const float *res, int32_t res_cap, float *dst, int32_t dst_cap, const int64_t *pos, const int64_t *end,
+                                 const int64_t *counts, int32_t batch, int32_t n, int32_t rate_in, int64_t delay_in, void *stream);
+/* agx_ring_write_rate of the first c_b rate columns of row b, c_b = clamp(counts[b], 0, n_cols / rate). */
+int agx_ring_write_rate_counted(float *buf, const float *src, const int64_t *pos, const int64_t *counts, int32_t batch, int32_t rows,
+                                int32_t n_cols, int32_t cap, int32_t rate, void *stream);
+/* agx_ring_write_pos of the first c_b columns of row b. */
+int agx_ring_write_pos_counted(float *buf, const float *src, int64_t buf_batch_stride, int64_t buf_row_stride, int64_t src_batch_stride,
+                               const int64_t *pos, const int64_t *counts, int32_t batch, int32_t rows, int32_t n, int32_t ring,
+                               void *stream);
+/* agx_attention_alibi_stream with the keys of row b ending at its count: the ring columns of the chunk's frames behind c_b --
+ * which agx_ring_write_pos_counted left unwritten -- are not live (staged as zeros, never multiplied as stored).  The
+ * queries below the count are bit for bit those of the uncounted call on a chunk of c_b frames; every query is written, and
+ * what the ones at and behind the count hold means nothing (NaN where a row has no live key): the caller masks them. */
+int agx_attention_alibi_stream_counted(const float *q, const float *kv, int64_t q_batch_stride, int64_t kv_batch_stride,
+                                       int64_t kv_row_stride, const int64_t *pos, const int64_t *counts, const float *slopes, float *out,
+                                       int32_t batch, int32_t heads, int32_t head_dim, int32_t tq, int32_t window, int32_t kv_ring,
+                                       float scale_div, void *stream);
+/* pos[b] += clamp(counts[b], 0, n). */
+int agx_stream_advance_counted(int64_t *pos, const int64_t *counts, int32_t batch, int64_t n, void *stream);
+/* agx_glu_dwconv_step on the first c_b frames of batch entry b: out is exact 0 at t >= c_b, and hist becomes the last K - 1
+ * values of [hist | g of the first c_b frames] (c_b == 0: not written). */
+int agx_glu_dwconv_step_counted(const float *u, const float *w, const float *bias, const float *gamma, const float *beta,
+                                const float *mean, const float *var, float eps, float *hist, float *out, const int64_t *counts, int32_t B,
+                                int32_t C, int32_t n, int32_t K, void *stream);
+/* agx_mask_tail with int64 counts for lengths: out[b, c, i] = i < clamp(counts[b], 0, t) ? x[b, c, i] : 0; out may be x. */
+int agx_mask_tail_counted(const float *x, const int64_t *counts, float *out, int32_t batch, int32_t channels, int32_t t, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

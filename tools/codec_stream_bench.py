@@ -15,7 +15,12 @@ difference of the two rows is the spread every row has to be read against.
 
 Beside every (a) row: the hop's real time, n * 320 / 24 000 s.
 
+``--counts`` measures the step with per-row frame counts instead, by the same protocol: the uncounted step (twice:
+the spread), the counted step with every count full, and the counted step with half of the rows paused (count 0; at B = 1 the one
+row).  The counts are device tensors the captured kernels read, so every replay takes the same frames.
+
     python tools/codec_stream_bench.py [--plain-only] > profiles/codec_stream.txt
+    python tools/codec_stream_bench.py --counts > profiles/stream_counts.txt
 """
 import argparse
 import os
@@ -81,15 +86,46 @@ def config_s(dev):
     return model
 
 
+def counted(model, dev, gen):
+    """The step with per-row counts beside the uncounted step, B in {1, 8}, n in {1, 4}."""
+    sf = model.scale_factor
+    for b in (1, 8):
+        for n in (1, 4):
+            chunk = (0.1 * torch.randn(b, 1, n * sf, generator=gen)).to(dev)
+            full = torch.full((b,), n, dtype=torch.int64, device=dev)
+            half = full.clone()
+            half[b // 2:] = 0                                                       # B = 1: the one row is paused
+            streams = [model.new_stream(b, max_chunk=4) for _ in range(3)]
+            plain = lambda: model.forward_stream(chunk, streams[0])                 # noqa: E731
+            cases = [("(a) forward_stream step", plain),
+                     ("(a) counts=, every row full", lambda: model.forward_stream(chunk, streams[1], counts=full)),
+                     (f"(a) counts=, {b - b // 2} of {b} rows paused", lambda: model.forward_stream(chunk, streams[2], counts=half)),
+                     ("(a) forward_stream step (again)", plain)]
+            times = measure(cases, STEPS_PER_GRAPH)
+            print(f"\nB = {b}, n = {n} new frames")
+            show(times)
+            names = list(times)
+            base = min(statistics.median(times[names[0]]), statistics.median(times[names[3]]))
+            spread = abs(statistics.median(times[names[0]]) - statistics.median(times[names[3]]))
+            print(f"  full counts / uncounted = {statistics.median(times[names[1]]) / base:.3f}; half paused / uncounted = "
+                  f"{statistics.median(times[names[2]]) / base:.3f}; the uncounted step against itself: {spread:.2f} us")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--plain-only", action="store_true", help="measure (b) alone (a checkout without the streaming step)")
+    ap.add_argument("--counts", action="store_true", help="the step with per-row frame counts beside the uncounted step")
     args = ap.parse_args()
     assert torch.cuda.is_available(), "needs the MI355X"
     dev = "cuda"
     model = config_s(dev)
     sf = model.scale_factor
     gen = torch.Generator().manual_seed(0)
+    if args.counts:
+        print(f"device: {torch.cuda.get_device_name(0)}; config S; per-call time over {ROUNDS} replays of a graph of {STEPS_PER_GRAPH} "
+              "back-to-back calls (median [min .. max]); --counts")
+        counted(model, dev, gen)
+        return
     print(f"device: {torch.cuda.get_device_name(0)}; config S; per-call time over {ROUNDS} replays of a graph of {STEPS_PER_GRAPH} "
           f"back-to-back calls (median [min .. max]){'; --plain-only' if args.plain_only else ''}")
     verdicts = []
