@@ -1118,18 +1118,33 @@ def _checked_pos(op: str, pos, b: int, device) -> Tensor:
     return pos
 
 
-def _checked_counts(op: str, counts, b: int, device) -> Tensor:
+def _checked_counts(op: str, counts, b: int, device, on: Optional[str] = None) -> Tensor:
     """``counts`` as the counted kernels read it (include/agx.h "Per-row frame counts"): a contiguous int64 device tensor of B
-    entries on the operands' device.  The values stay on the device -- the kernels clamp them to [0, n] -- so nothing here
-    synchronises or checks one."""
-    if not isinstance(counts, Tensor) or counts.dtype != torch.int64 or counts.dim() != 1 or counts.numel() != b \
-            or not counts.is_contiguous():
+    entries on the operands' device -- the one place that inspects it, for the ops and for the models and streams above them.
+    The values stay on the device -- the kernels clamp them to [0, n] -- so nothing here synchronises or checks one.  ``on``:
+    what ``device`` belongs to in the caller's words ("the cache on", "the stream on", "the conv state on"); None is an op, whose
+    operands must also be on the GPU."""
+    if not isinstance(counts, Tensor) or counts.dtype != torch.int64 or counts.dim() != 1 or counts.numel() != b:
         what = f"{tuple(counts.shape)} {counts.dtype}" if isinstance(counts, Tensor) else type(counts).__name__
         raise AgxError(f"{op}: counts must be a contiguous int64 device tensor of {b} entries (one frame count per batch row), got {what}")
-    _need_gpu(counts)
+    if not counts.is_contiguous():
+        raise AgxError(f"{op}: counts is not contiguous (stride {tuple(counts.stride())}): the kernels read {b} adjacent int64")
+    if on is None:
+        _need_gpu(counts)
     if counts.device != device:
-        raise AgxError(f"{op}: counts is on '{counts.device}', the operands are on '{device}'")
+        raise AgxError(f"{op}: counts is on '{counts.device}', {on or 'the operands are on'} '{device}'")
     return counts
+
+
+def _row_slices(what: str, rows, batch: int, of: str) -> list:
+    """The slices a per-row reset fills, one per entry of ``rows`` (None: the one slice of every row), for a cache or stream
+    (``of``) of ``batch`` rows; a row outside it is refused before anything is filled."""
+    if rows is None:
+        return [slice(None)]
+    rows = [int(r) for r in rows]
+    if any(not 0 <= r < batch for r in rows):
+        raise AgxError(f"{what}: rows {rows} are not rows of a {of} of batch {batch}")
+    return [slice(r, r + 1) for r in rows]
 
 
 def attention_alibi_stream(q: Tensor, kv: Tensor, pos: Tensor, slopes: Tensor, heads: int, head_dim: int, scale_div: float,

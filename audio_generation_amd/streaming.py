@@ -179,12 +179,8 @@ class CodecStream:
         self.end = torch.full((batch,), STREAM_LIVE, dtype=torch.int64, device=self.device)
 
     def _rows(self, rows, what: str) -> Optional[List[int]]:
-        if rows is None:
-            return None
-        rows = [int(r) for r in rows]
-        if any(not 0 <= r < self.batch for r in rows):
-            raise AgxError(f"{what}: rows {rows} are not rows of a stream of batch {self.batch}")
-        return rows
+        """``rows`` as checked ints (None: every row)."""
+        return None if rows is None else [sel.start for sel in ops._row_slices(what, rows, self.batch, "stream")]
 
     def finish(self, rows=None) -> None:
         """The streams of ``rows`` (default: every row) end at the frames their decoders have received: ``end[r] = dec_pos[r]``,
@@ -197,8 +193,7 @@ class CodecStream:
     def reset(self, rows=None) -> None:
         """``rows`` (default: every row) start a new stream at their next call: positions to 0, ``end`` to live and those rows of
         every ring to zero, all device fills.  Call it between steps, outside any captured graph."""
-        rows = self._rows(rows, "reset")
-        for sel in ([slice(None)] if rows is None else [slice(r, r + 1) for r in rows]):
+        for sel in ops._row_slices("reset", rows, self.batch, "stream"):
             self.enc_pos[sel].zero_()
             self.dec_pos[sel].zero_()
             self.end[sel].fill_(STREAM_LIVE)
@@ -251,20 +246,6 @@ def run_unit(u: Unit, p: UnitPlan, ring: Tensor, dst: Tensor, dst_ring: bool, po
                                 slope=post or 0.0, counts=counts)
 
 
-def _check_counts(what: str, counts, batch: int, device) -> None:
-    """The refusals of ``counts=``, before the first launch.  No value is read: the kernels clamp every entry to [0, n]."""
-    if counts is None:
-        return
-    if not isinstance(counts, Tensor) or counts.dtype != torch.int64 or counts.dim() != 1 or counts.numel() != batch:
-        got = f"{tuple(counts.shape)} {counts.dtype}" if isinstance(counts, Tensor) else type(counts).__name__
-        raise AgxError(f"{what}: counts must be a contiguous int64 device tensor of {batch} entries (one frame count per batch row), "
-                       f"got {got}")
-    if not counts.is_contiguous():
-        raise AgxError(f"{what}: counts is not contiguous (stride {tuple(counts.stride())}): the kernels read {batch} adjacent int64")
-    if counts.device != device:
-        raise AgxError(f"{what}: counts is on '{counts.device}', the stream on '{device}'")
-
-
 def _check(model, stream: CodecStream, x: Tensor, what: str, per_frame: int, channels: int, counts=None) -> int:
     """Every refusal of a step, before the first launch; returns the chunk's frames."""
     if not isinstance(stream, CodecStream) or stream.model_id != id(model):
@@ -286,7 +267,8 @@ def _check(model, stream: CodecStream, x: Tensor, what: str, per_frame: int, cha
         raise AgxError(f"{what}: a chunk of {n} frames exceeds the stream's max_chunk = {stream.max_chunk}")
     if x.dtype != torch.float32:
         raise AgxError(f"{what}: expected float32, got {x.dtype}")
-    _check_counts(what, counts, stream.batch, stream.device)
+    if counts is not None:
+        ops._checked_counts(what, counts, stream.batch, stream.device, on="the stream on")
     return n
 
 

@@ -791,7 +791,59 @@ class _TransformerNative(torch.autograd.Function):
         return (None, None, g if ctx.needs_input_grad[2] else None, gy, *grads)
 
 
-class TransformerCache:
+def _layer_kv(kv, layer: int) -> Tensor:
+    return kv[layer] if isinstance(kv, list) else kv      # a Transformer keeps one buffer per layer, a ConformerBlock its one
+
+
+class _HostCache:
+    """A key/value cache whose ``length`` -- the frames every row holds -- is one host integer.  ``state``: further per-row state
+    tensors that ``reset`` zeroes (none for a Transformer, the conv state for a ConformerBlock)."""
+
+    def __init__(self, kv, batch: int, capacity: int, window: Optional[int] = None, state: tuple = ()):
+        self.kv, self.batch, self.capacity, self.length, self.window, self._state = kv, batch, capacity, 0, window, state
+
+    def reset(self) -> None:
+        self.length = 0
+        for t in self._state:
+            t.zero_()
+
+    def kv_cache(self, layer: int = 0, counts=None) -> tuple:
+        """The ``kv_cache=`` of layer ``layer``'s attention call (``Attention._run_causal_bct``)."""
+        return _layer_kv(self.kv, layer), self.length
+
+    def advance(self, n: int, counts=None) -> None:
+        self.length += n
+
+
+class _StreamCache:
+    """A ring key/value cache whose positions live in device memory: ``pos``, int64 (B,), one per batch row, read by the kernels
+    and advanced by a kernel.  ``state``: as in ``_HostCache``."""
+
+    def __init__(self, kv, pos: Tensor, capacity: int, window: int, max_chunk: int, state: tuple = ()):
+        self.kv, self.pos, self.batch, self.capacity, self.window, self.max_chunk = kv, pos, pos.numel(), capacity, window, max_chunk
+        self._state = state
+
+    def reset(self, rows=None) -> None:
+        """Zero the positions (and the per-row state) of ``rows`` (default: every row) with device fills: those rows start a new
+        stream at their next call; what their ring columns hold is never read again.  Call it between steps, outside any
+        captured graph."""
+        for sel in ops._row_slices("reset", rows, self.batch, "cache"):
+            for t in (self.pos, *self._state):
+                t[sel].zero_()
+
+    def positions(self) -> list:
+        """The positions as a list of ints.  Synchronises: for tests and debugging, never called in the walk."""
+        return self.pos.tolist()
+
+    def kv_cache(self, layer: int = 0, counts: Optional[Tensor] = None) -> tuple:
+        """The ``kv_cache=`` of layer ``layer``'s attention call (``Attention._run_causal_bct``); ``counts``: the counted step."""
+        return _layer_kv(self.kv, layer), self.pos, counts
+
+    def advance(self, n: int, counts: Optional[Tensor] = None) -> None:
+        ops.stream_advance(self.pos, n, counts=counts)       # once per call: every layer read the same positions
+
+
+class TransformerCache(_HostCache):
     """The key/value cache of a causal ``Transformer`` (``Transformer.new_cache``): per layer one fp32
     (B, 2*H*Dh, capacity) buffer, K rows first, then V rows -- the kv layout of ``agx_attention_alibi_causal`` with
     ``kv_row_stride = capacity`` -- and one ``length``, the frames every layer holds.  The buffers come from ``torch.empty``
@@ -800,15 +852,19 @@ class TransformerCache:
     On a windowed Transformer (``window`` is its window) every buffer is a ring: frame ``p`` lives in column ``p mod capacity``,
     ``length`` keeps counting (a Python int: no 32-bit limit) and the kernel reads no column outside a workgroup's window."""
 
-    def __init__(self, kv: list, batch: int, capacity: int, window: Optional[int] = None):
-        self.kv, self.batch, self.capacity, self.length, self.window = kv, batch, capacity, 0, window
 
-    def reset(self) -> None:
-        self.length = 0
+class ConformerCache(_HostCache):
+    """The cache of a causal ``ConformerBlock`` (``ConformerBlock.new_cache``): ``kv``, the attention's fp32
+    (B, 2*H*Dh, capacity) key/value buffer with one ``length`` as ``TransformerCache`` has them -- a ring on a windowed block --,
+    and ``conv_state``, the conv block's (B, C, K - 1) post-GLU history (zeros: the start of a stream), which ``reset`` zeroes."""
+
+    def __init__(self, kv: Tensor, batch: int, capacity: int, window: Optional[int], conv_state: Tensor):
+        super().__init__(kv, batch, capacity, window, (conv_state,))
+        self.conv_state = conv_state
 
 
-def _checked_counts(what: str, counts, cache, stream_type, host_type, x: Tensor) -> Tensor:
-    """The refusals of ``counts=`` on a cached call, before any op.  No value is read: the kernels clamp every entry to [0, n]."""
+def _checked_counts(what: str, counts, cache, stream_type, host_type) -> Tensor:
+    """The refusals of ``counts=`` on a cached call, before any op: the cache's kind here, the tensor in ``ops._checked_counts``."""
     if cache is None:
         raise AgxError(f"{what}: counts= without cache=: a per-row frame count belongs to a cached step on a stream cache "
                        "(new_stream_cache)")
@@ -817,19 +873,10 @@ def _checked_counts(what: str, counts, cache, stream_type, host_type, x: Tensor)
                        f"counts need the device-held positions of a {stream_type.__name__} (new_stream_cache)")
     if not isinstance(cache, stream_type):
         raise AgxError(f"{what}: counts= needs a {stream_type.__name__} (new_stream_cache), got {type(cache).__name__}")
-    b = cache.batch
-    if not isinstance(counts, Tensor) or counts.dtype != torch.int64 or counts.dim() != 1 or counts.numel() != b:
-        got = f"{tuple(counts.shape)} {counts.dtype}" if isinstance(counts, Tensor) else type(counts).__name__
-        raise AgxError(f"{what}: counts must be a contiguous int64 device tensor of {b} entries (one frame count per batch row), "
-                       f"got {got}")
-    if not counts.is_contiguous():
-        raise AgxError(f"{what}: counts is not contiguous (stride {tuple(counts.stride())}): the kernels read {b} adjacent int64")
-    if counts.device != cache.pos.device:
-        raise AgxError(f"{what}: counts is on '{counts.device}', the cache on '{cache.pos.device}'")
-    return counts
+    return ops._checked_counts(what, counts, cache.batch, cache.pos.device, on="the cache on")
 
 
-class TransformerStreamCache:
+class TransformerStreamCache(_StreamCache):
     """The ring key/value cache of a windowed causal ``Transformer`` with the positions in device memory, one per batch row
     (``Transformer.new_stream_cache``): per layer one fp32 (B, 2*H*Dh, capacity) ring from ``torch.empty``, never cleared, and
     ``pos``, an int64 (B,) device tensor of the frames every row has consumed.  The kernels read ``pos`` (``ops.ring_write_pos``,
@@ -841,24 +888,63 @@ class TransformerStreamCache:
     ``n <= max_chunk = min(capacity - window + 1, context_x)``: stricter than ``TransformerCache`` at the start of a stream, where
     ``n + min(window - 1, length) <= capacity`` lets the first call fill the whole ring."""
 
-    def __init__(self, kv: list, pos: Tensor, capacity: int, window: int, max_chunk: int):
-        self.kv, self.pos, self.batch, self.capacity, self.window, self.max_chunk = kv, pos, pos.numel(), capacity, window, max_chunk
 
-    def reset(self, rows=None) -> None:
-        """Zero the positions of ``rows`` (default: every row) with a device fill: those rows start a new stream at their next
-        call; what their ring columns hold is never read again.  Call it between steps, outside any captured graph."""
-        if rows is None:
-            self.pos.zero_()
-            return
-        rows = [int(r) for r in rows]
-        if any(not 0 <= r < self.batch for r in rows):
-            raise AgxError(f"reset: rows {rows} are not rows of a cache of batch {self.batch}")
-        for r in rows:
-            self.pos[r:r + 1].zero_()
+class ConformerStreamCache(_StreamCache):
+    """The cache of a windowed causal ``ConformerBlock`` with the positions in device memory (``ConformerBlock.new_stream_cache``):
+    the ring ``kv`` and the int64 (B,) ``pos`` of ``TransformerStreamCache``, ``max_chunk`` as there, and ``conv_state``
+    (B, C, K - 1), whose rows ``reset`` zeroes with the positions.  The conv state holds values, not positions: the step kernel
+    shifts it by the call's frames whatever the row's age, so a cached step makes no host decision and every row is a stream of
+    its own."""
 
-    def positions(self) -> list:
-        """The positions as a list of ints.  Synchronises: for tests and debugging, never called in the walk."""
-        return self.pos.tolist()
+    def __init__(self, kv: Tensor, pos: Tensor, capacity: int, window: int, max_chunk: int, conv_state: Tensor):
+        super().__init__(kv, pos, capacity, window, max_chunk, (conv_state,))
+        self.conv_state = conv_state
+
+
+def _new_kv(what: str, model, inner_dims: list, batch: int, capacity: Optional[int]) -> tuple:
+    """The buffers of ``new_cache`` / ``new_stream_cache``: one empty fp32 (B, 2*H*Dh, capacity) per entry of ``inner_dims`` on the
+    parameters' device, ``capacity`` (default ``context_x``; a ring holds at least the window), and ``max_chunk``, the frames a
+    call on device-held positions may take: the worst case over every position (None without a window)."""
+    capacity = model.context_x if capacity is None else int(capacity)
+    if batch < 1 or capacity < 1:
+        raise AgxError(f"{what}: batch = {batch}, capacity = {capacity}")
+    if model.window is not None and capacity < model.window:
+        raise AgxError(f"{what}: a ring of capacity = {capacity} cannot hold a window of {model.window} frames")
+    device = next(model.parameters()).device
+    kv = [torch.empty((batch, 2 * d, capacity), dtype=torch.float32, device=device) for d in inner_dims]
+    return kv, capacity, None if model.window is None else min(capacity - model.window + 1, model.context_x)
+
+
+def _check_cached_call(model, this: str, x: Tensor, cache, on_device: bool, dim: Optional[int] = None) -> None:
+    """The refusals a cached call of a ``Transformer`` or a ``ConformerBlock`` (``this``) shares, before any op and without reading
+    a position: no gradient, no active dropout, the batch, the window, and the frames the cache can take -- on device-held
+    positions ``max_chunk``, the worst case; on a host ring what the first new query still sees; on a linear buffer its end.
+    ``dim``: a ConformerBlock's, the strict caller -- it also checks its ``dim``, and on a host cache it refuses ``n < 1`` and a
+    window other than its own even where it has none; a Transformer does neither (its attention layer's own check follows,
+    still before any op)."""
+    strict = dim is not None
+    if needs_grad(x, model):
+        raise AgxError("there is no backward through a cached call: run it under torch.no_grad()")
+    if model._dropout_active():
+        raise AgxError("a cached call with an active dropout site (training mode, dropout > 0) has no kernel")
+    if x.dim() != 3 or x.shape[0] != cache.batch or (strict and x.shape[1] != dim):
+        raise AgxError(f"cached call: x is {tuple(x.shape)}, the cache was made for batch {cache.batch}"
+                       + (f" of a block of dim {dim}" if strict else ""))
+    if (strict or on_device or model.window is not None) and cache.window != model.window:
+        raise AgxError(f"the cache was made for window {cache.window}, {this} has window {model.window}")
+    n, least = x.shape[-1], 1 if strict else 0
+    if on_device:
+        if n < 1 or n > cache.max_chunk:
+            raise AgxError(f"stream cache: a call takes 1 <= n <= max_chunk = {cache.max_chunk} frames (min(capacity {cache.capacity} "
+                           f"- window {model.window} + 1, context_x {model.context_x}): the worst case over every position), got {n}")
+    elif model.window is not None:       # a ring: the new frames must not overwrite what their first query still sees
+        behind = min(model.window - 1, cache.length)
+        if n < least or n + behind > cache.capacity:
+            raise AgxError(f"cached call: {n} new frames + the {behind} cached frames their window reaches exceed the ring's "
+                           f"capacity {cache.capacity}")
+    elif n < least or cache.length + n > min(cache.capacity, model.context_x):
+        raise AgxError(f"cached call: {cache.length} cached + {n} new frames exceed min(capacity {cache.capacity}, context_x "
+                       f"{model.context_x}) = {min(cache.capacity, model.context_x)}")
 
 
 class Transformer(nn.Module):
@@ -892,13 +978,7 @@ class Transformer(nn.Module):
         new frames must not overwrite a cached frame their first query still sees -- and the stream has no end."""
         if not self.causal or self.cross_attention:
             raise AgxError("new_cache: a key/value cache needs a causal self-attention Transformer (causal=True, no context_y)")
-        capacity = self.context_x if capacity is None else int(capacity)
-        if batch < 1 or capacity < 1:
-            raise AgxError(f"new_cache: batch = {batch}, capacity = {capacity}")
-        if self.window is not None and capacity < self.window:
-            raise AgxError(f"new_cache: a ring of capacity = {capacity} cannot hold a window of {self.window} frames")
-        device = next(self.parameters()).device
-        kv = [torch.empty((batch, 2 * a.inner_dim, capacity), dtype=torch.float32, device=device) for a, _ in self.layers]
+        kv, capacity, _ = _new_kv("new_cache", self, [a.inner_dim for a, _ in self.layers], batch, capacity)
         return TransformerCache(kv, batch, capacity, self.window)
 
     def new_stream_cache(self, batch: int, capacity: Optional[int] = None) -> "TransformerStreamCache":
@@ -908,62 +988,23 @@ class Transformer(nn.Module):
         if not self.causal or self.cross_attention or self.window is None:
             raise AgxError("new_stream_cache: device-held positions need a windowed causal self-attention Transformer "
                            "(causal=True, window=W, no context_y)")
-        capacity = self.context_x if capacity is None else int(capacity)
-        if batch < 1 or capacity < 1:
-            raise AgxError(f"new_stream_cache: batch = {batch}, capacity = {capacity}")
-        if capacity < self.window:
-            raise AgxError(f"new_stream_cache: a ring of capacity = {capacity} cannot hold a window of {self.window} frames")
-        device = next(self.parameters()).device
-        kv = [torch.empty((batch, 2 * a.inner_dim, capacity), dtype=torch.float32, device=device) for a, _ in self.layers]
-        pos = torch.zeros(batch, dtype=torch.int64, device=device)
-        return TransformerStreamCache(kv, pos, capacity, self.window, min(capacity - self.window + 1, self.context_x))
+        kv, capacity, max_chunk = _new_kv("new_stream_cache", self, [a.inner_dim for a, _ in self.layers], batch, capacity)
+        pos = torch.zeros(batch, dtype=torch.int64, device=kv[0].device)
+        return TransformerStreamCache(kv, pos, capacity, self.window, max_chunk)
 
-    def _check_stream_cache(self, x: Tensor, cache: "TransformerStreamCache") -> None:
-        """The refusals of a call on a stream cache, before any op; none of them reads a position."""
-        if not self.causal or self.cross_attention or self.window is None:
-            raise AgxError("a stream cache needs a windowed causal self-attention Transformer (causal=True, window=W, no context_y)")
-        if needs_grad(x, self):
-            raise AgxError("there is no backward through a cached call: run it under torch.no_grad()")
-        if self._dropout_active():
-            raise AgxError("a cached call with an active dropout site (training mode, dropout > 0) has no kernel")
-        for attention, _ in self.layers:
-            if attention.attention_dtype != "fp32":
-                raise AgxError(f"causal attention runs in fp32: attention_dtype = {attention.attention_dtype!r} has no kernel")
+    def _check_cache(self, x: Tensor, cache) -> None:
+        """The refusals of a cached call, before any op; on a stream cache none of them reads a position."""
+        on_device = isinstance(cache, TransformerStreamCache)
+        if not self.causal or self.cross_attention or (on_device and self.window is None):
+            raise AgxError("a stream cache needs a windowed causal self-attention Transformer (causal=True, window=W, no context_y)"
+                           if on_device else "a key/value cache needs a causal self-attention Transformer (causal=True, no context_y)")
+        _check_cached_call(self, "this Transformer", x, cache, on_device)
+        if on_device:       # on a host cache the attention layer itself refuses it, still before any op
+            for attention, _ in self.layers:
+                if attention.attention_dtype != "fp32":
+                    raise AgxError(f"causal attention runs in fp32: attention_dtype = {attention.attention_dtype!r} has no kernel")
         if len(cache.kv) != len(self.layers):
             raise AgxError(f"the cache holds {len(cache.kv)} layers, this Transformer has {len(self.layers)}")
-        if x.dim() != 3 or x.shape[0] != cache.batch:
-            raise AgxError(f"cached call: x is {tuple(x.shape)}, the cache was made for batch {cache.batch}")
-        if cache.window != self.window:
-            raise AgxError(f"the cache was made for window {cache.window}, this Transformer has window {self.window}")
-        n = x.shape[-1]
-        if n < 1 or n > cache.max_chunk:
-            raise AgxError(f"stream cache: a call takes 1 <= n <= max_chunk = {cache.max_chunk} frames (min(capacity {cache.capacity} "
-                           f"- window {self.window} + 1, context_x {self.context_x}): the worst case over every position), got {n}")
-
-    def _check_cache(self, x: Tensor, cache: TransformerCache) -> None:
-        """The refusals of a cached call, before any op."""
-        if not self.causal or self.cross_attention:
-            raise AgxError("a key/value cache needs a causal self-attention Transformer (causal=True, no context_y)")
-        if needs_grad(x, self):
-            raise AgxError("there is no backward through a cached call: run it under torch.no_grad()")
-        if self._dropout_active():
-            raise AgxError("a cached call with an active dropout site (training mode, dropout > 0) has no kernel")
-        if len(cache.kv) != len(self.layers):
-            raise AgxError(f"the cache holds {len(cache.kv)} layers, this Transformer has {len(self.layers)}")
-        if x.dim() != 3 or x.shape[0] != cache.batch:
-            raise AgxError(f"cached call: x is {tuple(x.shape)}, the cache was made for batch {cache.batch}")
-        if self.window is not None:       # a ring: the new frames must not overwrite what their first query still sees
-            if cache.window != self.window:
-                raise AgxError(f"the cache was made for window {cache.window}, this Transformer has window {self.window}")
-            behind = min(self.window - 1, cache.length)
-            if x.shape[-1] + behind > cache.capacity:
-                raise AgxError(f"cached call: {x.shape[-1]} new frames + the {behind} cached frames their window reaches exceed "
-                               f"the ring's capacity {cache.capacity}")
-            return
-        limit = min(cache.capacity, self.context_x)
-        if cache.length + x.shape[-1] > limit:
-            raise AgxError(f"cached call: {cache.length} cached + {x.shape[-1]} new frames exceed min(capacity {cache.capacity}, "
-                           f"context_x {self.context_x}) = {limit}")
 
     def _check_lengths(self, x: Tensor, y: Optional[Tensor], cache, lengths, y_lengths) -> tuple:
         """The refusals of a ragged call, before any op, and its (lengths, y_lengths) as checked device tensors."""
@@ -1037,7 +1078,6 @@ class Transformer(nn.Module):
         contract of the padded tails above -- valid frames bit for bit those of an uncounted call on them, exact 0 behind the
         count, NaN there harmless.  ``counts=None``: no counted op is called."""
         lengths, y_lengths = lens if lens is not None else (None, None)
-        on_device = isinstance(cache, TransformerStreamCache)
         if (y is not None) != self.cross_attention:
             raise AgxError("Cross attention requires two inputs: this Transformer was built with context_y and got no y"
                            if y is None else "this Transformer was built without context_y and takes no second sequence y")
@@ -1059,10 +1099,8 @@ class Transformer(nn.Module):
         for li, (attention, ff) in enumerate(self.layers):
             kept = None if keep is None else {}
             drop = None if seed is None else (seed, li)
-            if counts is not None:
-                x = attention.run_bct(x, x, kept, None, drop, kv_cache=(cache.kv[li], cache.pos, counts))
-            elif cache is not None:
-                x = attention.run_bct(x, x, kept, None, drop, kv_cache=(cache.kv[li], cache.pos if on_device else cache.length))
+            if cache is not None:
+                x = attention.run_bct(x, x, kept, None, drop, kv_cache=cache.kv_cache(li, counts))
             elif packed is not None:
                 x = attention.run_bct(x, x, kept, y if attention.cross_attention else None, drop,
                                       **packed.attn_args(attention.cross_attention))
@@ -1074,10 +1112,8 @@ class Transformer(nn.Module):
             x = ff.run_bct(x, x, kept, drop)
             if keep is not None:
                 keep.append(kept)
-        if on_device:
-            ops.stream_advance(cache.pos, x.shape[-1], counts=counts)      # once per call: every layer read the same positions
-        elif cache is not None:
-            cache.length += x.shape[-1]
+        if cache is not None:
+            cache.advance(x.shape[-1], counts)
         if lengths is not None:
             x = ops.mask_tail(x, lengths, out=x)
         if counts is not None:
@@ -1173,17 +1209,14 @@ class Transformer(nn.Module):
         if counts is not None:
             if lengths is not None or y_lengths is not None:
                 raise AgxError("counts= with lengths=: a counted call is a cached causal step and takes no lengths")
-            _checked_counts("Transformer", counts, cache, TransformerStreamCache, TransformerCache, x)
+            _checked_counts("Transformer", counts, cache, TransformerStreamCache, TransformerCache)
         if lengths is not None or y_lengths is not None:
             lens = self._check_lengths(x, y, cache, lengths, y_lengths)
             if needs_grad(x, self) or (y is not None and torch.is_grad_enabled() and y.requires_grad):
                 return _TransformerNative.apply(self, lens, x, y, *list(self.parameters()))
             return self._hip_bct(x, None, y, lens=lens)
         if cache is not None:
-            if isinstance(cache, TransformerStreamCache):
-                self._check_stream_cache(x, cache)
-            else:
-                self._check_cache(x, cache)
+            self._check_cache(x, cache)
             if y is not None:
                 raise AgxError("this Transformer was built without context_y and takes no second sequence y")
             return self._hip_bct(x, None, None, cache, counts=counts)
@@ -1330,16 +1363,8 @@ class ConformerConvBlock(nn.Module):
         """The refusals of ``counts=``, before any op.  No value is read: the kernel clamps every entry to [0, n]."""
         if conv_state is None:
             raise AgxError("ConformerConvBlock: counts= without a conv state: a per-row frame count belongs to a cached step")
-        b = conv_state.shape[0] if isinstance(conv_state, Tensor) else 0
-        if not isinstance(counts, Tensor) or counts.dtype != torch.int64 or counts.dim() != 1 or counts.numel() != b:
-            got = f"{tuple(counts.shape)} {counts.dtype}" if isinstance(counts, Tensor) else type(counts).__name__
-            raise AgxError(f"ConformerConvBlock: counts must be a contiguous int64 device tensor of {b} entries (one frame count per "
-                           f"batch row), got {got}")
-        if not counts.is_contiguous():
-            raise AgxError(f"ConformerConvBlock: counts is not contiguous (stride {tuple(counts.stride())}): the kernel reads {b} "
-                           "adjacent int64")
-        if counts.device != conv_state.device:
-            raise AgxError(f"ConformerConvBlock: counts is on '{counts.device}', the conv state on '{conv_state.device}'")
+        b, device = (conv_state.shape[0], conv_state.device) if isinstance(conv_state, Tensor) else (0, None)
+        ops._checked_counts("ConformerConvBlock", counts, b, device, on="the conv state on")
         if x.dim() == 3 and x.shape[-1] > ops.CONFORMER_MAX_STEP:
             raise AgxError(f"ConformerConvBlock: a counted call takes at most CONFORMER_MAX_STEP = {ops.CONFORMER_MAX_STEP} frames (the "
                            f"one launch of glu_dwconv_step), got {x.shape[-1]}")
@@ -1434,7 +1459,7 @@ class ConformerConvBlock(nn.Module):
         if not isinstance(cache, (ConformerCache, ConformerStreamCache)):
             raise AgxError(f"cache= takes a ConformerCache or a ConformerStreamCache (new_cache / new_stream_cache), got {type(cache).__name__}")
         if counts is not None:
-            _checked_counts("ConformerConvBlock", counts, cache, ConformerStreamCache, ConformerCache, x)
+            _checked_counts("ConformerConvBlock", counts, cache, ConformerStreamCache, ConformerCache)
         return self.run_bct(x.transpose(1, 2).contiguous(), conv_state=cache.conv_state, counts=counts).transpose(1, 2).contiguous()
 
 
@@ -1472,22 +1497,13 @@ class ConformerBlock(nn.Module):
         self.causal, self.window = bool(causal), self.attention.window
         self.last_dropout_seed = None
 
-    def _new_kv(self, what: str, batch: int, capacity: Optional[int]) -> tuple:
-        capacity = self.context_x if capacity is None else int(capacity)
-        if batch < 1 or capacity < 1:
-            raise AgxError(f"{what}: batch = {batch}, capacity = {capacity}")
-        if self.window is not None and capacity < self.window:
-            raise AgxError(f"{what}: a ring of capacity = {capacity} cannot hold a window of {self.window} frames")
-        device = next(self.parameters()).device
-        return torch.empty((batch, 2 * self.attention.inner_dim, capacity), dtype=torch.float32, device=device), capacity
-
     def new_cache(self, batch: int, capacity: Optional[int] = None) -> "ConformerCache":
         """An empty cache for ``batch`` sequences (``ConformerCache``): the attention's key/value buffer of ``capacity`` columns
         (default ``context_x``; a ring of at least ``window`` columns on a windowed block) as ``Transformer.new_cache`` makes it,
         and the conv state at the start of a stream.  Needs a causal block."""
         if not self.causal:
             raise AgxError("new_cache: a cache needs a causal ConformerBlock (causal=True)")
-        kv, capacity = self._new_kv("new_cache", batch, capacity)
+        (kv,), capacity, _ = _new_kv("new_cache", self, [self.attention.inner_dim], batch, capacity)
         return ConformerCache(kv, batch, capacity, self.window, self.conv_block.new_conv_state(batch))
 
     def new_stream_cache(self, batch: int, capacity: Optional[int] = None) -> "ConformerStreamCache":
@@ -1496,10 +1512,9 @@ class ConformerBlock(nn.Module):
         block.  A call takes ``1 <= n <= cache.max_chunk`` frames."""
         if not self.causal or self.window is None:
             raise AgxError("new_stream_cache: device-held positions need a windowed causal ConformerBlock (causal=True, window=W)")
-        kv, capacity = self._new_kv("new_stream_cache", batch, capacity)
+        (kv,), capacity, max_chunk = _new_kv("new_stream_cache", self, [self.attention.inner_dim], batch, capacity)
         pos = torch.zeros(batch, dtype=torch.int64, device=kv.device)
-        return ConformerStreamCache(kv, pos, capacity, self.window, min(capacity - self.window + 1, self.context_x),
-                                    self.conv_block.new_conv_state(batch))
+        return ConformerStreamCache(kv, pos, capacity, self.window, max_chunk, self.conv_block.new_conv_state(batch))
 
     def _check_cache(self, x: Tensor, cache) -> None:
         """The refusals of a cached call, before any op; on a stream cache none of them reads a position."""
@@ -1509,38 +1524,18 @@ class ConformerBlock(nn.Module):
         if not self.causal or (on_device and self.window is None):
             raise AgxError("a stream cache needs a windowed causal ConformerBlock (causal=True, window=W)" if on_device else
                            "a cache needs a causal ConformerBlock (causal=True)")
-        if needs_grad(x, self):
-            raise AgxError("there is no backward through a cached call: run it under torch.no_grad()")
-        if self._dropout_active():
-            raise AgxError("a cached call with an active dropout site (training mode, dropout > 0) has no kernel")
+        _check_cached_call(self, "this block", x, cache, on_device, self.dim)
         if self.conv_block.net[4].training:
             raise AgxError("a cached call with BatchNorm in training mode: batch statistics of a chunk are not those of the sequence "
                            "(a cached call runs in eval mode)")
         if self.attention.attention_dtype != "fp32":
             raise AgxError(f"causal attention runs in fp32: attention_dtype = {self.attention.attention_dtype!r} has no kernel")
-        if x.dim() != 3 or x.shape[0] != cache.batch or x.shape[1] != self.dim:
-            raise AgxError(f"cached call: x is {tuple(x.shape)}, the cache was made for batch {cache.batch} of a block of dim {self.dim}")
         if tuple(cache.kv.shape) != (cache.batch, 2 * self.attention.inner_dim, cache.capacity):
             raise AgxError(f"the cache's key/value buffer is {tuple(cache.kv.shape)}, this block needs "
                            f"{(cache.batch, 2 * self.attention.inner_dim, cache.capacity)}")
-        if cache.window != self.window:
-            raise AgxError(f"the cache was made for window {cache.window}, this block has window {self.window}")
         want = (cache.batch, self.dim, self.conv_block.kernel_size - 1)
         if tuple(cache.conv_state.shape) != want:
             raise AgxError(f"the cache's conv state is {tuple(cache.conv_state.shape)}, this block needs {want} (B, C, K - 1)")
-        n = x.shape[-1]
-        if on_device:
-            if n < 1 or n > cache.max_chunk:
-                raise AgxError(f"stream cache: a call takes 1 <= n <= max_chunk = {cache.max_chunk} frames (min(capacity {cache.capacity} "
-                               f"- window {self.window} + 1, context_x {self.context_x}): the worst case over every position), got {n}")
-        elif self.window is not None:       # a ring: the new frames must not overwrite what their first query still sees
-            behind = min(self.window - 1, cache.length)
-            if n < 1 or n + behind > cache.capacity:
-                raise AgxError(f"cached call: {n} new frames + the {behind} cached frames their window reaches exceed the ring's "
-                               f"capacity {cache.capacity}")
-        elif n < 1 or cache.length + n > min(cache.capacity, self.context_x):
-            raise AgxError(f"cached call: {cache.length} cached + {n} new frames exceed min(capacity {cache.capacity}, context_x "
-                           f"{self.context_x}) = {min(cache.capacity, self.context_x)}")
 
     def _dropout_active(self) -> bool:
         sites = [self.attention.dropout, self.conv_block.net[7]] + [f.net[i] for f in (self.first_ff, self.second_ff) for i in (3, 5)]
@@ -1561,25 +1556,16 @@ class ConformerBlock(nn.Module):
         if self.causal and _active_p(self.attention.dropout) > 0:
             raise AgxError("a causal ConformerBlock with attention dropout > 0 in training mode has no kernel (eval mode runs)")
         if cache is not None:
-            on_device = isinstance(cache, ConformerStreamCache)
             if counts is not None:
                 x = ops.mask_tail(x, None, counts=counts)
-                x = self.first_ff.run_bct(x, x, None, None, scale=0.5)
-                x = self.attention.run_bct(x, x, None, None, None, kv_cache=(cache.kv, cache.pos, counts))
-                x = self.conv_block.run_bct(x, x, None, None, conv_state=cache.conv_state, counts=counts, mask_counts=False)
-                x = self.second_ff.run_bct(x, x, None, None, scale=0.5)
-                ops.stream_advance(cache.pos, x.shape[-1], counts=counts)
-                x = _ln(self.layer_norm, x)
-                return ops.mask_tail(x, None, out=x, counts=counts)
             x = self.first_ff.run_bct(x, x, None, None, scale=0.5)
-            x = self.attention.run_bct(x, x, None, None, None, kv_cache=(cache.kv, cache.pos if on_device else cache.length))
-            x = self.conv_block.run_bct(x, x, None, None, conv_state=cache.conv_state)
+            x = self.attention.run_bct(x, x, None, None, None, kv_cache=cache.kv_cache(0, counts))
+            # the conv block's own mask is off on a counted step: the block masks its output once, behind the last LayerNorm
+            x = self.conv_block.run_bct(x, x, None, None, conv_state=cache.conv_state, counts=counts, mask_counts=counts is None)
             x = self.second_ff.run_bct(x, x, None, None, scale=0.5)
-            if on_device:
-                ops.stream_advance(cache.pos, x.shape[-1])
-            else:
-                cache.length += x.shape[-1]
-            return _ln(self.layer_norm, x)
+            cache.advance(x.shape[-1], counts)
+            x = _ln(self.layer_norm, x)
+            return x if counts is None else ops.mask_tail(x, None, out=x, counts=counts)
         seed = None
         if self._dropout_active():
             seed = self.last_dropout_seed = ops.draw_dropout_seed()
@@ -1611,7 +1597,7 @@ class ConformerBlock(nn.Module):
         Refused, before any op: no cache, a ``ConformerCache`` (its ``length`` is a host integer), a wrong dtype, shape or
         device, a non-contiguous tensor."""
         if counts is not None:
-            _checked_counts("ConformerBlock", counts, cache, ConformerStreamCache, ConformerCache, x)
+            _checked_counts("ConformerBlock", counts, cache, ConformerStreamCache, ConformerCache)
         if cache is not None:
             self._check_cache(x, cache)
             return self._hip_bct(x, None, cache, counts)
@@ -1621,48 +1607,6 @@ class ConformerBlock(nn.Module):
 
     def forward(self, x: Tensor, cache=None, counts=None) -> Tensor:
         return self.run_bct(x.transpose(1, 2).contiguous(), cache, counts).transpose(1, 2).contiguous()
-
-
-class ConformerCache:
-    """The cache of a causal ``ConformerBlock`` (``ConformerBlock.new_cache``): ``kv``, the attention's fp32
-    (B, 2*H*Dh, capacity) key/value buffer with one ``length`` as ``TransformerCache`` has them -- a ring on a windowed block --,
-    and ``conv_state``, the conv block's (B, C, K - 1) post-GLU history (zeros: the start of a stream)."""
-
-    def __init__(self, kv: Tensor, batch: int, capacity: int, window: Optional[int], conv_state: Tensor):
-        self.kv, self.batch, self.capacity, self.length, self.window, self.conv_state = kv, batch, capacity, 0, window, conv_state
-
-    def reset(self) -> None:
-        self.length = 0
-        self.conv_state.zero_()
-
-
-class ConformerStreamCache:
-    """The cache of a windowed causal ``ConformerBlock`` with the positions in device memory (``ConformerBlock.new_stream_cache``):
-    the ring ``kv`` and the int64 (B,) ``pos`` of ``TransformerStreamCache``, ``max_chunk`` as there, and ``conv_state``
-    (B, C, K - 1).  The conv state holds values, not positions: the step kernel shifts it by the call's frames whatever the
-    row's age, so a cached step makes no host decision and every row is a stream of its own."""
-
-    def __init__(self, kv: Tensor, pos: Tensor, capacity: int, window: int, max_chunk: int, conv_state: Tensor):
-        self.kv, self.pos, self.batch, self.capacity, self.window, self.max_chunk = kv, pos, pos.numel(), capacity, window, max_chunk
-        self.conv_state = conv_state
-
-    def reset(self, rows=None) -> None:
-        """Zero the positions and the conv-state rows of ``rows`` (default: every row) with device fills: those rows start a new
-        stream at their next call.  Call it between steps, outside any captured graph."""
-        if rows is None:
-            self.pos.zero_()
-            self.conv_state.zero_()
-            return
-        rows = [int(r) for r in rows]
-        if any(not 0 <= r < self.batch for r in rows):
-            raise AgxError(f"reset: rows {rows} are not rows of a cache of batch {self.batch}")
-        for r in rows:
-            self.pos[r:r + 1].zero_()
-            self.conv_state[r:r + 1].zero_()
-
-    def positions(self) -> list:
-        """The positions as a list of ints.  Synchronises: for tests and debugging, never called in the walk."""
-        return self.pos.tolist()
 
 
 class _ConformerNative(torch.autograd.Function):
