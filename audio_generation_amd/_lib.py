@@ -71,6 +71,9 @@ SIGNATURES = {
     "agx_resblock_kernel_name": (c_int, [_PD, c_char_p, c_size_t]),
     "agx_resblock_forward": (c_int, [_PD, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                      c_int32, c_void_p, c_size_t, c_void_p]),
+    "agx_resblock_q4_supported": (c_int, [_PD]),
+    "agx_resblock_forward_q4": (c_int, [_PD, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                        c_int32, c_int32, c_int32, c_void_p, c_size_t, c_void_p]),
     "agx_rvq_packed_floats": (c_int64, [c_int32, c_int32, c_int32]),
     "agx_rvq_pack": (c_int, [c_void_p, c_int32, c_int32, c_int32, c_void_p, c_void_p]),
     "agx_rvq_pack_sized": (c_int, [c_void_p, c_void_p, c_int32, c_int32, c_int32, c_void_p, c_void_p]),

@@ -62,7 +62,8 @@ struct Knob {
                          256 with double-buffered planes), 2 = resblock_b3 without the GEMM1 priority.  Values 7 / 8 / 9 (RVQ score bound: accumulation term x 4 / x 0 / \
                          candidate counts in the squared-error output) act in the PROBE build of rvq.hip only (-DAGX_RVQ_PROBE); agx_set_tuning refuses them otherwise */ \
     X(rvq_verify, 0)  /* DEBUG: 1 = rvq_forward is followed by the checker kernel (full defining search of every (frame, stage), agx_rvq_verify_counts) */               \
-    X(rb_sched, -1)   /* phase scheduling of the fused residual block (mfma_tile.hpp: 0 / 1 / 2; -1 = per-shape table) */
+    X(rb_sched, -1)   /* phase scheduling of the fused residual block (mfma_tile.hpp: 0 / 1 / 2; -1 = per-shape table) */                                                \
+    X(rb_q4, 1)       /* fused residual block, fp32 ring kernel: 1 = agx_resblock_q4_supported answers 1 where the row has channel-quad variants, 0 = nowhere */
 
 struct Tuning {
 #define AGX_KNOB_FIELD(name, value) Knob name{value};

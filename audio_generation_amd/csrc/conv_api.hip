@@ -209,4 +209,26 @@ int agx_resblock_forward(const agx_conv_desc *d, const float *x, const float *pa
     return run_conv(p2, d->impl, h, packed2, bias2, x, y, st);
 }
 
+int agx_resblock_q4_supported(const agx_conv_desc *d) {
+    using namespace agx;
+    ConvPlan p;
+    if (lower_resblock(d, &p) != AGX_OK) return 0;
+    return resblock_kernel(p, d->impl) == RB_P && resblock_p_quads(p) ? 1 : 0;
+}
+
+int agx_resblock_forward_q4(const agx_conv_desc *d, const float *x, const float *packed1, const float *bias1,
+                            const float *packed2, const float *bias2, float *y, int32_t post_act, int32_t x_is_q4,
+                            int32_t y_is_q4, void *workspace, size_t workspace_bytes, void *stream) {
+    using namespace agx;
+    (void)workspace, (void)workspace_bytes;   // one launch: the workspace of the two-launch form is never needed here
+    ConvPlan p1;
+    int rc = lower_resblock(d, &p1);
+    if (rc != AGX_OK) return rc;
+    if (!x || !packed1 || !packed2 || !y) return fail(AGX_ERR_NULL_POINTER, "agx_resblock_forward_q4: NULL pointer");
+    if (resblock_kernel(p1, d->impl) != RB_P || !resblock_p_quads(p1))
+        return fail(AGX_ERR_UNSUPPORTED, "agx_resblock_forward_q4: the block has no channel-quad form (ask agx_resblock_q4_supported first)");
+    return launch_resblock_p_quads(p1, x, packed1, bias1, packed2, bias2, y, post_act, x_is_q4 != 0, y_is_q4 != 0,
+                                   static_cast<hipStream_t>(stream));
+}
+
 }  // extern "C"

@@ -33,6 +33,10 @@ int launch_conv2d_b3(const ConvPlan &p, const float *x, const float *wp, const f
 bool resblock_p_supported(const ConvPlan &p);
 const char *resblock_p_variant(const ConvPlan &p);
 int launch_resblock_p(const ConvPlan &p, const float *x, const float *w1, const float *b1, const float *w2, const float *b2, float *y, int post_act, hipStream_t st);
+// ... with x and / or y in channel quads (include/agx.h): knob rb_q4, resblock_p_supported and the row's flag
+bool resblock_p_quads(const ConvPlan &p);
+int launch_resblock_p_quads(const ConvPlan &p, const float *x, const float *w1, const float *b1, const float *w2, const float *b2, float *y, int post_act,
+                            bool x_quads, bool y_quads, hipStream_t st);
 bool resblock_b3_supported(const ConvPlan &p);
 const char *resblock_b3_variant(const ConvPlan &p);
 int launch_resblock_b3(const ConvPlan &p, const float *x, const float *w1, const float *b1, const float *w2, const float *b2, float *y, int post_act, hipStream_t st);

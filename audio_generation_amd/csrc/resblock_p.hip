@@ -85,6 +85,12 @@ struct RbpGeom {
     static constexpr int BIAS0 = NSLOT * SLOT;         // [2][C] floats behind the ring: b1, b2 (zeros when absent)
     static constexpr int SCR0 = BIAS0 + 2 * C;         // 1 KiB per wave: transposition scratch of the tile tail (8 rows x 32 columns)
     static constexpr size_t LDS_BYTES = size_t(NSLOT * SLOT + 2 * C + 4 * 256) * sizeof(float);
+    // channel-quad input (q4[b][C/4][L][4], include/agx.h): a chunk is [CCH/4][BN + P][4], a 16-byte cell = one time step of a
+    // quad -- no alignment pad; it fits the same slot
+    static constexpr int QSPAN = BN + P;               // cells per quad row
+    static constexpr int QNCB = CCH / 4 * QSPAN;
+    static constexpr int QNIB = (QNCB + 63) / 64;
+    static_assert(QNIB <= NIB, "the quad chunk must fit the slot's input region");
     static_assert(AFL % 256 == 0, "weight chunk must be whole 1 KiB pieces");
     static_assert(KS == 2 || KS == 4 || KS == 8, "chunk of 4, 8 or 16 channels");
 };
@@ -96,7 +102,7 @@ struct Frag {
     float b[KS][NW];
 };
 
-template <int MW, int NW, int CCH, int D>
+template <int MW, int NW, int CCH, int D, bool XQ = false>
 __device__ __forceinline__ void load_frag(Frag<MW, NW, CCH / 2> &f, const float *__restrict__ As,
                                           const float *__restrict__ Bs, int j) {
     using G = RbpGeom<MW, NW, CCH, D>;
@@ -118,6 +124,22 @@ __device__ __forceinline__ void load_frag(Frag<MW, NW, CCH / 2> &f, const float 
             }
         }
     }
+    if (XQ) {   // quads: the KS channels of lane half lh at one column are 16 (KS = 2: 8) consecutive bytes
+#pragma unroll
+        for (int k = 0; k < NW; ++k) {
+            if (KS == 2) {
+                const f32x2 v = *reinterpret_cast<const f32x2 *>(Bs + (k * 32 + j * D) * 4);
+                f.b[0][k] = v[0], f.b[1][k] = v[1];
+            } else {
+#pragma unroll
+                for (int h4 = 0; h4 < KS / 4; ++h4) {
+                    const f32x4 v = *reinterpret_cast<const f32x4 *>(Bs + (h4 * G::QSPAN + k * 32 + j * D) * 4);
+                    f.b[4 * h4 + 0][k] = v[0], f.b[4 * h4 + 1][k] = v[1], f.b[4 * h4 + 2][k] = v[2], f.b[4 * h4 + 3][k] = v[3];
+                }
+            }
+        }
+        return;
+    }
 #pragma unroll
     for (int ks = 0; ks < KS; ++ks)
 #pragma unroll
@@ -137,15 +159,15 @@ __device__ __forceinline__ void mfma_frag(f32x16 (&acc)[MW][NW], const Frag<MW, 
 
 // One phase: request the operands of the NEXT phase, run this phase's MFMAs, with the LDS reads threaded
 // between the MFMAs (an MFMA holds the issue port for a fraction of its 64 cycles).
-template <int MW, int NW, int CCH, int D, class Extra>
+template <int MW, int NW, int CCH, int D, bool XQ, class Extra>
 __device__ __forceinline__ void phase(f32x16 (&acc)[MW][NW], const Frag<MW, NW, CCH / 2> &cur,
                                       Frag<MW, NW, CCH / 2> &nxt, const float *__restrict__ As,
                                       const float *__restrict__ Bs, int jn, Extra &&extra) {
     constexpr int KS = CCH / 2;
-    load_frag<MW, NW, CCH, D>(nxt, As, Bs, jn);
+    load_frag<MW, NW, CCH, D, XQ>(nxt, As, Bs, jn);
     extra();   // this phase's share of the interval's DMA instructions (address selects + 1-2 global_load_lds)
     mfma_frag<MW, NW, KS>(acc, cur);
-    constexpr int NDS = MW * (KS == 8 ? 2 : 1) + KS * NW, NMF = KS * MW * NW;
+    constexpr int NDS = MW * (KS == 8 ? 2 : 1) + (XQ ? NW * (KS == 8 ? 2 : 1) : KS * NW), NMF = KS * MW * NW;
     constexpr int PER = NMF / NDS > 0 ? NMF / NDS : 1;
 #pragma unroll
     for (int g = 0; g < NDS; ++g) {
@@ -155,16 +177,31 @@ __device__ __forceinline__ void phase(f32x16 (&acc)[MW][NW], const Frag<MW, NW, 
     __builtin_amdgcn_sched_barrier(0);
 }
 
-template <int MW, int NW, int CCH, int D, int NS>
+// XQ / YQ: the input / the output is in channel quads (q4[b][C/4][L][4]: the four consecutive channels an
+// accumulator register quad holds at one time step are 16 consecutive bytes) instead of [B][C][L].  With quads the tile tail
+// needs no transposition: the residual quad is one 16-byte load into the registers GEMM2 accumulates on, the finished quad
+// one 16-byte store (a half wave writes 512 contiguous bytes), and the B operand of a phase is one ds_read_b128 (KS = 2:
+// b64) per column block.  The lane half -> channel mapping (lh * KS + ks) is the same, so every output is the same fmaf
+// chain in the same order: the quad variants are bit-identical to the standard one.
+// NSQ = ring slots + kRbpXQ * XQ + kRbpYQ * YQ: the variant rides in the last template argument, so that the standard kernels keep
+// their symbols and, instruction for instruction, their code (tools/device_code_diff.py against the build before the quads).
+constexpr int kRbpXQ = 16, kRbpYQ = 32;
+template <int MW, int NW, int CCH, int D, int NSQ>
 __global__ __launch_bounds__(256, 2) void resblock_p_kernel(ConvPlan p, int tiles_per_clip, int ntiles, int step_b,
                                                             int step_t, int post_act,
                                                             const float *__restrict__ x,
                                                             const float *__restrict__ wt1, const float *__restrict__ b1,
                                                             const float *__restrict__ wt2, const float *__restrict__ b2,
                                                             float *__restrict__ y) {
+    constexpr int NS = NSQ % kRbpXQ;
+    constexpr bool XQ = (NSQ & kRbpXQ) != 0, YQ = (NSQ & kRbpYQ) != 0;
     using G = RbpGeom<MW, NW, CCH, D, NS>;
     constexpr int C = G::C, BN = G::BN, KS = G::KS, NCH = G::NCH, SLOT = G::SLOT, AFL = G::AFL, HS = G::HS;
     constexpr bool PRE3 = G::NSLOT == 3;
+    // input rows of a chunk: CCH rows of NCELL 4-column cells starting PA before the tile, or CCH/4 quad rows of one cell per
+    // time step starting P before it
+    constexpr int NCBX = XQ ? G::QNCB : G::NCB, NIBX = XQ ? G::QNIB : G::NIB, RBX = (NIBX + 3) / 4, NOPSX = G::RA + RBX;
+    constexpr int ROWC = XQ ? G::QSPAN : G::NCELL, PADX = XQ ? G::P : G::PA;
     extern __shared__ __attribute__((aligned(16))) float lds[];  // [3][AFL + BFL]
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);   // wave-uniform: LDS-DMA destinations stay in SGPRs
@@ -176,21 +213,22 @@ __global__ __launch_bounds__(256, 2) void resblock_p_kernel(ConvPlan p, int tile
     // Instruction slot (k, wave) of an interval moves piece n = wave + 4 k; a slot beyond the chunk's last piece repeats
     // piece n % count (same bytes to the same place: harmless), so that every slot issues unconditionally, branch-free.
     // input instruction n covers cells 64 n .. 64 n + 63 of the chunk (cell e = row e / NCELL, columns 4 (e % NCELL) ..)
-    unsigned boffB[G::RB];   // byte offset of this lane's cell inside the chunk's rows
-    int colB[G::RB];         // its first column relative to the LDS row start; hugely negative: beyond the chunk
-    int nB[G::RB];
+    unsigned boffB[RBX];     // byte offset of this lane's cell inside the chunk's rows
+    int colB[RBX];           // its first column relative to the LDS row start; hugely negative: beyond the chunk
+    int nB[RBX];
 #pragma unroll
-    for (int r = 0; r < G::RB; ++r) {
-        nB[r] = (wave + 4 * r) % G::NIB;
+    for (int r = 0; r < RBX; ++r) {
+        nB[r] = (wave + 4 * r) % NIBX;
         const int e = nB[r] * 64 + lane;
-        const int row = e / G::NCELL, col = e - row * G::NCELL;
-        colB[r] = e < G::NCB ? 4 * col : -(1 << 28);
-        boffB[r] = unsigned(row * Lin + 4 * col) * 4u;
+        const int row = e / ROWC, col = e - row * ROWC;
+        colB[r] = e < NCBX ? (XQ ? col : 4 * col) : -(1 << 28);
+        boffB[r] = XQ ? unsigned(row * Lin + col) * 16u : unsigned(row * Lin + 4 * col) * 4u;
     }
     const char *zpage = reinterpret_cast<const char *>(g_rbp_zero_page) + lane * 16;
     // consumer-side lane offsets (floats, relative to a slot)
     const int aLane = (KS == 4 ? lh * G::J * C * 4 : (KS == 8 ? 2 * lh * G::J * C * 4 : lh * 2)) + li * 4;
-    const int bLane = AFL + lh * KS * G::SPANP + n0 + li + G::SHIFT;
+    const int bLane = XQ ? AFL + (KS == 2 ? (n0 + li) * 4 + lh * 2 : (lh * (KS / 4) * G::QSPAN + n0 + li) * 4)
+                         : AFL + lh * KS * G::SPANP + n0 + li + G::SHIFT;
 
     // this workgroup's tiles: blockIdx.x, + gridDim.x, ...; (clip, time block) advance by (step_b, step_t) with carry
     const int my_tiles = int(blockIdx.x) < ntiles ? (ntiles - 1 - int(blockIdx.x)) / int(gridDim.x) + 1 : 0;
@@ -203,7 +241,7 @@ __global__ __launch_bounds__(256, 2) void resblock_p_kernel(ConvPlan p, int tile
     // last chunk (into a ring slot nobody reads any more).
     int iq = 0, ic = 0, ib = first_b, it = first_t, isl = 0;   // chunk index in the stream / in the tile, tile coordinates, ring slot
     const char *w_next = reinterpret_cast<const char *>(wt1);
-    const char *x_next = reinterpret_cast<const char *>(x + size_t(ib) * C * Lin + (it * BN - G::PA));
+    const char *x_next = reinterpret_cast<const char *>(x + size_t(ib) * C * Lin + (XQ ? 4 : 1) * (it * BN - PADX));
     float *d_slot = lds;
     const char *d_w = nullptr, *d_x = nullptr;
     int d_in0a = 0;
@@ -213,7 +251,7 @@ __global__ __launch_bounds__(256, 2) void resblock_p_kernel(ConvPlan p, int tile
         d_slot = lds + isl * SLOT;
         d_w = w_next;
         d_x = x_next;
-        d_in0a = it * BN - G::PA;
+        d_in0a = it * BN - PADX;
         ++iq;
         isl = isl + 1 == G::NSLOT ? 0 : isl + 1;
         w_next += AFL * sizeof(float);
@@ -224,7 +262,7 @@ __global__ __launch_bounds__(256, 2) void resblock_p_kernel(ConvPlan p, int tile
             it += step_t;
             if (it >= tiles_per_clip) it -= tiles_per_clip, ++ib;
             w_next = reinterpret_cast<const char *>(wt1);
-            x_next = reinterpret_cast<const char *>(x + size_t(ib) * C * Lin + (it * BN - G::PA));
+            x_next = reinterpret_cast<const char *>(x + size_t(ib) * C * Lin + (XQ ? 4 : 1) * (it * BN - PADX));
         }
     };
     auto dma_op = [&](int k) {
@@ -232,7 +270,7 @@ __global__ __launch_bounds__(256, 2) void resblock_p_kernel(ConvPlan p, int tile
             const int n = (wave + 4 * k) % G::NPA;
             const char *src = d_live ? d_w + n * 1024 + lane * 16 : zpage;
             glds_b128(reinterpret_cast<const float *>(src), d_slot + n * 256);
-        } else if (k < G::NOPS) {     // input rows, 64 cells per instruction
+        } else if (k < NOPSX) {       // input rows, 64 cells per instruction
             const int r = k - G::RA;
             const int pos = d_in0a + colB[r];
             const bool ok = d_live && pos >= 0 && pos < p.Lvalid;
@@ -243,7 +281,7 @@ __global__ __launch_bounds__(256, 2) void resblock_p_kernel(ConvPlan p, int tile
     auto issue = [&]() {
         begin_chunk();
 #pragma unroll
-        for (int k = 0; k < G::NOPS; ++k) dma_op(k);
+        for (int k = 0; k < NOPSX; ++k) dma_op(k);
     };
 
     if (nq == 0) return;
@@ -255,7 +293,7 @@ __global__ __launch_bounds__(256, 2) void resblock_p_kernel(ConvPlan p, int tile
     __syncthreads();
 
     Frag<MW, NW, KS> f0, f1;
-    if (PRE3) load_frag<MW, NW, CCH, D>(f0, lds + aLane, lds + bLane, 0);
+    if (PRE3) load_frag<MW, NW, CCH, D, XQ>(f0, lds + aLane, lds + bLane, 0);
 
     // ---- tile tail <-> memory: 16-byte pieces through a per-wave LDS scratch ----------------------------------------------
     // A piece = rows 8g .. 8g+7 of row block io x the 32 columns of column block kk: one instruction moves 8 rows x 128 B
@@ -292,6 +330,27 @@ __global__ __launch_bounds__(256, 2) void resblock_p_kernel(ConvPlan p, int tile
         const f32x4 v = *reinterpret_cast<const f32x4 *>(xbase + unsigned(((pass * HS + io) * 32 + 8 * g + prow) * linv + tq) * 4u);
         out[io][kk][4 * g + 0] = v[0], out[io][kk][4 * g + 1] = v[1], out[io][kk][4 * g + 2] = v[2], out[io][kk][4 * g + 3] = v[3];
     };
+    // Quads: piece (io, g, kk) of lane (li, lh) is quad row (pass * HS + io) * 8 + 2 g + lh at column kk * 32 + li -- the
+    // accumulator registers 4g .. 4g+3 themselves, 16 bytes in memory.
+    auto store_quad = [&](int pc, int pass, char *ybase, int tcol0, int linv) {
+        const int io = pc / (4 * NW), g = (pc / NW) % 4, kk = pc % NW;
+        f32x4 v4;
+#pragma unroll
+        for (int e = 0; e < 4; ++e) v4[e] = out[io][kk][4 * g + e];
+        const int tq = tcol0 + n0 + kk * 32 + li;
+        if (tq < Lin)
+            *reinterpret_cast<f32x4 *>(ybase + unsigned(((pass * HS + io) * 8 + 2 * g + lh) * linv + tq) * 16u) = v4;
+    };
+    auto load_quad = [&](int pc, int pass, const char *xbase, int tcol0, int linv) {
+        const int io = pc / (4 * NW), g = (pc / NW) % 4, kk = pc % NW;
+        const int tq = min(tcol0 + n0 + kk * 32 + li, Lin - 1);   // columns beyond the clip are never stored
+        const f32x4 v = *reinterpret_cast<const f32x4 *>(xbase + unsigned(((pass * HS + io) * 8 + 2 * g + lh) * linv + tq) * 16u);
+        out[io][kk][4 * g + 0] = v[0], out[io][kk][4 * g + 1] = v[1], out[io][kk][4 * g + 2] = v[2], out[io][kk][4 * g + 3] = v[3];
+    };
+    auto load_res = [&](int pc, int pass, const char *xbase, int tcol0, int linv) {
+        if (XQ) load_quad(pc, pass, xbase, tcol0, linv);
+        else load_piece(pc, pass, xbase, tcol0, linv);
+    };
 
     int q = 0, qs = 0, cb = first_b, ct = first_t;   // consumed chunks, their ring slot, tile coordinates
     for (int k = 0; k < my_tiles; ++k) {
@@ -308,7 +367,7 @@ __global__ __launch_bounds__(256, 2) void resblock_p_kernel(ConvPlan p, int tile
 #pragma unroll
                 for (int r = 0; r < 16; ++r) acc[i][kk][r] = 0.f;
         if (!PRE3)   // 2-slot ring: the tile's first operands are read here (its first chunk landed at the last barrier)
-            load_frag<MW, NW, CCH, D>(f0, lds + qs * SLOT + aLane, lds + qs * SLOT + bLane, 0);
+            load_frag<MW, NW, CCH, D, XQ>(f0, lds + qs * SLOT + aLane, lds + qs * SLOT + bLane, 0);
 
         const char *xb = reinterpret_cast<const char *>(x + size_t(b) * C * Lin);
         char *yb = reinterpret_cast<char *>(y + size_t(b) * C * Lin);
@@ -322,9 +381,9 @@ __global__ __launch_bounds__(256, 2) void resblock_p_kernel(ConvPlan p, int tile
 #define AGX_RBP_OPS(j)                                                                                                \
     [&]() {                                                                                                           \
         dma_op(j);                                                                                                    \
-        if (G::NOPS > 7) dma_op(j + 7);                                                                               \
+        if (NOPSX > 7) dma_op(j + 7);                                                                                 \
         if (EARLY && LAST_) {                                                                                         \
-            _Pragma("unroll") for (int pc = (j); pc < NPIECE; pc += 7) load_piece(pc, 0, xb, t0, linv);               \
+            _Pragma("unroll") for (int pc = (j); pc < NPIECE; pc += 7) load_res(pc, 0, xb, t0, linv);                 \
         }                                                                                                             \
     }
 #define AGX_RBP_CHUNK(FA, FB, LAST)                                                                                  \
@@ -336,20 +395,20 @@ __global__ __launch_bounds__(256, 2) void resblock_p_kernel(ConvPlan p, int tile
         const int qsn = qs + 1 == G::NSLOT ? 0 : qs + 1;                                                             \
         const float *As = lds + qs * SLOT + aLane, *Bs = lds + qs * SLOT + bLane;                                    \
         const float *An = lds + qsn * SLOT + aLane, *Bn = lds + qsn * SLOT + bLane;                                  \
-        phase<MW, NW, CCH, D>(acc, FA, FB, As, Bs, 1, AGX_RBP_OPS(0));                                               \
+        phase<MW, NW, CCH, D, XQ>(acc, FA, FB, As, Bs, 1, AGX_RBP_OPS(0));                                           \
         AGX_RSTAMP(2);                                                                                               \
-        phase<MW, NW, CCH, D>(acc, FB, FA, As, Bs, 2, AGX_RBP_OPS(1));                                               \
+        phase<MW, NW, CCH, D, XQ>(acc, FB, FA, As, Bs, 2, AGX_RBP_OPS(1));                                           \
         AGX_RSTAMP(3);                                                                                               \
-        phase<MW, NW, CCH, D>(acc, FA, FB, As, Bs, 3, AGX_RBP_OPS(2));                                               \
+        phase<MW, NW, CCH, D, XQ>(acc, FA, FB, As, Bs, 3, AGX_RBP_OPS(2));                                           \
         AGX_RSTAMP(4);                                                                                               \
-        phase<MW, NW, CCH, D>(acc, FB, FA, As, Bs, 4, AGX_RBP_OPS(3));                                               \
+        phase<MW, NW, CCH, D, XQ>(acc, FB, FA, As, Bs, 4, AGX_RBP_OPS(3));                                           \
         AGX_RSTAMP(5);                                                                                               \
-        phase<MW, NW, CCH, D>(acc, FA, FB, As, Bs, 5, AGX_RBP_OPS(4));                                               \
+        phase<MW, NW, CCH, D, XQ>(acc, FA, FB, As, Bs, 5, AGX_RBP_OPS(4));                                           \
         AGX_RSTAMP(6);                                                                                               \
-        phase<MW, NW, CCH, D>(acc, FB, FA, As, Bs, 6, AGX_RBP_OPS(5));                                               \
+        phase<MW, NW, CCH, D, XQ>(acc, FB, FA, As, Bs, 6, AGX_RBP_OPS(5));                                           \
         AGX_RSTAMP(7);                                                                                               \
         if (PRE3) {                                                                                                  \
-            phase<MW, NW, CCH, D>(acc, FA, FB, An, Bn, 0, AGX_RBP_OPS(6)); /* next chunk's first phase: complete since the last barrier */ \
+            phase<MW, NW, CCH, D, XQ>(acc, FA, FB, An, Bn, 0, AGX_RBP_OPS(6)); /* next chunk's first phase: complete since the last barrier */ \
         } else {                                                                                                     \
             AGX_RBP_OPS(6)();                                                                                        \
             mfma_frag<MW, NW, KS>(acc, FA);                                                                          \
@@ -360,7 +419,7 @@ __global__ __launch_bounds__(256, 2) void resblock_p_kernel(ConvPlan p, int tile
         AGX_RSTAMP(9);                                                                                               \
         __syncthreads();                                 /* everyone's has; slot q is free */                         \
         AGX_RSTAMP(10);                                                                                              \
-        if (!PRE3 && !(LAST)) load_frag<MW, NW, CCH, D>(FB, An, Bn, 0);                                               \
+        if (!PRE3 && !(LAST)) load_frag<MW, NW, CCH, D, XQ>(FB, An, Bn, 0);                                          \
         ++q; (void)q;                                                                                                \
         qs = qsn;                                                                                                    \
     }
@@ -410,7 +469,7 @@ __global__ __launch_bounds__(256, 2) void resblock_p_kernel(ConvPlan p, int tile
             if (pass > 0 || !EARLY) {   // (C = 256 only) the residual is requested here: exposed latency, twice per 8192-MFMA tile
                 if (pass > 0) load_w2(wa[0], 0, pass);
 #pragma unroll
-                for (int pc = 0; pc < NPIECE; ++pc) load_piece(pc, pass, xb, t0, linv);
+                for (int pc = 0; pc < NPIECE; ++pc) load_res(pc, pass, xb, t0, linv);
             }
             // residual pieces -> accumulator layout, + b2: GEMM2's accumulator starts from x + b2
 #pragma unroll
@@ -419,6 +478,12 @@ __global__ __launch_bounds__(256, 2) void resblock_p_kernel(ConvPlan p, int tile
                 for (int kk = 0; kk < NW; ++kk)
 #pragma unroll
                     for (int g = 0; g < 4; ++g) {
+                        if (XQ) {   // already in place
+                            const f32x4 b2q = *reinterpret_cast<const f32x4 *>(lds + G::BIAS0 + C + (pass * HS + io) * 32 + 8 * g + 4 * lh);
+#pragma unroll
+                            for (int s4 = 0; s4 < 4; ++s4) out[io][kk][4 * g + s4] += b2q[s4];
+                            continue;
+                        }
                         asm volatile("" ::: "memory");
 #pragma unroll
                         for (int e = 0; e < 4; ++e) scr[lane * 4 + e] = out[io][kk][4 * g + e];
@@ -454,17 +519,20 @@ __global__ __launch_bounds__(256, 2) void resblock_p_kernel(ConvPlan p, int tile
                         for (int r = 0; r < 16; ++r) out[io][kk][r] = leaky(out[io][kk][r], p.slope);
             }
 #pragma unroll
-            for (int pc = 0; pc < NPIECE; ++pc) store_piece(pc, pass, yb, t0, linv);
+            for (int pc = 0; pc < NPIECE; ++pc) {
+                if (YQ) store_quad(pc, pass, yb, t0, linv);
+                else store_piece(pc, pass, yb, t0, linv);
+            }
             if (pass == 0) AGX_TSTAMP(14);
         }
     }
 }
 
-template <int MW, int NW, int CCH, int D, int NS>
+template <int MW, int NW, int CCH, int D, int NS, bool XQ = false, bool YQ = false>
 static int launch_rbp(const ConvPlan &p, const float *x, const float *w1, const float *b1, const float *w2,
                       const float *b2, float *y, int post_act, hipStream_t st) {
     using G = RbpGeom<MW, NW, CCH, D, NS>;
-    auto kern = resblock_p_kernel<MW, NW, CCH, D, NS>;
+    auto kern = resblock_p_kernel<MW, NW, CCH, D, NS + (XQ ? kRbpXQ : 0) + (YQ ? kRbpYQ : 0)>;
     static DeviceOnce once;
     int n_cu = 0;
     if (int rc = prepare_kernel(reinterpret_cast<const void *>(kern), once, 160 * 1024, &n_cu, "resblock_p")) return rc;
@@ -489,14 +557,32 @@ struct RbpRow {
     int C;
     const char *name;       // pinned: tests/golden/kernel_names.json
     RbpLaunch launch[3];    // d = 1, 3, 9
+    RbpLaunch quad[3][3];   // [x in quads + 2 * y in quads - 1][d]: the channel-quad variants; NULL = the row opted out
 };
-template <int MW, int NW, int CCH, int NS>
+template <int MW, int NW, int CCH, int NS, bool XQ, bool YQ>
+static constexpr RbpLaunch rbp_launch(int di) {
+    return di == 0 ? launch_rbp<MW, NW, CCH, 1, NS, XQ, YQ> : di == 1 ? launch_rbp<MW, NW, CCH, 3, NS, XQ, YQ> : launch_rbp<MW, NW, CCH, 9, NS, XQ, YQ>;
+}
+// Q4: the row has the quad variants (an opted-out row does not instantiate them)
+template <int MW, int NW, int CCH, int NS, bool Q4>
 static constexpr RbpRow rbp_row(const char *name) {
-    return {RbpGeom<MW, NW, CCH, 1, NS>::C, name, {launch_rbp<MW, NW, CCH, 1, NS>, launch_rbp<MW, NW, CCH, 3, NS>, launch_rbp<MW, NW, CCH, 9, NS>}};
+    RbpRow r = {RbpGeom<MW, NW, CCH, 1, NS>::C, name, {}, {}};
+    for (int di = 0; di < 3; ++di) {
+        r.launch[di] = rbp_launch<MW, NW, CCH, NS, false, false>(di);
+        if constexpr (Q4) {
+            r.quad[0][di] = rbp_launch<MW, NW, CCH, NS, true, false>(di);
+            r.quad[1][di] = rbp_launch<MW, NW, CCH, NS, false, true>(di);
+            r.quad[2][di] = rbp_launch<MW, NW, CCH, NS, true, true>(di);
+        }
+    }
+    return r;
 }
 static const RbpRow kRbpRows[] = {
-    rbp_row<1, 4, 8, 3>("resblock_p<1,4,8>"), rbp_row<2, 2, 8, 3>("resblock_p<2,2,8>"), rbp_row<4, 1, 4, 3>("resblock_p<4,1,4>"),
-    rbp_row<8, 1, 4, 2>("resblock_p<8,1,4>")};   // 28.7 KB of weights per 4-channel chunk: two slots keep two workgroups per CU
+    rbp_row<1, 4, 8, 3, true>("resblock_p<1,4,8>"), rbp_row<2, 2, 8, 3, true>("resblock_p<2,2,8>"),
+    rbp_row<4, 1, 4, 3, true>("resblock_p<4,1,4>"),
+    // 28.7 KB of weights per 4-channel chunk: two slots keep two workgroups per CU.  No quads: the three variants spill (19 / 3 /
+    // 52 VGPRs of a budget the standard kernel already exceeds by 29)
+    rbp_row<8, 1, 4, 2, false>("resblock_p<8,1,4>")};
 
 static const RbpRow *rbp_row_of(int channels) {
     for (const RbpRow &r : kRbpRows)
@@ -522,6 +608,18 @@ int launch_resblock_p(const ConvPlan &p, const float *x, const float *w1, const 
                       const float *b2, float *y, int post_act, hipStream_t st) {
     if (!resblock_p_supported(p)) return fail(AGX_ERR_UNSUPPORTED, "resblock_p: unsupported shape");
     return rbp_row_of(p.Cin)->launch[p.d == 1 ? 0 : p.d == 3 ? 1 : 2](p, x, w1, b1, w2, b2, y, post_act, st);
+}
+
+bool resblock_p_quads(const ConvPlan &p) {
+    return tuning().rb_q4 == 1 && resblock_p_supported(p) && rbp_row_of(p.Cin)->quad[0][0] != nullptr;
+}
+
+int launch_resblock_p_quads(const ConvPlan &p, const float *x, const float *w1, const float *b1, const float *w2,
+                            const float *b2, float *y, int post_act, bool x_quads, bool y_quads, hipStream_t st) {
+    if (!resblock_p_quads(p)) return fail(AGX_ERR_UNSUPPORTED, "resblock_p: no channel-quad variant for this block");
+    const RbpRow *row = rbp_row_of(p.Cin);
+    const int di = p.d == 1 ? 0 : p.d == 3 ? 1 : 2, v = int(x_quads) + 2 * int(y_quads);
+    return (v ? row->quad[v - 1][di] : row->launch[di])(p, x, w1, b1, w2, b2, y, post_act, st);
 }
 
 }  // namespace agx

@@ -259,7 +259,7 @@ def encode_latents_long(model, x: Tensor, segment_frames: Optional[int] = None) 
     p = plan(n_frames, hop, rf.enc_halo_left, rf.enc_halo_right, whole_frames=length // sf)
     if p.single:
         return None
-    return _fold_run_unfold(x, p, sf, 1, model._encoders_hip)
+    return _fold_run_unfold(x, p, sf, 1, lambda t: model._encoders_hip(t, quads=False))
 
 
 def encode_long(model, x: Tensor, segment_frames: Optional[int] = None, codebook_n: Optional[int] = None):
@@ -286,7 +286,7 @@ def decode_long(model, zq: Tensor, segment_frames: Optional[int] = None) -> Tens
     p = plan(n_frames, hop, rf.dec_halo_left, rf.dec_halo_right)
     if p.single:
         return model.decode(zq)
-    return model.rearrange_out(_fold_run_unfold(zq, p, 1, rf.scale_factor, model._decoders_hip))
+    return model.rearrange_out(_fold_run_unfold(zq, p, 1, rf.scale_factor, lambda t: model._decoders_hip(t, quads=False)))
 
 
 def forward_long(model, x: Tensor, segment_frames: Optional[int] = None, codebook_n: Optional[int] = None):

@@ -289,6 +289,33 @@ def resblock_forward(desc: ConvDesc, x: Tensor, packed1: Tensor, bias1: Optional
     return y
 
 
+def resblock_q4_supported(desc: ConvDesc) -> bool:
+    """The block has the channel-quad variants of the fp32 ring kernel (``agx_resblock_q4_supported``; host-only query)."""
+    return bool(_lib.load().agx_resblock_q4_supported(ctypes.byref(desc)))
+
+
+def resblock_forward_q4(desc: ConvDesc, x: Tensor, packed1: Tensor, bias1: Optional[Tensor], packed2: Tensor,
+                        bias2: Optional[Tensor], post_act: bool = True, x_is_q4: bool = False, y_is_q4: bool = False) -> Tensor:
+    """``resblock_forward`` with the input and / or the output in channel quads (include/agx.h): a quad tensor is
+    ``(B, C / 4, L, 4)``, a standard one ``(B, C, L)``."""
+    lib = _lib.load()
+    _need_gpu(x, packed1, packed2, bias1, bias2)
+    x = _f32c(x)
+    b, c, length = desc.batch, desc.c_in, desc.l_in
+    if tuple(x.shape) != ((b, c // 4, length, 4) if x_is_q4 else (b, c, length)):
+        raise AgxError(f"resblock_forward_q4: x is {tuple(x.shape)}, descriptor says {(b, c, length)}, x_is_q4={bool(x_is_q4)}")
+    y = torch.empty((b, c // 4, length, 4) if y_is_q4 else (b, c, length), dtype=torch.float32, device=x.device)
+    ws_bytes = int(lib.agx_resblock_workspace_bytes(ctypes.byref(desc)))
+    ws = _workspace(ws_bytes, x.device, "agx_resblock_workspace_bytes")
+    tok = _observer.begin("resblock", desc) if _observer is not None else None
+    _lib.check(lib.agx_resblock_forward_q4(ctypes.byref(desc), _ptr(x), _ptr(packed1), _ptr(bias1), _ptr(packed2), _ptr(bias2),
+                                           _ptr(y), int(bool(post_act)), int(bool(x_is_q4)), int(bool(y_is_q4)),
+                                           _ptr(ws), ws_bytes, _stream()), "agx_resblock_forward_q4")
+    if tok is not None:
+        _observer.end(tok)
+    return y
+
+
 # ---------------------------------------------------------------------------- rvq
 def rvq_pack(codebooks: Tensor, sizes: Optional[Sequence[int]] = None) -> Tensor:
     """Stage images of (Q, K, D) codebooks; ``sizes[q] <= K`` = real codewords of stage q (rows beyond are padding

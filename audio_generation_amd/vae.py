@@ -218,6 +218,23 @@ class CausalResidualBlock1d(nn.Module):
 
     run_fused = run
 
+    def takes_quads(self, shape, post_slope: Optional[float]) -> bool:
+        """``run`` on a ``shape`` = (B, C, L) input would be ONE ``ops.resblock_forward`` call, and the library has the
+        channel-quad variants of its kernel (``agx_resblock_q4_supported``)."""
+        slope = leaky_slope(self.activation)
+        if self.depthwise or self.split_launches or slope is None or (post_slope is not None and post_slope != slope):
+            return False
+        return ops.resblock_q4_supported(self.conv1.desc(shape, 0, slope))
+
+    def run_quads(self, x: Tensor, post_slope: Optional[float], x_is_q4: bool, y_is_q4: bool) -> Tensor:
+        """``run`` of a block that ``takes_quads``, its input and / or output in channel quads ``(B, C / 4, L, 4)``."""
+        refuse_training_dropout(self, self.dropout)
+        c1, c2, impl = self.conv1.conv, self.conv2.conv, self.conv1.impl
+        shape = (x.shape[0], x.shape[1] * 4, x.shape[2]) if x_is_q4 else x.shape
+        return ops.resblock_forward_q4(self.conv1.desc(shape, 0, leaky_slope(self.activation)), x, c1.packed(CONV_CAUSAL, impl),
+                                       detached(c1.bias), c2.packed(CONV_CAUSAL, impl), detached(c2.bias),
+                                       post_act=post_slope is not None, x_is_q4=x_is_q4, y_is_q4=y_is_q4)
+
     def forward(self, x: Tensor) -> Tensor:
         return self.run(x, None)
 
@@ -299,12 +316,30 @@ def _multires_pair(block: nn.Module):
     return [(block.multires, None)] if hasattr(block, "multires") else []
 
 
-def _run_units(units: Sequence[Unit], x: Tensor) -> Tensor:
+def _run_units(units: Sequence[Unit], x: Tensor, quads: bool = True) -> Tensor:
     """Inference walk.  A bare conv runs as its ``forward()``, a conv behind ``nn.Identity`` as ``run_fused(x, None)``: the same
     launch, but the descriptor's slope field (unread without an epilogue) is 0.1 in the one and 0.0 in the other, and 0.0 in
-    the training forward of both -- kept as recorded in tests/golden/stack_launch_trace.json."""
-    for u in units:
-        x = u.layer(x) if u.bare else u.forward(x)
+    the training forward of both -- kept as recorded in tests/golden/stack_launch_trace.json.
+
+    ``quads``: a run of two or more consecutive residual blocks that all have the channel-quad variants of the fp32 ring kernel
+    (include/agx.h; ``takes_quads``) passes its activation from block to block in quads -- the first block writes them, the
+    last one reads them; same values bit for bit.  Device tensors without autograd only: everything else (and ``quads=False``:
+    long-form) makes the plain calls."""
+    i, n = 0, len(units)
+    quads = quads and x.is_cuda and x.dim() == 3 and not torch.is_grad_enabled()
+    while i < n:
+        u = units[i]
+        j = i
+        if quads and u.kind == "res":   # a run of residual blocks that all have the channel-quad variants
+            while j < n and units[j].kind == "res" and units[j].layer.takes_quads(x.shape, units[j].slope):
+                j += 1
+        if j - i >= 2:   # the activation BETWEEN the blocks travels in channel quads (include/agx.h): same kernels' arithmetic
+            for k in range(i, j):
+                x = units[k].layer.run_quads(x, units[k].slope, x_is_q4=k > i, y_is_q4=k < j - 1)
+            i = j
+        else:
+            x = u.layer(x) if u.bare else u.forward(x)
+            i += 1
     return x
 
 
@@ -401,12 +436,12 @@ class CausalVQAE(nn.Module):
     def rearrange_out(self, x: Tensor) -> Tensor:
         return x.transpose(1, 2).contiguous() if self.input_format == "b l c" else x
 
-    def _encoders_hip(self, x: Tensor) -> Tensor:
-        return _run_units(self._units("encoders"), x)
+    def _encoders_hip(self, x: Tensor, quads: bool = True) -> Tensor:
+        return _run_units(self._units("encoders"), x, quads)
 
-    def _decoders_hip(self, x: Tensor) -> Tensor:
+    def _decoders_hip(self, x: Tensor, quads: bool = True) -> Tensor:
         x, units = self._decoder_head_on_planes(x, self._units("decoders"))
-        return _run_units(units, x)
+        return _run_units(units, x, quads)
 
     def _decoder_head_on_planes(self, x: Tensor, decs):
         """bf16x3 decoders, inference: the k = 7 transposed conv (vae.py:269) writes its output as ACTIVATION PLANES

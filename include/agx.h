@@ -73,6 +73,8 @@ int32_t agx_sizeof_conv2d_desc(void);
  *                      search (binary64, oracle/rvq_exact.c) of every (frame, stage) on the residual the fast path searched and
  *                      counts the indices that differ (agx_rvq_verify_counts); tens of milliseconds per call at config S
  *   "conv_shape" 0|1   1: 128x128 conv tiles as four row-waves of 1x4 fragments
+ *   "rb_q4" 0|1        fused residual block on the fp32 ring kernel: 1 (default) agx_resblock_q4_supported answers 1 where the
+ *                      channel count has channel-quad variants, 0 nowhere (the in-process A/B switch of the quad layout)
  *   "rb_impl" 0|1      fused residual block: 1 (default) the persistent ring kernel (csrc/resblock_p.hip) where it applies,
  *                      0 the first kernel (csrc/resblock_mfma.hip) everywhere
  *   "conv_impl" 0|1    resampling / stride-1 1-D layers and the Conv2d layers the ring kernel has a geometry for (forward and
@@ -206,6 +208,21 @@ int agx_resblock_forward(const agx_conv_desc *d, const float *x, const float *pa
                          const float *bias1, const float *packed2, const float *bias2,
                          float *y, int32_t post_act, void *workspace, size_t workspace_bytes,
                          void *stream);
+
+/* Channel quads: a second fp32 activation format carried BETWEEN consecutive residual blocks at inference,
+ *   q4[b][C/4][L][4]        element (b, c, t) at ((b * C/4 + c/4) * L + t) * 4 + c % 4
+ * -- the four consecutive channels an MFMA accumulator register quad holds at one time step are 16 consecutive bytes, so the
+ * fp32 ring kernel (csrc/resblock_p.hip) loads the residual and stores its tile without the LDS transposition of its tile
+ * tail, and reads its B operand as 16-byte LDS words.  Same arithmetic in the same order: bit-identical to agx_resblock_forward.
+ * agx_resblock_q4_supported: 1 when the block runs on the fp32 ring kernel and its channel count has the quad variants
+ * (knob "rb_q4" = 0: 0 everywhere).  agx_resblock_forward_q4: x / y are in quads where x_is_q4 / y_is_q4 != 0 and [B][C][L]
+ * otherwise; error conventions of agx_resblock_forward, AGX_ERR_UNSUPPORTED (nothing launched) where the query answers 0.
+ * The workspace arguments are accepted for symmetry and unused. */
+int agx_resblock_q4_supported(const agx_conv_desc *d);
+int agx_resblock_forward_q4(const agx_conv_desc *d, const float *x, const float *packed1,
+                            const float *bias1, const float *packed2, const float *bias2,
+                            float *y, int32_t post_act, int32_t x_is_q4, int32_t y_is_q4,
+                            void *workspace, size_t workspace_bytes, void *stream);
 
 /* ------------------------------------------------------------------------- *
  * Residual vector quantiser (external `som_quantizer.ResidualQuantizer`;      *
