@@ -301,6 +301,15 @@ SIGNATURES = {
     "agx_glu_dwconv_step_counted": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_float, c_void_p,
                                             c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_void_p]),
     "agx_mask_tail_counted": (c_int, [c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_void_p]),
+    # the RVQ streaming step and its packets
+    "agx_rvq_step_packet_bytes": (c_int64, [c_int32, c_int32, c_int32]),
+    "agx_rvq_step_workspace_bytes": (c_size_t, [c_int32, c_int32, c_int32, c_int32, c_int32]),
+    "agx_rvq_step_encode": (c_int, [c_void_p, c_int64, c_int64, c_int64, c_void_p, c_void_p, c_void_p,
+                                    c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32,
+                                    c_void_p, c_int64, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "agx_rvq_step_decode": (c_int, [c_void_p, c_int32, c_void_p, c_void_p, c_void_p,
+                                    c_int32, c_int32, c_int32, c_int32, c_int32, c_int32,
+                                    c_void_p, c_int64, c_int64, c_int64, c_void_p, c_void_p]),
 }
 
 _lib = None

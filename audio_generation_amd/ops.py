@@ -463,6 +463,91 @@ def rvq_dequantize(codebook: Tensor, idx: Tensor, out: Optional[Tensor] = None,
     return out
 
 
+RVQ_STEP_MAX_N = 32    # AGX_RVQ_STEP_MAX_N: the frames per row one step takes
+
+
+def _step_operands(op: str, codebooks: Tensor, q_used: int, sizes: Optional[Sequence[int]], bits: Optional[int]):
+    """What the two step wrappers share -> (codebooks, Q, K, D, sizes as a host int32 array or None, bits)."""
+    codebooks = _f32c(codebooks)
+    if codebooks.dim() != 3:
+        raise AgxError(f"{op}: codebooks are {tuple(codebooks.shape)}, expected (Q, K, D)")
+    q_total, k, d = codebooks.shape
+    if not 0 <= q_used <= q_total:
+        raise AgxError(f"{op}: q_used={q_used} outside [0, {q_total}]")
+    arr = None
+    if sizes is not None:
+        if len(sizes) != q_total:
+            raise AgxError(f"{op}: {len(sizes)} sizes for {q_total} stages")
+        arr = (ctypes.c_int32 * q_total)(*[int(v) for v in sizes])
+    if bits is None:
+        bits = max(1, (max([int(v) for v in sizes] if sizes is not None else [k]) - 1).bit_length())
+    return codebooks, q_total, k, d, arr, int(bits)
+
+
+def rvq_step_packet_bytes(n: int, q_used: int, bits: int) -> int:
+    """Bytes of one row's packet: ``ceil(n q_used bits / 8)`` (``agx_rvq_step_packet_bytes``)."""
+    nbytes = int(_lib.load().agx_rvq_step_packet_bytes(n, q_used, bits))
+    if nbytes < 0:
+        raise AgxError(f"rvq_step_packet_bytes: bad arguments (n={n} outside 1 .. {RVQ_STEP_MAX_N}, q_used={q_used} outside 0 .. 64 or "
+                       f"bits={bits} outside 1 .. 16)")
+    return nbytes
+
+
+def rvq_step_encode(z: Tensor, codebooks: Tensor, q_used: int, sizes: Optional[Sequence[int]] = None, counts: Optional[Tensor] = None,
+                    bits: Optional[int] = None, want_zq: bool = True):
+    """The quantiser of a streaming chunk (``agx_rvq_step_encode``): z (B, D, n) fp32, any strides, n <= ``RVQ_STEP_MAX_N`` ->
+    (zq (B, D, n) or None, index (B, n, q_used) int64, packets (B, P) uint8).  Every frame below its row's count (``counts``:
+    int64 (B,), device; None: all n) gets the full defining search; behind the count zq is exact 0, index is -1 and the packet
+    bytes are 0.  Row b's first ``ceil(c_b q_used bits / 8)`` bytes are ``codes_pack(index[b, :c_b], bits)``.  ``bits`` defaults
+    to the width of the widest stage."""
+    lib = _lib.load()
+    _need_gpu(z, codebooks)
+    if z.dtype != torch.float32 or z.dim() != 3:
+        raise AgxError(f"rvq_step_encode: expected a float32 (B, D, n) tensor, got {z.dtype} {tuple(z.shape)}")
+    codebooks, q_total, k, d, arr, bits = _step_operands("rvq_step_encode", codebooks, q_used, sizes, bits)
+    b, dim, n = z.shape
+    if dim != d:
+        raise AgxError(f"rvq_step_encode: frame dim {dim} != codebook dim {d}")
+    if counts is not None:
+        counts = _checked_counts("rvq_step_encode", counts, b, z.device)
+    p = rvq_step_packet_bytes(n, q_used, bits)
+    zq = torch.empty((b, d, n), dtype=torch.float32, device=z.device) if want_zq else None
+    index = torch.empty((b, n, q_used), dtype=torch.int64, device=z.device)
+    packets = torch.empty((b, p), dtype=torch.uint8, device=z.device)
+    nbytes = int(lib.agx_rvq_step_workspace_bytes(b, n, d, k, q_used))
+    ws = _workspace(nbytes, z.device, "agx_rvq_step_workspace_bytes") if nbytes else None
+    zsb, zsd, zst = z.stride()
+    qsb, qsd, qst = zq.stride() if want_zq else (0, 0, 0)
+    _lib.check(lib.agx_rvq_step_encode(_ptr(z), zsb, zst, zsd, _ptr(codebooks), arr and ctypes.cast(arr, ctypes.c_void_p), _ptr(counts),
+                                       b, n, d, k, q_total, q_used, bits, _ptr(zq), qsb, qst, qsd, _ptr(index),
+                                       _ptr(packets) if p else None, _ptr(ws), nbytes, _stream()), "agx_rvq_step_encode")
+    return zq, index, packets
+
+
+def rvq_step_decode(packets: Tensor, n: int, codebooks: Tensor, q_used: int, bits: int, sizes: Optional[Sequence[int]] = None,
+                    counts: Optional[Tensor] = None, want_index: bool = False):
+    """Packets of ``rvq_step_encode`` -> zq (B, D, n), or (zq, index (B, n, q_used)) with ``want_index``: one launch
+    (``agx_rvq_step_decode``).  Behind a row's count zq is exact 0 and index -1, and the packet bytes there are not read; a code
+    ``>= sizes[q]`` adds nothing."""
+    lib = _lib.load()
+    _need_gpu(packets, codebooks)
+    codebooks, q_total, k, d, arr, bits = _step_operands("rvq_step_decode", codebooks, q_used, sizes, bits)
+    p = rvq_step_packet_bytes(n, q_used, bits)
+    if packets.dtype != torch.uint8 or packets.dim() != 2 or packets.shape[1] != p or not packets.is_contiguous():
+        raise AgxError(f"rvq_step_decode: packets must be a contiguous uint8 (B, {p}) tensor (n={n}, q_used={q_used}, bits={bits}), got "
+                       f"{packets.dtype} {tuple(packets.shape)}")
+    b = packets.shape[0]
+    if counts is not None:
+        counts = _checked_counts("rvq_step_decode", counts, b, packets.device)
+    zq = torch.empty((b, d, n), dtype=torch.float32, device=packets.device)
+    index = torch.empty((b, n, q_used), dtype=torch.int64, device=packets.device) if want_index else None
+    qsb, qsd, qst = zq.stride()
+    _lib.check(lib.agx_rvq_step_decode(_ptr(packets) if p else None, bits, _ptr(codebooks), arr and ctypes.cast(arr, ctypes.c_void_p),
+                                       _ptr(counts), b, n, d, k, q_total, q_used, _ptr(zq), qsb, qst, qsd, _ptr(index), _stream()),
+               "agx_rvq_step_decode")
+    return (zq, index) if want_index else zq
+
+
 # ------------------------------------------------------------------ attention block
 def layernorm_ct(x: Tensor, weight: Optional[Tensor], bias: Optional[Tensor], eps: float = 1e-5) -> Tensor:
     """LayerNorm over the channel dim of a (B, C, T) tensor."""

@@ -26,6 +26,10 @@ a row's latents, ``zq`` and waveform are bit for bit those of an uncounted strea
 behind them is exact 0 (NaN in the chunk there reaches no result and no ring).  ``index`` behind the count is the code of the
 zero latent and means nothing -- slice by ``counts`` -- and ``commit`` is computed over the whole chunk, zero latents included:
 it is not meaningful on a counted call.  ``counts=None`` is the uncounted call, launch for launch.
+
+Packets.  ``encode_codes_stream`` / ``decode_codes_stream`` are the two ends of a wire: the sender's step gives one
+packet row per stream, the receiver's step turns packet rows into audio.  Their quantiser is ``ops.rvq_step_encode`` /
+``ops.rvq_step_decode``, which read ``counts``: ``index`` behind a row's count is -1 and the packet bytes there are 0.
 """
 from __future__ import annotations
 
@@ -300,6 +304,61 @@ def decode_stream(model, zq: Tensor, stream: CodecStream, counts: Optional[Tenso
 def forward_stream(model, x: Tensor, stream: CodecStream, codebook_n: Optional[int] = None, counts: Optional[Tensor] = None):
     zq, commit, index = encode_stream(model, x, stream, codebook_n, counts)
     return decode_stream(model, zq, stream, counts), commit, index
+
+
+# --------------------------------------------------------------------------- packets
+def _step_quantizer(model, what: str, codebook_n):
+    """-> (codebooks (Q, K, D), q_used, sizes or None, bits) of the model's ``ResidualQuantizer`` for the step kernels."""
+    from .quantizer import ResidualQuantizer
+    q = model.quantizer
+    if not isinstance(q, ResidualQuantizer):
+        raise NotImplementedError(f"{what}: the bottleneck {type(q).__name__} is not a ResidualQuantizer")
+    uniform = min(q.codebook_sizes) == q.codebook_size
+    return q.codebooks.detach(), q._q_used(codebook_n), None if uniform else q.codebook_sizes, model._code_bits
+
+
+def encode_codes_stream(model, x: Tensor, stream: CodecStream, codebook_n: Optional[int] = None, counts: Optional[Tensor] = None):
+    """The sender's step -> (zq (B, D, n), index (B, n, Q), packets (B, P) uint8): ``encode_latents_stream``, then the RVQ step
+    (``ops.rvq_step_encode``: the full defining search of every frame below its row's count).  Behind a row's count ``zq`` is exact
+    0, ``index`` is -1 and the packet bytes are 0; row ``b``'s first ``ceil(c_b Q bits / 8)`` bytes are its packet, ``bits =
+    model._code_bits``.  Only the encoder rings of ``stream`` are used."""
+    cbs, q_used, sizes, bits = _step_quantizer(model, "encode_codes_stream", codebook_n)      # refusals precede the first launch
+    if isinstance(stream, CodecStream) and stream.max_chunk > ops.RVQ_STEP_MAX_N:
+        frames = model.rearrange_in(x).shape[-1] // stream.scale_factor
+        if frames > ops.RVQ_STEP_MAX_N:
+            raise AgxError(f"encode_codes_stream: a chunk of {frames} frames exceeds the {ops.RVQ_STEP_MAX_N} frames a quantiser step takes")
+    z = encode_latents_stream(model, x, stream, counts)
+    return ops.rvq_step_encode(z, cbs, q_used, sizes, counts, bits)
+
+
+def decode_codes_stream(model, packets: Tensor, stream: CodecStream, frames: int, codebook_n: Optional[int] = None,
+                        counts: Optional[Tensor] = None):
+    """The receiver's step -> (y, index (B, frames, Q)): the packets of ``frames`` frames per row (``encode_codes_stream``; the bytes
+    behind a row's count are not read) through ``ops.rvq_step_decode`` and the decoder stack step.  Only the decoder rings of
+    ``stream`` are used."""
+    what = "decode_codes_stream"
+    cbs, q_used, sizes, bits = _step_quantizer(model, what, codebook_n)
+    if not isinstance(stream, CodecStream) or stream.model_id != id(model):
+        raise AgxError(f"{what}: the stream belongs to another model (model.new_stream makes one for this model)")
+    if model.training:
+        raise NotImplementedError(f"{what}: a stream is inference only: call model.eval() (there is no backward through a stream)")
+    frames = int(frames)
+    if not 1 <= frames <= stream.max_chunk:
+        raise AgxError(f"{what}: frames = {frames} outside 1 .. the stream's max_chunk = {stream.max_chunk}")
+    if frames > ops.RVQ_STEP_MAX_N:
+        raise AgxError(f"{what}: frames = {frames} exceeds the {ops.RVQ_STEP_MAX_N} frames a quantiser step takes")
+    width = -((-frames * q_used * bits) // 8)
+    if not isinstance(packets, Tensor) or packets.dtype != torch.uint8 or packets.dim() != 2 or packets.shape[1] != width:
+        got = f"{packets.dtype} {tuple(packets.shape)}" if isinstance(packets, Tensor) else type(packets).__name__
+        raise AgxError(f"{what}: packets of {frames} frames x {q_used} codes x {bits} bits are uint8 (B, {width}), got {got}")
+    if packets.shape[0] != stream.batch:
+        raise AgxError(f"{what}: the packets have batch {packets.shape[0]}, the stream has {stream.batch}")
+    if packets.device != stream.device:
+        raise AgxError(f"{what}: the packets are on '{packets.device}', the stream on '{stream.device}'")
+    if counts is not None:
+        ops._checked_counts(what, counts, stream.batch, stream.device, on="the stream on")
+    zq, index = ops.rvq_step_decode(packets.contiguous(), frames, cbs, q_used, bits, sizes, counts, want_index=True)
+    return decode_stream(model, zq, stream, counts), index
 
 
 def flush_counts(stream: CodecStream, rows, n: int) -> Tensor:

@@ -606,6 +606,22 @@ class CausalVQAE(nn.Module):
                                         accumulate=zq is not None)
             return self.decode(zq.transpose(1, 2).contiguous()), index
 
+    def compress_stream(self, x_chunk, stream, codebook_n=None, counts=None):
+        """The sender's step of a live stream: the next ``n`` whole frames of every row -> (packets (B, P) uint8, index (B, n, Q)),
+        ``P = ceil(n Q bits / 8)``.  Row ``b``'s first ``ceil(c_b Q bits / 8)`` bytes are its packet -- ``ops.codes_pack`` of its
+        ``c_b = clamp(counts[b], 0, n)`` frames' codes -- and every byte behind them is 0; ``index`` behind the count is -1.  Uses
+        only the encoder rings of ``stream``."""
+        from . import streaming
+        _, index, packets = streaming.encode_codes_stream(self, x_chunk, stream, codebook_n, counts)
+        return packets, index
+
+    def decompress_stream(self, packets, stream, frames, codebook_n=None, counts=None):
+        """The receiver's step: packet rows of ``frames`` frames (``compress_stream``) -> (y, index), ``y`` as ``decode_stream``
+        returns it.  The bytes behind a row's count are not read.  Uses only the decoder rings of ``stream``; ``finish``,
+        ``decode_flush`` and ``reset`` are those of any stream."""
+        from . import streaming
+        return streaming.decode_codes_stream(self, packets, stream, frames, codebook_n, counts)
+
     def replace_quantizer(self, new_quantizer):
         self.quantizer = new_quantizer
 

@@ -26,7 +26,7 @@
 extern "C" {
 #endif
 
-#define AGX_VERSION 122 /* still 122 with the dropout entry points (agx_attention_alibi_dropout, agx_attention_alibi_dropout_backward, agx_attention_dropout_backward_workspace_bytes, agx_attention_dropout_kernel_name, agx_dropout_add) and with the cross-attention entry points (agx_attention_alibi_cross, agx_attention_alibi_cross_backward, agx_attention_cross_backward_workspace_bytes, agx_attention_cross_kernel_name): the ABI only grew -- no existing symbol, struct or meaning changed, so a binding made for 122 keeps working and the number stays; 122: agx_attention_kernel_name, agx_attention_backward_kernel_name (which attention kernel the forward / backward entry points run); 121: agx_conv_bwd_weight_kernel_name, agx_conv2d_bwd_weight_kernel_name, agx_conv_grouped_bwd_weight_kernel_name (kernel, operand copy, contraction slices and items of the weight-gradient ops); 120: activation planes (agx_planes_bytes / agx_planes_split / agx_conv_forward_planes / agx_conv_planes_supported): pre-split bf16x3 input of the decoder's resampling convs; conv_p one-phase geometries (k = 1, "same" k = 11 / 3) with GELU / residual epilogues; 119: agx_rvq_verify_counts + knob rvq_verify (debug: the full defining search beside the fast path); agx_rvq_debug_stamps and the b3_dbg 7/8/9 bound knobs exist in the probe build only; 118: agx_feature_means(_backward) (the feature-matching pair in one pass); 117: agx_rvq_debug_stamps (diagnostic); 116: agx_multires_backward, agx_layernorm_ct one-pass kernel (same signature); agx_rvq_forward (legacy form) needs the workspace of agx_rvq_workspace_bytes since 114; 115: agx_rvq_ema_stats, agx_conv2d_bwd_data_kernel_name; 114: agx_attention_alibi_backward_ex (any T), agx_rvq_forward_ex; 113: tile images (resblock_p / conv_p), agx_attention_alibi_ex, agx_sizeof_*; 0.1.1: agx_conv_desc gained groups / padding (zero = old behaviour); 111: resample, conv2d column split */
+#define AGX_VERSION 122 /* still 122 with the RVQ streaming step (agx_rvq_step_packet_bytes, agx_rvq_step_workspace_bytes, agx_rvq_step_encode, agx_rvq_step_decode), with the dropout entry points (agx_attention_alibi_dropout, agx_attention_alibi_dropout_backward, agx_attention_dropout_backward_workspace_bytes, agx_attention_dropout_kernel_name, agx_dropout_add) and with the cross-attention entry points (agx_attention_alibi_cross, agx_attention_alibi_cross_backward, agx_attention_cross_backward_workspace_bytes, agx_attention_cross_kernel_name): the ABI only grew -- no existing symbol, struct or meaning changed, so a binding made for 122 keeps working and the number stays; 122: agx_attention_kernel_name, agx_attention_backward_kernel_name (which attention kernel the forward / backward entry points run); 121: agx_conv_bwd_weight_kernel_name, agx_conv2d_bwd_weight_kernel_name, agx_conv_grouped_bwd_weight_kernel_name (kernel, operand copy, contraction slices and items of the weight-gradient ops); 120: activation planes (agx_planes_bytes / agx_planes_split / agx_conv_forward_planes / agx_conv_planes_supported): pre-split bf16x3 input of the decoder's resampling convs; conv_p one-phase geometries (k = 1, "same" k = 11 / 3) with GELU / residual epilogues; 119: agx_rvq_verify_counts + knob rvq_verify (debug: the full defining search beside the fast path); agx_rvq_debug_stamps and the b3_dbg 7/8/9 bound knobs exist in the probe build only; 118: agx_feature_means(_backward) (the feature-matching pair in one pass); 117: agx_rvq_debug_stamps (diagnostic); 116: agx_multires_backward, agx_layernorm_ct one-pass kernel (same signature); agx_rvq_forward (legacy form) needs the workspace of agx_rvq_workspace_bytes since 114; 115: agx_rvq_ema_stats, agx_conv2d_bwd_data_kernel_name; 114: agx_attention_alibi_backward_ex (any T), agx_rvq_forward_ex; 113: tile images (resblock_p / conv_p), agx_attention_alibi_ex, agx_sizeof_*; 0.1.1: agx_conv_desc gained groups / padding (zero = old behaviour); 111: resample, conv2d column split */
 
 #define AGX_OK 0
 #define AGX_ERR_BAD_SHAPE (-1)
@@ -1177,6 +1177,39 @@ int agx_glu_dwconv_step_counted(const float *u, const float *w, const float *bia
                                 int32_t C, int32_t n, int32_t K, void *stream);
 /* agx_mask_tail with int64 counts for lengths: out[b, c, i] = i < clamp(counts[b], 0, t) ? x[b, c, i] : 0; out may be x. */
 int agx_mask_tail_counted(const float *x, const int64_t *counts, float *out, int32_t batch, int32_t channels, int32_t t, void *stream);
+
+/* ---- RVQ streaming step and its packets -----------------------------------------------------------------------
+ * The quantiser of a streaming chunk: batch rows of n <= AGX_RVQ_STEP_MAX_N frames, counts as above (NULL: every row takes n).
+ * Frame (b, t) is live when t < c_b.  Every live frame gets the full DEFINING search of oracle/rvq_exact.c over every codeword
+ * of every stage (binary64, d ascending, subtract / multiply / add never fused, the smallest k on equal distance,
+ * r <- fl32(r - c) between stages): no score pass, no candidates, no error bound, and no input it is slow on.
+ *   codebooks : (q_total, K, D) fp32; sizes: host int32[q_total] or NULL, the real codewords of each stage (agx_rvq_pack_sized).
+ *   zq        : (B, D, n) by strides, fp32, may be NULL; live: ((0 + c_0) + c_1) + .. in binary32, stage order; dead: exact 0.
+ *   index     : (B, n, q_used) int64, contiguous; live: the codes; dead: -1.
+ *   packets   : (B, P) uint8, contiguous, P = agx_rvq_step_packet_bytes(n, q_used, bits), may be NULL.  Row b's first
+ *               ceil(c_b q_used bits / 8) bytes are the dense little-endian packing of its c_b q_used codes, frame-major and
+ *               stage-minor -- what agx_codes_pack gives for index[b, :c_b]; the unused high bits of the last byte and every
+ *               byte behind it are 0.  Rows never share a byte, and P does not depend on counts.
+ *   workspace : agx_rvq_step_workspace_bytes() bytes, 8-byte aligned; written before it is read.
+ * NaN or anything else in a dead frame's latent reaches no output; a NaN in a live frame gives unspecified codes, in bounds.
+ * q_used == 0: zq = 0 and P = 0.  One launch per stage and one for the outputs; no workgroup waits for another.
+ * Refused before the first launch: n > AGX_RVQ_STEP_MAX_N, q_total > 64, bits outside 1 .. 16, D > 8192, K > 65536, a stage
+ * wider than 2^bits when packets are asked for, NULL pointers, a small workspace. */
+#define AGX_RVQ_STEP_MAX_N 32
+/* ceil(n q_used bits / 8); host only; AGX_ERR_BAD_SHAPE (negative) on n outside 1 .. AGX_RVQ_STEP_MAX_N, q_used outside 0 .. 64
+ * or bits outside 1 .. 16. */
+int64_t agx_rvq_step_packet_bytes(int32_t n, int32_t q_used, int32_t bits);
+size_t agx_rvq_step_workspace_bytes(int32_t batch, int32_t n, int32_t dim, int32_t k, int32_t q_used);
+int agx_rvq_step_encode(const float *z, int64_t z_sb, int64_t z_st, int64_t z_sd, const float *codebooks, const int32_t *sizes,
+                        const int64_t *counts, int32_t batch, int32_t n, int32_t dim, int32_t k, int32_t q_total, int32_t q_used,
+                        int32_t bits, float *zq, int64_t q_sb, int64_t q_st, int64_t q_sd, int64_t *index, uint8_t *packets,
+                        void *workspace, size_t workspace_bytes, void *stream);
+/* Packets -> zq (and index, may be NULL), one launch.  A code >= sizes[q] (a corrupt packet, or bits wider than the stage)
+ * selects no codeword: it adds nothing and reads nothing; index holds it as it was read.  Packet bytes behind a row's first
+ * ceil(c_b q_used bits / 8) are not read.  Dead frames: zq exact 0, index -1. */
+int agx_rvq_step_decode(const uint8_t *packets, int32_t bits, const float *codebooks, const int32_t *sizes, const int64_t *counts,
+                        int32_t batch, int32_t n, int32_t dim, int32_t k, int32_t q_total, int32_t q_used, float *zq, int64_t q_sb,
+                        int64_t q_st, int64_t q_sd, int64_t *index, void *stream);
 
 #ifdef __cplusplus
 }

@@ -19,8 +19,15 @@ Beside every (a) row: the hop's real time, n * 320 / 24 000 s.
 the spread), the counted step with every count full, and the counted step with half of the rows paused (count 0; at B = 1 the one
 row).  The counts are device tensors the captured kernels read, so every replay takes the same frames.
 
+``--wire`` measures the RVQ streaming step and its packets, by the same protocol, against the composed launches of
+the existing paths: (i) the quantiser alone, ``quantize_bcl`` + ``mask_tail`` + ``codes_pack`` against ``rvq_step_encode``; (ii)
+the sender's step, ``encode_stream`` + ``codes_pack`` against ``compress_stream`` -- both with every count full and with half of
+the rows paused; (iii) the receiver's quantiser side, ``codes_unpack`` + Q x ``rvq_dequantize`` + a transposition against
+``rvq_step_decode``.
+
     python tools/codec_stream_bench.py [--plain-only] > profiles/codec_stream.txt
     python tools/codec_stream_bench.py --counts > profiles/stream_counts.txt
+    python tools/codec_stream_bench.py --wire > profiles/rvq_step.txt
 """
 import argparse
 import os
@@ -111,16 +118,120 @@ def counted(model, dev, gen):
                   f"{statistics.median(times[names[2]]) / base:.3f}; the uncounted step against itself: {spread:.2f} us")
 
 
+def _verdict(times, new, old):
+    """A claim holds when the new case's slowest round is below the fastest round of both rows of its comparator."""
+    names = list(times)
+    rows = [times[n] for n in names if n.startswith(old)]
+    assert len(rows) == 2 and new in times, (new, old, names)
+    med = [statistics.median(r) for r in rows]
+    ok = max(times[new]) < min(rows[0] + rows[1])
+    print(f"  {new} / {old} = {statistics.median(times[new]) / min(med):.3f}; comparator against itself: {abs(med[0] - med[1]):.2f} us; "
+          f"new's slowest round below the comparator's fastest: {'yes' if ok else 'NO'}")
+    return ok
+
+
+def wire(model, dev, gen):
+    """The RVQ streaming step and its packets beside the composed launches they replace, B in {1, 8}, n in {1, 4}:
+    (i) the quantiser alone, (ii) the sender's step, (iii) the receiver's quantiser side; full counts and half of the rows paused."""
+    from audio_generation_amd import ops, streaming
+    sf, bits, quant = model.scale_factor, model._code_bits, model.quantizer
+    cbs, q = quant.codebooks.detach(), quant.num_quantizers
+    met = {"(i)": [], "(ii)": [], "(iii)": []}
+    paused = {}
+    for b in (1, 8):
+        for n in (1, 4):
+            chunk = (0.1 * torch.randn(b, 1, n * sf, generator=gen)).to(dev)
+            full = torch.full((b,), n, dtype=torch.int64, device=dev)
+            half = full.clone()
+            half[b // 2:] = 0                                                       # B = 1: the one row is paused
+            with torch.no_grad():                                                   # the latents a step hands its quantiser
+                z = {"full": streaming.encode_latents_stream(model, chunk, model.new_stream(b, max_chunk=4), full),
+                     "half": streaming.encode_latents_stream(model, chunk, model.new_stream(b, max_chunk=4), half)}
+            counts = {"full": full, "half": half}
+            tag = {"full": "every row full", "half": f"{b - b // 2} of {b} rows paused"}
+            print(f"\nB = {b}, n = {n} new frames")
+
+            def old_q(which):
+                zq, index, _ = quant.quantize_bcl(z[which], None, update_codebook=False, prioritize_early=False)
+                return ops.mask_tail(zq, None, counts=counts[which]), ops.codes_pack(index, bits)
+
+            cases = []
+            for which in ("full", "half"):
+                cases += [(f"(i) quantize_bcl + mask_tail + codes_pack, {tag[which]}", lambda which=which: old_q(which)),
+                          (f"(i) rvq_step_encode, {tag[which]}",
+                           lambda which=which: ops.rvq_step_encode(z[which], cbs, q, None, counts[which], bits))]
+            cases += [(name + " (again)", fn) for name, fn in cases[0::2]]
+            times = measure(cases, STEPS_PER_GRAPH)
+            show(times)
+            for which in ("full", "half"):
+                ok = _verdict(times, f"(i) rvq_step_encode, {tag[which]}", f"(i) quantize_bcl + mask_tail + codes_pack, {tag[which]}")
+                if which == "full":
+                    met["(i)"].append(ok)
+            paused[(b, n, "(i)")] = (times[f"(i) rvq_step_encode, {tag['half']}"], times[f"(i) rvq_step_encode, {tag['full']}"])
+
+            streams = [model.new_stream(b, max_chunk=4) for _ in range(4)]
+
+            def old_send(s, which):
+                _, _, index = model.encode_stream(chunk, s, counts=counts[which])
+                return ops.codes_pack(index, bits)
+
+            cases = []
+            for i, which in enumerate(("full", "half")):
+                cases += [(f"(ii) encode_stream + codes_pack, {tag[which]}", lambda s=streams[2 * i], which=which: old_send(s, which)),
+                          (f"(ii) compress_stream, {tag[which]}",
+                           lambda s=streams[2 * i + 1], which=which: model.compress_stream(chunk, s, counts=counts[which]))]
+            cases += [(name + " (again)", fn) for name, fn in cases[0::2]]
+            times = measure(cases, STEPS_PER_GRAPH)
+            show(times)
+            for which in ("full", "half"):
+                ok = _verdict(times, f"(ii) compress_stream, {tag[which]}", f"(ii) encode_stream + codes_pack, {tag[which]}")
+                if which == "full":
+                    met["(ii)"].append(ok)
+            paused[(b, n, "(ii)")] = (times[f"(ii) compress_stream, {tag['half']}"], times[f"(ii) compress_stream, {tag['full']}"])
+
+            with torch.no_grad():
+                _, index, packets = ops.rvq_step_encode(z["full"], cbs, q, None, None, bits)
+            stream_bytes = ops.codes_pack(index, bits)
+
+            def old_recv():
+                idx = ops.codes_unpack(stream_bytes, b * n * q, bits).reshape(b, n, q)
+                zq = None
+                for i in range(q):
+                    zq = ops.rvq_dequantize(cbs[i], idx[..., i], out=zq, accumulate=zq is not None)
+                return zq.transpose(1, 2).contiguous()
+
+            cases = [("(iii) codes_unpack + Q x rvq_dequantize + transposition", old_recv),
+                     ("(iii) rvq_step_decode", lambda: ops.rvq_step_decode(packets, n, cbs, q, bits)),
+                     ("(iii) codes_unpack + Q x rvq_dequantize + transposition (again)", old_recv)]
+            times = measure(cases, STEPS_PER_GRAPH)
+            show(times)
+            met["(iii)"].append(_verdict(times, "(iii) rvq_step_decode", "(iii) codes_unpack + Q x rvq_dequantize + transposition"))
+    print("\n(a) full counts, new below old by more than the spread: quantiser alone "
+          f"{sum(met['(i)'])} of {len(met['(i)'])} cases, sender's step {sum(met['(ii)'])} of {len(met['(ii)'])} cases")
+    for (b, n, what), (h, f) in paused.items():
+        if b == 8:
+            print(f"(b) B = 8, n = {n}, {what}: 4 rows paused / every row full = {statistics.median(h) / statistics.median(f):.3f} "
+                  f"(paused's slowest round at or below full's fastest: {'yes' if max(h) <= min(f) else 'NO'}; median at or below: "
+                  f"{'yes' if statistics.median(h) <= statistics.median(f) else 'NO'})")
+    print(f"(c) receiver's quantiser side, new below old by more than the spread: {sum(met['(iii)'])} of {len(met['(iii)'])} cases")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--plain-only", action="store_true", help="measure (b) alone (a checkout without the streaming step)")
     ap.add_argument("--counts", action="store_true", help="the step with per-row frame counts beside the uncounted step")
+    ap.add_argument("--wire", action="store_true", help="the RVQ streaming step and its packets beside the composed launches")
     args = ap.parse_args()
     assert torch.cuda.is_available(), "needs the MI355X"
     dev = "cuda"
     model = config_s(dev)
     sf = model.scale_factor
     gen = torch.Generator().manual_seed(0)
+    if args.wire:
+        print(f"device: {torch.cuda.get_device_name(0)}; config S; per-call time over {ROUNDS} replays of a graph of {STEPS_PER_GRAPH} "
+              "back-to-back calls (median [min .. max]); --wire")
+        wire(model, dev, gen)
+        return
     if args.counts:
         print(f"device: {torch.cuda.get_device_name(0)}; config S; per-call time over {ROUNDS} replays of a graph of {STEPS_PER_GRAPH} "
               "back-to-back calls (median [min .. max]); --counts")
