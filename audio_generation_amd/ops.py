@@ -59,7 +59,7 @@ def _conv2d_macs(desc) -> int:
 def _kernel_name(symbol: str, *what, size: int = 96) -> str:
     """The answer of one of the library's host-only name queries (``agx_*_kernel_name``) for a descriptor or a shape."""
     buf = ctypes.create_string_buffer(size)
-    args = [ctypes.byref(w) if isinstance(w, ctypes.Structure) else int(w) for w in what]
+    args = [ctypes.byref(w) if isinstance(w, ctypes.Structure) else w if isinstance(w, float) else int(w) for w in what]
     _lib.check(getattr(_lib.load(), symbol)(*args, buf, len(buf)), symbol)
     return buf.value.decode()
 
@@ -568,6 +568,59 @@ def layernorm_ct(x: Tensor, weight: Optional[Tensor], bias: Optional[Tensor], ep
 ATTN_FP32, ATTN_BF16 = 0, 1
 
 
+def _attn_operands(op: str, q: Tensor, kv: Optional[Tensor], heads: int, head_dim: int, qkv_q: bool = False, self_form: bool = True):
+    """The (q, kv) pair of an attention call as the launchers take it -- the one place that knows the three layouts:
+
+    * ``kv`` None: ``q`` is a (B, 3*H*Dh, T) qkv tensor read in place.  The K rows start ``hd * T`` floats into each batch row
+      (the V rows follow them) and both batch strides are ``3 * hd * T``.
+    * ``q`` (B, H*Dh, Tq) and ``kv`` (B, 2*H*Dh, Tk), each at its own batch stride.
+    * ``qkv_q``: beside ``kv`` -- a (B, 2*H*Dh, cap) key/value buffer -- ``q`` may also be a (B, 3*H*Dh, Tq) qkv tensor of which
+      only the Q rows, the first H*Dh of every batch row, are read: the q batch stride is that of the tensor given.
+
+    Both tensors are made contiguous fp32 (``_f32c``: a wrapper that has to refuse another dtype first converts that tensor
+    first; a second conversion changes nothing), then the channel counts and the batch are checked.  ``self_form`` False: the
+    op has no in-place form and ``kv`` is a tensor.  Returns the view ``(b, tq, tk, hd, q, kv, qp, kp, sq, skv)``, one flat tuple (the
+    cached decode step comes through here once per layer and step): ``tk`` the columns of the kv tensor (T, Tk or cap), ``q`` /
+    ``kv`` the contiguous tensors, and the four C arguments -- q pointer, kv pointer, q batch stride, kv batch stride (in floats)."""
+    q = _f32c(q)
+    hd = heads * head_dim
+    b, cq, tq = q.shape
+    if kv is None and self_form:
+        if cq != 3 * hd:
+            raise AgxError(f"{op}: qkv has {cq} channels, expected {3 * hd}")
+        at = q.data_ptr()
+        return b, tq, tq, hd, q, None, ctypes.c_void_p(at), ctypes.c_void_p(at + 4 * hd * tq), 3 * hd * tq, 3 * hd * tq
+    kv = _f32c(kv)
+    bk, ckv, tk = kv.shape
+    if cq != hd and not (qkv_q and cq == 3 * hd):
+        raise AgxError(f"{op}: q has {cq} channels, expected {hd}" + (f" (or a {3 * hd}-channel qkv tensor)" if qkv_q else ""))
+    if ckv != 2 * hd:
+        raise AgxError(f"{op}: kv has {ckv} channels, expected {2 * hd}")
+    if bk != b:
+        raise AgxError(f"{op}: q has batch {b}, kv has batch {bk}")
+    return b, tq, tk, hd, q, kv, ctypes.c_void_p(q.data_ptr()), ctypes.c_void_p(kv.data_ptr()), cq * tq, 2 * hd * tk
+
+
+def _attn_grads(view):
+    """The uninitialised gradients of a view of ``_attn_operands``, laid out as its tensors are: ``(abi, grads)`` with ``abi`` the
+    view's four C arguments for the gradients and ``grads`` what the backward returns -- the one dqkv tensor of the in-place form,
+    written through pointers and strides, else ``(dq, dkv)``."""
+    _, tq, _, hd, q, kv, _, _, sq, skv = view
+    dq = torch.empty_like(q)
+    if kv is None:
+        return (_ptr(dq), ctypes.c_void_p(dq.data_ptr() + 4 * hd * tq), sq, skv), dq
+    dkv = torch.empty_like(kv)
+    return (_ptr(dq), _ptr(dkv), sq, skv), (dq, dkv)
+
+
+def _attn_same_out(op: str, view, out: Tensor, dout: Tensor, of: str = "") -> None:
+    """A backward's ``out`` and ``dout`` are both (B, H*Dh, Tq) of the view (``of``: whose shape that is, in the op's words)."""
+    b, tq, _, hd, *_ = view
+    want = (b, hd, tq)
+    if tuple(out.shape) != want or dout.shape != out.shape:
+        raise AgxError(f"{op}: out {tuple(out.shape)} / dout {tuple(dout.shape)} are not {of}{want}")
+
+
 def attention_alibi(qkv: Tensor, slopes: Tensor, heads: int, head_dim: int, scale_div: float,
                     precision: int = ATTN_FP32, flash: bool = False) -> Tensor:
     """softmax(QK^T/scale_div + ALiBi) V on a (B, 3*H*Dh, T) tensor -> (B, H*Dh, T), any T.
@@ -575,11 +628,8 @@ def attention_alibi(qkv: Tensor, slopes: Tensor, heads: int, head_dim: int, scal
     config 3); ``flash`` forces the online-softmax form for fp32 at T <= 256 as well."""
     lib = _lib.load()
     _need_gpu(qkv, slopes)
-    qkv = _f32c(qkv)
-    b, c3, t = qkv.shape
-    if c3 != 3 * heads * head_dim:
-        raise AgxError(f"attention_alibi: qkv has {c3} channels, expected {3 * heads * head_dim}")
-    out = torch.empty((b, heads * head_dim, t), dtype=torch.float32, device=qkv.device)
+    b, t, _, hd, qkv, *_ = _attn_operands("attention_alibi", qkv, None, heads, head_dim)
+    out = torch.empty((b, hd, t), dtype=torch.float32, device=qkv.device)
     tok = None
     if _observer is not None:    # the label tools/config_bench.py keys on: [:bf16][:flash], flash = any online-softmax kernel
         single_pass = attention_kernel_name(b, heads, head_dim, t, precision, flash).startswith("attention_alibi<")
@@ -649,17 +699,6 @@ def attention_alibi_backward(qkv: Tensor, slopes: Tensor, dout: Tensor, heads: i
     return dqkv
 
 
-def _cross_shapes(op: str, q: Tensor, kv: Tensor, heads: int, head_dim: int):
-    (b, cq, tq), (bk, ckv, tk) = q.shape, kv.shape
-    if cq != heads * head_dim:
-        raise AgxError(f"{op}: q has {cq} channels, expected {heads * head_dim}")
-    if ckv != 2 * heads * head_dim:
-        raise AgxError(f"{op}: kv has {ckv} channels, expected {2 * heads * head_dim}")
-    if bk != b:
-        raise AgxError(f"{op}: q has batch {b}, kv has batch {bk}")
-    return b, tq, tk
-
-
 def attention_cross_kernel_name(batch: int, heads: int, head_dim: int, tq: int, tk: int, backward: bool = False) -> str:
     """The kernel ``attention_alibi_cross`` runs for this shape, with ``backward`` the three kernels of
     ``attention_alibi_cross_backward`` (host-only); ``AgxError`` with the launcher's message if it refuses."""
@@ -671,9 +710,8 @@ def attention_alibi_cross(q: Tensor, kv: Tensor, slopes: Tensor, heads: int, hea
     then V rows) -> (B, H*Dh, Tq); the bias is ``-slope_h |i - j|`` on the absolute positions.  fp32, any Tq, Tk >= 1."""
     lib = _lib.load()
     _need_gpu(q, kv, slopes)
-    q, kv = _f32c(q), _f32c(kv)
-    b, tq, tk = _cross_shapes("attention_alibi_cross", q, kv, heads, head_dim)
-    out = torch.empty((b, heads * head_dim, tq), dtype=torch.float32, device=q.device)
+    b, tq, tk, hd, q, kv, *_ = _attn_operands("attention_alibi_cross", q, kv, heads, head_dim, self_form=False)
+    out = torch.empty((b, hd, tq), dtype=torch.float32, device=q.device)
     tok = None
     if _observer is not None:    # work: QK^T and PV, 2 * B * H * Tq * Tk * Dh MACs; bytes: q, kv read once + out written once
         tok = _observer.begin("other", ("attention_alibi_cross:flash", 4 * (q.numel() + kv.numel() + out.numel()),
@@ -691,10 +729,9 @@ def attention_alibi_cross_backward(q: Tensor, kv: Tensor, slopes: Tensor, out: T
     lib = _lib.load()
     _need_gpu(q, kv, slopes, out, dout)
     q, kv, out, dout = _f32c(q), _f32c(kv), _f32c(out), _f32c(dout)
-    b, tq, tk = _cross_shapes("attention_alibi_cross_backward", q, kv, heads, head_dim)
-    if out.shape != q.shape or dout.shape != q.shape:
-        raise AgxError(f"attention_alibi_cross_backward: out {tuple(out.shape)} / dout {tuple(dout.shape)} are not q's {tuple(q.shape)}")
-    dq, dkv = torch.empty_like(q), torch.empty_like(kv)
+    view = b, tq, tk, _, q, kv, *_ = _attn_operands("attention_alibi_cross_backward", q, kv, heads, head_dim, self_form=False)
+    _attn_same_out("attention_alibi_cross_backward", view, out, dout, of="q's ")
+    _, (dq, dkv) = _attn_grads(view)
     nbytes = int(lib.agx_attention_cross_backward_workspace_bytes(b, heads, tq))
     ws = _workspace(nbytes, q.device, "agx_attention_cross_backward_workspace_bytes")
     _lib.check(lib.agx_attention_alibi_cross_backward(_ptr(q), _ptr(kv), _ptr(_f32c(slopes)), _ptr(out), _ptr(dout), _ptr(dq),
@@ -714,28 +751,10 @@ def _drop_args(p: float, seed: int, stream_id: int):
     return ctypes.c_double(float(p)), ctypes.c_uint64(int(seed) & 0xFFFFFFFFFFFFFFFF), ctypes.c_uint32(int(stream_id) & 0xFFFFFFFF)
 
 
-def _off(t: Tensor, floats: int):
-    return ctypes.c_void_p(t.data_ptr() + 4 * floats)
-
-
 def attention_dropout_kernel_name(batch: int, heads: int, head_dim: int, tq: int, tk: int, p: float, backward: bool = False) -> str:
     """The kernel ``attention_alibi_dropout`` runs for this shape, with ``backward`` the three kernels of its backward
     (host-only); ``AgxError`` with the launcher's message if it refuses (head_dim > 128, p outside [0, 1))."""
-    buf = ctypes.create_string_buffer(96)
-    _lib.check(_lib.load().agx_attention_dropout_kernel_name(batch, heads, head_dim, tq, tk, float(p), int(bool(backward)), buf,
-                                                             len(buf)), "agx_attention_dropout_kernel_name")
-    return buf.value.decode()
-
-
-def _drop_shapes(op: str, q: Tensor, kv: Optional[Tensor], heads: int, head_dim: int):
-    """(b, tq, tk, hd) -- ``kv`` None: ``q`` is a (B, 3*H*Dh, T) qkv tensor, read in place through pointers and strides."""
-    hd = heads * head_dim
-    if kv is not None:
-        return (*_cross_shapes(op, q, kv, heads, head_dim), hd)
-    b, c3, t = q.shape
-    if c3 != 3 * hd:
-        raise AgxError(f"{op}: qkv has {c3} channels, expected {3 * hd}")
-    return b, t, t, hd
+    return _kernel_name("agx_attention_dropout_kernel_name", batch, heads, head_dim, tq, tk, float(p), bool(backward))
 
 
 def attention_alibi_dropout(q: Tensor, kv: Optional[Tensor], slopes: Tensor, heads: int, head_dim: int, scale_div: float,
@@ -745,11 +764,8 @@ def attention_alibi_dropout(q: Tensor, kv: Optional[Tensor], slopes: Tensor, hea
     (B, 3*H*Dh, T) qkv tensor (no copy).  fp32, head_dim <= 128, 0 <= p < 1."""
     lib = _lib.load()
     _need_gpu(q, kv, slopes)
-    q = _f32c(q)
-    kv = None if kv is None else _f32c(kv)
-    b, tq, tk, hd = _drop_shapes("attention_alibi_dropout", q, kv, heads, head_dim)
+    b, tq, tk, hd, q, kv, qp, kp, sq, skv = _attn_operands("attention_alibi_dropout", q, kv, heads, head_dim)
     out = torch.empty((b, hd, tq), dtype=torch.float32, device=q.device)
-    qp, kp, sq, skv = (_ptr(q), _ptr(kv), hd * tq, 2 * hd * tk) if kv is not None else (_ptr(q), _off(q, hd * tq), 3 * hd * tq, 3 * hd * tq)
     tok = None
     if _observer is not None:
         tok = _observer.begin("other", ("attention_alibi_dropout:flash", 4 * (q.numel() + (0 if kv is None else kv.numel()) + out.numel()),
@@ -769,26 +785,16 @@ def attention_alibi_dropout_backward(q: Tensor, kv: Optional[Tensor], slopes: Te
     lib = _lib.load()
     _need_gpu(q, kv, slopes, out, dout)
     q, out, dout = _f32c(q), _f32c(out), _f32c(dout)
-    kv = None if kv is None else _f32c(kv)
-    b, tq, tk, hd = _drop_shapes("attention_alibi_dropout_backward", q, kv, heads, head_dim)
-    if tuple(out.shape) != (b, hd, tq) or dout.shape != out.shape:
-        raise AgxError(f"attention_alibi_dropout_backward: out {tuple(out.shape)} / dout {tuple(dout.shape)} are not {(b, hd, tq)}")
-    dq = torch.empty_like(q)
-    if kv is not None:
-        dkv = torch.empty_like(kv)
-        ptrs = (_ptr(q), _ptr(kv), hd * tq, 2 * hd * tk)
-        dptrs = (_ptr(dq), _ptr(dkv), hd * tq, 2 * hd * tk)
-    else:
-        dkv = None
-        ptrs = (_ptr(q), _off(q, hd * tq), 3 * hd * tq, 3 * hd * tq)
-        dptrs = (_ptr(dq), _off(dq, hd * tq), 3 * hd * tq, 3 * hd * tq)
+    view = b, tq, tk, _, q, kv, *abi = _attn_operands("attention_alibi_dropout_backward", q, kv, heads, head_dim)
+    _attn_same_out("attention_alibi_dropout_backward", view, out, dout)
+    dabi, grads = _attn_grads(view)
     nbytes = int(lib.agx_attention_dropout_backward_workspace_bytes(b, heads, tq))
     ws = _workspace(nbytes, q.device, "agx_attention_dropout_backward_workspace_bytes")
-    _lib.check(lib.agx_attention_alibi_dropout_backward(*ptrs, _ptr(_f32c(slopes)), _ptr(out), _ptr(dout), *dptrs, _ptr(ws), nbytes,
+    _lib.check(lib.agx_attention_alibi_dropout_backward(*abi, _ptr(_f32c(slopes)), _ptr(out), _ptr(dout), *dabi, _ptr(ws), nbytes,
                                                         b, heads, head_dim, tq, tk, float(scale_div),
                                                         *_drop_args(p, seed, stream_id), _stream()),
                "agx_attention_alibi_dropout_backward")
-    return dq if kv is None else (dq, dkv)
+    return grads
 
 
 # ------------------------------------------------------------------ ragged batches (include/agx.h "Ragged batches")
@@ -821,12 +827,9 @@ def attention_alibi_ragged(q: Tensor, kv: Optional[Tensor], slopes: Tensor, head
     lib = _lib.load()
     op = "attention_alibi_ragged"
     _need_gpu(q, kv, slopes)
-    q = _f32c(q)
-    kv = None if kv is None else _f32c(kv)
-    b, tq, tk, hd = _drop_shapes(op, q, kv, heads, head_dim)
+    b, tq, tk, hd, q, kv, qp, kp, sq, skv = _attn_operands(op, q, kv, heads, head_dim)
     q_len, k_len = _len_arg(op, q_len, b, "q_len"), _len_arg(op, k_len, b, "k_len")
     out = torch.empty((b, hd, tq), dtype=torch.float32, device=q.device)
-    qp, kp, sq, skv = (_ptr(q), _ptr(kv), hd * tq, 2 * hd * tk) if kv is not None else (_ptr(q), _off(q, hd * tq), 3 * hd * tq, 3 * hd * tq)
     tok = None
     if _observer is not None:    # the full shape: the lengths live on the device
         tok = _observer.begin("other", ("attention_alibi_ragged:flash", 4 * (q.numel() + (0 if kv is None else kv.numel()) + out.numel()),
@@ -848,27 +851,17 @@ def attention_alibi_ragged_backward(q: Tensor, kv: Optional[Tensor], slopes: Ten
     op = "attention_alibi_ragged_backward"
     _need_gpu(q, kv, slopes, out, dout)
     q, out, dout = _f32c(q), _f32c(out), _f32c(dout)
-    kv = None if kv is None else _f32c(kv)
-    b, tq, tk, hd = _drop_shapes(op, q, kv, heads, head_dim)
-    if tuple(out.shape) != (b, hd, tq) or dout.shape != out.shape:
-        raise AgxError(f"{op}: out {tuple(out.shape)} / dout {tuple(dout.shape)} are not {(b, hd, tq)}")
+    view = b, tq, tk, _, q, kv, *abi = _attn_operands(op, q, kv, heads, head_dim)
+    _attn_same_out(op, view, out, dout)
     q_len, k_len = _len_arg(op, q_len, b, "q_len"), _len_arg(op, k_len, b, "k_len")
-    dq = torch.empty_like(q)
-    if kv is not None:
-        dkv = torch.empty_like(kv)
-        ptrs = (_ptr(q), _ptr(kv), hd * tq, 2 * hd * tk)
-        dptrs = (_ptr(dq), _ptr(dkv), hd * tq, 2 * hd * tk)
-    else:
-        dkv = None
-        ptrs = (_ptr(q), _off(q, hd * tq), 3 * hd * tq, 3 * hd * tq)
-        dptrs = (_ptr(dq), _off(dq, hd * tq), 3 * hd * tq, 3 * hd * tq)
+    dabi, grads = _attn_grads(view)
     nbytes = int(lib.agx_attention_ragged_backward_workspace_bytes(b, heads, tq))
     ws = _workspace(nbytes, q.device, "agx_attention_ragged_backward_workspace_bytes")
     count_macs("attention_bwd", 5 * b * heads * tq * tk * head_dim)
-    _lib.check(lib.agx_attention_alibi_ragged_backward(*ptrs, _ptr(_f32c(slopes)), _ptr(q_len), _ptr(k_len), _ptr(out), _ptr(dout),
-                                                       *dptrs, _ptr(ws), nbytes, b, heads, head_dim, tq, tk, float(scale_div),
+    _lib.check(lib.agx_attention_alibi_ragged_backward(*abi, _ptr(_f32c(slopes)), _ptr(q_len), _ptr(k_len), _ptr(out), _ptr(dout),
+                                                       *dabi, _ptr(ws), nbytes, b, heads, head_dim, tq, tk, float(scale_div),
                                                        _stream()), "agx_attention_alibi_ragged_backward")
-    return dq if kv is None else (dq, dkv)
+    return grads
 
 
 def mask_tail(x: Tensor, lengths: Optional[Tensor], out: Optional[Tensor] = None, *, counts: Optional[Tensor] = None) -> Tensor:
@@ -921,12 +914,13 @@ def _cu_arg(op: str, cu: Optional[Tensor], what: str, n_seq: Optional[int] = Non
 
 
 def _packed_args(op: str, q: Tensor, kv: Optional[Tensor], heads: int, head_dim: int, cu_q, cu_k, max_q, max_k):
-    """(nq, nk, hd, cu_q, cu_k, n_seq, max_q, max_k) of a packed call; ``kv`` None: ``q`` is a (1, 3*H*Dh, N) qkv tensor and
-    ``cu_k`` / ``max_k`` default to the queries'."""
+    """(view, cu_q, cu_k, n_seq, max_q, max_k) of a packed call, ``view`` that of ``_attn_operands`` with (nq, nk) for (tq, tk);
+    ``kv`` None: ``q`` is a (1, 3*H*Dh, N) qkv tensor and ``cu_k`` / ``max_k`` default to the queries'."""
+    q, kv = _f32c(q), None if kv is None else _f32c(kv)      # a dtype is refused before the rows are counted
     if q.dim() != 3 or q.shape[0] != 1 or (kv is not None and (kv.dim() != 3 or kv.shape[0] != 1)):
         raise AgxError(f"{op}: a packed batch is one row, q (1, C, N)" + ("" if kv is None else " and kv (1, 2*H*Dh, Nk)") +
                        f": got {tuple(q.shape)}" + ("" if kv is None else f" / {tuple(kv.shape)}"))
-    _, nq, nk, hd = _drop_shapes(op, q, kv, heads, head_dim)
+    view = _attn_operands(op, q, kv, heads, head_dim)
     if kv is None:
         cu_k, max_k = (cu_q if cu_k is None else cu_k), (max_q if max_k is None else max_k)
     elif cu_k is None or max_k is None:
@@ -936,7 +930,7 @@ def _packed_args(op: str, q: Tensor, kv: Optional[Tensor], heads: int, head_dim:
     cu_k = _cu_arg(op, cu_k, "cu_k", n_seq)
     if int(max_q) != max_q or int(max_k) != max_k or max_q < 0 or max_k < 0:
         raise AgxError(f"{op}: max_q = {max_q}, max_k = {max_k}: the bounds of the sequence lengths are integers >= 0")
-    return nq, nk, hd, cu_q, cu_k, n_seq, int(max_q), int(max_k)
+    return view, cu_q, cu_k, n_seq, int(max_q), int(max_k)
 
 
 def attention_alibi_packed(q: Tensor, kv: Optional[Tensor], slopes: Tensor, heads: int, head_dim: int, scale_div: float,
@@ -951,11 +945,9 @@ def attention_alibi_packed(q: Tensor, kv: Optional[Tensor], slopes: Tensor, head
     lib = _lib.load()
     op = "attention_alibi_packed"
     _need_gpu(q, kv, slopes)
-    q = _f32c(q)
-    kv = None if kv is None else _f32c(kv)
-    nq, nk, hd, cu_q, cu_k, n_seq, max_q, max_k = _packed_args(op, q, kv, heads, head_dim, cu_q, cu_k, max_q, max_k)
+    view, cu_q, cu_k, n_seq, max_q, max_k = _packed_args(op, q, kv, heads, head_dim, cu_q, cu_k, max_q, max_k)
+    _, nq, nk, hd, q, kv, qp, kp, _, _ = view        # one row: the kernels take the row strides (nq, nk), not batch strides
     out = torch.empty((1, hd, nq), dtype=torch.float32, device=q.device)
-    qp, kp = (_ptr(q), _ptr(kv)) if kv is not None else (_ptr(q), _off(q, hd * nq))
     tok = None
     if _observer is not None:    # an upper bound of the work, n_seq * max_q * max_k pairs: the lengths live on the device
         tok = _observer.begin("other", ("attention_alibi_packed:flash", 4 * (q.numel() + (0 if kv is None else kv.numel()) + out.numel()),
@@ -978,24 +970,17 @@ def attention_alibi_packed_backward(q: Tensor, kv: Optional[Tensor], slopes: Ten
     op = "attention_alibi_packed_backward"
     _need_gpu(q, kv, slopes, out, dout)
     q, out, dout = _f32c(q), _f32c(out), _f32c(dout)
-    kv = None if kv is None else _f32c(kv)
-    nq, nk, hd, cu_q, cu_k, n_seq, max_q, max_k = _packed_args(op, q, kv, heads, head_dim, cu_q, cu_k, max_q, max_k)
-    if tuple(out.shape) != (1, hd, nq) or dout.shape != out.shape:
-        raise AgxError(f"{op}: out {tuple(out.shape)} / dout {tuple(dout.shape)} are not {(1, hd, nq)}")
-    dq = torch.empty_like(q)
-    if kv is not None:
-        dkv = torch.empty_like(kv)
-        ptrs, dptrs = (_ptr(q), _ptr(kv), nq, nk), (_ptr(dq), _ptr(dkv), nq, nk)
-    else:
-        dkv = None
-        ptrs, dptrs = (_ptr(q), _off(q, hd * nq), nq, nk), (_ptr(dq), _off(dq, hd * nq), nq, nk)
+    view, cu_q, cu_k, n_seq, max_q, max_k = _packed_args(op, q, kv, heads, head_dim, cu_q, cu_k, max_q, max_k)
+    _, nq, nk, _, q, kv, qp, kp, _, _ = view         # one row: the kernels take the row strides (nq, nk), not batch strides
+    _attn_same_out(op, view, out, dout)
+    (dqp, dkp, _, _), grads = _attn_grads(view)
     nbytes = int(lib.agx_attention_packed_backward_workspace_bytes(heads, nq))
     ws = _workspace(nbytes, q.device, "agx_attention_packed_backward_workspace_bytes")
     count_macs("attention_bwd", 5 * heads * min(nq, n_seq * max_q) * min(nk, max_k) * head_dim)
-    _lib.check(lib.agx_attention_alibi_packed_backward(*ptrs, _ptr(_f32c(slopes)), _ptr(cu_q), _ptr(cu_k), _ptr(out), _ptr(dout),
-                                                       *dptrs, _ptr(ws), nbytes, n_seq, heads, head_dim, nq, nk, max_q, max_k,
+    _lib.check(lib.agx_attention_alibi_packed_backward(qp, kp, nq, nk, _ptr(_f32c(slopes)), _ptr(cu_q), _ptr(cu_k), _ptr(out), _ptr(dout),
+                                                       dqp, dkp, nq, nk, _ptr(ws), nbytes, n_seq, heads, head_dim, nq, nk, max_q, max_k,
                                                        float(scale_div), _stream()), "agx_attention_alibi_packed_backward")
-    return dq if kv is None else (dq, dkv)
+    return grads
 
 
 def pack_rows(x: Tensor, cu: Tensor, total: int) -> Tensor:
@@ -1059,30 +1044,16 @@ def attention_alibi_causal(q: Tensor, kv: Optional[Tensor], slopes: Tensor, head
     fp32, head_dim <= 128."""
     lib = _lib.load()
     _need_gpu(q, kv, slopes)
-    q = _f32c(q)
-    hd = heads * head_dim
-    b, cq, tq = q.shape
+    b, tq, cap, hd, q, kv, qp, kp, sq, skv = _attn_operands("attention_alibi_causal", q, kv, heads, head_dim, qkv_q=True)
     if kv is None:
-        if cq != 3 * hd:
-            raise AgxError(f"attention_alibi_causal: qkv has {cq} channels, expected {3 * hd}")
         if tk not in (None, tq):
             raise AgxError(f"attention_alibi_causal: tk = {tk} with kv=None (the keys are the {tq} columns of qkv)")
-        tk, cap = tq, tq
-        qp, kp, sq, skv = _ptr(q), _off(q, hd * tq), 3 * hd * tq, 3 * hd * tq
+        tk = tq
         nbytes = 4 * q.numel()
     else:
-        kv = _f32c(kv)
-        bk, ckv, cap = kv.shape
-        if cq not in (hd, 3 * hd):
-            raise AgxError(f"attention_alibi_causal: q has {cq} channels, expected {hd} (or a {3 * hd}-channel qkv tensor)")
-        if ckv != 2 * hd:
-            raise AgxError(f"attention_alibi_causal: kv has {ckv} channels, expected {2 * hd}")
-        if bk != b:
-            raise AgxError(f"attention_alibi_causal: q has batch {b}, kv has batch {bk}")
         tk = cap if tk is None else int(tk)
         if not 0 <= tk <= cap:
             raise AgxError(f"attention_alibi_causal: tk = {tk} is outside the kv buffer's {cap} columns")
-        qp, kp, sq, skv = _ptr(q), _ptr(kv), cq * tq, 2 * hd * cap
         nbytes = 4 * (b * hd * tq + 2 * b * hd * tk)
     out = torch.empty((b, hd, tq), dtype=torch.float32, device=q.device)
     tok = None
@@ -1103,18 +1074,13 @@ def attention_alibi_causal_backward(qkv: Tensor, slopes: Tensor, out: Tensor, do
     lib = _lib.load()
     _need_gpu(qkv, slopes, out, dout)
     qkv, out, dout = _f32c(qkv), _f32c(out), _f32c(dout)
-    hd = heads * head_dim
-    b, c3, t = qkv.shape
-    if c3 != 3 * hd:
-        raise AgxError(f"attention_alibi_causal_backward: qkv has {c3} channels, expected {3 * hd}")
-    if tuple(out.shape) != (b, hd, t) or dout.shape != out.shape:
-        raise AgxError(f"attention_alibi_causal_backward: out {tuple(out.shape)} / dout {tuple(dout.shape)} are not {(b, hd, t)}")
-    dqkv = torch.empty_like(qkv)
+    view = b, t, _, _, qkv, _, *abi = _attn_operands("attention_alibi_causal_backward", qkv, None, heads, head_dim)
+    _attn_same_out("attention_alibi_causal_backward", view, out, dout)
+    dabi, dqkv = _attn_grads(view)
     nbytes = int(lib.agx_attention_causal_backward_workspace_bytes(b, heads, t))
     ws = _workspace(nbytes, qkv.device, "agx_attention_causal_backward_workspace_bytes")
-    _lib.check(lib.agx_attention_alibi_causal_backward(_ptr(qkv), _off(qkv, hd * t), 3 * hd * t, 3 * hd * t, _ptr(_f32c(slopes)),
-                                                       _ptr(out), _ptr(dout), _ptr(dqkv), _off(dqkv, hd * t), 3 * hd * t, 3 * hd * t,
-                                                       _ptr(ws), nbytes, b, heads, head_dim, t, float(scale_div), _stream()),
+    _lib.check(lib.agx_attention_alibi_causal_backward(*abi, _ptr(_f32c(slopes)), _ptr(out), _ptr(dout), *dabi, _ptr(ws), nbytes,
+                                                       b, heads, head_dim, t, float(scale_div), _stream()),
                "agx_attention_alibi_causal_backward")
     return dqkv
 
@@ -1144,27 +1110,12 @@ def attention_alibi_window(q: Tensor, kv: Optional[Tensor], slopes: Tensor, head
     a 64-bit position.  fp32, head_dim <= 128."""
     lib = _lib.load()
     _need_gpu(q, kv, slopes)
-    q = _f32c(q)
-    hd = heads * head_dim
-    b, cq, tq = q.shape
+    b, tq, cap, hd, q, kv, qp, kp, sq, skv = _attn_operands("attention_alibi_window", q, kv, heads, head_dim, qkv_q=True)
     if kv is None:
-        if cq != 3 * hd:
-            raise AgxError(f"attention_alibi_window: qkv has {cq} channels, expected {3 * hd}")
         if q_pos0 != 0 or ring != 0:
             raise AgxError(f"attention_alibi_window: q_pos0 = {q_pos0}, ring = {ring} with kv=None (the keys are the {tq} columns of qkv)")
-        cap = tq
-        qp, kp, sq, skv = _ptr(q), _off(q, hd * tq), 3 * hd * tq, 3 * hd * tq
         nbytes = 4 * q.numel()
     else:
-        kv = _f32c(kv)
-        bk, ckv, cap = kv.shape
-        if cq not in (hd, 3 * hd):
-            raise AgxError(f"attention_alibi_window: q has {cq} channels, expected {hd} (or a {3 * hd}-channel qkv tensor)")
-        if ckv != 2 * hd:
-            raise AgxError(f"attention_alibi_window: kv has {ckv} channels, expected {2 * hd}")
-        if bk != b:
-            raise AgxError(f"attention_alibi_window: q has batch {b}, kv has batch {bk}")
-        qp, kp, sq, skv = _ptr(q), _ptr(kv), cq * tq, 2 * hd * cap
         nbytes = 4 * (b * hd * tq + 2 * b * hd * min(cap, tq + max(int(window), 1) - 1))
     out = torch.empty((b, hd, tq), dtype=torch.float32, device=q.device)
     tok = None
@@ -1186,19 +1137,13 @@ def attention_alibi_window_backward(qkv: Tensor, slopes: Tensor, out: Tensor, do
     lib = _lib.load()
     _need_gpu(qkv, slopes, out, dout)
     qkv, out, dout = _f32c(qkv), _f32c(out), _f32c(dout)
-    hd = heads * head_dim
-    b, c3, t = qkv.shape
-    if c3 != 3 * hd:
-        raise AgxError(f"attention_alibi_window_backward: qkv has {c3} channels, expected {3 * hd}")
-    if tuple(out.shape) != (b, hd, t) or dout.shape != out.shape:
-        raise AgxError(f"attention_alibi_window_backward: out {tuple(out.shape)} / dout {tuple(dout.shape)} are not {(b, hd, t)}")
-    dqkv = torch.empty_like(qkv)
+    view = b, t, _, _, qkv, _, *abi = _attn_operands("attention_alibi_window_backward", qkv, None, heads, head_dim)
+    _attn_same_out("attention_alibi_window_backward", view, out, dout)
+    dabi, dqkv = _attn_grads(view)
     nbytes = int(lib.agx_attention_window_backward_workspace_bytes(b, heads, t))
     ws = _workspace(nbytes, qkv.device, "agx_attention_window_backward_workspace_bytes")
-    _lib.check(lib.agx_attention_alibi_window_backward(_ptr(qkv), _off(qkv, hd * t), 3 * hd * t, 3 * hd * t, _ptr(_f32c(slopes)),
-                                                       _ptr(out), _ptr(dout), _ptr(dqkv), _off(dqkv, hd * t), 3 * hd * t, 3 * hd * t,
-                                                       _ptr(ws), nbytes, b, heads, head_dim, t, min(int(window), 0x7fffffff), float(scale_div),
-                                                       _stream()),
+    _lib.check(lib.agx_attention_alibi_window_backward(*abi, _ptr(_f32c(slopes)), _ptr(out), _ptr(dout), *dabi, _ptr(ws), nbytes,
+                                                       b, heads, head_dim, t, min(int(window), 0x7fffffff), float(scale_div), _stream()),
                "agx_attention_alibi_window_backward")
     return dqkv
 
@@ -1279,16 +1224,7 @@ def attention_alibi_stream(q: Tensor, kv: Tensor, pos: Tensor, slopes: Tensor, h
     of the window to the 64-key blocks can touch one block more or fewer."""
     lib = _lib.load()
     _need_gpu(q, kv, slopes)
-    q, kv = _f32c(q), _f32c(kv)
-    hd = heads * head_dim
-    b, cq, tq = q.shape
-    bk, ckv, cap = kv.shape
-    if cq not in (hd, 3 * hd):
-        raise AgxError(f"attention_alibi_stream: q has {cq} channels, expected {hd} (or a {3 * hd}-channel qkv tensor)")
-    if ckv != 2 * hd:
-        raise AgxError(f"attention_alibi_stream: kv has {ckv} channels, expected {2 * hd}")
-    if bk != b:
-        raise AgxError(f"attention_alibi_stream: q has batch {b}, kv has batch {bk}")
+    b, tq, cap, hd, q, kv, qp, kp, sq, skv = _attn_operands("attention_alibi_stream", q, kv, heads, head_dim, qkv_q=True, self_form=False)
     pos = _checked_pos("attention_alibi_stream", pos, b, q.device)
     if counts is not None:
         counts = _checked_counts("attention_alibi_stream", counts, b, q.device)
@@ -1300,13 +1236,12 @@ def attention_alibi_stream(q: Tensor, kv: Tensor, pos: Tensor, slopes: Tensor, h
         tok = _observer.begin("other", ("attention_alibi_stream:flash", nbytes + 4 * out.numel(),
                                         _window_macs(b, heads, head_dim, tq, window - 1, window)))
     if counts is not None:
-        _lib.check(lib.agx_attention_alibi_stream_counted(_ptr(q), _ptr(kv), cq * tq, 2 * hd * cap, cap, _ptr(pos), _ptr(counts),
-                                                          _ptr(_f32c(slopes)), _ptr(out), b, heads, head_dim, tq, window, int(ring),
-                                                          float(scale_div), _stream()), "agx_attention_alibi_stream_counted")
+        _lib.check(lib.agx_attention_alibi_stream_counted(qp, kp, sq, skv, cap, _ptr(pos), _ptr(counts), _ptr(_f32c(slopes)), _ptr(out), b, heads,
+                                                          head_dim, tq, window, int(ring), float(scale_div), _stream()),
+                   "agx_attention_alibi_stream_counted")
     else:
-        _lib.check(lib.agx_attention_alibi_stream(_ptr(q), _ptr(kv), cq * tq, 2 * hd * cap, cap, _ptr(pos), _ptr(_f32c(slopes)),
-                                                  _ptr(out), b, heads, head_dim, tq, window, int(ring), float(scale_div), _stream()),
-                   "agx_attention_alibi_stream")
+        _lib.check(lib.agx_attention_alibi_stream(qp, kp, sq, skv, cap, _ptr(pos), _ptr(_f32c(slopes)), _ptr(out), b, heads, head_dim, tq, window,
+                                                  int(ring), float(scale_div), _stream()), "agx_attention_alibi_stream")
     if tok is not None:
         _observer.end(tok)
     return out

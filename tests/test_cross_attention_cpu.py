@@ -99,15 +99,16 @@ def test_refusals_that_need_no_gpu(lib):
 
 
 def test_the_channel_count_check_of_the_wrappers():
-    """``ops._cross_shapes``: what ``attention_alibi_cross`` and ``attention_alibi_cross_backward`` call before anything else."""
+    """``ops._attn_operands``: what ``attention_alibi_cross`` and ``attention_alibi_cross_backward`` call before anything else;
+    its first three answers are (b, tq, tk)."""
     z = torch.zeros
-    assert ops._cross_shapes("op", z(2, 64, 4), z(2, 128, 5), 4, 16) == (2, 4, 5)
+    assert ops._attn_operands("op", z(2, 64, 4), z(2, 128, 5), 4, 16)[:3] == (2, 4, 5)
     with pytest.raises(AgxError, match=r"op: q has 60 channels, expected 64"):
-        ops._cross_shapes("op", z(1, 60, 4), z(1, 128, 5), 4, 16)
+        ops._attn_operands("op", z(1, 60, 4), z(1, 128, 5), 4, 16)
     with pytest.raises(AgxError, match=r"op: kv has 128 channels, expected 96"):
-        ops._cross_shapes("op", z(1, 48, 4), z(1, 128, 5), 3, 16)
+        ops._attn_operands("op", z(1, 48, 4), z(1, 128, 5), 3, 16)
     with pytest.raises(AgxError, match=r"op: q has batch 1, kv has batch 2"):
-        ops._cross_shapes("op", z(1, 64, 4), z(2, 128, 5), 4, 16)
+        ops._attn_operands("op", z(1, 64, 4), z(2, 128, 5), 4, 16)
 
 
 def test_the_checker_reproduces_the_reference(g9, meta):
