@@ -147,7 +147,7 @@ __global__ __launch_bounds__(256) void reduce_partial_kernel(const float *__rest
     const bool two = PAIR || mode == 3 || mode == 5;
     float acc[4] = {0.f, 0.f, 0.f, 0.f}, bcc[4] = {0.f, 0.f, 0.f, 0.f};
     const int64_t stride = int64_t(gridDim.x) * 256, first = int64_t(blockIdx.x) * 256 + threadIdx.x;
-    const int64_t n4 = vec ? n >> 2 : 0;
+    const int64_t n4 = n >> 2;
     // a workgroup sweeps 16 KB contiguous per operand and step, consecutive workgroups consecutive 16 KB (four loads of one
     // thread 4 MB apart -- the grid-stride form -- land in the same memory channel)
     auto term = [&](float a, float b, int u) {
@@ -155,21 +155,28 @@ __global__ __launch_bounds__(256) void reduce_partial_kernel(const float *__rest
         else acc[u] += loss_term(mode, a, b);
     };
     auto quad = [&](const float4 a, const float4 b, int u) { term(a.x, b.x, u); term(a.y, b.y, u); term(a.z, b.z, u); term(a.w, b.w, u); };
-    const float4 *x4 = reinterpret_cast<const float4 *>(x), *y4 = reinterpret_cast<const float4 *>(y);
     const float4 z4 = make_float4(0.f, 0.f, 0.f, 0.f);
     int64_t i = int64_t(blockIdx.x) * 1024 + threadIdx.x;
-    for (; i - threadIdx.x + 1024 <= n4; i += 4 * stride) {
-        float4 a[4], b[4];
+    // `ld(p, q)`: elements 4 q .. 4 q + 3 of p.  Which thread adds which element to which accumulator, and in which order, is
+    // the same whether an operand starts on a 16-byte boundary or not: the mean does not depend on where its operands start.
+    auto sweep = [&](auto ld) {
+        for (; i - threadIdx.x + 1024 <= n4; i += 4 * stride) {
+            float4 a[4], b[4];
 #pragma unroll
-        for (int u = 0; u < 4; ++u) a[u] = x4[i + u * 256];
+            for (int u = 0; u < 4; ++u) a[u] = ld(x, i + u * 256);
 #pragma unroll
-        for (int u = 0; u < 4; ++u) b[u] = two ? y4[i + u * 256] : z4;
+            for (int u = 0; u < 4; ++u) b[u] = two ? ld(y, i + u * 256) : z4;
 #pragma unroll
-        for (int u = 0; u < 4; ++u) quad(a[u], b[u], u);
-    }
+            for (int u = 0; u < 4; ++u) quad(a[u], b[u], u);
+        }
 #pragma unroll
-    for (int u = 0; u < 4; ++u)      // the workgroup that meets the end of the vector part: its last, partial 16 KB
-        if (i - threadIdx.x < n4 && i + u * 256 < n4) quad(x4[i + u * 256], two ? y4[i + u * 256] : z4, u);
+        for (int u = 0; u < 4; ++u)      // the workgroup that meets the end of the vector part: its last, partial 16 KB
+            if (i - threadIdx.x < n4 && i + u * 256 < n4) quad(ld(x, i + u * 256), two ? ld(y, i + u * 256) : z4, u);
+    };
+    if (vec)      // one 16-byte load
+        sweep([](const float *p, int64_t q) { return reinterpret_cast<const float4 *>(p)[q]; });
+    else          // an operand 4, 8 or 12 bytes off: the same four elements by 4-byte loads
+        sweep([](const float *p, int64_t q) { return make_float4(p[4 * q], p[4 * q + 1], p[4 * q + 2], p[4 * q + 3]); });
     for (int64_t e = 4 * n4 + first; e < n; e += stride) term(x[e], two ? y[e] : 0.f, 0);
     const float tot = block_sum_256((acc[0] + acc[1]) + (acc[2] + acc[3]), sh);
     if (threadIdx.x == 0) part[blockIdx.x] = tot;

@@ -100,6 +100,29 @@ def _f32c(t: Tensor) -> Tensor:
     return t if t.is_contiguous() else t.contiguous()
 
 
+def _checked_image(op: str, what: str, packed: Tensor, size: str, desc) -> None:
+    """``packed`` is the image ``size`` (``agx_conv_packed_floats`` / ``agx_conv_bwd_packed_floats``) describes for ``desc``:
+    float32, contiguous and exactly as long.  A kernel reads an image to its end wherever it is, so a short one is an
+    over-read that nothing downstream can see."""
+    need = getattr(_lib.load(), size)(ctypes.byref(desc))
+    if need < 0:
+        _lib.check(int(need), size)
+    if packed.dtype != torch.float32 or not packed.is_contiguous():
+        raise AgxError(f"{op}: {what} must be contiguous float32, got {packed.dtype}"
+                       + ("" if packed.is_contiguous() else ", not contiguous"))
+    if packed.numel() != need:
+        raise AgxError(f"{op}: {what} has {packed.numel()} floats, the layer's has {int(need)}")
+
+
+def _checked_bias(op: str, what: str, bias: Optional[Tensor], c_out: int) -> Optional[Tensor]:
+    if bias is None:
+        return None
+    bias = _f32c(bias)
+    if bias.numel() != c_out:
+        raise AgxError(f"{op}: {what} has {bias.numel()} entries for c_out={c_out}")
+    return bias
+
+
 def _workspace(nbytes: int, device, query: str) -> Tensor:
     """Exactly the bytes a ``*_workspace_bytes`` query of the library answered (a negative answer is its error code)."""
     nbytes = int(nbytes)
@@ -151,14 +174,19 @@ def conv_forward(desc: ConvDesc, x: Tensor, packed: Tensor, bias: Optional[Tenso
         raise AgxError(f"conv_forward: x is {tuple(x.shape)}, descriptor says "
                        f"{(desc.batch, desc.c_in, desc.l_in)}")
     l_out = conv_out_len(desc)
+    _checked_image("conv_forward", "the packed image", packed, "agx_conv_packed_floats", desc)
+    if out is not None and (tuple(out.shape) != (desc.batch, desc.c_out, l_out) or out.dtype != torch.float32
+                            or out.device != x.device or not out.is_contiguous()):
+        raise AgxError(f"conv_forward: out is {tuple(out.shape)} {out.dtype} on '{out.device}'"
+                       f"{'' if out.is_contiguous() else ', not contiguous'}; the layer writes contiguous float32 "
+                       f"{(desc.batch, desc.c_out, l_out)} on '{x.device}'")
     y = out if out is not None else torch.empty((desc.batch, desc.c_out, l_out), dtype=torch.float32,
                                                  device=x.device)
     if res is not None:
         res = _f32c(res)
         if res.shape != y.shape:
             raise AgxError(f"conv_forward: residual is {tuple(res.shape)}, output is {tuple(y.shape)}")
-    if bias is not None:
-        bias = _f32c(bias)
+    bias = _checked_bias("conv_forward", "bias", bias, desc.c_out)
     tok = _observer.begin("conv", desc) if _observer is not None else None
     _lib.check(lib.agx_conv_forward(ctypes.byref(desc), _ptr(x), _ptr(packed), _ptr(bias), _ptr(res),
                                     _ptr(y), _stream()), "agx_conv_forward")
@@ -207,7 +235,8 @@ def conv_forward_planes(desc: ConvDesc, x_planes: Tensor, packed: Tensor, bias: 
         raise AgxError(f"conv_forward_planes: planes are {tuple(x_planes.shape)} {x_planes.dtype}, descriptor says "
                        f"{(desc.batch, desc.c_in // 8, 3, desc.l_in, 8)} bfloat16")
     l_out = conv_out_len(desc)
-    bias = None if bias is None else _f32c(bias)
+    _checked_image("conv_forward_planes", "the packed image", packed, "agx_conv_packed_floats", desc)
+    bias = _checked_bias("conv_forward_planes", "bias", bias, desc.c_out)
     if out_planes:
         y = torch.empty((desc.batch, desc.c_out // 8, 3, l_out, 8), dtype=torch.bfloat16, device=x_planes.device)
     else:
@@ -235,6 +264,7 @@ def conv_bwd_data(desc: ConvDesc, dy: Tensor, packed_bwd: Tensor, add: Optional[
     l_out = conv_out_len(desc)
     if tuple(dy.shape) != (desc.batch, desc.c_out, l_out):
         raise AgxError(f"conv_bwd_data: dy is {tuple(dy.shape)}, expected {(desc.batch, desc.c_out, l_out)}")
+    _checked_image("conv_bwd_data", "the packed image", packed_bwd, "agx_conv_bwd_packed_floats", desc)
     dx = torch.empty((desc.batch, desc.c_in, desc.l_in), dtype=torch.float32, device=dy.device)
     for t, nm in ((add, "add"), (mask, "mask")):
         if t is not None and tuple(t.shape) != tuple(dx.shape):
@@ -253,6 +283,12 @@ def conv_bwd_weight(desc: ConvDesc, x: Tensor, dy: Tensor, v: Tensor, g: Optiona
     _need_gpu(x, dy, v, g)
     x, dy, v = _f32c(x), _f32c(dy), _f32c(v)
     g = None if g is None else _f32c(g)
+    k, groups = desc.kernel, max(1, desc.groups)
+    want_v = (desc.c_in, desc.c_out, k) if desc.kind == _lib.CONV_TRANSPOSED else (desc.c_out, desc.c_in // groups, k)
+    for t, nm, want in ((x, "x", (desc.batch, desc.c_in, desc.l_in)), (dy, "dy", (desc.batch, desc.c_out, conv_out_len(desc))),
+                        (v, "v", want_v)):
+        if tuple(t.shape) != want:
+            raise AgxError(f"conv_bwd_weight: {nm} is {tuple(t.shape)}, descriptor says {want}")
     dv = torch.empty_like(v)
     dg = None if g is None else torch.empty_like(g)
     db = torch.empty(desc.c_out, dtype=torch.float32, device=x.device) if want_bias else None
@@ -269,6 +305,16 @@ def conv_bwd_weight_kernel_name(desc: ConvDesc) -> str:
     return _kernel_name("agx_conv_bwd_weight_kernel_name", desc, size=128)
 
 
+def _checked_block(op: str, desc: ConvDesc, packed1: Tensor, bias1, packed2: Tensor, bias2):
+    """The images and biases of a fused residual block: ``packed1`` is the image of ``desc`` (the dilated k = 7 conv),
+    ``packed2`` that of the block's k = 1 conv in the same arithmetic.  Returns the two biases."""
+    c = desc.c_in
+    _checked_image(op, "packed1", packed1, "agx_conv_packed_floats", desc)
+    _checked_image(op, "packed2", packed2, "agx_conv_packed_floats",
+                   conv_desc(CONV_CAUSAL, desc.batch, c, c, desc.l_in, 1, 1, 1, impl=desc.impl))
+    return _checked_bias(op, "bias1", bias1, c), _checked_bias(op, "bias2", bias2, c)
+
+
 def resblock_forward(desc: ConvDesc, x: Tensor, packed1: Tensor, bias1: Optional[Tensor],
                      packed2: Tensor, bias2: Optional[Tensor], post_act: bool = True) -> Tensor:
     lib = _lib.load()
@@ -277,6 +323,7 @@ def resblock_forward(desc: ConvDesc, x: Tensor, packed1: Tensor, bias1: Optional
     if tuple(x.shape) != (desc.batch, desc.c_in, desc.l_in):
         raise AgxError(f"resblock_forward: x is {tuple(x.shape)}, descriptor says "
                        f"{(desc.batch, desc.c_in, desc.l_in)}")
+    bias1, bias2 = _checked_block("resblock_forward", desc, packed1, bias1, packed2, bias2)
     y = torch.empty_like(x)
     ws_bytes = int(lib.agx_resblock_workspace_bytes(ctypes.byref(desc)))
     ws = _workspace(ws_bytes, x.device, "agx_resblock_workspace_bytes")
@@ -304,6 +351,7 @@ def resblock_forward_q4(desc: ConvDesc, x: Tensor, packed1: Tensor, bias1: Optio
     b, c, length = desc.batch, desc.c_in, desc.l_in
     if tuple(x.shape) != ((b, c // 4, length, 4) if x_is_q4 else (b, c, length)):
         raise AgxError(f"resblock_forward_q4: x is {tuple(x.shape)}, descriptor says {(b, c, length)}, x_is_q4={bool(x_is_q4)}")
+    bias1, bias2 = _checked_block("resblock_forward_q4", desc, packed1, bias1, packed2, bias2)
     y = torch.empty((b, c // 4, length, 4) if y_is_q4 else (b, c, length), dtype=torch.float32, device=x.device)
     ws_bytes = int(lib.agx_resblock_workspace_bytes(ctypes.byref(desc)))
     ws = _workspace(ws_bytes, x.device, "agx_resblock_workspace_bytes")

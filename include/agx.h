@@ -15,6 +15,31 @@
  *     last error of the calling thread is returned by agx_last_error();
  *   - tensors are contiguous fp32, "NCL" (batch, channel, time) unless said
  *     otherwise; indices are int64 to match torch.argmin.
+ *
+ * Pointer alignment, family by family (tests/test_gpu_memory_contract.py::test_operand_placement runs each
+ * with its operands 4, 8 and 12 bytes past a 16-byte boundary and requires the bits of the aligned run):
+ *   - convolutions, forward (agx_conv_forward, agx_conv_forward_planes, agx_conv_pack*, agx_planes_split): operands
+ *     need 4-byte alignment only (bf16 planes: 4-byte as well); the result does not depend on it;
+ *   - fused residual block (agx_resblock_forward, agx_resblock_forward_q4): operands need 4-byte alignment only; the
+ *     result does not depend on it;
+ *   - convolutions, backward (agx_conv_bwd_data*, agx_conv_bwd_weight, agx_conv_grouped_bwd_*): operands need 4-byte
+ *     alignment only; the result does not depend on it;
+ *   - Conv2d (agx_conv2d_*): operands need 4-byte alignment only; the result does not depend on it;
+ *   - RVQ (agx_rvq_forward*, agx_rvq_ema_stats, agx_rvq_dequantize): fp32 operands need 4-byte alignment only, int64
+ *     indices and the float64 workspace 8-byte; the result does not depend on it;
+ *   - LayerNorm and ALiBi attention (agx_layernorm_ct*, agx_attention_alibi*): operands need 4-byte alignment only;
+ *     the result does not depend on it;
+ *   - wavelet fold, multires and group sum (agx_wavelet_fold*, agx_multires_*, agx_group_sum): operands need 4-byte
+ *     alignment only; the result does not depend on it;
+ *   - discriminator ops (agx_spectral_*, agx_reduce_mean*, agx_feature_means*, agx_avgpool1d*, agx_sigmoid*):
+ *     operands need 4-byte alignment only; the result does not depend on it (the loss reductions use 16-byte loads
+ *     when every pointer allows and 4-byte loads of the same elements in the same order otherwise);
+ *   - spectral and signal ops (agx_stft*, agx_fdft_*, agx_preemphasis, agx_lowpass_biquad, agx_resample): operands need 4-byte
+ *     alignment only; the result does not depend on it;
+ *   - bitstream and time folding (agx_codes_*, agx_time_fold, agx_time_unfold): int64 codes need 8-byte alignment,
+ *     fp32 tensors 4-byte, the packed stream none; the result does not depend on it.
+ * This is about operands (inputs, parameters, outputs, in/out buffers).  A workspace is 16-byte aligned, as every
+ * device allocation is (8-byte where a declaration says so).  No entry point refuses a pointer for its alignment.
  */
 #ifndef AGX_H
 #define AGX_H

@@ -9,7 +9,12 @@ patterns 0x00, 0x00, 0xFF, 0x7F and must
 4. run the kernel the case is there for (the family's name query).
 
 This is not a second parity suite: one or two of the smallest shapes at which the edge exists per kernel name.  The reference
-of a case is computed once (CPU, float64 or the oracle) and shared by its four runs.
+of a case is computed once (CPU, float64 or the oracle) and shared by its runs.
+
+``test_operand_placement`` runs the same table with the caller's operands 4, 8 and 12 bytes past a 16-byte boundary (a crop
+``wave[s:s + L]``, a batch slice, a parameter carved out of a flat buffer; what the wrapper allocates itself stays aligned)
+and requires, besides (1) and (2), the bits of the aligned run: include/agx.h promises that operands need 4-byte alignment
+only and that the result does not depend on it.
 """
 import ctypes
 
@@ -25,7 +30,7 @@ from oracle import bitstream, codec, rvq
 from oracle import discriminator as od
 from oracle import signal as osg
 from oracle import wavelets as owv
-from tests.guarded import Out, routed, run_contract
+from tests.guarded import PLACEMENT_RUNS, Out, routed, run_contract
 from tests.test_gpu_attention_flash import BF16_MAX_REL, _core
 from tests.test_gpu_attention_variants import CASES as ATTENTION_ROWS
 from tests.test_gpu_conv_p import LAYERS, _ref_epilogue
@@ -37,6 +42,10 @@ CASES = {}
 # case name -> the buffers known not to be bitwise reproducible run to run (invariance falls back to the reference check for
 # them).  No float atomics exist in csrc/: empty, and an op that turns up here is a finding to write down.
 NOT_REPRODUCIBLE = {}
+# case name -> the buffers whose bits may legitimately depend on where an operand starts, each with the kernel line that makes
+# its summation order depend on the address.  Empty: every wide access is base + 4 * index and every reduction runs in index
+# order ("Operand placement").
+PLACEMENT_DEPENDENT = {}
 
 
 def _set(knob, v):
@@ -957,6 +966,39 @@ def test_memory_contract(name):
     report = run_contract(one_run, DEV)
     assert set(report["irreproducible"]) == set(NOT_REPRODUCIBLE.get(name, ())), \
         f"{name}: buffers that differ between two runs on clean memory (largest difference): {report['irreproducible']}"
+
+
+def _assert_placed_as_asked(name, arena):
+    """A case cannot pass by not being skewed: every placement of a run sits where the run's schedule puts it."""
+    placed = [a for a in arena.allocs if a.what == "place"]
+    assert placed, f"{name}: the case places no operand"
+    for i, a in enumerate(placed):
+        asked = arena.skews[i % len(arena.skews)]
+        # float32, bfloat16 and uint8 get the run's skew as it is; the only placements that may stay behind it are the 8-byte
+        # types (int64, float64), which cannot start 4 bytes off their item size
+        want = asked // 8 * 8 if a.dtype in (torch.int64, torch.float64) else asked
+        assert a.asked == asked and a.skew == want, f"{name}: {a.describe()} was asked {a.asked} and got {a.skew}, the run says {asked}"
+    return any(a.skew for a in placed)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("name", list(CASES))
+def test_operand_placement(name):
+    one_run, names, _ = CASES[name]
+    if names is not None:
+        names()
+    skewed = []
+
+    def watched(arena):
+        outs = one_run(arena)
+        if any(arena.skews):
+            skewed.append(_assert_placed_as_asked(name, arena))
+        return outs
+    report = run_contract(watched, DEV, PLACEMENT_RUNS, irreproducible=tuple(PLACEMENT_DEPENDENT.get(name, ())))
+    assert len(skewed) == len(PLACEMENT_RUNS) - 1 and any(skewed), f"{name}: no operand was ever off alignment"
+    # only a case whose every operand is an 8-byte type has a run (skew 4) in which nothing moves
+    assert all(skewed) or name.split("/")[0] in ("codes",), f"{name}: runs without a skewed operand: {skewed}"
+    assert set(report["irreproducible"]) <= set(PLACEMENT_DEPENDENT.get(name, ()))
 
 
 def test_the_table_covers_every_family():
