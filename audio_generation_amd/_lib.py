@@ -310,6 +310,19 @@ SIGNATURES = {
     "agx_rvq_step_decode": (c_int, [c_void_p, c_int32, c_void_p, c_void_p, c_void_p,
                                     c_int32, c_int32, c_int32, c_int32, c_int32, c_int32,
                                     c_void_p, c_int64, c_int64, c_int64, c_void_p, c_void_p]),
+    # streaming wavelet blocks
+    "agx_wavelet_fold_table": (c_int, [c_void_p, c_void_p, c_int32, c_void_p, c_int32, c_int32, c_int32, c_void_p]),
+    "agx_wavelet_stream_in_step": (c_int, [c_int32, c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_int32, c_void_p, c_int32, c_void_p,
+                                           c_void_p, c_int32, c_int32, c_int32, c_int64, c_void_p]),
+    "agx_wavelet_stream_in_step_counted": (c_int, [c_int32, c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_int32, c_void_p, c_int32,
+                                                   c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int64, c_void_p]),
+    "agx_wavelet_stream_out_step": (c_int, [c_int32, c_int32, c_int32, c_int32, c_int32, c_float, c_void_p, c_void_p, c_void_p, c_void_p,
+                                            c_int32, c_void_p, c_int32, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int64, c_void_p]),
+    "agx_wavelet_stream_out_step_counted": (c_int, [c_int32, c_int32, c_int32, c_int32, c_int32, c_float, c_void_p, c_void_p, c_void_p,
+                                                    c_void_p, c_int32, c_void_p, c_int32, c_void_p, c_void_p, c_void_p, c_int32, c_int32,
+                                                    c_int32, c_int64, c_void_p]),
+    "agx_wavelet_stream_in_kernel_name": (c_int, [c_int32, c_int32, c_int32, c_int32, c_int32, c_char_p, c_size_t]),
+    "agx_wavelet_stream_out_kernel_name": (c_int, [c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, c_char_p, c_size_t]),
 }
 
 _lib = None

@@ -1,170 +1,9 @@
 // Streaming step of the codec's conv stacks: one chunk of n latent frames through one layer whose state is a ring of its own
-// INPUT (include/agx.h "Streaming conv stacks").  Every layer kind is the polyphase form of core.hip: lower_conv on the standard
-// packed image of agx_conv_pack,
-//     y[co, q t + ph] = epilogue(bias[co] + sum_{g, j, c} Wp[(g J + j) M + co q + ph][c] * x[16 g + c, t s + j d - P]),
-// with t running over the n * rt base positions of the step, t0 = pos[b] * rt - Dt, and x read from the ring at (index mod cap).
-//
-// One chain per output, whatever the schedule.  A lane owns one row m = co q + ph and NT base positions; the KS waves of a
-// workgroup own KS fixed contiguous ranges of the (g, j) reduction, each an fmaf chain from 0 in (g, j, c) order, and wave 0 adds
-// the KS partial sums in ascending order, then the bias.  KS is a function of the layer alone (stream_split); NT (how many columns
-// a lane carries) and the grid only decide which thread runs a chain, never what the chain is.  A wave streams its 64 rows of the
-// image (4 KiB contiguous per (g, j)) against operands it loads once and broadcasts across its lanes: at the bottleneck, where a
-// chunk is a handful of columns against megabytes of weights, the image stream is what bounds the step.
-#include "common.hpp"
+// INPUT (include/agx.h "Streaming conv stacks").  The step kernel and its launch tables are in conv_stream.hpp, which the steps of
+// the wavelet decoder block (wavelet_stream.hip) share; here: the kernel choice, the conv entry points and the ring plumbing.
+#include "conv_stream.hpp"
 
 namespace agx {
-
-struct StreamArgs {
-    const float *W, *bias, *src, *res;
-    float *dst;
-    const int64_t *pos, *end;
-    const int64_t *counts;   // counted form: row b takes its first clamp(counts[b], 0, n) frames
-    int n;                   // frames of the step
-    int Cin, Cout, M, q, J, s, d, P;
-    int nt;            // base positions of the step (n * rt)
-    int rt;            // base positions per frame
-    int64_t Dt;        // delay in base positions
-    int n_in;          // input columns of the step (n * rate_in): the extent of a plain source
-    int64_t first_off; // first new input column minus t0 * s (0, or 1 for the upsampling kind)
-    int src_cap, res_cap, dst_cap;   // 0 = plain tensor
-    int rate_out;
-    int epilogue;
-    float slope;
-};
-
-__device__ __forceinline__ int floor_mod(int64_t a, int cap) {
-    const int64_t r = a % cap;
-    return int(r < 0 ? r + cap : r);
-}
-
-// CNT, the counted form (include/agx.h "Per-row frame counts"): row b takes lim = clamp(counts[b], 0, n) rt of the step's base
-// positions.  The count only decides which outputs are stored -- a plain destination gets exact 0 past lim, a ring destination is
-// left alone -- never what a chain is: KS, NT and the grid are those of the uncounted step.  The uncounted instances compile it out.
-template <int KS, int NT, bool CNT>
-__global__ __launch_bounds__(64 * KS) void conv_stream_kernel(const StreamArgs a) {
-    __shared__ float red[KS > 1 ? KS * NT * 64 : 1];
-    const int lane = threadIdx.x & 63;
-    const int ks = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const int b = blockIdx.z;
-    const int m = blockIdx.x * 64 + lane;
-    const int tb = blockIdx.y * NT;
-    const int64_t t0 = a.pos[b] * a.rt - a.Dt;           // workgroup-uniform
-    const int mr = m < a.M ? m : a.M - 1;               // lanes past the last row repeat it and store nothing
-    int lim = a.nt;                                      // workgroup-uniform: the base positions row b takes
-    if (CNT) {
-        const int64_t c = a.counts[b];
-        lim = int(c < 0 ? 0 : c > a.n ? a.n : c) * a.rt;
-        if (tb >= lim) {      // nothing of this tile is taken: the whole workgroup leaves here, before the KS > 1 barrier
-            if (!a.dst_cap && ks == 0 && m < a.M) {
-                const int co = m / a.q, ph = m - co * a.q;
-                for (int i = 0; i < NT && tb + i < a.nt; ++i)
-                    a.dst[(size_t(b) * a.Cout + co) * (size_t(a.nt) * a.q) + (tb + i) * a.q + ph] = 0.f;
-            }
-            return;
-        }
-    }
-
-    // The NV = 16 NT activation values of one (g, j) -- 16 channels x NT columns -- are loaded once per wave, value v = c NT + i by
-    // lane (v mod 64) into register (v / 64), and broadcast to the fmaf chain by v_readlane: 6 memory instructions per (g, j)
-    // instead of one per multiply.  A lane therefore tracks ONE column, i = lane mod NT, and 1 or 2 channels.
-    constexpr int NV = kWG * NT, NR = (NV + 63) / 64, CSTEP = 64 / NT;
-    const int my_i = lane % NT, my_c = lane / NT;
-    const int64_t my_idx = (t0 + tb + my_i) * a.s - a.P;
-    // ring column (or plain offset) of tap 0 of the lane's column; taps add j d < cap
-    const int col0 = a.src_cap ? floor_mod(my_idx, a.src_cap) : int(my_idx - (t0 * a.s + a.first_off));
-    const int xpitch = a.src_cap ? a.src_cap : a.n_in;
-    const float *__restrict__ xb = a.src + size_t(b) * a.Cin * xpitch;
-    const float *__restrict__ W = a.W;
-
-    float acc[NT];
-#pragma unroll
-    for (int i = 0; i < NT; ++i) acc[i] = 0.f;
-
-    const int G = (a.Cin + kWG - 1) / kWG;
-    const int GJ = G * a.J;
-    const int chunk = (GJ + KS - 1) / KS;
-    const int gj_end = min(GJ, (ks + 1) * chunk);
-    // operands of one (g, j): the lane's 16 weights and its 1 or 2 activation values
-    auto fetch = [&](int gj, float4 (&wq)[4], int (&xr)[NR]) {
-        const int g = gj / a.J, j = gj - g * a.J;
-        const float4 *wp = reinterpret_cast<const float4 *>(W + (size_t(gj) * a.M + mr) * kWG);
-#pragma unroll
-        for (int k = 0; k < 4; ++k) wq[k] = wp[k];
-        int col = col0 + j * a.d;
-        bool ok = true;
-        if (a.src_cap) {
-            col = col >= a.src_cap ? col - a.src_cap : col;
-        } else {
-            ok = col >= 0 && col < a.n_in;       // a plain source holds the step's own columns only
-        }
-#pragma unroll
-        for (int r = 0; r < NR; ++r) {
-            const int ch = g * kWG + my_c + r * CSTEP;            // channels past Cin meet the image's zero padding
-            const bool have = ok && lane + 64 * r < NV && ch < a.Cin;
-            xr[r] = have ? __float_as_int(xb[size_t(ch) * xpitch + col]) : 0;
-        }
-    };
-    // the loads of (g, j) + 1 are in flight while the chain takes (g, j): the waves of a small step are few and latency-bound
-    float4 wn[4];
-    int xn[NR];
-    int gj = ks * chunk;
-    if (gj < gj_end) fetch(gj, wn, xn);
-    for (; gj < gj_end; ++gj) {
-        float4 wq[4];
-        int xr[NR];
-#pragma unroll
-        for (int k = 0; k < 4; ++k) wq[k] = wn[k];
-#pragma unroll
-        for (int r = 0; r < NR; ++r) xr[r] = xn[r];
-        if (gj + 1 < gj_end) fetch(gj + 1, wn, xn);
-        const float w[kWG] = {wq[0].x, wq[0].y, wq[0].z, wq[0].w, wq[1].x, wq[1].y, wq[1].z, wq[1].w,
-                              wq[2].x, wq[2].y, wq[2].z, wq[2].w, wq[3].x, wq[3].y, wq[3].z, wq[3].w};
-#pragma unroll
-        for (int c = 0; c < kWG; ++c)
-#pragma unroll
-            for (int i = 0; i < NT; ++i) {
-                const int v = c * NT + i;
-                acc[i] = fmaf(w[c], __int_as_float(__builtin_amdgcn_readlane(xr[v >> 6], v & 63)), acc[i]);
-            }
-    }
-
-    if (KS > 1) {
-#pragma unroll
-        for (int i = 0; i < NT; ++i) red[(ks * NT + i) * 64 + lane] = acc[i];
-        __syncthreads();
-        if (ks != 0) return;
-#pragma unroll
-        for (int i = 0; i < NT; ++i) {
-            float v = red[i * 64 + lane];
-            for (int k = 1; k < KS; ++k) v += red[(k * NT + i) * 64 + lane];
-            acc[i] = v;
-        }
-    }
-    if (m >= a.M) return;
-
-    const int co = m / a.q, ph = m - co * a.q;
-    const float bias = a.bias ? a.bias[co] : 0.f;
-    const int64_t end = a.end ? a.end[b] : 0;
-    const int n_out = a.nt * a.q;
-#pragma unroll
-    for (int i = 0; i < NT; ++i) {
-        if (tb + i >= a.nt) break;
-        if (CNT && tb + i >= lim) {                      // past the row's count: zero to a plain tensor, a ring is not written
-            if (!a.dst_cap) a.dst[(size_t(b) * a.Cout + co) * n_out + (tb + i) * a.q + ph] = 0.f;
-            continue;
-        }
-        const int64_t jo = (t0 + tb + i) * a.q + ph;     // the output's stream index
-        float v = acc[i] + bias;
-        if (a.epilogue & AGX_EPI_LEAKY_PRE) v = v > 0.f ? v : v * a.slope;
-        if (a.epilogue & AGX_EPI_RESIDUAL) v += a.res[(size_t(b) * a.Cout + co) * a.res_cap + floor_mod(jo, a.res_cap)];
-        if (a.epilogue & AGX_EPI_LEAKY_POST) v = v > 0.f ? v : v * a.slope;
-        if (a.end && !(jo >= 0 && jo / a.rate_out < end)) v = 0.f;
-        if (a.dst_cap)
-            a.dst[(size_t(b) * a.Cout + co) * a.dst_cap + floor_mod(jo, a.dst_cap)] = v;
-        else
-            a.dst[(size_t(b) * a.Cout + co) * n_out + (tb + i) * a.q + ph] = v;
-    }
-}
 
 // buf[b, c, (pos[b] * rate + t) mod cap] = src[b, c, t], t < n_cols: a stack's input chunk into its first ring.  CNT: only the
 // columns of the row's first clamp(counts[b], 0, n_cols / rate) frames; the others are neither read nor written.
@@ -193,13 +32,6 @@ __global__ __launch_bounds__(256) void stream_mark_end_kernel(const int64_t *__r
 }
 
 // ------------------------------------------------------------------ host side
-struct StreamPick {
-    int code;       // AGX_OK or the refusal
-    bool empty;
-    int ks, nt_tile;
-    StreamArgs a;
-};
-
 // The split of the (g, j) reduction over the waves of a workgroup: a function of the layer alone.
 static int stream_split(int c_in, int J) {
     const int gj = ceil_div(c_in, kWG) * J;
@@ -208,8 +40,8 @@ static int stream_split(int c_in, int J) {
     return ks;
 }
 
-static StreamPick stream_pick(const char *op, int kind, int c_in, int c_out, int kernel, int stride, int dilation, int batch, int n,
-                              int rate_in, int64_t delay_in) {
+StreamPick stream_pick(const char *op, int kind, int c_in, int c_out, int kernel, int stride, int dilation, int batch, int n,
+                       int rate_in, int64_t delay_in, bool same_ok) {
     StreamPick k{};
     if (batch <= 0 || n <= 0) {
         k.empty = true;
@@ -256,6 +88,17 @@ static StreamPick stream_pick(const char *op, int kind, int c_in, int c_out, int
             }
             a.rt = rate_in, a.Dt = delay_in + 1, a.first_off = 1;   // output t reads t - 1 .. t + 1: one base position behind
             break;
+        case AGX_CONV_SAME:
+            if (same_ok) {      // the wavelet block's steps only: output t reads t - P .. t + P, P base positions behind
+                if (kernel % 2 == 0 || dilation != 1) {
+                    k.code = fail(AGX_ERR_UNSUPPORTED, "%s: a \"same\" conv streams with an odd kernel and dilation 1 (K=%d d=%d)", op,
+                                  kernel, dilation);
+                    return k;
+                }
+                a.rt = rate_in, a.Dt = delay_in + p.P, a.first_off = p.P;
+                break;
+            }
+            [[fallthrough]];
         default:
             k.code = fail(AGX_ERR_UNSUPPORTED, "%s: conv kind %d has no streaming step", op, kind);
             return k;
@@ -272,32 +115,12 @@ static StreamPick stream_pick(const char *op, int kind, int c_in, int c_out, int
     return k;
 }
 
-template <int KS, bool CNT>
-static void stream_launch_nt(const StreamPick &k, dim3 grid, hipStream_t st) {
-    switch (k.nt_tile) {
-        case 1: hipLaunchKernelGGL((conv_stream_kernel<KS, 1, CNT>), grid, dim3(64 * KS), 0, st, k.a); break;
-        case 4: hipLaunchKernelGGL((conv_stream_kernel<KS, 4, CNT>), grid, dim3(64 * KS), 0, st, k.a); break;
-        default: hipLaunchKernelGGL((conv_stream_kernel<KS, 8, CNT>), grid, dim3(64 * KS), 0, st, k.a); break;
-    }
-}
-
-template <bool CNT>
-static void stream_launch(const StreamPick &k, dim3 grid, hipStream_t st) {
-    switch (k.ks) {
-        case 1: stream_launch_nt<1, CNT>(k, grid, st); break;
-        case 2: stream_launch_nt<2, CNT>(k, grid, st); break;
-        case 4: stream_launch_nt<4, CNT>(k, grid, st); break;
-        case 8: stream_launch_nt<8, CNT>(k, grid, st); break;
-        default: stream_launch_nt<16, CNT>(k, grid, st); break;
-    }
-}
-
 // The one launcher of both entry points: counts == nullptr is the uncounted step, the instances without the count.
-static int stream_step(const char *op, int32_t kind, int32_t c_in, int32_t c_out, int32_t kernel, int32_t stride, int32_t dilation,
-                       int32_t epilogue, float slope, const float *packed, const float *bias, const float *src, int32_t src_cap,
-                       const float *res, int32_t res_cap, float *dst, int32_t dst_cap, const int64_t *pos, const int64_t *end,
-                       const int64_t *counts, int32_t batch, int32_t n, int32_t rate_in, int64_t delay_in, void *stream) {
-    StreamPick k = stream_pick(op, kind, c_in, c_out, kernel, stride, dilation, batch, n, rate_in, delay_in);
+int stream_step(const char *op, int32_t kind, int32_t c_in, int32_t c_out, int32_t kernel, int32_t stride, int32_t dilation,
+                int32_t epilogue, float slope, const float *packed, const float *bias, const float *src, int32_t src_cap,
+                const float *res, int32_t res_cap, float *dst, int32_t dst_cap, const int64_t *pos, const int64_t *end,
+                const int64_t *counts, int32_t batch, int32_t n, int32_t rate_in, int64_t delay_in, void *stream, bool same_ok) {
+    StreamPick k = stream_pick(op, kind, c_in, c_out, kernel, stride, dilation, batch, n, rate_in, delay_in, same_ok);
     if (k.code) return k.code;
     if (k.empty) return AGX_OK;
     StreamArgs &a = k.a;
@@ -326,9 +149,9 @@ static int stream_step(const char *op, int32_t kind, int32_t c_in, int32_t c_out
     const dim3 grid(ceil_div(a.M, 64), ceil_div(a.nt, k.nt_tile), batch);
     hipStream_t st = static_cast<hipStream_t>(stream);
     if (counts)
-        stream_launch<true>(k, grid, st);
+        stream_launch<true, false>(k, grid, st);
     else
-        stream_launch<false>(k, grid, st);
+        stream_launch<false, false>(k, grid, st);
     return check_launch(op);
 }
 

@@ -2,6 +2,7 @@
 // Both are per-channel (depthwise) and pure bandwidth: one read of the input,
 // one write of the output, everything else stays in LDS / registers.
 #include "mfma_tile.hpp"
+#include "wavelet_fold.hpp"
 
 namespace agx {
 
@@ -278,21 +279,7 @@ __global__ __launch_bounds__(256) void wavelet_fold_kernel(const float *__restri
     const int n_bx = min((L * scale + 255) / 256, 64);     // 1-D grid: block = (row, stripe)
     const unsigned brow = blockIdx.x / n_bx, bstripe = blockIdx.x - brow * n_bx;
     const int c = brow % C;
-    const float sg = sigma[sigma_len == 1 ? 0 : c];
-    if (tid < P) {
-        const float t = space[tid];
-        kern[tid] = cosf(t) * expf(-(t * t) / sg);
-    }
-    __syncthreads();
-    const int fold = P / scale;
-    if (tid < scale) {
-        float lo = 0.f, hi = 0.f;
-        for (int p = 0; p < tid * fold; ++p) lo += kern[p];
-        for (int p = tid * fold; p < P; ++p) hi += kern[p];
-        s_lo[tid] = lo;
-        s_hi[tid] = hi;
-    }
-    __syncthreads();
+    wavelet_phase_sums(space, sigma[sigma_len == 1 ? 0 : c], P, scale, kern, s_lo, s_hi);
     const size_t in_row = size_t(brow) * L;
     const size_t out_row = in_row * scale;
     const int n_out = L * scale;

@@ -2403,3 +2403,150 @@ def stream_mark_end(pos: Tensor, end: Tensor, rows: Optional[Tensor] = None) -> 
         rows = _checked_pos("stream_mark_end", rows, rows.numel() if isinstance(rows, Tensor) else 0, pos.device)
     _lib.check(lib.agx_stream_mark_end(_ptr(pos), _ptr(end), _ptr(rows), 0 if rows is None else rows.numel(), pos.numel(), _stream()),
                "agx_stream_mark_end")
+
+
+# ------------------------------------------------------------------ streaming wavelet blocks (include/agx.h "Streaming wavelet blocks")
+def wavelet_fold_table(space: Tensor, sigma: Tensor, channels: int, scale: int) -> Tensor:
+    """The per-channel table the wavelet out-step reads (``agx_wavelet_fold_table``): (channels, 3 scale - 1) fp32 =
+    [S_hi[0 .. s) | S_lo[0 .. s) | the s - 1 tail taps], formed by the code of ``wavelet_fold``.  ``sigma``: 1 or ``channels``
+    entries.  One small launch."""
+    channels, scale = int(channels), int(scale)
+    p = space.numel()
+    if scale < 2 or p % scale:
+        raise AgxError(f"wavelet_fold_table: scale = {scale} must be >= 2 and divide n_points = {p}")
+    if sigma.numel() not in (1, channels):
+        raise AgxError(f"wavelet_fold_table: sigma has {sigma.numel()} entries for {channels} channels (1 or {channels})")
+    lib = _lib.load()
+    _need_gpu(space, sigma)
+    space, sigma = _f32c(space.reshape(-1)), _f32c(sigma.reshape(-1))
+    table = torch.empty((channels, 3 * scale - 1), dtype=torch.float32, device=space.device)
+    _lib.check(lib.agx_wavelet_fold_table(_ptr(space), _ptr(sigma), sigma.numel(), _ptr(table), channels, p, scale, _stream()),
+               "agx_wavelet_fold_table")
+    return table
+
+
+def wavelet_stream_in_kernel_name(c_in: int, hidden: int, kernel: int, n: int, rate_in: int) -> str:
+    """The kernel ``wavelet_stream_in_step`` runs for this layer and step (host-only); ``AgxError`` with the launcher's refusal."""
+    return _kernel_name("agx_wavelet_stream_in_kernel_name", c_in, hidden, kernel, n, rate_in)
+
+
+def wavelet_stream_out_kernel_name(hidden: int, c_out: int, kernel: int, scale: int, n: int, rate_h: int) -> str:
+    """The kernel ``wavelet_stream_out_step`` runs for this layer and step (host-only); ``AgxError`` with the launcher's refusal."""
+    return _kernel_name("agx_wavelet_stream_out_kernel_name", hidden, c_out, kernel, scale, n, rate_h)
+
+
+def _wavelet_step_operands(op: str, kind_desc, packed: Tensor, bias: Optional[Tensor], src: Tensor, dst: Tensor, pos, end, counts,
+                           c_in: int, c_out: int, n: int, src_need: int, dst_cols: int, dst_ring: bool, src_name: str):
+    """The checks the two wavelet steps share, in ``conv_stream_step``'s words; shapes first, so that every refusal precedes the
+    first use of the device.  Returns (b, packed, bias, pos, end, counts)."""
+    if n < 1:
+        raise AgxError(f"{op}: a step takes n >= 1 frames, got {n}")
+    for name, t in ((src_name, src), ("dst", dst)):
+        if not isinstance(t, Tensor) or t.dtype != torch.float32 or t.dim() != 3 or not t.is_contiguous():
+            raise AgxError(f"{op}: {name} must be a contiguous float32 (B, C, columns) tensor")
+    b = src.shape[0]
+    if src.shape[1] != c_in or src.shape[2] < src_need:
+        raise AgxError(f"{op}: {src_name} is {tuple(src.shape)} for {c_in} channels and a ring of at least {src_need} columns "
+                       "(the step's writes would alias its history)")
+    if tuple(dst.shape[:2]) != (b, c_out) or (dst.shape[2] < dst_cols if dst_ring else dst.shape[2] != dst_cols):
+        raise AgxError(f"{op}: dst is {tuple(dst.shape)} for batch {b}, c_out={c_out} and {dst_cols} "
+                       + ("new columns of a ring" if dst_ring else "plain columns"))
+    if dst.data_ptr() == src.data_ptr():
+        raise AgxError(f"{op}: the destination is one of the sources")
+    if end is None:
+        raise AgxError(f"{op}: end is needed (the block's zero padding and its raw tail are decided by the stream's end)")
+    lib = _lib.load()
+    _need_gpu(packed, bias, src, dst)
+    if any(t is not None and t.device != src.device for t in (packed, bias, dst)):
+        raise AgxError(f"{op}: operands on different devices")
+    pos = _checked_pos(op, pos, b, src.device)
+    end = _checked_pos(op, end, b, src.device)
+    if counts is not None:
+        counts = _checked_counts(op, counts, b, src.device)
+    packed = _f32c(packed)
+    need = lib.agx_conv_packed_floats(ctypes.byref(kind_desc))
+    if need < 0:
+        _lib.check(int(need), "agx_conv_packed_floats")
+    if packed.numel() != need:
+        raise AgxError(f"{op}: the packed image has {packed.numel()} floats, the layer's has {need}")
+    if bias is not None:
+        bias = _f32c(bias)
+        if bias.numel() != c_out:
+            raise AgxError(f"{op}: bias has {bias.numel()} entries for c_out={c_out}")
+    return b, packed, bias, pos, end, counts
+
+
+def wavelet_stream_in_step(c_in: int, hidden: int, kernel: int, packed: Tensor, bias: Optional[Tensor], src: Tensor, dst: Tensor,
+                           pos: Tensor, end: Tensor, n: int, rate_in: int, delay_in: int, counts: Optional[Tensor] = None) -> Tensor:
+    """conv_in of a wavelet block as a stream's step (``agx_wavelet_stream_in_step``): the "same" conv of ``kernel`` (odd) taps
+    from the block's input ring ``src`` (B, c_in, cap >= kernel - 1 + n rate_in) into the ring of the hidden activation ``dst``
+    (B, hidden, cap' >= n rate_in): the n rate_in columns [pos rate_in - D_h, ...), D_h = delay_in + (kernel - 1) / 2, exact 0
+    outside [0, end rate_in).  ``packed``: the ``conv_stream_pack`` image of the layer for ``CONV_SAME``.  ``counts``: the counted
+    form -- the ring is not written past a row's count.  Returns ``dst``."""
+    op = "wavelet_stream_in_step"
+    c_in, hidden, kernel, n, rate_in, delay_in = int(c_in), int(hidden), int(kernel), int(n), int(rate_in), int(delay_in)
+    if kernel < 1 or kernel % 2 == 0:
+        raise AgxError(f"{op}: a \"same\" conv streams with an odd kernel, got {kernel}")
+    if rate_in < 1 or delay_in < 0:
+        raise AgxError(f"{op}: rate_in = {rate_in} / delay_in = {delay_in}")
+    desc = conv_desc(CONV_SAME, 1, c_in, hidden, 1 << 20, kernel, 1, 1)
+    b, packed, bias, pos, end, counts = _wavelet_step_operands(op, desc, packed, bias, src, dst, pos, end, counts, c_in, hidden, n,
+                                                               kernel - 1 + n * rate_in, n * rate_in, True, "src")
+    lib = _lib.load()
+    tok = None
+    if _observer is not None:
+        tok = _observer.begin("other", (op, 4 * (packed.numel() + b * hidden * n * rate_in), 0))
+    head = (c_in, hidden, kernel, _ptr(packed), _ptr(bias), _ptr(src), src.shape[2], _ptr(dst), dst.shape[2], _ptr(pos), _ptr(end))
+    if counts is not None:
+        _lib.check(lib.agx_wavelet_stream_in_step_counted(*head, _ptr(counts), b, n, rate_in, delay_in, _stream()),
+                   "agx_wavelet_stream_in_step_counted")
+    else:
+        _lib.check(lib.agx_wavelet_stream_in_step(*head, b, n, rate_in, delay_in, _stream()), "agx_wavelet_stream_in_step")
+    if tok is not None:
+        _observer.end(tok)
+    return dst
+
+
+def wavelet_stream_out_step(hidden: int, c_out: int, kernel: int, scale: int, packed: Tensor, bias: Optional[Tensor], table: Tensor,
+                            h: Tensor, dst: Tensor, pos: Tensor, end: Tensor, n: int, rate_h: int, delay_h: int, dst_ring: bool = True,
+                            epilogue: int = 0, slope: float = 0.1, counts: Optional[Tensor] = None) -> Tensor:
+    """conv_out of a wavelet block with the fold fused into its operand fetch (``agx_wavelet_stream_out_step``): from the ring
+    ``h`` (B, hidden, cap >= 1 + ceil((kernel - 1) / scale) + n rate_h) of the in-step (``rate_h`` columns per frame, delay
+    ``delay_h``) and ``table`` (``wavelet_fold_table``) to the n rate_h scale columns [pos rate_h scale - D_out, ...), D_out =
+    delay_h scale + scale + (kernel - 1) / 2, exact 0 outside [0, end rate_h scale).  ``dst``: the consumer's ring or,
+    ``dst_ring=False``, a plain (B, c_out, n rate_h scale) tensor.  ``epilogue``: 0 or ``EPI_LEAKY_PRE``.  ``counts``: the counted
+    form.  Returns ``dst``."""
+    op = "wavelet_stream_out_step"
+    hidden, c_out, kernel, scale, n, rate_h, delay_h = int(hidden), int(c_out), int(kernel), int(scale), int(n), int(rate_h), int(delay_h)
+    if kernel < 1 or kernel % 2 == 0:
+        raise AgxError(f"{op}: a \"same\" conv streams with an odd kernel, got {kernel}")
+    if scale < 2:
+        raise AgxError(f"{op}: scale = {scale} < 2")
+    if rate_h < 1 or delay_h < 0:
+        raise AgxError(f"{op}: rate_h = {rate_h} / delay_h = {delay_h}")
+    if int(epilogue) & ~EPI_LEAKY_PRE:
+        raise AgxError(f"{op}: epilogue {epilogue} (bias and EPI_LEAKY_PRE are fused)")
+    if not isinstance(table, Tensor) or table.dtype != torch.float32 or tuple(table.shape) != (hidden, 3 * scale - 1) \
+            or not table.is_contiguous():
+        raise AgxError(f"{op}: table must be a contiguous float32 ({hidden}, {3 * scale - 1}) tensor (wavelet_fold_table)")
+    desc = conv_desc(CONV_SAME, 1, hidden, c_out, 1 << 20, kernel, 1, 1)
+    reach = 1 + -((1 - kernel) // scale)
+    b, packed, bias, pos, end, counts = _wavelet_step_operands(op, desc, packed, bias, h, dst, pos, end, counts, hidden, c_out, n,
+                                                               reach + n * rate_h, n * rate_h * scale, dst_ring, "h")
+    _need_gpu(table)
+    if table.device != h.device:
+        raise AgxError(f"{op}: operands on different devices")
+    lib = _lib.load()
+    tok = None
+    if _observer is not None:
+        tok = _observer.begin("other", (op, 4 * (packed.numel() + b * c_out * n * rate_h * scale), 0))
+    head = (hidden, c_out, kernel, scale, int(epilogue), float(slope), _ptr(packed), _ptr(bias), _ptr(table), _ptr(h), h.shape[2],
+            _ptr(dst), dst.shape[2] if dst_ring else 0, _ptr(pos), _ptr(end))
+    if counts is not None:
+        _lib.check(lib.agx_wavelet_stream_out_step_counted(*head, _ptr(counts), b, n, rate_h, delay_h, _stream()),
+                   "agx_wavelet_stream_out_step_counted")
+    else:
+        _lib.check(lib.agx_wavelet_stream_out_step(*head, b, n, rate_h, delay_h, _stream()), "agx_wavelet_stream_out_step")
+    if tok is not None:
+        _observer.end(tok)
+    return dst

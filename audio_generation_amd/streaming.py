@@ -30,6 +30,12 @@ it is not meaningful on a counted call.  ``counts=None`` is the uncounted call, 
 Packets.  ``encode_codes_stream`` / ``decode_codes_stream`` are the two ends of a wire: the sender's step gives one
 packet row per stream, the receiver's step turns packet rows into audio.  Their quantiser is ``ops.rvq_step_encode`` /
 ``ops.rvq_step_decode``, which read ``counts``: ``index`` behind a row's count is -1 and the packet bytes there are 0.
+
+Wavelet decoder blocks.  ``plan(..., wavelet_blocks=True)`` / ``model.new_stream(..., wavelet_blocks=True)`` stream a
+``WaveletLayer`` block as two launches: ``ops.wavelet_stream_in_step`` (``conv_in``, a "same" conv, into a ring of the hidden
+activation, ``CodecStream.dec_hidden``) and ``ops.wavelet_stream_out_step`` (``conv_out`` with the fold formed in its operand fetch
+from that ring, a per-channel table and the stream's ``end``, which decides the reference's raw tail).  Without the keyword such a
+model is refused as before.
 """
 from __future__ import annotations
 
@@ -39,7 +45,7 @@ from typing import List, Optional
 import torch
 
 from . import ops
-from ._lib import (CONV_CAUSAL, CONV_TRANSPOSED, CONV_UPSAMPLE, EPI_LEAKY_POST, EPI_LEAKY_PRE, EPI_RESIDUAL, STREAM_LIVE, AgxError,
+from ._lib import (CONV_CAUSAL, CONV_SAME, CONV_TRANSPOSED, CONV_UPSAMPLE, EPI_LEAKY_POST, EPI_LEAKY_PRE, EPI_RESIDUAL, STREAM_LIVE, AgxError,
                    needs_grad)
 from .units import Unit, detached, packed_image
 
@@ -52,10 +58,12 @@ def _ceil_div(a: int, b: int) -> int:
 
 @dataclass(frozen=True)
 class UnitPlan:
-    """One unit of a stack as a stream runs it.  ``kind``: "causal" | "convt" | "up" | "res"; ``k, s, d`` of its conv (of the
-    dilated conv of a residual unit); ``rate_in`` / ``delay_in`` and ``rate_out`` / ``delay_out`` in columns; ``reach``: input
-    columns it reads before the chunk's first new one; ``cap = reach + max_chunk * rate_in``: its ring, so that a step's writes
-    never alias the history the step reads."""
+    """One unit of a stack as a stream runs it.  ``kind``: "causal" | "convt" | "up" | "res" | "wavelet"; ``k, s, d`` of its conv
+    (of the dilated conv of a residual unit; of ``conv_in`` and the fold's scale for a wavelet unit); ``rate_in`` / ``delay_in`` and
+    ``rate_out`` / ``delay_out`` in columns; ``reach``: input columns it reads before the chunk's first new one; ``cap = reach +
+    max_chunk * rate_in``: its ring, so that a step's writes never alias the history the step reads.  A wavelet unit (DESIGN
+    4.23) has a second ring, of its hidden activation ``h``: ``hidden`` channels at ``rate_in`` columns per frame, lagging by
+    ``delay_h``, ``reach_h`` columns of history, capacity ``cap_h``; ``k_out``: the taps of ``conv_out``."""
     kind: str
     c_in: int
     c_out: int
@@ -68,6 +76,11 @@ class UnitPlan:
     delay_out: int
     reach: int
     cap: int
+    hidden: int = 0
+    k_out: int = 0
+    delay_h: int = 0
+    reach_h: int = 0
+    cap_h: int = 0
 
 
 @dataclass(frozen=True)
@@ -93,13 +106,30 @@ class StreamPlan:
 
 
 _REFUSED_UNITS = {
-    "wavelet": "a wavelet decoder block folds its time axis and has no streaming step",
+    "wavelet": "a wavelet decoder block streams only when asked for: new_stream(..., wavelet_blocks=True)",
     "multires": "a multiresolution layer has no streaming step",
     "resdw": "a depthwise residual block (depthwise=True) has no streaming step",
 }
 
 
-def _unit_plan(u: Unit, rate: int, delay: int, max_chunk: int) -> UnitPlan:
+def _wavelet_plan(u: Unit, rate: int, delay: int, max_chunk: int) -> UnitPlan:
+    """include/agx.h "Streaming wavelet blocks": D_h = D + p_in, D_out = D_h s + s + p_out; reach k_in - 1 in the input ring and
+    1 + ceil(2 p_out / s) in the ring of h."""
+    w = u.layer
+    k_in, k_out, s = w.wavelet_kernel_size, w.out_conv_kernel_size, w.scale_factor
+    if k_in % 2 == 0 or k_out % 2 == 0:
+        raise NotImplementedError(f"streaming: a wavelet block with even conv kernels ({k_in}, {k_out}) pads unevenly and has no step")
+    if s < 2:
+        raise NotImplementedError(f"streaming: a wavelet block with scale_factor {s} < 2 has no step")
+    delay_h = delay + (k_in - 1) // 2
+    reach_h = 1 + _ceil_div(k_out - 1, s)
+    return UnitPlan("wavelet", w.in_channels, w.out_channels, k_in, s, 1, rate, delay, rate * s, delay_h * s + s + (k_out - 1) // 2,
+                    k_in - 1, k_in - 1 + max_chunk * rate, w.hidden_channels, k_out, delay_h, reach_h, reach_h + max_chunk * rate)
+
+
+def _unit_plan(u: Unit, rate: int, delay: int, max_chunk: int, wavelet_blocks: bool = False) -> UnitPlan:
+    if u.kind == "wavelet" and wavelet_blocks:
+        return _wavelet_plan(u, rate, delay, max_chunk)
     if u.kind in _REFUSED_UNITS:
         raise NotImplementedError(f"streaming: {_REFUSED_UNITS[u.kind]}; use the plain or the *_long calls")
     if u.kind not in ("conv", "res"):
@@ -136,8 +166,9 @@ def _unit_plan(u: Unit, rate: int, delay: int, max_chunk: int) -> UnitPlan:
                     reach + max_chunk * rate)
 
 
-def plan(model, max_chunk: int) -> StreamPlan:
-    """Derived from the model's unit lists as they are wired; raises ``NotImplementedError`` for what a stream does not cover."""
+def plan(model, max_chunk: int, wavelet_blocks: bool = False) -> StreamPlan:
+    """Derived from the model's unit lists as they are wired; raises ``NotImplementedError`` for what a stream does not cover.
+    ``wavelet_blocks``: plan the wavelet decoder blocks instead of refusing them."""
     from .quantizer import ResidualQuantizer
     max_chunk = int(max_chunk)
     if max_chunk < 1:
@@ -150,7 +181,7 @@ def plan(model, max_chunk: int) -> StreamPlan:
     for which, rate in (("encoders", sf), ("decoders", 1)):
         delay, out = 0, []
         for u in model._units(which):
-            p = _unit_plan(u, rate, delay, max_chunk)
+            p = _unit_plan(u, rate, delay, max_chunk, wavelet_blocks)
             out.append(p)
             rate, delay = p.rate_out, p.delay_out
         if rate != (1 if which == "encoders" else sf):
@@ -165,19 +196,23 @@ class CodecStream:
     """The state of ``batch`` live streams through one ``CausalVQAE`` (``model.new_stream``): per unit one fp32 ring
     (B, c_in, cap) of its input, zero-filled; ``enc_pos`` / ``dec_pos``: the frames every row's encoder / decoder has received;
     ``end``: the frame at which a row's stream ended, ``ops.STREAM_LIVE`` while it is live.  All int64 (B,) on the device, read by
-    the kernels and advanced by a kernel.  ``decoder_delay``: samples by which ``decode_stream``'s output lags."""
+    the kernels and advanced by a kernel.  ``decoder_delay``: samples by which ``decode_stream``'s output lags.
+    ``wavelet_blocks=True``: the wavelet decoder blocks stream too; ``dec_hidden[i]`` is the ring (B, hidden, cap_h)
+    of unit ``i``'s hidden activation, None for every other unit -- ``dec_rings`` stays one ring per unit."""
 
-    def __init__(self, model, batch: int, max_chunk: int, device=None):
+    def __init__(self, model, batch: int, max_chunk: int, device=None, wavelet_blocks: bool = False):
         batch = int(batch)
         if batch < 1:
             raise AgxError(f"new_stream: batch = {batch} < 1")
-        self.plan = plan(model, max_chunk)
+        self.plan = plan(model, max_chunk, wavelet_blocks)
         self.model_id = id(model)
         self.batch, self.max_chunk = batch, self.plan.max_chunk
         self.scale_factor, self.decoder_delay = self.plan.scale_factor, self.plan.decoder_delay
         self.device = torch.device(device) if device is not None else next(model.parameters()).device
         self.enc_rings = [torch.zeros((batch, u.c_in, u.cap), dtype=torch.float32, device=self.device) for u in self.plan.encoders]
         self.dec_rings = [torch.zeros((batch, u.c_in, u.cap), dtype=torch.float32, device=self.device) for u in self.plan.decoders]
+        self.dec_hidden = [torch.zeros((batch, u.hidden, u.cap_h), dtype=torch.float32, device=self.device) if u.kind == "wavelet"
+                           else None for u in self.plan.decoders]
         self.enc_pos = torch.zeros(batch, dtype=torch.int64, device=self.device)
         self.dec_pos = torch.zeros(batch, dtype=torch.int64, device=self.device)
         self.end = torch.full((batch,), STREAM_LIVE, dtype=torch.int64, device=self.device)
@@ -201,8 +236,9 @@ class CodecStream:
             self.enc_pos[sel].zero_()
             self.dec_pos[sel].zero_()
             self.end[sel].fill_(STREAM_LIVE)
-            for ring in (*self.enc_rings, *self.dec_rings):
-                ring[sel].zero_()
+            for ring in (*self.enc_rings, *self.dec_rings, *self.dec_hidden):
+                if ring is not None:
+                    ring[sel].zero_()
 
     def positions(self) -> dict:
         """The positions as lists of ints.  Synchronises: for tests and debugging, never called in a step."""
@@ -215,26 +251,53 @@ def _image(layer) -> Tensor:
 
 
 def _run_stack(units: List[Unit], plans, rings: List[Tensor], x: Tensor, pos: Tensor, end: Optional[Tensor], n: int,
-               counts: Optional[Tensor] = None) -> Tensor:
+               counts: Optional[Tensor] = None, hidden: Optional[List[Optional[Tensor]]] = None) -> Tensor:
     """``n`` frames through a stack: the chunk into the first ring, one or two step launches per unit, the last unit into a plain
-    tensor, then the advance of ``pos``.  ``counts``: the same launches in their counted forms (None: the uncounted ones)."""
+    tensor, then the advance of ``pos``.  ``counts``: the same launches in their counted forms (None: the uncounted ones).
+    ``hidden``: per unit the ring of a wavelet unit's hidden activation (None: the stack has no such unit)."""
     b = x.shape[0]
     ops.ring_write_rate(rings[0], x, pos, plans[0].rate_in, counts=counts)
     out = None
     for i, (u, p) in enumerate(zip(units, plans)):
         last = i + 1 == len(units)
         dst = torch.empty((b, p.c_out, n * p.rate_out), dtype=torch.float32, device=x.device) if last else rings[i + 1]
-        out = run_unit(u, p, rings[i], dst, not last, pos, end, n, counts)
+        if p.kind == "wavelet":
+            out = run_unit(u, p, rings[i], dst, not last, pos, end, n, counts, hidden=hidden[i])
+        else:
+            out = run_unit(u, p, rings[i], dst, not last, pos, end, n, counts)
     ops.stream_advance(pos, n, counts=counts)
     return out
 
 
+def fold_table(layer) -> Tensor:
+    """The out-step's per-channel table of a ``WaveletLayer`` (``ops.wavelet_fold_table``), kept on the layer and rebuilt when
+    ``data_ptr`` / ``_version`` of ``wavelet_scale`` change -- the rule of ``units.packed_image``."""
+    sig = layer.wavelet_scale
+    key = (sig.data_ptr(), sig._version, layer.space.data_ptr())
+    slot = layer.__dict__.get("_fold_table")
+    if slot is None or slot[0] != key:
+        slot = (key, ops.wavelet_fold_table(layer.space, sig.detach(), layer.hidden_channels, layer.scale_factor))
+        layer.__dict__["_fold_table"] = slot
+    return slot[1]
+
+
 def run_unit(u: Unit, p: UnitPlan, ring: Tensor, dst: Tensor, dst_ring: bool, pos: Tensor, end: Optional[Tensor], n: int,
-             counts: Optional[Tensor] = None) -> Tensor:
+             counts: Optional[Tensor] = None, hidden: Optional[Tensor] = None) -> Tensor:
     """One unit's step: ``ring`` -> ``dst``.  A conv is one launch; a residual unit is two, its hidden activation (which only the
     k = 1 conv at the same column reads, so it needs no mask and no history) in a plain scratch tensor.  ``counts``: the counted
-    launches (the hidden activation is exact 0 behind a row's count)."""
+    launches (the hidden activation is exact 0 behind a row's count).  A wavelet unit is two: the in-step into ``hidden``, the
+    ring of its hidden activation, and the out-step, which folds on the fly."""
     post = u.slope
+    if p.kind == "wavelet":
+        w = u.layer
+        if hidden is None:
+            raise AgxError("streaming: a wavelet unit needs the ring of its hidden activation (CodecStream.dec_hidden)")
+        ops.wavelet_stream_in_step(p.c_in, p.hidden, p.k, packed_image(w.conv_in, "conv_stream_pack", CONV_SAME), detached(w.conv_in.bias),
+                                   ring, hidden, pos, end, n, p.rate_in, p.delay_in, counts=counts)
+        return ops.wavelet_stream_out_step(p.hidden, p.c_out, p.k_out, p.s, packed_image(w.conv_out, "conv_stream_pack", CONV_SAME),
+                                           detached(w.conv_out.bias), fold_table(w), hidden, dst, pos, end, n, p.rate_in, p.delay_h,
+                                           dst_ring=dst_ring, epilogue=EPI_LEAKY_PRE if post is not None else 0, slope=post or 0.0,
+                                           counts=counts)
     if p.kind == "res":
         c1, c2 = u.convs[0], u.convs[1]
         hid = torch.empty((ring.shape[0], c1.conv.out_channels, n * p.rate_in), dtype=torch.float32, device=ring.device)
@@ -297,7 +360,7 @@ def encode_stream(model, x: Tensor, stream: CodecStream, codebook_n: Optional[in
 def decode_stream(model, zq: Tensor, stream: CodecStream, counts: Optional[Tensor] = None) -> Tensor:
     n = _check(model, stream, zq, "decode_stream", 1, stream.plan.decoders[0].c_in, counts)
     y = _run_stack(model._units("decoders"), stream.plan.decoders, stream.dec_rings, zq.contiguous(), stream.dec_pos, stream.end, n,
-                   counts)
+                   counts, stream.dec_hidden)
     return model.rearrange_out(y)
 
 

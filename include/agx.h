@@ -1236,6 +1236,54 @@ int agx_rvq_step_decode(const uint8_t *packets, int32_t bits, const float *codeb
                         int32_t batch, int32_t n, int32_t dim, int32_t k, int32_t q_total, int32_t q_used, float *zq, int64_t q_sb,
                         int64_t q_st, int64_t q_sd, int64_t *index, void *stream);
 
+/* ---- Streaming wavelet blocks (csrc/wavelet_stream.hip) --------------------------------------------------------
+ * A wavelet decoder block (conv_in "same", k_in odd, p_in = (k_in - 1) / 2; fold by scale s >= 2 over n_points P, s | P;
+ * conv_out "same", k_out odd, p_out = (k_out - 1) / 2) as two steps of a stream, in the terms of "Streaming conv stacks".  The
+ * block sits at rate_in = r columns per frame with delay D; L_b = end[b] r is the length of row b's signal at the block's input,
+ * infinite while end[b] == AGX_STREAM_LIVE.
+ *   in-step   produces the n r columns [pos r - D_h, (pos + n) r - D_h) of h, D_h = D + p_in, into the ring of h:
+ *             h[l] = bias + sum_j W[j] x[l + j - p_in], x from the block's input ring (exact 0 outside [0, L_b) already);
+ *             stored as exact 0 unless 0 <= l < L_b.  Reach k_in - 1: src_cap >= k_in - 1 + n r.  rate_h = r, delay_h = D_h.
+ *   out-step  produces the n r s columns [pos r s - D_out, (pos + n) r s - D_out), D_out = D_h s + s + p_out:
+ *             out[u] = bias + sum_{c, j} Wo[o, c, j] y[c, u + j - p_out], then AGX_EPI_LEAKY_PRE; stored as exact 0 unless
+ *             0 <= u < L_b s.  y is never stored; with l0 = floor(v / s), ph = v - l0 s:
+ *                 y[c, v] = 0                                                          v < 0 or v >= L_b s
+ *                 y[c, v] = ph == 0 ? h[c, l0] S_hi[c, 0]
+ *                                   : fmaf(h[c, l0 + 1], S_lo[c, ph], h[c, l0] * S_hi[c, ph])    v < (L_b - 1) s + 1
+ *                 y[c, v] = tail[c, v - ((L_b - 1) s + 1)] * h[c, L_b - 1]              the last s - 1 live columns
+ *             -- agx_wavelet_fold's two taps and raw tail, the tail decided by the device-held end.  Every case is a select
+ *             on the index, never a product with a 0 of the table or of a mask: the column l0 + 1 behind ph == 0 may be one the
+ *             ring has not received, and it is not read.  Reach in h: 1 + ceil(2 p_out / s); h_cap >= that + n r.
+ *   table     (hidden, 3 s - 1) fp32 per channel: S_hi[0 .. s), S_lo[0 .. s), tail[0 .. s - 1) = kern[P - (s - 1) .. P), with
+ *             kern, S_hi and S_lo formed by the code of agx_wavelet_fold.  agx_wavelet_fold_table writes it in one launch.
+ * With these delays a step reads no column of h that has not been produced, and every tail column is computed in a step after
+ * end was set (D_out > s - 1).  Both steps are the kernel of agx_conv_stream_step -- the same fixed fmaf chain per output, KS a
+ * function of the layer alone -- on the standard image of agx_conv_pack for AGX_CONV_SAME; the out-step forms its operands on
+ * the fly.  dst of the out-step: a ring (dst_cap >= n r s) or, dst_cap == 0, a plain (B, c_out, n r s) tensor.  The _counted
+ * forms follow "Per-row frame counts".  batch or n <= 0: AGX_OK, nothing launched.  Refused before any launch or use of a
+ * pointer: s < 2, s not dividing P, an even kernel, a capacity too small, NULL pointers (end included), dst aliasing a source. */
+int agx_wavelet_fold_table(const float *space, const float *sigma, int32_t sigma_len, float *table, int32_t channels, int32_t n_points,
+                           int32_t scale, void *stream);
+int agx_wavelet_stream_in_step(int32_t c_in, int32_t hidden, int32_t kernel, const float *packed, const float *bias, const float *src,
+                               int32_t src_cap, float *dst, int32_t dst_cap, const int64_t *pos, const int64_t *end, int32_t batch, int32_t n,
+                               int32_t rate_in, int64_t delay_in, void *stream);
+int agx_wavelet_stream_in_step_counted(int32_t c_in, int32_t hidden, int32_t kernel, const float *packed, const float *bias, const float *src,
+                                       int32_t src_cap, float *dst, int32_t dst_cap, const int64_t *pos, const int64_t *end,
+                                       const int64_t *counts, int32_t batch, int32_t n, int32_t rate_in, int64_t delay_in, void *stream);
+int agx_wavelet_stream_out_step(int32_t hidden, int32_t c_out, int32_t kernel, int32_t scale, int32_t epilogue, float slope,
+                                const float *packed, const float *bias, const float *table, const float *h, int32_t h_cap, float *dst,
+                                int32_t dst_cap, const int64_t *pos, const int64_t *end, int32_t batch, int32_t n, int32_t rate_h,
+                                int64_t delay_h, void *stream);
+int agx_wavelet_stream_out_step_counted(int32_t hidden, int32_t c_out, int32_t kernel, int32_t scale, int32_t epilogue, float slope,
+                                        const float *packed, const float *bias, const float *table, const float *h, int32_t h_cap,
+                                        float *dst, int32_t dst_cap, const int64_t *pos, const int64_t *end, const int64_t *counts,
+                                        int32_t batch, int32_t n, int32_t rate_h, int64_t delay_h, void *stream);
+/* Host-only, in the style of agx_conv_stream_kernel_name: "conv_stream<KS,NT>" / "wavelet_stream_out<KS,NT>", "none" for an empty
+ * step, or the launcher's refusal.  KS does not move with n. */
+int agx_wavelet_stream_in_kernel_name(int32_t c_in, int32_t hidden, int32_t kernel, int32_t n, int32_t rate_in, char *buf, size_t buf_len);
+int agx_wavelet_stream_out_kernel_name(int32_t hidden, int32_t c_out, int32_t kernel, int32_t scale, int32_t n, int32_t rate_h, char *buf,
+                                       size_t buf_len);
+
 #ifdef __cplusplus
 }
 #endif
