@@ -323,6 +323,17 @@ SIGNATURES = {
                                                     c_int32, c_int64, c_void_p]),
     "agx_wavelet_stream_in_kernel_name": (c_int, [c_int32, c_int32, c_int32, c_int32, c_int32, c_char_p, c_size_t]),
     "agx_wavelet_stream_out_kernel_name": (c_int, [c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, c_char_p, c_size_t]),
+    # streaming multires layers and depthwise residual blocks
+    "agx_multires_stream_step": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_void_p, c_int32, c_void_p, c_void_p, c_int32,
+                                         c_int32, c_int32, c_int32, c_int32, c_int32, c_int64, c_void_p]),
+    "agx_multires_stream_step_counted": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_void_p, c_int32, c_void_p, c_void_p,
+                                                 c_void_p, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, c_int64, c_void_p]),
+    "agx_conv_stream_step_affine": (c_int, [c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, c_float, c_void_p, c_void_p,
+                                            c_void_p, c_void_p, c_void_p, c_int32, c_void_p, c_int32, c_void_p, c_int32, c_void_p, c_void_p,
+                                            c_int32, c_int32, c_int32, c_int64, c_void_p]),
+    "agx_conv_stream_step_affine_counted": (c_int, [c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, c_float, c_void_p,
+                                                    c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_void_p, c_int32, c_void_p, c_int32,
+                                                    c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int64, c_void_p]),
 }
 
 _lib = None

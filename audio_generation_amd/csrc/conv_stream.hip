@@ -119,7 +119,12 @@ StreamPick stream_pick(const char *op, int kind, int c_in, int c_out, int kernel
 int stream_step(const char *op, int32_t kind, int32_t c_in, int32_t c_out, int32_t kernel, int32_t stride, int32_t dilation,
                 int32_t epilogue, float slope, const float *packed, const float *bias, const float *src, int32_t src_cap,
                 const float *res, int32_t res_cap, float *dst, int32_t dst_cap, const int64_t *pos, const int64_t *end,
-                const int64_t *counts, int32_t batch, int32_t n, int32_t rate_in, int64_t delay_in, void *stream, bool same_ok) {
+                const int64_t *counts, int32_t batch, int32_t n, int32_t rate_in, int64_t delay_in, void *stream, bool same_ok,
+                bool affine, const float *scale, const float *shift) {
+    // the operand policy of a depthwise block's dilated conv (the padding lies behind the affine): refused by kind before anything else
+    if (affine && batch > 0 && n > 0 && (kind != AGX_CONV_CAUSAL || stride != 1 || src_cap == 0))
+        return fail(AGX_ERR_UNSUPPORTED, "%s: the per-channel affine is the operand of a stride-1 causal conv reading a ring (kind=%d s=%d "
+                    "src_cap=%d)", op, kind, stride, src_cap);
     StreamPick k = stream_pick(op, kind, c_in, c_out, kernel, stride, dilation, batch, n, rate_in, delay_in, same_ok);
     if (k.code) return k.code;
     if (k.empty) return AGX_OK;
@@ -141,13 +146,22 @@ int stream_step(const char *op, int32_t kind, int32_t c_in, int32_t c_out, int32
         if (res_cap < n_out) return fail(AGX_ERR_BAD_SHAPE, "%s: res_cap=%d < %lld new columns", op, res_cap, (long long)n_out);
         if (!res) return fail(AGX_ERR_NULL_POINTER, "%s: NULL residual ring", op);
     }
+    if (affine && (!scale || !shift)) return fail(AGX_ERR_NULL_POINTER, "%s: NULL scale or shift", op);
     if (!packed || !src || !dst || !pos) return fail(AGX_ERR_NULL_POINTER, "%s: NULL pointer", op);
     if (dst == src || dst == res) return fail(AGX_ERR_BAD_SHAPE, "%s: the destination is one of the sources", op);
     a.W = packed, a.bias = bias, a.src = src, a.res = (epilogue & AGX_EPI_RESIDUAL) ? res : nullptr, a.dst = dst, a.pos = pos, a.end = end;
     a.counts = counts, a.n = n;
     a.src_cap = src_cap, a.res_cap = res_cap, a.dst_cap = dst_cap, a.epilogue = epilogue, a.slope = slope;
+    a.scale = scale, a.shift = shift;
     const dim3 grid(ceil_div(a.M, 64), ceil_div(a.nt, k.nt_tile), batch);
     hipStream_t st = static_cast<hipStream_t>(stream);
+    if (affine) {
+        if (counts)
+            stream_launch<true, false, true>(k, grid, st);
+        else
+            stream_launch<false, false, true>(k, grid, st);
+        return check_launch(op);
+    }
     if (counts)
         stream_launch<true, false>(k, grid, st);
     else
@@ -192,6 +206,27 @@ int agx_conv_stream_step_counted(int32_t kind, int32_t c_in, int32_t c_out, int3
     if (!counts && batch > 0 && n > 0) return agx::fail(AGX_ERR_NULL_POINTER, "conv_stream_step_counted: NULL counts");
     return agx::stream_step("conv_stream_step_counted", kind, c_in, c_out, kernel, stride, dilation, epilogue, slope, packed, bias, src,
                             src_cap, res, res_cap, dst, dst_cap, pos, end, counts, batch, n, rate_in, delay_in, stream);
+}
+
+int agx_conv_stream_step_affine(int32_t kind, int32_t c_in, int32_t c_out, int32_t kernel, int32_t stride, int32_t dilation,
+                                int32_t epilogue, float slope, const float *packed, const float *bias, const float *scale,
+                                const float *shift, const float *src, int32_t src_cap, const float *res, int32_t res_cap, float *dst,
+                                int32_t dst_cap, const int64_t *pos, const int64_t *end, int32_t batch, int32_t n, int32_t rate_in,
+                                int64_t delay_in, void *stream) {
+    return agx::stream_step("conv_stream_step_affine", kind, c_in, c_out, kernel, stride, dilation, epilogue, slope, packed, bias, src,
+                            src_cap, res, res_cap, dst, dst_cap, pos, end, nullptr, batch, n, rate_in, delay_in, stream, false, true, scale,
+                            shift);
+}
+
+int agx_conv_stream_step_affine_counted(int32_t kind, int32_t c_in, int32_t c_out, int32_t kernel, int32_t stride, int32_t dilation,
+                                        int32_t epilogue, float slope, const float *packed, const float *bias, const float *scale,
+                                        const float *shift, const float *src, int32_t src_cap, const float *res, int32_t res_cap,
+                                        float *dst, int32_t dst_cap, const int64_t *pos, const int64_t *end, const int64_t *counts,
+                                        int32_t batch, int32_t n, int32_t rate_in, int64_t delay_in, void *stream) {
+    if (!counts && batch > 0 && n > 0) return agx::fail(AGX_ERR_NULL_POINTER, "conv_stream_step_affine_counted: NULL counts");
+    return agx::stream_step("conv_stream_step_affine_counted", kind, c_in, c_out, kernel, stride, dilation, epilogue, slope, packed, bias,
+                            src, src_cap, res, res_cap, dst, dst_cap, pos, end, counts, batch, n, rate_in, delay_in, stream, false, true,
+                            scale, shift);
 }
 
 int agx_conv_stream_kernel_name(int32_t kind, int32_t c_in, int32_t c_out, int32_t kernel, int32_t stride, int32_t dilation, int32_t n,

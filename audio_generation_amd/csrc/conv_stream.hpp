@@ -36,6 +36,8 @@ struct StreamArgs {
     // operand y[c, v] is formed from it, the per-channel table (Cin, 3 fold_s - 1) = [S_hi | S_lo | tail taps] and end[b]
     const float *tab;
     int fold_s, fold_rate;
+    // AFF, the operand policy of a depthwise residual block's dilated conv: the per-channel affine of the grouped k = 1 conv
+    const float *scale, *shift;
 };
 
 __device__ __forceinline__ int floor_mod(int64_t a, int cap) {
@@ -54,7 +56,13 @@ __device__ __forceinline__ int floor_mod(int64_t a, int cap) {
 //     else                     tail[v - ((L - 1) s + 1)] * h[L - 1]
 // Every case is a select on the index: the column l0 + 1 behind ph == 0 may be one the ring has not received yet, and it is
 // never read, let alone multiplied by the 0 that S_lo[0] holds.
-template <int KS, int NT, bool CNT, bool FOLD = false>
+//
+// AFF (include/agx.h "Streaming multires layers and depthwise residual blocks"): the operand of channel c at stream column i is
+//     i >= 0 && c < Cin ? fmaf(scale[c], x[c, i], shift[c]) : 0
+// -- the causal zero padding lies behind the affine, so a column before the start of the stream gives 0 and not shift[c], and so
+// does a channel that pads the last group of 16 (the plain fetch leaves those to the image's zero padding; shift would bias them).
+// A select on the index, like FOLD's cases.  Causal, stride 1, ring source: the host refuses everything else.
+template <int KS, int NT, bool CNT, bool FOLD = false, bool AFF = false>
 __global__ __launch_bounds__(64 * KS) void conv_stream_kernel(const StreamArgs a) {
     __shared__ float red[KS > 1 ? KS * NT * 64 : 1];
     const int lane = threadIdx.x & 63;
@@ -120,7 +128,8 @@ __global__ __launch_bounds__(64 * KS) void conv_stream_kernel(const StreamArgs a
     const int chunk = (GJ + KS - 1) / KS;
     const int gj_end = min(GJ, (ks + 1) * chunk);
     // operands of one (g, j): the lane's 16 weights and its 1 or 2 activation values
-    auto fetch = [&](int gj, float4 (&wq)[4], int (&xr)[NR]) {
+    // (AFF: also the lane's scale and shift, sc / sh -- the affine is applied where the value is used, so that the load stays in flight)
+    auto fetch = [&](int gj, float4 (&wq)[4], int (&xr)[NR], float (&sc)[NR], float (&sh)[NR]) {
         const int g = gj / a.J, j = gj - g * a.J;
         const float4 *wp = reinterpret_cast<const float4 *>(W + (size_t(gj) * a.M + mr) * kWG);
 #pragma unroll
@@ -156,6 +165,7 @@ __global__ __launch_bounds__(64 * KS) void conv_stream_kernel(const StreamArgs a
         }
         int col = col0 + j * a.d;
         bool ok = true;
+        if (AFF) ok = my_idx + int64_t(j) * a.d >= 0;      // the column's stream index, not only its ring column
         if (a.src_cap) {
             col = col >= a.src_cap ? col - a.src_cap : col;
         } else {
@@ -166,21 +176,26 @@ __global__ __launch_bounds__(64 * KS) void conv_stream_kernel(const StreamArgs a
             const int ch = g * kWG + my_c + r * CSTEP;            // channels past Cin meet the image's zero padding
             const bool have = ok && lane + 64 * r < NV && ch < a.Cin;
             xr[r] = have ? __float_as_int(xb[size_t(ch) * xpitch + col]) : 0;
+            if (AFF) {      // the select picks all three operands -- x is not read -- so fmaf(0, 0, 0) is the padding's exact 0
+                sc[r] = have ? a.scale[ch] : 0.f;
+                sh[r] = have ? a.shift[ch] : 0.f;
+            }
         }
     };
     // the loads of (g, j) + 1 are in flight while the chain takes (g, j): the waves of a small step are few and latency-bound
     float4 wn[4];
     int xn[NR];
+    float scn[NR], shn[NR];
     int gj = ks * chunk;
-    if (gj < gj_end) fetch(gj, wn, xn);
+    if (gj < gj_end) fetch(gj, wn, xn, scn, shn);
     for (; gj < gj_end; ++gj) {
         float4 wq[4];
         int xr[NR];
 #pragma unroll
         for (int k = 0; k < 4; ++k) wq[k] = wn[k];
 #pragma unroll
-        for (int r = 0; r < NR; ++r) xr[r] = xn[r];
-        if (gj + 1 < gj_end) fetch(gj + 1, wn, xn);
+        for (int r = 0; r < NR; ++r) xr[r] = AFF ? __float_as_int(fmaf(scn[r], __int_as_float(xn[r]), shn[r])) : xn[r];
+        if (gj + 1 < gj_end) fetch(gj + 1, wn, xn, scn, shn);
         const float w[kWG] = {wq[0].x, wq[0].y, wq[0].z, wq[0].w, wq[1].x, wq[1].y, wq[1].z, wq[1].w,
                               wq[2].x, wq[2].y, wq[2].z, wq[2].w, wq[3].x, wq[3].y, wq[3].z, wq[3].w};
 #pragma unroll
@@ -248,25 +263,26 @@ StreamPick stream_pick(const char *op, int kind, int c_in, int c_out, int kernel
 int stream_step(const char *op, int32_t kind, int32_t c_in, int32_t c_out, int32_t kernel, int32_t stride, int32_t dilation,
                 int32_t epilogue, float slope, const float *packed, const float *bias, const float *src, int32_t src_cap,
                 const float *res, int32_t res_cap, float *dst, int32_t dst_cap, const int64_t *pos, const int64_t *end,
-                const int64_t *counts, int32_t batch, int32_t n, int32_t rate_in, int64_t delay_in, void *stream, bool same_ok = false);
+                const int64_t *counts, int32_t batch, int32_t n, int32_t rate_in, int64_t delay_in, void *stream, bool same_ok = false,
+                bool affine = false, const float *scale = nullptr, const float *shift = nullptr);
 
-template <int KS, bool CNT, bool FOLD>
+template <int KS, bool CNT, bool FOLD, bool AFF>
 static void stream_launch_nt(const StreamPick &k, dim3 grid, hipStream_t st) {
     switch (k.nt_tile) {
-        case 1: hipLaunchKernelGGL((conv_stream_kernel<KS, 1, CNT, FOLD>), grid, dim3(64 * KS), 0, st, k.a); break;
-        case 4: hipLaunchKernelGGL((conv_stream_kernel<KS, 4, CNT, FOLD>), grid, dim3(64 * KS), 0, st, k.a); break;
-        default: hipLaunchKernelGGL((conv_stream_kernel<KS, 8, CNT, FOLD>), grid, dim3(64 * KS), 0, st, k.a); break;
+        case 1: hipLaunchKernelGGL((conv_stream_kernel<KS, 1, CNT, FOLD, AFF>), grid, dim3(64 * KS), 0, st, k.a); break;
+        case 4: hipLaunchKernelGGL((conv_stream_kernel<KS, 4, CNT, FOLD, AFF>), grid, dim3(64 * KS), 0, st, k.a); break;
+        default: hipLaunchKernelGGL((conv_stream_kernel<KS, 8, CNT, FOLD, AFF>), grid, dim3(64 * KS), 0, st, k.a); break;
     }
 }
 
-template <bool CNT, bool FOLD>
+template <bool CNT, bool FOLD, bool AFF = false>
 static void stream_launch(const StreamPick &k, dim3 grid, hipStream_t st) {
     switch (k.ks) {
-        case 1: stream_launch_nt<1, CNT, FOLD>(k, grid, st); break;
-        case 2: stream_launch_nt<2, CNT, FOLD>(k, grid, st); break;
-        case 4: stream_launch_nt<4, CNT, FOLD>(k, grid, st); break;
-        case 8: stream_launch_nt<8, CNT, FOLD>(k, grid, st); break;
-        default: stream_launch_nt<16, CNT, FOLD>(k, grid, st); break;
+        case 1: stream_launch_nt<1, CNT, FOLD, AFF>(k, grid, st); break;
+        case 2: stream_launch_nt<2, CNT, FOLD, AFF>(k, grid, st); break;
+        case 4: stream_launch_nt<4, CNT, FOLD, AFF>(k, grid, st); break;
+        case 8: stream_launch_nt<8, CNT, FOLD, AFF>(k, grid, st); break;
+        default: stream_launch_nt<16, CNT, FOLD, AFF>(k, grid, st); break;
     }
 }
 

@@ -2316,9 +2316,37 @@ def conv_stream_step(kind: int, c_in: int, c_out: int, kernel: int, stride: int,
     ``counts`` (int64 (B,), device; ``agx_conv_stream_step_counted``): row ``b`` takes the first ``c_b = clamp(counts[b], 0, n)``
     frames.  Its first ``c_b * rate_out`` output columns are bit for bit those of the uncounted step on these frames; behind them
     a plain ``dst`` holds exact 0 and a ring ``dst`` is not written.  The kernel reads ``counts``; the host never does."""
-    lib = _lib.load()
-    _need_gpu(packed, bias, src, dst, res)
+    return _conv_stream_step(kind, c_in, c_out, kernel, stride, dilation, packed, bias, src, dst, pos, n, rate_in, delay_in, src_ring,
+                             dst_ring, res, end, epilogue, slope, counts, None)
+
+
+def conv_stream_step_affine(c_in: int, c_out: int, kernel: int, dilation: int, packed: Tensor, bias: Optional[Tensor], scale: Tensor,
+                            shift: Tensor, src: Tensor, dst: Tensor, pos: Tensor, n: int, rate_in: int, delay_in: int,
+                            dst_ring: bool = True, end: Optional[Tensor] = None, epilogue: int = 0, slope: float = 0.1,
+                            counts: Optional[Tensor] = None, kind: int = CONV_CAUSAL, stride: int = 1, src_ring: bool = True) -> Tensor:
+    """``conv_stream_step`` of a stride-1 causal conv with a per-channel affine in its operand fetch
+    (``agx_conv_stream_step_affine``): ``scale`` / ``shift`` are two fp32 (c_in,) vectors, the folded weight and the
+    bias of the grouped k = 1 conv in front of a depthwise residual block's dilated conv.  The operand of channel ``c`` at stream
+    column ``i`` is ``fmaf(scale[c], x[c, i], shift[c])`` for ``i >= 0`` and exact 0 before the start of the stream: the causal
+    zero padding lies behind the affine.  ``kind`` / ``stride`` / ``src_ring`` are there to be refused: the policy is that of a
+    stride-1 causal conv reading a ring.  Everything else as in ``conv_stream_step``; every refusal precedes the launch."""
+    return _conv_stream_step(kind, c_in, c_out, kernel, stride, dilation, packed, bias, src, dst, pos, n, rate_in, delay_in, src_ring,
+                             dst_ring, None, end, epilogue, slope, counts, (scale, shift))
+
+
+def _conv_stream_step(kind, c_in, c_out, kernel, stride, dilation, packed, bias, src, dst, pos, n, rate_in, delay_in, src_ring, dst_ring,
+                      res, end, epilogue, slope, counts, affine) -> Tensor:
+    """The one body of ``conv_stream_step`` (``affine=None``) and ``conv_stream_step_affine`` (``affine=(scale, shift)``)."""
     n, rate_in, delay_in = int(n), int(rate_in), int(delay_in)
+    if affine is not None:      # shape refusals of the affine form first: they need no device
+        if kind != CONV_CAUSAL or int(stride) != 1 or not src_ring:
+            raise AgxError("conv_stream_step_affine: the affine is the operand of a stride-1 causal conv reading a ring "
+                           f"(kind={kind} stride={stride} src_ring={src_ring})")
+        if any(not isinstance(t, Tensor) or t.dtype != torch.float32 or t.dim() != 1 or t.numel() != int(c_in)
+                                   or not t.is_contiguous() for t in affine):
+            raise AgxError(f"conv_stream_step_affine: scale and shift are two contiguous float32 ({c_in},) vectors")
+    lib = _lib.load()
+    _need_gpu(packed, bias, src, dst, res, *(affine or ()))
     if n < 1:
         raise AgxError(f"conv_stream_step: a step takes n >= 1 frames, got {n}")
     for name, t in (("src", src), ("dst", dst), ("res", res)):
@@ -2336,7 +2364,7 @@ def conv_stream_step(kind: int, c_in: int, c_out: int, kernel: int, stride: int,
         raise AgxError("conv_stream_step: EPI_RESIDUAL and the residual ring go together")
     if res is not None and tuple(res.shape[:2]) != (b, c_out):
         raise AgxError(f"conv_stream_step: the residual ring is {tuple(res.shape)} for batch {b}, c_out={c_out}")
-    if any(t is not None and t.device != src.device for t in (packed, bias, dst, res)):
+    if any(t is not None and t.device != src.device for t in (packed, bias, dst, res, *(affine or ()))):
         raise AgxError("conv_stream_step: operands on different devices")
     pos = _checked_pos("conv_stream_step", pos, b, src.device)
     if end is not None:
@@ -2356,14 +2384,97 @@ def conv_stream_step(kind: int, c_in: int, c_out: int, kernel: int, stride: int,
     tok = None
     if _observer is not None:
         tok = _observer.begin("other", ("conv_stream_step", 4 * (packed.numel() + b * c_out * n * rate_out), 0))
-    head = (kind, c_in, c_out, kernel, stride, dilation, int(epilogue), float(slope), _ptr(packed), _ptr(bias), _ptr(src),
+    head = (kind, c_in, c_out, kernel, stride, dilation, int(epilogue), float(slope), _ptr(packed), _ptr(bias),
+            *(() if affine is None else (_ptr(affine[0]), _ptr(affine[1]))), _ptr(src),
             src.shape[2] if src_ring else 0, _ptr(res), res.shape[2] if res is not None else 0, _ptr(dst),
             dst.shape[2] if dst_ring else 0, _ptr(pos), _ptr(end))
-    if counts is not None:
+    if affine is not None and counts is not None:
+        _lib.check(lib.agx_conv_stream_step_affine_counted(*head, _ptr(counts), b, n, rate_in, delay_in, _stream()),
+                   "agx_conv_stream_step_affine_counted")
+    elif affine is not None:
+        _lib.check(lib.agx_conv_stream_step_affine(*head, b, n, rate_in, delay_in, _stream()), "agx_conv_stream_step_affine")
+    elif counts is not None:
         _lib.check(lib.agx_conv_stream_step_counted(*head, _ptr(counts), b, n, rate_in, delay_in, _stream()),
                    "agx_conv_stream_step_counted")
     else:
         _lib.check(lib.agx_conv_stream_step(*head, b, n, rate_in, delay_in, _stream()), "agx_conv_stream_step")
+    if tok is not None:
+        _observer.end(tok)
+    return dst
+
+
+MULTIRES_STREAM_TILE = 1024          # AGX_MULTIRES_STREAM_TILE
+MULTIRES_STREAM_LDS_BYTES = 65536    # AGX_MULTIRES_STREAM_LDS_BYTES
+
+
+def multires_stream_reach(kernel: int, depth: int) -> int:
+    """Input columns the cascade reads before an output's own: ``(K - 1)(2^depth - 1)``."""
+    return (int(kernel) - 1) * ((1 << int(depth)) - 1)
+
+
+def multires_stream_fits(kernel: int, depth: int, cols: int) -> bool:
+    """Whether ``multires_stream_step`` holds a step of ``cols`` columns: the two LDS rows of reach + tile floats and the taps of
+    one channel row within ``MULTIRES_STREAM_LDS_BYTES`` (the library's own refusal, host-only)."""
+    if int(depth) < 0 or int(depth) > 20 or int(kernel) < 1:
+        return False
+    tile = min(int(cols), MULTIRES_STREAM_TILE)
+    return 4 * (2 * (multires_stream_reach(kernel, depth) + tile) + 2 * int(kernel)) <= MULTIRES_STREAM_LDS_BYTES
+
+
+def multires_stream_step(h0: Tensor, h1: Tensor, w: Tensor, depth: int, src: Tensor, dst: Tensor, pos: Tensor, n: int, rate: int,
+                         delay: int, dst_ring: bool = True, end: Optional[Tensor] = None, counts: Optional[Tensor] = None) -> Tensor:
+    """One chunk of ``n`` frames through a ``CausalMultiresConv1d`` of a stream (``agx_multires_stream_step``), one
+    launch: from the layer's input ring ``src`` (B, C, cap >= (K - 1)(2^depth - 1) + n rate) to the n rate columns
+    [pos rate - delay, (pos + n) rate - delay) of ``dst`` -- the consumer's ring (B, C, cap' >= n rate) or, ``dst_ring=False``, a
+    plain (B, C, n rate) tensor --, each the cascade and GELU of ``multires_forward``, exact 0 where the index is negative or at
+    and behind ``end[b] rate`` (``end=None``: no mask).  ``h0`` / ``h1`` (C, 1, K) and ``w`` (C, depth + 2): the layer's parameters.
+    ``counts``: the counted form -- behind a row's count a plain ``dst`` holds exact 0, a ring is not written and no source column
+    is read.  Every refusal precedes the launch.  Returns ``dst``."""
+    op = "multires_stream_step"
+    depth, n, rate, delay = int(depth), int(n), int(rate), int(delay)
+    if n < 1:
+        raise AgxError(f"{op}: a step takes n >= 1 frames, got {n}")
+    if rate < 1 or delay < 0:
+        raise AgxError(f"{op}: rate = {rate} / delay = {delay}")
+    for name, t in (("src", src), ("dst", dst)):
+        if not isinstance(t, Tensor) or t.dtype != torch.float32 or t.dim() != 3 or not t.is_contiguous():
+            raise AgxError(f"{op}: {name} must be a contiguous float32 (B, C, columns) tensor")
+    b, c, cap = src.shape
+    k = h0.shape[-1]
+    if depth < 0 or tuple(h0.shape) != (c, 1, k) or tuple(h1.shape) != (c, 1, k) or tuple(w.shape) != (c, depth + 2):
+        raise AgxError(f"{op}: parameter shapes do not match (C,1,K) / (C,depth+2) for C={c}, depth={depth}")
+    if any(t.dtype != torch.float32 or not t.is_contiguous() for t in (h0, h1, w)):
+        raise AgxError(f"{op}: h0, h1 and w must be contiguous float32 tensors")
+    reach, cols = multires_stream_reach(k, depth), n * rate
+    if not multires_stream_fits(k, depth, cols):
+        raise AgxError(f"{op}: reach {reach} + a tile of {min(cols, MULTIRES_STREAM_TILE)} columns does not fit "
+                       f"{MULTIRES_STREAM_LDS_BYTES} bytes of LDS")
+    if cap < reach + cols:
+        raise AgxError(f"{op}: src is {tuple(src.shape)} for a ring of at least {reach + cols} columns (the step's writes would alias "
+                       "its history)")
+    if tuple(dst.shape[:2]) != (b, c) or (dst.shape[2] < cols if dst_ring else dst.shape[2] != cols):
+        raise AgxError(f"{op}: dst is {tuple(dst.shape)} for batch {b}, C={c} and {cols} "
+                       + ("new columns of a ring" if dst_ring else "plain columns"))
+    if dst.data_ptr() == src.data_ptr():
+        raise AgxError(f"{op}: the destination is the source")
+    lib = _lib.load()
+    _need_gpu(h0, h1, w, src, dst)
+    if any(t.device != src.device for t in (h0, h1, w, dst)):
+        raise AgxError(f"{op}: operands on different devices")
+    pos = _checked_pos(op, pos, b, src.device)
+    if end is not None:
+        end = _checked_pos(op, end, b, src.device)
+    if counts is not None:
+        counts = _checked_counts(op, counts, b, src.device)
+    tok = None
+    if _observer is not None:
+        tok = _observer.begin("other", (op, 4 * b * c * (reach + 2 * cols), 0))
+    head = (_ptr(h0), _ptr(h1), _ptr(w), _ptr(src), cap, _ptr(dst), dst.shape[2] if dst_ring else 0, _ptr(pos), _ptr(end))
+    if counts is not None:
+        _lib.check(lib.agx_multires_stream_step_counted(*head, _ptr(counts), b, c, n, k, depth, rate, delay, _stream()),
+                   "agx_multires_stream_step_counted")
+    else:
+        _lib.check(lib.agx_multires_stream_step(*head, b, c, n, k, depth, rate, delay, _stream()), "agx_multires_stream_step")
     if tok is not None:
         _observer.end(tok)
     return dst

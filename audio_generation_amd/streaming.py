@@ -36,6 +36,12 @@ Wavelet decoder blocks.  ``plan(..., wavelet_blocks=True)`` / ``mo
 activation, ``CodecStream.dec_hidden``) and ``ops.wavelet_stream_out_step`` (``conv_out`` with the fold formed in its operand fetch
 from that ring, a per-channel table and the stream's ``end``, which decides the reference's raw tail).  Without the keyword such a
 model is refused as before.
+
+Multires layers and depthwise residual blocks.  ``multires_layers=True`` streams a ``CausalMultiresConv1d`` as one
+launch (``ops.multires_stream_step``: the whole cascade on the ring of the layer's input); ``depthwise_blocks=True`` streams a
+residual block built with ``depthwise=True`` as the two launches of a plain one, the per-channel k = 1 conv formed in the dilated
+conv's operand fetch (``ops.conv_stream_step_affine``).  Both are causal: no ring of their own, no delay.  Without the
+keywords such models are refused as before.
 """
 from __future__ import annotations
 
@@ -58,8 +64,9 @@ def _ceil_div(a: int, b: int) -> int:
 
 @dataclass(frozen=True)
 class UnitPlan:
-    """One unit of a stack as a stream runs it.  ``kind``: "causal" | "convt" | "up" | "res" | "wavelet"; ``k, s, d`` of its conv
-    (of the dilated conv of a residual unit; of ``conv_in`` and the fold's scale for a wavelet unit); ``rate_in`` / ``delay_in`` and
+    """One unit of a stack as a stream runs it.  ``kind``: "causal" | "convt" | "up" | "res" | "resdw" | "wavelet" | "multires";
+    ``k, s, d`` of its conv (of the dilated conv of a residual unit; of ``conv_in`` and the fold's scale for a wavelet unit; the
+    taps of a multires unit, whose cascade has ``depth`` levels and ``reach = (k - 1)(2^depth - 1)``); ``rate_in`` / ``delay_in`` and
     ``rate_out`` / ``delay_out`` in columns; ``reach``: input columns it reads before the chunk's first new one; ``cap = reach +
     max_chunk * rate_in``: its ring, so that a step's writes never alias the history the step reads.  A wavelet unit (DESIGN
     4.23) has a second ring, of its hidden activation ``h``: ``hidden`` channels at ``rate_in`` columns per frame, lagging by
@@ -81,6 +88,7 @@ class UnitPlan:
     delay_h: int = 0
     reach_h: int = 0
     cap_h: int = 0
+    depth: int = 0
 
 
 @dataclass(frozen=True)
@@ -127,23 +135,47 @@ def _wavelet_plan(u: Unit, rate: int, delay: int, max_chunk: int) -> UnitPlan:
                     k_in - 1, k_in - 1 + max_chunk * rate, w.hidden_channels, k_out, delay_h, reach_h, reach_h + max_chunk * rate)
 
 
-def _unit_plan(u: Unit, rate: int, delay: int, max_chunk: int, wavelet_blocks: bool = False) -> UnitPlan:
+def _multires_plan(u: Unit, rate: int, delay: int, max_chunk: int) -> UnitPlan:
+    """include/agx.h "Streaming multires layers and depthwise residual blocks": causal, per channel, rate and delay unchanged;
+    reach (K - 1)(2^depth - 1) in the ring of its input."""
+    m = u.layer
+    if u.slope is not None:
+        raise NotImplementedError("streaming: a multires layer with an activation behind its GELU has no step")
+    reach = ops.multires_stream_reach(m.kernel_size, m.depth)
+    if not ops.multires_stream_fits(m.kernel_size, m.depth, max_chunk * rate):
+        raise NotImplementedError(f"streaming: a multires layer with reach {reach} (kernel {m.kernel_size}, depth {m.depth}) at "
+                                  f"{max_chunk * rate} columns per step does not fit the step kernel's "
+                                  f"{ops.MULTIRES_STREAM_LDS_BYTES} bytes of LDS")
+    return UnitPlan("multires", m.channels, m.channels, m.kernel_size, 1, 1, rate, delay, rate, delay, reach, reach + max_chunk * rate,
+                    depth=m.depth)
+
+
+def _unit_plan(u: Unit, rate: int, delay: int, max_chunk: int, wavelet_blocks: bool = False, multires_layers: bool = False,
+               depthwise_blocks: bool = False) -> UnitPlan:
     if u.kind == "wavelet" and wavelet_blocks:
         return _wavelet_plan(u, rate, delay, max_chunk)
-    if u.kind in _REFUSED_UNITS:
+    if u.kind == "multires" and multires_layers:
+        return _multires_plan(u, rate, delay, max_chunk)
+    resdw = u.kind == "resdw" and depthwise_blocks
+    if u.kind in _REFUSED_UNITS and not resdw:
         raise NotImplementedError(f"streaming: {_REFUSED_UNITS[u.kind]}; use the plain or the *_long calls")
-    if u.kind not in ("conv", "res"):
+    if u.kind not in ("conv", "res") and not resdw:
         raise NotImplementedError(f"streaming: no step for a unit of kind {u.kind!r}")
-    c = u.convs[0].conv
+    main = u.convs[1 if resdw else 0]          # a depthwise block's convs: [per-channel k = 1, dilated, k = 1]
+    c = main.conv
     k, s, d = c.kernel_size[0], c.stride[0], c.dilation[0]
-    layer_kind = u.convs[0].kind
-    if u.kind == "res":
-        c2 = u.convs[1].conv
+    layer_kind = main.kind
+    if resdw:
+        dw = u.convs[0].conv
+        if dw.groups != dw.in_channels or dw.in_channels != dw.out_channels or dw.kernel_size[0] != 1 or dw.stride[0] != 1:
+            raise NotImplementedError("streaming: the first conv of a depthwise residual block is a per-channel k = 1 conv")
+    if u.kind == "res" or resdw:
+        c2 = u.convs[-1].conv
         if u.inner_slope is None:
             raise NotImplementedError("streaming: a residual block around an activation the kernels do not fuse")
         if layer_kind != CONV_CAUSAL or s != 1 or c2.kernel_size[0] != 1 or c2.stride[0] != 1:
             raise NotImplementedError("streaming: a residual block is a stride-1 causal conv and a k = 1 conv")
-        kind, reach, rate_out, delay_out = "res", d * (k - 1), rate, delay
+        kind, reach, rate_out, delay_out = u.kind, d * (k - 1), rate, delay
     elif layer_kind == CONV_CAUSAL:
         reach = d * (k - 1) - s + 1
         if rate % s or delay % s:
@@ -166,9 +198,11 @@ def _unit_plan(u: Unit, rate: int, delay: int, max_chunk: int, wavelet_blocks: b
                     reach + max_chunk * rate)
 
 
-def plan(model, max_chunk: int, wavelet_blocks: bool = False) -> StreamPlan:
+def plan(model, max_chunk: int, wavelet_blocks: bool = False, multires_layers: bool = False,
+         depthwise_blocks: bool = False) -> StreamPlan:
     """Derived from the model's unit lists as they are wired; raises ``NotImplementedError`` for what a stream does not cover.
-    ``wavelet_blocks``: plan the wavelet decoder blocks instead of refusing them."""
+    ``wavelet_blocks``: plan the wavelet decoder blocks instead of refusing them; ``multires_layers`` /
+    ``depthwise_blocks``: likewise the multires layers and the depthwise residual blocks."""
     from .quantizer import ResidualQuantizer
     max_chunk = int(max_chunk)
     if max_chunk < 1:
@@ -181,7 +215,7 @@ def plan(model, max_chunk: int, wavelet_blocks: bool = False) -> StreamPlan:
     for which, rate in (("encoders", sf), ("decoders", 1)):
         delay, out = 0, []
         for u in model._units(which):
-            p = _unit_plan(u, rate, delay, max_chunk, wavelet_blocks)
+            p = _unit_plan(u, rate, delay, max_chunk, wavelet_blocks, multires_layers, depthwise_blocks)
             out.append(p)
             rate, delay = p.rate_out, p.delay_out
         if rate != (1 if which == "encoders" else sf):
@@ -198,13 +232,15 @@ class CodecStream:
     ``end``: the frame at which a row's stream ended, ``ops.STREAM_LIVE`` while it is live.  All int64 (B,) on the device, read by
     the kernels and advanced by a kernel.  ``decoder_delay``: samples by which ``decode_stream``'s output lags.
     ``wavelet_blocks=True``: the wavelet decoder blocks stream too; ``dec_hidden[i]`` is the ring (B, hidden, cap_h)
-    of unit ``i``'s hidden activation, None for every other unit -- ``dec_rings`` stays one ring per unit."""
+    of unit ``i``'s hidden activation, None for every other unit -- ``dec_rings`` stays one ring per unit.
+    ``multires_layers=True`` / ``depthwise_blocks=True``: those units stream too, on the ring of their input alone."""
 
-    def __init__(self, model, batch: int, max_chunk: int, device=None, wavelet_blocks: bool = False):
+    def __init__(self, model, batch: int, max_chunk: int, device=None, wavelet_blocks: bool = False, multires_layers: bool = False,
+                 depthwise_blocks: bool = False):
         batch = int(batch)
         if batch < 1:
             raise AgxError(f"new_stream: batch = {batch} < 1")
-        self.plan = plan(model, max_chunk, wavelet_blocks)
+        self.plan = plan(model, max_chunk, wavelet_blocks, multires_layers, depthwise_blocks)
         self.model_id = id(model)
         self.batch, self.max_chunk = batch, self.plan.max_chunk
         self.scale_factor, self.decoder_delay = self.plan.scale_factor, self.plan.decoder_delay
@@ -281,12 +317,32 @@ def fold_table(layer) -> Tensor:
     return slot[1]
 
 
+def depthwise_affine(layer) -> tuple:
+    """(scale, shift) of a depthwise residual block's per-channel k = 1 conv ``layer`` for ``ops.conv_stream_step_affine``: the
+    weight-norm folded weights as the plain call's image holds them (row ``c`` of the grouped image, ``ops.conv_pack``) and the
+    bias (zeros without one).  Kept on the layer and rebuilt when ``data_ptr`` / ``_version`` of its parameters change -- the rule
+    of ``units.packed_image`` -- so that a changed weight is seen and a captured step keeps its pointers."""
+    c = layer.conv
+    v, g = c.weights()
+    key = tuple(k for t in (v, g, c.bias) if t is not None for k in (t.data_ptr(), t._version))
+    slot = layer.__dict__.get("_stream_affine")
+    if slot is None or slot[0] != key:
+        n = c.in_channels
+        image = c.packed(layer.kind)                         # ((g J + j) M + m) x 16 with one channel per group: row m, column 0
+        scale = image[:n * 16].reshape(n, 16)[:, 0].contiguous()
+        shift = c.bias.detach() if c.bias is not None else torch.zeros_like(scale)
+        slot = (key, (scale, shift))
+        layer.__dict__["_stream_affine"] = slot
+    return slot[1]
+
+
 def run_unit(u: Unit, p: UnitPlan, ring: Tensor, dst: Tensor, dst_ring: bool, pos: Tensor, end: Optional[Tensor], n: int,
              counts: Optional[Tensor] = None, hidden: Optional[Tensor] = None) -> Tensor:
     """One unit's step: ``ring`` -> ``dst``.  A conv is one launch; a residual unit is two, its hidden activation (which only the
     k = 1 conv at the same column reads, so it needs no mask and no history) in a plain scratch tensor.  ``counts``: the counted
     launches (the hidden activation is exact 0 behind a row's count).  A wavelet unit is two: the in-step into ``hidden``, the
-    ring of its hidden activation, and the out-step, which folds on the fly."""
+    ring of its hidden activation, and the out-step, which folds on the fly.  A multires unit is one launch; a
+    depthwise residual unit is the two of a plain one, the first with the per-channel affine in its operand fetch."""
     post = u.slope
     if p.kind == "wavelet":
         w = u.layer
@@ -298,11 +354,22 @@ def run_unit(u: Unit, p: UnitPlan, ring: Tensor, dst: Tensor, dst_ring: bool, po
                                            detached(w.conv_out.bias), fold_table(w), hidden, dst, pos, end, n, p.rate_in, p.delay_h,
                                            dst_ring=dst_ring, epilogue=EPI_LEAKY_PRE if post is not None else 0, slope=post or 0.0,
                                            counts=counts)
-    if p.kind == "res":
-        c1, c2 = u.convs[0], u.convs[1]
+    if p.kind == "multires":
+        m = u.layer
+        return ops.multires_stream_step(m.h0.detach(), m.h1.detach(), m.w.detach(), p.depth, ring, dst, pos, n, p.rate_in, p.delay_in,
+                                        dst_ring=dst_ring, end=end, counts=counts)
+    if p.kind in ("res", "resdw"):
+        c1, c2 = u.convs[-2], u.convs[-1]
         hid = torch.empty((ring.shape[0], c1.conv.out_channels, n * p.rate_in), dtype=torch.float32, device=ring.device)
-        ops.conv_stream_step(CONV_CAUSAL, p.c_in, c1.conv.out_channels, p.k, 1, p.d, _image(c1), detached(c1.conv.bias), ring, hid, pos,
-                             n, p.rate_in, p.delay_in, dst_ring=False, epilogue=EPI_LEAKY_PRE, slope=u.inner_slope, counts=counts)
+        if p.kind == "resdw":
+            scale, shift = depthwise_affine(u.convs[0])
+            ops.conv_stream_step_affine(p.c_in, c1.conv.out_channels, p.k, p.d, _image(c1), detached(c1.conv.bias), scale, shift, ring, hid,
+                                        pos, n, p.rate_in, p.delay_in, dst_ring=False, epilogue=EPI_LEAKY_PRE, slope=u.inner_slope,
+                                        counts=counts)
+        else:
+            ops.conv_stream_step(CONV_CAUSAL, p.c_in, c1.conv.out_channels, p.k, 1, p.d, _image(c1), detached(c1.conv.bias), ring, hid,
+                                 pos, n, p.rate_in, p.delay_in, dst_ring=False, epilogue=EPI_LEAKY_PRE, slope=u.inner_slope,
+                                 counts=counts)
         return ops.conv_stream_step(CONV_CAUSAL, c1.conv.out_channels, p.c_out, 1, 1, 1, _image(c2), detached(c2.conv.bias), hid, dst, pos,
                                     n, p.rate_in, p.delay_in, src_ring=False, dst_ring=dst_ring, res=ring, end=end,
                                     epilogue=EPI_RESIDUAL | (EPI_LEAKY_POST if post is not None else 0), slope=post or 0.0,

@@ -539,11 +539,14 @@ class CausalVQAE(nn.Module):
         return longform.forward_long(self, x, segment_frames, codebook_n)
 
     # -- streaming on per-layer conv state rings (build-defined; streaming.py) -------------------
-    def new_stream(self, batch: int, max_chunk: int = 4, device=None, wavelet_blocks: bool = False):
+    def new_stream(self, batch: int, max_chunk: int = 4, device=None, wavelet_blocks: bool = False, multires_layers: bool = False,
+                   depthwise_blocks: bool = False):
         """A ``CodecStream`` for ``batch`` live streams that advance by 1 .. ``max_chunk`` latent frames per call.
-        ``wavelet_blocks=True``: wavelet decoder blocks stream too; without it such a model is refused."""
+        ``wavelet_blocks=True``: wavelet decoder blocks stream too; without it such a model is refused.
+        ``multires_layers=True`` / ``depthwise_blocks=True``: likewise the multires layers and the residual blocks built with
+        ``depthwise=True``."""
         from . import streaming
-        return streaming.CodecStream(self, batch, max_chunk, device, wavelet_blocks)
+        return streaming.CodecStream(self, batch, max_chunk, device, wavelet_blocks, multires_layers, depthwise_blocks)
 
     def encode_stream(self, x_chunk, stream, codebook_n=None, counts=None):
         """``encode`` of the next ``n`` whole frames of every row -> (zq (B, D, n), commit_loss, index (B, n, Q)); the conv state

@@ -1284,6 +1284,54 @@ int agx_wavelet_stream_in_kernel_name(int32_t c_in, int32_t hidden, int32_t kern
 int agx_wavelet_stream_out_kernel_name(int32_t hidden, int32_t c_out, int32_t kernel, int32_t scale, int32_t n, int32_t rate_h, char *buf,
                                        size_t buf_len);
 
+/* ---- Streaming multires layers and depthwise residual blocks (csrc/multires_stream.hip, csrc/conv_stream.hip) -----
+ * Both keep state only in the ring of their own input, in the terms of "Streaming conv stacks"; rate_out = rate_in and
+ * delay_out = delay_in for both.
+ *
+ * agx_multires_stream_step: one chunk of n frames of a (B, C, src_cap) ring through the whole cascade of agx_multires_forward,
+ * one launch.  With j = pos[b] rate - delay + t the stream index of output column t < n rate:
+ *     lo_0 = x;  level lvl = depth .. 1 has dilation dil = 2^(depth - lvl):
+ *         hi_lvl[j] = sum_k h1[c, k] lo[j - (K - 1 - k) dil],  lo'[j] = sum_k h0[c, k] lo[j - (K - 1 - k) dil]
+ *     (each an fmaf chain from 0 over the taps in ascending k), and
+ *     y[c, j] = gelu(fmaf(x[c, j], w[c, depth + 1], fmaf(w[c, 0], lo_depth[c, j], acc))),
+ *     acc = fmaf(w[c, 1], hi_1, .. fmaf(w[c, depth], hi_depth, 0)) -- the order of agx_multires_forward, the same erf GELU.
+ * reach = (K - 1)(2^depth - 1); src_cap >= reach + n rate.  Input columns of stream index < 0 are 0 in the ring (it starts
+ * zero-filled and every producer stores exact 0 there), so the cascade needs no select on the index.  An output with j < 0 or
+ * j >= end[b] rate is stored as exact 0 (end == NULL: no mask).  dst: the consumer's ring (dst_cap >= n rate, written at
+ * j mod dst_cap) or, dst_cap == 0, a plain (B, C, n rate) tensor.  Work is packed by outputs: a workgroup of 256 threads owns
+ * R = max(1, 256 / tile) channel rows of one batch entry and one tile of min(n rate, AGX_MULTIRES_STREAM_TILE) columns, with
+ * the reach as left halo, two LDS rows per channel row; the chain of an output does not depend on R, the tile, n or the ring
+ * phase.  The counted form follows "Per-row frame counts": no source column behind a row's count is read.
+ * Refused before any launch or use of a pointer: K < 1, depth outside 0 .. 20, a reach + tile whose two LDS rows and taps
+ * exceed AGX_MULTIRES_STREAM_LDS_BYTES (AGX_ERR_UNSUPPORTED), src_cap < reach + n rate, 0 < dst_cap < n rate, dst == src,
+ * NULL pointers, sizes beyond the grid.  batch or n <= 0: AGX_OK, nothing launched. */
+#define AGX_MULTIRES_STREAM_TILE 1024
+#define AGX_MULTIRES_STREAM_LDS_BYTES 65536
+int agx_multires_stream_step(const float *h0, const float *h1, const float *w, const float *src, int32_t src_cap, float *dst,
+                             int32_t dst_cap, const int64_t *pos, const int64_t *end, int32_t batch, int32_t channels, int32_t n,
+                             int32_t kernel, int32_t depth, int32_t rate, int64_t delay, void *stream);
+int agx_multires_stream_step_counted(const float *h0, const float *h1, const float *w, const float *src, int32_t src_cap, float *dst,
+                                     int32_t dst_cap, const int64_t *pos, const int64_t *end, const int64_t *counts, int32_t batch,
+                                     int32_t channels, int32_t n, int32_t kernel, int32_t depth, int32_t rate, int64_t delay,
+                                     void *stream);
+/* agx_conv_stream_step with a per-channel affine in the operand fetch -- the dilated conv of a depthwise residual block, whose
+ * grouped k = 1 conv (folded weight scale[c], bias shift[c]) is never stored.  The operand of channel c at stream column i is
+ *     i >= 0 && c < c_in ? fmaf(scale[c], x[c, i], shift[c]) : 0
+ * a select on the index, never a product with 0: before the start of the stream the conv sees its own zero padding, not the
+ * affine's bias, and the channels that pad the last group of 16 give 0.  Everything else -- the image, the chain of an output,
+ * the epilogue, the mask, the kernel choice -- is agx_conv_stream_step's.  AGX_CONV_CAUSAL with stride 1 from a ring only
+ * (src_cap > 0): everything else is AGX_ERR_UNSUPPORTED; scale or shift NULL: AGX_ERR_NULL_POINTER. */
+int agx_conv_stream_step_affine(int32_t kind, int32_t c_in, int32_t c_out, int32_t kernel, int32_t stride, int32_t dilation,
+                                int32_t epilogue, float slope, const float *packed, const float *bias, const float *scale,
+                                const float *shift, const float *src, int32_t src_cap, const float *res, int32_t res_cap, float *dst,
+                                int32_t dst_cap, const int64_t *pos, const int64_t *end, int32_t batch, int32_t n, int32_t rate_in,
+                                int64_t delay_in, void *stream);
+int agx_conv_stream_step_affine_counted(int32_t kind, int32_t c_in, int32_t c_out, int32_t kernel, int32_t stride, int32_t dilation,
+                                        int32_t epilogue, float slope, const float *packed, const float *bias, const float *scale,
+                                        const float *shift, const float *src, int32_t src_cap, const float *res, int32_t res_cap,
+                                        float *dst, int32_t dst_cap, const int64_t *pos, const int64_t *end, const int64_t *counts,
+                                        int32_t batch, int32_t n, int32_t rate_in, int64_t delay_in, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

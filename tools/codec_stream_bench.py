@@ -35,6 +35,19 @@ a kernel trace of its own; ``--wavelet-stats CSV`` prints the rows of such a tra
     rocprofv3 --kernel-trace --stats --output-format csv -d OUT -o wv -- python tools/codec_stream_bench.py --wavelet-steps
     python tools/codec_stream_bench.py --wavelet-stats OUT/.../wv_kernel_stats.csv >> profiles/wavelet_stream.txt
 
+``--multires`` / ``--depthwise`` measure a streamed hop of a model with multires layers (the config-4 model of
+tests/test_gpu_blocks.py: strides 2 4 5 8, stereo, one wavelet block, multires layers k = 3, depth = 4 in two encoder and two decoder
+blocks) resp. with depthwise residual blocks (config S built with ``depthwise=True``), DESIGN 4.24, by the same protocol at
+B in {1, 32}: (b) ``model.forward`` on the receptive field -- what a live user of the plain calls re-runs per hop -- beside (a) the
+``forward_stream`` step of a stream made with the keywords and (a0) the step of the same model WITHOUT those units, which is what the
+units add to a hop.  ``--multires-steps`` / ``--depthwise-steps`` run 100 eager steps per (B, n) of (a) and of (a0) and nothing
+else, for a kernel trace; ``--wavelet-stats CSV`` prints the stream's rows of such a trace too:
+
+    python tools/codec_stream_bench.py --multires > profiles/multires_depthwise_stream.txt
+    python tools/codec_stream_bench.py --depthwise >> profiles/multires_depthwise_stream.txt
+    rocprofv3 --kernel-trace --stats --output-format csv -d OUT -o mr -- python tools/codec_stream_bench.py --multires-steps
+    python tools/codec_stream_bench.py --wavelet-stats OUT/.../mr_kernel_stats.csv >> profiles/multires_depthwise_stream.txt
+
     python tools/codec_stream_bench.py [--plain-only] > profiles/codec_stream.txt
     python tools/codec_stream_bench.py --counts > profiles/stream_counts.txt
     python tools/codec_stream_bench.py --wire > profiles/rvq_step.txt
@@ -323,14 +336,94 @@ def wavelet_stats(path):
     """The rows of a kernel-statistics CSV (Name, Calls, TotalDurationNs, AverageNs, ...) that belong to the streamed decoder."""
     import csv
     rows = [r for r in csv.DictReader(open(path)) if any(k in r["Name"] for k in ("conv_stream_kernel", "wavelet", "ring_write_rate",
-                                                                                  "stream_advance"))]
+                                                                                  "stream_advance", "multires_stream"))]
     rows.sort(key=lambda r: -float(r["TotalDurationNs"]))
-    print("\nkernel statistics of 800 eager decode_stream steps (B in {1, 8} x n in {1, 4}); template arguments <KS, NT, CNT, FOLD>, "
-          "FOLD = true is the wavelet out-step")
+    print("\nkernel statistics of the eager steps of a stream; template arguments <KS, NT, CNT, FOLD, AFF>: FOLD = true is the wavelet "
+          "out-step, AFF = true the dilated conv of a depthwise block")
     print(f"  {'calls':>7} {'average us':>11} {'min us':>9} {'max us':>9}  kernel")
     for r in rows:
         print(f"  {int(r['Calls']):>7} {float(r['AverageNs']) / 1e3:>11.2f} {float(r['MinNs']) / 1e3:>9.2f} {float(r['MaxNs']) / 1e3:>9.2f}  "
               f"{r['Name'][:150]}")
+
+
+CONFIG4 = dict(in_channels=2, n_blocks=4, strides=(2, 4, 5, 8), num_quantizers=2, codebook_size=64, codebook_dim=512, input_format="n c l",
+               wavelet_decoders=[False, True, False, False])
+CONFIG4_MULTIRES = dict(multires_encoders=[True, False, True, False], multires_decoders=[False, False, True, True], multires_kernel_size=3,
+                        multires_depth=4)
+CONFIG_S = dict(in_channels=1, n_blocks=4, strides=(2, 4, 5, 8), num_quantizers=8, codebook_size=1024, codebook_dim=512,
+                input_format="n c l", wavelet_decoders=False)
+UNIT_BATCHES = (1, 32)
+
+
+def _unit_models(which, dev):
+    """(model with the units, the same model without them, the keywords of their streams) for ``which`` in "multires" / "depthwise"."""
+    base, extra = (CONFIG4, CONFIG4_MULTIRES) if which == "multires" else (CONFIG_S, dict(depthwise=True))
+    models = []
+    for kw in (dict(base, **extra), base):
+        torch.manual_seed(0)
+        model = CausalVQAE(**kw).eval().to(dev)
+        x = (0.1 * torch.randn(2, base["in_channels"], 36000, generator=torch.Generator().manual_seed(1234))).clamp(-1, 1).to(dev)
+        with torch.no_grad():
+            model.quantizer.init_from_latents(model._run_encoders(model.rearrange_in(x)))
+        models.append(model)
+    return models[0], models[1], dict(wavelet_blocks=True, multires_layers=True, depthwise_blocks=True), dict(wavelet_blocks=True)
+
+
+def unit_hop(which, dev, gen):
+    """A streamed hop of a model with multires layers / depthwise blocks beside the plain forward on its receptive field and beside
+    the streamed hop of the same model without those units."""
+    from audio_generation_amd import streaming
+    model, bare, kw, kw0 = _unit_models(which, dev)
+    sf, c = model.scale_factor, model.in_channels
+    plan, plan0 = streaming.plan(model, 4, **kw), streaming.plan(bare, 4, **kw0)
+    enc_left = -(-plan.enc_left // sf)
+    left, right = _decoder_left_halo(plan), plan.flush_frames
+    mine = [u for u in (*plan.encoders, *plan.decoders) if u.kind in ("multires", "resdw")]
+    launches = lambda p: sum(2 if u.kind in ("res", "resdw", "wavelet") else 1 for u in (*p.encoders, *p.decoders))     # noqa: E731
+    print(f"{which}: {len(mine)} such units; encoder left halo {enc_left} frames, decoder left halo {left}, right {right}; step launches "
+          f"per hop {launches(plan)} with the units, {launches(plan0)} without")
+    if which == "multires":
+        for u in mine:
+            print(f"  multires C={u.c_in} k={u.k} depth={u.depth} reach {u.reach} at {u.rate_in} columns per frame, delay {u.delay_in}")
+    verdicts = []
+    for b in UNIT_BATCHES:
+        for n in (1, 4):
+            frames = enc_left + left + n + right
+            window = (0.1 * torch.randn(b, c, frames * sf, generator=gen)).to(dev)
+            chunk = window[:, :, :n * sf].contiguous()
+            stream, stream0 = model.new_stream(b, max_chunk=4, **kw), bare.new_stream(b, max_chunk=4, **kw0)
+            plain = lambda: model(window)                                           # noqa: E731
+            cases = [(f"(b) model.forward on {frames} frames", plain),
+                     ("(a) forward_stream step", lambda: model.forward_stream(chunk, stream)),
+                     ("(a0) forward_stream step, the model without the units", lambda: bare.forward_stream(chunk, stream0)),
+                     (f"(b) model.forward on {frames} frames (again)", plain)]
+            times = measure(cases, STEPS_PER_GRAPH)
+            print(f"\nB = {b}, n = {n} new frames: the hop lasts {1e6 * n * sf / SAMPLE_RATE:.0f} us of audio")
+            show(times)
+            names = list(times)
+            b1, a, a0, b2 = (times[k] for k in names)
+            ok = max(a) < min(b1 + b2)
+            verdicts.append(ok)
+            print(f"  (b) / (a) = {min(statistics.median(b1), statistics.median(b2)) / statistics.median(a):.2f}; (a)'s slowest round below "
+                  f"(b)'s fastest: {'yes' if ok else 'NO'}; (a) - (a0) = {statistics.median(a) - statistics.median(a0):.2f} us for "
+                  f"{launches(plan) - launches(plan0)} more launches")
+    print(f"\n(a) below (b) by more than the spread: {sum(verdicts)} of {len(verdicts)} cases")
+
+
+def unit_steps(which, dev, gen):
+    """100 eager steps per (B, n) of the stream with the units and of the one without, and nothing else: the body of a kernel trace."""
+    model, bare, kw, kw0 = _unit_models(which, dev)
+    sf, c = model.scale_factor, model.in_channels
+    with torch.no_grad():
+        for b in UNIT_BATCHES:
+            for n in (1, 4):
+                chunk = (0.1 * torch.randn(b, c, n * sf, generator=gen)).to(dev)
+                for m, k in ((model, kw), (bare, kw0)):
+                    stream = m.new_stream(b, max_chunk=4, **k)
+                    for _ in range(100):
+                        m.forward_stream(chunk, stream)
+    torch.cuda.synchronize()
+    print(f"{which}: 100 forward_stream steps per (B, n), B in {UNIT_BATCHES} x n in (1, 4), with the units and without")
 
 
 def main():
@@ -341,12 +434,25 @@ def main():
     ap.add_argument("--wavelet", action="store_true", help="a streamed decoder hop of the reference default architecture (wavelet block)")
     ap.add_argument("--wavelet-steps", action="store_true", help="eager steps of that stream only: the body of a kernel trace")
     ap.add_argument("--wavelet-stats", metavar="CSV", help="print the stream's rows of a kernel-statistics CSV; needs no GPU")
+    for which in ("multires", "depthwise"):
+        ap.add_argument(f"--{which}", action="store_true", help=f"a streamed hop of a model with {which} units (DESIGN 4.24)")
+        ap.add_argument(f"--{which}-steps", action="store_true", help="eager steps of those streams only: the body of a kernel trace")
     args = ap.parse_args()
     if args.wavelet_stats is not None:
         wavelet_stats(args.wavelet_stats)
         return
     assert torch.cuda.is_available(), "needs the MI355X"
     dev = "cuda"
+    for which in ("multires", "depthwise"):
+        if getattr(args, which) or getattr(args, which + "_steps"):
+            gen = torch.Generator().manual_seed(0)
+            if getattr(args, which + "_steps"):
+                unit_steps(which, dev, gen)
+                return
+            print(f"device: {torch.cuda.get_device_name(0)}; per-call time over {ROUNDS} replays of a graph of {STEPS_PER_GRAPH} back-to-back "
+                  f"calls (median [min .. max]); --{which}")
+            unit_hop(which, dev, gen)
+            return
     if args.wavelet or args.wavelet_steps:
         gen = torch.Generator().manual_seed(0)
         if args.wavelet_steps:
