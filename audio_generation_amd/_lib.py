@@ -310,6 +310,15 @@ SIGNATURES = {
     "agx_rvq_step_decode": (c_int, [c_void_p, c_int32, c_void_p, c_void_p, c_void_p,
                                     c_int32, c_int32, c_int32, c_int32, c_int32, c_int32,
                                     c_void_p, c_int64, c_int64, c_int64, c_void_p, c_void_p]),
+    # per-row stage counts: `stages` after `counts`
+    "agx_rvq_step_encode_staged": (c_int, [c_void_p, c_int64, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_void_p,
+                                           c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32,
+                                           c_void_p, c_int64, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "agx_rvq_step_decode_staged": (c_int, [c_void_p, c_int32, c_void_p, c_void_p, c_void_p, c_void_p,
+                                           c_int32, c_int32, c_int32, c_int32, c_int32, c_int32,
+                                           c_void_p, c_int64, c_int64, c_int64, c_void_p, c_void_p]),
+    "agx_rvq_packets_restage": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32,
+                                        c_void_p, c_void_p, c_void_p]),
     # streaming wavelet blocks
     "agx_wavelet_fold_table": (c_int, [c_void_p, c_void_p, c_int32, c_void_p, c_int32, c_int32, c_int32, c_void_p]),
     "agx_wavelet_stream_in_step": (c_int, [c_int32, c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_int32, c_void_p, c_int32, c_void_p,

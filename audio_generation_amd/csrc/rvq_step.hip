@@ -11,6 +11,10 @@
 // rvq_step_output_kernel, one workgroup per row, combines the last stage and writes index, zq and the row's packet.
 //
 // Decode: rvq_step_decode_kernel, one workgroup per frame: the frame's codes out of the row's packet, then the stage-order sum.
+//
+// Per-row stage counts: every kernel reads q_b = clamp(stages[b], 0, Q) through step_stages, beside the frame count
+// (NULL: Q, the plain entry points).  Stage q of row b is searched, stored, packed and summed only when q < q_b; the row's packet is
+// dense over its own q_b.  rvq_packets_restage_kernel, one workgroup per row, re-packs a row to fewer stages: a bit gather.
 #include "common.hpp"
 
 // the whole file is the defining arithmetic or plain sums: nothing here may be fused
@@ -45,6 +49,13 @@ __device__ __forceinline__ int step_count(const int64_t *__restrict__ counts, in
     if (!counts) return n;
     const int64_t c = counts[b];
     return c < 0 ? 0 : (c > n ? n : int(c));
+}
+
+// q_b of row b: the stages it sends (include/agx.h "Per-row stage counts"); a null pointer is every stage of the launch
+__device__ __forceinline__ int step_stages(const int64_t *__restrict__ stages, int b, int Q) {
+    if (!stages) return Q;
+    const int64_t s = stages[b];
+    return s < 0 ? 0 : (s > Q ? Q : int(s));
 }
 
 // (distance, index) minimum over the wave, the lowest index on equal distance: a butterfly, every lane ends with the result
@@ -135,6 +146,7 @@ struct RvqStepArgs {
     int64_t z_sb, z_st, z_sd;
     const float *cb;          // (Q_total, K, D)
     const int64_t *counts;    // (B,) or null
+    const int64_t *stages;    // (B,) or null
     int n, D, K, Q;
     unsigned char *ws;
     RvqStepWs map;
@@ -150,6 +162,7 @@ __global__ __launch_bounds__(64) void rvq_step_search_kernel(RvqStepArgs a, int 
     const int j = blockIdx.y;
     const int b = int(f / a.n), t = int(f % a.n);
     if (t >= step_count(a.counts, b, a.n)) return;     // a dead frame: nothing of it is loaded
+    if (q >= step_stages(a.stages, b, a.Q)) return;    // a stage the row does not send: likewise, and the row's last partials stay
     const int kq = a.sizes.n[q];
     if (j * STEP_CW >= kq) return;                      // a short stage: no codeword here, and no partial is read for this block
     const int nb_max = (a.K + STEP_CW - 1) / STEP_CW;
@@ -194,6 +207,7 @@ __global__ __launch_bounds__(64) void rvq_step_search_kernel(RvqStepArgs a, int 
 struct RvqStepOutArgs {
     const float *cb;
     const int64_t *counts;
+    const int64_t *stages;
     int n, D, K, Q, bits;
     float *zq;
     int64_t q_sb, q_st, q_sd;
@@ -219,45 +233,55 @@ __device__ __forceinline__ unsigned step_packet_byte(const int *codes, int n_cod
     return v & 0xffu;
 }
 
-// one workgroup per row: grid (B), 256 threads, n Q ints of dynamic LDS
+// one workgroup per row: grid (B), 256 threads, n Q ints of dynamic LDS.  The row's codes lie in LDS dense over its own q_b
+// stages, as its packet holds them; its last live stage q_b - 1 is combined here, from the slot that stage's launch wrote.
 __global__ __launch_bounds__(256) void rvq_step_output_kernel(RvqStepOutArgs a) {
     extern __shared__ __align__(16) int step_codes[];
     const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int cnt = step_count(a.counts, b, a.n);
-    const int Q = a.Q;
-    if (Q > 0) {
+    const int qb = step_stages(a.stages, b, a.Q);
+    if (qb > 0) {
         const int nb_max = (a.K + STEP_CW - 1) / STEP_CW;
         const double *pd = reinterpret_cast<const double *>(a.ws + a.map.pd);
         const int32_t *pi = reinterpret_cast<const int32_t *>(a.ws + a.map.pi);
         const int32_t *codes = reinterpret_cast<const int32_t *>(a.ws + a.map.codes);
-        const int kl = a.sizes.n[Q - 1];
+        const int kl = a.sizes.n[qb - 1];
         for (int t = wave; t < cnt; t += 4) {              // live frames only: nothing of a dead frame's workspace is read
             const int64_t f = int64_t(b) * a.n + t;
-            const size_t slot = size_t((Q - 1) & 1) * size_t(a.F) + size_t(f);
+            const size_t slot = size_t((qb - 1) & 1) * size_t(a.F) + size_t(f);
             const int last = step_combine(pd + slot * nb_max, pi + slot * nb_max, (kl + STEP_CW - 1) / STEP_CW, kl, lane);
-            for (int q = lane; q < Q; q += 64) {
-                const int code = q == Q - 1 ? last : codes[size_t(f) * Q + q];
-                step_codes[t * Q + q] = code >= 0 && code < a.sizes.n[q] ? code : 0;   // (in bounds whatever the workspace held)
+            for (int q = lane; q < qb; q += 64) {
+                const int code = q == qb - 1 ? last : codes[size_t(f) * a.Q + q];
+                step_codes[t * qb + q] = code >= 0 && code < a.sizes.n[q] ? code : 0;   // (in bounds whatever the workspace held)
             }
         }
     }
     __syncthreads();
-    for (int e = tid; e < a.n * Q; e += 256)
-        a.index[size_t(b) * a.n * Q + e] = e < cnt * Q ? int64_t(step_codes[e]) : int64_t(-1);
+    for (int e = tid; e < a.n * a.Q; e += 256) {
+        const int t = e / a.Q, q = e % a.Q;
+        a.index[size_t(b) * a.n * a.Q + e] = t < cnt && q < qb ? int64_t(step_codes[t * qb + q]) : int64_t(-1);
+    }
     if (a.zq) {
         for (int e = tid; e < a.n * a.D; e += 256) {
             const int t = e / a.D, d = e % a.D;
             float acc = 0.f;
             if (t < cnt)
-                for (int q = 0; q < Q; ++q) acc = acc + a.cb[(size_t(q) * a.K + size_t(step_codes[t * Q + q])) * a.D + d];
+                for (int q = 0; q < qb; ++q) acc = acc + a.cb[(size_t(q) * a.K + size_t(step_codes[t * qb + q])) * a.D + d];
             a.zq[b * a.q_sb + t * a.q_st + d * a.q_sd] = acc;
         }
     }
     if (a.packets) {
-        const int live_bytes = (cnt * Q * a.bits + 7) / 8;
+        const int live_bytes = (cnt * qb * a.bits + 7) / 8;
         for (int i = tid; i < a.P; i += 256)
-            a.packets[size_t(b) * a.P + i] = i < live_bytes ? (unsigned char)step_packet_byte(step_codes, cnt * Q, a.bits, i) : (unsigned char)0;
+            a.packets[size_t(b) * a.P + i] = i < live_bytes ? (unsigned char)step_packet_byte(step_codes, cnt * qb, a.bits, i) : (unsigned char)0;
     }
+}
+
+// the `bits`-bit code that starts at bit `bit0` of a packet row; reads the bytes that hold it and no other
+__device__ __forceinline__ unsigned step_read_code(const unsigned char *__restrict__ row, int bit0, int bits) {
+    unsigned v = 0;
+    for (int o = bit0 >> 3, s = 0; o <= (bit0 + bits - 1) >> 3; ++o, s += 8) v |= unsigned(row[o]) << s;
+    return (v >> (bit0 & 7)) & ((1u << bits) - 1u);
 }
 
 struct RvqStepDecArgs {
@@ -265,6 +289,7 @@ struct RvqStepDecArgs {
     int P, bits;
     const float *cb;
     const int64_t *counts;
+    const int64_t *stages;
     int n, D, K, Q;
     float *zq;
     int64_t q_sb, q_st, q_sd;
@@ -278,16 +303,12 @@ __global__ __launch_bounds__(256) void rvq_step_decode_kernel(RvqStepDecArgs a) 
     const int64_t f = blockIdx.x;
     const int b = int(f / a.n), t = int(f % a.n), tid = threadIdx.x;
     const int cnt = step_count(a.counts, b, a.n);
+    const int qb = step_stages(a.stages, b, a.Q);
     const bool live = t < cnt;
     if (tid < a.Q) {
         int code = -1;
-        if (live) {                                        // bits of a live code lie inside the row's first ceil(c_b Q bits / 8) bytes
-            const int bit0 = (t * a.Q + tid) * a.bits;
-            const unsigned char *row = a.packets + size_t(b) * a.P;
-            unsigned v = 0;
-            for (int o = bit0 >> 3, s = 0; o <= (bit0 + a.bits - 1) >> 3; ++o, s += 8) v |= unsigned(row[o]) << s;
-            code = int((v >> (bit0 & 7)) & ((1u << a.bits) - 1u));
-        }
+        if (live && tid < qb)                              // bits of a live code lie inside the row's first ceil(c_b q_b bits / 8) bytes
+            code = int(step_read_code(a.packets + size_t(b) * a.P, (t * qb + tid) * a.bits, a.bits));
         codes[tid] = code;
         if (a.index) a.index[size_t(f) * a.Q + tid] = int64_t(code);
     }
@@ -295,11 +316,48 @@ __global__ __launch_bounds__(256) void rvq_step_decode_kernel(RvqStepDecArgs a) 
     for (int d = tid; d < a.D; d += 256) {
         float acc = 0.f;
         if (live)
-            for (int q = 0; q < a.Q; ++q) {
+            for (int q = 0; q < qb; ++q) {
                 const int code = codes[q];
                 if (code < a.sizes.n[q]) acc = acc + a.cb[(size_t(q) * a.K + size_t(code)) * a.D + d];   // a code past the stage adds and reads nothing
             }
         a.zq[b * a.q_sb + t * a.q_st + d * a.q_sd] = acc;
+    }
+}
+
+struct RvqRestageArgs {
+    const unsigned char *in;        // (B, P)
+    const int64_t *stages_in;       // (B,) or null: Q
+    const int64_t *stages_to;       // (B,)
+    const int64_t *counts;          // (B,) or null
+    int n, Q, bits, P;
+    unsigned char *out;             // (B, P), no byte shared with `in`
+    int64_t *stages_out;            // (B,) or null
+};
+
+// one workgroup per row: grid (B), 256 threads.  Output byte i collects the codes whose bits it holds -- code e of the output is
+// stage e % q_out of frame e / q_out, which the input holds at bit ((e / q_out) q_in + e % q_out) bits.  q_out <= q_in and the frame
+// lies below the count, so every bit read lies inside the row's first ceil(c_b q_in bits / 8) input bytes.
+__global__ __launch_bounds__(256) void rvq_packets_restage_kernel(RvqRestageArgs a) {
+    const int b = blockIdx.x, tid = threadIdx.x;
+    const int cnt = step_count(a.counts, b, a.n);
+    const int q_in = step_stages(a.stages_in, b, a.Q);
+    const int q_to = step_stages(a.stages_to, b, a.Q);
+    const int q_out = q_to < q_in ? q_to : q_in;
+    if (tid == 0 && a.stages_out) a.stages_out[b] = int64_t(q_out);
+    const unsigned char *row = a.in + size_t(b) * a.P;
+    const int n_codes = cnt * q_out;
+    const int live_bytes = (n_codes * a.bits + 7) / 8;
+    for (int i = tid; i < a.P; i += 256) {
+        unsigned v = 0;
+        if (i < live_bytes) {
+            const int lo = 8 * i;
+            for (int e = lo / a.bits; e < n_codes && e * a.bits < lo + 8; ++e) {
+                const unsigned code = step_read_code(row, ((e / q_out) * q_in + e % q_out) * a.bits, a.bits);
+                const int shift = e * a.bits - lo;
+                v |= shift >= 0 ? code << shift : code >> -shift;
+            }
+        }
+        a.out[size_t(b) * a.P + i] = (unsigned char)(v & 0xffu);
     }
 }
 
@@ -323,6 +381,52 @@ static int rvq_step_shape(const char *what, const int32_t *sizes, int32_t batch,
     return AGX_OK;
 }
 
+// the encode entry points: `stages` null is every stage for every row
+static int rvq_step_encode_any(const char *what, const float *z, int64_t z_sb, int64_t z_st, int64_t z_sd, const float *codebooks,
+                               const int32_t *sizes, const int64_t *counts, const int64_t *stages, int32_t batch, int32_t n, int32_t dim,
+                               int32_t k, int32_t q_total, int32_t q_used, int32_t bits, float *zq, int64_t q_sb, int64_t q_st,
+                               int64_t q_sd, int64_t *index, uint8_t *packets, void *workspace, size_t workspace_bytes, void *stream) {
+    RvqStepSizes sz;
+    if (int rc = rvq_step_shape(what, sizes, batch, n, dim, k, q_total, q_used, bits, &sz)) return rc;
+    for (int q = 0; q < q_used && packets; ++q)
+        if (sz.n[q] > (1 << bits))
+            return fail(AGX_ERR_UNSUPPORTED, "%s: stage %d has %d codewords, a packet of %d-bit codes cannot hold them", what, q, sz.n[q], bits);
+    if (!z || !codebooks || (q_used > 0 && !index)) return fail(AGX_ERR_NULL_POINTER, "%s: NULL pointer", what);
+    const size_t need = agx_rvq_step_workspace_bytes(batch, n, dim, k, q_used);
+    if (need > 0 && (!workspace || workspace_bytes < need))
+        return fail(AGX_ERR_WORKSPACE, "%s: workspace too small (%zu < %zu)", what, workspace_bytes, need);
+    if (need > 0 && (reinterpret_cast<uintptr_t>(workspace) & 7)) return fail(AGX_ERR_BAD_SHAPE, "%s: the workspace is not 8-byte aligned", what);
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    const int64_t F = int64_t(batch) * n;
+    const RvqStepWs map = rvq_step_ws(F, dim, k, q_used > 0 ? q_used : 1);
+    if (q_used > 0) {
+        RvqStepArgs a{z, z_sb, z_st, z_sd, codebooks, counts, stages, n, dim, k, q_used, static_cast<unsigned char *>(workspace), map, F, sz};
+        const dim3 grid((unsigned)F, (unsigned)ceil_div(k, STEP_CW));
+        for (int q = 0; q < q_used; ++q)
+            hipLaunchKernelGGL(rvq_step_search_kernel, grid, dim3(64), size_t(dim) * sizeof(float), st, a, q);
+    }
+    if (zq || packets || q_used > 0) {
+        const int P = int((int64_t(n) * q_used * bits + 7) / 8);
+        RvqStepOutArgs o{codebooks, counts, stages, n, dim, k, q_used, bits, zq, q_sb, q_st, q_sd, index, packets, P,
+                         static_cast<const unsigned char *>(workspace), map, F, sz};
+        hipLaunchKernelGGL(rvq_step_output_kernel, dim3((unsigned)batch), dim3(256), size_t(n) * (q_used > 0 ? q_used : 1) * sizeof(int), st, o);
+    }
+    return check_launch(what);
+}
+
+static int rvq_step_decode_any(const char *what, const uint8_t *packets, int32_t bits, const float *codebooks, const int32_t *sizes,
+                               const int64_t *counts, const int64_t *stages, int32_t batch, int32_t n, int32_t dim, int32_t k,
+                               int32_t q_total, int32_t q_used, float *zq, int64_t q_sb, int64_t q_st, int64_t q_sd, int64_t *index,
+                               void *stream) {
+    RvqStepSizes sz;
+    if (int rc = rvq_step_shape(what, sizes, batch, n, dim, k, q_total, q_used, bits, &sz)) return rc;
+    if (!codebooks || !zq || (q_used > 0 && !packets)) return fail(AGX_ERR_NULL_POINTER, "%s: NULL pointer", what);
+    const int P = int((int64_t(n) * q_used * bits + 7) / 8);
+    RvqStepDecArgs a{packets, P, bits, codebooks, counts, stages, n, dim, k, q_used, zq, q_sb, q_st, q_sd, index, sz};
+    hipLaunchKernelGGL(rvq_step_decode_kernel, dim3((unsigned)(int64_t(batch) * n)), dim3(256), 0, static_cast<hipStream_t>(stream), a);
+    return check_launch(what);
+}
+
 }  // namespace agx
 
 extern "C" {
@@ -341,46 +445,46 @@ int agx_rvq_step_encode(const float *z, int64_t z_sb, int64_t z_st, int64_t z_sd
                         const int64_t *counts, int32_t batch, int32_t n, int32_t dim, int32_t k, int32_t q_total, int32_t q_used,
                         int32_t bits, float *zq, int64_t q_sb, int64_t q_st, int64_t q_sd, int64_t *index, uint8_t *packets,
                         void *workspace, size_t workspace_bytes, void *stream) {
-    using namespace agx;
-    RvqStepSizes sz;
-    if (int rc = rvq_step_shape("rvq_step_encode", sizes, batch, n, dim, k, q_total, q_used, bits, &sz)) return rc;
-    for (int q = 0; q < q_used && packets; ++q)
-        if (sz.n[q] > (1 << bits))
-            return fail(AGX_ERR_UNSUPPORTED, "rvq_step_encode: stage %d has %d codewords, a packet of %d-bit codes cannot hold them", q, sz.n[q], bits);
-    if (!z || !codebooks || (q_used > 0 && !index)) return fail(AGX_ERR_NULL_POINTER, "rvq_step_encode: NULL pointer");
-    const size_t need = agx_rvq_step_workspace_bytes(batch, n, dim, k, q_used);
-    if (need > 0 && (!workspace || workspace_bytes < need))
-        return fail(AGX_ERR_WORKSPACE, "rvq_step_encode: workspace too small (%zu < %zu)", workspace_bytes, need);
-    if (need > 0 && (reinterpret_cast<uintptr_t>(workspace) & 7)) return fail(AGX_ERR_BAD_SHAPE, "rvq_step_encode: the workspace is not 8-byte aligned");
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    const int64_t F = int64_t(batch) * n;
-    const RvqStepWs map = rvq_step_ws(F, dim, k, q_used > 0 ? q_used : 1);
-    if (q_used > 0) {
-        RvqStepArgs a{z, z_sb, z_st, z_sd, codebooks, counts, n, dim, k, q_used, static_cast<unsigned char *>(workspace), map, F, sz};
-        const dim3 grid((unsigned)F, (unsigned)ceil_div(k, STEP_CW));
-        for (int q = 0; q < q_used; ++q)
-            hipLaunchKernelGGL(rvq_step_search_kernel, grid, dim3(64), size_t(dim) * sizeof(float), st, a, q);
-    }
-    if (zq || packets || q_used > 0) {
-        const int P = int((int64_t(n) * q_used * bits + 7) / 8);
-        RvqStepOutArgs o{codebooks, counts, n, dim, k, q_used, bits, zq, q_sb, q_st, q_sd, index, packets, P,
-                         static_cast<const unsigned char *>(workspace), map, F, sz};
-        hipLaunchKernelGGL(rvq_step_output_kernel, dim3((unsigned)batch), dim3(256), size_t(n) * (q_used > 0 ? q_used : 1) * sizeof(int), st, o);
-    }
-    return check_launch("rvq_step_encode");
+    return agx::rvq_step_encode_any("rvq_step_encode", z, z_sb, z_st, z_sd, codebooks, sizes, counts, nullptr, batch, n, dim, k, q_total,
+                                    q_used, bits, zq, q_sb, q_st, q_sd, index, packets, workspace, workspace_bytes, stream);
+}
+
+int agx_rvq_step_encode_staged(const float *z, int64_t z_sb, int64_t z_st, int64_t z_sd, const float *codebooks, const int32_t *sizes,
+                               const int64_t *counts, const int64_t *stages, int32_t batch, int32_t n, int32_t dim, int32_t k,
+                               int32_t q_total, int32_t q_used, int32_t bits, float *zq, int64_t q_sb, int64_t q_st, int64_t q_sd,
+                               int64_t *index, uint8_t *packets, void *workspace, size_t workspace_bytes, void *stream) {
+    return agx::rvq_step_encode_any("rvq_step_encode_staged", z, z_sb, z_st, z_sd, codebooks, sizes, counts, stages, batch, n, dim, k,
+                                    q_total, q_used, bits, zq, q_sb, q_st, q_sd, index, packets, workspace, workspace_bytes, stream);
 }
 
 int agx_rvq_step_decode(const uint8_t *packets, int32_t bits, const float *codebooks, const int32_t *sizes, const int64_t *counts,
                         int32_t batch, int32_t n, int32_t dim, int32_t k, int32_t q_total, int32_t q_used, float *zq, int64_t q_sb,
                         int64_t q_st, int64_t q_sd, int64_t *index, void *stream) {
+    return agx::rvq_step_decode_any("rvq_step_decode", packets, bits, codebooks, sizes, counts, nullptr, batch, n, dim, k, q_total, q_used,
+                                    zq, q_sb, q_st, q_sd, index, stream);
+}
+
+int agx_rvq_step_decode_staged(const uint8_t *packets, int32_t bits, const float *codebooks, const int32_t *sizes, const int64_t *counts,
+                               const int64_t *stages, int32_t batch, int32_t n, int32_t dim, int32_t k, int32_t q_total, int32_t q_used,
+                               float *zq, int64_t q_sb, int64_t q_st, int64_t q_sd, int64_t *index, void *stream) {
+    return agx::rvq_step_decode_any("rvq_step_decode_staged", packets, bits, codebooks, sizes, counts, stages, batch, n, dim, k, q_total,
+                                    q_used, zq, q_sb, q_st, q_sd, index, stream);
+}
+
+int agx_rvq_packets_restage(const uint8_t *in, const int64_t *stages_in, const int64_t *stages_to, const int64_t *counts, int32_t batch,
+                            int32_t n, int32_t q_used, int32_t bits, uint8_t *out, int64_t *stages_out, void *stream) {
     using namespace agx;
-    RvqStepSizes sz;
-    if (int rc = rvq_step_shape("rvq_step_decode", sizes, batch, n, dim, k, q_total, q_used, bits, &sz)) return rc;
-    if (!codebooks || !zq || (q_used > 0 && !packets)) return fail(AGX_ERR_NULL_POINTER, "rvq_step_decode: NULL pointer");
+    if (batch <= 0 || n <= 0 || n > AGX_RVQ_STEP_MAX_N || q_used < 0 || q_used > 64 || bits < 1 || bits > 16)
+        return fail(AGX_ERR_BAD_SHAPE, "rvq_packets_restage: bad shape B=%d n=%d q_used=%d bits=%d (n at most %d, q_used at most 64, bits 1 .. 16)",
+                    batch, n, q_used, bits, AGX_RVQ_STEP_MAX_N);
     const int P = int((int64_t(n) * q_used * bits + 7) / 8);
-    RvqStepDecArgs a{packets, P, bits, codebooks, counts, n, dim, k, q_used, zq, q_sb, q_st, q_sd, index, sz};
-    hipLaunchKernelGGL(rvq_step_decode_kernel, dim3((unsigned)(int64_t(batch) * n)), dim3(256), 0, static_cast<hipStream_t>(stream), a);
-    return check_launch("rvq_step_decode");
+    if (!stages_to || (P > 0 && (!in || !out))) return fail(AGX_ERR_NULL_POINTER, "rvq_packets_restage: NULL pointer");
+    const size_t total = size_t(batch) * size_t(P);
+    if (P > 0 && in < out + total && out < in + total)
+        return fail(AGX_ERR_BAD_SHAPE, "rvq_packets_restage: in and out overlap (a byte is gathered from bits other bytes' threads write)");
+    RvqRestageArgs a{in, stages_in, stages_to, counts, n, q_used, bits, P, out, stages_out};
+    hipLaunchKernelGGL(rvq_packets_restage_kernel, dim3((unsigned)batch), dim3(256), 0, static_cast<hipStream_t>(stream), a);
+    return check_launch("rvq_packets_restage");
 }
 
 }  // extern "C"

@@ -542,12 +542,16 @@ def rvq_step_packet_bytes(n: int, q_used: int, bits: int) -> int:
 
 
 def rvq_step_encode(z: Tensor, codebooks: Tensor, q_used: int, sizes: Optional[Sequence[int]] = None, counts: Optional[Tensor] = None,
-                    bits: Optional[int] = None, want_zq: bool = True):
+                    bits: Optional[int] = None, want_zq: bool = True, *, stages: Optional[Tensor] = None):
     """The quantiser of a streaming chunk (``agx_rvq_step_encode``): z (B, D, n) fp32, any strides, n <= ``RVQ_STEP_MAX_N`` ->
     (zq (B, D, n) or None, index (B, n, q_used) int64, packets (B, P) uint8).  Every frame below its row's count (``counts``:
     int64 (B,), device; None: all n) gets the full defining search; behind the count zq is exact 0, index is -1 and the packet
     bytes are 0.  Row b's first ``ceil(c_b q_used bits / 8)`` bytes are ``codes_pack(index[b, :c_b], bits)``.  ``bits`` defaults
-    to the width of the widest stage."""
+    to the width of the widest stage.
+
+    ``stages`` (int64 (B,), device; ``agx_rvq_step_encode_staged``): row b sends its first ``q_b = clamp(stages[b], 0, q_used)``
+    stages.  Only those are searched; zq is their sum, index is -1 at the others, and the row's packet is
+    ``codes_pack(index[b, :c_b, :q_b], bits)`` -- all of it what ``q_used = q_b`` gives for that row.  P does not change."""
     lib = _lib.load()
     _need_gpu(z, codebooks)
     if z.dtype != torch.float32 or z.dim() != 3:
@@ -558,6 +562,8 @@ def rvq_step_encode(z: Tensor, codebooks: Tensor, q_used: int, sizes: Optional[S
         raise AgxError(f"rvq_step_encode: frame dim {dim} != codebook dim {d}")
     if counts is not None:
         counts = _checked_counts("rvq_step_encode", counts, b, z.device)
+    if stages is not None:
+        stages = _checked_stages("rvq_step_encode", stages, b, z.device)
     p = rvq_step_packet_bytes(n, q_used, bits)
     zq = torch.empty((b, d, n), dtype=torch.float32, device=z.device) if want_zq else None
     index = torch.empty((b, n, q_used), dtype=torch.int64, device=z.device)
@@ -566,34 +572,78 @@ def rvq_step_encode(z: Tensor, codebooks: Tensor, q_used: int, sizes: Optional[S
     ws = _workspace(nbytes, z.device, "agx_rvq_step_workspace_bytes") if nbytes else None
     zsb, zsd, zst = z.stride()
     qsb, qsd, qst = zq.stride() if want_zq else (0, 0, 0)
-    _lib.check(lib.agx_rvq_step_encode(_ptr(z), zsb, zst, zsd, _ptr(codebooks), arr and ctypes.cast(arr, ctypes.c_void_p), _ptr(counts),
-                                       b, n, d, k, q_total, q_used, bits, _ptr(zq), qsb, qst, qsd, _ptr(index),
-                                       _ptr(packets) if p else None, _ptr(ws), nbytes, _stream()), "agx_rvq_step_encode")
+    head = (_ptr(z), zsb, zst, zsd, _ptr(codebooks), arr and ctypes.cast(arr, ctypes.c_void_p), _ptr(counts))
+    tail = (b, n, d, k, q_total, q_used, bits, _ptr(zq), qsb, qst, qsd, _ptr(index), _ptr(packets) if p else None, _ptr(ws), nbytes,
+            _stream())
+    if stages is None:
+        _lib.check(lib.agx_rvq_step_encode(*head, *tail), "agx_rvq_step_encode")
+    else:
+        _lib.check(lib.agx_rvq_step_encode_staged(*head, _ptr(stages), *tail), "agx_rvq_step_encode_staged")
     return zq, index, packets
 
 
+def _checked_packets(op: str, packets, n: int, q_used: int, bits: int) -> int:
+    """``packets`` as the step kernels read it: a contiguous uint8 (B, P) tensor, P = ``rvq_step_packet_bytes`` -> B."""
+    p = rvq_step_packet_bytes(n, q_used, bits)
+    if not isinstance(packets, Tensor) or packets.dtype != torch.uint8 or packets.dim() != 2 or packets.shape[1] != p \
+            or not packets.is_contiguous():
+        got = f"{packets.dtype} {tuple(packets.shape)}" if isinstance(packets, Tensor) else type(packets).__name__
+        raise AgxError(f"{op}: packets must be a contiguous uint8 (B, {p}) tensor (n={n}, q_used={q_used}, bits={bits}), got {got}")
+    return packets.shape[0]
+
+
 def rvq_step_decode(packets: Tensor, n: int, codebooks: Tensor, q_used: int, bits: int, sizes: Optional[Sequence[int]] = None,
-                    counts: Optional[Tensor] = None, want_index: bool = False):
+                    counts: Optional[Tensor] = None, want_index: bool = False, *, stages: Optional[Tensor] = None):
     """Packets of ``rvq_step_encode`` -> zq (B, D, n), or (zq, index (B, n, q_used)) with ``want_index``: one launch
     (``agx_rvq_step_decode``).  Behind a row's count zq is exact 0 and index -1, and the packet bytes there are not read; a code
-    ``>= sizes[q]`` adds nothing."""
+    ``>= sizes[q]`` adds nothing.  ``stages``: the tensor the sender (or ``rvq_packets_restage``) used -- row b's packet holds
+    ``q_b`` codes per frame, and index is -1 at the stages it does not hold (``agx_rvq_step_decode_staged``)."""
     lib = _lib.load()
     _need_gpu(packets, codebooks)
     codebooks, q_total, k, d, arr, bits = _step_operands("rvq_step_decode", codebooks, q_used, sizes, bits)
-    p = rvq_step_packet_bytes(n, q_used, bits)
-    if packets.dtype != torch.uint8 or packets.dim() != 2 or packets.shape[1] != p or not packets.is_contiguous():
-        raise AgxError(f"rvq_step_decode: packets must be a contiguous uint8 (B, {p}) tensor (n={n}, q_used={q_used}, bits={bits}), got "
-                       f"{packets.dtype} {tuple(packets.shape)}")
-    b = packets.shape[0]
+    b = _checked_packets("rvq_step_decode", packets, n, q_used, bits)
+    p = packets.shape[1]
     if counts is not None:
         counts = _checked_counts("rvq_step_decode", counts, b, packets.device)
+    if stages is not None:
+        stages = _checked_stages("rvq_step_decode", stages, b, packets.device)
     zq = torch.empty((b, d, n), dtype=torch.float32, device=packets.device)
     index = torch.empty((b, n, q_used), dtype=torch.int64, device=packets.device) if want_index else None
     qsb, qsd, qst = zq.stride()
-    _lib.check(lib.agx_rvq_step_decode(_ptr(packets) if p else None, bits, _ptr(codebooks), arr and ctypes.cast(arr, ctypes.c_void_p),
-                                       _ptr(counts), b, n, d, k, q_total, q_used, _ptr(zq), qsb, qst, qsd, _ptr(index), _stream()),
-               "agx_rvq_step_decode")
+    head = (_ptr(packets) if p else None, bits, _ptr(codebooks), arr and ctypes.cast(arr, ctypes.c_void_p), _ptr(counts))
+    tail = (b, n, d, k, q_total, q_used, _ptr(zq), qsb, qst, qsd, _ptr(index), _stream())
+    if stages is None:
+        _lib.check(lib.agx_rvq_step_decode(*head, *tail), "agx_rvq_step_decode")
+    else:
+        _lib.check(lib.agx_rvq_step_decode_staged(*head, _ptr(stages), *tail), "agx_rvq_step_decode_staged")
     return (zq, index) if want_index else zq
+
+
+def rvq_packets_restage(packets: Tensor, n: int, q_used: int, bits: int, stages_to: Tensor, stages_from: Optional[Tensor] = None,
+                        counts: Optional[Tensor] = None, out: Optional[Tensor] = None) -> Tuple[Tensor, Tensor]:
+    """Drop enhancement stages from packets that are already encoded (``agx_rvq_packets_restage``: one launch, no codebooks):
+    packets (B, P) of ``rvq_step_encode`` with ``stages=stages_from`` (None: ``q_used`` stages in every row) -> (packets (B, P),
+    stages (B,) int64), row b re-packed to ``q_out = min(q_in, clamp(stages_to[b], 0, q_used))`` stages -- byte for byte what the
+    encoder writes with ``q_out``, zero tail included.  ``stages`` is written by the kernel: hand it to ``rvq_step_decode`` or to
+    the next hop.  It never restages upward.  ``out``: a (B, P) uint8 tensor to write, sharing no byte with ``packets``."""
+    op = "rvq_packets_restage"
+    b = _checked_packets(op, packets, n, q_used, bits)                    # every refusal precedes the launch
+    stages_to = _checked_stages(op, stages_to, b, packets.device, on="the packets are on", name="stages_to")
+    if stages_from is not None:
+        stages_from = _checked_stages(op, stages_from, b, packets.device, on="the packets are on", name="stages_from")
+    if counts is not None:
+        counts = _checked_counts(op, counts, b, packets.device, on="the packets are on")
+    if out is not None and (not isinstance(out, Tensor) or out.dtype != torch.uint8 or out.shape != packets.shape
+                            or not out.is_contiguous() or out.device != packets.device):
+        raise AgxError(f"{op}: out must be a contiguous uint8 {tuple(packets.shape)} tensor on '{packets.device}'")
+    lib = _lib.load()
+    _need_gpu(packets)
+    if out is None:
+        out = torch.empty_like(packets)
+    stages_out = torch.empty(b, dtype=torch.int64, device=packets.device)
+    _lib.check(lib.agx_rvq_packets_restage(_ptr(packets), _ptr(stages_from), _ptr(stages_to), _ptr(counts), b, n, q_used, bits,
+                                           _ptr(out), _ptr(stages_out), _stream()), "agx_rvq_packets_restage")
+    return out, stages_out
 
 
 # ------------------------------------------------------------------ attention block
@@ -1223,22 +1273,28 @@ def _checked_pos(op: str, pos, b: int, device) -> Tensor:
     return pos
 
 
-def _checked_counts(op: str, counts, b: int, device, on: Optional[str] = None) -> Tensor:
+def _checked_counts(op: str, counts, b: int, device, on: Optional[str] = None, name: str = "counts", per: str = "frame count") -> Tensor:
     """``counts`` as the counted kernels read it (include/agx.h "Per-row frame counts"): a contiguous int64 device tensor of B
     entries on the operands' device -- the one place that inspects it, for the ops and for the models and streams above them.
     The values stay on the device -- the kernels clamp them to [0, n] -- so nothing here synchronises or checks one.  ``on``:
     what ``device`` belongs to in the caller's words ("the cache on", "the stream on", "the conv state on"); None is an op, whose
-    operands must also be on the GPU."""
+    operands must also be on the GPU.  ``name`` / ``per``: what the message calls the tensor (``_checked_stages``)."""
     if not isinstance(counts, Tensor) or counts.dtype != torch.int64 or counts.dim() != 1 or counts.numel() != b:
         what = f"{tuple(counts.shape)} {counts.dtype}" if isinstance(counts, Tensor) else type(counts).__name__
-        raise AgxError(f"{op}: counts must be a contiguous int64 device tensor of {b} entries (one frame count per batch row), got {what}")
+        raise AgxError(f"{op}: {name} must be a contiguous int64 device tensor of {b} entries (one {per} per batch row), got {what}")
     if not counts.is_contiguous():
-        raise AgxError(f"{op}: counts is not contiguous (stride {tuple(counts.stride())}): the kernels read {b} adjacent int64")
+        raise AgxError(f"{op}: {name} is not contiguous (stride {tuple(counts.stride())}): the kernels read {b} adjacent int64")
     if on is None:
         _need_gpu(counts)
     if counts.device != device:
-        raise AgxError(f"{op}: counts is on '{counts.device}', {on or 'the operands are on'} '{device}'")
+        raise AgxError(f"{op}: {name} is on '{counts.device}', {on or 'the operands are on'} '{device}'")
     return counts
+
+
+def _checked_stages(op: str, stages, b: int, device, on: Optional[str] = None, name: str = "stages") -> Tensor:
+    """``stages`` as the staged RVQ step kernels read it (include/agx.h "Per-row stage counts"): ``_checked_counts`` under its own
+    name.  The kernels clamp the values to [0, q_used]; the host never reads one."""
+    return _checked_counts(op, stages, b, device, on, name=name, per="stage count")
 
 
 def _row_slices(what: str, rows, batch: int, of: str) -> list:

@@ -447,26 +447,34 @@ def _step_quantizer(model, what: str, codebook_n):
     return q.codebooks.detach(), q._q_used(codebook_n), None if uniform else q.codebook_sizes, model._code_bits
 
 
-def encode_codes_stream(model, x: Tensor, stream: CodecStream, codebook_n: Optional[int] = None, counts: Optional[Tensor] = None):
+def _check_stages(what: str, stages, stream) -> None:
+    """``stages`` of a packet step (``ops._checked_stages``), refused before the first launch."""
+    if stages is not None and isinstance(stream, CodecStream):
+        ops._checked_stages(what, stages, stream.batch, stream.device, on="the stream on")
+
+
+def encode_codes_stream(model, x: Tensor, stream: CodecStream, codebook_n: Optional[int] = None, counts: Optional[Tensor] = None,
+                        stages: Optional[Tensor] = None):
     """The sender's step -> (zq (B, D, n), index (B, n, Q), packets (B, P) uint8): ``encode_latents_stream``, then the RVQ step
     (``ops.rvq_step_encode``: the full defining search of every frame below its row's count).  Behind a row's count ``zq`` is exact
     0, ``index`` is -1 and the packet bytes are 0; row ``b``'s first ``ceil(c_b Q bits / 8)`` bytes are its packet, ``bits =
-    model._code_bits``.  Only the encoder rings of ``stream`` are used."""
+    model._code_bits``.  Only the encoder rings of ``stream`` are used.
+
+    ``stages`` (int64 (B,), device): row ``b`` sends its first ``q_b = clamp(stages[b], 0, Q)`` stages -- its packet
+    is ``ceil(c_b q_b bits / 8)`` bytes dense over its own ``q_b``, ``zq`` is the sum of those stages and ``index`` is -1 at the
+    others.  ``P`` does not depend on it, and the encoder rings advance by ``c_b`` whatever ``q_b`` is."""
     cbs, q_used, sizes, bits = _step_quantizer(model, "encode_codes_stream", codebook_n)      # refusals precede the first launch
+    _check_stages("encode_codes_stream", stages, stream)
     if isinstance(stream, CodecStream) and stream.max_chunk > ops.RVQ_STEP_MAX_N:
         frames = model.rearrange_in(x).shape[-1] // stream.scale_factor
         if frames > ops.RVQ_STEP_MAX_N:
             raise AgxError(f"encode_codes_stream: a chunk of {frames} frames exceeds the {ops.RVQ_STEP_MAX_N} frames a quantiser step takes")
     z = encode_latents_stream(model, x, stream, counts)
-    return ops.rvq_step_encode(z, cbs, q_used, sizes, counts, bits)
+    return ops.rvq_step_encode(z, cbs, q_used, sizes, counts, bits, stages=stages)
 
 
-def decode_codes_stream(model, packets: Tensor, stream: CodecStream, frames: int, codebook_n: Optional[int] = None,
-                        counts: Optional[Tensor] = None):
-    """The receiver's step -> (y, index (B, frames, Q)): the packets of ``frames`` frames per row (``encode_codes_stream``; the bytes
-    behind a row's count are not read) through ``ops.rvq_step_decode`` and the decoder stack step.  Only the decoder rings of
-    ``stream`` are used."""
-    what = "decode_codes_stream"
+def _packet_step(model, what: str, packets, stream, frames, codebook_n, counts, stages):
+    """Every refusal of the receiver's step, before the first launch -> (codebooks, q_used, sizes, bits, frames)."""
     cbs, q_used, sizes, bits = _step_quantizer(model, what, codebook_n)
     if not isinstance(stream, CodecStream) or stream.model_id != id(model):
         raise AgxError(f"{what}: the stream belongs to another model (model.new_stream makes one for this model)")
@@ -487,8 +495,42 @@ def decode_codes_stream(model, packets: Tensor, stream: CodecStream, frames: int
         raise AgxError(f"{what}: the packets are on '{packets.device}', the stream on '{stream.device}'")
     if counts is not None:
         ops._checked_counts(what, counts, stream.batch, stream.device, on="the stream on")
-    zq, index = ops.rvq_step_decode(packets.contiguous(), frames, cbs, q_used, bits, sizes, counts, want_index=True)
+    _check_stages(what, stages, stream)
+    return cbs, q_used, sizes, bits, frames
+
+
+def decode_codes_stream(model, packets: Tensor, stream: CodecStream, frames: int, codebook_n: Optional[int] = None,
+                        counts: Optional[Tensor] = None, stages: Optional[Tensor] = None):
+    """The receiver's step -> (y, index (B, frames, Q)): the packets of ``frames`` frames per row (``encode_codes_stream``; the bytes
+    behind a row's count are not read) through ``ops.rvq_step_decode`` and the decoder stack step.  Only the decoder rings of
+    ``stream`` are used.
+
+    ``stages``: the tensor the sender, or the last ``restage_packets`` on the way, used.  Row ``b``'s frames are the sum of its
+    ``q_b`` stages and ``index`` is -1 at the others.  A row with ``c_b > 0`` and ``q_b == 0`` pushes ``c_b`` frames of the zero
+    latent through the decoder and advances by ``c_b``: sending no stage is silence of the quantiser, not a pause (``counts``
+    pauses a row)."""
+    what = "decode_codes_stream"
+    cbs, q_used, sizes, bits, frames = _packet_step(model, what, packets, stream, frames, codebook_n, counts, stages)
+    zq, index = ops.rvq_step_decode(packets.contiguous(), frames, cbs, q_used, bits, sizes, counts, want_index=True, stages=stages)
     return decode_stream(model, zq, stream, counts), index
+
+
+def restage_packets(model, packets: Tensor, frames: int, stages: Tensor, stages_from: Optional[Tensor] = None,
+                    codebook_n: Optional[int] = None, counts: Optional[Tensor] = None):
+    """A relay's step -> (packets (B, P), stages (B,) int64): packet rows of ``frames`` frames, sent with ``stages_from`` (None:
+    all ``Q`` stages), re-packed to ``min(q_in, clamp(stages[b], 0, Q))`` stages per row (``ops.rvq_packets_restage``: one launch,
+    no codebooks, no decoding, no stream).  The packets are byte for byte what the sender would have written at that stage count,
+    and the returned ``stages`` -- written on the device -- is what the receiver or the next relay takes."""
+    what = "restage_packets"
+    _, q_used, _, bits = _step_quantizer(model, what, codebook_n)
+    frames = int(frames)
+    if not 1 <= frames <= ops.RVQ_STEP_MAX_N:
+        raise AgxError(f"{what}: frames = {frames} outside 1 .. the {ops.RVQ_STEP_MAX_N} frames a quantiser step takes")
+    width = -((-frames * q_used * bits) // 8)
+    if not isinstance(packets, Tensor) or packets.dtype != torch.uint8 or packets.dim() != 2 or packets.shape[1] != width:
+        got = f"{packets.dtype} {tuple(packets.shape)}" if isinstance(packets, Tensor) else type(packets).__name__
+        raise AgxError(f"{what}: packets of {frames} frames x {q_used} codes x {bits} bits are uint8 (B, {width}), got {got}")
+    return ops.rvq_packets_restage(packets.contiguous(), frames, q_used, bits, stages, stages_from, counts)
 
 
 def flush_counts(stream: CodecStream, rows, n: int) -> Tensor:

@@ -610,21 +610,44 @@ class CausalVQAE(nn.Module):
                                         accumulate=zq is not None)
             return self.decode(zq.transpose(1, 2).contiguous()), index
 
-    def compress_stream(self, x_chunk, stream, codebook_n=None, counts=None):
+    def compress_stream(self, x_chunk, stream, codebook_n=None, counts=None, stages=None):
         """The sender's step of a live stream: the next ``n`` whole frames of every row -> (packets (B, P) uint8, index (B, n, Q)),
         ``P = ceil(n Q bits / 8)``.  Row ``b``'s first ``ceil(c_b Q bits / 8)`` bytes are its packet -- ``ops.codes_pack`` of its
         ``c_b = clamp(counts[b], 0, n)`` frames' codes -- and every byte behind them is 0; ``index`` behind the count is -1.  Uses
-        only the encoder rings of ``stream``."""
+        only the encoder rings of ``stream``.
+
+        ``stages`` (int64 (B,), device): one bitrate per row.  Row ``b`` sends its first ``q_b = clamp(stages[b], 0, Q)`` stages
+        (``stages_for_bitrate``): its packet is ``ceil(c_b q_b bits / 8)`` bytes, dense over its own ``q_b``, ``index`` is -1 at
+        the stages it does not send, and ``P`` stays what it is -- one captured step serves any mix of bitrates."""
         from . import streaming
-        _, index, packets = streaming.encode_codes_stream(self, x_chunk, stream, codebook_n, counts)
+        _, index, packets = streaming.encode_codes_stream(self, x_chunk, stream, codebook_n, counts, stages)
         return packets, index
 
-    def decompress_stream(self, packets, stream, frames, codebook_n=None, counts=None):
+    def decompress_stream(self, packets, stream, frames, codebook_n=None, counts=None, stages=None):
         """The receiver's step: packet rows of ``frames`` frames (``compress_stream``) -> (y, index), ``y`` as ``decode_stream``
         returns it.  The bytes behind a row's count are not read.  Uses only the decoder rings of ``stream``; ``finish``,
-        ``decode_flush`` and ``reset`` are those of any stream."""
+        ``decode_flush`` and ``reset`` are those of any stream.
+
+        ``stages``: the tensor the packets were written with (``compress_stream``, or the one ``restage_packets`` returned).  A
+        row with ``c_b > 0`` and ``q_b == 0`` pushes ``c_b`` frames of the zero latent through the decoder and advances."""
         from . import streaming
-        return streaming.decode_codes_stream(self, packets, stream, frames, codebook_n, counts)
+        return streaming.decode_codes_stream(self, packets, stream, frames, codebook_n, counts, stages)
+
+    def restage_packets(self, packets, frames, stages, stages_from=None, codebook_n=None, counts=None):
+        """A relay's step: packet rows of ``frames`` frames written with ``stages_from`` (None: every stage) -> (packets, stages)
+        with row ``b`` at ``min(q_in, clamp(stages[b], 0, Q))`` stages, byte for byte what ``compress_stream`` writes at that
+        count.  One launch, no codebooks, no decoding; the returned ``stages`` is written on the device.  Never upward."""
+        from . import streaming
+        return streaming.restage_packets(self, packets, frames, stages, stages_from, codebook_n, counts)
+
+    def stages_for_bitrate(self, bitrate, sample_rate) -> int:
+        """The stages a link of ``bitrate`` bits per second carries at ``sample_rate``: the largest ``q <= num_quantizers`` with
+        ``q * _code_bits * sample_rate / scale_factor <= bitrate`` -- ``utils.bitrate_calculator`` solved for the stage count,
+        at the width a code has on the wire.  0 when even one stage does not fit.  Host arithmetic."""
+        q = 0
+        while q < self.num_quantizers and (q + 1) * self._code_bits * sample_rate / self.scale_factor <= bitrate:
+            q += 1
+        return q
 
     def replace_quantizer(self, new_quantizer):
         self.quantizer = new_quantizer

@@ -1236,6 +1236,43 @@ int agx_rvq_step_decode(const uint8_t *packets, int32_t bits, const float *codeb
                         int32_t batch, int32_t n, int32_t dim, int32_t k, int32_t q_total, int32_t q_used, float *zq, int64_t q_sb,
                         int64_t q_st, int64_t q_sd, int64_t *index, void *stream);
 
+/* ---- Per-row stage counts -------------------------------------------------------------------------------------
+ * The first q stages of a frame's codes are a complete, coarser description of it, so a row's bitrate is the number of stages it
+ * sends.  stages is a contiguous int64 (B,) device tensor read by the kernels as counts is: q_b = clamp(stages[b], 0, q_used),
+ * the host never reads it, and NULL means q_b = q_used for every row.  Stage q of frame (b, t) is live when t < c_b and q < q_b.
+ * P = agx_rvq_step_packet_bytes(n, q_used, bits) depends on neither tensor: buffers and captured graphs keep their shapes.
+ *
+ * agx_rvq_step_encode_staged: agx_rvq_step_encode with stages after counts.
+ *   index   : (B, n, q_used); a live entry holds the code, every other entry -1.
+ *   zq      : a live frame: ((0 + c_0) + c_1) + .. + c_{q_b - 1} in binary32, stage order; behind the count, or q_b == 0: exact 0.
+ *   packets : row b's first ceil(c_b q_b bits / 8) bytes are the dense little-endian packing of index[b, :c_b, :q_b], frame-major
+ *             and stage-minor over the row's OWN q_b; the unused high bits of the last byte and every byte behind it are 0.
+ *   Row b's zq, index[b, :, :q_b] and live packet bytes are bit for bit what agx_rvq_step_encode gives for that row with
+ *   q_used = q_b: the stage count decides what is searched and stored, never how a distance or a sum is computed.  The search
+ *   launch of stage q leaves row b's workgroups right after reading counts and stages when q >= q_b: nothing of the frame, the
+ *   codebook or the workspace is loaded and no partial is written.  Launches, refusals and the workspace are those of
+ *   agx_rvq_step_encode for q_used.
+ * agx_rvq_step_decode_staged: agx_rvq_step_decode with stages after counts.  Frame t of row b reads its q_b codes from bit
+ *   (t q_b + q) bits on; bytes behind the row's first ceil(c_b q_b bits / 8) are not read; index is -1 where a stage is not
+ *   live; a code >= sizes[q] adds and reads nothing, as before.
+ * agx_rvq_packets_restage: packets of q_in = clamp(stages_in[b], 0, q_used) stages per row (stages_in NULL: q_used) ->
+ *   packets of q_out = min(q_in, clamp(stages_to[b], 0, q_used)) stages, in one launch, without codebooks or workspace: a bit
+ *   gather, output byte i collecting the codes whose bits it holds from their input bit positions.  out[b] is byte for byte the
+ *   packet agx_rvq_step_encode_staged writes with q_out, zero tail included; stages_out[b] = q_out (may be NULL) is written by
+ *   the kernel, so the receiver's stages never pass through the host.  in and out are (B, P) uint8, contiguous; input bytes
+ *   behind ceil(c_b q_in bits / 8) are not read.  Refused: in and out sharing a byte (AGX_ERR_BAD_SHAPE), stages_to == NULL
+ *   (AGX_ERR_NULL_POINTER), n, q_used or bits outside what agx_rvq_step_packet_bytes takes. */
+int agx_rvq_step_encode_staged(const float *z, int64_t z_sb, int64_t z_st, int64_t z_sd, const float *codebooks, const int32_t *sizes,
+                               const int64_t *counts, const int64_t *stages, int32_t batch, int32_t n, int32_t dim, int32_t k,
+                               int32_t q_total, int32_t q_used, int32_t bits, float *zq, int64_t q_sb, int64_t q_st, int64_t q_sd,
+                               int64_t *index, uint8_t *packets, void *workspace, size_t workspace_bytes, void *stream);
+int agx_rvq_step_decode_staged(const uint8_t *packets, int32_t bits, const float *codebooks, const int32_t *sizes, const int64_t *counts,
+                               const int64_t *stages, int32_t batch, int32_t n, int32_t dim, int32_t k, int32_t q_total, int32_t q_used,
+                               float *zq, int64_t q_sb, int64_t q_st, int64_t q_sd, int64_t *index, void *stream);
+int agx_rvq_packets_restage(const uint8_t *in, const int64_t *stages_in /* may be NULL */, const int64_t *stages_to,
+                            const int64_t *counts /* may be NULL */, int32_t batch, int32_t n, int32_t q_used, int32_t bits, uint8_t *out,
+                            int64_t *stages_out /* may be NULL */, void *stream);
+
 /* ---- Streaming wavelet blocks (csrc/wavelet_stream.hip) --------------------------------------------------------
  * A wavelet decoder block (conv_in "same", k_in odd, p_in = (k_in - 1) / 2; fold by scale s >= 2 over n_points P, s | P;
  * conv_out "same", k_out odd, p_out = (k_out - 1) / 2) as two steps of a stream, in the terms of "Streaming conv stacks".  The
