@@ -95,6 +95,16 @@ SIGNATURES = {
                                  c_int32, c_int32, c_int32, c_int32, c_int32, c_int32,
                                  c_void_p, c_int64, c_int64, c_int64, c_void_p,
                                  c_void_p, c_size_t, c_void_p]),
+    # per-row stage counts through the training call: `stages` after `index`
+    "agx_rvq_forward_staged": (c_int, [c_void_p, c_int64, c_int64, c_int64, c_void_p, c_void_p,
+                                       c_int32, c_int32, c_int32, c_int32, c_int32,
+                                       c_void_p, c_int64, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_void_p,
+                                       c_void_p, c_size_t, c_void_p]),
+    "agx_rvq_backward_staged": (c_int, [c_void_p, c_int64, c_int64, c_int64, c_void_p, c_void_p, c_void_p,
+                                        c_void_p, c_int64, c_int64, c_int64, c_void_p,
+                                        c_int32, c_int32, c_int32, c_int32, c_int32, c_int32,
+                                        c_void_p, c_int64, c_int64, c_int64, c_void_p,
+                                        c_void_p, c_size_t, c_void_p]),
     "agx_rvq_debug_stamps": (c_int, [c_void_p, c_int32]),
     "agx_rvq_verify_counts": (c_int, [POINTER(c_int64), c_int32]),
     "agx_rvq_dequantize": (c_int, [c_void_p, c_void_p, c_int64, c_int32, c_int32, c_void_p,

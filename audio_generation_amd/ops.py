@@ -387,12 +387,26 @@ def rvq_pack(codebooks: Tensor, sizes: Optional[Sequence[int]] = None) -> Tensor
     return packed
 
 
+def _rvq_stages(op: str, stages, x: Tensor) -> Optional[Tensor]:
+    """``stages`` of the quantiser's staged calls: None, or a contiguous int64 (B,) tensor on x's device -- refused
+    otherwise, before anything is launched and before the device is asked for."""
+    if stages is None:
+        return None
+    return _checked_stages(op, stages, x.shape[0] if x.dim() == 3 else -1, x.device, on="the inputs are on")
+
+
 def rvq_forward(x: Tensor, codebooks: Tensor, packed: Tensor, q_used: int,
-                layout: str = "b l c") -> Tuple[Tensor, Tensor, Tensor, Tensor]:
+                layout: str = "b l c", *, stages: Optional[Tensor] = None) -> Tuple[Tensor, Tensor, Tensor, Tensor]:
     """x: (B,T,D) for layout "b l c" or (B,D,T) for "b c l" (any strides).
     Returns (x_q in the same layout/shape, index (B,T,q_used) int64, sq_err (q_used) f64, commit): the commit loss
-    sum(sq_err) / x.numel() is a 0-d f32 tensor written by the same launch."""
+    sum(sq_err) / x.numel() is a 0-d f32 tensor written by the same launch.
+
+    ``stages`` (int64 (B,), device; ``agx_rvq_forward_staged``): row b keeps its first
+    ``q_b = clamp(stages[b], 0, q_used)`` stages and is exactly that row quantised alone with ``q_used = q_b`` -- index is -1 at its
+    other stages, x_q sums its live stages only (exact 0 for ``q_b == 0``), sq_err[q] sums the frames live at q.  The kernel reads
+    the tensor, the host never does; None is the unstaged call, bit for bit."""
     lib = _lib.load()
+    stages = _rvq_stages("rvq_forward", stages, x)
     _need_gpu(x, codebooks, packed)
     if x.dtype != torch.float32:
         raise AgxError(f"rvq_forward: expected float32, got {x.dtype}")
@@ -422,10 +436,12 @@ def rvq_forward(x: Tensor, codebooks: Tensor, packed: Tensor, q_used: int,
     buf = torch.empty(q_used + ws_bytes // 8, dtype=torch.float64, device=x.device)
     commit = torch.empty((), dtype=torch.float32, device=x.device)
     tok = _observer.begin("rvq", (b, t, d, k, q_used)) if _observer is not None else None
-    _lib.check(lib.agx_rvq_forward_ex(_ptr(x), sb, st, sd, _ptr(codebooks), _ptr(packed), b, t, d, k, q_used,
-                                      _ptr(xq), qb, qt, qd, _ptr(index), _ptr(buf), _ptr(commit),
-                                      ctypes.c_void_p(buf.data_ptr() + 8 * q_used), ws_bytes, _stream()),
-               "agx_rvq_forward_ex")
+    head = (_ptr(x), sb, st, sd, _ptr(codebooks), _ptr(packed), b, t, d, k, q_used, _ptr(xq), qb, qt, qd, _ptr(index))
+    tail = (_ptr(buf), _ptr(commit), ctypes.c_void_p(buf.data_ptr() + 8 * q_used), ws_bytes, _stream())
+    if stages is None:
+        _lib.check(lib.agx_rvq_forward_ex(*head, *tail), "agx_rvq_forward_ex")
+    else:
+        _lib.check(lib.agx_rvq_forward_staged(*head, _ptr(stages), *tail), "agx_rvq_forward_staged")
     if tok is not None:
         _observer.end(tok)
     if q_used == 0:
@@ -453,11 +469,18 @@ def rvq_ema_stats(frames: Tensor, codebooks: Tensor, index: Tensor) -> Tensor:
 
 
 def rvq_backward(x: Tensor, codebooks: Tensor, index: Tensor, g_xq: Optional[Tensor], g_commit: Optional[Tensor],
-                 layout: str = "b l c", want_codebook_grad: bool = False) -> Tuple[Tensor, Optional[Tensor]]:
+                 layout: str = "b l c", want_codebook_grad: bool = False, *,
+                 stages: Optional[Tensor] = None) -> Tuple[Tensor, Optional[Tensor]]:
     """Backward of the quantiser's training call (``agx_rvq_backward``): x and g_xq (any strides, ``None`` = zero) in
     ``layout`` as for ``rvq_forward``, index (B, T, q_used) as the forward returned it, g_commit a 0-d device tensor (``None`` =
-    zero; never read on the host) -> (dx contiguous in x's shape, d codebooks (Q, K, D) or ``None``)."""
+    zero; never read on the host) -> (dx contiguous in x's shape, d codebooks (Q, K, D) or ``None``).
+
+    ``stages``: the tensor the forward took (``agx_rvq_backward_staged``) -- the residual chain and the suffix sums of
+    row b's frames run over its ``q_b`` live stages only, so dx of a ``q_b == 0`` row is g_xq alone and a stage no row runs gets an
+    exactly zero codebook gradient.  Not the unstaged backward on the masked index, where a stage with index -1 still enters the
+    loss."""
     lib = _lib.load()
+    stages = _rvq_stages("rvq_backward", stages, x)
     _need_gpu(x, codebooks, index, g_xq, g_commit)
     for t_ in (x, g_xq, g_commit):
         if t_ is not None and t_.dtype != torch.float32:
@@ -487,9 +510,13 @@ def rvq_backward(x: Tensor, codebooks: Tensor, index: Tensor, g_xq: Optional[Ten
 
     def strides(t_):
         return [0, 0, 0] if t_ is None else [t_.stride(p) for p in perm]
-    _lib.check(lib.agx_rvq_backward(_ptr(x), *strides(x), _ptr(codebooks), _ptr(index), _ptr(g_xq), *strides(g_xq),
-                                    _ptr(g_commit), b, t, d, k, q_total, q_used, _ptr(dx), *strides(dx), _ptr(dcb),
-                                    _ptr(ws), nbytes, _stream()), "agx_rvq_backward")
+    head = (_ptr(x), *strides(x), _ptr(codebooks), _ptr(index))
+    tail = (_ptr(g_xq), *strides(g_xq), _ptr(g_commit), b, t, d, k, q_total, q_used, _ptr(dx), *strides(dx), _ptr(dcb),
+            _ptr(ws), nbytes, _stream())
+    if stages is None:
+        _lib.check(lib.agx_rvq_backward(*head, *tail), "agx_rvq_backward")
+    else:
+        _lib.check(lib.agx_rvq_backward_staged(*head, _ptr(stages), *tail), "agx_rvq_backward_staged")
     return dx, dcb
 
 

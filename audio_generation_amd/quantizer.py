@@ -29,6 +29,12 @@ differentiable in the selected codewords; exactly zero for codes nobody chose, s
 ``"ema"`` codebooks are a buffer and get no gradient.  No ATen arithmetic runs between the encoder's output and the decoder's
 input, forward or backward.
 
+**Quantiser dropout** (build-defined).  ``stages=`` (a contiguous int64 ``(B,)`` device tensor the kernels read and
+the host never does) gives every batch row its own stage count ``q_b = clamp(stages[b], 0, q_used)``: row b of the call is exactly
+row b quantised alone with ``codebook_n = q_b`` -- ``index`` is -1 at its other stages, ``x_q`` sums its live stages only, the
+commit loss is the mean over rows of each row's own loss -- and in the backward the residual chain and the sums ``S_q`` of a
+frame run over its live stages only.  ``dropout_stages`` draws the tensor; the EMA update sees the masked index.
+
 **Not performed** (their definition lives in the absent ``som_quantizer``; parity unpinned): the SOM
 neighbourhood update (``use_som`` / ``som_kernel_type``, ``vae.py:249-250``), early-stage prioritisation
 (``prioritize_early``, ``training.py:325-328``) and stale-code replacement (``vq_cutoff_freq`` only feeds
@@ -97,20 +103,23 @@ class _QuantizeNative(torch.autograd.Function):
     """The training call: the search launch forward, ``agx_rvq_backward`` backward (module docstring, "Training")."""
 
     @staticmethod
-    def forward(ctx, x: Tensor, codebooks: Tensor, packed: Tensor, q_used: int, layout: str):
-        xq, index, _, commit = ops.rvq_forward(x.detach(), codebooks.detach(), packed, q_used, layout)
+    def forward(ctx, x: Tensor, codebooks: Tensor, packed: Tensor, q_used: int, layout: str, stages: Optional[Tensor] = None):
+        staged = {} if stages is None else {"stages": stages}
+        xq, index, _, commit = ops.rvq_forward(x.detach(), codebooks.detach(), packed, q_used, layout, **staged)
         ctx.layout = layout
-        ctx.save_for_backward(x, codebooks, index)     # the codebooks' version counter guards against an update in between
+        ctx.staged = stages is not None
+        # the version counters guard against an update of the codebooks, or a write into `stages`, in between
+        ctx.save_for_backward(x, codebooks, index, *(() if stages is None else (stages,)))
         ctx.mark_non_differentiable(index)
         ctx.set_materialize_grads(False)               # an unused output arrives as None, not as a frame-sized zero tensor
         return xq, index, commit
 
     @staticmethod
     def backward(ctx, g_xq, _g_index, g_commit):
-        x, codebooks, index = ctx.saved_tensors
+        x, codebooks, index, *rest = ctx.saved_tensors
         dx, dcb = ops.rvq_backward(x, codebooks, index, g_xq, g_commit, ctx.layout,
-                                   want_codebook_grad=ctx.needs_input_grad[1])
-        return (dx if ctx.needs_input_grad[0] else None), dcb, None, None, None
+                                   want_codebook_grad=ctx.needs_input_grad[1], **({"stages": rest[0]} if ctx.staged else {}))
+        return (dx if ctx.needs_input_grad[0] else None), dcb, None, None, None, None
 
 
 class ResidualQuantizer(nn.Module):
@@ -157,8 +166,12 @@ class ResidualQuantizer(nn.Module):
     def _q_used(self, codebook_n) -> int:
         return self.num_quantizers if codebook_n is None else max(0, min(int(codebook_n), self.num_quantizers))
 
-    def _quantize(self, x: Tensor, layout: str, codebook_n, update_codebook: bool, prioritize_early: bool = False):
+    def _quantize(self, x: Tensor, layout: str, codebook_n, update_codebook: bool, prioritize_early: bool = False,
+                  stages: Optional[Tensor] = None):
         q_used = self._q_used(codebook_n)
+        staged = {}                                   # stages=None: today's calls, argument for argument
+        if stages is not None:                        # refused before the first launch (the pack included)
+            staged = {"stages": ops._rvq_stages(type(self).__name__, stages, x)}
         if prioritize_early:
             _warn_once("prioritize_early",
                        "audio_generation_amd.ResidualQuantizer: prioritize_early=True is accepted but IGNORED -- its "
@@ -175,21 +188,39 @@ class ResidualQuantizer(nn.Module):
             packed = self._packed_codebooks()
             if update_codebook and self.training and self.quantizer_class != "base":
                 cb = cb.clone()     # the EMA update below overwrites the buffer before the backward reads the codewords
-            xq, index, commit = _QuantizeNative.apply(x, cb, packed, q_used, layout)
+            xq, index, commit = _QuantizeNative.apply(x, cb, packed, q_used, layout, staged.get("stages"))
         else:
-            xq, index, _, commit = ops.rvq_forward(x.detach(), cb.detach(), self._packed_codebooks(), q_used, layout)
+            xq, index, _, commit = ops.rvq_forward(x.detach(), cb.detach(), self._packed_codebooks(), q_used, layout, **staged)
         if update_codebook and self.training:
+            # (staged: the index is -1 at dead stages, which agx_rvq_ema_stats neither counts nor subtracts -- the
+            # statistics are those of the live stages only, and a stage no row ran has count 0 and is left untouched)
             frames = x if layout == "b l c" else x.transpose(1, 2)
             self._ema_update(frames.reshape(-1, self.dim), index.reshape(-1, q_used))
         return xq, index, commit
 
-    def quantize_bcl(self, x: Tensor, codebook_n=None, update_codebook=False, prioritize_early=False):
+    def quantize_bcl(self, x: Tensor, codebook_n=None, update_codebook=False, prioritize_early=False, *, stages=None):
         """Native entry used by ``CausalVQAE.encode``: (B,D,T) in, (B,D,T) out."""
-        return self._quantize(x, "b c l", codebook_n, update_codebook, prioritize_early)
+        return self._quantize(x, "b c l", codebook_n, update_codebook, prioritize_early, stages)
 
-    def forward(self, x: Tensor, codebook_n=None, update_codebook=False, prioritize_early=False):
-        """Reference call contract (vae.py:315-318): (B,T,D) -> (x_q, index, commit_loss)."""
-        return self._quantize(x, "b l c", codebook_n, update_codebook, prioritize_early)
+    def forward(self, x: Tensor, codebook_n=None, update_codebook=False, prioritize_early=False, *, stages=None):
+        """Reference call contract (vae.py:315-318): (B,T,D) -> (x_q, index, commit_loss).  ``stages`` (int64 (B,) on the
+        device; build-defined, module docstring "Quantiser dropout"): row b uses its first ``clamp(stages[b], 0, q_used)``
+        stages -- see ``dropout_stages``."""
+        return self._quantize(x, "b l c", codebook_n, update_codebook, prioritize_early, stages)
+
+    def dropout_stages(self, batch: int, p: float = 1.0, low: int = 1, generator: Optional[torch.Generator] = None) -> Tensor:
+        """The usual quantiser-dropout draw for one training call: an int64 ``(batch,)`` tensor on the codebooks' device, each row
+        uniform over ``low .. num_quantizers`` with probability ``p`` and ``num_quantizers`` otherwise.  Host arithmetic outside
+        the training call: drawn on the CPU from ``generator`` (a CPU ``torch.Generator``; None: the global one), so a seed
+        reproduces the tensor with or without a GPU, then copied over."""
+        q = self.num_quantizers
+        if not 0 <= int(low) <= q:
+            raise ValueError(f"dropout_stages: low={low} outside [0, {q}]")
+        if not 0.0 <= float(p) <= 1.0:
+            raise ValueError(f"dropout_stages: p={p} outside [0, 1]")
+        drawn = torch.randint(int(low), q + 1, (int(batch),), generator=generator, dtype=torch.int64)
+        drop = torch.rand(int(batch), generator=generator) < float(p)
+        return torch.where(drop, drawn, torch.full_like(drawn, q)).to(self.codebooks.device)
 
     # --------------------------------------------------------- training bookkeeping
     def _invalidate_packed(self) -> None:

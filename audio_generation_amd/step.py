@@ -31,15 +31,16 @@ Tensor = torch.Tensor
 def _generator_side(model, x: Tensor, *, sample_rate, frequency_filter, codebook_frequency_scale, noise_aug_scale,
                     pre_emphasis, spectrograms, spec_windows, spec_loss_weight, reconstruction_loss_weight,
                     sparsity_weight, use_reconstruction_loss, use_commit_loss, update_codebook, prioritize_early,
-                    codebook_n):
-    """training.py:313-361: everything before the discriminators -> (x, y, loss, parts)."""
+                    codebook_n, stages=None):
+    """training.py:313-361: everything before the discriminators -> (x, y, loss, parts).  ``stages`` (build-defined): the
+    per-row stage counts of quantiser dropout, handed to the model as they are; the low-pass cutoff still follows codebook_n."""
     parts: Dict[str, Tensor] = {}
     if frequency_filter is not None:                                               # training.py:313-318
         n = model.num_quantizers if codebook_n is None else codebook_n
         x = sg.lowpass_biquad(x, sample_rate, frequency_filter * (1 + n * codebook_frequency_scale))
     x_in = x + torch.randn_like(x) * noise_aug_scale if noise_aug_scale else x    # :320-323
     y, commit_loss, _ = model(x_in, update_codebook=update_codebook, prioritize_early=prioritize_early,
-                              codebook_n=codebook_n)                               # :325-328
+                              codebook_n=codebook_n, **({} if stages is None else {"stages": stages}))   # :325-328
     loss = y.new_zeros(())
     if use_reconstruction_loss:                                                    # :330-341
         if pre_emphasis is not None:
@@ -66,16 +67,17 @@ def training_losses(model, x: Tensor, discriminators: Sequence = (), *, sample_r
                     spec_loss_weight: float = 1.0, reconstruction_loss_weight: float = 1.0,
                     generator_loss_weight: float = 1.0, sparsity_weight: float = 0.0,
                     use_reconstruction_loss: bool = True, use_commit_loss: bool = True,
-                    update_codebook: bool = False, prioritize_early: bool = False, codebook_n=None
-                    ) -> Tuple[Tensor, Optional[Tensor], Dict[str, float]]:
-    """-> (generator-side loss, summed discriminator loss or None, {term: value})."""
+                    update_codebook: bool = False, prioritize_early: bool = False, codebook_n=None,
+                    stages: Optional[Tensor] = None) -> Tuple[Tensor, Optional[Tensor], Dict[str, float]]:
+    """-> (generator-side loss, summed discriminator loss or None, {term: value}).  ``stages``: quantiser dropout, an int64
+    (B,) device tensor of per-row stage counts (``model.quantizer.dropout_stages``), passed through to the model."""
     x, y, loss, parts = _generator_side(
         model, x, sample_rate=sample_rate, frequency_filter=frequency_filter,
         codebook_frequency_scale=codebook_frequency_scale, noise_aug_scale=noise_aug_scale, pre_emphasis=pre_emphasis,
         spectrograms=spectrograms, spec_windows=spec_windows, spec_loss_weight=spec_loss_weight,
         reconstruction_loss_weight=reconstruction_loss_weight, sparsity_weight=sparsity_weight,
         use_reconstruction_loss=use_reconstruction_loss, use_commit_loss=use_commit_loss,
-        update_codebook=update_codebook, prioritize_early=prioritize_early, codebook_n=codebook_n)
+        update_codebook=update_codebook, prioritize_early=prioritize_early, codebook_n=codebook_n, stages=stages)
     d_loss = None
     if discriminators:                                                             # :363-373
         d_loss = y.new_zeros(())
@@ -108,7 +110,8 @@ def training_backward(model, x: Tensor, discriminators: Sequence = (), *, genera
         model, x, **{**dict(sample_rate=24000, frequency_filter=None, codebook_frequency_scale=0.0, noise_aug_scale=0.0,
                             pre_emphasis=None, spectrograms=None, spec_windows=(), spec_loss_weight=1.0,
                             reconstruction_loss_weight=1.0, sparsity_weight=0.0, use_reconstruction_loss=True,
-                            use_commit_loss=True, update_codebook=False, prioritize_early=False, codebook_n=None),
+                            use_commit_loss=True, update_codebook=False, prioritize_early=False, codebook_n=None,
+                            stages=None),
                      **terms})
     if not discriminators:
         if loss.requires_grad:

@@ -494,14 +494,20 @@ class CausalVQAE(nn.Module):
             cache[which] = units
         return cache[which]
 
-    def encode(self, x, update_codebook=False, codebook_n=None, prioritize_early=False):
-        """vae.py:307-322 -> (x_q (B,C,T), commit_loss, index (B,T,Q))."""
+    def encode(self, x, update_codebook=False, codebook_n=None, prioritize_early=False, *, stages=None):
+        """vae.py:307-322 -> (x_q (B,C,T), commit_loss, index (B,T,Q)).  ``stages`` (build-defined): an int64 (B,)
+        device tensor, one stage count per batch row -- quantiser dropout in training (``quantizer.dropout_stages``), a per-row
+        bitrate in eval; index is -1 at the stages a row does not use."""
         z = self._run_encoders(self.rearrange_in(x))  # (B, D, T)
         q = self.quantizer
         if hasattr(q, "quantize_bcl"):
             # native quantiser: reads and writes the (B,D,T) layout directly, no transposes
+            staged = {} if stages is None else {"stages": stages}
             zq, index, commit = q.quantize_bcl(z, codebook_n, update_codebook=update_codebook,
-                                               prioritize_early=prioritize_early)
+                                               prioritize_early=prioritize_early, **staged)
+        elif stages is not None:
+            raise NotImplementedError(f"stages= needs the native quantiser: {type(q).__name__} has no quantize_bcl, and the "
+                                      "reference call contract (vae.py:315-318) has no per-row stage count")
         else:
             # any replacement bottleneck honouring the reference call contract (vae.py:315-318)
             zq, index, commit = q(z.transpose(1, 2), codebook_n, update_codebook=update_codebook,
@@ -509,9 +515,9 @@ class CausalVQAE(nn.Module):
             zq = zq.transpose(1, 2).contiguous()
         return zq, commit, index
 
-    def forward(self, x, update_codebook=False, codebook_n=None, prioritize_early=False):
-        """vae.py:293-305 -> (y, commit_loss, index)."""
-        zq, commit, index = self.encode(x, update_codebook, codebook_n, prioritize_early)
+    def forward(self, x, update_codebook=False, codebook_n=None, prioritize_early=False, *, stages=None):
+        """vae.py:293-305 -> (y, commit_loss, index).  ``stages``: as ``encode``."""
+        zq, commit, index = self.encode(x, update_codebook, codebook_n, prioritize_early, stages=stages)
         y = self.rearrange_out(self._run_decoders(zq))
         return y, commit, index
 

@@ -325,6 +325,40 @@ int agx_rvq_backward(const float *x, int64_t x_sb, int64_t x_st, int64_t x_sd, c
                      float *dx, int64_t d_sb, int64_t d_st, int64_t d_sd, float *dcodebooks,
                      void *workspace, size_t workspace_bytes, void *stream);
 
+/* ---- Per-row stage counts through the training call: quantiser dropout -----------------------------------------
+ * stages is a contiguous int64 (B,) device tensor read by the kernels, never by the host, as in the 4.25 block:
+ * q_b = clamp(stages[b], 0, q_used), stage q of frame (b, t) is live when q < q_b, and NULL means q_b = q_used for every row --
+ * then the two calls ARE agx_rvq_forward_ex and agx_rvq_backward, the same kernels and the same bits.  The search is greedy, so
+ * row b of a staged call is exactly row b quantised alone with q_used = q_b.
+ *
+ * agx_rvq_forward_staged: agx_rvq_forward_ex with stages after index.
+ *   index   : (B, T, q_used); the code where live, -1 where not.
+ *   xq      : ((0 + c_0) + c_1) + .. + c_{q_b - 1} in binary32, stage order; exact 0 for q_b == 0.
+ *   sq_err  : sq_err[q] = sum over the frames live at stage q of the squared residual left after that stage; exact 0.0 when no
+ *             frame is live.  commit_loss = sum_q sq_err[q] / (B T D): the mean over rows of what each row's own q_used = q_b
+ *             call returns.
+ *   The search still runs all q_used stages for every frame (one workgroup's 32 frames may belong to different rows, and
+ *   skipping would save nothing that matters): launches, refusals, LDS and workspace are those of agx_rvq_forward_ex.
+ * agx_rvq_backward_staged: agx_rvq_backward with stages after index; index as agx_rvq_forward_staged wrote it.  The residual
+ *   chain and the suffix sums S_q of frame (b, t) run over its live stages only:
+ *   dx[b, t]         = g_xq[b, t] + a S_0[b, t]  (g_xq alone when q_b == 0), a = 2 g_commit / (B T D) unchanged;
+ *   dcodebooks[q][k] = -a * sum of S_q over the frames live at q that chose k (the order and tree of agx_rvq_backward); exact 0
+ *                      for rows nobody chose and stages no row runs.
+ *   This is not agx_rvq_backward on the masked index: there an index of -1 subtracts nothing but the stage's residual still
+ *   enters the loss.  Workspace rows S_q of dead stages are not written (and never read).
+ * Both validate everything before the first launch. */
+int agx_rvq_forward_staged(const float *x, int64_t x_sb, int64_t x_st, int64_t x_sd,
+                           const float *codebooks /* (Q,K,D) */, const float *packed,
+                           int32_t batch, int32_t t, int32_t dim, int32_t k, int32_t q_used,
+                           float *xq, int64_t q_sb, int64_t q_st, int64_t q_sd,
+                           int64_t *index, const int64_t *stages /* may be NULL */, double *sq_err, float *commit_loss,
+                           void *workspace, size_t workspace_bytes, void *stream);
+int agx_rvq_backward_staged(const float *x, int64_t x_sb, int64_t x_st, int64_t x_sd, const float *codebooks,
+                            const int64_t *index, const int64_t *stages /* may be NULL */, const float *g_xq, int64_t g_sb,
+                            int64_t g_st, int64_t g_sd, const float *g_commit, int32_t batch, int32_t t, int32_t dim, int32_t k,
+                            int32_t n_q, int32_t q_used, float *dx, int64_t d_sb, int64_t d_st, int64_t d_sd, float *dcodebooks,
+                            void *workspace, size_t workspace_bytes, void *stream);
+
 /* ------------------------------------------------------------------------- *
  * Activation planes (bf16x3 arithmetic, round 4)                              *
  * ------------------------------------------------------------------------- *
