@@ -353,7 +353,22 @@ SIGNATURES = {
     "agx_conv_stream_step_affine_counted": (c_int, [c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, c_float, c_void_p,
                                                     c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_void_p, c_int32, c_void_p, c_int32,
                                                     c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int64, c_void_p]),
+    # code prior
+    "agx_codes_embed": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_int32, c_void_p]),
+    "agx_codes_embed_backward_workspace_bytes": (c_size_t, [c_int32, c_int32, c_int32, c_int32]),
+    "agx_codes_embed_backward": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_int32, c_void_p,
+                                         c_size_t, c_void_p]),
+    "agx_codes_cross_entropy_workspace_bytes": (c_size_t, [c_int32, c_int32, c_int32]),
+    "agx_codes_cross_entropy": (c_int, [c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_void_p, c_void_p, c_void_p,
+                                        c_void_p, c_void_p, c_size_t, c_void_p]),
+    "agx_codes_cross_entropy_backward": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32,
+                                                 c_int32, c_void_p, c_void_p]),
+    "agx_codes_sample": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                 c_void_p, c_int32, c_int32, c_int32, c_int32, c_void_p]),
 }
+
+CODES_SAMPLE_MAX_K = 2048   # AGX_CODES_SAMPLE_MAX_K: the codes per stage agx_codes_sample orders in LDS
+CODES_SAMPLE_STREAM = 0x53414D50   # AGX_CODES_SAMPLE_STREAM: word 3 of the sampler's Philox counter
 
 _lib = None
 

@@ -2744,3 +2744,185 @@ def wavelet_stream_out_step(hidden: int, c_out: int, kernel: int, scale: int, pa
     if tok is not None:
         _observer.end(tok)
     return dst
+
+
+# --------------------------------------------------------------------------- code prior
+CODES_SAMPLE_MAX_K = _lib.CODES_SAMPLE_MAX_K
+
+
+def _prior_tensor(op: str, what: str, t, dtype, shape: tuple, device=None) -> Tensor:
+    """An operand of the code-prior ops as the kernels read it: a contiguous tensor of ``dtype`` and ``shape`` (an entry of
+    ``shape`` that is None is free), on ``device`` when one is given."""
+    if not isinstance(t, Tensor) or t.dtype != dtype or t.dim() != len(shape) or \
+            any(want is not None and have != want for have, want in zip(t.shape, shape)):
+        have = f"{tuple(t.shape)} {t.dtype}" if isinstance(t, Tensor) else type(t).__name__
+        raise AgxError(f"{op}: {what} must be a {dtype} tensor of shape {tuple('*' if s is None else s for s in shape)}, got {have}")
+    if not t.is_contiguous():
+        raise AgxError(f"{op}: {what} is not contiguous (stride {tuple(t.stride())})")
+    if device is not None and t.device != device:
+        raise AgxError(f"{op}: {what} is on '{t.device}', the operands are on '{device}'")
+    return t
+
+
+def _prior_sizes(op: str, sizes: Optional[Sequence[int]], n_q: int, k: int):
+    """``sizes`` as a host int32 array (None: every stage has ``k`` codes), refused here when a stage lies outside 1 .. k."""
+    if n_q > 64:
+        raise AgxError(f"{op}: at most 64 stages, got {n_q}")
+    if sizes is None:
+        return None
+    sizes = [int(v) for v in sizes]
+    if len(sizes) != n_q or any(not 1 <= v <= k for v in sizes):
+        raise AgxError(f"{op}: sizes {sizes} for {n_q} stages of at most {k} codes")
+    return (ctypes.c_int32 * n_q)(*sizes)
+
+
+def _arr_ptr(arr):
+    return None if arr is None else ctypes.cast(arr, ctypes.c_void_p)
+
+
+def codes_embed(index: Tensor, tables: Tensor, counts: Optional[Tensor] = None) -> Tensor:
+    """Gather-sum of one table row per stage (``agx_codes_embed``, one launch): index (B, n, Q) int64, tables (Q, R, D) fp32 ->
+    (B, D, n) fp32, channel-major, ``out[b, :, i] = ((0 + tables[0][index[b,i,0]]) + tables[1][index[b,i,1]]) + ...`` in stage
+    order.  An index outside [0, R) -- ``-1`` above all -- contributes nothing; ``counts`` (int64 (B,), device): the columns at or
+    behind ``clamp(counts[b], 0, n)`` are exact 0."""
+    op = "codes_embed"
+    _need_gpu(index, tables, counts)
+    tables = _prior_tensor(op, "tables", tables, torch.float32, (None, None, None))
+    n_q, r, d = tables.shape
+    index = _prior_tensor(op, "index", index, torch.int64, (None, None, n_q), tables.device)
+    b, n, _ = index.shape
+    _prior_sizes(op, None, n_q, r)
+    if b < 1 or n < 1 or r < 1 or d < 1:
+        raise AgxError(f"{op}: empty operands: index {tuple(index.shape)}, tables {tuple(tables.shape)}")
+    if counts is not None:
+        counts = _checked_counts(op, counts, b, tables.device)
+    out = torch.empty((b, d, n), dtype=torch.float32, device=tables.device)
+    tok = _observer.begin("other", (op, 4 * (b * n * n_q * d + b * d * n) + 8 * b * n * n_q, 0)) if _observer is not None else None
+    _lib.check(_lib.load().agx_codes_embed(_ptr(tables), _ptr(index), _ptr(counts), _ptr(out), b, n, n_q, r, d, _stream()),
+               "agx_codes_embed")
+    if tok is not None:
+        _observer.end(tok)
+    return out
+
+
+def codes_embed_backward(dout: Tensor, index: Tensor, rows: int, counts: Optional[Tensor] = None) -> Tensor:
+    """Backward of ``codes_embed`` for the tables (``agx_codes_embed_backward``): dout (B, D, n) fp32, index (B, n, Q) -> dtables
+    (Q, rows, D), ``dtables[q][r]`` the sum of ``dout[b, :, i]`` over the frames with ``index[b,i,q] == r`` below the row's count,
+    taken in frame order on one chain per element: no atomics, two calls agree bit for bit, exact 0 for a row nobody chose."""
+    op = "codes_embed_backward"
+    _need_gpu(dout, index, counts)
+    dout = _prior_tensor(op, "dout", dout, torch.float32, (None, None, None))
+    b, d, n = dout.shape
+    index = _prior_tensor(op, "index", index, torch.int64, (b, n, None), dout.device)
+    n_q, rows = index.shape[2], int(rows)
+    _prior_sizes(op, None, n_q, rows)
+    if b < 1 or n < 1 or n_q < 1 or rows < 1 or d < 1:
+        raise AgxError(f"{op}: empty operands: dout {tuple(dout.shape)}, index {tuple(index.shape)}, rows = {rows}")
+    if counts is not None:
+        counts = _checked_counts(op, counts, b, dout.device)
+    lib = _lib.load()
+    dtables = torch.empty((n_q, rows, d), dtype=torch.float32, device=dout.device)
+    nbytes = int(lib.agx_codes_embed_backward_workspace_bytes(b, n, n_q, d))
+    ws = _workspace(nbytes, dout.device, "agx_codes_embed_backward_workspace_bytes")
+    _lib.check(lib.agx_codes_embed_backward(_ptr(dout), _ptr(index), _ptr(counts), _ptr(dtables), b, n, n_q, rows, d, _ptr(ws), nbytes,
+                                            _stream()), "agx_codes_embed_backward")
+    return dtables
+
+
+def _ce_operands(op: str, logits: Tensor, target: Tensor, sizes):
+    logits = _prior_tensor(op, "logits", logits, torch.float32, (None, None, None))
+    b, c, t = logits.shape
+    target = _prior_tensor(op, "target", target, torch.int64, (b, t, None), logits.device)
+    n_q = target.shape[2]
+    if b < 1 or t < 1 or n_q < 1 or c < 1 or c % n_q:
+        raise AgxError(f"{op}: logits {tuple(logits.shape)} are not (B, Q K, T) for target {tuple(target.shape)} = (B, T, Q)")
+    k = c // n_q
+    return logits, target, b, t, n_q, k, _prior_sizes(op, sizes, n_q, k)
+
+
+def codes_cross_entropy(logits: Tensor, target: Tensor, sizes: Optional[Sequence[int]] = None):
+    """Cross-entropy of a code prior (``agx_codes_cross_entropy``): logits (B, Q K, T) fp32 -- channel ``q K + k``, the head conv's
+    output as it stands --, target (B, T, Q) int64, ``sizes[q] <= K`` the codes of stage q -> (loss 0-d fp32, nll (B, T, Q), lse
+    (B, T, Q), n_live 0-d int64).  Entry (b, t, q) is live when ``0 <= target < sizes[q]``; ``lse`` runs over ``k < sizes[q]``;
+    ``nll = lse - logit[target]``, exact 0 where dead; ``loss = sum(nll) / n_live`` with the count taken on the device, 0 when
+    nothing is live.  The sum runs in a fixed order: two calls agree bit for bit."""
+    op = "codes_cross_entropy"
+    _need_gpu(logits, target)
+    logits, target, b, t, n_q, k, arr = _ce_operands(op, logits, target, sizes)
+    lib = _lib.load()
+    nll = torch.empty((b, t, n_q), dtype=torch.float32, device=logits.device)
+    lse = torch.empty((b, t, n_q), dtype=torch.float32, device=logits.device)
+    loss = torch.empty((), dtype=torch.float32, device=logits.device)
+    n_live = torch.empty((), dtype=torch.int64, device=logits.device)
+    nbytes = int(lib.agx_codes_cross_entropy_workspace_bytes(b, t, n_q))
+    ws = _workspace(nbytes, logits.device, "agx_codes_cross_entropy_workspace_bytes")
+    tok = _observer.begin("other", (op, 4 * logits.numel() + 16 * target.numel(), 0)) if _observer is not None else None
+    _lib.check(lib.agx_codes_cross_entropy(_ptr(logits), _ptr(target), _arr_ptr(arr), b, t, n_q, k, _ptr(nll), _ptr(lse), _ptr(loss),
+                                           _ptr(n_live), _ptr(ws), nbytes, _stream()), "agx_codes_cross_entropy")
+    if tok is not None:
+        _observer.end(tok)
+    return loss, nll, lse, n_live
+
+
+def codes_cross_entropy_backward(logits: Tensor, target: Tensor, lse: Tensor, n_live: Tensor, g: Tensor,
+                                 sizes: Optional[Sequence[int]] = None) -> Tensor:
+    """Backward of ``codes_cross_entropy`` from its ``lse`` and ``n_live`` and ``g``, one fp32 on the device (the gradient of the
+    loss; never read on the host) -> dlogits (B, Q K, T), ``g (softmax - onehot) / n_live`` at live entries, exact 0 at dead ones
+    and at ``k >= sizes[q]``."""
+    op = "codes_cross_entropy_backward"
+    _need_gpu(logits, target, lse, n_live, g)
+    logits, target, b, t, n_q, k, arr = _ce_operands(op, logits, target, sizes)
+    lse = _prior_tensor(op, "lse", lse, torch.float32, (b, t, n_q), logits.device)
+    if not isinstance(n_live, Tensor) or n_live.dtype != torch.int64 or n_live.numel() != 1 or n_live.device != logits.device:
+        raise AgxError(f"{op}: n_live must be the one-element int64 device tensor the forward returned")
+    if not isinstance(g, Tensor) or g.dtype != torch.float32 or g.numel() != 1 or g.device != logits.device:
+        raise AgxError(f"{op}: g must hold one float32 on the operands' device")
+    dlogits = torch.empty(logits.shape, dtype=torch.float32, device=logits.device)
+    tok = _observer.begin("other", (op, 8 * logits.numel(), 0)) if _observer is not None else None
+    _lib.check(_lib.load().agx_codes_cross_entropy_backward(_ptr(logits), _ptr(target), _arr_ptr(arr), _ptr(lse), _ptr(n_live), _ptr(g),
+                                                            b, t, n_q, k, _ptr(dlogits), _stream()), "agx_codes_cross_entropy_backward")
+    if tok is not None:
+        _observer.end(tok)
+    return dlogits
+
+
+def codes_sample(logits: Tensor, n_q: int, seeds: Tensor, frame0: Tensor, temperature: Tensor, top_k: Tensor, top_p: Tensor,
+                 sizes: Optional[Sequence[int]] = None, counts: Optional[Tensor] = None, stages: Optional[Tensor] = None,
+                 carry: Optional[Tensor] = None) -> Tensor:
+    """Temperature / top-k / top-p sampling on the device (``agx_codes_sample``, one launch): logits (B, n_q K, n) fp32 -> codes
+    (B, n, n_q) int64, ``K <= CODES_SAMPLE_MAX_K``.  Per row, all on the device: ``seeds`` and ``frame0`` int64 (B,) -- frame i of row
+    b draws at Philox counter ``(frame0[b] + i, q)`` under key ``seeds[b]`` --, ``temperature`` fp32 (``<= 0``: the argmax),
+    ``top_k`` int64 (``<= 0``: off), ``top_p`` fp32 (``>= 1``: off).  include/agx.h "Code prior" states the contract of a row; a draw
+    is a pure function of (seed, frame, stage, logits, settings).  ``counts`` / ``stages``: -1 behind a row's frame count or stage
+    count.  ``carry`` (B, n_q) int64, in/out: takes the codes of frame ``c_b - 1`` where ``c_b >= 1``, untouched otherwise."""
+    op = "codes_sample"
+    _need_gpu(logits, seeds, frame0, temperature, top_k, top_p, counts, stages, carry)
+    logits = _prior_tensor(op, "logits", logits, torch.float32, (None, None, None))
+    b, c, n = logits.shape
+    n_q = int(n_q)
+    if b < 1 or n < 1 or n_q < 1 or c < 1 or c % n_q:
+        raise AgxError(f"{op}: logits {tuple(logits.shape)} are not (B, Q K, n) for Q = {n_q}")
+    k = c // n_q
+    if k > CODES_SAMPLE_MAX_K:
+        raise AgxError(f"{op}: K = {k} codes per stage exceed CODES_SAMPLE_MAX_K = {CODES_SAMPLE_MAX_K}")
+    arr = _prior_sizes(op, sizes, n_q, k)
+    dev = logits.device
+    seeds = _prior_tensor(op, "seeds", seeds, torch.int64, (b,), dev)
+    frame0 = _prior_tensor(op, "frame0", frame0, torch.int64, (b,), dev)
+    temperature = _prior_tensor(op, "temperature", temperature, torch.float32, (b,), dev)
+    top_k = _prior_tensor(op, "top_k", top_k, torch.int64, (b,), dev)
+    top_p = _prior_tensor(op, "top_p", top_p, torch.float32, (b,), dev)
+    if counts is not None:
+        counts = _checked_counts(op, counts, b, dev)
+    if stages is not None:
+        stages = _checked_stages(op, stages, b, dev)
+    if carry is not None:
+        carry = _prior_tensor(op, "carry", carry, torch.int64, (b, n_q), dev)
+    codes = torch.empty((b, n, n_q), dtype=torch.int64, device=dev)
+    tok = _observer.begin("other", (op, 4 * logits.numel() + 8 * codes.numel(), 0)) if _observer is not None else None
+    _lib.check(_lib.load().agx_codes_sample(_ptr(logits), _arr_ptr(arr), _ptr(seeds), _ptr(frame0), _ptr(temperature), _ptr(top_k),
+                                            _ptr(top_p), _ptr(counts), _ptr(stages), _ptr(carry), _ptr(codes), b, n, n_q, k, _stream()),
+               "agx_codes_sample")
+    if tok is not None:
+        _observer.end(tok)
+    return codes

@@ -616,6 +616,17 @@ class CausalVQAE(nn.Module):
                                         accumulate=zq is not None)
             return self.decode(zq.transpose(1, 2).contiguous()), index
 
+    def decode_codes(self, index: Tensor) -> Tensor:
+        """Codes -> waveform: index (B, T, q) int64, q <= Q -> ``decode`` of the sum of the codewords of the first q stages, which
+        ``ops.codes_embed`` forms in ONE launch (``decompress`` takes one per stage) and in the same stage order.  A ``-1`` -- a
+        stage a row does not use (``compress_stream(stages=)``, ``CodePrior.step(stages=)``) -- contributes nothing."""
+        cb = self.quantizer.codebooks.detach()
+        if not isinstance(index, Tensor) or index.dim() != 3 or not 1 <= index.shape[2] <= cb.shape[0]:
+            raise AgxError(f"decode_codes: index must be (B, T, q) with 1 <= q <= {cb.shape[0]}, got "
+                           f"{tuple(index.shape) if isinstance(index, Tensor) else type(index).__name__}")
+        with torch.no_grad():
+            return self.decode(ops.codes_embed(index.contiguous(), cb[:index.shape[2]]))
+
     def compress_stream(self, x_chunk, stream, codebook_n=None, counts=None, stages=None):
         """The sender's step of a live stream: the next ``n`` whole frames of every row -> (packets (B, P) uint8, index (B, n, Q)),
         ``P = ceil(n Q bits / 8)``.  Row ``b``'s first ``ceil(c_b Q bits / 8)`` bytes are its packet -- ``ops.codes_pack`` of its

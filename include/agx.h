@@ -1403,6 +1403,71 @@ int agx_conv_stream_step_affine_counted(int32_t kind, int32_t c_in, int32_t c_ou
                                         float *dst, int32_t dst_cap, const int64_t *pos, const int64_t *end, const int64_t *counts,
                                         int32_t batch, int32_t n, int32_t rate_in, int64_t delay_in, void *stream);
 
+/* ---- Code prior (csrc/prior.hip) --------------------------------------------------------------------------------
+ * The operations between a Transformer and the quantiser's codes.  Operands are fp32 or int64, contiguous; every argument is
+ * validated before the first launch; no call allocates or reads device data on the host, so every call can be captured.
+ * n_q <= 64 (AGX_ERR_UNSUPPORTED beyond).  `sizes` (HOST, n_q int32, 1 <= sizes[q] <= k; NULL: k everywhere) travels by value.
+ * `counts` / `stages` (int64 (B,), device, may be NULL) follow "Per-row frame counts" / "Per-row stage counts": c_b =
+ * clamp(counts[b], 0, n), q_b = clamp(stages[b], 0, n_q), NULL = n / n_q.
+ *
+ * agx_codes_embed: tables (n_q, rows, dim), index (B, n, n_q) -> out (B, dim, n), channel-major:
+ *     out[b, :, i] = ((0 + tables[0][index[b,i,0]]) + tables[1][index[b,i,1]]) + ...      in binary32, in stage order;
+ * an index outside [0, rows) contributes nothing (this covers -1); the columns i >= c_b are exact 0 and their indices are not
+ * read.  One launch for all stages. */
+int agx_codes_embed(const float *tables, const int64_t *index, const int64_t *counts /* may be NULL */, float *out, int32_t batch,
+                    int32_t n, int32_t n_q, int32_t rows, int32_t dim, void *stream);
+/* Its backward: dout (B, dim, n) -> dtables (n_q, rows, dim), every element written:
+ *     dtables[q][r] = the sum of dout[b, :, i] over the frames (b, i), i < c_b, with index[b,i,q] == r,
+ * ONE binary32 chain per element that starts at 0 and takes the frames in ascending (b, i) order -- no float atomics, two calls
+ * agree bit for bit (the convention of agx_rvq_backward's dcodebooks); exact 0 for a row nobody chose.  Three launches (dout as
+ * rows, the index as int32 per stage, the sums).  The workspace (8-byte aligned, AGX_ERR_WORKSPACE when short) is
+ * agx_codes_embed_backward_workspace_bytes(batch, n, n_q, dim) = B n (4 dim + 4 n_q) bytes rounded up to 8 twice. */
+size_t agx_codes_embed_backward_workspace_bytes(int32_t batch, int32_t n, int32_t n_q, int32_t dim);
+int agx_codes_embed_backward(const float *dout, const int64_t *index, const int64_t *counts /* may be NULL */, float *dtables,
+                             int32_t batch, int32_t n, int32_t n_q, int32_t rows, int32_t dim, void *workspace, size_t workspace_bytes,
+                             void *stream);
+/* agx_codes_cross_entropy: logits (B, n_q * k, t) -- the head conv's output as it stands, channel q * k + c --, target (B, t, n_q).
+ * Entry (b, t, q) is live when 0 <= target < sizes[q].  lse[b,t,q] = log sum_{c < sizes[q]} exp(logit_c) (online maximum and sum,
+ * binary32); nll[b,t,q] = lse - logit[target]; both exact 0 where dead.  *n_live (int64) = the live entries, counted on the device;
+ * *loss = sum(nll) / n_live, 0 when n_live == 0.  The sum runs in a fixed order in two stages -- the 64 entries of a workgroup on a
+ * tree, then the workgroups' partials (binary64) in ascending order on a tree of 256: two launches, no atomics.  The maximum and
+ * the sum of an entry are formed over four quarters of k and merged in ascending order.  Workspace:
+ * agx_codes_cross_entropy_workspace_bytes(batch, t, n_q) = 16 ceil(B t n_q / 64) bytes, 8-byte aligned.  B t n_q <= 2^36. */
+size_t agx_codes_cross_entropy_workspace_bytes(int32_t batch, int32_t t, int32_t n_q);
+int agx_codes_cross_entropy(const float *logits, const int64_t *target, const int32_t *sizes /* host, may be NULL */, int32_t batch,
+                            int32_t t, int32_t n_q, int32_t k, float *nll, float *lse, float *loss, int64_t *n_live, void *workspace,
+                            size_t workspace_bytes, void *stream);
+/* Its backward, from the forward's lse and n_live and one device float g (the gradient of loss): every element of dlogits
+ * (B, n_q * k, t) is written,
+ *     dlogits[b, q k + c, t] = g * (exp(logit_c - lse) - [c == target]) / n_live      at live entries, c < sizes[q],
+ * and exact 0 at dead entries, at c >= sizes[q] and everywhere when n_live == 0.  One launch. */
+int agx_codes_cross_entropy_backward(const float *logits, const int64_t *target, const int32_t *sizes /* host, may be NULL */,
+                                     const float *lse, const int64_t *n_live, const float *g, int32_t batch, int32_t t, int32_t n_q,
+                                     int32_t k, float *dlogits, void *stream);
+/* agx_codes_sample: logits (B, n_q * k, n) -> codes (B, n, n_q) int64.  seeds, frame0, top_k: int64 (B,); temperature, top_p:
+ * fp32 (B,) -- per row, so one captured step serves rows with different settings.  k <= AGX_CODES_SAMPLE_MAX_K
+ * (AGX_ERR_UNSUPPORTED beyond: the order and the prefix sums of one stage live in LDS).
+ * Row (b, i, q), i < c_b, q < q_b, over l_c, c < sizes[q]; every decision is made in binary64:
+ *   1. tau = temperature[b] <= 0: the code is the argmax, the lowest c on ties.  Otherwise:
+ *   2. the codes are ordered by (l_c descending, c ascending); the comparisons are exact (-0 == +0).
+ *   3. top_k[b] > 0 keeps the first min(top_k, size) of that order.
+ *   4. z = (double)l / (double)tau; e = exp(z - z_max) (1 where z == z_max); C_j = the prefix sums of e in that order.
+ *   5. top_p[b] < 1 keeps the shortest prefix with C_j / C_all >= top_p, and at least one code.
+ *   6. u = (w + 0.5) / 2^32, w = word 0 of Philox4x32-10 ("Dropout masks": the generator) at the counter
+ *      (lo32(f), hi32(f), q, AGX_CODES_SAMPLE_STREAM), f = frame0[b] + i, under the key (lo32(seeds[b]), hi32(seeds[b])).
+ *   7. the code is the first j of the kept prefix with C_j >= u * C_kept.
+ * The prefix sums may be formed in any order of additions (a workgroup scan): a result is pinned where the decisions of 5 and 7
+ * hold with a margin of 2^-36 of the kept mass (tests/prior_ref.py "decided").  codes is -1 at i >= c_b and at q >= q_b.
+ * `carry` (B, n_q) int64, may be NULL: carry[b] becomes the codes of frame c_b - 1 when c_b >= 1 and is untouched otherwise -- a
+ * paused row changes nothing.  A draw is a pure function of (seed, f, q, logits, settings): not of the chunking, the batch slot
+ * or a replay count.  NaN logits or settings give an unspecified code in [-1, size); no write goes out of bounds. */
+#define AGX_CODES_SAMPLE_MAX_K 2048
+#define AGX_CODES_SAMPLE_STREAM 0x53414D50u /* "SAMP": apart from every dropout site's stream id (4 l + 0 .. 3) */
+int agx_codes_sample(const float *logits, const int32_t *sizes /* host, may be NULL */, const int64_t *seeds, const int64_t *frame0,
+                     const float *temperature, const int64_t *top_k, const float *top_p, const int64_t *counts /* may be NULL */,
+                     const int64_t *stages /* may be NULL */, int64_t *carry /* may be NULL, in/out */, int64_t *codes, int32_t batch,
+                     int32_t n, int32_t n_q, int32_t k, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
