@@ -8,4 +8,4 @@ does not load the shared library; the first op call does, and raises if
 """
 from ._lib import AgxError, LIB_PATH  # noqa: F401
 
-__all__ = ["AgxError", "LIB_PATH", "vae", "quantizer", "conditioning", "activations", "ops", "prior"]
+__all__ = ["AgxError", "LIB_PATH", "vae", "quantizer", "conditioning", "activations", "ops", "prior", "entropy"]

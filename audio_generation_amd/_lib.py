@@ -365,10 +365,21 @@ SIGNATURES = {
                                                  c_int32, c_void_p, c_void_p]),
     "agx_codes_sample": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                  c_void_p, c_int32, c_int32, c_int32, c_int32, c_void_p]),
+    # entropy coding
+    "agx_codes_cum": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32,
+                              c_void_p]),
+    "agx_codes_rans_encode": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_int32,
+                                      c_int32, c_int32, c_void_p]),
+    "agx_codes_rans_decode": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                      c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, c_void_p]),
 }
 
 CODES_SAMPLE_MAX_K = 2048   # AGX_CODES_SAMPLE_MAX_K: the codes per stage agx_codes_sample orders in LDS
 CODES_SAMPLE_STREAM = 0x53414D50   # AGX_CODES_SAMPLE_STREAM: word 3 of the sampler's Philox counter
+RANS_SCALE_BITS = 16         # AGX_RANS_SCALE_BITS: a frequency table sums to 2^16
+RANS_L = 1 << 23             # AGX_RANS_L: the lower bound of the coder's state
+CODES_CUM_MAX_K = 2048       # AGX_CODES_CUM_MAX_K: the codes per stage agx_codes_cum scans in LDS
+RANS_MAX_SYMBOLS = 8192      # AGX_RANS_MAX_SYMBOLS: the symbols per row the coder keeps in LDS
 
 _lib = None
 

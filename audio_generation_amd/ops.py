@@ -2926,3 +2926,147 @@ def codes_sample(logits: Tensor, n_q: int, seeds: Tensor, frame0: Tensor, temper
     if tok is not None:
         _observer.end(tok)
     return codes
+
+
+# --------------------------------------------------------------------------- entropy coding
+RANS_SCALE_BITS = _lib.RANS_SCALE_BITS
+RANS_M = 1 << _lib.RANS_SCALE_BITS
+RANS_L = _lib.RANS_L
+RANS_MAX_SYMBOLS = _lib.RANS_MAX_SYMBOLS
+CODES_CUM_MAX_K = _lib.CODES_CUM_MAX_K
+
+
+def _entropy_limits(op: str, n_q: int, k: int, symbols: Optional[int] = None) -> None:
+    """The refusals of include/agx.h "Entropy coding" that need no tensor, made on the host before anything else."""
+    if n_q > 64:
+        raise AgxError(f"{op}: at most 64 stages, got {n_q}")
+    if k > CODES_CUM_MAX_K:
+        raise AgxError(f"{op}: K = {k} codes per stage exceed CODES_CUM_MAX_K = {CODES_CUM_MAX_K}")
+    if symbols is not None and symbols > RANS_MAX_SYMBOLS:
+        raise AgxError(f"{op}: n Q = {symbols} symbols per row exceed RANS_MAX_SYMBOLS = {RANS_MAX_SYMBOLS}")
+
+
+def _need_gpu_tables(t: Optional[Tensor]) -> None:
+    """``_need_gpu`` for the int32 frequency tables, the one operand of this library outside ``_DTYPES``."""
+    if t is not None and not t.is_cuda:
+        raise AgxError(f"audio_generation_amd runs on the MI355X only: got a tensor on '{t.device}'.  There is no CPU / eager fallback.")
+
+
+def _entropy_rows(op: str, b: int, dev, counts, stages):
+    if counts is not None:
+        counts = _checked_counts(op, counts, b, dev)
+    if stages is not None:
+        stages = _checked_stages(op, stages, b, dev)
+    return counts, stages
+
+
+def codes_cum(logits: Tensor, n_q: int, sizes: Optional[Sequence[int]] = None, counts: Optional[Tensor] = None,
+              stages: Optional[Tensor] = None, out: Optional[Tensor] = None, frame0: int = 0) -> Tensor:
+    """Logits -> exactly normalised integer frequency tables (``agx_codes_cum``, one launch): logits (B, n_q K, n) fp32 -> cum
+    int32 (B, n, n_q, K + 1), ``cum[b, i, q]`` the exclusive prefix sums of the frequencies of stage q at frame i: ``cum[0] == 0``,
+    strictly increasing below ``sizes[q]``, ``RANS_M`` from there on; include/agx.h "Entropy coding" states the contract of an
+    entry.  ``counts`` / ``stages``: the tables behind a row's frame count or stage count are exact 0 and their logits are not
+    read.  ``out`` (int32 (B, n_out, n_q, K + 1)) with ``frame0``: the call's frames land at ``out[:, frame0:frame0 + n]`` and
+    nothing else of ``out`` is touched -- a hop's tables gathered from one-frame steps.  ``K <= CODES_CUM_MAX_K``."""
+    op = "codes_cum"
+    logits = _prior_tensor(op, "logits", logits, torch.float32, (None, None, None))
+    b, c, n = logits.shape
+    n_q, frame0 = int(n_q), int(frame0)
+    if b < 1 or n < 1 or n_q < 1 or c < 1 or c % n_q:
+        raise AgxError(f"{op}: logits {tuple(logits.shape)} are not (B, Q K, n) for Q = {n_q}")
+    k = c // n_q
+    _entropy_limits(op, n_q, k)
+    arr = _prior_sizes(op, sizes, n_q, k)
+    if out is not None:
+        out = _prior_tensor(op, "out", out, torch.int32, (b, None, n_q, k + 1), logits.device)
+        if not 0 <= frame0 <= out.shape[1] - n:
+            raise AgxError(f"{op}: frames {frame0} .. {frame0 + n - 1} do not lie in a table buffer of {out.shape[1]} frames")
+    elif frame0:
+        raise AgxError(f"{op}: frame0 = {frame0} without a table buffer")
+    _need_gpu(logits, counts, stages)
+    _need_gpu_tables(out)
+    counts, stages = _entropy_rows(op, b, logits.device, counts, stages)
+    if out is None:
+        out = torch.empty((b, n, n_q, k + 1), dtype=torch.int32, device=logits.device)
+    tok = _observer.begin("other", (op, 4 * logits.numel() + 4 * b * n * n_q * (k + 1), 0)) if _observer is not None else None
+    _lib.check(_lib.load().agx_codes_cum(_ptr(logits), _arr_ptr(arr), _ptr(counts), _ptr(stages), _ptr(out), b, n, n_q, k, out.shape[1],
+                                         frame0, _stream()), "agx_codes_cum")
+    if tok is not None:
+        _observer.end(tok)
+    return out
+
+
+def _rans_tables(op: str, cum: Tensor):
+    if not isinstance(cum, Tensor) or cum.dim() != 4:
+        raise AgxError(f"{op}: cum must be an int32 (B, n, Q, K + 1) tensor, got "
+                       f"{tuple(cum.shape) if isinstance(cum, Tensor) else type(cum).__name__}")
+    cum = _prior_tensor(op, "cum", cum, torch.int32, (None, None, None, None))
+    b, n, n_q, k1 = cum.shape
+    if b < 1 or n < 1 or n_q < 1 or k1 < 2:
+        raise AgxError(f"{op}: cum {tuple(cum.shape)} is not (B, n, Q, K + 1)")
+    _entropy_limits(op, n_q, k1 - 1, n * n_q)
+    return cum, b, n, n_q, k1 - 1
+
+
+def codes_rans_encode(cum: Tensor, codes: Tensor, sizes: Optional[Sequence[int]] = None, counts: Optional[Tensor] = None,
+                      stages: Optional[Tensor] = None):
+    """Byte-wise rANS of a hop (``agx_codes_rans_encode``, one launch, one wave per row): cum int32 (B, n, Q, K + 1)
+    (``codes_cum``), codes int64 (B, n, Q) -> (packets uint8 (B, 2 n Q + 4), nbytes int64 (B,), status int64 (B,)).  Row b's
+    packet is its first ``nbytes[b]`` bytes -- 0 when the row codes nothing -- and every byte behind them is 0; its symbols are
+    its live entries (``counts`` / ``stages``) in (frame, stage) order.  ``status``: bit 0 when a live code lay outside its stage
+    (it is skipped).  The bytes are pinned by include/agx.h "Entropy coding" (tests/entropy_ref.py mirrors them in Python ints)."""
+    op = "codes_rans_encode"
+    cum, b, n, n_q, k = _rans_tables(op, cum)
+    codes = _prior_tensor(op, "codes", codes, torch.int64, (b, n, n_q), cum.device)
+    arr = _prior_sizes(op, sizes, n_q, k)
+    _need_gpu_tables(cum)
+    _need_gpu(codes, counts, stages)
+    counts, stages = _entropy_rows(op, b, cum.device, counts, stages)
+    packets = torch.empty((b, 2 * n * n_q + 4), dtype=torch.uint8, device=cum.device)
+    nbytes = torch.empty((b,), dtype=torch.int64, device=cum.device)
+    status = torch.empty((b,), dtype=torch.int64, device=cum.device)
+    tok = _observer.begin("other", (op, 8 * codes.numel() + 8 * codes.numel() + packets.numel(), 0)) if _observer is not None else None
+    _lib.check(_lib.load().agx_codes_rans_encode(_ptr(cum), _ptr(codes), _arr_ptr(arr), _ptr(counts), _ptr(stages), _ptr(packets),
+                                                 _ptr(nbytes), _ptr(status), b, n, n_q, k, _stream()), "agx_codes_rans_encode")
+    if tok is not None:
+        _observer.end(tok)
+    return packets, nbytes, status
+
+
+def codes_rans_decode(cum: Tensor, packets: Tensor, nbytes: Tensor, state: Tensor, status: Tensor, i0: int = 0, n: Optional[int] = None,
+                      sizes: Optional[Sequence[int]] = None, counts: Optional[Tensor] = None, stages: Optional[Tensor] = None,
+                      carry: Optional[Tensor] = None) -> Tensor:
+    """The receiver (``agx_codes_rans_decode``, one launch, one wave per row): frames ``i0 .. i0 + n - 1`` (default: all behind
+    ``i0``) of a hop whose tables are cum int32 (B, hop, Q, K + 1) -> codes int64 (B, n, Q), -1 behind a row's frame count
+    (``counts``, of the hop) and stage count.  packets uint8 (B, any width), nbytes int64 (B,).  ``state`` int64 (B, 2) and
+    ``status`` int64 (B,) are in/out: the coder's state and read cursor, and the row's error bits (1: a live code was skipped by
+    the sender -- never set here; 2: a read past the packet; 4: the packet did not end where the coder started); the call with
+    ``i0 == 0`` starts them, later ones continue.  ``carry`` int64 (B, Q), in/out: takes the codes of a row's last frame when this
+    call decoded it.  One call and ``n`` calls of one frame agree bit for bit."""
+    op = "codes_rans_decode"
+    cum, b, hop, n_q, k = _rans_tables(op, cum)
+    i0 = int(i0)
+    n = hop - i0 if n is None else int(n)
+    if n < 1 or i0 < 0 or i0 > hop - n:
+        raise AgxError(f"{op}: frames {i0} .. {i0 + n - 1} do not lie in a hop of {hop} frames")
+    dev = cum.device
+    packets = _prior_tensor(op, "packets", packets, torch.uint8, (b, None), dev)
+    if packets.shape[1] < 1:
+        raise AgxError(f"{op}: packets {tuple(packets.shape)} hold no byte")
+    nbytes = _prior_tensor(op, "nbytes", nbytes, torch.int64, (b,), dev)
+    state = _prior_tensor(op, "state", state, torch.int64, (b, 2), dev)
+    status = _prior_tensor(op, "status", status, torch.int64, (b,), dev)
+    if carry is not None:
+        carry = _prior_tensor(op, "carry", carry, torch.int64, (b, n_q), dev)
+    arr = _prior_sizes(op, sizes, n_q, k)
+    _need_gpu_tables(cum)
+    _need_gpu(packets, nbytes, state, status, counts, stages, carry)
+    counts, stages = _entropy_rows(op, b, dev, counts, stages)
+    codes = torch.empty((b, n, n_q), dtype=torch.int64, device=dev)
+    tok = _observer.begin("other", (op, 8 * codes.numel() + 8 * codes.numel() + packets.numel(), 0)) if _observer is not None else None
+    _lib.check(_lib.load().agx_codes_rans_decode(_ptr(cum), _ptr(packets), _ptr(nbytes), _arr_ptr(arr), _ptr(counts), _ptr(stages),
+                                                 _ptr(state), _ptr(codes), _ptr(carry), _ptr(status), b, hop, i0, n, n_q, k,
+                                                 packets.shape[1], _stream()), "agx_codes_rans_decode")
+    if tok is not None:
+        _observer.end(tok)
+    return codes

@@ -515,6 +515,69 @@ def decode_codes_stream(model, packets: Tensor, stream: CodecStream, frames: int
     return decode_stream(model, zq, stream, counts), index
 
 
+# --------------------------------------------------------------------------- coded packets
+def _coded_step(model, what: str, stream, coder, coder_state, frames, counts, stages):
+    """Every refusal of a coded step, before the first launch: those of ``_packet_step`` without the fixed packet width, and a
+    coder whose prior does not model this quantiser's codes -> (codebooks, q_used, frames)."""
+    from .entropy import PriorCoder, PriorCoderState
+    cbs, q_used, _, _ = _step_quantizer(model, what, None)
+    if not isinstance(stream, CodecStream) or stream.model_id != id(model):
+        raise AgxError(f"{what}: the stream belongs to another model (model.new_stream makes one for this model)")
+    if model.training:
+        raise NotImplementedError(f"{what}: a stream is inference only: call model.eval() (there is no backward through a stream)")
+    if not isinstance(coder, PriorCoder) or not isinstance(coder_state, PriorCoderState):
+        raise AgxError(f"{what}: coder must be a PriorCoder and coder_state the PriorCoderState of its new_state()")
+    q = model.quantizer
+    if coder.num_quantizers != q_used or tuple(coder.codebook_sizes) != tuple(int(v) for v in q.codebook_sizes):
+        raise AgxError(f"{what}: the prior models {coder.num_quantizers} stages of {tuple(coder.codebook_sizes)} codes, the quantiser has "
+                       f"{q_used} of {tuple(q.codebook_sizes)}")
+    frames = int(frames)
+    if not 1 <= frames <= min(stream.max_chunk, coder_state.max_frames):
+        raise AgxError(f"{what}: frames = {frames} outside 1 .. min(the stream's max_chunk = {stream.max_chunk}, the coder state's "
+                       f"max_frames = {coder_state.max_frames})")
+    if frames > ops.RVQ_STEP_MAX_N:
+        raise AgxError(f"{what}: frames = {frames} exceeds the {ops.RVQ_STEP_MAX_N} frames a quantiser step takes")
+    if coder_state.batch != stream.batch or coder_state.rans.device != stream.device:
+        raise AgxError(f"{what}: the coder state has batch {coder_state.batch} on '{coder_state.rans.device}', the stream {stream.batch} "
+                       f"on '{stream.device}'")
+    if counts is not None:
+        ops._checked_counts(what, counts, stream.batch, stream.device, on="the stream on")
+    _check_stages(what, stages, stream)
+    return cbs, q_used, frames
+
+
+def encode_coded_stream(model, x: Tensor, stream: CodecStream, coder, coder_state, counts: Optional[Tensor] = None,
+                        stages: Optional[Tensor] = None):
+    """The sender's coded step -> (packets (B, 2 n Q + 4) uint8, nbytes (B,) int64, index (B, n, Q)): the ``index`` of
+    ``encode_codes_stream`` -- the same encoder step and the same quantiser step, which is not asked for ``zq`` here -- put through
+    ``coder.encode``.  Row ``b``'s packet is its first ``nbytes[b]`` bytes.  The quantiser step kernel writes its dense packet bytes
+    next to the codes as it always does; they are dropped."""
+    what = "compress_stream_coded"
+    if not isinstance(x, Tensor):
+        raise AgxError(f"{what}: x_chunk must be a tensor, got {type(x).__name__}")
+    if not isinstance(stream, CodecStream) or stream.model_id != id(model):
+        raise AgxError(f"{what}: the stream belongs to another model (model.new_stream makes one for this model)")
+    frames = model.rearrange_in(x).shape[-1] // stream.scale_factor
+    cbs, q_used, _ = _coded_step(model, what, stream, coder, coder_state, frames, counts, stages)
+    _, _, sizes, bits = _step_quantizer(model, what, None)
+    z = encode_latents_stream(model, x, stream, counts)
+    _, index, _ = ops.rvq_step_encode(z, cbs, q_used, sizes, counts, bits, want_zq=False, stages=stages)
+    packets, nbytes = coder.encode(coder_state, index, counts, stages)
+    return packets, nbytes, index
+
+
+def decode_coded_stream(model, packets: Tensor, nbytes: Tensor, stream: CodecStream, coder, coder_state, frames: int,
+                        counts: Optional[Tensor] = None, stages: Optional[Tensor] = None):
+    """The receiver's coded step -> (y, index (B, frames, Q)): ``coder.decode``, then ``decode_stream`` of ``ops.codes_embed(index,
+    codebooks, counts)`` -- one launch for the sum of a frame's codewords, in stage order, a -1 contributing nothing.  As on the
+    dense path a row with ``c_b > 0`` and ``q_b == 0`` pushes ``c_b`` frames of the zero latent through the decoder."""
+    what = "decompress_stream_coded"
+    cbs, q_used, frames = _coded_step(model, what, stream, coder, coder_state, frames, counts, stages)
+    index = coder.decode(coder_state, packets, nbytes, frames, counts, stages)
+    zq = ops.codes_embed(index, cbs[:q_used].contiguous(), counts)
+    return decode_stream(model, zq, stream, counts), index
+
+
 def restage_packets(model, packets: Tensor, frames: int, stages: Tensor, stages_from: Optional[Tensor] = None,
                     codebook_n: Optional[int] = None, counts: Optional[Tensor] = None):
     """A relay's step -> (packets (B, P), stages (B,) int64): packet rows of ``frames`` frames, sent with ``stages_from`` (None:

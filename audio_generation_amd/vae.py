@@ -650,6 +650,22 @@ class CausalVQAE(nn.Module):
         from . import streaming
         return streaming.decode_codes_stream(self, packets, stream, frames, codebook_n, counts, stages)
 
+    def compress_stream_coded(self, x_chunk, stream, coder, coder_state, counts=None, stages=None):
+        """``compress_stream`` with the packets entropy-coded under a code prior (``entropy.PriorCoder``) ->
+        (packets (B, 2 n Q + 4) uint8, nbytes (B,) int64, index (B, n, Q)).  Row ``b``'s packet is its first ``nbytes[b]`` bytes, 0
+        behind them; ``index`` is that of ``compress_stream``.  ``coder_state`` is the sender's ``coder.new_state(...)``; the
+        prior's stage count and codebook sizes must be the quantiser's."""
+        from . import streaming
+        return streaming.encode_coded_stream(self, x_chunk, stream, coder, coder_state, counts, stages)
+
+    def decompress_stream_coded(self, packets, nbytes, stream, coder, coder_state, frames, counts=None, stages=None):
+        """The receiver of ``compress_stream_coded``: coded packet rows of ``frames`` frames -> (y, index) as ``decompress_stream``
+        returns them, with ``counts`` / ``stages`` the sender's.  ``coder_state`` is the receiver's own ``coder.new_state(...)``;
+        ``coder_state.status`` is 0 for every row whose packet decoded cleanly.  Lossless against the dense wire: ``index`` is the
+        sender's ``index``."""
+        from . import streaming
+        return streaming.decode_coded_stream(self, packets, nbytes, stream, coder, coder_state, frames, counts, stages)
+
     def restage_packets(self, packets, frames, stages, stages_from=None, codebook_n=None, counts=None):
         """A relay's step: packet rows of ``frames`` frames written with ``stages_from`` (None: every stage) -> (packets, stages)
         with row ``b`` at ``min(q_in, clamp(stages[b], 0, Q))`` stages, byte for byte what ``compress_stream`` writes at that

@@ -1468,6 +1468,68 @@ int agx_codes_sample(const float *logits, const int32_t *sizes /* host, may be N
                      const int64_t *stages /* may be NULL */, int64_t *carry /* may be NULL, in/out */, int64_t *codes, int32_t batch,
                      int32_t n, int32_t n_q, int32_t k, void *stream);
 
+/* ---- Entropy coding (csrc/entropy.hip) --------------------------------------------------------------------------
+ * The code prior's logits as the probability model of a byte-wise rANS coder for the stream packets.  Operands are fp32, int32,
+ * int64 or uint8, contiguous; every argument is validated before the first launch; no call allocates or reads device data on the
+ * host, so every call can be captured.  `sizes` (HOST, n_q int32, 1 <= sizes[q] <= k; NULL: k everywhere) travels by value.
+ * `counts` / `stages` (int64 (B,), device, may be NULL): c_b = clamp(counts[b], 0, n), q_b = clamp(stages[b], 0, n_q), NULL = n /
+ * n_q.  n_q <= 64 and k <= AGX_CODES_CUM_MAX_K (the frequencies and the table of one stage live in LDS, as the sampler's order
+ * does); n * n_q <= AGX_RANS_MAX_SYMBOLS for the coder (a row's symbols and bytes live in LDS); AGX_ERR_UNSUPPORTED beyond.
+ * M = 2^AGX_RANS_SCALE_BITS is the total of a table, L = AGX_RANS_L the coder's lower bound: its state x lies in [L, 2^31).
+ *
+ * agx_codes_cum: logits (B, n_q * k, n), as the head writes them -> cum, int32 (B, n_cum, n_q, k + 1): frame i of the call lands
+ * at frame i_cum + i of the table buffer (0 <= i_cum <= n_cum - n) and no other frame of it is touched.  Entry (b, i, q) is live
+ * when i < c_b and q < q_b; size = sizes[q].  A live entry, every decision in binary64:
+ *   1. e_c = exp((double)l_c - l_max), c < size; S = sum e_c, in any order (a workgroup reduction).
+ *   2. r_c = (M - size) * e_c / S; f_c = 1 + floor(r_c).
+ *   3. the lowest argmax a of the binary32 logits (-0 == +0) takes the rest: f_a += M - sum_c f_c.
+ *   4. cum[0] = 0, cum[c + 1] = cum[c] + f_c, cum[c] = M for size < c <= k.
+ * So f_c >= 1 below size, 0 at or above it, and cum[size] == M exactly, whatever the floating-point sums do.  A frequency is
+ * pinned where r_c keeps 2^-24 from the integer it could cross (tests/entropy_ref.py "decided").  A dead entry's table is exact
+ * 0 and its logits are not read.  NaN or infinite logits give unspecified frequencies that still obey the line above.  One
+ * launch, one workgroup per entry. */
+#define AGX_RANS_SCALE_BITS 16
+#define AGX_RANS_L (1u << 23)
+#define AGX_CODES_CUM_MAX_K 2048
+#define AGX_RANS_MAX_SYMBOLS 8192
+int agx_codes_cum(const float *logits, const int32_t *sizes /* host, may be NULL */, const int64_t *counts /* may be NULL */,
+                  const int64_t *stages /* may be NULL */, int32_t *cum, int32_t batch, int32_t n, int32_t n_q, int32_t k, int32_t n_cum,
+                  int32_t i_cum, void *stream);
+/* agx_codes_rans_encode: cum (B, n, n_q, k + 1), codes (B, n, n_q) int64 -> packets (B, P) uint8 with P = 2 n n_q + 4, nbytes
+ * (B,) int64, status (B,) int64.  A row's symbols are its live entries in (i, q) order, s_1 .. s_N:
+ *   1. x = L.
+ *   2. for j = N .. 1, with (start, f) = (cum[s_j], cum[s_j + 1] - cum[s_j]):
+ *        while x >= ((L >> 16) << 8) * f: push x & 255, x >>= 8;        then x = ((x / f) << 16) + (x % f) + start.
+ *   3. push the four bytes of x, least significant first.
+ *   4. the packet is the pushed bytes REVERSED: packet[0..3] is x big-endian.
+ * nbytes[b] is the packet's length, 0 when N == 0; every byte of the row behind it is 0.  A live code outside [0, size) -- or one
+ * whose pair is not that of a table (f < 1, start < 0, start + f > M) -- is skipped and sets bit 0 of status[b]; otherwise
+ * status[b] = 0.  x < 2^31 before every symbol and the threshold is >= 2^15, so a symbol pushes two bytes at the most and P always
+ * suffices (2 N + 4 is reached when every coded f is 1).  One launch, one wave per row. */
+int agx_codes_rans_encode(const int32_t *cum, const int64_t *codes, const int32_t *sizes /* host, may be NULL */,
+                          const int64_t *counts /* may be NULL */, const int64_t *stages /* may be NULL */, uint8_t *packets,
+                          int64_t *nbytes, int64_t *status, int32_t batch, int32_t n, int32_t n_q, int32_t k, void *stream);
+/* agx_codes_rans_decode: the receiver, a call for frames i0 .. i0 + n - 1 of a hop of `hop` frames (0 <= i0 <= hop - n; here c_b =
+ * clamp(counts[b], 0, hop)).  cum (B, hop, n_q, k + 1): the tables of the hop, of which the call reads frames i0 .. i0 + n - 1;
+ * packets (B, p) uint8 with any p >= 1; nbytes (B,) int64.  state (B, 2) int64, in/out: x and the read cursor; status (B,) int64,
+ * in/out: a call with i0 == 0 starts both anew, a later one continues them.  codes (B, n, n_q) int64, out.
+ * Row b decodes frames i0 <= i < min(i0 + n, c_b):
+ *   1. at i0 == 0: x = packet[0..3] big-endian, cursor = 4.
+ *   2. per symbol: slot = x & 0xffff; the code is the c < size with cum[c] <= slot < cum[c + 1]; x = f * (x >> 16) + slot - cum[c].
+ *   3. while x < L: x = (x << 8) | next byte -- two bytes at the most, as the coder pushes; bit 2 of status[b] if x < L remains.
+ *   4. a read at or past min(nbytes[b], p) is not performed: it yields 0 and sets bit 1 of status[b].
+ *   5. when the call decodes the row's last frame c_b - 1, bit 2 is set unless x == L and the cursor equals nbytes[b].
+ * codes is -1 at i >= c_b and at q >= q_b.  `carry` (B, n_q) int64, may be NULL, the sampler's semantics per call: carry[b]
+ * becomes the codes of the last frame of the row that this call decoded, frame min(i0 + n, c_b) - 1, with -1 at q >= q_b, and is
+ * untouched when the call decoded none -- after the hop it holds frame c_b - 1.  A row with c_b == 0 or q_b == 0 writes only its
+ * -1s (those of `carry` included where i0 < c_b and q_b == 0, as the sampler does) and status 0 at i0 == 0.  A corrupt packet gives codes in [-1, size) and a nonzero status; with any packet and any table
+ * no access leaves the operands.  Decoding a hop in one call is bit for bit decoding it in n calls of one frame.  One launch, one
+ * wave per row; the search of a table is shared by the lanes (compare, then ballot). */
+int agx_codes_rans_decode(const int32_t *cum, const uint8_t *packets, const int64_t *nbytes, const int32_t *sizes /* host, may be NULL */,
+                          const int64_t *counts /* may be NULL */, const int64_t *stages /* may be NULL */, int64_t *state /* in/out */,
+                          int64_t *codes, int64_t *carry /* may be NULL, in/out */, int64_t *status /* in/out */, int32_t batch,
+                          int32_t hop, int32_t i0, int32_t n, int32_t n_q, int32_t k, int32_t p, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
