@@ -35,9 +35,9 @@ __global__ __launch_bounds__(256) void multires_kernel(const float *__restrict__
         const int g = g0 + i;
         lo_a[i] = (g >= 0 && g < L) ? x[row + g] : 0.f;
     }
-    if (tid < K) {
-        hk0[tid] = h0[c * K + tid];
-        hk1[tid] = h1[c * K + tid];
+    for (int k = tid; k < K; k += 256) {  // K may exceed the block: LDS is the only limit on it
+        hk0[k] = h0[size_t(c) * K + k];
+        hk1[k] = h1[size_t(c) * K + k];
     }
     __syncthreads();
 

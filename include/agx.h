@@ -712,7 +712,10 @@ int agx_unpack_rows(const float *xp, const int32_t *cu, float *out, int32_t batc
 
 /* CausalMultiresConv1d.forward (wavelets.py:79-96): depth-level cascade of two
  * depthwise causal filters h0/h1 (C,1,K) with dilation 1,2,4,..., per-channel
- * mixing w (C, depth+2), exact GELU.  x, y (B, C, L).  One launch. */
+ * mixing w (C, depth+2), exact GELU.  x, y (B, C, L).  One launch.
+ * Limits: depth 0 .. 20 (AGX_ERR_BAD_SHAPE beyond), and LDS -- two rows of 1024 + (K - 1)(2^depth - 1) floats plus the 2 K
+ * taps within 150 KiB, AGX_ERR_UNSUPPORTED beyond.  K itself has no other limit: the taps are staged by a loop strided over
+ * the workgroup, so K > 256 runs.  A refusal launches nothing. */
 int agx_multires_forward(const float *x, const float *h0, const float *h1, const float *w, float *y,
                          int32_t batch, int32_t channels, int32_t length, int32_t kernel,
                          int32_t depth, void *stream);

@@ -8,8 +8,9 @@ crosses the start mask, and it is flushed past its end.
 
 Multires steps are compared with the whole-signal calls -- ``oracle.wavelets.multires_conv`` and the package's plain
 ``ops.multires_forward`` -- at the tolerance the suite holds that kernel to on ``randn`` input (1e-5 max abs,
-tests/test_gpu_blocks.py).  Depthwise steps are within 2 x the derived bound of the float64 restatement
-(tests/multires_stream_ref.py) on their own operands: the reference reads a float64 copy of the ring the kernel read.
+tests/test_gpu_blocks.py) -- and, beside that flat tolerance, both the step and the plain call are within 2 x the derived bound
+of the float64 restatement of the whole signal (tests/wavelet_ref.py).  Depthwise steps are within 2 x the derived bound of the
+float64 restatement (tests/multires_stream_ref.py) on their own operands: the reference reads a float64 copy of the ring the kernel read.
 """
 import pytest
 import torch
@@ -19,6 +20,7 @@ from audio_generation_amd._lib import CONV_CAUSAL, EPI_LEAKY_POST, EPI_LEAKY_PRE
 from oracle import wavelets as owv
 from tests import codec_stream_ref as cref
 from tests import multires_stream_ref as ref
+from tests import wavelet_ref
 from tests.test_gpu_conformer import _within
 from tests.test_gpu_conv_stream import MAX_CHUNK, SCHEDULES, T, _block
 
@@ -46,10 +48,13 @@ class Multires:
                                         counts=counts)
 
     def whole(self, x):
-        """The two references of the whole signal: the oracle and the package's plain call."""
+        """The references of the whole signal: the oracle, the package's plain call, and the float64 restatement with its bound --
+        which the plain call is held to here, once."""
         want = owv.multires_conv(x, self.h0, self.h1, self.w, self.depth)
         plain = ops.multires_forward(x.to(DEV), *self.dev, self.depth).cpu()
-        return want, plain
+        exact, _, bound = wavelet_ref.multires(x, self.h0, self.h1, self.w, self.depth)
+        _within(plain, exact, bound, f"plain multires call C={self.c} K={self.k} depth={self.depth}")
+        return want, plain, exact, bound
 
 
 class Depthwise:
@@ -156,10 +161,12 @@ def run_case(name, batch, feed, schedule, flush=(), check=True, start=None):
                     j = torch.arange(p * k.rate - k.delay, (p + n) * k.rate - k.delay)
                     live = (j >= 0) & (j < (host_end[r] if masked and host_end[r] != cref.LIVE else 1 << 40) * k.rate)
                     assert not bool(live.any()) or int(j[live].max()) < refs[0].shape[2]
-                    for label, whole in zip(("oracle", "plain call"), refs):
+                    for label, whole in zip(("oracle", "plain call"), refs[:2]):
                         err = float((got[r].cpu()[:, live] - whole[r][:, j[live]]).abs().max()) if bool(live.any()) else 0.0
                         print(f"{what} row {r} vs the {label}: max abs {err:.3e}")
                         assert err < MULTIRES_TOL, (what, label, err)
+                    if bool(live.any()):
+                        _within(got[r][:, live], refs[2][r][:, j[live]], refs[3][r][:, j[live]], f"{what} row {r} vs the restatement")
                     assert bool((got[r].cpu()[:, ~live] == 0).all()), what                # masked columns are exact zeros
             else:
                 scratch = torch.zeros(batch, k.c, cap_out, dtype=torch.float64)
