@@ -11,7 +11,7 @@
 //   bytes -> codes.    rans_decode_kernel: one wave per row, frame by frame.  The state x is the same in every lane; the search of
 //                      the k + 1 sorted entries of a table is two rounds of compare + ballot (64 samples, then the entries between
 //                      two of them); lane 0 writes.  The state and the read cursor live in device memory between calls.
-#include "common.hpp"
+#include "codes.hpp"
 
 // defining arithmetic: nothing here may be fused
 #pragma clang fp contract(off)
@@ -24,31 +24,14 @@ constexpr int CUM_MAX_K = AGX_CODES_CUM_MAX_K;
 constexpr int CUM_PER = CUM_MAX_K / 256;           // codes per thread of the scan
 constexpr uint32_t RANS_SKIP = 0xffffffffu;        // a gathered pair that is not coded: start 65535 with f 65536 cannot be a pair
 
-struct EntropySizes { int n[64]; };
-
-__device__ __forceinline__ int entropy_clamp(const int64_t *__restrict__ v, int b, int hi) {
-    if (!v) return hi;
-    const int64_t c = v[b];
-    return c < 0 ? 0 : (c > hi ? hi : int(c));
-}
-
 // ------------------------------------------------------------------------------------------------------------------ tables
 struct CumArgs {
     const float *logits;              // (B, Q K, n)
     const int64_t *counts, *stages;   // or null
     int32_t *cum;                     // (B, n_cum, Q, K + 1)
     int n, Q, K, n_cum, i_cum;
-    EntropySizes sizes;
+    StageSizes sizes;
 };
-
-// ascending keys are (l descending, k ascending); -0 counts as +0 and a NaN as -inf (the sampler's order)
-__device__ __forceinline__ unsigned long long cum_key(float l, int k) {
-    if (l != l) l = -1.0f / 0.0f;
-    if (l == 0.f) l = 0.f;
-    unsigned u = __float_as_uint(l);
-    u = (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-    return ((unsigned long long)(~u) << 32) | unsigned(k);
-}
 
 // grid (B n Q), 256 threads
 __global__ __launch_bounds__(256) void cum_kernel(CumArgs a) {
@@ -61,7 +44,7 @@ __global__ __launch_bounds__(256) void cum_kernel(CumArgs a) {
     const int q = blockIdx.x % a.Q;
     const int64_t f_in = blockIdx.x / a.Q;
     const int b = int(f_in / a.n), i = int(f_in % a.n);
-    const int cnt = entropy_clamp(a.counts, b, a.n), qb = entropy_clamp(a.stages, b, a.Q);
+    const int cnt = row_clamp(a.counts, b, a.n), qb = row_clamp(a.stages, b, a.Q);
     int32_t *out = a.cum + ((size_t(b) * a.n_cum + size_t(a.i_cum + i)) * a.Q + q) * size_t(a.K + 1);
     if (!(i < cnt && q < qb)) {                              // a dead entry: exact 0, its logits are not read
         for (int c = tid; c <= a.K; c += 256) out[c] = 0;
@@ -77,17 +60,13 @@ __global__ __launch_bounds__(256) void cum_kernel(CumArgs a) {
         const int c = tid + 256 * u;
         l[u] = c < size ? col[size_t(c) * a.n] : 0.f;
         if (c < size) {
-            const unsigned long long key = cum_key(l[u], c);
+            const unsigned long long key = code_key(l[u], c);
             best = key < best ? key : best;
         }
     }
-    for (int off = 32; off > 0; off >>= 1) {
-        const unsigned long long o = __shfl_xor(best, off);
-        best = o < best ? o : best;
-    }
+    best = wave_min_key(best);
     if (lane == 0) wbest[wave] = best;
-    __syncthreads();
-    for (int w = 0; w < 4; ++w) best = wbest[w] < best ? wbest[w] : best;
+    best = block_min_key(best, wbest);
     const int arg = int(unsigned(best));                     // the lowest argmax of the binary32 logits
     const double lmax = double(col[size_t(arg) * a.n]);
     double e[CUM_PER], part = 0.0;
@@ -155,7 +134,7 @@ struct EncodeArgs {
     uint8_t *packets;                 // (B, P), P = 2 n Q + 4
     int64_t *nbytes, *status;         // (B,)
     int n, Q, K;
-    EntropySizes sizes;
+    StageSizes sizes;
 };
 
 // grid (B), 64 threads; dynamic LDS: the packet's length (16 bytes), n Q gathered pairs (uint32), then 2 n Q + 4 bytes
@@ -165,7 +144,7 @@ __global__ __launch_bounds__(64) void rans_encode_kernel(EncodeArgs a) {
     const int N = a.n * a.Q, P = 2 * N + 4;
     uint32_t *sym = enc_lds + 4;
     uint8_t *buf = reinterpret_cast<uint8_t *>(sym + N);
-    const int cnt = entropy_clamp(a.counts, b, a.n), qb = entropy_clamp(a.stages, b, a.Q);
+    const int cnt = row_clamp(a.counts, b, a.n), qb = row_clamp(a.stages, b, a.Q);
     bool bad = false;
     for (int e = lane; e < N; e += 64) {
         const int i = e / a.Q, q = e % a.Q;
@@ -236,13 +215,13 @@ struct DecodeArgs {
     int64_t *carry;                   // (B, Q) or null
     int64_t *status;                  // (B,)
     int hop, i0, n, Q, K, P;
-    EntropySizes sizes;
+    StageSizes sizes;
 };
 
 // grid (B), 64 threads.  x, the cursor and the status are the same in every lane; lane 0 writes.
 __global__ __launch_bounds__(64) void rans_decode_kernel(DecodeArgs a) {
     const int lane = threadIdx.x, b = blockIdx.x;
-    const int cnt = entropy_clamp(a.counts, b, a.hop), qb = entropy_clamp(a.stages, b, a.Q);
+    const int cnt = row_clamp(a.counts, b, a.hop), qb = row_clamp(a.stages, b, a.Q);
     int64_t *codes = a.codes + size_t(b) * a.n * a.Q;
     for (int e = lane; e < a.n * a.Q; e += 64)
         if (!(a.i0 + e / a.Q < cnt && e % a.Q < qb)) codes[e] = -1;
@@ -305,17 +284,12 @@ __global__ __launch_bounds__(64) void rans_decode_kernel(DecodeArgs a) {
     }
 }
 
-static int entropy_sizes(const char *what, const int32_t *sizes, int n_q, int k, EntropySizes *sz) {
-    if (n_q > 64) return fail(AGX_ERR_UNSUPPORTED, "%s: at most 64 stages (Q=%d)", what, n_q);
-    if (k > CUM_MAX_K)
+// stage_sizes with this file's limit on K between its two refusals
+static int entropy_sizes(const char *what, const int32_t *sizes, int n_q, int k, StageSizes *sz) {
+    if (n_q <= 64 && k > CUM_MAX_K)
         return fail(AGX_ERR_UNSUPPORTED, "%s: K=%d exceeds %d codes per stage (the frequencies and the table of a stage live in LDS)", what, k,
                     CUM_MAX_K);
-    for (int q = 0; q < 64; ++q) sz->n[q] = k;
-    for (int q = 0; q < n_q && sizes; ++q) {
-        if (sizes[q] < 1 || sizes[q] > k) return fail(AGX_ERR_BAD_SHAPE, "%s: stage %d has %d codes (K=%d)", what, q, sizes[q], k);
-        sz->n[q] = sizes[q];
-    }
-    return AGX_OK;
+    return stage_sizes(what, sizes, n_q, k, sz);
 }
 
 }  // namespace agx
@@ -326,7 +300,7 @@ int agx_codes_cum(const float *logits, const int32_t *sizes, const int64_t *coun
                   int32_t n, int32_t n_q, int32_t k, int32_t n_cum, int32_t i_cum, void *stream) {
     using namespace agx;
     if (batch <= 0 || n <= 0 || n_q <= 0 || k <= 0) return fail(AGX_ERR_BAD_SHAPE, "codes_cum: bad shape B=%d n=%d Q=%d K=%d", batch, n, n_q, k);
-    EntropySizes sz;
+    StageSizes sz;
     if (int rc = entropy_sizes("codes_cum", sizes, n_q, k, &sz)) return rc;
     if (i_cum < 0 || n_cum < n || i_cum > n_cum - n)
         return fail(AGX_ERR_BAD_SHAPE, "codes_cum: frames %d .. %d do not lie in a table buffer of %d frames", i_cum, i_cum + n - 1, n_cum);
@@ -338,7 +312,7 @@ int agx_codes_cum(const float *logits, const int32_t *sizes, const int64_t *coun
     return check_launch("codes_cum");
 }
 
-static int rans_shape(const char *what, const int32_t *sizes, int32_t batch, int32_t n, int32_t n_q, int32_t k, agx::EntropySizes *sz) {
+static int rans_shape(const char *what, const int32_t *sizes, int32_t batch, int32_t n, int32_t n_q, int32_t k, agx::StageSizes *sz) {
     using namespace agx;
     if (batch <= 0 || n <= 0 || n_q <= 0 || k <= 0) return fail(AGX_ERR_BAD_SHAPE, "%s: bad shape B=%d n=%d Q=%d K=%d", what, batch, n, n_q, k);
     if (int rc = entropy_sizes(what, sizes, n_q, k, sz)) return rc;
@@ -352,7 +326,7 @@ int agx_codes_rans_encode(const int32_t *cum, const int64_t *codes, const int32_
                           uint8_t *packets, int64_t *nbytes, int64_t *status, int32_t batch, int32_t n, int32_t n_q, int32_t k,
                           void *stream) {
     using namespace agx;
-    EntropySizes sz;
+    StageSizes sz;
     if (int rc = rans_shape("codes_rans_encode", sizes, batch, n, n_q, k, &sz)) return rc;
     if (!cum || !codes || !packets || !nbytes || !status) return fail(AGX_ERR_NULL_POINTER, "codes_rans_encode: NULL pointer");
     const int N = n * n_q;
@@ -366,7 +340,7 @@ int agx_codes_rans_decode(const int32_t *cum, const uint8_t *packets, const int6
                           const int64_t *stages, int64_t *state, int64_t *codes, int64_t *carry, int64_t *status, int32_t batch,
                           int32_t hop, int32_t i0, int32_t n, int32_t n_q, int32_t k, int32_t p, void *stream) {
     using namespace agx;
-    EntropySizes sz;
+    StageSizes sz;
     if (int rc = rans_shape("codes_rans_decode", sizes, batch, hop, n_q, k, &sz)) return rc;
     if (n <= 0 || i0 < 0 || i0 > hop - n)
         return fail(AGX_ERR_BAD_SHAPE, "codes_rans_decode: frames %d .. %d do not lie in a hop of %d frames", i0, i0 + n - 1, hop);

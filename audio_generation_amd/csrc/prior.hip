@@ -16,21 +16,13 @@
 //                     by (logit descending, k ascending) -- a bitonic sort of 64-bit keys in LDS --, takes the prefix sums of
 //                     exp((l - l_max) / tau) in that order in binary64 (a workgroup scan), cuts at top_k / top_p and inverts the
 //                     distribution at a Philox draw.  Every decision is a comparison of binary64 values.
-#include "common.hpp"
+#include "codes.hpp"
 #include "philox.hpp"
 
 // gather-sums and defining arithmetic: nothing here may be fused
 #pragma clang fp contract(off)
 
 namespace agx {
-
-struct PriorSizes { int n[64]; };
-
-__device__ __forceinline__ int prior_clamp(const int64_t *__restrict__ v, int b, int hi) {
-    if (!v) return hi;
-    const int64_t c = v[b];
-    return c < 0 ? 0 : (c > hi ? hi : int(c));
-}
 
 // ---------------------------------------------------------------------------------------------------------------- embed
 constexpr int EMB_TI = 16;   // frames per tile
@@ -50,7 +42,7 @@ __global__ __launch_bounds__(256) void codes_embed_kernel(EmbedArgs a) {
     __shared__ int rows[EMB_TI][64];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int b = blockIdx.x / a.tiles_n, i0 = (blockIdx.x % a.tiles_n) * EMB_TI, d0 = blockIdx.y * EMB_DC;
-    const int cnt = prior_clamp(a.counts, b, a.n);
+    const int cnt = row_clamp(a.counts, b, a.n);
     for (int e = tid; e < EMB_TI * a.Q; e += 256) {
         const int fi = e / a.Q, q = e % a.Q, i = i0 + fi;
         int r = -1;
@@ -111,7 +103,7 @@ __global__ __launch_bounds__(256) void embed_index_kernel(const int64_t *__restr
     const int64_t f = e / Q;
     const int q = int(e % Q), b = int(f / n), i = int(f % n);
     const int64_t x = index[e];
-    idx[size_t(q) * size_t(F) + size_t(f)] = i < prior_clamp(counts, b, n) && x >= 0 && x < R ? int32_t(x) : int32_t(-1);
+    idx[size_t(q) * size_t(F) + size_t(f)] = i < row_clamp(counts, b, n) && x >= 0 && x < R ? int32_t(x) : int32_t(-1);
 }
 
 // destination (q, r): grid (R, Q), 256 threads; thread t owns channels t + 256 j.  Every wave walks the same frames.
@@ -167,7 +159,7 @@ struct CeArgs {
     const int64_t *target;    // (B, T, Q)
     int64_t E;                // B T Q
     int T, Q, K;
-    PriorSizes sizes;
+    StageSizes sizes;
 };
 
 // entry e of the thread map: t fastest, then q, then b
@@ -351,23 +343,8 @@ struct SampleArgs {
     int64_t *carry;             // (B, Q) or null
     int64_t *codes;             // (B, n, Q)
     int n, Q, K;
-    PriorSizes sizes;
+    StageSizes sizes;
 };
-
-// the sort key of code k with logit l: ascending keys are (l descending, k ascending).  -0 counts as +0 (the order is that of
-// the VALUES) and a NaN as -inf: it sorts last and carries no mass.
-__device__ __forceinline__ unsigned long long sample_key(float l, int k) {
-    if (l != l) l = -1.0f / 0.0f;
-    if (l == 0.f) l = 0.f;
-    unsigned u = __float_as_uint(l);
-    u = (u & 0x80000000u) ? ~u : (u | 0x80000000u);      // ascending in l
-    return ((unsigned long long)(~u) << 32) | unsigned(k);
-}
-__device__ __forceinline__ float sample_key_logit(unsigned long long key) {
-    unsigned u = ~unsigned(key >> 32);
-    u = (u & 0x80000000u) ? (u & 0x7fffffffu) : ~u;
-    return __uint_as_float(u);
-}
 
 // sum over the workgroup of one int per thread (integers: any order gives the same sum)
 __device__ __forceinline__ int sample_block_sum(int v, int *slot) {
@@ -390,7 +367,7 @@ __global__ __launch_bounds__(256) void sample_kernel(SampleArgs a) {
     const int q = blockIdx.x % a.Q;
     const int64_t f_in = blockIdx.x / a.Q;
     const int b = int(f_in / a.n), i = int(f_in % a.n);
-    const int cnt = prior_clamp(a.counts, b, a.n), qb = prior_clamp(a.stages, b, a.Q);
+    const int cnt = row_clamp(a.counts, b, a.n), qb = row_clamp(a.stages, b, a.Q);
     const bool live = i < cnt && q < qb;
     int64_t *code_out = a.codes + (size_t(b) * a.n + i) * a.Q + q;
     int64_t *carry_out = a.carry && i == cnt - 1 ? a.carry + size_t(b) * a.Q + q : nullptr;
@@ -406,21 +383,17 @@ __global__ __launch_bounds__(256) void sample_kernel(SampleArgs a) {
     const float tau_f = a.temperature[b];
     int P = 2;
     while (P < size) P <<= 1;
-    for (int k = tid; k < P; k += 256) key[k] = k < size ? sample_key(col[size_t(k) * a.n], k) : ~0ull;
+    for (int k = tid; k < P; k += 256) key[k] = k < size ? code_key(col[size_t(k) * a.n], k) : ~0ull;
     __syncthreads();
     int code;
     if (!(tau_f > 0.f)) {
         // greedy: the least key, by every thread over its own stride, then over the workgroup through LDS
         unsigned long long best = ~0ull;
         for (int k = tid; k < P; k += 256) best = key[k] < best ? key[k] : best;
-        for (int off = 32; off > 0; off >>= 1) {
-            const unsigned long long o = __shfl_xor(best, off);
-            best = o < best ? o : best;
-        }
         unsigned long long *wbest = reinterpret_cast<unsigned long long *>(cum);
+        best = wave_min_key(best);
         if (lane == 0) wbest[wave] = best;
-        __syncthreads();
-        for (int w = 0; w < 4; ++w) best = wbest[w] < best ? wbest[w] : best;
+        best = block_min_key(best, wbest);
         code = int(unsigned(best));
     } else {
         // (l descending, k ascending): bitonic sort of the P keys
@@ -436,7 +409,7 @@ __global__ __launch_bounds__(256) void sample_kernel(SampleArgs a) {
         const int64_t tk = a.top_k[b];
         const int kept0 = tk > 0 && tk < size ? int(tk) : size;
         const double tau = double(tau_f);
-        const double zmax = double(sample_key_logit(key[0])) / tau;
+        const double zmax = double(code_key_logit(key[0])) / tau;
         // prefix sums of e_j = exp(z_j - z_max) over the first kept0 codes of the order: SAMPLE_PER consecutive per thread,
         // then the threads' totals over the wave and the waves' over LDS
         double e[SAMPLE_PER], run = 0.0;
@@ -445,7 +418,7 @@ __global__ __launch_bounds__(256) void sample_kernel(SampleArgs a) {
             const int j = tid * SAMPLE_PER + u;
             double v = 0.0;
             if (j < kept0) {
-                const double z = double(sample_key_logit(key[j])) / tau;
+                const double z = double(code_key_logit(key[j])) / tau;
                 v = z == zmax ? 1.0 : exp(z - zmax);
             }
             run = run + v;
@@ -492,16 +465,6 @@ __global__ __launch_bounds__(256) void sample_kernel(SampleArgs a) {
         *code_out = code;
         if (carry_out) *carry_out = code;
     }
-}
-
-static int prior_sizes(const char *what, const int32_t *sizes, int q_total, int k, PriorSizes *sz) {
-    if (q_total > 64) return fail(AGX_ERR_UNSUPPORTED, "%s: at most 64 stages (Q=%d)", what, q_total);
-    for (int q = 0; q < 64; ++q) sz->n[q] = k;
-    for (int q = 0; q < q_total && sizes; ++q) {
-        if (sizes[q] < 1 || sizes[q] > k) return fail(AGX_ERR_BAD_SHAPE, "%s: stage %d has %d codes (K=%d)", what, q, sizes[q], k);
-        sz->n[q] = sizes[q];
-    }
-    return AGX_OK;
 }
 
 }  // namespace agx
@@ -554,10 +517,10 @@ int agx_codes_embed_backward(const float *dout, const int64_t *index, const int6
     return check_launch("codes_embed_backward");
 }
 
-static int ce_shape(const char *what, const int32_t *sizes, int32_t batch, int32_t t, int32_t n_q, int32_t k, agx::PriorSizes *sz) {
+static int ce_shape(const char *what, const int32_t *sizes, int32_t batch, int32_t t, int32_t n_q, int32_t k, agx::StageSizes *sz) {
     using namespace agx;
     if (batch <= 0 || t <= 0 || n_q <= 0 || k <= 0) return fail(AGX_ERR_BAD_SHAPE, "%s: bad shape B=%d T=%d Q=%d K=%d", what, batch, t, n_q, k);
-    if (int rc = prior_sizes(what, sizes, n_q, k, sz)) return rc;
+    if (int rc = stage_sizes(what, sizes, n_q, k, sz)) return rc;
     if (int64_t(batch) * t * n_q > (int64_t(1) << 36))
         return fail(AGX_ERR_UNSUPPORTED, "%s: B T Q = %lld entries exceed 2^36", what, (long long)batch * t * n_q);
     return AGX_OK;
@@ -572,7 +535,7 @@ int agx_codes_cross_entropy(const float *logits, const int64_t *target, const in
                             int32_t k, float *nll, float *lse, float *loss, int64_t *n_live, void *workspace, size_t workspace_bytes,
                             void *stream) {
     using namespace agx;
-    PriorSizes sz;
+    StageSizes sz;
     if (int rc = ce_shape("codes_cross_entropy", sizes, batch, t, n_q, k, &sz)) return rc;
     if (!logits || !target || !nll || !lse || !loss || !n_live) return fail(AGX_ERR_NULL_POINTER, "codes_cross_entropy: NULL pointer");
     const int64_t E = int64_t(batch) * t * n_q, nparts = ceil_div64(E, CE_ENTRIES);
@@ -592,7 +555,7 @@ int agx_codes_cross_entropy_backward(const float *logits, const int64_t *target,
                                      const int64_t *n_live, const float *g, int32_t batch, int32_t t, int32_t n_q, int32_t k,
                                      float *dlogits, void *stream) {
     using namespace agx;
-    PriorSizes sz;
+    StageSizes sz;
     if (int rc = ce_shape("codes_cross_entropy_backward", sizes, batch, t, n_q, k, &sz)) return rc;
     if (!logits || !target || !lse || !n_live || !g || !dlogits) return fail(AGX_ERR_NULL_POINTER, "codes_cross_entropy_backward: NULL pointer");
     const int64_t E = int64_t(batch) * t * n_q;
@@ -610,8 +573,8 @@ int agx_codes_sample(const float *logits, const int32_t *sizes, const int64_t *s
     if (k > AGX_CODES_SAMPLE_MAX_K)
         return fail(AGX_ERR_UNSUPPORTED, "codes_sample: K=%d exceeds %d codes per stage (the order and the prefix sums of a stage live in LDS)",
                     k, AGX_CODES_SAMPLE_MAX_K);
-    PriorSizes sz;
-    if (int rc = prior_sizes("codes_sample", sizes, n_q, k, &sz)) return rc;
+    StageSizes sz;
+    if (int rc = stage_sizes("codes_sample", sizes, n_q, k, &sz)) return rc;
     if (int64_t(batch) * n * n_q > 0x7fffffff)
         return fail(AGX_ERR_UNSUPPORTED, "codes_sample: B n Q = %lld rows exceed 2^31 - 1", (long long)batch * n * n_q);
     if (!logits || !seeds || !frame0 || !temperature || !top_k || !top_p || !codes) return fail(AGX_ERR_NULL_POINTER, "codes_sample: NULL pointer");

@@ -15,7 +15,7 @@
 //      candidate is decided, the rest are decided by the defining binary64 distance (sequential, unfused): squares by all
 //      lanes, the d-ordered sums of up to 16 pairs side by side, one lane each;
 //   C. r -= c, index written, squared residual accumulated, and the next stage's r' = fl(r - mu) split into the planes.
-#include "common.hpp"
+#include "codes.hpp"
 
 namespace agx {
 
@@ -46,13 +46,12 @@ __host__ __device__ inline int64_t rvq_stage_floats(int k, int dim) {
 // Stages may have fewer than K codewords (the reference takes one codebook size per quantizer, vae.py:233): rows
 // kq .. K-1 of such a stage are padding -- excluded from the mean and from cmax2, |c'|^2 = +inf (never a candidate),
 // zero in the score image; the stage's count rides in the image's tail for the kernel's full-search fallback.
-struct RvqSizes { int n[64]; };
 
 // mu[d] = mean_k c[k][d].  One wave per dimension d: lane L adds codewords L, L + 64, ... in order, the 64 partial sums are
 // combined by a fixed shuffle tree (deterministic).  (Round 2: one THREAD per d walking all K rows with a stride of D
 // floats -- 384 us per repack at 8 x 1024 x 512.)
 __global__ __launch_bounds__(256) void rvq_mean_kernel(const float *__restrict__ cb, int k, int dim,
-                                                       float *__restrict__ packed, RvqSizes sizes) {
+                                                       float *__restrict__ packed, StageSizes sizes) {
     const int q = blockIdx.y;
     const int kq = sizes.n[q];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -71,7 +70,7 @@ __global__ __launch_bounds__(256) void rvq_mean_kernel(const float *__restrict__
 }
 
 __global__ __launch_bounds__(256) void rvq_pack_kernel(const float *__restrict__ cb, int n_q, int k,
-                                                       int dim, float *__restrict__ packed, RvqSizes sizes) {
+                                                       int dim, float *__restrict__ packed, StageSizes sizes) {
     const int q = blockIdx.y;
     const bool pad = blockIdx.x * 256 + threadIdx.x >= sizes.n[q];
     const int code = blockIdx.x * 256 + threadIdx.x;
@@ -95,7 +94,7 @@ __global__ __launch_bounds__(256) void rvq_pack_kernel(const float *__restrict__
     img[size_t(dp) * k + k + code] = pad ? 0.f : sqrtf(acc);
 }
 
-__global__ __launch_bounds__(256) void rvq_cmax_kernel(int k, int dim, float *__restrict__ packed, RvqSizes sizes) {
+__global__ __launch_bounds__(256) void rvq_cmax_kernel(int k, int dim, float *__restrict__ packed, StageSizes sizes) {
     float *img = packed + blockIdx.x * rvq_stage_floats(k, dim);
     const float *c2 = img + size_t(rvq_dp(dim)) * k;
     const int kq = sizes.n[blockIdx.x];
@@ -585,13 +584,8 @@ int agx_rvq_pack_sized(const float *codebooks, const int32_t *sizes, int32_t n_q
     using namespace agx;
     if (n_q <= 0 || k <= 0 || dim <= 0) return fail(AGX_ERR_BAD_SHAPE, "rvq_pack: bad shape Q=%d K=%d D=%d", n_q, k, dim);
     if (!codebooks || !packed) return fail(AGX_ERR_NULL_POINTER, "rvq_pack: NULL pointer");
-    if (n_q > 64) return fail(AGX_ERR_UNSUPPORTED, "rvq_pack: at most 64 stages (Q=%d)", n_q);
-    RvqSizes sz;
-    for (int q = 0; q < 64; ++q) sz.n[q] = k;
-    for (int q = 0; q < n_q && sizes; ++q) {
-        if (sizes[q] < 1 || sizes[q] > k) return fail(AGX_ERR_BAD_SHAPE, "rvq_pack: stage %d has %d codewords (K=%d)", q, sizes[q], k);
-        sz.n[q] = sizes[q];
-    }
+    StageSizes sz;
+    if (int rc = stage_sizes("rvq_pack", sizes, n_q, k, &sz)) return rc;
     hipStream_t st = static_cast<hipStream_t>(stream);
     hipLaunchKernelGGL(rvq_mean_kernel, dim3(ceil_div(rvq_dp(dim), 64), n_q), dim3(256), 0, st, codebooks, k, dim, packed, sz);
     hipLaunchKernelGGL(rvq_pack_kernel, dim3(ceil_div(k, 256), n_q), dim3(256), 0, st, codebooks, n_q, k, dim, packed, sz);

@@ -13,10 +13,7 @@
         off[0][tid] = b * a.x_sb + t * a.x_st;
         off[1][tid] = b * a.g_sb + t * a.g_st;
         off[2][tid] = b * a.d_sb + t * a.d_st;
-        if constexpr (STAGED) {
-            const int64_t s = stages[b];
-            qfs[tid] = int(s < 0 ? 0 : (s > a.Q ? a.Q : s));
-        }
+        if constexpr (STAGED) qfs[tid] = count_clamp(stages[b], a.Q);
     }
     __syncthreads();
     auto stage = [&](const float *__restrict__ p, int64_t sd, const int64_t *o, float *tile) {

@@ -36,8 +36,7 @@
 #pragma unroll
         for (int j = 0; j < FPW; ++j) {
             const int64_t n = n0 + __builtin_amdgcn_readfirstlane(wave) + j * NWV;
-            const int64_t s = n < N ? stages[n / a.T] : 0;
-            qf[j] = __builtin_amdgcn_readfirstlane(int(s < 0 ? 0 : (s > a.Q ? a.Q : s)));
+            qf[j] = __builtin_amdgcn_readfirstlane(count_clamp(n < N ? stages[n / a.T] : 0, a.Q));
         }
     }
     auto live_at = [&](int j, int q) {             // is stage q of this wave's frame j live?

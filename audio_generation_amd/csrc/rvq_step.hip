@@ -12,10 +12,10 @@
 //
 // Decode: rvq_step_decode_kernel, one workgroup per frame: the frame's codes out of the row's packet, then the stage-order sum.
 //
-// Per-row stage counts: every kernel reads q_b = clamp(stages[b], 0, Q) through step_stages, beside the frame count
+// Per-row stage counts: every kernel reads q_b = clamp(stages[b], 0, Q) through row_clamp, beside the frame count
 // (NULL: Q, the plain entry points).  Stage q of row b is searched, stored, packed and summed only when q < q_b; the row's packet is
 // dense over its own q_b.  rvq_packets_restage_kernel, one workgroup per row, re-packs a row to fewer stages: a bit gather.
-#include "common.hpp"
+#include "codes.hpp"
 
 // the whole file is the defining arithmetic or plain sums: nothing here may be fused
 #pragma clang fp contract(off)
@@ -26,8 +26,6 @@ typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 constexpr int STEP_CW = 64;       // codewords per search workgroup: one per lane of its single wave
 constexpr int STEP_NO_CODE = 0x7fffffff;
-
-struct RvqStepSizes { int n[64]; };
 
 // workspace: [pd: 2 x F x NB double | res: 2 x F x D float | pi: 2 x F x NB int32 | codes: F x Q int32], each part 8-byte aligned
 struct RvqStepWs {
@@ -43,19 +41,6 @@ __host__ __device__ inline RvqStepWs rvq_step_ws(int64_t F, int D, int K, int Q)
     w.codes = w.pi + step_align8(2 * size_t(F) * nb * sizeof(int32_t));
     w.total = w.codes + step_align8(size_t(F) * size_t(Q) * sizeof(int32_t));
     return w;
-}
-
-__device__ __forceinline__ int step_count(const int64_t *__restrict__ counts, int b, int n) {
-    if (!counts) return n;
-    const int64_t c = counts[b];
-    return c < 0 ? 0 : (c > n ? n : int(c));
-}
-
-// q_b of row b: the stages it sends (include/agx.h "Per-row stage counts"); a null pointer is every stage of the launch
-__device__ __forceinline__ int step_stages(const int64_t *__restrict__ stages, int b, int Q) {
-    if (!stages) return Q;
-    const int64_t s = stages[b];
-    return s < 0 ? 0 : (s > Q ? Q : int(s));
 }
 
 // (distance, index) minimum over the wave, the lowest index on equal distance: a butterfly, every lane ends with the result
@@ -151,7 +136,7 @@ struct RvqStepArgs {
     unsigned char *ws;
     RvqStepWs map;
     int64_t F;
-    RvqStepSizes sizes;
+    StageSizes sizes;
 };
 
 // stage q of the search: grid (F, ceil(K / 64)), 64 threads, D floats of dynamic LDS
@@ -161,8 +146,8 @@ __global__ __launch_bounds__(64) void rvq_step_search_kernel(RvqStepArgs a, int 
     const int64_t f = blockIdx.x;
     const int j = blockIdx.y;
     const int b = int(f / a.n), t = int(f % a.n);
-    if (t >= step_count(a.counts, b, a.n)) return;     // a dead frame: nothing of it is loaded
-    if (q >= step_stages(a.stages, b, a.Q)) return;    // a stage the row does not send: likewise, and the row's last partials stay
+    if (t >= row_clamp(a.counts, b, a.n)) return;       // a dead frame: nothing of it is loaded
+    if (q >= row_clamp(a.stages, b, a.Q)) return;       // a stage the row does not send: likewise, and the row's last partials stay
     const int kq = a.sizes.n[q];
     if (j * STEP_CW >= kq) return;                      // a short stage: no codeword here, and no partial is read for this block
     const int nb_max = (a.K + STEP_CW - 1) / STEP_CW;
@@ -217,16 +202,17 @@ struct RvqStepOutArgs {
     const unsigned char *ws;
     RvqStepWs map;
     int64_t F;
-    RvqStepSizes sizes;
+    StageSizes sizes;
 };
 
-// byte i of a row's packet: the dense little-endian packing of `n_codes` codes of `bits` bits (codes: n_codes ints in LDS)
-__device__ __forceinline__ unsigned step_packet_byte(const int *codes, int n_codes, int bits, int i) {
-    const unsigned mask = (1u << bits) - 1u;
+// byte i of a row's packet: the dense little-endian packing of `n_codes` codes of `bits` bits; code_at(e) is code e of the row,
+// no wider than `bits`, and is asked only for the codes whose bits the byte holds
+template <class CodeAt>
+__device__ __forceinline__ unsigned step_packet_byte(CodeAt code_at, int n_codes, int bits, int i) {
     const int lo = 8 * i;
     unsigned v = 0;
     for (int e = lo / bits; e < n_codes && e * bits < lo + 8; ++e) {
-        const unsigned code = unsigned(codes[e]) & mask;
+        const unsigned code = code_at(e);
         const int shift = e * bits - lo;
         v |= shift >= 0 ? code << shift : code >> -shift;
     }
@@ -238,8 +224,8 @@ __device__ __forceinline__ unsigned step_packet_byte(const int *codes, int n_cod
 __global__ __launch_bounds__(256) void rvq_step_output_kernel(RvqStepOutArgs a) {
     extern __shared__ __align__(16) int step_codes[];
     const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int cnt = step_count(a.counts, b, a.n);
-    const int qb = step_stages(a.stages, b, a.Q);
+    const int cnt = row_clamp(a.counts, b, a.n);
+    const int qb = row_clamp(a.stages, b, a.Q);
     if (qb > 0) {
         const int nb_max = (a.K + STEP_CW - 1) / STEP_CW;
         const double *pd = reinterpret_cast<const double *>(a.ws + a.map.pd);
@@ -272,8 +258,10 @@ __global__ __launch_bounds__(256) void rvq_step_output_kernel(RvqStepOutArgs a) 
     }
     if (a.packets) {
         const int live_bytes = (cnt * qb * a.bits + 7) / 8;
+        const unsigned mask = (1u << a.bits) - 1u;
+        auto code_at = [&](int e) { return unsigned(step_codes[e]) & mask; };
         for (int i = tid; i < a.P; i += 256)
-            a.packets[size_t(b) * a.P + i] = i < live_bytes ? (unsigned char)step_packet_byte(step_codes, cnt * qb, a.bits, i) : (unsigned char)0;
+            a.packets[size_t(b) * a.P + i] = i < live_bytes ? (unsigned char)step_packet_byte(code_at, cnt * qb, a.bits, i) : (unsigned char)0;
     }
 }
 
@@ -294,7 +282,7 @@ struct RvqStepDecArgs {
     float *zq;
     int64_t q_sb, q_st, q_sd;
     int64_t *index;                 // (B, n, Q) or null
-    RvqStepSizes sizes;
+    StageSizes sizes;
 };
 
 // one workgroup per frame: grid (B n), 256 threads
@@ -302,8 +290,8 @@ __global__ __launch_bounds__(256) void rvq_step_decode_kernel(RvqStepDecArgs a) 
     __shared__ int codes[64];
     const int64_t f = blockIdx.x;
     const int b = int(f / a.n), t = int(f % a.n), tid = threadIdx.x;
-    const int cnt = step_count(a.counts, b, a.n);
-    const int qb = step_stages(a.stages, b, a.Q);
+    const int cnt = row_clamp(a.counts, b, a.n);
+    const int qb = row_clamp(a.stages, b, a.Q);
     const bool live = t < cnt;
     if (tid < a.Q) {
         int code = -1;
@@ -339,46 +327,32 @@ struct RvqRestageArgs {
 // lies below the count, so every bit read lies inside the row's first ceil(c_b q_in bits / 8) input bytes.
 __global__ __launch_bounds__(256) void rvq_packets_restage_kernel(RvqRestageArgs a) {
     const int b = blockIdx.x, tid = threadIdx.x;
-    const int cnt = step_count(a.counts, b, a.n);
-    const int q_in = step_stages(a.stages_in, b, a.Q);
-    const int q_to = step_stages(a.stages_to, b, a.Q);
+    const int cnt = row_clamp(a.counts, b, a.n);
+    const int q_in = row_clamp(a.stages_in, b, a.Q);
+    const int q_to = row_clamp(a.stages_to, b, a.Q);
     const int q_out = q_to < q_in ? q_to : q_in;
     if (tid == 0 && a.stages_out) a.stages_out[b] = int64_t(q_out);
     const unsigned char *row = a.in + size_t(b) * a.P;
     const int n_codes = cnt * q_out;
     const int live_bytes = (n_codes * a.bits + 7) / 8;
-    for (int i = tid; i < a.P; i += 256) {
-        unsigned v = 0;
-        if (i < live_bytes) {
-            const int lo = 8 * i;
-            for (int e = lo / a.bits; e < n_codes && e * a.bits < lo + 8; ++e) {
-                const unsigned code = step_read_code(row, ((e / q_out) * q_in + e % q_out) * a.bits, a.bits);
-                const int shift = e * a.bits - lo;
-                v |= shift >= 0 ? code << shift : code >> -shift;
-            }
-        }
-        a.out[size_t(b) * a.P + i] = (unsigned char)(v & 0xffu);
-    }
+    auto code_at = [&](int e) { return step_read_code(row, ((e / q_out) * q_in + e % q_out) * a.bits, a.bits); };
+    for (int i = tid; i < a.P; i += 256)
+        a.out[size_t(b) * a.P + i] = (unsigned char)(i < live_bytes ? step_packet_byte(code_at, n_codes, a.bits, i) : 0u);
 }
 
 // the shape checks both entry points share; `what` names the entry point.  Fills sz.
 static int rvq_step_shape(const char *what, const int32_t *sizes, int32_t batch, int32_t n, int32_t dim, int32_t k, int32_t q_total,
-                          int32_t q_used, int32_t bits, RvqStepSizes *sz) {
+                          int32_t q_used, int32_t bits, StageSizes *sz) {
     if (batch <= 0 || n <= 0 || dim <= 0 || k <= 0 || q_total <= 0 || q_used < 0 || q_used > q_total)
         return fail(AGX_ERR_BAD_SHAPE, "%s: bad shape B=%d n=%d D=%d K=%d Q=%d q_used=%d", what, batch, n, dim, k, q_total, q_used);
     if (bits < 1 || bits > 16) return fail(AGX_ERR_BAD_SHAPE, "%s: bits=%d outside 1 .. 16", what, bits);
     if (n > AGX_RVQ_STEP_MAX_N)
         return fail(AGX_ERR_UNSUPPORTED, "%s: a step takes at most %d frames per row, got n=%d (agx_rvq_forward is the kernel for long chunks)",
                     what, AGX_RVQ_STEP_MAX_N, n);
-    if (q_total > 64) return fail(AGX_ERR_UNSUPPORTED, "%s: at most 64 stages (Q=%d)", what, q_total);
+    if (q_total > 64) return fail(AGX_ERR_UNSUPPORTED, "%s: at most 64 stages (Q=%d)", what, q_total);   // ahead of the limits below, as ever
     if (dim > 8192 || k > 65536) return fail(AGX_ERR_UNSUPPORTED, "%s: D=%d (at most 8192) or K=%d (at most 65536) is too large", what, dim, k);
     if (int64_t(batch) * n > 0x7fffffff) return fail(AGX_ERR_UNSUPPORTED, "%s: B n = %lld frames exceed 2^31 - 1", what, (long long)batch * n);
-    for (int q = 0; q < 64; ++q) sz->n[q] = k;
-    for (int q = 0; q < q_total && sizes; ++q) {
-        if (sizes[q] < 1 || sizes[q] > k) return fail(AGX_ERR_BAD_SHAPE, "%s: stage %d has %d codewords (K=%d)", what, q, sizes[q], k);
-        sz->n[q] = sizes[q];
-    }
-    return AGX_OK;
+    return stage_sizes(what, sizes, q_total, k, sz);
 }
 
 // the encode entry points: `stages` null is every stage for every row
@@ -386,7 +360,7 @@ static int rvq_step_encode_any(const char *what, const float *z, int64_t z_sb, i
                                const int32_t *sizes, const int64_t *counts, const int64_t *stages, int32_t batch, int32_t n, int32_t dim,
                                int32_t k, int32_t q_total, int32_t q_used, int32_t bits, float *zq, int64_t q_sb, int64_t q_st,
                                int64_t q_sd, int64_t *index, uint8_t *packets, void *workspace, size_t workspace_bytes, void *stream) {
-    RvqStepSizes sz;
+    StageSizes sz;
     if (int rc = rvq_step_shape(what, sizes, batch, n, dim, k, q_total, q_used, bits, &sz)) return rc;
     for (int q = 0; q < q_used && packets; ++q)
         if (sz.n[q] > (1 << bits))
@@ -418,7 +392,7 @@ static int rvq_step_decode_any(const char *what, const uint8_t *packets, int32_t
                                const int64_t *counts, const int64_t *stages, int32_t batch, int32_t n, int32_t dim, int32_t k,
                                int32_t q_total, int32_t q_used, float *zq, int64_t q_sb, int64_t q_st, int64_t q_sd, int64_t *index,
                                void *stream) {
-    RvqStepSizes sz;
+    StageSizes sz;
     if (int rc = rvq_step_shape(what, sizes, batch, n, dim, k, q_total, q_used, bits, &sz)) return rc;
     if (!codebooks || !zq || (q_used > 0 && !packets)) return fail(AGX_ERR_NULL_POINTER, "%s: NULL pointer", what);
     const int P = int((int64_t(n) * q_used * bits + 7) / 8);

@@ -90,11 +90,7 @@ class PriorCoder(nn.Module):
         if not 1 <= frames <= state.max_frames:
             raise AgxError(f"{what}: a hop of {frames} frames outside 1 .. the state's max_frames = {state.max_frames}")
         dev = state.rans.device
-        if counts is not None:
-            counts = ops._checked_counts(what, counts, batch, dev, on="the state is on")
-        if stages is not None:
-            stages = ops._checked_stages(what, stages, batch, dev, on="the state is on")
-        return counts, stages
+        return ops._checked_rows(what, batch, dev, counts, stages, on="the state is on")
 
     def _frame_tables(self, state: PriorCoderState, tables: Tensor, i: int, counts, stages):
         """Frame ``i`` of the hop on either side: the prior's cached walk at n = 1 from ``carry`` and that frame's tables ->

@@ -365,6 +365,23 @@ def resblock_forward_q4(desc: ConvDesc, x: Tensor, packed1: Tensor, bias1: Optio
 
 
 # ---------------------------------------------------------------------------- rvq
+def _stage_sizes(op: str, sizes: Optional[Sequence[int]], n_q: int, k: int):
+    """``sizes`` as a host int32 array (None: every stage has ``k`` codes) for every op that takes one -- the quantiser, its step,
+    the code prior, the entropy coder --, refused here when there are more than 64 stages or a stage lies outside 1 .. k."""
+    if n_q > 64:
+        raise AgxError(f"{op}: at most 64 stages, got {n_q}")
+    if sizes is None:
+        return None
+    sizes = [int(v) for v in sizes]
+    if len(sizes) != n_q or any(not 1 <= v <= k for v in sizes):
+        raise AgxError(f"{op}: sizes {sizes} for {n_q} stages of at most {k} codes")
+    return (ctypes.c_int32 * n_q)(*sizes)
+
+
+def _arr_ptr(arr):
+    return None if arr is None else ctypes.cast(arr, ctypes.c_void_p)
+
+
 def rvq_pack(codebooks: Tensor, sizes: Optional[Sequence[int]] = None) -> Tensor:
     """Stage images of (Q, K, D) codebooks; ``sizes[q] <= K`` = real codewords of stage q (rows beyond are padding
     the search can never select) for quantizers with one codebook size per stage."""
@@ -379,20 +396,9 @@ def rvq_pack(codebooks: Tensor, sizes: Optional[Sequence[int]] = None) -> Tensor
     if sizes is None:
         _lib.check(lib.agx_rvq_pack(_ptr(codebooks), q, k, d, _ptr(packed), _stream()), "agx_rvq_pack")
     else:
-        if len(sizes) != q:
-            raise AgxError(f"rvq_pack: {len(sizes)} sizes for {q} stages")
-        arr = (ctypes.c_int32 * q)(*[int(v) for v in sizes])
-        _lib.check(lib.agx_rvq_pack_sized(_ptr(codebooks), ctypes.cast(arr, ctypes.c_void_p), q, k, d, _ptr(packed),
-                                          _stream()), "agx_rvq_pack_sized")
+        arr = _stage_sizes("rvq_pack", sizes, q, k)
+        _lib.check(lib.agx_rvq_pack_sized(_ptr(codebooks), _arr_ptr(arr), q, k, d, _ptr(packed), _stream()), "agx_rvq_pack_sized")
     return packed
-
-
-def _rvq_stages(op: str, stages, x: Tensor) -> Optional[Tensor]:
-    """``stages`` of the quantiser's staged calls: None, or a contiguous int64 (B,) tensor on x's device -- refused
-    otherwise, before anything is launched and before the device is asked for."""
-    if stages is None:
-        return None
-    return _checked_stages(op, stages, x.shape[0] if x.dim() == 3 else -1, x.device, on="the inputs are on")
 
 
 def rvq_forward(x: Tensor, codebooks: Tensor, packed: Tensor, q_used: int,
@@ -406,7 +412,7 @@ def rvq_forward(x: Tensor, codebooks: Tensor, packed: Tensor, q_used: int,
     other stages, x_q sums its live stages only (exact 0 for ``q_b == 0``), sq_err[q] sums the frames live at q.  The kernel reads
     the tensor, the host never does; None is the unstaged call, bit for bit."""
     lib = _lib.load()
-    stages = _rvq_stages("rvq_forward", stages, x)
+    _, stages = _checked_rows("rvq_forward", x.shape[0] if x.dim() == 3 else -1, x.device, stages=stages, on="the inputs are on")
     _need_gpu(x, codebooks, packed)
     if x.dtype != torch.float32:
         raise AgxError(f"rvq_forward: expected float32, got {x.dtype}")
@@ -480,7 +486,7 @@ def rvq_backward(x: Tensor, codebooks: Tensor, index: Tensor, g_xq: Optional[Ten
     exactly zero codebook gradient.  Not the unstaged backward on the masked index, where a stage with index -1 still enters the
     loss."""
     lib = _lib.load()
-    stages = _rvq_stages("rvq_backward", stages, x)
+    _, stages = _checked_rows("rvq_backward", x.shape[0] if x.dim() == 3 else -1, x.device, stages=stages, on="the inputs are on")
     _need_gpu(x, codebooks, index, g_xq, g_commit)
     for t_ in (x, g_xq, g_commit):
         if t_ is not None and t_.dtype != torch.float32:
@@ -549,13 +555,9 @@ def _step_operands(op: str, codebooks: Tensor, q_used: int, sizes: Optional[Sequ
     q_total, k, d = codebooks.shape
     if not 0 <= q_used <= q_total:
         raise AgxError(f"{op}: q_used={q_used} outside [0, {q_total}]")
-    arr = None
-    if sizes is not None:
-        if len(sizes) != q_total:
-            raise AgxError(f"{op}: {len(sizes)} sizes for {q_total} stages")
-        arr = (ctypes.c_int32 * q_total)(*[int(v) for v in sizes])
+    arr = _stage_sizes(op, sizes, q_total, k)
     if bits is None:
-        bits = max(1, (max([int(v) for v in sizes] if sizes is not None else [k]) - 1).bit_length())
+        bits = max(1, (max(arr or [k]) - 1).bit_length())
     return codebooks, q_total, k, d, arr, int(bits)
 
 
@@ -587,10 +589,7 @@ def rvq_step_encode(z: Tensor, codebooks: Tensor, q_used: int, sizes: Optional[S
     b, dim, n = z.shape
     if dim != d:
         raise AgxError(f"rvq_step_encode: frame dim {dim} != codebook dim {d}")
-    if counts is not None:
-        counts = _checked_counts("rvq_step_encode", counts, b, z.device)
-    if stages is not None:
-        stages = _checked_stages("rvq_step_encode", stages, b, z.device)
+    counts, stages = _checked_rows("rvq_step_encode", b, z.device, counts, stages)
     p = rvq_step_packet_bytes(n, q_used, bits)
     zq = torch.empty((b, d, n), dtype=torch.float32, device=z.device) if want_zq else None
     index = torch.empty((b, n, q_used), dtype=torch.int64, device=z.device)
@@ -599,7 +598,7 @@ def rvq_step_encode(z: Tensor, codebooks: Tensor, q_used: int, sizes: Optional[S
     ws = _workspace(nbytes, z.device, "agx_rvq_step_workspace_bytes") if nbytes else None
     zsb, zsd, zst = z.stride()
     qsb, qsd, qst = zq.stride() if want_zq else (0, 0, 0)
-    head = (_ptr(z), zsb, zst, zsd, _ptr(codebooks), arr and ctypes.cast(arr, ctypes.c_void_p), _ptr(counts))
+    head = (_ptr(z), zsb, zst, zsd, _ptr(codebooks), _arr_ptr(arr), _ptr(counts))
     tail = (b, n, d, k, q_total, q_used, bits, _ptr(zq), qsb, qst, qsd, _ptr(index), _ptr(packets) if p else None, _ptr(ws), nbytes,
             _stream())
     if stages is None:
@@ -630,14 +629,11 @@ def rvq_step_decode(packets: Tensor, n: int, codebooks: Tensor, q_used: int, bit
     codebooks, q_total, k, d, arr, bits = _step_operands("rvq_step_decode", codebooks, q_used, sizes, bits)
     b = _checked_packets("rvq_step_decode", packets, n, q_used, bits)
     p = packets.shape[1]
-    if counts is not None:
-        counts = _checked_counts("rvq_step_decode", counts, b, packets.device)
-    if stages is not None:
-        stages = _checked_stages("rvq_step_decode", stages, b, packets.device)
+    counts, stages = _checked_rows("rvq_step_decode", b, packets.device, counts, stages)
     zq = torch.empty((b, d, n), dtype=torch.float32, device=packets.device)
     index = torch.empty((b, n, q_used), dtype=torch.int64, device=packets.device) if want_index else None
     qsb, qsd, qst = zq.stride()
-    head = (_ptr(packets) if p else None, bits, _ptr(codebooks), arr and ctypes.cast(arr, ctypes.c_void_p), _ptr(counts))
+    head = (_ptr(packets) if p else None, bits, _ptr(codebooks), _arr_ptr(arr), _ptr(counts))
     tail = (b, n, d, k, q_total, q_used, _ptr(zq), qsb, qst, qsd, _ptr(index), _stream())
     if stages is None:
         _lib.check(lib.agx_rvq_step_decode(*head, *tail), "agx_rvq_step_decode")
@@ -658,8 +654,7 @@ def rvq_packets_restage(packets: Tensor, n: int, q_used: int, bits: int, stages_
     stages_to = _checked_stages(op, stages_to, b, packets.device, on="the packets are on", name="stages_to")
     if stages_from is not None:
         stages_from = _checked_stages(op, stages_from, b, packets.device, on="the packets are on", name="stages_from")
-    if counts is not None:
-        counts = _checked_counts(op, counts, b, packets.device, on="the packets are on")
+    counts, _ = _checked_rows(op, b, packets.device, counts, on="the packets are on")
     if out is not None and (not isinstance(out, Tensor) or out.dtype != torch.uint8 or out.shape != packets.shape
                             or not out.is_contiguous() or out.device != packets.device):
         raise AgxError(f"{op}: out must be a contiguous uint8 {tuple(packets.shape)} tensor on '{packets.device}'")
@@ -1322,6 +1317,15 @@ def _checked_stages(op: str, stages, b: int, device, on: Optional[str] = None, n
     """``stages`` as the staged RVQ step kernels read it (include/agx.h "Per-row stage counts"): ``_checked_counts`` under its own
     name.  The kernels clamp the values to [0, q_used]; the host never reads one."""
     return _checked_counts(op, stages, b, device, on, name=name, per="stage count")
+
+
+def _checked_rows(op: str, b: int, device, counts=None, stages=None, on: Optional[str] = None):
+    """The two per-row tensors of a call, each None or checked (``_checked_counts``, then ``_checked_stages``) -> (counts, stages)."""
+    if counts is not None:
+        counts = _checked_counts(op, counts, b, device, on)
+    if stages is not None:
+        stages = _checked_stages(op, stages, b, device, on)
+    return counts, stages
 
 
 def _row_slices(what: str, rows, batch: int, of: str) -> list:
@@ -2750,8 +2754,8 @@ def wavelet_stream_out_step(hidden: int, c_out: int, kernel: int, scale: int, pa
 CODES_SAMPLE_MAX_K = _lib.CODES_SAMPLE_MAX_K
 
 
-def _prior_tensor(op: str, what: str, t, dtype, shape: tuple, device=None) -> Tensor:
-    """An operand of the code-prior ops as the kernels read it: a contiguous tensor of ``dtype`` and ``shape`` (an entry of
+def _checked_operand(op: str, what: str, t, dtype, shape: tuple, device=None) -> Tensor:
+    """An operand of the code-prior and entropy ops as the kernels read it: a contiguous tensor of ``dtype`` and ``shape`` (an entry of
     ``shape`` that is None is free), on ``device`` when one is given."""
     if not isinstance(t, Tensor) or t.dtype != dtype or t.dim() != len(shape) or \
             any(want is not None and have != want for have, want in zip(t.shape, shape)):
@@ -2764,22 +2768,6 @@ def _prior_tensor(op: str, what: str, t, dtype, shape: tuple, device=None) -> Te
     return t
 
 
-def _prior_sizes(op: str, sizes: Optional[Sequence[int]], n_q: int, k: int):
-    """``sizes`` as a host int32 array (None: every stage has ``k`` codes), refused here when a stage lies outside 1 .. k."""
-    if n_q > 64:
-        raise AgxError(f"{op}: at most 64 stages, got {n_q}")
-    if sizes is None:
-        return None
-    sizes = [int(v) for v in sizes]
-    if len(sizes) != n_q or any(not 1 <= v <= k for v in sizes):
-        raise AgxError(f"{op}: sizes {sizes} for {n_q} stages of at most {k} codes")
-    return (ctypes.c_int32 * n_q)(*sizes)
-
-
-def _arr_ptr(arr):
-    return None if arr is None else ctypes.cast(arr, ctypes.c_void_p)
-
-
 def codes_embed(index: Tensor, tables: Tensor, counts: Optional[Tensor] = None) -> Tensor:
     """Gather-sum of one table row per stage (``agx_codes_embed``, one launch): index (B, n, Q) int64, tables (Q, R, D) fp32 ->
     (B, D, n) fp32, channel-major, ``out[b, :, i] = ((0 + tables[0][index[b,i,0]]) + tables[1][index[b,i,1]]) + ...`` in stage
@@ -2787,15 +2775,14 @@ def codes_embed(index: Tensor, tables: Tensor, counts: Optional[Tensor] = None) 
     behind ``clamp(counts[b], 0, n)`` are exact 0."""
     op = "codes_embed"
     _need_gpu(index, tables, counts)
-    tables = _prior_tensor(op, "tables", tables, torch.float32, (None, None, None))
+    tables = _checked_operand(op, "tables", tables, torch.float32, (None, None, None))
     n_q, r, d = tables.shape
-    index = _prior_tensor(op, "index", index, torch.int64, (None, None, n_q), tables.device)
+    index = _checked_operand(op, "index", index, torch.int64, (None, None, n_q), tables.device)
     b, n, _ = index.shape
-    _prior_sizes(op, None, n_q, r)
+    _stage_sizes(op, None, n_q, r)
     if b < 1 or n < 1 or r < 1 or d < 1:
         raise AgxError(f"{op}: empty operands: index {tuple(index.shape)}, tables {tuple(tables.shape)}")
-    if counts is not None:
-        counts = _checked_counts(op, counts, b, tables.device)
+    counts, _ = _checked_rows(op, b, tables.device, counts)
     out = torch.empty((b, d, n), dtype=torch.float32, device=tables.device)
     tok = _observer.begin("other", (op, 4 * (b * n * n_q * d + b * d * n) + 8 * b * n * n_q, 0)) if _observer is not None else None
     _lib.check(_lib.load().agx_codes_embed(_ptr(tables), _ptr(index), _ptr(counts), _ptr(out), b, n, n_q, r, d, _stream()),
@@ -2811,15 +2798,14 @@ def codes_embed_backward(dout: Tensor, index: Tensor, rows: int, counts: Optiona
     taken in frame order on one chain per element: no atomics, two calls agree bit for bit, exact 0 for a row nobody chose."""
     op = "codes_embed_backward"
     _need_gpu(dout, index, counts)
-    dout = _prior_tensor(op, "dout", dout, torch.float32, (None, None, None))
+    dout = _checked_operand(op, "dout", dout, torch.float32, (None, None, None))
     b, d, n = dout.shape
-    index = _prior_tensor(op, "index", index, torch.int64, (b, n, None), dout.device)
+    index = _checked_operand(op, "index", index, torch.int64, (b, n, None), dout.device)
     n_q, rows = index.shape[2], int(rows)
-    _prior_sizes(op, None, n_q, rows)
+    _stage_sizes(op, None, n_q, rows)
     if b < 1 or n < 1 or n_q < 1 or rows < 1 or d < 1:
         raise AgxError(f"{op}: empty operands: dout {tuple(dout.shape)}, index {tuple(index.shape)}, rows = {rows}")
-    if counts is not None:
-        counts = _checked_counts(op, counts, b, dout.device)
+    counts, _ = _checked_rows(op, b, dout.device, counts)
     lib = _lib.load()
     dtables = torch.empty((n_q, rows, d), dtype=torch.float32, device=dout.device)
     nbytes = int(lib.agx_codes_embed_backward_workspace_bytes(b, n, n_q, d))
@@ -2830,14 +2816,14 @@ def codes_embed_backward(dout: Tensor, index: Tensor, rows: int, counts: Optiona
 
 
 def _ce_operands(op: str, logits: Tensor, target: Tensor, sizes):
-    logits = _prior_tensor(op, "logits", logits, torch.float32, (None, None, None))
+    logits = _checked_operand(op, "logits", logits, torch.float32, (None, None, None))
     b, c, t = logits.shape
-    target = _prior_tensor(op, "target", target, torch.int64, (b, t, None), logits.device)
+    target = _checked_operand(op, "target", target, torch.int64, (b, t, None), logits.device)
     n_q = target.shape[2]
     if b < 1 or t < 1 or n_q < 1 or c < 1 or c % n_q:
         raise AgxError(f"{op}: logits {tuple(logits.shape)} are not (B, Q K, T) for target {tuple(target.shape)} = (B, T, Q)")
     k = c // n_q
-    return logits, target, b, t, n_q, k, _prior_sizes(op, sizes, n_q, k)
+    return logits, target, b, t, n_q, k, _stage_sizes(op, sizes, n_q, k)
 
 
 def codes_cross_entropy(logits: Tensor, target: Tensor, sizes: Optional[Sequence[int]] = None):
@@ -2872,7 +2858,7 @@ def codes_cross_entropy_backward(logits: Tensor, target: Tensor, lse: Tensor, n_
     op = "codes_cross_entropy_backward"
     _need_gpu(logits, target, lse, n_live, g)
     logits, target, b, t, n_q, k, arr = _ce_operands(op, logits, target, sizes)
-    lse = _prior_tensor(op, "lse", lse, torch.float32, (b, t, n_q), logits.device)
+    lse = _checked_operand(op, "lse", lse, torch.float32, (b, t, n_q), logits.device)
     if not isinstance(n_live, Tensor) or n_live.dtype != torch.int64 or n_live.numel() != 1 or n_live.device != logits.device:
         raise AgxError(f"{op}: n_live must be the one-element int64 device tensor the forward returned")
     if not isinstance(g, Tensor) or g.dtype != torch.float32 or g.numel() != 1 or g.device != logits.device:
@@ -2897,7 +2883,7 @@ def codes_sample(logits: Tensor, n_q: int, seeds: Tensor, frame0: Tensor, temper
     count.  ``carry`` (B, n_q) int64, in/out: takes the codes of frame ``c_b - 1`` where ``c_b >= 1``, untouched otherwise."""
     op = "codes_sample"
     _need_gpu(logits, seeds, frame0, temperature, top_k, top_p, counts, stages, carry)
-    logits = _prior_tensor(op, "logits", logits, torch.float32, (None, None, None))
+    logits = _checked_operand(op, "logits", logits, torch.float32, (None, None, None))
     b, c, n = logits.shape
     n_q = int(n_q)
     if b < 1 or n < 1 or n_q < 1 or c < 1 or c % n_q:
@@ -2905,19 +2891,16 @@ def codes_sample(logits: Tensor, n_q: int, seeds: Tensor, frame0: Tensor, temper
     k = c // n_q
     if k > CODES_SAMPLE_MAX_K:
         raise AgxError(f"{op}: K = {k} codes per stage exceed CODES_SAMPLE_MAX_K = {CODES_SAMPLE_MAX_K}")
-    arr = _prior_sizes(op, sizes, n_q, k)
+    arr = _stage_sizes(op, sizes, n_q, k)
     dev = logits.device
-    seeds = _prior_tensor(op, "seeds", seeds, torch.int64, (b,), dev)
-    frame0 = _prior_tensor(op, "frame0", frame0, torch.int64, (b,), dev)
-    temperature = _prior_tensor(op, "temperature", temperature, torch.float32, (b,), dev)
-    top_k = _prior_tensor(op, "top_k", top_k, torch.int64, (b,), dev)
-    top_p = _prior_tensor(op, "top_p", top_p, torch.float32, (b,), dev)
-    if counts is not None:
-        counts = _checked_counts(op, counts, b, dev)
-    if stages is not None:
-        stages = _checked_stages(op, stages, b, dev)
+    seeds = _checked_operand(op, "seeds", seeds, torch.int64, (b,), dev)
+    frame0 = _checked_operand(op, "frame0", frame0, torch.int64, (b,), dev)
+    temperature = _checked_operand(op, "temperature", temperature, torch.float32, (b,), dev)
+    top_k = _checked_operand(op, "top_k", top_k, torch.int64, (b,), dev)
+    top_p = _checked_operand(op, "top_p", top_p, torch.float32, (b,), dev)
+    counts, stages = _checked_rows(op, b, dev, counts, stages)
     if carry is not None:
-        carry = _prior_tensor(op, "carry", carry, torch.int64, (b, n_q), dev)
+        carry = _checked_operand(op, "carry", carry, torch.int64, (b, n_q), dev)
     codes = torch.empty((b, n, n_q), dtype=torch.int64, device=dev)
     tok = _observer.begin("other", (op, 4 * logits.numel() + 8 * codes.numel(), 0)) if _observer is not None else None
     _lib.check(_lib.load().agx_codes_sample(_ptr(logits), _arr_ptr(arr), _ptr(seeds), _ptr(frame0), _ptr(temperature), _ptr(top_k),
@@ -2952,14 +2935,6 @@ def _need_gpu_tables(t: Optional[Tensor]) -> None:
         raise AgxError(f"audio_generation_amd runs on the MI355X only: got a tensor on '{t.device}'.  There is no CPU / eager fallback.")
 
 
-def _entropy_rows(op: str, b: int, dev, counts, stages):
-    if counts is not None:
-        counts = _checked_counts(op, counts, b, dev)
-    if stages is not None:
-        stages = _checked_stages(op, stages, b, dev)
-    return counts, stages
-
-
 def codes_cum(logits: Tensor, n_q: int, sizes: Optional[Sequence[int]] = None, counts: Optional[Tensor] = None,
               stages: Optional[Tensor] = None, out: Optional[Tensor] = None, frame0: int = 0) -> Tensor:
     """Logits -> exactly normalised integer frequency tables (``agx_codes_cum``, one launch): logits (B, n_q K, n) fp32 -> cum
@@ -2969,23 +2944,23 @@ def codes_cum(logits: Tensor, n_q: int, sizes: Optional[Sequence[int]] = None, c
     read.  ``out`` (int32 (B, n_out, n_q, K + 1)) with ``frame0``: the call's frames land at ``out[:, frame0:frame0 + n]`` and
     nothing else of ``out`` is touched -- a hop's tables gathered from one-frame steps.  ``K <= CODES_CUM_MAX_K``."""
     op = "codes_cum"
-    logits = _prior_tensor(op, "logits", logits, torch.float32, (None, None, None))
+    logits = _checked_operand(op, "logits", logits, torch.float32, (None, None, None))
     b, c, n = logits.shape
     n_q, frame0 = int(n_q), int(frame0)
     if b < 1 or n < 1 or n_q < 1 or c < 1 or c % n_q:
         raise AgxError(f"{op}: logits {tuple(logits.shape)} are not (B, Q K, n) for Q = {n_q}")
     k = c // n_q
     _entropy_limits(op, n_q, k)
-    arr = _prior_sizes(op, sizes, n_q, k)
+    arr = _stage_sizes(op, sizes, n_q, k)
     if out is not None:
-        out = _prior_tensor(op, "out", out, torch.int32, (b, None, n_q, k + 1), logits.device)
+        out = _checked_operand(op, "out", out, torch.int32, (b, None, n_q, k + 1), logits.device)
         if not 0 <= frame0 <= out.shape[1] - n:
             raise AgxError(f"{op}: frames {frame0} .. {frame0 + n - 1} do not lie in a table buffer of {out.shape[1]} frames")
     elif frame0:
         raise AgxError(f"{op}: frame0 = {frame0} without a table buffer")
     _need_gpu(logits, counts, stages)
     _need_gpu_tables(out)
-    counts, stages = _entropy_rows(op, b, logits.device, counts, stages)
+    counts, stages = _checked_rows(op, b, logits.device, counts, stages)
     if out is None:
         out = torch.empty((b, n, n_q, k + 1), dtype=torch.int32, device=logits.device)
     tok = _observer.begin("other", (op, 4 * logits.numel() + 4 * b * n * n_q * (k + 1), 0)) if _observer is not None else None
@@ -3000,7 +2975,7 @@ def _rans_tables(op: str, cum: Tensor):
     if not isinstance(cum, Tensor) or cum.dim() != 4:
         raise AgxError(f"{op}: cum must be an int32 (B, n, Q, K + 1) tensor, got "
                        f"{tuple(cum.shape) if isinstance(cum, Tensor) else type(cum).__name__}")
-    cum = _prior_tensor(op, "cum", cum, torch.int32, (None, None, None, None))
+    cum = _checked_operand(op, "cum", cum, torch.int32, (None, None, None, None))
     b, n, n_q, k1 = cum.shape
     if b < 1 or n < 1 or n_q < 1 or k1 < 2:
         raise AgxError(f"{op}: cum {tuple(cum.shape)} is not (B, n, Q, K + 1)")
@@ -3017,11 +2992,11 @@ def codes_rans_encode(cum: Tensor, codes: Tensor, sizes: Optional[Sequence[int]]
     (it is skipped).  The bytes are pinned by include/agx.h "Entropy coding" (tests/entropy_ref.py mirrors them in Python ints)."""
     op = "codes_rans_encode"
     cum, b, n, n_q, k = _rans_tables(op, cum)
-    codes = _prior_tensor(op, "codes", codes, torch.int64, (b, n, n_q), cum.device)
-    arr = _prior_sizes(op, sizes, n_q, k)
+    codes = _checked_operand(op, "codes", codes, torch.int64, (b, n, n_q), cum.device)
+    arr = _stage_sizes(op, sizes, n_q, k)
     _need_gpu_tables(cum)
     _need_gpu(codes, counts, stages)
-    counts, stages = _entropy_rows(op, b, cum.device, counts, stages)
+    counts, stages = _checked_rows(op, b, cum.device, counts, stages)
     packets = torch.empty((b, 2 * n * n_q + 4), dtype=torch.uint8, device=cum.device)
     nbytes = torch.empty((b,), dtype=torch.int64, device=cum.device)
     status = torch.empty((b,), dtype=torch.int64, device=cum.device)
@@ -3050,18 +3025,18 @@ def codes_rans_decode(cum: Tensor, packets: Tensor, nbytes: Tensor, state: Tenso
     if n < 1 or i0 < 0 or i0 > hop - n:
         raise AgxError(f"{op}: frames {i0} .. {i0 + n - 1} do not lie in a hop of {hop} frames")
     dev = cum.device
-    packets = _prior_tensor(op, "packets", packets, torch.uint8, (b, None), dev)
+    packets = _checked_operand(op, "packets", packets, torch.uint8, (b, None), dev)
     if packets.shape[1] < 1:
         raise AgxError(f"{op}: packets {tuple(packets.shape)} hold no byte")
-    nbytes = _prior_tensor(op, "nbytes", nbytes, torch.int64, (b,), dev)
-    state = _prior_tensor(op, "state", state, torch.int64, (b, 2), dev)
-    status = _prior_tensor(op, "status", status, torch.int64, (b,), dev)
+    nbytes = _checked_operand(op, "nbytes", nbytes, torch.int64, (b,), dev)
+    state = _checked_operand(op, "state", state, torch.int64, (b, 2), dev)
+    status = _checked_operand(op, "status", status, torch.int64, (b,), dev)
     if carry is not None:
-        carry = _prior_tensor(op, "carry", carry, torch.int64, (b, n_q), dev)
-    arr = _prior_sizes(op, sizes, n_q, k)
+        carry = _checked_operand(op, "carry", carry, torch.int64, (b, n_q), dev)
+    arr = _stage_sizes(op, sizes, n_q, k)
     _need_gpu_tables(cum)
     _need_gpu(packets, nbytes, state, status, counts, stages, carry)
-    counts, stages = _entropy_rows(op, b, dev, counts, stages)
+    counts, stages = _checked_rows(op, b, dev, counts, stages)
     codes = torch.empty((b, n, n_q), dtype=torch.int64, device=dev)
     tok = _observer.begin("other", (op, 8 * codes.numel() + 8 * codes.numel() + packets.numel(), 0)) if _observer is not None else None
     _lib.check(_lib.load().agx_codes_rans_decode(_ptr(cum), _ptr(packets), _ptr(nbytes), _arr_ptr(arr), _ptr(counts), _ptr(stages),

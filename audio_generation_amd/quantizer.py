@@ -171,7 +171,8 @@ class ResidualQuantizer(nn.Module):
         q_used = self._q_used(codebook_n)
         staged = {}                                   # stages=None: today's calls, argument for argument
         if stages is not None:                        # refused before the first launch (the pack included)
-            staged = {"stages": ops._rvq_stages(type(self).__name__, stages, x)}
+            staged = {"stages": ops._checked_rows(type(self).__name__, x.shape[0] if x.dim() == 3 else -1, x.device, stages=stages,
+                                                  on="the inputs are on")[1]}
         if prioritize_early:
             _warn_once("prioritize_early",
                        "audio_generation_amd.ResidualQuantizer: prioritize_early=True is accepted but IGNORED -- its "

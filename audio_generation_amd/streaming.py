@@ -380,12 +380,17 @@ def run_unit(u: Unit, p: UnitPlan, ring: Tensor, dst: Tensor, dst_ring: bool, po
                                 slope=post or 0.0, counts=counts)
 
 
-def _check(model, stream: CodecStream, x: Tensor, what: str, per_frame: int, channels: int, counts=None) -> int:
-    """Every refusal of a step, before the first launch; returns the chunk's frames."""
+def _own_stream(model, stream, what: str, training_ok: bool = False) -> None:
+    """The two refusals every step starts with: a stream of another model, a model in training mode."""
     if not isinstance(stream, CodecStream) or stream.model_id != id(model):
         raise AgxError(f"{what}: the stream belongs to another model (model.new_stream makes one for this model)")
-    if model.training:
+    if model.training and not training_ok:
         raise NotImplementedError(f"{what}: a stream is inference only: call model.eval() (there is no backward through a stream)")
+
+
+def _check(model, stream: CodecStream, x: Tensor, what: str, per_frame: int, channels: int, counts=None) -> int:
+    """Every refusal of a step, before the first launch; returns the chunk's frames."""
+    _own_stream(model, stream, what)
     if needs_grad(x, model):
         raise NotImplementedError(f"{what}: a stream is inference only: call it under torch.no_grad()")
     if x.dim() != 3 or x.shape[1] != channels:
@@ -447,10 +452,30 @@ def _step_quantizer(model, what: str, codebook_n):
     return q.codebooks.detach(), q._q_used(codebook_n), None if uniform else q.codebook_sizes, model._code_bits
 
 
-def _check_stages(what: str, stages, stream) -> None:
-    """``stages`` of a packet step (``ops._checked_stages``), refused before the first launch."""
-    if stages is not None and isinstance(stream, CodecStream):
-        ops._checked_stages(what, stages, stream.batch, stream.device, on="the stream on")
+def _step_frames(what: str, frames, stream, extra_limit: Optional[int] = None) -> int:
+    """``frames`` of a packet step as an int, refused outside 1 .. the stream's ``max_chunk`` (and ``extra_limit``, the coder
+    state's ``max_frames``) or above the frames of a quantiser step; a relay has no stream (None) and only the latter bound."""
+    frames, step = int(frames), f"the {ops.RVQ_STEP_MAX_N} frames a quantiser step takes"
+    if stream is None:
+        top, limit = ops.RVQ_STEP_MAX_N, step
+    elif extra_limit is None:
+        top, limit = stream.max_chunk, f"the stream's max_chunk = {stream.max_chunk}"
+    else:
+        top = min(stream.max_chunk, extra_limit)
+        limit = f"min(the stream's max_chunk = {stream.max_chunk}, the coder state's max_frames = {extra_limit})"
+    if not 1 <= frames <= top:
+        raise AgxError(f"{what}: frames = {frames} outside 1 .. {limit}")
+    if frames > ops.RVQ_STEP_MAX_N:
+        raise AgxError(f"{what}: frames = {frames} exceeds {step}")
+    return frames
+
+
+def _checked_packet_rows(what: str, packets, frames: int, q_used: int, bits: int) -> None:
+    """Dense packets of ``frames`` frames: uint8 rows of ``ceil(frames q_used bits / 8)`` bytes."""
+    width = -((-frames * q_used * bits) // 8)
+    if not isinstance(packets, Tensor) or packets.dtype != torch.uint8 or packets.dim() != 2 or packets.shape[1] != width:
+        got = f"{packets.dtype} {tuple(packets.shape)}" if isinstance(packets, Tensor) else type(packets).__name__
+        raise AgxError(f"{what}: packets of {frames} frames x {q_used} codes x {bits} bits are uint8 (B, {width}), got {got}")
 
 
 def encode_codes_stream(model, x: Tensor, stream: CodecStream, codebook_n: Optional[int] = None, counts: Optional[Tensor] = None,
@@ -464,11 +489,13 @@ def encode_codes_stream(model, x: Tensor, stream: CodecStream, codebook_n: Optio
     is ``ceil(c_b q_b bits / 8)`` bytes dense over its own ``q_b``, ``zq`` is the sum of those stages and ``index`` is -1 at the
     others.  ``P`` does not depend on it, and the encoder rings advance by ``c_b`` whatever ``q_b`` is."""
     cbs, q_used, sizes, bits = _step_quantizer(model, "encode_codes_stream", codebook_n)      # refusals precede the first launch
-    _check_stages("encode_codes_stream", stages, stream)
-    if isinstance(stream, CodecStream) and stream.max_chunk > ops.RVQ_STEP_MAX_N:
-        frames = model.rearrange_in(x).shape[-1] // stream.scale_factor
-        if frames > ops.RVQ_STEP_MAX_N:
-            raise AgxError(f"encode_codes_stream: a chunk of {frames} frames exceeds the {ops.RVQ_STEP_MAX_N} frames a quantiser step takes")
+    if isinstance(stream, CodecStream):                      # (what is not one is refused by the encoder step, in its own words)
+        ops._checked_rows("encode_codes_stream", stream.batch, stream.device, stages=stages, on="the stream on")
+        if stream.max_chunk > ops.RVQ_STEP_MAX_N:
+            frames = model.rearrange_in(x).shape[-1] // stream.scale_factor
+            if frames > ops.RVQ_STEP_MAX_N:
+                raise AgxError(f"encode_codes_stream: a chunk of {frames} frames exceeds the {ops.RVQ_STEP_MAX_N} frames a quantiser step "
+                               "takes")
     z = encode_latents_stream(model, x, stream, counts)
     return ops.rvq_step_encode(z, cbs, q_used, sizes, counts, bits, stages=stages)
 
@@ -476,26 +503,14 @@ def encode_codes_stream(model, x: Tensor, stream: CodecStream, codebook_n: Optio
 def _packet_step(model, what: str, packets, stream, frames, codebook_n, counts, stages):
     """Every refusal of the receiver's step, before the first launch -> (codebooks, q_used, sizes, bits, frames)."""
     cbs, q_used, sizes, bits = _step_quantizer(model, what, codebook_n)
-    if not isinstance(stream, CodecStream) or stream.model_id != id(model):
-        raise AgxError(f"{what}: the stream belongs to another model (model.new_stream makes one for this model)")
-    if model.training:
-        raise NotImplementedError(f"{what}: a stream is inference only: call model.eval() (there is no backward through a stream)")
-    frames = int(frames)
-    if not 1 <= frames <= stream.max_chunk:
-        raise AgxError(f"{what}: frames = {frames} outside 1 .. the stream's max_chunk = {stream.max_chunk}")
-    if frames > ops.RVQ_STEP_MAX_N:
-        raise AgxError(f"{what}: frames = {frames} exceeds the {ops.RVQ_STEP_MAX_N} frames a quantiser step takes")
-    width = -((-frames * q_used * bits) // 8)
-    if not isinstance(packets, Tensor) or packets.dtype != torch.uint8 or packets.dim() != 2 or packets.shape[1] != width:
-        got = f"{packets.dtype} {tuple(packets.shape)}" if isinstance(packets, Tensor) else type(packets).__name__
-        raise AgxError(f"{what}: packets of {frames} frames x {q_used} codes x {bits} bits are uint8 (B, {width}), got {got}")
+    _own_stream(model, stream, what)
+    frames = _step_frames(what, frames, stream)
+    _checked_packet_rows(what, packets, frames, q_used, bits)
     if packets.shape[0] != stream.batch:
         raise AgxError(f"{what}: the packets have batch {packets.shape[0]}, the stream has {stream.batch}")
     if packets.device != stream.device:
         raise AgxError(f"{what}: the packets are on '{packets.device}', the stream on '{stream.device}'")
-    if counts is not None:
-        ops._checked_counts(what, counts, stream.batch, stream.device, on="the stream on")
-    _check_stages(what, stages, stream)
+    ops._checked_rows(what, stream.batch, stream.device, counts, stages, on="the stream on")
     return cbs, q_used, sizes, bits, frames
 
 
@@ -518,32 +533,22 @@ def decode_codes_stream(model, packets: Tensor, stream: CodecStream, frames: int
 # --------------------------------------------------------------------------- coded packets
 def _coded_step(model, what: str, stream, coder, coder_state, frames, counts, stages):
     """Every refusal of a coded step, before the first launch: those of ``_packet_step`` without the fixed packet width, and a
-    coder whose prior does not model this quantiser's codes -> (codebooks, q_used, frames)."""
+    coder whose prior does not model this quantiser's codes -> (codebooks, q_used, sizes, bits, frames)."""
     from .entropy import PriorCoder, PriorCoderState
-    cbs, q_used, _, _ = _step_quantizer(model, what, None)
-    if not isinstance(stream, CodecStream) or stream.model_id != id(model):
-        raise AgxError(f"{what}: the stream belongs to another model (model.new_stream makes one for this model)")
-    if model.training:
-        raise NotImplementedError(f"{what}: a stream is inference only: call model.eval() (there is no backward through a stream)")
+    cbs, q_used, sizes, bits = _step_quantizer(model, what, None)
+    _own_stream(model, stream, what)
     if not isinstance(coder, PriorCoder) or not isinstance(coder_state, PriorCoderState):
         raise AgxError(f"{what}: coder must be a PriorCoder and coder_state the PriorCoderState of its new_state()")
     q = model.quantizer
     if coder.num_quantizers != q_used or tuple(coder.codebook_sizes) != tuple(int(v) for v in q.codebook_sizes):
         raise AgxError(f"{what}: the prior models {coder.num_quantizers} stages of {tuple(coder.codebook_sizes)} codes, the quantiser has "
                        f"{q_used} of {tuple(q.codebook_sizes)}")
-    frames = int(frames)
-    if not 1 <= frames <= min(stream.max_chunk, coder_state.max_frames):
-        raise AgxError(f"{what}: frames = {frames} outside 1 .. min(the stream's max_chunk = {stream.max_chunk}, the coder state's "
-                       f"max_frames = {coder_state.max_frames})")
-    if frames > ops.RVQ_STEP_MAX_N:
-        raise AgxError(f"{what}: frames = {frames} exceeds the {ops.RVQ_STEP_MAX_N} frames a quantiser step takes")
+    frames = _step_frames(what, frames, stream, coder_state.max_frames)
     if coder_state.batch != stream.batch or coder_state.rans.device != stream.device:
         raise AgxError(f"{what}: the coder state has batch {coder_state.batch} on '{coder_state.rans.device}', the stream {stream.batch} "
                        f"on '{stream.device}'")
-    if counts is not None:
-        ops._checked_counts(what, counts, stream.batch, stream.device, on="the stream on")
-    _check_stages(what, stages, stream)
-    return cbs, q_used, frames
+    ops._checked_rows(what, stream.batch, stream.device, counts, stages, on="the stream on")
+    return cbs, q_used, sizes, bits, frames
 
 
 def encode_coded_stream(model, x: Tensor, stream: CodecStream, coder, coder_state, counts: Optional[Tensor] = None,
@@ -555,11 +560,9 @@ def encode_coded_stream(model, x: Tensor, stream: CodecStream, coder, coder_stat
     what = "compress_stream_coded"
     if not isinstance(x, Tensor):
         raise AgxError(f"{what}: x_chunk must be a tensor, got {type(x).__name__}")
-    if not isinstance(stream, CodecStream) or stream.model_id != id(model):
-        raise AgxError(f"{what}: the stream belongs to another model (model.new_stream makes one for this model)")
+    _own_stream(model, stream, what, training_ok=True)       # (that refusal keeps its place: behind the quantiser's, in _coded_step)
     frames = model.rearrange_in(x).shape[-1] // stream.scale_factor
-    cbs, q_used, _ = _coded_step(model, what, stream, coder, coder_state, frames, counts, stages)
-    _, _, sizes, bits = _step_quantizer(model, what, None)
+    cbs, q_used, sizes, bits, _ = _coded_step(model, what, stream, coder, coder_state, frames, counts, stages)
     z = encode_latents_stream(model, x, stream, counts)
     _, index, _ = ops.rvq_step_encode(z, cbs, q_used, sizes, counts, bits, want_zq=False, stages=stages)
     packets, nbytes = coder.encode(coder_state, index, counts, stages)
@@ -572,7 +575,7 @@ def decode_coded_stream(model, packets: Tensor, nbytes: Tensor, stream: CodecStr
     codebooks, counts)`` -- one launch for the sum of a frame's codewords, in stage order, a -1 contributing nothing.  As on the
     dense path a row with ``c_b > 0`` and ``q_b == 0`` pushes ``c_b`` frames of the zero latent through the decoder."""
     what = "decompress_stream_coded"
-    cbs, q_used, frames = _coded_step(model, what, stream, coder, coder_state, frames, counts, stages)
+    cbs, q_used, _, _, frames = _coded_step(model, what, stream, coder, coder_state, frames, counts, stages)
     index = coder.decode(coder_state, packets, nbytes, frames, counts, stages)
     zq = ops.codes_embed(index, cbs[:q_used].contiguous(), counts)
     return decode_stream(model, zq, stream, counts), index
@@ -586,13 +589,8 @@ def restage_packets(model, packets: Tensor, frames: int, stages: Tensor, stages_
     and the returned ``stages`` -- written on the device -- is what the receiver or the next relay takes."""
     what = "restage_packets"
     _, q_used, _, bits = _step_quantizer(model, what, codebook_n)
-    frames = int(frames)
-    if not 1 <= frames <= ops.RVQ_STEP_MAX_N:
-        raise AgxError(f"{what}: frames = {frames} outside 1 .. the {ops.RVQ_STEP_MAX_N} frames a quantiser step takes")
-    width = -((-frames * q_used * bits) // 8)
-    if not isinstance(packets, Tensor) or packets.dtype != torch.uint8 or packets.dim() != 2 or packets.shape[1] != width:
-        got = f"{packets.dtype} {tuple(packets.shape)}" if isinstance(packets, Tensor) else type(packets).__name__
-        raise AgxError(f"{what}: packets of {frames} frames x {q_used} codes x {bits} bits are uint8 (B, {width}), got {got}")
+    frames = _step_frames(what, frames, None)
+    _checked_packet_rows(what, packets, frames, q_used, bits)
     return ops.rvq_packets_restage(packets.contiguous(), frames, q_used, bits, stages, stages_from, counts)
 
 
