@@ -1,25 +1,10 @@
 // Conditioning on a vector (networks/conditioning.py): the FiLM projections, scale-and-shift and their backward, and the sigmoid
 // gate of SqueezeExcite with its backward.  All of it is memory-bound fp32 with no atomics; every sum has one fixed order.
-#include "common.hpp"
-
-#include <initializer_list>
+#include "rowwise.hpp"
 
 namespace {
 
-using agx::ceil_div64;
-using agx::check_launch;
-using agx::fail;
-
-constexpr int kWave = 64;
-constexpr int kSeg = 1024;          // floats of a row one wavefront of film_apply takes: 4 rounds of 64 lanes x 16 bytes
-constexpr int64_t kMaxGrid = 2147483647;
-
-// Sum over the 64 lanes; lane 0 holds the halving tree ((p0 + p32) + (p16 + p48)) + ... of the lanes' values.
-__device__ inline float wave_sum(float v) {
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o, kWave);
-    return v;
-}
+using namespace agx;
 
 // One wavefront per output (b, r).
 __global__ __launch_bounds__(256) void film_params_kernel(const float *__restrict__ cond, const float *__restrict__ w,
@@ -43,7 +28,7 @@ __device__ inline float film_one(float x, float g, float b) {
 }
 
 // A "slab" is what shares one alignment: the T floats of a (b, c) row (CT) or the T * C floats of a batch row (TC).  One
-// wavefront takes kSeg floats of a slab: scalar up to the first 16-byte boundary, float4 to the last whole quadruple, scalar tail.
+// wavefront takes kSeg floats of a slab: CT on the row walk (rowwise.hpp), TC on the same split with a channel that moves.
 template <int LAYOUT, bool BETA>
 __global__ __launch_bounds__(256) void film_apply_kernel(const float *x, const float *__restrict__ gb, float *out, int C,
                                                          int64_t len, int64_t segs, int64_t items, int vec) {
@@ -55,25 +40,14 @@ __global__ __launch_bounds__(256) void film_apply_kernel(const float *x, const f
     const int R = BETA ? 2 * C : C;
     const float *xs = x + slab * len + s0;
     float *os = out + slab * len + s0;
-    int head = vec ? int((4 - ((reinterpret_cast<uintptr_t>(xs) >> 2) & 3)) & 3) : n;
-    head = head < n ? head : n;
-    const int nvec = (n - head) / 4, tail0 = head + 4 * nvec;
+    const RowSplit sp = row_split(xs, n, vec);
     if (LAYOUT == AGX_FILM_CT) {
         const int64_t b = slab / C;
         const int c = int(slab - b * C);
         const float g = gb[b * R + c], be = BETA ? gb[b * R + C + c] : 0.f;
-        for (int i = lane; i < head; i += kWave) os[i] = film_one<BETA>(xs[i], g, be);      // all of it where vec == 0
-#pragma unroll 4
-        for (int q = lane; q < nvec; q += kWave) {
-            float4 v = *reinterpret_cast<const float4 *>(xs + head + 4 * q);
-            v.x = film_one<BETA>(v.x, g, be);
-            v.y = film_one<BETA>(v.y, g, be);
-            v.z = film_one<BETA>(v.z, g, be);
-            v.w = film_one<BETA>(v.w, g, be);
-            *reinterpret_cast<float4 *>(os + head + 4 * q) = v;
-        }
-        if (tail0 + lane < n) os[tail0 + lane] = film_one<BETA>(xs[tail0 + lane], g, be);
+        row_walk<4, false>(sp, xs, nullptr, os, n, lane, [&](float xv, float) { return film_one<BETA>(xv, g, be); });
     } else {
+        const int head = sp.head, nvec = sp.nvec, tail0 = sp.tail0;
         const float *gam = gb + slab * R, *bet = gam + C;    // bet is read with BETA only
         for (int i = lane; i < head; i += kWave) {      // all of it where vec == 0
             const int c = int((s0 + i) % C);
@@ -103,7 +77,7 @@ __global__ __launch_bounds__(256) void film_apply_kernel(const float *x, const f
 }
 
 // The reduction order of one (b, c), shared by the two backward kernels: walker j of 256 takes t = j, j + 256, ... in
-// increasing order; the walkers of a group of 64 are added in the halving tree of wave_sum; the groups as (g0 + g1) + (g2 + g3).
+// increasing order; the walkers are added in the workgroup order (rowwise.hpp).
 
 // CT: one workgroup per (b, c) row, thread j is walker j.
 template <bool BETA>
@@ -132,13 +106,14 @@ __global__ __launch_bounds__(256) void film_bwd_ct_kernel(const float *__restric
     }
     __syncthreads();
     if (threadIdx.x == 0) {
-        dgb[b * R + c] = (red[0][0] + red[0][1]) + (red[0][2] + red[0][3]);
-        if (BETA) dgb[b * R + C + c] = (red[1][0] + red[1][1]) + (red[1][2] + red[1][3]);
+        dgb[b * R + c] = groups_sum(red[0]);
+        if (BETA) dgb[b * R + C + c] = groups_sum(red[1]);
     }
 }
 
 // TC: one workgroup per (b, 64 channels).  A lane is a channel, wavefront g holds the 64 walkers 64 g .. 64 g + 63 of its
-// channels in registers and walks t = 64 g + m + 256 i: every load is one coalesced channel-fastest row.
+// channels in registers and walks t = 64 g + m + 256 i: every load is one coalesced channel-fastest row.  The workgroup order
+// (rowwise.hpp) is written out here: the 64 walkers of a group are registers of one lane, not lanes.
 template <bool BETA>
 __global__ __launch_bounds__(256) void film_bwd_tc_kernel(const float *__restrict__ x, const float *__restrict__ gb,
                                                           const float *__restrict__ dout, float *__restrict__ dx,
@@ -208,12 +183,10 @@ __global__ __launch_bounds__(256) void film_params_bwd_kernel(const float *__res
     }
 }
 
-__device__ inline float sigmoidf(float z) { return 1.f / (1.f + expf(-z)); }
-
 __global__ __launch_bounds__(256) void sigmoid_gate_kernel(const float *x, const float *__restrict__ z, float *out, int64_t n,
                                                            int vec) {
-    const int64_t i = int64_t(blockIdx.x) * 256 + threadIdx.x, stride = int64_t(gridDim.x) * 256;
-    const int64_t n4 = vec ? n / 4 : 0;
+    int64_t i, stride, n4;
+    flat_walk(n, vec, i, stride, n4);
     for (int64_t q = i; q < n4; q += stride) {
         float4 v = reinterpret_cast<const float4 *>(x)[q];
         const float4 zz = reinterpret_cast<const float4 *>(z)[q];
@@ -235,8 +208,8 @@ __device__ inline void gate_bwd_one(float x, float z, float d, float &dx, float 
 __global__ __launch_bounds__(256) void sigmoid_gate_bwd_kernel(const float *__restrict__ x, const float *__restrict__ z,
                                                                const float *__restrict__ dout, float *__restrict__ dx,
                                                                float *__restrict__ dz, int64_t n, int vec) {
-    const int64_t i = int64_t(blockIdx.x) * 256 + threadIdx.x, stride = int64_t(gridDim.x) * 256;
-    const int64_t n4 = vec ? n / 4 : 0;
+    int64_t i, stride, n4;
+    flat_walk(n, vec, i, stride, n4);
     for (int64_t q = i; q < n4; q += stride) {
         const float4 xv = reinterpret_cast<const float4 *>(x)[q], zv = reinterpret_cast<const float4 *>(z)[q];
         const float4 dv = reinterpret_cast<const float4 *>(dout)[q];
@@ -249,17 +222,6 @@ __global__ __launch_bounds__(256) void sigmoid_gate_bwd_kernel(const float *__re
         reinterpret_cast<float4 *>(dz)[q] = b;
     }
     for (int64_t e = 4 * n4 + i; e < n; e += stride) gate_bwd_one(x[e], z[e], dout[e], dx[e], dz[e]);
-}
-
-inline bool all_aligned16(std::initializer_list<const void *> ps) {
-    for (const void *p : ps)
-        if (reinterpret_cast<uintptr_t>(p) & 15) return false;
-    return true;
-}
-
-inline unsigned gate_blocks(int64_t n) {
-    const int64_t nb = ceil_div64(n, 1024);
-    return unsigned(nb < 65536 ? nb : 65536);
 }
 
 inline bool bad_layout(int32_t layout) { return layout != AGX_FILM_CT && layout != AGX_FILM_TC; }
@@ -284,9 +246,10 @@ int agx_film_apply(const float *x, const float *gb, float *out, int32_t B, int32
     if (!x || !gb || !out) return fail(AGX_ERR_NULL_POINTER, "film_apply: NULL pointer");
     const bool ct = layout == AGX_FILM_CT;
     const int64_t slabs = ct ? int64_t(B) * C : B, len = ct ? T : int64_t(T) * C;
-    const int64_t segs = ceil_div64(len, kSeg), items = slabs * segs, blocks = ceil_div64(items, 4);
-    if (blocks > kMaxGrid) return fail(AGX_ERR_BAD_SHAPE, "film_apply: (%d, %d, %d) exceeds the grid", B, C, T);
-    const int vec = ((reinterpret_cast<uintptr_t>(x) ^ reinterpret_cast<uintptr_t>(out)) & 15) == 0;
+    int64_t segs, items;
+    const int64_t blocks = walk_blocks(slabs, len, segs, items);
+    if (blocks < 0) return fail(AGX_ERR_BAD_SHAPE, "film_apply: (%d, %d, %d) exceeds the grid", B, C, T);
+    const int vec = same_phase16({x, out});
     hipStream_t st = static_cast<hipStream_t>(stream);
 #define AGX_FILM_APPLY(L, BETA) \
     hipLaunchKernelGGL((film_apply_kernel<L, BETA>), dim3(unsigned(blocks)), dim3(256), 0, st, x, gb, out, C, len, segs, items, vec)
@@ -338,7 +301,7 @@ int agx_film_params_backward(const float *cond, const float *w, const float *dgb
 int agx_sigmoid_gate(const float *x, const float *z, float *out, int64_t n, void *stream) {
     if (n <= 0) return AGX_OK;
     if (!x || !z || !out) return fail(AGX_ERR_NULL_POINTER, "sigmoid_gate: NULL pointer");
-    hipLaunchKernelGGL(sigmoid_gate_kernel, dim3(gate_blocks(n)), dim3(256), 0, static_cast<hipStream_t>(stream), x, z, out, n,
+    hipLaunchKernelGGL(sigmoid_gate_kernel, dim3(flat_blocks(n)), dim3(256), 0, static_cast<hipStream_t>(stream), x, z, out, n,
                        int(all_aligned16({x, z, out})));
     return check_launch("agx_sigmoid_gate");
 }
@@ -347,7 +310,7 @@ int agx_sigmoid_gate_backward(const float *x, const float *z, const float *dout,
                               void *stream) {
     if (n <= 0) return AGX_OK;
     if (!x || !z || !dout || !dx || !dz) return fail(AGX_ERR_NULL_POINTER, "sigmoid_gate_backward: NULL pointer");
-    hipLaunchKernelGGL(sigmoid_gate_bwd_kernel, dim3(gate_blocks(n)), dim3(256), 0, static_cast<hipStream_t>(stream), x, z, dout,
+    hipLaunchKernelGGL(sigmoid_gate_bwd_kernel, dim3(flat_blocks(n)), dim3(256), 0, static_cast<hipStream_t>(stream), x, z, dout,
                        dx, dz, n, int(all_aligned16({x, z, dout, dx, dz})));
     return check_launch("agx_sigmoid_gate_backward");
 }

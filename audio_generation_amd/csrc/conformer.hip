@@ -13,45 +13,14 @@
 // The causal form (agx.h: left = K - 1) is the same kernels with the other halo width, and it streams: hist (B, C, K - 1) holds the
 // post-GLU values of the K - 1 frames before a call -- the one place g is written -- and the step kernel (7) and the history
 // update (8) rewrite it in place.  Chunked calls are bit for bit the single call: an output's fma chain sees the same K operands.
-#include "common.hpp"
+#include "rowwise.hpp"
 
 namespace {
 
-using agx::ceil_div64;
-using agx::check_launch;
-using agx::fail;
+using namespace agx;
 
-constexpr int kWave = 64;
 constexpr int kTile = 1024;                       // output positions of a row one workgroup of the conv kernels takes
 constexpr int kMaxK = AGX_CONFORMER_MAX_K;        // taps; the LDS images hold kTile + kMaxK - 1 floats
-constexpr int kSeg = 1024;                        // floats of a row one wavefront of the element-wise walk takes
-constexpr int kRedSeg = 2048;                     // floats of a row one workgroup of a reduction takes: 8 per thread
-constexpr int64_t kMaxGrid = 2147483647;
-
-__device__ inline float sigmoidf(float z) { return 1.f / (1.f + expf(-z)); }
-__device__ inline float siluf(float a) { return a * sigmoidf(a); }
-// d silu / da = s (1 + a (1 - s)); s == 0 (a <= -89) gives exactly 0 and s == 1 (a >= 17) exactly 1
-__device__ inline float silu_gradf(float a) {
-    const float s = sigmoidf(a);
-    return s * fmaf(a, 1.f - s, 1.f);
-}
-
-// Sum over the 64 lanes; lane 0 holds the halving tree ((p0 + p32) + (p16 + p48)) + ... of the lanes' values.
-__device__ inline float wave_sum(float v) {
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o, kWave);
-    return v;
-}
-
-// Sum over the 256 threads of a workgroup, the same value in every thread: the halving tree per group of 64, the groups as
-// (g0 + g1) + (g2 + g3).  red holds 4 floats; two barriers.
-__device__ inline float block_sum(float v, float *red) {
-    v = wave_sum(v);
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-    __syncthreads();
-    return (red[0] + red[1]) + (red[2] + red[3]);
-}
 
 // Per-channel constants of the normalisation.
 struct Norm {
@@ -192,10 +161,9 @@ __global__ __launch_bounds__(64) void bn_stats_finish_kernel(const float *__rest
     }
 }
 
-// Kernel 3 and the last stage of kernel 4 on the walk of film_apply_kernel<CT>: one wavefront takes kSeg floats of a row, scalar
-// up to the first 16-byte boundary, float4 to the last whole quadruple, scalar tail.  BWD == false: out = silu(a(z)).
-// BWD == true (training): out = dz = gamma rstd (da - sum da / N - zhat sum (da zhat) / N), d = dy, sums[2 c], sums[2 c + 1] the
-// channel's two sums.  out may alias z (forward) or d (backward): an element is read by the lane that writes it, before it writes.
+// Kernel 3 and the last stage of kernel 4, on the row walk (rowwise.hpp).  BWD == false: out = silu(a(z)).  BWD == true
+// (training): out = dz = gamma rstd (da - sum da / N - zhat sum (da zhat) / N), d = dy, sums[2 c], sums[2 c + 1] the channel's two
+// sums.  out may alias z (forward) or d (backward).
 template <bool BWD>
 __global__ __launch_bounds__(256) void bn_silu_walk_kernel(const float *z, const float *d, const float *__restrict__ gamma,
                                                            const float *__restrict__ beta, const float *__restrict__ mean,
@@ -212,28 +180,12 @@ __global__ __launch_bounds__(256) void bn_silu_walk_kernel(const float *z, const
     const float k1 = BWD ? sums[2 * c] * inv_count : 0.f, k2 = BWD ? sums[2 * c + 1] * inv_count : 0.f;
     const float *zs = z + row * len + s0, *ds = BWD ? d + row * len + s0 : nullptr;
     float *os = out + row * len + s0;
-    int head = vec ? int((4 - ((reinterpret_cast<uintptr_t>(zs) >> 2) & 3)) & 3) : n;
-    head = head < n ? head : n;
-    const int nvec = (n - head) / 4, tail0 = head + 4 * nvec;
-    auto one = [&](float zv, float dv) {
+    row_walk<2, BWD>(row_split(zs, n, vec), zs, ds, os, n, lane, [&](float zv, float dv) {
         const float a = act_of(zv, nm);
         if (!BWD) return siluf(a);
         const float da = dv * silu_gradf(a);
         return nm.scale * fmaf(-zhat_of(zv, nm), k2, da - k1);
-    };
-    for (int i = lane; i < head; i += kWave) os[i] = one(zs[i], BWD ? ds[i] : 0.f);      // all of it where vec == 0
-#pragma unroll 2
-    for (int q = lane; q < nvec; q += kWave) {
-        float4 v = *reinterpret_cast<const float4 *>(zs + head + 4 * q);
-        float4 g = make_float4(0.f, 0.f, 0.f, 0.f);
-        if (BWD) g = *reinterpret_cast<const float4 *>(ds + head + 4 * q);
-        v.x = one(v.x, g.x);
-        v.y = one(v.y, g.y);
-        v.z = one(v.z, g.z);
-        v.w = one(v.w, g.w);
-        *reinterpret_cast<float4 *>(os + head + 4 * q) = v;
-    }
-    if (tail0 + lane < n) os[tail0 + lane] = one(zs[tail0 + lane], BWD ? ds[tail0 + lane] : 0.f);
+    });
 }
 
 // Kernel 4, stage 1.  One workgroup per (row, segment of kRedSeg floats): da = dy silu'(a), the partial sums of da and of
@@ -268,8 +220,8 @@ __global__ __launch_bounds__(256) void bn_silu_bwd_reduce_kernel(const float *dy
     }
 }
 
-// Kernel 4, stage 2.  One wavefront per channel; partials numbered p = b * segs + seg, lane l adds p = l, l + 64, ... in
-// increasing order, then the halving tree.  sums (2 C floats behind the partials) is what the training apply stage reads.
+// Kernel 4, stage 2.  One wavefront per channel: the channel finish order of channel_sum (rowwise.hpp), written out because both
+// slots are added in one pass over p.  sums (2 C floats behind the partials) is what the training apply stage reads.
 __global__ __launch_bounds__(64) void bn_silu_bwd_finish_kernel(const float *__restrict__ partial, float *__restrict__ sums,
                                                                 float *__restrict__ dgamma, float *__restrict__ dbeta, int C,
                                                                 int segs, int64_t count) {
@@ -295,7 +247,7 @@ __global__ __launch_bounds__(64) void bn_silu_bwd_finish_kernel(const float *__r
 // thread j takes the positions j, j + 256, ... of the tile:
 //   dg[t] = sum_k w[c, k] dz[t + left - k]   (fma chain in increasing k from 0)      du_a = dg s      du_gate = (dg a) (s (1 - s))
 // PARAMS: the tile's share of dw[c, k] = sum_t dz[t] g[t + k - left] for every k, and of dbias[c] = sum_t dz[t] (slot K): walker
-// sums in increasing t (fma), the halving tree per group of 64, the groups as (g0 + g1) + (g2 + g3).
+// sums in increasing t (fma), added in the workgroup order (rowwise.hpp), every slot behind the one barrier.
 template <bool PARAMS, bool CAUSAL>
 __global__ __launch_bounds__(256) void glu_dwconv_bwd_kernel(const float *__restrict__ dz, const float *__restrict__ u,
                                                              const float *__restrict__ w, float *__restrict__ du,
@@ -338,14 +290,14 @@ __global__ __launch_bounds__(256) void glu_dwconv_bwd_kernel(const float *__rest
         }
         __syncthreads();
         if (int(threadIdx.x) <= K) {
-            const float *r = red + 4 * threadIdx.x;
+            const float *r = red + 4 * threadIdx.x;      // groups_sum (rowwise.hpp) written out: a call reorders the loop set-up
             partial[int64_t(blockIdx.x) * (K + 1) + threadIdx.x] = (r[0] + r[1]) + (r[2] + r[3]);
         }
     }
 }
 
-// Kernel 5, stage 2.  One wavefront per channel, slot by slot: the channel's partials of a slot are numbered p = b * tiles + tile;
-// lane l adds p = l, l + 64, ... in increasing order, then the halving tree.
+// Kernel 5, stage 2.  One wavefront per channel, slot by slot: the channel finish order of channel_sum (rowwise.hpp) with tiles
+// for segments, written out because a call moves the loop-invariant index arithmetic.
 __global__ __launch_bounds__(64) void glu_dwconv_bwd_finish_kernel(const float *__restrict__ partial, float *__restrict__ dw,
                                                                    float *__restrict__ dbias, int C, int K, int tiles,
                                                                    int64_t count) {
@@ -367,8 +319,8 @@ __global__ __launch_bounds__(64) void glu_dwconv_bwd_finish_kernel(const float *
 // Kernel 6.  out = silu(x), or with d: out = d silu'(x).  out may alias x or d.
 template <bool BWD>
 __global__ __launch_bounds__(256) void silu_kernel(const float *x, const float *d, float *out, int64_t n, int vec) {
-    const int64_t i = int64_t(blockIdx.x) * 256 + threadIdx.x, stride = int64_t(gridDim.x) * 256;
-    const int64_t n4 = vec ? n / 4 : 0;
+    int64_t i, stride, n4;
+    flat_walk(n, vec, i, stride, n4);
     auto one = [](float xv, float dv) { return BWD ? dv * silu_gradf(xv) : siluf(xv); };
     for (int64_t q = i; q < n4; q += stride) {
         float4 v = reinterpret_cast<const float4 *>(x)[q];
@@ -479,39 +431,32 @@ __global__ __launch_bounds__(256) void glu_hist_update_kernel(const float *__res
     if (mine) hist[int64_t(row0) * H + e] = v;
 }
 
-inline bool all_aligned16(std::initializer_list<const void *> ps) {
-    for (const void *p : ps)
-        if (reinterpret_cast<uintptr_t>(p) & 15) return false;
-    return true;
-}
-
-inline unsigned flat_blocks(int64_t n) {
-    const int64_t nb = ceil_div64(n, 1024);
-    return unsigned(nb < 65536 ? nb : 65536);
-}
-
-// The shape of every op but the two SiLU ones.  AGX_OK: rows and the workgroup counts of the three walks are valid.
+// The shape of every op but the two SiLU ones: rows and the workgroup counts of the three passes over them.
 struct Shape {
-    int64_t rows, tiles, segs, wsegs;      // rows = B C; per row: conv tiles, reduction segments, element-wise segments
+    int64_t rows, tiles;            // rows = B C; conv tiles per row
+    int64_t segs, red;              // reducing pass: segments per row, workgroups = (row, segment) partials
+    int64_t wsegs, items, walk;     // row walk: segments per row, wavefront items, workgroups
 };
-inline int shape_of(const char *op, int32_t B, int32_t C, int32_t T, int32_t K, Shape &s) {
-    if (B <= 0 || C <= 0 || T <= 0) return fail(AGX_ERR_BAD_SHAPE, "%s: (B, C, T) = (%d, %d, %d)", op, B, C, T);
-    if (K < 1 || K > kMaxK) return fail(AGX_ERR_BAD_SHAPE, "%s: K = %d is outside [1, %d]", op, K, kMaxK);
+enum ShapeFault { kShapeOk, kShapeDims, kShapeTaps, kShapeGrid };
+// The computation.  The conv tiles are the finest of the three divisions of a row: within their grid, so are the other two.
+inline ShapeFault shape_fault(int32_t B, int32_t C, int32_t T, int32_t K, Shape &s) {
+    if (B <= 0 || C <= 0 || T <= 0) return kShapeDims;
+    if (K < 1 || K > kMaxK) return kShapeTaps;
     s.rows = int64_t(B) * C;
     s.tiles = ceil_div64(T, kTile);
-    s.segs = ceil_div64(T, kRedSeg);
-    s.wsegs = ceil_div64(T, kSeg);
-    if (s.tiles > kMaxGrid / s.rows)
-        return fail(AGX_ERR_BAD_SHAPE, "%s: (%d, %d, %d) exceeds the grid", op, B, C, T);
-    return AGX_OK;
+    if (s.tiles > kMaxGrid / s.rows) return kShapeGrid;
+    s.red = reduce_blocks(s.rows, T, s.segs);
+    s.walk = walk_blocks(s.rows, T, s.wsegs, s.items);
+    return kShapeOk;
 }
-inline bool shape_ok(int32_t B, int32_t C, int32_t T, int32_t K, Shape &s) {
-    if (B <= 0 || C <= 0 || T <= 0 || K < 1 || K > kMaxK) return false;
-    s.rows = int64_t(B) * C;
-    s.tiles = ceil_div64(T, kTile);
-    s.segs = ceil_div64(T, kRedSeg);
-    s.wsegs = ceil_div64(T, kSeg);
-    return s.tiles <= kMaxGrid / s.rows;
+// ... and its refusals.  AGX_OK: s is valid.
+inline int shape_of(const char *op, int32_t B, int32_t C, int32_t T, int32_t K, Shape &s) {
+    switch (shape_fault(B, C, T, K, s)) {
+    case kShapeDims: return fail(AGX_ERR_BAD_SHAPE, "%s: (B, C, T) = (%d, %d, %d)", op, B, C, T);
+    case kShapeTaps: return fail(AGX_ERR_BAD_SHAPE, "%s: K = %d is outside [1, %d]", op, K, kMaxK);
+    case kShapeGrid: return fail(AGX_ERR_BAD_SHAPE, "%s: (%d, %d, %d) exceeds the grid", op, B, C, T);
+    default: return AGX_OK;
+    }
 }
 
 }  // namespace
@@ -553,8 +498,8 @@ int agx_glu_dwconv_causal_forward(const float *u, const float *w, const float *b
 
 size_t agx_bn_stats_workspace_bytes(int32_t B, int32_t C, int32_t T) {
     Shape s;
-    if (!shape_ok(B, C, T, 1, s)) return 0;
-    return size_t(2 * s.rows * s.segs) * sizeof(float);
+    if (shape_fault(B, C, T, 1, s)) return 0;
+    return size_t(2 * s.red) * sizeof(float);
 }
 
 int agx_bn_stats(const float *z, float *mean, float *var, float *running_mean, float *running_var, int64_t *num_batches_tracked,
@@ -569,7 +514,7 @@ int agx_bn_stats(const float *z, float *mean, float *var, float *running_mean, f
         return fail(AGX_ERR_WORKSPACE, "bn_stats: workspace of %zu bytes, %zu needed", workspace_bytes, need);
     hipStream_t st = static_cast<hipStream_t>(stream);
     float *partial = static_cast<float *>(workspace);
-    hipLaunchKernelGGL(bn_stats_kernel, dim3(unsigned(s.rows * s.segs)), dim3(256), 0, st, z, partial, T, int(s.segs));
+    hipLaunchKernelGGL(bn_stats_kernel, dim3(unsigned(s.red)), dim3(256), 0, st, z, partial, T, int(s.segs));
     if (const int rc = check_launch("agx_bn_stats"); rc != AGX_OK) return rc;
     hipLaunchKernelGGL(bn_stats_finish_kernel, dim3(unsigned(C)), dim3(64), 0, st, static_cast<const float *>(partial), mean, var,
                        running_mean, running_var, num_batches_tracked, momentum, C, T, int(s.segs),
@@ -582,18 +527,16 @@ int agx_bn_silu_forward(const float *z, const float *gamma, const float *beta, c
     Shape s;
     if (const int rc = shape_of("bn_silu_forward", B, C, T, 1, s); rc != AGX_OK) return rc;
     if (!z || !gamma || !beta || !mean || !var || !y) return fail(AGX_ERR_NULL_POINTER, "bn_silu_forward: NULL pointer");
-    const int64_t items = s.rows * s.wsegs;
-    const int vec = ((reinterpret_cast<uintptr_t>(z) ^ reinterpret_cast<uintptr_t>(y)) & 15) == 0;
-    hipLaunchKernelGGL(bn_silu_walk_kernel<false>, dim3(unsigned(ceil_div64(items, 4))), dim3(256), 0, static_cast<hipStream_t>(stream),
-                       z, static_cast<const float *>(nullptr), gamma, beta, mean, var, static_cast<const float *>(nullptr), eps, 0.f, y,
-                       C, int64_t(T), s.wsegs, items, training != 0, vec);
+    hipLaunchKernelGGL(bn_silu_walk_kernel<false>, dim3(unsigned(s.walk)), dim3(256), 0, static_cast<hipStream_t>(stream), z,
+                       static_cast<const float *>(nullptr), gamma, beta, mean, var, static_cast<const float *>(nullptr), eps, 0.f, y, C,
+                       int64_t(T), s.wsegs, s.items, training != 0, int(same_phase16({z, y})));
     return check_launch("agx_bn_silu_forward");
 }
 
 size_t agx_bn_silu_backward_workspace_bytes(int32_t B, int32_t C, int32_t T) {
     Shape s;
-    if (!shape_ok(B, C, T, 1, s)) return 0;
-    return size_t(2 * s.rows * s.segs + 2 * int64_t(C)) * sizeof(float);
+    if (shape_fault(B, C, T, 1, s)) return 0;
+    return size_t(2 * s.red + 2 * int64_t(C)) * sizeof(float);
 }
 
 int agx_bn_silu_backward(const float *dy, const float *z, const float *gamma, const float *beta, const float *mean, const float *var,
@@ -607,24 +550,22 @@ int agx_bn_silu_backward(const float *dy, const float *z, const float *gamma, co
     if (!workspace || workspace_bytes < need)
         return fail(AGX_ERR_WORKSPACE, "bn_silu_backward: workspace of %zu bytes, %zu needed", workspace_bytes, need);
     hipStream_t st = static_cast<hipStream_t>(stream);
-    float *partial = static_cast<float *>(workspace), *sums = partial + 2 * s.rows * s.segs;
-    hipLaunchKernelGGL(bn_silu_bwd_reduce_kernel, dim3(unsigned(s.rows * s.segs)), dim3(256), 0, st, dy, z, gamma, beta, mean, var, eps,
+    float *partial = static_cast<float *>(workspace), *sums = partial + 2 * s.red;
+    hipLaunchKernelGGL(bn_silu_bwd_reduce_kernel, dim3(unsigned(s.red)), dim3(256), 0, st, dy, z, gamma, beta, mean, var, eps,
                        dz, partial, C, T, int(s.segs), training != 0);
     if (const int rc = check_launch("agx_bn_silu_backward"); rc != AGX_OK) return rc;
     hipLaunchKernelGGL(bn_silu_bwd_finish_kernel, dim3(unsigned(C)), dim3(64), 0, st, static_cast<const float *>(partial), sums, dgamma,
                        dbeta, C, int(s.segs), int64_t(B) * s.segs);
     if (const int rc = check_launch("agx_bn_silu_backward"); rc != AGX_OK || !training || !dz) return rc;
-    const int64_t items = s.rows * s.wsegs;
-    const uintptr_t pz = reinterpret_cast<uintptr_t>(z), pd = reinterpret_cast<uintptr_t>(dy), po = reinterpret_cast<uintptr_t>(dz);
-    const int vec = (((pz ^ pd) | (pz ^ po)) & 15) == 0;
-    hipLaunchKernelGGL(bn_silu_walk_kernel<true>, dim3(unsigned(ceil_div64(items, 4))), dim3(256), 0, st, z, dy, gamma, beta, mean, var,
-                       static_cast<const float *>(sums), eps, 1.f / (float(B) * float(T)), dz, C, int64_t(T), s.wsegs, items, 1, vec);
+    hipLaunchKernelGGL(bn_silu_walk_kernel<true>, dim3(unsigned(s.walk)), dim3(256), 0, st, z, dy, gamma, beta, mean, var,
+                       static_cast<const float *>(sums), eps, 1.f / (float(B) * float(T)), dz, C, int64_t(T), s.wsegs, s.items, 1,
+                       int(same_phase16({z, dy, dz})));
     return check_launch("agx_bn_silu_backward");
 }
 
 size_t agx_glu_dwconv_backward_workspace_bytes(int32_t B, int32_t C, int32_t T, int32_t K) {
     Shape s;
-    if (!shape_ok(B, C, T, K, s)) return 0;
+    if (shape_fault(B, C, T, K, s)) return 0;
     return size_t(s.rows * s.tiles * (K + 1)) * sizeof(float);
 }
 

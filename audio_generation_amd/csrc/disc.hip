@@ -3,16 +3,9 @@
 // All are bandwidth- or latency-trivial next to the conv stacks; written for determinism
 // (fixed reduction orders, no atomics).
 #include "conv_kernels.hpp"
+#include "rowwise.hpp"
 
 namespace agx {
-
-__device__ __forceinline__ float block_sum_256(float v, float *sh4) {
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) sh4[threadIdx.x >> 6] = v;
-    __syncthreads();
-    return (sh4[0] + sh4[1]) + (sh4[2] + sh4[3]);
-}
 
 // ------------------------------------------------------------------ spectral norm
 // t[c] = sum_r W[r, c] u[r]   (64 columns per block, rows in 4 interleaved slices)
@@ -47,7 +40,7 @@ __global__ __launch_bounds__(256) void sn_normalize_kernel(const float *__restri
     __shared__ float sh[4];
     float acc = 0.f;
     for (int i = threadIdx.x; i < n; i += 256) acc = fmaf(src[i], src[i], acc);
-    const float nrm = fmaxf(sqrtf(block_sum_256(acc, sh)), eps);
+    const float nrm = fmaxf(sqrtf(block_sum(acc, sh)), eps);
     for (int i = threadIdx.x; i < n; i += 256) dst[i] = src[i] / nrm;
 }
 
@@ -57,7 +50,7 @@ __global__ __launch_bounds__(256) void sn_dot_kernel(const float *__restrict__ u
     __shared__ float sh[4];
     float acc = 0.f;
     for (int i = threadIdx.x; i < n; i += 256) acc = fmaf(u[i], s[i], acc);
-    const float tot = block_sum_256(acc, sh);
+    const float tot = block_sum(acc, sh);
     if (threadIdx.x == 0) sigma[0] = tot;
 }
 
@@ -105,7 +98,7 @@ __global__ __launch_bounds__(256) void sn_rowdot_kernel(const float *__restrict_
     const size_t base = size_t(blockIdx.x) * cols;
     float acc = 0.f;
     for (int c = threadIdx.x; c < cols; c += 256) acc = fmaf(g[base + c], w[base + c], acc);
-    const float tot = block_sum_256(acc, sh);
+    const float tot = block_sum(acc, sh);
     if (threadIdx.x == 0) rowdot[blockIdx.x] = tot;
 }
 
@@ -178,11 +171,11 @@ __global__ __launch_bounds__(256) void reduce_partial_kernel(const float *__rest
     else          // an operand 4, 8 or 12 bytes off: the same four elements by 4-byte loads
         sweep([](const float *p, int64_t q) { return make_float4(p[4 * q], p[4 * q + 1], p[4 * q + 2], p[4 * q + 3]); });
     for (int64_t e = 4 * n4 + first; e < n; e += stride) term(x[e], two ? y[e] : 0.f, 0);
-    const float tot = block_sum_256((acc[0] + acc[1]) + (acc[2] + acc[3]), sh);
+    const float tot = block_sum((acc[0] + acc[1]) + (acc[2] + acc[3]), sh);
     if (threadIdx.x == 0) part[blockIdx.x] = tot;
     if (PAIR) {
         __syncthreads();
-        const float tb = block_sum_256((bcc[0] + bcc[1]) + (bcc[2] + bcc[3]), sh);
+        const float tb = block_sum((bcc[0] + bcc[1]) + (bcc[2] + bcc[3]), sh);
         if (threadIdx.x == 0) part[gridDim.x + blockIdx.x] = tb;
     }
 }
@@ -310,11 +303,6 @@ int agx_avgpool1d(const float *x, float *y, int64_t rows, int32_t l_in, int32_t 
     return check_launch("agx_avgpool1d");
 }
 
-static inline int aligned16(const void *a, const void *b, const void *c, const void *d) {
-    return ((reinterpret_cast<uintptr_t>(a) | reinterpret_cast<uintptr_t>(b) | reinterpret_cast<uintptr_t>(c) |
-             reinterpret_cast<uintptr_t>(d)) & 15) == 0;
-}
-
 int agx_reduce_mean(const float *x, const float *y, int64_t n, int32_t mode, float *out, float *workspace,
                     void *stream) {
     using namespace agx;
@@ -322,7 +310,7 @@ int agx_reduce_mean(const float *x, const float *y, int64_t n, int32_t mode, flo
     if (!x || !out || !workspace || ((mode == 3 || mode == 5) && !y)) return fail(AGX_ERR_NULL_POINTER, "reduce_mean: NULL pointer");
     hipStream_t st = static_cast<hipStream_t>(stream);
     const int nb = int(ceil_div64(n, 4096) < 1024 ? ceil_div64(n, 4096) : 1024);
-    hipLaunchKernelGGL(reduce_partial_kernel<0>, dim3(nb), dim3(256), 0, st, x, y, n, mode, aligned16(x, y, nullptr, nullptr),
+    hipLaunchKernelGGL(reduce_partial_kernel<0>, dim3(nb), dim3(256), 0, st, x, y, n, mode, int(all_aligned16({x, y})),
                        workspace);
     hipLaunchKernelGGL(reduce_final_kernel, dim3(1), dim3(256), 0, st, workspace, nb, 1.0 / double(n), out);
     return check_launch("agx_reduce_mean");
@@ -335,7 +323,7 @@ int agx_reduce_mean_backward(const float *x, const float *y, int64_t n, int32_t 
     if (!x || !grad || !dx || ((mode == 3 || mode == 5) && !y)) return fail(AGX_ERR_NULL_POINTER, "reduce_mean_backward: NULL pointer");
     const int nb = int(ceil_div64(n, 2048) < 8192 ? ceil_div64(n, 2048) : 8192);
     hipLaunchKernelGGL(reduce_mean_bwd_kernel<0>, dim3(nb), dim3(256), 0, static_cast<hipStream_t>(stream), x, y, n, mode,
-                       aligned16(x, y, dx, dy), grad, float(1.0 / double(n)), dx, dy);
+                       int(all_aligned16({x, y, dx, dy})), grad, float(1.0 / double(n)), dx, dy);
     return check_launch("agx_reduce_mean_backward");
 }
 
@@ -345,7 +333,7 @@ int agx_feature_means(const float *x, const float *y, int64_t n, float *out, flo
     if (!x || !y || !out || !workspace) return fail(AGX_ERR_NULL_POINTER, "feature_means: NULL pointer");
     hipStream_t st = static_cast<hipStream_t>(stream);
     const int nb = int(ceil_div64(n, 4096) < 1024 ? ceil_div64(n, 4096) : 1024);
-    hipLaunchKernelGGL(reduce_partial_kernel<1>, dim3(nb), dim3(256), 0, st, x, y, n, 3, aligned16(x, y, nullptr, nullptr), workspace);
+    hipLaunchKernelGGL(reduce_partial_kernel<1>, dim3(nb), dim3(256), 0, st, x, y, n, 3, int(all_aligned16({x, y})), workspace);
     hipLaunchKernelGGL(reduce_final_kernel, dim3(2), dim3(256), 0, st, workspace, nb, 1.0 / double(n), out);
     return check_launch("agx_feature_means");
 }
@@ -357,7 +345,7 @@ int agx_feature_means_backward(const float *x, const float *y, int64_t n, const 
     if (!x || !y || !grad || (!dx && !dy)) return fail(AGX_ERR_NULL_POINTER, "feature_means_backward: NULL pointer");
     const int nb = int(ceil_div64(n, 2048) < 8192 ? ceil_div64(n, 2048) : 8192);
     hipLaunchKernelGGL(reduce_mean_bwd_kernel<1>, dim3(nb), dim3(256), 0, static_cast<hipStream_t>(stream), x, y, n, 3,
-                       aligned16(x, y, dx, dy), grad, float(1.0 / double(n)), dx, dy);
+                       int(all_aligned16({x, y, dx, dy})), grad, float(1.0 / double(n)), dx, dy);
     return check_launch("agx_feature_means_backward");
 }
 

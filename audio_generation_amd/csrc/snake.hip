@@ -9,25 +9,11 @@
 //
 // The sine is OCML's sincosf: one range reduction per element, sin^2 = s * s and sin 2 theta = 2 * (s * c) from its two
 // results.  Its large-argument path has no data-dependent loop, so Inf and NaN cost what a large finite argument costs.
-#include "common.hpp"
+#include "rowwise.hpp"
 
 namespace {
 
-using agx::ceil_div64;
-using agx::check_launch;
-using agx::fail;
-
-constexpr int kWave = 64;
-constexpr int kSeg = 1024;          // floats of a row one wavefront of the element-wise walk takes: 4 rounds of 64 lanes x 16 bytes
-constexpr int kRedSeg = 2048;       // floats of a row one workgroup of the reducing backward takes: 8 per thread
-constexpr int64_t kMaxGrid = 2147483647;
-
-// Sum over the 64 lanes; lane 0 holds the halving tree ((p0 + p32) + (p16 + p48)) + ... of the lanes' values.
-__device__ inline float wave_sum(float v) {
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o, kWave);
-    return v;
-}
+using namespace agx;
 
 struct Row {
     float a, inv, ainv;     // alpha, 1 / (alpha + eps), alpha * inv
@@ -61,9 +47,8 @@ __device__ inline float snake_bwd_one(float x, const Row &r, float &term) {
     return fmaf(r.ainv, sin2, (r.relu && !(x >= 0.f)) ? 0.f : 1.f);
 }
 
-// The walk of film_apply_kernel<CT>: one wavefront takes kSeg floats of a row, scalar up to the first 16-byte boundary, float4
-// to the last whole quadruple, scalar tail.  BWD == false: out = snake(x).  BWD == true: out = dx, d = dout (frozen alphas).
-// out may alias x (forward) or d (backward): an element is read by the lane that writes it, before it writes.
+// The row walk (rowwise.hpp).  BWD == false: out = snake(x).  BWD == true: out = dx, d = dout (frozen alphas).  out may alias x
+// (forward) or d (backward).
 template <bool BWD>
 __global__ __launch_bounds__(256) void snake_walk_kernel(const float *x, const float *d, const float *__restrict__ alpha, float *out,
                                                          int channels, int64_t len, int64_t segs, int64_t items, int variant,
@@ -76,30 +61,15 @@ __global__ __launch_bounds__(256) void snake_walk_kernel(const float *x, const f
     const Row r = row_of(alpha, row, channels, variant, eps);
     const float *xs = x + row * len + s0, *ds = BWD ? d + row * len + s0 : nullptr;
     float *os = out + row * len + s0;
-    int head = vec ? int((4 - ((reinterpret_cast<uintptr_t>(xs) >> 2) & 3)) & 3) : n;
-    head = head < n ? head : n;
-    const int nvec = (n - head) / 4, tail0 = head + 4 * nvec;
     float unused;
-    auto one = [&](float xv, float dv) { return BWD ? dv * snake_bwd_one<false>(xv, r, unused) : snake_fwd_one(xv, r); };
-    for (int i = lane; i < head; i += kWave) os[i] = one(xs[i], BWD ? ds[i] : 0.f);      // all of it where vec == 0
-#pragma unroll 2
-    for (int q = lane; q < nvec; q += kWave) {
-        float4 v = *reinterpret_cast<const float4 *>(xs + head + 4 * q);
-        float4 g = make_float4(0.f, 0.f, 0.f, 0.f);
-        if (BWD) g = *reinterpret_cast<const float4 *>(ds + head + 4 * q);
-        v.x = one(v.x, g.x);
-        v.y = one(v.y, g.y);
-        v.z = one(v.z, g.z);
-        v.w = one(v.w, g.w);
-        *reinterpret_cast<float4 *>(os + head + 4 * q) = v;
-    }
-    if (tail0 + lane < n) os[tail0 + lane] = one(xs[tail0 + lane], BWD ? ds[tail0 + lane] : 0.f);
+    row_walk<2, BWD>(row_split(xs, n, vec), xs, ds, os, n, lane,
+                     [&](float xv, float dv) { return BWD ? dv * snake_bwd_one<false>(xv, r, unused) : snake_fwd_one(xv, r); });
 }
 
 // Stage 1 of dalpha, with dx in the same pass: one workgroup per (row, segment of kRedSeg floats).  Walker j of 256 takes the
-// segment's elements j, j + 256, ... in increasing order (fma of dout and the element's term); the walkers of a group of 64 are
-// added in the halving tree of wave_sum, the groups as (g0 + g1) + (g2 + g3).  The walk is by index, never by address: the
-// order does not depend on how the operands are aligned.  dx may be NULL, or alias dout.
+// segment's elements j, j + 256, ... in increasing order (fma of dout and the element's term); the walkers are added in the
+// workgroup order (rowwise.hpp).  The walk is by index, never by address: the order does not depend on how the operands are
+// aligned.  dx may be NULL, or alias dout.
 __global__ __launch_bounds__(256) void snake_bwd_reduce_kernel(const float *__restrict__ x, const float *__restrict__ alpha,
                                                                const float *dout, float *dx, float *__restrict__ partial,
                                                                int channels, int64_t len, int64_t segs, int variant, float eps) {
@@ -121,20 +91,14 @@ __global__ __launch_bounds__(256) void snake_bwd_reduce_kernel(const float *__re
     acc = wave_sum(acc);
     if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = acc;
     __syncthreads();
-    if (threadIdx.x == 0) partial[blockIdx.x] = (red[0] + red[1]) + (red[2] + red[3]);
+    if (threadIdx.x == 0) partial[blockIdx.x] = groups_sum(red);
 }
 
-// Stage 2: one wavefront per channel.  The channel's partials are numbered p = b * segs + seg over its rows b * channels + c;
-// lane l adds p = l, l + 64, ... in increasing order, then the halving tree.
+// Stage 2: one wavefront per channel, the channel finish order (rowwise.hpp) over its rows b * channels + c.
 __global__ __launch_bounds__(64) void snake_bwd_finish_kernel(const float *__restrict__ partial, float *__restrict__ dalpha,
                                                               int channels, int64_t segs, int64_t count) {
     const int c = blockIdx.x;
-    float acc = 0.f;
-    for (int64_t p = threadIdx.x; p < count; p += kWave) {
-        const int64_t b = p / segs;
-        acc += partial[(b * channels + c) * segs + (p - b * segs)];
-    }
-    acc = wave_sum(acc);
+    const float acc = channel_sum(partial, c, channels, segs, 1, 0, count);
     if (threadIdx.x == 0) dalpha[c] = acc;
 }
 
@@ -151,20 +115,6 @@ inline int snake_shape(const char *op, int64_t rows, int32_t channels, int64_t n
     return AGX_OK;
 }
 
-// Workgroups of the element-wise walk, or -1 beyond the grid.
-inline int64_t walk_blocks(int64_t rows, int64_t n, int64_t &segs, int64_t &items) {
-    segs = ceil_div64(n, kSeg);
-    if (segs > kMaxGrid * 4 / rows) return -1;
-    items = rows * segs;
-    return ceil_div64(items, 4);
-}
-
-// Workgroups of the reducing backward = floats of its workspace, or -1 beyond the grid.
-inline int64_t reduce_blocks(int64_t rows, int64_t n, int64_t &segs) {
-    segs = ceil_div64(n, kRedSeg);
-    return segs > kMaxGrid / rows ? -1 : rows * segs;
-}
-
 }  // namespace
 
 int agx_snake_forward(const float *x, const float *alpha, float *out, int64_t rows, int32_t channels, int64_t n, int32_t variant,
@@ -175,7 +125,7 @@ int agx_snake_forward(const float *x, const float *alpha, float *out, int64_t ro
     int64_t segs, items;
     const int64_t blocks = walk_blocks(rows, n, segs, items);
     if (blocks < 0) return fail(AGX_ERR_BAD_SHAPE, "snake_forward: (%lld, %lld) exceeds the grid", (long long)rows, (long long)n);
-    const int vec = ((reinterpret_cast<uintptr_t>(x) ^ reinterpret_cast<uintptr_t>(out)) & 15) == 0;
+    const int vec = same_phase16({x, out});
     hipLaunchKernelGGL(snake_walk_kernel<false>, dim3(unsigned(blocks)), dim3(256), 0, static_cast<hipStream_t>(stream), x,
                        static_cast<const float *>(nullptr), alpha, out, channels, n, segs, items, variant, eps, vec);
     return check_launch("agx_snake_forward");
@@ -200,8 +150,7 @@ int agx_snake_backward(const float *x, const float *alpha, const float *dout, fl
         int64_t segs, items;
         const int64_t blocks = walk_blocks(rows, n, segs, items);
         if (blocks < 0) return fail(AGX_ERR_BAD_SHAPE, "snake_backward: (%lld, %lld) exceeds the grid", (long long)rows, (long long)n);
-        const uintptr_t px = reinterpret_cast<uintptr_t>(x), pd = reinterpret_cast<uintptr_t>(dout), po = reinterpret_cast<uintptr_t>(dx);
-        const int vec = (((px ^ pd) | (px ^ po)) & 15) == 0;
+        const int vec = same_phase16({x, dout, dx});
         hipLaunchKernelGGL(snake_walk_kernel<true>, dim3(unsigned(blocks)), dim3(256), 0, st, x, dout, alpha, dx, channels, n, segs,
                            items, variant, eps, vec);
         return check_launch("agx_snake_backward");

@@ -2,6 +2,7 @@
 // Both are per-channel (depthwise) and pure bandwidth: one read of the input,
 // one write of the output, everything else stays in LDS / registers.
 #include "mfma_tile.hpp"
+#include "rowwise.hpp"
 #include "wavelet_fold.hpp"
 
 namespace agx {
@@ -102,6 +103,8 @@ __global__ __launch_bounds__(256) void multires_kernel(const float *__restrict__
 // deterministic, no atomics.
 constexpr int MRB_TT = 512;
 
+// The wave order of wave_sum (rowwise.hpp) into the slot's four floats, written out (a call reschedules the store); groups_sum
+// adds them behind the kernel's barrier.
 __device__ __forceinline__ float mrb_block_sum(float v, float *red, int slot) {
     for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
     if ((threadIdx.x & 63) == 0) red[4 * slot + (threadIdx.x >> 6)] = v;
@@ -228,8 +231,7 @@ __global__ __launch_bounds__(256) void multires_bwd_kernel(const float *__restri
     }
     __syncthreads();
     if (tid < NP) {
-        const float *r = red + 4 * tid;
-        part[size_t(blockIdx.x) * NP + tid] = (r[0] + r[1]) + (r[2] + r[3]);      // (row, tile) order, as before
+        part[size_t(blockIdx.x) * NP + tid] = groups_sum(red + 4 * tid);      // (row, tile) order, as before
     }
 }
 
@@ -366,7 +368,7 @@ __global__ __launch_bounds__(256) void wavelet_fold_bwd_kernel(const float *__re
     for (int off = 32; off > 0; off >>= 1) dsig += __shfl_xor(dsig, off);
     if ((tid & 63) == 0) red[tid >> 6] = dsig;
     __syncthreads();
-    if (tid == 0) dsig_part[blockIdx.x] = (red[0] + red[1]) + (red[2] + red[3]);
+    if (tid == 0) dsig_part[blockIdx.x] = groups_sum(red);
 }
 
 // dsigma[c] = sum_b part[b*C + c]   (or the sum over everything when sigma is shared)

@@ -1951,6 +1951,19 @@ def _same_out(op: str, x: Tensor, out: Optional[Tensor]) -> Tensor:
     return out
 
 
+def _elementwise(op: str, lib, symbol: str, x: Tensor, out: Optional[Tensor], traffic: Optional[int], args) -> Tensor:
+    """What every elementwise wrapper ends in: ``x`` must be contiguous float32, ``out`` is checked against it (or made), and
+    ``symbol(*args(out), stream)`` runs -- under the observer, as ``traffic`` bytes per element, unless ``traffic`` is None."""
+    if x.dtype != torch.float32 or not x.is_contiguous():
+        raise AgxError(f"{op}: x must be a contiguous float32 tensor")
+    out = _same_out(op, x, out)
+    tok = _observer.begin("other", (op, traffic * x.numel())) if traffic is not None and _observer is not None else None
+    _lib.check(getattr(lib, symbol)(*args(out), _stream()), symbol)
+    if tok is not None:
+        _observer.end(tok)
+    return out
+
+
 def film_params(cond: Tensor, w: Tensor, bias: Optional[Tensor]) -> Tensor:
     """``gb[b, r] = bias[r] + sum_d cond[b, d] w[r, d]``: cond (B, D), w (R, D), bias (R) or None -> (B, R)."""
     lib = _lib.load()
@@ -1975,15 +1988,8 @@ def film_apply(x: Tensor, gb: Tensor, has_beta: bool, layout: int = FILM_CT, out
     lib = _lib.load()
     _need_gpu(x, gb, out)
     b, c, t = _film_shape("film_apply", x, gb, has_beta, layout)
-    if x.dtype != torch.float32 or not x.is_contiguous():
-        raise AgxError("film_apply: x must be a contiguous float32 tensor")
-    out = _same_out("film_apply", x, out)
-    tok = _observer.begin("other", ("film_apply", 8 * x.numel())) if _observer is not None else None
-    _lib.check(lib.agx_film_apply(_ptr(x), _ptr(_f32c(gb)), _ptr(out), b, c, t, int(bool(has_beta)), int(layout), _stream()),
-               "agx_film_apply")
-    if tok is not None:
-        _observer.end(tok)
-    return out
+    return _elementwise("film_apply", lib, "agx_film_apply", x, out, 8,
+                        lambda out: (_ptr(x), _ptr(_f32c(gb)), _ptr(out), b, c, t, int(bool(has_beta)), int(layout)))
 
 
 def film_backward(x: Tensor, gb: Tensor, dout: Tensor, has_beta: bool, layout: int = FILM_CT):
@@ -2025,12 +2031,7 @@ def sigmoid_gate(x: Tensor, z: Tensor, out: Optional[Tensor] = None) -> Tensor:
     _need_gpu(x, z, out)
     if x.dtype != torch.float32 or not x.is_contiguous() or z.shape != x.shape:
         raise AgxError(f"sigmoid_gate: x must be a contiguous float32 tensor and z of its shape (x {tuple(x.shape)}, z {tuple(z.shape)})")
-    out = _same_out("sigmoid_gate", x, out)
-    tok = _observer.begin("other", ("sigmoid_gate", 12 * x.numel())) if _observer is not None else None
-    _lib.check(lib.agx_sigmoid_gate(_ptr(x), _ptr(_f32c(z)), _ptr(out), x.numel(), _stream()), "agx_sigmoid_gate")
-    if tok is not None:
-        _observer.end(tok)
-    return out
+    return _elementwise("sigmoid_gate", lib, "agx_sigmoid_gate", x, out, 12, lambda out: (_ptr(x), _ptr(_f32c(z)), _ptr(out), x.numel()))
 
 
 def sigmoid_gate_backward(x: Tensor, z: Tensor, dout: Tensor):
@@ -2071,13 +2072,8 @@ def snake_forward(x: Tensor, alpha: Tensor, variant: int, eps: float = 1e-6, out
     lib = _lib.load()
     _need_gpu(x, alpha, out)
     rows, channels, n = _snake_shape("snake_forward", x, alpha, variant)
-    out = _same_out("snake_forward", x, out)
-    tok = _observer.begin("other", ("snake_forward", 8 * x.numel())) if _observer is not None else None
-    _lib.check(lib.agx_snake_forward(_ptr(x), _ptr(_f32c(alpha)), _ptr(out), rows, channels, n, int(variant), float(eps), _stream()),
-               "agx_snake_forward")
-    if tok is not None:
-        _observer.end(tok)
-    return out
+    return _elementwise("snake_forward", lib, "agx_snake_forward", x, out, 8,
+                        lambda out: (_ptr(x), _ptr(_f32c(alpha)), _ptr(out), rows, channels, n, int(variant), float(eps)))
 
 
 def snake_backward(x: Tensor, alpha: Tensor, dout: Tensor, variant: int, eps: float = 1e-6, want_dx: bool = True,
@@ -2140,91 +2136,76 @@ def _bct(op: str, *tensors: Tensor):
     return x.shape
 
 
-def glu_dwconv(u: Tensor, w: Tensor, bias: Tensor, bn: Optional[tuple] = None, eps: float = 1e-5) -> Tensor:
-    """``z = bias + depthwise_same_conv(u[:, :C] * sigmoid(u[:, C:]), w)``: u (B, 2 C, T) -> (B, C, T), one launch, the GLU
-    output never written.  ``bn`` = (gamma, beta, running_mean, running_var): the eval-mode module -- the normalisation on the
-    given statistics and SiLU applied in the same launch, ``y`` returned and ``z`` not written."""
-    lib = _lib.load()
-    _need_gpu(u, w, bias, *(bn or ()))
-    b, c, t, k = _glu_shape("glu_dwconv", u, w)
-    w, (bias,) = _f32c(w), _bn_vectors("glu_dwconv", c, bias)
-    bn = (None,) * 4 if bn is None else _bn_vectors("glu_dwconv", c, *bn)
-    out = torch.empty((b, c, t), dtype=torch.float32, device=u.device)
-    tok = _observer.begin("other", ("glu_dwconv", 12 * out.numel())) if _observer is not None else None
-    _lib.check(lib.agx_glu_dwconv_forward(_ptr(u), _ptr(w), _ptr(bias), *(_ptr(v) for v in bn), float(eps), _ptr(out), b, c, t, k,
-                                          _stream()), "agx_glu_dwconv_forward")
-    if tok is not None:
-        _observer.end(tok)
-    return out
-
-
-def glu_dwconv_backward(dz: Tensor, u: Tensor, w: Tensor, want_du: bool = True, want_params: bool = True):
-    """(du (B, 2 C, T) or None, dw of w's shape or None, dbias (C) or None) of ``glu_dwconv`` without ``bn``."""
-    lib = _lib.load()
-    _need_gpu(dz, u, w)
-    b, c, t, k = _glu_shape("glu_dwconv_backward", u, w)
-    if tuple(dz.shape) != (b, c, t):
-        raise AgxError(f"glu_dwconv_backward: dz is {tuple(dz.shape)}, expected {(b, c, t)}")
-    dz, w = _f32c(dz), _f32c(w)
-    du = torch.empty_like(u) if want_du else None
-    dw = dbias = ws = None
-    nbytes = 0
-    if want_params:
-        dw, dbias = torch.empty_like(w), torch.empty(c, dtype=torch.float32, device=u.device)
-        nbytes = int(lib.agx_glu_dwconv_backward_workspace_bytes(b, c, t, k))
-        ws = _workspace(nbytes, u.device, "agx_glu_dwconv_backward_workspace_bytes")
-    _lib.check(lib.agx_glu_dwconv_backward(_ptr(dz), _ptr(u), _ptr(w), _ptr(du), _ptr(dw), _ptr(dbias), _ptr(ws), nbytes, b, c, t, k,
-                                           _stream()), "agx_glu_dwconv_backward")
-    return du, dw, dbias
-
-
-CONFORMER_MAX_STEP = _lib.CONFORMER_MAX_STEP
-
-
 def _glu_hist(op: str, hist: Optional[Tensor], b: int, c: int, k: int) -> None:
     """A conv state is a contiguous float32 (B, C, K - 1) tensor: it is written in place, so it is never copied."""
     if hist is not None and (tuple(hist.shape) != (b, c, k - 1) or hist.dtype != torch.float32 or not hist.is_contiguous()):
         raise AgxError(f"{op}: hist must be a contiguous float32 {(b, c, k - 1)} tensor (B, C, K - 1), got {tuple(hist.shape)} {hist.dtype}")
 
 
-def glu_dwconv_causal(u: Tensor, w: Tensor, bias: Tensor, bn: Optional[tuple] = None, eps: float = 1e-5,
-                      hist: Optional[Tensor] = None) -> Tensor:
-    """``glu_dwconv`` with the causal conv: an output sees its own frame and the K - 1 before it.  ``hist`` (B, C, K - 1), oldest
-    frame first: the post-GLU values of the K - 1 frames before ``u`` (None: zeros, the start of a sequence); read, not written."""
+def _glu_dwconv_forward(op: str, symbol: str, u: Tensor, w: Tensor, bias: Tensor, bn: Optional[tuple], eps: float, hist: tuple) -> Tensor:
+    """``glu_dwconv`` (``hist`` = ()) and ``glu_dwconv_causal`` (``hist`` = (the state or None,), an operand of its symbol)."""
     lib = _lib.load()
-    _need_gpu(u, w, bias, hist, *(bn or ()))
-    b, c, t, k = _glu_shape("glu_dwconv_causal", u, w)
-    w, (bias,) = _f32c(w), _bn_vectors("glu_dwconv_causal", c, bias)
-    bn = (None,) * 4 if bn is None else _bn_vectors("glu_dwconv_causal", c, *bn)
-    _glu_hist("glu_dwconv_causal", hist, b, c, k)
+    _need_gpu(u, w, bias, *hist, *(bn or ()))
+    b, c, t, k = _glu_shape(op, u, w)
+    w, (bias,) = _f32c(w), _bn_vectors(op, c, bias)
+    bn = (None,) * 4 if bn is None else _bn_vectors(op, c, *bn)
+    for h in hist:
+        _glu_hist(op, h, b, c, k)
     out = torch.empty((b, c, t), dtype=torch.float32, device=u.device)
-    tok = _observer.begin("other", ("glu_dwconv_causal", 12 * out.numel())) if _observer is not None else None
-    _lib.check(lib.agx_glu_dwconv_causal_forward(_ptr(u), _ptr(w), _ptr(bias), *(_ptr(v) for v in bn), float(eps), _ptr(hist), _ptr(out),
-                                                 b, c, t, k, _stream()), "agx_glu_dwconv_causal_forward")
+    tok = _observer.begin("other", (op, 12 * out.numel())) if _observer is not None else None
+    _lib.check(getattr(lib, symbol)(_ptr(u), _ptr(w), _ptr(bias), *(_ptr(v) for v in bn), float(eps), *(_ptr(h) for h in hist), _ptr(out),
+                                    b, c, t, k, _stream()), symbol)
     if tok is not None:
         _observer.end(tok)
     return out
 
 
-def glu_dwconv_causal_backward(dz: Tensor, u: Tensor, w: Tensor, want_du: bool = True, want_params: bool = True):
-    """(du (B, 2 C, T) or None, dw of w's shape or None, dbias (C) or None) of ``glu_dwconv_causal`` without ``bn`` and without
-    ``hist``: there is no backward through a cached call."""
+def _glu_dwconv_backward(op: str, symbol: str, dz: Tensor, u: Tensor, w: Tensor, want_du: bool, want_params: bool):
+    """``glu_dwconv_backward`` and ``glu_dwconv_causal_backward``: ``symbol`` and its ``_workspace_bytes`` query."""
     lib = _lib.load()
     _need_gpu(dz, u, w)
-    b, c, t, k = _glu_shape("glu_dwconv_causal_backward", u, w)
+    b, c, t, k = _glu_shape(op, u, w)
     if tuple(dz.shape) != (b, c, t):
-        raise AgxError(f"glu_dwconv_causal_backward: dz is {tuple(dz.shape)}, expected {(b, c, t)}")
+        raise AgxError(f"{op}: dz is {tuple(dz.shape)}, expected {(b, c, t)}")
     dz, w = _f32c(dz), _f32c(w)
     du = torch.empty_like(u) if want_du else None
     dw = dbias = ws = None
     nbytes = 0
     if want_params:
         dw, dbias = torch.empty_like(w), torch.empty(c, dtype=torch.float32, device=u.device)
-        nbytes = int(lib.agx_glu_dwconv_causal_backward_workspace_bytes(b, c, t, k))
-        ws = _workspace(nbytes, u.device, "agx_glu_dwconv_causal_backward_workspace_bytes")
-    _lib.check(lib.agx_glu_dwconv_causal_backward(_ptr(dz), _ptr(u), _ptr(w), _ptr(du), _ptr(dw), _ptr(dbias), _ptr(ws), nbytes, b, c, t,
-                                                  k, _stream()), "agx_glu_dwconv_causal_backward")
+        nbytes = int(getattr(lib, symbol + "_workspace_bytes")(b, c, t, k))
+        ws = _workspace(nbytes, u.device, symbol + "_workspace_bytes")
+    _lib.check(getattr(lib, symbol)(_ptr(dz), _ptr(u), _ptr(w), _ptr(du), _ptr(dw), _ptr(dbias), _ptr(ws), nbytes, b, c, t, k, _stream()),
+               symbol)
     return du, dw, dbias
+
+
+def glu_dwconv(u: Tensor, w: Tensor, bias: Tensor, bn: Optional[tuple] = None, eps: float = 1e-5) -> Tensor:
+    """``z = bias + depthwise_same_conv(u[:, :C] * sigmoid(u[:, C:]), w)``: u (B, 2 C, T) -> (B, C, T), one launch, the GLU
+    output never written.  ``bn`` = (gamma, beta, running_mean, running_var): the eval-mode module -- the normalisation on the
+    given statistics and SiLU applied in the same launch, ``y`` returned and ``z`` not written."""
+    return _glu_dwconv_forward("glu_dwconv", "agx_glu_dwconv_forward", u, w, bias, bn, eps, ())
+
+
+def glu_dwconv_backward(dz: Tensor, u: Tensor, w: Tensor, want_du: bool = True, want_params: bool = True):
+    """(du (B, 2 C, T) or None, dw of w's shape or None, dbias (C) or None) of ``glu_dwconv`` without ``bn``."""
+    return _glu_dwconv_backward("glu_dwconv_backward", "agx_glu_dwconv_backward", dz, u, w, want_du, want_params)
+
+
+CONFORMER_MAX_STEP = _lib.CONFORMER_MAX_STEP
+
+
+def glu_dwconv_causal(u: Tensor, w: Tensor, bias: Tensor, bn: Optional[tuple] = None, eps: float = 1e-5,
+                      hist: Optional[Tensor] = None) -> Tensor:
+    """``glu_dwconv`` with the causal conv: an output sees its own frame and the K - 1 before it.  ``hist`` (B, C, K - 1), oldest
+    frame first: the post-GLU values of the K - 1 frames before ``u`` (None: zeros, the start of a sequence); read, not written."""
+    return _glu_dwconv_forward("glu_dwconv_causal", "agx_glu_dwconv_causal_forward", u, w, bias, bn, eps, (hist,))
+
+
+def glu_dwconv_causal_backward(dz: Tensor, u: Tensor, w: Tensor, want_du: bool = True, want_params: bool = True):
+    """(du (B, 2 C, T) or None, dw of w's shape or None, dbias (C) or None) of ``glu_dwconv_causal`` without ``bn`` and without
+    ``hist``: there is no backward through a cached call."""
+    return _glu_dwconv_backward("glu_dwconv_causal_backward", "agx_glu_dwconv_causal_backward", dz, u, w, want_du, want_params)
 
 
 def glu_dwconv_step(u: Tensor, w: Tensor, bias: Tensor, bn: tuple, hist: Optional[Tensor], eps: float = 1e-5,
@@ -2308,13 +2289,8 @@ def bn_silu(z: Tensor, gamma: Tensor, beta: Tensor, mean: Tensor, var: Tensor, e
     _need_gpu(z, gamma, beta, mean, var, out)
     b, c, t = _bct("bn_silu", z)
     gamma, beta, mean, var = _bn_vectors("bn_silu", c, gamma, beta, mean, var)
-    out = _same_out("bn_silu", z, out)
-    tok = _observer.begin("other", ("bn_silu", 8 * z.numel())) if _observer is not None else None
-    _lib.check(lib.agx_bn_silu_forward(_ptr(z), _ptr(gamma), _ptr(beta), _ptr(mean), _ptr(var), float(eps), int(bool(training)),
-                                       _ptr(out), b, c, t, _stream()), "agx_bn_silu_forward")
-    if tok is not None:
-        _observer.end(tok)
-    return out
+    return _elementwise("bn_silu", lib, "agx_bn_silu_forward", z, out, 8,
+                        lambda out: (_ptr(z), _ptr(gamma), _ptr(beta), _ptr(mean), _ptr(var), float(eps), int(bool(training)), _ptr(out), b, c, t))
 
 
 def bn_silu_backward(dy: Tensor, z: Tensor, gamma: Tensor, beta: Tensor, mean: Tensor, var: Tensor, eps: float = 1e-5,
@@ -2342,14 +2318,7 @@ def silu(x: Tensor, out: Optional[Tensor] = None) -> Tensor:
     """``x * sigmoid(x)`` elementwise; ``out`` may be ``x`` (in place)."""
     lib = _lib.load()
     _need_gpu(x, out)
-    if x.dtype != torch.float32 or not x.is_contiguous():
-        raise AgxError("silu: x must be a contiguous float32 tensor")
-    out = _same_out("silu", x, out)
-    tok = _observer.begin("other", ("silu", 8 * x.numel())) if _observer is not None else None
-    _lib.check(lib.agx_silu(_ptr(x), _ptr(out), x.numel(), _stream()), "agx_silu")
-    if tok is not None:
-        _observer.end(tok)
-    return out
+    return _elementwise("silu", lib, "agx_silu", x, out, 8, lambda out: (_ptr(x), _ptr(out), x.numel()))
 
 
 def silu_backward(x: Tensor, dout: Tensor, out: Optional[Tensor] = None) -> Tensor:
@@ -2358,9 +2327,7 @@ def silu_backward(x: Tensor, dout: Tensor, out: Optional[Tensor] = None) -> Tens
     _need_gpu(x, dout, out)
     if x.dtype != torch.float32 or not x.is_contiguous() or dout.shape != x.shape or dout.dtype != torch.float32 or not dout.is_contiguous():
         raise AgxError(f"silu_backward: x and dout must be contiguous float32 tensors of one shape (x {tuple(x.shape)}, dout {tuple(dout.shape)})")
-    out = _same_out("silu_backward", x, out)
-    _lib.check(lib.agx_silu_backward(_ptr(x), _ptr(dout), _ptr(out), x.numel(), _stream()), "agx_silu_backward")
-    return out
+    return _elementwise("silu_backward", lib, "agx_silu_backward", x, out, None, lambda out: (_ptr(x), _ptr(dout), _ptr(out), x.numel()))
 
 
 # ------------------------------------------------------------------ streaming conv stacks (include/agx.h "Streaming conv stacks")
